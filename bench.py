@@ -16,18 +16,25 @@ process (before torch or the GPU is touched) and relays its output; launched by 
 a pool per device behind `starkhip_multipool_*` (no process group, no collective), N x steps proofs placed by the library; it prints
 the same JSON line (`config.parallelism` says which form ran).
 
+A plain run (`--steps N --warmup W`) sets up, warms up, times the N steps, writes the last step's proof if `--dump-outputs DIR` is
+given, and prints the line.  Everything else -- the checks of the timed proofs against the proofs the warm-up made one at a time and
+against the oracle's digest, the one-in-flight pass (`kernels`, latency), the untimed hand-over legs and the CPU baseline -- runs only
+with `--full` (where `--no-solo`, `--no-boundary` and `--no-cpu-baseline` switch parts of it off).
+
 Prints ONE JSON line on rank 0.  What is measured where (DESIGN.md section 6 has every field):
 
   value / ms_per_step     the timed region: operands -> proof bytes, `--inflight` contexts per GPU
   roofline                the kernel with the most device time INSIDE the timed region (with five or more in flight:
                           leaf_hash_lane_kernel in groups), HIP events on the stream it is launched on, taken in the timed region
-  kernels                 rank 0, untimed, ONE proof in flight: uncontended HIP-event durations of the three heavy kernels (the
+  kernels                 --full, rank 0, untimed, ONE proof in flight: uncontended HIP-event durations of the three heavy kernels (the
                           figures the committed rocprof summaries under profiles/ must agree with); PMC traffic per launch from
                           profiles/pmc_traffic_latest.json
-  value_host_rows         rank 0, untimed leg on the SAME pool: page-locked host ROWS -> H2D -> transpose -> proof -> D2H
+  value_host_rows         --full, rank 0, untimed leg on the SAME pool: page-locked host ROWS -> H2D -> transpose -> proof -> D2H
                           (BASELINE.md section 4's literal hand-over); value_compact: a recorded trace; value_device_resident: the
                           column-major trace already in HBM (rounds 1-3's headline)
-  cpu_baseline            rank 0 at N = 1: the CPU oracle on a bounded sample of the same workload, measured in this run
+  cpu_baseline            --full, rank 0 at N = 1: the CPU oracle on a bounded sample of the same workload, measured in this run
+  timed_proofs_verified   --full: the last proof of every input made in the timed region is accepted by the verifier and equals the
+                          proof of the same input made alone; oracle_digest_match: input 0x5eed0001 against the CPU oracle's digest
   value_steady_state      proofs/s over the middle of the timed region only: completions after the first and before the last `inflight`
                           per pool (the pool's start and tail dropped); null when the run is shorter than three waves
   host                    what the host side had: CPUs granted, the pool's CPU budget and threads, process CPU-seconds per proof in the
@@ -212,14 +219,43 @@ def thread_cpu_by_name():
     return out
 
 
+DUMP_WORDS = 1 << 21  # proof words written by --dump-outputs at most (2 x 8 bytes each, plus the index): 48 MB
+
+
+def dump_outputs(out_dir, proof):
+    """--dump-outputs: the proof blob the last timed step returned (u64 words), exactly, as float64.  proof_words.npy holds
+    [low 32 bits, high 32 bits] per word at the word offsets in proof_index.npy: every word, or, for a proof of more than DUMP_WORDS
+    words, the same seeded sample of offsets in every run of the same length; proof_sha256.npy (32 bytes as float32) covers the whole blob."""
+    import hashlib
+    import numpy as np
+    words = np.ascontiguousarray(proof, dtype=np.uint64)
+    idx = np.arange(words.size, dtype=np.int64)
+    if words.size > DUMP_WORDS:
+        idx = np.sort(np.random.default_rng(0).choice(words.size, size=DUMP_WORDS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    picked = words[idx]
+    halves = np.stack([picked & np.uint64(0xFFFFFFFF), picked >> np.uint64(32)], axis=1)
+    np.save(os.path.join(out_dir, "proof_words.npy"), halves.astype(np.float64))
+    np.save(os.path.join(out_dir, "proof_index.npy"), idx.astype(np.float64))
+    digest = np.frombuffer(hashlib.sha256(words.tobytes()).digest(), dtype=np.uint8)
+    np.save(os.path.join(out_dir, "proof_sha256.npy"), digest.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=48)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-boundary", action="store_true", help="skip the untimed legs (host rows, recorded trace, device-resident trace)")
-    ap.add_argument("--no-solo", action="store_true", help="skip the untimed one-proof-in-flight pass (`kernels`, latency); for profiling runs")
+    ap.add_argument("--steps", type=int, default=48, help="timed steps per device; a step is one proof")
+    ap.add_argument("--warmup", type=int, default=1,
+                    help="untimed warm-up proofs per device before the timed steps, submitted in whole waves of the pool's contexts "
+                         "(at least one wave, so that every context has proven), after one proof of every input with nothing else in flight")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the checks of the timed proofs against the proofs the warm-up made one at "
+                         "a time and against the oracle's digest, the one-proof-in-flight pass, the untimed hand-over legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the proof of the last timed step to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-boundary", action="store_true", help="with --full: skip the untimed legs (host rows, recorded trace, device-resident trace)")
+    ap.add_argument("--no-solo", action="store_true", help="with --full: skip the untimed one-proof-in-flight pass (`kernels`, latency); for profiling runs")
     ap.add_argument("--input", choices=("witness", "device"), default="witness",
                     help="what the TIMED region starts from: witness = the driver's operand on the host (generate_trace, upload and read-back inside; "
                          "the reference's boundary, the default); device = a column-major trace already in HBM (rounds 1-3's headline, for A/B runs)")
@@ -296,17 +332,22 @@ def main():
     n_inputs = inflight * n_pools
     seeds = [0x5EED0000 + 1 + rank * n_inputs + i for i in range(n_inputs)]
     inputs = [synthetic_final_exp_input(s) for s in seeds]
-    helper = S.Prover(local_rank)  # page-locked staging for the host-rows leg / device traces
+    helper = None  # page-locked staging for the host-rows leg / device traces, made when one of them needs it
     host_rows = None
     device_work = []
 
+    def staging_rows():
+        nonlocal helper, host_rows
+        if host_rows is None:
+            helper = S.Prover(local_rank)
+            host_rows = helper.host_array((n, C))  # page-locked, reused for every generated trace
+        return host_rows
+
     def make_device_traces():
         # traces generated on the host, moved to HBM as column-major u64 (as int64 bit patterns)
-        nonlocal host_rows
         if device_work:
             return
-        if host_rows is None:
-            host_rows = helper.host_array((n, C))  # page-locked, reused for every generated trace
+        staging_rows()
         for i in range(inflight):
             _, pis = S.trace_final_exp(inputs[i], out=host_rows)
             d_rows = torch.from_numpy(host_rows.view(np.int64)).to(f"cuda:{local_rank}")
@@ -324,14 +365,16 @@ def main():
             return pool.submit_device(air, cfg, d_cols.data_ptr(), n, pis, layout=1)
         return pool.submit_witness(air, inputs[i % n_inputs])
 
-    # warm-up: every context proves once (buffers, tables, plans); one proof in flight at a time gives the reference bytes of
-    # each input, which the proofs of the timed region are compared with below
+    # warm-up: every context proves (buffers, tables, plans): each input once with one proof in flight -- with --full these are the
+    # reference bytes the proofs of the timed region are compared with below -- then all contexts at once, `--warmup` proofs per device
+    # in whole waves
     solo_proofs = {}
     for i in range(n_inputs):
-        pr, _ = pool.wait(submit(i))
-        solo_proofs[i] = pr
-    for w in range(max(1, args.warmup)):
-        for t in [submit(i) for i in range(n_inputs)]:  # ... and all contexts at once
+        pr, _ = pool.wait(submit(i), keep=args.full)
+        if args.full:
+            solo_proofs[i] = pr
+    for w in range(max(1, -(-args.warmup // inflight))):
+        for t in [submit(i) for i in range(n_inputs)]:
             pool.wait(t, keep=False)
     phase_ms = {k: 0.0 for k in S.PHASE_NAMES}
     total_steps = args.steps * n_pools  # per process: `steps` per device
@@ -399,16 +442,18 @@ def main():
                 steady_n += 1
     steady = parallel.sum_over_ranks(dist, steady if steady_n == len(done_by_slot) else float("nan"), device=reduce_device)
 
-    # ---- untimed: what was timed is checked -- every kept proof of the timed region is accepted by the verifier and equals,
+    # ---- untimed, --full: what was timed is checked -- every kept proof of the timed region is accepted by the verifier and equals,
     # byte for byte, the proof of the same input made with nothing else in flight; rank 0's first input also has an oracle digest
-    timed_verified = 0
-    for i, pr in sorted(timed_last.items()):
-        S.verify_stark_proof(air, cfg, pr)
-        if not np.array_equal(pr, solo_proofs[i]):
-            raise SystemExit(f"proof of input {seeds[i]:#x} made with {inflight} in flight per device differs from the one made alone")
-        timed_verified += 1
+    timed_verified = None
+    if args.full:
+        timed_verified = 0
+        for i, pr in sorted(timed_last.items()):
+            S.verify_stark_proof(air, cfg, pr)
+            if not np.array_equal(pr, solo_proofs[i]):
+                raise SystemExit(f"proof of input {seeds[i]:#x} made with {inflight} in flight per device differs from the one made alone")
+            timed_verified += 1
     oracle_match = None
-    if rank == 0 and 0 in timed_last:
+    if args.full and rank == 0 and 0 in timed_last:
         try:
             import hashlib
             want = open(os.path.join(ROOT, "tests", "golden", "final_exp_seed_%x_proof.sha256" % seeds[0])).read().split()[0]
@@ -486,7 +531,7 @@ def main():
         solo_host = {"fiat_shamir": 0.0, "other": 0.0}
         t_solo, solo_gen = None, None
         kernels = {}
-        if not args.no_solo:
+        if args.full and not args.no_solo:
             n_solo = 3
             t_solo = time.perf_counter()
             solo_gen = 0.0
@@ -572,9 +617,10 @@ def main():
             "poseidon_perms_per_s": perms / (lh_ms * 1e-3) if lh_ms > 0 else None,
             "constraint_evals_per_s": (S.air_num_constraints(air) * float(N) / (solo_ms["quotient_eval"] * 1e-3)) if solo_ms["quotient_eval"] > 0 else None,
             "timed_proofs_verified": timed_verified,
-            "timed_proofs_check": (f"the last proof of each of the {inflight} inputs made INSIDE the timed region: accepted by the verifier and byte-identical to "
-                                   "the proof of the same input made with one in flight"
-                                   + ("; input 0x5eed0001 also matches the CPU oracle's digest (tests/golden/final_exp_seed_5eed0001_proof.sha256)" if oracle_match else "")),
+            "timed_proofs_check": ((f"the last proof of each of the {inflight} inputs made INSIDE the timed region: accepted by the verifier and byte-identical to "
+                                    "the proof of the same input made with one in flight"
+                                    + ("; input 0x5eed0001 also matches the CPU oracle's digest (tests/golden/final_exp_seed_5eed0001_proof.sha256)" if oracle_match else ""))
+                                   if args.full else "not checked in this run (bench.py --full checks them)"),
             "oracle_digest_match": oracle_match,
             "generate_trace_ms_timed_region": (sum(gen_ms) / len(gen_ms)) if (gen_ms and args.input == "witness") else None,
             "latency_ms_one_in_flight": t_solo * 1e3 if t_solo else None,
@@ -588,7 +634,7 @@ def main():
                      "region, which include the time a kernel shares the CUs with the other contexts' kernels"),
             "reference_published": {"value": 1 / 92.0, "unit": "proofs/s", "hardware": "AWS r6a.8xlarge, 32-core EPYC 7R13 (reference README.md:39)"},
         }
-        if not args.no_boundary and world == 1 and not n_dev:  # per-GPU figures, taken at N = 1 (other ranks would wait in the teardown meanwhile)
+        if args.full and not args.no_boundary and world == 1 and not n_dev:  # per-GPU figures, taken at N = 1 (other ranks would wait in the teardown meanwhile)
             # ---- untimed legs on the SAME pool, `inflight` in flight: the other hand-over forms of the same boundary
             try:
                 def leg(submit_one, reps):
@@ -599,8 +645,7 @@ def main():
                         pool.wait(t, keep=False)
                     return reps / (time.perf_counter() - t0)
                 reps = 3 * inflight  # three waves of the pool per leg
-                if host_rows is None:
-                    host_rows = helper.host_array((n, C))
+                staging_rows()
                 _, pis0 = S.trace_final_exp(inputs[0], out=host_rows)
                 out["value_host_rows"] = {"value": leg(lambda i: pool.submit(air, cfg, host_rows, pis0), reps), "unit": "proofs/s per GPU", "in_flight": inflight,
                                           "what": "page-locked host ROWS (4.8 GB, what generate_trace returns) -> H2D -> transpose -> proof -> D2H; generation not included"}
@@ -618,14 +663,17 @@ def main():
                                             "in_flight": inflight, "what": "operand -> generate_trace -> upload -> proof -> D2H"}
             except Exception as e:  # never lose the main line to an auxiliary leg
                 out["value_host_rows"] = {"value": None, "error": str(e)}
-        if not args.no_cpu_baseline and world == 1 and n_dev <= 1:  # rank 0 at N = 1 only: other ranks would sit in the teardown barrier meanwhile
+        if args.full and not args.no_cpu_baseline and world == 1 and n_dev <= 1:  # rank 0 at N = 1 only: other ranks would sit in the teardown barrier meanwhile
             try:
                 out["cpu_baseline"] = cpu_baseline_sample(S, S.air_program(air), C, log_n, cfg.rate_bits)
             except Exception as e:  # the oracle is a checker, never a dependency of the measured path
                 out["cpu_baseline"] = {"value": None, "unit": "proofs/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, timed_last[(total_steps - 1) % n_inputs])
         print(json.dumps(out), flush=True)
     pool.close()
-    helper.close()
+    if helper is not None:
+        helper.close()
     if dist is not None:
         dist.destroy_process_group()
 

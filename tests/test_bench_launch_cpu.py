@@ -79,3 +79,34 @@ def test_the_library_has_no_peer_to_peer_call():
     assert out.returncode == 0, out.stderr
     peer = [l for l in out.stdout.splitlines() if "Peer" in l or "hipIpc" in l]
     assert peer == [], peer
+
+
+def test_dump_outputs_writes_the_proof_exactly_and_samples_a_long_one(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` writes the last timed proof as float64 halves of its u64 words: exact for every word, a fixed
+    seeded sample of the offsets above DUMP_WORDS words (the same offsets in every run), and the whole blob's SHA-256."""
+    import hashlib
+    import numpy as np
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", os.environ.get("GPU_MAX_HW_QUEUES", "4"))  # importing bench must not change this process
+    monkeypatch.syspath_prepend(ROOT)
+    import bench
+    proof = np.random.default_rng(5).integers(0, np.iinfo(np.uint64).max, size=1000, dtype=np.uint64, endpoint=True)
+    proof[:3] = [0, 2**64 - 1, 2**32]
+
+    def load(d):
+        w, idx, sha = (np.load(os.path.join(d, f)) for f in ("proof_words.npy", "proof_index.npy", "proof_sha256.npy"))
+        assert w.dtype == np.float64 and idx.dtype == np.float64 and sha.dtype == np.float32 and sha.shape == (32,)
+        assert bytes(sha.astype(np.uint8)) == hashlib.sha256(proof.tobytes()).digest()
+        back = w[:, 0].astype(np.uint64) | (w[:, 1].astype(np.uint64) << np.uint64(32))
+        return back, idx.astype(np.int64)
+
+    bench.dump_outputs(str(tmp_path / "all"), proof)
+    back, idx = load(tmp_path / "all")
+    assert np.array_equal(idx, np.arange(proof.size)) and np.array_equal(back, proof)
+
+    monkeypatch.setattr(bench, "DUMP_WORDS", 100)
+    bench.dump_outputs(str(tmp_path / "a"), proof)
+    bench.dump_outputs(str(tmp_path / "b"), proof)
+    back_a, idx_a = load(tmp_path / "a")
+    back_b, idx_b = load(tmp_path / "b")
+    assert idx_a.size == 100 and np.array_equal(idx_a, idx_b) and np.all(np.diff(idx_a) > 0)
+    assert np.array_equal(back_a, proof[idx_a]) and np.array_equal(back_b, back_a)

@@ -14,7 +14,7 @@ if [ "$PART" != "bench" ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 if [ "$PART" != "tests" ]; then
-  timeout -k 10 600 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || rc=$?
+  timeout -k 10 600 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || rc=$?
   tail -3 $OUT/${TAG}_bench.err
   python3 - <<PY
 import json

@@ -14,8 +14,8 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 if [ "$PART" != "sig" ]; then
 cd /tmp && export TMPDIR=/tmp
-ONE="python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-boundary --inflight 1"
-rocprofv3 --kernel-trace --stats -d $OUT/prof_kt -o kt -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-boundary --inflight 1 > $OUT/prof_kt.log 2>&1
+ONE="python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-boundary --inflight 1"
+rocprofv3 --kernel-trace --stats -d $OUT/prof_kt -o kt -- python3 $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-boundary --inflight 1 > $OUT/prof_kt.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $OUT/prof_fetch -o fetch -- $ONE > $OUT/prof_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $OUT/prof_write -o write -- $ONE > $OUT/prof_write.log 2>&1
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_LDS SQ_BUSY_CYCLES -d $OUT/prof_sq -o sq -- $ONE > $OUT/prof_sq.log 2>&1
@@ -44,7 +44,7 @@ python3 tools/lane_group_stats.py $(db prof_ov) $OUT/${TAG}_lane_groups.json > /
 grep '^{"metric"' $OUT/prof_kt.log | tail -1 > $OUT/${TAG}_bench_under_rocprof.json
 rm -rf $OUT/prof_kt $OUT/prof_fetch $OUT/prof_write $OUT/prof_sq $OUT/prof_ov $OUT/prof_lfetch $OUT/prof_lwrite $OUT/prof_lsq
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 -o /tmp/valu_rate_bench tools/valu_rate_bench.hip && /tmp/valu_rate_bench > $OUT/${TAG}_valu_rates.txt 2>&1 || true
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 head -8 $OUT/${TAG}_kernel_stats.csv; cat $OUT/${TAG}_kernel_overlap.txt; cat $OUT/${TAG}_pmc_traffic.json | head -40; tail -c 3000 $OUT/${TAG}_bench.json
 fi
 if [ "$PART" != "prof" ]; then
