@@ -189,6 +189,12 @@ extern "C" {
     pub fn starkhip_host_free(p: *mut c_void);
 
     pub fn starkhip_verify(air: Air, cfg: *const starkhip_config_t, proof: *const u64, proof_words: usize) -> c_int;
+    // verifier (GPU): the query rounds of a batch on the context's device; results[i] = starkhip_verify's code for proof i
+    pub fn starkhip_verify_batch(ctx: *mut c_void, n: usize, airs: *const Air, cfgs: *const starkhip_config_t, proofs: *const *const u64,
+                                 proof_words: *const usize, results: *mut c_int) -> c_int;
+    pub fn starkhip_last_verify_timings(ctx: *mut c_void, out: *mut f64) -> c_int;
+    pub fn starkhip_verify_batch_replay(n: usize, airs: *const Air, cfgs: *const starkhip_config_t, proofs: *const *const u64,
+                                        proof_words: *const usize, results: *mut c_int) -> c_int;
     pub fn starkhip_proof_layout(proof: *const u64, proof_words: usize, out: *mut starkhip_proof_layout_t) -> c_int;
     pub fn starkhip_free(p: *mut c_void);
     pub fn starkhip_proof_blob_stats(out: *mut u64);
@@ -354,6 +360,27 @@ impl Prover {
         let mut ms = [0f32; STARKHIP_N_PHASES];
         check(unsafe { starkhip_last_timings(self.ctx, ms.as_mut_ptr()) })?;
         Ok(ms)
+    }
+
+    /// `verify_stark_proof` (:67,113,146,177) for a batch, with the query rounds on this context's device.  `Err` when the call
+    /// failed (HIP, out of memory); otherwise one verdict per proof, exactly what [`verify`] returns for it.
+    pub fn verify_batch(&mut self, proofs: &[(Air, &Config, &Proof)]) -> Result<Vec<Result<(), Error>>, Error> {
+        let airs: Vec<Air> = proofs.iter().map(|p| p.0).collect();
+        let cfgs: Vec<starkhip_config_t> = proofs.iter().map(|p| *p.1).collect();
+        let ptrs: Vec<*const u64> = proofs.iter().map(|p| p.2 .0.as_ptr()).collect();
+        let words: Vec<usize> = proofs.iter().map(|p| p.2 .0.len()).collect();
+        let mut rcs = vec![0 as c_int; proofs.len()];
+        check(unsafe {
+            starkhip_verify_batch(self.ctx, proofs.len(), airs.as_ptr(), cfgs.as_ptr(), ptrs.as_ptr(), words.as_ptr(), rcs.as_mut_ptr())
+        })?;
+        Ok(rcs.into_iter().map(check).collect())
+    }
+
+    /// The last [`Prover::verify_batch`]: host prelude ms, upload ms, device ms, the process's CPU seconds in the call.
+    pub fn last_verify_timings(&mut self) -> Result<[f64; 4], Error> {
+        let mut out = [0f64; 4];
+        check(unsafe { starkhip_last_verify_timings(self.ctx, out.as_mut_ptr()) })?;
+        Ok(out)
     }
 }
 

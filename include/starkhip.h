@@ -395,6 +395,25 @@ void starkhip_poseidon_permute_host_many(uint64_t state[12], size_t n, int which
 /* --- verifier (CPU) ------------------------------------------------------------------- */
 int starkhip_verify(starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* proof, size_t proof_words);
 
+/* --- verifier (GPU) -------------------------------------------------------------------
+ * The same verdicts as starkhip_verify (verify_stark_proof, src/aggregate_proof.rs:67,113,146,177) for a batch of proofs, with the
+ * query rounds -- the verifier's bulk: a re-hash of each opened trace leaf and a dot product over it -- on the context's device.
+ * The host runs each proof's prelude (shapes, the Fiat-Shamir replay, proof of work, the quotient identity at zeta) on at most 16
+ * threads.  Returns STARKHIP_OK when the call ran; results[i] is then exactly what starkhip_verify returns for proof i (OK,
+ * STARKHIP_ERR_VERIFY, STARKHIP_ERR_BAD_SHAPE or STARKHIP_ERR_BAD_AIR).  NULL ctx: STARKHIP_ERR_NO_DEVICE; HIP and OOM errors
+ * describe the call, not a proof.  Proofs are uploaded in chunks of at most the context option "verify_chunk_mb" of device memory
+ * (default 1024; a proof bigger than that goes alone); page-locked pool blobs are copied directly, other memory through a
+ * page-locked staging buffer.  Not concurrently with prove() on the same context. */
+int starkhip_verify_batch(void* ctx, size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                          const size_t* proof_words, int* results);
+/* the last starkhip_verify_batch of this context: host prelude ms, upload ms (stream time of the copies), device ms (kernels),
+ * and the process's CPU seconds during the call */
+int starkhip_last_verify_timings(void* ctx, double out[4]);
+/* tests: starkhip_verify_batch's host side with the device's part replayed on the CPU (same descriptors, the same per-query
+ * routine, the host permutation); no device needed */
+int starkhip_verify_batch_replay(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                                 const size_t* proof_words, int* results);
+
 void starkhip_free(void* p);
 const char* starkhip_error_string(int code);
 

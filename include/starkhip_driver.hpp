@@ -91,6 +91,7 @@ class Prover {
   public:
     explicit Prover(int device = 0) { check("starkhip_init", starkhip_init(device, &ctx_)); }
     ~Prover() { starkhip_shutdown(ctx_); }
+    void* handle() const { return ctx_; }  // the context (starkhip_init), e.g. for verify_batch_on_device
     Prover(const Prover&) = delete;
     Prover& operator=(const Prover&) = delete;
 
@@ -403,6 +404,24 @@ inline std::vector<SignatureProofs> prove_batch(Pool& pool, const std::vector<Si
     out.reserve(sigs.size());
     for (SignatureTickets& t : tickets) out.push_back(wait_signature(pool, t, verify));
     return out;
+}
+
+// verify_stark_proof (src/aggregate_proof.rs:67,113,146,177) for a batch, with the query rounds on `ctx`'s device
+// (starkhip_verify_batch): one code per proof, exactly what starkhip_verify returns for it; throws if the call itself failed
+inline std::vector<int> verify_batch_on_device(void* ctx, const std::vector<const Proof*>& proofs) {
+    std::vector<starkhip_air_t> airs;
+    std::vector<starkhip_config_t> cfgs;
+    std::vector<const uint64_t*> blobs;
+    std::vector<size_t> words;
+    for (const Proof* p : proofs) {
+        airs.push_back(p->air);
+        cfgs.push_back(p->config);
+        blobs.push_back(p->words.data());
+        words.push_back(p->words.size());
+    }
+    std::vector<int> rcs(proofs.size(), 0);
+    check("starkhip_verify_batch", starkhip_verify_batch(ctx, proofs.size(), airs.data(), cfgs.data(), blobs.data(), words.data(), rcs.data()));
+    return rcs;
 }
 
 }  // namespace starkhip_driver

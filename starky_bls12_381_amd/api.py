@@ -93,6 +93,10 @@ lib.starkhip_field_ops_batch.argtypes = [C.c_void_p, C.c_int, _u64p, _u64p, _u64
 lib.starkhip_poseidon_permute_host.argtypes = [_u64p]
 lib.starkhip_poseidon_permute_host.restype = None
 lib.starkhip_verify.argtypes = [C.c_int, C.POINTER(StarkConfig), _u64p, C.c_size_t]
+_verify_batch_args = [C.c_size_t, C.POINTER(C.c_int), C.POINTER(StarkConfig), C.POINTER(_u64p), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+lib.starkhip_verify_batch.argtypes = [C.c_void_p] + _verify_batch_args
+lib.starkhip_verify_batch_replay.argtypes = _verify_batch_args
+lib.starkhip_last_verify_timings.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
 lib.starkhip_free.argtypes = [C.c_void_p]
 lib.starkhip_free.restype = None
 lib.starkhip_host_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
@@ -559,6 +563,21 @@ class Prover:
         _chk(lib.starkhip_poseidon_permute_batch(self._ctx, _p64(s), s.shape[0]))
         return s
 
+    def verify_batch(self, items):
+        """starkhip_verify_batch: `items` = [(air, config, proof), ...] -> the code starkhip_verify gives each proof (0 = accepted),
+        with the query rounds on this context's device.  A failed call (HIP, out of memory) raises StarkhipError."""
+        return _verify_batch(items, self._ctx)
+
+    def verify_stark_proof_device(self, air, config, proof):
+        """verify_stark_proof with the query rounds on the device; raises StarkhipError on rejection, like verify_stark_proof."""
+        _chk(self.verify_batch([(air, config, proof)])[0])
+
+    def last_verify_timings(self):
+        """The last verify_batch: {"prelude_ms", "upload_ms", "device_ms", "cpu_s"} (cpu_s: the process's CPU seconds in the call)."""
+        out = (C.c_double * 4)()
+        _chk(lib.starkhip_last_verify_timings(self._ctx, out))
+        return dict(zip(("prelude_ms", "upload_ms", "device_ms", "cpu_s"), list(out)))
+
 
 # ----------------------------------------------------------------------------- proof pool (submit / wait)
 class PoolConfig(C.Structure):
@@ -866,6 +885,27 @@ def verify_stark_proof(air, config, proof):
     """Mirror of starky::verifier::verify_stark_proof; raises StarkhipError on rejection."""
     p = np.ascontiguousarray(proof, dtype=np.uint64)
     _chk(lib.starkhip_verify(air, C.byref(config), _p64(p), p.size))
+
+
+def _verify_batch(items, ctx=None, replay=False):
+    items = list(items)
+    n = len(items)
+    keep = [np.ascontiguousarray(p, dtype=np.uint64) for _, _, p in items]
+    airs = (C.c_int * max(n, 1))(*[int(a) for a, _, _ in items])
+    cfgs = (StarkConfig * max(n, 1))(*[c for _, c, _ in items])
+    ptrs = (_u64p * max(n, 1))(*[_p64(p) for p in keep])
+    words = (C.c_size_t * max(n, 1))(*[p.size for p in keep])
+    res = (C.c_int * max(n, 1))()
+    if replay:
+        _chk(lib.starkhip_verify_batch_replay(n, airs, cfgs, ptrs, words, res))
+    else:
+        _chk(lib.starkhip_verify_batch(ctx, n, airs, cfgs, ptrs, words, res))
+    return [int(r) for r in res[:n]]
+
+
+def verify_batch_replay(items):
+    """starkhip_verify_batch_replay (tests): the device verifier's host side with its device part replayed on the CPU."""
+    return _verify_batch(items, replay=True)
 
 
 def trace_rows_to_poly_values(trace_rows):

@@ -57,6 +57,13 @@ void blob_free(void* p) {
     free(p);
 }
 
+bool blob_is_pinned(const void* p, size_t bytes) {
+    std::lock_guard<std::mutex> g(g_mu);
+    for (const Slot& s : g_slots)
+        if ((const char*)p >= (const char*)s.p && (const char*)p + bytes <= (const char*)s.p + s.cap) return true;
+    return false;
+}
+
 int blob_arena_add(const void* owner, size_t bytes, unsigned count) {
     for (unsigned i = 0; i < count; i++) {
         void* p = nullptr;

@@ -16,6 +16,7 @@ namespace starkhip {
 
 uint64_t* blob_alloc(size_t bytes);  // an idle arena blob of at least `bytes` (the smallest that fits), else malloc; nullptr: out of memory
 void blob_free(void* p);             // an arena blob goes back to the arena, anything else to free(); nullptr is fine
+bool blob_is_pinned(const void* p, size_t bytes);  // [p, p + bytes) lies inside one arena blob (page-locked: copies to the device need no staging)
 // `count` new page-locked blobs of `bytes` owned by `owner`.  Device-wide synchronisation inside: warm-up only.  0 or a hipError_t.
 int blob_arena_add(const void* owner, size_t bytes, unsigned count);
 void blob_arena_drop(const void* owner);  // the owner goes away: its idle blobs are released now, its busy ones when they are freed

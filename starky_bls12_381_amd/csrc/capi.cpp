@@ -20,6 +20,7 @@
 #include "prover.h"
 #include "proof.h"
 #include "quotient_plan.h"
+#include "verifier.h"
 
 using namespace starkhip;
 
@@ -597,6 +598,32 @@ int starkhip_verify(starkhip_air_t air, const starkhip_config_t* cfg, const uint
     const AirInfo* a = air_get(air);
     if (!a) return STARKHIP_ERR_BAD_AIR;
     return verify_proof(*a, *cfg, proof, proof_words);
+}
+
+int starkhip_verify_batch(void* ctx, size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                          const size_t* proof_words, int* results) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    try {
+        return verify_batch_device((Ctx*)ctx, n, airs, cfgs, proofs, proof_words, results);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+
+int starkhip_last_verify_timings(void* ctx, double out[4]) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    if (!out) return STARKHIP_ERR_BAD_SHAPE;
+    memcpy(out, ctx_verify_timings((Ctx*)ctx), 4 * sizeof(double));
+    return STARKHIP_OK;
+}
+
+int starkhip_verify_batch_replay(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                                 const size_t* proof_words, int* results) {
+    try {
+        return verify_batch_replay(n, airs, cfgs, proofs, proof_words, results);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
 }
 
 void starkhip_proof_blob_stats(uint64_t out[5]) {

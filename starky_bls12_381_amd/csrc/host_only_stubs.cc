@@ -19,6 +19,8 @@
 #include "prover.h"
 #include "scheduler.h"
 #include "trace_log.h"
+#include "verifier.h"
+#include "verify_query.h"
 
 namespace starkhip {
 std::atomic<uint64_t> g_wait_cpu_ns(0);
@@ -33,6 +35,7 @@ struct Ctx {
     HashService* hs = nullptr;
     bool hash_requested = false, urgent = false;
     float timings[STARKHIP_N_PHASES] = {0}, ktimings[3] = {0}, htimings[2] = {0};
+    double verify_timings[4] = {0};
     std::set<int> blob_airs;
 };
 int ctx_create(int device, Ctx** out, int) {
@@ -51,6 +54,9 @@ void ctx_destroy(Ctx* c) {
 size_t ctx_device_bytes(Ctx*) { return 0; }
 size_t ctx_pinned_bytes(Ctx*) { return 0; }
 const float* ctx_timings(Ctx* c) { return c->timings; }
+long ctx_verify_chunk_mb(Ctx*) { return 1024; }
+double* ctx_verify_timings(Ctx* c) { return c->verify_timings; }
+int ctx_device(Ctx* c) { return c->device; }
 const float* ctx_kernel_timings(Ctx* c) { return c->ktimings; }
 const float* ctx_host_timings(Ctx* c) { return c->htimings; }
 void ctx_commit_info(Ctx*, int* form, unsigned* group) { *form = 0; *group = 1; }
@@ -117,6 +123,14 @@ hipError_t launch_leaf_hash_multi(const LeafHashBatch&, unsigned count, size_t, 
     g_fake_merged += count;
     return hipSuccess;
 }
+// the device verifier's launches (verifier_device.cpp): no device here
+hipError_t launch_ext_powers(gl2_t*, gl2_t, size_t, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_verify_leaf_digests(const gl_t*, const VQLeaf*, size_t, gl_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_verify_range(const gl_t*, const VQProof*, size_t, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_verify_combine(const gl_t*, const VQProof*, const uint32_t*, size_t, const gl2_t*, gl2_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_verify_queries(const gl_t*, const VQProof*, const uint32_t*, const uint64_t*, size_t, const gl_t*, const gl2_t*, uint32_t*, hipStream_t) {
+    return hipErrorNoDevice;
+}
 }  // namespace starkhip
 
 // ---- no-op HIP runtime: only what scheduler.cpp calls (the sanitizer builds do not link libamdhip64)
@@ -135,4 +149,14 @@ hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+// ... and what the device verifier's host side calls before its first launch fails
+hipError_t hipMalloc(void** p, size_t bytes) { *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipMemcpy(void*, const void*, size_t, hipMemcpyKind) { return hipSuccess; }
+hipError_t hipMemcpyAsync(void*, const void*, size_t, hipMemcpyKind, hipStream_t) { return hipSuccess; }
+hipError_t hipMemsetAsync(void*, int, size_t, hipStream_t) { return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { free((void*)e); return hipSuccess; }
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return hipSuccess; }
 }

@@ -25,6 +25,8 @@ struct QOp;  // quotient_ops.h
 struct QTRec;  // quotient_plan.h
 struct QTStream;
 struct QTContrib;
+struct VQProof;  // verify_query.h
+struct VQLeaf;
 }
 
 namespace starkhip {
@@ -121,5 +123,14 @@ hipError_t launch_query_leaf_rows(const gl_t* rows, size_t width, const uint32_t
                                   size_t off, hipStream_t st);
 hipError_t launch_query_path(const gl_t* digests, size_t n_leaves, unsigned depth, const uint32_t* xs, unsigned shift, size_t n_queries, gl_t* out,
                              size_t stride, size_t off, hipStream_t st);
+
+// device verifier (verifier_device.cpp): the row-form digests of opened leaves (kernels_hash.hip), then kernels_verify.hip's range check
+// of the query sections (bad[p] |= 1), fri_combine_initial's sums (two per query) and the per-query checks (one status word per query)
+hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, hipStream_t st);
+hipError_t launch_verify_range(const gl_t* words, const VQProof* proofs, size_t n_proofs, uint32_t* bad, hipStream_t st);
+hipError_t launch_verify_combine(const gl_t* words, const VQProof* proofs, const uint32_t* query_proof, size_t n_queries, const gl2_t* apow,
+                                 gl2_t* sums, hipStream_t st);
+hipError_t launch_verify_queries(const gl_t* words, const VQProof* proofs, const uint32_t* query_proof, const uint64_t* x_index, size_t n_queries,
+                                 const gl_t* digests, const gl2_t* sums, uint32_t* status, hipStream_t st);
 
 }  // namespace starkhip

@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "poseidon_merged.h"
 #include "poseidon_dev.h"
+#include "verify_query.h"
 
 namespace starkhip {
 
@@ -317,14 +318,9 @@ __global__ __launch_bounds__(256) void leaf_hash_multi_kernel(LeafHashBatch B, s
     leaf_hash_body(B.mat[blockIdx.y], n_cols, log_n, rate_bits, B.digests[blockIdx.y]);
 }
 
-// ---- the row form (poseidon_dev.h): 16 lanes per leaf, for commitments whose quad launch would leave most of the chip idle.
-// Same digests as leaf_hash_kernel.  Lane e < 8 of a row absorbs column 8 b + e of block b (the rate), lanes 8 .. 11 carry the
-// capacity, lanes 12 .. 15 idle as mirrors.  One wave = 4 leaves; adjacent rows read adjacent points of a column.
-__global__ __launch_bounds__(256) void leaf_hash_row_kernel(const gl_t* __restrict__ mat, size_t n_cols, unsigned log_n, unsigned rate_bits,
-                                                             gl_t* __restrict__ digests) { STARKHIP_PRIO_ENTRY
-    // [lane of the row][entry]: entries 0 .. 31 the round constants (zero beyond round 29), 32 + 3 t + {0, 1, 2} the merged triples' k1, k2
-    // (lane 0 only) and k3; everything zero on lanes 12 .. 15
-    __shared__ RcPair rcs[16][64];
+// [lane of the row][entry]: entries 0 .. 31 the round constants (zero beyond round 29), 32 + 3 t + {0, 1, 2} the merged triples' k1, k2
+// (lane 0 only) and k3; everything zero on lanes 12 .. 15.  Filled by the whole block; the caller synchronises.
+__device__ __forceinline__ void row_rcs_fill(RcPair (*rcs)[64]) {
     for (unsigned idx = threadIdx.x; idx < 16 * 64; idx += blockDim.x) {
         const unsigned e = idx / 64, r = idx % 64;
         RcPair c = {0, 0};
@@ -339,6 +335,15 @@ __global__ __launch_bounds__(256) void leaf_hash_row_kernel(const gl_t* __restri
         }
         rcs[e][r] = c;
     }
+}
+
+// ---- the row form (poseidon_dev.h): 16 lanes per leaf, for commitments whose quad launch would leave most of the chip idle.
+// Same digests as leaf_hash_kernel.  Lane e < 8 of a row absorbs column 8 b + e of block b (the rate), lanes 8 .. 11 carry the
+// capacity, lanes 12 .. 15 idle as mirrors.  One wave = 4 leaves; adjacent rows read adjacent points of a column.
+__global__ __launch_bounds__(256) void leaf_hash_row_kernel(const gl_t* __restrict__ mat, size_t n_cols, unsigned log_n, unsigned rate_bits,
+                                                             gl_t* __restrict__ digests) { STARKHIP_PRIO_ENTRY
+    __shared__ RcPair rcs[16][64];
+    row_rcs_fill(rcs);
     __syncthreads();
     const unsigned log_N = log_n + rate_bits;
     const size_t N = (size_t)1 << log_N;
@@ -384,6 +389,46 @@ __global__ __launch_bounds__(256) void leaf_hash_row_kernel(const gl_t* __restri
     }
     if (e < 4) digests[4 * j + e] = gl_canon(s);
 #undef STARKHIP_ROW_PERMUTE
+}
+
+// ---- the device verifier's leaf digests (verifier_device.cpp): opened leaves of query rounds, contiguous words in the proof, one
+// descriptor each (verify_query.h: VQLeaf), hashed in the row form -- the shortest chain per permutation, and a batch has only a few
+// thousand long chains.  Lane e < 8 of a row absorbs word 8 b + e of block b, one block ahead; the host sorts the descriptors longest
+// first, so the longest chains start first and the waves hold chains of like length.
+__global__ __launch_bounds__(256) void verify_leaf_digest_kernel(const gl_t* __restrict__ words, const VQLeaf* __restrict__ leaves, size_t n_leaves,
+                                                                  gl_t* __restrict__ digests) { STARKHIP_PRIO_ENTRY
+    __shared__ RcPair rcs[16][64];
+    row_rcs_fill(rcs);
+    __syncthreads();
+    const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const unsigned e = (unsigned)tid & 15u;
+    const size_t q = tid >> 4;
+    if (q >= n_leaves) return;  // whole rows drop out together
+    const VQLeaf lf = leaves[q];
+    const gl_t* in = words + lf.off;
+    gl_t* out = digests + 4 * (size_t)lf.slot;
+    if (lf.len <= 4) {  // hash_or_noop: short leaves are copied, zero padded
+        if (e < 4) out[e] = e < lf.len ? in[e] : 0;
+        return;
+    }
+    RowConsts K;
+    row_consts_init(K, e, ROW_MERGED.coef[e]);
+    const RcPair* rc = rcs[e];
+    const bool absorbs = e < 8;
+    const gl_t* mine = in + (absorbs ? e : 0);  // lanes 8 .. 15 never load
+    const size_t n_full = lf.len / 8, rem = lf.len % 8;
+    gl_t s = 0, nx = 0;
+    if (n_full && absorbs) nx = mine[0];
+    for (size_t b = 0; b < n_full; b++) {
+        if (absorbs) s = nx;
+        if (b + 1 < n_full && absorbs) nx = mine[8 * (b + 1)];  // requested one permutation ahead
+        s = poseidon_permute_row_merged_asm(s, rc, K);
+    }
+    if (rem) {  // the last, partial block overwrites elements 0 .. rem - 1 only
+        if (e < rem) s = mine[8 * n_full];
+        s = poseidon_permute_row_merged_asm(s, rc, K);
+    }
+    if (e < 4) out[e] = gl_canon(s);
 }
 
 // ---- the lane form (poseidon_dev.h): one lane per leaf, for big commitments when several are in flight (the pool picks).
@@ -745,6 +790,12 @@ hipError_t launch_leaf_hash_row(const gl_t* mat, size_t n_cols, unsigned log_n, 
     size_t N = (size_t)1 << (log_n + rate_bits);
     if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
     hipLaunchKernelGGL(leaf_hash_row_kernel, dim3(nblocks(16 * N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+    return hipGetLastError();
+}
+hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, hipStream_t st) {
+    if (!n_leaves) return hipSuccess;
+    if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(verify_leaf_digest_kernel, dim3(nblocks(16 * n_leaves, 256)), dim3(256), 0, st, words, leaves, n_leaves, digests);
     return hipGetLastError();
 }
 hipError_t launch_leaf_hash_lane(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st) {

@@ -30,6 +30,7 @@
 #include "quotient_plan.h"
 #include "prover.h"
 #include "scheduler.h"
+#include "verifier.h"
 
 #ifdef STARKHIP_ROCTX  // make ROCTX=1: phase ranges for rocprofv3 --marker-trace; the default build has no profiler-SDK dependency
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -143,6 +144,8 @@ struct Ctx {
 #endif
     long opt_lde_closed_forms = 1;   // constant / unit-vector columns skip their transforms (kernels_lde.hip); 0: every column is transformed
     long opt_host_commit_leaves = 64; // trace commitments of at most this many leaves (and >= 64 columns) are hashed by host threads (0: never)
+    long opt_verify_chunk_mb = 1024;  // device memory one chunk of starkhip_verify_batch may take (verifier_device.cpp)
+    double verify_timings[4] = {0};   // the last starkhip_verify_batch: host prelude ms, upload ms, device ms, host CPU seconds
     std::vector<gl_t> host_lde;      // their LDE on the host
     // op-stream program (quotient_impl = 1; kept as the cross-check)
     int prog_air = -1;
@@ -507,6 +510,7 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
     else if (k == "host_commit_leaves" && value >= 0 && value <= 4096) c->opt_host_commit_leaves = value;
     else if (k == "leaf_hash_form" && value >= 0 && value <= 4) c->opt_leaf_hash_form = value;
     else if (k == "quotient_chunks" && value >= 0 && value <= 4096) c->opt_quotient_chunks = value;  // plans are cached by (AIR, chunks)
+    else if (k == "verify_chunk_mb" && value >= 1) c->opt_verify_chunk_mb = value;
     else return STARKHIP_ERR_BAD_SHAPE;
     return STARKHIP_OK;
 }
@@ -527,6 +531,9 @@ size_t ctx_device_bytes(Ctx* c) {
 }
 size_t ctx_pinned_bytes(Ctx* c) { return c->host_staging_cap + c->rb_cap; }
 const float* ctx_timings(Ctx* c) { return c->timings; }
+long ctx_verify_chunk_mb(Ctx* c) { return c->opt_verify_chunk_mb; }
+double* ctx_verify_timings(Ctx* c) { return c->verify_timings; }
+int ctx_device(Ctx* c) { return c->device; }
 const float* ctx_kernel_timings(Ctx* c) { return c->ktimings; }
 const float* ctx_host_timings(Ctx* c) { return c->htimings; }
 void ctx_commit_info(Ctx* c, int* form, unsigned* group) {

@@ -14,6 +14,7 @@
 #include "airs.h"
 #include "poseidon.h"
 #include "proof.h"
+#include "verifier.h"
 
 namespace starkhip {
 
@@ -65,8 +66,9 @@ static gl2_t fri_fold_eval(gl_t x, size_t x_index_within_coset, unsigned arity_b
     return res;
 }
 
-int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words) {
-    ProofLayout pl;
+int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words, bool check_query_words,
+                   VerifyPrelude* out) {
+    ProofLayout& pl = out->pl;
     if (!pl.read_header(proof, words)) return STARKHIP_ERR_BAD_SHAPE;
     const AirProgram& P = air.prog;
     const unsigned factor = P.degree > 1 ? P.degree - 1 : 1;
@@ -74,9 +76,12 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
         pl.n_queries != cfg.num_query_rounds || pl.n_challenges != cfg.num_challenges || pl.Q != (size_t)factor * cfg.num_challenges ||
         pl.arity_bits != cfg.arity_bits)
         return STARKHIP_ERR_BAD_SHAPE;
-    for (size_t i = 16; i < words; i++)
+    const size_t skip_lo = check_query_words ? words : pl.off_queries, skip_hi = check_query_words ? words : pl.off_final;
+    for (size_t i = 16; i < skip_lo; i++)
         if (proof[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
-    FriGeometry geo;
+    for (size_t i = skip_hi; i < words; i++)
+        if (proof[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    FriGeometry& geo = out->geo;
     if (!FriGeometry::make(cfg, (unsigned)pl.log_n, &geo)) return STARKHIP_ERR_BAD_SHAPE;
     if (geo.arities.size() != pl.L || geo.final_poly_len != pl.final_len) return STARKHIP_ERR_BAD_SHAPE;
 
@@ -98,7 +103,8 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
     for (size_t q = 0; q < Q; q++) ch.observe_ext(op_q[q]);
     for (size_t c = 0; c < C; c++) ch.observe_ext(op_next[c]);
     gl2_t fri_alpha = ch.get_ext();
-    std::vector<gl2_t> betas(pl.L);
+    std::vector<gl2_t>& betas = out->betas;
+    betas.resize(pl.L);
     for (size_t l = 0; l < pl.L; l++) {
         ch.observe_many(proof + pl.off_fri_caps + l * 4 * ncap, 4 * ncap);
         betas[l] = ch.get_ext();
@@ -107,7 +113,8 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
     ch.observe(proof[pl.off_pow]);
     gl_t pow_response = ch.get();
     if (cfg.proof_of_work_bits > 0 && (pow_response >> (64 - cfg.proof_of_work_bits)) != 0) return STARKHIP_ERR_VERIFY;
-    std::vector<size_t> indices(pl.n_queries);
+    std::vector<size_t>& indices = out->indices;
+    indices.resize(pl.n_queries);
     for (auto& x : indices) x = (size_t)(ch.get() % N);
 
     // ---- quotient identity at zeta
@@ -127,14 +134,31 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
         if (!gl2_eq(acc[i], gl2_mul(z_h, s))) return STARKHIP_ERR_VERIFY;
     }
 
-    // ---- FRI
-    gl2_t gzeta = gl2_mul_base(zeta, g);
+    // ---- what the FRI queries take from here
+    out->zeta = zeta;
+    out->gzeta = gl2_mul_base(zeta, g);
+    out->fri_alpha = fri_alpha;
     // precomputed reduced openings per batch: sum_j alpha^j open_j
     gl2_t red0 = gl2_zero(), red1 = gl2_zero();
     for (size_t q = Q; q-- > 0;) red0 = gl2_add(gl2_mul(red0, fri_alpha), op_q[q]);
     for (size_t c = C; c-- > 0;) red0 = gl2_add(gl2_mul(red0, fri_alpha), op_local[c]);
     for (size_t c = C; c-- > 0;) red1 = gl2_add(gl2_mul(red1, fri_alpha), op_next[c]);
-    gl2_t alpha_pow_C = gl2_pow(fri_alpha, C);
+    out->red0 = red0;
+    out->red1 = red1;
+    out->alpha_pow_C = gl2_pow(fri_alpha, C);
+    return STARKHIP_OK;
+}
+
+int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words) {
+    VerifyPrelude pre;
+    if (int rc = verify_prelude(air, cfg, proof, words, true, &pre); rc != STARKHIP_OK) return rc;
+    const ProofLayout& pl = pre.pl;
+    const FriGeometry& geo = pre.geo;
+    const size_t C = pl.C, Q = pl.Q, ncap = pl.ncap;
+    const gl2_t fri_alpha = pre.fri_alpha, zeta = pre.zeta, gzeta = pre.gzeta, red0 = pre.red0, red1 = pre.red1, alpha_pow_C = pre.alpha_pow_C;
+    const std::vector<gl2_t>& betas = pre.betas;
+    const std::vector<size_t>& indices = pre.indices;
+    const gl2_t* final_poly = (const gl2_t*)(proof + pl.off_final);
 
     // The 84 query rounds are independent and dominated by re-hashing a trace leaf each (FinalExp: 9191 permutations per
     // leaf, 0.8 M in all -- about a second on one core), so they are checked by a few host threads.

@@ -1,0 +1,394 @@
+// Device verifier: starkhip_verify_batch (and its CPU replay, starkhip_verify_batch_replay).  Per proof, the host runs the
+// prelude the CPU verifier runs (verify_prelude: shapes, the Fiat-Shamir replay, proof of work, the quotient identity at zeta) on
+// a bounded set of threads; the query rounds -- a leaf re-hash of C / 8 permutations per query and a dot product of C terms, the
+// verifier's bulk -- go to the GPU in chunks of proofs whose device footprint stays under the context's "verify_chunk_mb":
+//   upload   each proof's caps, FRI caps, query rounds and final polynomial (page-locked pool blobs directly, anything else through
+//            two page-locked staging halves)
+//   kernels  range check of the query sections, the row-form digests of every opened leaf (longest first), powers of the FRI
+//            alpha and fri_combine_initial's sums, then one lane per query for the Merkle paths and the FRI layers (verify_query.h)
+//   result   one status word per query and one range flag per proof; BAD_SHAPE wins over VERIFY, as on the CPU.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <time.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <thread>
+#include <vector>
+
+#include "airs.h"
+#include "blob_arena.h"
+#include "kernels.h"
+#include "poseidon.h"
+#include "proof.h"
+#include "prover.h"
+#include "scheduler.h"
+#include "verifier.h"
+#include "verify_query.h"
+
+namespace starkhip {
+namespace {
+
+struct Item {
+    int code = STARKHIP_OK;
+    bool queries = false;  // the prelude passed: the query rounds decide
+    VerifyPrelude pre;
+};
+
+bool query_words_in_range(const uint64_t* proof, const ProofLayout& pl) {
+    for (size_t i = pl.off_queries; i < pl.off_final; i++)
+        if (proof[i] >= GL_P) return false;
+    return true;
+}
+
+// the preludes of a batch on at most 16 host threads (cpu_budget(): the CPUs this process may use)
+void run_preludes(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs, const size_t* words,
+                  std::vector<Item>& items) {
+    items.assign(n, Item());
+    std::atomic<size_t> next(0);
+    auto worker = [&]() {
+        for (size_t i; (i = next.fetch_add(1)) < n;) {
+            Item& it = items[i];
+            int id;  // read as an int: a caller's id need not be one of the enum's values
+            memcpy(&id, &airs[i], sizeof id);
+            const AirInfo* a = air_get(id);
+            if (!a) {
+                it.code = STARKHIP_ERR_BAD_AIR;
+                continue;
+            }
+            if (!proofs[i]) {
+                it.code = STARKHIP_ERR_BAD_SHAPE;
+                continue;
+            }
+            const int rc = verify_prelude(*a, cfgs[i], proofs[i], words[i], false, &it.pre);
+            if (rc == STARKHIP_OK) it.queries = true;
+            else if (rc == STARKHIP_ERR_VERIFY) it.code = query_words_in_range(proofs[i], it.pre.pl) ? STARKHIP_ERR_VERIFY : STARKHIP_ERR_BAD_SHAPE;
+            else it.code = rc;
+        }
+    };
+    const size_t n_threads = std::min<size_t>({(size_t)16, (size_t)std::max(1u, cpu_budget()), n});
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < n_threads; t++) pool.emplace_back(worker);
+    worker();
+    for (auto& t : pool) t.join();
+}
+
+// A proof's words in the chunk's buffer: [trace cap | quotient cap] then [FRI caps .. final polynomial] of the blob
+size_t head_words(const ProofLayout& pl) { return 8 * pl.ncap; }
+size_t region_words(const ProofLayout& pl) { return head_words(pl) + (pl.off_pow - pl.off_fri_caps); }
+size_t device_bytes(const ProofLayout& pl) {
+    const size_t per_query = (2 + pl.L) * (4 * 8 + sizeof(VQLeaf)) + 2 * sizeof(gl2_t) + 8 + 4 + 4;
+    return 8 * region_words(pl) + sizeof(gl2_t) * (pl.C + pl.Q) + pl.n_queries * per_query + sizeof(VQProof) + 4;
+}
+
+struct Chunk {
+    std::vector<size_t> ids;  // batch indices of its proofs
+    std::vector<VQProof> proofs;
+    std::vector<VQLeaf> leaves;
+    std::vector<uint32_t> query_proof;
+    std::vector<uint64_t> x_index;
+    size_t words = 0, apow = 0, digests = 0, bytes = 0;
+};
+
+void chunk_add(Chunk& ch, size_t id, const VerifyPrelude& pre) {
+    const ProofLayout& pl = pre.pl;
+    VQProof P;
+    memset(&P, 0, sizeof P);
+    const size_t h = head_words(pl);
+    P.base = ch.words;
+    P.query_words = pl.query_words;
+    P.off_quot_cap = 4 * pl.ncap;
+    P.off_fri_caps = h;
+    P.off_queries = h + (pl.off_queries - pl.off_fri_caps);
+    P.off_final = h + (pl.off_final - pl.off_fri_caps);
+    P.apow = ch.apow;
+    P.C = (uint32_t)pl.C;
+    P.Q = (uint32_t)pl.Q;
+    P.L = (uint32_t)pl.L;
+    P.log_N = (uint32_t)pl.log_N;
+    P.cap_h = (uint32_t)pl.cap_h;
+    P.final_len = (uint32_t)pl.final_len;
+    P.first_query = (uint32_t)ch.query_proof.size();
+    P.first_digest = (uint32_t)ch.digests;
+    for (size_t l = 0; l < pl.L; l++) {
+        P.arity_bits[l] = pre.geo.arities[l];
+        P.layer_depth[l] = (uint32_t)pl.layer_depth[l];
+        P.betas[l] = pre.betas[l];
+    }
+    P.zeta = pre.zeta;
+    P.gzeta = pre.gzeta;
+    P.red0 = pre.red0;
+    P.red1 = pre.red1;
+    P.alpha_pow_C = pre.alpha_pow_C;
+    const size_t d0 = pl.log_N - pl.cap_h, per_q = 2 + pl.L;
+    for (size_t q = 0; q < pl.n_queries; q++) {
+        const uint32_t slot = (uint32_t)(ch.digests + q * per_q);
+        size_t o = P.base + P.off_queries + q * pl.query_words;
+        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.C, slot});
+        o += pl.C + 4 * d0;
+        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.Q, slot + 1});
+        o += pl.Q + 4 * d0;
+        for (size_t l = 0; l < pl.L; l++) {
+            const size_t arity = (size_t)1 << pre.geo.arities[l];
+            ch.leaves.push_back(VQLeaf{o, (uint32_t)(2 * arity), (uint32_t)(slot + 2 + l)});
+            o += 2 * arity + 4 * pl.layer_depth[l];
+        }
+        ch.query_proof.push_back((uint32_t)ch.proofs.size());
+        ch.x_index.push_back(pre.indices[q]);
+    }
+    ch.proofs.push_back(P);
+    ch.ids.push_back(id);
+    ch.words += region_words(pl);
+    ch.apow += pl.C + pl.Q;
+    ch.digests += pl.n_queries * per_q;
+    ch.bytes += device_bytes(pl);
+}
+
+// proofs in batch order, a new chunk whenever the next proof would take the current one past `cap` bytes (a proof bigger than
+// the cap gets a chunk of its own); the leaves of a chunk longest first
+std::vector<Chunk> make_chunks(const std::vector<Item>& items, size_t cap) {
+    std::vector<Chunk> out;
+    for (size_t i = 0; i < items.size(); i++) {
+        if (!items[i].queries) continue;
+        if (out.empty() || (!out.back().ids.empty() && out.back().bytes + device_bytes(items[i].pre.pl) > cap)) out.emplace_back();
+        chunk_add(out.back(), i, items[i].pre);
+    }
+    for (Chunk& ch : out)
+        std::stable_sort(ch.leaves.begin(), ch.leaves.end(), [](const VQLeaf& a, const VQLeaf& b) { return a.len > b.len; });
+    return out;
+}
+
+// the two pieces of proof `id`'s region: (source, words, destination word)
+struct Piece {
+    const uint64_t* src;
+    size_t words, dst;
+};
+void pieces(const Chunk& ch, size_t k, const uint64_t* proof, const ProofLayout& pl, Piece out[2]) {
+    const size_t base = ch.proofs[k].base;
+    out[0] = Piece{proof + pl.off_trace_cap, head_words(pl), base};
+    out[1] = Piece{proof + pl.off_fri_caps, pl.off_pow - pl.off_fri_caps, base + head_words(pl)};
+}
+
+// the per-proof results of a chunk from its query statuses and range flags
+void chunk_results(const Chunk& ch, const std::vector<uint32_t>& status, const std::vector<uint32_t>& bad, std::vector<Item>& items) {
+    for (size_t k = 0; k < ch.ids.size(); k++) {
+        const VQProof& P = ch.proofs[k];
+        const size_t nq = items[ch.ids[k]].pre.pl.n_queries;
+        uint32_t any = 0;
+        for (size_t q = 0; q < nq; q++) any |= status[P.first_query + q];
+        items[ch.ids[k]].code = bad[k] ? STARKHIP_ERR_BAD_SHAPE : any ? STARKHIP_ERR_VERIFY : STARKHIP_OK;
+    }
+}
+
+double process_cpu_s() {
+    timespec ts;
+    if (clock_gettime(CLOCK_PROCESS_CPUTIME_ID, &ts) != 0) return 0;
+    return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
+}
+double wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+bool call_args_ok(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs, const size_t* words,
+                  const int* results) {
+    return n == 0 || (airs && cfgs && proofs && words && results);
+}
+
+// ---- device memory of one call, released on every way out
+struct DevMem {
+    std::vector<void*> bufs;
+    void* staging = nullptr;
+    hipStream_t st = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}, sev[2] = {nullptr, nullptr};
+    ~DevMem() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (void* b : bufs) (void)hipFree(b);
+        if (staging) (void)hipHostFree(staging);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : sev)
+            if (e) (void)hipEventDestroy(e);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    template <class T>
+    hipError_t alloc(T** p, size_t count) {
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) bufs.push_back(v);
+        *p = (T*)v;
+        return e;
+    }
+};
+
+const size_t STAGING_HALF = (size_t)32 << 20;  // bytes per page-locked staging half
+
+}  // namespace
+
+#define VHIP(x)                                                                          \
+    do {                                                                                 \
+        const hipError_t e_ = (x);                                                       \
+        if (e_ != hipSuccess) {                                                          \
+            (void)hipGetLastError();                                                     \
+            return e_ == hipErrorOutOfMemory ? STARKHIP_ERR_OOM : STARKHIP_ERR_HIP;      \
+        }                                                                                \
+    } while (0)
+
+int verify_batch_device(Ctx* c, size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                        const size_t* proof_words, int* results) {
+    if (!c) return STARKHIP_ERR_NO_DEVICE;
+    if (!call_args_ok(n, airs, cfgs, proofs, proof_words, results)) return STARKHIP_ERR_BAD_SHAPE;
+    double* tm = ctx_verify_timings(c);
+    for (int i = 0; i < 4; i++) tm[i] = 0;
+    const double cpu0 = process_cpu_s(), t0 = wall_ms();
+    std::vector<Item> items;
+    run_preludes(n, airs, cfgs, proofs, proof_words, items);
+    tm[0] = wall_ms() - t0;
+    const std::vector<Chunk> chunks = make_chunks(items, (size_t)ctx_verify_chunk_mb(c) << 20);
+    if (!chunks.empty()) {
+        VHIP(hipSetDevice(ctx_device(c)));
+        size_t max_words = 0, max_apow = 0, max_dig = 0, max_q = 0, max_p = 0, max_leaves = 0;
+        for (const Chunk& ch : chunks) {
+            max_words = std::max(max_words, ch.words);
+            max_apow = std::max(max_apow, ch.apow);
+            max_dig = std::max(max_dig, ch.digests);
+            max_q = std::max(max_q, ch.query_proof.size());
+            max_p = std::max(max_p, ch.proofs.size());
+            max_leaves = std::max(max_leaves, ch.leaves.size());
+        }
+        DevMem m;
+        gl_t *d_words, *d_dig;
+        gl2_t *d_apow, *d_sums;
+        VQProof* d_proofs;
+        VQLeaf* d_leaves;
+        uint32_t *d_qproof, *d_status, *d_bad;
+        uint64_t* d_xidx;
+        VHIP(m.alloc(&d_words, max_words));
+        VHIP(m.alloc(&d_apow, max_apow));
+        VHIP(m.alloc(&d_dig, 4 * max_dig));
+        VHIP(m.alloc(&d_sums, 2 * max_q));
+        VHIP(m.alloc(&d_proofs, max_p));
+        VHIP(m.alloc(&d_leaves, max_leaves));
+        VHIP(m.alloc(&d_qproof, max_q));
+        VHIP(m.alloc(&d_xidx, max_q));
+        VHIP(m.alloc(&d_status, max_q));
+        VHIP(m.alloc(&d_bad, max_p));
+        VHIP(hipStreamCreateWithFlags(&m.st, hipStreamNonBlocking));
+        for (hipEvent_t& e : m.ev) VHIP(hipEventCreate(&e));
+        for (hipEvent_t& e : m.sev) VHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        bool used[2] = {false, false};
+        unsigned half = 0;
+        std::vector<uint32_t> status, bad;
+        for (const Chunk& ch : chunks) {
+            VHIP(hipEventRecord(m.ev[0], m.st));
+            VHIP(hipMemcpyAsync(d_proofs, ch.proofs.data(), ch.proofs.size() * sizeof(VQProof), hipMemcpyHostToDevice, m.st));
+            VHIP(hipMemcpyAsync(d_leaves, ch.leaves.data(), ch.leaves.size() * sizeof(VQLeaf), hipMemcpyHostToDevice, m.st));
+            VHIP(hipMemcpyAsync(d_qproof, ch.query_proof.data(), ch.query_proof.size() * 4, hipMemcpyHostToDevice, m.st));
+            VHIP(hipMemcpyAsync(d_xidx, ch.x_index.data(), ch.x_index.size() * 8, hipMemcpyHostToDevice, m.st));
+            VHIP(hipMemsetAsync(d_bad, 0, ch.proofs.size() * 4, m.st));
+            for (size_t k = 0; k < ch.ids.size(); k++) {
+                const size_t id = ch.ids[k];
+                Piece pc[2];
+                pieces(ch, k, proofs[id], items[id].pre.pl, pc);
+                const bool pinned = blob_is_pinned(proofs[id], proof_words[id] * 8);
+                for (const Piece& p : pc) {
+                    if (pinned) {
+                        VHIP(hipMemcpyAsync(d_words + p.dst, p.src, p.words * 8, hipMemcpyHostToDevice, m.st));
+                        continue;
+                    }
+                    if (!m.staging) VHIP(hipHostMalloc(&m.staging, 2 * STAGING_HALF, hipHostMallocDefault));
+                    for (size_t done = 0; done < p.words;) {  // pageable: through the two staging halves in turn
+                        const size_t w = std::min(p.words - done, STAGING_HALF / 8);
+                        if (used[half]) VHIP(event_wait_sleeping(m.sev[half]));  // the copy that last read this half has run
+                        uint64_t* s = (uint64_t*)m.staging + half * (STAGING_HALF / 8);
+                        memcpy(s, p.src + done, w * 8);
+                        VHIP(hipMemcpyAsync(d_words + p.dst + done, s, w * 8, hipMemcpyHostToDevice, m.st));
+                        VHIP(hipEventRecord(m.sev[half], m.st));
+                        used[half] = true;
+                        half ^= 1;
+                        done += w;
+                    }
+                }
+            }
+            VHIP(hipEventRecord(m.ev[1], m.st));
+            for (size_t k = 0; k < ch.ids.size(); k++) {
+                const VQProof& P = ch.proofs[k];
+                VHIP(launch_ext_powers(d_apow + P.apow, items[ch.ids[k]].pre.fri_alpha, P.C + P.Q, m.st));
+            }
+            VHIP(launch_verify_range(d_words, d_proofs, ch.proofs.size(), d_bad, m.st));
+            VHIP(launch_verify_leaf_digests(d_words, d_leaves, ch.leaves.size(), d_dig, m.st));
+            VHIP(launch_verify_combine(d_words, d_proofs, d_qproof, ch.query_proof.size(), d_apow, d_sums, m.st));
+            VHIP(launch_verify_queries(d_words, d_proofs, d_qproof, d_xidx, ch.query_proof.size(), d_dig, d_sums, d_status, m.st));
+            VHIP(hipEventRecord(m.ev[2], m.st));
+            VHIP(event_wait_sleeping(m.ev[2]));
+            status.resize(ch.query_proof.size());
+            bad.resize(ch.proofs.size());
+            VHIP(hipMemcpy(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost));
+            VHIP(hipMemcpy(bad.data(), d_bad, bad.size() * 4, hipMemcpyDeviceToHost));
+            float up = 0, dev = 0;
+            VHIP(hipEventElapsedTime(&up, m.ev[0], m.ev[1]));
+            VHIP(hipEventElapsedTime(&dev, m.ev[1], m.ev[2]));
+            tm[1] += up;
+            tm[2] += dev;
+            chunk_results(ch, status, bad, items);
+        }
+    }
+    for (size_t i = 0; i < n; i++) results[i] = items[i].code;
+    tm[3] = process_cpu_s() - cpu0;
+    return STARKHIP_OK;
+}
+
+// The same host side, with the device's work done on the CPU: the region copies into one buffer, the range check, every leaf
+// digest through the host permutation, the sums as dot products with the powers of alpha, and verify_query.h per query.
+int verify_batch_replay(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                        const size_t* proof_words, int* results) {
+    if (!call_args_ok(n, airs, cfgs, proofs, proof_words, results)) return STARKHIP_ERR_BAD_SHAPE;
+    std::vector<Item> items;
+    run_preludes(n, airs, cfgs, proofs, proof_words, items);
+    for (const Chunk& ch : make_chunks(items, (size_t)1024 << 20)) {
+        std::vector<gl_t> W(ch.words);
+        std::vector<uint32_t> bad(ch.proofs.size(), 0), status(ch.query_proof.size(), 0);
+        std::vector<gl2_t> apow(ch.apow), sums(2 * ch.query_proof.size());
+        std::vector<gl_t> dig(4 * ch.digests);
+        for (size_t k = 0; k < ch.ids.size(); k++) {
+            const size_t id = ch.ids[k];
+            const VQProof& P = ch.proofs[k];
+            Piece pc[2];
+            pieces(ch, k, proofs[id], items[id].pre.pl, pc);
+            for (const Piece& p : pc) memcpy(W.data() + p.dst, p.src, p.words * 8);
+            for (uint64_t i = P.base + P.off_queries; i < P.base + P.off_final; i++) bad[k] |= W[i] >= GL_P;
+            gl2_t a = gl2_one();
+            for (size_t i = 0; i < (size_t)P.C + P.Q; i++, a = gl2_mul(a, items[id].pre.fri_alpha)) apow[P.apow + i] = a;
+        }
+        for (const VQLeaf& lf : ch.leaves) {  // hash_or_noop
+            gl_t* out = dig.data() + 4 * (size_t)lf.slot;
+            const gl_t* in = W.data() + lf.off;
+            if (lf.len <= 4) {
+                for (uint32_t i = 0; i < 4; i++) out[i] = i < lf.len ? in[i] : 0;
+                continue;
+            }
+            gl_t s[12] = {0};
+            for (uint32_t off = 0; off < lf.len; off += 8) {
+                for (uint32_t i = 0; i < 8 && off + i < lf.len; i++) s[i] = in[off + i];
+                poseidon_permute_host(s);
+            }
+            for (int i = 0; i < 4; i++) out[i] = s[i];
+        }
+        for (size_t g = 0; g < ch.query_proof.size(); g++) {
+            const VQProof& P = ch.proofs[ch.query_proof[g]];
+            const uint32_t qi = (uint32_t)g - P.first_query;
+            const gl_t* tleaf = W.data() + P.base + P.off_queries + (uint64_t)qi * P.query_words;
+            const gl_t* qleaf = tleaf + P.C + 4 * (P.log_N - P.cap_h);
+            gl2_t st = gl2_zero(), sq = gl2_zero();
+            for (uint32_t c = 0; c < P.C; c++) st = gl2_add(st, gl2_mul_base(apow[P.apow + c], tleaf[c]));
+            for (uint32_t q = 0; q < P.Q; q++) sq = gl2_add(sq, gl2_mul_base(apow[P.apow + P.C + q], qleaf[q]));
+            sums[2 * g] = gl2_add(st, sq);
+            sums[2 * g + 1] = st;
+            status[g] = vq_check_query(P, W.data() + P.base, dig.data() + 4 * ((size_t)P.first_digest + (size_t)qi * (2 + P.L)), sums[2 * g],
+                                       sums[2 * g + 1], ch.x_index[g], qi);
+        }
+        chunk_results(ch, status, bad, items);
+    }
+    for (size_t i = 0; i < n; i++) results[i] = items[i].code;
+    return STARKHIP_OK;
+}
+
+}  // namespace starkhip

@@ -54,6 +54,8 @@ def main():
     ap.add_argument("--gather-ms", type=float, default=0.0, help="pool: how long a merged commitment waits for stragglers (0 = default)")
     ap.add_argument("--collect", action="store_true", help="N > 1: gather every proof on every rank afterwards (raw buffers) and check all signatures")
     ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--verify-device", action="store_true", help="also verify the last step's proofs in one starkhip_verify_batch (query rounds on "
+                    "the GPU): adds verify_device_s and verify_device_cpu_s beside verify_s, the host verifier's time")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -114,10 +116,23 @@ def main():
 
     # ---- untimed: what the reference does right after each prove (verify_stark_proof) and what its recursion enforces
     verified = 0
+    t_verify = time.perf_counter()
     if not args.no_verify:
         for (_, name), (air, proof, cfg) in results.items():
             S.verify_stark_proof(air, cfg, proof)
             verified += 1
+    verify_s, device_verify = time.perf_counter() - t_verify, None
+    if args.verify_device:
+        vp = S.Prover(local_rank)
+        items = [(air, cfg, proof) for _, (air, proof, cfg) in sorted(results.items())]
+        t_verify = time.perf_counter()
+        codes = vp.verify_batch(items)
+        device_verify = {"verify_s": verify_s, "verify_device_s": time.perf_counter() - t_verify}
+        device_verify["verify_device_cpu_s"] = vp.last_verify_timings()["cpu_s"]
+        device_verify["verify_device_ms"] = {k: v for k, v in vp.last_verify_timings().items() if k != "cpu_s"}
+        vp.close()
+        if any(codes):
+            raise SystemExit("device verifier rejected %d of %d proofs" % (sum(1 for c in codes if c), len(codes)))
     merged = G.collect_results(dist, results, device=dev) if (dist is not None and args.collect) else results
     verdicts = G.check_signatures(merged, sigs, natives, args.batch)
     checked, valid = len(verdicts), sum(verdicts.values())
@@ -140,6 +155,8 @@ def main():
                     + (" -- REHEARSAL over gloo on one GPU, not a measurement" if rehearse else ""),
             "plan": {str(r): [f"{i}:{n}" for i, n in jobs] for r, jobs in enumerate(plan)} if args.batch <= 2 else f"{6 * args.batch} jobs, longest first over {world} rank(s)",
         }
+        if device_verify is not None:
+            out.update(device_verify)
         print(json.dumps(out), flush=True)
     for pv in all_provers:
         pv.close()

@@ -12,6 +12,9 @@
 //                                       the same from ONE process on several GPUs (starkhip_multipool_*: a pool per listed device --
 //                                       an ordinal may repeat --, jobs placed longest first); --digests adds a digest of every proof
 //                                       of the last step (the bytes do not depend on which device, pool or context made a proof)
+//   signature_demo --batch 8 --verify-on device
+//                                       also verifies the last step's proofs with starkhip_verify_batch (query rounds on the GPU) and
+//                                       adds verify_device_s and verify_device_cpu_s beside verify_s (default: --verify-on host)
 // Exit code 0 = every proof verified, the public inputs chain, and final_exponentiate(ml1 * ml2) == 1 for every signature.
 // Operand file: B records of 120 little-endian u32 limbs -- pk x, y (12 each), H(m) x, y (24 each), signature x, y (24 each);
 // Z = (1, 0) is implied (tools/make_signature_operands.py derives them from the reference vector).  Build: make demo
@@ -72,7 +75,7 @@ static double seconds_since(std::chrono::steady_clock::time_point t0) { return s
 
 int main(int argc, char** argv) {
     size_t batch = 0, steps = 3, warmup = 1, pipeline = 1;
-    bool use_pool = false, timeline = false, digests = false;
+    bool use_pool = false, timeline = false, digests = false, verify_on_device = false;
     std::vector<int> devices;
     const char* operands = nullptr;
     starkhip_pool_config_t cfg;
@@ -107,6 +110,11 @@ int main(int argc, char** argv) {
                 p = *end == ',' ? end + 1 : end;
             }
         } else if (a == "--digests") digests = true;
+        else if (a == "--verify-on") {  // host (default): starkhip_verify per proof; device: also starkhip_verify_batch, timed beside it
+            const std::string v = val();
+            if (v != "host" && v != "device") { fprintf(stderr, "signature_demo: --verify-on wants host or device\n"); return 2; }
+            verify_on_device = v == "device";
+        }
         else {
             fprintf(stderr, "signature_demo: unknown option %s\n", a.c_str());
             return 2;
@@ -200,6 +208,29 @@ int main(int argc, char** argv) {
                 checks.push_back(std::async(std::launch::async, [p] { return starkhip_verify(p->air, &p->config, p->words.data(), p->words.size()); }));
         for (auto& c : checks) verified += c.get() == STARKHIP_OK;
         for (size_t i = 0; i < proofs.size(); i++) ok += proofs[i].valid && proofs[i].linked && starkhip_driver::statement_holds(proofs[i], sigs[i]);
+        // the same verdicts with the query rounds on the device: one starkhip_verify_batch over every proof of the step
+        std::string device_json;
+        double device_block_s = 0;  // kept out of verify_s, which stays the host verifier's (and the statement checks') time as before
+        if (verify_on_device) {
+            const auto tb = std::chrono::steady_clock::now();
+            starkhip_driver::Prover verifier(devices.empty() ? cfg.device : devices[0]);
+            std::vector<const starkhip_driver::Proof*> all;
+            for (const SignatureProofs& s : proofs)
+                for (const starkhip_driver::Proof* p : {&s.pp1, &s.ml1, &s.pp2, &s.ml2, &s.fp12_mul, &s.final_exp}) all.push_back(p);
+            const auto td = std::chrono::steady_clock::now();
+            const std::vector<int> rcs = starkhip_driver::verify_batch_on_device(verifier.handle(), all);
+            const double dev_s = seconds_since(td);
+            double tm[4] = {0, 0, 0, 0};
+            starkhip_last_verify_timings(verifier.handle(), tm);
+            size_t dev_ok = 0;
+            for (int rc : rcs) dev_ok += rc == STARKHIP_OK;
+            if (dev_ok != verified) verified = 0;  // the two verifiers disagree: the run fails
+            char buf[256];
+            snprintf(buf, sizeof buf, "\"verify_device_s\": %.3f, \"verify_device_cpu_s\": %.3f, \"verify_device_ms\": {\"prelude\": %.1f, \"upload\": %.1f, \"device\": %.1f}, ",
+                     dev_s, tm[3], tm[0], tm[1], tm[2]);
+            device_json = buf;
+            device_block_s = seconds_since(tb);
+        }
         if (timeline) {
             double t0 = 1e300;
             for (const SignatureProofs& s : proofs)
@@ -240,9 +271,9 @@ int main(int argc, char** argv) {
         const starkhip_pool_stats_t st = pool.stats();
         printf("{\"metric\": \"BLS signature checks/s, end to end from compiled host code (operands -> natives -> trace generation -> 6 STARK proofs each)\", "
                "\"value\": %.4f, \"unit\": \"signatures/s\", \"batch\": %zu, \"steps\": %zu, \"warmup\": %zu, \"ms_per_step\": %.1f, \"best_ms\": %.1f, \"step_ms\": [%s], "
-               "\"batches_in_flight\": %zu, \"proofs_per_step\": %zu, \"proofs_verified_after_timing\": %zu, \"verify_s\": %.2f, \"signatures_valid_linked_bound\": %zu, "
+               "\"batches_in_flight\": %zu, \"proofs_per_step\": %zu, \"proofs_verified_after_timing\": %zu, \"verify_s\": %.2f, %s\"signatures_valid_linked_bound\": %zu, "
                "\"commit_launches\": {\"big\": %lu, \"small_merged\": %lu, \"small_requests\": %lu, \"max_merged\": %lu}, \"pools\": %zu, \"commit_launches_per_pool\": [%s], \"hw_queues_late\": %d, \"proof_digests\": [%s], \"operands\": \"%s\"}\n",
-               batch / per_step, batch, steps, warmup, per_step * 1e3, best * 1e3, step_ms.c_str(), pipeline, 6 * batch, verified, seconds_since(tv), ok, st.big_commit_launches,
+               batch / per_step, batch, steps, warmup, per_step * 1e3, best * 1e3, step_ms.c_str(), pipeline, 6 * batch, verified, seconds_since(tv) - device_block_s, device_json.c_str(), ok, st.big_commit_launches,
                st.small_commit_launches, st.small_commit_requests, st.max_merged_commitments, pool.devices(), per_device_json.c_str(), starkhip_hw_queues_status(), digest_json.c_str(), operands ? operands : "reference vector (src/native.rs:1480-1498)");
         return verified == 6 * batch && ok == batch ? 0 : 1;
     } catch (const std::exception& e) {
