@@ -118,6 +118,21 @@ pub struct starkhip_ticket_info_t {
     pub leaf_hash_group: c_uint,
 }
 
+/// `starkhip_pool_verify_stats_t`: a pool's verifier, cumulative.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct starkhip_pool_verify_stats_t {
+    pub proofs_checked: std::os::raw::c_ulong,
+    pub verify_jobs: std::os::raw::c_ulong,
+    pub rejected: std::os::raw::c_ulong,
+    pub device_batches: std::os::raw::c_ulong,
+    pub upload_ms: f64,
+    pub device_ms: f64,
+    pub prelude_ms: f64,
+    pub prelude_cpu_s: f64,
+    pub arena_bytes: u64,
+}
+
 extern "C" {
     pub fn starkhip_config_standard_fast(cfg: *mut starkhip_config_t);
     pub fn starkhip_config_for_air(air: Air, cfg: *mut starkhip_config_t) -> c_int;
@@ -183,6 +198,17 @@ extern "C" {
     pub fn starkhip_multipool_wait(mpool: *mut c_void, ticket: u64, proof: *mut *mut u64, proof_words: *mut usize,
                                    info: *mut starkhip_ticket_info_t) -> c_int;
     pub fn starkhip_hw_queues_status() -> c_int;
+    pub fn starkhip_pool_set_option(pool: *mut c_void, name: *const c_char, value: c_long) -> c_int;
+    pub fn starkhip_pool_submit_verify(pool: *mut c_void, air: Air, cfg: *const starkhip_config_t, proof: *const u64, proof_words: usize,
+                                       ticket: *mut u64) -> c_int;
+    pub fn starkhip_pool_verify_stats(pool: *mut c_void, out: *mut starkhip_pool_verify_stats_t) -> c_int;
+    pub fn starkhip_multipool_set_option(mpool: *mut c_void, name: *const c_char, value: c_long) -> c_int;
+    pub fn starkhip_multipool_submit_verify(mpool: *mut c_void, slot: c_int, air: Air, cfg: *const starkhip_config_t, proof: *const u64,
+                                            proof_words: usize, ticket: *mut u64) -> c_int;
+    pub fn starkhip_multipool_verify_batch(mpool: *mut c_void, n: usize, airs: *const Air, cfgs: *const starkhip_config_t,
+                                           proofs: *const *const u64, proof_words: *const usize, results: *mut c_int) -> c_int;
+    pub fn starkhip_plan_verify(n: usize, airs: *const Air, n_pools: usize, slots: *mut c_int, order: *mut usize) -> c_int;
+    pub fn starkhip_air_verify_cost(air: Air) -> f64;
 
     pub fn starkhip_last_timings(ctx: *mut c_void, ms: *mut f32) -> c_int;
     pub fn starkhip_host_alloc(ctx: *mut c_void, bytes: usize, out: *mut *mut c_void) -> c_int;

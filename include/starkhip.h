@@ -293,6 +293,34 @@ void starkhip_proof_blob_stats(uint64_t out[5]);
  * of 4 hardware queues (a line on stderr says so once).  Detected without touching HIP (the runtime's open /dev/kfd). */
 int starkhip_hw_queues_status(void);
 
+/* --- verification inside a pool ----------------------------------------------------------------------------------
+ * The reference's drivers call verify_stark_proof straight after prove (src/aggregate_proof.rs:67,113,146,177).  A pool does the same on its
+ * own device: a verifier per pool with persistent device memory (an arena in two halves), its own stream at normal priority, preludes on
+ * a few host threads (at the generator threads' nice value) and proofs batched as their preludes finish; after its one-time setup it
+ * allocates nothing and never synchronises the device.
+ * Options (STARKHIP_ERR_BAD_SHAPE for an unknown name or a value out of range):
+ *   "verify_proofs"   0 (default) or 1: every proving ticket submitted from then on is checked before starkhip_pool_wait returns it.  OK: wait
+ *                     behaves as without the option; otherwise wait returns starkhip_verify's code (STARKHIP_ERR_VERIFY, BAD_SHAPE) and
+ *                     frees the proof.  The verifier reads the host blob the caller receives; the prover context is free already.
+ *   "verify_arena_mb" the verifier's device memory (default 1024), allocated at the first verify work, or when "verify_proofs" is
+ *                     switched on in a pool created with warm_up.  A proof larger than half of it is verified alone.  Changing it
+ *                     once the arena exists: STARKHIP_ERR_BAD_SHAPE. */
+int starkhip_pool_set_option(void* pool, const char* name, long value);
+/* A verification job for any proof (of this pool, another one, or the oracle); cfg == NULL: starkhip_config_for_air.  The proof stays the
+ * caller's until the ticket has been waited for.  starkhip_pool_wait on the ticket returns exactly starkhip_verify's code for it (OK,
+ * VERIFY, BAD_SHAPE, BAD_AIR), or HIP / OOM if the device work failed; it sets *proof = NULL and *proof_words = 0, and of `info` only
+ * t_submit, t_prove_start (the prelude started) and t_done (every other field is zero). */
+int starkhip_pool_submit_verify(void* pool, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* proof, size_t proof_words,
+                                uint64_t* ticket);
+/* cumulative: proofs checked for "verify_proofs", verify jobs, rejections (of both), device batches; the batches' summed upload and
+ * kernel time (ms of stream time), the preludes' summed wall ms and the prelude threads' CPU seconds; the arena's bytes (0: none yet) */
+typedef struct {
+    unsigned long proofs_checked, verify_jobs, rejected, device_batches;
+    double upload_ms, device_ms, prelude_ms, prelude_cpu_s;
+    uint64_t arena_bytes;
+} starkhip_pool_verify_stats_t;
+int starkhip_pool_verify_stats(void* pool, starkhip_pool_verify_stats_t* out);
+
 /* --- one caller, many devices -------------------------------------------------------------------------------------
  * The reference's caller is ONE process: generate_aggregate_proof issues its six proves from one thread (src/aggregate_proof.rs:304-370,
  * `aggregate_proof` :402-414).  A multi-device handle lets that caller use a node of GPUs as it is -- no process group, no collective
@@ -326,6 +354,19 @@ int starkhip_multipool_submit_witness_batch(void* mpool, size_t n_jobs, const st
                                             const size_t* n_limbs, uint64_t pow_witness, uint64_t* tickets, int* rcs);
 int starkhip_multipool_ticket_slot(const void* mpool, uint64_t ticket); /* -1: not a ticket of this handle */
 int starkhip_multipool_wait(void* mpool, uint64_t ticket, uint64_t** proof, size_t* proof_words, starkhip_ticket_info_t* info);
+/* the option on every pool of the handle */
+int starkhip_multipool_set_option(void* mpool, const char* name, long value);
+/* as starkhip_pool_submit_verify; slot = -1: the pool with the least outstanding verify cost (starkhip_air_verify_cost) */
+int starkhip_multipool_submit_verify(void* mpool, int slot, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* proof,
+                                     size_t proof_words, uint64_t* ticket);
+/* starkhip_verify_batch's contract, with the proofs spread over the handle's devices as verify jobs: longest first by
+ * starkhip_air_verify_cost, each to the pool with the least cost so far (starkhip_plan_verify) */
+int starkhip_multipool_verify_batch(void* mpool, size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                                    const size_t* proof_words, int* results);
+/* that placement alone (no GPU needed): slots[i] for proof i on n_pools idle pools, order[k] the k-th proof placed (order may be NULL);
+ * starkhip_air_verify_cost: the CPU verifier's milliseconds per proof of the AIR (profiles/r07_verify_device_split.json) */
+int starkhip_plan_verify(size_t n, const starkhip_air_t* airs, size_t n_pools, int* slots, size_t* order);
+double starkhip_air_verify_cost(starkhip_air_t air);
 /* the placement rule alone (no GPU needed): the slot each job of a batch gets on n_pools idle pools; starkhip_air_cost is the relative
  * single-GPU proving cost the rule uses (FinalExp 92, MillerLoop 12.5, PairingPrecomp 4.5, ECCAgg 3, FP12Mul 0.22) */
 int starkhip_plan_lpt(size_t n_jobs, const starkhip_air_t* airs, size_t n_pools, int* slots);

@@ -202,6 +202,15 @@ inline SignatureProofs prove_signature(Prover& pv, const uint32_t pk_x[12], cons
 // (src/aggregate_proof.rs:304-370, :402-414), so `Pool(devices, cfg)` gives that process a pool per device behind the same
 // submit / wait -- jobs go to the pool with the least outstanding work, FinalExp-class jobs to the pool with the fewest of them
 // (longest processing time first).  No process group and no collective: the proofs are independent.
+// How Pool::wait checks a proof: host (starkhip_verify on the caller's thread after wait: the default), pool (the pool's device verifier
+// checked it before wait returned -- its "verify_proofs" option is on; a rejection throws from wait), none.  `true` / `false` mean host / none.
+enum class VerifyOn { none, host, pool };
+struct VerifyMode {
+    VerifyOn on;
+    VerifyMode(bool v) : on(v ? VerifyOn::host : VerifyOn::none) {}
+    VerifyMode(VerifyOn o) : on(o) {}
+};
+
 class Pool {
   public:
     explicit Pool(const starkhip_pool_config_t& cfg) { check("starkhip_pool_create", starkhip_pool_create(&cfg, &pool_)); }
@@ -259,7 +268,7 @@ class Pool {
         return t;
     }
     // the finished proof of `ticket`; verify = the reference's verify_stark_proof(..).unwrap() right after prove
-    Proof wait(starkhip_air_t air, uint64_t ticket, bool verify = true, starkhip_ticket_info_t* info = nullptr) {
+    Proof wait(starkhip_air_t air, uint64_t ticket, VerifyMode verify = true, starkhip_ticket_info_t* info = nullptr) {
         Proof p;
         p.air = air;
         check("starkhip_config_for_air", starkhip_config_for_air(air, &p.config));
@@ -270,8 +279,26 @@ class Pool {
         if (info) *info = p.info;
         p.words = Words(blob, words);
         p.n_public_inputs = (size_t)starkhip_air_public_inputs(air);
-        if (verify) check("starkhip_verify", starkhip_verify(air, &p.config, p.words.data(), p.words.size()));
+        if (verify.on == VerifyOn::host) check("starkhip_verify", starkhip_verify(air, &p.config, p.words.data(), p.words.size()));
         return p;
+    }
+    // starkhip_pool_set_option (every pool of a multi-device handle): "verify_proofs", "verify_arena_mb"
+    void set_option(const char* name, long value) {
+        if (multi_) check("starkhip_multipool_set_option", starkhip_multipool_set_option(pool_, name, value));
+        else check("starkhip_pool_set_option", starkhip_pool_set_option(pool_, name, value));
+    }
+    // the pools' verifiers, summed
+    starkhip_pool_verify_stats_t verify_stats() {
+        starkhip_pool_verify_stats_t s;
+        memset(&s, 0, sizeof s);
+        for (size_t k = 0; k < devices(); k++) {
+            starkhip_pool_verify_stats_t one;
+            check("starkhip_pool_verify_stats", starkhip_pool_verify_stats(multi_ ? starkhip_multipool_pool(pool_, k) : pool_, &one));
+            s.proofs_checked += one.proofs_checked; s.verify_jobs += one.verify_jobs; s.rejected += one.rejected; s.device_batches += one.device_batches;
+            s.upload_ms += one.upload_ms; s.device_ms += one.device_ms; s.prelude_ms += one.prelude_ms; s.prelude_cpu_s += one.prelude_cpu_s;
+            s.arena_bytes += one.arena_bytes;
+        }
+        return s;
     }
     // launches of the commitment scheduler (summed over the devices' pools); slot >= 0: that device's pool alone
     starkhip_pool_stats_t stats(int slot = -1) {
@@ -372,7 +399,7 @@ inline bool statement_holds(const SignatureProofs& p, const SignatureOperands& s
            is(p.ml2.public_inputs() + 12, NEG_G1_Y, 12);
 }
 
-inline SignatureProofs wait_signature(Pool& pool, SignatureTickets& t, bool verify = true) {
+inline SignatureProofs wait_signature(Pool& pool, SignatureTickets& t, VerifyMode verify = true) {
     SignatureProofs s;
     SignatureTickets::Tail tl = t.tail.get();
     const std::array<uint64_t, 2> tail = tl.tickets;
@@ -390,13 +417,13 @@ inline SignatureProofs wait_signature(Pool& pool, SignatureTickets& t, bool veri
 }
 
 // the six proofs of one signature, all in flight at once
-inline SignatureProofs prove_signature(Pool& pool, const SignatureOperands& s, bool verify = true) {
+inline SignatureProofs prove_signature(Pool& pool, const SignatureOperands& s, VerifyMode verify = true) {
     SignatureTickets t = submit_signature(pool, s);
     return wait_signature(pool, t, verify);
 }
 
 // BASELINE configs[4]: a batch of signatures = 6 B proofs in flight on one pool
-inline std::vector<SignatureProofs> prove_batch(Pool& pool, const std::vector<SignatureOperands>& sigs, bool verify = true) {
+inline std::vector<SignatureProofs> prove_batch(Pool& pool, const std::vector<SignatureOperands>& sigs, VerifyMode verify = true) {
     std::vector<SignatureTickets> tickets;
     tickets.reserve(sigs.size());
     for (const SignatureOperands& s : sigs) tickets.push_back(submit_signature(pool, s));

@@ -636,6 +636,21 @@ lib.starkhip_multipool_wait.argtypes = lib.starkhip_pool_wait.argtypes
 lib.starkhip_plan_lpt.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_int)]
 lib.starkhip_air_cost.argtypes = [C.c_int]
 lib.starkhip_air_cost.restype = C.c_double
+# the pool's verifier (starkhip_pool_set_option "verify_proofs", starkhip_pool_submit_verify)
+class PoolVerifyStats(C.Structure):
+    _fields_ = [(n, C.c_ulong) for n in ("proofs_checked", "verify_jobs", "rejected", "device_batches")] + \
+               [(n, C.c_double) for n in ("upload_ms", "device_ms", "prelude_ms", "prelude_cpu_s")] + [("arena_bytes", C.c_uint64)]
+
+
+lib.starkhip_pool_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
+lib.starkhip_pool_submit_verify.argtypes = [C.c_void_p, C.c_int, C.POINTER(StarkConfig), _u64p, C.c_size_t, C.POINTER(C.c_uint64)]
+lib.starkhip_pool_verify_stats.argtypes = [C.c_void_p, C.POINTER(PoolVerifyStats)]
+lib.starkhip_multipool_set_option.argtypes = lib.starkhip_pool_set_option.argtypes
+lib.starkhip_multipool_submit_verify.argtypes = [C.c_void_p, C.c_int] + lib.starkhip_pool_submit_verify.argtypes[1:]
+lib.starkhip_multipool_verify_batch.argtypes = [C.c_void_p] + _verify_batch_args
+lib.starkhip_plan_verify.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+lib.starkhip_air_verify_cost.argtypes = [C.c_int]
+lib.starkhip_air_verify_cost.restype = C.c_double
 lib.starkhip_hw_queues_status.argtypes = []
 
 
@@ -715,9 +730,11 @@ class ProofPool:
     """
 
     def __init__(self, device=0, big_contexts=0, small_contexts=0, generator_threads=0, trace_threads=0, commit_policy=0, gather_ms=0.0,
-                 stream_priority=0, warm_up=0, devices=None):
+                 stream_priority=0, warm_up=0, devices=None, verify_proofs=False, verify_arena_mb=0):
         """`devices` (a list of ordinals, one pool each; an ordinal may repeat): ONE process on several GPUs through
-        starkhip_multipool_* -- the submits then take `slot` (-1: the library places the job, longest processing time first)."""
+        starkhip_multipool_* -- the submits then take `slot` (-1: the library places the job, longest processing time first).
+        `verify_proofs`: every proof is checked by the pool's device verifier before wait returns it; `verify_arena_mb` (0: the
+        library's default) sizes that verifier's device memory."""
         cfg = PoolConfig(device, big_contexts, small_contexts, generator_threads, trace_threads, commit_policy, stream_priority, warm_up, gather_ms)
         self._h = C.c_void_p()
         self._multi = devices is not None
@@ -727,6 +744,59 @@ class ProofPool:
         else:
             _chk(lib.starkhip_pool_create(C.byref(cfg), C.byref(self._h)))
         self._keep = {}  # ticket -> inputs that must outlive the proof
+        self._verify_tickets = set()
+        try:
+            if verify_arena_mb:
+                self.set_option("verify_arena_mb", verify_arena_mb)
+            if verify_proofs:
+                self.set_option("verify_proofs", 1)
+        except StarkhipError:
+            self.close()
+            raise
+
+    def set_option(self, name, value):
+        """starkhip_pool_set_option on every pool of the handle: "verify_proofs" (0 / 1), "verify_arena_mb"."""
+        if self._multi:
+            _chk(lib.starkhip_multipool_set_option(self._h, name.encode(), int(value)))
+        else:
+            _chk(lib.starkhip_pool_set_option(self._h, name.encode(), int(value)))
+
+    def submit_verify(self, air, proof, config=None, slot=-1):
+        """A verification job for any proof (starkhip_pool_submit_verify); wait(ticket) returns starkhip_verify's code for it."""
+        p = np.ascontiguousarray(proof, dtype=np.uint64)
+        cfg = StarkConfig.from_buffer_copy(config) if config is not None else None
+        t = C.c_uint64()
+        _chk(self._call("submit_verify", slot, air, C.byref(cfg) if cfg is not None else None, _p64(p), p.size, C.byref(t)))
+        self._keep[t.value] = (p, cfg)
+        self._verify_tickets.add(t.value)
+        return t.value
+
+    def verify_batch(self, items):
+        """`items` = [(air, config, proof), ...] -> the code starkhip_verify gives each proof.  On several devices
+        starkhip_multipool_verify_batch (longest first over the devices); on one pool every proof is submitted, then waited for."""
+        items = list(items)
+        if self._multi:
+            n = len(items)
+            keep = [np.ascontiguousarray(p, dtype=np.uint64) for _, _, p in items]
+            airs = (C.c_int * max(n, 1))(*[int(a) for a, _, _ in items])
+            cfgs = (StarkConfig * max(n, 1))(*[c for _, c, _ in items])
+            ptrs = (_u64p * max(n, 1))(*[_p64(p) for p in keep])
+            words = (C.c_size_t * max(n, 1))(*[p.size for p in keep])
+            res = (C.c_int * max(n, 1))()
+            _chk(lib.starkhip_multipool_verify_batch(self._h, n, airs, cfgs, ptrs, words, res))
+            return [int(r) for r in res[:n]]
+        tickets = [self.submit_verify(a, p, c) for a, c, p in items]
+        return [self.wait(t) for t in tickets]
+
+    def verify_stats(self):
+        """starkhip_pool_verify_stats summed over the handle's pools (arena_bytes too)."""
+        out = None
+        for h in self._pools():
+            r = PoolVerifyStats()
+            _chk(lib.starkhip_pool_verify_stats(h, C.byref(r)))
+            one = {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in PoolVerifyStats._fields_}
+            out = one if out is None else {n: out[n] + one[n] for n in out}
+        return out
 
     def _call(self, name, slot, *args):
         if self._multi:
@@ -748,6 +818,7 @@ class ProofPool:
             (lib.starkhip_multipool_destroy if self._multi else lib.starkhip_pool_destroy)(self._h)
             self._h = C.c_void_p()
             self._keep.clear()
+            self._verify_tickets.clear()
 
     def __del__(self):
         try:
@@ -838,6 +909,11 @@ class ProofPool:
         info = TicketInfo()
         rc = (lib.starkhip_multipool_wait if self._multi else lib.starkhip_pool_wait)(self._h, ticket, C.byref(out), C.byref(words), C.byref(info))
         self._keep.pop(ticket, None)
+        if ticket in self._verify_tickets:  # a verify job: its verdict (a failure of the device work still raises)
+            self._verify_tickets.discard(ticket)
+            if rc in (ERR_HIP, ERR_OOM, ERR_NO_DEVICE):
+                _chk(rc)
+            return rc
         _chk(rc)
         proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy() if keep else None
         lib.starkhip_free(out)

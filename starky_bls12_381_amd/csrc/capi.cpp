@@ -443,6 +443,28 @@ int starkhip_pool_stats(void* pool, starkhip_pool_stats_t* out) {
     return pool_stats((Pool*)pool, out);
 }
 
+int starkhip_pool_set_option(void* pool, const char* name, long value) {
+    if (!pool) return STARKHIP_ERR_NO_DEVICE;
+    try {
+        return pool_set_option((Pool*)pool, name, value);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+int starkhip_pool_submit_verify(void* pool, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* proof, size_t proof_words,
+                                uint64_t* ticket) {
+    if (!pool) return STARKHIP_ERR_NO_DEVICE;
+    try {
+        return pool_submit_verify((Pool*)pool, air, cfg, proof, proof_words, ticket);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+int starkhip_pool_verify_stats(void* pool, starkhip_pool_verify_stats_t* out) {
+    if (!pool || !out) return STARKHIP_ERR_BAD_SHAPE;
+    return pool_verify_stats((Pool*)pool, out);
+}
+
 // ---- a pool per device behind one handle (scheduler.cpp)
 int starkhip_multipool_create(const int* devices, size_t n_devices, const starkhip_pool_config_t* cfg, void** mpool) {
     if (!devices || !n_devices || !cfg || !mpool) return STARKHIP_ERR_BAD_SHAPE;
@@ -506,6 +528,38 @@ int starkhip_multipool_wait(void* mpool, uint64_t ticket, uint64_t** proof, size
     if (!mpool) return STARKHIP_ERR_NO_DEVICE;
     return multipool_wait((MultiPool*)mpool, ticket, proof, proof_words, info);
 }
+int starkhip_multipool_set_option(void* mpool, const char* name, long value) {
+    if (!mpool) return STARKHIP_ERR_NO_DEVICE;
+    try {
+        return multipool_set_option((MultiPool*)mpool, name, value);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+int starkhip_multipool_submit_verify(void* mpool, int slot, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* proof,
+                                     size_t proof_words, uint64_t* ticket) {
+    if (!mpool) return STARKHIP_ERR_NO_DEVICE;
+    try {
+        return multipool_submit_verify((MultiPool*)mpool, slot, air, cfg, proof, proof_words, ticket);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+int starkhip_multipool_verify_batch(void* mpool, size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
+                                    const size_t* proof_words, int* results) {
+    if (!mpool) return STARKHIP_ERR_NO_DEVICE;
+    try {
+        return multipool_verify_batch((MultiPool*)mpool, n, (const int*)airs, cfgs, proofs, proof_words, results);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+int starkhip_plan_verify(size_t n, const starkhip_air_t* airs, size_t n_pools, int* slots, size_t* order) {
+    if ((n && (!airs || !slots)) || !n_pools) return STARKHIP_ERR_BAD_SHAPE;
+    plan_verify(n, (const int*)airs, n_pools, slots, order);
+    return STARKHIP_OK;
+}
+double starkhip_air_verify_cost(starkhip_air_t air) { return air_verify_cost(air); }
 int starkhip_plan_lpt(size_t n_jobs, const starkhip_air_t* airs, size_t n_pools, int* slots) {
     if ((n_jobs && (!airs || !slots)) || !n_pools) return STARKHIP_ERR_BAD_SHAPE;
     plan_lpt(n_jobs, (const int*)airs, n_pools, slots);

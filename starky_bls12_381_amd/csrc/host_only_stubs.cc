@@ -20,6 +20,7 @@
 #include "scheduler.h"
 #include "trace_log.h"
 #include "verifier.h"
+#include "verify_chunk.h"
 #include "verify_query.h"
 
 namespace starkhip {
@@ -123,22 +124,48 @@ hipError_t launch_leaf_hash_multi(const LeafHashBatch&, unsigned count, size_t, 
     g_fake_merged += count;
     return hipSuccess;
 }
-// the device verifier's launches (verifier_device.cpp): no device here
-hipError_t launch_ext_powers(gl2_t*, gl2_t, size_t, hipStream_t) { return hipErrorNoDevice; }
-hipError_t launch_verify_leaf_digests(const gl_t*, const VQLeaf*, size_t, gl_t*, hipStream_t) { return hipErrorNoDevice; }
-hipError_t launch_verify_range(const gl_t*, const VQProof*, size_t, uint32_t*, hipStream_t) { return hipErrorNoDevice; }
-hipError_t launch_verify_combine(const gl_t*, const VQProof*, const uint32_t*, size_t, const gl2_t*, gl2_t*, hipStream_t) { return hipErrorNoDevice; }
-hipError_t launch_verify_queries(const gl_t*, const VQProof*, const uint32_t*, const uint64_t*, size_t, const gl_t*, const gl2_t*, uint32_t*, hipStream_t) {
-    return hipErrorNoDevice;
+// the device verifier's launches (verifier_device.cpp, verify_service.cpp): with the pretended device, their routine on the host --
+// the same code as starkhip_verify_batch_replay's (verify_query.h, the host permutation) on the "device" buffers, which are host memory
+// here, so that a CPU build of the pool gives real verdicts; without it, no device
+hipError_t launch_ext_powers(gl2_t* out, gl2_t alpha, size_t n, hipStream_t) {
+    if (!fake_device()) return hipErrorNoDevice;
+    verify_host_ext_powers(out, alpha, n);
+    return hipSuccess;
+}
+hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n, gl_t* digests, hipStream_t) {
+    if (!fake_device()) return hipErrorNoDevice;
+    verify_host_leaf_digests(words, leaves, n, digests);
+    return hipSuccess;
+}
+hipError_t launch_verify_range(const gl_t* words, const VQProof* proofs, size_t n, uint32_t* bad, hipStream_t) {
+    if (!fake_device()) return hipErrorNoDevice;
+    verify_host_range(words, proofs, n, bad);
+    return hipSuccess;
+}
+hipError_t launch_verify_combine(const gl_t* words, const VQProof* proofs, const uint32_t* qp, size_t nq, const gl2_t* apow, gl2_t* sums, hipStream_t) {
+    if (!fake_device()) return hipErrorNoDevice;
+    verify_host_combine(words, proofs, qp, nq, apow, sums);
+    return hipSuccess;
+}
+hipError_t launch_verify_queries(const gl_t* words, const VQProof* proofs, const uint32_t* qp, const uint64_t* xi, size_t nq, const gl_t* dig,
+                                 const gl2_t* sums, uint32_t* status, hipStream_t) {
+    if (!fake_device()) return hipErrorNoDevice;
+    verify_host_queries(words, proofs, qp, xi, nq, dig, sums, status);
+    return hipSuccess;
 }
 }  // namespace starkhip
 
-// ---- no-op HIP runtime: only what scheduler.cpp calls (the sanitizer builds do not link libamdhip64)
+// ---- no-op HIP runtime: only what scheduler.cpp calls (the sanitizer builds do not link libamdhip64).  Copies and fills are real (the
+// "device" is host memory and every stream is synchronous); every allocation -- device, page-locked, stream -- is counted
+// (starkhip_stub_allocations: the pool's verifier must not allocate after its setup)
+static std::atomic<unsigned long> g_stub_allocs(0);
+extern "C" unsigned long starkhip_stub_allocations(void) { return g_stub_allocs.load(); }
 extern "C" {
 hipError_t hipSetDevice(int) { return hipSuccess; }
+hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)malloc(1); return hipSuccess; }
-hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)malloc(1); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { g_stub_allocs++; *s = (hipStream_t)malloc(1); return hipSuccess; }
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { g_stub_allocs++; *s = (hipStream_t)malloc(1); return hipSuccess; }
 hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) { *least = 1; *greatest = -1; return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { free((void*)s); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
@@ -147,16 +174,16 @@ hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuc
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { g_stub_allocs++; *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
-// ... and what the device verifier's host side calls before its first launch fails
-hipError_t hipMalloc(void** p, size_t bytes) { *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+// ... and what the device verifier's host side calls
+hipError_t hipMalloc(void** p, size_t bytes) { g_stub_allocs++; *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipMemcpy(void*, const void*, size_t, hipMemcpyKind) { return hipSuccess; }
-hipError_t hipMemcpyAsync(void*, const void*, size_t, hipMemcpyKind, hipStream_t) { return hipSuccess; }
-hipError_t hipMemsetAsync(void*, int, size_t, hipStream_t) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t)malloc(1); return hipSuccess; }
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { if (n) memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { if (n) memset(d, v, n); return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { g_stub_allocs++; *e = (hipEvent_t)malloc(1); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { g_stub_allocs++; *e = (hipEvent_t)malloc(1); return hipSuccess; }
 hipError_t hipEventDestroy(hipEvent_t e) { free((void*)e); return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return hipSuccess; }
 }

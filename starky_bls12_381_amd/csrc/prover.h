@@ -39,6 +39,10 @@ int pool_wait(Pool* p, uint64_t ticket, uint64_t** proof, size_t* words, starkhi
 int pool_stats(Pool* p, starkhip_pool_stats_t* out);
 int pool_reservation(Pool* p, starkhip_pool_reservation_t* out);
 int pool_host_info(Pool* p, starkhip_pool_host_info_t* out);
+int pool_set_option(Pool* p, const char* name, long value);
+int pool_submit_verify(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* proof, size_t words, uint64_t* ticket);
+int pool_verify_stats(Pool* p, starkhip_pool_verify_stats_t* out);
+double air_verify_cost(int air);
 unsigned cpu_budget();  // scheduler.cpp: CPUs this process may really use
 void host_cpu_seconds(double out[3]);
 // a pool per device behind one handle (scheduler.cpp): placement by outstanding cost, longest job first
@@ -61,6 +65,11 @@ int multipool_submit_witness_batch(MultiPool* mp, size_t n, const int* airs, con
                                    uint64_t* tickets, int* rcs);
 int multipool_ticket_slot(const MultiPool* mp, uint64_t ticket);
 int multipool_wait(MultiPool* mp, uint64_t ticket, uint64_t** proof, size_t* words, starkhip_ticket_info_t* info);
+int multipool_set_option(MultiPool* mp, const char* name, long value);
+int multipool_submit_verify(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint64_t* proof, size_t words, uint64_t* ticket);
+int multipool_verify_batch(MultiPool* mp, size_t n, const int* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs, const size_t* words,
+                           int* results);
+void plan_verify(size_t n, const int* airs, size_t n_pools, int* slots, size_t* order);
 void plan_lpt(size_t n, const int* airs, size_t n_pools, int* slots);
 size_t ctx_device_bytes(Ctx* c);  // device memory this context holds (work buffers, tables, plans)
 size_t ctx_pinned_bytes(Ctx* c);  // page-locked host memory it holds (upload staging; proof blobs are counted by starkhip_proof_blob_stats)

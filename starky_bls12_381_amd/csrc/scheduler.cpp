@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "prover.h"
 #include "trace_log.h"
+#include "verify_service.h"
 
 namespace starkhip {
 
@@ -395,7 +396,7 @@ double air_cost(int air) {
 
 namespace {
 
-enum JobKind { JOB_DENSE, JOB_COMPACT, JOB_WITNESS, JOB_COLUMNS };
+enum JobKind { JOB_DENSE, JOB_COMPACT, JOB_WITNESS, JOB_COLUMNS, JOB_VERIFY };
 
 struct Job {
     uint64_t id = 0;
@@ -414,8 +415,11 @@ struct Job {
     std::vector<uint64_t> own_pis, own_rows;  // own_rows: the toy AIR's generator writes plain rows (it does not record)
     bool big = false;
     double cost = 0;  // relative proving cost (air_cost): what the job adds to its pool's load until it is done
+    bool verify = false;  // "verify_proofs" was on when it was submitted: the pool's verifier checks the proof before wait returns it
+    const uint64_t* vproof = nullptr;  // JOB_VERIFY: the caller's proof (never freed here)
+    size_t vwords = 0;
     // result
-    int state = 0;  // 0 queued for generation / proving, 1 running, 2 done
+    int state = 0;  // 0 queued for generation / proving, 1 running, 3 verifying, 2 done
     int rc = STARKHIP_OK;
     uint64_t* proof = nullptr;
     size_t words = 0;
@@ -477,6 +481,14 @@ struct Pool {
     double load = 0;        // sum of air_cost over the jobs that are not done (under mu): what a multi-device handle balances
     unsigned big_open = 0;  // FinalExp-class jobs that are not done (under mu)
     unsigned waiters = 0;   // callers inside pool_wait (under mu): pool_destroy lets them leave before it frees anything
+    // the pool's device verifier (verify_service.h), made at the first verify work (or when "verify_proofs" is switched on in a warmed pool)
+    std::mutex vs_mu;       // creation, submission and shutdown of `vs`; taken before mu, never after it
+    std::unique_ptr<VerifyService> vs;
+    bool vs_closed = false;       // pool_destroy has drained it (under vs_mu)
+    bool verify_proofs = false;   // under mu
+    size_t verify_arena_mb = 1024;  // under mu
+    unsigned long verified_proofs = 0, verify_jobs = 0;  // under mu
+    double vload = 0;       // sum of air_verify_cost over the verify jobs that are not done (under mu)
     std::map<int, int> idle_big, idle_small;                 // idle contexts by the AIR they proved last (under mu)
     unsigned stream_priority = 0;
     bool warm_device_traces = false;  // warm_up == 2: the caller's traces are column-major device memory: no trace buffers are reserved
@@ -501,7 +513,8 @@ struct Pool {
         j->rc = rc;
         j->state = 2;
         j->t[4] = now();
-        load = std::max(0.0, load - j->cost);
+        if (j->kind == JOB_VERIFY) vload = std::max(0.0, vload - j->cost);
+        else load = std::max(0.0, load - j->cost);
         if (j->big && big_open > 0) big_open--;
         cv_done.notify_all();
     }
@@ -520,6 +533,42 @@ struct Pool {
         if (trace_threads_cfg) return (int)trace_threads_cfg;
         if (big_job) return (int)std::min(16u, std::max(1u, cpus * 3 / 4));
         return (int)std::min(4u, std::max(1u, cpus / 4));
+    }
+
+    // a verdict of the pool's verifier: a verify job's code, or a proving job's status once its proof has been checked
+    void on_verdict(Job* j, int code, double t_prelude) {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            if (j->kind == JOB_VERIFY) j->t[3] = std::max(0.0, t_prelude - t0);
+            else verified_proofs++;
+        }
+        finish(j, code);
+    }
+
+    // hands `proof` of job j to the verifier, making it first; false (and *rc) if it cannot be made
+    bool verify_submit(Job* j, const uint64_t* proof, size_t words, int* rc) {
+        std::lock_guard<std::mutex> g(vs_mu);
+        if (vs_closed) {
+            *rc = STARKHIP_ERR_BAD_SHAPE;
+            return false;
+        }
+        if (!vs && (*rc = make_verifier()) != STARKHIP_OK) return false;
+        vs->submit(j->air, j->cfg, proof, words, j);
+        return true;
+    }
+
+    int make_verifier() {  // under vs_mu
+        size_t mb;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            mb = verify_arena_mb;
+        }
+        const unsigned threads = std::min(4u, std::max(1u, cpus / 4));
+        std::unique_ptr<VerifyService> v(new VerifyService(device, mb << 20, hs ? hs->gather_ms : 25.0, threads, gen_nice,
+                                                           [this](void* tag, int code, double tp) { on_verdict((Job*)tag, code, tp); }));
+        const int rc = v->start();
+        if (rc == STARKHIP_OK) vs = std::move(v);
+        return rc;
     }
 
     void generator_loop() {
@@ -738,6 +787,14 @@ struct Pool {
                 j->own_log = nullptr;
                 j->trace = nullptr;
             }
+            // "verify_proofs": the context is free already; the job waits for its verdict on the host blob the caller will receive
+            if (rc == STARKHIP_OK && j->verify) {
+                {
+                    std::lock_guard<std::mutex> g(mu);
+                    j->state = 3;
+                }
+                if (verify_submit(j, j->proof, j->words, &rc)) continue;
+            }
             finish(j, rc);
         }
     }
@@ -826,6 +883,13 @@ void pool_destroy(Pool* p) {
     p->cv_big.notify_all();
     p->cv_small.notify_all();
     for (std::thread& t : p->threads) t.join();  // queued jobs are still run to completion: their callers may be waiting
+    std::unique_ptr<VerifyService> vs;
+    {   // ... and so is queued verify work (it may read the contexts' page-locked blobs: before the contexts go)
+        std::lock_guard<std::mutex> g(p->vs_mu);
+        p->vs_closed = true;
+        vs = std::move(p->vs);
+    }
+    vs.reset();
     {   // every job is done now, so every caller blocked in pool_wait is on its way out: let them go before anything is freed
         std::unique_lock<std::mutex> lk(p->mu);
         p->cv_done.wait(lk, [&] { return p->waiters == 0; });
@@ -854,6 +918,7 @@ static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     }
     j->id = p->next_id++;
     j->t[0] = p->now();
+    j->verify = p->verify_proofs;
     j->cost = air_cost(j->air);
     p->load += j->cost;
     if (j->big) p->big_open++;
@@ -944,6 +1009,18 @@ int pool_wait(Pool* p, uint64_t ticket, uint64_t** proof, size_t* words, starkhi
         if (p->stop) p->cv_done.notify_all();
     }
     const int rc = j->rc;
+    if (j->kind == JOB_VERIFY) {  // a verdict: no proof to hand over, and only the job's submit, prelude start and end times
+        if (info) {
+            memset(info, 0, sizeof *info);
+            info->t_submit = j->t[0];
+            info->t_prove_start = j->t[3];
+            info->t_done = j->t[4];
+        }
+        if (proof) *proof = nullptr;
+        if (words) *words = 0;
+        delete j;
+        return rc;
+    }
     if (info) {
         memcpy(info->phase_ms, j->phase_ms, sizeof info->phase_ms);
         memcpy(info->kernel_ms, j->kernel_ms, sizeof info->kernel_ms);
@@ -1002,6 +1079,100 @@ int pool_stats(Pool* p, starkhip_pool_stats_t* out) {
     out->small_commit_launches = s.small_launches;
     out->small_commit_requests = s.small_requests;
     out->max_merged_commitments = s.max_merged;
+    return STARKHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the pool's verifier
+// What verifying one proof of each AIR costs, for spreading verify work over the pools of a multi-device handle: the CPU verifier's
+// milliseconds per proof, prelude (the Fiat-Shamir replay and the AIR at zeta) plus query rounds (C / 8 permutations per opened trace
+// leaf), from the 48 proofs of eight signatures (profiles/r07_verify_device_split.json: FinalExp 55 + 121, MillerLoop 51 + 159, FP12Mul
+// 32 + 98, PairingPrecomp 20 + 49).  Those two parts are what the device verifier's host and device sides scale with.  ECCAgg was not
+// in that batch: it takes FinalExp's figure (the same 8192 rows, the same query count).
+double air_verify_cost(int air) {
+    switch (air) {
+        case STARKHIP_AIR_FINAL_EXP: return 176.0;
+        case STARKHIP_AIR_ECC_AGGREGATE: return 176.0;
+        case STARKHIP_AIR_MILLER_LOOP: return 209.8;
+        case STARKHIP_AIR_FP12_MUL: return 129.6;
+        case STARKHIP_AIR_PAIRING_PRECOMP: return 68.4;
+        default: return 0.01;
+    }
+}
+
+int pool_set_option(Pool* p, const char* name, long value) {
+    if (!name) return STARKHIP_ERR_BAD_SHAPE;
+    if (strcmp(name, "verify_proofs") == 0) {
+        if (value != 0 && value != 1) return STARKHIP_ERR_BAD_SHAPE;
+        std::lock_guard<std::mutex> g(p->vs_mu);
+        {
+            std::lock_guard<std::mutex> g2(p->mu);
+            p->verify_proofs = value == 1;
+        }
+        if (value == 1 && p->warm && !p->vs && !p->vs_closed) return p->make_verifier();  // a warmed pool allocates now, not in its first proof
+        return STARKHIP_OK;
+    }
+    if (strcmp(name, "verify_arena_mb") == 0) {
+        if (value < 1 || value > (1l << 20)) return STARKHIP_ERR_BAD_SHAPE;
+        std::lock_guard<std::mutex> g(p->vs_mu);
+        if (p->vs) return STARKHIP_ERR_BAD_SHAPE;  // the arena exists already
+        std::lock_guard<std::mutex> g2(p->mu);
+        p->verify_arena_mb = (size_t)value;
+        return STARKHIP_OK;
+    }
+    return STARKHIP_ERR_BAD_SHAPE;
+}
+
+int pool_submit_verify(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* proof, size_t words, uint64_t* ticket) {
+    if (!ticket) return STARKHIP_ERR_BAD_SHAPE;
+    Job* j = new (std::nothrow) Job();
+    if (!j) return STARKHIP_ERR_OOM;
+    j->kind = JOB_VERIFY;
+    j->air = air;
+    j->vproof = proof;
+    j->vwords = words;
+    j->leaf_hash_group = 0;
+    // an id without an AIR gets starkhip_verify's BAD_AIR without the verifier (and without a config to look up)
+    int now_rc = STARKHIP_OK;
+    if (!air_get(air)) now_rc = STARKHIP_ERR_BAD_AIR;
+    else if (cfg) j->cfg = *cfg;
+    else now_rc = starkhip_config_for_air((starkhip_air_t)air, &j->cfg);
+    {
+        std::lock_guard<std::mutex> g(p->mu);
+        if (p->stop) {
+            delete j;
+            return STARKHIP_ERR_BAD_SHAPE;
+        }
+        j->id = p->next_id++;
+        j->t[0] = p->now();
+        j->cost = air_verify_cost(air);
+        p->vload += j->cost;
+        p->verify_jobs++;
+        p->jobs[j->id] = j;
+        *ticket = j->id;
+    }
+    if (now_rc == STARKHIP_OK && p->verify_submit(j, proof, words, &now_rc)) return STARKHIP_OK;
+    p->finish(j, now_rc);
+    return STARKHIP_OK;
+}
+
+int pool_verify_stats(Pool* p, starkhip_pool_verify_stats_t* out) {
+    memset(out, 0, sizeof *out);
+    {
+        std::lock_guard<std::mutex> g(p->vs_mu);
+        if (p->vs) {
+            const VerifyService::Stats s = p->vs->stats();
+            out->rejected = s.rejected;
+            out->device_batches = s.batches;
+            out->upload_ms = s.upload_ms;
+            out->device_ms = s.device_ms;
+            out->prelude_ms = s.prelude_ms;
+            out->prelude_cpu_s = s.prelude_cpu_s;
+            out->arena_bytes = s.arena_bytes;
+        }
+    }
+    std::lock_guard<std::mutex> g(p->mu);
+    out->proofs_checked = p->verified_proofs;
+    out->verify_jobs = p->verify_jobs;
     return STARKHIP_OK;
 }
 
@@ -1169,6 +1340,85 @@ int multipool_wait(MultiPool* mp, uint64_t ticket, uint64_t** proof, size_t* wor
     const int slot = multipool_ticket_slot(mp, ticket);
     if (slot < 0) return STARKHIP_ERR_BAD_SHAPE;
     return pool_wait(mp->pools[(size_t)slot], ticket & (((uint64_t)1 << TICKET_SLOT_SHIFT) - 1), proof, words, info);
+}
+
+int multipool_set_option(MultiPool* mp, const char* name, long value) {
+    int first = STARKHIP_OK;
+    for (Pool* p : mp->pools) {
+        const int rc = pool_set_option(p, name, value);
+        if (rc != STARKHIP_OK && first == STARKHIP_OK) first = rc;
+    }
+    return first;
+}
+
+// verify work goes to the pool with the least outstanding verify cost (air_verify_cost), ties to the lowest slot
+int multipool_submit_verify(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint64_t* proof, size_t words, uint64_t* ticket) {
+    if (!ticket || slot >= (int)mp->pools.size()) return STARKHIP_ERR_BAD_SHAPE;
+    std::lock_guard<std::mutex> g(mp->mu);
+    size_t at = slot >= 0 ? (size_t)slot : 0;
+    if (slot < 0) {
+        double best = 0;
+        for (size_t i = 0; i < mp->pools.size(); i++) {
+            double v;
+            {
+                std::lock_guard<std::mutex> gp(mp->pools[i]->mu);
+                v = mp->pools[i]->vload;
+            }
+            if (i == 0 || v < best) {
+                best = v;
+                at = i;
+            }
+        }
+    }
+    uint64_t inner = 0;
+    const int rc = pool_submit_verify(mp->pools[at], air, cfg, proof, words, &inner);
+    if (rc == STARKHIP_OK) *ticket = ((uint64_t)(at + 1) << TICKET_SLOT_SHIFT) | inner;
+    return rc;
+}
+
+// placement of a verify batch on n_pools idle pools: longest first by air_verify_cost (ties in the caller's order), each to the pool
+// with the least cost so far; order[k] = the k-th proof placed
+void plan_verify(size_t n, const int* airs, size_t n_pools, int* slots, size_t* order) {
+    std::vector<size_t> ord(n);
+    for (size_t i = 0; i < n; i++) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return air_verify_cost(airs[a]) > air_verify_cost(airs[b]); });
+    std::vector<double> load(n_pools, 0.0);
+    for (size_t k = 0; k < n; k++) {
+        const size_t i = ord[k];
+        size_t best = 0;
+        for (size_t s = 1; s < n_pools; s++)
+            if (load[s] < load[best]) best = s;
+        slots[i] = (int)best;
+        load[best] += air_verify_cost(airs[i]);
+        if (order) order[k] = i;
+    }
+}
+
+// starkhip_verify_batch's contract over the handle's devices: every proof a verify job of the pool plan_verify gives it, all submitted
+// (longest first) before the first wait
+int multipool_verify_batch(MultiPool* mp, size_t n, const int* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs, const size_t* words,
+                           int* results) {
+    if (n && (!airs || !cfgs || !proofs || !words || !results)) return STARKHIP_ERR_BAD_SHAPE;
+    std::vector<int> slots(n);
+    std::vector<size_t> order(n);
+    plan_verify(n, airs, mp->pools.size(), slots.data(), order.data());
+    std::vector<uint64_t> tickets(n, 0);
+    int first = STARKHIP_OK;
+    for (size_t i : order) {
+        const int rc = multipool_submit_verify(mp, slots[i], airs[i], &cfgs[i], proofs[i], words[i], &tickets[i]);
+        if (rc != STARKHIP_OK) {
+            tickets[i] = 0;
+            results[i] = rc;
+            if (first == STARKHIP_OK) first = rc;
+        }
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (!tickets[i]) continue;
+        const int rc = multipool_wait(mp, tickets[i], nullptr, nullptr, nullptr);
+        results[i] = rc;
+        if ((rc == STARKHIP_ERR_HIP || rc == STARKHIP_ERR_OOM) && first == STARKHIP_OK) first = rc;  // the device work failed: the call did
+    }
+    return first;
 }
 
 // the plan alone, for tests and for callers that want to see it: slot per job of a batch placed on `n_pools` idle pools

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "airs.h"
@@ -25,16 +26,14 @@
 #include "prover.h"
 #include "scheduler.h"
 #include "verifier.h"
+#include "verify_chunk.h"
 #include "verify_query.h"
 
 namespace starkhip {
-namespace {
 
-struct Item {
-    int code = STARKHIP_OK;
-    bool queries = false;  // the prelude passed: the query rounds decide
-    VerifyPrelude pre;
-};
+const size_t VERIFY_STAGING_HALF = (size_t)32 << 20;  // bytes per page-locked staging half
+
+namespace {
 
 bool query_words_in_range(const uint64_t* proof, const ProofLayout& pl) {
     for (size_t i = pl.off_queries; i < pl.off_final; i++)
@@ -42,56 +41,34 @@ bool query_words_in_range(const uint64_t* proof, const ProofLayout& pl) {
     return true;
 }
 
-// the preludes of a batch on at most 16 host threads (cpu_budget(): the CPUs this process may use)
-void run_preludes(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs, const size_t* words,
-                  std::vector<Item>& items) {
-    items.assign(n, Item());
-    std::atomic<size_t> next(0);
-    auto worker = [&]() {
-        for (size_t i; (i = next.fetch_add(1)) < n;) {
-            Item& it = items[i];
-            int id;  // read as an int: a caller's id need not be one of the enum's values
-            memcpy(&id, &airs[i], sizeof id);
-            const AirInfo* a = air_get(id);
-            if (!a) {
-                it.code = STARKHIP_ERR_BAD_AIR;
-                continue;
-            }
-            if (!proofs[i]) {
-                it.code = STARKHIP_ERR_BAD_SHAPE;
-                continue;
-            }
-            const int rc = verify_prelude(*a, cfgs[i], proofs[i], words[i], false, &it.pre);
-            if (rc == STARKHIP_OK) it.queries = true;
-            else if (rc == STARKHIP_ERR_VERIFY) it.code = query_words_in_range(proofs[i], it.pre.pl) ? STARKHIP_ERR_VERIFY : STARKHIP_ERR_BAD_SHAPE;
-            else it.code = rc;
-        }
-    };
-    const size_t n_threads = std::min<size_t>({(size_t)16, (size_t)std::max(1u, cpu_budget()), n});
-    std::vector<std::thread> pool;
-    for (size_t t = 1; t < n_threads; t++) pool.emplace_back(worker);
-    worker();
-    for (auto& t : pool) t.join();
-}
-
 // A proof's words in the chunk's buffer: [trace cap | quotient cap] then [FRI caps .. final polynomial] of the blob
 size_t head_words(const ProofLayout& pl) { return 8 * pl.ncap; }
 size_t region_words(const ProofLayout& pl) { return head_words(pl) + (pl.off_pow - pl.off_fri_caps); }
-size_t device_bytes(const ProofLayout& pl) {
+
+}  // namespace
+
+void verify_prelude_item(int id, const starkhip_config_t& cfg, const uint64_t* proof, size_t words, VerifyItem* it) {
+    const AirInfo* a = air_get(id);
+    if (!a) {
+        it->code = STARKHIP_ERR_BAD_AIR;
+        return;
+    }
+    if (!proof) {
+        it->code = STARKHIP_ERR_BAD_SHAPE;
+        return;
+    }
+    const int rc = verify_prelude(*a, cfg, proof, words, false, &it->pre);
+    if (rc == STARKHIP_OK) it->queries = true;
+    else if (rc == STARKHIP_ERR_VERIFY) it->code = query_words_in_range(proof, it->pre.pl) ? STARKHIP_ERR_VERIFY : STARKHIP_ERR_BAD_SHAPE;
+    else it->code = rc;
+}
+
+size_t verify_device_bytes(const ProofLayout& pl) {
     const size_t per_query = (2 + pl.L) * (4 * 8 + sizeof(VQLeaf)) + 2 * sizeof(gl2_t) + 8 + 4 + 4;
     return 8 * region_words(pl) + sizeof(gl2_t) * (pl.C + pl.Q) + pl.n_queries * per_query + sizeof(VQProof) + 4;
 }
 
-struct Chunk {
-    std::vector<size_t> ids;  // batch indices of its proofs
-    std::vector<VQProof> proofs;
-    std::vector<VQLeaf> leaves;
-    std::vector<uint32_t> query_proof;
-    std::vector<uint64_t> x_index;
-    size_t words = 0, apow = 0, digests = 0, bytes = 0;
-};
-
-void chunk_add(Chunk& ch, size_t id, const VerifyPrelude& pre) {
+void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     const ProofLayout& pl = pre.pl;
     VQProof P;
     memset(&P, 0, sizeof P);
@@ -139,46 +116,201 @@ void chunk_add(Chunk& ch, size_t id, const VerifyPrelude& pre) {
     }
     ch.proofs.push_back(P);
     ch.ids.push_back(id);
+    ch.alphas.push_back(pre.fri_alpha);
     ch.words += region_words(pl);
     ch.apow += pl.C + pl.Q;
     ch.digests += pl.n_queries * per_q;
-    ch.bytes += device_bytes(pl);
+    ch.bytes += verify_device_bytes(pl);
+}
+
+void verify_chunk_seal(VerifyChunk& ch) {
+    std::stable_sort(ch.leaves.begin(), ch.leaves.end(), [](const VQLeaf& a, const VQLeaf& b) { return a.len > b.len; });
+}
+
+bool verify_bufs_carve(const VerifyChunk& ch, void* base, size_t cap, VerifyDevBufs* b) {
+    size_t at = 0;
+    bool ok = true;
+    auto take = [&](auto** p, size_t count) {
+        using T = std::remove_reference_t<decltype(**p)>;
+        at = (at + 255) & ~(size_t)255;
+        *p = (T*)((char*)base + at);
+        at += std::max<size_t>(count, 1) * sizeof(T);
+        ok = ok && at <= cap;
+    };
+    const size_t nq = ch.query_proof.size(), np = ch.proofs.size();
+    take(&b->words, ch.words);
+    take(&b->apow, ch.apow);
+    take(&b->dig, 4 * ch.digests);
+    take(&b->sums, 2 * nq);
+    take(&b->proofs, np);
+    take(&b->leaves, ch.leaves.size());
+    take(&b->qproof, nq);
+    take(&b->xidx, nq);
+    take(&b->status, nq);
+    take(&b->bad, np);
+    return ok;
+}
+
+void verify_pieces(const VerifyChunk& ch, size_t k, const uint64_t* proof, const ProofLayout& pl, VerifyPiece out[2]) {
+    const size_t base = ch.proofs[k].base;
+    out[0] = VerifyPiece{proof + pl.off_trace_cap, head_words(pl), base};
+    out[1] = VerifyPiece{proof + pl.off_fri_caps, pl.off_pow - pl.off_fri_caps, base + head_words(pl)};
+}
+
+hipError_t VerifyStaging::copy(gl_t* dst, const uint64_t* src, size_t words, bool pinned, hipStream_t st) {
+    if (pinned) return hipMemcpyAsync(dst, src, words * 8, hipMemcpyHostToDevice, st);
+    if (!mem) {
+        if (!lazy) return hipErrorInvalidValue;
+        const hipError_t e = hipHostMalloc(&mem, 2 * VERIFY_STAGING_HALF, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            mem = nullptr;
+            return e;
+        }
+    }
+    for (size_t done = 0; done < words;) {  // pageable: through the two staging halves in turn
+        const size_t w = std::min(words - done, VERIFY_STAGING_HALF / 8);
+        if (used[half]) {
+            const hipError_t e = event_wait_sleeping(sev[half]);  // the copy that last read this half has run
+            if (e != hipSuccess) return e;
+        }
+        uint64_t* s = (uint64_t*)mem + half * (VERIFY_STAGING_HALF / 8);
+        memcpy(s, src + done, w * 8);
+        hipError_t e = hipMemcpyAsync(dst + done, s, w * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventRecord(sev[half], st);
+        if (e != hipSuccess) return e;
+        used[half] = true;
+        half ^= 1;
+        done += w;
+    }
+    return hipSuccess;
+}
+
+hipError_t verify_chunk_upload_descriptors(const VerifyChunk& ch, const VerifyDevBufs& b, hipStream_t st) {
+    hipError_t e = hipMemcpyAsync(b.proofs, ch.proofs.data(), ch.proofs.size() * sizeof(VQProof), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.leaves, ch.leaves.data(), ch.leaves.size() * sizeof(VQLeaf), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.qproof, ch.query_proof.data(), ch.query_proof.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.xidx, ch.x_index.data(), ch.x_index.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(b.bad, 0, ch.proofs.size() * 4, st);
+    return e;
+}
+
+hipError_t verify_chunk_launch(const VerifyChunk& ch, const VerifyDevBufs& b, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < ch.proofs.size() && e == hipSuccess; k++) {
+        const VQProof& P = ch.proofs[k];
+        e = launch_ext_powers(b.apow + P.apow, ch.alphas[k], P.C + P.Q, st);
+    }
+    if (e == hipSuccess) e = launch_verify_range(b.words, b.proofs, ch.proofs.size(), b.bad, st);
+    if (e == hipSuccess) e = launch_verify_leaf_digests(b.words, b.leaves, ch.leaves.size(), b.dig, st);
+    if (e == hipSuccess) e = launch_verify_combine(b.words, b.proofs, b.qproof, ch.query_proof.size(), b.apow, b.sums, st);
+    if (e == hipSuccess) e = launch_verify_queries(b.words, b.proofs, b.qproof, b.xidx, ch.query_proof.size(), b.dig, b.sums, b.status, st);
+    return e;
+}
+
+void verify_chunk_codes(const VerifyChunk& ch, const uint32_t* status, const uint32_t* bad, const size_t* n_queries, int* codes) {
+    for (size_t k = 0; k < ch.ids.size(); k++) {
+        const VQProof& P = ch.proofs[k];
+        uint32_t any = 0;
+        for (size_t q = 0; q < n_queries[k]; q++) any |= status[P.first_query + q];
+        codes[k] = bad[k] ? STARKHIP_ERR_BAD_SHAPE : any ? STARKHIP_ERR_VERIFY : STARKHIP_OK;
+    }
+}
+
+void verify_host_range(const gl_t* W, const VQProof* proofs, size_t n, uint32_t* bad) {
+    for (size_t k = 0; k < n; k++) {
+        const VQProof& P = proofs[k];
+        for (uint64_t i = P.base + P.off_queries; i < P.base + P.off_final; i++) bad[k] |= W[i] >= GL_P;
+    }
+}
+
+void verify_host_ext_powers(gl2_t* out, gl2_t alpha, size_t n) {
+    gl2_t a = gl2_one();
+    for (size_t i = 0; i < n; i++, a = gl2_mul(a, alpha)) out[i] = a;
+}
+
+void verify_host_leaf_digests(const gl_t* W, const VQLeaf* leaves, size_t n, gl_t* dig) {
+    for (size_t k = 0; k < n; k++) {  // hash_or_noop
+        const VQLeaf& lf = leaves[k];
+        gl_t* out = dig + 4 * (size_t)lf.slot;
+        const gl_t* in = W + lf.off;
+        if (lf.len <= 4) {
+            for (uint32_t i = 0; i < 4; i++) out[i] = i < lf.len ? in[i] : 0;
+            continue;
+        }
+        gl_t s[12] = {0};
+        for (uint32_t off = 0; off < lf.len; off += 8) {
+            for (uint32_t i = 0; i < 8 && off + i < lf.len; i++) s[i] = in[off + i];
+            poseidon_permute_host(s);
+        }
+        for (int i = 0; i < 4; i++) out[i] = s[i];
+    }
+}
+
+void verify_host_combine(const gl_t* W, const VQProof* proofs, const uint32_t* query_proof, size_t n_queries, const gl2_t* apow, gl2_t* sums) {
+    for (size_t g = 0; g < n_queries; g++) {
+        const VQProof& P = proofs[query_proof[g]];
+        const uint32_t qi = (uint32_t)g - P.first_query;
+        const gl_t* tleaf = W + P.base + P.off_queries + (uint64_t)qi * P.query_words;
+        const gl_t* qleaf = tleaf + P.C + 4 * (P.log_N - P.cap_h);
+        gl2_t st = gl2_zero(), sq = gl2_zero();
+        for (uint32_t c = 0; c < P.C; c++) st = gl2_add(st, gl2_mul_base(apow[P.apow + c], tleaf[c]));
+        for (uint32_t q = 0; q < P.Q; q++) sq = gl2_add(sq, gl2_mul_base(apow[P.apow + P.C + q], qleaf[q]));
+        sums[2 * g] = gl2_add(st, sq);
+        sums[2 * g + 1] = st;
+    }
+}
+
+void verify_host_queries(const gl_t* W, const VQProof* proofs, const uint32_t* query_proof, const uint64_t* x_index, size_t n_queries,
+                         const gl_t* dig, const gl2_t* sums, uint32_t* status) {
+    for (size_t g = 0; g < n_queries; g++) {
+        const VQProof& P = proofs[query_proof[g]];
+        const uint32_t qi = (uint32_t)g - P.first_query;
+        status[g] = vq_check_query(P, W + P.base, dig + 4 * ((size_t)P.first_digest + (size_t)qi * (2 + P.L)), sums[2 * g], sums[2 * g + 1],
+                                   x_index[g], qi);
+    }
+}
+
+namespace {
+
+// the preludes of a batch on at most 16 host threads (cpu_budget(): the CPUs this process may use)
+void run_preludes(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs, const size_t* words,
+                  std::vector<VerifyItem>& items) {
+    items.assign(n, VerifyItem());
+    std::atomic<size_t> next(0);
+    auto worker = [&]() {
+        for (size_t i; (i = next.fetch_add(1)) < n;) {
+            int id;  // read as an int: a caller's id need not be one of the enum's values
+            memcpy(&id, &airs[i], sizeof id);
+            verify_prelude_item(id, cfgs[i], proofs[i], words[i], &items[i]);
+        }
+    };
+    const size_t n_threads = std::min<size_t>({(size_t)16, (size_t)std::max(1u, cpu_budget()), n});
+    std::vector<std::thread> pool;
+    for (size_t t = 1; t < n_threads; t++) pool.emplace_back(worker);
+    worker();
+    for (auto& t : pool) t.join();
 }
 
 // proofs in batch order, a new chunk whenever the next proof would take the current one past `cap` bytes (a proof bigger than
 // the cap gets a chunk of its own); the leaves of a chunk longest first
-std::vector<Chunk> make_chunks(const std::vector<Item>& items, size_t cap) {
-    std::vector<Chunk> out;
+std::vector<VerifyChunk> make_chunks(const std::vector<VerifyItem>& items, size_t cap) {
+    std::vector<VerifyChunk> out;
     for (size_t i = 0; i < items.size(); i++) {
         if (!items[i].queries) continue;
-        if (out.empty() || (!out.back().ids.empty() && out.back().bytes + device_bytes(items[i].pre.pl) > cap)) out.emplace_back();
-        chunk_add(out.back(), i, items[i].pre);
+        if (out.empty() || (!out.back().ids.empty() && out.back().bytes + verify_device_bytes(items[i].pre.pl) > cap)) out.emplace_back();
+        verify_chunk_add(out.back(), i, items[i].pre);
     }
-    for (Chunk& ch : out)
-        std::stable_sort(ch.leaves.begin(), ch.leaves.end(), [](const VQLeaf& a, const VQLeaf& b) { return a.len > b.len; });
+    for (VerifyChunk& ch : out) verify_chunk_seal(ch);
     return out;
 }
 
-// the two pieces of proof `id`'s region: (source, words, destination word)
-struct Piece {
-    const uint64_t* src;
-    size_t words, dst;
-};
-void pieces(const Chunk& ch, size_t k, const uint64_t* proof, const ProofLayout& pl, Piece out[2]) {
-    const size_t base = ch.proofs[k].base;
-    out[0] = Piece{proof + pl.off_trace_cap, head_words(pl), base};
-    out[1] = Piece{proof + pl.off_fri_caps, pl.off_pow - pl.off_fri_caps, base + head_words(pl)};
-}
-
 // the per-proof results of a chunk from its query statuses and range flags
-void chunk_results(const Chunk& ch, const std::vector<uint32_t>& status, const std::vector<uint32_t>& bad, std::vector<Item>& items) {
-    for (size_t k = 0; k < ch.ids.size(); k++) {
-        const VQProof& P = ch.proofs[k];
-        const size_t nq = items[ch.ids[k]].pre.pl.n_queries;
-        uint32_t any = 0;
-        for (size_t q = 0; q < nq; q++) any |= status[P.first_query + q];
-        items[ch.ids[k]].code = bad[k] ? STARKHIP_ERR_BAD_SHAPE : any ? STARKHIP_ERR_VERIFY : STARKHIP_OK;
-    }
+void chunk_results(const VerifyChunk& ch, const std::vector<uint32_t>& status, const std::vector<uint32_t>& bad, std::vector<VerifyItem>& items) {
+    std::vector<size_t> nq(ch.ids.size());
+    std::vector<int> codes(ch.ids.size());
+    for (size_t k = 0; k < ch.ids.size(); k++) nq[k] = items[ch.ids[k]].pre.pl.n_queries;
+    verify_chunk_codes(ch, status.data(), bad.data(), nq.data(), codes.data());
+    for (size_t k = 0; k < ch.ids.size(); k++) items[ch.ids[k]].code = codes[k];
 }
 
 double process_cpu_s() {
@@ -196,16 +328,16 @@ bool call_args_ok(size_t n, const starkhip_air_t* airs, const starkhip_config_t*
 // ---- device memory of one call, released on every way out
 struct DevMem {
     std::vector<void*> bufs;
-    void* staging = nullptr;
+    VerifyStaging staging;
     hipStream_t st = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}, sev[2] = {nullptr, nullptr};
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     ~DevMem() {
         if (st) (void)hipStreamSynchronize(st);
         for (void* b : bufs) (void)hipFree(b);
-        if (staging) (void)hipHostFree(staging);
+        if (staging.mem) (void)hipHostFree(staging.mem);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : sev)
+        for (hipEvent_t e : staging.sev)
             if (e) (void)hipEventDestroy(e);
         if (st) (void)hipStreamDestroy(st);
     }
@@ -218,8 +350,6 @@ struct DevMem {
         return e;
     }
 };
-
-const size_t STAGING_HALF = (size_t)32 << 20;  // bytes per page-locked staging half
 
 }  // namespace
 
@@ -239,14 +369,14 @@ int verify_batch_device(Ctx* c, size_t n, const starkhip_air_t* airs, const star
     double* tm = ctx_verify_timings(c);
     for (int i = 0; i < 4; i++) tm[i] = 0;
     const double cpu0 = process_cpu_s(), t0 = wall_ms();
-    std::vector<Item> items;
+    std::vector<VerifyItem> items;
     run_preludes(n, airs, cfgs, proofs, proof_words, items);
     tm[0] = wall_ms() - t0;
-    const std::vector<Chunk> chunks = make_chunks(items, (size_t)ctx_verify_chunk_mb(c) << 20);
+    const std::vector<VerifyChunk> chunks = make_chunks(items, (size_t)ctx_verify_chunk_mb(c) << 20);
     if (!chunks.empty()) {
         VHIP(hipSetDevice(ctx_device(c)));
         size_t max_words = 0, max_apow = 0, max_dig = 0, max_q = 0, max_p = 0, max_leaves = 0;
-        for (const Chunk& ch : chunks) {
+        for (const VerifyChunk& ch : chunks) {
             max_words = std::max(max_words, ch.words);
             max_apow = std::max(max_apow, ch.apow);
             max_dig = std::max(max_dig, ch.digests);
@@ -255,74 +385,39 @@ int verify_batch_device(Ctx* c, size_t n, const starkhip_air_t* airs, const star
             max_leaves = std::max(max_leaves, ch.leaves.size());
         }
         DevMem m;
-        gl_t *d_words, *d_dig;
-        gl2_t *d_apow, *d_sums;
-        VQProof* d_proofs;
-        VQLeaf* d_leaves;
-        uint32_t *d_qproof, *d_status, *d_bad;
-        uint64_t* d_xidx;
-        VHIP(m.alloc(&d_words, max_words));
-        VHIP(m.alloc(&d_apow, max_apow));
-        VHIP(m.alloc(&d_dig, 4 * max_dig));
-        VHIP(m.alloc(&d_sums, 2 * max_q));
-        VHIP(m.alloc(&d_proofs, max_p));
-        VHIP(m.alloc(&d_leaves, max_leaves));
-        VHIP(m.alloc(&d_qproof, max_q));
-        VHIP(m.alloc(&d_xidx, max_q));
-        VHIP(m.alloc(&d_status, max_q));
-        VHIP(m.alloc(&d_bad, max_p));
+        VerifyDevBufs b;
+        VHIP(m.alloc(&b.words, max_words));
+        VHIP(m.alloc(&b.apow, max_apow));
+        VHIP(m.alloc(&b.dig, 4 * max_dig));
+        VHIP(m.alloc(&b.sums, 2 * max_q));
+        VHIP(m.alloc(&b.proofs, max_p));
+        VHIP(m.alloc(&b.leaves, max_leaves));
+        VHIP(m.alloc(&b.qproof, max_q));
+        VHIP(m.alloc(&b.xidx, max_q));
+        VHIP(m.alloc(&b.status, max_q));
+        VHIP(m.alloc(&b.bad, max_p));
         VHIP(hipStreamCreateWithFlags(&m.st, hipStreamNonBlocking));
         for (hipEvent_t& e : m.ev) VHIP(hipEventCreate(&e));
-        for (hipEvent_t& e : m.sev) VHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        bool used[2] = {false, false};
-        unsigned half = 0;
+        for (hipEvent_t& e : m.staging.sev) VHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         std::vector<uint32_t> status, bad;
-        for (const Chunk& ch : chunks) {
+        for (const VerifyChunk& ch : chunks) {
             VHIP(hipEventRecord(m.ev[0], m.st));
-            VHIP(hipMemcpyAsync(d_proofs, ch.proofs.data(), ch.proofs.size() * sizeof(VQProof), hipMemcpyHostToDevice, m.st));
-            VHIP(hipMemcpyAsync(d_leaves, ch.leaves.data(), ch.leaves.size() * sizeof(VQLeaf), hipMemcpyHostToDevice, m.st));
-            VHIP(hipMemcpyAsync(d_qproof, ch.query_proof.data(), ch.query_proof.size() * 4, hipMemcpyHostToDevice, m.st));
-            VHIP(hipMemcpyAsync(d_xidx, ch.x_index.data(), ch.x_index.size() * 8, hipMemcpyHostToDevice, m.st));
-            VHIP(hipMemsetAsync(d_bad, 0, ch.proofs.size() * 4, m.st));
+            VHIP(verify_chunk_upload_descriptors(ch, b, m.st));
             for (size_t k = 0; k < ch.ids.size(); k++) {
                 const size_t id = ch.ids[k];
-                Piece pc[2];
-                pieces(ch, k, proofs[id], items[id].pre.pl, pc);
+                VerifyPiece pc[2];
+                verify_pieces(ch, k, proofs[id], items[id].pre.pl, pc);
                 const bool pinned = blob_is_pinned(proofs[id], proof_words[id] * 8);
-                for (const Piece& p : pc) {
-                    if (pinned) {
-                        VHIP(hipMemcpyAsync(d_words + p.dst, p.src, p.words * 8, hipMemcpyHostToDevice, m.st));
-                        continue;
-                    }
-                    if (!m.staging) VHIP(hipHostMalloc(&m.staging, 2 * STAGING_HALF, hipHostMallocDefault));
-                    for (size_t done = 0; done < p.words;) {  // pageable: through the two staging halves in turn
-                        const size_t w = std::min(p.words - done, STAGING_HALF / 8);
-                        if (used[half]) VHIP(event_wait_sleeping(m.sev[half]));  // the copy that last read this half has run
-                        uint64_t* s = (uint64_t*)m.staging + half * (STAGING_HALF / 8);
-                        memcpy(s, p.src + done, w * 8);
-                        VHIP(hipMemcpyAsync(d_words + p.dst + done, s, w * 8, hipMemcpyHostToDevice, m.st));
-                        VHIP(hipEventRecord(m.sev[half], m.st));
-                        used[half] = true;
-                        half ^= 1;
-                        done += w;
-                    }
-                }
+                for (const VerifyPiece& p : pc) VHIP(m.staging.copy(b.words + p.dst, p.src, p.words, pinned, m.st));
             }
             VHIP(hipEventRecord(m.ev[1], m.st));
-            for (size_t k = 0; k < ch.ids.size(); k++) {
-                const VQProof& P = ch.proofs[k];
-                VHIP(launch_ext_powers(d_apow + P.apow, items[ch.ids[k]].pre.fri_alpha, P.C + P.Q, m.st));
-            }
-            VHIP(launch_verify_range(d_words, d_proofs, ch.proofs.size(), d_bad, m.st));
-            VHIP(launch_verify_leaf_digests(d_words, d_leaves, ch.leaves.size(), d_dig, m.st));
-            VHIP(launch_verify_combine(d_words, d_proofs, d_qproof, ch.query_proof.size(), d_apow, d_sums, m.st));
-            VHIP(launch_verify_queries(d_words, d_proofs, d_qproof, d_xidx, ch.query_proof.size(), d_dig, d_sums, d_status, m.st));
+            VHIP(verify_chunk_launch(ch, b, m.st));
             VHIP(hipEventRecord(m.ev[2], m.st));
             VHIP(event_wait_sleeping(m.ev[2]));
             status.resize(ch.query_proof.size());
             bad.resize(ch.proofs.size());
-            VHIP(hipMemcpy(status.data(), d_status, status.size() * 4, hipMemcpyDeviceToHost));
-            VHIP(hipMemcpy(bad.data(), d_bad, bad.size() * 4, hipMemcpyDeviceToHost));
+            VHIP(hipMemcpy(status.data(), b.status, status.size() * 4, hipMemcpyDeviceToHost));
+            VHIP(hipMemcpy(bad.data(), b.bad, bad.size() * 4, hipMemcpyDeviceToHost));
             float up = 0, dev = 0;
             VHIP(hipEventElapsedTime(&up, m.ev[0], m.ev[1]));
             VHIP(hipEventElapsedTime(&dev, m.ev[1], m.ev[2]));
@@ -341,50 +436,25 @@ int verify_batch_device(Ctx* c, size_t n, const starkhip_air_t* airs, const star
 int verify_batch_replay(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
                         const size_t* proof_words, int* results) {
     if (!call_args_ok(n, airs, cfgs, proofs, proof_words, results)) return STARKHIP_ERR_BAD_SHAPE;
-    std::vector<Item> items;
+    std::vector<VerifyItem> items;
     run_preludes(n, airs, cfgs, proofs, proof_words, items);
-    for (const Chunk& ch : make_chunks(items, (size_t)1024 << 20)) {
+    for (const VerifyChunk& ch : make_chunks(items, (size_t)1024 << 20)) {
         std::vector<gl_t> W(ch.words);
         std::vector<uint32_t> bad(ch.proofs.size(), 0), status(ch.query_proof.size(), 0);
         std::vector<gl2_t> apow(ch.apow), sums(2 * ch.query_proof.size());
         std::vector<gl_t> dig(4 * ch.digests);
         for (size_t k = 0; k < ch.ids.size(); k++) {
             const size_t id = ch.ids[k];
-            const VQProof& P = ch.proofs[k];
-            Piece pc[2];
-            pieces(ch, k, proofs[id], items[id].pre.pl, pc);
-            for (const Piece& p : pc) memcpy(W.data() + p.dst, p.src, p.words * 8);
-            for (uint64_t i = P.base + P.off_queries; i < P.base + P.off_final; i++) bad[k] |= W[i] >= GL_P;
-            gl2_t a = gl2_one();
-            for (size_t i = 0; i < (size_t)P.C + P.Q; i++, a = gl2_mul(a, items[id].pre.fri_alpha)) apow[P.apow + i] = a;
+            VerifyPiece pc[2];
+            verify_pieces(ch, k, proofs[id], items[id].pre.pl, pc);
+            for (const VerifyPiece& p : pc) memcpy(W.data() + p.dst, p.src, p.words * 8);
+            verify_host_ext_powers(apow.data() + ch.proofs[k].apow, ch.alphas[k], (size_t)ch.proofs[k].C + ch.proofs[k].Q);
         }
-        for (const VQLeaf& lf : ch.leaves) {  // hash_or_noop
-            gl_t* out = dig.data() + 4 * (size_t)lf.slot;
-            const gl_t* in = W.data() + lf.off;
-            if (lf.len <= 4) {
-                for (uint32_t i = 0; i < 4; i++) out[i] = i < lf.len ? in[i] : 0;
-                continue;
-            }
-            gl_t s[12] = {0};
-            for (uint32_t off = 0; off < lf.len; off += 8) {
-                for (uint32_t i = 0; i < 8 && off + i < lf.len; i++) s[i] = in[off + i];
-                poseidon_permute_host(s);
-            }
-            for (int i = 0; i < 4; i++) out[i] = s[i];
-        }
-        for (size_t g = 0; g < ch.query_proof.size(); g++) {
-            const VQProof& P = ch.proofs[ch.query_proof[g]];
-            const uint32_t qi = (uint32_t)g - P.first_query;
-            const gl_t* tleaf = W.data() + P.base + P.off_queries + (uint64_t)qi * P.query_words;
-            const gl_t* qleaf = tleaf + P.C + 4 * (P.log_N - P.cap_h);
-            gl2_t st = gl2_zero(), sq = gl2_zero();
-            for (uint32_t c = 0; c < P.C; c++) st = gl2_add(st, gl2_mul_base(apow[P.apow + c], tleaf[c]));
-            for (uint32_t q = 0; q < P.Q; q++) sq = gl2_add(sq, gl2_mul_base(apow[P.apow + P.C + q], qleaf[q]));
-            sums[2 * g] = gl2_add(st, sq);
-            sums[2 * g + 1] = st;
-            status[g] = vq_check_query(P, W.data() + P.base, dig.data() + 4 * ((size_t)P.first_digest + (size_t)qi * (2 + P.L)), sums[2 * g],
-                                       sums[2 * g + 1], ch.x_index[g], qi);
-        }
+        verify_host_range(W.data(), ch.proofs.data(), ch.proofs.size(), bad.data());
+        verify_host_leaf_digests(W.data(), ch.leaves.data(), ch.leaves.size(), dig.data());
+        verify_host_combine(W.data(), ch.proofs.data(), ch.query_proof.data(), ch.query_proof.size(), apow.data(), sums.data());
+        verify_host_queries(W.data(), ch.proofs.data(), ch.query_proof.data(), ch.x_index.data(), ch.query_proof.size(), dig.data(), sums.data(),
+                            status.data());
         chunk_results(ch, status, bad, items);
     }
     for (size_t i = 0; i < n; i++) results[i] = items[i].code;

@@ -54,6 +54,8 @@ def main():
     ap.add_argument("--gather-ms", type=float, default=0.0, help="pool: how long a merged commitment waits for stragglers (0 = default)")
     ap.add_argument("--collect", action="store_true", help="N > 1: gather every proof on every rank afterwards (raw buffers) and check all signatures")
     ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--verify-pool", action="store_true", help="pool driver: every proof is checked by the pool's device verifier before wait "
+                    "returns it, inside the timed region (\"verify_proofs\"); adds pool_verify, the verifier's stats")
     ap.add_argument("--verify-device", action="store_true", help="also verify the last step's proofs in one starkhip_verify_batch (query rounds on "
                     "the GPU): adds verify_device_s and verify_device_cpu_s beside verify_s, the host verifier's time")
     args = ap.parse_args()
@@ -88,7 +90,8 @@ def main():
         big = max(1, args.big_inflight if args.batch > 1 else 1)
         small = args.small_inflight if args.small_inflight > 0 else 5
         provers = S.ProofPool(local_rank, big_contexts=big, small_contexts=small, generator_threads=args.gen_threads,
-                              trace_threads=args.trace_threads, commit_policy=args.policy, gather_ms=args.gather_ms, stream_priority=args.priority, warm_up=1)
+                              trace_threads=args.trace_threads, commit_policy=args.policy, gather_ms=args.gather_ms, stream_priority=args.priority, warm_up=1,
+                              verify_proofs=args.verify_pool)
         all_provers = [provers]
     elif args.small_inflight > 0:
         provers = {"big": [S.Prover(local_rank) for _ in range(max(1, args.big_inflight))],
@@ -133,6 +136,7 @@ def main():
         vp.close()
         if any(codes):
             raise SystemExit("device verifier rejected %d of %d proofs" % (sum(1 for c in codes if c), len(codes)))
+    pool_verify = provers.verify_stats() if (args.driver == "pool" and args.verify_pool) else None
     merged = G.collect_results(dist, results, device=dev) if (dist is not None and args.collect) else results
     verdicts = G.check_signatures(merged, sigs, natives, args.batch)
     checked, valid = len(verdicts), sum(verdicts.values())
@@ -157,6 +161,8 @@ def main():
         }
         if device_verify is not None:
             out.update(device_verify)
+        if pool_verify is not None:
+            out["pool_verify"] = pool_verify
         print(json.dumps(out), flush=True)
     for pv in all_provers:
         pv.close()

@@ -15,6 +15,9 @@
 //   signature_demo --batch 8 --verify-on device
 //                                       also verifies the last step's proofs with starkhip_verify_batch (query rounds on the GPU) and
 //                                       adds verify_device_s and verify_device_cpu_s beside verify_s (default: --verify-on host)
+//   signature_demo --batch 8 --verify-on pool
+//                                       every proof is checked by the pool's device verifier before wait returns it, inside the timed
+//                                       region ("verify_proofs"); the JSON line's pool_verify and cpu_s_per_signature say what it cost
 // Exit code 0 = every proof verified, the public inputs chain, and final_exponentiate(ml1 * ml2) == 1 for every signature.
 // Operand file: B records of 120 little-endian u32 limbs -- pk x, y (12 each), H(m) x, y (24 each), signature x, y (24 each);
 // Z = (1, 0) is implied (tools/make_signature_operands.py derives them from the reference vector).  Build: make demo
@@ -22,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <ctime>
 #include <memory>
 #include <string>
 
@@ -75,7 +79,7 @@ static double seconds_since(std::chrono::steady_clock::time_point t0) { return s
 
 int main(int argc, char** argv) {
     size_t batch = 0, steps = 3, warmup = 1, pipeline = 1;
-    bool use_pool = false, timeline = false, digests = false, verify_on_device = false;
+    bool use_pool = false, timeline = false, digests = false, verify_on_device = false, verify_in_pool = false;
     std::vector<int> devices;
     const char* operands = nullptr;
     starkhip_pool_config_t cfg;
@@ -112,8 +116,9 @@ int main(int argc, char** argv) {
         } else if (a == "--digests") digests = true;
         else if (a == "--verify-on") {  // host (default): starkhip_verify per proof; device: also starkhip_verify_batch, timed beside it
             const std::string v = val();
-            if (v != "host" && v != "device") { fprintf(stderr, "signature_demo: --verify-on wants host or device\n"); return 2; }
+            if (v != "host" && v != "device" && v != "pool") { fprintf(stderr, "signature_demo: --verify-on wants host, device or pool\n"); return 2; }
             verify_on_device = v == "device";
+            verify_in_pool = v == "pool";
         }
         else {
             fprintf(stderr, "signature_demo: unknown option %s\n", a.c_str());
@@ -149,13 +154,18 @@ int main(int argc, char** argv) {
         starkhip_driver::tune_host_allocator();
         std::unique_ptr<starkhip_driver::Pool> pool_owner(devices.empty() ? new starkhip_driver::Pool(cfg) : new starkhip_driver::Pool(devices, cfg));
         starkhip_driver::Pool& pool = *pool_owner;
+        if (verify_in_pool) pool.set_option("verify_proofs", 1);  // every proof checked by the pool's device verifier inside the timed region
+        const starkhip_driver::VerifyMode in_timing = verify_in_pool ? starkhip_driver::VerifyOn::pool : starkhip_driver::VerifyOn::none;
+        double host_cpu0[3];
+        starkhip_host_cpu_seconds(host_cpu0);
+        const double proc_cpu0 = (double)clock() / CLOCKS_PER_SEC;
         std::vector<SignatureProofs> proofs;
         double total = 0, best = 1e30;
         std::string step_ms;
         if (pipeline == 1) {
             for (size_t k = 0; k < warmup + steps; k++) {
                 const auto t0 = std::chrono::steady_clock::now();
-                proofs = starkhip_driver::prove_batch(pool, sigs, /*verify=*/false);
+                proofs = starkhip_driver::prove_batch(pool, sigs, in_timing);
                 const double sec = seconds_since(t0);
                 if (k >= warmup) {
                     total += sec;
@@ -177,7 +187,7 @@ int main(int argc, char** argv) {
             };
             auto wait_batch = [&]() {
                 std::vector<SignatureProofs> out;
-                for (auto& t : flying.front()) out.push_back(starkhip_driver::wait_signature(pool, t, false));
+                for (auto& t : flying.front()) out.push_back(starkhip_driver::wait_signature(pool, t, in_timing));
                 flying.erase(flying.begin());
                 return out;
             };
@@ -199,6 +209,22 @@ int main(int argc, char** argv) {
             while (!flying.empty()) proofs = wait_batch();  // drain (untimed)
         }
         const double per_step = total / (steps ? steps : 1);
+        // host CPU seconds per signature over every step (warm-up included), by role; with --verify-on pool also the verifier's
+        std::string cpu_json;
+        {
+            double host_cpu1[3];
+            starkhip_host_cpu_seconds(host_cpu1);
+            const double sig_count = (double)batch * (double)(warmup + steps + (pipeline > 1 ? pipeline : 0));
+            const starkhip_pool_verify_stats_t vs = pool.verify_stats();
+            char buf[640];
+            snprintf(buf, sizeof buf, "\"cpu_s_per_signature\": {\"process\": %.3f, \"recording\": %.3f, \"prover_threads\": %.3f, \"verify_preludes\": %.3f}, "
+                     "\"pool_verify\": {\"proofs_checked\": %lu, \"rejected\": %lu, \"device_batches\": %lu, \"upload_ms\": %.1f, \"device_ms\": %.1f, "
+                     "\"prelude_ms\": %.1f, \"prelude_cpu_s\": %.3f, \"arena_mb\": %.0f}, ",
+                     ((double)clock() / CLOCKS_PER_SEC - proc_cpu0) / sig_count, (host_cpu1[0] - host_cpu0[0]) / sig_count, (host_cpu1[1] - host_cpu0[1]) / sig_count,
+                     vs.prelude_cpu_s / sig_count, vs.proofs_checked, vs.rejected, vs.device_batches, vs.upload_ms, vs.device_ms, vs.prelude_ms, vs.prelude_cpu_s,
+                     (double)vs.arena_bytes / (1 << 20));
+            cpu_json = buf;
+        }
         // untimed: what the reference does after each prove (verify_stark_proof) and what its recursion enforces on the public inputs
         size_t verified = 0, ok = 0;
         const auto tv = std::chrono::steady_clock::now();
@@ -231,6 +257,7 @@ int main(int argc, char** argv) {
             device_json = buf;
             device_block_s = seconds_since(tb);
         }
+        device_json += cpu_json;
         if (timeline) {
             double t0 = 1e300;
             for (const SignatureProofs& s : proofs)
