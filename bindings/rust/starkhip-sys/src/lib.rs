@@ -141,6 +141,12 @@ extern "C" {
     pub fn starkhip_air_constraint_degree(air: Air) -> c_int;
     pub fn starkhip_air_num_constraints(air: Air) -> c_int;
     pub fn starkhip_air_default_rows(air: Air) -> c_int;
+    // User-defined AIRs.  A registered AIR's id is a plain c_int (STARKHIP_AIR_CUSTOM_BASE and up): the `Air` enum names the built-in
+    // AIRs only, so the entry points that take `Air` cannot carry one.
+    pub fn starkhip_air_check_program(blob: *const u64, words: usize, why: *mut c_char, why_len: usize) -> c_int;
+    pub fn starkhip_air_register(blob: *const u64, words: usize, name: *const c_char, default_rows: u32, id_out: *mut c_int) -> c_int;
+    pub fn starkhip_check_trace(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                on_device: c_int, public_inputs: *const u64, violations: *mut u64, first: *mut u64) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

@@ -48,13 +48,26 @@ typedef struct {
     uint32_t num_query_rounds;   /* 84  */
 } starkhip_config_t;
 
+/* Ids of AIRs registered at run time (starkhip_air_register): BASE, BASE + 1, ... in registration order, never reused; at most
+ * CAPACITY of them per process */
+#define STARKHIP_AIR_CUSTOM_BASE 1024
+#define STARKHIP_AIR_CUSTOM_CAPACITY 4096
+/* limits of a registered constraint program (starkhip_air_check_program); the five built-in AIRs are far inside them
+ * (MillerLoop: 97 330 columns, ECCAgg: 12 824 public inputs, FinalExp: 2.4 M code words) */
+#define STARKHIP_AIR_MAX_COLUMNS (1u << 20)
+#define STARKHIP_AIR_MAX_PUBLIC_INPUTS 65535u /* a public-input index travels in 16 bits of a device op (quotient_ops.h) */
+#define STARKHIP_AIR_MAX_CODE_WORDS (1u << 26)
+#define STARKHIP_AIR_MAX_DEGREE 8u /* 4 gates + 3 factors + 1 for a first / last-row constraint: the most a program can reach */
+
 typedef enum {
     STARKHIP_AIR_FP12_MUL = 0,
     STARKHIP_AIR_PAIRING_PRECOMP = 1,
     STARKHIP_AIR_MILLER_LOOP = 2,
     STARKHIP_AIR_FINAL_EXP = 3,
     STARKHIP_AIR_ECC_AGGREGATE = 4, /* ECCAggStark: sum of the 512 sync-committee keys whose bit is set (src/ecc_aggregate.rs) */
-    STARKHIP_AIR_TEST_FIBONACCI = 100 /* 2-column toy AIR used by the unit tests */
+    STARKHIP_AIR_TEST_FIBONACCI = 100, /* 2-column toy AIR used by the unit tests */
+    /* widens the enum's range over the ids of registered AIRs (starkhip_air_register), which C++ callers cast to starkhip_air_t */
+    STARKHIP_AIR_CUSTOM_LAST = (STARKHIP_AIR_CUSTOM_BASE + STARKHIP_AIR_CUSTOM_CAPACITY - 1)
 } starkhip_air_t;
 
 enum {
@@ -94,6 +107,28 @@ int starkhip_air_program(starkhip_air_t air, const uint64_t** blob, size_t* word
  * are base-field.  Host only. */
 int starkhip_air_eval_frame(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
                             const uint64_t masks[8], const uint64_t* alphas, int n_alpha, uint64_t* acc_out);
+
+/* --- user-defined AIRs ------------------------------------------------------------------
+ * A starky user's own `impl Stark` reaches the library as its constraint program: the blob starkhip_air_program returns (format:
+ * starky_bls12_381_amd/csrc/air_ir.h and INTEGRATION.md; starky_bls12_381_amd/air_builder.py builds one).  starkhip_air_check_program
+ * is the validator every registration runs: OK, or STARKHIP_ERR_BAD_AIR with the reason in `why` (NUL-terminated, truncated to
+ * why_len; why may be NULL).  What it accepts cannot make a kernel, the plan builder or a verifier address outside its buffers. */
+int starkhip_air_check_program(const uint64_t* blob, size_t words, char* why, size_t why_len);
+/* Validates and registers a program; *id_out is its id from then on, for every entry point that takes an AIR (prove, the pools,
+ * verify, verify_batch, the queries above, starkhip_check_trace).  The same blob again: the same id (its first name and rows stay).
+ * name may be NULL; default_rows is 0 or a power of two in 2..8192 (what starkhip_air_default_rows reports).  BAD_AIR for a program
+ * the validator refuses or a full registry (STARKHIP_AIR_CUSTOM_CAPACITY), BAD_SHAPE for bad arguments.  Thread-safe.  A registered
+ * AIR has no trace generator: starkhip_pool_submit_witness and the witness batch refuse it with BAD_AIR.  Its config
+ * (starkhip_config_for_air) is standard_fast with the smallest rate_bits >= 1 with 2^rate_bits >= degree - 1. */
+int starkhip_air_register(const uint64_t* blob, size_t words, const char* name, uint32_t default_rows, starkhip_air_t* id_out);
+/* Does `trace` satisfy the AIR?  Every row r is checked with local = r, next = (r + 1) mod n: plain constraints on every row,
+ * transition constraints on rows < n - 1, first-row ones on row 0, last-row ones on row n - 1 -- oracle_check_trace's rule.
+ * *violations = the (row, constraint) pairs whose value is nonzero; first = {constraint, row, value} of the lowest violated constraint
+ * and, of its rows, the lowest (all zero when there is none).  trace, n_rows, n_cols, layout, on_device and public_inputs (the AIR's
+ * count) as starkhip_prove takes them; one call at a time per context, not beside a prove on it.  The constraints are evaluated on the
+ * context's device (csrc/kernels_check.hip); a value is recomputed on the host from the one frame. */
+int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                         const uint64_t* public_inputs, uint64_t* violations, uint64_t first[3]);
 
 /* --- natives + trace generation (host) ----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.

@@ -111,9 +111,34 @@ class Prover {
         return p;
     }
 
+    // Does a row-major trace [n_rows][columns] satisfy `air` (built-in or registered)?  Every constraint on every row, on the device
+    // (starkhip_check_trace); `first` = {constraint, row, value} of the lowest violated constraint, on its lowest row
+    struct TraceCheck {
+        uint64_t violations = 0;
+        uint64_t first[3] = {0, 0, 0};
+    };
+    TraceCheck check_trace(starkhip_air_t air, const uint64_t* trace_rows, size_t n_rows, const std::vector<uint64_t>& pis) {
+        const int cols = starkhip_air_columns(air);
+        check("starkhip_air_columns", cols < 0 ? cols : STARKHIP_OK);
+        TraceCheck r;
+        check("starkhip_check_trace", starkhip_check_trace(ctx_, air, trace_rows, n_rows, (size_t)cols, 0, 0, pis.data(), &r.violations, r.first));
+        return r;
+    }
+
   private:
     void* ctx_ = nullptr;
 };
+
+// A user-defined AIR (the caller's own `impl Stark`) from its constraint program (starkhip.h: starkhip_air_register); the id works
+// wherever a built-in one does.  Throws Error(BAD_AIR) with the validator's reason for a program it refuses.
+inline starkhip_air_t register_air(const std::vector<uint64_t>& blob, const char* name = nullptr, uint32_t default_rows = 0) {
+    char why[256] = {0};
+    const int rc = starkhip_air_check_program(blob.data(), blob.size(), why, sizeof why);
+    if (rc != STARKHIP_OK) throw Error((std::string("starkhip_air_check_program: ") + why).c_str(), rc);
+    starkhip_air_t id;
+    check("starkhip_air_register", starkhip_air_register(blob.data(), blob.size(), name, default_rows, &id));
+    return id;
+}
 
 namespace detail {
 // generate_trace + public inputs of one AIR, recorded: `gen(trace, n_rows, pis)` is the one starkhip_trace_* call

@@ -34,6 +34,7 @@ AIR_FP12_MUL, AIR_PAIRING_PRECOMP, AIR_MILLER_LOOP, AIR_FINAL_EXP, AIR_ECC_AGGRE
 AIR_NAMES = {AIR_FP12_MUL: "FP12MulStark", AIR_PAIRING_PRECOMP: "PairingPrecompStark", AIR_MILLER_LOOP: "MillerLoopStark",
              AIR_FINAL_EXP: "FinalExponentiateStark", AIR_ECC_AGGREGATE: "ECCAggStark", AIR_TEST_FIBONACCI: "TestFibonacci"}
 ECC_NUM_POINTS = 512  # src/ecc_aggregate.rs:7
+AIR_CUSTOM_BASE, AIR_CUSTOM_CAPACITY = 1024, 4096  # ids of registered AIRs (register_air): BASE, BASE + 1, ...
 
 ERR_QUOTIENT_NOT_DIVISIBLE, ERR_ZETA_IN_SUBGROUP, ERR_BAD_SHAPE, ERR_HIP, ERR_OOM, ERR_NO_DEVICE, ERR_VERIFY, ERR_BAD_AIR = range(-1, -9, -1)
 
@@ -185,6 +186,32 @@ def air_program(air):
     words = C.c_size_t()
     _chk(lib.starkhip_air_program(air, C.byref(blob), C.byref(words)))
     return np.ctypeslib.as_array(blob, shape=(words.value,)).copy()
+
+
+lib.starkhip_air_check_program.argtypes = [_u64p, C.c_size_t, C.c_char_p, C.c_size_t]
+lib.starkhip_air_register.argtypes = [_u64p, C.c_size_t, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
+lib.starkhip_check_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, _u64p, _u64p]
+
+
+def air_check_program(blob):
+    """The validator starkhip_air_register runs: None for a program it accepts, else the reason it refuses it."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint64)
+    why = C.create_string_buffer(512)
+    rc = lib.starkhip_air_check_program(_p64(blob), blob.size, why, len(why))
+    if rc == 0:
+        return None
+    if rc != ERR_BAD_AIR:
+        raise StarkhipError(rc)
+    return why.value.decode()
+
+
+def register_air(blob, name=None, default_rows=0):
+    """Register a constraint program (csrc/air_ir.h format; air_builder.AirBuilder makes one) and return its AIR id, usable wherever a
+    built-in id is.  The same blob again returns the same id.  A program the validator refuses raises StarkhipError(ERR_BAD_AIR)."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint64)
+    out = C.c_int()
+    _chk(lib.starkhip_air_register(_p64(blob), blob.size, name.encode() if name is not None else None, default_rows, C.byref(out)))
+    return out.value
 
 
 lib.starkhip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -476,6 +503,39 @@ class Prover:
         proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
         lib.starkhip_free(out)
         return proof
+
+    def check_trace(self, air, trace, public_inputs, layout=0):
+        """Every constraint of `air` on every row of `trace` (row-major [n][C], or column-major [C][n] with layout=1), on this context's
+        device: (violations, (constraint, row, value) of the lowest violated constraint, on its lowest row).  No violation: (0, (0, 0, 0))."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        if trace.ndim != 2 or layout not in (0, 1):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if pis.size != air_public_inputs(air):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        bad = C.c_uint64()
+        first = np.zeros(3, dtype=np.uint64)
+        t0 = time.perf_counter()
+        rc = lib.starkhip_check_trace(self._ctx, air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, _p64(pis), C.byref(bad),
+                                      _p64(first))
+        self.last_call_s = time.perf_counter() - t0
+        _chk(rc)
+        return bad.value, tuple(int(x) for x in first)
+
+    def check_trace_device(self, air, trace_ptr, n_rows, public_inputs, layout=1):
+        """check_trace on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if pis.size != air_public_inputs(air):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        bad = C.c_uint64()
+        first = np.zeros(3, dtype=np.uint64)
+        t0 = time.perf_counter()
+        rc = lib.starkhip_check_trace(self._ctx, air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, _p64(pis), C.byref(bad),
+                                      _p64(first))
+        self.last_call_s = time.perf_counter() - t0
+        _chk(rc)
+        return bad.value, tuple(int(x) for x in first)
 
     def lde_bench(self, n_cols, log_n, rate_bits, reps=5, const_per_64=0, device_ptr=None, each=False):
         """starkhip_lde_bench: average milliseconds of one values -> LDE launch over `n_cols` synthetic columns."""

@@ -1,0 +1,135 @@
+// Validation of a caller's constraint program (air_validate.h).
+#include "air_validate.h"
+
+#include <algorithm>
+
+namespace starkhip {
+
+namespace {
+bool refuse(std::string* why, const std::string& msg) {
+    if (why) *why = msg;
+    return false;
+}
+}  // namespace
+
+bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std::string* why) {
+    if (!blob || words < 8) return refuse(why, "blob shorter than its 8-word header");
+    if (blob[0] != AIR_MAGIC) return refuse(why, "bad magic (not a SAIR_IR1 program)");
+    const uint64_t n_cols = blob[1], n_pis = blob[2], degree = blob[3], n_constraints = blob[4], n_consts = blob[5], n_code = blob[6],
+                   n_groups = blob[7];
+    if (n_cols < 1 || n_cols > STARKHIP_AIR_MAX_COLUMNS) return refuse(why, "n_cols " + std::to_string(n_cols) + " outside 1.." + std::to_string(STARKHIP_AIR_MAX_COLUMNS));
+    if (n_pis > STARKHIP_AIR_MAX_PUBLIC_INPUTS) return refuse(why, "n_pis " + std::to_string(n_pis) + " above " + std::to_string(STARKHIP_AIR_MAX_PUBLIC_INPUTS));
+    if (degree < 1 || degree > STARKHIP_AIR_MAX_DEGREE) return refuse(why, "degree " + std::to_string(degree) + " outside 1.." + std::to_string(STARKHIP_AIR_MAX_DEGREE));
+    if (n_code < 2 || n_code > STARKHIP_AIR_MAX_CODE_WORDS) return refuse(why, "code size " + std::to_string(n_code) + " outside 2.." + std::to_string(STARKHIP_AIR_MAX_CODE_WORDS));
+    if (n_consts > n_code) return refuse(why, "more constants than code words");
+    if (n_constraints < 1 || n_constraints > n_code) return refuse(why, "n_constraints " + std::to_string(n_constraints) + " not in 1..code size");
+    if (n_groups < 1 || n_groups > n_code) return refuse(why, "n_groups " + std::to_string(n_groups) + " not in 1..code size");
+    const uint64_t code_u64 = (n_code + 1) / 2;
+    if ((uint64_t)words != 8 + n_consts + code_u64 + n_groups)  // every count is below 2^27 here: no overflow
+        return refuse(why, "blob length " + std::to_string(words) + " differs from the " + std::to_string(8 + n_consts + code_u64 + n_groups) + " words its header implies");
+    const uint64_t* consts = blob + 8;
+    const uint64_t* code64 = consts + n_consts;
+    const uint64_t* groups = code64 + code_u64;
+    for (uint64_t i = 0; i < n_consts; i++)
+        if (consts[i] >= GL_P) return refuse(why, "constant " + std::to_string(i) + " is not canonical");
+    if ((n_code & 1) && (code64[code_u64 - 1] >> 32) != 0) return refuse(why, "nonzero padding after the last code word");
+
+    AirProgram P;
+    P.n_cols = (uint32_t)n_cols;
+    P.n_pis = (uint32_t)n_pis;
+    P.degree = (uint32_t)degree;
+    P.n_constraints = (uint32_t)n_constraints;
+    P.consts.assign(consts, consts + n_consts);
+    P.code.resize(n_code);
+    for (uint64_t i = 0; i < n_code; i++) P.code[i] = (uint32_t)(code64[i / 2] >> (32 * (i & 1)));
+    P.group_off.resize(n_groups);
+    P.group_k0.resize(n_groups);
+    for (uint64_t g = 0; g < n_groups; g++) {
+        P.group_off[g] = (uint32_t)groups[g];
+        P.group_k0[g] = (uint32_t)(groups[g] >> 32);
+    }
+
+    auto cellref_ok = [&](uint32_t ref, bool gate, std::string* msg) {
+        if (ref & ~(REF_COL_MASK | REF_NEXT | REF_COMPL)) return *msg = "cell reference with unknown flag bits", false;
+        if (!gate && (ref & REF_COMPL)) return *msg = "REF_COMPL on a term factor (gates only)", false;
+        if ((ref & REF_COL_MASK) >= n_cols) return *msg = "column " + std::to_string(ref & REF_COL_MASK) + " out of range", false;
+        return true;
+    };
+    const std::vector<uint32_t>& code = P.code;
+    size_t i = 0;
+    uint64_t k = 0, g = 0;
+    std::string msg;
+    for (;;) {
+        if (i >= n_code) return refuse(why, "code ends without its END word");
+        const uint32_t gw = code[i];
+        if (gw == 0) {
+            if (i + 1 != n_code) return refuse(why, "trailing words after END");
+            break;
+        }
+        const std::string at = "group " + std::to_string(g) + " (code word " + std::to_string(i) + "): ";
+        if ((gw & 15u) != 1u || (gw & 0xC0u)) return refuse(why, at + "not a GROUP word");
+        const uint32_t kind = (gw >> 4) & 3u, ng = (gw >> 8) & 255u, m = gw >> 16;
+        if (m < 1 || m > AIR_MAX_GROUP) return refuse(why, at + "m = " + std::to_string(m) + " outside 1.." + std::to_string(AIR_MAX_GROUP));
+        if (ng > 4) return refuse(why, at + std::to_string(ng) + " gates (at most 4)");
+        if (g >= n_groups) return refuse(why, at + "more groups than the group table holds");
+        if (P.group_off[g] != i || P.group_k0[g] != k) return refuse(why, at + "group table entry differs from the code");
+        g++;
+        i++;
+        if (n_code - i < ng) return refuse(why, at + "gates run past the code");
+        for (uint32_t j = 0; j < ng; j++, i++)
+            if (!cellref_ok(code[i], true, &msg)) return refuse(why, at + "gate: " + msg);
+        for (uint32_t c = 0; c < m; c++, k++) {
+            const std::string atk = "constraint " + std::to_string(k) + ": ";
+            uint32_t maxf = 0;
+            for (;;) {
+                if (i >= n_code) return refuse(why, atk + "terms run past the code");
+                const uint32_t tw = code[i++];
+                const uint32_t nf = tw & 3u, ck = (tw >> 2) & 7u, idx = tw >> 6;
+                if (ck > CK_NEG_PI) return refuse(why, atk + "coefficient kind " + std::to_string(ck) + " (at most 4)");
+                if (ck == CK_CONST && idx >= n_consts) return refuse(why, atk + "const index " + std::to_string(idx) + " out of range");
+                if ((ck == CK_PI || ck == CK_NEG_PI) && idx >= n_pis) return refuse(why, atk + "public input index " + std::to_string(idx) + " out of range");
+                if ((ck == CK_PLUS || ck == CK_MINUS) && idx != 0) return refuse(why, atk + "index on a +-1 term");
+                if (n_code - i < nf) return refuse(why, atk + "factors run past the code");
+                for (uint32_t f = 0; f < nf; f++, i++)
+                    if (!cellref_ok(code[i], false, &msg)) return refuse(why, atk + msg);
+                maxf = std::max(maxf, nf);
+                if (tw & 32u) break;
+            }
+            const uint32_t deg = ng + maxf + ((kind == KIND_FIRST || kind == KIND_LAST) ? 1u : 0u);
+            if (deg > degree) return refuse(why, atk + "degree " + std::to_string(deg) + " above the declared " + std::to_string(degree));
+        }
+    }
+    if (g != n_groups) return refuse(why, "group table has " + std::to_string(n_groups) + " entries, the code " + std::to_string(g) + " groups");
+    if (k != n_constraints) return refuse(why, "n_constraints " + std::to_string(n_constraints) + " but the code has " + std::to_string(k));
+    if (out) *out = std::move(P);
+    return true;
+}
+
+gl_t air_constraint_value(const AirProgram& P, uint32_t k, const gl_t* local, const gl_t* next, const gl_t* pis) {
+    // the group of constraint k: the last one whose first constraint is <= k
+    const size_t g = (size_t)(std::upper_bound(P.group_k0.begin(), P.group_k0.end(), k) - P.group_k0.begin()) - 1;
+    const uint32_t* w = P.code.data() + P.group_off[g];
+    const uint32_t ng = (*w >> 8) & 255u;
+    w++;
+    auto cell = [&](uint32_t ref) { return ((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]; };
+    gl_t G = 1;
+    for (uint32_t j = 0; j < ng; j++, w++) G = gl_mul(G, (*w & REF_COMPL) ? gl_sub(1, cell(*w)) : cell(*w));
+    for (uint32_t c = P.group_k0[g];; c++) {
+        gl_t body = 0;
+        for (;;) {
+            const uint32_t tw = *w++;
+            const uint32_t nf = tw & 3u, ck = (tw >> 2) & 7u, idx = tw >> 6;
+            gl_t u = 1;
+            for (uint32_t f = 0; f < nf; f++) u = gl_mul(u, cell(*w++));
+            if (ck == CK_PLUS) body = gl_add(body, u);
+            else if (ck == CK_MINUS) body = gl_sub(body, u);
+            else if (ck == CK_CONST) body = gl_add(body, gl_mul(u, P.consts[idx]));
+            else if (ck == CK_PI) body = gl_add(body, gl_mul(u, pis[idx]));
+            else body = gl_sub(body, gl_mul(u, pis[idx]));
+            if (tw & 32u) break;
+        }
+        if (c == k) return gl_mul(G, body);
+    }
+}
+
+}  // namespace starkhip

@@ -1,0 +1,26 @@
+// Validator of a caller's serialised constraint program (air_ir.h, magic SAIR_IR1) and the per-constraint host evaluator the
+// trace checker reports with.
+//
+// A registered program goes straight into the quotient kernels, the plan builder and the verifiers, which index the LDE and the
+// opened rows by its cell references without further checks.  air_parse_checked() is the one gate in front of them: what it
+// accepts parses exactly by the grammar of air_ir.h, every reference is inside the declared columns, public inputs and const
+// table, and the declared degree covers every constraint by AirBuilder::emit's rule.  The limits (STARKHIP_AIR_MAX_*) are in
+// include/starkhip.h.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/starkhip.h"
+#include "air_ir.h"
+
+namespace starkhip {
+
+// The reason of a refusal goes to *why (may be NULL).  On success *out holds the program, group tables included.
+bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std::string* why);
+
+// mask-free value G * body of constraint k (0 <= k < n_constraints) on one frame: what oracle_check_trace compares with zero
+gl_t air_constraint_value(const AirProgram& P, uint32_t k, const gl_t* local, const gl_t* next, const gl_t* pis);
+
+}  // namespace starkhip

@@ -1,7 +1,11 @@
-// AIR registry: builds each constraint program once, on first use.
+// AIR registry: builds each built-in constraint program once, on first use, and holds the programs registered at run time.
 #include "airs.h"
 
+#include <atomic>
+#include <map>
+#include <memory>
 #include <mutex>
+#include <string>
 
 namespace starkhip {
 
@@ -25,9 +29,51 @@ Slot g_slots[] = {
     {STARKHIP_AIR_ECC_AGGREGATE, "ECCAggStark", 8192, build_air_ecc_aggregate},  // src/aggregate_proof.rs:188-189
     {STARKHIP_AIR_TEST_FIBONACCI, "TestFibonacci", 64, build_air_fibonacci},
 };
+// Registered AIRs: entries are published once, with release order, and never change or move afterwards, so a reader needs no lock;
+// the registry's mutex orders registrations among themselves.
+struct Custom {
+    AirInfo info;
+    std::string name;
+};
+std::atomic<Custom*> g_custom[STARKHIP_AIR_CUSTOM_CAPACITY];
+std::mutex g_custom_mu;
+int g_custom_count = 0;                            // under g_custom_mu
+struct BlobLess {
+    bool operator()(const std::vector<uint64_t>* a, const std::vector<uint64_t>* b) const { return *a < *b; }
+};
+std::map<const std::vector<uint64_t>*, int, BlobLess> g_custom_ids;  // registered blob (the entry's own copy) -> id, under g_custom_mu
 }  // namespace
 
+int air_register(AirProgram&& prog, const std::vector<uint64_t>& blob, const char* name, uint32_t default_rows, int* id) {
+    std::lock_guard<std::mutex> g(g_custom_mu);
+    auto it = g_custom_ids.find(&blob);
+    if (it != g_custom_ids.end()) {
+        *id = it->second;
+        return STARKHIP_OK;
+    }
+    if (g_custom_count >= STARKHIP_AIR_CUSTOM_CAPACITY) return STARKHIP_ERR_BAD_AIR;
+    const int new_id = STARKHIP_AIR_CUSTOM_BASE + g_custom_count;
+    std::unique_ptr<Custom> c(new Custom());
+    c->name = name ? std::string(name) : "CustomAir" + std::to_string(new_id);
+    c->info.prog = std::move(prog);
+    c->info.id = new_id;
+    c->info.name = c->name.c_str();
+    c->info.cols = c->info.prog.n_cols;
+    c->info.pis = c->info.prog.n_pis;
+    c->info.degree = c->info.prog.degree;
+    c->info.default_rows = default_rows;
+    c->info.blob = blob;
+    g_custom_ids.emplace(&c->info.blob, new_id);
+    g_custom[g_custom_count++].store(c.release(), std::memory_order_release);  // lives as long as the process
+    *id = new_id;
+    return STARKHIP_OK;
+}
+
 const AirInfo* air_get(int id) {
+    if (id >= STARKHIP_AIR_CUSTOM_BASE && id < STARKHIP_AIR_CUSTOM_BASE + STARKHIP_AIR_CUSTOM_CAPACITY) {
+        const Custom* c = g_custom[id - STARKHIP_AIR_CUSTOM_BASE].load(std::memory_order_acquire);
+        return c ? &c->info : nullptr;
+    }
     for (auto& s : g_slots) {
         if (s.id != id) continue;
         std::call_once(s.once, [&s]() {

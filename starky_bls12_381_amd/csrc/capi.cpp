@@ -9,6 +9,7 @@
 #include <new>
 
 #include "air_eval.h"
+#include "air_validate.h"
 #include "airs.h"
 #include "blob_arena.h"
 #include "kernels.h"
@@ -63,8 +64,13 @@ int starkhip_config_for_air(starkhip_air_t air, starkhip_config_t* cfg) {
         case STARKHIP_AIR_TEST_FIBONACCI:
             return STARKHIP_OK;
         default:
-            return STARKHIP_ERR_BAD_AIR;
+            break;
     }
+    const AirInfo* a = (int)air >= STARKHIP_AIR_CUSTOM_BASE ? air_get(air) : nullptr;
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    // a registered AIR: the quotient's degree factor degree - 1 must fit the blow-up (starkhip_prove's rule)
+    while ((1u << cfg->rate_bits) + 1 < a->degree) cfg->rate_bits++;
+    return STARKHIP_OK;
 }
 
 int starkhip_air_columns(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->cols : STARKHIP_ERR_BAD_AIR; }
@@ -103,6 +109,51 @@ int starkhip_air_eval_frame(starkhip_air_t air, const uint64_t* local, const uin
         return STARKHIP_ERR_OOM;
     }
     return STARKHIP_OK;
+}
+
+int starkhip_air_check_program(const uint64_t* blob, size_t words, char* why, size_t why_len) {
+    std::string msg;
+    bool ok;
+    try {
+        ok = air_parse_checked(blob, words, nullptr, &msg);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+    if (why && why_len) {
+        const size_t n = std::min(msg.size(), why_len - 1);
+        memcpy(why, msg.data(), n);
+        why[n] = 0;
+    }
+    return ok ? STARKHIP_OK : STARKHIP_ERR_BAD_AIR;
+}
+
+int starkhip_air_register(const uint64_t* blob, size_t words, const char* name, uint32_t default_rows, starkhip_air_t* id_out) {
+    if (!id_out || (default_rows && (default_rows < 2 || default_rows > 8192 || (default_rows & (default_rows - 1))))) return STARKHIP_ERR_BAD_SHAPE;
+    try {
+        AirProgram prog;
+        if (!air_parse_checked(blob, words, &prog, nullptr)) return STARKHIP_ERR_BAD_AIR;
+        int id = 0;
+        const int rc = air_register(std::move(prog), std::vector<uint64_t>(blob, blob + words), name, default_rows, &id);
+        if (rc == STARKHIP_OK) *id_out = (starkhip_air_t)id;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+
+int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                         const uint64_t* public_inputs, uint64_t* violations, uint64_t first[3]) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    if (!trace || !violations || !first || (a->pis && !public_inputs) || (layout != 0 && layout != 1) || n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;
+    try {
+        return check_trace((Ctx*)ctx, *a, trace, n_rows, layout, on_device, public_inputs, violations, first);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    } catch (const std::exception&) {
+        return STARKHIP_ERR_BAD_SHAPE;
+    }
 }
 
 int starkhip_quotient_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[8]) {

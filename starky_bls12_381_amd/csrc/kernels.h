@@ -103,6 +103,12 @@ hipError_t launch_quotient_tiles(const QTRec* recs, const QTStream* streams, con
 hipError_t launch_quotient_tiles_combine(const gl_t* partial, unsigned n_chunks, const gl_t* tab, unsigned log_n, unsigned qdb, gl_t* out,
                                          hipStream_t st);
 
+// kernels_check.hip: every constraint on every row of a column-major trace [C][2^log_n] (starkhip_check_trace); `ops` / chunk_op /
+// chunk_k0 from compile_quotient_ops (ops of chunk c: [chunk_op[c], chunk_op[c + 1]), its first constraint chunk_k0[c]).  out[0] +=
+// violations, out[1] = min(out[1], (k << 32) | row); the caller presets them to 0 and ~0.
+hipError_t launch_check_trace(const QOp* ops, const uint32_t* chunk_op, const uint32_t* chunk_k0, unsigned n_chunks, const gl_t* trace,
+                              const gl_t* pis, unsigned log_n, unsigned long long* out, hipStream_t st);
+
 // kernels_fri.hip
 hipError_t launch_ext_powers(gl2_t* out, gl2_t base, size_t count, hipStream_t st);
 // weights of the evaluation at z (and, rotated by one, at w_n z) from values on coset 0 of the LDE; scale = (z^n - 7^n) / (n 7^n)

@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "air_validate.h"
 #include "airs.h"
 #include "blob_arena.h"
 #include "kernels.h"
@@ -153,6 +154,11 @@ struct Ctx {
     DevBuf d_ops, d_loads, d_chunk_off;  // compile_quotient_ops() + attach_cell_cache() output for prog_air
     unsigned prog_slots = 0;
     std::vector<uint32_t> chunk_k_after;
+    // trace checker (starkhip_check_trace): the op stream of chk_air cut for chk_want chunks (chk_chunks of them came out), the chunks'
+    // first ops and constraints, the results
+    int chk_air = -1;
+    unsigned chk_want = 0, chk_chunks = 0;
+    DevBuf d_chk_ops, d_chk_meta, d_chk_out;
     // work buffers
     // `lde` is the one big buffer (19.3 GB for FinalExp).  Before the LDE kernel writes it, it holds everything that waits for that
     // kernel: the trace columns as its LAST quarter (the LDE goes out in launches that overwrite only columns already transformed:
@@ -451,7 +457,7 @@ void ctx_destroy(Ctx* c) {
         for (DevBuf* b : {&t->tw_fwd, &t->tw_inv, &t->coset_scale, &t->qtab, &t->qshift_inv, &t->lde2_fwd, &t->lde2_inv, &t->lde2_cs, &t->lde2_oh, &t->lde_wave}) b->release();
     for (auto& d : c->plan_cache)
         for (DevBuf* b : {&d->q_recs, &d->q_streams, &d->q_chunk_tile_off, &d->q_tile_list, &d->q_contrib_off, &d->q_contribs, &d->q_consts, &d->q_apow}) b->release();
-    DevBuf* bufs[] = {&c->d_ops, &c->d_loads, &c->d_chunk_off, &c->staging,
+    DevBuf* bufs[] = {&c->d_ops, &c->d_loads, &c->d_chunk_off, &c->d_chk_ops, &c->d_chk_meta, &c->d_chk_out, &c->staging,
                       &c->values, &c->lde, &c->digests, &c->pis, &c->apow, &c->chunk_scale, &c->partial, &c->qvals, &c->qcoef,
                       &c->qlde, &c->qdigests, &c->zpow, &c->gzpow, &c->open_local, &c->open_next, &c->open_q, &c->ext_apow, &c->comb_partial,
                       &c->comb_out, &c->fri_coef, &c->fri_vals, &c->scale_tab, &c->pow_state, &c->pow_best, &c->qidx, &c->gather_t,
@@ -520,7 +526,7 @@ size_t ctx_device_bytes(Ctx* c) {
         for (DevBuf* b : {&t->tw_fwd, &t->tw_inv, &t->coset_scale, &t->qtab, &t->qshift_inv, &t->lde2_fwd, &t->lde2_inv, &t->lde2_cs, &t->lde2_oh, &t->lde_wave}) total += b->cap;
     for (auto& d : c->plan_cache)
         for (DevBuf* b : {&d->q_recs, &d->q_streams, &d->q_chunk_tile_off, &d->q_tile_list, &d->q_contrib_off, &d->q_contribs, &d->q_consts, &d->q_apow}) total += b->cap;
-    DevBuf* bufs[] = {&c->d_ops, &c->d_loads, &c->d_chunk_off, &c->staging, &c->values, &c->lde, &c->digests, &c->pis, &c->apow, &c->chunk_scale, &c->partial,
+    DevBuf* bufs[] = {&c->d_ops, &c->d_loads, &c->d_chunk_off, &c->d_chk_ops, &c->d_chk_meta, &c->d_chk_out, &c->staging, &c->values, &c->lde, &c->digests, &c->pis, &c->apow, &c->chunk_scale, &c->partial,
                       &c->qvals, &c->qcoef, &c->qlde, &c->qdigests, &c->zpow, &c->gzpow, &c->open_local, &c->open_next, &c->open_q, &c->ext_apow,
                       &c->comb_partial, &c->comb_out, &c->fri_coef, &c->fri_vals, &c->scale_tab, &c->pow_state, &c->pow_best, &c->qidx, &c->gather_t,
                       &c->gather_q};
@@ -1317,6 +1323,81 @@ int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigne
 }
 
 // kernel-level test entry: a recorded trace through expand_trace_kernel + zero_cells_kernel, handed back column-major [C][rows]
+// starkhip_check_trace.  The trace goes where prove() would put it -- column-major in `values`, or the caller's own device memory --
+// with the LDE buffer as the upload staging of row-major host rows.  The op stream is cached per context like the quotient's.
+int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
+                uint64_t* violations, uint64_t first[3]) {
+    const AirProgram& P = air.prog;
+    unsigned log_n = 0;
+    while (((size_t)1 << log_n) < n_rows) log_n++;
+    if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || log_n > 13) return STARKHIP_ERR_BAD_SHAPE;
+    for (size_t i = 0; i < P.n_pis; i++)
+        if (pis[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    const size_t n = n_rows, C = P.n_cols;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->st;
+    // (n / 64) x chunks waves: enough to fill 256 CUs several times over, at most one chunk per group
+    const size_t blocks = (n + 63) / 64;
+    const unsigned want = (unsigned)std::min<size_t>({1024, P.group_off.size(), std::max<size_t>(1, (32768 + blocks - 1) / blocks)});
+    if (c->chk_air != air.id || c->chk_want != want) {
+        c->chk_air = -1;
+        const QProgram Q = compile_quotient_ops(P, want);
+        const size_t nc = Q.chunk_k_after.size();
+        std::vector<uint32_t> meta(2 * nc + 1);  // chunk_op[nc + 1], chunk_k0[nc]
+        for (size_t j = 0; j <= nc; j++) meta[j] = Q.chunk_batch[j] * QOP_BATCH;
+        for (size_t j = 0; j < nc; j++) meta[nc + 1 + j] = j ? P.n_constraints - Q.chunk_k_after[j - 1] : 0;
+        HIPCHK(c->d_chk_ops.ensure(Q.ops.size() * sizeof(QOp)));
+        HIPCHK(c->d_chk_meta.ensure(meta.size() * 4));
+        HIPCHK(hipMemcpyAsync(c->d_chk_ops.p, Q.ops.data(), Q.ops.size() * sizeof(QOp), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(c->d_chk_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(stream_wait(c));  // Q and meta go out of scope
+        c->chk_air = air.id;
+        c->chk_want = want;
+        c->chk_chunks = (unsigned)nc;
+    }
+    const unsigned nc = c->chk_chunks;
+    const gl_t* d_trace;
+    if (on_device && layout == 1) {
+        d_trace = trace;  // the caller's memory: read only
+    } else {
+        HIPCHK(c->values.ensure(C * n * 8));
+        if (on_device) {
+            HIPCHK(launch_transpose(trace, c->values.as<gl_t>(), n, C, st));
+        } else if (layout == 1) {
+            HIPCHK(hipMemcpyAsync(c->values.p, trace, C * n * 8, hipMemcpyHostToDevice, st));
+        } else {
+            HIPCHK(c->lde.ensure(C * n * 8));
+            HIPCHK(hipMemcpyAsync(c->lde.p, trace, C * n * 8, hipMemcpyHostToDevice, st));
+            HIPCHK(launch_transpose(c->lde.as<gl_t>(), c->values.as<gl_t>(), n, C, st));
+        }
+        d_trace = c->values.as<gl_t>();
+    }
+    HIPCHK(c->pis.ensure(std::max<size_t>(1, P.n_pis) * 8));
+    if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, st));
+    const unsigned long long init[2] = {0, ~0ull};
+    unsigned long long res[2];
+    HIPCHK(c->d_chk_out.ensure(sizeof init));
+    HIPCHK(hipMemcpyAsync(c->d_chk_out.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    const uint32_t* meta = c->d_chk_meta.as<uint32_t>();
+    HIPCHK(launch_check_trace(c->d_chk_ops.as<QOp>(), meta, meta + nc + 1, nc, d_trace, c->pis.as<gl_t>(), log_n,
+                              c->d_chk_out.as<unsigned long long>(), st));
+    HIPCHK(hipMemcpyAsync(res, c->d_chk_out.p, sizeof res, hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(c));
+    *violations = res[0];
+    first[0] = first[1] = first[2] = 0;
+    if (!res[0]) return STARKHIP_OK;
+    // the value of the first violation, from its frame: rows r and r + 1 (mod n) of every column
+    const uint32_t k = (uint32_t)(res[1] >> 32), r = (uint32_t)res[1];
+    std::vector<gl_t> frame(2 * C);
+    HIPCHK(hipMemcpy2DAsync(frame.data(), 8, d_trace + r, n * 8, 8, C, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpy2DAsync(frame.data() + C, 8, d_trace + ((r + 1) & (n - 1)), n * 8, 8, C, hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(c));
+    first[0] = k;
+    first[1] = r;
+    first[2] = air_constraint_value(P, k, frame.data(), frame.data() + C, pis);
+    return STARKHIP_OK;
+}
+
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor) {
     HIPCHK(hipSetDevice(c->device));
     const size_t nw = log->total_words(), nr = log->total_records(), nz = log->total_late_zeros();
