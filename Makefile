@@ -50,7 +50,7 @@ build/asan/liboracle_asan.so: oracle/stark_oracle.c oracle/oracle_field.h
 asan-test: asan
 	LD_PRELOAD=$$(gcc -print-file-name=libasan.so):$$(gcc -print-file-name=libubsan.so) ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 \
 	STARKHIP_LIBRARY=$(CURDIR)/build/asan/libstarkhip_host_asan.so STARKHIP_ORACLE_LIBRARY=$(CURDIR)/build/asan/liboracle_asan.so \
-	python -m pytest tests/test_native_cpu.py tests/test_quotient_plan_cpu.py tests/test_toy_air_cpu.py tests/test_trace_log_cpu.py tests/test_ecc_aggregate_cpu.py -x -q -m "not gpu" -p no:cacheprovider
+	python -m pytest tests/test_native_cpu.py tests/test_quotient_plan_cpu.py tests/test_toy_air_cpu.py tests/test_trace_log_cpu.py tests/test_ecc_aggregate_cpu.py tests/test_stark_config_cpu.py -x -q -m "not gpu" -p no:cacheprovider
 
 # ThreadSanitizer on the threaded trace recording (trace_tasks.cpp): three traces recorded on 6 threads
 tsan-test: tests/tsan_trace_main.cpp $(ASAN_SRCS) $(HDRS)

@@ -228,6 +228,10 @@ extern "C" {
     pub fn starkhip_verify_batch_replay(n: usize, airs: *const Air, cfgs: *const starkhip_config_t, proofs: *const *const u64,
                                         proof_words: *const usize, results: *mut c_int) -> c_int;
     pub fn starkhip_proof_layout(proof: *const u64, proof_words: usize, out: *mut starkhip_proof_layout_t) -> c_int;
+    /// The config rule of every entry point (no GPU): the FRI reduction arities and final polynomial length of a config at
+    /// 2^log_n rows, or `STARKHIP_ERR_BAD_SHAPE` for a config the prover and verifiers refuse.
+    pub fn starkhip_fri_geometry(cfg: *const starkhip_config_t, log_n: c_uint, arities_out: *mut c_uint, cap: usize, n_layers: *mut usize,
+                                 final_poly_len: *mut usize) -> c_int;
     pub fn starkhip_free(p: *mut c_void);
     pub fn starkhip_proof_blob_stats(out: *mut u64);
     pub fn starkhip_error_string(code: c_int) -> *const c_char;

@@ -37,6 +37,13 @@
 extern "C" {
 #endif
 
+/* starky's StarkConfig with its FriConfig, flattened.  Accepted range (one rule for every prove, pool, multipool and verify entry
+ * point; starkhip_fri_geometry applies it): num_challenges == 2, rate_bits <= 8 and at least log2 of the AIR's quotient degree
+ * factor (degree - 1), cap_height <= 16 and <= degree_bits + rate_bits, 1 <= arity_bits <= 8, proof_of_work_bits <= 64.  The FRI
+ * layers are plonky2's ConstantArityBits(arity_bits, final_poly_bits): while db > final_poly_bits && db + rate_bits - arity_bits >=
+ * cap_height (over the integers) a layer of arity_bits; a config where a layer would take db below zero (plonky2's
+ * assert!(degree_bits >= arity_bits)) or that needs more than 16 layers is refused.  num_query_rounds may be 0 (a proof with no
+ * query rounds, as plonky2 makes it); security_bits is not read.  Anything else is STARKHIP_ERR_BAD_SHAPE before any device work. */
 typedef struct {
     uint32_t security_bits;      /* 100 */
     uint32_t num_challenges;     /* 2   */
@@ -457,6 +464,12 @@ int starkhip_selfcheck_hash_tables(unsigned n_states);
  * has read; the last one reads a copy of its columns (csrc/lde_ranges.h).  Writes up to `cap` launches as triples
  * {first column, end column, 1 if it reads the copy} and returns how many the plan has. */
 size_t starkhip_lde_launch_ranges(size_t n_cols, unsigned rate_bits, uint64_t* triples, size_t cap);
+/* The config rule above for a trace of 2^log_n rows (no GPU needed): STARKHIP_OK and the FRI geometry -- up to `cap` reduction
+ * arity bits in arities_out, the layer count in *n_layers and the final polynomial's length in *final_poly_len -- or
+ * STARKHIP_ERR_BAD_SHAPE for a config every entry point refuses.  The AIR-dependent part (rate_bits against the degree) is not
+ * checked here. */
+int starkhip_fri_geometry(const starkhip_config_t* cfg, unsigned log_n, unsigned* arities_out, size_t cap, size_t* n_layers,
+                          size_t* final_poly_len);
 /* CPU check (no GPU needed) of the tiled constraint plan the quotient kernel executes (csrc/quotient_plan.h): builds the plan
  * of `air` with `want_chunks` chunks, derives the per-proof weights from random alphas / public inputs and replays the
  * record streams on one random frame with the kernel's own accumulators; the result must equal the plain fold

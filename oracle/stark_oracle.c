@@ -426,16 +426,28 @@ EXPORT int oracle_prove(const uint64_t* air_blob, size_t air_words, const oracle
     if (((size_t)1 << logn) != n_rows) return ERR_BAD_SHAPE;
     const size_t n = n_rows, C = P.n_cols;
     const unsigned r = cfg->rate_bits, capH = cfg->cap_height, logN = logn + r;
-    const size_t N = n << r, ncap = (size_t)1 << capH;
     const int nch = (int)cfg->num_challenges;
-    /* A.8 fri_params: ConstantArityBits(arity_bits, final_poly_bits) */
+    /* the accepted configs (include/starkhip.h, starkhip_config_t); the product's rule is FriGeometry::make */
+    if (nch != 2 || r > 8 || capH > 16 || cfg->arity_bits < 1 || cfg->arity_bits > 8 || cfg->proof_of_work_bits > 64 || logN < capH) {
+        free(P.code);
+        return ERR_BAD_SHAPE;
+    }
+    const size_t N = n << r, ncap = (size_t)1 << capH;
+    /* A.8 fri_params: ConstantArityBits(arity_bits, final_poly_bits), the loop condition over the integers, refused where plonky2's
+     * assert!(degree_bits >= arity_bits) fires */
     unsigned arities[16]; int L = 0;
-    { unsigned db = logn; while (db > cfg->final_poly_bits && db + r - cfg->arity_bits >= capH) { arities[L++] = cfg->arity_bits; db -= cfg->arity_bits; } }
-    { unsigned tot = 0; for (int i = 0; i < L; i++) tot += arities[i]; if (tot > logn + r - capH || logN < capH) return ERR_BAD_SHAPE; }
+    {
+        long db = logn;
+        while (db > (long)cfg->final_poly_bits && db + (long)r - (long)cfg->arity_bits >= (long)capH) {
+            if (db < (long)cfg->arity_bits || L == 16) { free(P.code); return ERR_BAD_SHAPE; }
+            arities[L++] = cfg->arity_bits;
+            db -= cfg->arity_bits;
+        }
+    }
     /* A.6 quotient geometry */
     const unsigned factor = P.degree > 1 ? P.degree - 1 : 1;
     unsigned qdb = 0; while ((1u << qdb) < factor) qdb++;
-    if (qdb > r) return ERR_BAD_SHAPE;
+    if (qdb > r) { free(P.code); return ERR_BAD_SHAPE; }
     const size_t Q = (size_t)factor * nch;
 
     /* ---- A.3 trace commit */

@@ -239,6 +239,19 @@ def proof_layout(proof):
     return out
 
 
+lib.starkhip_fri_geometry.argtypes = [C.POINTER(StarkConfig), C.c_uint, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.POINTER(C.c_size_t)]
+
+
+def fri_geometry(config, log_n):
+    """starkhip_fri_geometry: (FRI reduction arity bits, final polynomial length) of `config` at 2^log_n rows -- the config rule of
+    every prove and verify entry point.  A refused config raises StarkhipError(ERR_BAD_SHAPE)."""
+    ar = (C.c_uint * 16)()
+    n_layers, final_len = C.c_size_t(), C.c_size_t()
+    _chk(lib.starkhip_fri_geometry(C.byref(config), log_n, ar, 16, C.byref(n_layers), C.byref(final_len)))
+    return [int(a) for a in ar[:n_layers.value]], final_len.value
+
+
 def quotient_plan_check(air, want_chunks=4, seed=1):
     """CPU replay of the tiled constraint plan against the plain fold; returns the plan statistics (see starkhip.h)."""
     stats = np.zeros(8, dtype=np.uint64)

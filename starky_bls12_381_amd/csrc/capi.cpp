@@ -680,6 +680,16 @@ int starkhip_selfcheck_hash_tables(unsigned n_states) {
     if (fours < 0) return -1;
     return quad_merged_tables_selfcheck(n_states) + fours;
 }
+int starkhip_fri_geometry(const starkhip_config_t* cfg, unsigned log_n, unsigned* arities_out, size_t cap, size_t* n_layers, size_t* final_poly_len) {
+    if (!cfg) return STARKHIP_ERR_BAD_SHAPE;
+    FriGeometry g;
+    if (!FriGeometry::make(*cfg, log_n, &g)) return STARKHIP_ERR_BAD_SHAPE;
+    for (size_t l = 0; l < g.arities.size() && l < cap; l++) arities_out[l] = g.arities[l];
+    if (n_layers) *n_layers = g.arities.size();
+    if (final_poly_len) *final_poly_len = g.final_poly_len;
+    return STARKHIP_OK;
+}
+
 size_t starkhip_lde_launch_ranges(size_t n_cols, unsigned rate_bits, uint64_t* triples, size_t cap) {
     const std::vector<LdeLaunch> plan = lde_launch_plan(n_cols, rate_bits);
     for (size_t i = 0; i < plan.size() && i < cap; i++) {

@@ -47,18 +47,20 @@ static inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1
 
 hipError_t launch_query_leaf_colmajor(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, const uint32_t* xs, size_t n_queries,
                                       gl_t* out, size_t stride, size_t off, hipStream_t st) {
+    if (n_queries == 0 || n_cols == 0) return hipSuccess;  // num_query_rounds = 0: a grid of zero blocks is a launch error
     hipLaunchKernelGGL(query_leaf_colmajor_kernel, dim3(nb(n_cols, 256), (unsigned)n_queries), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, xs,
                        out, stride, off);
     return hipGetLastError();
 }
 hipError_t launch_query_leaf_rows(const gl_t* rows, size_t width, const uint32_t* xs, unsigned shift, size_t n_queries, gl_t* out, size_t stride,
                                   size_t off, hipStream_t st) {
+    if (n_queries == 0 || width == 0) return hipSuccess;
     hipLaunchKernelGGL(query_leaf_rows_kernel, dim3(nb(width, 64), (unsigned)n_queries), dim3(64), 0, st, rows, width, xs, shift, out, stride, off);
     return hipGetLastError();
 }
 hipError_t launch_query_path(const gl_t* digests, size_t n_leaves, unsigned depth, const uint32_t* xs, unsigned shift, size_t n_queries, gl_t* out,
                              size_t stride, size_t off, hipStream_t st) {
-    if (depth == 0) return hipSuccess;
+    if (depth == 0 || n_queries == 0) return hipSuccess;
     hipLaunchKernelGGL(query_path_kernel, dim3(nb(4 * depth, 64), (unsigned)n_queries), dim3(64), 0, st, digests, n_leaves, depth, xs, shift, out,
                        stride, off);
     return hipGetLastError();

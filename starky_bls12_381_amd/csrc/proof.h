@@ -14,26 +14,41 @@ struct FriGeometry {
     unsigned log_n, rate_bits, cap_h, log_N;
     std::vector<unsigned> arities;  // reduction_arity_bits
     size_t final_poly_len;
-    // plonky2 FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits), App. A.8
+    // The one config rule of every prove, pool and verify entry point (starkhip_fri_geometry exposes it): plonky2
+    // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits), App. A.8,
+    //     while db > final_poly_bits && db + rate_bits - arity_bits >= cap_height { push arity_bits; assert!(db >= arity_bits); db -= arity_bits }
+    // with the comparison taken over the integers, refused where plonky2's assert fires; then the limits the proof header can carry
+    // (ProofLayout::read_header) and the ones the project supports: 2 challenges, rate_bits <= 8, cap_height <= 16 and <= log_n +
+    // rate_bits, 1 <= arity_bits <= 8, at most 16 FRI layers, proof_of_work_bits <= 64, log_n <= 32.  False = BAD_SHAPE.
     static bool make(const starkhip_config_t& cfg, unsigned log_n, FriGeometry* g) {
         g->log_n = log_n;
         g->rate_bits = cfg.rate_bits;
         g->cap_h = cfg.cap_height;
         g->log_N = log_n + cfg.rate_bits;
         g->arities.clear();
+        g->final_poly_len = 0;
+        if (cfg.num_challenges != 2 || cfg.rate_bits > 8 || cfg.cap_height > 16 || cfg.arity_bits < 1 || cfg.arity_bits > 8 ||
+            cfg.proof_of_work_bits > 64 || log_n > 32 || g->log_N < g->cap_h)
+            return false;
         unsigned db = log_n;
-        if (cfg.arity_bits == 0) return false;
         while (db > cfg.final_poly_bits && db + cfg.rate_bits >= cfg.cap_height + cfg.arity_bits) {
+            if (db < cfg.arity_bits || g->arities.size() == 16) return false;
             g->arities.push_back(cfg.arity_bits);
             db -= cfg.arity_bits;
         }
-        unsigned total = 0;
-        for (unsigned a : g->arities) total += a;
-        if (g->log_N < g->cap_h || total > g->log_N - g->cap_h) return false;
+        // every layer keeps db + rate_bits >= cap_height, so the arities never exceed log_N - cap_height
         g->final_poly_len = (size_t)1 << db;
         return true;
     }
 };
+
+// log2 of the quotient degree factor (degree - 1, at least 1) of an AIR of constraint degree `degree`; a config needs rate_bits >= it
+inline unsigned quotient_degree_bits(unsigned degree) {
+    const unsigned factor = degree > 1 ? degree - 1 : 1;
+    unsigned qdb = 0;
+    while ((1u << qdb) < factor) qdb++;
+    return qdb;
+}
 
 struct ProofLayout {
     size_t C, Q, log_n, rate_bits, cap_h, L, n_queries, final_len, n_pis, arity_bits, n_challenges;

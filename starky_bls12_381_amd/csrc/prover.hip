@@ -1111,7 +1111,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
 #define HIPCHK_FREE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { fprintf(stderr, "starkhip: HIP error %s (%s)\n", hipGetErrorString(_e), #expr); err = 1; } } while (0)
         HIPCHK_FREE(c->gather_t.ensure(nq * stride * 8));
         gl_t* dq = c->gather_t.as<gl_t>();
-        HIPCHK_FREE(hipMemcpyAsync(c->qidx.p, xs.data(), nq * 4, hipMemcpyHostToDevice, st));
+        if (nq) HIPCHK_FREE(hipMemcpyAsync(c->qidx.p, xs.data(), nq * 4, hipMemcpyHostToDevice, st));
         const uint32_t* dxs = c->qidx.as<uint32_t>();
         size_t off = 0;
         if (!err) {
@@ -1130,7 +1130,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
                 off += 4 * pl.layer_depth[l];
                 len = n_leaves;
             }
-            HIPCHK_FREE(hipMemcpyAsync(out + pl.off_queries, dq, nq * stride * 8, hipMemcpyDeviceToHost, st));
+            if (nq) HIPCHK_FREE(hipMemcpyAsync(out + pl.off_queries, dq, nq * stride * 8, hipMemcpyDeviceToHost, st));
         }
         pl.write_header(out);
         memcpy(out + pl.off_trace_cap, trace_cap.data(), 4 * ncap * 8);

@@ -24,6 +24,7 @@
 #include <unordered_map>
 
 #include "kernels.h"
+#include "proof.h"
 #include "prover.h"
 #include "trace_log.h"
 #include "verify_service.h"
@@ -919,6 +920,11 @@ static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     unsigned log_n = 0;
     const size_t rows = j->kind == JOB_WITNESS ? a->default_rows : j->n_rows;
     while (((size_t)1 << log_n) < rows) log_n++;
+    FriGeometry geo;  // a config prove() would refuse is refused here, before it takes a place in a queue
+    if (!FriGeometry::make(j->cfg, log_n, &geo) || quotient_degree_bits(a->prog.degree) > j->cfg.rate_bits) {
+        delete j;
+        return STARKHIP_ERR_BAD_SHAPE;
+    }
     j->big = HashService::is_big(log_n, j->cfg.rate_bits);
     std::lock_guard<std::mutex> g(p->mu);
     if (p->stop) {

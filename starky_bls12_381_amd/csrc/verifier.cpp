@@ -71,6 +71,8 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     ProofLayout& pl = out->pl;
     if (!pl.read_header(proof, words)) return STARKHIP_ERR_BAD_SHAPE;
     const AirProgram& P = air.prog;
+    FriGeometry& geo = out->geo;
+    if (!FriGeometry::make(cfg, (unsigned)pl.log_n, &geo) || quotient_degree_bits(P.degree) > cfg.rate_bits) return STARKHIP_ERR_BAD_SHAPE;
     const unsigned factor = P.degree > 1 ? P.degree - 1 : 1;
     if (pl.C != P.n_cols || pl.n_pis != P.n_pis || pl.rate_bits != cfg.rate_bits || pl.cap_h != cfg.cap_height ||
         pl.n_queries != cfg.num_query_rounds || pl.n_challenges != cfg.num_challenges || pl.Q != (size_t)factor * cfg.num_challenges ||
@@ -81,8 +83,6 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
         if (proof[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     for (size_t i = skip_hi; i < words; i++)
         if (proof[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
-    FriGeometry& geo = out->geo;
-    if (!FriGeometry::make(cfg, (unsigned)pl.log_n, &geo)) return STARKHIP_ERR_BAD_SHAPE;
     if (geo.arities.size() != pl.L || geo.final_poly_len != pl.final_len) return STARKHIP_ERR_BAD_SHAPE;
 
     const size_t C = pl.C, Q = pl.Q, n = (size_t)1 << pl.log_n, N = (size_t)1 << pl.log_N, ncap = pl.ncap;

@@ -187,6 +187,7 @@ hipError_t VerifyStaging::copy(gl_t* dst, const uint64_t* src, size_t words, boo
 
 hipError_t verify_chunk_upload_descriptors(const VerifyChunk& ch, const VerifyDevBufs& b, hipStream_t st) {
     hipError_t e = hipMemcpyAsync(b.proofs, ch.proofs.data(), ch.proofs.size() * sizeof(VQProof), hipMemcpyHostToDevice, st);
+    if (ch.query_proof.empty()) return e == hipSuccess ? hipMemsetAsync(b.bad, 0, ch.proofs.size() * 4, st) : e;  // num_query_rounds = 0
     if (e == hipSuccess) e = hipMemcpyAsync(b.leaves, ch.leaves.data(), ch.leaves.size() * sizeof(VQLeaf), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(b.qproof, ch.query_proof.data(), ch.query_proof.size() * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(b.xidx, ch.x_index.data(), ch.x_index.size() * 8, hipMemcpyHostToDevice, st);
@@ -416,7 +417,7 @@ int verify_batch_device(Ctx* c, size_t n, const starkhip_air_t* airs, const star
             VHIP(event_wait_sleeping(m.ev[2]));
             status.resize(ch.query_proof.size());
             bad.resize(ch.proofs.size());
-            VHIP(hipMemcpy(status.data(), b.status, status.size() * 4, hipMemcpyDeviceToHost));
+            if (!status.empty()) VHIP(hipMemcpy(status.data(), b.status, status.size() * 4, hipMemcpyDeviceToHost));
             VHIP(hipMemcpy(bad.data(), b.bad, bad.size() * 4, hipMemcpyDeviceToHost));
             float up = 0, dev = 0;
             VHIP(hipEventElapsedTime(&up, m.ev[0], m.ev[1]));

@@ -279,7 +279,7 @@ int VerifyService::launch(Half& h, std::vector<Req*>& reqs, bool whole) {
     if (e == hipSuccess) e = hipEventRecord(h.ev[1], st_);
     if (e == hipSuccess) e = verify_chunk_launch(h.ch, b, st_);
     const size_t nq = h.ch.query_proof.size(), np = h.ch.proofs.size();
-    if (e == hipSuccess) e = hipMemcpyAsync(h.results, b.status, nq * 4, hipMemcpyDeviceToHost, st_);
+    if (e == hipSuccess && nq) e = hipMemcpyAsync(h.results, b.status, nq * 4, hipMemcpyDeviceToHost, st_);
     if (e == hipSuccess) e = hipMemcpyAsync(h.results + nq, b.bad, np * 4, hipMemcpyDeviceToHost, st_);
     if (e == hipSuccess) e = hipEventRecord(h.ev[2], st_);
     if (e != hipSuccess) {
