@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/starkhip.h"
+#include "air_ir.h"
 #include "gl.h"
 
 namespace starkhip {
@@ -42,9 +43,11 @@ struct FriGeometry {
     }
 };
 
-// log2 of the quotient degree factor (degree - 1, at least 1) of an AIR of constraint degree `degree`; a config needs rate_bits >= it
+// the quotient degree factor of an AIR of constraint degree `degree`: degree - 1, at least 1 (a proof has 2 x factor quotient polynomials)
+inline unsigned quotient_factor(unsigned degree) { return degree > 1 ? degree - 1 : 1; }
+// log2 of it, rounded up; a config needs rate_bits >= it
 inline unsigned quotient_degree_bits(unsigned degree) {
-    const unsigned factor = degree > 1 ? degree - 1 : 1;
+    const unsigned factor = quotient_factor(degree);
     unsigned qdb = 0;
     while ((1u << qdb) < factor) qdb++;
     return qdb;
@@ -59,6 +62,15 @@ struct ProofLayout {
         off_pow, off_pis, total;
     std::vector<size_t> layer_depth;  // siblings per FRI layer
 
+    // the layout of a proof of AIR program `P` with 2^log_n rows under `cfg` (`geo`: FriGeometry::make(cfg, log_n))
+    static ProofLayout make(const AirProgram& P, const starkhip_config_t& cfg, const FriGeometry& geo, unsigned log_n) {
+        ProofLayout pl;
+        pl.C = P.n_cols; pl.Q = (size_t)quotient_factor(P.degree) * 2; pl.log_n = log_n; pl.rate_bits = cfg.rate_bits; pl.cap_h = cfg.cap_height;
+        pl.L = geo.arities.size(); pl.n_queries = cfg.num_query_rounds; pl.final_len = geo.final_poly_len; pl.n_pis = P.n_pis;
+        pl.arity_bits = cfg.arity_bits; pl.n_challenges = 2;
+        pl.compute();
+        return pl;
+    }
     void compute() {
         ncap = (size_t)1 << cap_h;
         log_N = log_n + rate_bits;

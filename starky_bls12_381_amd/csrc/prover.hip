@@ -1,7 +1,8 @@
 // Host driver of the GPU prover: the MI355X-native replacement of starky::prover::prove as called at
-// /root/reference/src/aggregate_proof.rs:59-65 (and :105, :138, :169).  Follows the transcript of
-// SURVEY.md App. A.5 step by step; every heavy step is one of the kernels in kernels_*.hip, the host
-// only runs the Fiat-Shamir challenger, two length-n synthetic divisions and the proof assembly.
+// /root/reference/src/aggregate_proof.rs:59-65 (and :105, :138, :169).  prove() follows the transcript of SURVEY.md App. A.5 as a list
+// of phases (the methods of ProveCall), sized and laid out by one ProofShape and one table of work buffers that ctx_reserve() shares;
+// every heavy step is one of the kernels in kernels_*.hip, the host only runs the Fiat-Shamir challenger, two length-n synthetic
+// divisions and the proof assembly.  Below prove(): the pool's reservation and the kernel-level entry points of the tests.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -67,22 +68,21 @@ struct PhaseRanges {
         }                                                                                                  \
     } while (0)
 
-struct DevBuf {
+struct DevBuf {  // device memory that goes with its owner (a Ctx, or cached tables / a plan that were never finished); not copied anywhere
     void* p = nullptr;
     size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
+    ~DevBuf() { release(); }
     void release() {
         if (p) (void)hipFree(p);
         p = nullptr;
         cap = 0;
+    }
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
     }
     template <class T>
     T* as() const { return (T*)p; }
@@ -126,12 +126,14 @@ struct Ctx {
         DevBuf tw_fwd, tw_inv, coset_scale, qtab, qshift_inv;
         DevBuf lde2_fwd, lde2_inv, lde2_cs, lde2_oh;  // kernels_lde.hip tables (log_n >= 8)
         DevBuf lde_wave;                               // ... and of its wave-resident kernel (log_n == 13)
+        std::vector<DevBuf*> bufs() { return {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave}; }
     };
     struct PlanDev {  // tiled plan (quotient_plan.h) of one AIR on the device
         int air = -1;
         unsigned chunks = 0, want = 0;
         uint32_t recs = 0;
         DevBuf q_recs, q_streams, q_chunk_tile_off, q_tile_list, q_contrib_off, q_contribs, q_consts, q_apow;
+        std::vector<DevBuf*> bufs() { return {&q_recs, &q_streams, &q_chunk_tile_off, &q_tile_list, &q_contrib_off, &q_contribs, &q_consts, &q_apow}; }
     };
     std::vector<std::unique_ptr<Tables>> table_cache;
     std::vector<std::unique_ptr<PlanDev>> plan_cache;
@@ -159,17 +161,31 @@ struct Ctx {
     int chk_air = -1;
     unsigned chk_want = 0, chk_chunks = 0;
     DevBuf d_chk_ops, d_chk_meta, d_chk_out;
-    // work buffers
+    // work buffers of a proof: work_buffers() below is the one table of their sizes (prove() and ctx_reserve() allocate from it)
     // `lde` is the one big buffer (19.3 GB for FinalExp).  Before the LDE kernel writes it, it holds everything that waits for that
     // kernel: the trace columns as its LAST quarter (the LDE goes out in launches that overwrite only columns already transformed:
     // run_lde_trace) and, at its start, the upload staging (row-major rows before the transpose, a recording's words before the
     // expansion).  Coefficients are the LDE kernel's scratch inside a column's own block and are not kept: openings and the FRI
     // combination read coset 0 of the LDE (kernels_fri.hip).  `values` is the 1/64 of the columns the last LDE launch reads (75 MB), a
     // whole trace only for rate_bits == 0, and starkhip_lde_batch's in-place values / coefficients.  Together 19.6 GB per FinalExp
-    // context; rounds 1-3: values + coefficients + staging + LDE = 33.7 GB.
+    // context; rounds 1-3: values + coefficients + staging + LDE = 33.7 GB.  `staging` serves the kernel-level test entries
+    // (expand_log, permute_batch, field_ops) alone.
     DevBuf staging, values, lde, digests, pis, apow, chunk_scale, partial, qvals, qcoef, qlde, qdigests, zpow, gzpow, open_local,
         open_next, open_q, ext_apow, comb_partial, comb_out, fri_coef, fri_vals, fri_rows[16], fri_digests[16], scale_tab, pow_state,
-        pow_best, qidx, gather_t, gather_q;
+        pow_best, qidx, gather_t;
+    // every device buffer the context holds, cached tables and plans included: what ctx_destroy releases and ctx_device_bytes adds up
+    std::vector<DevBuf*> dev_bufs() {
+        std::vector<DevBuf*> v = {&d_ops, &d_loads, &d_chunk_off, &d_chk_ops, &d_chk_meta, &d_chk_out, &staging, &values, &lde, &digests, &pis,
+                                  &apow, &chunk_scale, &partial, &qvals, &qcoef, &qlde, &qdigests, &zpow, &gzpow, &open_local, &open_next, &open_q,
+                                  &ext_apow, &comb_partial, &comb_out, &fri_coef, &fri_vals, &scale_tab, &pow_state, &pow_best, &qidx, &gather_t};
+        for (DevBuf& b : fri_rows) v.push_back(&b);
+        for (DevBuf& b : fri_digests) v.push_back(&b);
+        for (auto& t : table_cache)
+            for (DevBuf* b : t->bufs()) v.push_back(b);
+        for (auto& d : plan_cache)
+            for (DevBuf* b : d->bufs()) v.push_back(b);
+        return v;
+    }
 };
 
 // Wait for everything enqueued on the context's stream -- SLEEPING, not spinning: the wait goes through an event created with
@@ -231,15 +247,8 @@ static int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb) {
             c->tab = t.get();
             return 0;
         }
-    std::unique_ptr<Ctx::Tables> fresh(new Ctx::Tables());
+    std::unique_ptr<Ctx::Tables> fresh(new Ctx::Tables());  // a half-built set of tables is not kept: it goes with `fresh`, buffers and all
     Ctx::Tables* T = fresh.get();
-    struct Release {  // a half-built set of tables is not kept
-        Ctx::Tables* t;
-        ~Release() {
-            if (!t) return;
-            for (DevBuf* b : {&t->tw_fwd, &t->tw_inv, &t->coset_scale, &t->qtab, &t->qshift_inv, &t->lde2_fwd, &t->lde2_inv, &t->lde2_cs, &t->lde2_oh, &t->lde_wave}) b->release();
-        }
-    } guard{T};
     const unsigned log_N = log_n + rate;
     const size_t N = (size_t)1 << log_N, size = (size_t)1 << (log_n + qdb);
     HIPCHK(T->tw_fwd.ensure(N / 2 * 8 + 8));
@@ -267,7 +276,6 @@ static int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb) {
     T->log_n = log_n;
     T->rate = rate;
     T->qdb = qdb;
-    guard.t = nullptr;
     c->table_cache.push_back(std::move(fresh));
     c->tab = T;
     return 0;
@@ -351,13 +359,6 @@ static int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points) {
     const QTPlan Q = build_quotient_plan(air.prog, want);
     std::unique_ptr<Ctx::PlanDev> fresh(new Ctx::PlanDev());
     Ctx::PlanDev* D = fresh.get();
-    struct Release {
-        Ctx::PlanDev* d;
-        ~Release() {
-            if (!d) return;
-            for (DevBuf* b : {&d->q_recs, &d->q_streams, &d->q_chunk_tile_off, &d->q_tile_list, &d->q_contrib_off, &d->q_contribs, &d->q_consts, &d->q_apow}) b->release();
-        }
-    } guard{D};
     struct Up { DevBuf* b; const void* src; size_t bytes; };
     const std::vector<gl_t>& consts = air.prog.consts;
     const gl_t zero = 0;
@@ -378,7 +379,6 @@ static int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points) {
     D->want = want;
     D->chunks = Q.n_chunks;
     D->recs = (uint32_t)Q.recs.size();
-    guard.d = nullptr;
     c->plan_cache.push_back(std::move(fresh));
     c->plan = D;
     return 0;
@@ -453,18 +453,7 @@ void ctx_destroy(Ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->st);
-    for (auto& t : c->table_cache)
-        for (DevBuf* b : {&t->tw_fwd, &t->tw_inv, &t->coset_scale, &t->qtab, &t->qshift_inv, &t->lde2_fwd, &t->lde2_inv, &t->lde2_cs, &t->lde2_oh, &t->lde_wave}) b->release();
-    for (auto& d : c->plan_cache)
-        for (DevBuf* b : {&d->q_recs, &d->q_streams, &d->q_chunk_tile_off, &d->q_tile_list, &d->q_contrib_off, &d->q_contribs, &d->q_consts, &d->q_apow}) b->release();
-    DevBuf* bufs[] = {&c->d_ops, &c->d_loads, &c->d_chunk_off, &c->d_chk_ops, &c->d_chk_meta, &c->d_chk_out, &c->staging,
-                      &c->values, &c->lde, &c->digests, &c->pis, &c->apow, &c->chunk_scale, &c->partial, &c->qvals, &c->qcoef,
-                      &c->qlde, &c->qdigests, &c->zpow, &c->gzpow, &c->open_local, &c->open_next, &c->open_q, &c->ext_apow, &c->comb_partial,
-                      &c->comb_out, &c->fri_coef, &c->fri_vals, &c->scale_tab, &c->pow_state, &c->pow_best, &c->qidx, &c->gather_t,
-                      &c->gather_q};
-    for (auto b : bufs) b->release();
-    for (auto& b : c->fri_rows) b.release();
-    for (auto& b : c->fri_digests) b.release();
+    for (DevBuf* b : c->dev_bufs()) b->release();
     for (auto& e : c->ev) (void)hipEventDestroy(e);
     for (auto& e : c->kev) (void)hipEventDestroy(e);
     if (c->rb) (void)hipHostFree(c->rb);
@@ -522,17 +511,7 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
 }
 size_t ctx_device_bytes(Ctx* c) {
     size_t total = 0;
-    for (auto& t : c->table_cache)
-        for (DevBuf* b : {&t->tw_fwd, &t->tw_inv, &t->coset_scale, &t->qtab, &t->qshift_inv, &t->lde2_fwd, &t->lde2_inv, &t->lde2_cs, &t->lde2_oh, &t->lde_wave}) total += b->cap;
-    for (auto& d : c->plan_cache)
-        for (DevBuf* b : {&d->q_recs, &d->q_streams, &d->q_chunk_tile_off, &d->q_tile_list, &d->q_contrib_off, &d->q_contribs, &d->q_consts, &d->q_apow}) total += b->cap;
-    DevBuf* bufs[] = {&c->d_ops, &c->d_loads, &c->d_chunk_off, &c->d_chk_ops, &c->d_chk_meta, &c->d_chk_out, &c->staging, &c->values, &c->lde, &c->digests, &c->pis, &c->apow, &c->chunk_scale, &c->partial,
-                      &c->qvals, &c->qcoef, &c->qlde, &c->qdigests, &c->zpow, &c->gzpow, &c->open_local, &c->open_next, &c->open_q, &c->ext_apow,
-                      &c->comb_partial, &c->comb_out, &c->fri_coef, &c->fri_vals, &c->scale_tab, &c->pow_state, &c->pow_best, &c->qidx, &c->gather_t,
-                      &c->gather_q};
-    for (auto b : bufs) total += b->cap;
-    for (auto& b : c->fri_rows) total += b.cap;
-    for (auto& b : c->fri_digests) total += b.cap;
+    for (DevBuf* b : c->dev_bufs()) total += b->cap;
     return total;
 }
 size_t ctx_pinned_bytes(Ctx* c) { return c->host_staging_cap + c->rb_cap; }
@@ -564,386 +543,403 @@ struct HostWatch {  // accumulates wall time of the host-side stretches of prove
     void start() { t0 = std::chrono::steady_clock::now(); }
     void stop() { ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
-}  // namespace
 
-int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* trace, size_t n_rows, int layout, int on_device,
-          const uint64_t* pis_host, size_t n_pis, uint64_t pow_witness, uint64_t** proof_out, size_t* proof_words) {
-    struct ReadBackGuard {  // an early return between a read_back() and its stream_wait() must not leave destinations of this call behind
-        Ctx* c;
-        ~ReadBackGuard() {
-            c->rb_pending.clear();
-            c->rb_used = 0;
+// fn(0) .. fn(n_threads - 1) side by side: fn(0) on the calling thread, the others on helper threads created for this call; where no
+// thread is to be had the calling thread does that share too
+template <class F>
+static void run_on_helpers(unsigned n_threads, const F& fn) {
+    std::vector<std::thread> helpers;
+    for (unsigned w = 1; w < n_threads; w++) {
+        try {
+            helpers.emplace_back(fn, w);
+        } catch (const std::system_error&) {
+            fn(w);
         }
-    } read_back_guard{c};
-    const AirProgram& P = air.prog;
-    unsigned log_n = 0;
-    while (((size_t)1 << log_n) < n_rows) log_n++;
-    if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || n_pis != P.n_pis || cfg.num_challenges != 2 || log_n > 13) return STARKHIP_ERR_BAD_SHAPE;
+    }
+    fn(0);
+    for (std::thread& t : helpers) t.join();
+}
+
+// The context's page-locked upload staging holds at least `need` bytes; where it does not, it is replaced by one of `grow_to` (>= need)
+// bytes -- hipHostFree + hipHostMalloc wait for the device, so every caller grows by its own policy to make that rare
+static hipError_t ensure_host_staging(Ctx* c, size_t need, size_t grow_to) {
+    if (c->host_staging_cap >= need) return hipSuccess;
+    if (c->host_staging) (void)hipHostFree(c->host_staging);
+    c->host_staging = nullptr;
+    c->host_staging_cap = 0;
+    const hipError_t e = hipHostMalloc(&c->host_staging, grow_to, hipHostMallocDefault);
+    if (e == hipSuccess) c->host_staging_cap = grow_to;
+    return e;
+}
+
+// Where a recording lands in the ONE array of 32-bit words that expand_trace_kernel / zero_cells_kernel read.  A log recorded by several
+// threads comes in parts (trace_log.h): each part's words land at its base, then the parts' offsets (already shifted by that base) back
+// to back, then their late zeros.
+struct LogPiece { size_t at; const uint32_t* src; size_t words; };
+static std::vector<LogPiece> recording_pieces(const TraceLog& log) {
+    const size_t nw = log.total_words(), nr = log.total_records();
+    std::vector<LogPiece> pieces;
+    size_t at_r = 0, at_z = 0;
+    log.for_each_part([&](const TraceLog& part) {
+        if (!part.words.empty()) pieces.push_back({part.base, part.words.data(), part.words.size()});
+        if (!part.offsets.empty()) pieces.push_back({nw + at_r, part.offsets.data(), part.offsets.size()});
+        if (!part.late_zeros.empty()) pieces.push_back({nw + nr + at_z, part.late_zeros.data(), part.late_zeros.size()});
+        at_r += part.offsets.size();
+        at_z += part.late_zeros.size();
+    });
+    return pieces;
+}
+
+// A dense trace of n rows x C columns into column-major device memory: `*d_values` is where it is afterwards -- `dst`, or the caller's
+// own column-major device memory (read only).  Row-major host rows go up into the start of the LDE buffer (idle until the LDE kernel
+// writes it; C n words) and are transposed from there.
+static int upload_dense(Ctx* c, const uint64_t* trace, int layout, int on_device, size_t n, size_t C, gl_t* dst, const gl_t** d_values) {
+    *d_values = dst;
+    if (on_device && layout == 1) *d_values = trace;
+    else if (on_device) HIPCHK(launch_transpose(trace, dst, n, C, c->st));
+    else if (layout == 1) HIPCHK(hipMemcpyAsync(dst, trace, C * n * 8, hipMemcpyHostToDevice, c->st));
+    else {
+        HIPCHK(hipMemcpyAsync(c->lde.p, trace, C * n * 8, hipMemcpyHostToDevice, c->st));
+        HIPCHK(launch_transpose(c->lde.as<gl_t>(), dst, n, C, c->st));
+    }
+    return 0;
+}
+
+// The leaf hash of a LONE context's commitment in the form use_pair_form / use_row_form / "leaf_hash_form" pick; `*form` says which
+// (HashService::Timing::form)
+static hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form) {
+    *form = c->opt_leaf_hash_form == 3 ? 3 : use_pair_form(c, n_cols, log_n + rate) ? 5 : use_row_form(c, n_cols, log_n + rate) ? 1 : 0;
+    if (*form == 3) return launch_leaf_hash_lane(lde, n_cols, log_n, rate, digests, st);
+    if (*form == 5) return launch_leaf_hash_pair(lde, n_cols, log_n, rate, digests, st);
+    if (*form == 1) return launch_leaf_hash_row(lde, n_cols, log_n, rate, digests, st);
+    return launch_leaf_hash(lde, n_cols, log_n, rate, digests, st);
+}
+
+// The dimensions of one proof, derived in one place: prove() and ctx_reserve() size and lay out everything from these.
+struct ProofShape {
+    unsigned log_n, r, cap_h, log_N, qdb, factor;  // log2 of rows, blow-up, cap size, LDE points; the quotient's degree bits and factor
+    size_t n, N, C, Q, size, ncap, L;              // rows, LDE points, trace and quotient columns, quotient points (n << qdb), cap nodes, FRI layers
     FriGeometry geo;
-    if (!FriGeometry::make(cfg, log_n, &geo)) return STARKHIP_ERR_BAD_SHAPE;
-    const unsigned r = cfg.rate_bits, cap_h = cfg.cap_height, log_N = log_n + r;
-    const unsigned factor = P.degree > 1 ? P.degree - 1 : 1;
-    unsigned qdb = 0;
-    while ((1u << qdb) < factor) qdb++;
-    if (qdb > r) return STARKHIP_ERR_BAD_SHAPE;
-    for (size_t i = 0; i < n_pis; i++)
-        if (pis_host[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
-    const size_t n = n_rows, N = n << r, C = P.n_cols, Q = (size_t)factor * 2, size = n << qdb, ncap = (size_t)1 << cap_h;
-    const size_t L = geo.arities.size();
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->st;
-    int rc;
-    if ((rc = ensure_tables(c, log_n, r, qdb))) return rc;
-    const bool tiled = c->opt_quotient_impl == 0;
-    if ((rc = tiled ? ensure_plan(c, air, size) : ensure_program(c, air, size))) return rc;
-    const unsigned n_chunks = tiled ? c->plan->chunks : c->prog_chunks;
-
-    // ---- buffers
-    // The trace waits for the LDE INSIDE the buffer the LDE is written to, as its last C n words (trace_in_lde: run_lde_trace below);
-    // a separate buffer only when there is no room beside it (rate_bits == 0, or a recording longer than the rest of the buffer).
-    size_t park_words = 0;  // what the upload parks at the start of the LDE buffer, in 64-bit words
-    if (layout == 2) {
-        const TraceLog* log = (const TraceLog*)trace;
-        park_words = (log->total_words() + log->total_records() + log->total_late_zeros() + 2 + 1) / 2;
-    } else if (!on_device && layout == 0) {
-        park_words = C * n;
+    ProofLayout pl;
+    // STARKHIP_ERR_BAD_SHAPE for what prove() refuses: rows that are no power of two in 2 .. 8192, a config that the one config rule
+    // (FriGeometry::make) refuses or whose blow-up is below the AIR's quotient degree
+    static int make(const AirProgram& P, const starkhip_config_t& cfg, size_t n_rows, ProofShape* s) {
+        unsigned log_n = 0;
+        while (((size_t)1 << log_n) < n_rows) log_n++;
+        if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || cfg.num_challenges != 2 || log_n > 13) return STARKHIP_ERR_BAD_SHAPE;
+        if (!FriGeometry::make(cfg, log_n, &s->geo) || quotient_degree_bits(P.degree) > cfg.rate_bits) return STARKHIP_ERR_BAD_SHAPE;
+        s->log_n = log_n; s->r = cfg.rate_bits; s->cap_h = cfg.cap_height; s->log_N = log_n + s->r;
+        s->qdb = quotient_degree_bits(P.degree); s->factor = quotient_factor(P.degree);
+        s->n = n_rows; s->N = s->n << s->r; s->C = P.n_cols; s->Q = (size_t)s->factor * 2; s->size = s->n << s->qdb;
+        s->ncap = (size_t)1 << s->cap_h; s->L = s->geo.arities.size();
+        s->pl = ProofLayout::make(P, cfg, s->geo, log_n);
+        return STARKHIP_OK;
     }
-    const bool trace_in_lde = r >= 1 && park_words <= (((size_t)1 << r) - 1) * C * n && !(on_device && layout == 1);
-    if (trace_in_lde) HIPCHK(c->values.ensure(lde_tail_columns(C) * n * 8));  // the columns the last LDE launch reads (run_lde_trace)
-    else if (!(on_device && layout == 1)) HIPCHK(c->values.ensure(C * n * 8));
-    HIPCHK(c->lde.ensure(std::max(C * N * 8, park_words * 8)));
-    gl_t* const d_trace = trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>();
-    HIPCHK(c->digests.ensure(digest_words(N) * 8));
-    HIPCHK(c->pis.ensure(std::max<size_t>(1, n_pis) * 8));
-    HIPCHK(c->apow.ensure(2 * (AIR_MAX_GROUP + 1) * 8));
-    HIPCHK(c->chunk_scale.ensure(2 * n_chunks * 8));
-    HIPCHK(c->partial.ensure((size_t)n_chunks * 2 * size * 8));
-    HIPCHK(c->qvals.ensure(2 * size * 8));
-    HIPCHK(c->qcoef.ensure(Q * n * 8));
-    HIPCHK(c->qlde.ensure(Q * N * 8));
-    HIPCHK(c->qdigests.ensure(digest_words(N) * 8));
-    HIPCHK(c->zpow.ensure(2 * n * 16));  // powers of zeta (the quotient polynomials' openings), then the coset-0 weights of zeta
-    HIPCHK(c->gzpow.ensure(n * 16));     // the weights of g zeta
-    HIPCHK(c->open_local.ensure(C * 16));
-    HIPCHK(c->open_next.ensure(C * 16));
-    HIPCHK(c->open_q.ensure(Q * 16));
-    HIPCHK(c->ext_apow.ensure((C + Q) * 16));
-    const size_t comb_ppc = 256, comb_chunks = (C + comb_ppc - 1) / comb_ppc;
-    HIPCHK(c->comb_partial.ensure(comb_chunks * n * 16));
-    HIPCHK(c->comb_out.ensure(2 * n * 16));
-    HIPCHK(c->fri_coef.ensure(2 * N * 8));
-    HIPCHK(c->fri_vals.ensure(2 * N * 8));
-    HIPCHK(c->scale_tab.ensure(N * 8));
-    HIPCHK(c->pow_state.ensure(12 * 8));
-    HIPCHK(c->pow_best.ensure(8));
-    HIPCHK(c->qidx.ensure(cfg.num_query_rounds * 4));
+};
 
-    int evi = 0;
-    PhaseRanges ranges;  // rocTX ranges named like the phases of starkhip_last_timings (visible with rocprofv3 --marker-trace)
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:upload");
+// fri_combine_kernel sums the trace columns in chunks of this many, one partial sum per chunk (comb_partial)
+static const size_t COMB_PPC = 256;
+static size_t comb_chunks(size_t C) { return (C + COMB_PPC - 1) / COMB_PPC; }
 
-    // ---- phase 0: trace into column-major device memory (trace_rows_to_poly_values)
-    const gl_t* d_values;
-    if (layout == 2) {  // compact trace: upload the generator's write log and expand it here
-        const TraceLog* log = (const TraceLog*)trace;
-        const size_t nw = log->total_words(), nr = log->total_records(), nz = log->total_late_zeros();
-        if (log->rows != n || log->cols != C) return STARKHIP_ERR_BAD_SHAPE;
-        uint32_t* d_words = c->lde.as<uint32_t>();  // the recording's words wait at the start of the (still unused) LDE buffer
-        uint32_t* d_offsets = d_words + nw;
-        uint32_t* d_zeros = d_offsets + nr;
-        HIPCHK(hipMemsetAsync(d_trace, 0, C * n * 8, st));
-        {  // A log recorded by several threads comes in parts (trace_log.h): each part's words land at its base, its offsets
-           // (already shifted by that base) and late zeros back to back.  The parts are gathered into ONE page-locked staging
-           // buffer of the context and go up as ONE copy: a FinalExp recording has 53 parts x 3 arrays, and on a GPU that other
-           // proofs keep busy every one of 160 dependent stream operations waits its turn (measured: 0.9 - 1.6 s of "upload" for a
-           // proof whose copies queued behind other proofs' commitments, against 6 ms alone).
-            const size_t total = nw + nr + nz;
-            if (c->host_staging_cap < total * 4) {
-                if (c->host_staging) (void)hipHostFree(c->host_staging);
-                c->host_staging = nullptr;
-                c->host_staging_cap = 0;
-                const size_t want = total * 4 + total;  // + 25 %: the next recording of this AIR is about as long
-                HIPCHK(hipHostMalloc(&c->host_staging, want, hipHostMallocDefault));
-                c->host_staging_cap = want;
-            }
-            uint32_t* h = (uint32_t*)c->host_staging;
-            size_t at_r = 0, at_z = 0;
-            struct Piece { uint32_t* dst; const uint32_t* src; size_t words; };
-            std::vector<Piece> pieces;
-            log->for_each_part([&](const TraceLog& part) {
-                if (!part.words.empty()) pieces.push_back({h + part.base, part.words.data(), part.words.size()});
-                if (!part.offsets.empty()) pieces.push_back({h + nw + at_r, part.offsets.data(), part.offsets.size()});
-                if (!part.late_zeros.empty()) pieces.push_back({h + nw + nr + at_z, part.late_zeros.data(), part.late_zeros.size()});
-                at_r += part.offsets.size();
-                at_z += part.late_zeros.size();
-            });
-            // 150 MB for FinalExp: gathered on a few threads (10 ms on one), pieces dealt round-robin
-            const unsigned n_thr = total * 4 > ((size_t)32 << 20) ? 4 : 1;
-            auto gather = [&](unsigned w) {
-                for (size_t i = w; i < pieces.size(); i += n_thr) memcpy(pieces[i].dst, pieces[i].src, pieces[i].words * 4);
-            };
-            std::vector<std::thread> helpers;
-            for (unsigned w = 1; w < n_thr; w++) {
-                try {
-                    helpers.emplace_back(gather, w);
-                } catch (const std::system_error&) {
-                    gather(w);  // no thread to be had: this one does that share too
-                }
-            }
-            gather(0);
-            for (std::thread& t : helpers) t.join();
-            if (total) HIPCHK(hipMemcpyAsync(d_words, h, total * 4, hipMemcpyHostToDevice, st));
-        }
-        if (nr) HIPCHK(launch_expand_trace(d_words, d_offsets, nr, d_trace, n, st));
-        if (nz) HIPCHK(launch_zero_cells(d_zeros, nz / 2, d_trace, n, st));
-        d_values = d_trace;
-    } else if (layout == 3) {
-        // The literal argument of starky's prove(): `Vec<PolynomialValues<F>>`, one heap allocation per column
-        // (/root/reference/src/aggregate_proof.rs:168-175) -- `trace` is a table of C column pointers.  C separate pageable copies of
-        // 64 KB would each be staged by the runtime (73 527 of them for FinalExp); instead host threads gather runs of columns into
-        // the two halves of the context's page-locked staging and every half goes up as one copy, the gather of the next half under
-        // the copy of this one.  Column-major device memory is just the columns back to back.
-        const uint64_t* const* cols = (const uint64_t* const*)trace;
-        const size_t col_bytes = n * 8;
-        if (c->host_staging_cap < 2 * col_bytes || c->host_staging_cap < ((size_t)32 << 20)) {
-            const size_t want = std::max<size_t>(2 * col_bytes, (size_t)128 << 20);
-            if (c->host_staging_cap < want) {
-                if (c->host_staging) (void)hipHostFree(c->host_staging);
-                c->host_staging = nullptr;
-                c->host_staging_cap = 0;
-                HIPCHK(hipHostMalloc(&c->host_staging, want, hipHostMallocDefault));
-                c->host_staging_cap = want;
-            }
-        }
-        for (auto& e : c->col_ev)
-            if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
-        const size_t half_bytes = c->host_staging_cap / 2, per_half = std::max<size_t>(1, half_bytes / col_bytes);
-        bool used[2] = {false, false};
-        unsigned h = 0;
-        for (size_t c0 = 0; c0 < C; c0 += per_half, h ^= 1) {
-            const size_t cnt = std::min(per_half, C - c0);
-            char* dst = (char*)c->host_staging + (size_t)h * half_bytes;
-            if (used[h]) HIPCHK(event_wait_sleeping(c->col_ev[h]));  // the copy that last read this half has run
-            const unsigned n_thr = cnt * col_bytes > ((size_t)8 << 20) ? 4 : 1;
-            auto gather = [&](unsigned w) {
-                for (size_t i = w; i < cnt; i += n_thr) memcpy(dst + i * col_bytes, cols[c0 + i], col_bytes);
-            };
-            std::vector<std::thread> helpers;
-            for (unsigned w = 1; w < n_thr; w++) {
-                try {
-                    helpers.emplace_back(gather, w);
-                } catch (const std::system_error&) {
-                    gather(w);
-                }
-            }
-            gather(0);
-            for (std::thread& t : helpers) t.join();
-            HIPCHK(hipMemcpyAsync(d_trace + c0 * n, dst, cnt * col_bytes, hipMemcpyHostToDevice, st));
-            HIPCHK(hipEventRecord(c->col_ev[h], st));
-            used[h] = true;
-        }
-        d_values = d_trace;
-    } else if (on_device && layout == 1) {
-        d_values = trace;  // the caller's memory: read only
-    } else if (on_device) {
-        HIPCHK(launch_transpose(trace, d_trace, n, C, st));
-        d_values = d_trace;
-    } else if (layout == 1) {
-        HIPCHK(hipMemcpyAsync(d_trace, trace, C * n * 8, hipMemcpyHostToDevice, st));
-        d_values = d_trace;
-    } else {
-        // row-major host rows: up into the start of the LDE buffer (idle until the LDE kernel writes it), transposed from there
-        HIPCHK(hipMemcpyAsync(c->lde.p, trace, C * n * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(launch_transpose(c->lde.as<gl_t>(), d_trace, n, C, st));
-        d_values = d_trace;
+// THE size of every work buffer of a proof of shape `s` whose quotient is evaluated in `n_chunks` chunks.  prove() and ctx_reserve()
+// both allocate from this list, so a context that a pool has warmed never grows a buffer inside a proof (see ctx_reserve).  What the
+// two do not share is theirs to say: `values_bytes` (a whole trace, the tail of run_lde_trace, or nothing) and `park_bytes`, what
+// the upload stages at the start of the LDE buffer.
+struct BufWant { DevBuf* b; size_t bytes; };
+static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n_chunks, size_t values_bytes, size_t park_bytes) {
+    const size_t n = s.n, N = s.N, C = s.C, Q = s.Q, size = s.size, nq = s.pl.n_queries;
+    std::vector<BufWant> w = {
+        {&c->values, values_bytes}, {&c->lde, std::max(C * N * 8, park_bytes)}, {&c->digests, digest_words(N) * 8},
+        {&c->pis, std::max<size_t>(1, s.pl.n_pis) * 8}, {&c->apow, 2 * (AIR_MAX_GROUP + 1) * 8}, {&c->chunk_scale, 2 * (size_t)n_chunks * 8},
+        {&c->partial, (size_t)n_chunks * 2 * size * 8}, {&c->qvals, 2 * size * 8}, {&c->qcoef, Q * n * 8}, {&c->qlde, Q * N * 8},
+        {&c->qdigests, digest_words(N) * 8},
+        {&c->zpow, 2 * n * 16},  // powers of zeta (the quotient polynomials' openings), then the coset-0 weights of zeta
+        {&c->gzpow, n * 16},     // the weights of g zeta
+        {&c->open_local, C * 16}, {&c->open_next, C * 16}, {&c->open_q, Q * 16}, {&c->ext_apow, (C + Q) * 16},
+        {&c->comb_partial, comb_chunks(C) * n * 16}, {&c->comb_out, 2 * n * 16}, {&c->fri_coef, 2 * N * 8}, {&c->fri_vals, 2 * N * 8},
+        {&c->scale_tab, N * 8}, {&c->pow_state, 12 * 8}, {&c->pow_best, 8}, {&c->qidx, nq * 4},
+        {&c->gather_t, nq * s.pl.query_words * 8}};  // every query round's leaves and Merkle paths, in proof layout
+    size_t len = N;
+    for (size_t l = 0; l < s.L; l++) {  // a FRI layer's leaves and digests stay on the device for the query phase
+        w.push_back({&c->fri_rows[l], len * 2 * 8});
+        len >>= s.geo.arities[l];
+        w.push_back({&c->fri_digests[l], digest_words(len) * 8});
     }
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:ifft_lde");
+    return w;
+}
 
-    // ---- phase 1: IFFT + LDE (PolynomialBatch::from_values, App. A.3)
+// What one prove() call carries from phase to phase, and the phases: named like the entries of starkhip_last_timings and the rocTX
+// ranges, run by prove() in that order.  Each enqueues its work on the context's stream; where the host needs a result it requests a
+// read-back that the NEXT phase's first stream_wait completes -- prove() records the phase boundary in between -- so the host vectors
+// those land in live here.  A vector that one phase alone fills and reads is local to it, in front of the stream_wait that lets it go.
+struct ProveCall {
+    Ctx* c;
+    const AirInfo& air;
+    const starkhip_config_t& cfg;
+    const ProofShape& s;
+    hipStream_t st;
+    const uint64_t *trace, *pis_host;  // prove()'s arguments
+    int layout, on_device;
+    uint64_t pow_witness;
+    bool tiled;          // the quotient's evaluator: the tiled plan, or the op-stream interpreter
+    unsigned n_chunks;   // ... and the chunks its constraints are cut into
+    bool trace_in_lde;   // the trace waits for the LDE inside the LDE buffer, as its last C n words (run_lde_trace)
+    gl_t* d_trace;       // where the upload puts the trace, column-major
+    const gl_t* d_values = nullptr;  // where it is: d_trace, or the caller's own device memory
+    Challenger ch;
+    HostWatch fs, host_other;  // Fiat-Shamir hashing / other host arithmetic of this proof
+    std::vector<gl_t> trace_cap, quot_cap, quot_tail, fri_caps;
+    std::vector<gl2_t> op_local, op_next, op_q, final_poly;
+    gl_t alphas[2] = {0, 0};
+    gl2_t zeta = gl2_zero();
+    uint64_t* out = nullptr;  // the proof blob, from queries() on
+    int upload(), ifft_lde(), trace_merkle(), quotient(), quotient_commit(), openings(), fri_combine(), fri_commit(), pow(), queries();
+    int upload_recording(const TraceLog* log), upload_column_table(const uint64_t* const* cols), leaf_hash_on_host();
+    int run_quotient_tiles(unsigned debug_mode, gl_t* qvals_out, bool timed), run_quotient_ops(), compare_quotient_evaluators();
+};
+
+// ---- phase 0: trace into column-major device memory (trace_rows_to_poly_values), by layout
+// compact trace: upload the generator's write log and expand it here
+int ProveCall::upload_recording(const TraceLog* log) {
+    const size_t n = s.n, C = s.C;
+    const size_t nw = log->total_words(), nr = log->total_records(), nz = log->total_late_zeros();
+    if (log->rows != n || log->cols != C) return STARKHIP_ERR_BAD_SHAPE;
+    uint32_t* d_words = c->lde.as<uint32_t>();  // the recording's words wait at the start of the (still unused) LDE buffer
+    uint32_t* d_offsets = d_words + nw;
+    uint32_t* d_zeros = d_offsets + nr;
+    HIPCHK(hipMemsetAsync(d_trace, 0, C * n * 8, st));
+    // The parts (recording_pieces) are gathered into ONE page-locked staging buffer of the context and go up as ONE copy: a FinalExp
+    // recording has 53 parts x 3 arrays, and on a GPU that other proofs keep busy every one of 160 dependent stream operations waits
+    // its turn (measured: 0.9 - 1.6 s of "upload" for a proof whose copies queued behind other proofs' commitments, against 6 ms alone).
+    const size_t total = nw + nr + nz;
+    HIPCHK(ensure_host_staging(c, total * 4, total * 4 + total));  // + 25 %: the next recording of this AIR is about as long
+    uint32_t* h = (uint32_t*)c->host_staging;
+    const std::vector<LogPiece> pieces = recording_pieces(*log);
+    // 150 MB for FinalExp: gathered on a few threads (10 ms on one), pieces dealt round-robin
+    const unsigned n_thr = total * 4 > ((size_t)32 << 20) ? 4 : 1;
+    run_on_helpers(n_thr, [&](unsigned w) {
+        for (size_t i = w; i < pieces.size(); i += n_thr) memcpy(h + pieces[i].at, pieces[i].src, pieces[i].words * 4);
+    });
+    if (total) HIPCHK(hipMemcpyAsync(d_words, h, total * 4, hipMemcpyHostToDevice, st));
+    if (nr) HIPCHK(launch_expand_trace(d_words, d_offsets, nr, d_trace, n, st));
+    if (nz) HIPCHK(launch_zero_cells(d_zeros, nz / 2, d_trace, n, st));
+    d_values = d_trace;
+    return 0;
+}
+
+// The literal argument of starky's prove(): `Vec<PolynomialValues<F>>`, one heap allocation per column
+// (/root/reference/src/aggregate_proof.rs:168-175) -- `cols` is a table of C column pointers.  C separate pageable copies of 64 KB would
+// each be staged by the runtime (73 527 of them for FinalExp); instead host threads gather runs of columns into the two halves of
+// the context's page-locked staging and every half goes up as one copy, the gather of the next half under the copy of this one.
+// Column-major device memory is just the columns back to back.
+int ProveCall::upload_column_table(const uint64_t* const* cols) {
+    const size_t n = s.n, C = s.C, col_bytes = n * 8;
+    HIPCHK(ensure_host_staging(c, std::max<size_t>(2 * col_bytes, (size_t)32 << 20), std::max<size_t>(2 * col_bytes, (size_t)128 << 20)));
+    for (auto& e : c->col_ev)
+        if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync));
+    const size_t half_bytes = c->host_staging_cap / 2, per_half = std::max<size_t>(1, half_bytes / col_bytes);
+    bool used[2] = {false, false};
+    unsigned h = 0;
+    for (size_t c0 = 0; c0 < C; c0 += per_half, h ^= 1) {
+        const size_t cnt = std::min(per_half, C - c0);
+        char* dst = (char*)c->host_staging + (size_t)h * half_bytes;
+        if (used[h]) HIPCHK(event_wait_sleeping(c->col_ev[h]));  // the copy that last read this half has run
+        const unsigned n_thr = cnt * col_bytes > ((size_t)8 << 20) ? 4 : 1;
+        run_on_helpers(n_thr, [&](unsigned w) {
+            for (size_t i = w; i < cnt; i += n_thr) memcpy(dst + i * col_bytes, cols[c0 + i], col_bytes);
+        });
+        HIPCHK(hipMemcpyAsync(d_trace + c0 * n, dst, cnt * col_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipEventRecord(c->col_ev[h], st));
+        used[h] = true;
+    }
+    d_values = d_trace;
+    return 0;
+}
+
+int ProveCall::upload() {
+    if (layout == 2) return upload_recording((const TraceLog*)trace);
+    if (layout == 3) return upload_column_table((const uint64_t* const*)trace);
+    return upload_dense(c, trace, layout, on_device, s.n, s.C, d_trace, &d_values);
+}
+
+// ---- phase 1: IFFT + LDE (PolynomialBatch::from_values, App. A.3)
+int ProveCall::ifft_lde() {
     HIPCHK(hipEventRecord(c->kev[4], st));
-    HIPCHK(run_lde_trace(c, d_values, c->lde.as<gl_t>(), c->values.as<gl_t>(), C, log_n, r, trace_in_lde));
+    HIPCHK(run_lde_trace(c, d_values, c->lde.as<gl_t>(), c->values.as<gl_t>(), s.C, s.log_n, s.r, trace_in_lde));
     HIPCHK(hipEventRecord(c->kev[5], st));
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:trace_merkle");
+    return 0;
+}
 
-    // ---- phase 2: Merkle tree over bit-reversed LDE rows
+// A commitment of a few leaves is a latency chain on the GPU whatever the form: FP12Mul (16 rows at blow-up 2) has 32 leaves of
+// 7 536 sequential permutations -- 42 ms in the row form at 5.6 us per permutation on eight waves of a chip that holds 4 096.
+// The host permutation the challenger uses runs at 0.8 us, and 32 independent leaves spread over the process's CPUs: the LDE
+// (15 MB) comes down, host threads hash the leaves, the digests go back up and the tree is built on the device as usual.
+// Same function, same bytes (tests/test_gpu_airs.py: FP12Mul against the oracle).
+int ProveCall::leaf_hash_on_host() {
+    const size_t n = s.n, N = s.N, C = s.C;
+    const unsigned r = s.r, log_N = s.log_N;
+    if (c->hs && !HashService::is_big(s.log_n, r)) {  // a pooled proof was announced to the scheduler's window: it is not coming
+        c->hs->abandon_small();
+        c->hash_requested = true;
+    }
+    c->hash_timing.form = 4;
+    c->hash_timing.group = 1;
+    c->host_lde.resize(C * N);
+    HIPCHK(hipMemcpyAsync(c->host_lde.data(), c->lde.p, C * N * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(c));
+    std::vector<gl_t> leaf_digests(4 * N);
+    const gl_t* lde_h = c->host_lde.data();
+    const unsigned n_thr = (unsigned)std::min<size_t>(N, std::max(1u, cpu_budget()));
+    run_on_helpers(n_thr, [&](unsigned w) {
+        for (size_t j = w; j < N; j += n_thr) {
+            size_t i = 0;  // leaf j holds the LDE row of natural point index bitrev(j) = k * R + s, stored coset-major at [s][k]
+            for (unsigned b = 0; b < log_N; b++) i |= ((j >> b) & 1) << (log_N - 1 - b);
+            const size_t s_ = i & (((size_t)1 << r) - 1), k_ = i >> r;
+            gl_t state[12] = {0};
+            const gl_t* col = lde_h + s_ * n + k_;
+            for (size_t off = 0; off < C; off += 8) {
+                const size_t cnt = std::min<size_t>(8, C - off);
+                for (size_t e = 0; e < cnt; e++) state[e] = col[(off + e) * N];
+                poseidon_permute_host(state);
+            }
+            for (int e = 0; e < 4; e++) leaf_digests[4 * j + e] = state[e];
+        }
+    });
+    HIPCHK(hipMemcpyAsync(c->digests.p, leaf_digests.data(), 4 * N * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(stream_wait(c));  // leaf_digests goes out of scope
+    return 0;
+}
+
+// ---- phase 2: Merkle tree over bit-reversed LDE rows
+int ProveCall::trace_merkle() {
     HIPCHK(hipEventRecord(c->kev[0], st));
-    if (N <= (size_t)c->opt_host_commit_leaves && C >= 64 && c->opt_leaf_hash_form == 0) {
-        // A commitment of a few leaves is a latency chain on the GPU whatever the form: FP12Mul (16 rows at blow-up 2) has 32 leaves of
-        // 7 536 sequential permutations -- 42 ms in the row form at 5.6 us per permutation on eight waves of a chip that holds 4 096.
-        // The host permutation the challenger uses runs at 0.8 us, and 32 independent leaves spread over the process's CPUs: the LDE
-        // (15 MB) comes down, host threads hash the leaves, the digests go back up and the tree is built on the device as usual.
-        // Same function, same bytes (tests/test_gpu_airs.py: FP12Mul against the oracle).
-        if (c->hs && !HashService::is_big(log_n, r)) {  // a pooled proof was announced to the scheduler's window: it is not coming
-            c->hs->abandon_small();
-            c->hash_requested = true;
-        }
-        c->hash_timing.form = 4;
-        c->hash_timing.group = 1;
-        c->host_lde.resize(C * N);
-        HIPCHK(hipMemcpyAsync(c->host_lde.data(), c->lde.p, C * N * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(stream_wait(c));
-        std::vector<gl_t> leaf_digests(4 * N);
-        const gl_t* lde_h = c->host_lde.data();
-        const unsigned n_thr = (unsigned)std::min<size_t>(N, std::max(1u, cpu_budget()));
-        auto work = [&](unsigned w) {
-            for (size_t j = w; j < N; j += n_thr) {
-                size_t i = 0;  // leaf j holds the LDE row of natural point index bitrev(j) = k * R + s, stored coset-major at [s][k]
-                for (unsigned b = 0; b < log_N; b++) i |= ((j >> b) & 1) << (log_N - 1 - b);
-                const size_t s_ = i & (((size_t)1 << r) - 1), k_ = i >> r;
-                gl_t state[12] = {0};
-                const gl_t* col = lde_h + s_ * n + k_;
-                for (size_t off = 0; off < C; off += 8) {
-                    const size_t cnt = std::min<size_t>(8, C - off);
-                    for (size_t e = 0; e < cnt; e++) state[e] = col[(off + e) * N];
-                    poseidon_permute_host(state);
-                }
-                for (int e = 0; e < 4; e++) leaf_digests[4 * j + e] = state[e];
-            }
-        };
-        std::vector<std::thread> helpers;
-        for (unsigned w = 1; w < n_thr; w++) {
-            try {
-                helpers.emplace_back(work, w);
-            } catch (const std::system_error&) {
-                work(w);
-            }
-        }
-        work(0);
-        for (std::thread& t : helpers) t.join();
-        HIPCHK(hipMemcpyAsync(c->digests.p, leaf_digests.data(), 4 * N * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(stream_wait(c));  // leaf_digests goes out of scope
+    if (s.N <= (size_t)c->opt_host_commit_leaves && s.C >= 64 && c->opt_leaf_hash_form == 0) {
+        if (int rc = leaf_hash_on_host()) return rc;
     } else if (c->hs) {  // pooled: the scheduler decides when this commitment runs and which others share its launch
         c->hash_requested = true;
-        HIPCHK(c->hs->hash(c->lde.as<gl_t>(), C, log_n, r, c->digests.as<gl_t>(), st, c->hash_ready, c->hash_done, !HashService::is_big(log_n, r), c->urgent,
+        HIPCHK(c->hs->hash(c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st, c->hash_ready, c->hash_done, !HashService::is_big(s.log_n, s.r), c->urgent,
                            &c->hash_timing));
-    } else if (c->opt_leaf_hash_form == 3) {
-        c->hash_timing.form = 3; c->hash_timing.group = 1;
-        HIPCHK(launch_leaf_hash_lane(c->lde.as<gl_t>(), C, log_n, r, c->digests.as<gl_t>(), st));
-    } else if (use_pair_form(c, C, log_N)) {
-        c->hash_timing.form = 5; c->hash_timing.group = 1;
-        HIPCHK(launch_leaf_hash_pair(c->lde.as<gl_t>(), C, log_n, r, c->digests.as<gl_t>(), st));
-    } else if (use_row_form(c, C, log_N)) {
-        c->hash_timing.form = 1; c->hash_timing.group = 1;
-        HIPCHK(launch_leaf_hash_row(c->lde.as<gl_t>(), C, log_n, r, c->digests.as<gl_t>(), st));
     } else {
-        c->hash_timing.form = 0; c->hash_timing.group = 1;
-        HIPCHK(launch_leaf_hash(c->lde.as<gl_t>(), C, log_n, r, c->digests.as<gl_t>(), st));
+        c->hash_timing.group = 1;
+        HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st, &c->hash_timing.form));
     }
     HIPCHK(hipEventRecord(c->kev[1], st));
-    HIPCHK(launch_merkle_levels(c->digests.as<gl_t>(), log_N, cap_h, st));
-    std::vector<gl_t> trace_cap(4 * ncap), quot_cap(4 * ncap);
-    HIPCHK(read_back(c, trace_cap.data(), c->digests.as<gl_t>() + 4 * level_off(N, log_N - cap_h), 4 * ncap * 8, st));
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:quotient");
-    HIPCHK(stream_wait(c));
+    HIPCHK(launch_merkle_levels(c->digests.as<gl_t>(), s.log_N, s.cap_h, st));
+    trace_cap.resize(4 * s.ncap);
+    HIPCHK(read_back(c, trace_cap.data(), c->digests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
+    return 0;
+}
 
-    HostWatch fs, host_other;  // Fiat-Shamir hashing / other host arithmetic of this proof
-    Challenger ch;
+// The tiled evaluator (quotient_plan.h) with the context's current plan: per-proof weights of the plan's records, one pass over the
+// LDE in LDS-staged column tiles, the chunks' partial sums combined into `qvals_out` ([2][size] words).  `timed`: the pass is the proof's
+// quotient evaluation and is bracketed by kev[2] / kev[3].
+int ProveCall::run_quotient_tiles(unsigned debug_mode, gl_t* qvals_out, bool timed) {
+    const Ctx::PlanDev& D = *c->plan;
+    HIPCHK(launch_quotient_weights(D.q_recs.as<QTRec>(), D.q_contrib_off.as<uint32_t>(), D.q_contribs.as<QTContrib>(), D.recs, D.q_apow.as<gl_t>(),
+                                   air.prog.n_constraints, D.q_consts.as<gl_t>(), c->pis.as<gl_t>(), alphas[0], alphas[1], st));
+    if (timed) HIPCHK(hipEventRecord(c->kev[2], st));
+    HIPCHK(launch_quotient_tiles(D.q_recs.as<QTRec>(), D.q_streams.as<QTStream>(), D.q_chunk_tile_off.as<uint32_t>(), D.q_tile_list.as<uint32_t>(), D.chunks,
+                                 c->lde.as<gl_t>(), c->tab->qtab.as<gl_t>(), c->partial.as<gl_t>(), s.log_n, s.r, s.qdb, (unsigned)s.C, debug_mode, st));
+    if (timed) HIPCHK(hipEventRecord(c->kev[3], st));
+    HIPCHK(launch_quotient_tiles_combine(c->partial.as<gl_t>(), D.chunks, c->tab->qtab.as<gl_t>(), s.log_n, s.qdb, qvals_out, st));
+    return 0;
+}
+
+// The op-stream interpreter (quotient_ops.h; "quotient_impl" = 1, kept as the cross-check) into qvals
+int ProveCall::run_quotient_ops() {
+    std::vector<gl_t> apow(2 * (AIR_MAX_GROUP + 1)), cscale(2 * n_chunks);
+    for (int j = 0; j < 2; j++) {
+        apow[j * (AIR_MAX_GROUP + 1)] = 1;
+        for (unsigned m = 1; m <= AIR_MAX_GROUP; m++) apow[j * (AIR_MAX_GROUP + 1) + m] = gl_mul(apow[j * (AIR_MAX_GROUP + 1) + m - 1], alphas[j]);
+        for (unsigned k = 0; k < n_chunks; k++) cscale[k * 2 + j] = gl_pow(alphas[j], c->chunk_k_after[k]);
+    }
+    HIPCHK(hipMemcpyAsync(c->apow.p, apow.data(), apow.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(c->chunk_scale.p, cscale.data(), cscale.size() * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(c->kev[2], st));
+    HIPCHK(launch_quotient_eval(c->d_ops.as<QOp>(), c->d_loads.as<uint32_t>(), c->prog_slots, c->d_chunk_off.as<uint32_t>(), n_chunks,
+                                c->pis.as<gl_t>(), c->lde.as<gl_t>(), c->tab->qtab.as<gl_t>(), c->apow.as<gl_t>(), alphas[0], alphas[1],
+                                c->partial.as<gl_t>(), s.log_n, s.r, s.qdb, st));
+    HIPCHK(hipEventRecord(c->kev[3], st));
+    HIPCHK(launch_quotient_combine(c->partial.as<gl_t>(), c->chunk_scale.as<gl_t>(), n_chunks, c->tab->qtab.as<gl_t>(), s.log_n, s.qdb,
+                                   c->qvals.as<gl_t>(), st));
+    HIPCHK(stream_wait(c));  // apow / cscale go out of scope
+    return 0;
+}
+
+// development aid ("quotient_debug" = 9 with the interpreter): the tiled evaluator's values against the interpreter's on this very proof (stderr)
+int ProveCall::compare_quotient_evaluators() {
+    const size_t n = s.n, size = s.size, qdb = s.qdb;
+    if (int rc = ensure_plan(c, air, size)) return rc;
+    std::vector<gl_t> ref(2 * size), got(2 * size);
+    HIPCHK(read_back(c, ref.data(), c->qvals.p, 2 * size * 8, st));
+    HIPCHK(c->partial.ensure((size_t)std::max(n_chunks, c->plan->chunks) * 2 * size * 8));
+    if (int rc = run_quotient_tiles(0, c->comb_partial.as<gl_t>(), false)) return rc;
+    HIPCHK(read_back(c, got.data(), c->comb_partial.p, 2 * size * 8, st));
+    HIPCHK(stream_wait(c));
+    size_t bad = 0, last_blk = (size_t)-1;
+    for (size_t i = 0; i < 2 * size; i++)
+        if (ref[i] != got[i]) {
+            const size_t ii = i % size, k = ii >> qdb, spp = ii & (((size_t)1 << qdb) - 1), tt = spp * n + k, blk = tt / 64;
+            if (blk != last_blk && bad < 4096) fprintf(stderr, "quotient mismatch alpha %zu point-block %zu (sp %zu, k %zu..)\n", i / size, blk, spp, k & ~(size_t)63);
+            last_blk = blk;
+            bad++;
+        }
+    fprintf(stderr, "quotient compare: %zu of %zu values differ\n", bad, 2 * size);
+    return 0;
+}
+
+// ---- phase 3: quotient polynomials (App. A.6)
+int ProveCall::quotient() {
+    const size_t n = s.n, size = s.size, factor = s.factor;
+    HIPCHK(stream_wait(c));  // the trace cap
     fs.start();
     ch.observe_many(trace_cap.data(), trace_cap.size());  // public inputs are NOT observed (App. A.5)
-    gl_t alphas[2] = {ch.get(), ch.get()};
+    alphas[0] = ch.get();
+    alphas[1] = ch.get();
     fs.stop();
-
-    // ---- phase 3: quotient polynomials (App. A.6)
-    {
-        if (n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis_host, n_pis * 8, hipMemcpyHostToDevice, st));
-        if (tiled) {
-            // per-proof weights of the plan's records, then one pass over the LDE in LDS-staged column tiles
-            HIPCHK(launch_quotient_weights(c->plan->q_recs.as<QTRec>(), c->plan->q_contrib_off.as<uint32_t>(), c->plan->q_contribs.as<QTContrib>(), c->plan->recs,
-                                           c->plan->q_apow.as<gl_t>(), P.n_constraints, c->plan->q_consts.as<gl_t>(), c->pis.as<gl_t>(), alphas[0], alphas[1], st));
-            HIPCHK(hipEventRecord(c->kev[2], st));
-            HIPCHK(launch_quotient_tiles(c->plan->q_recs.as<QTRec>(), c->plan->q_streams.as<QTStream>(),
-                                         c->plan->q_chunk_tile_off.as<uint32_t>(), c->plan->q_tile_list.as<uint32_t>(), n_chunks, c->lde.as<gl_t>(),
-                                         c->tab->qtab.as<gl_t>(), c->partial.as<gl_t>(), log_n, r, qdb, (unsigned)C, (unsigned)((c->opt_quotient_debug <= 4 || c->opt_quotient_debug == 8) ? c->opt_quotient_debug : 0), st));
-            HIPCHK(hipEventRecord(c->kev[3], st));
-            HIPCHK(launch_quotient_tiles_combine(c->partial.as<gl_t>(), n_chunks, c->tab->qtab.as<gl_t>(), log_n, qdb, c->qvals.as<gl_t>(), st));
-        } else {
-            std::vector<gl_t> apow(2 * (AIR_MAX_GROUP + 1)), cscale(2 * n_chunks);
-            for (int j = 0; j < 2; j++) {
-                apow[j * (AIR_MAX_GROUP + 1)] = 1;
-                for (unsigned m = 1; m <= AIR_MAX_GROUP; m++) apow[j * (AIR_MAX_GROUP + 1) + m] = gl_mul(apow[j * (AIR_MAX_GROUP + 1) + m - 1], alphas[j]);
-                for (unsigned p = 0; p < n_chunks; p++) cscale[p * 2 + j] = gl_pow(alphas[j], c->chunk_k_after[p]);
-            }
-            HIPCHK(hipMemcpyAsync(c->apow.p, apow.data(), apow.size() * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(c->chunk_scale.p, cscale.data(), cscale.size() * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(hipEventRecord(c->kev[2], st));
-            HIPCHK(launch_quotient_eval(c->d_ops.as<QOp>(), c->d_loads.as<uint32_t>(), c->prog_slots, c->d_chunk_off.as<uint32_t>(), n_chunks,
-                                        c->pis.as<gl_t>(), c->lde.as<gl_t>(), c->tab->qtab.as<gl_t>(), c->apow.as<gl_t>(), alphas[0], alphas[1],
-                                        c->partial.as<gl_t>(), log_n, r, qdb, st));
-            HIPCHK(hipEventRecord(c->kev[3], st));
-            HIPCHK(launch_quotient_combine(c->partial.as<gl_t>(), c->chunk_scale.as<gl_t>(), n_chunks, c->tab->qtab.as<gl_t>(), log_n, qdb,
-                                           c->qvals.as<gl_t>(), st));
-            HIPCHK(stream_wait(c));  // apow / cscale go out of scope
-        }
-        if (c->opt_quotient_debug == 9 && !tiled) {
-            // development aid: the tiled evaluator's values against the interpreter's on this very proof (stderr)
-            int rc2;
-            if ((rc2 = ensure_plan(c, air, size))) return rc2;
-            std::vector<gl_t> ref(2 * size), got(2 * size);
-            HIPCHK(read_back(c, ref.data(), c->qvals.p, 2 * size * 8, st));
-            HIPCHK(c->partial.ensure((size_t)std::max(n_chunks, c->plan->chunks) * 2 * size * 8));
-            HIPCHK(launch_quotient_weights(c->plan->q_recs.as<QTRec>(), c->plan->q_contrib_off.as<uint32_t>(), c->plan->q_contribs.as<QTContrib>(), c->plan->recs,
-                                           c->plan->q_apow.as<gl_t>(), P.n_constraints, c->plan->q_consts.as<gl_t>(), c->pis.as<gl_t>(), alphas[0], alphas[1], st));
-            HIPCHK(launch_quotient_tiles(c->plan->q_recs.as<QTRec>(), c->plan->q_streams.as<QTStream>(),
-                                         c->plan->q_chunk_tile_off.as<uint32_t>(), c->plan->q_tile_list.as<uint32_t>(), c->plan->chunks, c->lde.as<gl_t>(),
-                                         c->tab->qtab.as<gl_t>(), c->partial.as<gl_t>(), log_n, r, qdb, (unsigned)C, 0, st));
-            HIPCHK(launch_quotient_tiles_combine(c->partial.as<gl_t>(), c->plan->chunks, c->tab->qtab.as<gl_t>(), log_n, qdb, c->comb_partial.as<gl_t>(), st));
-            HIPCHK(read_back(c, got.data(), c->comb_partial.p, 2 * size * 8, st));
-            HIPCHK(stream_wait(c));
-            size_t bad = 0;
-            size_t last_blk = (size_t)-1;
-            for (size_t i = 0; i < 2 * size; i++)
-                if (ref[i] != got[i]) {
-                    const size_t ii = i % size, k = ii >> qdb, spp = ii & (((size_t)1 << qdb) - 1), tt = spp * n + k, blk = tt / 64;
-                    if (blk != last_blk && bad < 4096) fprintf(stderr, "quotient mismatch alpha %zu point-block %zu (sp %zu, k %zu..)\n", i / size, blk, spp, k & ~(size_t)63);
-                    last_blk = blk;
-                    bad++;
-                }
-            fprintf(stderr, "quotient compare: %zu of %zu values differ\n", bad, 2 * size);
-        }
-        // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
-        HIPCHK(launch_ntt_global(c->qvals.as<gl_t>(), 2, size, log_n + qdb, c->tab->tw_inv.as<gl_t>(), log_N, nullptr, c->tab->qshift_inv.as<gl_t>(),
-                                 gl_inv((gl_t)size), st));
-        // trim_to_len(n * factor) must succeed, then chunks of n: [alpha0: c0..cf-1, alpha1: c0..cf-1]
-        std::vector<gl_t> tail;
-        if (size > (size_t)factor * n) {
-            tail.resize(2 * (size - factor * n));
-            for (int j = 0; j < 2; j++)
-                HIPCHK(read_back(c, tail.data() + j * (size - factor * n), c->qvals.as<gl_t>() + j * size + factor * n,
-                                      (size - factor * n) * 8, st));
-        }
+    if (s.pl.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis_host, s.pl.n_pis * 8, hipMemcpyHostToDevice, st));
+    const unsigned debug = (unsigned)((c->opt_quotient_debug <= 4 || c->opt_quotient_debug == 8) ? c->opt_quotient_debug : 0);
+    if (int rc = tiled ? run_quotient_tiles(debug, c->qvals.as<gl_t>(), true) : run_quotient_ops()) return rc;
+    if (c->opt_quotient_debug == 9 && !tiled)
+        if (int rc = compare_quotient_evaluators()) return rc;
+    // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
+    HIPCHK(launch_ntt_global(c->qvals.as<gl_t>(), 2, size, s.log_n + s.qdb, c->tab->tw_inv.as<gl_t>(), s.log_N, nullptr, c->tab->qshift_inv.as<gl_t>(),
+                             gl_inv((gl_t)size), st));
+    // trim_to_len(n * factor) must succeed (quotient_commit() looks at the tail), then chunks of n: [alpha0: c0..cf-1, alpha1: c0..cf-1]
+    if (size > factor * n) {
+        quot_tail.resize(2 * (size - factor * n));
         for (int j = 0; j < 2; j++)
-            HIPCHK(hipMemcpyAsync(c->qcoef.as<gl_t>() + (size_t)j * factor * n, c->qvals.as<gl_t>() + j * size, (size_t)factor * n * 8,
-                                  hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipEventRecord(c->ev[evi++], st));
-        ranges.next("starkhip:quotient_commit");
-        HIPCHK(stream_wait(c));
-        for (gl_t v : tail)
-            if (v != 0) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
+            HIPCHK(read_back(c, quot_tail.data() + j * (size - factor * n), c->qvals.as<gl_t>() + j * size + factor * n, (size - factor * n) * 8, st));
     }
+    for (int j = 0; j < 2; j++)
+        HIPCHK(hipMemcpyAsync(c->qcoef.as<gl_t>() + (size_t)j * factor * n, c->qvals.as<gl_t>() + j * size, factor * n * 8, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
 
-    // ---- phase 4: quotient commit (PolynomialBatch::from_coeffs)
-    HIPCHK(run_lde(c, c->qcoef.as<gl_t>(), nullptr, c->qlde.as<gl_t>(), Q, log_n, r, 1));
-    HIPCHK(launch_leaf_hash(c->qlde.as<gl_t>(), Q, log_n, r, c->qdigests.as<gl_t>(), st));
-    HIPCHK(launch_merkle_levels(c->qdigests.as<gl_t>(), log_N, cap_h, st));
-    HIPCHK(read_back(c, quot_cap.data(), c->qdigests.as<gl_t>() + 4 * level_off(N, log_N - cap_h), 4 * ncap * 8, st));
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:openings");
-    HIPCHK(stream_wait(c));
+// ---- phase 4: quotient commit (PolynomialBatch::from_coeffs)
+int ProveCall::quotient_commit() {
+    HIPCHK(stream_wait(c));  // the quotient's coefficients beyond n * factor
+    for (gl_t v : quot_tail)
+        if (v != 0) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
+    HIPCHK(run_lde(c, c->qcoef.as<gl_t>(), nullptr, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, 1));
+    HIPCHK(launch_leaf_hash(c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
+    HIPCHK(launch_merkle_levels(c->qdigests.as<gl_t>(), s.log_N, s.cap_h, st));
+    quot_cap.resize(4 * s.ncap);
+    HIPCHK(read_back(c, quot_cap.data(), c->qdigests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
+    return 0;
+}
+
+// ---- phase 5: openings (App. A.7)
+int ProveCall::openings() {
+    const size_t n = s.n, C = s.C, Q = s.Q;
+    HIPCHK(stream_wait(c));  // the quotient cap
     fs.start();
     ch.observe_many(quot_cap.data(), quot_cap.size());
-    gl2_t zeta = ch.get_ext();
+    zeta = ch.get_ext();
     fs.stop();
     if (c->opt_zeta_on_coset > 0)  // test hook ("zeta_on_coset" = k + 1): zeta = 7 w_n^k, a point of coset 0 itself (probability 2^-115 in a real transcript)
-        zeta = gl2_make(gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(log_n), (uint64_t)(c->opt_zeta_on_coset - 1) & (n - 1))), 0);
+        zeta = gl2_make(gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(s.log_n), (uint64_t)(c->opt_zeta_on_coset - 1) & (n - 1))), 0);
     if (gl2_eq(gl2_pow(zeta, n), gl2_one())) return STARKHIP_ERR_ZETA_IN_SUBGROUP;
-    gl2_t gzeta = gl2_mul_base(zeta, gl_root_of_unity(log_n));
-
-    // ---- phase 5: openings (App. A.7)
-    std::vector<gl2_t> op_local(C), op_next(C), op_q(Q);
     // the trace polynomials from their values on coset 0 of the LDE (kernels_fri.hip: the context keeps no coefficients of them), the
     // quotient polynomials from their coefficients
     const gl_t shift_n = gl_pow(GL_GENERATOR, n);  // 7^n
@@ -951,116 +947,117 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
     // (zh = 0: zeta lies on the coset 7 H itself -- the weights are then an indicator vector, coset_weights_kernel; starky proves there too)
     const gl2_t w_scale = gl2_mul_base(zh, gl_inv(gl_mul((gl_t)n, shift_n)));
     HIPCHK(launch_ext_powers(c->zpow.as<gl2_t>(), zeta, n, st));
-    HIPCHK(launch_coset_weights(c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), zeta, w_scale, log_n, st));
-    HIPCHK(launch_openings(c->lde.as<gl_t>(), N, C, n, c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), c->open_local.as<gl2_t>(),
+    HIPCHK(launch_coset_weights(c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), zeta, w_scale, s.log_n, st));
+    HIPCHK(launch_openings(c->lde.as<gl_t>(), s.N, C, n, c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), c->open_local.as<gl2_t>(),
                            c->open_next.as<gl2_t>(), st));
     HIPCHK(launch_openings(c->qcoef.as<gl_t>(), n, Q, n, c->zpow.as<gl2_t>(), nullptr, c->open_q.as<gl2_t>(), nullptr, st));
+    op_local.resize(C);
+    op_next.resize(C);
+    op_q.resize(Q);
     HIPCHK(read_back(c, op_local.data(), c->open_local.p, C * 16, st));
     HIPCHK(read_back(c, op_next.data(), c->open_next.p, C * 16, st));
     HIPCHK(read_back(c, op_q.data(), c->open_q.p, Q * 16, st));
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:fri_combine");
-    HIPCHK(stream_wait(c));
+    return 0;
+}
+
+// ---- phase 6: FRI batch combination (prove_openings, App. A.8)
+int ProveCall::fri_combine() {
+    const size_t n = s.n, N = s.N, C = s.C, Q = s.Q;
+    HIPCHK(stream_wait(c));  // the openings
     fs.start();  // 2 (2 C + Q) field elements through the sponge, one permutation per 8: the longest host stretch of a proof
     for (size_t i = 0; i < C; i++) ch.observe_ext(op_local[i]);
     for (size_t i = 0; i < Q; i++) ch.observe_ext(op_q[i]);
     for (size_t i = 0; i < C; i++) ch.observe_ext(op_next[i]);
-
-    // ---- phase 6: FRI batch combination (prove_openings, App. A.8)
-    gl2_t fri_alpha = ch.get_ext();
+    const gl2_t fri_alpha = ch.get_ext();
     fs.stop();
-    std::vector<gl2_t> fin(n);
-    {
-        HIPCHK(launch_ext_powers(c->ext_apow.as<gl2_t>(), fri_alpha, C + Q, st));
-        // sum_j alpha^j trace_j: the sum is taken on coset 0 of the LDE (n values a column) and turned into coefficients by ONE inverse
-        // coset transform of its two words -- linear, so these are the coefficients of the reference's sum of coefficient vectors
-        gl_t* comb_t = c->comb_out.as<gl_t>();                 // [2][n] words
-        gl2_t* comb_q = c->comb_out.as<gl2_t>() + n;           // [n] extension elements
-        HIPCHK(launch_fri_combine(c->lde.as<gl_t>(), N, C, n, c->ext_apow.as<gl2_t>(), comb_ppc, comb_chunks, c->comb_partial.as<gl2_t>(), st));
-        HIPCHK(launch_ext_reduce(c->comb_partial.as<gl2_t>(), comb_chunks, n, comb_t, st));
-        HIPCHK(launch_ntt_global(comb_t, 2, n, log_n, c->tab->tw_inv.as<gl_t>(), log_N, nullptr, c->tab->qshift_inv.as<gl_t>(), gl_inv((gl_t)n), st));
-        HIPCHK(launch_fri_combine(c->qcoef.as<gl_t>(), n, Q, n, c->ext_apow.as<gl2_t>() + C, Q, 1, comb_q, st));  // alpha^(C+q) quotient_q
-        std::vector<gl_t> F1w(2 * n);
-        std::vector<gl2_t> F1(n), tailq(n), F0(n), q0(n), q1(n);
-        HIPCHK(read_back(c, F1w.data(), comb_t, n * 16, st));
-        HIPCHK(read_back(c, tailq.data(), comb_q, n * 16, st));
-        HIPCHK(stream_wait(c));
-        host_other.start();
-        for (size_t k = 0; k < n; k++) F1[k] = gl2_make(F1w[k], F1w[n + k]);
-        for (size_t k = 0; k < n; k++) F0[k] = gl2_add(F1[k], tailq[k]);
-        divide_by_linear(F0.data(), n, zeta, q0.data());   // batch 0: trace ++ quotient at zeta
-        divide_by_linear(F1.data(), n, gzeta, q1.data());  // batch 1: trace at g*zeta
-        gl2_t shift = gl2_pow(fri_alpha, C);               // alpha^{|batch 1|}
-        for (size_t k = 0; k < n; k++) fin[k] = gl2_add(gl2_mul(q0[k], shift), q1[k]);
-        // upload as SoA, zero padded to N (lde(rate_bits))
-        std::vector<gl_t> soa(2 * N, 0);
-        for (size_t k = 0; k < n; k++) {
-            soa[k] = fin[k].a0;
-            soa[N + k] = fin[k].a1;
-        }
-        host_other.stop();
-        HIPCHK(hipMemcpyAsync(c->fri_coef.p, soa.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(stream_wait(c));
+    const gl2_t gzeta = gl2_mul_base(zeta, gl_root_of_unity(s.log_n));
+    HIPCHK(launch_ext_powers(c->ext_apow.as<gl2_t>(), fri_alpha, C + Q, st));
+    // sum_j alpha^j trace_j: the sum is taken on coset 0 of the LDE (n values a column) and turned into coefficients by ONE inverse
+    // coset transform of its two words -- linear, so these are the coefficients of the reference's sum of coefficient vectors
+    gl_t* comb_t = c->comb_out.as<gl_t>();        // [2][n] words
+    gl2_t* comb_q = c->comb_out.as<gl2_t>() + n;  // [n] extension elements
+    HIPCHK(launch_fri_combine(c->lde.as<gl_t>(), N, C, n, c->ext_apow.as<gl2_t>(), COMB_PPC, comb_chunks(C), c->comb_partial.as<gl2_t>(), st));
+    HIPCHK(launch_ext_reduce(c->comb_partial.as<gl2_t>(), comb_chunks(C), n, comb_t, st));
+    HIPCHK(launch_ntt_global(comb_t, 2, n, s.log_n, c->tab->tw_inv.as<gl_t>(), s.log_N, nullptr, c->tab->qshift_inv.as<gl_t>(), gl_inv((gl_t)n), st));
+    HIPCHK(launch_fri_combine(c->qcoef.as<gl_t>(), n, Q, n, c->ext_apow.as<gl2_t>() + C, Q, 1, comb_q, st));  // alpha^(C+q) quotient_q
+    std::vector<gl_t> F1w(2 * n);
+    std::vector<gl2_t> F1(n), tailq(n), F0(n), q0(n), q1(n), fin(n);
+    HIPCHK(read_back(c, F1w.data(), comb_t, n * 16, st));
+    HIPCHK(read_back(c, tailq.data(), comb_q, n * 16, st));
+    HIPCHK(stream_wait(c));
+    host_other.start();
+    for (size_t k = 0; k < n; k++) F1[k] = gl2_make(F1w[k], F1w[n + k]);
+    for (size_t k = 0; k < n; k++) F0[k] = gl2_add(F1[k], tailq[k]);
+    divide_by_linear(F0.data(), n, zeta, q0.data());  // batch 0: trace ++ quotient at zeta
+    divide_by_linear(F1.data(), n, gzeta, q1.data());   // batch 1: trace at g*zeta
+    const gl2_t shift = gl2_pow(fri_alpha, C);          // alpha^{|batch 1|}
+    for (size_t k = 0; k < n; k++) fin[k] = gl2_add(gl2_mul(q0[k], shift), q1[k]);
+    // upload as SoA, zero padded to N (lde(rate_bits))
+    std::vector<gl_t> soa(2 * N, 0);
+    for (size_t k = 0; k < n; k++) {
+        soa[k] = fin[k].a0;
+        soa[N + k] = fin[k].a1;
     }
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:fri_commit");
+    host_other.stop();
+    HIPCHK(hipMemcpyAsync(c->fri_coef.p, soa.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(stream_wait(c));  // soa goes out of scope
+    return 0;
+}
 
-    // ---- phase 7: FRI commit phase (fri_committed_trees)
-    std::vector<gl_t> fri_caps(L * 4 * ncap);
-    std::vector<gl2_t> final_poly(geo.final_poly_len);
-    {
-        size_t len = N;
-        unsigned log_len = log_N;
-        gl_t shift = GL_GENERATOR;
-        gl_t* coef = c->fri_coef.as<gl_t>();
-        gl_t* vals = c->fri_vals.as<gl_t>();
-        for (size_t l = 0; l <= L; l++) {
-            if (l == L) break;
-            // values on shift * <w_len>
-            HIPCHK(hipMemcpyAsync(vals, coef, len * 8, hipMemcpyDeviceToDevice, st));
-            HIPCHK(hipMemcpyAsync(vals + len, coef + len, len * 8, hipMemcpyDeviceToDevice, st));
-            HIPCHK(launch_fill_powers(c->scale_tab.as<gl_t>(), 1, shift, len, st));
-            HIPCHK(launch_ntt_global(vals, 2, len, log_len, c->tab->tw_fwd.as<gl_t>(), log_N, c->scale_tab.as<gl_t>(), nullptr, 1, st));
-            const unsigned ab = geo.arities[l];
-            const size_t n_leaves = len >> ab, width = 2 << ab;
-            HIPCHK(c->fri_rows[l].ensure(len * 2 * 8));
-            HIPCHK(c->fri_digests[l].ensure(digest_words(n_leaves) * 8));
-            HIPCHK(launch_fri_leaves(vals, log_len, ab, c->fri_rows[l].as<gl_t>(), st));
-            HIPCHK(launch_leaf_hash_rows(c->fri_rows[l].as<gl_t>(), width, n_leaves, c->fri_digests[l].as<gl_t>(), st));
-            HIPCHK(launch_merkle_levels(c->fri_digests[l].as<gl_t>(), log_len - ab, cap_h, st));
-            // leaves and digests stay on the device (the query phase gathers from them); only the cap feeds the transcript
-            gl_t* cap = fri_caps.data() + l * 4 * ncap;
-            HIPCHK(read_back(c, cap, c->fri_digests[l].as<gl_t>() + 4 * level_off(n_leaves, log_len - ab - cap_h), 4 * ncap * 8, st));
-            HIPCHK(stream_wait(c));
-            fs.start();
-            ch.observe_many(cap, 4 * ncap);
-            gl2_t beta = ch.get_ext();
-            fs.stop();
-            // fold coefficients; output goes to the other half of fri_vals' sibling buffer: reuse coef in place via temp
-            HIPCHK(launch_fri_fold(coef, len, ab, beta, vals, st));  // vals now holds folded coefficients SoA [2][len >> ab]
-            std::swap(coef, vals);
-            len >>= ab;
-            log_len -= ab;
-            for (unsigned b = 0; b < ab; b++) shift = gl_sqr(shift);
-        }
-        // final polynomial: truncate to len >> rate_bits; the dropped coefficients must be zero
-        std::vector<gl_t> fc(2 * len);
-        HIPCHK(read_back(c, fc.data(), coef, len * 8, st));
-        HIPCHK(read_back(c, fc.data() + len, coef + len, len * 8, st));
+// ---- phase 7: FRI commit phase (fri_committed_trees)
+int ProveCall::fri_commit() {
+    const size_t ncap = s.ncap;
+    fri_caps.resize(s.L * 4 * ncap);
+    final_poly.resize(s.geo.final_poly_len);
+    size_t len = s.N;
+    unsigned log_len = s.log_N;
+    gl_t shift = GL_GENERATOR;
+    gl_t* coef = c->fri_coef.as<gl_t>();
+    gl_t* vals = c->fri_vals.as<gl_t>();
+    for (size_t l = 0; l < s.L; l++) {
+        // values on shift * <w_len>
+        HIPCHK(hipMemcpyAsync(vals, coef, len * 8, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(vals + len, coef + len, len * 8, hipMemcpyDeviceToDevice, st));
+        HIPCHK(launch_fill_powers(c->scale_tab.as<gl_t>(), 1, shift, len, st));
+        HIPCHK(launch_ntt_global(vals, 2, len, log_len, c->tab->tw_fwd.as<gl_t>(), s.log_N, c->scale_tab.as<gl_t>(), nullptr, 1, st));
+        const unsigned ab = s.geo.arities[l];
+        const size_t n_leaves = len >> ab, width = 2 << ab;
+        HIPCHK(launch_fri_leaves(vals, log_len, ab, c->fri_rows[l].as<gl_t>(), st));
+        HIPCHK(launch_leaf_hash_rows(c->fri_rows[l].as<gl_t>(), width, n_leaves, c->fri_digests[l].as<gl_t>(), st));
+        HIPCHK(launch_merkle_levels(c->fri_digests[l].as<gl_t>(), log_len - ab, s.cap_h, st));
+        // leaves and digests stay on the device (the query phase gathers from them); only the cap feeds the transcript
+        gl_t* cap = fri_caps.data() + l * 4 * ncap;
+        HIPCHK(read_back(c, cap, c->fri_digests[l].as<gl_t>() + 4 * level_off(n_leaves, log_len - ab - s.cap_h), 4 * ncap * 8, st));
         HIPCHK(stream_wait(c));
-        if ((len >> r) != geo.final_poly_len) return STARKHIP_ERR_BAD_SHAPE;
-        for (size_t k = 0; k < len; k++) {
-            if (k < geo.final_poly_len) final_poly[k] = gl2_make(fc[k], fc[len + k]);
-            else if (fc[k] || fc[len + k]) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
-        }
         fs.start();
-        for (auto& e : final_poly) ch.observe_ext(e);
+        ch.observe_many(cap, 4 * ncap);
+        const gl2_t beta = ch.get_ext();
         fs.stop();
+        // fold the coefficients into the other buffer, which then holds them SoA [2][len >> ab], and swap the two
+        HIPCHK(launch_fri_fold(coef, len, ab, beta, vals, st));
+        std::swap(coef, vals);
+        len >>= ab;
+        log_len -= ab;
+        for (unsigned b = 0; b < ab; b++) shift = gl_sqr(shift);
     }
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:pow");
+    // final polynomial: truncate to len >> rate_bits; the dropped coefficients must be zero
+    std::vector<gl_t> fc(2 * len);
+    HIPCHK(read_back(c, fc.data(), coef, len * 8, st));
+    HIPCHK(read_back(c, fc.data() + len, coef + len, len * 8, st));
+    HIPCHK(stream_wait(c));
+    if ((len >> s.r) != s.geo.final_poly_len) return STARKHIP_ERR_BAD_SHAPE;
+    for (size_t k = 0; k < len; k++) {
+        if (k < s.geo.final_poly_len) final_poly[k] = gl2_make(fc[k], fc[len + k]);
+        else if (fc[k] || fc[len + k]) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
+    }
+    fs.start();
+    for (auto& e : final_poly) ch.observe_ext(e);
+    fs.stop();
+    return 0;
+}
 
-    // ---- phase 8: proof of work (fri_proof_of_work): smallest nonce unless one is supplied
+// ---- phase 8: proof of work (fri_proof_of_work): smallest nonce unless one is supplied
+int ProveCall::pow() {
     if (pow_witness == STARKHIP_POW_SEARCH) {
         if (cfg.proof_of_work_bits == 0) {
             pow_witness = 0;
@@ -1083,14 +1080,14 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
     }
     ch.observe(pow_witness);
     (void)ch.get();  // pow_response
-    HIPCHK(hipEventRecord(c->ev[evi++], st));
-    ranges.next("starkhip:queries");
+    return 0;
+}
 
-    // ---- phase 9: query rounds (fri_prover_query_rounds)
-    ProofLayout pl;
-    pl.C = C; pl.Q = Q; pl.log_n = log_n; pl.rate_bits = r; pl.cap_h = cap_h; pl.L = L; pl.n_queries = cfg.num_query_rounds;
-    pl.final_len = geo.final_poly_len; pl.n_pis = n_pis; pl.arity_bits = cfg.arity_bits; pl.n_challenges = 2;
-    pl.compute();
+// ---- phase 9: query rounds (fri_prover_query_rounds) and the proof's assembly.  From blob_alloc on a failing HIP call is noted, not
+// returned from (HIPCHK_FREE): the copy into the blob may be in flight, so the stream is waited for before the blob is freed.
+int ProveCall::queries() {
+    const ProofLayout& pl = s.pl;
+    const size_t N = s.N, C = s.C, Q = s.Q, L = s.L, ncap = s.ncap;
     if (!c->hs && !c->blob_airs.count(air.id)) {
         // a context on its own (not a pool's: those reserve at warm-up) gets its two page-locked blobs with its first proof of an AIR,
         // the proof that also grows the work buffers -- hipHostMalloc waits for the device like the hipMallocs before it
@@ -1098,79 +1095,134 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
         if (pinned) (void)blob_arena_add(c, pl.total * 8, 2);  // failure: malloc serves the proof
         c->blob_airs.insert(air.id);
     }
-    uint64_t* out = blob_alloc(pl.total * 8);  // page-locked if the context has reserved blobs (blob_arena.h)
+    out = blob_alloc(pl.total * 8);  // page-locked if the context has reserved blobs (blob_arena.h)
     if (!out) return STARKHIP_ERR_OOM;
-    {
-        const size_t nq = cfg.num_query_rounds;
-        std::vector<uint32_t> xs(nq);
-        for (size_t q = 0; q < nq; q++) xs[q] = (uint32_t)(ch.get() % N);
-        // every round's leaves and Merkle paths are gathered on the device, already in proof layout
-        const size_t stride = pl.query_words;
-        const unsigned d0 = log_N - cap_h;
-        int err = 0;
+    const size_t nq = pl.n_queries;
+    std::vector<uint32_t> xs(nq);
+    for (size_t q = 0; q < nq; q++) xs[q] = (uint32_t)(ch.get() % N);
+    // every round's leaves and Merkle paths are gathered on the device, already in proof layout
+    const size_t stride = pl.query_words;
+    const unsigned d0 = s.log_N - s.cap_h;
+    int err = 0;
 #define HIPCHK_FREE(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { fprintf(stderr, "starkhip: HIP error %s (%s)\n", hipGetErrorString(_e), #expr); err = 1; } } while (0)
-        HIPCHK_FREE(c->gather_t.ensure(nq * stride * 8));
-        gl_t* dq = c->gather_t.as<gl_t>();
-        if (nq) HIPCHK_FREE(hipMemcpyAsync(c->qidx.p, xs.data(), nq * 4, hipMemcpyHostToDevice, st));
-        const uint32_t* dxs = c->qidx.as<uint32_t>();
-        size_t off = 0;
-        if (!err) {
-            HIPCHK_FREE(launch_query_leaf_colmajor(c->lde.as<gl_t>(), C, log_n, r, dxs, nq, dq, stride, off, st)); off += C;
-            HIPCHK_FREE(launch_query_path(c->digests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
-            HIPCHK_FREE(launch_query_leaf_colmajor(c->qlde.as<gl_t>(), Q, log_n, r, dxs, nq, dq, stride, off, st)); off += Q;
-            HIPCHK_FREE(launch_query_path(c->qdigests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
-            size_t len = N;
-            unsigned shift_bits = 0;
-            for (size_t l = 0; l < L; l++) {
-                const unsigned ab = geo.arities[l];
-                const size_t width = 2 << ab, n_leaves = len >> ab;
-                shift_bits += ab;
-                HIPCHK_FREE(launch_query_leaf_rows(c->fri_rows[l].as<gl_t>(), width, dxs, shift_bits, nq, dq, stride, off, st)); off += width;
-                HIPCHK_FREE(launch_query_path(c->fri_digests[l].as<gl_t>(), n_leaves, (unsigned)pl.layer_depth[l], dxs, shift_bits, nq, dq, stride, off, st));
-                off += 4 * pl.layer_depth[l];
-                len = n_leaves;
-            }
-            if (nq) HIPCHK_FREE(hipMemcpyAsync(out + pl.off_queries, dq, nq * stride * 8, hipMemcpyDeviceToHost, st));
+    gl_t* dq = c->gather_t.as<gl_t>();
+    if (nq) HIPCHK_FREE(hipMemcpyAsync(c->qidx.p, xs.data(), nq * 4, hipMemcpyHostToDevice, st));
+    const uint32_t* dxs = c->qidx.as<uint32_t>();
+    size_t off = 0;
+    if (!err) {
+        HIPCHK_FREE(launch_query_leaf_colmajor(c->lde.as<gl_t>(), C, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += C;
+        HIPCHK_FREE(launch_query_path(c->digests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
+        HIPCHK_FREE(launch_query_leaf_colmajor(c->qlde.as<gl_t>(), Q, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += Q;
+        HIPCHK_FREE(launch_query_path(c->qdigests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
+        size_t len = N;
+        unsigned shift_bits = 0;
+        for (size_t l = 0; l < L; l++) {
+            const unsigned ab = s.geo.arities[l];
+            const size_t width = 2 << ab, n_leaves = len >> ab;
+            shift_bits += ab;
+            HIPCHK_FREE(launch_query_leaf_rows(c->fri_rows[l].as<gl_t>(), width, dxs, shift_bits, nq, dq, stride, off, st)); off += width;
+            HIPCHK_FREE(launch_query_path(c->fri_digests[l].as<gl_t>(), n_leaves, (unsigned)pl.layer_depth[l], dxs, shift_bits, nq, dq, stride, off, st));
+            off += 4 * pl.layer_depth[l];
+            len = n_leaves;
         }
-        pl.write_header(out);
-        memcpy(out + pl.off_trace_cap, trace_cap.data(), 4 * ncap * 8);
-        memcpy(out + pl.off_quot_cap, quot_cap.data(), 4 * ncap * 8);
-        memcpy(out + pl.off_local, op_local.data(), C * 16);
-        memcpy(out + pl.off_next, op_next.data(), C * 16);
-        memcpy(out + pl.off_quot_open, op_q.data(), Q * 16);
-        if (L) memcpy(out + pl.off_fri_caps, fri_caps.data(), L * 4 * ncap * 8);
-        HIPCHK_FREE(stream_wait(c));
-#undef HIPCHK_FREE
-        if (err || off != stride) {
-            blob_free(out);
-            return STARKHIP_ERR_HIP;
-        }
-        memcpy(out + pl.off_final, final_poly.data(), geo.final_poly_len * 16);
-        out[pl.off_pow] = pow_witness;
-        if (n_pis) memcpy(out + pl.off_pis, pis_host, n_pis * 8);
+        if (nq) HIPCHK_FREE(hipMemcpyAsync(out + pl.off_queries, dq, nq * stride * 8, hipMemcpyDeviceToHost, st));
     }
+    pl.write_header(out);
+    memcpy(out + pl.off_trace_cap, trace_cap.data(), 4 * ncap * 8);
+    memcpy(out + pl.off_quot_cap, quot_cap.data(), 4 * ncap * 8);
+    memcpy(out + pl.off_local, op_local.data(), C * 16);
+    memcpy(out + pl.off_next, op_next.data(), C * 16);
+    memcpy(out + pl.off_quot_open, op_q.data(), Q * 16);
+    if (L) memcpy(out + pl.off_fri_caps, fri_caps.data(), L * 4 * ncap * 8);
+    HIPCHK_FREE(stream_wait(c));  // xs goes out of scope
+#undef HIPCHK_FREE
+    if (err || off != stride) {
+        blob_free(out);
+        return STARKHIP_ERR_HIP;
+    }
+    memcpy(out + pl.off_final, final_poly.data(), s.geo.final_poly_len * 16);
+    out[pl.off_pow] = pow_witness;
+    if (pl.n_pis) memcpy(out + pl.off_pis, pis_host, pl.n_pis * 8);
+    return 0;
+}
+
+}  // namespace
+
+// The transcript of SURVEY.md App. A.5: argument checks, tables and plan, buffers, then the phases.  The order of what they enqueue on the
+// context's stream and the places where the host waits for it make the phase timings mean what starkhip.h says; a pool's overlap depends on it.
+int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* trace, size_t n_rows, int layout, int on_device,
+          const uint64_t* pis_host, size_t n_pis, uint64_t pow_witness, uint64_t** proof_out, size_t* proof_words) {
+    struct ReadBackGuard {  // an early return between a read_back() and its stream_wait() must not leave destinations of this call behind
+        Ctx* c;
+        ~ReadBackGuard() {
+            c->rb_pending.clear();
+            c->rb_used = 0;
+        }
+    } read_back_guard{c};
+    ProofShape s;
+    if (n_pis != air.prog.n_pis || ProofShape::make(air.prog, cfg, n_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
+    for (size_t i = 0; i < n_pis; i++)
+        if (pis_host[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->st;
+    if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
+    const bool tiled = c->opt_quotient_impl == 0;
+    if (int rc = tiled ? ensure_plan(c, air, s.size) : ensure_program(c, air, s.size)) return rc;
+    const unsigned n_chunks = tiled ? c->plan->chunks : c->prog_chunks;
+
+    // ---- buffers
+    // The trace waits for the LDE INSIDE the buffer the LDE is written to, as its last C n words (trace_in_lde: run_lde_trace);
+    // a separate buffer only when there is no room beside it (rate_bits == 0, or a recording longer than the rest of the buffer).
+    const size_t n = s.n, N = s.N, C = s.C;
+    const bool callers_columns = on_device && layout == 1;  // column-major device memory of the caller's: read where it is
+    size_t park_words = 0;  // what the upload parks at the start of the LDE buffer, in 64-bit words
+    if (layout == 2) {
+        const TraceLog* log = (const TraceLog*)trace;
+        park_words = (log->total_words() + log->total_records() + log->total_late_zeros() + 2 + 1) / 2;
+    } else if (!on_device && layout == 0) {
+        park_words = C * n;
+    }
+    const bool trace_in_lde = s.r >= 1 && park_words <= (((size_t)1 << s.r) - 1) * C * n && !callers_columns;
+    // `values`: the columns the last LDE launch reads (run_lde_trace), a whole trace, or nothing this proof needs
+    const size_t values_bytes = trace_in_lde ? lde_tail_columns(C) * n * 8 : callers_columns ? 0 : C * n * 8;
+    for (const BufWant& w : work_buffers(c, s, n_chunks, values_bytes, park_words * 8)) HIPCHK(w.b->ensure(w.bytes));
+
+    ProveCall p{c, air, cfg, s, st, trace, pis_host, layout, on_device, pow_witness, tiled, n_chunks, trace_in_lde,
+                trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()};
+    // before each phase: the boundary event of starkhip_last_timings on the stream and the phase's rocTX range (rocprofv3 --marker-trace)
+    static const struct { const char* range; int (ProveCall::*run)(); } PHASES[STARKHIP_N_PHASES - 1] = {
+        {"starkhip:upload", &ProveCall::upload}, {"starkhip:ifft_lde", &ProveCall::ifft_lde}, {"starkhip:trace_merkle", &ProveCall::trace_merkle},
+        {"starkhip:quotient", &ProveCall::quotient}, {"starkhip:quotient_commit", &ProveCall::quotient_commit}, {"starkhip:openings", &ProveCall::openings},
+        {"starkhip:fri_combine", &ProveCall::fri_combine}, {"starkhip:fri_commit", &ProveCall::fri_commit}, {"starkhip:pow", &ProveCall::pow},
+        {"starkhip:queries", &ProveCall::queries}};
+    int evi = 0;
+    PhaseRanges ranges;
+    for (const auto& ph : PHASES) {
+        HIPCHK(hipEventRecord(c->ev[evi++], st));
+        ranges.next(ph.range);
+        if (int rc = (p.*ph.run)()) return rc;
+    }
+    uint64_t* const out = p.out;
     if (hipEventRecord(c->ev[evi++], st) != hipSuccess || stream_wait(c) != hipSuccess) {
         blob_free(out);
         return STARKHIP_ERR_HIP;
     }
     for (int i = 0; i < STARKHIP_N_PHASES - 1; i++) (void)hipEventElapsedTime(&c->timings[i], c->ev[i], c->ev[i + 1]);
+    (void)hipEventElapsedTime(&c->timings[STARKHIP_N_PHASES - 1], c->ev[0], c->ev[STARKHIP_N_PHASES - 1]);
+    (void)hipEventElapsedTime(&c->ktimings[2], c->kev[2], c->kev[3]);
     if (c->opt_quotient_debug >= 1 && c->opt_quotient_debug <= 8) {  // profiling build only: timings are valid, the proof is not
         blob_free(out);
-        (void)hipEventElapsedTime(&c->timings[STARKHIP_N_PHASES - 1], c->ev[0], c->ev[STARKHIP_N_PHASES - 1]);
-        (void)hipEventElapsedTime(&c->ktimings[2], c->kev[2], c->kev[3]);
         return STARKHIP_ERR_VERIFY;
     }
-    (void)hipEventElapsedTime(&c->timings[STARKHIP_N_PHASES - 1], c->ev[0], c->ev[STARKHIP_N_PHASES - 1]);
-    c->htimings[0] = (float)fs.ms;
-    c->htimings[1] = (float)host_other.ms;
+    c->htimings[0] = (float)p.fs.ms;
+    c->htimings[1] = (float)p.host_other.ms;
     (void)hipEventElapsedTime(&c->ktimings[0], c->kev[4], c->kev[5]);
     // pooled: the commitment kernel's own duration on the scheduler's launch stream (kev[0] .. kev[1] on this context's stream would
     // include the wait for its group to form)
     if (c->hs && c->hash_timing.form != 4) (void)hipEventElapsedTime(&c->ktimings[1], c->hash_timing.t0, c->hash_timing.t1);
     else (void)hipEventElapsedTime(&c->ktimings[1], c->kev[0], c->kev[1]);
-    (void)hipEventElapsedTime(&c->ktimings[2], c->kev[2], c->kev[3]);
     *proof_out = out;
-    *proof_words = pl.total;
+    *proof_words = s.pl.total;
     return STARKHIP_OK;
 }
 
@@ -1180,55 +1232,18 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
 // the device -- measured in a batch of 8 signatures: a PairingPrecomp proof with 212 ms of device time held its context for 2.3 s
 // because its buffers grew while four FinalExp proofs kept the device busy.
 int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t log_bytes, unsigned proof_blobs, bool device_traces) {
-    const AirProgram& P = air.prog;
-    const size_t n = air.default_rows;
-    unsigned log_n = 0;
-    while (((size_t)1 << log_n) < n) log_n++;
-    FriGeometry geo;
-    if (!FriGeometry::make(cfg, log_n, &geo)) return STARKHIP_ERR_BAD_SHAPE;
-    const unsigned r = cfg.rate_bits;
-    const unsigned factor = P.degree > 1 ? P.degree - 1 : 1;
-    unsigned qdb = 0;
-    while ((1u << qdb) < factor) qdb++;
-    if (qdb > r) return STARKHIP_ERR_BAD_SHAPE;
-    const size_t N = n << r, C = P.n_cols, Q = (size_t)factor * 2, size = n << qdb, L = geo.arities.size();
+    ProofShape s;
+    if (ProofShape::make(air.prog, cfg, air.default_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure_tables(c, log_n, r, qdb))) return rc;
-    if ((rc = ensure_plan(c, air, size))) return rc;
-    const unsigned n_chunks = c->plan->chunks;
-    const size_t comb_chunks = (C + 255) / 256;
-    ProofLayout pl;
-    pl.C = C; pl.Q = Q; pl.log_n = log_n; pl.rate_bits = r; pl.cap_h = cfg.cap_height; pl.L = L; pl.n_queries = cfg.num_query_rounds;
-    pl.final_len = geo.final_poly_len; pl.n_pis = P.n_pis; pl.arity_bits = cfg.arity_bits; pl.n_challenges = 2;
-    pl.compute();
-    struct Want { DevBuf* b; size_t bytes; };
-    // (`values`: a trace waits for its LDE inside the LDE buffer, prove() phase 0, but for the tail of run_lde_trace; rate_bits == 0 makes
-    // prove() grow it to a whole trace on demand)
-    const Want wants[] = {{&c->values, r >= 1 ? lde_tail_columns(C) * n * 8 : C * n * 8}, {&c->lde, std::max(C * N * 8, log_bytes + 64)}, {&c->digests, digest_words(N) * 8},
-                          {&c->pis, std::max<size_t>(1, P.n_pis) * 8}, {&c->apow, 2 * (AIR_MAX_GROUP + 1) * 8}, {&c->chunk_scale, 2 * (size_t)n_chunks * 8},
-                          {&c->partial, (size_t)n_chunks * 2 * size * 8}, {&c->qvals, 2 * size * 8}, {&c->qcoef, Q * n * 8}, {&c->qlde, Q * N * 8},
-                          {&c->qdigests, digest_words(N) * 8}, {&c->zpow, 2 * n * 16}, {&c->gzpow, n * 16}, {&c->open_local, C * 16}, {&c->open_next, C * 16},
-                          {&c->open_q, Q * 16}, {&c->ext_apow, (C + Q) * 16}, {&c->comb_partial, comb_chunks * n * 16}, {&c->comb_out, 2 * n * 16},
-                          {&c->fri_coef, 2 * N * 8}, {&c->fri_vals, 2 * N * 8}, {&c->scale_tab, N * 8}, {&c->pow_state, 12 * 8}, {&c->pow_best, 8},
-                          {&c->qidx, cfg.num_query_rounds * 4}, {&c->gather_t, cfg.num_query_rounds * pl.query_words * 8}};
-    for (const Want& w : wants) HIPCHK(w.b->ensure(w.bytes));
-    size_t len = N;
-    for (size_t l = 0; l < L; l++) {
-        const unsigned ab = geo.arities[l];
-        HIPCHK(c->fri_rows[l].ensure(len * 2 * 8));
-        HIPCHK(c->fri_digests[l].ensure(digest_words(len >> ab) * 8));
-        len >>= ab;
-    }
-    if (log_bytes && !device_traces && c->host_staging_cap < log_bytes) {
-        if (c->host_staging) (void)hipHostFree(c->host_staging);
-        c->host_staging = nullptr;
-        c->host_staging_cap = 0;
-        HIPCHK(hipHostMalloc(&c->host_staging, log_bytes, hipHostMallocDefault));
-        c->host_staging_cap = log_bytes;
-    }
+    if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
+    if (int rc = ensure_plan(c, air, s.size)) return rc;
+    // `values`: a trace waits for its LDE inside the LDE buffer (prove(): trace_in_lde) but for the tail of run_lde_trace; rate_bits == 0
+    // makes prove() ask for a whole trace.  The LDE buffer also stages the upload: a recording of log_bytes.
+    const size_t values_bytes = (s.r >= 1 ? lde_tail_columns(s.C) : s.C) * s.n * 8;
+    for (const BufWant& w : work_buffers(c, s, c->plan->chunks, values_bytes, log_bytes + 64)) HIPCHK(w.b->ensure(w.bytes));
+    if (log_bytes && !device_traces) HIPCHK(ensure_host_staging(c, log_bytes, log_bytes));
     if (proof_blobs && !c->blob_airs.count(air.id)) {  // page-locked blobs for this AIR's proofs, once per context
-        if (blob_arena_add(c, pl.total * 8, proof_blobs) != 0) return STARKHIP_ERR_OOM;
+        if (blob_arena_add(c, s.pl.total * 8, proof_blobs) != 0) return STARKHIP_ERR_OOM;
         c->blob_airs.insert(air.id);
     }
     return stream_wait(c) == hipSuccess ? STARKHIP_OK : STARKHIP_ERR_HIP;
@@ -1357,21 +1372,9 @@ int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows
     }
     const unsigned nc = c->chk_chunks;
     const gl_t* d_trace;
-    if (on_device && layout == 1) {
-        d_trace = trace;  // the caller's memory: read only
-    } else {
-        HIPCHK(c->values.ensure(C * n * 8));
-        if (on_device) {
-            HIPCHK(launch_transpose(trace, c->values.as<gl_t>(), n, C, st));
-        } else if (layout == 1) {
-            HIPCHK(hipMemcpyAsync(c->values.p, trace, C * n * 8, hipMemcpyHostToDevice, st));
-        } else {
-            HIPCHK(c->lde.ensure(C * n * 8));
-            HIPCHK(hipMemcpyAsync(c->lde.p, trace, C * n * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(launch_transpose(c->lde.as<gl_t>(), c->values.as<gl_t>(), n, C, st));
-        }
-        d_trace = c->values.as<gl_t>();
-    }
+    if (!(on_device && layout == 1)) HIPCHK(c->values.ensure(C * n * 8));
+    if (!on_device && layout != 1) HIPCHK(c->lde.ensure(C * n * 8));  // the staging of row-major host rows
+    if (int rc = upload_dense(c, trace, layout, on_device, n, C, c->values.as<gl_t>(), &d_trace)) return rc;
     HIPCHK(c->pis.ensure(std::max<size_t>(1, P.n_pis) * 8));
     if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, st));
     const unsigned long long init[2] = {0, ~0ull};
@@ -1402,14 +1405,7 @@ int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor) {
     HIPCHK(hipSetDevice(c->device));
     const size_t nw = log->total_words(), nr = log->total_records(), nz = log->total_late_zeros();
     std::vector<uint32_t> h(nw + nr + nz);
-    size_t at_r = 0, at_z = 0;
-    log->for_each_part([&](const TraceLog& part) {
-        std::copy(part.words.begin(), part.words.end(), h.begin() + part.base);
-        std::copy(part.offsets.begin(), part.offsets.end(), h.begin() + nw + at_r);
-        std::copy(part.late_zeros.begin(), part.late_zeros.end(), h.begin() + nw + nr + at_z);
-        at_r += part.offsets.size();
-        at_z += part.late_zeros.size();
-    });
+    for (const LogPiece& pc : recording_pieces(*log)) std::copy(pc.src, pc.src + pc.words, h.begin() + pc.at);
     const size_t cells = log->rows * log->cols;
     HIPCHK(c->values.ensure(cells * 8));
     HIPCHK(c->staging.ensure(std::max<size_t>(h.size(), 1) * 4));
@@ -1431,10 +1427,8 @@ int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_
     HIPCHK(c->lde.ensure(n_cols * N * 8));
     HIPCHK(c->digests.ensure(digest_words(N) * 8));
     HIPCHK(hipMemcpyAsync(c->lde.p, lde_natural, n_cols * N * 8, hipMemcpyHostToDevice, c->st));
-    if (c->opt_leaf_hash_form == 3) HIPCHK(launch_leaf_hash_lane(c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st));
-    else if (use_pair_form(c, n_cols, log_N)) HIPCHK(launch_leaf_hash_pair(c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st));
-    else if (use_row_form(c, n_cols, log_N)) HIPCHK(launch_leaf_hash_row(c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st));
-    else HIPCHK(launch_leaf_hash(c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st));
+    int form;
+    HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st, &form));
     HIPCHK(launch_merkle_levels(c->digests.as<gl_t>(), log_N, cap_h, c->st));
     HIPCHK(hipMemcpyAsync(cap_out, c->digests.as<gl_t>() + 4 * level_off(N, log_N - cap_h), ((size_t)4 << cap_h) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(stream_wait(c));

@@ -73,7 +73,7 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     const AirProgram& P = air.prog;
     FriGeometry& geo = out->geo;
     if (!FriGeometry::make(cfg, (unsigned)pl.log_n, &geo) || quotient_degree_bits(P.degree) > cfg.rate_bits) return STARKHIP_ERR_BAD_SHAPE;
-    const unsigned factor = P.degree > 1 ? P.degree - 1 : 1;
+    const unsigned factor = quotient_factor(P.degree);
     if (pl.C != P.n_cols || pl.n_pis != P.n_pis || pl.rate_bits != cfg.rate_bits || pl.cap_h != cfg.cap_height ||
         pl.n_queries != cfg.num_query_rounds || pl.n_challenges != cfg.num_challenges || pl.Q != (size_t)factor * cfg.num_challenges ||
         pl.arity_bits != cfg.arity_bits)

@@ -338,12 +338,19 @@ def test_prove_from_separately_allocated_columns_matches_the_oracle(prover):
 def test_pool_reports_its_reservation():
     """starkhip_pool_reservation: a warmed FinalExp-class context holds the LDE (the trace waits for it inside that buffer, uploads are
     staged in it, coefficients are not kept) and small buffers -- under 20 GB, where rounds 1-3 held 30 (values + coefficients + staging
-    + LDE)."""
+    + LDE).  A proof grows none of it: the warm-up and prove() size the work buffers from one table (a buffer that grows inside a
+    proof is freed first, and hipFree waits for every stream of the device)."""
+    air, args = S.AIR_PAIRING_PRECOMP, _precomp_args(0x5EED3400)
     pool = S.ProofPool(0, big_contexts=1, small_contexts=1, generator_threads=1, warm_up=1)
     try:
         r = pool.reservation()
+        proof, _ = pool.wait(pool.submit_witness(air, *args))
+        after = pool.reservation()
     finally:
         pool.close()
+    S.verify_stark_proof(air, S.StarkConfig.for_air(air), proof)
+    for k in ("device_bytes", "big_context_device_bytes", "small_context_device_bytes"):
+        assert after[k] == r[k], k
     C_, n = S.air_columns(S.AIR_FINAL_EXP), 8192
     assert r["big_contexts"] == 1 and r["small_contexts"] == 1
     assert 8 * C_ * n * 4 <= r["big_context_device_bytes"] <= 20e9
