@@ -455,6 +455,12 @@ int starkhip_trace_log_expand_device(void* ctx, const void* log, uint64_t* trace
 /* device field arithmetic under test: out[i] = canonical(op(a[i], b[i])) with the lazy-reduction helpers the kernels use
  * (op codes: starky_bls12_381_amd/csrc/kernels_selftest.hip); lets the tests feed boundary operands */
 int starkhip_field_ops_batch(void* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+/* the leaf-hash forms' permutations under test, on whole 12-word states in place (a sponge fixes its first block's capacity, so the
+ * commitments cannot steer values into a later round): form 0 the generic loop, 1 quad, 2 row, 3 lane, 4 pair ("leaf_hash_form"),
+ * each through the function its leaf kernel calls; variant 0 = the full permutation, variant 1 (quad, lane, pair) = the form with the
+ * capacity-only last round, which specifies words 8 .. 11 (pair: 2 .. 5 and 8 .. 11) -- the other words come back unchanged.  Canonical
+ * words out.  STARKHIP_ERR_BAD_SHAPE for a form or variant that does not exist, before any device work. */
+int starkhip_poseidon_permute_batch_form(void* ctx, int form, int variant, uint64_t* states, size_t n_states);
 /* CPU check (no GPU needed) of the constant tables the leaf-hash kernels use for their merged partial rounds -- three at a time in the
  * quad form, four at a time in the lane and pair forms: replays both formulations on n_states inputs against the plain permutation;
  * returns the number of mismatches (0 = good), -1 if a sum of the four-round merge would not fit its 64-bit accumulator */

@@ -90,6 +90,7 @@ lib.starkhip_last_host_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
 lib.starkhip_lde_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_uint, _u64p, _u64p]
 lib.starkhip_merkle_cap.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_uint, _u64p]
 lib.starkhip_poseidon_permute_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t]
+lib.starkhip_poseidon_permute_batch_form.argtypes = [C.c_void_p, C.c_int, C.c_int, _u64p, C.c_size_t]
 lib.starkhip_field_ops_batch.argtypes = [C.c_void_p, C.c_int, _u64p, _u64p, _u64p, C.c_size_t]
 lib.starkhip_poseidon_permute_host.argtypes = [_u64p]
 lib.starkhip_poseidon_permute_host.restype = None
@@ -631,9 +632,16 @@ class Prover:
         _chk(lib.starkhip_field_ops_batch(self._ctx, op, _p64(a), _p64(b), _p64(out), a.size))
         return out
 
-    def poseidon_permute_batch(self, states):
+    def poseidon_permute_batch(self, states, form=0, variant=0):
+        """The permutation of every row of `states` (n x 12).  form: 0 the generic device loop, 1 .. 4 the quad, row, lane and pair forms of
+        the leaf hash, each through the function its leaf kernel calls; variant 1 (quad, lane, pair): the form with the capacity-only last
+        round, which specifies words 8 .. 11 (pair: 2 .. 5 and 8 .. 11) and returns the other words unchanged."""
         s = np.ascontiguousarray(states, dtype=np.uint64).copy()
-        _chk(lib.starkhip_poseidon_permute_batch(self._ctx, _p64(s), s.shape[0]))
+        assert s.ndim == 2 and s.shape[1] == 12
+        if form == 0 and variant == 0:
+            _chk(lib.starkhip_poseidon_permute_batch(self._ctx, _p64(s), s.shape[0]))
+        else:
+            _chk(lib.starkhip_poseidon_permute_batch_form(self._ctx, form, variant, _p64(s), s.shape[0]))
         return s
 
     def verify_batch(self, items):

@@ -671,6 +671,10 @@ int starkhip_poseidon_permute_batch(void* ctx, uint64_t* states, size_t n_states
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     return permute_batch((Ctx*)ctx, states, n_states);
 }
+int starkhip_poseidon_permute_batch_form(void* ctx, int form, int variant, uint64_t* states, size_t n_states) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    return permute_batch_form((Ctx*)ctx, form, variant, states, n_states);
+}
 int starkhip_field_ops_batch(void* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     return field_ops((Ctx*)ctx, op, a, b, out, n);

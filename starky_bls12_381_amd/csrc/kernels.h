@@ -78,6 +78,10 @@ hipError_t launch_leaf_hash_row(const gl_t* mat, size_t n_cols, unsigned log_n, 
 hipError_t launch_leaf_hash_rows(const gl_t* rows, size_t width, size_t n_leaves, gl_t* digests, hipStream_t st);
 hipError_t launch_merkle_levels(gl_t* digests, unsigned log_leaves, unsigned cap_h, hipStream_t st);
 hipError_t launch_permute_batch(gl_t* states, size_t n, hipStream_t st);
+// how many variants of its permutation a form's leaf kernel uses (0: no such form); kernels_hash.hip, the test entry points
+inline unsigned permute_form_variants(int form) { return form == 0 || form == 2 ? 1u : form == 1 || form == 3 || form == 4 ? 2u : 0u; }
+hipError_t launch_permute_quad_form(bool cap_only, const gl_t* in, gl_t* out, size_t n, hipStream_t st);   // kernels_hash_quad_form.hip
+hipError_t launch_permute_batch_form(int form, int variant, const gl_t* in, gl_t* out, size_t n, hipStream_t st);
 // kernels_selftest.hip
 // CPU replay of the leaf-hash kernel's merged-partial-round tables against the plain permutation; mismatching states out of n
 int quad_merged_tables_selfcheck(unsigned n);

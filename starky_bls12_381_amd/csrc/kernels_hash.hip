@@ -15,12 +15,7 @@
 
 namespace starkhip {
 
-// ---- per-lane tables of the quad permutation (poseidon_dev.h), built on the host once per device
-struct QuadMergedTables {
-    uint32_t coef[4][64];  // per lane: n3[3][12], n1[3], n2[3], m00 (lane 0 only), b2[3], b3[3], pad to 50, cf[12] at 50, pad
-    RcPair tk[2 * QUAD_MERGED_TRIPLES];       // k1, k2 per triple
-    RcPair tk3[4][3 * QUAD_MERGED_TRIPLES];   // per lane: k3[mo] per triple
-};
+// ---- per-lane tables of the quad permutation (poseidon_dev.h: QuadMergedTables), built on the host once per device
 __constant__ QuadMergedTables QUAD_MERGED;
 
 // Lane l owns state elements l, l + 4, l + 8 (slots 0, 1, 2); its rotated operand (r, m) is element ((l + r) & 3) + 4 m.
@@ -199,6 +194,13 @@ static hipError_t ensure_row_merged_tables() {
     return e;
 }
 
+// the host image of the quad form's tables, built once (also what kernels_hash_quad_form.hip uploads)
+const QuadMergedTables& quad_merged_tables_host() {
+    static QuadMergedTables T;  // zero-initialised; filled once
+    static std::once_flag once;
+    std::call_once(once, [] { build_quad_merged_tables(T); });
+    return T;
+}
 static hipError_t ensure_quad_merged_tables() {
     static std::mutex mu;
     static bool done[64] = {false};
@@ -208,12 +210,7 @@ static hipError_t ensure_quad_merged_tables() {
     std::lock_guard<std::mutex> g(mu);
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     if (done[dev]) return hipSuccess;
-    static QuadMergedTables T;  // zero-initialised; filled once
-    static bool built = false;
-    if (!built) {
-        build_quad_merged_tables(T);
-        built = true;
-    }
+    const QuadMergedTables& T = quad_merged_tables_host();
     e = hipMemcpyToSymbol(HIP_SYMBOL(QUAD_MERGED), &T, sizeof T);
     if (e == hipSuccess) done[dev] = true;
     return e;
@@ -762,6 +759,106 @@ __global__ void permute_batch_kernel(gl_t* states, size_t n) { STARKHIP_PRIO_ENT
     for (int e = 0; e < 12; e++) states[12 * i + e] = s[e];
 }
 
+// ---- test entry points (starkhip_poseidon_permute_batch_form): the permutation of each leaf-hash form on WHOLE 12-word states, so that a
+// test can place any value at any round of it (a sponge fixes the capacity of its first block).  Each kernel takes its leaf kernel's launch
+// bounds and table staging, loads state q into the form's register layout, calls the function the leaf kernel calls and writes the canonical
+// words to out + 12 q.  Every lane stays active to the end; lanes beyond the last state shadow it (as leaf_hash_lane_kernel does) and write
+// nothing.  CAP_ONLY variants compute only part of the state in their last round: the words they are not specified to produce are written
+// as the INPUT words, and a test compares the others.
+//
+// (The quad form's entry point is kernels_hash_quad_form.hip: see there why it is a translation unit of its own.)
+//
+// Row form: lane e < 12 of a row of 16 holds word e, lanes 12 .. 15 start from zero as in the leaf kernel (mirrors, never read).
+__global__ __launch_bounds__(256) void permute_row_form_kernel(const gl_t* __restrict__ in, gl_t* __restrict__ out, size_t n) { STARKHIP_PRIO_ENTRY
+    __shared__ RcPair rcs[16][64];
+    row_rcs_fill(rcs);
+    __syncthreads();
+    const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const unsigned e = (unsigned)tid & 15u;
+    const bool live = (tid >> 4) < n;
+    const size_t q = live ? tid >> 4 : n - 1;
+    RowConsts K;
+    row_consts_init(K, e, ROW_MERGED.coef[e]);
+    gl_t s = e < 12 ? in[12 * q + e] : 0;
+    s = poseidon_permute_row_merged_asm(s, rcs[e], K);
+    if (live && e < 12) out[12 * q + e] = gl_canon(s);
+}
+
+// Lane form: one lane per state, words 0 .. 3 / 4 .. 7 / 8 .. 11 in the three tuples.  CAP_ONLY specifies words 8 .. 11 (st.t2).
+template <bool CAP_ONLY>
+__global__ __launch_bounds__(256, 2) void permute_lane_form_kernel(const gl_t* __restrict__ in, gl_t* __restrict__ out, size_t n) {
+    __shared__ LaneTables T;
+    {
+        const uint32_t* src = (const uint32_t*)&LANE_TABLES;
+        uint32_t* dst = (uint32_t*)&T;
+        for (unsigned idx = threadIdx.x; idx < sizeof(LaneTables) / 4; idx += blockDim.x) dst[idx] = src[idx];
+    }
+    __syncthreads();
+    const size_t q_raw = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const bool live = q_raw < n;
+    const gl_t* mine = in + 12 * (live ? q_raw : n - 1);
+    LaneZeros Z;
+    lane_zeros_init(Z);
+    LaneMfma M;
+    const unsigned lane = threadIdx.x & 63u;
+    lane_mfma_init(M, lane);
+    LaneState st;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        lane_set(st.t0, e, mine[e]);
+        lane_set(st.t1, e, mine[4 + e]);
+        lane_set(st.t2, e, mine[8 + e]);
+    }
+    poseidon_permute_lane_asm<CAP_ONLY>(st, &T, Z, M, lane);
+    if (!live) return;
+    gl_t* o = out + 12 * q_raw;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        o[e] = CAP_ONLY ? mine[e] : gl_canon(lane_get(st.t0, e));
+        o[4 + e] = CAP_ONLY ? mine[4 + e] : gl_canon(lane_get(st.t1, e));
+        o[8 + e] = gl_canon(lane_get(st.t2, e));
+    }
+}
+
+// Pair form: lane l < 32 of a wave holds words 0 .. 5 of state 32 w + l, lane l + 32 its words 6 .. 11.  CAP_ONLY specifies each lane's
+// elements 2 .. 5: words 2 .. 5 and 8 .. 11.
+template <bool CAP_ONLY>
+__global__ __launch_bounds__(256, 2) void permute_pair_form_kernel(const gl_t* __restrict__ in, gl_t* __restrict__ out, size_t n) {
+    __shared__ PairTables T;
+    {
+        const uint32_t* src = (const uint32_t*)&PAIR_TABLES;
+        uint32_t* dst = (uint32_t*)&T;
+        for (unsigned idx = threadIdx.x; idx < sizeof(PairTables) / 4; idx += blockDim.x) dst[idx] = src[idx];
+    }
+    __syncthreads();
+    const unsigned lane = threadIdx.x & 63u, half = lane >> 5;
+    const size_t q_raw = (blockIdx.x * (size_t)(blockDim.x >> 6) + (threadIdx.x >> 6)) * 32u + (lane & 31u);
+    const bool live = q_raw < n;
+    const gl_t* mine = in + 12 * (live ? q_raw : n - 1) + 6 * half;
+    LaneZeros Z;
+    lane_zeros_init(Z);
+    PairMfma M;
+    pair_mfma_init(M, lane);
+    uint64_t mask_lo = 0xFFFFFFFFull;
+    asm volatile("" : "+s"(mask_lo));
+    PairState st;
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        pair_set(st.t0, e, mine[e]);
+        pair_set(st.t1, e, mine[2 + e]);
+        pair_set(st.t2, e, mine[4 + e]);
+    }
+    poseidon_permute_pair_asm<CAP_ONLY>(st, &T, Z, M, lane, mask_lo);
+    if (!live) return;
+    gl_t* o = out + 12 * q_raw + 6 * half;
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        o[e] = CAP_ONLY ? mine[e] : gl_canon(pair_get(st.t0, e));
+        o[2 + e] = gl_canon(pair_get(st.t1, e));
+        o[4 + e] = gl_canon(pair_get(st.t2, e));
+    }
+}
+
 // Proof-of-work grinding (plonky2 fri_proof_of_work, App. A.8): the challenger's sponge state with its
 // pending inputs already written in; candidate nonce goes to lane `pos`; the response is state[7]
 // after one permutation.  Keeps the MINIMUM valid nonce in *best (initialised to UINT64_MAX).
@@ -837,6 +934,30 @@ hipError_t launch_merkle_levels(gl_t* digests, unsigned log_leaves, unsigned cap
 }
 hipError_t launch_permute_batch(gl_t* states, size_t n, hipStream_t st) {
     hipLaunchKernelGGL(permute_batch_kernel, dim3(nblocks(n, 64)), dim3(64), 0, st, states, n);
+    return hipGetLastError();
+}
+// form: 0 the generic loop, 1 quad, 2 row, 3 lane, 4 pair (the "leaf_hash_form" numbering); variant 1 = the form's capacity-only last round
+// (quad, lane, pair).  The caller has checked both (permute_form_variants) and n >= 1; `in` and `out` do not overlap.
+hipError_t launch_permute_batch_form(int form, int variant, const gl_t* in, gl_t* out, size_t n, hipStream_t st) {
+    if (variant < 0 || (unsigned)variant >= permute_form_variants(form) || n == 0) return hipErrorInvalidValue;
+    if (form == 0) {
+        if (hipError_t e = hipMemcpyAsync(out, in, n * 96, hipMemcpyDeviceToDevice, st); e != hipSuccess) return e;
+        return launch_permute_batch(out, n, st);
+    }
+    if (form == 1) {
+        return launch_permute_quad_form(variant != 0, in, out, n, st);
+    } else if (form == 2) {
+        if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
+        hipLaunchKernelGGL(permute_row_form_kernel, dim3(nblocks(16 * n, 256)), dim3(256), 0, st, in, out, n);
+    } else if (form == 3) {
+        if (hipError_t e = ensure_lane_tables(); e != hipSuccess) return e;
+        if (variant) hipLaunchKernelGGL(permute_lane_form_kernel<true>, dim3(nblocks(n, 256)), dim3(256), 0, st, in, out, n);
+        else hipLaunchKernelGGL(permute_lane_form_kernel<false>, dim3(nblocks(n, 256)), dim3(256), 0, st, in, out, n);
+    } else {
+        if (hipError_t e = ensure_pair_tables(); e != hipSuccess) return e;
+        if (variant) hipLaunchKernelGGL(permute_pair_form_kernel<true>, dim3(nblocks(n, 128)), dim3(256), 0, st, in, out, n);
+        else hipLaunchKernelGGL(permute_pair_form_kernel<false>, dim3(nblocks(n, 128)), dim3(256), 0, st, in, out, n);
+    }
     return hipGetLastError();
 }
 hipError_t launch_pow_grind(const gl_t* base_state, int pos, unsigned pow_bits, uint64_t start, uint64_t count, unsigned long long* best,

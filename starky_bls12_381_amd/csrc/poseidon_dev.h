@@ -258,6 +258,13 @@ struct QuadMergedCoef {
 };
 static const int QUAD_MERGED_TRIPLES = 7;  // = POSEIDON_MERGED_TRIPLES (poseidon_merged.h): partial rounds 0..20; the 22nd stays a plain round
 
+// The host-built image of the per-lane tables (kernels_hash.hip: build_quad_merged_tables), uploaded to constant memory once per device
+struct QuadMergedTables {
+    uint32_t coef[4][64];  // per lane: n3[3][12], n1[3], n2[3], m00 (lane 0 only), b2[3], b3[3], pad to 50, cf[12] at 50, pad
+    RcPair tk[2 * QUAD_MERGED_TRIPLES];       // k1, k2 per triple
+    RcPair tk3[4][3 * QUAD_MERGED_TRIPLES];   // per lane: k3[mo] per triple
+};
+
 // y is the same value in the four lanes of a quad; returns y^7 in all of them.  Even lanes form x^3, odd lanes x^4 in one
 // multiply, and every lane finds the other factor in its right-hand neighbour.
 __device__ __forceinline__ gl_t sbox_quad_uniform(gl_t y, bool even_lane) {

@@ -82,6 +82,7 @@ int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out);
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);
 int permute_batch(Ctx* c, uint64_t* states, size_t n);
+int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n);
 struct TraceLog;
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor);
 int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms = nullptr);

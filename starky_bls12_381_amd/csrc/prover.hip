@@ -1445,6 +1445,21 @@ int permute_batch(Ctx* c, uint64_t* states, size_t n) {
     return STARKHIP_OK;
 }
 
+// the permutation of one leaf-hash form on whole states (kernels_hash.hip: the test entry points); a bad form or variant launches nothing
+int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n) {
+    if (variant < 0 || (unsigned)variant >= permute_form_variants(form)) return STARKHIP_ERR_BAD_SHAPE;
+    if (n == 0) return STARKHIP_OK;
+    if (!states) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->staging.ensure(2 * n * 96));
+    gl_t* in = c->staging.as<gl_t>();
+    HIPCHK(hipMemcpyAsync(in, states, n * 96, hipMemcpyHostToDevice, c->st));
+    HIPCHK(launch_permute_batch_form(form, variant, in, in + 12 * n, n, c->st));
+    HIPCHK(hipMemcpyAsync(states, in + 12 * n, n * 96, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
 int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(c->staging.ensure(3 * n * 8));

@@ -20,9 +20,8 @@ def test_poseidon_permutation_batch(prover):
     states[1] = np.arange(12)
     states[2] = P - 1
     out = prover.poseidon_permute_batch(states)
-    for i in range(0, 1000, 37):
-        assert np.array_equal(out[i], O.poseidon_permute(states[i]))
-    assert np.array_equal(out[2], O.poseidon_permute(states[2]))
+    for i in range(1000):   # (a microsecond-scale C call each: all of them, not a sample)
+        assert np.array_equal(out[i], O.poseidon_permute(states[i])), i
 
 
 @pytest.mark.parametrize("log_n,rate_bits,ncols", [(1, 1, 5), (4, 1, 301), (6, 2, 130), (7, 1, 33), (8, 1, 37), (8, 2, 16), (9, 2, 21), (10, 2, 257),

@@ -355,9 +355,14 @@ def random_round():
     return [AB.edge_value() for _ in range(12)], [random.getrandbits(64) % P for _ in range(12)]
 
 
-def test_round(order, partial, first_out=0):
-    for _ in range(40):
-        state, rc = random_round()
+def drawn(cases, draw, count):
+    """the testers' inputs: `cases` where the caller brings its own round-entry states (tests/test_poseidon_steering_cpu.py), else
+    `count` random draws"""
+    return cases if cases is not None else (draw() for _ in range(count))
+
+
+def test_round(order, partial, first_out=0, cases=None):
+    for state, rc in drawn(cases, random_round, 40):
         vregs = fresh()
         set_state(vregs, state)
         for r in range(12):
@@ -366,9 +371,8 @@ def test_round(order, partial, first_out=0):
         assert get_state(vregs)[first_out:] == AB.reference_round(state, rc, partial)[first_out:], partial
 
 
-def test_round_mfma(order, partial, lanes=1, sems=SEMS, sregs={}, first_out=0):
-    for _ in range(40):
-        state, rc = random_round()
+def test_round_mfma(order, partial, lanes=1, sems=SEMS, sregs={}, first_out=0, cases=None):
+    for state, rc in drawn(cases, random_round, 40):
         vregs = fresh(lanes)
         set_state(vregs, state, lanes)
         RC = mfma_round_constants(rc)
@@ -382,18 +386,23 @@ def test_round_mfma(order, partial, lanes=1, sems=SEMS, sregs={}, first_out=0):
 
 
 def random_four():
-    """state, the four rounds' constants, the state four partial rounds later"""
+    """state, the four rounds' constants"""
     state = [AB.edge_value() for _ in range(12)]
     cs = [[random.getrandbits(64) % P for _ in range(12)] for _ in range(4)]
+    return state, cs
+
+
+def four_later(state, cs):
+    """the state len(cs) partial rounds later"""
     want = state
     for c in cs:
         want = AB.reference_round(want, c, True)
-    return state, cs, want
+    return want
 
 
-def test_four(order):
-    for _ in range(30):
-        state, cs, want = random_four()
+def test_four(order, cases=None):
+    for state, cs in drawn(cases, random_four, 30):
+        want = four_later(state, cs)
         (M, N2, N3, N4), (k1, k2, k3, k4) = four_tables(cs)
         vregs = fresh()
         set_state(vregs, state)

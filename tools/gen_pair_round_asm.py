@@ -223,13 +223,13 @@ SEMS = {"pmfma": sem_pmfma}
 SREGS = {MASK_LO: [1, 0]}
 
 
-def test_round_pair(order, partial, first_out=0):
-    L.test_round_mfma(order, partial, LANES, SEMS, SREGS, first_out)
+def test_round_pair(order, partial, first_out=0, cases=None):
+    L.test_round_mfma(order, partial, LANES, SEMS, SREGS, first_out, cases)
 
 
-def test_four_pair(order):
-    for _ in range(30):
-        state, cs, want = L.random_four()
+def test_four_pair(order, cases=None):
+    for state, cs in L.drawn(cases, L.random_four, 30):
+        want = L.four_later(state, cs)
         (M, N2, N3, N4), (k1, k2, k3, k4) = L.four_tables(cs)
         vregs = L.fresh(LANES)
         L.set_state(vregs, state, LANES)

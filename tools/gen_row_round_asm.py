@@ -255,10 +255,22 @@ def check_state(vregs, want, what):
         assert (vregs[S_LO][e] | (vregs[S_HI][e] << 32)) % P == want[e], (what, e)
 
 
-def test(order, partial):
-    for _ in range(100):
-        state = [AB.edge_value() for _ in range(12)]
-        rc = [random.getrandbits(64) % P for _ in range(12)]
+def random_round():
+    return [AB.edge_value() for _ in range(12)], [random.getrandbits(64) % P for _ in range(12)]
+
+
+def random_triple():
+    return [AB.edge_value() for _ in range(12)], [[random.getrandbits(64) % P for _ in range(12)] for _ in range(3)]
+
+
+def drawn(cases, draw, count):
+    """the testers' inputs: `cases` where the caller brings its own round-entry states (tests/test_poseidon_steering_cpu.py), else
+    `count` random draws"""
+    return cases if cases is not None else (draw() for _ in range(count))
+
+
+def test(order, partial, cases=None):
+    for state, rc in drawn(cases, random_round, 100):
         vregs = {r: [junk() for _ in range(NL)] for r in range(176, 256)}
         vregs[S_LO], vregs[S_HI] = row_words(state, junk)
         vregs[SEED_A], vregs[SEED_B] = row_words(rc, int)
@@ -272,10 +284,8 @@ def test(order, partial):
         check_state(vregs, AB.reference_round(state, rc, partial), partial)
 
 
-def test_triple(order):
-    for _ in range(60):
-        state = [AB.edge_value() for _ in range(12)]
-        cs = [[random.getrandbits(64) % P for _ in range(12)] for _ in range(3)]
+def test_triple(order, cases=None):
+    for state, cs in drawn(cases, random_triple, 60):
         (M, N2, N3), (k1, k2, k3) = AB.merged_tables(cs)
         assert max(max(r) for r in N3) < 1 << 21
         # reference: three plain partial rounds
