@@ -31,7 +31,7 @@ TraceLog*& armed_trace_log() {
     return armed;
 }
 static std::atomic<int> g_trace_threads(1);
-static thread_local int tl_trace_threads = 0;  // a pool's generator thread sets its own share (scheduler.cpp)
+static thread_local int tl_trace_threads = 0;  // a pool's generator thread sets its own share (pool.cpp)
 int trace_threads() { return tl_trace_threads > 0 ? tl_trace_threads : g_trace_threads.load(); }
 void set_thread_trace_threads(int n) { tl_trace_threads = n < 0 ? 0 : n > 64 ? 64 : n; }
 }  // namespace starkhip
@@ -388,7 +388,7 @@ int starkhip_prove_compact(void* ctx, starkhip_air_t air, const starkhip_config_
     }
 }
 
-// ---- proof pool (scheduler.cpp)
+// ---- proof pool (pool.cpp)
 // One hardware queue per in-flight proof: with HIP's default of 4, streams share queues and kernels of different proofs serialise behind
 // each other (-6 % on the FinalExp pool).  The runtime reads GPU_MAX_HW_QUEUES ONCE, when the process first uses HIP, so setting it here
 // works only in a process that has not.  Whether it has is visible without touching HIP: initialising the runtime opens the compute
@@ -516,7 +516,7 @@ int starkhip_pool_verify_stats(void* pool, starkhip_pool_verify_stats_t* out) {
     return pool_verify_stats((Pool*)pool, out);
 }
 
-// ---- a pool per device behind one handle (scheduler.cpp)
+// ---- a pool per device behind one handle (multipool.cpp)
 int starkhip_multipool_create(const int* devices, size_t n_devices, const starkhip_pool_config_t* cfg, void** mpool) {
     if (!devices || !n_devices || !cfg || !mpool) return STARKHIP_ERR_BAD_SHAPE;
     *mpool = nullptr;

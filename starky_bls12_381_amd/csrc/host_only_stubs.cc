@@ -157,7 +157,7 @@ hipError_t launch_verify_queries(const gl_t* words, const VQProof* proofs, const
 }
 }  // namespace starkhip
 
-// ---- no-op HIP runtime: only what scheduler.cpp calls (the sanitizer builds do not link libamdhip64).  Copies and fills are real (the
+// ---- no-op HIP runtime: only what hash_service.cpp calls (the sanitizer builds do not link libamdhip64).  Copies and fills are real (the
 // "device" is host memory and every stream is synchronous); every allocation -- device, page-locked, stream -- is counted
 // (starkhip_stub_allocations: the pool's verifier must not allocate after its setup)
 static std::atomic<unsigned long> g_stub_allocs(0);

@@ -43,9 +43,9 @@ int pool_set_option(Pool* p, const char* name, long value);
 int pool_submit_verify(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* proof, size_t words, uint64_t* ticket);
 int pool_verify_stats(Pool* p, starkhip_pool_verify_stats_t* out);
 double air_verify_cost(int air);
-unsigned cpu_budget();  // scheduler.cpp: CPUs this process may really use
+unsigned cpu_budget();  // multipool.cpp: CPUs this process may really use
 void host_cpu_seconds(double out[3]);
-// a pool per device behind one handle (scheduler.cpp): placement by outstanding cost, longest job first
+// a pool per device behind one handle (multipool.cpp): placement by outstanding cost, longest job first
 struct MultiPool;
 double air_cost(int air);
 int multipool_create(const int* devices, size_t n, const starkhip_pool_config_t& cfg, MultiPool** out);

@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -24,12 +25,39 @@
 
 namespace starkhip {
 
-unsigned cpu_budget();  // CPUs this process may really use (cgroup quota, affinity mask; scheduler.cpp)
+unsigned cpu_budget();  // CPUs this process may really use (cgroup quota, affinity mask; multipool.cpp)
+uint64_t thread_cpu_ns();  // trace_tasks.cpp: CPU time of the calling thread
+void set_thread_trace_threads(int n);  // capi.cpp: trace_threads() of the calling thread (0 = the process-wide setting)
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 hipError_t event_wait_sleeping(hipEvent_t ev);  // prover.hip: a few queries, then sleeps of 20 .. 200 microseconds between them
 
 class HashService {
   public:
-    explicit HashService(int device);
+    static bool is_big(unsigned log_n, unsigned rate_bits) { return log_n + rate_bits >= 15; }  // >= 2048 waves: fills every SIMD twice
+#ifndef STARKHIP_QUEUED_WAIT_MS
+#define STARKHIP_QUEUED_WAIT_MS 300.0
+#endif
+    // What the pool decides once, before the service starts (pool_create); never written afterwards.
+    struct Config {
+        double gather_ms = 25.0;  // how long a small window waits for announced proofs that have not reached their commitment
+        // 0 (default): small commitments that arrive together share a launch, and a big one starts whenever it arrives;
+        // 1: in addition the two classes never overlap (a big commitment waits for the small window to drain and vice versa).
+        // Measured on one MI355X: a batch of 8 signatures 3.5 against 3.2 signatures/s, one signature 0.42
+        // against 0.47 s -- a lone wave on a SIMD runs about twice as fast as one of two, so a FinalExp commitment that starts
+        // beside a MillerLoop latency chain loses less than it would by waiting for it.
+        int policy = 0;
+        bool big_lane = false;    // big commitments in groups, a group of two or more in the lane form (one lane per leaf): pools with five or
+                                  // more big contexts; STARKHIP_POOL_BIG_LANE=0 / 1 overrides
+        unsigned lane_group = 4;  // STARKHIP_POOL_LANE_GROUP: commitments per lane-form group (four fill the chip: two waves of 256 registers per SIMD)
+        double big_gather_ms = 1000.0;  // lane form: how long a group of big commitments waits at most for proofs that HAVE STARTED to join (a group of three
+                                        // wastes a quarter of a 350 ms launch: full groups measured 6.46 against 6.2 - 6.3 proofs/s with a 150 ms bound)
+        double big_queued_wait_ms = STARKHIP_QUEUED_WAIT_MS;  // ... and for jobs that have not started (queued, or being recorded) when nobody who has started is on the
+                                             // way: a recording plus upload plus LDE -- what the soonest of them needs -- not the full bound (a short batch,
+                                             // or the tail of one, would otherwise hold a commitment for several proof lengths)
+        int big_contexts = 0;    // the pool's number of big contexts: when all of them wait here, nobody else can come
+        size_t row_leaves = 64;  // STARKHIP_POOL_ROW_LEAVES: small commitments of at most this many leaves go out in the row form, one launch each (0: never)
+    };
+    HashService(int device, const Config& cfg);
     ~HashService();
     HashService(const HashService&) = delete;
     HashService& operator=(const HashService&) = delete;
@@ -39,8 +67,8 @@ class HashService {
     void announce_small();
     void announce_big();   // a FinalExp-class proof has started: its commitment will come (lane-form groups wait for it)
     void abandon_big();
-    void finish_big();     // that proof has ended
     void abandon_small();
+    void set_big_queued(int n);  // the pool's count of big jobs that have not started yet (queued, or their trace being recorded)
     // Leaf digests of the coset-major LDE `mat` (kernels_hash.hip: launch_leaf_hash) into `digests`, ordered after everything
     // enqueued on `st` so far; when this returns, `st` has been made to wait for the launch (the caller goes on enqueueing).
     // `ready` / `done` are events owned by the caller's context.
@@ -55,31 +83,7 @@ class HashService {
     hipError_t hash(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st, hipEvent_t ready,
                     hipEvent_t done, bool announced, bool urgent = false, Timing* timing = nullptr);
 
-    static bool is_big(unsigned log_n, unsigned rate_bits) { return log_n + rate_bits >= 15; }  // >= 2048 waves: fills every SIMD twice
-    double gather_ms = 25.0;  // how long a small window waits for announced proofs that have not reached their commitment
-    // 0 (default): small commitments that arrive together share a launch, and a big one starts whenever it arrives;
-    // 1: in addition the two classes never overlap (a big commitment waits for the small window to drain and vice versa).
-    // Measured on one MI355X: a batch of 8 signatures 3.5 against 3.2 signatures/s, one signature 0.42
-    // against 0.47 s -- a lone wave on a SIMD runs about twice as fast as one of two, so a FinalExp commitment that starts
-    // beside a MillerLoop latency chain loses less than it would by waiting for it.
-    int policy = 0;
-    unsigned BIG_LANE_GROUP = 4;  // STARKHIP_POOL_LANE_GROUP: commitments per lane-form group (four fill the chip: two waves of 256 registers per SIMD)
-    double big_gather_ms_ = 1000.0; // lane form: how long a group of big commitments waits at most for proofs that HAVE STARTED to join (a group of three
-                                    // wastes a quarter of a 350 ms launch: full groups measured 6.46 against 6.2 - 6.3 proofs/s with a 150 ms bound)
-#ifndef STARKHIP_QUEUED_WAIT_MS
-#define STARKHIP_QUEUED_WAIT_MS 300.0
-#endif
-    double big_queued_wait_ms_ = STARKHIP_QUEUED_WAIT_MS;  // ... and for jobs that have not started (queued, or being recorded) when nobody who has started is on the
-                                         // way: a recording plus upload plus LDE -- what the soonest of them needs -- not the full bound (a short batch,
-                                         // or the tail of one, would otherwise hold a commitment for several proof lengths)
-    void set_big_queued(int n);     // the pool's count of big jobs that have not started yet (queued, or their trace being recorded)
-    bool big_lane_ = false;  // big commitments in groups, a group of two or more in the lane form (pools with five or more big contexts;
-                             // STARKHIP_POOL_BIG_LANE=0 / 1 overrides)
-    int big_expected_ = 0;   // big proofs that have started and not yet reached their commitment
-    int big_queued_ = 0;     // big jobs of the pool that have not started (under mu_)
-    int big_contexts_ = 0;   // the pool's number of big contexts (set once): when all of them wait here, nobody else can come
-    int big_active_ = 0;     // big proofs being proved (before, in or after their commitment)  // STARKHIP_POOL_BIG_LANE=1: big commitments in the lane form (one lane per leaf)
-    size_t row_leaves_ = 64;  // STARKHIP_POOL_ROW_LEAVES: small commitments of at most this many leaves go out in the row form, one launch each (0: never)
+    const Config cfg;
 
     struct Stats {
         unsigned long big_launches = 0, small_launches = 0, small_requests = 0, max_merged = 0;
@@ -115,13 +119,15 @@ class HashService {
     hipStream_t small_st_[N_SMALL_STREAMS] = {};
     unsigned next_small_st_ = 0;
     hipStream_t pick_small_stream(hipError_t* err);
-    std::mutex mu_;
+    std::mutex mu_;  // guards the queues, counters, flags and stats_ below
     std::condition_variable cv_, cv_done_;
     std::deque<Req*> big_, small_;
-    int announced_ = 0;  // small proofs that have started and not yet asked for their commitment
+    int announced_ = 0;     // small proofs that have started and not yet asked for their commitment
+    int big_expected_ = 0;  // big proofs that have started and not yet reached their commitment
+    int big_queued_ = 0;    // big jobs of the pool that have not started
     bool stop_ = false, last_was_big_ = false;
-    std::vector<hipEvent_t> running_big_, running_small_;  // done events of launches that may still be executing
     Stats stats_;
+    std::vector<hipEvent_t> running_big_, running_small_;  // done events of launches that may still be executing (the service thread's own)
     std::thread th_;
 };
 

@@ -17,8 +17,6 @@
 
 namespace starkhip {
 
-uint64_t thread_cpu_ns();  // trace_tasks.cpp
-
 namespace {
 double steady_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 const size_t RESULT_WORDS = (size_t)1 << 19;  // page-locked result words per half (a status per query, a range flag per proof)

@@ -172,7 +172,7 @@ def test_final_exp_four_in_flight_match_the_oracle_digest():
 
 def test_final_exp_in_lane_form_groups_match_the_oracle_digest(monkeypatch):
     """Pools with five or more FinalExp-class contexts send their big commitments out in GROUPS in the lane form (one lane per leaf,
-    scheduled asm rounds; scheduler.cpp).  Forced here on four contexts: eight proofs of the benchmark's first seeded input, two groups
+    scheduled asm rounds; hash_service.cpp).  Forced here on four contexts: eight proofs of the benchmark's first seeded input, two groups
     of four commitments -- every proof's SHA-256 is the CPU oracle's."""
     air = S.AIR_FINAL_EXP
     cfg = S.StarkConfig.for_air(air)
@@ -193,7 +193,7 @@ def test_final_exp_in_lane_form_groups_match_the_oracle_digest(monkeypatch):
 
 
 def test_failures_of_final_exp_class_jobs_inside_lane_groups():
-    """scheduler.cpp's announce / withdraw / group logic for the 8192-row class with REAL kernels (the sanitizer harness runs it against
+    """hash_service.cpp's announce / withdraw / group logic for the 8192-row class with REAL kernels (the sanitizer harness runs it against
     a fake device): a pool of five big contexts sends FinalExp-class commitments out in lane-form groups that wait for proofs which
     have started.  (FinalExp itself -- degree 5 at blow-up 4, quotient_degree_factor == blow-up -- has no quotient chunk that must
     vanish, so like starky's prove() it cannot notice a broken trace; the 8192-row AIR that can is ECCAgg, degree 4: its commitment

@@ -1,5 +1,5 @@
-"""The proof pool's host logic (csrc/scheduler.cpp: generator threads, context workers, commitment scheduler, shutdown) under
-ThreadSanitizer on the CPU: tests/tsan_pool_main.cpp against the stand-in device of csrc/host_only_stubs.cc (no GPU, no proofs:
+"""The proof pool's host logic (csrc/pool.cpp, hash_service.cpp, multipool.cpp: generator threads, context workers, commitment
+scheduler, shutdown) under ThreadSanitizer on the CPU: tests/tsan_pool_main.cpp against the stand-in device of csrc/host_only_stubs.cc (no GPU, no proofs:
 contexts exist, prove() sleeps, asks the scheduler for its commitment and returns a blob).  All three commit policies, jobs that
 fail before and after their commitment, concurrent submit / wait, destroy with work queued."""
 import glob

@@ -1,4 +1,4 @@
-// Sanitizer harness for the proof pool's host logic (csrc/scheduler.cpp): generator threads, context workers, the commitment
+// Sanitizer harness for the proof pool's host logic (csrc/pool.cpp, hash_service.cpp, multipool.cpp): generator threads, context workers, the commitment
 // scheduler (gather window, merged launches, the two classes), job-to-context matching, failing jobs, shutdown with work queued.
 // Built by `make tsan-test` / `make asan-test` WITHOUT a GPU against the stand-ins of csrc/host_only_stubs.cc
 // (STARKHIP_FAKE_DEVICE=1: contexts exist, prove() sleeps and returns a blob that ends in the public inputs).  Test

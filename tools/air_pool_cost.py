@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What one proof of each AIR costs the chip when the pool is full of them: N proofs of ONE AIR through the library's pool (its default
 contexts, trace generation inside), milliseconds per proof = elapsed / N.  These are the weights of the longest-job-first placement
-(csrc/scheduler.cpp air_cost, parallel.AIR_COST): what a job adds to a device's queue is its share of the device's time, not its latency.
+(csrc/multipool.cpp air_cost, parallel.AIR_COST): what a job adds to a device's queue is its share of the device's time, not its latency.
 
     python tools/air_pool_cost.py [--proofs 48] > profiles/rNN_air_pool_cost.json
 """
