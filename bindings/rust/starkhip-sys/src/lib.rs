@@ -48,6 +48,8 @@ pub const STARKHIP_ERR_NO_DEVICE: c_int = -6;
 pub const STARKHIP_ERR_VERIFY: c_int = -7;
 pub const STARKHIP_ERR_BAD_AIR: c_int = -8;
 pub const STARKHIP_POW_SEARCH: u64 = u64::MAX;
+/// A registered AIR is proved on any power of two of rows in 2 ..= 2^STARKHIP_MAX_LOG_ROWS; a built-in AIR on at most 8192.
+pub const STARKHIP_MAX_LOG_ROWS: u32 = 20;
 pub const STARKHIP_N_PHASES: usize = 11;
 
 /// `starkhip_proof_layout_t`: word offsets of every field of the proof blob.

@@ -59,6 +59,12 @@ typedef struct {
  * CAPACITY of them per process */
 #define STARKHIP_AIR_CUSTOM_BASE 1024
 #define STARKHIP_AIR_CUSTOM_CAPACITY 4096
+/* Trace lengths.  A REGISTERED AIR is proved, checked and submitted to pools on any power of two of rows in 2 .. 2^STARKHIP_MAX_LOG_ROWS;
+ * the built-in AIRs (STARKHIP_AIR_TEST_FIBONACCI included) keep the reference's largest trace, 8192 rows -- their layouts are the
+ * reference's; a registered copy of a built-in program is how a caller proves it longer.  The bound comes from 32-bit byte offsets
+ * into one LDE column in the quotient kernel (2^(20 + 8) points of 8 bytes with rate_bits <= 8).  A trace whose buffers do not fit the
+ * device is STARKHIP_ERR_OOM and leaves the context usable. */
+#define STARKHIP_MAX_LOG_ROWS 20
 /* limits of a registered constraint program (starkhip_air_check_program); the five built-in AIRs are far inside them
  * (MillerLoop: 97 330 columns, ECCAgg: 12 824 public inputs, FinalExp: 2.4 M code words) */
 #define STARKHIP_AIR_MAX_COLUMNS (1u << 20)
@@ -123,7 +129,7 @@ int starkhip_air_eval_frame(starkhip_air_t air, const uint64_t* local, const uin
 int starkhip_air_check_program(const uint64_t* blob, size_t words, char* why, size_t why_len);
 /* Validates and registers a program; *id_out is its id from then on, for every entry point that takes an AIR (prove, the pools,
  * verify, verify_batch, the queries above, starkhip_check_trace).  The same blob again: the same id (its first name and rows stay).
- * name may be NULL; default_rows is 0 or a power of two in 2..8192 (what starkhip_air_default_rows reports).  BAD_AIR for a program
+ * name may be NULL; default_rows is 0 or a power of two in 2..2^STARKHIP_MAX_LOG_ROWS (what starkhip_air_default_rows reports).  BAD_AIR for a program
  * the validator refuses or a full registry (STARKHIP_AIR_CUSTOM_CAPACITY), BAD_SHAPE for bad arguments.  Thread-safe.  A registered
  * AIR has no trace generator: starkhip_pool_submit_witness and the witness batch refuse it with BAD_AIR.  Its config
  * (starkhip_config_for_air) is standard_fast with the smallest rate_bits >= 1 with 2^rate_bits >= degree - 1. */
@@ -165,7 +171,9 @@ void starkhip_shutdown(void* ctx);
  * (what trace_rows_to_poly_values returns).  trace_on_device != 0: `trace` is a device pointer
  * (already resident in HBM; the benchmark path).  pow_witness: STARKHIP_POW_SEARCH = smallest valid
  * nonce, otherwise use the given one.  *proof is a blob in the layout below.
- * Shapes: n_rows a power of two, 2 <= n_rows <= 8192 (the reference's largest trace; one LDS image per column),
+ * Shapes: n_rows a power of two, 2 <= n_rows <= 8192 for a built-in AIR (the reference's largest trace; one LDS image per column) and
+ * 2 <= n_rows <= 2^STARKHIP_MAX_LOG_ROWS for a registered one (from 2^14 rows on a column is transformed by several workgroups in two
+ * passes: csrc/kernels_lde_long.hip),
  * n_pis and n_cols as the AIR declares (n_cols is checked before the buffer is touched: it is read as n_rows x n_cols words), num_challenges = 2, and rate_bits large enough for the AIR's
  * constraint degree (2^rate_bits >= degree - 1); anything else is STARKHIP_ERR_BAD_SHAPE before any GPU work. */
 int starkhip_prove(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols,
@@ -184,7 +192,7 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
 /* Tuning knobs of a context (defaults are the measured best; tests and profiling tools use them to reach the other code
  * paths): "quotient_impl" 0 = tiled evaluator / 1 = op-stream interpreter, "quotient_chunks" (0 = automatic),
  * "quotient_waves", "quotient_slots", "lde_closed_forms" (1 = constant and unit-vector trace columns take their closed-form LDE
- * instead of five transforms, 0 = every column is transformed; same bytes either way), "host_commit_leaves" (default 64: trace commitments of at most this many leaves -- FP12Mul's 32 -- are hashed by host threads with the
+ * instead of five transforms, 0 = every column is transformed; same bytes either way; traces of 2^14 rows and more have no closed forms and transform every column), "host_commit_leaves" (default 64: trace commitments of at most this many leaves -- FP12Mul's 32 -- are hashed by host threads with the
  * challenger's permutation, 0.8 us against 5.6 us per permutation of a lone GPU wave; 0 = never; only with "leaf_hash_form" 0), "leaf_hash_form" (0 = a context on its own
  * hashes commitments of <= 4096 leaves in the row form -- 16 lanes per leaf, the shortest chain per leaf --, those of >= 32 768 leaves in
  * the pair form -- two lanes per leaf, one 256-register wave per SIMD -- and the ones between in the quad form; 1 = quad always; 2 = row always;
@@ -437,9 +445,13 @@ int starkhip_host_alloc(void* ctx, size_t bytes, void** out);
 void starkhip_host_free(void* p);
 
 /* --- kernel-level entry points (parity tests / micro-benchmarks) ---------------------- */
-/* values column-major [C][n] (host) -> coeffs [C][n] and LDE [C][N] in NATURAL point order i <-> 7*w_N^i */
+/* values column-major [C][n] (host) -> coeffs [C][n] and LDE [C][N] in NATURAL point order i <-> 7*w_N^i.  1 <= log_n <=
+ * STARKHIP_MAX_LOG_ROWS and rate_bits <= 8, BAD_SHAPE otherwise; from log_n 14 on through csrc/kernels_lde_long.hip */
 int starkhip_lde_batch(void* ctx, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out,
                        uint64_t* lde_out);
+/* n_vecs vectors of 2^log_len words (16 <= log_len <= 26; BAD_SHAPE otherwise) transformed in place by the multi-workgroup transform, as
+ * prove() transforms the quotient's values and the FRI layers: X[k] = sum_j x[j] w^(jk), or the inverse with 2^-log_len (inverse != 0) */
+int starkhip_ntt_long(void* ctx, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);
 /* Merkle cap of the matrix whose leaf j is the row bitrev(j) of an LDE given column-major natural order [C][N] */
 int starkhip_merkle_cap(void* ctx, const uint64_t* lde_colmajor, size_t n_cols, unsigned log_N, unsigned cap_height, uint64_t* cap_out);
 int starkhip_poseidon_permute_batch(void* ctx, uint64_t* states, size_t n_states);
@@ -447,7 +459,8 @@ int starkhip_poseidon_permute_batch(void* ctx, uint64_t* states, size_t n_states
  * every 64 of them constant (these take a closed form; a FinalExp trace has 11 in 64), `reps` launches between two HIP events; average
  * milliseconds per launch.  const_per_64 + 256: unit vectors instead of constants.  device_values != NULL: the caller's own column-major
  * matrix in device memory (n_cols x 2^log_n words) instead of the synthetic one.  reps == 0: one launch with no warm-up launch in front
- * of it.  each_ms (may be NULL): min(reps, 16) durations, launch by launch */
+ * of it.  each_ms (may be NULL): min(reps, 16) durations, launch by launch.  log_n up to STARKHIP_MAX_LOG_ROWS and rate_bits <= 8
+ * (BAD_SHAPE otherwise); columns of 2^14 rows and more have no closed forms, so const_per_64 changes nothing there */
 int starkhip_lde_bench(void* ctx, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values,
                        float* ms_per_launch, float* each_ms);
 /* a finished log through the device's expansion kernels (csrc/kernels_trace.hip) into a host matrix, COLUMN-major [C][n_rows] */

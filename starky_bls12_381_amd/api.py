@@ -35,6 +35,7 @@ AIR_NAMES = {AIR_FP12_MUL: "FP12MulStark", AIR_PAIRING_PRECOMP: "PairingPrecompS
              AIR_FINAL_EXP: "FinalExponentiateStark", AIR_ECC_AGGREGATE: "ECCAggStark", AIR_TEST_FIBONACCI: "TestFibonacci"}
 ECC_NUM_POINTS = 512  # src/ecc_aggregate.rs:7
 AIR_CUSTOM_BASE, AIR_CUSTOM_CAPACITY = 1024, 4096  # ids of registered AIRs (register_air): BASE, BASE + 1, ...
+MAX_LOG_ROWS = 20  # STARKHIP_MAX_LOG_ROWS: a registered AIR's trace has up to 2^20 rows (a built-in AIR's: 8192)
 
 ERR_QUOTIENT_NOT_DIVISIBLE, ERR_ZETA_IN_SUBGROUP, ERR_BAD_SHAPE, ERR_HIP, ERR_OOM, ERR_NO_DEVICE, ERR_VERIFY, ERR_BAD_AIR = range(-1, -9, -1)
 
@@ -87,6 +88,7 @@ lib.starkhip_prove_columns.argtypes = [C.c_void_p, C.c_int, C.POINTER(StarkConfi
 lib.starkhip_last_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
 lib.starkhip_last_kernel_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
 lib.starkhip_last_host_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+lib.starkhip_ntt_long.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_int]
 lib.starkhip_lde_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_uint, _u64p, _u64p]
 lib.starkhip_merkle_cap.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_uint, _u64p]
 lib.starkhip_poseidon_permute_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t]
@@ -208,7 +210,8 @@ def air_check_program(blob):
 
 def register_air(blob, name=None, default_rows=0):
     """Register a constraint program (csrc/air_ir.h format; air_builder.AirBuilder makes one) and return its AIR id, usable wherever a
-    built-in id is.  The same blob again returns the same id.  A program the validator refuses raises StarkhipError(ERR_BAD_AIR)."""
+    built-in id is.  The same blob again returns the same id.  A program the validator refuses raises StarkhipError(ERR_BAD_AIR).
+    default_rows: 0, or a power of two in 2 .. 2^MAX_LOG_ROWS (anything else: ERR_BAD_SHAPE)."""
     blob = np.ascontiguousarray(blob, dtype=np.uint64)
     out = C.c_int()
     _chk(lib.starkhip_air_register(_p64(blob), blob.size, name.encode() if name is not None else None, default_rows, C.byref(out)))
@@ -606,6 +609,13 @@ class Prover:
         ms = (C.c_float * 3)()
         _chk(lib.starkhip_last_kernel_timings(self._ctx, ms))
         return {"lde_columns": float(ms[0]), "leaf_hash": float(ms[1]), "quotient_eval": float(ms[2])}
+
+    def ntt_long(self, vectors, inverse=False):
+        """starkhip_ntt_long: the rows of `vectors` (2^16 .. 2^26 words each) through the multi-workgroup transform; returns the transforms."""
+        v = np.ascontiguousarray(vectors, dtype=np.uint64).copy()
+        n_vecs, n = v.shape
+        _chk(lib.starkhip_ntt_long(self._ctx, _p64(v), n_vecs, n.bit_length() - 1, 1 if inverse else 0))
+        return v
 
     def lde_batch(self, values_colmajor, rate_bits):
         v = np.ascontiguousarray(values_colmajor, dtype=np.uint64)

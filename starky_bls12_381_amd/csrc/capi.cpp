@@ -128,7 +128,7 @@ int starkhip_air_check_program(const uint64_t* blob, size_t words, char* why, si
 }
 
 int starkhip_air_register(const uint64_t* blob, size_t words, const char* name, uint32_t default_rows, starkhip_air_t* id_out) {
-    if (!id_out || (default_rows && (default_rows < 2 || default_rows > 8192 || (default_rows & (default_rows - 1))))) return STARKHIP_ERR_BAD_SHAPE;
+    if (!id_out || (default_rows && (default_rows < 2 || default_rows > (1u << STARKHIP_MAX_LOG_ROWS) || (default_rows & (default_rows - 1))))) return STARKHIP_ERR_BAD_SHAPE;
     try {
         AirProgram prog;
         if (!air_parse_checked(blob, words, &prog, nullptr)) return STARKHIP_ERR_BAD_AIR;
@@ -648,6 +648,10 @@ int starkhip_lde_batch(void* ctx, const uint64_t* values, size_t n_cols, unsigne
                        uint64_t* lde_out) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     return lde_batch((Ctx*)ctx, values, n_cols, log_n, rate_bits, coeffs_out, lde_out);
+}
+int starkhip_ntt_long(void* ctx, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    return ntt_long((Ctx*)ctx, data, n_vecs, log_len, inverse);
 }
 int starkhip_merkle_cap(void* ctx, const uint64_t* lde_colmajor, size_t n_cols, unsigned log_N, unsigned cap_height, uint64_t* cap_out) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;

@@ -102,6 +102,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
     return STARKHIP_OK;
 }
 int lde_batch(Ctx*, const uint64_t*, size_t, unsigned, unsigned, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
+int ntt_long(Ctx*, uint64_t*, size_t, unsigned, int) { return STARKHIP_ERR_NO_DEVICE; }
 int merkle_cap(Ctx*, const uint64_t*, size_t, unsigned, unsigned, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int permute_batch(Ctx*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int permute_batch_form(Ctx*, int, int, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }

@@ -57,6 +57,25 @@ size_t lde_wave_table_words(unsigned rate_bits);
 hipError_t lde_wave_upload_tables(unsigned rate_bits, gl_t* d_tab, hipStream_t st);
 hipError_t launch_lde_columns_wave(const gl_t* values, gl_t* lde, size_t n_cols, unsigned rate_bits, const gl_t* d_tab, const gl_t* oh, unsigned* next,
                                    hipStream_t st);
+// 2^14 .. 2^26 points, a vector split over workgroups in two passes (kernels_lde_long.hip; tools/lde_long_model.py).  `sub`: the
+// sub-transforms' twiddles (lde_long_sub_words() words, the same for every length; the inverse ones carry the inverse's n^-1);
+// tw_fwd / tw_inv: the inter-pass twiddles w_n^(+-j0 k1) of ONE length (2^log_n words each, lde_long_fill_twiddles).
+bool lde_long_supported(unsigned log_n);
+size_t lde_long_sub_words();
+hipError_t lde_long_upload_sub_tables(gl_t* d_sub, hipStream_t st);
+hipError_t lde_long_fill_twiddles(gl_t* d_fwd, gl_t* d_inv, unsigned log_n, hipStream_t st);
+struct LdeLongTables {
+    const gl_t *sub, *tw_fwd, *tw_inv;
+};
+// values -> coeffs -> lde (coset-major); `coeffs` is required unless from_coeffs (it is the transforms' scratch too; may be `values`);
+// cs[s][j] = (7 w_N^s)^j, N words
+hipError_t launch_lde_columns_long(const gl_t* values, gl_t* coeffs, gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate_bits, const LdeLongTables& tb,
+                                   const gl_t* cs, int from_coeffs, hipStream_t st);
+// n_vecs vectors, vec_stride words apart in src, mid and dst alike: src (* pre_scale) -> mid -> dst (* post_scale); the inverse carries
+// n^-1.  mid must not overlap src; dst may be mid or src.
+hipError_t launch_ntt_long(const gl_t* src, gl_t* mid, gl_t* dst, size_t n_vecs, size_t vec_stride, unsigned log_n, bool inverse, const gl_t* pre_scale,
+                           const gl_t* post_scale, const LdeLongTables& tb, hipStream_t st);
+// one workgroup per vector: the short vectors of a proof (up to 2^15 words), and those beyond 2^26
 hipError_t launch_ntt_global(gl_t* data, size_t n_vecs, size_t vec_stride, unsigned log_n, const gl_t* tw, unsigned tw_log,
                              const gl_t* pre_scale, const gl_t* post_scale, gl_t final_mul, hipStream_t st);
 

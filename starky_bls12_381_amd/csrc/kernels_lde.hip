@@ -23,101 +23,12 @@
 
 #include "gl_dev.h"
 #include "kernels.h"
+#include "lde_radix.h"
 
 namespace starkhip {
 
-// ---------------------------------------------------------------- register sub-transforms
-constexpr int bitrev_c(int k, int bits) {
-    int r = 0;
-    for (int i = 0; i < bits; i++) r |= ((k >> i) & 1) << (bits - 1 - i);
-    return r;
-}
-constexpr int ilog2_c(int x) { return x <= 1 ? 0 : 1 + ilog2_c(x >> 1); }
-
-// Decimation-in-frequency radix-2 network of size R on v[BASE + STRIDE * i], root w_R = 2^(39 * 64 / R) (or its
-// inverse).  Leaves X[k] at i = bitrev(k).
-template <int R, bool INV, int BASE, int STRIDE>
-struct Dif {
-    static __device__ __forceinline__ void run(gl_t (&v)[16]) {
-        constexpr int H = R / 2;
-        constexpr int E_FWD = (39 * (64 / R)) % 192;
-        constexpr int E = INV ? (192 - E_FWD) % 192 : E_FWD;
-#pragma unroll
-        for (int i = 0; i < H; i++) {
-            const int e = (E * i) % 192;
-            const gl_t a = v[BASE + STRIDE * i], b = v[BASE + STRIDE * (i + H)];
-#ifdef STARKHIP_LDE_NN_BUTTERFLY  // the round-2 form: both operands arbitrary representatives, two wrap corrections per sum and difference
-            v[BASE + STRIDE * i] = gl_add_nn(a, b);
-            v[BASE + STRIDE * (i + H)] = e < 96 ? gl_mul_pow2_nn(gl_sub_nn(a, b), e) : gl_mul_pow2_nn(gl_sub_nn(b, a), e - 96);
-#else
-            // One operand canonical (3 instructions) makes both the sum and the difference single-correction forms (4 + 5
-            // instead of 7 + 8): the second wrap of a + b or a - b needs BOTH operands >= p - 1 (gl_dev.h).  The subtrahend is
-            // the canonical one: b for (a - b) 2^e, a for the negated form (b - a) 2^(e - 96).
-            if (e < 96) {
-                const gl_t bc = gl_canon(b);
-                v[BASE + STRIDE * i] = gl_add_nc(a, bc);
-                v[BASE + STRIDE * (i + H)] = gl_mul_pow2_nn(gl_sub_nc(a, bc), e);
-            } else {
-                const gl_t ac = gl_canon(a);
-                v[BASE + STRIDE * i] = gl_add_nc(b, ac);
-                v[BASE + STRIDE * (i + H)] = gl_mul_pow2_nn(gl_sub_nc(b, ac), e - 96);
-            }
-#endif
-        }
-        Dif<H, INV, BASE, STRIDE>::run(v);
-        Dif<H, INV, BASE + STRIDE * H, STRIDE>::run(v);
-    }
-};
-template <bool INV, int BASE, int STRIDE>
-struct Dif<1, INV, BASE, STRIDE> {
-    static __device__ __forceinline__ void run(gl_t (&)[16]) {}
-};
-
-// S = 16 / R independent size-R transforms: transform m lives in v[m + S * i]; natural order in and out.
-template <int R, bool INV, int M>
-struct SubNtts {
-    static __device__ __forceinline__ void run(gl_t (&v)[16]) {
-        constexpr int S = 16 / R;
-        Dif<R, INV, M, S>::run(v);
-        if constexpr (M + 1 < S) SubNtts<R, INV, M + 1>::run(v);
-    }
-};
-template <int R>
-__device__ __forceinline__ void unscramble(gl_t (&v)[16]) {
-    constexpr int S = 16 / R, LOGR = ilog2_c(R);
-    gl_t w[16];
-#pragma unroll
-    for (int m = 0; m < S; m++)
-#pragma unroll
-        for (int k = 0; k < R; k++) w[m + S * k] = v[m + S * bitrev_c(k, LOGR)];
-#pragma unroll
-    for (int i = 0; i < 16; i++) v[i] = w[i];
-}
-
-// ---------------------------------------------------------------- pass structure
-template <int LOGN>
-struct LdePlan {
-    static constexpr int N = 1 << LOGN;
-    static constexpr int T = N / 16;                       // threads per column
-    static constexpr int FULL = LOGN / 4;                  // radix-16 passes
-    static constexpr int TAIL = LOGN % 4;                  // log2 of the last pass's radix (0: none)
-    static constexpr int NP = FULL + (TAIL ? 1 : 0);
-    static constexpr int radix(int p) { return p < FULL ? 16 : (1 << TAIL); }
-    static constexpr int ns(int p) { return p == 0 ? 1 : ns(p - 1) * radix(p - 1); }
-    // twiddle table: passes 1 .. NP-1, each radix(p) rows of ns(p) entries
-    static constexpr int tw_off(int p) { return p <= 1 ? 0 : tw_off(p - 1) + radix(p - 1) * ns(p - 1); }
-    static constexpr int tw_words() { return tw_off(NP); }
-    static constexpr int THREADS = T < 256 ? 256 : T;
-    static constexpr int CPB = THREADS / T;                // columns per workgroup
-    static constexpr int LDS_COL = N + N / 16;             // padded elements per column
-};
-
+// (register sub-transforms, LdePlan and the exchange barrier: lde_radix.h)
 __device__ __forceinline__ int lds_pad(int a) { return a + (a >> 4); }
-#ifdef STARKHIP_LDE_FULL_BARRIER
-__device__ __forceinline__ void lde_lds_barrier() { __syncthreads(); }
-#else
-__device__ __forceinline__ void lde_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#endif
 
 // The inter-pass twiddles of pass P for this thread: w_{NS*R}^{i * (j mod NS)}, j = t + m * T; the inverse transform's last pass also
 // carries n^-1 (row 0).  Uniform row base + 32-bit lane offset => scalar-base loads, no per-load address registers.  They depend on the
@@ -245,6 +156,7 @@ __global__ __launch_bounds__(LdePlan<LOGN>::THREADS, 4) void lde_columns_v2_kern
             //   constant c:   coefficients (c, 0, ..., 0), LDE = c everywhere;
             //   unit vector e_r (one 1 in row r, zeros elsewhere): coefficients n^-1 w_n^(-r j) = oh[(r j) mod n], and its LDE is
             //   the LDE of e_0 rotated by r inside every coset: lde_r[s][k] = lde_0[s][(k - r) mod n] = oh[n + s n + ((k - r) mod n)].
+            // (Traces of 2^14 rows and more -- kernels_lde_long.hip -- have no closed forms: every column is transformed there.)
             // Both are the exact field values the transforms would produce (canonical), so the proof bytes do not change.  The
             // class is found from the values themselves (one barrier per column); one workgroup = one column here.
             if (oh != nullptr) {
@@ -632,28 +544,6 @@ __global__ __launch_bounds__(512, 4) void lde_columns_wave_kernel(const gl_t* va
 }
 
 // ---------------------------------------------------------------- host side
-template <int LOGN>
-static void fill_tw(std::vector<gl_t>& out, bool inv) {
-    using PL = LdePlan<LOGN>;
-    out.assign(PL::tw_words() ? PL::tw_words() : 1, 1);
-    const gl_t ninv = gl_inv((gl_t)PL::N);
-    if (PL::NP == 1) out[0] = inv ? ninv : 1;
-    for (int p = 1; p < PL::NP; p++) {
-        const int R = PL::radix(p), NS = PL::ns(p);
-        gl_t w = gl_root_of_unity(ilog2_c(NS * R));
-        if (inv) w = gl_inv(w);
-        const gl_t scale = (inv && p == PL::NP - 1) ? ninv : 1;
-        for (int i = 0; i < R; i++) {
-            const gl_t wi = gl_pow(w, i);
-            gl_t acc = scale;
-            for (int jj = 0; jj < NS; jj++) {
-                out[PL::tw_off(p) + i * NS + jj] = acc;
-                acc = gl_mul(acc, wi);
-            }
-        }
-    }
-}
-
 template <int LOGN>
 static hipError_t launch_v2(const gl_t* values, gl_t* coeffs, gl_t* lde, size_t n_cols, unsigned rate_bits, const gl_t* tw_fwd,
                             const gl_t* tw_inv, const gl_t* cs, const gl_t* oh, int from_coeffs, hipStream_t st) {

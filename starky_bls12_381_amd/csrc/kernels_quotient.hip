@@ -206,7 +206,7 @@ __global__ __launch_bounds__(64) void quotient_eval_kernel(QuotientParams P) { S
     L.mask_tr = P.tab[t];
     L.mask_first = P.tab[size + t];
     L.mask_last = P.tab[2 * size + t];
-    L.boff_local = (s * (unsigned)n + k) * 8u;  // < 2^32: N * 8 <= 2^(13+3+3)
+    L.boff_local = (s * (unsigned)n + k) * 8u;  // < 2^32: N * 8 <= 2^(20+8+3) (STARKHIP_MAX_LOG_ROWS rows, rate_bits <= 8)
     L.boff_next = (s * (unsigned)n + ((k + 1) & (unsigned)(n - 1))) * 8u;
     L.col_shift = P.log_n + P.rate_bits + 3;
     gl_t* cache_lane = cell_cache + threadIdx.x;
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(64 * (QT_WAVES + 1), 4) void quotient_tiles_kernel(
     const unsigned k_next = (k + 1) & (unsigned)(n - 1);
     const char* const lde = (const char*)P.lde;
     const unsigned col_shift = P.log_n + P.rate_bits + 3;
-    const uint32_t boff_local = (s * (unsigned)n + k) * 8u;  // < 2^32: N * 8 <= 2^(13+3+3)
+    const uint32_t boff_local = (s * (unsigned)n + k) * 8u;  // < 2^32: N * 8 <= 2^(20+8+3) (STARKHIP_MAX_LOG_ROWS rows, rate_bits <= 8)
     const uint32_t boff_next = (s * (unsigned)n + k_next) * 8u;
     const uint32_t* tiles = P.tile_list + P.chunk_tile_off[chunk];
     const unsigned n_tiles = P.chunk_tile_off[chunk + 1] - P.chunk_tile_off[chunk];

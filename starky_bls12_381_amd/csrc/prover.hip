@@ -126,7 +126,19 @@ struct Ctx {
         DevBuf tw_fwd, tw_inv, coset_scale, qtab, qshift_inv;
         DevBuf lde2_fwd, lde2_inv, lde2_cs, lde2_oh;  // kernels_lde.hip tables (log_n >= 8)
         DevBuf lde_wave;                               // ... and of its wave-resident kernel (log_n == 13)
-        std::vector<DevBuf*> bufs() { return {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave}; }
+        // kernels_lde_long.hip (log_n >= 14, and the proof's other vectors of 2^16 .. 2^20 words): the coset powers (7 w_N^s)^j, the
+        // sub-transforms' twiddles, and the inter-pass twiddles of every length this shape has transformed (ensure_long_tw)
+        DevBuf long_cs, long_sub;
+        struct LongTw { unsigned log_len; DevBuf fwd, inv; };
+        std::vector<std::unique_ptr<LongTw>> long_tw;
+        std::vector<DevBuf*> bufs() {
+            std::vector<DevBuf*> v = {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave, &long_cs, &long_sub};
+            for (auto& t : long_tw) {
+                v.push_back(&t->fwd);
+                v.push_back(&t->inv);
+            }
+            return v;
+        }
     };
     struct PlanDev {  // tiled plan (quotient_plan.h) of one AIR on the device
         int air = -1;
@@ -250,7 +262,7 @@ static int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb) {
     std::unique_ptr<Ctx::Tables> fresh(new Ctx::Tables());  // a half-built set of tables is not kept: it goes with `fresh`, buffers and all
     Ctx::Tables* T = fresh.get();
     const unsigned log_N = log_n + rate;
-    const size_t N = (size_t)1 << log_N, size = (size_t)1 << (log_n + qdb);
+    const size_t N = (size_t)1 << log_N, size = (size_t)1 << (log_n + qdb), n_rows = (size_t)1 << log_n;
     HIPCHK(T->tw_fwd.ensure(N / 2 * 8 + 8));
     HIPCHK(T->tw_inv.ensure(N / 2 * 8 + 8));
     HIPCHK(T->coset_scale.ensure(N * 8));
@@ -273,6 +285,11 @@ static int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb) {
             HIPCHK(lde_wave_upload_tables(rate, T->lde_wave.as<gl_t>(), c->st));
         }
     }
+    if (lde_long_supported(log_n)) {
+        HIPCHK(T->long_cs.ensure(N * 8));
+        for (size_t s = 0; s < ((size_t)1 << rate); s++)
+            HIPCHK(launch_fill_powers(T->long_cs.as<gl_t>() + s * n_rows, 1, gl_mul(GL_GENERATOR, gl_pow(w, s)), n_rows, c->st));
+    }
     T->log_n = log_n;
     T->rate = rate;
     T->qdb = qdb;
@@ -281,8 +298,46 @@ static int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb) {
     return 0;
 }
 
+// Vectors of 2^16 .. 2^26 words go through the multi-workgroup transform (kernels_lde_long.hip; above 2^20 words in tiles narrower than a
+// cache line); shorter ones stay with the one-workgroup ntt_global_kernel (no proof of up to 8192 rows changes its kernels).  So does what
+// is longer still: only 2^19 rows and more at rate_bits 8 have such a vector.  Trace columns take it from 2^14 rows on (run_lde).
+static bool long_vector(unsigned log_len) { return log_len > 15 && lde_long_supported(log_len); }
+
+// The long transform's tables for vectors of 2^log_len words, cached with the current shape's tables
+static int ensure_long_tw(Ctx* c, unsigned log_len, LdeLongTables* out) {
+    Ctx::Tables* T = c->tab;
+    if (!T->long_sub.p) {
+        HIPCHK(T->long_sub.ensure(lde_long_sub_words() * 8));
+        if (hipError_t e = lde_long_upload_sub_tables(T->long_sub.as<gl_t>(), c->st); e != hipSuccess) {
+            T->long_sub.release();
+            HIPCHK(e);
+        }
+    }
+    Ctx::Tables::LongTw* tw = nullptr;
+    for (auto& t : T->long_tw)
+        if (t->log_len == log_len) tw = t.get();
+    if (!tw) {
+        std::unique_ptr<Ctx::Tables::LongTw> fresh(new Ctx::Tables::LongTw());
+        fresh->log_len = log_len;
+        HIPCHK(fresh->fwd.ensure(((size_t)8) << log_len));
+        HIPCHK(fresh->inv.ensure(((size_t)8) << log_len));
+        HIPCHK(lde_long_fill_twiddles(fresh->fwd.as<gl_t>(), fresh->inv.as<gl_t>(), log_len, c->st));
+        tw = fresh.get();
+        T->long_tw.push_back(std::move(fresh));
+    }
+    if (out) *out = LdeLongTables{T->long_sub.as<gl_t>(), tw->fwd.as<gl_t>(), tw->inv.as<gl_t>()};
+    return 0;
+}
+
 // IFFT + coset LDE of `cols` columns with the tables of ensure_tables(log_n, rate, .)
 static hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs) {
+    // 2^14 rows and more: a column is split over workgroups; `coeffs` is that transform's scratch as well (required unless from_coeffs).
+    // No closed forms for constant / unit-vector columns there ("lde_closed_forms" has nothing to switch).
+    if (lde_long_supported(log_n)) {
+        LdeLongTables tb;
+        if (const int rc = ensure_long_tw(c, log_n, &tb)) return rc == STARKHIP_ERR_OOM ? hipErrorOutOfMemory : hipErrorUnknown;
+        return launch_lde_columns_long(values, coeffs, lde, cols, log_n, rate, tb, c->tab->long_cs.as<gl_t>(), from_coeffs, c->st);
+    }
     // 8192-row traces (FinalExp, ECCAgg): values -> LDE with nothing kept in between goes through the wave-resident kernel
     if (lde_wave_supported(log_n) && !coeffs && !from_coeffs && c->opt_lde_impl == 0) {
         // the launch's column counter: the last word of the table buffer, cleared in stream order before every launch
@@ -615,18 +670,24 @@ static hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_
     return launch_leaf_hash(lde, n_cols, log_n, rate, digests, st);
 }
 
+// THE rule for trace lengths: the built-in AIRs keep the reference's largest trace (8192 rows; their layouts are the reference's), a
+// registered AIR goes up to 2^STARKHIP_MAX_LOG_ROWS.  That bound comes from the quotient kernel's 32-bit byte offsets into one LDE column
+// (kernels_quotient.hip: N * 8 < 2^32 with rate_bits <= 8).
+static unsigned max_log_rows(const AirInfo& air) { return air.id >= STARKHIP_AIR_CUSTOM_BASE ? (unsigned)STARKHIP_MAX_LOG_ROWS : 13u; }
+
 // The dimensions of one proof, derived in one place: prove() and ctx_reserve() size and lay out everything from these.
 struct ProofShape {
     unsigned log_n, r, cap_h, log_N, qdb, factor;  // log2 of rows, blow-up, cap size, LDE points; the quotient's degree bits and factor
     size_t n, N, C, Q, size, ncap, L;              // rows, LDE points, trace and quotient columns, quotient points (n << qdb), cap nodes, FRI layers
     FriGeometry geo;
     ProofLayout pl;
-    // STARKHIP_ERR_BAD_SHAPE for what prove() refuses: rows that are no power of two in 2 .. 8192, a config that the one config rule
-    // (FriGeometry::make) refuses or whose blow-up is below the AIR's quotient degree
-    static int make(const AirProgram& P, const starkhip_config_t& cfg, size_t n_rows, ProofShape* s) {
+    // STARKHIP_ERR_BAD_SHAPE for what prove() refuses: rows that are no power of two in 2 .. 2^max_log_rows(air), a config that the one
+    // config rule (FriGeometry::make) refuses or whose blow-up is below the AIR's quotient degree
+    static int make(const AirInfo& air, const starkhip_config_t& cfg, size_t n_rows, ProofShape* s) {
+        const AirProgram& P = air.prog;
         unsigned log_n = 0;
-        while (((size_t)1 << log_n) < n_rows) log_n++;
-        if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || cfg.num_challenges != 2 || log_n > 13) return STARKHIP_ERR_BAD_SHAPE;
+        while (log_n < 63 && ((size_t)1 << log_n) < n_rows) log_n++;
+        if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || cfg.num_challenges != 2 || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
         if (!FriGeometry::make(cfg, log_n, &s->geo) || quotient_degree_bits(P.degree) > cfg.rate_bits) return STARKHIP_ERR_BAD_SHAPE;
         s->log_n = log_n; s->r = cfg.rate_bits; s->cap_h = cfg.cap_height; s->log_N = log_n + s->r;
         s->qdb = quotient_degree_bits(P.degree); s->factor = quotient_factor(P.degree);
@@ -666,6 +727,43 @@ static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n
         w.push_back({&c->fri_digests[l], digest_words(len) * 8});
     }
     return w;
+}
+
+// `values` of a proof: the columns the last LDE launch of a parked trace reads (run_lde_trace), a whole trace, or -- a short trace read
+// from the caller's own columns -- nothing.  A long trace always has a whole trace of words there: its coefficients (run_lde).
+static size_t values_bytes_for(const ProofShape& s, bool trace_in_lde, bool callers_columns) {
+    if (lde_long_supported(s.log_n)) return s.C * s.n * 8;
+    return trace_in_lde ? lde_tail_columns(s.C) * s.n * 8 : callers_columns ? 0 : s.C * s.n * 8;
+}
+
+// The long transform's tables for every length a proof of shape `s` transforms: the trace and quotient columns (n), the quotient's
+// values (n << qdb), the combined polynomial (n) and the FRI layers
+static int ensure_long_tables(Ctx* c, const ProofShape& s) {
+    std::vector<unsigned> logs = {s.log_n, s.log_n + s.qdb};
+    unsigned log_len = s.log_N;
+    for (size_t l = 0; l < s.L; l++) {
+        logs.push_back(log_len);
+        log_len -= s.geo.arities[l];
+    }
+    for (unsigned lg : logs)
+        if (lg == s.log_n ? lde_long_supported(lg) : long_vector(lg))
+            if (int rc = ensure_long_tw(c, lg, nullptr)) return rc;
+    return 0;
+}
+
+// In-place transform of n_vecs vectors of 2^log_len words, vec_stride apart, as launch_ntt_global does it (inverse: tw_inv's direction and
+// final_mul = 2^-log_len) -- through the multi-workgroup transform where the vectors are long, with `mid` (as many words, not `data`) between its passes
+static int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,
+                   const gl_t* post_scale) {
+    if (long_vector(log_len)) {
+        LdeLongTables tb;
+        if (int rc = ensure_long_tw(c, log_len, &tb)) return rc;
+        HIPCHK(launch_ntt_long(data, mid, data, n_vecs, vec_stride, log_len, inverse, pre_scale, post_scale, tb, c->st));
+        return 0;
+    }
+    HIPCHK(launch_ntt_global(data, n_vecs, vec_stride, log_len, inverse ? c->tab->tw_inv.as<gl_t>() : c->tab->tw_fwd.as<gl_t>(), (unsigned)c->tab->log_n + c->tab->rate,
+                             pre_scale, post_scale, inverse ? gl_inv((gl_t)1 << log_len) : 1, c->st));
+    return 0;
 }
 
 // What one prove() call carries from phase to phase, and the phases: named like the entries of starkhip_last_timings and the rocTX
@@ -765,7 +863,8 @@ int ProveCall::upload() {
 // ---- phase 1: IFFT + LDE (PolynomialBatch::from_values, App. A.3)
 int ProveCall::ifft_lde() {
     HIPCHK(hipEventRecord(c->kev[4], st));
-    HIPCHK(run_lde_trace(c, d_values, c->lde.as<gl_t>(), c->values.as<gl_t>(), s.C, s.log_n, s.r, trace_in_lde));
+    if (lde_long_supported(s.log_n)) HIPCHK(run_lde(c, d_values, c->values.as<gl_t>(), c->lde.as<gl_t>(), s.C, s.log_n, s.r, 0));  // coefficients into `values`
+    else HIPCHK(run_lde_trace(c, d_values, c->lde.as<gl_t>(), c->values.as<gl_t>(), s.C, s.log_n, s.r, trace_in_lde));
     HIPCHK(hipEventRecord(c->kev[5], st));
     return 0;
 }
@@ -903,8 +1002,8 @@ int ProveCall::quotient() {
     if (c->opt_quotient_debug == 9 && !tiled)
         if (int rc = compare_quotient_evaluators()) return rc;
     // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
-    HIPCHK(launch_ntt_global(c->qvals.as<gl_t>(), 2, size, s.log_n + s.qdb, c->tab->tw_inv.as<gl_t>(), s.log_N, nullptr, c->tab->qshift_inv.as<gl_t>(),
-                             gl_inv((gl_t)size), st));
+    if (int rc = run_ntt(c, c->qvals.as<gl_t>(), c->partial.as<gl_t>(), 2, size, s.log_n + s.qdb, true, nullptr, c->tab->qshift_inv.as<gl_t>()))  // (the chunks' partial sums are spent)
+        return rc;
     // trim_to_len(n * factor) must succeed (quotient_commit() looks at the tail), then chunks of n: [alpha0: c0..cf-1, alpha1: c0..cf-1]
     if (size > factor * n) {
         quot_tail.resize(2 * (size - factor * n));
@@ -978,7 +1077,7 @@ int ProveCall::fri_combine() {
     gl2_t* comb_q = c->comb_out.as<gl2_t>() + n;  // [n] extension elements
     HIPCHK(launch_fri_combine(c->lde.as<gl_t>(), N, C, n, c->ext_apow.as<gl2_t>(), COMB_PPC, comb_chunks(C), c->comb_partial.as<gl2_t>(), st));
     HIPCHK(launch_ext_reduce(c->comb_partial.as<gl2_t>(), comb_chunks(C), n, comb_t, st));
-    HIPCHK(launch_ntt_global(comb_t, 2, n, s.log_n, c->tab->tw_inv.as<gl_t>(), s.log_N, nullptr, c->tab->qshift_inv.as<gl_t>(), gl_inv((gl_t)n), st));
+    if (int rc = run_ntt(c, comb_t, c->fri_vals.as<gl_t>(), 2, n, s.log_n, true, nullptr, c->tab->qshift_inv.as<gl_t>())) return rc;  // (fri_vals: idle until fri_commit)
     HIPCHK(launch_fri_combine(c->qcoef.as<gl_t>(), n, Q, n, c->ext_apow.as<gl2_t>() + C, Q, 1, comb_q, st));  // alpha^(C+q) quotient_q
     std::vector<gl_t> F1w(2 * n);
     std::vector<gl2_t> F1(n), tailq(n), F0(n), q0(n), q1(n), fin(n);
@@ -1016,10 +1115,16 @@ int ProveCall::fri_commit() {
     gl_t* vals = c->fri_vals.as<gl_t>();
     for (size_t l = 0; l < s.L; l++) {
         // values on shift * <w_len>
-        HIPCHK(hipMemcpyAsync(vals, coef, len * 8, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(vals + len, coef + len, len * 8, hipMemcpyDeviceToDevice, st));
         HIPCHK(launch_fill_powers(c->scale_tab.as<gl_t>(), 1, shift, len, st));
-        HIPCHK(launch_ntt_global(vals, 2, len, log_len, c->tab->tw_fwd.as<gl_t>(), s.log_N, c->scale_tab.as<gl_t>(), nullptr, 1, st));
+        if (long_vector(log_len)) {  // coef -> vals in the transform's first pass, the second in place
+            LdeLongTables tb;
+            if (int rc = ensure_long_tw(c, log_len, &tb)) return rc;
+            HIPCHK(launch_ntt_long(coef, vals, vals, 2, len, log_len, false, c->scale_tab.as<gl_t>(), nullptr, tb, st));
+        } else {
+            HIPCHK(hipMemcpyAsync(vals, coef, len * 8, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(vals + len, coef + len, len * 8, hipMemcpyDeviceToDevice, st));
+            HIPCHK(launch_ntt_global(vals, 2, len, log_len, c->tab->tw_fwd.as<gl_t>(), s.log_N, c->scale_tab.as<gl_t>(), nullptr, 1, st));
+        }
         const unsigned ab = s.geo.arities[l];
         const size_t n_leaves = len >> ab, width = 2 << ab;
         HIPCHK(launch_fri_leaves(vals, log_len, ab, c->fri_rows[l].as<gl_t>(), st));
@@ -1160,7 +1265,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
         }
     } read_back_guard{c};
     ProofShape s;
-    if (n_pis != air.prog.n_pis || ProofShape::make(air.prog, cfg, n_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
+    if (n_pis != air.prog.n_pis || ProofShape::make(air, cfg, n_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     for (size_t i = 0; i < n_pis; i++)
         if (pis_host[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
@@ -1182,10 +1287,14 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
     } else if (!on_device && layout == 0) {
         park_words = C * n;
     }
-    const bool trace_in_lde = s.r >= 1 && park_words <= (((size_t)1 << s.r) - 1) * C * n && !callers_columns;
+    // A long trace (2^14 rows and more) is not parked there: its transform goes through the LDE buffer between its two passes and keeps
+    // the coefficients in `values`, a whole trace of words, whoever owns the input (run_lde).
+    const bool long_trace = lde_long_supported(s.log_n);
+    const bool trace_in_lde = s.r >= 1 && park_words <= (((size_t)1 << s.r) - 1) * C * n && !callers_columns && !long_trace;
     // `values`: the columns the last LDE launch reads (run_lde_trace), a whole trace, or nothing this proof needs
-    const size_t values_bytes = trace_in_lde ? lde_tail_columns(C) * n * 8 : callers_columns ? 0 : C * n * 8;
+    const size_t values_bytes = values_bytes_for(s, trace_in_lde, callers_columns);
     for (const BufWant& w : work_buffers(c, s, n_chunks, values_bytes, park_words * 8)) HIPCHK(w.b->ensure(w.bytes));
+    if (int rc = ensure_long_tables(c, s)) return rc;
 
     ProveCall p{c, air, cfg, s, st, trace, pis_host, layout, on_device, pow_witness, tiled, n_chunks, trace_in_lde,
                 trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()};
@@ -1233,14 +1342,15 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
 // because its buffers grew while four FinalExp proofs kept the device busy.
 int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t log_bytes, unsigned proof_blobs, bool device_traces) {
     ProofShape s;
-    if (ProofShape::make(air.prog, cfg, air.default_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
+    if (ProofShape::make(air, cfg, air.default_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
     if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
     if (int rc = ensure_plan(c, air, s.size)) return rc;
     // `values`: a trace waits for its LDE inside the LDE buffer (prove(): trace_in_lde) but for the tail of run_lde_trace; rate_bits == 0
     // makes prove() ask for a whole trace.  The LDE buffer also stages the upload: a recording of log_bytes.
-    const size_t values_bytes = (s.r >= 1 ? lde_tail_columns(s.C) : s.C) * s.n * 8;
+    const size_t values_bytes = values_bytes_for(s, s.r >= 1, false);
     for (const BufWant& w : work_buffers(c, s, c->plan->chunks, values_bytes, log_bytes + 64)) HIPCHK(w.b->ensure(w.bytes));
+    if (int rc = ensure_long_tables(c, s)) return rc;
     if (log_bytes && !device_traces) HIPCHK(ensure_host_staging(c, log_bytes, log_bytes));
     if (proof_blobs && !c->blob_airs.count(air.id)) {  // page-locked blobs for this AIR's proofs, once per context
         if (blob_arena_add(c, s.pl.total * 8, proof_blobs) != 0) return STARKHIP_ERR_OOM;
@@ -1251,7 +1361,7 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t
 
 // ---------------------------------------------------------------- kernel-level entry points (tests)
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out) {
-    if (log_n < 1 || log_n > 13) return STARKHIP_ERR_BAD_SHAPE;
+    if (log_n < 1 || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
     int rc;
     if ((rc = ensure_tables(c, log_n, rate_bits, 0))) return rc;
@@ -1288,17 +1398,35 @@ int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, uns
     return STARKHIP_OK;
 }
 
+// kernel-level test entry: n_vecs vectors of 2^log_len words (2^16 .. 2^26) through the multi-workgroup transform as prove() runs it on
+// the quotient's values and the FRI layers -- in place, forward or inverse (with 2^-log_len)
+int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse) {
+    if (!long_vector(log_len) || !n_vecs || !data) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = ensure_tables(c, 1, 0, 0)) return rc;  // (the long tables are cached with a shape's)
+    const size_t words = n_vecs << log_len;
+    HIPCHK(c->values.ensure(words * 8));
+    HIPCHK(c->lde.ensure(words * 8));
+    HIPCHK(hipMemcpyAsync(c->values.p, data, words * 8, hipMemcpyHostToDevice, c->st));
+    if (int rc = run_ntt(c, c->values.as<gl_t>(), c->lde.as<gl_t>(), n_vecs, (size_t)1 << log_len, log_len, inverse != 0, nullptr, nullptr)) return rc;
+    HIPCHK(hipMemcpyAsync(data, c->values.p, words * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
 // micro-benchmark entry: the trace LDE of `n_cols` synthetic columns (powers of a generator: no constant or unit column, so every
 // column is transformed unless const_per_64 says otherwise), `reps` launches timed with HIP events on the context's stream; average milliseconds per launch
 int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms) {
-    if (log_n < 1 || log_n > 13 || !n_cols) return STARKHIP_ERR_BAD_SHAPE;
+    if (log_n < 1 || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8 || !n_cols) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
     int rc;
     if ((rc = ensure_tables(c, log_n, rate_bits, 0))) return rc;
     const size_t n = (size_t)1 << log_n, N = n << rate_bits;
-    HIPCHK(c->values.ensure(n_cols * n * 8));
+    const bool long_cols = lde_long_supported(log_n);
+    HIPCHK(c->values.ensure(n_cols * n * 8 * (long_cols ? 2 : 1)));  // long columns: + the coefficients the transform keeps, beside the input
     HIPCHK(c->lde.ensure(n_cols * N * 8));
     const gl_t* in = device_values ? (const gl_t*)device_values : c->values.as<gl_t>();  // the caller's own column-major matrix, or the synthetic one
+    gl_t* const cf = long_cols ? c->values.as<gl_t>() + n_cols * n : nullptr;
     if (device_values) const_per_64 = 0;
     else HIPCHK(launch_fill_powers(c->values.as<gl_t>(), 3, GL_GENERATOR, n_cols * n, c->st));
     // `const_per_64` of every 64 columns constant (a FinalExp trace: 11 of 64 take a closed form), in runs of up to 12 as its Fp12 blocks are
@@ -1319,11 +1447,11 @@ int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigne
         if (err == hipSuccess) err = hipEventCreate(&e);
     if (err == hipSuccess && cold && touch) err = hipMemsetAsync(c->lde.p, 0, n_cols * N * 8, c->st);  // every page of the output written once just before
     if (err == hipSuccess && cold && prewarm)  // a few milliseconds of the same arithmetic on a small footprint, then the launch that is timed
-        for (int k = 0; k < 4 && err == hipSuccess; k++) err = run_lde(c, in, nullptr, c->lde.as<gl_t>(), std::min<size_t>(n_cols, 4096), log_n, rate_bits, 0);
-    if (err == hipSuccess) err = cold ? hipStreamSynchronize(c->st) : run_lde(c, in, nullptr, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);  // warm-up
+        for (int k = 0; k < 4 && err == hipSuccess; k++) err = run_lde(c, in, cf, c->lde.as<gl_t>(), std::min<size_t>(n_cols, 4096), log_n, rate_bits, 0);
+    if (err == hipSuccess) err = cold ? hipStreamSynchronize(c->st) : run_lde(c, in, cf, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);  // warm-up
     if (err == hipSuccess) err = hipEventRecord(ev[0], c->st);
     for (unsigned r = 0; r < reps && err == hipSuccess; r++) {
-        err = run_lde(c, in, nullptr, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);
+        err = run_lde(c, in, cf, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);
         if (err == hipSuccess) err = hipEventRecord(ev[r + 1], c->st);
     }
     if (err == hipSuccess) err = hipEventSynchronize(ev[reps]);
@@ -1344,8 +1472,8 @@ int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows
                 uint64_t* violations, uint64_t first[3]) {
     const AirProgram& P = air.prog;
     unsigned log_n = 0;
-    while (((size_t)1 << log_n) < n_rows) log_n++;
-    if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || log_n > 13) return STARKHIP_ERR_BAD_SHAPE;
+    while (log_n < 63 && ((size_t)1 << log_n) < n_rows) log_n++;
+    if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
     for (size_t i = 0; i < P.n_pis; i++)
         if (pis[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     const size_t n = n_rows, C = P.n_cols;
