@@ -135,6 +135,23 @@ pub struct starkhip_pool_verify_stats_t {
     pub arena_bytes: u64,
 }
 
+/// `STARKHIP_CHECK_LIST_MAX`: the most entries `starkhip_check_trace_report` lists.
+pub const STARKHIP_CHECK_LIST_MAX: usize = 1 << 20;
+
+/// `starkhip_check_report_t`: the summary of `starkhip_check_trace_report`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct starkhip_check_report_t {
+    /// (row, constraint) pairs with a nonzero value: `starkhip_check_trace`'s number
+    pub violations: u64,
+    /// constraints with at least one such row
+    pub constraints_violated: u64,
+    /// rows with at least one such constraint
+    pub rows_violated: u64,
+    /// entries written to `list`: min(cap, violations)
+    pub listed: u64,
+}
+
 extern "C" {
     pub fn starkhip_config_standard_fast(cfg: *mut starkhip_config_t);
     pub fn starkhip_config_for_air(air: Air, cfg: *mut starkhip_config_t) -> c_int;
@@ -149,6 +166,15 @@ extern "C" {
     pub fn starkhip_air_register(blob: *const u64, words: usize, name: *const c_char, default_rows: u32, id_out: *mut c_int) -> c_int;
     pub fn starkhip_check_trace(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                 on_device: c_int, public_inputs: *const u64, violations: *mut u64, first: *mut u64) -> c_int;
+    // The full report: per_constraint [starkhip_air_num_constraints(air)] or null, row_mask [(n_rows + 63) / 64] or null (bit r & 63 of
+    // word r >> 6), list cap x {constraint, row, value} (may be null when cap == 0; cap <= STARKHIP_CHECK_LIST_MAX), by constraint, then row.
+    pub fn starkhip_check_trace_report(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                       on_device: c_int, public_inputs: *const u64, per_constraint: *mut u32, row_mask: *mut u64,
+                                       list: *mut u64, cap: usize, out: *mut starkhip_check_report_t) -> c_int;
+    // tests, small shapes: the same host side with the device passes replayed on the CPU; `trace` is host memory
+    pub fn starkhip_check_trace_report_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                              public_inputs: *const u64, per_constraint: *mut u32, row_mask: *mut u64, list: *mut u64,
+                                              cap: usize, out: *mut starkhip_check_report_t) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

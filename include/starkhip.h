@@ -142,6 +142,34 @@ int starkhip_air_register(const uint64_t* blob, size_t words, const char* name, 
  * context's device (csrc/kernels_check.hip); a value is recomputed on the host from the one frame. */
 int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
                          const uint64_t* public_inputs, uint64_t* violations, uint64_t first[3]);
+/* The same check, reported in full: which constraints fail, on which rows, and the values of the first of them.  The rule, trace,
+ * n_rows, n_cols, layout, on_device, public_inputs and the BAD_SHAPE cases are starkhip_check_trace's; cap > STARKHIP_CHECK_LIST_MAX,
+ * a NULL `out`, or a NULL `list` with cap > 0 are BAD_SHAPE too.  One call at a time per context, not beside a prove on it.
+ *   per_constraint[k] (starkhip_air_num_constraints(air) entries, or NULL): the rows on which constraint k is violated;
+ *   row_mask ((n_rows + 63) / 64 words, or NULL): bit (r & 63) of word r >> 6 is set when some constraint is violated on row r;
+ *   list (cap x {constraint, row, value}; may be NULL when cap == 0): the first min(cap, violations) violations in the order
+ *     (constraint ascending, then row ascending), each with the value G * body of that constraint on that row as the device
+ *     computed it (canonical, nonzero).  A cut inside a constraint's rows keeps its lowest rows.  The list is the same on every run.
+ * A satisfying trace gives an all-zero report.  Two passes on the context's device (csrc/kernels_check_report.hip): one counts,
+ * and, when there is something to list, one over the chunks of the listed constraints writes the entries; the host orders them.
+ * starkhip_check_trace itself is unchanged and cheaper: it is the one to ask "does it hold?". */
+#define STARKHIP_CHECK_LIST_MAX (1u << 20)
+typedef struct {
+    uint64_t violations;            /* (row, constraint) pairs with a nonzero value: starkhip_check_trace's number */
+    uint64_t constraints_violated;  /* constraints with at least one such row */
+    uint64_t rows_violated;         /* rows with at least one such constraint */
+    uint64_t listed;                /* entries written to `list`: min(cap, violations) */
+} starkhip_check_report_t;
+int starkhip_check_trace_report(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                                const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
+                                starkhip_check_report_t* out);
+/* tests: starkhip_check_trace_report's host side (argument checks, selection of the listed constraints, ordering, truncation, summary)
+ * with the two device passes replayed by host loops over the program's per-constraint evaluator, which fill each constraint's
+ * entries in a scrambled row order.  `trace` is host memory.  It walks the program on every row, each pass, on one thread --
+ * O(rows x program), times up to a group's length for the constraints late in a group: for small shapes.  No device needed. */
+int starkhip_check_trace_report_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                       const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
+                                       starkhip_check_report_t* out);
 
 /* --- natives + trace generation (host) ----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.

@@ -194,6 +194,49 @@ def air_program(air):
 lib.starkhip_air_check_program.argtypes = [_u64p, C.c_size_t, C.c_char_p, C.c_size_t]
 lib.starkhip_air_register.argtypes = [_u64p, C.c_size_t, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
 lib.starkhip_check_trace.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, _u64p, _u64p]
+CHECK_LIST_MAX = 1 << 20  # STARKHIP_CHECK_LIST_MAX
+
+
+class _CheckReportStruct(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("violations", "constraints_violated", "rows_violated", "listed")]
+
+
+_u32p = C.POINTER(C.c_uint32)
+lib.starkhip_check_trace_report.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, _u32p, _u64p, _u64p,
+                                            C.c_size_t, C.POINTER(_CheckReportStruct)]
+lib.starkhip_check_trace_report_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _u64p, _u32p, _u64p, _u64p, C.c_size_t,
+                                                   C.POINTER(_CheckReportStruct)]
+
+
+class CheckReport:
+    """What starkhip_check_trace_report found.  `violations`: (row, constraint) pairs with a nonzero value (check_trace's number);
+    `constraints_violated`, `rows_violated`; `per_constraint` (np.uint32[K]): rows on which each constraint is violated; `row_mask`
+    (np.uint64[(n + 63) // 64]): bit r & 63 of word r >> 6; `rows`: the violated rows, ascending; `list` (np.uint64[listed, 3]): the
+    first min(cap, violations) violations as (constraint, row, value), by constraint, then row."""
+
+    def __init__(self, summary, per_constraint, row_mask, entries):
+        self.violations, self.constraints_violated, self.rows_violated = (int(summary.violations), int(summary.constraints_violated),
+                                                                          int(summary.rows_violated))
+        self.per_constraint, self.row_mask = per_constraint, row_mask
+        self.rows = np.flatnonzero(np.unpackbits(row_mask.view(np.uint8), bitorder="little"))
+        self.list = entries[:int(summary.listed)].copy()
+
+    def __repr__(self):
+        return (f"CheckReport(violations={self.violations}, constraints_violated={self.constraints_violated}, "
+                f"rows_violated={self.rows_violated}, listed={len(self.list)})")
+
+
+def _check_trace_report(call, air, n_rows, cap):
+    """`call(per_constraint, row_mask, list, cap, summary)` -> rc: one of the two report entry points with its leading arguments bound."""
+    cap = int(cap)
+    if cap < 0:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    per = np.zeros(air_num_constraints(air), dtype=np.uint32)
+    mask = np.zeros((n_rows + 63) // 64, dtype=np.uint64)
+    entries = np.zeros((min(cap, CHECK_LIST_MAX), 3), dtype=np.uint64)  # a larger cap is the library's to refuse
+    summary = _CheckReportStruct()
+    _chk(call(per.ctypes.data_as(_u32p), _p64(mask), _p64(entries) if cap else None, cap, C.byref(summary)))
+    return CheckReport(summary, per, mask, entries)
 
 
 def air_check_program(blob):
@@ -553,6 +596,30 @@ class Prover:
         self.last_call_s = time.perf_counter() - t0
         _chk(rc)
         return bad.value, tuple(int(x) for x in first)
+
+    def check_trace_report(self, air, trace, public_inputs, layout=0, cap=1024):
+        """check_trace in full (starkhip_check_trace_report): a CheckReport with the count of violated rows per constraint, the violated
+        rows and the first `cap` violations (constraint, row, value) by constraint, then row."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        if trace.ndim != 2 or layout not in (0, 1):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+        return self._check_trace_report(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, public_inputs, cap)
+
+    def check_trace_report_device(self, air, trace_ptr, n_rows, public_inputs, layout=1, cap=1024):
+        """check_trace_report on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
+        return self._check_trace_report(air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, public_inputs, cap)
+
+    def _check_trace_report(self, air, trace_arg, n_rows, n_cols, layout, on_device, public_inputs, cap):
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if pis.size != air_public_inputs(air):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        t0 = time.perf_counter()
+        try:
+            return _check_trace_report(lambda *out: lib.starkhip_check_trace_report(self._ctx, air, trace_arg, n_rows, n_cols, layout, on_device,
+                                                                                    _p64(pis), *out), air, n_rows, cap)
+        finally:
+            self.last_call_s = time.perf_counter() - t0
 
     def lde_bench(self, n_cols, log_n, rate_bits, reps=5, const_per_64=0, device_ptr=None, each=False):
         """starkhip_lde_bench: average milliseconds of one values -> LDE launch over `n_cols` synthetic columns."""
@@ -1073,6 +1140,20 @@ def _verify_batch(items, ctx=None, replay=False):
 def verify_batch_replay(items):
     """starkhip_verify_batch_replay (tests): the device verifier's host side with its device part replayed on the CPU."""
     return _verify_batch(items, replay=True)
+
+
+def check_trace_report_replay(air, trace, public_inputs, layout=0, cap=1024):
+    """starkhip_check_trace_report_replay (tests, small shapes): Prover.check_trace_report's host side with the two device passes
+    replayed on the CPU; no device needed."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    if pis.size != air_public_inputs(air):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    return _check_trace_report(lambda *out: lib.starkhip_check_trace_report_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout,
+                                                                                   _p64(pis), *out), air, n_rows, cap)
 
 
 def trace_rows_to_poly_values(trace_rows):

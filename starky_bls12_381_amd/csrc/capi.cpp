@@ -12,6 +12,7 @@
 #include "air_validate.h"
 #include "airs.h"
 #include "blob_arena.h"
+#include "check_report.h"
 #include "kernels.h"
 #include "lde_ranges.h"
 #include "trace_log.h"
@@ -149,6 +150,44 @@ int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, s
     if (!trace || !violations || !first || (a->pis && !public_inputs) || (layout != 0 && layout != 1) || n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;
     try {
         return check_trace((Ctx*)ctx, *a, trace, n_rows, layout, on_device, public_inputs, violations, first);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    } catch (const std::exception&) {
+        return STARKHIP_ERR_BAD_SHAPE;
+    }
+}
+
+// what both report entry points refuse before they look at the trace
+static int check_report_args(const AirInfo* a, const uint64_t* trace, size_t n_cols, int layout, const uint64_t* public_inputs, uint64_t* list,
+                             size_t cap, starkhip_check_report_t* out) {
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    if (!trace || !out || (a->pis && !public_inputs) || (layout != 0 && layout != 1) || n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;
+    if (cap > STARKHIP_CHECK_LIST_MAX || (cap && !list)) return STARKHIP_ERR_BAD_SHAPE;
+    return STARKHIP_OK;
+}
+
+int starkhip_check_trace_report(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                                const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
+                                starkhip_check_report_t* out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    if (int rc = check_report_args(a, trace, n_cols, layout, public_inputs, list, cap, out)) return rc;
+    try {
+        return check_trace_report((Ctx*)ctx, *a, trace, n_rows, layout, on_device, public_inputs, per_constraint, row_mask, list, cap, out);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    } catch (const std::exception&) {
+        return STARKHIP_ERR_BAD_SHAPE;
+    }
+}
+
+int starkhip_check_trace_report_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                       const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
+                                       starkhip_check_report_t* out) {
+    const AirInfo* a = air_get(air);
+    if (int rc = check_report_args(a, trace, n_cols, layout, public_inputs, list, cap, out)) return rc;
+    try {
+        return check_trace_report_replay(*a, trace, n_rows, layout, public_inputs, per_constraint, row_mask, list, cap, out);
     } catch (const std::bad_alloc&) {
         return STARKHIP_ERR_OOM;
     } catch (const std::exception&) {

@@ -1,0 +1,36 @@
+// Host half of starkhip_check_trace_report, the same for the device path (prover.hip: check_trace_report) and for the replay without a
+// device (check_report.cpp: check_trace_report_replay): argument checks, the summary, the selection of the constraints that are
+// listed, the order of the list and its truncation.  What differs is who runs the two passes (kernels_check_report.hip, or host loops).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "airs.h"
+
+namespace starkhip {
+
+// THE rule for trace lengths (prove(), ctx_reserve() and the trace checkers): the built-in AIRs keep the reference's largest trace
+// (8192 rows; their layouts are the reference's), a registered AIR goes up to 2^STARKHIP_MAX_LOG_ROWS.  That bound comes from the quotient kernel's 32-bit byte offsets into one LDE column
+// (kernels_quotient.hip: N * 8 < 2^32 with rate_bits <= 8).
+inline unsigned max_log_rows(const AirInfo& air) { return air.id >= STARKHIP_AIR_CUSTOM_BASE ? (unsigned)STARKHIP_MAX_LOG_ROWS : 13u; }
+
+// What starkhip_check_trace and the report refuse with BAD_SHAPE: rows that are no power of two in 2 .. 2^max_log_rows(air), a public
+// input that is not canonical.  *log_n = log2(n_rows).
+int check_trace_shape(const AirInfo& air, size_t n_rows, const uint64_t* pis, unsigned* log_n);
+
+struct CheckPasses {
+    virtual ~CheckPasses() {}
+    // counts[k] (zeroed, n_constraints entries) = rows on which constraint k is violated; mask (zeroed, (n + 63) / 64 words) = those rows
+    virtual int count(uint32_t* counts, uint64_t* mask) = 0;
+    // entries[3 * (base[k] + i)] = {k, row, value} for the counts[k] violations of every constraint with base[k] != ~0, in any order of
+    // i; `total` entries in all.  `mask` is what count() gave.
+    virtual int list(const uint32_t* base, const uint64_t* mask, size_t total, uint64_t* entries) = 0;
+};
+
+int check_report_run(const AirProgram& P, size_t n_rows, CheckPasses& passes, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list,
+                     size_t cap, starkhip_check_report_t* out);
+
+int check_trace_report_replay(const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, const uint64_t* pis, uint32_t* per_constraint,
+                              uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out);
+
+}  // namespace starkhip

@@ -131,6 +131,15 @@ hipError_t launch_quotient_tiles_combine(const gl_t* partial, unsigned n_chunks,
 // violations, out[1] = min(out[1], (k << 32) | row); the caller presets them to 0 and ~0.
 hipError_t launch_check_trace(const QOp* ops, const uint32_t* chunk_op, const uint32_t* chunk_k0, unsigned n_chunks, const gl_t* trace,
                               const gl_t* pis, unsigned log_n, unsigned long long* out, hipStream_t st);
+// kernels_check_report.hip (starkhip_check_trace_report), over the same op stream.  Count: counts[k] += rows on which constraint k is
+// violated, row_mask[r >> 6] |= 1 << (r & 63) for every row with a violation; both preset to 0.  List: over chunks[0 .. n_launched),
+// the violations of the constraints with base[k] != ~0 as {k, row, value} at list[base[k] + (a slot from cursors[k], preset to 0)];
+// slots at or past list_len are not written.
+hipError_t launch_check_report_count(const QOp* ops, const uint32_t* chunk_op, const uint32_t* chunk_k0, unsigned n_chunks, const gl_t* trace,
+                                     const gl_t* pis, unsigned log_n, uint32_t* counts, unsigned long long* row_mask, hipStream_t st);
+hipError_t launch_check_report_list(const QOp* ops, const uint32_t* chunk_op, const uint32_t* chunk_k0, const uint32_t* chunks, unsigned n_launched,
+                                    const gl_t* trace, const gl_t* pis, unsigned log_n, uint32_t* cursors, const unsigned long long* row_mask,
+                                    const uint32_t* base, unsigned long long* list, uint32_t list_len, hipStream_t st);
 
 // kernels_fri.hip
 hipError_t launch_ext_powers(gl2_t* out, gl2_t base, size_t count, hipStream_t st);

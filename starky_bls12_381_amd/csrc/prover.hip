@@ -23,6 +23,7 @@
 #include "air_validate.h"
 #include "airs.h"
 #include "blob_arena.h"
+#include "check_report.h"
 #include "kernels.h"
 #include "lde_ranges.h"
 #include "trace_log.h"
@@ -172,7 +173,8 @@ struct Ctx {
     // first ops and constraints, the results
     int chk_air = -1;
     unsigned chk_want = 0, chk_chunks = 0;
-    DevBuf d_chk_ops, d_chk_meta, d_chk_out;
+    std::vector<uint32_t> chk_k0;  // [chk_chunks + 1] the chunks' first constraints on the host, then n_constraints
+    DevBuf d_chk_ops, d_chk_meta, d_chk_out, d_chk_rep, d_chk_list;  // the last two: starkhip_check_trace_report's (check_trace_report)
     // work buffers of a proof: work_buffers() below is the one table of their sizes (prove() and ctx_reserve() allocate from it)
     // `lde` is the one big buffer (19.3 GB for FinalExp).  Before the LDE kernel writes it, it holds everything that waits for that
     // kernel: the trace columns as its LAST quarter (the LDE goes out in launches that overwrite only columns already transformed:
@@ -187,7 +189,7 @@ struct Ctx {
         pow_best, qidx, gather_t;
     // every device buffer the context holds, cached tables and plans included: what ctx_destroy releases and ctx_device_bytes adds up
     std::vector<DevBuf*> dev_bufs() {
-        std::vector<DevBuf*> v = {&d_ops, &d_loads, &d_chunk_off, &d_chk_ops, &d_chk_meta, &d_chk_out, &staging, &values, &lde, &digests, &pis,
+        std::vector<DevBuf*> v = {&d_ops, &d_loads, &d_chunk_off, &d_chk_ops, &d_chk_meta, &d_chk_out, &d_chk_rep, &d_chk_list, &staging, &values, &lde, &digests, &pis,
                                   &apow, &chunk_scale, &partial, &qvals, &qcoef, &qlde, &qdigests, &zpow, &gzpow, &open_local, &open_next, &open_q,
                                   &ext_apow, &comb_partial, &comb_out, &fri_coef, &fri_vals, &scale_tab, &pow_state, &pow_best, &qidx, &gather_t};
         for (DevBuf& b : fri_rows) v.push_back(&b);
@@ -669,11 +671,6 @@ static hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_
     if (*form == 1) return launch_leaf_hash_row(lde, n_cols, log_n, rate, digests, st);
     return launch_leaf_hash(lde, n_cols, log_n, rate, digests, st);
 }
-
-// THE rule for trace lengths: the built-in AIRs keep the reference's largest trace (8192 rows; their layouts are the reference's), a
-// registered AIR goes up to 2^STARKHIP_MAX_LOG_ROWS.  That bound comes from the quotient kernel's 32-bit byte offsets into one LDE column
-// (kernels_quotient.hip: N * 8 < 2^32 with rate_bits <= 8).
-static unsigned max_log_rows(const AirInfo& air) { return air.id >= STARKHIP_AIR_CUSTOM_BASE ? (unsigned)STARKHIP_MAX_LOG_ROWS : 13u; }
 
 // The dimensions of one proof, derived in one place: prove() and ctx_reserve() size and lay out everything from these.
 struct ProofShape {
@@ -1468,14 +1465,14 @@ int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigne
 // kernel-level test entry: a recorded trace through expand_trace_kernel + zero_cells_kernel, handed back column-major [C][rows]
 // starkhip_check_trace.  The trace goes where prove() would put it -- column-major in `values`, or the caller's own device memory --
 // with the LDE buffer as the upload staging of row-major host rows.  The op stream is cached per context like the quotient's.
-int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                uint64_t* violations, uint64_t first[3]) {
+// What both checkers do before their kernels: the shape checks, the op stream of `air` (cached), the trace on the device (*d_trace)
+// and the public inputs in c->pis.
+static int check_trace_prepare(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
+                               unsigned* log_n_out, const gl_t** d_trace) {
     const AirProgram& P = air.prog;
     unsigned log_n = 0;
-    while (log_n < 63 && ((size_t)1 << log_n) < n_rows) log_n++;
-    if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
-    for (size_t i = 0; i < P.n_pis; i++)
-        if (pis[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    if (int rc = check_trace_shape(air, n_rows, pis, &log_n)) return rc;
+    *log_n_out = log_n;
     const size_t n = n_rows, C = P.n_cols;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->st;
@@ -1494,17 +1491,29 @@ int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows
         HIPCHK(hipMemcpyAsync(c->d_chk_ops.p, Q.ops.data(), Q.ops.size() * sizeof(QOp), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(c->d_chk_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(stream_wait(c));  // Q and meta go out of scope
+        c->chk_k0.assign(meta.begin() + nc + 1, meta.end());
+        c->chk_k0.push_back(P.n_constraints);
         c->chk_air = air.id;
         c->chk_want = want;
         c->chk_chunks = (unsigned)nc;
     }
-    const unsigned nc = c->chk_chunks;
-    const gl_t* d_trace;
     if (!(on_device && layout == 1)) HIPCHK(c->values.ensure(C * n * 8));
     if (!on_device && layout != 1) HIPCHK(c->lde.ensure(C * n * 8));  // the staging of row-major host rows
-    if (int rc = upload_dense(c, trace, layout, on_device, n, C, c->values.as<gl_t>(), &d_trace)) return rc;
+    if (int rc = upload_dense(c, trace, layout, on_device, n, C, c->values.as<gl_t>(), d_trace)) return rc;
     HIPCHK(c->pis.ensure(std::max<size_t>(1, P.n_pis) * 8));
     if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, st));
+    return STARKHIP_OK;
+}
+
+int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
+                uint64_t* violations, uint64_t first[3]) {
+    const AirProgram& P = air.prog;
+    unsigned log_n = 0;
+    const gl_t* d_trace = nullptr;
+    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &log_n, &d_trace)) return rc;
+    const size_t n = n_rows, C = P.n_cols;
+    hipStream_t st = c->st;
+    const unsigned nc = c->chk_chunks;
     const unsigned long long init[2] = {0, ~0ull};
     unsigned long long res[2];
     HIPCHK(c->d_chk_out.ensure(sizeof init));
@@ -1527,6 +1536,71 @@ int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows
     first[1] = r;
     first[2] = air_constraint_value(P, k, frame.data(), frame.data() + C, pis);
     return STARKHIP_OK;
+}
+
+// starkhip_check_trace_report: the two passes of kernels_check_report.hip under the host half of check_report.h.  d_chk_rep holds
+// counts[K] (the cursors of the second pass), row_mask[W], base[K] and the launched chunks[nc]; d_chk_list the entries.
+namespace {
+struct DevicePasses : CheckPasses {
+    Ctx* c;
+    const AirProgram& P;
+    const gl_t* d_trace;
+    unsigned log_n;
+    size_t K, W, off_mask, off_base, off_chunks;
+    DevicePasses(Ctx* c_, const AirProgram& P_, const gl_t* t, unsigned log_n_) : c(c_), P(P_), d_trace(t), log_n(log_n_) {
+        K = P.n_constraints;
+        W = (((size_t)1 << log_n) + 63) / 64;
+        off_mask = (K * 4 + 7) / 8 * 8;
+        off_base = off_mask + W * 8;
+        off_chunks = off_base + K * 4;
+    }
+    uint32_t* d_counts() const { return c->d_chk_rep.as<uint32_t>(); }
+    unsigned long long* d_mask() const { return (unsigned long long*)((char*)c->d_chk_rep.p + off_mask); }
+    int count(uint32_t* counts, uint64_t* mask) override {
+        const unsigned nc = c->chk_chunks;
+        HIPCHK(c->d_chk_rep.ensure(off_chunks + (size_t)nc * 4));
+        HIPCHK(hipMemsetAsync(c->d_chk_rep.p, 0, off_base, c->st));
+        const uint32_t* meta = c->d_chk_meta.as<uint32_t>();
+        HIPCHK(launch_check_report_count(c->d_chk_ops.as<QOp>(), meta, meta + nc + 1, nc, d_trace, c->pis.as<gl_t>(), log_n, d_counts(), d_mask(), c->st));
+        HIPCHK(hipMemcpyAsync(mask, d_mask(), W * 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipMemcpyAsync(counts, d_counts(), K * 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(stream_wait(c));
+        return STARKHIP_OK;
+    }
+    int list(const uint32_t* base, const uint64_t*, size_t total, uint64_t* entries) override {
+        const unsigned nc = c->chk_chunks;
+        std::vector<uint32_t> chunks;  // those with a listed constraint
+        for (unsigned j = 0; j < nc; j++)
+            for (uint32_t k = c->chk_k0[j]; k < c->chk_k0[j + 1]; k++)
+                if (base[k] != ~0u) {
+                    chunks.push_back(j);
+                    break;
+                }
+        if (chunks.empty() || total > 0xFFFFFFFFull / 2) return STARKHIP_ERR_HIP;
+        HIPCHK(c->d_chk_list.ensure(total * 24));
+        char* rep = (char*)c->d_chk_rep.p;
+        HIPCHK(hipMemsetAsync(rep, 0, K * 4, c->st));  // the counts become the cursors
+        HIPCHK(hipMemcpyAsync(rep + off_base, base, K * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(rep + off_chunks, chunks.data(), chunks.size() * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemsetAsync(c->d_chk_list.p, 0xFF, total * 24, c->st));  // an entry nobody wrote fails the host's check of its segment
+        const uint32_t* meta = c->d_chk_meta.as<uint32_t>();
+        HIPCHK(launch_check_report_list(c->d_chk_ops.as<QOp>(), meta, meta + nc + 1, (const uint32_t*)(rep + off_chunks), (unsigned)chunks.size(), d_trace,
+                                        c->pis.as<gl_t>(), log_n, d_counts(), d_mask(), (const uint32_t*)(rep + off_base),
+                                        c->d_chk_list.as<unsigned long long>(), (uint32_t)total, c->st));
+        HIPCHK(hipMemcpyAsync(entries, c->d_chk_list.p, total * 24, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(stream_wait(c));  // `chunks` goes out of scope
+        return STARKHIP_OK;
+    }
+};
+}  // namespace
+
+int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
+                       uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out) {
+    unsigned log_n = 0;
+    const gl_t* d_trace = nullptr;
+    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &log_n, &d_trace)) return rc;
+    DevicePasses passes(c, air.prog, d_trace, log_n);
+    return check_report_run(air.prog, n_rows, passes, per_constraint, row_mask, list, cap, out);
 }
 
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor) {

@@ -1,6 +1,10 @@
 """Times starkhip_check_trace on a real FinalExp trace (8192 rows x 73 527 columns, 360 800 constraints) -- from host rows, and
 from column-major device memory (no upload: the kernel plus a few small copies) -- against oracle_check_trace on the host's CPUs,
-and the proof time of one mid-sized random AIR (300 columns, 4096 rows).  Prints one JSON line."""
+and the proof time of one mid-sized random AIR (300 columns, 4096 rows).  Prints one JSON line.
+
+--report: times starkhip_check_trace_report instead, on the same trace in column-major device memory: the plain check (for the ratio),
+the report on the clean trace (its first pass alone) and the report with cap = 1024 after every cell of row 4000 was raised by one
+(both passes).  Best and median of five after a warm-up call; one JSON line."""
 import ctypes as C
 import json
 import os
@@ -28,7 +32,43 @@ def best(f, reps):
     return min(ts) * 1e3, sorted(ts)[len(ts) // 2] * 1e3, out
 
 
+def report_mode():
+    torch.cuda.set_device(0)
+    out = {}
+    pv = S.Prover(0)
+    air = S.AIR_FINAL_EXP
+    t, pis = S.trace_final_exp(fp_arr(*[int(s) for s in native_vectors()["final_exp_input_aa"]]))
+    n = t.shape[0]
+    cols = torch.from_numpy(np.ascontiguousarray(t.T).view(np.int64)).to("cuda:0")
+    del t
+    torch.cuda.synchronize()
+    pv.check_trace_device(air, cols.data_ptr(), n, pis, layout=1)  # warm-up: op stream, buffers
+    mn, md, r = best(lambda: pv.check_trace_device(air, cols.data_ptr(), n, pis, layout=1), 5)
+    out["check_trace_clean_ms"] = {"min": mn, "median": md}
+    assert r[0] == 0, r
+    pv.check_trace_report_device(air, cols.data_ptr(), n, pis, layout=1)
+    mn, md, rep = best(lambda: pv.check_trace_report_device(air, cols.data_ptr(), n, pis, layout=1), 5)
+    out["report_clean_ms"] = {"min": mn, "median": md}
+    assert rep.violations == 0 and len(rep.list) == 0, rep
+    out["report_clean_over_check_trace"] = out["report_clean_ms"]["min"] / out["check_trace_clean_ms"]["min"]
+    p_minus_1 = int(np.array([S.P - 1], dtype=np.uint64).view(np.int64)[0])
+    row = cols[:, 4000]
+    cols[:, 4000] = torch.where(row == p_minus_1, torch.zeros_like(row), row + 1)  # as test_check_trace_on_a_final_exp_trace corrupts it
+    torch.cuda.synchronize()
+    plain = pv.check_trace_device(air, cols.data_ptr(), n, pis, layout=1)
+    pv.check_trace_report_device(air, cols.data_ptr(), n, pis, layout=1, cap=1024)
+    mn, md, rep = best(lambda: pv.check_trace_report_device(air, cols.data_ptr(), n, pis, layout=1, cap=1024), 5)
+    out["report_row_4000_corrupted_cap_1024_ms"] = {"min": mn, "median": md}
+    assert rep.violations == plain[0] > 0 and tuple(int(x) for x in rep.list[0]) == plain[1], (rep, plain)
+    out["row_4000_corrupted"] = {"violations": rep.violations, "constraints_violated": rep.constraints_violated, "rows_violated": rep.rows_violated,
+                                 "rows": rep.rows.tolist()[:16], "listed": len(rep.list)}
+    pv.close()
+    print(json.dumps(out))
+
+
 def main():
+    if "--report" in sys.argv[1:]:
+        return report_mode()
     torch.cuda.set_device(0)
     out = {}
     pv = S.Prover(0)
