@@ -10,8 +10,7 @@ namespace starkhip {
 
 int check_trace_shape(const AirInfo& air, size_t n_rows, const uint64_t* pis, unsigned* log_n_out) {
     unsigned log_n = 0;
-    while (log_n < 63 && ((size_t)1 << log_n) < n_rows) log_n++;
-    if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
+    if (!log2_rows(n_rows, &log_n) || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
     for (size_t i = 0; i < air.prog.n_pis; i++)
         if (pis[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     *log_n_out = log_n;

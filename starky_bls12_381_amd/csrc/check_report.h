@@ -1,4 +1,4 @@
-// Host half of starkhip_check_trace_report, the same for the device path (prover.hip: check_trace_report) and for the replay without a
+// Host half of starkhip_check_trace_report, the same for the device path (check_trace.hip: check_trace_report) and for the replay without a
 // device (check_report.cpp: check_trace_report_replay): argument checks, the summary, the selection of the constraints that are
 // listed, the order of the list and its truncation.  What differs is who runs the two passes (kernels_check_report.hip, or host loops).
 #pragma once
@@ -13,6 +13,13 @@ namespace starkhip {
 // (8192 rows; their layouts are the reference's), a registered AIR goes up to 2^STARKHIP_MAX_LOG_ROWS.  That bound comes from the quotient kernel's 32-bit byte offsets into one LDE column
 // (kernels_quotient.hip: N * 8 < 2^32 with rate_bits <= 8).
 inline unsigned max_log_rows(const AirInfo& air) { return air.id >= STARKHIP_AIR_CUSTOM_BASE ? (unsigned)STARKHIP_MAX_LOG_ROWS : 13u; }
+// ... and for log2(rows): true and *log_n = log2(n_rows) for a power of two from 2 on, false for every other count
+inline bool log2_rows(size_t n_rows, unsigned* log_n) {
+    unsigned l = 0;
+    while (l < 63 && ((size_t)1 << l) < n_rows) l++;
+    *log_n = l;
+    return n_rows >= 2 && ((size_t)1 << l) == n_rows;
+}
 
 // What starkhip_check_trace and the report refuse with BAD_SHAPE: rows that are no power of two in 2 .. 2^max_log_rows(air), a public
 // input that is not canonical.  *log_n = log2(n_rows).

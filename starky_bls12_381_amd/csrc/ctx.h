@@ -1,0 +1,212 @@
+// The prover context and what the host files around it share: Ctx and its device buffers (DevBuf), the error macro of every HIP call
+// (HIPCHK), and the declarations of ctx.hip -- the sleeping wait and the read-back arena, the per-shape table cache, the per-AIR plan and
+// op-stream program caches, the transform dispatch and the uploads that proof, trace checkers and test entries have in common.
+// Internal to the .hip files that define prover.h's functions (ctx.hip, prover.hip, check_trace.hip, kernel_entries.hip): prover.h stays
+// the opaque interface for capi.cpp, the pools and the verifier.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <stdio.h>
+
+#include <memory>
+#include <set>
+#include <system_error>
+#include <thread>
+#include <vector>
+
+#include "airs.h"
+#include "kernels.h"
+#include "prover.h"
+#include "scheduler.h"
+#include "trace_log.h"
+
+namespace starkhip {
+
+#define HIPCHK(expr)                                                                                       \
+    do {                                                                                                   \
+        hipError_t _e = (expr);                                                                            \
+        if (_e != hipSuccess) {                                                                            \
+            fprintf(stderr, "starkhip: HIP error %s at %s:%d (%s)\n", hipGetErrorString(_e), __FILE__, __LINE__, #expr); \
+            (void)hipDeviceSynchronize(); /* pending async copies target host buffers that are about to go out of scope */ \
+            return _e == hipErrorOutOfMemory ? STARKHIP_ERR_OOM : STARKHIP_ERR_HIP;                        \
+        }                                                                                                  \
+    } while (0)
+
+struct DevBuf {  // device memory that goes with its owner (a Ctx, or cached tables / a plan that were never finished); not copied anywhere
+    void* p = nullptr;
+    size_t cap = 0;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    template <class T>
+    T* as() const { return (T*)p; }
+};
+
+struct Ctx {
+    int device = 0;
+    hipStream_t st = nullptr;       // the stream of the current proof: st_normal, or st_high for a proof the pool marks urgent
+    hipStream_t st_normal = nullptr, st_high = nullptr;
+    hipEvent_t ev[STARKHIP_N_PHASES + 1] = {};
+    float timings[STARKHIP_N_PHASES] = {0};
+    hipEvent_t kev[6] = {};       // the three heavy kernels bracketed on their own: leaf hash, quotient evaluation, trace LDE
+    float ktimings[3] = {0};      // lde_columns, leaf_hash (trace), quotient_eval
+    float htimings[2] = {0};      // host time inside the last prove: Fiat-Shamir hashing (the challenger's sequential sponge), other host arithmetic
+    HashService* hs = nullptr;    // a pooled context's trace commitments are launched by the pool's scheduler (scheduler.h)
+    hipEvent_t hash_ready = nullptr, hash_done = nullptr;
+    HashService::Timing hash_timing;  // pooled: the commitment kernel's own start / stop on ITS launch stream, its form and group
+    hipEvent_t wait_ev = nullptr;  // hipEventBlockingSync: see stream_wait()
+    // Read-backs (caps, openings, FRI batches, the nonce) land in a page-locked arena and are copied to where prove() wants them when the
+    // host next waits for the stream (read_back() / stream_wait()): hipMemcpyAsync into PAGEABLE memory does not return until the copy has
+    // run, and the runtime waits for it spinning -- every context thread of a pool burned a CPU for as long as its proof's kernels ran
+    // (0.84 CPU-seconds per FinalExp proof with eight in flight against 0.27 with the arena; bench.py: host.cpu_seconds_per_proof_by_role).
+    void* rb = nullptr;
+    size_t rb_cap = 0, rb_used = 0;
+    struct Pending { void* dst; const void* src; size_t bytes; };
+    std::vector<Pending> rb_pending;
+    void* host_staging = nullptr;  // page-locked: a recording's parts gathered for one upload (prove(), layout 2); scattered columns (layout 3)
+    size_t host_staging_cap = 0;
+    hipEvent_t col_ev[2] = {nullptr, nullptr};  // layout 3: the two halves of host_staging, each free again when its copy has run
+    std::set<int> blob_airs;  // AIRs this context has reserved page-locked proof blobs for (blob_arena.h)
+    bool hash_requested = false;
+    bool urgent = false;  // ctx_set_urgent
+    // tuning (starkhip_set_option; defaults are the measured best)
+    long opt_quotient_impl = 0;   // 0: tiled evaluator (quotient_plan.h), 1: op-stream interpreter (quotient_ops.h)
+    long opt_quotient_waves = 65536, opt_quotient_slots = 0, opt_quotient_chunks = 0, opt_quotient_debug = 0, opt_zeta_on_coset = 0;
+    // Shape-dependent tables and the per-AIR constraint plan are CACHED per context: a pooled context that alternates between
+    // AIRs (a PairingPrecomp proof, then an FP12Mul one) finds both again instead of rebuilding the plan on the host and
+    // re-allocating device buffers -- hipFree synchronises the whole device, i.e. waits for every other proof's kernels.
+    struct Tables {
+        int log_n = -1, rate = -1, qdb = -1;
+        DevBuf tw_fwd, tw_inv, coset_scale, qtab, qshift_inv;
+        DevBuf lde2_fwd, lde2_inv, lde2_cs, lde2_oh;  // kernels_lde.hip tables (log_n >= 8)
+        DevBuf lde_wave;                               // ... and of its wave-resident kernel (log_n == 13)
+        // kernels_lde_long.hip (log_n >= 14, and the proof's other vectors of 2^16 .. 2^20 words): the coset powers (7 w_N^s)^j, the
+        // sub-transforms' twiddles, and the inter-pass twiddles of every length this shape has transformed (ensure_long_tw)
+        DevBuf long_cs, long_sub;
+        struct LongTw { unsigned log_len; DevBuf fwd, inv; };
+        std::vector<std::unique_ptr<LongTw>> long_tw;
+        std::vector<DevBuf*> bufs() {
+            std::vector<DevBuf*> v = {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave, &long_cs, &long_sub};
+            for (auto& t : long_tw) {
+                v.push_back(&t->fwd);
+                v.push_back(&t->inv);
+            }
+            return v;
+        }
+    };
+    struct PlanDev {  // tiled plan (quotient_plan.h) of one AIR on the device
+        int air = -1;
+        unsigned chunks = 0, want = 0;
+        uint32_t recs = 0;
+        DevBuf q_recs, q_streams, q_chunk_tile_off, q_tile_list, q_contrib_off, q_contribs, q_consts, q_apow;
+        std::vector<DevBuf*> bufs() { return {&q_recs, &q_streams, &q_chunk_tile_off, &q_tile_list, &q_contrib_off, &q_contribs, &q_consts, &q_apow}; }
+    };
+    std::vector<std::unique_ptr<Tables>> table_cache;
+    std::vector<std::unique_ptr<PlanDev>> plan_cache;
+    Tables* tab = nullptr;    // the current shape's (ensure_tables)
+    PlanDev* plan = nullptr;  // the current AIR's (ensure_plan)
+    long opt_leaf_hash_form = 0;     // 0: a lone context's commitments: row form for <= 4096 leaves, pair form for >= 32 768, quad form between; 1: quad always; 2: row always; 3: lane always; 4: pair always
+    long opt_lde_impl = 0;           // 0: 8192-row traces take lde_columns_wave_kernel; 1: lde_columns_v2_kernel for every shape (the cross-check)
+    long opt_lde_closed_forms = 1;   // constant / unit-vector columns skip their transforms (kernels_lde.hip); 0: every column is transformed
+    long opt_host_commit_leaves = 64; // trace commitments of at most this many leaves (and >= 64 columns) are hashed by host threads (0: never)
+    long opt_verify_chunk_mb = 1024;  // device memory one chunk of starkhip_verify_batch may take (verifier_device.cpp)
+    double verify_timings[4] = {0};   // the last starkhip_verify_batch: host prelude ms, upload ms, device ms, host CPU seconds
+    std::vector<gl_t> host_lde;      // their LDE on the host
+    // op-stream program (quotient_impl = 1; kept as the cross-check)
+    struct OpProgram {
+        int air = -1;
+        unsigned chunks = 0, slots = 0;
+        DevBuf ops, loads, chunk_off;  // compile_quotient_ops() + attach_cell_cache() output for `air`
+        std::vector<uint32_t> chunk_k_after;
+        std::vector<DevBuf*> bufs() { return {&ops, &loads, &chunk_off}; }
+    } prog;
+    // trace checker (starkhip_check_trace): the op stream of `air` cut for `want` chunks (`chunks` of them came out), the chunks'
+    // first ops and constraints, the results
+    struct CheckProgram {
+        int air = -1;
+        unsigned want = 0, chunks = 0;
+        std::vector<uint32_t> k0;  // [chunks + 1] the chunks' first constraints on the host, then n_constraints
+        DevBuf ops, meta, out, rep, list;  // the last two: starkhip_check_trace_report's (check_trace_report)
+        std::vector<DevBuf*> bufs() { return {&ops, &meta, &out, &rep, &list}; }
+    } chk;
+    // work buffers of a proof: work_buffers() in prover.hip is the one table of their sizes (prove() and ctx_reserve() allocate from it)
+    // `lde` is the one big buffer (19.3 GB for FinalExp).  Before the LDE kernel writes it, it holds everything that waits for that
+    // kernel: the trace columns as its LAST quarter (the LDE goes out in launches that overwrite only columns already transformed:
+    // run_lde_trace) and, at its start, the upload staging (row-major rows before the transpose, a recording's words before the
+    // expansion).  Coefficients are the LDE kernel's scratch inside a column's own block and are not kept: openings and the FRI
+    // combination read coset 0 of the LDE (kernels_fri.hip).  `values` is the 1/64 of the columns the last LDE launch reads (75 MB), a
+    // whole trace only for rate_bits == 0, and starkhip_lde_batch's in-place values / coefficients.  Together 19.6 GB per FinalExp
+    // context; rounds 1-3: values + coefficients + staging + LDE = 33.7 GB.  `staging` serves the kernel-level test entries
+    // (expand_log, permute_batch, field_ops) alone.
+    DevBuf staging, values, lde, digests, pis, apow, chunk_scale, partial, qvals, qcoef, qlde, qdigests, zpow, gzpow, open_local,
+        open_next, open_q, ext_apow, comb_partial, comb_out, fri_coef, fri_vals, fri_rows[16], fri_digests[16], scale_tab, pow_state,
+        pow_best, qidx, gather_t;
+    // every device buffer the context holds, cached tables and plans included: what ctx_destroy releases and ctx_device_bytes adds up
+    std::vector<DevBuf*> dev_bufs() {
+        std::vector<DevBuf*> v = {&staging, &values, &lde, &digests, &pis,
+                                  &apow, &chunk_scale, &partial, &qvals, &qcoef, &qlde, &qdigests, &zpow, &gzpow, &open_local, &open_next, &open_q,
+                                  &ext_apow, &comb_partial, &comb_out, &fri_coef, &fri_vals, &scale_tab, &pow_state, &pow_best, &qidx, &gather_t};
+        for (DevBuf& b : fri_rows) v.push_back(&b);
+        for (DevBuf& b : fri_digests) v.push_back(&b);
+        for (DevBuf* b : prog.bufs()) v.push_back(b);
+        for (DevBuf* b : chk.bufs()) v.push_back(b);
+        for (auto& t : table_cache)
+            for (DevBuf* b : t->bufs()) v.push_back(b);
+        for (auto& d : plan_cache)
+            for (DevBuf* b : d->bufs()) v.push_back(b);
+        return v;
+    }
+};
+
+// ---- ctx.hip
+hipError_t stream_wait(Ctx* c);
+hipError_t read_back(Ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st);
+hipError_t ensure_host_staging(Ctx* c, size_t need, size_t grow_to);
+int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb);
+bool long_vector(unsigned log_len);
+int ensure_long_tw(Ctx* c, unsigned log_len, LdeLongTables* out);
+int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points);
+int ensure_program(Ctx* c, const AirInfo& air, size_t quotient_points);
+hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs);
+int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,
+            const gl_t* post_scale);
+int upload_dense(Ctx* c, const uint64_t* trace, int layout, int on_device, size_t n, size_t C, gl_t* dst, const gl_t** d_values);
+hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form);
+
+// digest buffer: level 0 (n_leaves nodes) followed by level 1, ... ; offset of level l in nodes
+static inline size_t level_off(size_t n_leaves, unsigned l) { return 2 * n_leaves - (2 * n_leaves >> l); }
+static inline size_t digest_words(size_t n_leaves) { return 8 * n_leaves; }
+
+// fn(0) .. fn(n_threads - 1) side by side: fn(0) on the calling thread, the others on helper threads created for this call; where no
+// thread is to be had the calling thread does that share too
+template <class F>
+static void run_on_helpers(unsigned n_threads, const F& fn) {
+    std::vector<std::thread> helpers;
+    for (unsigned w = 1; w < n_threads; w++) {
+        try {
+            helpers.emplace_back(fn, w);
+        } catch (const std::system_error&) {
+            fn(w);
+        }
+    }
+    fn(0);
+    for (std::thread& t : helpers) t.join();
+}
+
+// Where a recording lands in the ONE array of 32-bit words that expand_trace_kernel / zero_cells_kernel read.  A log recorded by several
+// threads comes in parts (trace_log.h): each part's words land at its base, then the parts' offsets (already shifted by that base) back
+// to back, then their late zeros.
+struct LogPiece { size_t at; const uint32_t* src; size_t words; };
+std::vector<LogPiece> recording_pieces(const TraceLog& log);
+
+}  // namespace starkhip

@@ -117,7 +117,7 @@ int host_alloc(Ctx*, size_t, void**) { return STARKHIP_ERR_NO_DEVICE; }
 void host_free(void*) {}
 int quad_merged_tables_selfcheck(unsigned) { return 0; }  // the real one is compiled with the HIP sources
 
-hipError_t event_wait_sleeping(hipEvent_t) { return hipSuccess; }  // prover.hip's sleeping wait: the fake device is always done
+hipError_t event_wait_sleeping(hipEvent_t) { return hipSuccess; }  // ctx.hip's sleeping wait: the fake device is always done
 
 // the two launches the commitment scheduler makes
 static std::atomic<unsigned long> g_fake_launches(0), g_fake_merged(0);

@@ -1,0 +1,208 @@
+// Kernel-level entry points: single kernels, or a transform as prove() dispatches it, on data of the caller's.  NOT on the proving
+// path -- only the tests and the micro-benchmarks call them (starkhip_lde_batch, starkhip_ntt_long, starkhip_lde_bench,
+// starkhip_expand_log, starkhip_merkle_cap, starkhip_permute_batch(_form), starkhip_field_ops, starkhip_host_alloc / _free).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ctx.h"
+
+namespace starkhip {
+
+int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out) {
+    if (log_n < 1 || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_tables(c, log_n, rate_bits, 0))) return rc;
+    const size_t n = (size_t)1 << log_n, N = n << rate_bits;
+    HIPCHK(c->values.ensure(n_cols * n * 8));
+    HIPCHK(c->lde.ensure(n_cols * N * 8));
+    HIPCHK(hipMemcpyAsync(c->values.p, values, n_cols * n * 8, hipMemcpyHostToDevice, c->st));
+    // the LDE comes from the kernel prove() uses for this shape: for 8192 rows the wave-resident one, which keeps no coefficients --
+    // those, when asked for, come from the other kernel afterwards (in place of the values, which the first run leaves untouched)
+    const bool wave = lde_wave_supported(log_n) && c->opt_lde_impl == 0;
+    std::vector<gl_t> tmp;
+    if (wave) {
+        HIPCHK(run_lde(c, c->values.as<gl_t>(), nullptr, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0));
+        if (lde_out) {
+            tmp.resize(n_cols * N);
+            HIPCHK(hipMemcpyAsync(tmp.data(), c->lde.p, n_cols * N * 8, hipMemcpyDeviceToHost, c->st));
+            HIPCHK(stream_wait(c));
+        }
+    }
+    if (!wave || coeffs_out) HIPCHK(run_lde(c, c->values.as<gl_t>(), c->values.as<gl_t>(), c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0));
+    if (coeffs_out) HIPCHK(hipMemcpyAsync(coeffs_out, c->values.p, n_cols * n * 8, hipMemcpyDeviceToHost, c->st));  // in place
+    HIPCHK(stream_wait(c));
+    if (lde_out) {
+        // device layout is coset-major; hand back NATURAL point order i = k * R + s
+        if (!wave) {
+            tmp.resize(n_cols * N);
+            HIPCHK(hipMemcpy(tmp.data(), c->lde.p, n_cols * N * 8, hipMemcpyDeviceToHost));
+        }
+        const size_t R = (size_t)1 << rate_bits;
+        for (size_t col = 0; col < n_cols; col++)
+            for (size_t s = 0; s < R; s++)
+                for (size_t k = 0; k < n; k++) lde_out[col * N + k * R + s] = tmp[col * N + s * n + k];
+    }
+    return STARKHIP_OK;
+}
+
+// kernel-level test entry: n_vecs vectors of 2^log_len words (2^16 .. 2^26) through the multi-workgroup transform as prove() runs it on
+// the quotient's values and the FRI layers -- in place, forward or inverse (with 2^-log_len)
+int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse) {
+    if (!long_vector(log_len) || !n_vecs || !data) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = ensure_tables(c, 1, 0, 0)) return rc;  // (the long tables are cached with a shape's)
+    const size_t words = n_vecs << log_len;
+    HIPCHK(c->values.ensure(words * 8));
+    HIPCHK(c->lde.ensure(words * 8));
+    HIPCHK(hipMemcpyAsync(c->values.p, data, words * 8, hipMemcpyHostToDevice, c->st));
+    if (int rc = run_ntt(c, c->values.as<gl_t>(), c->lde.as<gl_t>(), n_vecs, (size_t)1 << log_len, log_len, inverse != 0, nullptr, nullptr)) return rc;
+    HIPCHK(hipMemcpyAsync(data, c->values.p, words * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+// micro-benchmark entry: the trace LDE of `n_cols` synthetic columns (powers of a generator: no constant or unit column, so every
+// column is transformed unless const_per_64 says otherwise), `reps` launches timed with HIP events on the context's stream; average milliseconds per launch
+int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms) {
+    if (log_n < 1 || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8 || !n_cols) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure_tables(c, log_n, rate_bits, 0))) return rc;
+    const size_t n = (size_t)1 << log_n, N = n << rate_bits;
+    const bool long_cols = lde_long_supported(log_n);
+    HIPCHK(c->values.ensure(n_cols * n * 8 * (long_cols ? 2 : 1)));  // long columns: + the coefficients the transform keeps, beside the input
+    HIPCHK(c->lde.ensure(n_cols * N * 8));
+    const gl_t* in = device_values ? (const gl_t*)device_values : c->values.as<gl_t>();  // the caller's own column-major matrix, or the synthetic one
+    gl_t* const cf = long_cols ? c->values.as<gl_t>() + n_cols * n : nullptr;
+    if (device_values) const_per_64 = 0;
+    else HIPCHK(launch_fill_powers(c->values.as<gl_t>(), 3, GL_GENERATOR, n_cols * n, c->st));
+    // `const_per_64` of every 64 columns constant (a FinalExp trace: 11 of 64 take a closed form), in runs of up to 12 as its Fp12 blocks are
+    // (+ 256: unit vectors instead -- one 1 per column, at a different row each -- the other closed form: FinalExp's 8192 row selectors)
+    const bool unit = (const_per_64 & 256u) != 0, prewarm = (const_per_64 & 1024u) != 0, touch = (const_per_64 & 2048u) != 0;  // + 1024 / + 2048 (with reps == 0): see below
+    const_per_64 &= 255u;
+    for (size_t c0 = 0; const_per_64 && c0 < n_cols; c0 += 64) {
+        const size_t cnt = std::min<size_t>(const_per_64, n_cols - c0);
+        HIPCHK(hipMemsetAsync(c->values.as<gl_t>() + c0 * n, unit ? 0 : 1, cnt * n * 8, c->st));
+        for (size_t k = 0; unit && k < cnt; k++) HIPCHK(hipMemsetAsync(c->values.as<gl_t>() + (c0 + k) * n + ((c0 + k) * 37) % n, 1, 1, c->st));
+    }
+    const bool cold = reps == 0;  // reps == 0: ONE launch with no warm-up launch in front of it
+    if (cold) reps = 1;
+    reps = std::min(reps, 16u);
+    std::vector<hipEvent_t> ev(reps + 1, nullptr);
+    hipError_t err = hipSuccess;
+    for (hipEvent_t& e : ev)
+        if (err == hipSuccess) err = hipEventCreate(&e);
+    if (err == hipSuccess && cold && touch) err = hipMemsetAsync(c->lde.p, 0, n_cols * N * 8, c->st);  // every page of the output written once just before
+    if (err == hipSuccess && cold && prewarm)  // a few milliseconds of the same arithmetic on a small footprint, then the launch that is timed
+        for (int k = 0; k < 4 && err == hipSuccess; k++) err = run_lde(c, in, cf, c->lde.as<gl_t>(), std::min<size_t>(n_cols, 4096), log_n, rate_bits, 0);
+    if (err == hipSuccess) err = cold ? hipStreamSynchronize(c->st) : run_lde(c, in, cf, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);  // warm-up
+    if (err == hipSuccess) err = hipEventRecord(ev[0], c->st);
+    for (unsigned r = 0; r < reps && err == hipSuccess; r++) {
+        err = run_lde(c, in, cf, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);
+        if (err == hipSuccess) err = hipEventRecord(ev[r + 1], c->st);
+    }
+    if (err == hipSuccess) err = hipEventSynchronize(ev[reps]);
+    float ms = 0;
+    if (err == hipSuccess) err = hipEventElapsedTime(&ms, ev[0], ev[reps]);
+    for (unsigned r = 0; r < reps && err == hipSuccess && each_ms; r++) err = hipEventElapsedTime(&each_ms[r], ev[r], ev[r + 1]);
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    HIPCHK(err);
+    *ms_out = ms / reps;
+    return STARKHIP_OK;
+}
+
+// kernel-level test entry: a recorded trace through expand_trace_kernel + zero_cells_kernel, handed back column-major [C][rows]
+int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor) {
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nw = log->total_words(), nr = log->total_records(), nz = log->total_late_zeros();
+    std::vector<uint32_t> h(nw + nr + nz);
+    for (const LogPiece& pc : recording_pieces(*log)) std::copy(pc.src, pc.src + pc.words, h.begin() + pc.at);
+    const size_t cells = log->rows * log->cols;
+    HIPCHK(c->values.ensure(cells * 8));
+    HIPCHK(c->staging.ensure(std::max<size_t>(h.size(), 1) * 4));
+    uint32_t* d = c->staging.as<uint32_t>();
+    if (!h.empty()) HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemsetAsync(c->values.p, 0, cells * 8, c->st));
+    if (nr) HIPCHK(launch_expand_trace(d, d + nw, nr, c->values.as<gl_t>(), log->rows, c->st));
+    if (nz) HIPCHK(launch_zero_cells(d + nw + nr, nz / 2, c->values.as<gl_t>(), log->rows, c->st));
+    HIPCHK(hipMemcpyAsync(out_colmajor, c->values.p, cells * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out) {
+    if (log_N < cap_h) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t N = (size_t)1 << log_N;
+    // treat the input as rate_bits = 0 (coset-major == natural)
+    HIPCHK(c->lde.ensure(n_cols * N * 8));
+    HIPCHK(c->digests.ensure(digest_words(N) * 8));
+    HIPCHK(hipMemcpyAsync(c->lde.p, lde_natural, n_cols * N * 8, hipMemcpyHostToDevice, c->st));
+    int form;
+    HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st, &form));
+    HIPCHK(launch_merkle_levels(c->digests.as<gl_t>(), log_N, cap_h, c->st));
+    HIPCHK(hipMemcpyAsync(cap_out, c->digests.as<gl_t>() + 4 * level_off(N, log_N - cap_h), ((size_t)4 << cap_h) * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+int permute_batch(Ctx* c, uint64_t* states, size_t n) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->staging.ensure(n * 12 * 8));
+    HIPCHK(hipMemcpyAsync(c->staging.p, states, n * 96, hipMemcpyHostToDevice, c->st));
+    HIPCHK(launch_permute_batch(c->staging.as<gl_t>(), n, c->st));
+    HIPCHK(hipMemcpyAsync(states, c->staging.p, n * 96, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+// the permutation of one leaf-hash form on whole states (kernels_hash.hip: the test entry points); a bad form or variant launches nothing
+int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n) {
+    if (variant < 0 || (unsigned)variant >= permute_form_variants(form)) return STARKHIP_ERR_BAD_SHAPE;
+    if (n == 0) return STARKHIP_OK;
+    if (!states) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->staging.ensure(2 * n * 96));
+    gl_t* in = c->staging.as<gl_t>();
+    HIPCHK(hipMemcpyAsync(in, states, n * 96, hipMemcpyHostToDevice, c->st));
+    HIPCHK(launch_permute_batch_form(form, variant, in, in + 12 * n, n, c->st));
+    HIPCHK(hipMemcpyAsync(states, in + 12 * n, n * 96, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->staging.ensure(3 * n * 8));
+    gl_t* d = c->staging.as<gl_t>();
+    HIPCHK(hipMemcpyAsync(d, a, n * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(d + n, b, n * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(launch_field_ops(op, d, d + n, d + 2 * n, n, c->st));
+    HIPCHK(hipMemcpyAsync(out, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+int host_alloc(Ctx* c, size_t bytes, void** out) {
+    if (bytes == 0) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    void* p = nullptr;
+    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return STARKHIP_ERR_OOM;
+    }
+    HIPCHK(e);
+    *out = p;
+    return STARKHIP_OK;
+}
+
+void host_free(void* p) {
+    if (p) (void)hipHostFree(p);
+}
+
+}  // namespace starkhip

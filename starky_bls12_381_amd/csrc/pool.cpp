@@ -28,7 +28,6 @@
 namespace starkhip {
 
 extern std::atomic<uint64_t> g_trace_worker_cpu_ns;       // CPU time of the recordings' helper threads
-extern std::atomic<uint64_t> g_wait_cpu_ns;               // prover.hip: CPU time inside the context threads' waits for the device
 static std::atomic<uint64_t> g_gen_cpu_ns(0), g_prove_cpu_ns(0);  // ... of the generator threads inside a recording, of the context threads inside prove()
 void host_cpu_seconds(double out[3]) {
     out[0] = (double)(g_gen_cpu_ns.load() + g_trace_worker_cpu_ns.load()) * 1e-9;

@@ -1,4 +1,5 @@
-// Internal interface between the C ABI (capi.cpp) and the GPU prover driver (prover.hip).
+// Internal interface between the C ABI (capi.cpp) and the GPU prover driver: the context (ctx.hip), the proof (prover.hip), the trace checkers
+// (check_trace.hip) and the kernel-level entries of the tests (kernel_entries.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -2,28 +2,22 @@
 // /root/reference/src/aggregate_proof.rs:59-65 (and :105, :138, :169).  prove() follows the transcript of SURVEY.md App. A.5 as a list
 // of phases (the methods of ProveCall), sized and laid out by one ProofShape and one table of work buffers that ctx_reserve() shares;
 // every heavy step is one of the kernels in kernels_*.hip, the host only runs the Fiat-Shamir challenger, two length-n synthetic
-// divisions and the proof assembly.  Below prove(): the pool's reservation and the kernel-level entry points of the tests.
+// divisions and the proof assembly.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
+// checkers' host halves check_trace.hip, the kernel-level entry points of the tests kernel_entries.hip.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <time.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <chrono>
-#include <memory>
-#include <set>
-#include <string>
-#include <system_error>
-#include <thread>
 #include <vector>
 
-#include "air_validate.h"
 #include "airs.h"
 #include "blob_arena.h"
 #include "check_report.h"
+#include "ctx.h"
 #include "kernels.h"
 #include "lde_ranges.h"
 #include "trace_log.h"
@@ -33,7 +27,6 @@
 #include "quotient_plan.h"
 #include "prover.h"
 #include "scheduler.h"
-#include "verifier.h"
 
 #ifdef STARKHIP_ROCTX  // make ROCTX=1: phase ranges for rocprofv3 --marker-trace; the default build has no profiler-SDK dependency
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -58,304 +51,6 @@ struct PhaseRanges {
 #endif
 };
 
-
-#define HIPCHK(expr)                                                                                       \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess) {                                                                            \
-            fprintf(stderr, "starkhip: HIP error %s at %s:%d (%s)\n", hipGetErrorString(_e), __FILE__, __LINE__, #expr); \
-            (void)hipDeviceSynchronize(); /* pending async copies target host buffers that are about to go out of scope */ \
-            return _e == hipErrorOutOfMemory ? STARKHIP_ERR_OOM : STARKHIP_ERR_HIP;                        \
-        }                                                                                                  \
-    } while (0)
-
-struct DevBuf {  // device memory that goes with its owner (a Ctx, or cached tables / a plan that were never finished); not copied anywhere
-    void* p = nullptr;
-    size_t cap = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        release();
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    template <class T>
-    T* as() const { return (T*)p; }
-};
-
-struct Ctx {
-    int device = 0;
-    hipStream_t st = nullptr;       // the stream of the current proof: st_normal, or st_high for a proof the pool marks urgent
-    hipStream_t st_normal = nullptr, st_high = nullptr;
-    hipEvent_t ev[STARKHIP_N_PHASES + 1];
-    float timings[STARKHIP_N_PHASES] = {0};
-    hipEvent_t kev[6];            // the three heavy kernels bracketed on their own: leaf hash, quotient evaluation, trace LDE
-    float ktimings[3] = {0};      // lde_columns, leaf_hash (trace), quotient_eval
-    float htimings[2] = {0};      // host time inside the last prove: Fiat-Shamir hashing (the challenger's sequential sponge), other host arithmetic
-    HashService* hs = nullptr;    // a pooled context's trace commitments are launched by the pool's scheduler (scheduler.h)
-    hipEvent_t hash_ready = nullptr, hash_done = nullptr;
-    HashService::Timing hash_timing;  // pooled: the commitment kernel's own start / stop on ITS launch stream, its form and group
-    hipEvent_t wait_ev = nullptr;  // hipEventBlockingSync: see stream_wait()
-    // Read-backs (caps, openings, FRI batches, the nonce) land in a page-locked arena and are copied to where prove() wants them when the
-    // host next waits for the stream (read_back() / stream_wait()): hipMemcpyAsync into PAGEABLE memory does not return until the copy has
-    // run, and the runtime waits for it spinning -- every context thread of a pool burned a CPU for as long as its proof's kernels ran
-    // (0.84 CPU-seconds per FinalExp proof with eight in flight against 0.27 with the arena; bench.py: host.cpu_seconds_per_proof_by_role).
-    void* rb = nullptr;
-    size_t rb_cap = 0, rb_used = 0;
-    struct Pending { void* dst; const void* src; size_t bytes; };
-    std::vector<Pending> rb_pending;
-    void* host_staging = nullptr;  // page-locked: a recording's parts gathered for one upload (prove(), layout 2); scattered columns (layout 3)
-    size_t host_staging_cap = 0;
-    hipEvent_t col_ev[2] = {nullptr, nullptr};  // layout 3: the two halves of host_staging, each free again when its copy has run
-    std::set<int> blob_airs;  // AIRs this context has reserved page-locked proof blobs for (blob_arena.h)
-    bool hash_requested = false;
-    bool urgent = false;  // ctx_set_urgent
-    // tuning (starkhip_set_option; defaults are the measured best)
-    long opt_quotient_impl = 0;   // 0: tiled evaluator (quotient_plan.h), 1: op-stream interpreter (quotient_ops.h)
-    long opt_quotient_waves = 65536, opt_quotient_slots = 0, opt_quotient_chunks = 0, opt_quotient_debug = 0, opt_zeta_on_coset = 0;
-    // Shape-dependent tables and the per-AIR constraint plan are CACHED per context: a pooled context that alternates between
-    // AIRs (a PairingPrecomp proof, then an FP12Mul one) finds both again instead of rebuilding the plan on the host and
-    // re-allocating device buffers -- hipFree synchronises the whole device, i.e. waits for every other proof's kernels.
-    struct Tables {
-        int log_n = -1, rate = -1, qdb = -1;
-        DevBuf tw_fwd, tw_inv, coset_scale, qtab, qshift_inv;
-        DevBuf lde2_fwd, lde2_inv, lde2_cs, lde2_oh;  // kernels_lde.hip tables (log_n >= 8)
-        DevBuf lde_wave;                               // ... and of its wave-resident kernel (log_n == 13)
-        // kernels_lde_long.hip (log_n >= 14, and the proof's other vectors of 2^16 .. 2^20 words): the coset powers (7 w_N^s)^j, the
-        // sub-transforms' twiddles, and the inter-pass twiddles of every length this shape has transformed (ensure_long_tw)
-        DevBuf long_cs, long_sub;
-        struct LongTw { unsigned log_len; DevBuf fwd, inv; };
-        std::vector<std::unique_ptr<LongTw>> long_tw;
-        std::vector<DevBuf*> bufs() {
-            std::vector<DevBuf*> v = {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave, &long_cs, &long_sub};
-            for (auto& t : long_tw) {
-                v.push_back(&t->fwd);
-                v.push_back(&t->inv);
-            }
-            return v;
-        }
-    };
-    struct PlanDev {  // tiled plan (quotient_plan.h) of one AIR on the device
-        int air = -1;
-        unsigned chunks = 0, want = 0;
-        uint32_t recs = 0;
-        DevBuf q_recs, q_streams, q_chunk_tile_off, q_tile_list, q_contrib_off, q_contribs, q_consts, q_apow;
-        std::vector<DevBuf*> bufs() { return {&q_recs, &q_streams, &q_chunk_tile_off, &q_tile_list, &q_contrib_off, &q_contribs, &q_consts, &q_apow}; }
-    };
-    std::vector<std::unique_ptr<Tables>> table_cache;
-    std::vector<std::unique_ptr<PlanDev>> plan_cache;
-    Tables* tab = nullptr;    // the current shape's (ensure_tables)
-    PlanDev* plan = nullptr;  // the current AIR's (ensure_plan)
-    long opt_leaf_hash_form = 0;     // 0: a lone context's commitments: row form for <= 4096 leaves, pair form for >= 32 768, quad form between; 1: quad always; 2: row always; 3: lane always; 4: pair always
-#ifdef STARKHIP_LDE_V2_DEFAULT      // A/B builds (make variant NAME=ldev2 DEFS=-DSTARKHIP_LDE_V2_DEFAULT): pooled contexts cannot be given an option from outside
-    long opt_lde_impl = 1;
-#else
-    long opt_lde_impl = 0;           // 0: 8192-row traces take lde_columns_wave_kernel; 1: lde_columns_v2_kernel for every shape (the cross-check)
-#endif
-    long opt_lde_closed_forms = 1;   // constant / unit-vector columns skip their transforms (kernels_lde.hip); 0: every column is transformed
-    long opt_host_commit_leaves = 64; // trace commitments of at most this many leaves (and >= 64 columns) are hashed by host threads (0: never)
-    long opt_verify_chunk_mb = 1024;  // device memory one chunk of starkhip_verify_batch may take (verifier_device.cpp)
-    double verify_timings[4] = {0};   // the last starkhip_verify_batch: host prelude ms, upload ms, device ms, host CPU seconds
-    std::vector<gl_t> host_lde;      // their LDE on the host
-    // op-stream program (quotient_impl = 1; kept as the cross-check)
-    int prog_air = -1;
-    unsigned prog_chunks = 0;
-    DevBuf d_ops, d_loads, d_chunk_off;  // compile_quotient_ops() + attach_cell_cache() output for prog_air
-    unsigned prog_slots = 0;
-    std::vector<uint32_t> chunk_k_after;
-    // trace checker (starkhip_check_trace): the op stream of chk_air cut for chk_want chunks (chk_chunks of them came out), the chunks'
-    // first ops and constraints, the results
-    int chk_air = -1;
-    unsigned chk_want = 0, chk_chunks = 0;
-    std::vector<uint32_t> chk_k0;  // [chk_chunks + 1] the chunks' first constraints on the host, then n_constraints
-    DevBuf d_chk_ops, d_chk_meta, d_chk_out, d_chk_rep, d_chk_list;  // the last two: starkhip_check_trace_report's (check_trace_report)
-    // work buffers of a proof: work_buffers() below is the one table of their sizes (prove() and ctx_reserve() allocate from it)
-    // `lde` is the one big buffer (19.3 GB for FinalExp).  Before the LDE kernel writes it, it holds everything that waits for that
-    // kernel: the trace columns as its LAST quarter (the LDE goes out in launches that overwrite only columns already transformed:
-    // run_lde_trace) and, at its start, the upload staging (row-major rows before the transpose, a recording's words before the
-    // expansion).  Coefficients are the LDE kernel's scratch inside a column's own block and are not kept: openings and the FRI
-    // combination read coset 0 of the LDE (kernels_fri.hip).  `values` is the 1/64 of the columns the last LDE launch reads (75 MB), a
-    // whole trace only for rate_bits == 0, and starkhip_lde_batch's in-place values / coefficients.  Together 19.6 GB per FinalExp
-    // context; rounds 1-3: values + coefficients + staging + LDE = 33.7 GB.  `staging` serves the kernel-level test entries
-    // (expand_log, permute_batch, field_ops) alone.
-    DevBuf staging, values, lde, digests, pis, apow, chunk_scale, partial, qvals, qcoef, qlde, qdigests, zpow, gzpow, open_local,
-        open_next, open_q, ext_apow, comb_partial, comb_out, fri_coef, fri_vals, fri_rows[16], fri_digests[16], scale_tab, pow_state,
-        pow_best, qidx, gather_t;
-    // every device buffer the context holds, cached tables and plans included: what ctx_destroy releases and ctx_device_bytes adds up
-    std::vector<DevBuf*> dev_bufs() {
-        std::vector<DevBuf*> v = {&d_ops, &d_loads, &d_chunk_off, &d_chk_ops, &d_chk_meta, &d_chk_out, &d_chk_rep, &d_chk_list, &staging, &values, &lde, &digests, &pis,
-                                  &apow, &chunk_scale, &partial, &qvals, &qcoef, &qlde, &qdigests, &zpow, &gzpow, &open_local, &open_next, &open_q,
-                                  &ext_apow, &comb_partial, &comb_out, &fri_coef, &fri_vals, &scale_tab, &pow_state, &pow_best, &qidx, &gather_t};
-        for (DevBuf& b : fri_rows) v.push_back(&b);
-        for (DevBuf& b : fri_digests) v.push_back(&b);
-        for (auto& t : table_cache)
-            for (DevBuf* b : t->bufs()) v.push_back(b);
-        for (auto& d : plan_cache)
-            for (DevBuf* b : d->bufs()) v.push_back(b);
-        return v;
-    }
-};
-
-// Wait for everything enqueued on the context's stream -- SLEEPING, not spinning: the wait goes through an event created with
-// hipEventBlockingSync (an interrupt-driven wait).  With several proofs in flight every context has a host thread waiting for
-// its stream most of the time; hipStreamSynchronize spins by default (hipDeviceScheduleAuto on a many-core host), and spinning
-// threads eat the CPUs -- in a container with a CPU quota, the quota -- that trace generation and the other proofs' Fiat-Shamir
-// hashing need.  Per event, so nothing about the device's scheduling flags changes for other libraries in the process (RCCL).
-// Waiting for an event WITHOUT a CPU: hipEventSynchronize on a hipEventBlockingSync event does not sleep on this runtime -- measured with
-// eight proofs in flight, 0.80 of the 0.84 CPU-seconds a context thread spends per FinalExp proof were inside that call (it yields, so it
-// only shows where CPUs are idle; where they are not, it takes them from the recordings, which run at nice 10).  The device phases it
-// waits for are milliseconds long, so: look a few times, then sleep in steps that grow from 20 to 200 microseconds.
-hipError_t event_wait_sleeping(hipEvent_t ev) {
-#ifdef STARKHIP_RUNTIME_WAIT  // A/B builds: the runtime's own wait (rounds 3-4)
-    return hipEventSynchronize(ev);
-#endif
-    for (int spin = 0; spin < 8; spin++) {
-        const hipError_t q = hipEventQuery(ev);
-        if (q != hipErrorNotReady) return q;
-    }
-    (void)hipGetLastError();  // hipErrorNotReady is not an error (and must not surface at the next launch)
-    timespec ts = {0, 20000};
-    for (;;) {
-        nanosleep(&ts, nullptr);
-        const hipError_t q = hipEventQuery(ev);
-        if (q != hipErrorNotReady) return q;
-        (void)hipGetLastError();
-        if (ts.tv_nsec < 200000) ts.tv_nsec += ts.tv_nsec / 2;
-    }
-}
-
-uint64_t thread_cpu_ns();                      // trace_tasks.cpp
-std::atomic<uint64_t> g_wait_cpu_ns(0);       // CPU time the context threads spend INSIDE their waits for the device (should be next to nothing)
-static hipError_t stream_wait(Ctx* c) {
-    const uint64_t cpu0 = thread_cpu_ns();
-    hipError_t e = hipEventRecord(c->wait_ev, c->st);
-    if (e == hipSuccess) e = event_wait_sleeping(c->wait_ev);
-    g_wait_cpu_ns.fetch_add(thread_cpu_ns() - cpu0);
-    for (const Ctx::Pending& p : c->rb_pending)  // the read-backs requested since the last wait have landed in the arena
-        if (e == hipSuccess) memcpy(p.dst, p.src, p.bytes);
-    c->rb_pending.clear();
-    c->rb_used = 0;
-    return e;
-}
-
-// device -> host on the context's stream, complete after the next stream_wait(c); `dst` may be pageable
-static hipError_t read_back(Ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
-    const size_t need = (bytes + 63) & ~(size_t)63;
-    if (!c->rb || c->rb_used + need > c->rb_cap || st != c->st) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);  // does not fit: the direct (blocking) way
-    void* slot = (char*)c->rb + c->rb_used;
-    c->rb_used += need;
-    const hipError_t e = hipMemcpyAsync(slot, src, bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) c->rb_pending.push_back({dst, slot, bytes});
-    return e;
-}
-
-static int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb) {
-    for (auto& t : c->table_cache)
-        if (t->log_n == (int)log_n && t->rate == (int)rate && t->qdb == (int)qdb) {
-            c->tab = t.get();
-            return 0;
-        }
-    std::unique_ptr<Ctx::Tables> fresh(new Ctx::Tables());  // a half-built set of tables is not kept: it goes with `fresh`, buffers and all
-    Ctx::Tables* T = fresh.get();
-    const unsigned log_N = log_n + rate;
-    const size_t N = (size_t)1 << log_N, size = (size_t)1 << (log_n + qdb), n_rows = (size_t)1 << log_n;
-    HIPCHK(T->tw_fwd.ensure(N / 2 * 8 + 8));
-    HIPCHK(T->tw_inv.ensure(N / 2 * 8 + 8));
-    HIPCHK(T->coset_scale.ensure(N * 8));
-    HIPCHK(T->qtab.ensure(4 * size * 8));
-    HIPCHK(T->qshift_inv.ensure(size * 8));
-    gl_t w = gl_root_of_unity(log_N);
-    HIPCHK(launch_fill_powers(T->tw_fwd.as<gl_t>(), 1, w, N / 2, c->st));
-    HIPCHK(launch_fill_powers(T->tw_inv.as<gl_t>(), 1, gl_inv(w), N / 2, c->st));
-    HIPCHK(launch_fill_coset_scale(T->coset_scale.as<gl_t>(), log_n, rate, c->st));
-    HIPCHK(launch_quotient_tables(T->qtab.as<gl_t>(), log_n, qdb, c->st));
-    HIPCHK(launch_fill_powers(T->qshift_inv.as<gl_t>(), 1, gl_inv(GL_GENERATOR), size, c->st));
-    if (lde_v2_supported(log_n)) {
-        HIPCHK(T->lde2_fwd.ensure(lde_v2_tw_words(log_n) * 8));
-        HIPCHK(T->lde2_inv.ensure(lde_v2_tw_words(log_n) * 8));
-        HIPCHK(T->lde2_cs.ensure(N * 8));
-        HIPCHK(T->lde2_oh.ensure(std::max<size_t>(1, lde_v2_oh_words(log_n, rate)) * 8));
-        HIPCHK(lde_v2_upload_tables(log_n, rate, T->lde2_fwd.as<gl_t>(), T->lde2_inv.as<gl_t>(), T->lde2_cs.as<gl_t>(), T->lde2_oh.as<gl_t>(), c->st));
-        if (lde_wave_supported(log_n)) {
-            HIPCHK(T->lde_wave.ensure((lde_wave_table_words(rate) + 1) * 8));  // + the launches' column counter
-            HIPCHK(lde_wave_upload_tables(rate, T->lde_wave.as<gl_t>(), c->st));
-        }
-    }
-    if (lde_long_supported(log_n)) {
-        HIPCHK(T->long_cs.ensure(N * 8));
-        for (size_t s = 0; s < ((size_t)1 << rate); s++)
-            HIPCHK(launch_fill_powers(T->long_cs.as<gl_t>() + s * n_rows, 1, gl_mul(GL_GENERATOR, gl_pow(w, s)), n_rows, c->st));
-    }
-    T->log_n = log_n;
-    T->rate = rate;
-    T->qdb = qdb;
-    c->table_cache.push_back(std::move(fresh));
-    c->tab = T;
-    return 0;
-}
-
-// Vectors of 2^16 .. 2^26 words go through the multi-workgroup transform (kernels_lde_long.hip; above 2^20 words in tiles narrower than a
-// cache line); shorter ones stay with the one-workgroup ntt_global_kernel (no proof of up to 8192 rows changes its kernels).  So does what
-// is longer still: only 2^19 rows and more at rate_bits 8 have such a vector.  Trace columns take it from 2^14 rows on (run_lde).
-static bool long_vector(unsigned log_len) { return log_len > 15 && lde_long_supported(log_len); }
-
-// The long transform's tables for vectors of 2^log_len words, cached with the current shape's tables
-static int ensure_long_tw(Ctx* c, unsigned log_len, LdeLongTables* out) {
-    Ctx::Tables* T = c->tab;
-    if (!T->long_sub.p) {
-        HIPCHK(T->long_sub.ensure(lde_long_sub_words() * 8));
-        if (hipError_t e = lde_long_upload_sub_tables(T->long_sub.as<gl_t>(), c->st); e != hipSuccess) {
-            T->long_sub.release();
-            HIPCHK(e);
-        }
-    }
-    Ctx::Tables::LongTw* tw = nullptr;
-    for (auto& t : T->long_tw)
-        if (t->log_len == log_len) tw = t.get();
-    if (!tw) {
-        std::unique_ptr<Ctx::Tables::LongTw> fresh(new Ctx::Tables::LongTw());
-        fresh->log_len = log_len;
-        HIPCHK(fresh->fwd.ensure(((size_t)8) << log_len));
-        HIPCHK(fresh->inv.ensure(((size_t)8) << log_len));
-        HIPCHK(lde_long_fill_twiddles(fresh->fwd.as<gl_t>(), fresh->inv.as<gl_t>(), log_len, c->st));
-        tw = fresh.get();
-        T->long_tw.push_back(std::move(fresh));
-    }
-    if (out) *out = LdeLongTables{T->long_sub.as<gl_t>(), tw->fwd.as<gl_t>(), tw->inv.as<gl_t>()};
-    return 0;
-}
-
-// IFFT + coset LDE of `cols` columns with the tables of ensure_tables(log_n, rate, .)
-static hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs) {
-    // 2^14 rows and more: a column is split over workgroups; `coeffs` is that transform's scratch as well (required unless from_coeffs).
-    // No closed forms for constant / unit-vector columns there ("lde_closed_forms" has nothing to switch).
-    if (lde_long_supported(log_n)) {
-        LdeLongTables tb;
-        if (const int rc = ensure_long_tw(c, log_n, &tb)) return rc == STARKHIP_ERR_OOM ? hipErrorOutOfMemory : hipErrorUnknown;
-        return launch_lde_columns_long(values, coeffs, lde, cols, log_n, rate, tb, c->tab->long_cs.as<gl_t>(), from_coeffs, c->st);
-    }
-    // 8192-row traces (FinalExp, ECCAgg): values -> LDE with nothing kept in between goes through the wave-resident kernel
-    if (lde_wave_supported(log_n) && !coeffs && !from_coeffs && c->opt_lde_impl == 0) {
-        // the launch's column counter: the last word of the table buffer, cleared in stream order before every launch
-        unsigned* next = (unsigned*)(c->tab->lde_wave.as<gl_t>() + lde_wave_table_words(rate));
-        if (hipError_t e = hipMemsetAsync(next, 0, sizeof(unsigned), c->st); e != hipSuccess) return e;
-        return launch_lde_columns_wave(values, lde, cols, rate, c->tab->lde_wave.as<gl_t>(),
-                                       (c->opt_lde_closed_forms && lde_v2_oh_words(log_n, rate)) ? c->tab->lde2_oh.as<gl_t>() : nullptr, next, c->st);
-    }
-    if (lde_v2_supported(log_n))
-        return launch_lde_columns_v2(values, coeffs, lde, cols, log_n, rate, c->tab->lde2_fwd.as<gl_t>(), c->tab->lde2_inv.as<gl_t>(),
-                                     c->tab->lde2_cs.as<gl_t>(),
-                                     (c->opt_lde_closed_forms && lde_v2_oh_words(log_n, rate)) ? c->tab->lde2_oh.as<gl_t>() : nullptr, from_coeffs, c->st);
-    return launch_lde_columns(values, coeffs, lde, cols, log_n, rate, c->tab->tw_fwd.as<gl_t>(), c->tab->tw_inv.as<gl_t>(), log_n + rate,
-                              c->tab->coset_scale.as<gl_t>(), from_coeffs, c->st);
-}
-
 // The LDE of a trace whose columns are parked in the buffer the LDE goes to, as its last C n words (in_place).  lde_ranges.h has the
 // launch plan and why it is safe: launches over 3/4, 3/16, 3/64 of the columns for R = 4, each overwriting only columns an earlier
 // launch has transformed, and the last lde_tail_columns(C) columns -- 1/64 of them, 75 MB for FinalExp -- from a copy (`tail`).  Carried
@@ -373,214 +68,6 @@ static hipError_t run_lde_trace(Ctx* c, const gl_t* values, gl_t* lde, gl_t* tai
         if (hipError_t e = run_lde(c, in, nullptr, lde + l.a * R * n, l.b - l.a, log_n, rate, 0); e != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-static int ensure_program(Ctx* c, const AirInfo& air, size_t quotient_points) {
-    // enough (point-block x chunk) waves to fill 256 CUs several times over
-    size_t blocks = (quotient_points + 63) / 64;
-    size_t target_waves = (size_t)std::max(64L, c->opt_quotient_waves);  // measured on FinalExp: 8 K waves 61.3 ms, 16 K 56.4, 32 K 54.3, 64 K 53.5, 128 K 52.9
-    unsigned want = (unsigned)std::min<size_t>(256, std::max<size_t>(1, (target_waves + blocks - 1) / blocks));
-    want = (unsigned)std::min<size_t>(want, air.prog.group_off.size());
-    if (c->prog_air == air.id && c->prog_chunks == want) return 0;
-    QProgram Q = compile_quotient_ops(air.prog, want);
-    want = (unsigned)Q.chunk_k_after.size();
-    // per-wave LDS cell cache, OFF by default: measured on FinalExp (MI355X) 0 slots 40 ms, 16: 44, 32: 67, 48: 94 ms.
-    // The kernel is bound by memory (253 GB fetched per launch, 6.1 TB/s) and its throughput is proportional to the waves
-    // in flight; Belady replacement would hit 38 / 56 / 64 % with 16 / 32 / 64 slots, but the LDS those slots take costs more
-    // occupancy than the hits return.  Option "quotient_slots" (0..64) keeps the path testable.
-    c->prog_slots = (unsigned)std::min(64L, std::max(0L, c->opt_quotient_slots));
-    attach_cell_cache(Q, c->prog_slots);
-    HIPCHK(c->d_loads.ensure(Q.loads.size() * 4));
-    HIPCHK(hipMemcpyAsync(c->d_loads.p, Q.loads.data(), Q.loads.size() * 4, hipMemcpyHostToDevice, c->st));
-    c->chunk_k_after = Q.chunk_k_after;
-    HIPCHK(c->d_ops.ensure(Q.ops.size() * sizeof(QOp)));
-    HIPCHK(hipMemcpyAsync(c->d_ops.p, Q.ops.data(), Q.ops.size() * sizeof(QOp), hipMemcpyHostToDevice, c->st));
-    HIPCHK(c->d_chunk_off.ensure(Q.chunk_batch.size() * 4));
-    HIPCHK(hipMemcpyAsync(c->d_chunk_off.p, Q.chunk_batch.data(), Q.chunk_batch.size() * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(stream_wait(c));  // Q goes out of scope
-    c->prog_air = air.id;
-    c->prog_chunks = want;
-    return 0;
-}
-
-// Tiled plan of `air` on the device.  Chunks: enough (64-point block x chunk) workgroups to fill 256 CUs several times over.
-static int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points) {
-    const size_t blocks = (quotient_points + 63) / 64;
-    unsigned want = (unsigned)std::min<size_t>(512, std::max<size_t>(1, (8192 + blocks - 1) / blocks));  // FinalExp: 4 chunks 29.8 ms, 8: 29.4, 16: 29.0, 32: 28.9
-    if (c->opt_quotient_chunks > 0) want = (unsigned)c->opt_quotient_chunks;
-    for (auto& pd : c->plan_cache)
-        if (pd->air == air.id && pd->want == want) {
-            c->plan = pd.get();
-            return 0;
-        }
-    const QTPlan Q = build_quotient_plan(air.prog, want);
-    std::unique_ptr<Ctx::PlanDev> fresh(new Ctx::PlanDev());
-    Ctx::PlanDev* D = fresh.get();
-    struct Up { DevBuf* b; const void* src; size_t bytes; };
-    const std::vector<gl_t>& consts = air.prog.consts;
-    const gl_t zero = 0;
-    const Up ups[] = {{&D->q_recs, Q.recs.data(), Q.recs.size() * sizeof(QTRec)},
-                      {&D->q_streams, Q.streams.data(), Q.streams.size() * sizeof(QTStream)},
-                      {&D->q_chunk_tile_off, Q.chunk_tile_off.data(), Q.chunk_tile_off.size() * 4},
-                      {&D->q_tile_list, Q.tile_list.empty() ? (const void*)&zero : (const void*)Q.tile_list.data(), std::max<size_t>(1, Q.tile_list.size()) * 4},
-                      {&D->q_contrib_off, Q.contrib_off.data(), Q.contrib_off.size() * 4},
-                      {&D->q_contribs, Q.contribs.empty() ? (const void*)&zero : (const void*)Q.contribs.data(), std::max<size_t>(1, Q.contribs.size()) * sizeof(QTContrib)},
-                      {&D->q_consts, consts.empty() ? (const void*)&zero : (const void*)consts.data(), std::max<size_t>(1, consts.size()) * 8}};
-    for (const Up& u : ups) {
-        HIPCHK(u.b->ensure(u.bytes));
-        HIPCHK(hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, c->st));
-    }
-    HIPCHK(D->q_apow.ensure(std::max<size_t>(1, air.prog.n_constraints) * 16));
-    HIPCHK(stream_wait(c));  // Q goes out of scope
-    D->air = air.id;
-    D->want = want;
-    D->chunks = Q.n_chunks;
-    D->recs = (uint32_t)Q.recs.size();
-    c->plan_cache.push_back(std::move(fresh));
-    c->plan = D;
-    return 0;
-}
-
-// digest buffer: level 0 (n_leaves nodes) followed by level 1, ... ; offset of level l in nodes
-static inline size_t level_off(size_t n_leaves, unsigned l) { return 2 * n_leaves - (2 * n_leaves >> l); }
-static inline size_t digest_words(size_t n_leaves) { return 8 * n_leaves; }
-
-// Which leaf-hash form a LONE context uses (a pool's commitments go through its scheduler, which merges the small ones into quad
-// launches): the quad form of a commitment with <= 4096 leaves is at most 256 waves on 1024 SIMDs, each a chain of up to 12 167
-// sequential permutations, so the form with fewer instructions per wave and permutation wins (MillerLoop 119 -> ms, kernels_hash.hip).
-static bool use_row_form(const Ctx* c, size_t n_cols, unsigned log_N) {
-    if (c->opt_leaf_hash_form == 1) return false;
-    if (c->opt_leaf_hash_form == 2) return true;
-    if (c->opt_leaf_hash_form == 3 || c->opt_leaf_hash_form == 4) return false;
-    return log_N <= 12 && n_cols >= 64;
-}
-// The pair form (two lanes per leaf, 256 registers per wave) fills the chip from 32 768 leaves on: 1 024 waves, one per SIMD.
-static bool use_pair_form(const Ctx* c, size_t n_cols, unsigned log_N) {
-    if (c->opt_leaf_hash_form == 4) return true;
-    if (c->opt_leaf_hash_form != 0) return false;
-    return log_N >= 15 && n_cols >= 64;
-}
-
-int ctx_create(int device, Ctx** out, int priority) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return STARKHIP_ERR_NO_DEVICE;
-    if (device < 0 || device >= count) return STARKHIP_ERR_NO_DEVICE;
-    HIPCHK(hipSetDevice(device));
-    Ctx* c = new Ctx();
-    c->device = device;
-    for (auto& e : c->ev) e = nullptr;
-    for (auto& e : c->kev) e = nullptr;
-    bool ok;
-    if (priority) {  // +1: the highest stream priority of the device, -1: the lowest (pooled contexts, starkhip_pool_config_t)
-        int least = 0, greatest = 0;
-        ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-             hipStreamCreateWithPriority(&c->st_normal, hipStreamDefault, priority > 0 ? greatest : least) == hipSuccess;
-    } else {
-        ok = hipStreamCreate(&c->st_normal) == hipSuccess;
-    }
-    c->st = c->st_normal;
-    for (auto& e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    for (auto& e : c->kev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->hash_ready, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->hash_done, hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->wait_ev, hipEventDisableTiming | hipEventBlockingSync) == hipSuccess;
-    ok = ok && hipEventCreate(&c->hash_timing.t0) == hipSuccess && hipEventCreate(&c->hash_timing.t1) == hipSuccess;
-    if (ok && hipHostMalloc(&c->rb, (size_t)8 << 20, hipHostMallocDefault) == hipSuccess) c->rb_cap = (size_t)8 << 20;  // (without it read-backs go the direct way)
-    else c->rb = nullptr;
-    if (!ok) {  // release whatever was created
-        if (c->rb) (void)hipHostFree(c->rb);
-        if (c->hash_ready) (void)hipEventDestroy(c->hash_ready);
-        if (c->hash_done) (void)hipEventDestroy(c->hash_done);
-        if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
-        if (c->hash_timing.t0) (void)hipEventDestroy(c->hash_timing.t0);
-        if (c->hash_timing.t1) (void)hipEventDestroy(c->hash_timing.t1);
-        for (auto& e : c->ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto& e : c->kev)
-            if (e) (void)hipEventDestroy(e);
-        if (c->st_normal) (void)hipStreamDestroy(c->st_normal);
-        delete c;
-        return STARKHIP_ERR_HIP;
-    }
-    *out = c;
-    return 0;
-}
-
-void ctx_destroy(Ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->st);
-    for (DevBuf* b : c->dev_bufs()) b->release();
-    for (auto& e : c->ev) (void)hipEventDestroy(e);
-    for (auto& e : c->kev) (void)hipEventDestroy(e);
-    if (c->rb) (void)hipHostFree(c->rb);
-    (void)hipEventDestroy(c->hash_ready);
-    (void)hipEventDestroy(c->hash_done);
-    (void)hipEventDestroy(c->wait_ev);
-    (void)hipEventDestroy(c->hash_timing.t0);
-    (void)hipEventDestroy(c->hash_timing.t1);
-    for (auto& e : c->col_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->host_staging) (void)hipHostFree(c->host_staging);
-    blob_arena_drop(c);
-    (void)hipStreamDestroy(c->st_normal);
-    if (c->st_high) (void)hipStreamDestroy(c->st_high);
-    delete c;
-}
-void ctx_attach_hash_service(Ctx* c, HashService* hs) { c->hs = hs; }
-// The next proofs of this context run on a high-priority stream (urgent = true) or on its ordinary one.  Between proofs only:
-// a context's stream is idle then.
-int ctx_set_urgent(Ctx* c, bool urgent) {
-    if (urgent && !c->st_high) {
-        HIPCHK(hipSetDevice(c->device));
-        int least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(hipStreamCreateWithPriority(&c->st_high, hipStreamDefault, greatest));
-    }
-    c->st = urgent ? c->st_high : c->st_normal;
-    c->urgent = urgent;
-    return STARKHIP_OK;
-}
-bool ctx_has_hash_service(Ctx* c) { return c->hs != nullptr; }
-void ctx_hash_request_reset(Ctx* c) { c->hash_requested = false; }
-bool ctx_hash_requested(Ctx* c) { return c->hash_requested; }
-
-hipStream_t ctx_stream(Ctx* c) { return c->st; }
-int ctx_set_option(Ctx* c, const char* name, long value) {
-    if (!c || !name) return STARKHIP_ERR_BAD_SHAPE;
-    const std::string k(name);
-    if (k == "quotient_impl" && (value == 0 || value == 1)) c->opt_quotient_impl = value;
-    else if (k == "quotient_waves" && value >= 64) { c->opt_quotient_waves = value; c->prog_air = -1; }
-    else if (k == "quotient_slots" && value >= 0 && value <= 64) { c->opt_quotient_slots = value; c->prog_air = -1; }
-#ifdef STARKHIP_DEBUG  // make DEBUG_KNOBS=1 only: modes 1..4, 8 switch arithmetic off (timing decomposition; the proof is then WRONG and
-                       // prove() refuses to return it), 9 compares the two evaluators point by point on stderr
-    else if (k == "quotient_debug" && value >= 0 && value <= 9) c->opt_quotient_debug = value;
-#endif
-    else if (k == "zeta_on_coset" && value >= 0) c->opt_zeta_on_coset = value;  // tests: substitute zeta = 7 w_n^(value - 1); the proof is not a transcript any more
-    else if (k == "lde_closed_forms" && (value == 0 || value == 1)) c->opt_lde_closed_forms = value;
-    else if (k == "lde_impl" && (value == 0 || value == 1)) c->opt_lde_impl = value;
-    else if (k == "host_commit_leaves" && value >= 0 && value <= 4096) c->opt_host_commit_leaves = value;
-    else if (k == "leaf_hash_form" && value >= 0 && value <= 4) c->opt_leaf_hash_form = value;
-    else if (k == "quotient_chunks" && value >= 0 && value <= 4096) c->opt_quotient_chunks = value;  // plans are cached by (AIR, chunks)
-    else if (k == "verify_chunk_mb" && value >= 1) c->opt_verify_chunk_mb = value;
-    else return STARKHIP_ERR_BAD_SHAPE;
-    return STARKHIP_OK;
-}
-size_t ctx_device_bytes(Ctx* c) {
-    size_t total = 0;
-    for (DevBuf* b : c->dev_bufs()) total += b->cap;
-    return total;
-}
-size_t ctx_pinned_bytes(Ctx* c) { return c->host_staging_cap + c->rb_cap; }
-const float* ctx_timings(Ctx* c) { return c->timings; }
-long ctx_verify_chunk_mb(Ctx* c) { return c->opt_verify_chunk_mb; }
-double* ctx_verify_timings(Ctx* c) { return c->verify_timings; }
-int ctx_device(Ctx* c) { return c->device; }
-const float* ctx_kernel_timings(Ctx* c) { return c->ktimings; }
-const float* ctx_host_timings(Ctx* c) { return c->htimings; }
-void ctx_commit_info(Ctx* c, int* form, unsigned* group) {
-    *form = c->hash_timing.form;
-    *group = c->hash_timing.group;
 }
 
 // (F(X) - F(z)) / (X - z), padded with one zero coefficient back to length n (plonky2 divide_by_linear + push(0))
@@ -601,77 +88,6 @@ struct HostWatch {  // accumulates wall time of the host-side stretches of prove
     void stop() { ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
-// fn(0) .. fn(n_threads - 1) side by side: fn(0) on the calling thread, the others on helper threads created for this call; where no
-// thread is to be had the calling thread does that share too
-template <class F>
-static void run_on_helpers(unsigned n_threads, const F& fn) {
-    std::vector<std::thread> helpers;
-    for (unsigned w = 1; w < n_threads; w++) {
-        try {
-            helpers.emplace_back(fn, w);
-        } catch (const std::system_error&) {
-            fn(w);
-        }
-    }
-    fn(0);
-    for (std::thread& t : helpers) t.join();
-}
-
-// The context's page-locked upload staging holds at least `need` bytes; where it does not, it is replaced by one of `grow_to` (>= need)
-// bytes -- hipHostFree + hipHostMalloc wait for the device, so every caller grows by its own policy to make that rare
-static hipError_t ensure_host_staging(Ctx* c, size_t need, size_t grow_to) {
-    if (c->host_staging_cap >= need) return hipSuccess;
-    if (c->host_staging) (void)hipHostFree(c->host_staging);
-    c->host_staging = nullptr;
-    c->host_staging_cap = 0;
-    const hipError_t e = hipHostMalloc(&c->host_staging, grow_to, hipHostMallocDefault);
-    if (e == hipSuccess) c->host_staging_cap = grow_to;
-    return e;
-}
-
-// Where a recording lands in the ONE array of 32-bit words that expand_trace_kernel / zero_cells_kernel read.  A log recorded by several
-// threads comes in parts (trace_log.h): each part's words land at its base, then the parts' offsets (already shifted by that base) back
-// to back, then their late zeros.
-struct LogPiece { size_t at; const uint32_t* src; size_t words; };
-static std::vector<LogPiece> recording_pieces(const TraceLog& log) {
-    const size_t nw = log.total_words(), nr = log.total_records();
-    std::vector<LogPiece> pieces;
-    size_t at_r = 0, at_z = 0;
-    log.for_each_part([&](const TraceLog& part) {
-        if (!part.words.empty()) pieces.push_back({part.base, part.words.data(), part.words.size()});
-        if (!part.offsets.empty()) pieces.push_back({nw + at_r, part.offsets.data(), part.offsets.size()});
-        if (!part.late_zeros.empty()) pieces.push_back({nw + nr + at_z, part.late_zeros.data(), part.late_zeros.size()});
-        at_r += part.offsets.size();
-        at_z += part.late_zeros.size();
-    });
-    return pieces;
-}
-
-// A dense trace of n rows x C columns into column-major device memory: `*d_values` is where it is afterwards -- `dst`, or the caller's
-// own column-major device memory (read only).  Row-major host rows go up into the start of the LDE buffer (idle until the LDE kernel
-// writes it; C n words) and are transposed from there.
-static int upload_dense(Ctx* c, const uint64_t* trace, int layout, int on_device, size_t n, size_t C, gl_t* dst, const gl_t** d_values) {
-    *d_values = dst;
-    if (on_device && layout == 1) *d_values = trace;
-    else if (on_device) HIPCHK(launch_transpose(trace, dst, n, C, c->st));
-    else if (layout == 1) HIPCHK(hipMemcpyAsync(dst, trace, C * n * 8, hipMemcpyHostToDevice, c->st));
-    else {
-        HIPCHK(hipMemcpyAsync(c->lde.p, trace, C * n * 8, hipMemcpyHostToDevice, c->st));
-        HIPCHK(launch_transpose(c->lde.as<gl_t>(), dst, n, C, c->st));
-    }
-    return 0;
-}
-
-// The leaf hash of a LONE context's commitment in the form use_pair_form / use_row_form / "leaf_hash_form" pick; `*form` says which
-// (HashService::Timing::form)
-static hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form) {
-    *form = c->opt_leaf_hash_form == 3 ? 3 : use_pair_form(c, n_cols, log_n + rate) ? 5 : use_row_form(c, n_cols, log_n + rate) ? 1 : 0;
-    if (*form == 3) return launch_leaf_hash_lane(lde, n_cols, log_n, rate, digests, st);
-    if (*form == 5) return launch_leaf_hash_pair(lde, n_cols, log_n, rate, digests, st);
-    if (*form == 1) return launch_leaf_hash_row(lde, n_cols, log_n, rate, digests, st);
-    return launch_leaf_hash(lde, n_cols, log_n, rate, digests, st);
-}
-
 // The dimensions of one proof, derived in one place: prove() and ctx_reserve() size and lay out everything from these.
 struct ProofShape {
     unsigned log_n, r, cap_h, log_N, qdb, factor;  // log2 of rows, blow-up, cap size, LDE points; the quotient's degree bits and factor
@@ -683,8 +99,7 @@ struct ProofShape {
     static int make(const AirInfo& air, const starkhip_config_t& cfg, size_t n_rows, ProofShape* s) {
         const AirProgram& P = air.prog;
         unsigned log_n = 0;
-        while (log_n < 63 && ((size_t)1 << log_n) < n_rows) log_n++;
-        if (n_rows < 2 || ((size_t)1 << log_n) != n_rows || cfg.num_challenges != 2 || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
+        if (!log2_rows(n_rows, &log_n) || cfg.num_challenges != 2 || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
         if (!FriGeometry::make(cfg, log_n, &s->geo) || quotient_degree_bits(P.degree) > cfg.rate_bits) return STARKHIP_ERR_BAD_SHAPE;
         s->log_n = log_n; s->r = cfg.rate_bits; s->cap_h = cfg.cap_height; s->log_N = log_n + s->r;
         s->qdb = quotient_degree_bits(P.degree); s->factor = quotient_factor(P.degree);
@@ -745,21 +160,6 @@ static int ensure_long_tables(Ctx* c, const ProofShape& s) {
     for (unsigned lg : logs)
         if (lg == s.log_n ? lde_long_supported(lg) : long_vector(lg))
             if (int rc = ensure_long_tw(c, lg, nullptr)) return rc;
-    return 0;
-}
-
-// In-place transform of n_vecs vectors of 2^log_len words, vec_stride apart, as launch_ntt_global does it (inverse: tw_inv's direction and
-// final_mul = 2^-log_len) -- through the multi-workgroup transform where the vectors are long, with `mid` (as many words, not `data`) between its passes
-static int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,
-                   const gl_t* post_scale) {
-    if (long_vector(log_len)) {
-        LdeLongTables tb;
-        if (int rc = ensure_long_tw(c, log_len, &tb)) return rc;
-        HIPCHK(launch_ntt_long(data, mid, data, n_vecs, vec_stride, log_len, inverse, pre_scale, post_scale, tb, c->st));
-        return 0;
-    }
-    HIPCHK(launch_ntt_global(data, n_vecs, vec_stride, log_len, inverse ? c->tab->tw_inv.as<gl_t>() : c->tab->tw_fwd.as<gl_t>(), (unsigned)c->tab->log_n + c->tab->rate,
-                             pre_scale, post_scale, inverse ? gl_inv((gl_t)1 << log_len) : 1, c->st));
     return 0;
 }
 
@@ -947,12 +347,12 @@ int ProveCall::run_quotient_ops() {
     for (int j = 0; j < 2; j++) {
         apow[j * (AIR_MAX_GROUP + 1)] = 1;
         for (unsigned m = 1; m <= AIR_MAX_GROUP; m++) apow[j * (AIR_MAX_GROUP + 1) + m] = gl_mul(apow[j * (AIR_MAX_GROUP + 1) + m - 1], alphas[j]);
-        for (unsigned k = 0; k < n_chunks; k++) cscale[k * 2 + j] = gl_pow(alphas[j], c->chunk_k_after[k]);
+        for (unsigned k = 0; k < n_chunks; k++) cscale[k * 2 + j] = gl_pow(alphas[j], c->prog.chunk_k_after[k]);
     }
     HIPCHK(hipMemcpyAsync(c->apow.p, apow.data(), apow.size() * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->chunk_scale.p, cscale.data(), cscale.size() * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(c->kev[2], st));
-    HIPCHK(launch_quotient_eval(c->d_ops.as<QOp>(), c->d_loads.as<uint32_t>(), c->prog_slots, c->d_chunk_off.as<uint32_t>(), n_chunks,
+    HIPCHK(launch_quotient_eval(c->prog.ops.as<QOp>(), c->prog.loads.as<uint32_t>(), c->prog.slots, c->prog.chunk_off.as<uint32_t>(), n_chunks,
                                 c->pis.as<gl_t>(), c->lde.as<gl_t>(), c->tab->qtab.as<gl_t>(), c->apow.as<gl_t>(), alphas[0], alphas[1],
                                 c->partial.as<gl_t>(), s.log_n, s.r, s.qdb, st));
     HIPCHK(hipEventRecord(c->kev[3], st));
@@ -1270,7 +670,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
     if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
     const bool tiled = c->opt_quotient_impl == 0;
     if (int rc = tiled ? ensure_plan(c, air, s.size) : ensure_program(c, air, s.size)) return rc;
-    const unsigned n_chunks = tiled ? c->plan->chunks : c->prog_chunks;
+    const unsigned n_chunks = tiled ? c->plan->chunks : c->prog.chunks;
 
     // ---- buffers
     // The trace waits for the LDE INSIDE the buffer the LDE is written to, as its last C n words (trace_in_lde: run_lde_trace);
@@ -1354,342 +754,6 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t
         c->blob_airs.insert(air.id);
     }
     return stream_wait(c) == hipSuccess ? STARKHIP_OK : STARKHIP_ERR_HIP;
-}
-
-// ---------------------------------------------------------------- kernel-level entry points (tests)
-int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out) {
-    if (log_n < 1 || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8) return STARKHIP_ERR_BAD_SHAPE;
-    HIPCHK(hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure_tables(c, log_n, rate_bits, 0))) return rc;
-    const size_t n = (size_t)1 << log_n, N = n << rate_bits;
-    HIPCHK(c->values.ensure(n_cols * n * 8));
-    HIPCHK(c->lde.ensure(n_cols * N * 8));
-    HIPCHK(hipMemcpyAsync(c->values.p, values, n_cols * n * 8, hipMemcpyHostToDevice, c->st));
-    // the LDE comes from the kernel prove() uses for this shape: for 8192 rows the wave-resident one, which keeps no coefficients --
-    // those, when asked for, come from the other kernel afterwards (in place of the values, which the first run leaves untouched)
-    const bool wave = lde_wave_supported(log_n) && c->opt_lde_impl == 0;
-    std::vector<gl_t> tmp;
-    if (wave) {
-        HIPCHK(run_lde(c, c->values.as<gl_t>(), nullptr, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0));
-        if (lde_out) {
-            tmp.resize(n_cols * N);
-            HIPCHK(hipMemcpyAsync(tmp.data(), c->lde.p, n_cols * N * 8, hipMemcpyDeviceToHost, c->st));
-            HIPCHK(stream_wait(c));
-        }
-    }
-    if (!wave || coeffs_out) HIPCHK(run_lde(c, c->values.as<gl_t>(), c->values.as<gl_t>(), c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0));
-    if (coeffs_out) HIPCHK(hipMemcpyAsync(coeffs_out, c->values.p, n_cols * n * 8, hipMemcpyDeviceToHost, c->st));  // in place
-    HIPCHK(stream_wait(c));
-    if (lde_out) {
-        // device layout is coset-major; hand back NATURAL point order i = k * R + s
-        if (!wave) {
-            tmp.resize(n_cols * N);
-            HIPCHK(hipMemcpy(tmp.data(), c->lde.p, n_cols * N * 8, hipMemcpyDeviceToHost));
-        }
-        const size_t R = (size_t)1 << rate_bits;
-        for (size_t col = 0; col < n_cols; col++)
-            for (size_t s = 0; s < R; s++)
-                for (size_t k = 0; k < n; k++) lde_out[col * N + k * R + s] = tmp[col * N + s * n + k];
-    }
-    return STARKHIP_OK;
-}
-
-// kernel-level test entry: n_vecs vectors of 2^log_len words (2^16 .. 2^26) through the multi-workgroup transform as prove() runs it on
-// the quotient's values and the FRI layers -- in place, forward or inverse (with 2^-log_len)
-int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse) {
-    if (!long_vector(log_len) || !n_vecs || !data) return STARKHIP_ERR_BAD_SHAPE;
-    HIPCHK(hipSetDevice(c->device));
-    if (int rc = ensure_tables(c, 1, 0, 0)) return rc;  // (the long tables are cached with a shape's)
-    const size_t words = n_vecs << log_len;
-    HIPCHK(c->values.ensure(words * 8));
-    HIPCHK(c->lde.ensure(words * 8));
-    HIPCHK(hipMemcpyAsync(c->values.p, data, words * 8, hipMemcpyHostToDevice, c->st));
-    if (int rc = run_ntt(c, c->values.as<gl_t>(), c->lde.as<gl_t>(), n_vecs, (size_t)1 << log_len, log_len, inverse != 0, nullptr, nullptr)) return rc;
-    HIPCHK(hipMemcpyAsync(data, c->values.p, words * 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(stream_wait(c));
-    return STARKHIP_OK;
-}
-
-// micro-benchmark entry: the trace LDE of `n_cols` synthetic columns (powers of a generator: no constant or unit column, so every
-// column is transformed unless const_per_64 says otherwise), `reps` launches timed with HIP events on the context's stream; average milliseconds per launch
-int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms) {
-    if (log_n < 1 || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8 || !n_cols) return STARKHIP_ERR_BAD_SHAPE;
-    HIPCHK(hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure_tables(c, log_n, rate_bits, 0))) return rc;
-    const size_t n = (size_t)1 << log_n, N = n << rate_bits;
-    const bool long_cols = lde_long_supported(log_n);
-    HIPCHK(c->values.ensure(n_cols * n * 8 * (long_cols ? 2 : 1)));  // long columns: + the coefficients the transform keeps, beside the input
-    HIPCHK(c->lde.ensure(n_cols * N * 8));
-    const gl_t* in = device_values ? (const gl_t*)device_values : c->values.as<gl_t>();  // the caller's own column-major matrix, or the synthetic one
-    gl_t* const cf = long_cols ? c->values.as<gl_t>() + n_cols * n : nullptr;
-    if (device_values) const_per_64 = 0;
-    else HIPCHK(launch_fill_powers(c->values.as<gl_t>(), 3, GL_GENERATOR, n_cols * n, c->st));
-    // `const_per_64` of every 64 columns constant (a FinalExp trace: 11 of 64 take a closed form), in runs of up to 12 as its Fp12 blocks are
-    // (+ 256: unit vectors instead -- one 1 per column, at a different row each -- the other closed form: FinalExp's 8192 row selectors)
-    const bool unit = (const_per_64 & 256u) != 0, prewarm = (const_per_64 & 1024u) != 0, touch = (const_per_64 & 2048u) != 0;  // + 1024 / + 2048 (with reps == 0): see below
-    const_per_64 &= 255u;
-    for (size_t c0 = 0; const_per_64 && c0 < n_cols; c0 += 64) {
-        const size_t cnt = std::min<size_t>(const_per_64, n_cols - c0);
-        HIPCHK(hipMemsetAsync(c->values.as<gl_t>() + c0 * n, unit ? 0 : 1, cnt * n * 8, c->st));
-        for (size_t k = 0; unit && k < cnt; k++) HIPCHK(hipMemsetAsync(c->values.as<gl_t>() + (c0 + k) * n + ((c0 + k) * 37) % n, 1, 1, c->st));
-    }
-    const bool cold = reps == 0;  // reps == 0: ONE launch with no warm-up launch in front of it
-    if (cold) reps = 1;
-    reps = std::min(reps, 16u);
-    std::vector<hipEvent_t> ev(reps + 1, nullptr);
-    hipError_t err = hipSuccess;
-    for (hipEvent_t& e : ev)
-        if (err == hipSuccess) err = hipEventCreate(&e);
-    if (err == hipSuccess && cold && touch) err = hipMemsetAsync(c->lde.p, 0, n_cols * N * 8, c->st);  // every page of the output written once just before
-    if (err == hipSuccess && cold && prewarm)  // a few milliseconds of the same arithmetic on a small footprint, then the launch that is timed
-        for (int k = 0; k < 4 && err == hipSuccess; k++) err = run_lde(c, in, cf, c->lde.as<gl_t>(), std::min<size_t>(n_cols, 4096), log_n, rate_bits, 0);
-    if (err == hipSuccess) err = cold ? hipStreamSynchronize(c->st) : run_lde(c, in, cf, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);  // warm-up
-    if (err == hipSuccess) err = hipEventRecord(ev[0], c->st);
-    for (unsigned r = 0; r < reps && err == hipSuccess; r++) {
-        err = run_lde(c, in, cf, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0);
-        if (err == hipSuccess) err = hipEventRecord(ev[r + 1], c->st);
-    }
-    if (err == hipSuccess) err = hipEventSynchronize(ev[reps]);
-    float ms = 0;
-    if (err == hipSuccess) err = hipEventElapsedTime(&ms, ev[0], ev[reps]);
-    for (unsigned r = 0; r < reps && err == hipSuccess && each_ms; r++) err = hipEventElapsedTime(&each_ms[r], ev[r], ev[r + 1]);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    HIPCHK(err);
-    *ms_out = ms / reps;
-    return STARKHIP_OK;
-}
-
-// kernel-level test entry: a recorded trace through expand_trace_kernel + zero_cells_kernel, handed back column-major [C][rows]
-// starkhip_check_trace.  The trace goes where prove() would put it -- column-major in `values`, or the caller's own device memory --
-// with the LDE buffer as the upload staging of row-major host rows.  The op stream is cached per context like the quotient's.
-// What both checkers do before their kernels: the shape checks, the op stream of `air` (cached), the trace on the device (*d_trace)
-// and the public inputs in c->pis.
-static int check_trace_prepare(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                               unsigned* log_n_out, const gl_t** d_trace) {
-    const AirProgram& P = air.prog;
-    unsigned log_n = 0;
-    if (int rc = check_trace_shape(air, n_rows, pis, &log_n)) return rc;
-    *log_n_out = log_n;
-    const size_t n = n_rows, C = P.n_cols;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->st;
-    // (n / 64) x chunks waves: enough to fill 256 CUs several times over, at most one chunk per group
-    const size_t blocks = (n + 63) / 64;
-    const unsigned want = (unsigned)std::min<size_t>({1024, P.group_off.size(), std::max<size_t>(1, (32768 + blocks - 1) / blocks)});
-    if (c->chk_air != air.id || c->chk_want != want) {
-        c->chk_air = -1;
-        const QProgram Q = compile_quotient_ops(P, want);
-        const size_t nc = Q.chunk_k_after.size();
-        std::vector<uint32_t> meta(2 * nc + 1);  // chunk_op[nc + 1], chunk_k0[nc]
-        for (size_t j = 0; j <= nc; j++) meta[j] = Q.chunk_batch[j] * QOP_BATCH;
-        for (size_t j = 0; j < nc; j++) meta[nc + 1 + j] = j ? P.n_constraints - Q.chunk_k_after[j - 1] : 0;
-        HIPCHK(c->d_chk_ops.ensure(Q.ops.size() * sizeof(QOp)));
-        HIPCHK(c->d_chk_meta.ensure(meta.size() * 4));
-        HIPCHK(hipMemcpyAsync(c->d_chk_ops.p, Q.ops.data(), Q.ops.size() * sizeof(QOp), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(c->d_chk_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(stream_wait(c));  // Q and meta go out of scope
-        c->chk_k0.assign(meta.begin() + nc + 1, meta.end());
-        c->chk_k0.push_back(P.n_constraints);
-        c->chk_air = air.id;
-        c->chk_want = want;
-        c->chk_chunks = (unsigned)nc;
-    }
-    if (!(on_device && layout == 1)) HIPCHK(c->values.ensure(C * n * 8));
-    if (!on_device && layout != 1) HIPCHK(c->lde.ensure(C * n * 8));  // the staging of row-major host rows
-    if (int rc = upload_dense(c, trace, layout, on_device, n, C, c->values.as<gl_t>(), d_trace)) return rc;
-    HIPCHK(c->pis.ensure(std::max<size_t>(1, P.n_pis) * 8));
-    if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, st));
-    return STARKHIP_OK;
-}
-
-int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                uint64_t* violations, uint64_t first[3]) {
-    const AirProgram& P = air.prog;
-    unsigned log_n = 0;
-    const gl_t* d_trace = nullptr;
-    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &log_n, &d_trace)) return rc;
-    const size_t n = n_rows, C = P.n_cols;
-    hipStream_t st = c->st;
-    const unsigned nc = c->chk_chunks;
-    const unsigned long long init[2] = {0, ~0ull};
-    unsigned long long res[2];
-    HIPCHK(c->d_chk_out.ensure(sizeof init));
-    HIPCHK(hipMemcpyAsync(c->d_chk_out.p, init, sizeof init, hipMemcpyHostToDevice, st));
-    const uint32_t* meta = c->d_chk_meta.as<uint32_t>();
-    HIPCHK(launch_check_trace(c->d_chk_ops.as<QOp>(), meta, meta + nc + 1, nc, d_trace, c->pis.as<gl_t>(), log_n,
-                              c->d_chk_out.as<unsigned long long>(), st));
-    HIPCHK(hipMemcpyAsync(res, c->d_chk_out.p, sizeof res, hipMemcpyDeviceToHost, st));
-    HIPCHK(stream_wait(c));
-    *violations = res[0];
-    first[0] = first[1] = first[2] = 0;
-    if (!res[0]) return STARKHIP_OK;
-    // the value of the first violation, from its frame: rows r and r + 1 (mod n) of every column
-    const uint32_t k = (uint32_t)(res[1] >> 32), r = (uint32_t)res[1];
-    std::vector<gl_t> frame(2 * C);
-    HIPCHK(hipMemcpy2DAsync(frame.data(), 8, d_trace + r, n * 8, 8, C, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpy2DAsync(frame.data() + C, 8, d_trace + ((r + 1) & (n - 1)), n * 8, 8, C, hipMemcpyDeviceToHost, st));
-    HIPCHK(stream_wait(c));
-    first[0] = k;
-    first[1] = r;
-    first[2] = air_constraint_value(P, k, frame.data(), frame.data() + C, pis);
-    return STARKHIP_OK;
-}
-
-// starkhip_check_trace_report: the two passes of kernels_check_report.hip under the host half of check_report.h.  d_chk_rep holds
-// counts[K] (the cursors of the second pass), row_mask[W], base[K] and the launched chunks[nc]; d_chk_list the entries.
-namespace {
-struct DevicePasses : CheckPasses {
-    Ctx* c;
-    const AirProgram& P;
-    const gl_t* d_trace;
-    unsigned log_n;
-    size_t K, W, off_mask, off_base, off_chunks;
-    DevicePasses(Ctx* c_, const AirProgram& P_, const gl_t* t, unsigned log_n_) : c(c_), P(P_), d_trace(t), log_n(log_n_) {
-        K = P.n_constraints;
-        W = (((size_t)1 << log_n) + 63) / 64;
-        off_mask = (K * 4 + 7) / 8 * 8;
-        off_base = off_mask + W * 8;
-        off_chunks = off_base + K * 4;
-    }
-    uint32_t* d_counts() const { return c->d_chk_rep.as<uint32_t>(); }
-    unsigned long long* d_mask() const { return (unsigned long long*)((char*)c->d_chk_rep.p + off_mask); }
-    int count(uint32_t* counts, uint64_t* mask) override {
-        const unsigned nc = c->chk_chunks;
-        HIPCHK(c->d_chk_rep.ensure(off_chunks + (size_t)nc * 4));
-        HIPCHK(hipMemsetAsync(c->d_chk_rep.p, 0, off_base, c->st));
-        const uint32_t* meta = c->d_chk_meta.as<uint32_t>();
-        HIPCHK(launch_check_report_count(c->d_chk_ops.as<QOp>(), meta, meta + nc + 1, nc, d_trace, c->pis.as<gl_t>(), log_n, d_counts(), d_mask(), c->st));
-        HIPCHK(hipMemcpyAsync(mask, d_mask(), W * 8, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipMemcpyAsync(counts, d_counts(), K * 4, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(stream_wait(c));
-        return STARKHIP_OK;
-    }
-    int list(const uint32_t* base, const uint64_t*, size_t total, uint64_t* entries) override {
-        const unsigned nc = c->chk_chunks;
-        std::vector<uint32_t> chunks;  // those with a listed constraint
-        for (unsigned j = 0; j < nc; j++)
-            for (uint32_t k = c->chk_k0[j]; k < c->chk_k0[j + 1]; k++)
-                if (base[k] != ~0u) {
-                    chunks.push_back(j);
-                    break;
-                }
-        if (chunks.empty() || total > 0xFFFFFFFFull / 2) return STARKHIP_ERR_HIP;
-        HIPCHK(c->d_chk_list.ensure(total * 24));
-        char* rep = (char*)c->d_chk_rep.p;
-        HIPCHK(hipMemsetAsync(rep, 0, K * 4, c->st));  // the counts become the cursors
-        HIPCHK(hipMemcpyAsync(rep + off_base, base, K * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(hipMemcpyAsync(rep + off_chunks, chunks.data(), chunks.size() * 4, hipMemcpyHostToDevice, c->st));
-        HIPCHK(hipMemsetAsync(c->d_chk_list.p, 0xFF, total * 24, c->st));  // an entry nobody wrote fails the host's check of its segment
-        const uint32_t* meta = c->d_chk_meta.as<uint32_t>();
-        HIPCHK(launch_check_report_list(c->d_chk_ops.as<QOp>(), meta, meta + nc + 1, (const uint32_t*)(rep + off_chunks), (unsigned)chunks.size(), d_trace,
-                                        c->pis.as<gl_t>(), log_n, d_counts(), d_mask(), (const uint32_t*)(rep + off_base),
-                                        c->d_chk_list.as<unsigned long long>(), (uint32_t)total, c->st));
-        HIPCHK(hipMemcpyAsync(entries, c->d_chk_list.p, total * 24, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(stream_wait(c));  // `chunks` goes out of scope
-        return STARKHIP_OK;
-    }
-};
-}  // namespace
-
-int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                       uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out) {
-    unsigned log_n = 0;
-    const gl_t* d_trace = nullptr;
-    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &log_n, &d_trace)) return rc;
-    DevicePasses passes(c, air.prog, d_trace, log_n);
-    return check_report_run(air.prog, n_rows, passes, per_constraint, row_mask, list, cap, out);
-}
-
-int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor) {
-    HIPCHK(hipSetDevice(c->device));
-    const size_t nw = log->total_words(), nr = log->total_records(), nz = log->total_late_zeros();
-    std::vector<uint32_t> h(nw + nr + nz);
-    for (const LogPiece& pc : recording_pieces(*log)) std::copy(pc.src, pc.src + pc.words, h.begin() + pc.at);
-    const size_t cells = log->rows * log->cols;
-    HIPCHK(c->values.ensure(cells * 8));
-    HIPCHK(c->staging.ensure(std::max<size_t>(h.size(), 1) * 4));
-    uint32_t* d = c->staging.as<uint32_t>();
-    if (!h.empty()) HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemsetAsync(c->values.p, 0, cells * 8, c->st));
-    if (nr) HIPCHK(launch_expand_trace(d, d + nw, nr, c->values.as<gl_t>(), log->rows, c->st));
-    if (nz) HIPCHK(launch_zero_cells(d + nw + nr, nz / 2, c->values.as<gl_t>(), log->rows, c->st));
-    HIPCHK(hipMemcpyAsync(out_colmajor, c->values.p, cells * 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(stream_wait(c));
-    return STARKHIP_OK;
-}
-
-int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out) {
-    if (log_N < cap_h) return STARKHIP_ERR_BAD_SHAPE;
-    HIPCHK(hipSetDevice(c->device));
-    const size_t N = (size_t)1 << log_N;
-    // treat the input as rate_bits = 0 (coset-major == natural)
-    HIPCHK(c->lde.ensure(n_cols * N * 8));
-    HIPCHK(c->digests.ensure(digest_words(N) * 8));
-    HIPCHK(hipMemcpyAsync(c->lde.p, lde_natural, n_cols * N * 8, hipMemcpyHostToDevice, c->st));
-    int form;
-    HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st, &form));
-    HIPCHK(launch_merkle_levels(c->digests.as<gl_t>(), log_N, cap_h, c->st));
-    HIPCHK(hipMemcpyAsync(cap_out, c->digests.as<gl_t>() + 4 * level_off(N, log_N - cap_h), ((size_t)4 << cap_h) * 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(stream_wait(c));
-    return STARKHIP_OK;
-}
-
-int permute_batch(Ctx* c, uint64_t* states, size_t n) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(c->staging.ensure(n * 12 * 8));
-    HIPCHK(hipMemcpyAsync(c->staging.p, states, n * 96, hipMemcpyHostToDevice, c->st));
-    HIPCHK(launch_permute_batch(c->staging.as<gl_t>(), n, c->st));
-    HIPCHK(hipMemcpyAsync(states, c->staging.p, n * 96, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(stream_wait(c));
-    return STARKHIP_OK;
-}
-
-// the permutation of one leaf-hash form on whole states (kernels_hash.hip: the test entry points); a bad form or variant launches nothing
-int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n) {
-    if (variant < 0 || (unsigned)variant >= permute_form_variants(form)) return STARKHIP_ERR_BAD_SHAPE;
-    if (n == 0) return STARKHIP_OK;
-    if (!states) return STARKHIP_ERR_BAD_SHAPE;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(c->staging.ensure(2 * n * 96));
-    gl_t* in = c->staging.as<gl_t>();
-    HIPCHK(hipMemcpyAsync(in, states, n * 96, hipMemcpyHostToDevice, c->st));
-    HIPCHK(launch_permute_batch_form(form, variant, in, in + 12 * n, n, c->st));
-    HIPCHK(hipMemcpyAsync(states, in + 12 * n, n * 96, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(stream_wait(c));
-    return STARKHIP_OK;
-}
-
-int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(c->staging.ensure(3 * n * 8));
-    gl_t* d = c->staging.as<gl_t>();
-    HIPCHK(hipMemcpyAsync(d, a, n * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(d + n, b, n * 8, hipMemcpyHostToDevice, c->st));
-    HIPCHK(launch_field_ops(op, d, d + n, d + 2 * n, n, c->st));
-    HIPCHK(hipMemcpyAsync(out, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(stream_wait(c));
-    return STARKHIP_OK;
-}
-
-int host_alloc(Ctx* c, size_t bytes, void** out) {
-    if (bytes == 0) return STARKHIP_ERR_BAD_SHAPE;
-    HIPCHK(hipSetDevice(c->device));
-    void* p = nullptr;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        return STARKHIP_ERR_OOM;
-    }
-    HIPCHK(e);
-    *out = p;
-    return STARKHIP_OK;
-}
-
-void host_free(void* p) {
-    if (p) (void)hipHostFree(p);
 }
 
 }  // namespace starkhip

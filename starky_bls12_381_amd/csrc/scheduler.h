@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -29,7 +30,8 @@ unsigned cpu_budget();  // CPUs this process may really use (cgroup quota, affin
 uint64_t thread_cpu_ns();  // trace_tasks.cpp: CPU time of the calling thread
 void set_thread_trace_threads(int n);  // capi.cpp: trace_threads() of the calling thread (0 = the process-wide setting)
 inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-hipError_t event_wait_sleeping(hipEvent_t ev);  // prover.hip: a few queries, then sleeps of 20 .. 200 microseconds between them
+hipError_t event_wait_sleeping(hipEvent_t ev);  // ctx.hip: a few queries, then sleeps of 20 .. 200 microseconds between them
+extern std::atomic<uint64_t> g_wait_cpu_ns;     // ctx.hip: CPU time inside the context threads' waits for the device
 
 class HashService {
   public:

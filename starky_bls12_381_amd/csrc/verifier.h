@@ -38,7 +38,7 @@ int verify_batch_device(Ctx* c, size_t n, const starkhip_air_t* airs, const star
 int verify_batch_replay(size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
                         const size_t* proof_words, int* results);
 
-// per context (prover.hip): the device-memory cap of one chunk of a batch ("verify_chunk_mb") and the last batch's timings
+// per context (ctx.hip): the device-memory cap of one chunk of a batch ("verify_chunk_mb") and the last batch's timings
 // [host prelude ms, upload ms, device ms, host CPU seconds]
 long ctx_verify_chunk_mb(Ctx* c);
 double* ctx_verify_timings(Ctx* c);
