@@ -150,7 +150,7 @@ int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, s
  *   list (cap x {constraint, row, value}; may be NULL when cap == 0): the first min(cap, violations) violations in the order
  *     (constraint ascending, then row ascending), each with the value G * body of that constraint on that row as the device
  *     computed it (canonical, nonzero).  A cut inside a constraint's rows keeps its lowest rows.  The list is the same on every run.
- * A satisfying trace gives an all-zero report.  Two passes on the context's device (csrc/kernels_check_report.hip): one counts,
+ * A satisfying trace gives an all-zero report.  Two passes on the context's device (csrc/kernels_check.hip): one counts,
  * and, when there is something to list, one over the chunks of the listed constraints writes the entries; the host orders them.
  * starkhip_check_trace itself is unchanged and cheaper: it is the one to ask "does it hold?". */
 #define STARKHIP_CHECK_LIST_MAX (1u << 20)

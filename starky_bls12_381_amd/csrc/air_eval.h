@@ -37,37 +37,37 @@ template <class O>
 void air_eval_folded(const AirProgram& p, const typename O::T* local, const typename O::T* next, const gl_t* pis,
                      const typename O::T masks[4], const typename O::T* alphas, int n_alpha, typename O::T* acc) {
     typedef typename O::T T;
-    const uint32_t* w = p.code.data();
+    AirReader rd(p);
     for (int j = 0; j < n_alpha; j++) acc[j] = O::zero();
     std::vector<T> t(n_alpha), apow(n_alpha);
-    while ((*w & 15u) == 1u) {
-        uint32_t kind = (*w >> 4) & 3u, ng = (*w >> 8) & 255u, m = *w >> 16;
-        w++;
-        T G = masks[kind];
-        for (uint32_t g = 0; g < ng; g++, w++) {
-            T v = ((*w & REF_NEXT) ? next : local)[*w & REF_COL_MASK];
-            if (*w & REF_COMPL) v = O::sub(O::one(), v);
+    auto cell = [&](uint32_t ref) { return ((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]; };
+    GroupWord grp;
+    while (rd.group(&grp)) {
+        T G = masks[grp.kind];
+        for (uint32_t g = 0; g < grp.n_gates; g++) {
+            const uint32_t ref = rd.ref();
+            T v = cell(ref);
+            if (ref & REF_COMPL) v = O::sub(O::one(), v);
             G = O::mul(G, v);
         }
         for (int j = 0; j < n_alpha; j++) {
             t[j] = O::zero();
             apow[j] = O::one();
         }
-        for (uint32_t c = 0; c < m; c++) {
+        for (uint32_t c = 0; c < grp.m; c++) {
             T body = O::zero();
             for (;;) {
-                uint32_t tw = *w++;
-                uint32_t nf = tw & 3u, ck = (tw >> 2) & 7u, idx = tw >> 6;
+                const TermWord tw = rd.term();
                 T v = O::one();
-                for (uint32_t f = 0; f < nf; f++, w++) v = O::mul(v, ((*w & REF_NEXT) ? next : local)[*w & REF_COL_MASK]);
-                switch (ck) {
+                for (uint32_t f = 0; f < tw.nf; f++) v = O::mul(v, cell(rd.ref()));
+                switch (tw.ck) {
                     case CK_PLUS: body = O::add(body, v); break;
                     case CK_MINUS: body = O::sub(body, v); break;
-                    case CK_CONST: body = O::add(body, O::mul_base(v, p.consts[idx])); break;
-                    case CK_PI: body = O::add(body, O::mul_base(v, pis[idx])); break;
-                    default: body = O::sub(body, O::mul_base(v, pis[idx])); break;
+                    case CK_CONST: body = O::add(body, O::mul_base(v, p.consts[tw.idx])); break;
+                    case CK_PI: body = O::add(body, O::mul_base(v, pis[tw.idx])); break;
+                    default: body = O::sub(body, O::mul_base(v, pis[tw.idx])); break;
                 }
-                if (tw & 32u) break;
+                if (tw.last) break;
             }
             for (int j = 0; j < n_alpha; j++) {
                 t[j] = O::add(O::mul(t[j], alphas[j]), body);

@@ -46,6 +46,29 @@ enum : uint32_t { REF_NEXT = 1u << 30, REF_COMPL = 1u << 31, REF_COL_MASK = 0xFF
 static const uint32_t AIR_MAX_GROUP = 255;
 static const uint64_t AIR_MAGIC = 0x3152495F52494153ULL;  // "SAIR_IR1"
 
+// The rows a constraint of `kind` applies to, of a trace of n rows: the one rule of the device checkers' walker
+// (kernels_check.hip) and of the host replay (check_report.cpp).  Written without short-circuit operators: in the walker's loop
+// `kind` changes and the row does not, and this way the row's two comparisons leave the loop and no branch on `kind` is left in it.
+template <class I>
+GL_HD bool constraint_applies(uint32_t kind, I row, I n) {
+    const bool is_first = row == 0, is_last = row == n - 1;
+    return (kind == KIND_PLAIN) | ((kind == KIND_TRANSITION) & !is_last) | ((kind == KIND_FIRST) & is_first) | ((kind == KIND_LAST) & is_last);
+}
+
+// The two code words above, decoded: the only place that knows their bit layout.
+struct GroupWord {
+    uint32_t kind, n_gates, m;
+    static GroupWord decode(uint32_t w) { return {(w >> 4) & 3u, (w >> 8) & 255u, w >> 16}; }
+    uint32_t encode() const { return 1u | (kind << 4) | (n_gates << 8) | (m << 16); }
+    static bool is_group(uint32_t w) { return (w & 15u) == 1u; }  // the tag alone: END (0) is not one
+};
+struct TermWord {
+    uint32_t nf, ck, idx;
+    bool last;
+    static TermWord decode(uint32_t w) { return {w & 3u, (w >> 2) & 7u, w >> 6, (w & 32u) != 0}; }
+    uint32_t encode() const { return nf | (ck << 2) | (last ? 32u : 0u) | (idx << 6); }
+};
+
 struct AirProgram {
     uint32_t n_cols = 0, n_pis = 0, degree = 0, n_constraints = 0;
     std::vector<uint64_t> consts;
@@ -76,6 +99,24 @@ struct AirProgram {
             b.push_back((uint64_t)group_off[i] | ((uint64_t)group_k0[i] << 32));
         return b;
     }
+};
+
+// Forward cursor over the code of a VALIDATED program (the builder's, or one air_parse_checked accepted): nothing is checked
+// here.  The caller reads in the stream's own order: group(), its n_gates x ref(), then per constraint term() and its nf x ref()
+// until a term is `last`, m constraints in all, then group() again.
+struct AirReader {
+    const uint32_t* w;
+    explicit AirReader(const AirProgram& p, size_t word = 0) {
+        static const uint32_t END = 0;  // a default-constructed program has no code at all
+        w = p.code.empty() ? &END : p.code.data() + word;
+    }
+    bool group(GroupWord* g) {  // false at END
+        if (!GroupWord::is_group(*w)) return false;
+        *g = GroupWord::decode(*w++);
+        return true;
+    }
+    TermWord term() { return TermWord::decode(*w++); }
+    uint32_t ref() { return *w++; }  // the next cellref: a gate of the group, or a factor of the term, just read
 };
 
 // ------------------------------------------------------------------ symbolic layer
@@ -327,8 +368,7 @@ class AirBuilder {
                 ck = CK_CONST;
                 idx = const_index(m.coef);
             }
-            uint32_t w = (uint32_t)m.f.size() | (ck << 2) | ((t + 1 == body.m.size()) ? 1u << 5 : 0) | (idx << 6);
-            p.words.push_back(w);
+            p.words.push_back(TermWord{(uint32_t)m.f.size(), ck, idx, t + 1 == body.m.size()}.encode());
             for (uint32_t r : m.f) p.words.push_back(r);
         }
         cur_.push_back(std::move(p));
@@ -339,7 +379,7 @@ class AirBuilder {
         if (!open_) return;
         prog_.group_off.push_back((uint32_t)prog_.code.size());
         prog_.group_k0.push_back(prog_.n_constraints - (uint32_t)cur_.size());
-        prog_.code.push_back(1u | (cur_kind_ << 4) | ((uint32_t)cur_gates_.size() << 8) | ((uint32_t)cur_.size() << 16));
+        prog_.code.push_back(GroupWord{cur_kind_, (uint32_t)cur_gates_.size(), (uint32_t)cur_.size()}.encode());
         for (uint32_t g : cur_gates_) prog_.code.push_back(g);
         for (auto& p : cur_) prog_.code.insert(prog_.code.end(), p.words.begin(), p.words.end());
         cur_.clear();

@@ -67,8 +67,9 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
             break;
         }
         const std::string at = "group " + std::to_string(g) + " (code word " + std::to_string(i) + "): ";
-        if ((gw & 15u) != 1u || (gw & 0xC0u)) return refuse(why, at + "not a GROUP word");
-        const uint32_t kind = (gw >> 4) & 3u, ng = (gw >> 8) & 255u, m = gw >> 16;
+        const GroupWord grp = GroupWord::decode(gw);
+        if (grp.encode() != gw) return refuse(why, at + "not a GROUP word");  // another tag, or a reserved bit
+        const uint32_t kind = grp.kind, ng = grp.n_gates, m = grp.m;
         if (m < 1 || m > AIR_MAX_GROUP) return refuse(why, at + "m = " + std::to_string(m) + " outside 1.." + std::to_string(AIR_MAX_GROUP));
         if (ng > 4) return refuse(why, at + std::to_string(ng) + " gates (at most 4)");
         if (g >= n_groups) return refuse(why, at + "more groups than the group table holds");
@@ -83,8 +84,8 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
             uint32_t maxf = 0;
             for (;;) {
                 if (i >= n_code) return refuse(why, atk + "terms run past the code");
-                const uint32_t tw = code[i++];
-                const uint32_t nf = tw & 3u, ck = (tw >> 2) & 7u, idx = tw >> 6;
+                const TermWord tw = TermWord::decode(code[i++]);
+                const uint32_t nf = tw.nf, ck = tw.ck, idx = tw.idx;
                 if (ck > CK_NEG_PI) return refuse(why, atk + "coefficient kind " + std::to_string(ck) + " (at most 4)");
                 if (ck == CK_CONST && idx >= n_consts) return refuse(why, atk + "const index " + std::to_string(idx) + " out of range");
                 if ((ck == CK_PI || ck == CK_NEG_PI) && idx >= n_pis) return refuse(why, atk + "public input index " + std::to_string(idx) + " out of range");
@@ -93,7 +94,7 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
                 for (uint32_t f = 0; f < nf; f++, i++)
                     if (!cellref_ok(code[i], false, &msg)) return refuse(why, atk + msg);
                 maxf = std::max(maxf, nf);
-                if (tw & 32u) break;
+                if (tw.last) break;
             }
             const uint32_t deg = ng + maxf + ((kind == KIND_FIRST || kind == KIND_LAST) ? 1u : 0u);
             if (deg > degree) return refuse(why, atk + "degree " + std::to_string(deg) + " above the declared " + std::to_string(degree));
@@ -108,25 +109,27 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
 gl_t air_constraint_value(const AirProgram& P, uint32_t k, const gl_t* local, const gl_t* next, const gl_t* pis) {
     // the group of constraint k: the last one whose first constraint is <= k
     const size_t g = (size_t)(std::upper_bound(P.group_k0.begin(), P.group_k0.end(), k) - P.group_k0.begin()) - 1;
-    const uint32_t* w = P.code.data() + P.group_off[g];
-    const uint32_t ng = (*w >> 8) & 255u;
-    w++;
+    AirReader rd(P, P.group_off[g]);
+    GroupWord grp;
+    rd.group(&grp);
     auto cell = [&](uint32_t ref) { return ((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]; };
     gl_t G = 1;
-    for (uint32_t j = 0; j < ng; j++, w++) G = gl_mul(G, (*w & REF_COMPL) ? gl_sub(1, cell(*w)) : cell(*w));
+    for (uint32_t j = 0; j < grp.n_gates; j++) {
+        const uint32_t ref = rd.ref();
+        G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, cell(ref)) : cell(ref));
+    }
     for (uint32_t c = P.group_k0[g];; c++) {
         gl_t body = 0;
         for (;;) {
-            const uint32_t tw = *w++;
-            const uint32_t nf = tw & 3u, ck = (tw >> 2) & 7u, idx = tw >> 6;
+            const TermWord tw = rd.term();
             gl_t u = 1;
-            for (uint32_t f = 0; f < nf; f++) u = gl_mul(u, cell(*w++));
-            if (ck == CK_PLUS) body = gl_add(body, u);
-            else if (ck == CK_MINUS) body = gl_sub(body, u);
-            else if (ck == CK_CONST) body = gl_add(body, gl_mul(u, P.consts[idx]));
-            else if (ck == CK_PI) body = gl_add(body, gl_mul(u, pis[idx]));
-            else body = gl_sub(body, gl_mul(u, pis[idx]));
-            if (tw & 32u) break;
+            for (uint32_t f = 0; f < tw.nf; f++) u = gl_mul(u, cell(rd.ref()));
+            if (tw.ck == CK_PLUS) body = gl_add(body, u);
+            else if (tw.ck == CK_MINUS) body = gl_sub(body, u);
+            else if (tw.ck == CK_CONST) body = gl_add(body, gl_mul(u, P.consts[tw.idx]));
+            else if (tw.ck == CK_PI) body = gl_add(body, gl_mul(u, pis[tw.idx]));
+            else body = gl_sub(body, gl_mul(u, pis[tw.idx]));
+            if (tw.last) break;
         }
         if (c == k) return gl_mul(G, body);
     }

@@ -68,11 +68,11 @@ struct ReplayPasses : CheckPasses {
     ReplayPasses(const AirProgram& P_, const uint64_t* rows_, size_t n_, const uint64_t* pis_) : P(P_), rows(rows_), pis(pis_), n(n_), kind(P_.n_constraints) {
         for (size_t g = 0; g < P.group_off.size(); g++) {
             const uint32_t end = g + 1 < P.group_k0.size() ? P.group_k0[g + 1] : P.n_constraints;
-            for (uint32_t k = P.group_k0[g]; k < end; k++) kind[k] = (uint8_t)((P.code[P.group_off[g]] >> 4) & 3u);
+            for (uint32_t k = P.group_k0[g]; k < end; k++) kind[k] = (uint8_t)GroupWord::decode(P.code[P.group_off[g]]).kind;
         }
     }
     bool applies(uint32_t k, size_t r) const {
-        return kind[k] == KIND_PLAIN || (kind[k] == KIND_TRANSITION && r != n - 1) || (kind[k] == KIND_FIRST && r == 0) || (kind[k] == KIND_LAST && r == n - 1);
+        return constraint_applies(kind[k], r, n);
     }
     gl_t value(uint32_t k, size_t r) const { return air_constraint_value(P, k, rows + r * P.n_cols, rows + ((r + 1) % n) * P.n_cols, pis); }
     int count(uint32_t* counts, uint64_t* mask) override {

@@ -1,6 +1,6 @@
 // Host half of starkhip_check_trace_report, the same for the device path (check_trace.hip: check_trace_report) and for the replay without a
 // device (check_report.cpp: check_trace_report_replay): argument checks, the summary, the selection of the constraints that are
-// listed, the order of the list and its truncation.  What differs is who runs the two passes (kernels_check_report.hip, or host loops).
+// listed, the order of the list and its truncation.  What differs is who runs the two passes (kernels_check.hip, or host loops).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

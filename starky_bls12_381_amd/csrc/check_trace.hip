@@ -1,6 +1,6 @@
-// Host halves of the two trace checkers: starkhip_check_trace (kernels_check.hip) and starkhip_check_trace_report
-// (kernels_check_report.hip under check_report.h).  What they share is check_trace_prepare: the shape checks, the cached op stream of
-// the AIR (Ctx::CheckProgram), the trace and the public inputs on the device.
+// Host halves of the two trace checkers: starkhip_check_trace and starkhip_check_trace_report (the latter under check_report.h);
+// their kernels are in kernels_check.hip.  What they share is check_trace_prepare: the shape checks, the cached op stream of the
+// AIR (Ctx::CheckProgram), the trace and the public inputs on the device -- together the CheckView the kernels read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,14 +15,12 @@ namespace starkhip {
 
 // starkhip_check_trace.  The trace goes where prove() would put it -- column-major in `values`, or the caller's own device memory --
 // with the LDE buffer as the upload staging of row-major host rows.  The op stream is cached per context like the quotient's.
-// What both checkers do before their kernels: the shape checks, the op stream of `air` (cached), the trace on the device (*d_trace)
-// and the public inputs in c->pis.
+// What both checkers do before their kernels: the shape checks, the op stream of `air` (cached), the trace on the device and the
+// public inputs in c->pis; *V is what the kernels read of it.
 static int check_trace_prepare(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                               unsigned* log_n_out, const gl_t** d_trace) {
+                               CheckView* V) {
     const AirProgram& P = air.prog;
-    unsigned log_n = 0;
-    if (int rc = check_trace_shape(air, n_rows, pis, &log_n)) return rc;
-    *log_n_out = log_n;
+    if (int rc = check_trace_shape(air, n_rows, pis, &V->log_n)) return rc;
     const size_t n = n_rows, C = P.n_cols;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->st;
@@ -49,28 +47,30 @@ static int check_trace_prepare(Ctx* c, const AirInfo& air, const uint64_t* trace
     }
     if (!(on_device && layout == 1)) HIPCHK(c->values.ensure(C * n * 8));
     if (!on_device && layout != 1) HIPCHK(c->lde.ensure(C * n * 8));  // the staging of row-major host rows
-    if (int rc = upload_dense(c, trace, layout, on_device, n, C, c->values.as<gl_t>(), d_trace)) return rc;
+    if (int rc = upload_dense(c, trace, layout, on_device, n, C, c->values.as<gl_t>(), &V->trace)) return rc;
     HIPCHK(c->pis.ensure(std::max<size_t>(1, P.n_pis) * 8));
     if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, st));
+    V->ops = c->chk.ops.as<QOp>();
+    V->n_chunks = c->chk.chunks;
+    V->chunk_op = c->chk.meta.as<uint32_t>();  // chunk_op[n_chunks + 1], chunk_k0[n_chunks]
+    V->chunk_k0 = V->chunk_op + V->n_chunks + 1;
+    V->pis = c->pis.as<gl_t>();
     return STARKHIP_OK;
 }
 
 int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
                 uint64_t* violations, uint64_t first[3]) {
     const AirProgram& P = air.prog;
-    unsigned log_n = 0;
-    const gl_t* d_trace = nullptr;
-    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &log_n, &d_trace)) return rc;
+    CheckView V = {};
+    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &V)) return rc;
+    const gl_t* d_trace = V.trace;
     const size_t n = n_rows, C = P.n_cols;
     hipStream_t st = c->st;
-    const unsigned nc = c->chk.chunks;
     const unsigned long long init[2] = {0, ~0ull};
     unsigned long long res[2];
     HIPCHK(c->chk.out.ensure(sizeof init));
     HIPCHK(hipMemcpyAsync(c->chk.out.p, init, sizeof init, hipMemcpyHostToDevice, st));
-    const uint32_t* meta = c->chk.meta.as<uint32_t>();
-    HIPCHK(launch_check_trace(c->chk.ops.as<QOp>(), meta, meta + nc + 1, nc, d_trace, c->pis.as<gl_t>(), log_n,
-                              c->chk.out.as<unsigned long long>(), st));
+    HIPCHK(launch_check_trace(V, c->chk.out.as<unsigned long long>(), st));
     HIPCHK(hipMemcpyAsync(res, c->chk.out.p, sizeof res, hipMemcpyDeviceToHost, st));
     HIPCHK(stream_wait(c));
     *violations = res[0];
@@ -88,18 +88,17 @@ int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows
     return STARKHIP_OK;
 }
 
-// starkhip_check_trace_report: the two passes of kernels_check_report.hip under the host half of check_report.h.  chk.rep holds
+// starkhip_check_trace_report: the two report passes of kernels_check.hip under the host half of check_report.h.  chk.rep holds
 // counts[K] (the cursors of the second pass), row_mask[W], base[K] and the launched chunks[nc]; chk.list the entries.
 namespace {
 struct DevicePasses : CheckPasses {
     Ctx* c;
     const AirProgram& P;
-    const gl_t* d_trace;
-    unsigned log_n;
+    const CheckView& V;
     size_t K, W, off_mask, off_base, off_chunks;
-    DevicePasses(Ctx* c_, const AirProgram& P_, const gl_t* t, unsigned log_n_) : c(c_), P(P_), d_trace(t), log_n(log_n_) {
+    DevicePasses(Ctx* c_, const AirProgram& P_, const CheckView& V_) : c(c_), P(P_), V(V_) {
         K = P.n_constraints;
-        W = (((size_t)1 << log_n) + 63) / 64;
+        W = (((size_t)1 << V.log_n) + 63) / 64;
         off_mask = (K * 4 + 7) / 8 * 8;
         off_base = off_mask + W * 8;
         off_chunks = off_base + K * 4;
@@ -107,20 +106,17 @@ struct DevicePasses : CheckPasses {
     uint32_t* d_counts() const { return c->chk.rep.as<uint32_t>(); }
     unsigned long long* d_mask() const { return (unsigned long long*)((char*)c->chk.rep.p + off_mask); }
     int count(uint32_t* counts, uint64_t* mask) override {
-        const unsigned nc = c->chk.chunks;
-        HIPCHK(c->chk.rep.ensure(off_chunks + (size_t)nc * 4));
+        HIPCHK(c->chk.rep.ensure(off_chunks + (size_t)V.n_chunks * 4));
         HIPCHK(hipMemsetAsync(c->chk.rep.p, 0, off_base, c->st));
-        const uint32_t* meta = c->chk.meta.as<uint32_t>();
-        HIPCHK(launch_check_report_count(c->chk.ops.as<QOp>(), meta, meta + nc + 1, nc, d_trace, c->pis.as<gl_t>(), log_n, d_counts(), d_mask(), c->st));
+        HIPCHK(launch_check_report_count(V, d_counts(), d_mask(), c->st));
         HIPCHK(hipMemcpyAsync(mask, d_mask(), W * 8, hipMemcpyDeviceToHost, c->st));
         HIPCHK(hipMemcpyAsync(counts, d_counts(), K * 4, hipMemcpyDeviceToHost, c->st));
         HIPCHK(stream_wait(c));
         return STARKHIP_OK;
     }
     int list(const uint32_t* base, const uint64_t*, size_t total, uint64_t* entries) override {
-        const unsigned nc = c->chk.chunks;
         std::vector<uint32_t> chunks;  // those with a listed constraint
-        for (unsigned j = 0; j < nc; j++)
+        for (unsigned j = 0; j < V.n_chunks; j++)
             for (uint32_t k = c->chk.k0[j]; k < c->chk.k0[j + 1]; k++)
                 if (base[k] != ~0u) {
                     chunks.push_back(j);
@@ -133,10 +129,8 @@ struct DevicePasses : CheckPasses {
         HIPCHK(hipMemcpyAsync(rep + off_base, base, K * 4, hipMemcpyHostToDevice, c->st));
         HIPCHK(hipMemcpyAsync(rep + off_chunks, chunks.data(), chunks.size() * 4, hipMemcpyHostToDevice, c->st));
         HIPCHK(hipMemsetAsync(c->chk.list.p, 0xFF, total * 24, c->st));  // an entry nobody wrote fails the host's check of its segment
-        const uint32_t* meta = c->chk.meta.as<uint32_t>();
-        HIPCHK(launch_check_report_list(c->chk.ops.as<QOp>(), meta, meta + nc + 1, (const uint32_t*)(rep + off_chunks), (unsigned)chunks.size(), d_trace,
-                                        c->pis.as<gl_t>(), log_n, d_counts(), d_mask(), (const uint32_t*)(rep + off_base),
-                                        c->chk.list.as<unsigned long long>(), (uint32_t)total, c->st));
+        HIPCHK(launch_check_report_list(V, (const uint32_t*)(rep + off_chunks), (unsigned)chunks.size(), d_counts(), d_mask(),
+                                        (const uint32_t*)(rep + off_base), c->chk.list.as<unsigned long long>(), (uint32_t)total, c->st));
         HIPCHK(hipMemcpyAsync(entries, c->chk.list.p, total * 24, hipMemcpyDeviceToHost, c->st));
         HIPCHK(stream_wait(c));  // `chunks` goes out of scope
         return STARKHIP_OK;
@@ -146,10 +140,9 @@ struct DevicePasses : CheckPasses {
 
 int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
                        uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out) {
-    unsigned log_n = 0;
-    const gl_t* d_trace = nullptr;
-    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &log_n, &d_trace)) return rc;
-    DevicePasses passes(c, air.prog, d_trace, log_n);
+    CheckView V = {};
+    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &V)) return rc;
+    DevicePasses passes(c, air.prog, V);
     return check_report_run(air.prog, n_rows, passes, per_constraint, row_mask, list, cap, out);
 }
 

@@ -126,19 +126,23 @@ hipError_t launch_quotient_tiles(const QTRec* recs, const QTStream* streams, con
 hipError_t launch_quotient_tiles_combine(const gl_t* partial, unsigned n_chunks, const gl_t* tab, unsigned log_n, unsigned qdb, gl_t* out,
                                          hipStream_t st);
 
-// kernels_check.hip: every constraint on every row of a column-major trace [C][2^log_n] (starkhip_check_trace); `ops` / chunk_op /
-// chunk_k0 from compile_quotient_ops (ops of chunk c: [chunk_op[c], chunk_op[c + 1]), its first constraint chunk_k0[c]).  out[0] +=
-// violations, out[1] = min(out[1], (k << 32) | row); the caller presets them to 0 and ~0.
-hipError_t launch_check_trace(const QOp* ops, const uint32_t* chunk_op, const uint32_t* chunk_k0, unsigned n_chunks, const gl_t* trace,
-                              const gl_t* pis, unsigned log_n, unsigned long long* out, hipStream_t st);
-// kernels_check_report.hip (starkhip_check_trace_report), over the same op stream.  Count: counts[k] += rows on which constraint k is
-// violated, row_mask[r >> 6] |= 1 << (r & 63) for every row with a violation; both preset to 0.  List: over chunks[0 .. n_launched),
-// the violations of the constraints with base[k] != ~0 as {k, row, value} at list[base[k] + (a slot from cursors[k], preset to 0)];
-// slots at or past list_len are not written.
-hipError_t launch_check_report_count(const QOp* ops, const uint32_t* chunk_op, const uint32_t* chunk_k0, unsigned n_chunks, const gl_t* trace,
-                                     const gl_t* pis, unsigned log_n, uint32_t* counts, unsigned long long* row_mask, hipStream_t st);
-hipError_t launch_check_report_list(const QOp* ops, const uint32_t* chunk_op, const uint32_t* chunk_k0, const uint32_t* chunks, unsigned n_launched,
-                                    const gl_t* trace, const gl_t* pis, unsigned log_n, uint32_t* cursors, const unsigned long long* row_mask,
+// kernels_check.hip: the trace checkers' kernels (starkhip_check_trace, starkhip_check_trace_report).  What all three read: the op
+// stream of compile_quotient_ops cut into chunks, and a column-major trace [C][2^log_n] with its public inputs.
+struct CheckView {  // the four pointers the op loop reads come first: one fetch of kernel arguments brings them
+    const QOp* ops;
+    const uint32_t* chunk_op;  // [n_chunks + 1] first op of each chunk
+    const gl_t* trace;         // column-major [C][2^log_n]
+    const gl_t* pis;
+    const uint32_t* chunk_k0;  // [n_chunks] index of each chunk's first constraint
+    unsigned n_chunks, log_n;
+};
+// Every constraint on every row: out[0] += violations, out[1] = min(out[1], (k << 32) | row); the caller presets them to 0 and ~0.
+hipError_t launch_check_trace(const CheckView& v, unsigned long long* out, hipStream_t st);
+// The report's two passes.  Count: counts[k] += rows on which constraint k is violated, row_mask[r >> 6] |= 1 << (r & 63) for every
+// row with a violation; both preset to 0.  List: over chunks[0 .. n_launched), the violations of the constraints with base[k] != ~0
+// as {k, row, value} at list[base[k] + (a slot from cursors[k], preset to 0)]; slots at or past list_len are not written.
+hipError_t launch_check_report_count(const CheckView& v, uint32_t* counts, unsigned long long* row_mask, hipStream_t st);
+hipError_t launch_check_report_list(const CheckView& v, const uint32_t* chunks, unsigned n_launched, uint32_t* cursors, const unsigned long long* row_mask,
                                     const uint32_t* base, unsigned long long* list, uint32_t list_len, hipStream_t st);
 
 // kernels_fri.hip

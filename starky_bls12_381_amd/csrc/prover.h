@@ -80,7 +80,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
 // starkhip_check_trace: every constraint of `air` on every row of the trace, on the device (kernels_check.hip)
 int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
                 uint64_t* violations, uint64_t first[3]);
-// starkhip_check_trace_report: the same check with per-constraint counts, the rows and a list (kernels_check_report.hip, check_report.h)
+// starkhip_check_trace_report: the same check with per-constraint counts, the rows and a list (kernels_check.hip, check_report.h)
 int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
                        uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out);
 int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);

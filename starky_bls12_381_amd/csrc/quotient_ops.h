@@ -54,31 +54,29 @@ struct QProgram {
 inline QProgram compile_quotient_ops(const AirProgram& P, unsigned want) {
     // pass 1: ops of every group
     std::vector<std::vector<QOp>> groups;
-    const std::vector<uint32_t>& code = P.code;
-    size_t i = 0;
-    while (i < code.size() && code[i] != 0) {
-        const uint32_t gw = code[i++];
-        const uint32_t kind = (gw >> 4) & 3u, ng = (gw >> 8) & 255u, m = gw >> 16;
+    AirReader rd(P);
+    GroupWord grp;
+    while (rd.group(&grp)) {
         std::vector<QOp> g;
-        g.push_back({QOP_GROUP | (kind << QOP_KIND_SHIFT), 0, 0});
-        for (uint32_t j = 0; j < ng; j++) g.push_back({QOP_GATE, code[i++], 0});
-        for (uint32_t c = 0; c < m; c++) {
-            uint32_t tw;
+        g.push_back({QOP_GROUP | (grp.kind << QOP_KIND_SHIFT), 0, 0});
+        for (uint32_t j = 0; j < grp.n_gates; j++) g.push_back({QOP_GATE, rd.ref(), 0});
+        for (uint32_t c = 0; c < grp.m; c++) {
+            TermWord tw;
             do {
-                tw = code[i++];
-                const uint32_t nf = tw & 3u, ck = (tw >> 2) & 7u, idx = tw >> 6;
-                for (uint32_t f = 0; f + 1 < nf; f++) g.push_back({QOP_FACTOR | (f ? QOP_PREV : 0u), code[i++], 0});
+                tw = rd.term();
+                const uint32_t nf = tw.nf, ck = tw.ck;
+                for (uint32_t f = 0; f + 1 < nf; f++) g.push_back({QOP_FACTOR | (f ? QOP_PREV : 0u), rd.ref(), 0});
                 QOp t;
-                t.hdr = QOP_TERM | (ck << QOP_CK_SHIFT) | ((tw & 32u) ? QOP_FOLD : 0u) | (nf >= 2 ? QOP_PREV : 0u) | (nf == 0 ? QOP_NOCELL : 0u);
+                t.hdr = QOP_TERM | (ck << QOP_CK_SHIFT) | (tw.last ? QOP_FOLD : 0u) | (nf >= 2 ? QOP_PREV : 0u) | (nf == 0 ? QOP_NOCELL : 0u);
                 if (nf == 1 && (ck == CK_PLUS || ck == CK_MINUS || ck == CK_CONST)) t.hdr |= QOP_SIMPLE;
-                t.ref = nf ? code[i++] : 0;
+                t.ref = nf ? rd.ref() : 0;
                 t.k = 0;
-                if (ck == CK_CONST) t.k = P.consts[idx];
-                else if (ck == CK_PI || ck == CK_NEG_PI) t.hdr |= idx << QOP_IDX_SHIFT;
+                if (ck == CK_CONST) t.k = P.consts[tw.idx];
+                else if (ck == CK_PI || ck == CK_NEG_PI) t.hdr |= tw.idx << QOP_IDX_SHIFT;
                 g.push_back(t);
-            } while (!(tw & 32u));
+            } while (!tw.last);
         }
-        g.push_back({QOP_ENDGROUP | (m << QOP_IDX_SHIFT), 0, 0});
+        g.push_back({QOP_ENDGROUP | (grp.m << QOP_IDX_SHIFT), 0, 0});
         groups.push_back(std::move(g));
     }
     size_t total = 0;

@@ -152,41 +152,39 @@ inline QTPlan build_quotient_plan(const AirProgram& P, unsigned want_chunks) {
     std::vector<uint32_t> sg_kind;
     std::vector<Term> terms;
     terms.reserve(P.code.size() / 2);
-    const std::vector<uint32_t>& code = P.code;
-    size_t i = 0;
+    AirReader rd(P);
+    GroupWord grp;
     uint32_t k = 0;
-    while (i < code.size() && code[i] != 0) {
-        const uint32_t gw = code[i++];
-        const uint32_t kind = (gw >> 4) & 3u, ng = (gw >> 8) & 255u, m = gw >> 16;
-        if (ng > 4) throw std::runtime_error("quotient_plan: more than four gates");
-        std::string key((const char*)&kind, 4);
-        key.append((const char*)&code[i], ng * 4);  // gates are stored sorted by the builder
+    while (rd.group(&grp)) {
+        if (grp.n_gates > 4) throw std::runtime_error("quotient_plan: more than four gates");
+        uint32_t gates[4];  // stored sorted by the builder
+        for (uint32_t g = 0; g < grp.n_gates; g++) gates[g] = rd.ref();
+        std::string key((const char*)&grp.kind, 4);
+        key.append((const char*)gates, grp.n_gates * 4);
         uint32_t sg;
         auto it = sg_index.find(key);
         if (it == sg_index.end()) {
             sg = (uint32_t)sg_gates.size();
             sg_index.emplace(std::move(key), sg);
-            sg_gates.emplace_back(code.begin() + i, code.begin() + i + ng);
-            sg_kind.push_back(kind);
+            sg_gates.emplace_back(gates, gates + grp.n_gates);
+            sg_kind.push_back(grp.kind);
         } else {
             sg = it->second;
         }
-        i += ng;
-        for (uint32_t c = 0; c < m; c++, k++) {
-            uint32_t tw;
+        for (uint32_t c = 0; c < grp.m; c++, k++) {
+            TermWord tw;
             do {
-                tw = code[i++];
-                const uint32_t nf = tw & 3u, ck = (tw >> 2) & 7u, idx = tw >> 6;
+                tw = rd.term();
                 Term t;
                 t.sg = sg;
                 t.cells[0] = t.cells[1] = t.cells[2] = NONE;
-                for (uint32_t f = 0; f < nf; f++) t.cells[f] = code[i++] & (REF_COL_MASK | REF_NEXT);
-                std::sort(t.cells, t.cells + nf);
+                for (uint32_t f = 0; f < tw.nf; f++) t.cells[f] = rd.ref() & (REF_COL_MASK | REF_NEXT);
+                std::sort(t.cells, t.cells + tw.nf);
                 t.e = K - 1 - k;
-                t.coef = ck | (idx << 3);
-                if (ck == CK_CONST && P.consts[idx] == 0) continue;  // explicit zero term of an identically-zero constraint
+                t.coef = tw.ck | (tw.idx << 3);
+                if (tw.ck == CK_CONST && P.consts[tw.idx] == 0) continue;  // explicit zero term of an identically-zero constraint
                 terms.push_back(t);
-            } while (!(tw & 32u));
+            } while (!tw.last);
         }
     }
     if (k != K) throw std::runtime_error("quotient_plan: constraint count mismatch");

@@ -1,4 +1,4 @@
-"""starkhip_check_trace_report on the device (kernels_check_report.hip) against an expectation built from the CPU oracle, against its
+"""starkhip_check_trace_report on the device (kernels_check.hip) against an expectation built from the CPU oracle, against its
 own host replay, and against starkhip_check_trace, on random AIRs of 8 to 1024 rows and on a real FP12Mul trace."""
 import os
 import subprocess
