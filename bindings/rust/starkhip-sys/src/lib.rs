@@ -152,6 +152,20 @@ pub struct starkhip_check_report_t {
     pub listed: u64,
 }
 
+/// `starkhip_free_cells_t`: the summary of `starkhip_check_trace_free_cells`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct starkhip_free_cells_t {
+    /// n_rows * n_cols
+    pub cells: u64,
+    /// cells no constraint notices when delta is added to them
+    pub free_cells: u64,
+    /// columns with all n_rows rows free
+    pub free_columns: u64,
+    /// columns with some, not all, rows free
+    pub partly_free_columns: u64,
+}
+
 extern "C" {
     pub fn starkhip_config_standard_fast(cfg: *mut starkhip_config_t);
     pub fn starkhip_config_for_air(air: Air, cfg: *mut starkhip_config_t) -> c_int;
@@ -175,6 +189,15 @@ extern "C" {
     pub fn starkhip_check_trace_report_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                               public_inputs: *const u64, per_constraint: *mut u32, row_mask: *mut u64, list: *mut u64,
                                               cap: usize, out: *mut starkhip_check_report_t) -> c_int;
+    // The cells no constraint notices when `delta` (nonzero, canonical; draw it at random) is added to them, one at a time:
+    // per_column [n_cols] or null, free_mask [n_cols][(n_rows + 63) / 64] or null (bit r & 63 of word r >> 6 of column c).
+    pub fn starkhip_check_trace_free_cells(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                           on_device: c_int, public_inputs: *const u64, delta: u64, per_column: *mut u32,
+                                           free_mask: *mut u64, out: *mut starkhip_free_cells_t) -> c_int;
+    // tests, small shapes: the same rule as host loops; `trace` is host memory
+    pub fn starkhip_check_trace_free_cells_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                                  public_inputs: *const u64, delta: u64, per_column: *mut u32, free_mask: *mut u64,
+                                                  out: *mut starkhip_free_cells_t) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

@@ -170,6 +170,40 @@ int starkhip_check_trace_report(void* ctx, starkhip_air_t air, const uint64_t* t
 int starkhip_check_trace_report_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
                                        const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
                                        starkhip_check_report_t* out);
+/* The opposite question: which cells of the trace could a prover change without any constraint noticing?  Under-constrained cells
+ * are a soundness bug that a satisfying trace never shows.  `delta` is a nonzero canonical field element.  Cell (r, c) is CAUGHT
+ * when some constraint that reads column c is nonzero on the frame the read puts the cell in, with this one cell replaced by
+ * cell + delta mod p: a read as a local cell tests frame r, a read as a next cell tests frame (r - 1) mod n, a constraint that reads
+ * c both ways tests both, each with only its own occurrence changed; and the constraint has to apply to that frame by
+ * starkhip_check_trace's rule (plain: every row, the wrap frame n - 1 included; transition: rows < n - 1; first / last: row 0 / n - 1).
+ * Every other cell is FREE: all cells of a column no constraint reads, row 0 of a column that only transition constraints read and
+ * only as `next`, a gated cell on the rows where its gate is off.  The trace itself need not satisfy the AIR: a cell is free when
+ * the constraints that read it are all zero AFTER the change; on a satisfying trace that is "the changed trace still satisfies".
+ *   per_column (n_cols entries, or NULL): the free rows of each column;
+ *   free_mask (n_cols x (n_rows + 63) / 64 words, or NULL): bit (r & 63) of word r >> 6 of column c is set when cell (r, c) is free;
+ *     bits at or beyond n_rows are zero.  It is read back from the device only when asked for (75 MB for FinalExp);
+ *   out: cells = n_rows * n_cols, free_cells, free_columns (all n_rows rows free), partly_free_columns.
+ * Two limits.  The test is NECESSARY, NOT SUFFICIENT: it changes one cell at a time and does not see a cheat that changes several
+ * cells together.  And it is PROBABILISTIC IN delta: a constrained cell reads as free for at most `degree` values of delta per
+ * (constraint, cell) pair -- the roots of the constraint as a polynomial in delta -- so draw delta at random for a real audit.
+ * trace, n_rows, n_cols, layout, on_device, public_inputs and the BAD_SHAPE cases are starkhip_check_trace's; delta == 0,
+ * delta >= p and a NULL `out` are BAD_SHAPE too.  The result is a pure function of the arguments, the same on every run.  One call at
+ * a time per context, not beside a prove on it; starkhip_check_trace, the report and their results are unchanged.  On the context's
+ * device (csrc/kernels_free_cells.hip) every constraint is re-evaluated once per cell it reads, several times the plain check's work. */
+typedef struct {
+    uint64_t cells;                /* n_rows * n_cols */
+    uint64_t free_cells;           /* cells no constraint notices */
+    uint64_t free_columns;         /* columns with all n_rows rows free */
+    uint64_t partly_free_columns;  /* columns with some, not all, rows free */
+} starkhip_free_cells_t;
+int starkhip_check_trace_free_cells(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                    int on_device, const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column,
+                                    uint64_t* free_mask, starkhip_free_cells_t* out);
+/* tests: the same rule as host loops over the program's per-constraint evaluator on changed frames, on one thread -- O(rows x
+ * (constraint, cell) pairs x constraint length): for small shapes.  `trace` is host memory.  No device needed. */
+int starkhip_check_trace_free_cells_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                           const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* free_mask,
+                                           starkhip_free_cells_t* out);
 
 /* --- natives + trace generation (host) ----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.

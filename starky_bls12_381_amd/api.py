@@ -239,6 +239,62 @@ def _check_trace_report(call, air, n_rows, cap):
     return CheckReport(summary, per, mask, entries)
 
 
+class _FreeCellsStruct(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("cells", "free_cells", "free_columns", "partly_free_columns")]
+
+
+lib.starkhip_check_trace_free_cells.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, C.c_uint64, _u32p,
+                                                _u64p, C.POINTER(_FreeCellsStruct)]
+lib.starkhip_check_trace_free_cells_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _u64p, C.c_uint64, _u32p, _u64p,
+                                                       C.POINTER(_FreeCellsStruct)]
+# The delta free_cells adds when the caller names none: fixed, so that a result can be reproduced.  A constrained cell reads as free
+# for at most `degree` values of delta per (constraint, cell) pair: a real audit should pass a random one, 1 <= delta < P.
+DEFAULT_DELTA = 0x9E3779B97F4A7C15
+
+
+class FreeCells:
+    """What starkhip_check_trace_free_cells found: the cells of a trace that no constraint notices when delta is added to them, one
+    at a time.  `cells` = rows x columns, `free` of them free; `free_columns`: columns with every row free (no constraint reads
+    them, or none that applies), `partly_free_columns`: some rows; `per_column` (np.uint32[C]): the free rows of each column; `mask`
+    (bool[n, C], or None when it was not asked for): mask[r, c] is True when cell (r, c) is free; `mask_words` (np.uint64[C, (n + 63)
+    // 64], or None): the same as the library wrote it, bit r & 63 of word r >> 6 of column c.  A necessary test, not a sufficient
+    one: it does not see a cheat that changes several cells together."""
+
+    def __init__(self, summary, per_column, words, n_rows):
+        self.cells, self.free = int(summary.cells), int(summary.free_cells)
+        self.free_columns, self.partly_free_columns = int(summary.free_columns), int(summary.partly_free_columns)
+        self.per_column, self.mask_words = per_column, words
+        self._n_rows, self._mask = n_rows, None
+
+    @property
+    def mask(self):  # unpacked on first use: eight times the words, 600 MB for FinalExp
+        if self._mask is None and self.mask_words is not None:
+            bits = np.unpackbits(self.mask_words.view(np.uint8).reshape(self.mask_words.shape[0], -1), axis=1, bitorder="little")
+            self._mask = np.ascontiguousarray(bits[:, :self._n_rows].T).astype(bool)
+        return self._mask
+
+    def __repr__(self):
+        return (f"FreeCells(cells={self.cells}, free={self.free}, free_columns={self.free_columns}, "
+                f"partly_free_columns={self.partly_free_columns})")
+
+
+def _free_cells(call, n_rows, n_cols, mask):
+    """`call(per_column, free_mask, summary)` -> rc: one of the two free-cell entry points with its leading arguments bound."""
+    per = np.zeros(n_cols, dtype=np.uint32)
+    words = np.zeros((n_cols, (n_rows + 63) // 64), dtype=np.uint64) if mask else None
+    summary = _FreeCellsStruct()
+    _chk(call(per.ctypes.data_as(_u32p), _p64(words) if mask else None, C.byref(summary)))
+    return FreeCells(summary, per, words, n_rows)
+
+
+def _free_cells_args(air, public_inputs, delta):
+    pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    delta = int(delta)
+    if pis.size != air_public_inputs(air) or not 0 <= delta < 1 << 64:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    return pis, delta
+
+
 def air_check_program(blob):
     """The validator starkhip_air_register runs: None for a program it accepts, else the reason it refuses it."""
     blob = np.ascontiguousarray(blob, dtype=np.uint64)
@@ -618,6 +674,29 @@ class Prover:
         try:
             return _check_trace_report(lambda *out: lib.starkhip_check_trace_report(self._ctx, air, trace_arg, n_rows, n_cols, layout, on_device,
                                                                                     _p64(pis), *out), air, n_rows, cap)
+        finally:
+            self.last_call_s = time.perf_counter() - t0
+
+    def free_cells(self, air, trace, public_inputs, layout=0, delta=DEFAULT_DELTA, mask=True):
+        """The cells of `trace` (as check_trace takes it) that no constraint of `air` notices when `delta` is added to them
+        (starkhip_check_trace_free_cells): a FreeCells.  mask=False leaves the per-cell bitmap on the device.  DEFAULT_DELTA is a fixed
+        constant; pass a random delta in 1 .. P - 1 for a real audit."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        if trace.ndim != 2 or layout not in (0, 1):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+        return self._free_cells(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, public_inputs, delta, mask)
+
+    def free_cells_device(self, air, trace_ptr, n_rows, public_inputs, layout=1, delta=DEFAULT_DELTA, mask=True):
+        """free_cells on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
+        return self._free_cells(air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, public_inputs, delta, mask)
+
+    def _free_cells(self, air, trace_arg, n_rows, n_cols, layout, on_device, public_inputs, delta, mask):
+        pis, delta = _free_cells_args(air, public_inputs, delta)
+        t0 = time.perf_counter()
+        try:
+            return _free_cells(lambda *out: lib.starkhip_check_trace_free_cells(self._ctx, air, trace_arg, n_rows, n_cols, layout, on_device,
+                                                                                _p64(pis), delta, *out), n_rows, n_cols, mask)
         finally:
             self.last_call_s = time.perf_counter() - t0
 
@@ -1154,6 +1233,17 @@ def check_trace_report_replay(air, trace, public_inputs, layout=0, cap=1024):
         raise StarkhipError(ERR_BAD_SHAPE)
     return _check_trace_report(lambda *out: lib.starkhip_check_trace_report_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout,
                                                                                    _p64(pis), *out), air, n_rows, cap)
+
+
+def free_cells_replay(air, trace, public_inputs, layout=0, delta=DEFAULT_DELTA, mask=True):
+    """starkhip_check_trace_free_cells_replay (tests, small shapes): Prover.free_cells' rule as host loops; no device needed."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    pis, delta = _free_cells_args(air, public_inputs, delta)
+    return _free_cells(lambda *out: lib.starkhip_check_trace_free_cells_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout,
+                                                                               _p64(pis), delta, *out), n_rows, n_cols, mask)
 
 
 def trace_rows_to_poly_values(trace_rows):

@@ -22,5 +22,7 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
 
 // mask-free value G * body of constraint k (0 <= k < n_constraints) on one frame: what oracle_check_trace compares with zero
 gl_t air_constraint_value(const AirProgram& P, uint32_t k, const gl_t* local, const gl_t* next, const gl_t* pis);
+// the same for a caller that knows where the constraint is: the code words of its group and of its own first term
+gl_t air_constraint_value_at(const AirProgram& P, uint32_t group_word, uint32_t term_word, const gl_t* local, const gl_t* next, const gl_t* pis);
 
 }  // namespace starkhip

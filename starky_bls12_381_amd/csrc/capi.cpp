@@ -13,6 +13,7 @@
 #include "airs.h"
 #include "blob_arena.h"
 #include "check_report.h"
+#include "free_cells.h"
 #include "kernels.h"
 #include "lde_ranges.h"
 #include "trace_log.h"
@@ -188,6 +189,44 @@ int starkhip_check_trace_report_replay(starkhip_air_t air, const uint64_t* trace
     if (int rc = check_report_args(a, trace, n_cols, layout, public_inputs, list, cap, out)) return rc;
     try {
         return check_trace_report_replay(*a, trace, n_rows, layout, public_inputs, per_constraint, row_mask, list, cap, out);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    } catch (const std::exception&) {
+        return STARKHIP_ERR_BAD_SHAPE;
+    }
+}
+
+// what both free-cell entry points refuse before they look at the trace
+static int free_cells_args(const AirInfo* a, const uint64_t* trace, size_t n_cols, int layout, const uint64_t* public_inputs, uint64_t delta,
+                           starkhip_free_cells_t* out) {
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    if (!trace || !out || (a->pis && !public_inputs) || (layout != 0 && layout != 1) || n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;
+    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    return STARKHIP_OK;
+}
+
+int starkhip_check_trace_free_cells(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                                    const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* free_mask,
+                                    starkhip_free_cells_t* out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    if (int rc = free_cells_args(a, trace, n_cols, layout, public_inputs, delta, out)) return rc;
+    try {
+        return check_trace_free_cells((Ctx*)ctx, *a, trace, n_rows, layout, on_device, public_inputs, delta, per_column, free_mask, out);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    } catch (const std::exception&) {
+        return STARKHIP_ERR_BAD_SHAPE;
+    }
+}
+
+int starkhip_check_trace_free_cells_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                           const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* free_mask,
+                                           starkhip_free_cells_t* out) {
+    const AirInfo* a = air_get(air);
+    if (int rc = free_cells_args(a, trace, n_cols, layout, public_inputs, delta, out)) return rc;
+    try {
+        return check_trace_free_cells_replay(*a, trace, n_rows, layout, public_inputs, delta, per_column, free_mask, out);
     } catch (const std::bad_alloc&) {
         return STARKHIP_ERR_OOM;
     } catch (const std::exception&) {

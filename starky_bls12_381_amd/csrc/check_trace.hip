@@ -1,6 +1,6 @@
-// Host halves of the two trace checkers: starkhip_check_trace and starkhip_check_trace_report (the latter under check_report.h);
-// their kernels are in kernels_check.hip.  What they share is check_trace_prepare: the shape checks, the cached op stream of the
-// AIR (Ctx::CheckProgram), the trace and the public inputs on the device -- together the CheckView the kernels read.
+// Host halves of the trace checkers: starkhip_check_trace, starkhip_check_trace_report (under check_report.h; kernels_check.hip) and
+// starkhip_check_trace_free_cells (free_cells.h; kernels_free_cells.hip).  What they share is check_trace_prepare: the shape checks, the
+// cached op stream of the AIR (Ctx::CheckProgram), the trace and the public inputs on the device -- the CheckView the kernels read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include "air_validate.h"
 #include "check_report.h"
 #include "ctx.h"
+#include "free_cells.h"
 #include "quotient_ops.h"
 
 namespace starkhip {
@@ -144,6 +145,43 @@ int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t
     if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &V)) return rc;
     DevicePasses passes(c, air.prog, V);
     return check_report_run(air.prog, n_rows, passes, per_constraint, row_mask, list, cap, out);
+}
+
+// starkhip_check_trace_free_cells: the audit kernel of kernels_free_cells.hip over the view the checkers share, then the count per
+// column.  One launch each: a FinalExp audit stays far below a second.  The bitmap comes back only when asked for.
+int check_trace_free_cells(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
+                           uint64_t delta, uint32_t* per_column, uint64_t* free_mask, starkhip_free_cells_t* out) {
+    const AirProgram& P = air.prog;
+    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    CheckView V = {};
+    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &V)) return rc;
+    const size_t n = n_rows, C = P.n_cols, W = (n + 63) / 64;
+    hipStream_t st = c->st;
+    Ctx::FreeCellsProgram& fc = c->free_chk;
+    if (fc.air != air.id || fc.want != c->chk.want) {  // op indices of the stream check_trace_prepare cached: the same cut gives the same ones
+        fc.air = -1;
+        const FreeProgram F = compile_free_cells(compile_quotient_ops(P, c->chk.want));
+        if (F.cons.size() != P.n_constraints) return STARKHIP_ERR_HIP;
+        HIPCHK(fc.cons.ensure(F.cons.size() * sizeof(FreeCon)));
+        HIPCHK(fc.pivots.ensure(std::max<size_t>(1, F.pivots.size()) * 4));
+        HIPCHK(hipMemcpyAsync(fc.cons.p, F.cons.data(), F.cons.size() * sizeof(FreeCon), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(fc.pivots.p, F.pivots.data(), F.pivots.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(stream_wait(c));  // F goes out of scope
+        fc.air = air.id;
+        fc.want = c->chk.want;
+    }
+    HIPCHK(fc.words.ensure(C * W * 8));
+    HIPCHK(fc.per_column.ensure(C * 4));
+    HIPCHK(hipMemsetAsync(fc.words.p, 0, C * W * 8, st));
+    HIPCHK(launch_free_cells(V, fc.cons.as<FreeCon>(), fc.pivots.as<uint32_t>(), P.n_constraints, delta, fc.words.as<unsigned long long>(), st));
+    HIPCHK(launch_free_cells_count(fc.words.as<unsigned long long>(), (uint32_t)C, V.log_n, fc.per_column.as<uint32_t>(), st));
+    std::vector<uint32_t> per(C);
+    HIPCHK(hipMemcpyAsync(per.data(), fc.per_column.p, C * 4, hipMemcpyDeviceToHost, st));
+    if (free_mask) HIPCHK(hipMemcpyAsync(free_mask, fc.words.p, C * W * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(c));
+    if (per_column) std::copy(per.begin(), per.end(), per_column);
+    *out = free_cells_summary(per.data(), n, C);
+    return STARKHIP_OK;
 }
 
 }  // namespace starkhip

@@ -160,12 +160,21 @@ struct Ctx {
         for (DevBuf& b : fri_digests) v.push_back(&b);
         for (DevBuf* b : prog.bufs()) v.push_back(b);
         for (DevBuf* b : chk.bufs()) v.push_back(b);
+        for (DevBuf* b : free_chk.bufs()) v.push_back(b);
         for (auto& t : table_cache)
             for (DevBuf* b : t->bufs()) v.push_back(b);
         for (auto& d : plan_cache)
             for (DevBuf* b : d->bufs()) v.push_back(b);
         return v;
     }
+    // free-cell audit (starkhip_check_trace_free_cells): compile_free_cells of the op stream in `chk` -- same AIR, same `want` -- and
+    // the results: the bitmap [C][(n + 63) / 64] and the free rows of each column.  Last, so that the work buffers stay where they were.
+    struct FreeCellsProgram {
+        int air = -1;
+        unsigned want = 0;
+        DevBuf cons, pivots, words, per_column;
+        std::vector<DevBuf*> bufs() { return {&cons, &pivots, &words, &per_column}; }
+    } free_chk;
 };
 
 // ---- ctx.hip

@@ -1,0 +1,114 @@
+// starkhip_check_trace_free_cells' host half (free_cells.h): the compiled form the kernel walks, the summary, and the replay
+// without a device.
+#include "free_cells.h"
+
+#include <algorithm>
+
+#include "air_validate.h"
+#include "check_report.h"
+
+namespace starkhip {
+
+static const uint32_t PIVOT_KEY = REF_COL_MASK | REF_NEXT;
+
+static void add_pivot(std::vector<uint32_t>& pivots, size_t first, uint32_t ref) {
+    const uint32_t key = ref & PIVOT_KEY;
+    if (std::find(pivots.begin() + first, pivots.end(), key) == pivots.end()) pivots.push_back(key);
+}
+
+FreeProgram compile_free_cells(const QProgram& Q) {
+    FreeProgram F;
+    uint32_t g0 = 0, g1 = 0, t0 = 0, kind = 0;
+    const uint32_t n_ops = Q.chunk_batch.back() * QOP_BATCH;  // what follows are guard batches
+    for (uint32_t i = 0; i < n_ops; i++) {
+        const uint32_t hdr = Q.ops[i].hdr, op = hdr & 7u;
+        if (op == QOP_GROUP) {
+            g0 = i;
+            kind = (hdr >> QOP_KIND_SHIFT) & 3u;
+            g1 = i + 1;
+            while ((Q.ops[g1].hdr & 7u) == QOP_GATE) g1++;
+            t0 = g1;
+            i = g1 - 1;
+            continue;
+        }
+        if (op != QOP_TERM || !(hdr & QOP_FOLD)) continue;
+        FreeCon c = {g0, g1, t0, i + 1, (uint32_t)F.pivots.size(), 0, kind, 0};
+        for (uint32_t j = g0 + 1; j < g1; j++) add_pivot(F.pivots, c.piv0, Q.ops[j].ref);
+        for (uint32_t j = t0; j <= i; j++)
+            if (!(Q.ops[j].hdr & QOP_NOCELL)) add_pivot(F.pivots, c.piv0, Q.ops[j].ref);
+        c.piv1 = (uint32_t)F.pivots.size();
+        F.cons.push_back(c);
+        t0 = i + 1;
+    }
+    return F;
+}
+
+starkhip_free_cells_t free_cells_summary(const uint32_t* per_column, size_t n_rows, size_t n_cols) {
+    starkhip_free_cells_t s = {(uint64_t)n_rows * n_cols, 0, 0, 0};
+    for (size_t c = 0; c < n_cols; c++) {
+        s.free_cells += per_column[c];
+        s.free_columns += per_column[c] == n_rows;
+        s.partly_free_columns += per_column[c] != 0 && per_column[c] != n_rows;
+    }
+    return s;
+}
+
+int check_trace_free_cells_replay(const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, const uint64_t* pis, uint64_t delta,
+                                  uint32_t* per_column, uint64_t* free_mask, starkhip_free_cells_t* out) {
+    unsigned log_n = 0;
+    if (int rc = check_trace_shape(air, n_rows, pis, &log_n)) return rc;
+    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    const AirProgram& P = air.prog;
+    const size_t n = n_rows, C = P.n_cols, W = (n + 63) / 64;
+    std::vector<uint64_t> rows(n * C);  // row-major, and ours to change: a cell is raised in place, evaluated and put back
+    for (size_t r = 0; r < n; r++)
+        for (size_t c = 0; c < C; c++) rows[r * C + c] = layout == 1 ? trace[c * n + r] : trace[r * C + c];
+    std::vector<uint64_t> caught(C * W, 0);
+    AirReader rd(P);
+    GroupWord grp;
+    std::vector<uint32_t> pivots;
+    for (size_t g = 0; rd.group(&grp); g++) {
+        const uint32_t group_word = P.group_off[g];
+        std::vector<uint32_t> gates(grp.n_gates);
+        for (uint32_t& ref : gates) ref = rd.ref();
+        for (uint32_t j = 0; j < grp.m; j++) {
+            const uint32_t term_word = (uint32_t)(rd.w - P.code.data());
+            pivots.clear();
+            for (uint32_t ref : gates) add_pivot(pivots, 0, ref);
+            TermWord tw;
+            do {
+                tw = rd.term();
+                for (uint32_t f = 0; f < tw.nf; f++) add_pivot(pivots, 0, rd.ref());
+            } while (!tw.last);
+            for (uint32_t piv : pivots) {
+                const size_t col = piv & REF_COL_MASK;
+                for (size_t r = 0; r < n; r++) {
+                    const size_t frame = (piv & REF_NEXT) ? (r + n - 1) % n : r;
+                    if (!constraint_applies<size_t>(grp.kind, frame, n)) continue;
+                    uint64_t& cell = rows[r * C + col];
+                    const uint64_t kept = cell;
+                    cell = gl_add(kept, delta);
+                    const gl_t v = air_constraint_value_at(P, group_word, term_word, &rows[frame * C], &rows[(frame + 1) % n * C], pis);
+                    cell = kept;
+                    if (v != 0) caught[col * W + (r >> 6)] |= 1ull << (r & 63);
+                }
+            }
+        }
+    }
+    std::vector<uint32_t> per(C);
+    for (size_t c = 0; c < C; c++) {
+        size_t set = 0;
+        for (size_t w = 0; w < W; w++) {
+            const uint64_t all = n - w * 64 >= 64 ? ~0ull : (1ull << (n - w * 64)) - 1;
+            const uint64_t free_w = ~caught[c * W + w] & all;
+            if (free_mask) free_mask[c * W + w] = free_w;
+            set += (size_t)__builtin_popcountll(free_w);
+        }
+        per[c] = (uint32_t)set;
+    }
+    if (per_column) std::copy(per.begin(), per.end(), per_column);
+    *out = free_cells_summary(per.data(), n, C);
+    return STARKHIP_OK;
+}
+
+}  // namespace starkhip

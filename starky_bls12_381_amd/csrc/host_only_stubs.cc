@@ -111,6 +111,9 @@ int check_trace(Ctx*, const AirInfo&, const uint64_t*, size_t, int, int, const u
 int check_trace_report(Ctx*, const AirInfo&, const uint64_t*, size_t, int, int, const uint64_t*, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_check_report_t*) {
     return STARKHIP_ERR_NO_DEVICE;
 }
+int check_trace_free_cells(Ctx*, const AirInfo&, const uint64_t*, size_t, int, int, const uint64_t*, uint64_t, uint32_t*, uint64_t*, starkhip_free_cells_t*) {
+    return STARKHIP_ERR_NO_DEVICE;
+}
 int lde_bench(Ctx*, size_t, unsigned, unsigned, unsigned, unsigned, const uint64_t*, float*, float*) { return STARKHIP_ERR_NO_DEVICE; }
 int field_ops(Ctx*, int, const uint64_t*, const uint64_t*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int host_alloc(Ctx*, size_t, void**) { return STARKHIP_ERR_NO_DEVICE; }

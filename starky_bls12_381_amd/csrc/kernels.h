@@ -145,6 +145,14 @@ hipError_t launch_check_report_count(const CheckView& v, uint32_t* counts, unsig
 hipError_t launch_check_report_list(const CheckView& v, const uint32_t* chunks, unsigned n_launched, uint32_t* cursors, const unsigned long long* row_mask,
                                     const uint32_t* base, unsigned long long* list, uint32_t list_len, hipStream_t st);
 
+// kernels_free_cells.hip: the free-cell audit (starkhip_check_trace_free_cells) over the same view.  caught[c][blockIdx.x] |= the rows
+// of the wave whose cell of column c some constraint notices when delta is added to it (zeroed by the caller); `cons` and `pivots` are
+// compile_free_cells' (free_cells.h).  The count turns the caught words into free words in place and sets per_column[c] to their bits.
+struct FreeCon;
+hipError_t launch_free_cells(const CheckView& v, const FreeCon* cons, const uint32_t* pivots, uint32_t n_constraints, gl_t delta,
+                             unsigned long long* caught, hipStream_t st);
+hipError_t launch_free_cells_count(unsigned long long* words, uint32_t n_cols, unsigned log_n, uint32_t* per_column, hipStream_t st);
+
 // kernels_fri.hip
 hipError_t launch_ext_powers(gl2_t* out, gl2_t base, size_t count, hipStream_t st);
 // weights of the evaluation at z (and, rotated by one, at w_n z) from values on coset 0 of the LDE; scale = (z^n - 7^n) / (n 7^n)

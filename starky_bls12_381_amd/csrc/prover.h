@@ -83,6 +83,9 @@ int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows
 // starkhip_check_trace_report: the same check with per-constraint counts, the rows and a list (kernels_check.hip, check_report.h)
 int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
                        uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out);
+// starkhip_check_trace_free_cells: the cells no constraint notices when delta is added to them (kernels_free_cells.hip, free_cells.h)
+int check_trace_free_cells(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
+                           uint64_t delta, uint32_t* per_column, uint64_t* free_mask, starkhip_free_cells_t* out);
 int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out);
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);

@@ -4,7 +4,13 @@ and the proof time of one mid-sized random AIR (300 columns, 4096 rows).  Prints
 
 --report: times starkhip_check_trace_report instead, on the same trace in column-major device memory: the plain check (for the ratio),
 the report on the clean trace (its first pass alone) and the report with cap = 1024 after every cell of row 4000 was raised by one
-(both passes).  Best and median of five after a warm-up call; one JSON line."""
+(both passes).  Best and median of five after a warm-up call; one JSON line.
+
+--free-cells [OUT_DIR]: times starkhip_check_trace_free_cells (Prover.free_cells_device) on the same trace in column-major device
+memory, with and without the read-back of the per-cell bitmap, beside the plain check for the ratio; one warm-up call, best and
+median of five, call times from Python.  Then audits one real trace of each built-in AIR and records cells, free cells, wholly and
+partly free columns and the indices of the wholly free columns.  Prints the two results as JSON lines and, with OUT_DIR, writes
+them to OUT_DIR/free_cells_final_exp.json and OUT_DIR/free_cells_builtin_airs.json."""
 import ctypes as C
 import json
 import os
@@ -66,9 +72,71 @@ def report_mode():
     print(json.dumps(out))
 
 
+def builtin_traces():
+    """(name, AIR, generator of (row-major trace, public inputs)) for one real trace of each built-in AIR, the ones the tests prove."""
+    from bls_util import random_fp12
+    from test_ecc_aggregate_cpu import pack, reference_vector
+    b = {k: int(s) for k, s in native_vectors()["bls_signature"].items()}
+    hm = (fp_arr(b["hm_x1"], b["hm_x2"]), fp_arr(b["hm_y1"], b["hm_y2"]), fp_arr(b["hm_z1"], b["hm_z2"]))
+    sig = (fp_arr(b["gx"]), fp_arr(b["gy"]), fp_arr(b["s_x1"], b["s_x2"]), fp_arr(b["s_y1"], b["s_y2"]), fp_arr(b["s_z1"], b["s_z2"]))
+    pts, bits, _ = reference_vector()
+    return [("FP12Mul", S.AIR_FP12_MUL, lambda: S.trace_fp12_mul(random_fp12(0x5EED7200), random_fp12(0x5EED7201))),
+            ("PairingPrecomp", S.AIR_PAIRING_PRECOMP, lambda: S.trace_pairing_precomp(*hm)),
+            ("MillerLoop", S.AIR_MILLER_LOOP, lambda: S.trace_miller_loop(*sig)),
+            ("ECCAgg", S.AIR_ECC_AGGREGATE, lambda: S.trace_ecc_aggregate(*pack(pts, bits))),
+            ("FinalExp", S.AIR_FINAL_EXP, lambda: S.trace_final_exp(fp_arr(*[int(s) for s in native_vectors()["final_exp_input_aa"]])))]
+
+
+def free_cells_mode(out_dir):
+    torch.cuda.set_device(0)
+    pv = S.Prover(0)
+    timing, audit = {"delta": hex(S.DEFAULT_DELTA), "times": "call times from Python, ms"}, {"delta": hex(S.DEFAULT_DELTA), "airs": {}}
+    for name, air, make in builtin_traces():
+        t, pis = make()
+        n = t.shape[0]
+        cols = torch.from_numpy(np.ascontiguousarray(t.T).view(np.int64)).to("cuda:0")
+        del t
+        torch.cuda.synchronize()
+        assert pv.check_trace_device(air, cols.data_ptr(), n, pis, layout=1)[0] == 0  # also the warm-up of the plain check
+        fc = pv.free_cells_device(air, cols.data_ptr(), n, pis, layout=1, mask=False)  # warm-up: compiled form, buffers
+        first_ms = pv.last_call_s * 1e3
+        audit["airs"][name] = {"rows": n, "columns": int(fc.per_column.size), "cells": fc.cells, "free_cells": fc.free, "free_columns": fc.free_columns,
+                               "partly_free_columns": fc.partly_free_columns, "first_call_ms": first_ms,
+                               "wholly_free_column_indices": np.flatnonzero(fc.per_column == n).tolist()}
+        if air == S.AIR_FINAL_EXP:
+            mn, md, _ = best(lambda: pv.check_trace_device(air, cols.data_ptr(), n, pis, layout=1), 5)
+            timing["check_trace_clean_ms"] = {"min": mn, "median": md}
+            mn, md, again = best(lambda: pv.free_cells_device(air, cols.data_ptr(), n, pis, layout=1, mask=False), 5)
+            timing["free_cells_no_mask_ms"] = {"min": mn, "median": md}
+            assert np.array_equal(again.per_column, fc.per_column)
+            pv.free_cells_device(air, cols.data_ptr(), n, pis, layout=1, mask=True)
+            mn, md, full = best(lambda: pv.free_cells_device(air, cols.data_ptr(), n, pis, layout=1, mask=True), 5)
+            timing["free_cells_with_mask_ms"] = {"min": mn, "median": md}
+            ones = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint8)  # the bitmap's bits per column, without unpacking it
+            assert np.array_equal(full.per_column, fc.per_column)
+            assert np.array_equal(ones[full.mask_words.view(np.uint8)].reshape(fc.per_column.size, -1).sum(axis=1), fc.per_column)
+            timing["mask_bytes"] = int(full.mask_words.nbytes)
+            timing["no_mask_over_check_trace"] = timing["free_cells_no_mask_ms"]["min"] / timing["check_trace_clean_ms"]["min"]
+            timing["with_mask_over_check_trace"] = timing["free_cells_with_mask_ms"]["min"] / timing["check_trace_clean_ms"]["min"]
+            timing["op_evaluations_over_check_trace"] = 17459006 / 1932601  # counted from the program: re-walks against the plain walk
+            timing["first_call_ms"] = first_ms
+        del cols
+    pv.close()
+    for fname, obj in (("free_cells_final_exp.json", timing), ("free_cells_builtin_airs.json", audit)):
+        print(json.dumps(obj))
+        if out_dir:
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, fname), "w") as f:
+                json.dump(obj, f, indent=1)
+                f.write("\n")
+
+
 def main():
     if "--report" in sys.argv[1:]:
         return report_mode()
+    if "--free-cells" in sys.argv[1:]:
+        rest = sys.argv[sys.argv.index("--free-cells") + 1:]
+        return free_cells_mode(rest[0] if rest else None)
     torch.cuda.set_device(0)
     out = {}
     pv = S.Prover(0)
