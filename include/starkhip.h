@@ -22,7 +22,9 @@
  *
  * Because `S: Stark` is a compile-time generic in the reference, the AIR is selected by id.
  * All field elements are canonical Goldilocks values (< 2^64 - 2^32 + 1) in little-endian
- * uint64_t.  Fp elements are 12 little-endian u32 limbs (src/fp.rs:1).
+ * uint64_t -- every word the library writes, and every public input, program constant, `delta` and proof word it is given
+ * (anything else there is STARKHIP_ERR_BAD_SHAPE, or a rejected proof).  The one exception is the CELLS OF A TRACE: see starkhip_prove.
+ * Fp elements are 12 little-endian u32 limbs (src/fp.rs:1).
  *
  * Threading: one in-flight prove per context; different contexts (GPUs) may run concurrently.
  * Ownership: the caller owns every input for the duration of the call; buffers returned through
@@ -138,8 +140,10 @@ int starkhip_air_register(const uint64_t* blob, size_t words, const char* name, 
  * transition constraints on rows < n - 1, first-row ones on row 0, last-row ones on row n - 1 -- oracle_check_trace's rule.
  * *violations = the (row, constraint) pairs whose value is nonzero; first = {constraint, row, value} of the lowest violated constraint
  * and, of its rows, the lowest (all zero when there is none).  trace, n_rows, n_cols, layout, on_device and public_inputs (the AIR's
- * count) as starkhip_prove takes them; one call at a time per context, not beside a prove on it.  The constraints are evaluated on the
- * context's device (csrc/kernels_check.hip); a value is recomputed on the host from the one frame. */
+ * count) as starkhip_prove takes them -- a cell is any 64-bit word of its class mod p, and the answer is the one for the trace reduced
+ * mod p, here, in the report and in the free-cell audit below (their host replays included) -- one call at a time per context, not
+ * beside a prove on it.  The constraints are evaluated on the context's device (csrc/kernels_check.hip), which reduces every cell
+ * as it loads it; a value is recomputed on the host from the one frame. */
 int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
                          const uint64_t* public_inputs, uint64_t* violations, uint64_t first[3]);
 /* The same check, reported in full: which constraints fail, on which rows, and the values of the first of them.  The rule, trace,
@@ -237,15 +241,21 @@ void starkhip_shutdown(void* ctx);
  * 2 <= n_rows <= 2^STARKHIP_MAX_LOG_ROWS for a registered one (from 2^14 rows on a column is transformed by several workgroups in two
  * passes: csrc/kernels_lde_long.hip),
  * n_pis and n_cols as the AIR declares (n_cols is checked before the buffer is touched: it is read as n_rows x n_cols words), num_challenges = 2, and rate_bits large enough for the AIR's
- * constraint degree (2^rate_bits >= degree - 1); anything else is STARKHIP_ERR_BAD_SHAPE before any GPU work. */
+ * constraint degree (2^rate_bits >= degree - 1); anything else is STARKHIP_ERR_BAD_SHAPE before any GPU work.
+ * Trace cells: a 64-bit word w of the trace is read as the field element w mod p, so p .. 2^64 - 1 are accepted as second
+ * representatives of 0 .. 2^32 - 2 (plonky2's GoldilocksField keeps such words in memory).  This holds for every entry that reads a
+ * trace -- this one, starkhip_prove_columns, the pools' submits, starkhip_check_trace, its report and the free-cell audit, on host
+ * or device memory, in either layout -- and every result (proof bytes, counts, `first`, lists and their values, masks) is what the same
+ * call returns for the trace reduced mod p.  The caller's buffer is only read.  (A refusal would cost a pass over 4.8 GB of a
+ * device-resident FinalExp trace, after the point where bad shapes are refused; tests/test_gpu_noncanonical_cells.py.) */
 int starkhip_prove(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols,
                    int trace_layout, int trace_on_device, const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness,
                    uint64_t** proof, size_t* proof_words);
 
 /* The same proof from the LITERAL argument of starky's prove(): `trace_poly_values: Vec<PolynomialValues<F>>`
  * (src/aggregate_proof.rs:57-65, :104-111, :137-144, :168-175) is one heap allocation per column -- 73 527 of them for FinalExp.
- * `columns` is a table of n_cols host pointers, each to n_rows canonical words (PolynomialValues<GoldilocksField>::values; the field
- * type is repr(transparent) over u64).  The library gathers the scattered columns through the context's page-locked staging, half
+ * `columns` is a table of n_cols host pointers, each to n_rows words, canonical or not: read mod p, as starkhip_prove reads its
+ * trace (PolynomialValues<GoldilocksField>::values; the field type is repr(transparent) over u64, and its words may be >= p).  The library gathers the scattered columns through the context's page-locked staging, half
  * by half under the copies, so a binding at prove() itself needs no 4.8 GB host-side repack.  Byte-identical to starkhip_prove on
  * the same matrix; shapes and errors as starkhip_prove (a NULL column pointer: STARKHIP_ERR_BAD_SHAPE). */
 int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* const* columns, size_t n_rows, size_t n_cols,

@@ -14,6 +14,7 @@ struct ExtOps {
     static T zero() { return gl2_zero(); }
     static T one() { return gl2_one(); }
     static T from_base(gl_t x) { return gl2_from_base(x); }
+    static T canon(T x) { return gl2_make(gl_from_u64(x.a0), gl_from_u64(x.a1)); }
     static T add(T a, T b) { return gl2_add(a, b); }
     static T sub(T a, T b) { return gl2_sub(a, b); }
     static T mul(T a, T b) { return gl2_mul(a, b); }
@@ -26,6 +27,7 @@ struct BaseOps {
     static T zero() { return 0; }
     static T one() { return 1; }
     static T from_base(gl_t x) { return x; }
+    static T canon(T x) { return gl_from_u64(x); }
     static T add(T a, T b) { return gl_add(a, b); }
     static T sub(T a, T b) { return gl_sub(a, b); }
     static T mul(T a, T b) { return gl_mul(a, b); }
@@ -40,7 +42,8 @@ void air_eval_folded(const AirProgram& p, const typename O::T* local, const type
     AirReader rd(p);
     for (int j = 0; j < n_alpha; j++) acc[j] = O::zero();
     std::vector<T> t(n_alpha), apow(n_alpha);
-    auto cell = [&](uint32_t ref) { return ((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]; };
+    // a cell is any 64-bit word of its class mod p (starkhip.h, starkhip_prove): add and sub need canonical operands
+    auto cell = [&](uint32_t ref) { return O::canon(((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]); };
     GroupWord grp;
     while (rd.group(&grp)) {
         T G = masks[grp.kind];

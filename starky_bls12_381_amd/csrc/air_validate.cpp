@@ -107,7 +107,7 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
 }
 
 gl_t air_constraint_value_at(const AirProgram& P, uint32_t group_word, uint32_t term_word, const gl_t* local, const gl_t* next, const gl_t* pis) {
-    auto cell = [&](uint32_t ref) { return ((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]; };
+    auto cell = [&](uint32_t ref) { return gl_from_u64(((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]); };  // any word of the class mod p
     AirReader rd(P, group_word);
     GroupWord grp;
     rd.group(&grp);

@@ -87,7 +87,7 @@ int check_trace_free_cells_replay(const AirInfo& air, const uint64_t* trace, siz
                     if (!constraint_applies<size_t>(grp.kind, frame, n)) continue;
                     uint64_t& cell = rows[r * C + col];
                     const uint64_t kept = cell;
-                    cell = gl_add(kept, delta);
+                    cell = gl_add(gl_from_u64(kept), delta);  // the cell is any word of its class mod p
                     const gl_t v = air_constraint_value_at(P, group_word, term_word, &rows[frame * C], &rows[(frame + 1) % n * C], pis);
                     cell = kept;
                     if (v != 0) caught[col * W + (r >> 6)] |= 1ull << (r & 63);

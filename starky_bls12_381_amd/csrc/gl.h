@@ -3,7 +3,9 @@
 //
 // Semantics follow plonky2_field 0.1.1 GoldilocksField / QuadraticExtension as used
 // by the reference at /root/reference/src/aggregate_proof.rs:235-237 (F, D = 2);
-// SURVEY.md App. A.1.  All values stored by this library are canonical (< p).
+// SURVEY.md App. A.1.  All values STORED by this library are canonical (< p); of the values it READS, the cells of a caller's trace may
+// be any 64-bit word of their class (starkhip.h, starkhip_prove).  gl_sub and gl_neg below take canonical operands only: code that reads a
+// trace cell reduces it first (gl_from_u64), or hands it to gl_mul, which reduces any operands, or to gl_add as one of the two.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -25,10 +27,12 @@ typedef uint64_t gl_t;
 #define GL_POWER_OF_TWO_GENERATOR 1753635133440165772ULL
 #define GL_TWO_ADICITY 32
 
+// a canonical, b ANY 64-bit word (or the other way round): the canonical a + b mod p.  gl_sub and gl_neg need canonical operands.
 GL_HD gl_t gl_add(gl_t a, gl_t b) {
-    // a, b < p  =>  a + b < 2p < 2^65
+    // a < p, b < 2^64  =>  a + b < 2^64 + p.  No carry: s < 2^64, and one subtraction of p leaves s - p < 2^32.  Carry: the wrapped
+    // s = a + b - 2^64 <= p - 2, so s + eps <= 2^64 - 2 does not wrap again, and one subtraction of p at most is left to do.
     gl_t s = a + b;
-    // if carry: true sum = s + 2^64 = s + eps (mod p), and s < p - 1 so no second wrap.
+    // if carry: true sum = s + 2^64 = s + eps (mod p)
     // Written with masks: on the host these are data-dependent and a branch would mispredict half the time.
     s += (gl_t)(0 - (gl_t)(s < a)) & GL_EPS;
     s -= (gl_t)(0 - (gl_t)(s >= GL_P)) & GL_P;

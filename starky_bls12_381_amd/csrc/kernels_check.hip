@@ -57,20 +57,24 @@ __device__ __forceinline__ void walk_chunk(const CheckView& V, uint32_t chunk, A
             continue;
         }
         if (op != QOP_GATE && op != QOP_FACTOR && op != QOP_TERM) continue;  // NOP padding, ENDGROUP
+        // A cell is ANY 64-bit word of its class mod p (starkhip.h, starkhip_prove), and x, v and u below may be one.  gl_mul reduces
+        // any operands and gl_add takes one of them raw (gl.h); a subtrahend has to be canonical, so the two places a raw word could be
+        // one reduce it first -- a wave-uniform choice, nothing per load (a reduction at the load cost 3.5 % of a FinalExp check).
         gl_t x = 1;
         if (!(hdr & QOP_NOCELL)) x = V.trace[((size_t)(ref & REF_COL_MASK) << V.log_n) + ((ref & REF_NEXT) ? rn : r)];  // 64-bit: 4.8 GB
         if (op == QOP_GATE) {
-            G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, x) : x);
+            G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, gl_from_u64(x)) : x);
             continue;
         }
+        const bool prev = (hdr & QOP_PREV) != 0;
         if (op == QOP_FACTOR) {
-            v = (hdr & QOP_PREV) ? gl_mul(v, x) : x;
+            v = prev ? gl_mul(v, x) : x;
             continue;
         }
-        const gl_t u = (hdr & QOP_PREV) ? gl_mul(v, x) : x;  // NOCELL: x = 1
+        const gl_t u = prev ? gl_mul(v, x) : x;  // NOCELL: x = 1
         const uint32_t ck = (hdr >> QOP_CK_SHIFT) & 7u;
         if (ck == CK_PLUS) body = gl_add(body, u);
-        else if (ck == CK_MINUS) body = gl_sub(body, u);
+        else if (ck == CK_MINUS) body = gl_sub(body, prev ? u : gl_from_u64(u));
         else if (ck == CK_CONST) body = gl_add(body, gl_mul(u, V.ops[i].k));
         else if (ck == CK_PI) body = gl_add(body, gl_mul(u, V.pis[hdr >> QOP_IDX_SHIFT]));
         else body = gl_sub(body, gl_mul(u, V.pis[hdr >> QOP_IDX_SHIFT]));

@@ -64,27 +64,29 @@ __global__ __launch_bounds__(64) void free_cells_kernel(FreeCellsParams P) { STA
             if ((have & all) == all) continue;  // wave-uniform
             const bool next_pivot = (piv & REF_NEXT) != 0;
             const uint32_t r_local = next_pivot ? rp : rc, r_next = next_pivot ? rc : rn;
+            // a cell is any 64-bit word of its class mod p, reduced where walk_chunk reduces it: as a subtrahend (gl_add takes it raw)
             auto cell = [&](uint32_t ref) {
                 const gl_t x = V.trace[((size_t)(ref & REF_COL_MASK) << V.log_n) + ((ref & REF_NEXT) ? r_next : r_local)];
-                return (ref & (REF_COL_MASK | REF_NEXT)) == piv ? gl_add(x, P.delta) : x;
+                return (ref & (REF_COL_MASK | REF_NEXT)) == piv ? gl_add(P.delta, x) : x;
             };
             gl_t G = 1, body = 0, v = 1;
             for (uint32_t i = cn.g0 + 1; i < cn.g1; i++) {  // the gates; op g0 is the GROUP
                 const uint32_t ref = V.ops[i].ref;
                 const gl_t x = cell(ref);
-                G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, x) : x);
+                G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, gl_from_u64(x)) : x);
             }
             for (uint32_t i = cn.t0; i < cn.t1; i++) {  // FACTOR and TERM ops alone: as walk_chunk evaluates them
                 const uint32_t hdr = V.ops[i].hdr, ref = V.ops[i].ref;
                 const gl_t x = (hdr & QOP_NOCELL) ? 1 : cell(ref);
+                const bool prev = (hdr & QOP_PREV) != 0;
                 if ((hdr & 7u) == QOP_FACTOR) {
-                    v = (hdr & QOP_PREV) ? gl_mul(v, x) : x;
+                    v = prev ? gl_mul(v, x) : x;
                     continue;
                 }
-                const gl_t u = (hdr & QOP_PREV) ? gl_mul(v, x) : x;
+                const gl_t u = prev ? gl_mul(v, x) : x;
                 const uint32_t ck = (hdr >> QOP_CK_SHIFT) & 7u;
                 if (ck == CK_PLUS) body = gl_add(body, u);
-                else if (ck == CK_MINUS) body = gl_sub(body, u);
+                else if (ck == CK_MINUS) body = gl_sub(body, prev ? u : gl_from_u64(u));
                 else if (ck == CK_CONST) body = gl_add(body, gl_mul(u, V.ops[i].k));
                 else if (ck == CK_PI) body = gl_add(body, gl_mul(u, V.pis[hdr >> QOP_IDX_SHIFT]));
                 else body = gl_sub(body, gl_mul(u, V.pis[hdr >> QOP_IDX_SHIFT]));
