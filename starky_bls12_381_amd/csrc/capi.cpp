@@ -38,6 +38,18 @@ int trace_threads() { return tl_trace_threads > 0 ? tl_trace_threads : g_trace_t
 void set_thread_trace_threads(int n) { tl_trace_threads = n < 0 ? 0 : n > 64 ? 64 : n; }
 }  // namespace starkhip
 
+// a call below the C ABI from an entry that reads a trace: what it throws becomes a status
+template <class F>
+static int guarded(F call) {
+    try {
+        return call();
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    } catch (const std::exception&) {
+        return STARKHIP_ERR_BAD_SHAPE;
+    }
+}
+
 extern "C" {
 
 void starkhip_config_standard_fast(starkhip_config_t* cfg) {
@@ -148,61 +160,38 @@ int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, s
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     const AirInfo* a = air_get(air);
     if (!a) return STARKHIP_ERR_BAD_AIR;
-    if (!trace || !violations || !first || (a->pis && !public_inputs) || (layout != 0 && layout != 1) || n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;
-    try {
-        return check_trace((Ctx*)ctx, *a, trace, n_rows, layout, on_device, public_inputs, violations, first);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (in.check(*a) || !violations || !first || (a->pis && !public_inputs)) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] { return check_trace((Ctx*)ctx, *a, in, public_inputs, violations, first); });
 }
 
-// what both report entry points refuse before they look at the trace
-static int check_report_args(const AirInfo* a, const uint64_t* trace, size_t n_cols, int layout, const uint64_t* public_inputs, uint64_t* list,
-                             size_t cap, starkhip_check_report_t* out) {
+// what the checkers' entry points refuse before they look at the trace: an unknown AIR, a trace argument that cannot be one of it
+// (TraceInput::check), missing public inputs or result -- and `extra`, what the entry refuses of its own arguments
+static int checker_args(const AirInfo* a, const TraceInput& in, const uint64_t* public_inputs, const void* out, bool extra) {
     if (!a) return STARKHIP_ERR_BAD_AIR;
-    if (!trace || !out || (a->pis && !public_inputs) || (layout != 0 && layout != 1) || n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;
-    if (cap > STARKHIP_CHECK_LIST_MAX || (cap && !list)) return STARKHIP_ERR_BAD_SHAPE;
+    if (in.check(*a) || !out || (a->pis && !public_inputs) || extra) return STARKHIP_ERR_BAD_SHAPE;
     return STARKHIP_OK;
 }
+static bool bad_list(const uint64_t* list, size_t cap) { return cap > STARKHIP_CHECK_LIST_MAX || (cap && !list); }
+static bool bad_delta(uint64_t delta) { return delta == 0 || delta >= GL_P; }
 
 int starkhip_check_trace_report(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
                                 const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
                                 starkhip_check_report_t* out) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     const AirInfo* a = air_get(air);
-    if (int rc = check_report_args(a, trace, n_cols, layout, public_inputs, list, cap, out)) return rc;
-    try {
-        return check_trace_report((Ctx*)ctx, *a, trace, n_rows, layout, on_device, public_inputs, per_constraint, row_mask, list, cap, out);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = checker_args(a, in, public_inputs, out, bad_list(list, cap))) return rc;
+    return guarded([&] { return check_trace_report((Ctx*)ctx, *a, in, public_inputs, per_constraint, row_mask, list, cap, out); });
 }
 
 int starkhip_check_trace_report_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
                                        const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
                                        starkhip_check_report_t* out) {
     const AirInfo* a = air_get(air);
-    if (int rc = check_report_args(a, trace, n_cols, layout, public_inputs, list, cap, out)) return rc;
-    try {
-        return check_trace_report_replay(*a, trace, n_rows, layout, public_inputs, per_constraint, row_mask, list, cap, out);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
-}
-
-// what both free-cell entry points refuse before they look at the trace
-static int free_cells_args(const AirInfo* a, const uint64_t* trace, size_t n_cols, int layout, const uint64_t* public_inputs, uint64_t delta,
-                           starkhip_free_cells_t* out) {
-    if (!a) return STARKHIP_ERR_BAD_AIR;
-    if (!trace || !out || (a->pis && !public_inputs) || (layout != 0 && layout != 1) || n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;
-    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
-    return STARKHIP_OK;
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = checker_args(a, in, public_inputs, out, bad_list(list, cap))) return rc;
+    return guarded([&] { return check_trace_report_replay(*a, in, public_inputs, per_constraint, row_mask, list, cap, out); });
 }
 
 int starkhip_check_trace_free_cells(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
@@ -210,28 +199,18 @@ int starkhip_check_trace_free_cells(void* ctx, starkhip_air_t air, const uint64_
                                     starkhip_free_cells_t* out) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     const AirInfo* a = air_get(air);
-    if (int rc = free_cells_args(a, trace, n_cols, layout, public_inputs, delta, out)) return rc;
-    try {
-        return check_trace_free_cells((Ctx*)ctx, *a, trace, n_rows, layout, on_device, public_inputs, delta, per_column, free_mask, out);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    return guarded([&] { return check_trace_free_cells((Ctx*)ctx, *a, in, public_inputs, delta, per_column, free_mask, out); });
 }
 
 int starkhip_check_trace_free_cells_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
                                            const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* free_mask,
                                            starkhip_free_cells_t* out) {
     const AirInfo* a = air_get(air);
-    if (int rc = free_cells_args(a, trace, n_cols, layout, public_inputs, delta, out)) return rc;
-    try {
-        return check_trace_free_cells_replay(*a, trace, n_rows, layout, public_inputs, delta, per_column, free_mask, out);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    return guarded([&] { return check_trace_free_cells_replay(*a, in, public_inputs, delta, per_column, free_mask, out); });
 }
 
 int starkhip_quotient_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[8]) {
@@ -289,40 +268,26 @@ int starkhip_init(int device_ordinal, void** ctx) {
 }
 void starkhip_shutdown(void* ctx) { ctx_destroy((Ctx*)ctx); }
 
-int starkhip_prove(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols,
-                   int trace_layout, int trace_on_device, const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness, uint64_t** proof,
-                   size_t* proof_words) {
+// the three starkhip_prove* entries once each has named its trace; `armed`: it is a recording that is still armed on this thread
+static int prove_entry(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const TraceInput& in, bool armed, const uint64_t* public_inputs,
+                       size_t n_pis, uint64_t pow_witness, uint64_t** proof, size_t* proof_words) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     const AirInfo* a = air_get(air);
     if (!a) return STARKHIP_ERR_BAD_AIR;
-    if (!cfg || !trace || !proof || !proof_words || (n_pis && !public_inputs)) return STARKHIP_ERR_BAD_SHAPE;
-    if (trace_layout != 0 && trace_layout != 1) return STARKHIP_ERR_BAD_SHAPE;
-    if (n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;  // the caller's buffer is read as n_rows x columns words
-    try {
-        return prove((Ctx*)ctx, *a, *cfg, trace, n_rows, trace_layout, trace_on_device, public_inputs, n_pis, pow_witness, proof, proof_words);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
+    if (armed || in.check(*a) || !cfg || !proof || !proof_words || (n_pis && !public_inputs)) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] { return prove((Ctx*)ctx, *a, *cfg, in, public_inputs, n_pis, pow_witness, proof, proof_words); });
+}
+
+int starkhip_prove(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols,
+                   int trace_layout, int trace_on_device, const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness, uint64_t** proof,
+                   size_t* proof_words) {
+    return prove_entry(ctx, air, cfg, TraceInput::dense(trace, n_rows, n_cols, trace_layout, trace_on_device), false, public_inputs, n_pis, pow_witness,
+                       proof, proof_words);
 }
 
 int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* const* columns, size_t n_rows, size_t n_cols,
                            const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness, uint64_t** proof, size_t* proof_words) {
-    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
-    const AirInfo* a = air_get(air);
-    if (!a) return STARKHIP_ERR_BAD_AIR;
-    if (!cfg || !columns || !proof || !proof_words || (n_pis && !public_inputs)) return STARKHIP_ERR_BAD_SHAPE;
-    if (n_cols != a->cols) return STARKHIP_ERR_BAD_SHAPE;  // the table is read as `columns` pointers of n_rows words each
-    for (size_t i = 0; i < n_cols; i++)
-        if (!columns[i]) return STARKHIP_ERR_BAD_SHAPE;
-    try {
-        return prove((Ctx*)ctx, *a, *cfg, (const uint64_t*)columns, n_rows, 3, 0, public_inputs, n_pis, pow_witness, proof, proof_words);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
+    return prove_entry(ctx, air, cfg, TraceInput::column_table(columns, n_rows, n_cols), false, public_inputs, n_pis, pow_witness, proof, proof_words);
 }
 
 int starkhip_set_option(void* ctx, const char* name, long value) {
@@ -450,20 +415,8 @@ int starkhip_trace_log_expand_host(const void* log, uint64_t* trace_rowmajor, si
 }
 int starkhip_prove_compact(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const void* log, const uint64_t* public_inputs,
                            size_t n_pis, uint64_t pow_witness, uint64_t** proof, size_t* proof_words) {
-    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
-    const AirInfo* a = air_get(air);
-    if (!a) return STARKHIP_ERR_BAD_AIR;
-    const TraceLog* l = (const TraceLog*)log;
-    if (!l || armed_trace_log() == l || l->cols != a->cols || !l->rows) return STARKHIP_ERR_BAD_SHAPE;
-    if (!cfg || !proof || !proof_words || (n_pis && !public_inputs)) return STARKHIP_ERR_BAD_SHAPE;
-    try {
-        return prove((Ctx*)ctx, *a, *cfg, (const uint64_t*)l, l->rows, /*layout: compact log*/ 2, 0, public_inputs, n_pis, pow_witness, proof,
-                     proof_words);
-    } catch (const std::bad_alloc&) {
-        return STARKHIP_ERR_OOM;
-    } catch (const std::exception&) {
-        return STARKHIP_ERR_BAD_SHAPE;
-    }
+    return prove_entry(ctx, air, cfg, TraceInput::recording(log), log && armed_trace_log() == (const TraceLog*)log, public_inputs, n_pis, pow_witness,
+                       proof, proof_words);
 }
 
 // ---- proof pool (pool.cpp)
@@ -529,18 +482,19 @@ int starkhip_pool_submit(void* pool, starkhip_air_t air, const starkhip_config_t
                          int trace_layout, int trace_on_device, const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness,
                          uint64_t* ticket) {
     if (!pool) return STARKHIP_ERR_NO_DEVICE;
-    return pool_submit((Pool*)pool, air, cfg, trace, n_rows, n_cols, trace_layout, trace_on_device, public_inputs, n_pis, pow_witness, ticket);
+    return pool_submit((Pool*)pool, air, cfg, TraceInput::dense(trace, n_rows, n_cols, trace_layout, trace_on_device), public_inputs, n_pis, pow_witness,
+                       ticket);
 }
 int starkhip_pool_submit_columns(void* pool, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* const* columns, size_t n_rows,
                                  size_t n_cols, const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness, uint64_t* ticket) {
     if (!pool) return STARKHIP_ERR_NO_DEVICE;
-    return pool_submit_columns((Pool*)pool, air, cfg, columns, n_rows, n_cols, public_inputs, n_pis, pow_witness, ticket);
+    return pool_submit((Pool*)pool, air, cfg, TraceInput::column_table(columns, n_rows, n_cols), public_inputs, n_pis, pow_witness, ticket);
 }
 int starkhip_pool_submit_compact(void* pool, starkhip_air_t air, const starkhip_config_t* cfg, const void* log, const uint64_t* public_inputs,
                                  size_t n_pis, uint64_t pow_witness, uint64_t* ticket) {
     if (!pool) return STARKHIP_ERR_NO_DEVICE;
     if (log && armed_trace_log() == (const TraceLog*)log) return STARKHIP_ERR_BAD_SHAPE;
-    return pool_submit_compact((Pool*)pool, air, cfg, log, public_inputs, n_pis, pow_witness, ticket);
+    return pool_submit((Pool*)pool, air, cfg, TraceInput::recording(log), public_inputs, n_pis, pow_witness, ticket);
 }
 int starkhip_pool_submit_witness(void* pool, starkhip_air_t air, const starkhip_config_t* cfg, const uint32_t* operands, size_t n_limbs,
                                  uint64_t pow_witness, uint64_t* ticket) {
@@ -618,20 +572,21 @@ int starkhip_multipool_submit(void* mpool, int slot, starkhip_air_t air, const s
                               size_t n_cols, int trace_layout, int trace_on_device, const uint64_t* public_inputs, size_t n_pis,
                               uint64_t pow_witness, uint64_t* ticket) {
     if (!mpool) return STARKHIP_ERR_NO_DEVICE;
-    return multipool_submit((MultiPool*)mpool, slot, air, cfg, trace, n_rows, n_cols, trace_layout, trace_on_device, public_inputs, n_pis, pow_witness,
-                            ticket);
+    return multipool_submit((MultiPool*)mpool, slot, air, cfg, TraceInput::dense(trace, n_rows, n_cols, trace_layout, trace_on_device), public_inputs,
+                            n_pis, pow_witness, ticket);
 }
 int starkhip_multipool_submit_columns(void* mpool, int slot, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* const* columns,
                                       size_t n_rows, size_t n_cols, const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness,
                                       uint64_t* ticket) {
     if (!mpool) return STARKHIP_ERR_NO_DEVICE;
-    return multipool_submit_columns((MultiPool*)mpool, slot, air, cfg, columns, n_rows, n_cols, public_inputs, n_pis, pow_witness, ticket);
+    return multipool_submit((MultiPool*)mpool, slot, air, cfg, TraceInput::column_table(columns, n_rows, n_cols), public_inputs, n_pis, pow_witness,
+                            ticket);
 }
 int starkhip_multipool_submit_compact(void* mpool, int slot, starkhip_air_t air, const starkhip_config_t* cfg, const void* log,
                                       const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness, uint64_t* ticket) {
     if (!mpool) return STARKHIP_ERR_NO_DEVICE;
     if (log && armed_trace_log() == (const TraceLog*)log) return STARKHIP_ERR_BAD_SHAPE;
-    return multipool_submit_compact((MultiPool*)mpool, slot, air, cfg, log, public_inputs, n_pis, pow_witness, ticket);
+    return multipool_submit((MultiPool*)mpool, slot, air, cfg, TraceInput::recording(log), public_inputs, n_pis, pow_witness, ticket);
 }
 int starkhip_multipool_submit_witness(void* mpool, int slot, starkhip_air_t air, const starkhip_config_t* cfg, const uint32_t* operands,
                                       size_t n_limbs, uint64_t pow_witness, uint64_t* ticket) {

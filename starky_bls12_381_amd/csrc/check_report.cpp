@@ -104,20 +104,15 @@ struct ReplayPasses : CheckPasses {
 };
 }  // namespace
 
-int check_trace_report_replay(const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, const uint64_t* pis, uint32_t* per_constraint,
-                              uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out) {
+int check_trace_report_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint32_t* per_constraint, uint64_t* row_mask,
+                              uint64_t* list, size_t cap, starkhip_check_report_t* out) {
     unsigned log_n = 0;
-    if (int rc = check_trace_shape(air, n_rows, pis, &log_n)) return rc;
+    if (int rc = check_trace_shape(air, in.n_rows, pis, &log_n)) return rc;
     const AirProgram& P = air.prog;
     std::vector<uint64_t> rows;
-    if (layout == 1) {  // column-major [C][n]
-        rows.resize(n_rows * P.n_cols);
-        for (size_t c = 0; c < P.n_cols; c++)
-            for (size_t r = 0; r < n_rows; r++) rows[r * P.n_cols + c] = trace[c * n_rows + r];
-        trace = rows.data();
-    }
-    ReplayPasses passes(P, trace, n_rows, pis);
-    return check_report_run(P, n_rows, passes, per_constraint, row_mask, list, cap, out);
+    in.to_row_major(rows);
+    ReplayPasses passes(P, rows.data(), in.n_rows, pis);
+    return check_report_run(P, in.n_rows, passes, per_constraint, row_mask, list, cap, out);
 }
 
 }  // namespace starkhip

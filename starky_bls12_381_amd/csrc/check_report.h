@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "airs.h"
+#include "trace_input.h"
 
 namespace starkhip {
 
@@ -37,7 +38,7 @@ struct CheckPasses {
 int check_report_run(const AirProgram& P, size_t n_rows, CheckPasses& passes, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list,
                      size_t cap, starkhip_check_report_t* out);
 
-int check_trace_report_replay(const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, const uint64_t* pis, uint32_t* per_constraint,
-                              uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out);
+int check_trace_report_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint32_t* per_constraint, uint64_t* row_mask,
+                              uint64_t* list, size_t cap, starkhip_check_report_t* out);
 
 }  // namespace starkhip

@@ -18,11 +18,11 @@ namespace starkhip {
 // with the LDE buffer as the upload staging of row-major host rows.  The op stream is cached per context like the quotient's.
 // What both checkers do before their kernels: the shape checks, the op stream of `air` (cached), the trace on the device and the
 // public inputs in c->pis; *V is what the kernels read of it.
-static int check_trace_prepare(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                               CheckView* V) {
+static int check_trace_prepare(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, CheckView* V) {
     const AirProgram& P = air.prog;
-    if (int rc = check_trace_shape(air, n_rows, pis, &V->log_n)) return rc;
-    const size_t n = n_rows, C = P.n_cols;
+    if (int rc = check_trace_shape(air, in.n_rows, pis, &V->log_n)) return rc;
+    const size_t n = in.n_rows, C = P.n_cols;
+    if (in.n_cols != C) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->st;
     // (n / 64) x chunks waves: enough to fill 256 CUs several times over, at most one chunk per group
@@ -46,9 +46,9 @@ static int check_trace_prepare(Ctx* c, const AirInfo& air, const uint64_t* trace
         c->chk.want = want;
         c->chk.chunks = (unsigned)nc;
     }
-    if (!(on_device && layout == 1)) HIPCHK(c->values.ensure(C * n * 8));
-    if (!on_device && layout != 1) HIPCHK(c->lde.ensure(C * n * 8));  // the staging of row-major host rows
-    if (int rc = upload_dense(c, trace, layout, on_device, n, C, c->values.as<gl_t>(), &V->trace)) return rc;
+    if (!in.callers_columns()) HIPCHK(c->values.ensure(C * n * 8));
+    if (in.park_words(C)) HIPCHK(c->lde.ensure(in.park_words(C) * 8));  // the staging of row-major host rows
+    if (int rc = upload_dense(c, in, c->values.as<gl_t>(), &V->trace)) return rc;
     HIPCHK(c->pis.ensure(std::max<size_t>(1, P.n_pis) * 8));
     if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, st));
     V->ops = c->chk.ops.as<QOp>();
@@ -59,13 +59,12 @@ static int check_trace_prepare(Ctx* c, const AirInfo& air, const uint64_t* trace
     return STARKHIP_OK;
 }
 
-int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                uint64_t* violations, uint64_t first[3]) {
+int check_trace(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t* violations, uint64_t first[3]) {
     const AirProgram& P = air.prog;
     CheckView V = {};
-    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &V)) return rc;
+    if (int rc = check_trace_prepare(c, air, in, pis, &V)) return rc;
     const gl_t* d_trace = V.trace;
-    const size_t n = n_rows, C = P.n_cols;
+    const size_t n = in.n_rows, C = P.n_cols;
     hipStream_t st = c->st;
     const unsigned long long init[2] = {0, ~0ull};
     unsigned long long res[2];
@@ -139,23 +138,23 @@ struct DevicePasses : CheckPasses {
 };
 }  // namespace
 
-int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                       uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out) {
+int check_trace_report(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint32_t* per_constraint, uint64_t* row_mask,
+                       uint64_t* list, size_t cap, starkhip_check_report_t* out) {
     CheckView V = {};
-    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &V)) return rc;
+    if (int rc = check_trace_prepare(c, air, in, pis, &V)) return rc;
     DevicePasses passes(c, air.prog, V);
-    return check_report_run(air.prog, n_rows, passes, per_constraint, row_mask, list, cap, out);
+    return check_report_run(air.prog, in.n_rows, passes, per_constraint, row_mask, list, cap, out);
 }
 
 // starkhip_check_trace_free_cells: the audit kernel of kernels_free_cells.hip over the view the checkers share, then the count per
 // column.  One launch each: a FinalExp audit stays far below a second.  The bitmap comes back only when asked for.
-int check_trace_free_cells(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                           uint64_t delta, uint32_t* per_column, uint64_t* free_mask, starkhip_free_cells_t* out) {
+int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                           uint64_t* free_mask, starkhip_free_cells_t* out) {
     const AirProgram& P = air.prog;
     if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     CheckView V = {};
-    if (int rc = check_trace_prepare(c, air, trace, n_rows, layout, on_device, pis, &V)) return rc;
-    const size_t n = n_rows, C = P.n_cols, W = (n + 63) / 64;
+    if (int rc = check_trace_prepare(c, air, in, pis, &V)) return rc;
+    const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64;
     hipStream_t st = c->st;
     Ctx::FreeCellsProgram& fc = c->free_chk;
     if (fc.air != air.id || fc.want != c->chk.want) {  // op indices of the stream check_trace_prepare cached: the same cut gives the same ones

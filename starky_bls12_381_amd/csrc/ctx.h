@@ -73,9 +73,9 @@ struct Ctx {
     size_t rb_cap = 0, rb_used = 0;
     struct Pending { void* dst; const void* src; size_t bytes; };
     std::vector<Pending> rb_pending;
-    void* host_staging = nullptr;  // page-locked: a recording's parts gathered for one upload (prove(), layout 2); scattered columns (layout 3)
+    void* host_staging = nullptr;  // page-locked: a recording's parts gathered for one upload (prove()); a column table's scattered columns
     size_t host_staging_cap = 0;
-    hipEvent_t col_ev[2] = {nullptr, nullptr};  // layout 3: the two halves of host_staging, each free again when its copy has run
+    hipEvent_t col_ev[2] = {nullptr, nullptr};  // a column table: the two halves of host_staging, each free again when its copy has run
     std::set<int> blob_airs;  // AIRs this context has reserved page-locked proof blobs for (blob_arena.h)
     bool hash_requested = false;
     bool urgent = false;  // ctx_set_urgent
@@ -189,7 +189,7 @@ int ensure_program(Ctx* c, const AirInfo& air, size_t quotient_points);
 hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs);
 int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,
             const gl_t* post_scale);
-int upload_dense(Ctx* c, const uint64_t* trace, int layout, int on_device, size_t n, size_t C, gl_t* dst, const gl_t** d_values);
+int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values);
 hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form);
 
 // digest buffer: level 0 (n_leaves nodes) followed by level 1, ... ; offset of level l in nodes

@@ -392,13 +392,14 @@ std::vector<LogPiece> recording_pieces(const TraceLog& log) {
 // A dense trace of n rows x C columns into column-major device memory: `*d_values` is where it is afterwards -- `dst`, or the caller's
 // own column-major device memory (read only).  Row-major host rows go up into the start of the LDE buffer (idle until the LDE kernel
 // writes it; C n words) and are transposed from there.
-int upload_dense(Ctx* c, const uint64_t* trace, int layout, int on_device, size_t n, size_t C, gl_t* dst, const gl_t** d_values) {
+int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values) {
+    const size_t n = in.n_rows, C = in.n_cols;
     *d_values = dst;
-    if (on_device && layout == 1) *d_values = trace;
-    else if (on_device) HIPCHK(launch_transpose(trace, dst, n, C, c->st));
-    else if (layout == 1) HIPCHK(hipMemcpyAsync(dst, trace, C * n * 8, hipMemcpyHostToDevice, c->st));
+    if (in.callers_columns()) *d_values = in.words;
+    else if (in.on_device) HIPCHK(launch_transpose(in.words, dst, n, C, c->st));
+    else if (in.form == TraceForm::ColMajor) HIPCHK(hipMemcpyAsync(dst, in.words, C * n * 8, hipMemcpyHostToDevice, c->st));
     else {
-        HIPCHK(hipMemcpyAsync(c->lde.p, trace, C * n * 8, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(c->lde.p, in.words, C * n * 8, hipMemcpyHostToDevice, c->st));
         HIPCHK(launch_transpose(c->lde.as<gl_t>(), dst, n, C, c->st));
     }
     return 0;

@@ -53,16 +53,15 @@ starkhip_free_cells_t free_cells_summary(const uint32_t* per_column, size_t n_ro
     return s;
 }
 
-int check_trace_free_cells_replay(const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, const uint64_t* pis, uint64_t delta,
-                                  uint32_t* per_column, uint64_t* free_mask, starkhip_free_cells_t* out) {
+int check_trace_free_cells_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                  uint64_t* free_mask, starkhip_free_cells_t* out) {
     unsigned log_n = 0;
-    if (int rc = check_trace_shape(air, n_rows, pis, &log_n)) return rc;
+    if (int rc = check_trace_shape(air, in.n_rows, pis, &log_n)) return rc;
     if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     const AirProgram& P = air.prog;
-    const size_t n = n_rows, C = P.n_cols, W = (n + 63) / 64;
-    std::vector<uint64_t> rows(n * C);  // row-major, and ours to change: a cell is raised in place, evaluated and put back
-    for (size_t r = 0; r < n; r++)
-        for (size_t c = 0; c < C; c++) rows[r * C + c] = layout == 1 ? trace[c * n + r] : trace[r * C + c];
+    const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64;
+    std::vector<uint64_t> rows;  // row-major, and ours to change: a cell is raised in place, evaluated and put back
+    in.to_row_major(rows);
     std::vector<uint64_t> caught(C * W, 0);
     AirReader rd(P);
     GroupWord grp;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "airs.h"
+#include "trace_input.h"
 #include "quotient_ops.h"
 
 namespace starkhip {
@@ -37,7 +38,7 @@ FreeProgram compile_free_cells(const QProgram& Q);
 starkhip_free_cells_t free_cells_summary(const uint32_t* per_column, size_t n_rows, size_t n_cols);
 
 // The rule above as host loops over air_constraint_value_at on changed frames, one thread: for tests at small shapes.
-int check_trace_free_cells_replay(const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, const uint64_t* pis, uint64_t delta,
-                                  uint32_t* per_column, uint64_t* free_mask, starkhip_free_cells_t* out);
+int check_trace_free_cells_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                  uint64_t* free_mask, starkhip_free_cells_t* out);
 
 }  // namespace starkhip

@@ -18,7 +18,6 @@
 #include "kernels.h"
 #include "prover.h"
 #include "scheduler.h"
-#include "trace_log.h"
 #include "verifier.h"
 #include "verify_chunk.h"
 #include "verify_query.h"
@@ -75,12 +74,12 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t&, size_t, un
     return STARKHIP_OK;
 }
 
-int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* trace, size_t n_rows, int layout, int, const uint64_t* pis,
-          size_t n_pis, uint64_t pow_witness, uint64_t** proof_out, size_t* proof_words) {
+int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow_witness,
+          uint64_t** proof_out, size_t* proof_words) {
     if (!fake_device()) return STARKHIP_ERR_NO_DEVICE;
     if (n_pis != air.prog.n_pis) return STARKHIP_ERR_BAD_SHAPE;              // before the "commitment", like the real one
     if (pow_witness == 0xBAD) return STARKHIP_ERR_BAD_SHAPE;                  // a job that fails before its commitment (tests)
-    if (layout == 2 && ((const TraceLog*)trace)->rows != n_rows) return STARKHIP_ERR_BAD_SHAPE;
+    const size_t n_rows = in.n_rows;
     std::this_thread::sleep_for(std::chrono::milliseconds(air.cols > 50000 ? 3 : 1));  // "upload + LDE"
     unsigned log_n = 0;
     while (((size_t)1 << log_n) < n_rows) log_n++;
@@ -107,11 +106,11 @@ int merkle_cap(Ctx*, const uint64_t*, size_t, unsigned, unsigned, uint64_t*) { r
 int permute_batch(Ctx*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int permute_batch_form(Ctx*, int, int, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int expand_log(Ctx*, const TraceLog*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
-int check_trace(Ctx*, const AirInfo&, const uint64_t*, size_t, int, int, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
-int check_trace_report(Ctx*, const AirInfo&, const uint64_t*, size_t, int, int, const uint64_t*, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_check_report_t*) {
+int check_trace(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
+int check_trace_report(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_check_report_t*) {
     return STARKHIP_ERR_NO_DEVICE;
 }
-int check_trace_free_cells(Ctx*, const AirInfo&, const uint64_t*, size_t, int, int, const uint64_t*, uint64_t, uint32_t*, uint64_t*, starkhip_free_cells_t*) {
+int check_trace_free_cells(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t, uint32_t*, uint64_t*, starkhip_free_cells_t*) {
     return STARKHIP_ERR_NO_DEVICE;
 }
 int lde_bench(Ctx*, size_t, unsigned, unsigned, unsigned, unsigned, const uint64_t*, float*, float*) { return STARKHIP_ERR_NO_DEVICE; }

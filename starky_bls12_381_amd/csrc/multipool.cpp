@@ -201,20 +201,10 @@ static int multipool_place(MultiPool* mp, int air, int slot, bool verify, uint64
     return rc;
 }
 
-int multipool_submit(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
-                     int on_device, const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket) {
-    if (on_device && slot < 0) return STARKHIP_ERR_BAD_SHAPE;  // device memory belongs to one device: the caller says which
-    return multipool_place(mp, air, slot, false, ticket,
-                           [&](Pool* p, uint64_t* t) { return pool_submit(p, air, cfg, trace, n_rows, n_cols, layout, on_device, pis, n_pis, pow, t); });
-}
-int multipool_submit_columns(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint64_t* const* columns, size_t n_rows, size_t n_cols,
-                             const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket) {
-    return multipool_place(mp, air, slot, false, ticket,
-                           [&](Pool* p, uint64_t* t) { return pool_submit_columns(p, air, cfg, columns, n_rows, n_cols, pis, n_pis, pow, t); });
-}
-int multipool_submit_compact(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const void* log, const uint64_t* pis, size_t n_pis,
-                             uint64_t pow, uint64_t* ticket) {
-    return multipool_place(mp, air, slot, false, ticket, [&](Pool* p, uint64_t* t) { return pool_submit_compact(p, air, cfg, log, pis, n_pis, pow, t); });
+int multipool_submit(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow,
+                     uint64_t* ticket) {
+    if (in.on_device && slot < 0) return STARKHIP_ERR_BAD_SHAPE;  // device memory belongs to one device: the caller says which
+    return multipool_place(mp, air, slot, false, ticket, [&](Pool* p, uint64_t* t) { return pool_submit(p, air, cfg, in, pis, n_pis, pow, t); });
 }
 int multipool_submit_witness(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint32_t* operands, size_t n_limbs, uint64_t pow,
                              uint64_t* ticket) {

@@ -22,7 +22,6 @@
 #include "proof.h"
 #include "prover.h"
 #include "scheduler.h"
-#include "trace_log.h"
 #include "verify_service.h"
 
 namespace starkhip {
@@ -178,17 +177,9 @@ struct Pool {
             std::lock_guard<std::mutex> g(mu);
             gen_running--;
             j->info.t_generate_end = now();
-            if (j->own_log) {
-                j->kind = JOB_COMPACT;
-                j->trace = (const uint64_t*)j->own_log;
-                j->n_rows = ((const TraceLog*)j->own_log)->rows;
-            } else {
-                j->kind = JOB_DENSE;
-                j->trace = j->own_rows.data();
-                j->n_rows = air_get(j->air)->default_rows;
-                j->layout = 0;
-                j->on_device = 0;
-            }
+            const AirInfo* a = air_get(j->air);
+            j->kind = JOB_PROVE;
+            j->in = j->own_log ? TraceInput::recording(j->own_log) : TraceInput::dense(j->own_rows.data(), a->default_rows, a->cols, 0, 0);
             j->pis = j->own_pis.data();
             j->n_pis = j->own_pis.size();
             if (j->big && big_in_gen > 0) big_in_gen--;
@@ -236,8 +227,7 @@ struct Pool {
         const uint64_t cpu0 = thread_cpu_ns();
         try {
             const AirInfo* a = air_get(j->air);
-            rc = prove(c, *a, j->cfg, j->trace, j->n_rows, j->kind == JOB_COMPACT ? 2 : j->kind == JOB_COLUMNS ? 3 : j->layout, j->on_device, j->pis,
-                       j->n_pis, j->pow, &j->proof, &j->words);
+            rc = prove(c, *a, j->cfg, j->in, j->pis, j->n_pis, j->pow, &j->proof, &j->words);
         } catch (const std::bad_alloc&) {
             rc = STARKHIP_ERR_OOM;
         } catch (const std::exception&) {
@@ -257,7 +247,7 @@ struct Pool {
         if (j->own_log) {
             starkhip_trace_log_free(j->own_log);
             j->own_log = nullptr;
-            j->trace = nullptr;
+            j->in = TraceInput();
         }
         return rc;
     }
@@ -427,7 +417,7 @@ void pool_destroy(Pool* p) {
 static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     const AirInfo* a = air_get(j->air);
     unsigned log_n = 0;
-    const size_t rows = j->kind == JOB_WITNESS ? a->default_rows : j->n_rows;
+    const size_t rows = j->kind == JOB_RECORD ? a->default_rows : j->in.n_rows;
     while (((size_t)1 << log_n) < rows) log_n++;
     FriGeometry geo;  // a config prove() would refuse is refused here, before it takes a place in a queue
     if (!FriGeometry::make(j->cfg, log_n, &geo) || quotient_degree_bits(a->prog.degree) > j->cfg.rate_bits) {
@@ -448,7 +438,7 @@ static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     if (j->big) p->big_open++;
     p->jobs[j->id] = j;
     *ticket = j->id;
-    if (j->kind == JOB_WITNESS) {
+    if (j->kind == JOB_RECORD) {
         if (j->big) p->big_in_gen++;
         p->q_gen.push_back(j);
         p->cv_gen.notify_one();
@@ -460,68 +450,37 @@ static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     return STARKHIP_OK;
 }
 
-// What every submit does: the checks they share (`args_ok`: the caller's own), the job with the fields they all set, `fill` for the
-// rest of it (its status ends the submit when it is not OK), and the queue.
-template <class Fill>
-static int submit_job(Pool* p, int air, JobKind kind, const starkhip_config_t* cfg, bool args_ok, size_t n_cols, const uint64_t* pis, size_t n_pis,
-                      uint64_t pow, uint64_t* ticket, Fill fill) {
+// A trace the caller has: refused here as every entry refuses it (TraceInput::check), then queued for a context.  The caller keeps the
+// trace's memory alive until the job is done; only a column table is copied, and the view re-pointed at the copy.
+int pool_submit(Pool* p, int air, const starkhip_config_t* cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket) {
     const AirInfo* a = air_get(air);
     if (!a) return STARKHIP_ERR_BAD_AIR;
-    const bool witness = kind == JOB_WITNESS;  // its columns and public inputs come from the recording, its config may be the AIR's default
-    if (witness && witness_limbs(air) < 0) return STARKHIP_ERR_BAD_AIR;  // a registered AIR: no generator to run
-    if (!args_ok || !ticket || (n_pis && !pis) || (!witness && (!cfg || n_cols != a->cols))) return STARKHIP_ERR_BAD_SHAPE;
-    Job* j = new (std::nothrow) Job();
+    if (in.check(*a) || !cfg || !ticket || (n_pis && !pis)) return STARKHIP_ERR_BAD_SHAPE;
+    std::unique_ptr<Job> j(new (std::nothrow) Job());
     if (!j) return STARKHIP_ERR_OOM;
-    j->air = air; j->kind = kind; j->n_cols = n_cols; j->pis = pis; j->n_pis = n_pis; j->pow = pow;
-    int rc = STARKHIP_OK;
-    if (cfg) j->cfg = *cfg;
-    else rc = starkhip_config_for_air((starkhip_air_t)air, &j->cfg);
-    if (rc == STARKHIP_OK) rc = fill(j);
-    if (rc != STARKHIP_OK) {
-        delete j;
-        return rc;
-    }
-    return pool_enqueue(p, j, ticket);
-}
-
-int pool_submit(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
-                const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket) {
-    return submit_job(p, air, JOB_DENSE, cfg, trace && (layout == 0 || layout == 1), n_cols, pis, n_pis, pow, ticket, [&](Job* j) {
-        j->trace = trace; j->n_rows = n_rows; j->layout = layout; j->on_device = on_device;
-        return STARKHIP_OK;
-    });
-}
-
-int pool_submit_columns(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* const* columns, size_t n_rows, size_t n_cols,
-                        const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket) {
-    const AirInfo* a = air_get(air);
-    bool ok = columns != nullptr;
-    for (size_t i = 0; ok && a && n_cols == a->cols && i < n_cols; i++) ok = columns[i] != nullptr;  // (the table is n_cols long only if n_cols is right)
-    return submit_job(p, air, JOB_COLUMNS, cfg, ok, n_cols, pis, n_pis, pow, ticket, [&](Job* j) {
+    j->air = air; j->cfg = *cfg; j->in = in; j->pis = pis; j->n_pis = n_pis; j->pow = pow;
+    if (in.form == TraceForm::ColumnTable) {
         try {
-            j->columns.assign(columns, columns + n_cols);
+            j->columns.assign(in.columns, in.columns + in.n_cols);
         } catch (const std::bad_alloc&) {
-            return (int)STARKHIP_ERR_OOM;
+            return STARKHIP_ERR_OOM;
         }
-        j->trace = (const uint64_t*)j->columns.data(); j->n_rows = n_rows;
-        return (int)STARKHIP_OK;
-    });
+        j->in.columns = j->columns.data();
+    }
+    return pool_enqueue(p, j.release(), ticket);
 }
 
-int pool_submit_compact(Pool* p, int air, const starkhip_config_t* cfg, const void* log, const uint64_t* pis, size_t n_pis, uint64_t pow,
-                        uint64_t* ticket) {
-    const TraceLog* l = (const TraceLog*)log;
-    return submit_job(p, air, JOB_COMPACT, cfg, l && l->rows, l ? l->cols : 0, pis, n_pis, pow, ticket, [&](Job* j) {
-        j->trace = (const uint64_t*)l; j->n_rows = l->rows;
-        return STARKHIP_OK;
-    });
-}
-
+// A trace the pool records itself: its columns and public inputs come from the recording, its config may be the AIR's default
 int pool_submit_witness(Pool* p, int air, const starkhip_config_t* cfg, const uint32_t* operands, size_t n_limbs, uint64_t pow, uint64_t* ticket) {
-    return submit_job(p, air, JOB_WITNESS, cfg, operands && (size_t)witness_limbs(air) == n_limbs, 0, nullptr, 0, pow, ticket, [&](Job* j) {
-        j->operands.assign(operands, operands + n_limbs);
-        return STARKHIP_OK;
-    });
+    if (!air_get(air) || witness_limbs(air) < 0) return STARKHIP_ERR_BAD_AIR;  // (a registered AIR: no generator to run)
+    if (!operands || (size_t)witness_limbs(air) != n_limbs || !ticket) return STARKHIP_ERR_BAD_SHAPE;
+    std::unique_ptr<Job> j(new (std::nothrow) Job());
+    if (!j) return STARKHIP_ERR_OOM;
+    j->air = air; j->kind = JOB_RECORD; j->pow = pow;
+    if (cfg) j->cfg = *cfg;
+    else if (int rc = starkhip_config_for_air((starkhip_air_t)air, &j->cfg)) return rc;
+    j->operands.assign(operands, operands + n_limbs);
+    return pool_enqueue(p, j.release(), ticket);
 }
 
 int pool_wait(Pool* p, uint64_t ticket, uint64_t** proof, size_t* words, starkhip_ticket_info_t* info) {

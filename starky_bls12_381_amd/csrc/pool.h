@@ -7,24 +7,23 @@
 #include <vector>
 
 #include "airs.h"
+#include "trace_input.h"
 
 namespace starkhip {
 
-enum JobKind { JOB_DENSE, JOB_COMPACT, JOB_WITNESS, JOB_COLUMNS, JOB_VERIFY };
+enum JobKind { JOB_RECORD, JOB_PROVE, JOB_VERIFY };  // a witness job that still needs its recording; a job with its trace; a proof to check
 enum class JobState { Queued, Running, Verifying, Done };  // Queued: for its recording or for a context
 
 struct Job {
     uint64_t id = 0;
     int air = 0;
     starkhip_config_t cfg;
-    JobKind kind = JOB_DENSE;
-    const uint64_t* trace = nullptr;  // dense: caller's matrix; compact: a TraceLog*
-    size_t n_rows = 0, n_cols = 0;
-    int layout = 0, on_device = 0;
+    JobKind kind = JOB_PROVE;
+    TraceInput in;  // JOB_PROVE: the trace, in the caller's memory or in this job's own (columns, own_log, own_rows)
     const uint64_t* pis = nullptr;
     size_t n_pis = 0;
     uint64_t pow = 0;
-    std::vector<const uint64_t*> columns;  // JOB_COLUMNS: the caller's column pointers (the table is copied at submit, the columns are not)
+    std::vector<const uint64_t*> columns;  // a column table's pointers (the table is copied at submit, the columns are not)
     std::vector<uint32_t> operands;   // witness jobs
     void* own_log = nullptr;          // witness jobs: the recording, freed when proven
     std::vector<uint64_t> own_pis, own_rows;  // own_rows: the toy AIR's generator writes plain rows (it does not record)

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "airs.h"
+#include "trace_input.h"
 
 namespace starkhip {
 
@@ -29,12 +30,7 @@ bool ctx_hash_requested(Ctx* c);  // the current / last prove() reached its trac
 struct Pool;
 int pool_create(const starkhip_pool_config_t& cfg, Pool** out, unsigned cpu_share = 1);  // cpu_share: pools that split this process's CPUs
 void pool_destroy(Pool* p);
-int pool_submit(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
-                const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket);
-int pool_submit_columns(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* const* columns, size_t n_rows, size_t n_cols,
-                        const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket);
-int pool_submit_compact(Pool* p, int air, const starkhip_config_t* cfg, const void* log, const uint64_t* pis, size_t n_pis, uint64_t pow,
-                        uint64_t* ticket);
+int pool_submit(Pool* p, int air, const starkhip_config_t* cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket);
 int pool_submit_witness(Pool* p, int air, const starkhip_config_t* cfg, const uint32_t* operands, size_t n_limbs, uint64_t pow, uint64_t* ticket);
 int pool_wait(Pool* p, uint64_t ticket, uint64_t** proof, size_t* words, starkhip_ticket_info_t* info);
 int pool_stats(Pool* p, starkhip_pool_stats_t* out);
@@ -54,12 +50,8 @@ void multipool_destroy(MultiPool* mp);
 size_t multipool_size(const MultiPool* mp);
 Pool* multipool_pool(MultiPool* mp, size_t slot);
 int multipool_device(const MultiPool* mp, size_t slot);
-int multipool_submit(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
-                     int on_device, const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket);
-int multipool_submit_columns(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint64_t* const* columns, size_t n_rows, size_t n_cols,
-                             const uint64_t* pis, size_t n_pis, uint64_t pow, uint64_t* ticket);
-int multipool_submit_compact(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const void* log, const uint64_t* pis, size_t n_pis,
-                             uint64_t pow, uint64_t* ticket);
+int multipool_submit(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow,
+                     uint64_t* ticket);
 int multipool_submit_witness(MultiPool* mp, int slot, int air, const starkhip_config_t* cfg, const uint32_t* operands, size_t n_limbs, uint64_t pow,
                              uint64_t* ticket);
 int multipool_submit_witness_batch(MultiPool* mp, size_t n, const int* airs, const uint32_t* const* operands, const size_t* n_limbs, uint64_t pow,
@@ -75,23 +67,21 @@ void plan_lpt(size_t n, const int* airs, size_t n_pools, int* slots);
 size_t ctx_device_bytes(Ctx* c);  // device memory this context holds (work buffers, tables, plans)
 size_t ctx_pinned_bytes(Ctx* c);  // page-locked host memory it holds (upload staging; proof blobs are counted by starkhip_proof_blob_stats)
 
-int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* trace, size_t n_rows, int layout, int on_device,
-          const uint64_t* pis, size_t n_pis, uint64_t pow_witness, uint64_t** proof_out, size_t* proof_words);
+int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow_witness,
+          uint64_t** proof_out, size_t* proof_words);
 // starkhip_check_trace: every constraint of `air` on every row of the trace, on the device (kernels_check.hip)
-int check_trace(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                uint64_t* violations, uint64_t first[3]);
+int check_trace(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t* violations, uint64_t first[3]);
 // starkhip_check_trace_report: the same check with per-constraint counts, the rows and a list (kernels_check.hip, check_report.h)
-int check_trace_report(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                       uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap, starkhip_check_report_t* out);
+int check_trace_report(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint32_t* per_constraint, uint64_t* row_mask,
+                       uint64_t* list, size_t cap, starkhip_check_report_t* out);
 // starkhip_check_trace_free_cells: the cells no constraint notices when delta is added to them (kernels_free_cells.hip, free_cells.h)
-int check_trace_free_cells(Ctx* c, const AirInfo& air, const uint64_t* trace, size_t n_rows, int layout, int on_device, const uint64_t* pis,
-                           uint64_t delta, uint32_t* per_column, uint64_t* free_mask, starkhip_free_cells_t* out);
+int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                           uint64_t* free_mask, starkhip_free_cells_t* out);
 int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out);
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);
 int permute_batch(Ctx* c, uint64_t* states, size_t n);
 int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n);
-struct TraceLog;
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor);
 int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms = nullptr);
 int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);

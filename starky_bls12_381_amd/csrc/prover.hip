@@ -173,8 +173,8 @@ struct ProveCall {
     const starkhip_config_t& cfg;
     const ProofShape& s;
     hipStream_t st;
-    const uint64_t *trace, *pis_host;  // prove()'s arguments
-    int layout, on_device;
+    const TraceInput& in;  // prove()'s arguments
+    const uint64_t* pis_host;
     uint64_t pow_witness;
     bool tiled;          // the quotient's evaluator: the tiled plan, or the op-stream interpreter
     unsigned n_chunks;   // ... and the chunks its constraints are cut into
@@ -252,9 +252,11 @@ int ProveCall::upload_column_table(const uint64_t* const* cols) {
 }
 
 int ProveCall::upload() {
-    if (layout == 2) return upload_recording((const TraceLog*)trace);
-    if (layout == 3) return upload_column_table((const uint64_t* const*)trace);
-    return upload_dense(c, trace, layout, on_device, s.n, s.C, d_trace, &d_values);
+    switch (in.form) {
+        case TraceForm::Recording: return upload_recording(in.log);
+        case TraceForm::ColumnTable: return upload_column_table(in.columns);
+        default: return upload_dense(c, in, d_trace, &d_values);
+    }
 }
 
 // ---- phase 1: IFFT + LDE (PolynomialBatch::from_values, App. A.3)
@@ -652,8 +654,8 @@ int ProveCall::queries() {
 
 // The transcript of SURVEY.md App. A.5: argument checks, tables and plan, buffers, then the phases.  The order of what they enqueue on the
 // context's stream and the places where the host waits for it make the phase timings mean what starkhip.h says; a pool's overlap depends on it.
-int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* trace, size_t n_rows, int layout, int on_device,
-          const uint64_t* pis_host, size_t n_pis, uint64_t pow_witness, uint64_t** proof_out, size_t* proof_words) {
+int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in, const uint64_t* pis_host, size_t n_pis, uint64_t pow_witness,
+          uint64_t** proof_out, size_t* proof_words) {
     struct ReadBackGuard {  // an early return between a read_back() and its stream_wait() must not leave destinations of this call behind
         Ctx* c;
         ~ReadBackGuard() {
@@ -662,7 +664,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
         }
     } read_back_guard{c};
     ProofShape s;
-    if (n_pis != air.prog.n_pis || ProofShape::make(air, cfg, n_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
+    if (n_pis != air.prog.n_pis || in.n_cols != air.prog.n_cols || ProofShape::make(air, cfg, in.n_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     for (size_t i = 0; i < n_pis; i++)
         if (pis_host[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
@@ -676,14 +678,8 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
     // The trace waits for the LDE INSIDE the buffer the LDE is written to, as its last C n words (trace_in_lde: run_lde_trace);
     // a separate buffer only when there is no room beside it (rate_bits == 0, or a recording longer than the rest of the buffer).
     const size_t n = s.n, N = s.N, C = s.C;
-    const bool callers_columns = on_device && layout == 1;  // column-major device memory of the caller's: read where it is
-    size_t park_words = 0;  // what the upload parks at the start of the LDE buffer, in 64-bit words
-    if (layout == 2) {
-        const TraceLog* log = (const TraceLog*)trace;
-        park_words = (log->total_words() + log->total_records() + log->total_late_zeros() + 2 + 1) / 2;
-    } else if (!on_device && layout == 0) {
-        park_words = C * n;
-    }
+    const bool callers_columns = in.callers_columns();
+    const size_t park_words = in.park_words(C);  // what the upload parks at the start of the LDE buffer, in 64-bit words
     // A long trace (2^14 rows and more) is not parked there: its transform goes through the LDE buffer between its two passes and keeps
     // the coefficients in `values`, a whole trace of words, whoever owns the input (run_lde).
     const bool long_trace = lde_long_supported(s.log_n);
@@ -693,7 +689,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const uint64
     for (const BufWant& w : work_buffers(c, s, n_chunks, values_bytes, park_words * 8)) HIPCHK(w.b->ensure(w.bytes));
     if (int rc = ensure_long_tables(c, s)) return rc;
 
-    ProveCall p{c, air, cfg, s, st, trace, pis_host, layout, on_device, pow_witness, tiled, n_chunks, trace_in_lde,
+    ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde,
                 trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()};
     // before each phase: the boundary event of starkhip_last_timings on the stream and the phase's rocTX range (rocprofv3 --marker-trace)
     static const struct { const char* range; int (ProveCall::*run)(); } PHASES[STARKHIP_N_PHASES - 1] = {

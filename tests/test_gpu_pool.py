@@ -3,6 +3,7 @@ byte-identical to the ones from a plain context -- and so to the CPU oracle's --
 import hashlib
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -297,6 +298,51 @@ def test_batch_regime_miller_and_precomp_beside_a_lane_group_match_the_oracle(mo
         for a, (proof, _) in zip(args, got):
             trace, pis = gen(*a)
             assert np.array_equal(proof, O.prove(S.air_program(air), cfg, S.trace_rows_to_poly_values(trace), pis))
+
+
+DEVICE_SUBMIT_CHILD = r"""
+import os, sys, faulthandler
+faulthandler.dump_traceback_later(100, exit=True)
+sys.path[:0] = [%(root)r, os.path.join(%(root)r, "tests")]
+import numpy as np, torch   # torch first: its HIP runtime has to be the process's first
+import starky_bls12_381_amd as S
+torch.cuda.set_device(0)
+air = S.AIR_TEST_FIBONACCI
+cfg = S.StarkConfig.for_air(air)
+t, pis = S.trace_fibonacci(3, 5, 64)
+pv = S.Prover(0)
+proof = pv.prove(air, cfg, t, pis)
+pv.close()
+w = int(proof[int(S.proof_layout(proof).off_pow_witness)])
+for devices in (None, [0]):
+    pool = S.ProofPool(0, big_contexts=1, small_contexts=1, devices=devices)
+    try:
+        for layout, host in ((0, t), (1, t.T.copy())):
+            dev = torch.from_numpy(np.ascontiguousarray(host).view(np.int64)).to("cuda:0")
+            torch.cuda.synchronize()
+            got = pool.wait(pool.submit_device(air, cfg, dev.data_ptr(), 64, pis, pow_witness=w, layout=layout, slot=0))[0]
+            assert np.array_equal(got, proof), (devices, layout)
+            torch.cuda.synchronize()
+            assert np.array_equal(dev.cpu().numpy().view(np.uint64), host)  # read in place, left as it was
+        if devices is not None:  # device memory belongs to one device: the library does not place it
+            try:
+                pool.submit_device(air, cfg, dev.data_ptr(), 64, pis, pow_witness=w, layout=1, slot=-1)
+                raise SystemExit("device memory without a slot was accepted")
+            except S.StarkhipError as e:
+                assert e.code == S.ERR_BAD_SHAPE, e.code
+    finally:
+        pool.close()
+print("device submits ok")
+"""
+
+
+def test_pool_submits_of_device_memory_match_the_single_context_proof():
+    """ProofPool.submit_device: a trace in device memory, row-major (transposed on the device) and column-major (read where it is),
+    through one pool and through a multi-device handle with its slot named; the four proofs equal Prover.prove of the same host rows
+    byte for byte, and the multi-device handle refuses device memory it would have to place itself."""
+    # in a child process: a torch tensor needs torch's HIP runtime, which has to come up before the library's
+    r = subprocess.run([sys.executable, "-c", DEVICE_SUBMIT_CHILD % {"root": ROOT}], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "device submits ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 def test_prove_from_separately_allocated_columns_matches_the_oracle(prover):

@@ -126,8 +126,177 @@ static int multi_device_pass() {
     return 0;
 }
 
+// What every entry that takes a trace refuses, and with which code: starkhip_prove*, starkhip_pool_submit* and starkhip_multipool_submit*
+// for a dense trace, a column table and a recording.  Every case starts from arguments that are accepted (asserted first) and has exactly
+// one thing wrong; the doubly-wrong cases at the end pin the order of the checks.
+enum Entry { E_PROVE, E_POOL, E_MULTI };
+struct Handles { void *ctx, *pool, *mp; };
+struct TraceArgs {
+    starkhip_air_t air;
+    const starkhip_config_t* cfg;
+    const void* trace;  // dense words, a column table or a log, by the family of the entry
+    size_t n_rows, n_cols;
+    int layout, on_device;
+    const uint64_t* pis;
+    size_t n_pis;
+    bool handle, out;  // false: a null context / pool / handle; a null ticket (proof pointer for starkhip_prove*)
+    int slot;
+};
+enum Family { F_DENSE, F_COLUMNS, F_COMPACT };
+
+// the status of the entry; of the wait, and of a look at the fake proof, where the submit was accepted
+static int call_entry(const Handles& h, Entry e, Family f, const TraceArgs& a) {
+    uint64_t* proof = nullptr;
+    size_t words = 0;
+    uint64_t ticket = 0;
+    const uint64_t pow = 0;
+    const uint64_t* dense = (const uint64_t*)a.trace;
+    const uint64_t* const* table = (const uint64_t* const*)a.trace;
+    int rc;
+    if (e == E_PROVE) {
+        void* ctx = a.handle ? h.ctx : nullptr;
+        uint64_t** pp = a.out ? &proof : nullptr;
+        rc = f == F_DENSE     ? starkhip_prove(ctx, a.air, a.cfg, dense, a.n_rows, a.n_cols, a.layout, a.on_device, a.pis, a.n_pis, pow, pp, &words)
+             : f == F_COLUMNS ? starkhip_prove_columns(ctx, a.air, a.cfg, table, a.n_rows, a.n_cols, a.pis, a.n_pis, pow, pp, &words)
+                              : starkhip_prove_compact(ctx, a.air, a.cfg, a.trace, a.pis, a.n_pis, pow, pp, &words);
+    } else if (e == E_POOL) {
+        void* pool = a.handle ? h.pool : nullptr;
+        uint64_t* t = a.out ? &ticket : nullptr;
+        rc = f == F_DENSE     ? starkhip_pool_submit(pool, a.air, a.cfg, dense, a.n_rows, a.n_cols, a.layout, a.on_device, a.pis, a.n_pis, pow, t)
+             : f == F_COLUMNS ? starkhip_pool_submit_columns(pool, a.air, a.cfg, table, a.n_rows, a.n_cols, a.pis, a.n_pis, pow, t)
+                              : starkhip_pool_submit_compact(pool, a.air, a.cfg, a.trace, a.pis, a.n_pis, pow, t);
+        if (rc == STARKHIP_OK) rc = starkhip_pool_wait(pool, ticket, &proof, &words, nullptr);
+    } else {
+        void* mp = a.handle ? h.mp : nullptr;
+        uint64_t* t = a.out ? &ticket : nullptr;
+        rc = f == F_DENSE     ? starkhip_multipool_submit(mp, a.slot, a.air, a.cfg, dense, a.n_rows, a.n_cols, a.layout, a.on_device, a.pis, a.n_pis, pow, t)
+             : f == F_COLUMNS ? starkhip_multipool_submit_columns(mp, a.slot, a.air, a.cfg, table, a.n_rows, a.n_cols, a.pis, a.n_pis, pow, t)
+                              : starkhip_multipool_submit_compact(mp, a.slot, a.air, a.cfg, a.trace, a.pis, a.n_pis, pow, t);
+        if (rc == STARKHIP_OK) rc = starkhip_multipool_wait(mp, ticket, &proof, &words, nullptr);
+    }
+    if (rc == STARKHIP_OK) {
+        if (words != 4 + a.n_pis || proof[1] != (uint64_t)a.air || proof[2] != a.n_rows) rc = 1000;
+        starkhip_free(proof);
+    }
+    return rc;
+}
+
+static int refusal_table() {
+    const starkhip_air_t FIB = STARKHIP_AIR_TEST_FIBONACCI, MUL = STARKHIP_AIR_FP12_MUL, NO_AIR = (starkhip_air_t)999;
+    const int SHAPE = STARKHIP_ERR_BAD_SHAPE;
+    Handles h = {nullptr, nullptr, nullptr};
+    starkhip_pool_config_t pc;
+    memset(&pc, 0, sizeof pc);
+    pc.big_contexts = 1;
+    pc.small_contexts = 2;
+    pc.generator_threads = 1;
+    pc.trace_threads = 1;
+    const int devices[2] = {0, 1};
+    CHECK(starkhip_init(0, &h.ctx) == STARKHIP_OK);
+    CHECK(starkhip_pool_create(&pc, &h.pool) == STARKHIP_OK);
+    CHECK(starkhip_multipool_create(devices, 2, &pc, &h.mp) == STARKHIP_OK);
+
+    // the toy AIR's rows, row-major, column-major and as a column table; an FP12Mul recording
+    const size_t fib_rows = (size_t)starkhip_air_default_rows(FIB), fib_cols = (size_t)starkhip_air_columns(FIB), fib_pis = (size_t)starkhip_air_public_inputs(FIB);
+    const size_t mul_rows = (size_t)starkhip_air_default_rows(MUL), mul_cols = (size_t)starkhip_air_columns(MUL), mul_pis = (size_t)starkhip_air_public_inputs(MUL);
+    CHECK(fib_rows >= 2 && fib_cols >= 2 && fib_pis > 0 && mul_pis > 0 && mul_cols != fib_cols);
+    std::vector<uint64_t> rows(fib_rows * fib_cols), colmajor(fib_rows * fib_cols), pis_fib(fib_pis), pis_mul(mul_pis);
+    CHECK(starkhip_trace_fibonacci(3, 5, rows.data(), fib_rows, pis_fib.data()) == STARKHIP_OK);
+    for (size_t r = 0; r < fib_rows; r++)
+        for (size_t c = 0; c < fib_cols; c++) colmajor[c * fib_rows + r] = rows[r * fib_cols + c];
+    std::vector<const uint64_t*> table(fib_cols), holed;
+    for (size_t c = 0; c < fib_cols; c++) table[c] = &colmajor[c * fib_rows];
+    holed = table;
+    holed[fib_cols - 1] = nullptr;
+    const std::vector<uint32_t> ops = limbs(288, 77);
+    void *log = nullptr, *armed = nullptr;
+    CHECK(starkhip_trace_log_begin(&log) == STARKHIP_OK);
+    CHECK(starkhip_trace_fp12_mul(ops.data(), ops.data() + 144, nullptr, mul_rows, pis_mul.data()) == STARKHIP_OK);
+    CHECK(starkhip_trace_log_end(log) == STARKHIP_OK);
+    starkhip_config_t cfg_fib, cfg_mul;
+    CHECK(starkhip_config_for_air(FIB, &cfg_fib) == STARKHIP_OK && starkhip_config_for_air(MUL, &cfg_mul) == STARKHIP_OK);
+
+    const TraceArgs dense_ok = {FIB, &cfg_fib, rows.data(), fib_rows, fib_cols, 0, 0, pis_fib.data(), fib_pis, true, true, 0};
+    const TraceArgs columns_ok = {FIB, &cfg_fib, table.data(), fib_rows, fib_cols, 0, 0, pis_fib.data(), fib_pis, true, true, 0};
+    const TraceArgs compact_ok = {MUL, &cfg_mul, log, mul_rows, mul_cols, 0, 0, pis_mul.data(), mul_pis, true, true, 0};
+    struct Case { const char* what; Family f; TraceArgs a; int want; };
+    std::vector<Case> cases;
+    auto add = [&](const char* what, Family f, int want, auto change) {
+        TraceArgs a = f == F_DENSE ? dense_ok : f == F_COLUMNS ? columns_ok : compact_ok;
+        change(a);
+        cases.push_back({what, f, a, want});
+    };
+    for (Family f : {F_DENSE, F_COLUMNS, F_COMPACT}) {
+        add("accepted", f, STARKHIP_OK, [](TraceArgs&) {});
+        add("placed by the library", f, STARKHIP_OK, [](TraceArgs& a) { a.slot = -1; });
+        add("null handle", f, STARKHIP_ERR_NO_DEVICE, [](TraceArgs& a) { a.handle = false; });
+        add("unknown AIR", f, STARKHIP_ERR_BAD_AIR, [&](TraceArgs& a) { a.air = NO_AIR; });
+        add("null trace", f, SHAPE, [](TraceArgs& a) { a.trace = nullptr; });
+        add("null ticket", f, SHAPE, [](TraceArgs& a) { a.out = false; });
+        add("public inputs missing", f, SHAPE, [](TraceArgs& a) { a.pis = nullptr; });
+    }
+    add("column-major", F_DENSE, STARKHIP_OK, [&](TraceArgs& a) { a.trace = colmajor.data(); a.layout = 1; });
+    add("device memory, in a slot", F_DENSE, STARKHIP_OK, [](TraceArgs& a) { a.on_device = 1; });
+    add("layout 2", F_DENSE, SHAPE, [](TraceArgs& a) { a.layout = 2; });
+    add("layout -1", F_DENSE, SHAPE, [](TraceArgs& a) { a.layout = -1; });
+    for (Family f : {F_DENSE, F_COLUMNS}) {
+        add("a column too many", f, SHAPE, [](TraceArgs& a) { a.n_cols++; });
+        add("a column too few", f, SHAPE, [](TraceArgs& a) { a.n_cols--; });
+    }
+    add("null column", F_COLUMNS, SHAPE, [&](TraceArgs& a) { a.trace = holed.data(); });
+    add("another AIR's recording", F_COMPACT, SHAPE, [&](TraceArgs& a) { a.air = FIB; a.cfg = &cfg_fib; a.pis = pis_fib.data(); a.n_pis = fib_pis; });
+    for (const Case& c : cases)
+        for (Entry e : {E_PROVE, E_POOL, E_MULTI}) {
+            const int got = call_entry(h, e, c.f, c.a);
+            if (got != c.want) {
+                fprintf(stderr, "tsan_pool: refusal table: %s, family %d, entry %d: %d, want %d\n", c.what, (int)c.f, (int)e, got, c.want);
+                return 1;
+            }
+        }
+    // device memory belongs to one device: a multi-device handle wants the slot
+    TraceArgs no_slot = dense_ok;
+    no_slot.on_device = 1;
+    no_slot.slot = -1;
+    CHECK(call_entry(h, E_MULTI, F_DENSE, no_slot) == SHAPE);
+    // a recording that is still armed on this thread
+    std::vector<uint64_t> pis_armed(mul_pis);
+    CHECK(starkhip_trace_log_begin(&armed) == STARKHIP_OK);
+    CHECK(starkhip_trace_fp12_mul(ops.data(), ops.data() + 144, nullptr, mul_rows, pis_armed.data()) == STARKHIP_OK);
+    TraceArgs still_armed = compact_ok;
+    still_armed.trace = armed;
+    for (Entry e : {E_PROVE, E_POOL, E_MULTI}) CHECK(call_entry(h, e, F_COMPACT, still_armed) == SHAPE);
+    // wrong in two ways: no handle before the AIR, the AIR before the trace -- but for an armed recording in the submits and device
+    // memory without a slot, which are refused before the AIR is looked at
+    for (Family f : {F_DENSE, F_COLUMNS, F_COMPACT})
+        for (Entry e : {E_PROVE, E_POOL, E_MULTI}) {
+            TraceArgs a = f == F_DENSE ? dense_ok : f == F_COLUMNS ? columns_ok : compact_ok;
+            a.air = NO_AIR;
+            a.trace = nullptr;
+            CHECK(call_entry(h, e, f, a) == STARKHIP_ERR_BAD_AIR);
+            a.handle = false;
+            CHECK(call_entry(h, e, f, a) == STARKHIP_ERR_NO_DEVICE);
+        }
+    still_armed.air = NO_AIR;
+    CHECK(call_entry(h, E_PROVE, F_COMPACT, still_armed) == STARKHIP_ERR_BAD_AIR);
+    CHECK(call_entry(h, E_POOL, F_COMPACT, still_armed) == SHAPE);
+    CHECK(call_entry(h, E_MULTI, F_COMPACT, still_armed) == SHAPE);
+    no_slot.air = NO_AIR;
+    CHECK(call_entry(h, E_MULTI, F_DENSE, no_slot) == SHAPE);
+    CHECK(starkhip_trace_log_end(armed) == STARKHIP_OK);
+    CHECK(call_entry(h, E_POOL, F_COMPACT, [&] { TraceArgs a = compact_ok; a.trace = armed; return a; }()) == STARKHIP_OK);  // finished: accepted
+
+    starkhip_trace_log_free(armed);
+    starkhip_trace_log_free(log);
+    starkhip_multipool_destroy(h.mp);
+    starkhip_pool_destroy(h.pool);
+    starkhip_shutdown(h.ctx);
+    printf("refusal table: ok (%zu cases on three entries each)\n", cases.size());
+    return 0;
+}
+
 int main() {
     setenv("STARKHIP_FAKE_DEVICE", "1", 1);
+    if (int rc = refusal_table()) return rc;
     if (int rc = multi_device_pass()) return rc;
     for (unsigned pass = 0; pass < 4; pass++) {
         const unsigned policy = pass < 3 ? pass : 0;
