@@ -550,6 +550,9 @@ int starkhip_poseidon_permute_batch_form(void* ctx, int form, int variant, uint6
  * quad form, four at a time in the lane and pair forms: replays both formulations on n_states inputs against the plain permutation;
  * returns the number of mismatches (0 = good), -1 if a sum of the four-round merge would not fit its 64-bit accumulator */
 int starkhip_selfcheck_hash_tables(unsigned n_states);
+/* The host-built table a leaf-hash form's kernels read from constant memory (no GPU needed; form 1 quad, 2 row, 3 lane, 4 pair as in
+ * "leaf_hash_form"): returns the image's size in bytes and copies it to `out` when `cap` suffices; 0 for an unknown form */
+size_t starkhip_hash_table_image(int form, void* out, size_t cap);
 /* The launch plan of a trace's LDE (no GPU needed).  The trace columns wait for the LDE inside the buffer the LDE is written to, as
  * its last n_cols * n words, so the LDE goes out in several launches, each overwriting only parked columns that an earlier launch
  * has read; the last one reads a copy of its columns (csrc/lde_ranges.h).  Writes up to `cap` launches as triples

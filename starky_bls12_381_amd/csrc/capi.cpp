@@ -721,6 +721,19 @@ int starkhip_selfcheck_hash_tables(unsigned n_states) {
     if (fours < 0) return -1;
     return quad_merged_tables_selfcheck(n_states) + fours;
 }
+size_t starkhip_hash_table_image(int form, void* out, size_t cap) {
+    const void* image = nullptr;
+    size_t bytes = 0;
+    switch (form) {
+        case FORM_QUAD: image = quad_merged_tables_host(); bytes = sizeof(QuadMergedTables); break;
+        case FORM_ROW: image = row_merged_tables_host(); bytes = sizeof(RowMergedTables); break;
+        case FORM_LANE: image = lane_tables_host(); bytes = sizeof(LaneTables); break;
+        case FORM_PAIR: image = pair_tables_host(); bytes = sizeof(PairTables); break;
+    }
+    if (!image) return 0;
+    if (out && cap >= bytes) memcpy(out, image, bytes);
+    return bytes;
+}
 int starkhip_fri_geometry(const starkhip_config_t* cfg, unsigned log_n, unsigned* arities_out, size_t cap, size_t* n_layers, size_t* final_poly_len) {
     if (!cfg) return STARKHIP_ERR_BAD_SHAPE;
     FriGeometry g;

@@ -240,15 +240,15 @@ int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points) {
 // launches): the quad form of a commitment with <= 4096 leaves is at most 256 waves on 1024 SIMDs, each a chain of up to 12 167
 // sequential permutations, so the form with fewer instructions per wave and permutation wins (MillerLoop 119 -> ms, kernels_hash.hip).
 static bool use_row_form(const Ctx* c, size_t n_cols, unsigned log_N) {
-    if (c->opt_leaf_hash_form == 1) return false;
-    if (c->opt_leaf_hash_form == 2) return true;
-    if (c->opt_leaf_hash_form == 3 || c->opt_leaf_hash_form == 4) return false;
+    if (c->opt_leaf_hash_form == FORM_QUAD) return false;
+    if (c->opt_leaf_hash_form == FORM_ROW) return true;
+    if (c->opt_leaf_hash_form == FORM_LANE || c->opt_leaf_hash_form == FORM_PAIR) return false;
     return log_N <= 12 && n_cols >= 64;
 }
 // The pair form (two lanes per leaf, 256 registers per wave) fills the chip from 32 768 leaves on: 1 024 waves, one per SIMD.
 static bool use_pair_form(const Ctx* c, size_t n_cols, unsigned log_N) {
-    if (c->opt_leaf_hash_form == 4) return true;
-    if (c->opt_leaf_hash_form != 0) return false;
+    if (c->opt_leaf_hash_form == FORM_PAIR) return true;
+    if (c->opt_leaf_hash_form != FORM_AUTO) return false;
     return log_N >= 15 && n_cols >= 64;
 }
 
@@ -340,7 +340,7 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
     else if (k == "lde_closed_forms" && (value == 0 || value == 1)) c->opt_lde_closed_forms = value;
     else if (k == "lde_impl" && (value == 0 || value == 1)) c->opt_lde_impl = value;
     else if (k == "host_commit_leaves" && value >= 0 && value <= 4096) c->opt_host_commit_leaves = value;
-    else if (k == "leaf_hash_form" && value >= 0 && value <= 4) c->opt_leaf_hash_form = value;
+    else if (k == "leaf_hash_form" && value >= FORM_AUTO && value <= FORM_PAIR) c->opt_leaf_hash_form = value;
     else if (k == "quotient_chunks" && value >= 0 && value <= 4096) c->opt_quotient_chunks = value;  // plans are cached by (AIR, chunks)
     else if (k == "verify_chunk_mb" && value >= 1) c->opt_verify_chunk_mb = value;
     else return STARKHIP_ERR_BAD_SHAPE;
@@ -408,11 +408,9 @@ int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values)
 // The leaf hash of a LONE context's commitment in the form use_pair_form / use_row_form / "leaf_hash_form" pick; `*form` says which
 // (HashService::Timing::form)
 hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form) {
-    *form = c->opt_leaf_hash_form == 3 ? 3 : use_pair_form(c, n_cols, log_n + rate) ? 5 : use_row_form(c, n_cols, log_n + rate) ? 1 : 0;
-    if (*form == 3) return launch_leaf_hash_lane(lde, n_cols, log_n, rate, digests, st);
-    if (*form == 5) return launch_leaf_hash_pair(lde, n_cols, log_n, rate, digests, st);
-    if (*form == 1) return launch_leaf_hash_row(lde, n_cols, log_n, rate, digests, st);
-    return launch_leaf_hash(lde, n_cols, log_n, rate, digests, st);
+    const LeafHashForm f = c->opt_leaf_hash_form == FORM_LANE ? FORM_LANE : use_pair_form(c, n_cols, log_n + rate) ? FORM_PAIR : use_row_form(c, n_cols, log_n + rate) ? FORM_ROW : FORM_QUAD;
+    *form = leaf_hash_sent(f);
+    return launch_leaf_hash_form(f, lde, n_cols, log_n, rate, digests, st);
 }
 
 // In-place transform of n_vecs vectors of 2^log_len words, vec_stride apart, as launch_ntt_global does it (inverse: tw_inv's direction and

@@ -109,17 +109,17 @@ void HashService::drain(std::vector<hipEvent_t>& evs) {
 
 void HashService::launch_big(Req* r, bool lane, unsigned group) {
     hipStream_t s = (r->urgent && st_high_) ? st_high_ : st_;
+    const LeafHashForm form = lane ? FORM_LANE : FORM_PAIR;
     hipError_t e = hipSuccess;
     if (lane) s = pick_small_stream(&e);  // lane-form grids are a quarter of the chip each: they must overlap, not queue in one stream
     if (e == hipSuccess) e = wait_ready(r);
     if (r->timing) {
-        r->timing->form = lane ? 3 : 5;
+        r->timing->form = leaf_hash_sent(form);
         r->timing->group = group;
         if (e == hipSuccess && r->timing->t0) e = hipEventRecord(r->timing->t0, s);
     }
     // a big commitment on its own: the pair form (is_big() = 32 768 leaves or more: 1 024 waves of it fill the chip)
-    if (e == hipSuccess) e = lane ? launch_leaf_hash_lane(r->mat, r->n_cols, r->log_n, r->rate_bits, r->digests, s)
-                                  : launch_leaf_hash_pair(r->mat, r->n_cols, r->log_n, r->rate_bits, r->digests, s);
+    if (e == hipSuccess) e = launch_leaf_hash_form(form, r->mat, r->n_cols, r->log_n, r->rate_bits, r->digests, s);
     if (e == hipSuccess && r->timing && r->timing->t1) e = hipEventRecord(r->timing->t1, s);
     if (e == hipSuccess) e = hipEventRecord(r->done, s);
     r->err = e;
@@ -185,7 +185,7 @@ void HashService::launch_small(std::vector<Req*>& reqs) {
             const bool row_form = cfg.row_leaves && (((size_t)1 << (g[0]->log_n + g[0]->rate_bits)) <= cfg.row_leaves);
             for (size_t i = 0; i < cnt; i++)
                 if (Timing* t = g[at + i]->timing) {
-                    t->form = row_form ? 1 : 2;
+                    t->form = row_form ? SENT_ROW : SENT_MERGED;
                     t->group = (unsigned)cnt;
                     if (e == hipSuccess && t->t0) e = hipEventRecord(t->t0, s);
                 }
@@ -193,7 +193,7 @@ void HashService::launch_small(std::vector<Req*>& reqs) {
                 // the row form (16 lanes per leaf): shortest chain per leaf at 2.8 x the chip time.  Measured with every small commitment
                 // of a pool in it: one signature 0.36 -> 0.38 s, a batch of 8 3.8 -> 3.3 signatures/s; only the tiny ones take it by default
                 for (size_t i = 0; i < cnt && e == hipSuccess; i++)
-                    e = launch_leaf_hash_row(B.mat[i], g[0]->n_cols, g[0]->log_n, g[0]->rate_bits, B.digests[i], s);
+                    e = launch_leaf_hash_form(FORM_ROW, B.mat[i], g[0]->n_cols, g[0]->log_n, g[0]->rate_bits, B.digests[i], s);
             } else if (e == hipSuccess) {
                 e = launch_leaf_hash_multi(B, (unsigned)cnt, g[0]->n_cols, g[0]->log_n, g[0]->rate_bits, s);
             }

@@ -59,7 +59,7 @@ double* ctx_verify_timings(Ctx* c) { return c->verify_timings; }
 int ctx_device(Ctx* c) { return c->device; }
 const float* ctx_kernel_timings(Ctx* c) { return c->ktimings; }
 const float* ctx_host_timings(Ctx* c) { return c->htimings; }
-void ctx_commit_info(Ctx*, int* form, unsigned* group) { *form = 0; *group = 1; }
+void ctx_commit_info(Ctx*, int* form, unsigned* group) { *form = SENT_QUAD; *group = 1; }
 int ctx_set_option(Ctx*, const char*, long) { return STARKHIP_ERR_NO_DEVICE; }
 void ctx_attach_hash_service(Ctx* c, HashService* hs) { c->hs = hs; }
 bool ctx_has_hash_service(Ctx* c) { return c->hs != nullptr; }
@@ -117,16 +117,12 @@ int lde_bench(Ctx*, size_t, unsigned, unsigned, unsigned, unsigned, const uint64
 int field_ops(Ctx*, int, const uint64_t*, const uint64_t*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int host_alloc(Ctx*, size_t, void**) { return STARKHIP_ERR_NO_DEVICE; }
 void host_free(void*) {}
-int quad_merged_tables_selfcheck(unsigned) { return 0; }  // the real one is compiled with the HIP sources
 
 hipError_t event_wait_sleeping(hipEvent_t) { return hipSuccess; }  // ctx.hip's sleeping wait: the fake device is always done
 
 // the two launches the commitment scheduler makes
 static std::atomic<unsigned long> g_fake_launches(0), g_fake_merged(0);
-hipError_t launch_leaf_hash(const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { g_fake_launches++; return hipSuccess; }
-hipError_t launch_leaf_hash_row(const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { g_fake_launches++; return hipSuccess; }
-hipError_t launch_leaf_hash_lane(const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { g_fake_launches++; return hipSuccess; }
-hipError_t launch_leaf_hash_pair(const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { g_fake_launches++; return hipSuccess; }
+hipError_t launch_leaf_hash_form(LeafHashForm, const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { g_fake_launches++; return hipSuccess; }
 hipError_t launch_leaf_hash_multi(const LeafHashBatch&, unsigned count, size_t, unsigned, unsigned, hipStream_t) {
     g_fake_launches++;
     g_fake_merged += count;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "gl.h"
+#include "poseidon_tables.h"  // the host-built tables of the leaf-hash forms and their CPU checks
 
 // First statement of every kernel except the lane-form leaf hash: its waves raise their issue priority (s_setprio 2).  A lane-form group
 // of four saturates the SIMDs' issue slots for a third of a second; whatever else is resident beside it in that time -- the LDE and the
@@ -87,27 +88,52 @@ struct LeafHashBatch {
     gl_t* digests[LEAF_HASH_MAX_BATCH];
 };
 hipError_t launch_leaf_hash_multi(const LeafHashBatch& B, unsigned count, size_t n_cols, unsigned log_n, unsigned rate_bits, hipStream_t st);
-hipError_t launch_leaf_hash(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st);
-// the same digests from the row form (16 lanes per leaf): shorter chain per leaf, 4x the lane-instructions -- for a lone commitment of few leaves
-// the same digests from the lane form (one lane per leaf): fewest instructions per permutation, but 1/4 of the waves -- for big commitments when several are in flight
-hipError_t launch_leaf_hash_lane(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st);
-// the same digests from the pair form (two lanes per leaf, one 256-register wave per SIMD at 32 768 leaves): a LONE big commitment
-hipError_t launch_leaf_hash_pair(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st);
-hipError_t launch_leaf_hash_row(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st);
+// The leaf-hash forms in the numbering of the "leaf_hash_form" option and of the test entries (starkhip_poseidon_permute_batch_form,
+// starkhip_hash_table_image).  FORM_AUTO: the option's "the library picks"; as a permutation entry, the generic loop.
+enum LeafHashForm : int {
+    FORM_AUTO = 0,
+    FORM_QUAD = 1,  // four lanes per leaf
+    FORM_ROW = 2,   // 16 lanes per leaf: shorter chain per leaf, 4x the lane-instructions -- for a lone commitment of few leaves
+    FORM_LANE = 3,  // one lane per leaf: fewest instructions per permutation, but 1/4 of the waves -- for big commitments when several are in flight
+    FORM_PAIR = 4,  // two lanes per leaf, one 256-register wave per SIMD at 32 768 leaves: a LONE big commitment
+};
+// How a trace commitment went out, as starkhip_ticket_info_t.leaf_hash_form reports it (starkhip.h: public values)
+enum LeafHashSent : int {
+    SENT_QUAD = 0,
+    SENT_ROW = 1,
+    SENT_MERGED = 2,  // one grid merged with other proofs' commitments (quad form)
+    SENT_LANE = 3,
+    SENT_HOST = 4,    // hashed by host threads
+    SENT_PAIR = 5,
+};
+// what a lone launch of `form` (not FORM_AUTO) is reported as
+inline LeafHashSent leaf_hash_sent(LeafHashForm form) {
+    return form == FORM_ROW ? SENT_ROW : form == FORM_LANE ? SENT_LANE : form == FORM_PAIR ? SENT_PAIR : SENT_QUAD;
+}
+// the same digests from every form; hipErrorInvalidValue for FORM_AUTO
+hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st);
+// Copies a host-built table (poseidon_tables.h) to its __constant__ symbol once per device, under a lock.  `done`: the symbol's own
+// flags, one per device, set after a successful copy.  hipErrorInvalidDevice for a device index outside 0 .. 63, hipErrorInvalidValue
+// for an image that could not be built (null).
+hipError_t upload_table_once(const void* symbol, const void* image, size_t bytes, bool (&done)[64]);
 hipError_t launch_leaf_hash_rows(const gl_t* rows, size_t width, size_t n_leaves, gl_t* digests, hipStream_t st);
 hipError_t launch_merkle_levels(gl_t* digests, unsigned log_leaves, unsigned cap_h, hipStream_t st);
 hipError_t launch_permute_batch(gl_t* states, size_t n, hipStream_t st);
 // how many variants of its permutation a form's leaf kernel uses (0: no such form); kernels_hash.hip, the test entry points
-inline unsigned permute_form_variants(int form) { return form == 0 || form == 2 ? 1u : form == 1 || form == 3 || form == 4 ? 2u : 0u; }
+inline unsigned permute_form_variants(int form) {
+    switch (form) {
+        case FORM_AUTO: case FORM_ROW: return 1u;
+        case FORM_QUAD: case FORM_LANE: case FORM_PAIR: return 2u;
+    }
+    return 0u;
+}
 hipError_t launch_permute_quad_form(bool cap_only, const gl_t* in, gl_t* out, size_t n, hipStream_t st);   // kernels_hash_quad_form.hip
+// variant 1 = the form's capacity-only last round (quad, lane, pair)
 hipError_t launch_permute_batch_form(int form, int variant, const gl_t* in, gl_t* out, size_t n, hipStream_t st);
-// kernels_selftest.hip
-// CPU replay of the leaf-hash kernel's merged-partial-round tables against the plain permutation; mismatching states out of n
-int quad_merged_tables_selfcheck(unsigned n);
-int merged_fours_selfcheck(unsigned n);   // poseidon_host.cpp: the same for the four-round merges of the lane and pair forms
-hipError_t launch_field_ops(int op, const gl_t* a, const gl_t* b, gl_t* out, size_t n, hipStream_t st);
 hipError_t launch_pow_grind(const gl_t* base_state, int pos, unsigned pow_bits, uint64_t start, uint64_t count, unsigned long long* best,
                             hipStream_t st);
+// kernels_selftest.hip
+hipError_t launch_field_ops(int op, const gl_t* a, const gl_t* b, gl_t* out, size_t n, hipStream_t st);
 
 // kernels_quotient.hip
 hipError_t launch_quotient_tables(gl_t* tab, unsigned log_n, unsigned qdb, hipStream_t st);

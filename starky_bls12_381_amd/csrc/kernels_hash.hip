@@ -4,217 +4,18 @@
 // reference reaches through prove() at /root/reference/src/aggregate_proof.rs:59.
 #include <hip/hip_runtime.h>
 
-#include <string.h>
-
 #include <mutex>
 
 #include "kernels.h"
-#include "poseidon_merged.h"
 #include "poseidon_dev.h"
 #include "verify_query.h"
 
 namespace starkhip {
 
-// ---- per-lane tables of the quad permutation (poseidon_dev.h: QuadMergedTables), built on the host once per device
+// ---- the host-built tables (poseidon_tables.h), one image per device in constant memory; each symbol with its own upload flags
 __constant__ QuadMergedTables QUAD_MERGED;
-
-// Lane l owns state elements l, l + 4, l + 8 (slots 0, 1, 2); its rotated operand (r, m) is element ((l + r) & 3) + 4 m.
-static inline int quad_elem(int l, int m) { return l + 4 * m; }
-static inline int quad_col(int l, int r, int m) { return ((l + r) & 3) + 4 * m; }
-
-// The per-lane views of poseidon_merged.h's tables and of the circulant MDS matrix.
-static void build_quad_merged_tables(QuadMergedTables& T) {
-    static PoseidonMergedTables P;
-    build_poseidon_merged_tables(P);
-    static const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-    auto split = [](gl_t v) { return RcPair{v & 0xFFFFFFFFull, v >> 32}; };
-    for (int l = 0; l < 4; l++) {
-        uint32_t* c = T.coef[l];
-        for (int r = 0; r < 4; r++)
-            for (int m = 0; m < 3; m++) {
-                const int col = quad_col(l, r, m);
-                for (int mo = 0; mo < 3; mo++) c[12 * mo + 3 * r + m] = (uint32_t)P.N3[quad_elem(l, mo)][col];
-            }
-        for (int m = 0; m < 3; m++) {
-            c[36 + m] = (uint32_t)P.M[0][quad_elem(l, m)];   // the lane's own columns of row 0
-            c[39 + m] = (uint32_t)P.N2[0][quad_elem(l, m)];
-        }
-        c[42] = l == 0 ? (uint32_t)P.M[0][0] : 0;
-        for (int mo = 0; mo < 3; mo++) {
-            c[43 + mo] = (uint32_t)P.N2[quad_elem(l, mo)][0];
-            c[46 + mo] = (uint32_t)P.M[quad_elem(l, mo)][0];
-        }
-        c[49] = 0;
-        // cf[3 r + d]: coefficient of the operand (r, m') for the output slot m with (m' - m) mod 3 = d:
-        // CIRC[(col - out) mod 12] with col - out = ((l + r) & 3) - l + 4 d
-        for (int r = 0; r < 4; r++)
-            for (int d = 0; d < 3; d++) c[50 + 3 * r + d] = CIRC[((((l + r) & 3) - l + 4 * d) % 12 + 12) % 12];
-        c[62] = c[63] = 0;
-    }
-    // every lane seeds its partial sum of y1 / y2 with a quarter of the constant (4^-1 = (3p + 1) / 4 mod p)
-    const gl_t quarter = (gl_t)((((unsigned __int128)3 * GL_P) + 1) / 4);
-    for (int t = 0; t < QUAD_MERGED_TRIPLES; t++) {
-        T.tk[2 * t] = split(gl_mul(P.k1[t], quarter));
-        T.tk[2 * t + 1] = split(gl_mul(P.k2[t], quarter));
-        for (int l = 0; l < 4; l++)
-            for (int mo = 0; mo < 3; mo++) T.tk3[l][3 * t + mo] = split(P.k3[t][quad_elem(l, mo)]);
-    }
-}
-
-// Host replay of the quad formulation with exactly the tables the kernel gets (per-lane coefficient views included), against
-// the plain host permutation: a CPU-side check of build_quad_merged_tables (tests/test_field_hash_cpu.py).  Returns the
-// number of mismatching states out of `n`.
-int quad_merged_tables_selfcheck(unsigned n) {
-    static QuadMergedTables T;
-    build_quad_merged_tables(T);
-    auto join = [](const RcPair& c) { return (gl_t)(c.lo | (c.hi << 32)); };
-    // the plain layer as the kernel computes it: per lane, twelve coefficients by rotation and slot difference
-    auto mds_lanes = [&](gl_t* s) {
-        gl_t out[12];
-        for (int l = 0; l < 4; l++)
-            for (int mo = 0; mo < 3; mo++) {
-                gl_t acc = 0;
-                for (int r = 0; r < 4; r++)
-                    for (int m = 0; m < 3; m++) acc = gl_add(acc, gl_mul(s[quad_col(l, r, m)], T.coef[l][50 + 3 * r + (m - mo + 3) % 3]));
-                if (l == 0 && mo == 0) acc = gl_add(acc, gl_mul(s[0], 8));
-                out[quad_elem(l, mo)] = acc;
-            }
-        for (int i = 0; i < 12; i++) s[i] = out[i];
-    };
-    int bad = 0;
-    uint64_t seed = 0x9E3779B97F4A7C15ull;
-    for (unsigned it = 0; it < n; it++) {
-        gl_t s[12], want[12];
-        for (int i = 0; i < 12; i++) {
-            seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
-            s[i] = it == 0 ? 0 : it == 1 ? GL_P - 1 : seed % GL_P;
-            want[i] = s[i];
-        }
-        poseidon_permute(want);
-        const uint64_t* RC = POSEIDON_RC_HOST;
-        int r = 0;
-        for (; r < 4; r++) {
-            for (int i = 0; i < 12; i++) s[i] = poseidon_sbox(gl_add(s[i], RC[12 * r + i]));
-            mds_lanes(s);
-        }
-        for (int i = 0; i < 12; i++) s[i] = gl_add(s[i], RC[12 * r + i]);
-        for (int t = 0; t < QUAD_MERGED_TRIPLES; t++, r += 3) {
-            gl_t u[12];
-            for (int i = 0; i < 12; i++) u[i] = s[i];
-            u[0] = poseidon_sbox(u[0]);
-            // y1, y2: per-lane partial sums with the quartered constants, exactly as the kernel adds them up
-            gl_t y1 = 0, y2p = 0;
-            for (int l = 0; l < 4; l++) {
-                const uint32_t* c = T.coef[l];
-                gl_t a = join(T.tk[2 * t]), b = join(T.tk[2 * t + 1]);
-                for (int m = 0; m < 3; m++) {
-                    a = gl_add(a, gl_mul(u[quad_elem(l, m)], c[36 + m]));
-                    b = gl_add(b, gl_mul(u[quad_elem(l, m)], c[39 + m]));
-                }
-                y1 = gl_add(y1, a);
-                y2p = gl_add(y2p, b);
-            }
-            const gl_t x2 = poseidon_sbox(y1);
-            gl_t y2 = y2p;
-            for (int l = 0; l < 4; l++) y2 = gl_add(y2, gl_mul(x2, T.coef[l][42]));
-            const gl_t x3 = poseidon_sbox(y2);
-            for (int l = 0; l < 4; l++) {
-                const uint32_t* c = T.coef[l];
-                for (int mo = 0; mo < 3; mo++) {
-                    gl_t acc = join(T.tk3[l][3 * t + mo]);
-                    for (int rr = 0; rr < 4; rr++)
-                        for (int m = 0; m < 3; m++) acc = gl_add(acc, gl_mul(u[quad_col(l, rr, m)], c[12 * mo + 3 * rr + m]));
-                    acc = gl_add(acc, gl_mul(x2, c[43 + mo]));
-                    acc = gl_add(acc, gl_mul(x3, c[46 + mo]));
-                    s[quad_elem(l, mo)] = acc;
-                }
-            }
-        }
-        s[0] = poseidon_sbox(s[0]);  // round 25, plain
-        mds_lanes(s);
-        r++;
-        for (int i = 0; i < 12; i++) s[i] = gl_add(s[i], RC[12 * r + i]);
-        for (; r < 30; r++) {
-            for (int i = 0; i < 12; i++) s[i] = poseidon_sbox(s[i]);
-            mds_lanes(s);
-            if (r + 1 < 30)
-                for (int i = 0; i < 12; i++) s[i] = gl_add(s[i], RC[12 * (r + 1) + i]);
-        }
-        for (int i = 0; i < 12; i++)
-            if (s[i] != want[i]) {
-                bad++;
-                break;
-            }
-    }
-    return bad;
-}
-
-// ---- the row form's merged triples: per-lane coefficient rows and constants (poseidon_dev.h: RowMergedTables)
 __constant__ RowMergedTables ROW_MERGED;
-static void build_row_merged_tables(RowMergedTables& T) {
-    static PoseidonMergedTables P;
-    build_poseidon_merged_tables(P);
-    auto split = [](gl_t v) { return RcPair{v & 0xFFFFFFFFull, v >> 32}; };
-    for (int e = 0; e < 16; e++) {
-        uint32_t* c = T.coef[e];
-        for (int k = 0; k < 20; k++) c[k] = 0;
-        if (e >= 12) continue;
-        for (int k = 0; k < 12; k++) c[k] = (uint32_t)P.N3[e][(e + k) % 12];
-        c[12] = (uint32_t)P.M[0][e];
-        c[13] = (uint32_t)P.N2[0][e];
-        c[14] = (uint32_t)P.N2[e][0];
-        c[15] = (uint32_t)P.M[e][0];
-        c[16] = (uint32_t)P.N3[e][0];
-        c[17] = e == 0 ? (uint32_t)P.M[0][0] : 0;
-        c[18] = e == 0 ? (uint32_t)P.N2[0][0] : 0;
-    }
-    for (int t = 0; t < POSEIDON_MERGED_TRIPLES; t++) {
-        T.k1[t] = split(P.k1[t]);
-        T.k2[t] = split(P.k2[t]);
-        for (int e = 0; e < 12; e++) T.k3[t][e] = split(P.k3[t][e]);
-    }
-}
-static hipError_t ensure_row_merged_tables() {
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> g(mu);
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    static RowMergedTables T;
-    static bool built = false;
-    if (!built) {
-        build_row_merged_tables(T);
-        built = true;
-    }
-    e = hipMemcpyToSymbol(HIP_SYMBOL(ROW_MERGED), &T, sizeof T);
-    if (e == hipSuccess) done[dev] = true;
-    return e;
-}
-
-// the host image of the quad form's tables, built once (also what kernels_hash_quad_form.hip uploads)
-const QuadMergedTables& quad_merged_tables_host() {
-    static QuadMergedTables T;  // zero-initialised; filled once
-    static std::once_flag once;
-    std::call_once(once, [] { build_quad_merged_tables(T); });
-    return T;
-}
-static hipError_t ensure_quad_merged_tables() {
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> g(mu);
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    const QuadMergedTables& T = quad_merged_tables_host();
-    e = hipMemcpyToSymbol(HIP_SYMBOL(QUAD_MERGED), &T, sizeof T);
-    if (e == hipSuccess) done[dev] = true;
-    return e;
-}
+static bool quad_uploaded[64], row_uploaded[64], lane_uploaded[64], pair_uploaded[64];
 
 // Leaf digests of a column-major matrix laid out coset-major (see kernels_ntt.hip):
 //   element (column c, physical point q) at mat[c * N + q], q = s * n + k  <->  natural index i = k * R + s.
@@ -497,73 +298,6 @@ __global__ __launch_bounds__(256, 2) void leaf_hash_lane_kernel(const gl_t* __re
         for (int e = 0; e < 4; e++) digests[4 * j + e] = gl_canon(lane_get(st.t0, e));
     }
 }
-static bool build_lane_tables(LaneTables& T) {
-    static PoseidonMergedFours P;
-    build_poseidon_merged_fours(P);
-    if (!P.sums_fit) return false;   // (a property of the MDS matrix, checked where the tables are made: the accumulators' 64 bits)
-    auto split = [](gl_t v) { return RcPair{v & 0xFFFFFFFFull, v >> 32}; };
-    memset(&T, 0, sizeof T);
-    for (int r = 0; r < 30; r++)
-        for (int e = 0; e < 12; e++) T.rc[r][e] = split(POSEIDON_RC_HOST[12 * r + e]);
-    for (int e = 0; e < 12; e++) T.rc0[e] = POSEIDON_RC_HOST[e];
-    for (int t = 0; t < POSEIDON_MERGED_FOURS; t++) {
-        T.kf[t][0] = split(P.k1[t]);
-        T.kf[t][1] = split(P.k2[t]);
-        T.kf[t][2] = split(P.k3[t]);
-        for (int e = 0; e < 12; e++) T.k4[t][e] = split(P.k4[t][e]);
-    }
-    for (int r = 0; r < 12; r++) {
-        for (int c = 0; c < 12; c++) T.row[r][c] = (uint32_t)P.N4[r][c];
-        T.row[r][12] = (uint32_t)P.N3[r][0];
-        T.row[r][13] = (uint32_t)P.N2[r][0];
-        T.row[r][14] = (uint32_t)P.M[r][0];
-        T.m0[r] = (uint32_t)P.M[0][r];
-        T.n20[r] = (uint32_t)P.N2[0][r];
-        T.n30[r] = (uint32_t)P.N3[0][r];
-    }
-    T.n30[12] = (uint32_t)P.N2[0][0];
-    // The matrix-pipe rounds (poseidon_dev.h: poseidon_permute_lane_asm): table m serves the round whose layer is seeded with rc[next[m]].
-    // The products see signed bytes (byte - 128) and the spare K-values add 34 818 = STARKHIP_LANE_K_OFFSET to every plane, so the 64-bit
-    // constant whose bytes ride in the weight tile is  RC[g] = rc[g] - (34 818 - 128 rowsum[g]) * 0x0101010101010101  mod p.
-    static const int CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-    static const int NEXT_ROUND[9] = {1, 2, 3, 4, 25, 26, 27, 28, 29};
-    for (int m = 0; m < 9; m++)
-        for (unsigned lane = 0; lane < 64; lane++) {
-            const unsigned row = lane & 31u, half = lane >> 5, g = (row & 3u) + 4u * (row >> 3);
-            const bool live = ((row >> 2) & 1u) == half && g < 12u;
-            gl_t RC = 0;
-            if (live) {
-                uint64_t rowsum = 0;
-                for (int j = 0; j < 12; j++) rowsum += (uint64_t)CIRC[(j + 12 - (int)g) % 12] + ((g == 0 && j == 0) ? 8u : 0u);
-                const gl_t off = gl_mul((gl_t)(STARKHIP_LANE_K_OFFSET - 128 * rowsum), 0x0101010101010101ull % GL_P);
-                RC = gl_sub(POSEIDON_RC_HOST[12 * NEXT_ROUND[m] + g], off);
-            }
-            for (int b = 0; b < 8; b++) {
-                const uint32_t byte = (uint32_t)(RC >> (8 * b)) & 0xFFu;
-                T.rcb[m][b][lane] = live ? ((byte & 0x7Fu) | ((2u * (byte >> 7) + 40u) << 8) | (127u << 16) | (127u << 24)) : 0u;
-            }
-        }
-    return true;
-}
-static hipError_t ensure_lane_tables() {
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> g(mu);
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    static LaneTables T;
-    static bool built = false;
-    if (!built) {
-        if (!build_lane_tables(T)) return hipErrorInvalidValue;
-        built = true;
-    }
-    e = hipMemcpyToSymbol(HIP_SYMBOL(LANE_TABLES), &T, sizeof T);
-    if (e == hipSuccess) done[dev] = true;
-    return e;
-}
 
 // ---- the pair form (poseidon_dev.h): two lanes per leaf, for a LONE commitment of >= 32 768 leaves (1 024 waves: one per SIMD).
 // Same digests as leaf_hash_kernel.  Lane l < 32 of a wave absorbs columns 8 b .. 8 b + 5 of block b at point 32 w + l, lane l + 32
@@ -656,76 +390,6 @@ __global__ __launch_bounds__(256, 2) void leaf_hash_pair_kernel(const gl_t* __re
         digests[4 * j + 2] = gl_canon(pair_get(st.t1, 0));
         digests[4 * j + 3] = gl_canon(pair_get(st.t1, 1));
     }
-}
-static bool build_pair_tables(PairTables& T) {
-    static PoseidonMergedFours P;
-    build_poseidon_merged_fours(P);
-    if (!P.sums_fit) return false;
-    auto split = [](gl_t v) { return RcPair{v & 0xFFFFFFFFull, v >> 32}; };
-    memset(&T, 0, sizeof T);
-    for (unsigned h = 0; h < 2; h++) {
-        for (unsigned e = 0; e < 6; e++) T.rc0[h][e] = POSEIDON_RC_HOST[6 * h + e];
-        for (int t = 0; t < POSEIDON_MERGED_FOURS; t++)
-            for (unsigned r = 0; r < 6; r++) T.k4[t][h][r] = split(P.k4[t][6 * h + r]);
-        uint32_t* c = T.coef[h];
-        for (unsigned e = 0; e < 6; e++) {
-            c[e] = (uint32_t)P.M[0][6 * h + e];
-            c[8 + e] = (uint32_t)P.N2[0][6 * h + e];
-            c[16 + e] = (uint32_t)P.N3[0][6 * h + e];
-        }
-        c[16 + 6] = (uint32_t)P.N2[0][0];
-        for (unsigned r = 0; r < 6; r++) {
-            const unsigned g = 6 * h + r;
-            uint32_t* row = c + 24 + 16 * r;
-            for (unsigned jj = 0; jj < 12; jj++) row[jj] = (uint32_t)P.N4[g][(6 * h + jj) % 12];   // own six, then the partner's
-            row[12] = (uint32_t)P.N3[g][0];
-            row[13] = (uint32_t)P.N2[g][0];
-            row[14] = (uint32_t)P.M[g][0];
-        }
-    }
-    for (int t = 0; t < POSEIDON_MERGED_FOURS; t++) {   // the constants of the three dot products enter once: through the lower half
-        T.kf[t][0][0] = split(P.k1[t]);
-        T.kf[t][0][1] = split(P.k2[t]);
-        T.kf[t][0][2] = split(P.k3[t]);
-    }
-    // the matrix-pipe rounds' constants, as in build_lane_tables (the same offsets: a row still sums twelve signed bytes)
-    static const int CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-    static const int NEXT_ROUND[PAIR_MFMA_ROUNDS] = {1, 2, 3, 4, 25, 26, 27, 28, 29, 30};
-    for (int m = 0; m < PAIR_MFMA_ROUNDS; m++)
-        for (unsigned lane = 0; lane < 64; lane++) {
-            const unsigned row = lane & 31u, khalf = lane >> 5, i = (row & 3u) + 4u * (row >> 3), out_half = (row >> 2) & 1u;
-            if (khalf != 0 || i >= 12u) continue;
-            const unsigned g = 6u * out_half + i % 6u, pp = i / 6u;
-            uint64_t rowsum = 0;
-            for (int jj = 0; jj < 12; jj++) rowsum += (uint64_t)CIRC[(jj + 12 - (int)g) % 12] + ((g == 0 && jj == 0) ? 8u : 0u);
-            const gl_t off = gl_mul((gl_t)(STARKHIP_LANE_K_OFFSET - 128 * rowsum), 0x0101010101010101ull % GL_P);
-            const gl_t rc = NEXT_ROUND[m] < 30 ? POSEIDON_RC_HOST[12 * NEXT_ROUND[m] + g] : 0;
-            const gl_t RC = gl_sub(rc, off);
-            for (unsigned qq = 0; qq < 4; qq++) {
-                const uint32_t byte = (uint32_t)(RC >> (8 * (2 * qq + pp))) & 0xFFu;
-                T.rcb[m][qq][lane] = (byte & 0x7Fu) | ((2u * (byte >> 7) + 40u) << 8) | (127u << 16) | (127u << 24);
-            }
-        }
-    return true;
-}
-static hipError_t ensure_pair_tables() {
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    std::lock_guard<std::mutex> g(mu);
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    static PairTables T;
-    static bool built = false;
-    if (!built) {
-        if (!build_pair_tables(T)) return hipErrorInvalidValue;
-        built = true;
-    }
-    e = hipMemcpyToSymbol(HIP_SYMBOL(PAIR_TABLES), &T, sizeof T);
-    if (e == hipSuccess) done[dev] = true;
-    return e;
 }
 
 // Leaves stored row-major and already in tree order: leaf j = rows[j][0..width)
@@ -877,34 +541,51 @@ __global__ void pow_grind_kernel(const gl_t* __restrict__ base_state, int pos, u
 
 static inline unsigned nblocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
-hipError_t launch_leaf_hash(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st) {
-    size_t N = (size_t)1 << (log_n + rate_bits);
-    if (hipError_t e = ensure_quad_merged_tables(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(leaf_hash_kernel, dim3(nblocks(4 * N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
-    return hipGetLastError();
+hipError_t upload_table_once(const void* symbol, const void* image, size_t bytes, bool (&done)[64]) {
+    static std::mutex mu;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> g(mu);
+    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    if (done[dev]) return hipSuccess;
+    if (!image) return hipErrorInvalidValue;
+    e = hipMemcpyToSymbol(symbol, image, bytes);
+    if (e == hipSuccess) done[dev] = true;
+    return e;
 }
-hipError_t launch_leaf_hash_row(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st) {
-    size_t N = (size_t)1 << (log_n + rate_bits);
-    if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(leaf_hash_row_kernel, dim3(nblocks(16 * N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+static hipError_t ensure_quad_merged_tables() { return upload_table_once(&QUAD_MERGED, quad_merged_tables_host(), sizeof QUAD_MERGED, quad_uploaded); }
+static hipError_t ensure_row_merged_tables() { return upload_table_once(&ROW_MERGED, row_merged_tables_host(), sizeof ROW_MERGED, row_uploaded); }
+static hipError_t ensure_lane_tables() { return upload_table_once(&LANE_TABLES, lane_tables_host(), sizeof LANE_TABLES, lane_uploaded); }
+static hipError_t ensure_pair_tables() { return upload_table_once(&PAIR_TABLES, pair_tables_host(), sizeof PAIR_TABLES, pair_uploaded); }
+
+hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st) {
+    const size_t N = (size_t)1 << (log_n + rate_bits);
+    switch (form) {
+        case FORM_QUAD:
+            if (hipError_t e = ensure_quad_merged_tables(); e != hipSuccess) return e;
+            hipLaunchKernelGGL(leaf_hash_kernel, dim3(nblocks(4 * N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+            break;
+        case FORM_ROW:
+            if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
+            hipLaunchKernelGGL(leaf_hash_row_kernel, dim3(nblocks(16 * N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+            break;
+        case FORM_LANE:
+            if (hipError_t e = ensure_lane_tables(); e != hipSuccess) return e;
+            hipLaunchKernelGGL(leaf_hash_lane_kernel, dim3(nblocks(N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+            break;
+        case FORM_PAIR:
+            if (hipError_t e = ensure_pair_tables(); e != hipSuccess) return e;
+            hipLaunchKernelGGL(leaf_hash_pair_kernel, dim3(nblocks(N, 128)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+            break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, hipStream_t st) {
     if (!n_leaves) return hipSuccess;
     if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
     hipLaunchKernelGGL(verify_leaf_digest_kernel, dim3(nblocks(16 * n_leaves, 256)), dim3(256), 0, st, words, leaves, n_leaves, digests);
-    return hipGetLastError();
-}
-hipError_t launch_leaf_hash_lane(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st) {
-    size_t N = (size_t)1 << (log_n + rate_bits);
-    if (hipError_t e = ensure_lane_tables(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(leaf_hash_lane_kernel, dim3(nblocks(N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
-    return hipGetLastError();
-}
-hipError_t launch_leaf_hash_pair(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st) {
-    size_t N = (size_t)1 << (log_n + rate_bits);
-    if (hipError_t e = ensure_pair_tables(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(leaf_hash_pair_kernel, dim3(nblocks(N, 128)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
     return hipGetLastError();
 }
 hipError_t launch_leaf_hash_multi(const LeafHashBatch& B, unsigned count, size_t n_cols, unsigned log_n, unsigned rate_bits, hipStream_t st) {
@@ -936,27 +617,28 @@ hipError_t launch_permute_batch(gl_t* states, size_t n, hipStream_t st) {
     hipLaunchKernelGGL(permute_batch_kernel, dim3(nblocks(n, 64)), dim3(64), 0, st, states, n);
     return hipGetLastError();
 }
-// form: 0 the generic loop, 1 quad, 2 row, 3 lane, 4 pair (the "leaf_hash_form" numbering); variant 1 = the form's capacity-only last round
-// (quad, lane, pair).  The caller has checked both (permute_form_variants) and n >= 1; `in` and `out` do not overlap.
+// form: a LeafHashForm, FORM_AUTO = the generic loop; variant 1 = the form's capacity-only last round (quad, lane, pair).  The caller has
+// checked both (permute_form_variants) and n >= 1; `in` and `out` do not overlap.
 hipError_t launch_permute_batch_form(int form, int variant, const gl_t* in, gl_t* out, size_t n, hipStream_t st) {
     if (variant < 0 || (unsigned)variant >= permute_form_variants(form) || n == 0) return hipErrorInvalidValue;
-    if (form == 0) {
-        if (hipError_t e = hipMemcpyAsync(out, in, n * 96, hipMemcpyDeviceToDevice, st); e != hipSuccess) return e;
-        return launch_permute_batch(out, n, st);
-    }
-    if (form == 1) {
-        return launch_permute_quad_form(variant != 0, in, out, n, st);
-    } else if (form == 2) {
-        if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
-        hipLaunchKernelGGL(permute_row_form_kernel, dim3(nblocks(16 * n, 256)), dim3(256), 0, st, in, out, n);
-    } else if (form == 3) {
-        if (hipError_t e = ensure_lane_tables(); e != hipSuccess) return e;
-        if (variant) hipLaunchKernelGGL(permute_lane_form_kernel<true>, dim3(nblocks(n, 256)), dim3(256), 0, st, in, out, n);
-        else hipLaunchKernelGGL(permute_lane_form_kernel<false>, dim3(nblocks(n, 256)), dim3(256), 0, st, in, out, n);
-    } else {
-        if (hipError_t e = ensure_pair_tables(); e != hipSuccess) return e;
-        if (variant) hipLaunchKernelGGL(permute_pair_form_kernel<true>, dim3(nblocks(n, 128)), dim3(256), 0, st, in, out, n);
-        else hipLaunchKernelGGL(permute_pair_form_kernel<false>, dim3(nblocks(n, 128)), dim3(256), 0, st, in, out, n);
+    switch (form) {
+        case FORM_AUTO:
+            if (hipError_t e = hipMemcpyAsync(out, in, n * 96, hipMemcpyDeviceToDevice, st); e != hipSuccess) return e;
+            return launch_permute_batch(out, n, st);
+        case FORM_QUAD: return launch_permute_quad_form(variant != 0, in, out, n, st);
+        case FORM_ROW:
+            if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
+            hipLaunchKernelGGL(permute_row_form_kernel, dim3(nblocks(16 * n, 256)), dim3(256), 0, st, in, out, n);
+            break;
+        case FORM_LANE:
+            if (hipError_t e = ensure_lane_tables(); e != hipSuccess) return e;
+            if (variant) hipLaunchKernelGGL(permute_lane_form_kernel<true>, dim3(nblocks(n, 256)), dim3(256), 0, st, in, out, n);
+            else hipLaunchKernelGGL(permute_lane_form_kernel<false>, dim3(nblocks(n, 256)), dim3(256), 0, st, in, out, n);
+            break;
+        default:  // FORM_PAIR
+            if (hipError_t e = ensure_pair_tables(); e != hipSuccess) return e;
+            if (variant) hipLaunchKernelGGL(permute_pair_form_kernel<true>, dim3(nblocks(n, 128)), dim3(256), 0, st, in, out, n);
+            else hipLaunchKernelGGL(permute_pair_form_kernel<false>, dim3(nblocks(n, 128)), dim3(256), 0, st, in, out, n);
     }
     return hipGetLastError();
 }

@@ -5,17 +5,14 @@
 // leaf_hash_body passes its one LDS array of triple constants to poseidon_permute_quad_merged at all three call sites; a fourth call site
 // with another array in the same module undoes that and leaf_hash_kernel comes out differently scheduled (186 instead of 188 VGPRs).  So
 // that the shipped kernel stays byte for byte what it was, this kernel lives here with its own constant-memory image of the SAME
-// host-built tables (quad_merged_tables_host, kernels_hash.hip) and calls the same poseidon_permute_quad_merged (poseidon_dev.h).
+// host-built tables (quad_merged_tables_host, poseidon_tables.cpp) and calls the same poseidon_permute_quad_merged (poseidon_dev.h).
 #include <hip/hip_runtime.h>
-
-#include <mutex>
 
 #include "kernels.h"
 #include "poseidon_dev.h"
 
 namespace starkhip {
 
-const QuadMergedTables& quad_merged_tables_host();   // kernels_hash.hip
 __constant__ QuadMergedTables QUAD_MERGED_FORM;
 
 // Quad form: lane l of a quad holds words l, l + 4, l + 8.  CAP_ONLY specifies words 8 .. 11 (slot 2 of the four lanes).
@@ -65,19 +62,8 @@ __global__ __launch_bounds__(256) void permute_quad_form_kernel(const gl_t* __re
 
 hipError_t launch_permute_quad_form(bool cap_only, const gl_t* in, gl_t* out, size_t n, hipStream_t st) {
     if (n == 0) return hipErrorInvalidValue;
-    {
-        static std::mutex mu;
-        static bool done[64] = {false};
-        int dev = 0;
-        if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
-        std::lock_guard<std::mutex> g(mu);
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!done[dev]) {
-            const QuadMergedTables& T = quad_merged_tables_host();
-            if (hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(QUAD_MERGED_FORM), &T, sizeof T); e != hipSuccess) return e;
-            done[dev] = true;
-        }
-    }
+    static bool uploaded[64];  // QUAD_MERGED_FORM's own: kernels_hash.hip's QUAD_MERGED is another symbol of the same type
+    if (hipError_t e = upload_table_once(&QUAD_MERGED_FORM, quad_merged_tables_host(), sizeof QUAD_MERGED_FORM, uploaded); e != hipSuccess) return e;
     const unsigned blocks = (unsigned)((4 * n + 255) / 256);
     if (cap_only) hipLaunchKernelGGL(permute_quad_form_kernel<true>, dim3(blocks), dim3(256), 0, st, in, out, n);
     else hipLaunchKernelGGL(permute_quad_form_kernel<false>, dim3(blocks), dim3(256), 0, st, in, out, n);

@@ -39,9 +39,8 @@ GL_HD void acc_mad(acc128& a, uint64_t s, uint32_t k) {
     a.hi += (p1 >> 32) + carry;
 }
 
-// MDS layer: out[r] = sum_i s[(i + r) % 12] * CIRC[i] + (r == 0) * 8 * s[0]
+// MDS layer: out[r] = sum_i s[(i + r) % 12] * POSEIDON_MDS_CIRC[i] + (r == 0) * 8 * s[0]
 GL_HD void poseidon_mds(gl_t* s) {
-    const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     // split into 32-bit halves: sums stay below 2^32 * 12 * 41 < 2^42, no carries needed
     // duplicated (lo[i + 12] == lo[i]) so the circulant index i + r needs no modulo (host compilers do not unroll this)
     uint64_t lo[24], hi[24];
@@ -56,8 +55,8 @@ GL_HD void poseidon_mds(gl_t* s) {
         uint64_t al = 0, ah = 0;
 #pragma unroll
         for (int i = 0; i < 12; i++) {
-            al += lo[i + r] * CIRC[i];
-            ah += hi[i + r] * CIRC[i];
+            al += lo[i + r] * POSEIDON_MDS_CIRC[i];
+            ah += hi[i + r] * POSEIDON_MDS_CIRC[i];
         }
         if (r == 0) {
             al += lo[0] * 8;

@@ -15,6 +15,7 @@
 
 #include "gl_dev.h"
 #include "poseidon.h"
+#include "poseidon_tables.h"  // RcPair and the host-built tables the kernels read
 
 namespace starkhip {
 
@@ -186,12 +187,6 @@ __device__ __forceinline__ gl_t sbox_lane0_nc(gl_t s0, bool lane0) {
     return lane0 ? x7 : s0;
 }
 
-// Round constants as the kernels stage them in LDS: per constant two 64-bit words (low half, high half), so each
-// is directly the 64-bit addend of the first multiply-add of its accumulator.
-struct RcPair {
-    uint64_t lo, hi;
-};
-
 // MDS layer; the accumulators start from this lane's three round constants of the NEXT round.
 // cf: this lane's twelve circulant coefficients (above); diag0 = 8 on lane 0, 0 elsewhere (MDS_MATRIX_DIAG has a single non-zero
 // entry, at element 0 = lane 0's slot 0).  CAP_ONLY: only slot 2 (the capacity element) is computed, s0 and s1 are left as
@@ -255,14 +250,6 @@ struct QuadMergedCoef {
     uint32_t m00;           // M[0][0] on lane 0, 0 elsewhere (the x_2 term of y2 is added once)
     uint32_t b2[3], b3[3];  // (M Mz)[l + 4 mo][0], M[l + 4 mo][0]
     uint32_t cf[12];        // the circulant coefficients of the plain layers (poseidon_mds_quad)
-};
-static const int QUAD_MERGED_TRIPLES = 7;  // = POSEIDON_MERGED_TRIPLES (poseidon_merged.h): partial rounds 0..20; the 22nd stays a plain round
-
-// The host-built image of the per-lane tables (kernels_hash.hip: build_quad_merged_tables), uploaded to constant memory once per device
-struct QuadMergedTables {
-    uint32_t coef[4][64];  // per lane: n3[3][12], n1[3], n2[3], m00 (lane 0 only), b2[3], b3[3], pad to 50, cf[12] at 50, pad
-    RcPair tk[2 * QUAD_MERGED_TRIPLES];       // k1, k2 per triple
-    RcPair tk3[4][3 * QUAD_MERGED_TRIPLES];   // per lane: k3[mo] per triple
 };
 
 // y is the same value in the four lanes of a quad; returns y^7 in all of them.  Even lanes form x^3, odd lanes x^4 in one
@@ -488,11 +475,6 @@ struct RowConsts {
     // M[e][0]); misc1 = (N3[e][0], M[0][0] on lane 0, N2[0][0] on lane 0, -).  All zero on lanes 12 .. 15.
     row_u32x4 n3k0, n3k1, n3k2, misc0, misc1;
 };
-// Per-lane coefficient rows of the merged triples, built on the host once per device (kernels_hash.hip)
-struct RowMergedTables {
-    uint32_t coef[16][20];                       // [lane]: n3k[12], then misc0[4], misc1[4]
-    RcPair k1[7], k2[7], k3[7][12];              // POSEIDON_MERGED_TRIPLES = 7
-};
 __device__ __forceinline__ void row_consts_init(RowConsts& K, unsigned e, const uint32_t* __restrict__ coef /* RowMergedTables::coef[e] */) {
     constexpr uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     K.c0 = e == 0 ? 25u : 17u;
@@ -630,25 +612,13 @@ __device__ __forceinline__ gl_t poseidon_permute_row(gl_t s, const RcPair* __res
 // Everything is uniform over the wave here -- round constants, the merged layers' coefficients -- so it comes from one LDS image by
 // broadcast reads (a scalar-register formulation would need some 230 coefficients per merge in 100 SGPRs).
 typedef const __attribute__((address_space(3))) gl_t* lds_gl_ptr;
-struct LaneTables {
-    RcPair rc[31][12];         // round constants in halves; rc[30] = 0 (the "next round" of the last one)
-    RcPair kf[5][3];           // k1, k2, k3 of the merged fours (poseidon_merged.h)
-    RcPair k4[5][12];
-    uint32_t row[12][16];      // per output row of the dense layer: N4[r][0 .. 11], N3[r][0], N2[r][0], M[r][0], -
-    uint32_t m0[12], n20[12];  // row 0 of M and of N2 (the first two intermediate dot products) ...
-    uint32_t n30[16];          // ... and of N3, then N2[0][0] (the third)
-    // The rounds whose circulant layer runs on the matrix pipe (full rounds 0 .. 3 and 26 .. 28, the plain partial rounds 24 and 25;
-    // lane_round_asm.inc, tools/gen_lane_round_asm.py): per round, byte plane and LANE the fourth dword of the weight tile -- the constant
-    // bytes that ride in the spare K-values (kernels_hash.hip: build_lane_tables)
-    uint32_t rcb[9][8][64];
-    gl_t rc0[12];              // the first round's constants as whole words (added to the state at the start of every permutation)
-};
 
 // ---- the lane form's rounds as scheduled asm blocks (tools/gen_lane_round_asm.py -> lane_round_asm.inc; the block sizes are in its
 // header), LDS loads a row ahead with counted waits -- hipcc made 1337 slots of a full round and 1464 of three merged partial rounds, a
 // third of them wait states (history section 5).  The state lives in three 8-register tuples bound to v[80:103]: the rate is the first
 // two, the capacity the third.  Partial rounds 4 .. 23 run FOUR at a time (poseidon_merged.h), 24 and 25 as plain rounds.
 #include "lane_round_asm.inc"
+static_assert(STARKHIP_LANE_K_OFFSET == LANE_K_OFFSET, "poseidon_tables.cpp packs the matrix-pipe rounds' constants for this offset");
 typedef uint32_t lane_u32x8 __attribute__((ext_vector_type(8)));
 struct LaneState {
     lane_u32x8 t0, t1, t2;
@@ -800,17 +770,6 @@ __device__ __forceinline__ void poseidon_permute_lane_asm(LaneState& st, const L
 #else
 #include "pair_round_asm.inc"
 #endif
-constexpr int PAIR_MFMA_ROUNDS = 10;   // full rounds 0 .. 3, the plain partial rounds 24 and 25, full rounds 26 .. 29
-struct PairTables {
-    gl_t rc0[2][6];                 // [half]: the first round's constants of the half's elements
-    RcPair kf[5][2][3];             // [merged four][half]: k1, k2, k3 -- in the lower half only (the sums are added across the pair), zero in the upper
-    RcPair k4[5][2][6];             // [merged four][half][local output]
-    // per half, 480 bytes: rows 0 of M, N2 and N3 against the half's own six elements (8 dwords each; N2[0][0] in dword 6 of the third),
-    // then per local output r (g = 6 half + r) sixteen dwords: N4[g][own six], N4[g][the partner's six, neighbours crossed], N3[g][0],
-    // N2[g][0], M[g][0], 0
-    uint32_t coef[2][120];
-    uint32_t rcb[PAIR_MFMA_ROUNDS][4][64];   // per matrix-pipe round, instruction and LANE: dword 3 of the weight tile (the constants' bytes)
-};
 typedef uint32_t pair_u32x4 __attribute__((ext_vector_type(4)));
 struct PairState {
     pair_u32x4 t0, t1, t2;          // the lane's six elements: (0, 1), (2, 3), (4, 5), low dword first

@@ -124,12 +124,11 @@ AVX512_TARGET inline __m256i sbox_4(__m256i x) {
 #define MV_A(x) _mm512_load_si512((const void*)(x))
 #define MV_B(x) _mm256_load_si256((const __m256i*)((x) + 8))
 
-// MDS layer: out[r] = sum_i CIRC[i] * s[(i + r) % 12] + (r == 0) * 8 * s[0]
+// MDS layer: out[r] = sum_i POSEIDON_MDS_CIRC[i] * s[(i + r) % 12] + (r == 0) * 8 * s[0]
 // With `partial` the vector's element 0 is zero and x0 is the value it stands for: its column of the matrix is added at
 // the end, so the scalar S-box that produces x0 runs beside the vector part instead of in front of it.
 template <bool partial>
 AVX512_TARGET inline void mds_t(V12& s, gl_t x0) {
-    static const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     alignas(64) uint64_t lo[24], hi[24];
     const __m512i m32 = _mm512_set1_epi64((long long)EPS);
     const __m256i m32h = _mm256_set1_epi64x((long long)EPS);
@@ -146,15 +145,15 @@ AVX512_TARGET inline void mds_t(V12& s, gl_t x0) {
     __m512i La = _mm512_setzero_si512(), Ha = _mm512_setzero_si512();
     __m256i Lb = _mm256_setzero_si256(), Hb = _mm256_setzero_si256();
     for (int i = 0; i < 12; i++) {  // fully unrolled by the compiler
-        const __m512i c = _mm512_set1_epi64((long long)CIRC[i]);
-        const __m256i ch = _mm256_set1_epi64x((long long)CIRC[i]);
+        const __m512i c = _mm512_set1_epi64((long long)POSEIDON_MDS_CIRC[i]);
+        const __m256i ch = _mm256_set1_epi64x((long long)POSEIDON_MDS_CIRC[i]);
         La = _mm512_add_epi64(La, _mm512_mul_epu32(_mm512_loadu_si512((const void*)(lo + i)), c));      // outputs r = 0..7 see s[r + i]
         Ha = _mm512_add_epi64(Ha, _mm512_mul_epu32(_mm512_loadu_si512((const void*)(hi + i)), c));
         Lb = _mm256_add_epi64(Lb, _mm256_mul_epu32(_mm256_loadu_si256((const __m256i*)(lo + 8 + i)), ch));  // r = 8..11
         Hb = _mm256_add_epi64(Hb, _mm256_mul_epu32(_mm256_loadu_si256((const __m256i*)(hi + 8 + i)), ch));
     }
     if (partial) {
-        // column 0: CIRC[(12 - r) % 12] for output r, + 8 on output 0
+        // column 0: POSEIDON_MDS_CIRC[(12 - r) % 12] for output r, + 8 on output 0
         static const long long C0A[8] = {17 + 8, 20, 34, 18, 39, 13, 13, 28};
         static const long long C0B[4] = {2, 16, 41, 15};
         const __m512i ca = _mm512_loadu_si512((const void*)C0A);
@@ -192,10 +191,9 @@ struct alignas(64) MdsColumns {
 };
 const MdsColumns& mds_columns() {
     static const MdsColumns C = [] {
-        static const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
         MdsColumns c = {};
         for (int j = 0; j < 12; j++)
-            for (int r = 0; r < 12; r++) c.col[j][r] = CIRC[(j - r + 12) % 12] + ((r == 0 && j == 0) ? 8 : 0);
+            for (int r = 0; r < 12; r++) c.col[j][r] = POSEIDON_MDS_CIRC[(j - r + 12) % 12] + ((r == 0 && j == 0) ? 8 : 0);
         return c;
     }();
     return C;

@@ -22,31 +22,35 @@ struct PoseidonMergedTables {
     gl_t k1[POSEIDON_MERGED_TRIPLES], k2[POSEIDON_MERGED_TRIPLES], k3[POSEIDON_MERGED_TRIPLES][12];
 };
 
-inline void build_poseidon_merged_tables(PoseidonMergedTables& T) {
-    static const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-    uint64_t Mz[12][12];
+// M = the MDS matrix, Mz = M with row 0 zeroed; exact integer products; a matrix times a vector mod p
+inline void merged_mds(uint64_t (&M)[12][12], uint64_t (&Mz)[12][12]) {
     for (int i = 0; i < 12; i++)
         for (int j = 0; j < 12; j++) {
-            T.M[i][j] = CIRC[(j - i + 12) % 12] + ((i == 0 && j == 0) ? 8 : 0);
-            Mz[i][j] = i == 0 ? 0 : T.M[i][j];
+            M[i][j] = POSEIDON_MDS_CIRC[(j - i + 12) % 12] + ((i == 0 && j == 0) ? 8 : 0);
+            Mz[i][j] = i == 0 ? 0 : M[i][j];
         }
-    auto mul = [](const uint64_t (&a)[12][12], const uint64_t (&b)[12][12], uint64_t (&o)[12][12]) {
-        for (int i = 0; i < 12; i++)
-            for (int j = 0; j < 12; j++) {
-                uint64_t acc = 0;
-                for (int k = 0; k < 12; k++) acc += a[i][k] * b[k][j];
-                o[i][j] = acc;
-            }
-    };
-    mul(T.M, Mz, T.N2);
-    mul(T.N2, Mz, T.N3);
-    auto matvec_mod = [](const uint64_t (&a)[12][12], const gl_t* v, gl_t* o) {
-        for (int i = 0; i < 12; i++) {
-            unsigned __int128 acc = 0;
-            for (int j = 0; j < 12; j++) acc += (unsigned __int128)a[i][j] * v[j];
-            o[i] = (gl_t)(acc % GL_P);
+}
+inline void merged_mul(const uint64_t (&a)[12][12], const uint64_t (&b)[12][12], uint64_t (&o)[12][12]) {
+    for (int i = 0; i < 12; i++)
+        for (int j = 0; j < 12; j++) {
+            uint64_t acc = 0;
+            for (int k = 0; k < 12; k++) acc += a[i][k] * b[k][j];
+            o[i][j] = acc;
         }
-    };
+}
+inline void merged_matvec_mod(const uint64_t (&a)[12][12], const gl_t* v, gl_t* o) {
+    for (int i = 0; i < 12; i++) {
+        unsigned __int128 acc = 0;
+        for (int j = 0; j < 12; j++) acc += (unsigned __int128)a[i][j] * v[j];
+        o[i] = (gl_t)(acc % GL_P);
+    }
+}
+
+inline void build_poseidon_merged_tables(PoseidonMergedTables& T) {
+    uint64_t Mz[12][12];
+    merged_mds(T.M, Mz);
+    merged_mul(T.M, Mz, T.N2);
+    merged_mul(T.N2, Mz, T.N3);
     const uint64_t* RC = POSEIDON_RC_HOST;
     for (int t = 0; t < POSEIDON_MERGED_TRIPLES; t++) {
         const int r = 4 + 3 * t;
@@ -55,11 +59,11 @@ inline void build_poseidon_merged_tables(PoseidonMergedTables& T) {
             c1z[i] = i ? RC[12 * (r + 1) + i] : 0;
             c2z[i] = i ? RC[12 * (r + 2) + i] : 0;
         }
-        matvec_mod(T.M, c1z, a);
+        merged_matvec_mod(T.M, c1z, a);
         T.k1[t] = RC[12 * (r + 1)];
         T.k2[t] = gl_add(a[0], RC[12 * (r + 2)]);
-        matvec_mod(T.N2, c1z, a);
-        matvec_mod(T.M, c2z, b);
+        merged_matvec_mod(T.N2, c1z, a);
+        merged_matvec_mod(T.M, c2z, b);
         for (int i = 0; i < 12; i++) T.k3[t][i] = gl_add(gl_add(a[i], b[i]), RC[12 * (r + 3) + i]);
     }
 }
@@ -81,24 +85,11 @@ struct PoseidonMergedFours {
 };
 
 inline void build_poseidon_merged_fours(PoseidonMergedFours& T) {
-    static const uint32_t CIRC[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     uint64_t Mz[12][12];
-    for (int i = 0; i < 12; i++)
-        for (int j = 0; j < 12; j++) {
-            T.M[i][j] = CIRC[(j - i + 12) % 12] + ((i == 0 && j == 0) ? 8 : 0);
-            Mz[i][j] = i == 0 ? 0 : T.M[i][j];
-        }
-    auto mul = [](const uint64_t (&a)[12][12], const uint64_t (&b)[12][12], uint64_t (&o)[12][12]) {
-        for (int i = 0; i < 12; i++)
-            for (int j = 0; j < 12; j++) {
-                uint64_t acc = 0;
-                for (int k = 0; k < 12; k++) acc += a[i][k] * b[k][j];
-                o[i][j] = acc;
-            }
-    };
-    mul(T.M, Mz, T.N2);
-    mul(T.N2, Mz, T.N3);
-    mul(T.N3, Mz, T.N4);
+    merged_mds(T.M, Mz);
+    merged_mul(T.M, Mz, T.N2);
+    merged_mul(T.N2, Mz, T.N3);
+    merged_mul(T.N3, Mz, T.N4);
     T.sums_fit = true;
     for (int g = 0; g < 12; g++) {
         unsigned __int128 tot = T.N3[g][0] + T.N2[g][0] + T.M[g][0];
@@ -108,13 +99,6 @@ inline void build_poseidon_merged_fours(PoseidonMergedFours& T) {
         const unsigned __int128 limit = ((unsigned __int128)1 << 64) - ((unsigned __int128)1 << 32);
         if (tot * 0xFFFFFFFFull + 0xFFFFFFFFull >= limit) T.sums_fit = false;
     }
-    auto matvec_mod = [](const uint64_t (&a)[12][12], const gl_t* v, gl_t* o) {
-        for (int i = 0; i < 12; i++) {
-            unsigned __int128 acc = 0;
-            for (int j = 0; j < 12; j++) acc += (unsigned __int128)a[i][j] * v[j];
-            o[i] = (gl_t)(acc % GL_P);
-        }
-    };
     const uint64_t* RC = POSEIDON_RC_HOST;
     for (int t = 0; t < POSEIDON_MERGED_FOURS; t++) {
         const int r = 4 + 4 * t;
@@ -124,15 +108,15 @@ inline void build_poseidon_merged_fours(PoseidonMergedFours& T) {
             c2z[i] = i ? RC[12 * (r + 2) + i] : 0;
             c3z[i] = i ? RC[12 * (r + 3) + i] : 0;
         }
-        matvec_mod(T.M, c1z, a);
+        merged_matvec_mod(T.M, c1z, a);
         T.k1[t] = RC[12 * (r + 1)];
         T.k2[t] = gl_add(a[0], RC[12 * (r + 2)]);
-        matvec_mod(T.N2, c1z, a);
-        matvec_mod(T.M, c2z, b);
+        merged_matvec_mod(T.N2, c1z, a);
+        merged_matvec_mod(T.M, c2z, b);
         T.k3[t] = gl_add(gl_add(a[0], b[0]), RC[12 * (r + 3)]);
-        matvec_mod(T.N3, c1z, a);
-        matvec_mod(T.N2, c2z, b);
-        matvec_mod(T.M, c3z, c);
+        merged_matvec_mod(T.N3, c1z, a);
+        merged_matvec_mod(T.N2, c2z, b);
+        merged_matvec_mod(T.M, c3z, c);
         for (int i = 0; i < 12; i++) T.k4[t][i] = gl_add(gl_add(gl_add(a[i], b[i]), c[i]), RC[12 * (r + 4) + i]);
     }
 }

@@ -280,7 +280,7 @@ int ProveCall::leaf_hash_on_host() {
         c->hs->abandon_small();
         c->hash_requested = true;
     }
-    c->hash_timing.form = 4;
+    c->hash_timing.form = SENT_HOST;
     c->hash_timing.group = 1;
     c->host_lde.resize(C * N);
     HIPCHK(hipMemcpyAsync(c->host_lde.data(), c->lde.p, C * N * 8, hipMemcpyDeviceToHost, st));
@@ -311,7 +311,7 @@ int ProveCall::leaf_hash_on_host() {
 // ---- phase 2: Merkle tree over bit-reversed LDE rows
 int ProveCall::trace_merkle() {
     HIPCHK(hipEventRecord(c->kev[0], st));
-    if (s.N <= (size_t)c->opt_host_commit_leaves && s.C >= 64 && c->opt_leaf_hash_form == 0) {
+    if (s.N <= (size_t)c->opt_host_commit_leaves && s.C >= 64 && c->opt_leaf_hash_form == FORM_AUTO) {
         if (int rc = leaf_hash_on_host()) return rc;
     } else if (c->hs) {  // pooled: the scheduler decides when this commitment runs and which others share its launch
         c->hash_requested = true;
@@ -420,7 +420,7 @@ int ProveCall::quotient_commit() {
     for (gl_t v : quot_tail)
         if (v != 0) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
     HIPCHK(run_lde(c, c->qcoef.as<gl_t>(), nullptr, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, 1));
-    HIPCHK(launch_leaf_hash(c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
+    HIPCHK(launch_leaf_hash_form(FORM_QUAD, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
     HIPCHK(launch_merkle_levels(c->qdigests.as<gl_t>(), s.log_N, s.cap_h, st));
     quot_cap.resize(4 * s.ncap);
     HIPCHK(read_back(c, quot_cap.data(), c->qdigests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
@@ -721,7 +721,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     (void)hipEventElapsedTime(&c->ktimings[0], c->kev[4], c->kev[5]);
     // pooled: the commitment kernel's own duration on the scheduler's launch stream (kev[0] .. kev[1] on this context's stream would
     // include the wait for its group to form)
-    if (c->hs && c->hash_timing.form != 4) (void)hipEventElapsedTime(&c->ktimings[1], c->hash_timing.t0, c->hash_timing.t1);
+    if (c->hs && c->hash_timing.form != SENT_HOST) (void)hipEventElapsedTime(&c->ktimings[1], c->hash_timing.t0, c->hash_timing.t1);
     else (void)hipEventElapsedTime(&c->ktimings[1], c->kev[0], c->kev[1]);
     *proof_out = out;
     *proof_words = s.pl.total;

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "gl.h"
+#include "kernels.h"  // LeafHashSent
 
 namespace starkhip {
 
@@ -71,15 +72,15 @@ class HashService {
     void abandon_big();
     void abandon_small();
     void set_big_queued(int n);  // the pool's count of big jobs that have not started yet (queued, or their trace being recorded)
-    // Leaf digests of the coset-major LDE `mat` (kernels_hash.hip: launch_leaf_hash) into `digests`, ordered after everything
+    // Leaf digests of the coset-major LDE `mat` (kernels_hash.hip: launch_leaf_hash_form) into `digests`, ordered after everything
     // enqueued on `st` so far; when this returns, `st` has been made to wait for the launch (the caller goes on enqueueing).
     // `ready` / `done` are events owned by the caller's context.
     // `timing` (optional): two timing-enabled events of the caller's, recorded on the LAUNCH stream right before and after the kernel
-    // that hashes this commitment (its own duration, not the wait for its group), and how it went out: form 0 = quad, 1 = row,
-    // 2 = one grid merged with other proofs' commitments (quad form), 3 = lane; group = commitments launched side by side with it.
+    // that hashes this commitment (its own duration, not the wait for its group), and how it went out: form = a LeafHashSent
+    // (kernels.h); group = commitments launched side by side with it.
     struct Timing {
         hipEvent_t t0 = nullptr, t1 = nullptr;
-        int form = 0;
+        int form = SENT_QUAD;
         unsigned group = 1;
     };
     hipError_t hash(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st, hipEvent_t ready,

@@ -1,5 +1,7 @@
 """CPU tests: oracle vs known-answer vectors, product host code vs oracle, C-ABI exports."""
 import ctypes
+import hashlib
+import json
 import os
 import re
 
@@ -164,6 +166,24 @@ def test_merged_partial_round_tables_reproduce_the_permutation():
     import starky_bls12_381_amd as S
     assert S.lib.starkhip_selfcheck_hash_tables(200) == 0
 
+
+def test_hash_table_images_match_the_recorded_ones():
+    """The tables the leaf-hash kernels read from constant memory (csrc/poseidon_tables.cpp), byte for byte against
+    tests/golden/hash_table_images.json: size and SHA-256 of each form's image, recorded from the builders as they stood inside
+    kernels_hash.hip before they became host code (one packer of the matrix-pipe rounds' constant bytes for the lane and pair forms
+    since).  A wrong byte here is a wrong digest on the GPU."""
+    f = S.lib.starkhip_hash_table_image
+    f.restype = ctypes.c_size_t
+    f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "hash_table_images.json")))
+    assert sorted(g["form"] for g in golden.values()) == [1, 2, 3, 4]
+    for name, g in golden.items():
+        assert f(g["form"], None, 0) == g["bytes"], name
+        buf = ctypes.create_string_buffer(g["bytes"] + 8)
+        assert f(g["form"], buf, g["bytes"] - 1) == g["bytes"] and buf.raw == bytes(g["bytes"] + 8), name   # too small: nothing written
+        assert f(g["form"], buf, g["bytes"]) == g["bytes"] and buf.raw[g["bytes"]:] == bytes(8), name
+        assert hashlib.sha256(buf.raw[:g["bytes"]]).hexdigest() == g["sha256"], name
+    assert f(0, None, 0) == 0 and f(5, None, 0) == 0 and f(-1, None, 0) == 0
 
 
 def test_lde_launch_plan_never_overwrites_a_column_it_has_not_read():

@@ -3,6 +3,10 @@ capacity-only last rounds the leaf kernels use -- on boundary states at every ro
 inverting the rounds; tests/test_poseidon_steering_cpu.py shows the helper right), at every position of a wave and with partly
 filled last waves.  Prover.poseidon_permute_batch(states, form, variant) runs the very functions the leaf kernels call on whole
 12-word states.  Every comparison is equality of integers against the permutation in Python integers."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -12,6 +16,7 @@ import starky_bls12_381_amd as S
 
 pytestmark = pytest.mark.gpu
 P = S.P
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FORM_NAMES = {0: "generic", 1: "quad", 2: "row", 3: "lane", 4: "pair"}
 FORM_VARIANTS = [(0, 0), (1, 0), (1, 1), (2, 0), (3, 0), (3, 1), (4, 0), (4, 1)]
@@ -119,3 +124,44 @@ def test_merkle_cap_with_round_0_steered_leaves(prover, form, ncols):
     finally:
         prover.set_option("leaf_hash_form", 0)
     assert np.array_equal(cap, O.merkle_cap(np.ascontiguousarray(mat.T), 2))
+
+
+# One fresh process: for the quad form and then the row form, the permutation entry and a commitment in that form, in the order
+# given.  The quad form's two entries read two constant-memory symbols of one type (kernels_hash.hip, kernels_hash_quad_form.hip); the row
+# form's read one.  64 leaves x 9 columns: one full block and a remainder of one, in a part-filled last wave.
+UPLOAD_ORDER_CHILD = """
+import os, sys
+sys.path[:0] = [%(root)r, os.path.join(%(root)r, "tests")]
+import numpy as np
+import oracle_lib as O
+import starky_bls12_381_amd as S
+rng = np.random.default_rng(0x0DE2)
+states = rng.integers(0, S.P, size=(5, 12), dtype=np.uint64)
+want = np.array([S.poseidon_permute_host(s) for s in states])
+mat = rng.integers(0, S.P, size=(9, 64), dtype=np.uint64)
+want_cap = O.merkle_cap(np.ascontiguousarray(mat.T), 2)
+pv = S.Prover(0)
+def permute(form):
+    assert np.array_equal(pv.poseidon_permute_batch(states, form, 0), want), ("permutation", form)
+def commit(form):
+    pv.set_option("leaf_hash_form", form)
+    try:
+        cap = pv.merkle_cap(mat, 2)
+    finally:
+        pv.set_option("leaf_hash_form", 0)
+    assert np.array_equal(cap, want_cap), ("cap", form)
+for form in (1, 2):
+    for step in %(order)s:
+        step(form)
+pv.close()
+print("upload order ok")
+"""
+
+
+def test_each_table_is_uploaded_before_its_first_use_whichever_entry_comes_first():
+    """Each constant-memory table is uploaded by the first launch that reads it, and by every entry that can be that launch: in a fresh
+    process (the suite's own order would have uploaded everything long before), the permutation entry before the commitment and the
+    other way round.  Against the host permutation and the oracle's cap."""
+    for order in ("(permute, commit)", "(commit, permute)"):
+        r = subprocess.run([sys.executable, "-c", UPLOAD_ORDER_CHILD % {"root": ROOT, "order": order}], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and "upload order ok" in r.stdout, order + "\n" + r.stdout[-2000:] + r.stderr[-4000:]

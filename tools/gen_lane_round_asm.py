@@ -188,7 +188,7 @@ def block_four():
 # sbyte = byte XOR 0x80 read as signed = byte - 128 (the pipe's operands are signed).  The spare K-values 12 .. 15 carry the constants:
 # the B side holds (1, 64, 127, 127) in every lane, the A side -- per row, round and plane, one dword per lane from LDS -- holds
 # (c7, 2 m + 40, 127, 127) with c7 + 128 m = byte b of a 64-bit constant RC[g]: together + RC byte + 34 818, which makes every S_b[g]
-# non-negative (34 818 >= 128 * 272, the largest row sum) and lets the host fold the offsets into RC (kernels_hash.hip).
+# non-negative (34 818 >= 128 * 272, the largest row sum) and lets the host fold the offsets into RC (poseidon_tables.cpp).
 # Recombination: lo = S0 + S1 2^8 + S2 2^16 + S3 2^24 (two v_lshl_add_u32 and one multiply-add by 2^16), hi likewise from planes 4 .. 7,
 # then the fold lo + hi 2^32 the multiply-add form already uses.  Per round 24 XORs + 48 byte permutes + 8 LDS dwords + 8 MFMA (which
 # cost the vector issue < 1 slot each, measured by the probe) + 72 + 48 instead of 288 multiply-adds + 48 + 12 LDS rows.
