@@ -262,7 +262,15 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
                            const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness, uint64_t** proof, size_t* proof_words);
 
 /* Tuning knobs of a context (defaults are the measured best; tests and profiling tools use them to reach the other code
- * paths): "quotient_impl" 0 = tiled evaluator / 1 = op-stream interpreter, "quotient_chunks" (0 = automatic),
+ * paths): "quotient_impl" 0 = tiled evaluator / 1 = op-stream interpreter, "quotient_cosets" (tiled evaluator only; 0, the default =
+ * every constraint is evaluated on the cosets of n_rows points that its own degree needs -- max(1, d - 1) of them for d cell factors, d
+ * for a first-row or last-row constraint -- and the classes' values are recombined into the quotient's coefficient chunks; 1 = every
+ * constraint on all 2^quotient_degree_bits cosets and one inverse transform of all values.  For a trace that satisfies the AIR the two
+ * give the same proof bytes.  For a trace that violates a constraint they do not: the violated class's sum is not divisible by Z_H, so
+ * its values on a few cosets and on all of them interpolate to different polynomials; either proof is rejected by the verifier, an AIR
+ * whose quotient has a spare coset (degree 4) fails with STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE either way, and starkhip_check_trace is the
+ * tool for such a trace.  AIRs of degree above 5, the profiling modes and the comparison of the two evaluators always run as 1),
+ * "quotient_chunks" (0 = automatic),
  * "quotient_waves", "quotient_slots", "lde_closed_forms" (1 = constant and unit-vector trace columns take their closed-form LDE
  * instead of five transforms, 0 = every column is transformed; same bytes either way; traces of 2^14 rows and more have no closed forms and transform every column), "host_commit_leaves" (default 64: trace commitments of at most this many leaves -- FP12Mul's 32 -- are hashed by host threads with the
  * challenger's permutation, 0.8 us against 5.6 us per permutation of a lone GPU wave; 0 = never; only with "leaf_hash_form" 0), "leaf_hash_form" (0 = a context on its own
@@ -570,6 +578,19 @@ int starkhip_fri_geometry(const starkhip_config_t* cfg, unsigned log_n, unsigned
  * acc = acc * alpha + mask * c_k over all constraints.  stats = {chunks, supergroups, pieces, records, LDS cell records,
  * direct loads, tiles, term contributions}.  0 = equal, STARKHIP_ERR_VERIFY = different, BAD_SHAPE = malformed plan. */
 int starkhip_quotient_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[8]);
+/* The class of every constraint of `air` (n = its constraint count): the number of cosets of n_rows points that fix the constraint's
+ * part of the quotient -- max(1, d - 1) for a plain or transition constraint with d cell factors (gates + longest monomial), d for a
+ * first-row or last-row one, at most the quotient factor. */
+int starkhip_quotient_classes(starkhip_air_t air, uint8_t* classes, size_t n);
+/* The constants that turn the classes' values on their cosets into the quotient's coefficient chunks, 656 words: [t] the inverse of
+ * coset t's shift g_t = 7 w^t (w of order rows << quotient_degree_bits); [8 + 8 t + m] c_t^m with c_t = g_t^rows; [72 + (8 k + m) 8 + t]
+ * entry (m, t) of the inverse of the k x k Vandermonde matrix c_t^m. */
+int starkhip_quotient_solve_table(unsigned log_rows, unsigned quotient_degree_bits, uint64_t* out, size_t n);
+/* CPU replay of the per-class plans ("quotient_cosets" = 0) on one random frame: every class's chunks give the plain fold restricted
+ * to the constraints of that class, the classes add up to the whole fold, and the plan of coset t holds the classes above t and no other.
+ * stats: [0] classes, [1] cosets, [2] chunks, [3] work rows, [4] records, [5] piece ends, [6] tile phases, [7] contributions,
+ * [8 + c] constraints of class c + 1, [24 + t] chunks of coset t. */
+int starkhip_quotient_class_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[32]);
 /* host-side permutation (the one the Fiat-Shamir challenger uses) */
 void starkhip_poseidon_permute_host(uint64_t state[12]);
 /* n chained host permutations; which = 0: the challenger's tuned permutation, 1: the portable loop */

@@ -363,6 +363,35 @@ def quotient_plan_check(air, want_chunks=4, seed=1):
                     (int(x) for x in stats)))
 
 
+lib.starkhip_quotient_classes.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_size_t]
+lib.starkhip_quotient_solve_table.argtypes = [C.c_uint, C.c_uint, _u64p, C.c_size_t]
+lib.starkhip_quotient_class_plan_check.argtypes = [C.c_int, C.c_uint, C.c_uint64, _u64p]
+
+
+def quotient_classes(air):
+    """The class of every constraint: on how many cosets of n points the quotient evaluates it (starkhip_quotient_classes)."""
+    out = np.zeros(air_num_constraints(air), dtype=np.uint8)
+    _chk(lib.starkhip_quotient_classes(air, out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+    return out
+
+
+def quotient_solve_table(log_rows, quotient_degree_bits):
+    """(ginv[8], cpow[8][8], vinv[9][8][8]): the constants of the classes' recombination (starkhip_quotient_solve_table)."""
+    out = np.zeros(8 + 64 + 9 * 64, dtype=np.uint64)
+    _chk(lib.starkhip_quotient_solve_table(log_rows, quotient_degree_bits, _p64(out), out.size))
+    return out[:8], out[8:72].reshape(8, 8), out[72:].reshape(9, 8, 8)
+
+
+def quotient_class_plan_check(air, want_chunks=4, seed=1):
+    """CPU replay of the per-class plans against the plain fold restricted to each class (starkhip_quotient_class_plan_check)."""
+    st = np.zeros(32, dtype=np.uint64)
+    _chk(lib.starkhip_quotient_class_plan_check(air, want_chunks, seed, _p64(st)))
+    st = [int(x) for x in st]
+    k, t = st[0], st[1]
+    return {"classes": k, "cosets": t, "chunks": st[2], "work_rows": st[3], "records": st[4], "piece_ends": st[5], "tile_phases": st[6],
+            "contributions": st[7], "class_constraints": st[8:8 + k], "coset_chunks": st[24:24 + t]}
+
+
 lib.starkhip_air_eval_frame.argtypes = [C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p, C.c_int, _u64p]
 
 

@@ -260,6 +260,113 @@ int starkhip_quotient_plan_check(starkhip_air_t air, unsigned want_chunks, uint6
     }
 }
 
+int starkhip_quotient_classes(starkhip_air_t air, uint8_t* classes, size_t n) {
+    const AirInfo* a = air_get(air);
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    if (!classes || n != a->prog.n_constraints) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] {
+        const std::vector<uint8_t> cls = quotient_constraint_classes(a->prog, quotient_factor(a->prog.degree));
+        std::copy(cls.begin(), cls.end(), classes);
+        return (int)STARKHIP_OK;
+    });
+}
+
+int starkhip_quotient_solve_table(unsigned log_rows, unsigned quotient_degree_bits, uint64_t* out, size_t n) {
+    if (!out || n != QT_SOLVE_WORDS || log_rows > 32) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] {
+        const std::vector<gl_t> tab = quotient_solve_table(log_rows, quotient_degree_bits);
+        std::copy(tab.begin(), tab.end(), out);
+        return (int)STARKHIP_OK;
+    });
+}
+
+int starkhip_quotient_class_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[32]) {
+    const AirInfo* a = air_get(air);
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    return guarded([&] {
+        const AirProgram& P = a->prog;
+        const unsigned n_classes = quotient_factor(P.degree), n_cosets = 1u << quotient_degree_bits(P.degree);
+        QTClassPlan CP = build_quotient_class_plan(P, want_chunks, n_classes, n_cosets);
+        const std::vector<uint8_t> cls = quotient_constraint_classes(P, n_classes);
+        uint64_t s = seed;
+        auto rnd = [&]() {  // splitmix64, reduced
+            s += 0x9E3779B97F4A7C15ULL;
+            uint64_t z = s;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+            return gl_from_u64((z ^ (z >> 31)) % GL_P);
+        };
+        std::vector<gl_t> local(a->cols), next(a->cols), pis(a->pis ? a->pis : 1);
+        for (auto& v : local) v = rnd();
+        for (auto& v : next) v = rnd();
+        for (auto& v : pis) v = rnd();
+        gl_t masks[4] = {1, rnd(), rnd(), rnd()}, alphas[2] = {rnd(), rnd()};
+        // the plain fold acc alpha + mask c, restricted to each class: acc_j[class] = sum_k in class mask c_k alpha_j^(K-1-k)
+        std::vector<gl_t> want(2 * (n_classes + 1), 0);
+        {
+            const uint32_t K = P.n_constraints;
+            std::vector<gl_t> body(K);  // mask(kind) * gates * c_k
+            AirReader rd(P);
+            GroupWord grp;
+            uint32_t k = 0;
+            auto cell = [&](uint32_t ref) { return ((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]; };
+            while (rd.group(&grp)) {
+                gl_t G = masks[grp.kind];
+                for (uint32_t g = 0; g < grp.n_gates; g++) {
+                    const uint32_t ref = rd.ref();
+                    G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, cell(ref)) : cell(ref));
+                }
+                for (uint32_t c = 0; c < grp.m; c++, k++) {
+                    gl_t b = 0;
+                    TermWord tw;
+                    do {
+                        tw = rd.term();
+                        gl_t v = 1;
+                        for (uint32_t f = 0; f < tw.nf; f++) v = gl_mul(v, cell(rd.ref()));
+                        const gl_t coef = tw.ck == CK_PLUS ? 1 : tw.ck == CK_MINUS ? GL_P - 1 : tw.ck == CK_CONST ? P.consts[tw.idx] : tw.ck == CK_PI ? pis[tw.idx] : gl_neg(pis[tw.idx]);
+                        b = gl_add(b, gl_mul(v, coef));
+                    } while (!tw.last);
+                    body[k] = gl_mul(G, b);
+                }
+            }
+            for (int j = 0; j < 2; j++) {
+                gl_t pw = 1;
+                for (uint32_t e = 0; e < K; e++, pw = gl_mul(pw, alphas[j])) {
+                    const uint32_t kk = K - 1 - e;
+                    want[2 * (cls[kk] - 1) + j] = gl_add(want[2 * (cls[kk] - 1) + j], gl_mul(body[kk], pw));
+                }
+                for (unsigned c = 0; c < n_classes; c++) want[2 * n_classes + j] = gl_add(want[2 * n_classes + j], want[2 * c + j]);
+            }
+            gl_t full[2];
+            air_eval_folded<BaseOps>(P, local.data(), next.data(), pis.data(), masks, alphas, 2, full);
+            if (full[0] != want[2 * n_classes] || full[1] != want[2 * n_classes + 1]) return (int)STARKHIP_ERR_VERIFY;  // the classes sum to the full fold
+        }
+        quotient_plan_weights_host(P, CP.plan, alphas, pis.data());
+        // coset t: its chunks are its work rows, and the sums of its accumulators are the restricted folds of the classes above t (a
+        // spare coset: the whole fold in accumulator 0) -- nothing of a class at or below t
+        bool ok = CP.coset_chunk_off.size() == n_cosets + 1 && CP.work.size() == CP.plan.n_chunks;
+        for (unsigned t = 0; ok && t < n_cosets; t++) {
+            gl_t got[2], by_acc[QT_MAX_ACCS][2];
+            ok = quotient_plan_eval_host(CP.plan, local.data(), next.data(), masks, got, CP.coset_chunk_off[t], CP.coset_chunk_off[t + 1], by_acc);
+            for (unsigned a = 0; ok && a < QT_MAX_ACCS; a++) {
+                const bool runs = t < n_classes ? (a >= t && a < n_classes) : a == 0;
+                const gl_t* w = t < n_classes ? &want[2 * a] : &want[2 * n_classes];
+                if (runs ? (by_acc[a][0] != w[0] || by_acc[a][1] != w[1]) : (by_acc[a][0] != 0 || by_acc[a][1] != 0)) return (int)STARKHIP_ERR_VERIFY;
+            }
+            for (uint32_t r = CP.coset_chunk_off[t]; ok && r < CP.coset_chunk_off[t + 1]; r++)
+                ok = CP.work[r].chunk == r && CP.work[r].coset == t && CP.work[r].acc_lo == (t < n_classes ? t : 0u) && CP.work[r].acc_hi == (t < n_classes ? n_classes : 1u);
+        }
+        if (stats) {
+            for (int i = 0; i < 32; i++) stats[i] = 0;
+            stats[0] = n_classes; stats[1] = n_cosets; stats[2] = CP.plan.n_chunks; stats[3] = CP.work.size(); stats[4] = CP.plan.recs.size();
+            stats[5] = CP.plan.n_piece_ends; stats[6] = CP.plan.tile_phases; stats[7] = CP.plan.contribs.size();
+            for (unsigned c = 0; c < n_classes && c < 8; c++) stats[8 + c] = CP.class_constraints[c];
+            for (unsigned t = 0; t < n_cosets && t < 8; t++) stats[24 + t] = CP.coset_chunk_off[t + 1] - CP.coset_chunk_off[t];
+        }
+        return (int)(ok ? STARKHIP_OK : STARKHIP_ERR_BAD_SHAPE);
+    });
+}
+
 int starkhip_init(int device_ordinal, void** ctx) {
     Ctx* c = nullptr;
     int rc = ctx_create(device_ordinal, &c);

@@ -81,6 +81,7 @@ struct Ctx {
     bool urgent = false;  // ctx_set_urgent
     // tuning (starkhip_set_option; defaults are the measured best)
     long opt_quotient_impl = 0;   // 0: tiled evaluator (quotient_plan.h), 1: op-stream interpreter (quotient_ops.h)
+    long opt_quotient_cosets = 0; // 0: every constraint on the cosets its class needs (QTClassPlan), 1: every constraint on every coset
     long opt_quotient_waves = 65536, opt_quotient_slots = 0, opt_quotient_chunks = 0, opt_quotient_debug = 0, opt_zeta_on_coset = 0;
     // Shape-dependent tables and the per-AIR constraint plan are CACHED per context: a pooled context that alternates between
     // AIRs (a PairingPrecomp proof, then an FP12Mul one) finds both again instead of rebuilding the plan on the host and
@@ -88,6 +89,7 @@ struct Ctx {
     struct Tables {
         int log_n = -1, rate = -1, qdb = -1;
         DevBuf tw_fwd, tw_inv, coset_scale, qtab, qshift_inv;
+        DevBuf qsolve;  // quotient_solve_table: the constants of the recombination of the classes' chunks
         DevBuf lde2_fwd, lde2_inv, lde2_cs, lde2_oh;  // kernels_lde.hip tables (log_n >= 8)
         DevBuf lde_wave;                               // ... and of its wave-resident kernel (log_n == 13)
         // kernels_lde_long.hip (log_n >= 14, and the proof's other vectors of 2^16 .. 2^20 words): the coset powers (7 w_N^s)^j, the
@@ -96,7 +98,7 @@ struct Ctx {
         struct LongTw { unsigned log_len; DevBuf fwd, inv; };
         std::vector<std::unique_ptr<LongTw>> long_tw;
         std::vector<DevBuf*> bufs() {
-            std::vector<DevBuf*> v = {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave, &long_cs, &long_sub};
+            std::vector<DevBuf*> v = {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &qsolve, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave, &long_cs, &long_sub};
             for (auto& t : long_tw) {
                 v.push_back(&t->fwd);
                 v.push_back(&t->inv);
@@ -108,8 +110,14 @@ struct Ctx {
         int air = -1;
         unsigned chunks = 0, want = 0;
         uint32_t recs = 0;
-        DevBuf q_recs, q_streams, q_chunk_tile_off, q_tile_list, q_contrib_off, q_contribs, q_consts, q_apow;
-        std::vector<DevBuf*> bufs() { return {&q_recs, &q_streams, &q_chunk_tile_off, &q_tile_list, &q_contrib_off, &q_contribs, &q_consts, &q_apow}; }
+        // by class (QTClassPlan): the work rows (chunk, coset), the (coset, slot) pairs that run -- each a vector of the recombination --
+        // and the rows of each; by_class is part of the cache key
+        bool by_class = false;
+        unsigned n_work = 0, n_vecs = 0, n_classes = 0;
+        DevBuf q_recs, q_streams, q_chunk_tile_off, q_tile_list, q_contrib_off, q_contribs, q_consts, q_apow, q_work, q_sum_off, q_vec_slot, q_vec_of;
+        std::vector<DevBuf*> bufs() {
+            return {&q_recs, &q_streams, &q_chunk_tile_off, &q_tile_list, &q_contrib_off, &q_contribs, &q_consts, &q_apow, &q_work, &q_sum_off, &q_vec_slot, &q_vec_of};
+        }
     };
     std::vector<std::unique_ptr<Tables>> table_cache;
     std::vector<std::unique_ptr<PlanDev>> plan_cache;
@@ -148,13 +156,13 @@ struct Ctx {
     // whole trace only for rate_bits == 0, and starkhip_lde_batch's in-place values / coefficients.  Together 19.6 GB per FinalExp
     // context; rounds 1-3: values + coefficients + staging + LDE = 33.7 GB.  `staging` serves the kernel-level test entries
     // (expand_log, permute_batch, field_ops) alone.
-    DevBuf staging, values, lde, digests, pis, apow, chunk_scale, partial, qvals, qcoef, qlde, qdigests, zpow, gzpow, open_local,
+    DevBuf staging, values, lde, digests, pis, apow, chunk_scale, partial, qclass, qvals, qcoef, qlde, qdigests, zpow, gzpow, open_local,
         open_next, open_q, ext_apow, comb_partial, comb_out, fri_coef, fri_vals, fri_rows[16], fri_digests[16], scale_tab, pow_state,
         pow_best, qidx, gather_t;
     // every device buffer the context holds, cached tables and plans included: what ctx_destroy releases and ctx_device_bytes adds up
     std::vector<DevBuf*> dev_bufs() {
         std::vector<DevBuf*> v = {&staging, &values, &lde, &digests, &pis,
-                                  &apow, &chunk_scale, &partial, &qvals, &qcoef, &qlde, &qdigests, &zpow, &gzpow, &open_local, &open_next, &open_q,
+                                  &apow, &chunk_scale, &partial, &qclass, &qvals, &qcoef, &qlde, &qdigests, &zpow, &gzpow, &open_local, &open_next, &open_q,
                                   &ext_apow, &comb_partial, &comb_out, &fri_coef, &fri_vals, &scale_tab, &pow_state, &pow_best, &qidx, &gather_t};
         for (DevBuf& b : fri_rows) v.push_back(&b);
         for (DevBuf& b : fri_digests) v.push_back(&b);
@@ -184,7 +192,7 @@ hipError_t ensure_host_staging(Ctx* c, size_t need, size_t grow_to);
 int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb);
 bool long_vector(unsigned log_len);
 int ensure_long_tw(Ctx* c, unsigned log_len, LdeLongTables* out);
-int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points);
+int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points, bool by_class = false);
 int ensure_program(Ctx* c, const AirInfo& air, size_t quotient_points);
 hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs);
 int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,

@@ -90,6 +90,12 @@ int ensure_tables(Ctx* c, unsigned log_n, unsigned rate, unsigned qdb) {
     HIPCHK(launch_fill_coset_scale(T->coset_scale.as<gl_t>(), log_n, rate, c->st));
     HIPCHK(launch_quotient_tables(T->qtab.as<gl_t>(), log_n, qdb, c->st));
     HIPCHK(launch_fill_powers(T->qshift_inv.as<gl_t>(), 1, gl_inv(GL_GENERATOR), size, c->st));
+    if (((size_t)1 << qdb) <= QT_MAX_COSETS) {
+        const std::vector<gl_t> solve = quotient_solve_table(log_n, qdb);
+        HIPCHK(T->qsolve.ensure(solve.size() * 8));
+        HIPCHK(hipMemcpyAsync(T->qsolve.p, solve.data(), solve.size() * 8, hipMemcpyHostToDevice, c->st));
+        HIPCHK(stream_wait(c));  // `solve` goes out of scope
+    }
     if (lde_v2_supported(log_n)) {
         HIPCHK(T->lde2_fwd.ensure(lde_v2_tw_words(log_n) * 8));
         HIPCHK(T->lde2_inv.ensure(lde_v2_tw_words(log_n) * 8));
@@ -199,22 +205,40 @@ int ensure_program(Ctx* c, const AirInfo& air, size_t quotient_points) {
 }
 
 // Tiled plan of `air` on the device.  Chunks: enough (64-point block x chunk) workgroups to fill 256 CUs several times over.
-int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points) {
+// by_class: the plans of the classes and the cosets' work rows (QTClassPlan), else one plan for every coset.
+int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points, bool by_class) {
     const size_t blocks = (quotient_points + 63) / 64;
     unsigned want = (unsigned)std::min<size_t>(512, std::max<size_t>(1, (8192 + blocks - 1) / blocks));  // FinalExp: 4 chunks 29.8 ms, 8: 29.4, 16: 29.0, 32: 28.9
     if (c->opt_quotient_chunks > 0) want = (unsigned)c->opt_quotient_chunks;
+    by_class = by_class && quotient_factor(air.prog.degree) <= QT_MAX_ACCS;  // the kernel holds that many pairs of sums
     for (auto& pd : c->plan_cache)
-        if (pd->air == air.id && pd->want == want) {
+        if (pd->air == air.id && pd->want == want && pd->by_class == by_class) {
             c->plan = pd.get();
             return 0;
         }
-    const QTPlan Q = build_quotient_plan(air.prog, want);
+    QTClassPlan CP;
+    const unsigned n_cosets = 1u << quotient_degree_bits(air.prog.degree);
+    if (by_class) CP = build_quotient_class_plan(air.prog, want, quotient_factor(air.prog.degree), n_cosets);
+    else CP.plan = build_quotient_plan(air.prog, want);
+    const QTPlan& Q = CP.plan;
+    std::vector<uint32_t> vec_slot, vec_of((size_t)CP.n_cosets * (CP.n_classes + 1) + 1, 0xFFFFFFFFu);  // the (coset, slot) pairs that run, in order, and back
+    for (unsigned t = 0; t < CP.n_cosets; t++)
+        for (unsigned s = 0; s <= CP.n_classes; s++)
+            if (t < CP.n_classes ? (s >= t && s < CP.n_classes) : s == CP.n_classes) {
+                vec_of[t * (CP.n_classes + 1) + s] = (uint32_t)vec_slot.size();
+                vec_slot.push_back(t * (CP.n_classes + 1) + s);
+            }
     std::unique_ptr<Ctx::PlanDev> fresh(new Ctx::PlanDev());
     Ctx::PlanDev* D = fresh.get();
     struct Up { DevBuf* b; const void* src; size_t bytes; };
     const std::vector<gl_t>& consts = air.prog.consts;
     const gl_t zero = 0;
-    const Up ups[] = {{&D->q_recs, Q.recs.data(), Q.recs.size() * sizeof(QTRec)},
+    auto words = [&](const std::vector<uint32_t>& v) { return v.empty() ? (const void*)&zero : (const void*)v.data(); };
+    const Up ups[] = {{&D->q_work, CP.work.empty() ? (const void*)&zero : (const void*)CP.work.data(), std::max<size_t>(1, CP.work.size()) * sizeof(QTClassPlan::Work)},
+                      {&D->q_sum_off, words(CP.coset_chunk_off), std::max<size_t>(1, CP.coset_chunk_off.size()) * 4},
+                      {&D->q_vec_slot, words(vec_slot), std::max<size_t>(1, vec_slot.size()) * 4},
+                      {&D->q_vec_of, words(vec_of), std::max<size_t>(1, vec_of.size()) * 4},
+                      {&D->q_recs, Q.recs.data(), Q.recs.size() * sizeof(QTRec)},
                       {&D->q_streams, Q.streams.data(), Q.streams.size() * sizeof(QTStream)},
                       {&D->q_chunk_tile_off, Q.chunk_tile_off.data(), Q.chunk_tile_off.size() * 4},
                       {&D->q_tile_list, Q.tile_list.empty() ? (const void*)&zero : (const void*)Q.tile_list.data(), std::max<size_t>(1, Q.tile_list.size()) * 4},
@@ -229,6 +253,10 @@ int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points) {
     HIPCHK(stream_wait(c));  // Q goes out of scope
     D->air = air.id;
     D->want = want;
+    D->by_class = by_class;
+    D->n_work = (unsigned)CP.work.size();
+    D->n_vecs = (unsigned)vec_slot.size();
+    D->n_classes = CP.n_classes;
     D->chunks = Q.n_chunks;
     D->recs = (uint32_t)Q.recs.size();
     c->plan_cache.push_back(std::move(fresh));
@@ -341,6 +369,7 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
     else if (k == "lde_impl" && (value == 0 || value == 1)) c->opt_lde_impl = value;
     else if (k == "host_commit_leaves" && value >= 0 && value <= 4096) c->opt_host_commit_leaves = value;
     else if (k == "leaf_hash_form" && value >= FORM_AUTO && value <= FORM_PAIR) c->opt_leaf_hash_form = value;
+    else if (k == "quotient_cosets" && (value == 0 || value == 1)) c->opt_quotient_cosets = value;
     else if (k == "quotient_chunks" && value >= 0 && value <= 4096) c->opt_quotient_chunks = value;  // plans are cached by (AIR, chunks)
     else if (k == "verify_chunk_mb" && value >= 1) c->opt_verify_chunk_mb = value;
     else return STARKHIP_ERR_BAD_SHAPE;

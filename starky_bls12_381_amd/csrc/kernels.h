@@ -148,7 +148,14 @@ hipError_t launch_quotient_weights(QTRec* recs, const uint32_t* contrib_off, con
                                    const gl_t* consts, const gl_t* pis, gl_t alpha0, gl_t alpha1, hipStream_t st);
 hipError_t launch_quotient_tiles(const QTRec* recs, const QTStream* streams, const uint32_t* chunk_tile_off,
                                  const uint32_t* tile_list, unsigned n_chunks, const gl_t* lde, const gl_t* tab, gl_t* partial, unsigned log_n,
-                                 unsigned rate_bits, unsigned qdb, unsigned n_cols, unsigned dbg, hipStream_t st);
+                                 unsigned rate_bits, unsigned qdb, unsigned n_cols, unsigned dbg, hipStream_t st, const uint32_t* work = nullptr,
+                                 unsigned n_work = 0, unsigned n_accs = 1);
+// by class (QTClassPlan, "quotient_cosets" = 0): the classes' sums on their cosets / Z_H as 2 n_vecs vectors of n words, and -- after the
+// inverse transform of those -- the quotient's coefficient chunks [2][n << qdb] (kernels_quotient.hip)
+hipError_t launch_quotient_class_sums(const gl_t* partial, const uint32_t* sum_off, const uint32_t* vec_slot, unsigned n_vecs, unsigned n_slots,
+                                      const gl_t* tab, unsigned log_n, unsigned qdb, gl_t* out, hipStream_t st);
+hipError_t launch_quotient_class_solve(const gl_t* a, const uint32_t* vec_of, unsigned n_classes, const gl_t* solve, unsigned log_n, unsigned qdb,
+                                       gl_t* out, hipStream_t st);
 hipError_t launch_quotient_tiles_combine(const gl_t* partial, unsigned n_chunks, const gl_t* tab, unsigned log_n, unsigned qdb, gl_t* out,
                                          hipStream_t st);
 

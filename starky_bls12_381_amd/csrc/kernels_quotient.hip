@@ -1,17 +1,22 @@
-// Constraint-quotient evaluation on gfx950: the device twin of starky's compute_quotient_polys
-// (SURVEY.md App. A.6), which calls S::eval_packed_generic once per LDE point
-// (/root/reference/src/final_exponentiate.rs:907, src/miller_loop.rs:644,
-//  src/calc_pairing_precomp.rs:376, src/fp12_mul.rs:58).
+// Constraint-quotient evaluation on gfx950: the device twin of starky's compute_quotient_polys, which calls
+// S::eval_packed_generic once per LDE point.  What a proof needs is the quotient's coefficient chunks; the fold per point is
+// acc_j = sum_k mask_k c_k alpha_j^(K-1-k), and field arithmetic is exact, so the sum is regrouped freely (quotient_plan.h).
 //
-// Two evaluators live here; both produce exactly the reference's fold  acc_j = sum_k mask_k c_k alpha_j^(K-1-k).
-//
-//  * quotient_tiles_kernel (default): the tiled plan of quotient_plan.h.  Constraints are regrouped by (kind, gates) and by
-//    64-column tile, with per-proof alpha weights; a workgroup stages each tile's 64-point slice in LDS once (a producer wave,
-//    direct-to-LDS loads) and seven waves run wave-uniform record streams over it: every LDE cell is read from HBM once
-//    (FinalExp: 30 GB fetched per launch against 253 GB for the interpreter; 29 ms against 40 ms).  Measured on MI355X:
-//    vector and scalar instructions of a SIMD's waves do NOT overlap for this kind of code -- time = (VALU + SALU + LDS
-//    instructions) x 4 cycles per SIMD -- so the kernel is written for total instruction count: 12 multiply-adds per record,
-//    everything else amortised (details at the kernel).
+//  * quotient_tiles_kernel: the tiled plan of quotient_plan.h.  Constraints are regrouped by (kind, gates, class) into supergroups
+//    and by 64-column tile into pieces, with per-proof alpha weights (quotient_weights_kernel).  A workgroup of eight evaluating
+//    waves owns 64 points of ONE coset and one chunk of tiles; the waves stage each tile's 64-point slice in LDS themselves
+//    (direct-to-LDS loads, double buffered, one barrier per tile) and each runs its own wave-uniform stream of 32-byte records
+//    through a private LDS ring: a record is one cell read and twelve v_mad_u64_u32 into six unreduced 64-bit sums per alpha;
+//    a piece ends with two folds times mask * gate product.  Plain records run four at a time without a test, degree-2 monomials two
+//    pairs at a time.  The kernel is bound by instruction issue, not by HBM (every LDE cell is read about once), so it is written for
+//    instruction count, and the planner for even waves.
+//  * by class (the default, ctx option "quotient_cosets" = 0): a constraint with d cell factors is evaluated on max(1, d - 1) of the
+//    2^qdb cosets only (d for first-row and last-row constraints): coset t runs the plan of the classes above t, a workgroup keeps
+//    one pair of sums per class, and quotient_class_sums_kernel, an inverse size-n transform per (class, coset) and
+//    quotient_class_solve_kernel turn the classes' sums into the coefficient chunks.  FinalExp: 0.70 of the records.
+//    "quotient_cosets" = 1 runs every constraint on every coset (quotient_tiles_combine_kernel, then one inverse transform of all
+//    n << qdb values): the same bytes for a trace that satisfies the AIR, and what the profiling modes and the comparison with the
+//    interpreter use.
 //  * quotient_eval_kernel (ctx option "quotient_impl" = 1): the op-stream interpreter of round 1, one global load per op.
 //    Kept as the second implementation the tests cross-check the first against on the GPU.
 //
@@ -27,7 +32,7 @@
 // s_waitcnt counts are compile-time constants and the HBM / MALL latency sits behind three batches of work; LDS
 // reads are issued one batch ahead.  The batch loop is unrolled four times so both staging rings are registers.
 //
-// Field arithmetic is the lazy-reduction form of gl_dev.h.  The program is cut into `n_chunks` pieces at group
+// Field arithmetic is the lazy-reduction form of gl_dev.h.  The interpreter's program is cut into `n_chunks` pieces at group
 // boundaries so that (points / 64) x n_chunks waves fill the chip; a chunk's partial fold is scaled by
 // alpha^(constraints after the chunk) in the combine kernel, which is exact in the field.
 #include <hip/hip_runtime.h>
@@ -273,12 +278,13 @@ __global__ void quotient_combine_kernel(const gl_t* __restrict__ partial, const 
 //
 // A workgroup of QT_WAVES waves owns 64 coset points and one chunk of the plan.  For every tile of the chunk it stages
 // the 64-point slice of QT_TILE_COLS columns (+ the successor row) in LDS -- double buffered: the next tile's cells are
-// requested before the current tile's records are processed and stored afterwards, one barrier per tile -- and each
-// wave runs its own stream of wave-uniform records over the staged cells:
+// requested when the waves enter the current tile, one barrier per tile -- and each wave runs its own stream of wave-uniform
+// records over the staged cells:
 //     x = cell (LDS), product of cells, or 1;   S_j[i][l] += x_i * w_j,l     (x = x_1 2^32 + x_0, w_j = sum_l w_j,l 2^(22 l))
-// i.e. twelve v_mad_u64_u32 with the weight limb as scalar operand and no carries (each product < 2^54, a piece has at most
-// 96 records); at the end of a piece the six sums of each alpha are folded mod p, multiplied by mask * G and added to acc_j.
-// Gate cells and factors outside the tile are direct loads; a piece's gate cells are requested when the previous piece ends.
+// i.e. twelve v_mad_u64_u32 with the weight limb as scalar operand and no carries (each product < 2^54, a chain has at most
+// QT_MAX_CHAIN records); at the end of a piece the six sums of each alpha are folded mod p, multiplied by mask * G and added to the
+// sums of the piece's class.  Gate cells and factors outside the tile are direct loads; a piece's gate cells are requested when its
+// descriptor record comes up, ahead of its records.
 struct QTParams {
     const QTRec* recs;
     const QTStream* streams;          // [n_chunks][QT_WAVES]
@@ -286,7 +292,11 @@ struct QTParams {
     const uint32_t* tile_list;
     const gl_t* lde;                  // [C][N] coset-major
     const gl_t* tab;                  // quotient_tables_kernel output
-    gl_t* partial;                    // [n_chunks][2][size]
+    gl_t* partial;                    // [n_chunks][2][size]; with `work`: [work rows][n_accs][2][n]
+    const uint32_t* work;             // nullptr: every chunk on every coset (blockIdx.y = chunk).  Else QTClassPlan::work, blockIdx.y = its row:
+                                      // (chunk, coset, first accumulator, last + 1) -- the workgroup evaluates that chunk on that coset's points
+                                      // alone and writes the sums of each of these accumulators (one per constraint class)
+    unsigned n_accs;
     unsigned log_n, rate_bits, qdb, n_cols;
     unsigned dbg;  // profiling only: 1 = the producer loads nothing, 2 = the evaluators skip the arithmetic (results are garbage)
 };
@@ -368,10 +378,14 @@ __global__ __launch_bounds__(64 * (QT_WAVES + 1), 4) void quotient_tiles_kernel(
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // 0 .. QT_WAVES - 1 evaluate; SMALL_N: wave QT_WAVES stages the tiles
     const unsigned lane = threadIdx.x & 63u;
     const size_t n = (size_t)1 << P.log_n, size = n << P.qdb;
-    const unsigned t_raw = blockIdx.x * 64u + lane;
+    // by class (P.work): blockIdx.x counts the 64-point blocks of ONE coset; a SMALL_N block spans the cosets as ever and only the
+    // lanes of the row's coset write their sums
+    const unsigned chunk = P.work ? P.work[4u * blockIdx.y] : blockIdx.y;
+    const unsigned coset = P.work ? P.work[4u * blockIdx.y + 1u] : 0u;
+    const unsigned acc_lo = P.work ? P.work[4u * blockIdx.y + 2u] : 0u, acc_hi = P.work ? P.work[4u * blockIdx.y + 3u] : 1u;
+    const unsigned t_raw = blockIdx.x * 64u + lane + ((P.work && !SMALL_N) ? coset << P.log_n : 0u);
     const bool live = t_raw < size;  // domains smaller than a wave (FP12Mul: 32 points): idle lanes shadow point 0
     const unsigned t = live ? t_raw : 0;
-    const unsigned chunk = blockIdx.y;
     const unsigned sp = t >> P.log_n, k = t & (unsigned)(n - 1);
     const unsigned s = sp << (P.rate_bits - P.qdb);  // LDE coset of this quotient point
     const unsigned k_next = (k + 1) & (unsigned)(n - 1);
@@ -413,7 +427,7 @@ __global__ __launch_bounds__(64 * (QT_WAVES + 1), 4) void quotient_tiles_kernel(
             }
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
-        asm volatile("s_barrier" ::: "memory");  // the evaluators' reduction barrier
+        for (unsigned a = acc_lo; a < acc_hi; a++) asm volatile("s_barrier\n\ts_barrier" ::: "memory");  // the evaluators' reduction barriers
         return;
     }
     // ---- n >= 64 (every AIR but FP12Mul): no producer wave.  Round 5 had seven evaluating waves and a producer per workgroup; with
@@ -514,6 +528,14 @@ __global__ __launch_bounds__(64 * (QT_WAVES + 1), 4) void quotient_tiles_kernel(
     };
 
     gl_t acc0 = 0, acc1 = 0, v = 1;
+    // A plan by class has one pair of sums per class (the accumulator a piece's descriptor names).  The pair of the class under way is
+    // (acc0, acc1); the others rest in private memory and change places with it when a piece of another class starts -- the planner
+    // orders a wave's pieces of a tile class by class -- so that the record and piece-end paths hold no register more than before.
+    gl_t acc_rest[2 * QT_MAX_ACCS];
+#pragma unroll
+    for (unsigned a = 0; a < 2 * QT_MAX_ACCS; a++) acc_rest[a] = 0;
+    asm volatile("" : : "v"(&acc_rest[0]) : "memory");  // stays an array in memory: promoted to registers it would cost sixteen of them
+    unsigned acc_cur = 0;
     uint64_t S0[6] = {0, 0, 0, 0, 0, 0}, S1[6] = {0, 0, 0, 0, 0, 0};
     uint32_t piece_ctl = 0;
     gl_t gate[4] = {0, 0, 0, 0};
@@ -523,6 +545,14 @@ __global__ __launch_bounds__(64 * (QT_WAVES + 1), 4) void quotient_tiles_kernel(
     auto gates_request = [&](const Rec& d) {
         const uint32_t dgate[4] = {d.a.z, d.a.w, d.b.x, d.b.y};
         piece_ctl = __builtin_amdgcn_readfirstlane(d.b.z);
+        const unsigned acc_new = (piece_ctl >> QT_ACC_SHIFT) & (QT_MAX_ACCS - 1u);
+        if (acc_new != acc_cur) {  // the previous piece has ended: its class's sums make room for this one's
+            acc_rest[2 * acc_cur] = acc0;
+            acc_rest[2 * acc_cur + 1] = acc1;
+            acc0 = acc_rest[2 * acc_new];
+            acc1 = acc_rest[2 * acc_new + 1];
+            acc_cur = acc_new;
+        }
         const uint32_t ng = ((piece_ctl >> 2) & 7u) + ((piece_ctl >> QT_FOREIGN_SHIFT) & 7u);  // gates, then the absorbed pieces' cells (quotient_plan.h)
 #pragma unroll
         for (unsigned g = 0; g < 4; g++)
@@ -659,7 +689,8 @@ __global__ __launch_bounds__(64 * (QT_WAVES + 1), 4) void quotient_tiles_kernel(
             gl_t x = X;                                                                                               \
             if ((ctl & QT_ODD_SOURCE) != 0) {                                                                         \
                 if (ctl & (QT_TILE | QT_STOP)) {                                                                      \
-                    /* every LDS read of this tile has returned; the gate loads of the next piece stay in flight */   \
+                    /* the barrier waits for everything this wave has in flight (vmcnt(0) lgkmcnt(0)): its LDS reads of this   */ \
+                    /* tile, its share of the next tile -- and the gate loads of a piece that has already started         */ \
                     QT_TILE_BARRIER()                                                                                 \
                     ti++;                                                                                             \
                     if ((ctl & QT_STOP) != 0 || ti >= n_tiles) goto stream_done;                                      \
@@ -832,15 +863,21 @@ stream_done:
     }
 #endif
 
-    // acc of the eight waves -> partial[chunk]
+    // acc of the eight waves -> partial[chunk], accumulator after accumulator
+    acc_rest[2 * acc_cur] = acc0;
+    acc_rest[2 * acc_cur + 1] = acc1;
     gl_t* red = tile[0];
-    red[(wave * 2 + 0) * 64 + lane] = gl_canon(acc0);
-    red[(wave * 2 + 1) * 64 + lane] = gl_canon(acc1);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (wave < 2 && live) {
-        gl_t sum = 0;
-        for (unsigned w = 0; w < QT_WAVES; w++) sum = gl_add(sum, red[(w * 2 + wave) * 64 + lane]);
-        P.partial[((size_t)chunk * 2 + wave) * size + t] = sum;
+    for (unsigned a = acc_lo; a < acc_hi; a++) {
+        red[(wave * 2 + 0) * 64 + lane] = gl_canon(acc_rest[2 * a]);
+        red[(wave * 2 + 1) * 64 + lane] = gl_canon(acc_rest[2 * a + 1]);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (wave < 2 && live) {
+            gl_t sum = 0;
+            for (unsigned w = 0; w < QT_WAVES; w++) sum = gl_add(sum, red[(w * 2 + wave) * 64 + lane]);
+            if (!P.work) P.partial[((size_t)chunk * 2 + wave) * size + t] = sum;
+            else if (sp == coset) P.partial[(((size_t)blockIdx.y * P.n_accs + a) * 2 + wave) * n + k] = sum;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // `red` is read: the next accumulator may overwrite it
     }
 }
 
@@ -907,14 +944,20 @@ hipError_t launch_quotient_weights(QTRec* recs, const uint32_t* contrib_off, con
 
 hipError_t launch_quotient_tiles(const QTRec* recs, const QTStream* streams, const uint32_t* chunk_tile_off,
                                  const uint32_t* tile_list, unsigned n_chunks, const gl_t* lde, const gl_t* tab, gl_t* partial, unsigned log_n,
-                                 unsigned rate_bits, unsigned qdb, unsigned n_cols, unsigned dbg, hipStream_t st) {
+                                 unsigned rate_bits, unsigned qdb, unsigned n_cols, unsigned dbg, hipStream_t st, const uint32_t* work,
+                                 unsigned n_work, unsigned n_accs) {
     QTParams P;
     P.dbg = dbg;
+    P.work = work;
+    P.n_accs = n_accs;
     P.recs = recs; P.streams = streams; P.chunk_tile_off = chunk_tile_off; P.tile_list = tile_list;
     P.lde = lde; P.tab = tab; P.partial = partial; P.log_n = log_n; P.rate_bits = rate_bits; P.qdb = qdb; P.n_cols = n_cols;
     const size_t size = (size_t)1 << (log_n + qdb);
     const bool small = log_n < 6 || size < 64;
-    const dim3 grid((unsigned)((size + 63) / 64), n_chunks), block(64 * (QT_WAVES + (small ? 1 : 0)));  // SMALL_N: + the producer wave
+    if (work && n_work == 0) return hipSuccess;  // no class has a constraint
+    // by class: one grid row per (chunk, coset) of the work list, over the 64-point blocks of that coset
+    const dim3 grid((unsigned)(work && !small ? ((size_t)1 << log_n) / 64 : (size + 63) / 64), work ? n_work : n_chunks),
+        block(64 * (QT_WAVES + (small ? 1 : 0)));  // SMALL_N: + the producer wave
 #ifdef STARKHIP_DEBUG  // make DEBUG_KNOBS=1: profiling variants with parts switched off (results are garbage); not in the release library
     switch (dbg) {  // 1 tile loads, 2 arithmetic, 3 both, 4 piece ends, 8 factors outside the tile not loaded
         case 0: break;
@@ -929,6 +972,75 @@ hipError_t launch_quotient_tiles(const QTRec* recs, const QTStream* streams, con
 #endif
     if (small) hipLaunchKernelGGL((quotient_tiles_kernel<true, 0>), grid, block, 0, st, P);
     else hipLaunchKernelGGL((quotient_tiles_kernel<false, 0>), grid, block, 0, st, P);
+    return hipGetLastError();
+}
+
+// ---- by class: from the classes' partial sums on their cosets to the quotient's coefficient chunks
+//
+// The sum S of the constraints of class k, divided by Z_H, is a polynomial of degree < k n:  S(x) = sum_{m<k} x^(m n) A_m(x), deg A_m < n.
+// On coset t -- shift g_t = 7 w_(n << qdb)^t -- x^n is the constant c_t = 7^n w_(2^qdb)^t, so the inverse size-n transform of the
+// coset's values, unshifted by g_t^-i, is  a_t[i] = sum_m c_t^m A_m[i]:  a k x k Vandermonde system per coefficient index i, in the
+// distinct points c_0 .. c_(k-1).  Its inverse is a host constant per (shape, k) (QuotientSolveTab), and the A_m of all classes add up to
+// the quotient's chunks -- what the inverse transform of all n << qdb values gives for a trace that satisfies the AIR.
+
+// vector v = 2 * (index of a (coset, slot) pair that runs) + alpha:  out[v][i] = (that class's sums of the coset's work rows) / Z_H on that
+// coset.  sum_off: the cosets' first rows; slot s < n_slots - 1 is accumulator s (class s + 1), the last slot (a spare coset) accumulator 0.
+__global__ void quotient_class_sums_kernel(const gl_t* __restrict__ partial, const uint32_t* __restrict__ sum_off, const uint32_t* __restrict__ vec_slot,
+                                           unsigned n_slots, const gl_t* __restrict__ tab, unsigned log_n, unsigned qdb, gl_t* __restrict__ out) { STARKHIP_PRIO_ENTRY
+    const size_t n = (size_t)1 << log_n, size = n << qdb;
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned v = blockIdx.y >> 1, j = blockIdx.y & 1u;
+    const uint32_t slot = vec_slot[v], t = slot / n_slots, s = slot % n_slots, n_accs = n_slots - 1, a = s == n_accs ? 0u : s;
+    gl_t acc = 0;
+    for (uint32_t w = sum_off[t]; w < sum_off[t + 1]; w++) acc = gl_add(acc, partial[(((size_t)w * n_accs + a) * 2 + j) * n + i]);
+    out[(size_t)blockIdx.y * n + i] = gl_mul(acc, tab[3 * size + (size_t)t * n + i]);
+}
+
+// a: the vectors of quotient_class_sums_kernel after the inverse size-n transform.  out[j][m n + i] = chunk m of alpha j for m < n_classes;
+// for a spare coset t >= n_classes, which evaluated every constraint:  out[j][t n + i] = a_t[i] - sum_m c_t^m chunk_m[i], zero exactly
+// when the chunks agree with the constraints on that coset too -- the words trim_to_len wants to be zero (ProveCall::quotient_commit).
+__global__ void quotient_class_solve_kernel(const gl_t* __restrict__ a, const uint32_t* __restrict__ vec_of, unsigned n_classes,
+                                            const gl_t* __restrict__ solve, unsigned log_n, unsigned qdb, gl_t* __restrict__ out) { STARKHIP_PRIO_ENTRY
+    const size_t n = (size_t)1 << log_n, size = n << qdb;
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned j = blockIdx.y, n_cosets = 1u << qdb, n_slots = n_classes + 1;
+    const gl_t* ginv = solve + QT_SOLVE_GINV;
+    const gl_t* cpow = solve + QT_SOLVE_CPOW;
+    const gl_t* vinv = solve + QT_SOLVE_VINV;
+    gl_t A[QT_MAX_COSETS], unshift[QT_MAX_COSETS];
+    for (unsigned t = 0; t < QT_MAX_COSETS; t++) {
+        A[t] = 0;
+        unshift[t] = t < n_cosets ? gl_pow(ginv[t], i) : 0;
+    }
+    auto value = [&](unsigned t, unsigned s) { return gl_mul(a[((size_t)vec_of[t * n_slots + s] * 2 + j) * n + i], unshift[t]); };
+    for (unsigned s = 0; s < n_classes; s++)
+        for (unsigned t = 0; t <= s; t++) {
+            const gl_t x = value(t, s);
+            for (unsigned m = 0; m <= s; m++) A[m] = gl_add(A[m], gl_mul(vinv[((s + 1) * QT_MAX_COSETS + m) * QT_MAX_COSETS + t], x));
+        }
+    for (unsigned m = 0; m < n_classes; m++) out[(size_t)j * size + m * n + i] = A[m];
+    for (unsigned t = n_classes; t < n_cosets; t++) {
+        gl_t e = 0;
+        for (unsigned m = 0; m < n_classes; m++) e = gl_add(e, gl_mul(cpow[t * QT_MAX_COSETS + m], A[m]));
+        out[(size_t)j * size + t * n + i] = gl_sub(value(t, n_classes), e);
+    }
+}
+
+hipError_t launch_quotient_class_sums(const gl_t* partial, const uint32_t* sum_off, const uint32_t* vec_slot, unsigned n_vecs, unsigned n_slots,
+                                      const gl_t* tab, unsigned log_n, unsigned qdb, gl_t* out, hipStream_t st) {
+    if (!n_vecs) return hipSuccess;
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(quotient_class_sums_kernel, dim3((unsigned)((n + 255) / 256), 2 * n_vecs), dim3(256), 0, st, partial, sum_off, vec_slot, n_slots, tab,
+                       log_n, qdb, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_quotient_class_solve(const gl_t* a, const uint32_t* vec_of, unsigned n_classes, const gl_t* solve, unsigned log_n, unsigned qdb,
+                                       gl_t* out, hipStream_t st) {
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(quotient_class_solve_kernel, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, st, a, vec_of, n_classes, solve, log_n, qdb, out);
     return hipGetLastError();
 }
 

@@ -114,17 +114,20 @@ struct ProofShape {
 static const size_t COMB_PPC = 256;
 static size_t comb_chunks(size_t C) { return (C + COMB_PPC - 1) / COMB_PPC; }
 
-// THE size of every work buffer of a proof of shape `s` whose quotient is evaluated in `n_chunks` chunks.  prove() and ctx_reserve()
+// THE size of every work buffer of a proof of shape `s` whose quotient is evaluated in `n_chunks` chunks -- by class (`plan` non-null and
+// by_class) in plan->n_work rows of one coset each, recombined from 2 plan->n_vecs vectors of n words (and as many of scratch).  prove() and ctx_reserve()
 // both allocate from this list, so a context that a pool has warmed never grows a buffer inside a proof (see ctx_reserve).  What the
 // two do not share is theirs to say: `values_bytes` (a whole trace, the tail of run_lde_trace, or nothing) and `park_bytes`, what
 // the upload stages at the start of the LDE buffer.
 struct BufWant { DevBuf* b; size_t bytes; };
-static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n_chunks, size_t values_bytes, size_t park_bytes) {
+static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n_chunks, const Ctx::PlanDev* plan, size_t values_bytes, size_t park_bytes) {
     const size_t n = s.n, N = s.N, C = s.C, Q = s.Q, size = s.size, nq = s.pl.n_queries;
+    const bool by_class = plan && plan->by_class;
+    const size_t partial_words = by_class ? std::max<size_t>((size_t)plan->n_work * plan->n_classes * 2 * n, 2 * size) : (size_t)n_chunks * 2 * size;
     std::vector<BufWant> w = {
         {&c->values, values_bytes}, {&c->lde, std::max(C * N * 8, park_bytes)}, {&c->digests, digest_words(N) * 8},
         {&c->pis, std::max<size_t>(1, s.pl.n_pis) * 8}, {&c->apow, 2 * (AIR_MAX_GROUP + 1) * 8}, {&c->chunk_scale, 2 * (size_t)n_chunks * 8},
-        {&c->partial, (size_t)n_chunks * 2 * size * 8}, {&c->qvals, 2 * size * 8}, {&c->qcoef, Q * n * 8}, {&c->qlde, Q * N * 8},
+        {&c->partial, partial_words * 8}, {&c->qclass, by_class ? (size_t)plan->n_vecs * 2 * 2 * n * 8 : 0}, {&c->qvals, 2 * size * 8}, {&c->qcoef, Q * n * 8}, {&c->qlde, Q * N * 8},
         {&c->qdigests, digest_words(N) * 8},
         {&c->zpow, 2 * n * 16},  // powers of zeta (the quotient polynomials' openings), then the coset-0 weights of zeta
         {&c->gzpow, n * 16},     // the weights of g zeta
@@ -191,6 +194,7 @@ struct ProveCall {
     int upload(), ifft_lde(), trace_merkle(), quotient(), quotient_commit(), openings(), fri_combine(), fri_commit(), pow(), queries();
     int upload_recording(const TraceLog* log), upload_column_table(const uint64_t* const* cols), leaf_hash_on_host();
     int run_quotient_tiles(unsigned debug_mode, gl_t* qvals_out, bool timed), run_quotient_ops(), compare_quotient_evaluators();
+    int run_quotient_classes();
 };
 
 // ---- phase 0: trace into column-major device memory (trace_rows_to_poly_values), by layout
@@ -343,6 +347,26 @@ int ProveCall::run_quotient_tiles(unsigned debug_mode, gl_t* qvals_out, bool tim
     return 0;
 }
 
+// The tiled evaluator by class ("quotient_cosets" = 0, QTClassPlan): every class's chunks on the cosets the class needs, then from the
+// classes' sums to the quotient's COEFFICIENTS in qvals ([2][size] words, chunk after chunk) -- what the inverse transform of all
+// `size` values gives (kernels_quotient.hip has the algebra).  kev[2] / kev[3] bracket the pass over the LDE as in run_quotient_tiles.
+int ProveCall::run_quotient_classes() {
+    const Ctx::PlanDev& D = *c->plan;
+    HIPCHK(launch_quotient_weights(D.q_recs.as<QTRec>(), D.q_contrib_off.as<uint32_t>(), D.q_contribs.as<QTContrib>(), D.recs, D.q_apow.as<gl_t>(),
+                                   air.prog.n_constraints, D.q_consts.as<gl_t>(), c->pis.as<gl_t>(), alphas[0], alphas[1], st));
+    HIPCHK(hipEventRecord(c->kev[2], st));
+    HIPCHK(launch_quotient_tiles(D.q_recs.as<QTRec>(), D.q_streams.as<QTStream>(), D.q_chunk_tile_off.as<uint32_t>(), D.q_tile_list.as<uint32_t>(), D.chunks,
+                                 c->lde.as<gl_t>(), c->tab->qtab.as<gl_t>(), c->partial.as<gl_t>(), s.log_n, s.r, s.qdb, (unsigned)s.C, 0, st,
+                                 D.q_work.as<uint32_t>(), D.n_work, D.n_classes));
+    HIPCHK(hipEventRecord(c->kev[3], st));
+    gl_t* const vecs = c->qclass.as<gl_t>();
+    HIPCHK(launch_quotient_class_sums(c->partial.as<gl_t>(), D.q_sum_off.as<uint32_t>(), D.q_vec_slot.as<uint32_t>(), D.n_vecs, D.n_classes + 1,
+                                      c->tab->qtab.as<gl_t>(), s.log_n, s.qdb, vecs, st));
+    if (int rc = run_ntt(c, vecs, vecs + (size_t)2 * D.n_vecs * s.n, 2 * D.n_vecs, s.n, s.log_n, true, nullptr, nullptr)) return rc;
+    HIPCHK(launch_quotient_class_solve(vecs, D.q_vec_of.as<uint32_t>(), D.n_classes, c->tab->qsolve.as<gl_t>(), s.log_n, s.qdb, c->qvals.as<gl_t>(), st));
+    return 0;
+}
+
 // The op-stream interpreter (quotient_ops.h; "quotient_impl" = 1, kept as the cross-check) into qvals
 int ProveCall::run_quotient_ops() {
     std::vector<gl_t> apow(2 * (AIR_MAX_GROUP + 1)), cscale(2 * n_chunks);
@@ -397,12 +421,16 @@ int ProveCall::quotient() {
     fs.stop();
     if (s.pl.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis_host, s.pl.n_pis * 8, hipMemcpyHostToDevice, st));
     const unsigned debug = (unsigned)((c->opt_quotient_debug <= 4 || c->opt_quotient_debug == 8) ? c->opt_quotient_debug : 0);
-    if (int rc = tiled ? run_quotient_tiles(debug, c->qvals.as<gl_t>(), true) : run_quotient_ops()) return rc;
-    if (c->opt_quotient_debug == 9 && !tiled)
-        if (int rc = compare_quotient_evaluators()) return rc;
-    // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
-    if (int rc = run_ntt(c, c->qvals.as<gl_t>(), c->partial.as<gl_t>(), 2, size, s.log_n + s.qdb, true, nullptr, c->tab->qshift_inv.as<gl_t>()))  // (the chunks' partial sums are spent)
-        return rc;
+    if (tiled && c->plan->by_class) {  // the classes' sums on their cosets, recombined: the coefficients are in qvals
+        if (int rc = run_quotient_classes()) return rc;
+    } else {
+        if (int rc = tiled ? run_quotient_tiles(debug, c->qvals.as<gl_t>(), true) : run_quotient_ops()) return rc;
+        if (c->opt_quotient_debug == 9 && !tiled)
+            if (int rc = compare_quotient_evaluators()) return rc;
+        // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
+        if (int rc = run_ntt(c, c->qvals.as<gl_t>(), c->partial.as<gl_t>(), 2, size, s.log_n + s.qdb, true, nullptr, c->tab->qshift_inv.as<gl_t>()))  // (the chunks' partial sums are spent)
+            return rc;
+    }
     // trim_to_len(n * factor) must succeed (quotient_commit() looks at the tail), then chunks of n: [alpha0: c0..cf-1, alpha1: c0..cf-1]
     if (size > factor * n) {
         quot_tail.resize(2 * (size - factor * n));
@@ -671,7 +699,9 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     hipStream_t st = c->st;
     if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
     const bool tiled = c->opt_quotient_impl == 0;
-    if (int rc = tiled ? ensure_plan(c, air, s.size) : ensure_program(c, air, s.size)) return rc;
+    // the profiling modes and the evaluators' comparison run every constraint on every coset, like "quotient_cosets" = 1
+    const bool by_class = tiled && c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0;
+    if (int rc = tiled ? ensure_plan(c, air, s.size, by_class) : ensure_program(c, air, s.size)) return rc;
     const unsigned n_chunks = tiled ? c->plan->chunks : c->prog.chunks;
 
     // ---- buffers
@@ -686,7 +716,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     const bool trace_in_lde = s.r >= 1 && park_words <= (((size_t)1 << s.r) - 1) * C * n && !callers_columns && !long_trace;
     // `values`: the columns the last LDE launch reads (run_lde_trace), a whole trace, or nothing this proof needs
     const size_t values_bytes = values_bytes_for(s, trace_in_lde, callers_columns);
-    for (const BufWant& w : work_buffers(c, s, n_chunks, values_bytes, park_words * 8)) HIPCHK(w.b->ensure(w.bytes));
+    for (const BufWant& w : work_buffers(c, s, n_chunks, tiled ? c->plan : nullptr, values_bytes, park_words * 8)) HIPCHK(w.b->ensure(w.bytes));
     if (int rc = ensure_long_tables(c, s)) return rc;
 
     ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde,
@@ -738,11 +768,11 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t
     if (ProofShape::make(air, cfg, air.default_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
     if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
-    if (int rc = ensure_plan(c, air, s.size)) return rc;
+    if (int rc = ensure_plan(c, air, s.size, c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0)) return rc;
     // `values`: a trace waits for its LDE inside the LDE buffer (prove(): trace_in_lde) but for the tail of run_lde_trace; rate_bits == 0
     // makes prove() ask for a whole trace.  The LDE buffer also stages the upload: a recording of log_bytes.
     const size_t values_bytes = values_bytes_for(s, s.r >= 1, false);
-    for (const BufWant& w : work_buffers(c, s, c->plan->chunks, values_bytes, log_bytes + 64)) HIPCHK(w.b->ensure(w.bytes));
+    for (const BufWant& w : work_buffers(c, s, c->plan->chunks, c->plan, values_bytes, log_bytes + 64)) HIPCHK(w.b->ensure(w.bytes));
     if (int rc = ensure_long_tables(c, s)) return rc;
     if (log_bytes && !device_traces) HIPCHK(ensure_host_staging(c, log_bytes, log_bytes));
     if (proof_blobs && !c->blob_airs.count(air.id)) {  // page-locked blobs for this AIR's proofs, once per context

@@ -20,7 +20,11 @@
 // Layout for the kernel: the tiles of the program are cut into `n_chunks` contiguous ranges of about equal cost; a
 // workgroup of QT_WAVES waves handles (64 points) x (one chunk) and walks the chunk's tiles in step (one barrier per tile);
 // inside a tile the pieces are dealt to the waves (largest first), big pieces are split -- the contribution is linear in T.
-// Each wave reads its own stream of 32-byte wave-uniform records and a stream of piece descriptors.
+// Each wave reads its own stream of 32-byte wave-uniform records; a piece's descriptor rides in it as a no-op record.
+//
+// By class (QTClassPlan, at the end of this file): a constraint's part of the quotient has a degree set by the constraint's own degree,
+// so it is evaluated on as many of the quotient's cosets as that degree needs, not on all of them; coset t has a plan of its own that
+// holds the classes above t, and the classes' sums are recombined into coefficient chunks (kernels_quotient.hip).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -81,7 +85,8 @@ struct QTRec {
 };
 static_assert(sizeof(QTRec) == 32, "records are fetched as 8 dwords");
 
-// piece descriptor: ctl = kind | n_gates << 2 | complement mask << 5 | n_foreign << 9
+// piece descriptor: ctl = kind | n_gates << 2 | complement mask << 5 | n_foreign << 9 | accumulator << 12
+// (accumulator: class - 1 in a plan built by class -- the kernel keeps one pair of sums per class -- else 0)
 // gate[0 .. n_gates) are the gate cells; gate[n_gates .. n_gates + n_foreign) are FOREIGN cells: the single cells of tiny pieces of the same
 // supergroup that lived in other tiles and were absorbed into this one (a piece end costs as much as fifteen records; 10 594 of FinalExp's
 // 32 850 closed a piece of exactly one record).  All of them are requested when the piece starts, so a foreign cell is in a register
@@ -102,6 +107,7 @@ static const uint32_t QT_AUX_PAIRS_MASK = 0xFFFFu;
 static const uint32_t QT_AUX_DPAIRS_SHIFT = 16, QT_AUX_DPAIRS_MASK = 0x7FFFu;
 static const uint32_t QT_AUX_SLOT = 0x80000000u;   // aux of a QT_SRC_GLOBAL record: the cell is descriptor slot (aux & 3), not column aux
 static const unsigned QT_FOREIGN_SHIFT = 9;
+static const unsigned QT_ACC_SHIFT = 12, QT_MAX_ACCS = 4;   // [14:12] of a descriptor's ctl; the kernel holds QT_MAX_ACCS pairs of sums
 static_assert(sizeof(QTPiece) == 32, "piece descriptors are fetched as 8 dwords");
 
 // one term's share of a record's weight: coefficient * alpha^e
@@ -142,14 +148,18 @@ inline uint32_t tile_of(uint32_t cellref) { return (cellref & REF_COL_MASK) / QT
 }  // namespace qt_detail
 
 // Build the plan.  `want_chunks` >= 1; the result may have fewer (never more than the number of non-empty tiles).
-inline QTPlan build_quotient_plan(const AirProgram& P, unsigned want_chunks) {
+// With `classes` (quotient_constraint_classes) the plan holds the constraints of class >= `min_class` alone, each with the power of
+// alpha it has in the whole program, and a supergroup is (kind, gates, class): a monomial shared by constraints of several classes gets
+// one record per class with that class's contributions, and gate folding (pass 1b) and the absorption of tiny pieces join parts of
+// one class only.  Every piece names its class's accumulator in its descriptor.
+inline QTPlan build_quotient_plan(const AirProgram& P, unsigned want_chunks, const std::vector<uint8_t>* classes = nullptr, unsigned min_class = 0) {
     using namespace qt_detail;
     const uint32_t K = P.n_constraints;
     const uint32_t NONE = 0xFFFFFFFFu;
     // ---- pass 1: terms with their supergroup
     std::unordered_map<std::string, uint32_t> sg_index;
     std::vector<std::vector<uint32_t>> sg_gates;
-    std::vector<uint32_t> sg_kind;
+    std::vector<uint32_t> sg_kind;  // kind | class << 8: the head of a supergroup's key
     std::vector<Term> terms;
     terms.reserve(P.code.size() / 2);
     AirReader rd(P);
@@ -159,19 +169,23 @@ inline QTPlan build_quotient_plan(const AirProgram& P, unsigned want_chunks) {
         if (grp.n_gates > 4) throw std::runtime_error("quotient_plan: more than four gates");
         uint32_t gates[4];  // stored sorted by the builder
         for (uint32_t g = 0; g < grp.n_gates; g++) gates[g] = rd.ref();
-        std::string key((const char*)&grp.kind, 4);
-        key.append((const char*)gates, grp.n_gates * 4);
-        uint32_t sg;
-        auto it = sg_index.find(key);
-        if (it == sg_index.end()) {
-            sg = (uint32_t)sg_gates.size();
-            sg_index.emplace(std::move(key), sg);
-            sg_gates.emplace_back(gates, gates + grp.n_gates);
-            sg_kind.push_back(grp.kind);
-        } else {
-            sg = it->second;
-        }
+        uint32_t sg = NONE, sg_head = NONE;
         for (uint32_t c = 0; c < grp.m; c++, k++) {
+            const uint32_t head = grp.kind | (classes ? (uint32_t)(*classes)[k] << 8 : 0u);
+            if (head != sg_head) {  // the constraints of a group share kind and gates, not the class
+                std::string key((const char*)&head, 4);
+                key.append((const char*)gates, grp.n_gates * 4);
+                auto it = sg_index.find(key);
+                if (it == sg_index.end()) {
+                    sg = (uint32_t)sg_gates.size();
+                    sg_index.emplace(std::move(key), sg);
+                    sg_gates.emplace_back(gates, gates + grp.n_gates);
+                    sg_kind.push_back(head);
+                } else {
+                    sg = it->second;
+                }
+                sg_head = head;
+            }
             TermWord tw;
             do {
                 tw = rd.term();
@@ -183,6 +197,7 @@ inline QTPlan build_quotient_plan(const AirProgram& P, unsigned want_chunks) {
                 t.e = K - 1 - k;
                 t.coef = tw.ck | (tw.idx << 3);
                 if (tw.ck == CK_CONST && P.consts[tw.idx] == 0) continue;  // explicit zero term of an identically-zero constraint
+                if (classes && (*classes)[k] < min_class) continue;      // this coset does not need it
                 terms.push_back(t);
             } while (!tw.last);
         }
@@ -604,7 +619,12 @@ inline QTPlan build_quotient_plan(const AirProgram& P, unsigned want_chunks) {
             bool descriptor_due = true;  // the next piece that does not go on from the previous tile opens with its descriptor
             for (uint32_t t = t_lo; t < t_hi; t++) {
                 const uint32_t tile = tiles[t];
-                const std::vector<uint32_t>& mine = assign[t - t_lo][w];
+                std::vector<uint32_t>& mine = assign[t - t_lo][w];
+                {  // between a piece that goes on from the previous tile (first) and one that goes on in the next (last) the order is
+                   // free: class by class, so that the kernel changes accumulators as rarely as may be
+                    const size_t lo = carry_in[t - t_lo][w] ? 1 : 0, hi = mine.size() - ((t + 1 < t_hi && carry_in[t + 1 - t_lo][w] && !mine.empty()) ? 1 : 0);
+                    if (lo < hi) std::stable_sort(mine.begin() + lo, mine.begin() + hi, [&](uint32_t a, uint32_t b) { return (sg_kind[pieces[a].sg] >> 8) < (sg_kind[pieces[b].sg] >> 8); });
+                }
                 for (size_t pi = 0; pi < mine.size(); pi++) {
                     const uint32_t p = mine[pi];
                     const Piece& pc = pieces[p];
@@ -627,7 +647,9 @@ inline QTPlan build_quotient_plan(const AirProgram& P, unsigned want_chunks) {
                         if (slots)
                             for (uint32_t b : pc.foreign)
                                 if (monos[b].cells[0] != NONE) d.gate[gates.size() + n_foreign++] = monos[b].cells[0] & (REF_COL_MASK | REF_NEXT);
-                        d.ctl = sg_kind[pc.sg] | ((uint32_t)gates.size() << 2) | (compl_mask << 5) | (n_foreign << QT_FOREIGN_SHIFT);
+                        const uint32_t cls = sg_kind[pc.sg] >> 8;
+                        if (cls > QT_MAX_ACCS) throw std::runtime_error("quotient_plan: more classes than the kernel has accumulators");
+                        d.ctl = (sg_kind[pc.sg] & 3u) | ((uint32_t)gates.size() << 2) | (compl_mask << 5) | (n_foreign << QT_FOREIGN_SHIFT) | ((cls ? cls - 1 : 0u) << QT_ACC_SHIFT);
                         Q.recs.push_back({QT_DESC, 0, {d.gate[0], d.gate[1], d.gate[2], d.gate[3], d.ctl, 0}});
                         rec_c_begin.push_back(0);
                         rec_c_end.push_back(0);
@@ -878,9 +900,14 @@ inline gl_t qt_fold_sums_host(const uint64_t S[6]) {
     return r;
 }
 
-inline bool quotient_plan_eval_host(const QTPlan& Q, const gl_t* local, const gl_t* next, const gl_t masks[4], gl_t acc[2]) {
+// `c_begin` .. `c_end`: the chunks to replay (all of them by default; one coset's chunks of a QTClassPlan); `by_acc`: the sums of every
+// accumulator (a plan by class: of class a + 1) on their own, [QT_MAX_ACCS][2] -- `acc` is their total
+inline bool quotient_plan_eval_host(const QTPlan& Q, const gl_t* local, const gl_t* next, const gl_t masks[4], gl_t acc[2], unsigned c_begin = 0,
+                                    unsigned c_end = 0xFFFFFFFFu, gl_t (*by_acc)[2] = nullptr) {
     acc[0] = acc[1] = 0;
-    for (unsigned c = 0; c < Q.n_chunks; c++)
+    if (by_acc)
+        for (unsigned a = 0; a < QT_MAX_ACCS; a++) by_acc[a][0] = by_acc[a][1] = 0;
+    for (unsigned c = c_begin; c < std::min(c_end, Q.n_chunks); c++)
         for (unsigned w = 0; w < QT_WAVES; w++) {
             const QTStream& st = Q.streams[c * QT_WAVES + w];
             const QTRec* rec = &Q.recs[st.rec_off];
@@ -935,7 +962,7 @@ inline bool quotient_plan_eval_host(const QTPlan& Q, const gl_t* local, const gl
                     if (n_in_piece || in_product || have_desc) return false;
                     cur.gate[0] = rec->w[0], cur.gate[1] = rec->w[1], cur.gate[2] = rec->w[2], cur.gate[3] = rec->w[3];
                     cur.ctl = rec->w[4];
-                    if (rec->w[5]) return false;
+                    if (rec->w[5] || (cur.ctl >> (QT_ACC_SHIFT + 3)) || ((cur.ctl >> QT_ACC_SHIFT) & 7u) >= QT_MAX_ACCS) return false;
                     have_desc = true;
                     v = 1;
                     continue;
@@ -990,7 +1017,9 @@ inline bool quotient_plan_eval_host(const QTPlan& Q, const gl_t* local, const gl
                         G = gl_mul(G, gv);
                     }
                     for (int j = 0; j < 2; j++) {
-                        acc[j] = gl_add(acc[j], gl_mul(G, qt_fold_sums_host(S[j])));
+                        const gl_t part = gl_mul(G, qt_fold_sums_host(S[j]));
+                        acc[j] = gl_add(acc[j], part);
+                        if (by_acc) by_acc[(pc->ctl >> QT_ACC_SHIFT) & 7u][j] = gl_add(by_acc[(pc->ctl >> QT_ACC_SHIFT) & 7u][j], part);
                         for (int l = 0; l < 6; l++) S[j][l] = 0;
                     }
                     n_in_piece = 0;
@@ -1000,6 +1029,156 @@ inline bool quotient_plan_eval_host(const QTPlan& Q, const gl_t* local, const gl
             if (n_in_piece || announced || fast) return false;
         }
     return true;
+}
+
+// ---- constraint classes: every constraint on the cosets its own degree needs
+//
+// A constraint with d cell factors (its gates plus its longest monomial) contributes  mask * c / Z_H  to the quotient, a polynomial of
+// degree  d (n - 1) - n < (d - 1) n  when it is plain,  (d - 1) n - d + 1 < (d - 1) n  for a transition (mask x - g^-1), and
+// d n - d - 1 < d n  for a first-row or last-row constraint (mask of degree n - 1) -- for a trace that satisfies it.  A polynomial
+// of degree below k n is fixed by its values on k cosets of n points: k is the constraint's CLASS, max(1, d - 1) for plain and
+// transition constraints, max(1, d) for first-row and last-row ones, clamped to `max_class` (the AIR's quotient factor; the builder
+// of air_ir.h refuses what would lie above it).
+inline std::vector<uint8_t> quotient_constraint_classes(const AirProgram& P, unsigned max_class) {
+    std::vector<uint8_t> cls;
+    cls.reserve(P.n_constraints);
+    AirReader rd(P);
+    GroupWord grp;
+    while (rd.group(&grp)) {
+        for (uint32_t g = 0; g < grp.n_gates; g++) rd.ref();
+        for (uint32_t c = 0; c < grp.m; c++) {
+            uint32_t longest = 0;
+            TermWord tw;
+            do {
+                tw = rd.term();
+                for (uint32_t f = 0; f < tw.nf; f++) rd.ref();
+                longest = std::max(longest, tw.nf);
+            } while (!tw.last);
+            const uint32_t d = grp.n_gates + longest;
+            const uint32_t k = (grp.kind == KIND_FIRST || grp.kind == KIND_LAST) ? d : (d ? d - 1 : 0);
+            cls.push_back((uint8_t)std::min<uint32_t>(std::max<uint32_t>(1, k), std::max(1u, max_class)));
+        }
+    }
+    return cls;
+}
+
+// The plans of the quotient's cosets t = 0 .. n_cosets - 1 (the kernel's point order tt = t n + k): the plan of coset t holds the parts
+// of class > t, with its own tiles -- only those that hold one of its cells --, chunks and streams; `plan` holds these plans back to
+// back and `work` is the list of workgroup rows, coset after coset: the chunk of `plan`, its coset, and the accumulators [acc_lo, acc_hi)
+// its pieces may name (class - 1 for the classes above the coset).  A workgroup keeps one pair of sums per class and writes them to
+// partial[row][accumulator][2][n].  Chunks have about equal cost over all cosets (a coset gets chunks by its share of the terms): a
+// lighter coset has fewer chunks, not shorter ones, and a coset above every class present has none.
+// A SPARE coset t >= n_classes (a quotient factor that is no power of two: degree 4 has three chunks on four cosets) runs EVERY
+// constraint into accumulator 0: its values check the chunks the classes gave (starky's trim_to_len; quotient_class_solve_kernel).
+struct QTClassPlan {
+    QTPlan plan;
+    unsigned n_cosets = 0, n_classes = 0;
+    std::vector<uint32_t> coset_chunk_off;  // [n_cosets + 1]: chunks of `plan` of coset t = its work rows
+    struct Work { uint32_t chunk, coset, acc_lo, acc_hi; };
+    std::vector<Work> work;
+    std::vector<uint32_t> class_constraints, class_terms;  // [n_classes] statistics
+};
+
+// The constants of the recombination (quotient_class_solve_kernel) for rows n = 2^log_n on 2^qdb cosets, QT_SOLVE_WORDS words:
+//   [QT_SOLVE_GINV + t]  g_t^-1,  g_t = 7 w_(n << qdb)^t        [QT_SOLVE_CPOW + 8 t + m]  c_t^m,  c_t = g_t^n
+//   [QT_SOLVE_VINV + (8 k + m) 8 + t]  entry (m, t) of the inverse of the k x k matrix V[t][m] = c_t^m  (k <= 2^qdb):
+//   column t holds the coefficients of the Lagrange polynomial  prod_{u != t} (x - c_u) / (c_t - c_u)
+static const unsigned QT_MAX_COSETS = 8;  // a term has at most three cells and four gates: degree <= 8, factor <= 7
+enum : unsigned { QT_SOLVE_GINV = 0, QT_SOLVE_CPOW = QT_MAX_COSETS, QT_SOLVE_VINV = QT_SOLVE_CPOW + QT_MAX_COSETS * QT_MAX_COSETS,
+                  QT_SOLVE_WORDS = QT_SOLVE_VINV + (QT_MAX_COSETS + 1) * QT_MAX_COSETS * QT_MAX_COSETS };
+inline std::vector<gl_t> quotient_solve_table(unsigned log_n, unsigned qdb) {
+    const unsigned n_cosets = 1u << qdb;
+    if (n_cosets > QT_MAX_COSETS) throw std::runtime_error("quotient_plan: more cosets than the recombination knows");
+    std::vector<gl_t> tab(QT_SOLVE_WORDS, 0);
+    gl_t c[QT_MAX_COSETS];
+    for (unsigned t = 0; t < n_cosets; t++) {
+        const gl_t g = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(log_n + qdb), t));
+        tab[QT_SOLVE_GINV + t] = gl_inv(g);
+        c[t] = gl_pow(g, (uint64_t)1 << log_n);
+        gl_t pw = 1;
+        for (unsigned m = 0; m < QT_MAX_COSETS; m++, pw = gl_mul(pw, c[t])) tab[QT_SOLVE_CPOW + QT_MAX_COSETS * t + m] = pw;
+    }
+    for (unsigned k = 1; k <= n_cosets; k++)
+        for (unsigned t = 0; t < k; t++) {
+            gl_t poly[QT_MAX_COSETS + 1] = {1}, denom = 1;  // prod (x - c_u), lowest coefficient first
+            unsigned deg = 0;
+            for (unsigned u = 0; u < k; u++) {
+                if (u == t) continue;
+                denom = gl_mul(denom, gl_sub(c[t], c[u]));
+                poly[deg + 1] = 0;
+                for (unsigned m = deg + 1; m > 0; m--) poly[m] = gl_sub(poly[m - 1], gl_mul(poly[m], c[u]));
+                poly[0] = gl_neg(gl_mul(poly[0], c[u]));
+                deg++;
+            }
+            const gl_t dinv = gl_inv(denom);
+            for (unsigned m = 0; m < k; m++) tab[QT_SOLVE_VINV + (QT_MAX_COSETS * k + m) * QT_MAX_COSETS + t] = gl_mul(poly[m], dinv);
+        }
+    return tab;
+}
+
+inline QTClassPlan build_quotient_class_plan(const AirProgram& P, unsigned want_chunks, unsigned n_classes, unsigned n_cosets) {
+    if (n_classes < 1 || n_classes > n_cosets || n_classes > QT_MAX_ACCS || n_cosets > QT_MAX_COSETS) throw std::runtime_error("quotient_plan: classes and cosets do not fit");
+    QTClassPlan CP;
+    CP.n_cosets = n_cosets;
+    CP.n_classes = n_classes;
+    const std::vector<uint8_t> cls = quotient_constraint_classes(P, n_classes);
+    CP.class_constraints.assign(n_classes, 0);
+    CP.class_terms.assign(n_classes, 0);
+    {
+        AirReader rd(P);
+        GroupWord grp;
+        uint32_t k = 0;
+        while (rd.group(&grp)) {
+            for (uint32_t g = 0; g < grp.n_gates; g++) rd.ref();
+            for (uint32_t c = 0; c < grp.m; c++, k++) {
+                CP.class_constraints[cls[k] - 1]++;
+                TermWord tw;
+                do {
+                    tw = rd.term();
+                    for (uint32_t f = 0; f < tw.nf; f++) rd.ref();
+                    CP.class_terms[cls[k] - 1]++;
+                } while (!tw.last);
+            }
+        }
+    }
+    uint64_t all_terms = 0;
+    for (uint32_t t : CP.class_terms) all_terms += t;
+    QTPlan& M = CP.plan;
+    M.n_cols = P.n_cols;
+    M.n_constraints = P.n_constraints;
+    M.n_chunks = 0;
+    M.contrib_off.push_back(0);
+    auto append = [&](const QTPlan& Q) {  // Q's chunks behind those M has
+        const uint32_t rec0 = (uint32_t)M.recs.size(), piece0 = (uint32_t)M.pieces.size(), tile0 = (uint32_t)M.tile_list.size(), con0 = (uint32_t)M.contribs.size();
+        M.recs.insert(M.recs.end(), Q.recs.begin(), Q.recs.end());
+        M.pieces.insert(M.pieces.end(), Q.pieces.begin(), Q.pieces.end());
+        for (const QTStream& st : Q.streams) M.streams.push_back({st.rec_off + rec0, st.piece_off + piece0});
+        for (unsigned c = 0; c < Q.n_chunks; c++) M.chunk_tile_off.push_back(Q.chunk_tile_off[c] + tile0);
+        M.tile_list.insert(M.tile_list.end(), Q.tile_list.begin(), Q.tile_list.end());
+        for (size_t r = 1; r < Q.contrib_off.size(); r++) M.contrib_off.push_back(Q.contrib_off[r] + con0);
+        M.contribs.insert(M.contribs.end(), Q.contribs.begin(), Q.contribs.end());
+        M.n_chunks += Q.n_chunks;
+        M.n_supergroups += Q.n_supergroups; M.n_pieces += Q.n_pieces; M.n_piece_ends += Q.n_piece_ends; M.n_absorbed += Q.n_absorbed;
+        M.n_cell_records += Q.n_cell_records; M.n_direct_loads += Q.n_direct_loads;
+        M.cost_sum_max += Q.cost_sum_max; M.cost_sum_mean += Q.cost_sum_mean; M.rec_sum_max += Q.rec_sum_max; M.rec_sum_total += Q.rec_sum_total;
+        M.tile_phases += Q.tile_phases;
+    };
+    for (unsigned t = 0; t < n_cosets; t++) {
+        CP.coset_chunk_off.push_back(M.n_chunks);
+        uint64_t terms_above = 0;  // of the classes above t
+        for (unsigned c = t; c < n_classes; c++) terms_above += CP.class_terms[c];
+        if (t < n_classes) {
+            if (terms_above == 0) continue;  // nothing above this coset: no chunks, no work
+            const unsigned want = (unsigned)std::max<uint64_t>(1, ((uint64_t)want_chunks * terms_above + all_terms / 2) / std::max<uint64_t>(1, all_terms));
+            append(build_quotient_plan(P, want, &cls, t + 1));
+        } else {
+            append(build_quotient_plan(P, std::max(1u, want_chunks)));
+        }
+        for (uint32_t c = CP.coset_chunk_off[t]; c < M.n_chunks; c++) CP.work.push_back({c, t, t < n_classes ? t : 0u, t < n_classes ? n_classes : 1u});
+    }
+    CP.coset_chunk_off.push_back(M.n_chunks);
+    M.chunk_tile_off.push_back((uint32_t)M.tile_list.size());
+    return CP;
 }
 
 }  // namespace starkhip
