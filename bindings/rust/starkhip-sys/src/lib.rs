@@ -166,6 +166,26 @@ pub struct starkhip_free_cells_t {
     pub partly_free_columns: u64,
 }
 
+/// `starkhip_free_cell_classes_t`: the summary of `starkhip_check_trace_free_cell_classes`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct starkhip_free_cell_classes_t {
+    /// n_rows * n_cols = caught + silent + gated + unread
+    pub cells: u64,
+    /// cells some constraint notices when delta is added to them
+    pub caught: u64,
+    /// free cells that a constraint reads with its gates open
+    pub silent: u64,
+    /// free cells read only behind a zero gate product
+    pub gated: u64,
+    /// free cells no constraint that applies reads
+    pub unread: u64,
+    /// columns with at least one silent cell
+    pub silent_columns: u64,
+    /// constraints whose gates were open on no row of the trace
+    pub constraints_never_open: u64,
+}
+
 extern "C" {
     pub fn starkhip_config_standard_fast(cfg: *mut starkhip_config_t);
     pub fn starkhip_config_for_air(air: Air, cfg: *mut starkhip_config_t) -> c_int;
@@ -198,6 +218,15 @@ extern "C" {
     pub fn starkhip_check_trace_free_cells_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                                   public_inputs: *const u64, delta: u64, per_column: *mut u32, free_mask: *mut u64,
                                                   out: *mut starkhip_free_cells_t) -> c_int;
+    // The free cells of that audit by class: per_column [n_cols][3] (silent, gated, unread rows) or null, planes
+    // [3][n_cols][(n_rows + 63) / 64] (read, open, caught; cumulative) or null, open_rows [starkhip_air_num_constraints(air)] or null.
+    pub fn starkhip_check_trace_free_cell_classes(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                                  on_device: c_int, public_inputs: *const u64, delta: u64, per_column: *mut u32,
+                                                  planes: *mut u64, open_rows: *mut u32, out: *mut starkhip_free_cell_classes_t) -> c_int;
+    // tests, small shapes: the same rule as host loops; `trace` is host memory
+    pub fn starkhip_check_trace_free_cell_classes_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                                         public_inputs: *const u64, delta: u64, per_column: *mut u32, planes: *mut u64,
+                                                         open_rows: *mut u32, out: *mut starkhip_free_cell_classes_t) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

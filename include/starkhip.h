@@ -208,6 +208,42 @@ int starkhip_check_trace_free_cells(void* ctx, starkhip_air_t air, const uint64_
 int starkhip_check_trace_free_cells_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
                                            const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* free_mask,
                                            starkhip_free_cells_t* out);
+/* The audit's free cells, told apart: of the cells starkhip_check_trace_free_cells calls free, which does no constraint read, which
+ * are read only behind closed gates, and which are read with the gates open and still not noticed?  Only the last class is where a
+ * missing constraint hides.  An OCCURRENCE is constraint k reading column c as a local or as a next cell (a gate counts as a read).
+ * It puts cell (r, c) in frame r (local) or frame (r - 1) mod n (next), and it counts only when k applies to that frame.  On that
+ * frame, with this one cell replaced by cell + delta mod p (only this occurrence's read changed), let G' be the product of the
+ * group's gates (1 for a group without gates) and body' the constraint's body.  Per cell, over its counting occurrences:
+ *   read:   there is one;   open: some has G' != 0;   caught: some has G' * body' != 0 -- starkhip_check_trace_free_cells's rule, bit
+ *   for bit.  read contains open contains caught, and the classes are CAUGHT = caught, SILENT = open and not caught (a body with no
+ *   live coefficient for the cell on that frame, e.g. a zero co-factor), GATED = read and not open, UNREAD = not read (padding, a
+ *   column no constraint reads, row 0 of a column read only as `next`).  SILENT, GATED and UNREAD partition the audit's free cells.
+ * G' is taken AFTER the change: a cell that is itself a gate opens or closes its own gate.  open_rows[k] is taken on the UNCHANGED
+ * trace: the frames r constraint k applies to with G != 0 -- zero for a constraint this trace never exercised.
+ *   per_column (n_cols x 3, or NULL): the silent, gated and unread rows of each column;
+ *   planes (3 x n_cols x (n_rows + 63) / 64 words, or NULL): plane 0 read, 1 open, 2 caught, each laid out as free_mask above, bits
+ *     at or beyond n_rows zero.  Cumulative, not disjoint class masks: the audit of several traces of one shape is the OR of their
+ *     planes.  Read back from the device only when asked for (3 x 75 MB for FinalExp);
+ *   open_rows (starkhip_air_num_constraints(air) entries, or NULL);
+ *   out: cells = caught + silent + gated + unread, the columns holding a silent cell, the constraints with open_rows[k] == 0.
+ * The audit's two limits carry over: NECESSARY, NOT SUFFICIENT (one cell at a time), and PROBABILISTIC IN delta (a caught cell reads
+ * as silent, an open one as gated, for the at most `degree` roots in delta per occurrence).  Arguments, layouts, the BAD_SHAPE cases
+ * (delta == 0, delta >= p, a NULL `out`) and "one call at a time per context, not beside a prove" are starkhip_check_trace_free_cells's;
+ * cells are read mod p, the trace need not satisfy the AIR, and the result is a pure function of the arguments, the same bytes on
+ * every run.  On the context's device (csrc/kernels_free_classes.hip) it is the audit's walks, the body skipped where every gate
+ * product of the wave is zero; the other checkers and their results are unchanged. */
+typedef struct {
+    uint64_t cells, caught, silent, gated, unread;  /* caught + silent + gated + unread == cells */
+    uint64_t silent_columns;                        /* columns with at least one silent cell */
+    uint64_t constraints_never_open;                /* constraints with open_rows[k] == 0 */
+} starkhip_free_cell_classes_t;
+int starkhip_check_trace_free_cell_classes(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                           int on_device, const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column,
+                                           uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out);
+/* tests: the same rule as host loops on one thread, as starkhip_check_trace_free_cells_replay: for small shapes.  No device needed. */
+int starkhip_check_trace_free_cell_classes_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                                  const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* planes,
+                                                  uint32_t* open_rows, starkhip_free_cell_classes_t* out);
 
 /* --- natives + trace generation (host) ----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.

@@ -295,6 +295,85 @@ def _free_cells_args(air, public_inputs, delta):
     return pis, delta
 
 
+class _FreeCellClassesStruct(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("cells", "caught", "silent", "gated", "unread", "silent_columns", "constraints_never_open")]
+
+
+lib.starkhip_check_trace_free_cell_classes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, C.c_uint64,
+                                                       _u32p, _u64p, _u32p, C.POINTER(_FreeCellClassesStruct)]
+lib.starkhip_check_trace_free_cell_classes_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _u64p, C.c_uint64, _u32p, _u64p,
+                                                              _u32p, C.POINTER(_FreeCellClassesStruct)]
+_POPCOUNT8 = np.array([bin(i).count("1") for i in range(256)], dtype=np.uint32)
+
+
+def _plane_rows(words):
+    """Set bits per column of uint64 words [C, W]."""
+    return _POPCOUNT8[words.view(np.uint8)].reshape(words.shape[0], -1).sum(axis=1, dtype=np.uint32)
+
+
+class FreeCellClasses:
+    """What starkhip_check_trace_free_cell_classes found: FreeCells' free cells told apart.  A cell is unread when no constraint that
+    applies reads it, gated when every constraint that reads it has a zero gate product there, silent when one reads it with its gates
+    open and still does not notice delta added to it -- where a missing constraint hides -- and caught otherwise.  The summary:
+    `cells` = `n_caught` + `n_silent` + `n_gated` + `n_unread`, `silent_columns` (columns holding a silent cell) and
+    `constraints_never_open`; `per_column` (np.uint32[C, 3]): the silent, gated and unread rows of each column; `open_rows`
+    (np.uint32[K]): per constraint, the rows of the unchanged trace on which its gates were open.  `plane_words` (np.uint64[3, C,
+    (n + 63) // 64], or None when the planes were not asked for): the cumulative bitmaps read, open, caught as the library wrote
+    them; `read`, `open`, `caught` (bool[n, C], None without planes) unpack them, and `silent` = open & ~caught, `gated` = read & ~open,
+    `unread` = ~read.  The limits are FreeCells': one cell at a time, probabilistic in delta."""
+
+    def __init__(self, summary, per_column, plane_words, open_rows, n_rows):
+        self.cells, self.n_caught, self.n_silent = int(summary.cells), int(summary.caught), int(summary.silent)
+        self.n_gated, self.n_unread = int(summary.gated), int(summary.unread)
+        self.silent_columns, self.constraints_never_open = int(summary.silent_columns), int(summary.constraints_never_open)
+        self.per_column, self.plane_words, self.open_rows = per_column, plane_words, open_rows
+        self._n_rows, self._planes = n_rows, None
+
+    def _plane(self, i):  # unpacked on first use: eight times the words
+        if self.plane_words is None:
+            return None
+        if self._planes is None:
+            w = self.plane_words
+            bits = np.unpackbits(w.view(np.uint8).reshape(3, w.shape[1], -1), axis=2, bitorder="little")
+            self._planes = np.ascontiguousarray(bits[:, :, :self._n_rows].transpose(0, 2, 1)).astype(bool)
+        return self._planes[i]
+
+    read = property(lambda self: self._plane(0))
+    open = property(lambda self: self._plane(1))
+    caught = property(lambda self: self._plane(2))
+    silent = property(lambda self: None if self.plane_words is None else self._plane(1) & ~self._plane(2))
+    gated = property(lambda self: None if self.plane_words is None else self._plane(0) & ~self._plane(1))
+    unread = property(lambda self: None if self.plane_words is None else ~self._plane(0))
+
+    def merge(self, other):
+        """The audit of both traces (one AIR, one shape): the OR of the planes.  Summary and per_column are recomputed from the merged
+        planes, open_rows are added.  Both results need their planes."""
+        a, b = self.plane_words, other.plane_words
+        if a is None or b is None or a.shape != b.shape or self._n_rows != other._n_rows or self.open_rows.shape != other.open_rows.shape:
+            raise StarkhipError(ERR_BAD_SHAPE)
+        words = a | b
+        per = np.stack([_plane_rows(words[1] & ~words[2]), _plane_rows(words[0] & ~words[1]),
+                        np.uint32(self._n_rows) - _plane_rows(words[0])], axis=1).astype(np.uint32)
+        open_rows = self.open_rows + other.open_rows
+        summary = _FreeCellClassesStruct(self.cells, int(_plane_rows(words[2]).sum()), int(per[:, 0].sum()), int(per[:, 1].sum()),
+                                         int(per[:, 2].sum()), int((per[:, 0] != 0).sum()), int((open_rows == 0).sum()))
+        return FreeCellClasses(summary, per, words, open_rows, self._n_rows)
+
+    def __repr__(self):
+        return (f"FreeCellClasses(cells={self.cells}, caught={self.n_caught}, silent={self.n_silent}, gated={self.n_gated}, "
+                f"unread={self.n_unread}, silent_columns={self.silent_columns}, constraints_never_open={self.constraints_never_open})")
+
+
+def _free_cell_classes(call, air, n_rows, n_cols, planes):
+    """`call(per_column, planes, open_rows, summary)` -> rc: one of the two entry points with its leading arguments bound."""
+    per = np.zeros((n_cols, 3), dtype=np.uint32)
+    words = np.zeros((3, n_cols, (n_rows + 63) // 64), dtype=np.uint64) if planes else None
+    open_rows = np.zeros(air_num_constraints(air), dtype=np.uint32)
+    summary = _FreeCellClassesStruct()
+    _chk(call(per.ctypes.data_as(_u32p), _p64(words) if planes else None, open_rows.ctypes.data_as(_u32p), C.byref(summary)))
+    return FreeCellClasses(summary, per, words, open_rows, n_rows)
+
+
 def air_check_program(blob):
     """The validator starkhip_air_register runs: None for a program it accepts, else the reason it refuses it."""
     blob = np.ascontiguousarray(blob, dtype=np.uint64)
@@ -726,6 +805,30 @@ class Prover:
         try:
             return _free_cells(lambda *out: lib.starkhip_check_trace_free_cells(self._ctx, air, trace_arg, n_rows, n_cols, layout, on_device,
                                                                                 _p64(pis), delta, *out), n_rows, n_cols, mask)
+        finally:
+            self.last_call_s = time.perf_counter() - t0
+
+    def free_cell_classes(self, air, trace, public_inputs, layout=0, delta=DEFAULT_DELTA, planes=True):
+        """free_cells' free cells told apart (starkhip_check_trace_free_cell_classes): a FreeCellClasses -- unread, gated off, or read with
+        the gates open and not noticed -- with the rows each constraint's gates were open on.  planes=False leaves the three bitmaps on
+        the device."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        if trace.ndim != 2 or layout not in (0, 1):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+        return self._free_cell_classes(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, public_inputs, delta, planes)
+
+    def free_cell_classes_device(self, air, trace_ptr, n_rows, public_inputs, layout=1, delta=DEFAULT_DELTA, planes=True):
+        """free_cell_classes on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
+        return self._free_cell_classes(air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, public_inputs, delta, planes)
+
+    def _free_cell_classes(self, air, trace_arg, n_rows, n_cols, layout, on_device, public_inputs, delta, planes):
+        pis, delta = _free_cells_args(air, public_inputs, delta)
+        t0 = time.perf_counter()
+        try:
+            return _free_cell_classes(lambda *out: lib.starkhip_check_trace_free_cell_classes(self._ctx, air, trace_arg, n_rows, n_cols, layout,
+                                                                                              on_device, _p64(pis), delta, *out),
+                                      air, n_rows, n_cols, planes)
         finally:
             self.last_call_s = time.perf_counter() - t0
 
@@ -1273,6 +1376,18 @@ def free_cells_replay(air, trace, public_inputs, layout=0, delta=DEFAULT_DELTA, 
     pis, delta = _free_cells_args(air, public_inputs, delta)
     return _free_cells(lambda *out: lib.starkhip_check_trace_free_cells_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout,
                                                                                _p64(pis), delta, *out), n_rows, n_cols, mask)
+
+
+def free_cell_classes_replay(air, trace, public_inputs, layout=0, delta=DEFAULT_DELTA, planes=True):
+    """starkhip_check_trace_free_cell_classes_replay (tests, small shapes): Prover.free_cell_classes' rule as host loops; no device needed."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    pis, delta = _free_cells_args(air, public_inputs, delta)
+    return _free_cell_classes(lambda *out: lib.starkhip_check_trace_free_cell_classes_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols,
+                                                                                             layout, _p64(pis), delta, *out),
+                              air, n_rows, n_cols, planes)
 
 
 def trace_rows_to_poly_values(trace_rows):

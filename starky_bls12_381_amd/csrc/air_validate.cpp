@@ -131,6 +131,34 @@ gl_t air_constraint_value_at(const AirProgram& P, uint32_t group_word, uint32_t 
     }
 }
 
+void air_constraint_parts_at(const AirProgram& P, uint32_t group_word, uint32_t term_word, const gl_t* local, const gl_t* next, const gl_t* pis,
+                             gl_t* G_out, gl_t* body_out) {
+    auto cell = [&](uint32_t ref) { return gl_from_u64(((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]); };  // any word of the class mod p
+    AirReader rd(P, group_word);
+    GroupWord grp;
+    rd.group(&grp);
+    gl_t G = 1;
+    for (uint32_t j = 0; j < grp.n_gates; j++) {
+        const uint32_t ref = rd.ref();
+        G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, cell(ref)) : cell(ref));
+    }
+    rd = AirReader(P, term_word);
+    gl_t body = 0;
+    for (;;) {
+        const TermWord tw = rd.term();
+        gl_t u = 1;
+        for (uint32_t f = 0; f < tw.nf; f++) u = gl_mul(u, cell(rd.ref()));
+        if (tw.ck == CK_PLUS) body = gl_add(body, u);
+        else if (tw.ck == CK_MINUS) body = gl_sub(body, u);
+        else if (tw.ck == CK_CONST) body = gl_add(body, gl_mul(u, P.consts[tw.idx]));
+        else if (tw.ck == CK_PI) body = gl_add(body, gl_mul(u, pis[tw.idx]));
+        else body = gl_sub(body, gl_mul(u, pis[tw.idx]));
+        if (tw.last) break;
+    }
+    *G_out = G;
+    *body_out = body;
+}
+
 gl_t air_constraint_value(const AirProgram& P, uint32_t k, const gl_t* local, const gl_t* next, const gl_t* pis) {
     // the group of constraint k: the last one whose first constraint is <= k
     const size_t g = (size_t)(std::upper_bound(P.group_k0.begin(), P.group_k0.end(), k) - P.group_k0.begin()) - 1;

@@ -24,5 +24,9 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
 gl_t air_constraint_value(const AirProgram& P, uint32_t k, const gl_t* local, const gl_t* next, const gl_t* pis);
 // the same for a caller that knows where the constraint is: the code words of its group and of its own first term
 gl_t air_constraint_value_at(const AirProgram& P, uint32_t group_word, uint32_t term_word, const gl_t* local, const gl_t* next, const gl_t* pis);
+// the two factors of that value apart: *G the product of the group's gates (1 for a group without gates), *body the constraint's
+// body, both canonical.  What the free-cell classes ask (free_cells.h): was the gate open, and did the body notice?
+void air_constraint_parts_at(const AirProgram& P, uint32_t group_word, uint32_t term_word, const gl_t* local, const gl_t* next, const gl_t* pis,
+                             gl_t* G, gl_t* body);
 
 }  // namespace starkhip

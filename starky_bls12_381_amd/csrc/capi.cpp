@@ -213,6 +213,25 @@ int starkhip_check_trace_free_cells_replay(starkhip_air_t air, const uint64_t* t
     return guarded([&] { return check_trace_free_cells_replay(*a, in, public_inputs, delta, per_column, free_mask, out); });
 }
 
+int starkhip_check_trace_free_cell_classes(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                           int on_device, const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column,
+                                           uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    return guarded([&] { return check_trace_free_cell_classes((Ctx*)ctx, *a, in, public_inputs, delta, per_column, planes, open_rows, out); });
+}
+
+int starkhip_check_trace_free_cell_classes_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                                  const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* planes,
+                                                  uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    return guarded([&] { return check_trace_free_cell_classes_replay(*a, in, public_inputs, delta, per_column, planes, open_rows, out); });
+}
+
 int starkhip_quotient_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[8]) {
     const AirInfo* a = air_get(air);
     if (!a) return STARKHIP_ERR_BAD_AIR;

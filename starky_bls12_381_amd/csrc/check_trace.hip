@@ -1,5 +1,6 @@
 // Host halves of the trace checkers: starkhip_check_trace, starkhip_check_trace_report (under check_report.h; kernels_check.hip) and
-// starkhip_check_trace_free_cells (free_cells.h; kernels_free_cells.hip).  What they share is check_trace_prepare: the shape checks, the
+// starkhip_check_trace_free_cells with starkhip_check_trace_free_cell_classes (free_cells.h; kernels_free_cells.hip,
+// kernels_free_classes.hip).  What they share is check_trace_prepare: the shape checks, the
 // cached op stream of the AIR (Ctx::CheckProgram), the trace and the public inputs on the device -- the CheckView the kernels read.
 #include <hip/hip_runtime.h>
 
@@ -146,6 +147,26 @@ int check_trace_report(Ctx* c, const AirInfo& air, const TraceInput& in, const u
     return check_report_run(air.prog, in.n_rows, passes, per_constraint, row_mask, list, cap, out);
 }
 
+// What the two free-cell entries walk: compile_free_cells of the op stream check_trace_prepare cached for `air`, on the device, cached
+// in c->free_chk.  Op indices of that stream: the same cut gives the same ones.
+static int free_cells_program(Ctx* c, const AirInfo& air) {
+    const AirProgram& P = air.prog;
+    hipStream_t st = c->st;
+    Ctx::FreeCellsProgram& fc = c->free_chk;
+    if (fc.air == air.id && fc.want == c->chk.want) return STARKHIP_OK;
+    fc.air = -1;
+    const FreeProgram F = compile_free_cells(compile_quotient_ops(P, c->chk.want));
+    if (F.cons.size() != P.n_constraints) return STARKHIP_ERR_HIP;
+    HIPCHK(fc.cons.ensure(F.cons.size() * sizeof(FreeCon)));
+    HIPCHK(fc.pivots.ensure(std::max<size_t>(1, F.pivots.size()) * 4));
+    HIPCHK(hipMemcpyAsync(fc.cons.p, F.cons.data(), F.cons.size() * sizeof(FreeCon), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(fc.pivots.p, F.pivots.data(), F.pivots.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(stream_wait(c));  // F goes out of scope
+    fc.air = air.id;
+    fc.want = c->chk.want;
+    return STARKHIP_OK;
+}
+
 // starkhip_check_trace_free_cells: the audit kernel of kernels_free_cells.hip over the view the checkers share, then the count per
 // column.  One launch each: a FinalExp audit stays far below a second.  The bitmap comes back only when asked for.
 int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
@@ -157,18 +178,7 @@ int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, con
     const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64;
     hipStream_t st = c->st;
     Ctx::FreeCellsProgram& fc = c->free_chk;
-    if (fc.air != air.id || fc.want != c->chk.want) {  // op indices of the stream check_trace_prepare cached: the same cut gives the same ones
-        fc.air = -1;
-        const FreeProgram F = compile_free_cells(compile_quotient_ops(P, c->chk.want));
-        if (F.cons.size() != P.n_constraints) return STARKHIP_ERR_HIP;
-        HIPCHK(fc.cons.ensure(F.cons.size() * sizeof(FreeCon)));
-        HIPCHK(fc.pivots.ensure(std::max<size_t>(1, F.pivots.size()) * 4));
-        HIPCHK(hipMemcpyAsync(fc.cons.p, F.cons.data(), F.cons.size() * sizeof(FreeCon), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(fc.pivots.p, F.pivots.data(), F.pivots.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(stream_wait(c));  // F goes out of scope
-        fc.air = air.id;
-        fc.want = c->chk.want;
-    }
+    if (int rc = free_cells_program(c, air)) return rc;
     HIPCHK(fc.words.ensure(C * W * 8));
     HIPCHK(fc.per_column.ensure(C * 4));
     HIPCHK(hipMemsetAsync(fc.words.p, 0, C * W * 8, st));
@@ -180,6 +190,38 @@ int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, con
     HIPCHK(stream_wait(c));
     if (per_column) std::copy(per.begin(), per.end(), per_column);
     *out = free_cells_summary(per.data(), n, C);
+    return STARKHIP_OK;
+}
+
+// starkhip_check_trace_free_cell_classes: the kernel of kernels_free_classes.hip over the same view and the same compiled form, then
+// the count per column.  Buffers of its own beside the audit's, so that neither call disturbs the other's.  The planes come back
+// only when asked for.
+int check_trace_free_cell_classes(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                  uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
+    const AirProgram& P = air.prog;
+    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    CheckView V = {};
+    if (int rc = check_trace_prepare(c, air, in, pis, &V)) return rc;
+    const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64, K = P.n_constraints;
+    hipStream_t st = c->st;
+    Ctx::FreeCellsProgram& fc = c->free_chk;
+    if (int rc = free_cells_program(c, air)) return rc;
+    HIPCHK(fc.planes.ensure(3 * C * W * 8));
+    HIPCHK(fc.class_counts.ensure((3 * C + K) * 4));  // per_column [C][3], open_rows [K]
+    uint32_t* d_per = fc.class_counts.as<uint32_t>();
+    uint32_t* d_open = d_per + 3 * C;
+    HIPCHK(hipMemsetAsync(fc.planes.p, 0, 3 * C * W * 8, st));
+    HIPCHK(hipMemsetAsync(d_open, 0, K * 4, st));
+    HIPCHK(launch_free_cell_classes(V, fc.cons.as<FreeCon>(), fc.pivots.as<uint32_t>(), P.n_constraints, delta, fc.planes.as<unsigned long long>(),
+                                    C * W, d_open, st));
+    HIPCHK(launch_free_cell_classes_count(fc.planes.as<unsigned long long>(), C * W, (uint32_t)C, V.log_n, d_per, st));
+    std::vector<uint32_t> counts(3 * C + K);
+    HIPCHK(hipMemcpyAsync(counts.data(), d_per, counts.size() * 4, hipMemcpyDeviceToHost, st));
+    if (planes) HIPCHK(hipMemcpyAsync(planes, fc.planes.p, 3 * C * W * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(stream_wait(c));
+    if (per_column) std::copy(counts.begin(), counts.begin() + 3 * C, per_column);
+    if (open_rows) std::copy(counts.begin() + 3 * C, counts.end(), open_rows);
+    *out = free_cell_classes_summary(counts.data(), counts.data() + 3 * C, n, C, K);
     return STARKHIP_OK;
 }
 

@@ -181,7 +181,9 @@ struct Ctx {
         int air = -1;
         unsigned want = 0;
         DevBuf cons, pivots, words, per_column;
-        std::vector<DevBuf*> bufs() { return {&cons, &pivots, &words, &per_column}; }
+        // starkhip_check_trace_free_cell_classes: the planes [3][C][(n + 63) / 64], and per_column [C][3] followed by open_rows [K]
+        DevBuf planes, class_counts;
+        std::vector<DevBuf*> bufs() { return {&cons, &pivots, &words, &per_column, &planes, &class_counts}; }
     } free_chk;
 };
 

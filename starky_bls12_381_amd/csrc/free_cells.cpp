@@ -1,5 +1,5 @@
 // starkhip_check_trace_free_cells' host half (free_cells.h): the compiled form the kernel walks, the summary, and the replay
-// without a device.
+// without a device; and the same for starkhip_check_trace_free_cell_classes, which walks that compiled form too.
 #include "free_cells.h"
 
 #include <algorithm>
@@ -107,6 +107,95 @@ int check_trace_free_cells_replay(const AirInfo& air, const TraceInput& in, cons
     }
     if (per_column) std::copy(per.begin(), per.end(), per_column);
     *out = free_cells_summary(per.data(), n, C);
+    return STARKHIP_OK;
+}
+
+starkhip_free_cell_classes_t free_cell_classes_summary(const uint32_t* per_column, const uint32_t* open_rows, size_t n_rows, size_t n_cols,
+                                                       size_t n_constraints) {
+    starkhip_free_cell_classes_t s = {(uint64_t)n_rows * n_cols, 0, 0, 0, 0, 0, 0};
+    for (size_t c = 0; c < n_cols; c++) {
+        s.silent += per_column[3 * c];
+        s.gated += per_column[3 * c + 1];
+        s.unread += per_column[3 * c + 2];
+        s.silent_columns += per_column[3 * c] != 0;
+    }
+    s.caught = s.cells - s.silent - s.gated - s.unread;
+    for (size_t k = 0; k < n_constraints; k++) s.constraints_never_open += open_rows[k] == 0;
+    return s;
+}
+
+int check_trace_free_cell_classes_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                         uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
+    unsigned log_n = 0;
+    if (int rc = check_trace_shape(air, in.n_rows, pis, &log_n)) return rc;
+    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    const AirProgram& P = air.prog;
+    const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64;
+    std::vector<uint64_t> rows;  // row-major, and ours to change: a cell is raised in place, evaluated and put back
+    in.to_row_major(rows);
+    std::vector<uint64_t> bits(3 * C * W, 0);  // read, open, caught
+    uint64_t *rd_p = bits.data(), *op_p = rd_p + C * W, *ca_p = op_p + C * W;
+    std::vector<uint32_t> open(P.n_constraints, 0);
+    AirReader rd(P);
+    GroupWord grp;
+    std::vector<uint32_t> pivots;
+    size_t k = 0;
+    for (size_t g = 0; rd.group(&grp); g++) {
+        const uint32_t group_word = P.group_off[g];
+        std::vector<uint32_t> gates(grp.n_gates);
+        for (uint32_t& ref : gates) ref = rd.ref();
+        for (uint32_t j = 0; j < grp.m; j++, k++) {
+            const uint32_t term_word = (uint32_t)(rd.w - P.code.data());
+            pivots.clear();
+            for (uint32_t ref : gates) add_pivot(pivots, 0, ref);
+            TermWord tw;
+            do {
+                tw = rd.term();
+                for (uint32_t f = 0; f < tw.nf; f++) add_pivot(pivots, 0, rd.ref());
+            } while (!tw.last);
+            gl_t G, body;
+            for (size_t r = 0; r < n; r++) {  // the unchanged trace: the frames this constraint's gates are open on
+                if (!constraint_applies<size_t>(grp.kind, r, n)) continue;
+                air_constraint_parts_at(P, group_word, term_word, &rows[r * C], &rows[(r + 1) % n * C], pis, &G, &body);
+                open[k] += G != 0;
+            }
+            for (uint32_t piv : pivots) {
+                const size_t col = piv & REF_COL_MASK;
+                for (size_t r = 0; r < n; r++) {
+                    const size_t frame = (piv & REF_NEXT) ? (r + n - 1) % n : r;
+                    if (!constraint_applies<size_t>(grp.kind, frame, n)) continue;
+                    uint64_t& cell = rows[r * C + col];
+                    const uint64_t kept = cell;
+                    cell = gl_add(gl_from_u64(kept), delta);  // the cell is any word of its class mod p
+                    air_constraint_parts_at(P, group_word, term_word, &rows[frame * C], &rows[(frame + 1) % n * C], pis, &G, &body);
+                    cell = kept;
+                    const size_t at = col * W + (r >> 6);
+                    const uint64_t bit = 1ull << (r & 63);
+                    rd_p[at] |= bit;
+                    if (G != 0) op_p[at] |= bit;
+                    if (gl_mul(G, body) != 0) ca_p[at] |= bit;
+                }
+            }
+        }
+    }
+    std::vector<uint32_t> per(3 * C);
+    for (size_t c = 0; c < C; c++) {
+        uint32_t silent = 0, gated = 0, unread = 0;
+        for (size_t w = 0; w < W; w++) {
+            const uint64_t all = n - w * 64 >= 64 ? ~0ull : (1ull << (n - w * 64)) - 1;
+            const uint64_t r_w = rd_p[c * W + w], o_w = op_p[c * W + w], c_w = ca_p[c * W + w];
+            silent += (uint32_t)__builtin_popcountll(o_w & ~c_w);
+            gated += (uint32_t)__builtin_popcountll(r_w & ~o_w);
+            unread += (uint32_t)__builtin_popcountll(~r_w & all);
+        }
+        per[3 * c] = silent;
+        per[3 * c + 1] = gated;
+        per[3 * c + 2] = unread;
+    }
+    if (per_column) std::copy(per.begin(), per.end(), per_column);
+    if (planes) std::copy(bits.begin(), bits.end(), planes);
+    if (open_rows) std::copy(open.begin(), open.end(), open_rows);
+    *out = free_cell_classes_summary(per.data(), open.data(), n, C, P.n_constraints);
     return STARKHIP_OK;
 }
 

@@ -113,6 +113,10 @@ int check_trace_report(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*,
 int check_trace_free_cells(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t, uint32_t*, uint64_t*, starkhip_free_cells_t*) {
     return STARKHIP_ERR_NO_DEVICE;
 }
+int check_trace_free_cell_classes(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t, uint32_t*, uint64_t*, uint32_t*,
+                                  starkhip_free_cell_classes_t*) {
+    return STARKHIP_ERR_NO_DEVICE;
+}
 int lde_bench(Ctx*, size_t, unsigned, unsigned, unsigned, unsigned, const uint64_t*, float*, float*) { return STARKHIP_ERR_NO_DEVICE; }
 int field_ops(Ctx*, int, const uint64_t*, const uint64_t*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int host_alloc(Ctx*, size_t, void**) { return STARKHIP_ERR_NO_DEVICE; }

@@ -186,6 +186,15 @@ hipError_t launch_free_cells(const CheckView& v, const FreeCon* cons, const uint
                              unsigned long long* caught, hipStream_t st);
 hipError_t launch_free_cells_count(unsigned long long* words, uint32_t n_cols, unsigned log_n, uint32_t* per_column, hipStream_t st);
 
+// kernels_free_classes.hip: the audit's free cells by class (starkhip_check_trace_free_cell_classes) over the same view and the same
+// `cons` and `pivots`.  planes [3][C][(n + 63) / 64] -- read, open, caught; plane_words = C x (n + 63) / 64 -- and open_rows [K] are
+// zeroed by the caller and only gain bits and counts.  The count leaves the planes as they are and sets per_column[c][0 .. 2] to the
+// column's silent, gated and unread rows.
+hipError_t launch_free_cell_classes(const CheckView& v, const FreeCon* cons, const uint32_t* pivots, uint32_t n_constraints, gl_t delta,
+                                    unsigned long long* planes, size_t plane_words, uint32_t* open_rows, hipStream_t st);
+hipError_t launch_free_cell_classes_count(const unsigned long long* planes, size_t plane_words, uint32_t n_cols, unsigned log_n,
+                                          uint32_t* per_column, hipStream_t st);
+
 // kernels_fri.hip
 hipError_t launch_ext_powers(gl2_t* out, gl2_t base, size_t count, hipStream_t st);
 // weights of the evaluation at z (and, rotated by one, at w_n z) from values on coset 0 of the LDE; scale = (z^n - 7^n) / (n 7^n)

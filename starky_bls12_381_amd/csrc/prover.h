@@ -77,6 +77,10 @@ int check_trace_report(Ctx* c, const AirInfo& air, const TraceInput& in, const u
 // starkhip_check_trace_free_cells: the cells no constraint notices when delta is added to them (kernels_free_cells.hip, free_cells.h)
 int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
                            uint64_t* free_mask, starkhip_free_cells_t* out);
+// starkhip_check_trace_free_cell_classes: those cells as unread, gated off or silent, and the rows each constraint's gates were open on
+// (kernels_free_classes.hip, free_cells.h)
+int check_trace_free_cell_classes(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                  uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out);
 int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out);
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);

@@ -10,7 +10,13 @@ the report on the clean trace (its first pass alone) and the report with cap = 1
 memory, with and without the read-back of the per-cell bitmap, beside the plain check for the ratio; one warm-up call, best and
 median of five, call times from Python.  Then audits one real trace of each built-in AIR and records cells, free cells, wholly and
 partly free columns and the indices of the wholly free columns.  Prints the two results as JSON lines and, with OUT_DIR, writes
-them to OUT_DIR/free_cells_final_exp.json and OUT_DIR/free_cells_builtin_airs.json."""
+them to OUT_DIR/free_cells_final_exp.json and OUT_DIR/free_cells_builtin_airs.json.
+
+--free-classes [OUT_DIR]: times starkhip_check_trace_free_cell_classes (Prover.free_cell_classes_device) the same way, without and with
+the read-back of the three planes, beside the plain check and the free-cell audit timed in the same session; one warm-up call, best
+and median of five.  Then classifies one real trace of each built-in AIR and records the four class totals, the columns holding
+silent cells, the wholly unread columns and the constraints that were never open, each list as runs of indices ("3,7-9").  Prints the two results as
+JSON lines and, with OUT_DIR, writes them to OUT_DIR/free_cell_classes_final_exp.json and OUT_DIR/free_cell_classes_builtin_airs.json."""
 import ctypes as C
 import json
 import os
@@ -131,9 +137,73 @@ def free_cells_mode(out_dir):
                 f.write("\n")
 
 
+def index_ranges(idx):
+    """Ascending indices as one string of runs, "3,7-9,12": thousands of columns stay one line of the JSON file."""
+    idx = np.asarray(idx, dtype=np.int64)
+    if idx.size == 0:
+        return ""
+    cut = np.flatnonzero(np.diff(idx) != 1)
+    first, last = idx[np.r_[0, cut + 1]], idx[np.r_[cut, idx.size - 1]]
+    return ",".join(str(a) if a == b else f"{a}-{b}" for a, b in zip(first.tolist(), last.tolist()))
+
+
+def free_classes_mode(out_dir):
+    torch.cuda.set_device(0)
+    pv = S.Prover(0)
+    timing, audit = {"delta": hex(S.DEFAULT_DELTA), "times": "call times from Python, ms"}, {"delta": hex(S.DEFAULT_DELTA), "airs": {}}
+    for name, air, make in builtin_traces():
+        t, pis = make()
+        n = t.shape[0]
+        cols = torch.from_numpy(np.ascontiguousarray(t.T).view(np.int64)).to("cuda:0")
+        del t
+        torch.cuda.synchronize()
+        assert pv.check_trace_device(air, cols.data_ptr(), n, pis, layout=1)[0] == 0  # also the warm-up of the plain check
+        fc = pv.free_cells_device(air, cols.data_ptr(), n, pis, layout=1, mask=False)  # warm-up of the audit: compiled form, buffers
+        cl = pv.free_cell_classes_device(air, cols.data_ptr(), n, pis, layout=1, planes=False)  # warm-up: the planes' buffers
+        first_ms = pv.last_call_s * 1e3
+        assert cl.n_silent + cl.n_gated + cl.n_unread == fc.free and np.array_equal(cl.per_column.sum(axis=1, dtype=np.uint32), fc.per_column)
+        silent_cols = np.flatnonzero(cl.per_column[:, 0])
+        audit["airs"][name] = {"rows": n, "columns": int(cl.per_column.shape[0]), "constraints": int(cl.open_rows.size), "cells": cl.cells,
+                               "caught": cl.n_caught, "silent": cl.n_silent, "gated": cl.n_gated, "unread": cl.n_unread,
+                               "silent_columns": cl.silent_columns, "constraints_never_open": cl.constraints_never_open, "first_call_ms": first_ms,
+                               "most_silent_rows_in_a_column": int(cl.per_column[:, 0].max()),
+                               "silent_column_indices": index_ranges(silent_cols),
+                               "wholly_unread_column_indices": index_ranges(np.flatnonzero(cl.per_column[:, 2] == n)),
+                               "never_open_constraint_indices": index_ranges(np.flatnonzero(cl.open_rows == 0))}
+        if air == S.AIR_FINAL_EXP:
+            mn, md, _ = best(lambda: pv.check_trace_device(air, cols.data_ptr(), n, pis, layout=1), 5)
+            timing["check_trace_clean_ms"] = {"min": mn, "median": md}
+            mn, md, _ = best(lambda: pv.free_cells_device(air, cols.data_ptr(), n, pis, layout=1, mask=False), 5)
+            timing["free_cells_no_mask_ms"] = {"min": mn, "median": md}
+            mn, md, again = best(lambda: pv.free_cell_classes_device(air, cols.data_ptr(), n, pis, layout=1, planes=False), 5)
+            timing["free_cell_classes_no_planes_ms"] = {"min": mn, "median": md}
+            assert np.array_equal(again.per_column, cl.per_column) and np.array_equal(again.open_rows, cl.open_rows)
+            pv.free_cell_classes_device(air, cols.data_ptr(), n, pis, layout=1, planes=True)
+            mn, md, full = best(lambda: pv.free_cell_classes_device(air, cols.data_ptr(), n, pis, layout=1, planes=True), 5)
+            timing["free_cell_classes_with_planes_ms"] = {"min": mn, "median": md}
+            assert np.array_equal(full.per_column, cl.per_column)
+            timing["plane_bytes"] = int(full.plane_words.nbytes)
+            timing["no_planes_over_free_cells"] = timing["free_cell_classes_no_planes_ms"]["min"] / timing["free_cells_no_mask_ms"]["min"]
+            timing["no_planes_over_check_trace"] = timing["free_cell_classes_no_planes_ms"]["min"] / timing["check_trace_clean_ms"]["min"]
+            timing["first_call_ms"] = first_ms
+            del full
+        del cols
+    pv.close()
+    for fname, obj in (("free_cell_classes_final_exp.json", timing), ("free_cell_classes_builtin_airs.json", audit)):
+        print(json.dumps(obj))
+        if out_dir:
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, fname), "w") as f:
+                json.dump(obj, f, indent=1)
+                f.write("\n")
+
+
 def main():
     if "--report" in sys.argv[1:]:
         return report_mode()
+    if "--free-classes" in sys.argv[1:]:
+        rest = sys.argv[sys.argv.index("--free-classes") + 1:]
+        return free_classes_mode(rest[0] if rest else None)
     if "--free-cells" in sys.argv[1:]:
         rest = sys.argv[sys.argv.index("--free-cells") + 1:]
         return free_cells_mode(rest[0] if rest else None)
