@@ -47,6 +47,9 @@ pub const STARKHIP_ERR_OOM: c_int = -5;
 pub const STARKHIP_ERR_NO_DEVICE: c_int = -6;
 pub const STARKHIP_ERR_VERIFY: c_int = -7;
 pub const STARKHIP_ERR_BAD_AIR: c_int = -8;
+pub const STARKHIP_ERR_TRACE: c_int = -9;
+/// First word of the check blob a checking prove hands back with `STARKHIP_ERR_TRACE` ("SSCHK001").
+pub const STARKHIP_CHECK_MAGIC: u64 = 0x3130304B48435353;
 pub const STARKHIP_POW_SEARCH: u64 = u64::MAX;
 /// A registered AIR is proved on any power of two of rows in 2 ..= 2^STARKHIP_MAX_LOG_ROWS; a built-in AIR on at most 8192.
 pub const STARKHIP_MAX_LOG_ROWS: u32 = 20;
@@ -209,6 +212,14 @@ extern "C" {
     pub fn starkhip_check_trace_report_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                               public_inputs: *const u64, per_constraint: *mut u32, row_mask: *mut u64, list: *mut u64,
                                               cap: usize, out: *mut starkhip_check_report_t) -> c_int;
+    // "check_trace" (starkhip_set_option) / "check_traces" (starkhip_pool_set_option): a prove that returns STARKHIP_ERR_TRACE hands back a
+    // check blob instead of a proof (starkhip_free); this validates it and points `list` (listed x {constraint, row, value}) into it
+    pub fn starkhip_check_blob_layout(blob: *const u64, words: usize, out: *mut starkhip_check_report_t, list: *mut *const u64) -> c_int;
+    // {traces checked, traces rejected} by the context's proofs so far
+    pub fn starkhip_check_stats(ctx: *mut c_void, out: *mut u64) -> c_int;
+    // tests, small shapes: the blob such a prove must hand back, without a device (OK and a null blob for a satisfying trace)
+    pub fn starkhip_check_blob_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int, public_inputs: *const u64,
+                                      cap: usize, blob: *mut *mut u64, words: *mut usize) -> c_int;
     // The cells no constraint notices when `delta` (nonzero, canonical; draw it at random) is added to them, one at a time:
     // per_column [n_cols] or null, free_mask [n_cols][(n_rows + 63) / 64] or null (bit r & 63 of word r >> 6 of column c).
     pub fn starkhip_check_trace_free_cells(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
@@ -288,6 +299,7 @@ extern "C" {
     pub fn starkhip_pool_submit_verify(pool: *mut c_void, air: Air, cfg: *const starkhip_config_t, proof: *const u64, proof_words: usize,
                                        ticket: *mut u64) -> c_int;
     pub fn starkhip_pool_verify_stats(pool: *mut c_void, out: *mut starkhip_pool_verify_stats_t) -> c_int;
+    pub fn starkhip_pool_check_stats(pool: *mut c_void, out: *mut u64) -> c_int;
     pub fn starkhip_multipool_set_option(mpool: *mut c_void, name: *const c_char, value: c_long) -> c_int;
     pub fn starkhip_multipool_submit_verify(mpool: *mut c_void, slot: c_int, air: Air, cfg: *const starkhip_config_t, proof: *const u64,
                                             proof_words: usize, ticket: *mut u64) -> c_int;
@@ -651,7 +663,11 @@ impl Pool {
     pub fn wait(&self, mut ticket: Ticket<'_>) -> Result<Proof, Error> {
         let (mut p, mut w) = (std::ptr::null_mut::<u64>(), 0usize);
         ticket.waited = true; // starkhip_pool_wait consumes the ticket whatever it returns
-        check(unsafe { self.raw_wait(ticket.id, &mut p, &mut w) })?;
+        let rc = unsafe { self.raw_wait(ticket.id, &mut p, &mut w) };
+        if rc != STARKHIP_OK && !p.is_null() {
+            unsafe { starkhip_free(p as *mut c_void) }; // "check_traces": STARKHIP_ERR_TRACE comes with a check blob, which this wrapper does not keep
+        }
+        check(rc)?;
         Ok(unsafe { Prover::take(p, w) })
     }
 }

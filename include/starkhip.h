@@ -96,7 +96,8 @@ enum {
     STARKHIP_ERR_OOM = -5,
     STARKHIP_ERR_NO_DEVICE = -6,
     STARKHIP_ERR_VERIFY = -7,
-    STARKHIP_ERR_BAD_AIR = -8
+    STARKHIP_ERR_BAD_AIR = -8,
+    STARKHIP_ERR_TRACE = -9 /* "check_trace" / "check_traces": the trace violates the AIR; a check blob is handed back instead of a proof */
 };
 
 #define STARKHIP_POW_SEARCH UINT64_MAX
@@ -174,6 +175,35 @@ int starkhip_check_trace_report(void* ctx, starkhip_air_t air, const uint64_t* t
 int starkhip_check_trace_report_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
                                        const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
                                        starkhip_check_report_t* out);
+/* --- the check inside prove() ------------------------------------------------------------------------------------
+ * With the context option "check_trace" = 1 (a pool's "check_traces") every starkhip_prove, _prove_columns and _prove_compact runs
+ * starkhip_check_trace's rule -- every constraint on every row, cells read mod p -- on the copy of the trace it has just put in device
+ * memory (parked in the LDE buffer, in the trace buffer, or the caller's own column-major device memory read in place), after the
+ * upload and before anything of the LDE is enqueued.  Nothing goes up twice, and it works for a recording and a column table, which the
+ * stand-alone checkers do not take.  A satisfying trace: the proof goes on, with the bytes it has without the option.  A violating one:
+ * the call returns STARKHIP_ERR_TRACE, no later phase has been enqueued (a pooled proof has not asked for its commitment), the context
+ * stays usable, and *proof / *proof_words hand back a CHECK BLOB instead of a proof -- library-owned, released with starkhip_free:
+ *   word 0  STARKHIP_CHECK_MAGIC ("SSCHK001"; a proof starts with the proof magic)     word 4  constraints_violated
+ *   word 1  AIR id                                                                     word 5  rows_violated
+ *   word 2  n_rows                                                                     word 6  listed
+ *   word 3  violations                                                                 word 7  0
+ *   then listed x {constraint, row, value}: what starkhip_check_trace_report returns for the same trace with cap = "check_trace_list"
+ *   (0 .. STARKHIP_CHECK_LIST_MAX, default 16) -- same order, same values, same cut.  `violations` is starkhip_check_trace's count and
+ *   entry 0 its `first`.
+ * The plain check kernel decides (24.6 ms for FinalExp); the report's two passes run only for a violating trace.  The
+ * first checked proof of an AIR on a context allocates the AIR's check program on the device, and a device allocation waits for every
+ * stream of the device: a pool sees one such pause per context and AIR (there is no warm-up for it).
+ * starkhip_check_blob_layout validates magic and length (BAD_SHAPE otherwise; a proof blob, a truncated blob and one whose `listed`
+ * disagrees with its length are refused) and points *list (may be NULL) into the blob, NULL when nothing is listed.
+ * starkhip_check_stats: out = {traces checked, traces rejected} by this context's proofs so far. */
+#define STARKHIP_CHECK_MAGIC 0x3130304B48435353ULL
+int starkhip_check_blob_layout(const uint64_t* blob, size_t words, starkhip_check_report_t* out, const uint64_t** list);
+int starkhip_check_stats(void* ctx, uint64_t out[2]);
+/* tests: what a checking prove must hand back for `trace` (host memory) with "check_trace_list" = cap, without a device: STARKHIP_OK
+ * and *blob = NULL for a satisfying trace, STARKHIP_ERR_TRACE and the blob (starkhip_free) otherwise.  Built on
+ * starkhip_check_trace_report_replay: for small shapes.  Arguments and BAD_SHAPE cases as there. */
+int starkhip_check_blob_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const uint64_t* public_inputs,
+                               size_t cap, uint64_t** blob, size_t* words);
 /* The opposite question: which cells of the trace could a prover change without any constraint noticing?  Under-constrained cells
  * are a soundness bug that a satisfying trace never shows.  `delta` is a nonzero canonical field element.  Cell (r, c) is CAUGHT
  * when some constraint that reads column c is nonzero on the frame the read puts the cell in, with this one cell replaced by
@@ -305,8 +335,11 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
  * give the same proof bytes.  For a trace that violates a constraint they do not: the violated class's sum is not divisible by Z_H, so
  * its values on a few cosets and on all of them interpolate to different polynomials; either proof is rejected by the verifier, an AIR
  * whose quotient has a spare coset (degree 4) fails with STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE either way, and starkhip_check_trace is the
- * tool for such a trace.  AIRs of degree above 5, the profiling modes and the comparison of the two evaluators always run as 1),
+ * tool for such a trace -- or "check_trace" below, which refuses it inside the prove call.  AIRs of degree above 5, the profiling modes and the comparison of the two evaluators always run as 1),
  * "quotient_chunks" (0 = automatic),
+ * "check_trace" (0 = default / 1: every prove on the context checks its trace against the AIR before the LDE and returns
+ * STARKHIP_ERR_TRACE with a check blob for a violating one -- "the check inside prove()" above), "check_trace_list" (0 ..
+ * STARKHIP_CHECK_LIST_MAX, default 16: the violations such a blob lists),
  * "quotient_waves", "quotient_slots", "lde_closed_forms" (1 = constant and unit-vector trace columns take their closed-form LDE
  * instead of five transforms, 0 = every column is transformed; same bytes either way; traces of 2^14 rows and more have no closed forms and transform every column), "host_commit_leaves" (default 64: trace commitments of at most this many leaves -- FP12Mul's 32 -- are hashed by host threads with the
  * challenger's permutation, 0.8 us against 5.6 us per permutation of a lone GPU wave; 0 = never; only with "leaf_hash_form" 0), "leaf_hash_form" (0 = a context on its own
@@ -470,8 +503,15 @@ int starkhip_hw_queues_status(void);
  *                     frees the proof.  The verifier reads the host blob the caller receives; the prover context is free already.
  *   "verify_arena_mb" the verifier's device memory (default 1024), allocated at the first verify work, or when "verify_proofs" is
  *                     switched on in a pool created with warm_up.  A proof larger than half of it is verified alone.  Changing it
- *                     once the arena exists: STARKHIP_ERR_BAD_SHAPE. */
+ *                     once the arena exists: STARKHIP_ERR_BAD_SHAPE.
+ *   "check_traces"    0 (default) or 1: every proving ticket submitted from then on has its trace checked against the AIR by its context,
+ *                     as the context option "check_trace" does, whichever submit it came through (a witness job's recording included).
+ *                     A violating trace: starkhip_pool_wait returns STARKHIP_ERR_TRACE and hands over the check blob in *proof
+ *                     (starkhip_free); with "verify_proofs" on as well it never reaches the verifier.
+ *   "check_trace_list" 0 .. STARKHIP_CHECK_LIST_MAX (default 16): the violations such a blob lists; read at submit too. */
 int starkhip_pool_set_option(void* pool, const char* name, long value);
+/* out = {traces checked, traces rejected}, summed over the pool's contexts (per slot of a multi-device handle: starkhip_multipool_pool) */
+int starkhip_pool_check_stats(void* pool, uint64_t out[2]);
 /* A verification job for any proof (of this pool, another one, or the oracle); cfg == NULL: starkhip_config_for_air.  The proof stays the
  * caller's until the ticket has been waited for.  starkhip_pool_wait on the ticket returns exactly starkhip_verify's code for it (OK,
  * VERIFY, BAD_SHAPE, BAD_AIR), or HIP / OOM if the device work failed; it sets *proof = NULL and *proof_words = 0, and of `info` only
@@ -538,7 +578,7 @@ double starkhip_air_verify_cost(starkhip_air_t air);
 int starkhip_plan_lpt(size_t n_jobs, const starkhip_air_t* airs, size_t n_pools, int* slots);
 double starkhip_air_cost(starkhip_air_t air);
 
-/* per-phase device timings of the last prove on this ctx, milliseconds (HIP events):
+/* per-phase device timings of the last prove on this ctx, milliseconds (HIP events; with "check_trace" on, [0] includes the check):
  * [0] upload/transpose [1] ifft+lde [2] trace leaf hash + merkle [3] quotient [4] quotient commit
  * [5] openings [6] fri combine [7] fri commit [8] pow [9] queries [10] total */
 #define STARKHIP_N_PHASES 11

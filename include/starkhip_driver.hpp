@@ -299,15 +299,16 @@ class Pool {
         check("starkhip_config_for_air", starkhip_config_for_air(air, &p.config));
         uint64_t* blob = nullptr;
         size_t words = 0;
-        if (multi_) check("starkhip_multipool_wait", starkhip_multipool_wait(pool_, ticket, &blob, &words, &p.info));
-        else check("starkhip_pool_wait", starkhip_pool_wait(pool_, ticket, &blob, &words, &p.info));
+        const int rc = multi_ ? starkhip_multipool_wait(pool_, ticket, &blob, &words, &p.info) : starkhip_pool_wait(pool_, ticket, &blob, &words, &p.info);
+        if (rc != STARKHIP_OK) starkhip_free(blob);  // "check_traces": a refused trace (STARKHIP_ERR_TRACE) comes with a check blob; this driver does not keep it
+        check(multi_ ? "starkhip_multipool_wait" : "starkhip_pool_wait", rc);
         if (info) *info = p.info;
         p.words = Words(blob, words);
         p.n_public_inputs = (size_t)starkhip_air_public_inputs(air);
         if (verify.on == VerifyOn::host) check("starkhip_verify", starkhip_verify(air, &p.config, p.words.data(), p.words.size()));
         return p;
     }
-    // starkhip_pool_set_option (every pool of a multi-device handle): "verify_proofs", "verify_arena_mb"
+    // starkhip_pool_set_option (every pool of a multi-device handle): "verify_proofs", "verify_arena_mb", "check_traces", "check_trace_list"
     void set_option(const char* name, long value) {
         if (multi_) check("starkhip_multipool_set_option", starkhip_multipool_set_option(pool_, name, value));
         else check("starkhip_pool_set_option", starkhip_pool_set_option(pool_, name, value));

@@ -37,7 +37,7 @@ ECC_NUM_POINTS = 512  # src/ecc_aggregate.rs:7
 AIR_CUSTOM_BASE, AIR_CUSTOM_CAPACITY = 1024, 4096  # ids of registered AIRs (register_air): BASE, BASE + 1, ...
 MAX_LOG_ROWS = 20  # STARKHIP_MAX_LOG_ROWS: a registered AIR's trace has up to 2^20 rows (a built-in AIR's: 8192)
 
-ERR_QUOTIENT_NOT_DIVISIBLE, ERR_ZETA_IN_SUBGROUP, ERR_BAD_SHAPE, ERR_HIP, ERR_OOM, ERR_NO_DEVICE, ERR_VERIFY, ERR_BAD_AIR = range(-1, -9, -1)
+ERR_QUOTIENT_NOT_DIVISIBLE, ERR_ZETA_IN_SUBGROUP, ERR_BAD_SHAPE, ERR_HIP, ERR_OOM, ERR_NO_DEVICE, ERR_VERIFY, ERR_BAD_AIR, ERR_TRACE = range(-1, -10, -1)
 
 
 class StarkConfig(C.Structure):
@@ -237,6 +237,88 @@ def _check_trace_report(call, air, n_rows, cap):
     summary = _CheckReportStruct()
     _chk(call(per.ctypes.data_as(_u32p), _p64(mask), _p64(entries) if cap else None, cap, C.byref(summary)))
     return CheckReport(summary, per, mask, entries)
+
+
+CHECK_MAGIC = 0x3130304B48435353  # STARKHIP_CHECK_MAGIC, "SSCHK001"
+lib.starkhip_check_blob_layout.argtypes = [_u64p, C.c_size_t, C.POINTER(_CheckReportStruct), C.POINTER(_u64p)]
+lib.starkhip_check_blob_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _u64p, C.c_size_t, C.POINTER(_u64p), C.POINTER(C.c_size_t)]
+lib.starkhip_check_stats.argtypes = [C.c_void_p, _u64p]
+lib.starkhip_pool_check_stats.argtypes = [C.c_void_p, _u64p]
+
+
+class CheckBlobReport(CheckReport):
+    """A check blob read (parse_check_blob): a CheckReport with the summary -- `violations`, `constraints_violated`, `rows_violated` --
+    and `list` (np.uint64[listed, 3]): the first "check_trace_list" violations as (constraint, row, value), by constraint, then row;
+    with the blob's `air` and `n_rows`.  The per-constraint counts and the row mask are not in a blob: `per_constraint`, `row_mask`
+    and `rows` are None."""
+
+    def __init__(self, air, n_rows, summary, entries):
+        self.air, self.n_rows = int(air), int(n_rows)
+        self.per_constraint = self.row_mask = self.rows = None
+        self.violations, self.constraints_violated, self.rows_violated = (int(summary.violations), int(summary.constraints_violated),
+                                                                          int(summary.rows_violated))
+        self.list = entries
+
+    def __repr__(self):
+        return (f"CheckBlobReport(air={self.air}, n_rows={self.n_rows}, violations={self.violations}, "
+                f"constraints_violated={self.constraints_violated}, rows_violated={self.rows_violated}, listed={len(self.list)})")
+
+
+def parse_check_blob(blob):
+    """starkhip_check_blob_layout on a check blob (np.uint64): its CheckBlobReport; StarkhipError(ERR_BAD_SHAPE) for anything else."""
+    b = np.ascontiguousarray(blob, dtype=np.uint64).reshape(-1)
+    summary = _CheckReportStruct()
+    lst = _u64p()
+    _chk(lib.starkhip_check_blob_layout(_p64(b), b.size, C.byref(summary), C.byref(lst)))
+    listed = int(summary.listed)
+    entries = b[8:8 + 3 * listed].reshape(listed, 3).copy()
+    return CheckBlobReport(b[1], b[2], summary, entries)
+
+
+class TraceViolation(StarkhipError):
+    """ERR_TRACE from a prove with "check_trace" on, or from a pool with "check_traces": the trace violates the AIR.  `.blob` is the
+    check blob (np.uint64) and `.report` its CheckBlobReport."""
+
+    def __init__(self, blob):
+        super().__init__(ERR_TRACE)
+        self.blob = blob
+        self.report = parse_check_blob(blob)
+
+
+def _take_blob(rc, out, words, keep=True):
+    """The result of a proving call: the proof as a numpy copy (None unless `keep`), the library's blob freed; TraceViolation with the
+    check blob for ERR_TRACE, StarkhipError for every other failure."""
+    if rc == ERR_TRACE and out:
+        blob = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
+        lib.starkhip_free(out)
+        raise TraceViolation(blob)
+    _chk(rc)
+    proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy() if keep else None
+    lib.starkhip_free(out)
+    return proof
+
+
+def check_blob_replay(air, trace, public_inputs, layout=0, cap=16):
+    """starkhip_check_blob_replay (tests, small shapes): the check blob a checking prove must hand back for `trace` with
+    "check_trace_list" = cap, or None for a satisfying trace; no device needed."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1) or int(cap) < 0:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    if pis.size != air_public_inputs(air):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    out = _u64p()
+    words = C.c_size_t()
+    rc = lib.starkhip_check_blob_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, _p64(pis), int(cap), C.byref(out),
+                                        C.byref(words))
+    if rc == 0:
+        return None
+    if rc != ERR_TRACE:
+        raise StarkhipError(rc)
+    blob = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
+    lib.starkhip_free(out)
+    return blob
 
 
 class _FreeCellsStruct(C.Structure):
@@ -695,10 +777,7 @@ class Prover:
             t0 = time.perf_counter()
             rc = lib.starkhip_prove_compact(self._ctx, air, C.byref(config), trace._h, _p64(pis), pis.size, pow_witness, C.byref(out), C.byref(words))
             self.last_call_s = time.perf_counter() - t0  # the C call alone, without the copy into a numpy array below
-            _chk(rc)
-            proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
-            lib.starkhip_free(out)
-            return proof
+            return _take_blob(rc, out, words)
         trace = np.ascontiguousarray(trace, dtype=np.uint64)
         if trace.ndim != 2 or layout not in (0, 1):
             raise StarkhipError(ERR_BAD_SHAPE)
@@ -710,10 +789,7 @@ class Prover:
         rc = lib.starkhip_prove(self._ctx, air, C.byref(config), trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, _p64(pis), pis.size,
                                 pow_witness, C.byref(out), C.byref(words))
         self.last_call_s = time.perf_counter() - t0
-        _chk(rc)
-        proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
-        lib.starkhip_free(out)
-        return proof
+        return _take_blob(rc, out, words)
 
     def prove_columns(self, air, config, columns, public_inputs, pow_witness=POW_SEARCH):
         """starky's literal `prove(stark, &config, trace_poly_values, ..)`: `columns` is a sequence of separately allocated 1-D uint64
@@ -722,11 +798,9 @@ class Prover:
         pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
         out = _u64p()
         words = C.c_size_t()
-        _chk(lib.starkhip_prove_columns(self._ctx, air, C.byref(config), table, n_rows, len(keep), _p64(pis), pis.size, pow_witness, C.byref(out),
-                                        C.byref(words)))
-        proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
-        lib.starkhip_free(out)
-        return proof
+        rc = lib.starkhip_prove_columns(self._ctx, air, C.byref(config), table, n_rows, len(keep), _p64(pis), pis.size, pow_witness, C.byref(out),
+                                        C.byref(words))
+        return _take_blob(rc, out, words)
 
     def check_trace(self, air, trace, public_inputs, layout=0):
         """Every constraint of `air` on every row of `trace` (row-major [n][C], or column-major [C][n] with layout=1), on this context's
@@ -847,8 +921,15 @@ class Prover:
         return np.ascontiguousarray(out.T)
 
     def set_option(self, name, value):
-        """Tuning knob of this context (starkhip_set_option)."""
+        """Tuning knob of this context (starkhip_set_option).  "check_trace" = 1: every prove* checks its trace against the AIR on the
+        device before the LDE and raises TraceViolation for a violating one ("check_trace_list": the violations its report lists)."""
         _chk(lib.starkhip_set_option(self._ctx, name.encode(), int(value)))
+
+    def check_stats(self):
+        """starkhip_check_stats: {"checked", "rejected"} -- traces this context's proofs have checked / refused so far."""
+        out = np.zeros(2, dtype=np.uint64)
+        _chk(lib.starkhip_check_stats(self._ctx, _p64(out)))
+        return {"checked": int(out[0]), "rejected": int(out[1])}
 
     def prove_device(self, air, config, trace_ptr, n_rows, public_inputs, pow_witness=POW_SEARCH, layout=1, keep=True):
         """trace_ptr: integer device address of a uint64 trace (n_rows x air_columns(air) words) already resident in HBM
@@ -856,11 +937,11 @@ class Prover:
         pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
         out = _u64p()
         words = C.c_size_t()
-        _chk(lib.starkhip_prove(self._ctx, air, C.byref(config), C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, _p64(pis), pis.size, pow_witness,
-                                C.byref(out), C.byref(words)))
-        proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy() if keep else None
-        lib.starkhip_free(out)
-        return proof
+        t0 = time.perf_counter()
+        rc = lib.starkhip_prove(self._ctx, air, C.byref(config), C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, _p64(pis), pis.size, pow_witness,
+                                C.byref(out), C.byref(words))
+        self.last_call_s = time.perf_counter() - t0
+        return _take_blob(rc, out, words, keep)
 
     def host_array(self, shape, dtype=np.uint64):
         """Page-locked host array (starkhip_host_alloc) to generate traces into, again and again (`trace_*(…, out=buf)`):
@@ -1124,7 +1205,8 @@ class ProofPool:
             raise
 
     def set_option(self, name, value):
-        """starkhip_pool_set_option on every pool of the handle: "verify_proofs" (0 / 1), "verify_arena_mb"."""
+        """starkhip_pool_set_option on every pool of the handle: "verify_proofs" (0 / 1), "verify_arena_mb", "check_traces" (0 / 1: wait
+        raises TraceViolation for a trace that violates its AIR), "check_trace_list"."""
         if self._multi:
             _chk(lib.starkhip_multipool_set_option(self._h, name.encode(), int(value)))
         else:
@@ -1166,6 +1248,15 @@ class ProofPool:
             one = {n: (float if t is C.c_double else int)(getattr(r, n)) for n, t in PoolVerifyStats._fields_}
             out = one if out is None else {n: out[n] + one[n] for n in out}
         return out
+
+    def check_stats(self, per_pool=False):
+        """starkhip_pool_check_stats: {"checked", "rejected"} summed over the handle's pools, or one dict per pool."""
+        each = []
+        for h in self._pools():
+            out = np.zeros(2, dtype=np.uint64)
+            _chk(lib.starkhip_pool_check_stats(h, _p64(out)))
+            each.append({"checked": int(out[0]), "rejected": int(out[1])})
+        return each if per_pool else {n: sum(e[n] for e in each) for n in each[0]}
 
     def _call(self, name, slot, *args):
         if self._multi:
@@ -1271,7 +1362,8 @@ class ProofPool:
         return [int(t) for t in tickets]
 
     def wait(self, ticket, keep=True):
-        """(proof, info) of `ticket`; raises StarkhipError with the proof's status if it failed.  info: phase_ms / kernel_ms
+        """(proof, info) of `ticket`; raises StarkhipError with the proof's status if it failed (TraceViolation, with the report, for a
+        trace the pool's "check_traces" refused).  info: phase_ms / kernel_ms
         dicts and the job's timeline in seconds since the pool was created."""
         out = _u64p()
         words = C.c_size_t()
@@ -1283,9 +1375,7 @@ class ProofPool:
             if rc in (ERR_HIP, ERR_OOM, ERR_NO_DEVICE):
                 _chk(rc)
             return rc
-        _chk(rc)
-        proof = np.ctypeslib.as_array(out, shape=(words.value,)).copy() if keep else None
-        lib.starkhip_free(out)
+        proof = _take_blob(rc, out, words, keep)
         return proof, {"phase_ms": dict(zip(PHASE_NAMES, [float(x) for x in info.phase_ms])),
                        "kernel_ms": {"lde_columns": float(info.kernel_ms[0]), "leaf_hash": float(info.kernel_ms[1]), "quotient_eval": float(info.kernel_ms[2])},
                        "host_ms": {"fiat_shamir": float(info.host_ms[0]), "other": float(info.host_ms[1])},

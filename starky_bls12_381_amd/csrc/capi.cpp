@@ -194,6 +194,26 @@ int starkhip_check_trace_report_replay(starkhip_air_t air, const uint64_t* trace
     return guarded([&] { return check_trace_report_replay(*a, in, public_inputs, per_constraint, row_mask, list, cap, out); });
 }
 
+int starkhip_check_blob_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const uint64_t* public_inputs,
+                               size_t cap, uint64_t** blob, size_t* words) {
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = checker_args(a, in, public_inputs, blob, !words || cap > STARKHIP_CHECK_LIST_MAX)) return rc;
+    return guarded([&] { return check_blob_replay(*a, in, public_inputs, cap, blob, words); });
+}
+
+int starkhip_check_blob_layout(const uint64_t* blob, size_t words, starkhip_check_report_t* out, const uint64_t** list) {
+    if (!out || !check_blob_read(blob, words, out, list)) return STARKHIP_ERR_BAD_SHAPE;
+    return STARKHIP_OK;
+}
+
+int starkhip_check_stats(void* ctx, uint64_t out[2]) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    if (!out) return STARKHIP_ERR_BAD_SHAPE;
+    ctx_check_stats((Ctx*)ctx, out);
+    return STARKHIP_OK;
+}
+
 int starkhip_check_trace_free_cells(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
                                     const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* free_mask,
                                     starkhip_free_cells_t* out) {
@@ -674,6 +694,11 @@ int starkhip_pool_verify_stats(void* pool, starkhip_pool_verify_stats_t* out) {
     return pool_verify_stats((Pool*)pool, out);
 }
 
+int starkhip_pool_check_stats(void* pool, uint64_t out[2]) {
+    if (!pool || !out) return STARKHIP_ERR_BAD_SHAPE;
+    return pool_check_stats((Pool*)pool, out);
+}
+
 // ---- a pool per device behind one handle (multipool.cpp)
 int starkhip_multipool_create(const int* devices, size_t n_devices, const starkhip_pool_config_t* cfg, void** mpool) {
     if (!devices || !n_devices || !cfg || !mpool) return STARKHIP_ERR_BAD_SHAPE;
@@ -938,6 +963,7 @@ const char* starkhip_error_string(int code) {
         case STARKHIP_ERR_NO_DEVICE: return "no such HIP device / context";
         case STARKHIP_ERR_VERIFY: return "proof rejected";
         case STARKHIP_ERR_BAD_AIR: return "unknown or unbuildable AIR id";
+        case STARKHIP_ERR_TRACE: return "the trace violates the AIR (\"check_trace\"): a check blob is returned instead of a proof";
         default: return "unknown error";
     }
 }

@@ -1,6 +1,9 @@
 // starkhip_check_trace_report's host half (check_report.h) and its replay without a device.
 #include "check_report.h"
 
+#include <stdlib.h>
+#include <string.h>
+
 #include <algorithm>
 #include <vector>
 
@@ -113,6 +116,37 @@ int check_trace_report_replay(const AirInfo& air, const TraceInput& in, const ui
     in.to_row_major(rows);
     ReplayPasses passes(P, rows.data(), in.n_rows, pis);
     return check_report_run(P, in.n_rows, passes, per_constraint, row_mask, list, cap, out);
+}
+
+uint64_t* check_blob_make(int air, size_t n_rows, const starkhip_check_report_t& rep, const uint64_t* list, size_t* words) {
+    const size_t total = CHECK_BLOB_HEADER + 3 * (size_t)rep.listed;
+    uint64_t* b = (uint64_t*)malloc(total * 8);
+    if (!b) return nullptr;
+    const uint64_t head[CHECK_BLOB_HEADER] = {STARKHIP_CHECK_MAGIC, (uint64_t)air, n_rows, rep.violations, rep.constraints_violated, rep.rows_violated, rep.listed, 0};
+    memcpy(b, head, sizeof head);
+    if (rep.listed) memcpy(b + CHECK_BLOB_HEADER, list, 3 * (size_t)rep.listed * 8);
+    *words = total;
+    return b;
+}
+
+bool check_blob_read(const uint64_t* blob, size_t words, starkhip_check_report_t* out, const uint64_t** list) {
+    if (!blob || words < CHECK_BLOB_HEADER || blob[0] != STARKHIP_CHECK_MAGIC || blob[7] != 0) return false;
+    const uint64_t listed = blob[6];
+    if (listed > STARKHIP_CHECK_LIST_MAX || listed > blob[3] || words != CHECK_BLOB_HEADER + 3 * (size_t)listed) return false;
+    *out = starkhip_check_report_t{blob[3], blob[4], blob[5], listed};
+    if (list) *list = listed ? blob + CHECK_BLOB_HEADER : nullptr;
+    return true;
+}
+
+int check_blob_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, size_t cap, uint64_t** blob, size_t* words) {
+    *blob = nullptr;
+    *words = 0;
+    std::vector<uint64_t> list(3 * std::max<size_t>(1, cap));
+    starkhip_check_report_t rep = {0, 0, 0, 0};
+    if (int rc = check_trace_report_replay(air, in, pis, nullptr, nullptr, list.data(), cap, &rep)) return rc;
+    if (!rep.violations) return STARKHIP_OK;
+    *blob = check_blob_make(air.id, in.n_rows, rep, list.data(), words);
+    return *blob ? STARKHIP_ERR_TRACE : STARKHIP_ERR_OOM;
 }
 
 }  // namespace starkhip

@@ -41,4 +41,15 @@ int check_report_run(const AirProgram& P, size_t n_rows, CheckPasses& passes, ui
 int check_trace_report_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint32_t* per_constraint, uint64_t* row_mask,
                               uint64_t* list, size_t cap, starkhip_check_report_t* out);
 
+// The check blob a prove() with "check_trace" hands back for a violating trace (starkhip.h has the table): CHECK_BLOB_HEADER words
+// {magic, AIR id, n_rows, violations, constraints_violated, rows_violated, listed, 0}, then the report's list.  From malloc, never
+// from the proof arena: starkhip_free releases it like a proof.  nullptr: out of memory.
+static const size_t CHECK_BLOB_HEADER = 8;
+uint64_t* check_blob_make(int air, size_t n_rows, const starkhip_check_report_t& rep, const uint64_t* list, size_t* words);
+// *list points into the blob; false for anything that is not exactly one check blob
+bool check_blob_read(const uint64_t* blob, size_t words, starkhip_check_report_t* out, const uint64_t** list);
+// what prove() must hand back for this trace with "check_trace_list" = cap, without a device: STARKHIP_OK and no blob, or
+// STARKHIP_ERR_TRACE and the blob (check_trace_report_replay underneath)
+int check_blob_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, size_t cap, uint64_t** blob, size_t* words);
+
 }  // namespace starkhip

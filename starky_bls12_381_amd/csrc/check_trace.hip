@@ -1,7 +1,8 @@
 // Host halves of the trace checkers: starkhip_check_trace, starkhip_check_trace_report (under check_report.h; kernels_check.hip) and
 // starkhip_check_trace_free_cells with starkhip_check_trace_free_cell_classes (free_cells.h; kernels_free_cells.hip,
-// kernels_free_classes.hip).  What they share is check_trace_prepare: the shape checks, the
-// cached op stream of the AIR (Ctx::CheckProgram), the trace and the public inputs on the device -- the CheckView the kernels read.
+// kernels_free_classes.hip), and the check prove() runs on its own copy of the trace ("check_trace": check_trace_in_prove).  What the
+// stand-alone ones share is check_trace_prepare: the shape checks, the cached op stream of the AIR (check_program, Ctx::CheckProgram),
+// the trace and the public inputs on the device -- the CheckView the kernels read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,16 +16,11 @@
 
 namespace starkhip {
 
-// starkhip_check_trace.  The trace goes where prove() would put it -- column-major in `values`, or the caller's own device memory --
-// with the LDE buffer as the upload staging of row-major host rows.  The op stream is cached per context like the quotient's.
-// What both checkers do before their kernels: the shape checks, the op stream of `air` (cached), the trace on the device and the
-// public inputs in c->pis; *V is what the kernels read of it.
-static int check_trace_prepare(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, CheckView* V) {
+// The op stream of `air` for a trace of n_rows, compiled and uploaded once and cached per context like the quotient's (Ctx::CheckProgram),
+// and the part of the view that comes from it.  It allocates only the program's own buffers: prove() calls it with a trace parked in the
+// LDE buffer.  A device allocation all the same, so the first check of an AIR on a context waits for every stream of the device.
+static int check_program(Ctx* c, const AirInfo& air, size_t n, CheckView* V) {
     const AirProgram& P = air.prog;
-    if (int rc = check_trace_shape(air, in.n_rows, pis, &V->log_n)) return rc;
-    const size_t n = in.n_rows, C = P.n_cols;
-    if (in.n_cols != C) return STARKHIP_ERR_BAD_SHAPE;
-    HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->st;
     // (n / 64) x chunks waves: enough to fill 256 CUs several times over, at most one chunk per group
     const size_t blocks = (n + 63) / 64;
@@ -47,16 +43,42 @@ static int check_trace_prepare(Ctx* c, const AirInfo& air, const TraceInput& in,
         c->chk.want = want;
         c->chk.chunks = (unsigned)nc;
     }
+    HIPCHK(c->chk.out.ensure(2 * sizeof(unsigned long long)));
+    V->ops = c->chk.ops.as<QOp>();
+    V->n_chunks = c->chk.chunks;
+    V->chunk_op = c->chk.meta.as<uint32_t>();  // chunk_op[n_chunks + 1], chunk_k0[n_chunks]
+    V->chunk_k0 = V->chunk_op + V->n_chunks + 1;
+    return STARKHIP_OK;
+}
+
+// What the stand-alone checkers do before their kernels: the shape checks, the op stream of `air` (check_program), then the trace where
+// prove() would put it -- column-major in `values`, or the caller's own device memory, with the LDE buffer as the upload staging of
+// row-major host rows -- and the public inputs in c->pis; *V is what the kernels read of it.
+static int check_trace_prepare(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, CheckView* V) {
+    const AirProgram& P = air.prog;
+    if (int rc = check_trace_shape(air, in.n_rows, pis, &V->log_n)) return rc;
+    const size_t n = in.n_rows, C = P.n_cols;
+    if (in.n_cols != C) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->st;
+    if (int rc = check_program(c, air, n, V)) return rc;
     if (!in.callers_columns()) HIPCHK(c->values.ensure(C * n * 8));
     if (in.park_words(C)) HIPCHK(c->lde.ensure(in.park_words(C) * 8));  // the staging of row-major host rows
     if (int rc = upload_dense(c, in, c->values.as<gl_t>(), &V->trace)) return rc;
     HIPCHK(c->pis.ensure(std::max<size_t>(1, P.n_pis) * 8));
     if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, st));
-    V->ops = c->chk.ops.as<QOp>();
-    V->n_chunks = c->chk.chunks;
-    V->chunk_op = c->chk.meta.as<uint32_t>();  // chunk_op[n_chunks + 1], chunk_k0[n_chunks]
-    V->chunk_k0 = V->chunk_op + V->n_chunks + 1;
     V->pis = c->pis.as<gl_t>();
+    return STARKHIP_OK;
+}
+
+// the plain check over a view: res = {violations, (constraint << 32 | row) of the lowest violated constraint on its lowest row}, after
+// the next stream_wait
+static int enqueue_check(Ctx* c, const CheckView& V, unsigned long long res[2]) {
+    hipStream_t st = c->st;
+    const unsigned long long init[2] = {0, ~0ull};
+    HIPCHK(hipMemcpyAsync(c->chk.out.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_check_trace(V, c->chk.out.as<unsigned long long>(), st));
+    HIPCHK(read_back(c, res, c->chk.out.p, 2 * sizeof(unsigned long long), st));
     return STARKHIP_OK;
 }
 
@@ -67,12 +89,8 @@ int check_trace(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t
     const gl_t* d_trace = V.trace;
     const size_t n = in.n_rows, C = P.n_cols;
     hipStream_t st = c->st;
-    const unsigned long long init[2] = {0, ~0ull};
     unsigned long long res[2];
-    HIPCHK(c->chk.out.ensure(sizeof init));
-    HIPCHK(hipMemcpyAsync(c->chk.out.p, init, sizeof init, hipMemcpyHostToDevice, st));
-    HIPCHK(launch_check_trace(V, c->chk.out.as<unsigned long long>(), st));
-    HIPCHK(hipMemcpyAsync(res, c->chk.out.p, sizeof res, hipMemcpyDeviceToHost, st));
+    if (int rc = enqueue_check(c, V, res)) return rc;
     HIPCHK(stream_wait(c));
     *violations = res[0];
     first[0] = first[1] = first[2] = 0;
@@ -145,6 +163,34 @@ int check_trace_report(Ctx* c, const AirInfo& air, const TraceInput& in, const u
     if (int rc = check_trace_prepare(c, air, in, pis, &V)) return rc;
     DevicePasses passes(c, air.prog, V);
     return check_report_run(air.prog, in.n_rows, passes, per_constraint, row_mask, list, cap, out);
+}
+
+// "check_trace" inside prove(): the trace is where phase 0 left it (`d_trace`, column-major: parked in the LDE buffer, in `values`, or
+// the caller's own memory), c->pis is allocated, and nothing here touches `values` or `lde`.  The plain kernel with its 16-byte
+// read-back decides; only a violated trace pays for the report's two passes, whose summary and first `cap` entries make the check
+// blob (check_report.h).  STARKHIP_OK, or STARKHIP_ERR_TRACE with *blob.
+int check_trace_in_prove(Ctx* c, const AirInfo& air, const gl_t* d_trace, size_t n_rows, const uint64_t* pis, uint64_t** blob, size_t* words) {
+    const AirProgram& P = air.prog;
+    CheckView V = {};
+    if (!log2_rows(n_rows, &V.log_n)) return STARKHIP_ERR_BAD_SHAPE;
+    if (int rc = check_program(c, air, n_rows, &V)) return rc;
+    if (P.n_pis) HIPCHK(hipMemcpyAsync(c->pis.p, pis, P.n_pis * 8, hipMemcpyHostToDevice, c->st));
+    V.trace = d_trace;
+    V.pis = c->pis.as<gl_t>();
+    unsigned long long res[2] = {0, 0};
+    if (int rc = enqueue_check(c, V, res)) return rc;
+    HIPCHK(stream_wait(c));
+    c->traces_checked++;
+    if (!res[0]) return STARKHIP_OK;
+    c->traces_rejected++;
+    const size_t cap = (size_t)c->opt_check_trace_list;
+    std::vector<uint64_t> list(3 * std::max<size_t>(1, std::min<size_t>(cap, res[0])));
+    starkhip_check_report_t rep = {0, 0, 0, 0};
+    DevicePasses passes(c, P, V);
+    if (int rc = check_report_run(P, n_rows, passes, nullptr, nullptr, list.data(), cap, &rep)) return rc;
+    if (rep.violations != res[0]) return STARKHIP_ERR_HIP;  // the two kernels walk one op stream over one trace
+    *blob = check_blob_make(air.id, n_rows, rep, list.data(), words);
+    return *blob ? STARKHIP_ERR_TRACE : STARKHIP_ERR_OOM;
 }
 
 // What the two free-cell entries walk: compile_free_cells of the op stream check_trace_prepare cached for `air`, on the device, cached

@@ -8,6 +8,7 @@
 
 #include <stdio.h>
 
+#include <atomic>
 #include <memory>
 #include <set>
 #include <system_error>
@@ -129,6 +130,11 @@ struct Ctx {
     long opt_host_commit_leaves = 64; // trace commitments of at most this many leaves (and >= 64 columns) are hashed by host threads (0: never)
     long opt_verify_chunk_mb = 1024;  // device memory one chunk of starkhip_verify_batch may take (verifier_device.cpp)
     double verify_timings[4] = {0};   // the last starkhip_verify_batch: host prelude ms, upload ms, device ms, host CPU seconds
+    // "check_trace": prove() checks the trace it has uploaded against the AIR before the LDE (check_trace_in_prove) and lists up to
+    // "check_trace_list" violations in the blob of a refusal; a pool sets both per job (ctx_set_check_trace).  The counters are read by
+    // other threads (starkhip_pool_check_stats).
+    long opt_check_trace = 0, opt_check_trace_list = 16;
+    std::atomic<uint64_t> traces_checked{0}, traces_rejected{0};
     std::vector<gl_t> host_lde;      // their LDE on the host
     // op-stream program (quotient_impl = 1; kept as the cross-check)
     struct OpProgram {
@@ -200,6 +206,9 @@ hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t c
 int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,
             const gl_t* post_scale);
 int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values);
+// ---- check_trace.hip
+int check_trace_in_prove(Ctx* c, const AirInfo& air, const gl_t* d_trace, size_t n_rows, const uint64_t* pis, uint64_t** blob, size_t* words);
+// ---- ctx.hip
 hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form);
 
 // digest buffer: level 0 (n_leaves nodes) followed by level 1, ... ; offset of level l in nodes

@@ -33,7 +33,8 @@ static bool fake_device() {
 struct Ctx {
     int device = 0;
     HashService* hs = nullptr;
-    bool hash_requested = false, urgent = false;
+    bool hash_requested = false, urgent = false, check_trace = false;
+    std::atomic<uint64_t> traces_checked{0};
     float timings[STARKHIP_N_PHASES] = {0}, ktimings[3] = {0}, htimings[2] = {0};
     double verify_timings[4] = {0};
     std::set<int> blob_airs;
@@ -66,6 +67,8 @@ bool ctx_has_hash_service(Ctx* c) { return c->hs != nullptr; }
 void ctx_hash_request_reset(Ctx* c) { c->hash_requested = false; }
 bool ctx_hash_requested(Ctx* c) { return c->hash_requested; }
 int ctx_set_urgent(Ctx* c, bool urgent) { c->urgent = urgent; return STARKHIP_OK; }
+void ctx_set_check_trace(Ctx* c, bool on, size_t) { c->check_trace = on; }  // the pretended check finds every trace satisfying
+void ctx_check_stats(Ctx* c, uint64_t out[2]) { out[0] = c->traces_checked.load(); out[1] = 0; }
 int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t&, size_t, unsigned proof_blobs, bool) {
     if (proof_blobs && !c->blob_airs.count(air.id)) {  // the fake proofs are tiny; what is exercised is the arena's bookkeeping
         if (blob_arena_add(c, 64 + air.prog.n_pis * 8, proof_blobs) != 0) return STARKHIP_ERR_OOM;
@@ -81,6 +84,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     if (pow_witness == 0xBAD) return STARKHIP_ERR_BAD_SHAPE;                  // a job that fails before its commitment (tests)
     const size_t n_rows = in.n_rows;
     std::this_thread::sleep_for(std::chrono::milliseconds(air.cols > 50000 ? 3 : 1));  // "upload + LDE"
+    if (c->check_trace) c->traces_checked++;
     unsigned log_n = 0;
     while (((size_t)1 << log_n) < n_rows) log_n++;
     if (c->hs) {

@@ -59,6 +59,8 @@ struct Pool {
     bool verify_proofs = false;   // under mu
     size_t verify_arena_mb = 1024;  // under mu
     unsigned long verified_proofs = 0, verify_jobs = 0;  // under mu
+    bool check_traces = false;    // under mu
+    size_t check_trace_list = 16; // under mu
     double vload = 0;       // sum of air_verify_cost over the verify jobs that are not done (under mu)
     std::map<int, int> idle_big, idle_small;                 // idle contexts by the AIR they proved last (under mu)
     unsigned stream_priority = 0;
@@ -225,6 +227,7 @@ struct Pool {
         if (announce) hs->announce_small();
         ctx_hash_request_reset(c);
         const uint64_t cpu0 = thread_cpu_ns();
+        ctx_set_check_trace(c, j->check, j->check_list);
         try {
             const AirInfo* a = air_get(j->air);
             rc = prove(c, *a, j->cfg, j->in, j->pis, j->n_pis, j->pow, &j->proof, &j->words);
@@ -302,6 +305,7 @@ struct Pool {
             if (big && stream_priority == 1) (void)ctx_set_urgent(c, urgent);
             int rc = prove_job(c, j, big, announce_big);
             // "verify_proofs": the context is free already; the job waits for its verdict on the host blob the caller will receive
+            // (a trace its context refused -- STARKHIP_ERR_TRACE, j->proof its check blob -- never gets there)
             if (rc == STARKHIP_OK && j->verify) {
                 {
                     std::lock_guard<std::mutex> g(mu);
@@ -433,6 +437,8 @@ static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     j->id = p->next_id++;
     j->info.t_submit = p->now();
     j->verify = p->verify_proofs;
+    j->check = p->check_traces;
+    j->check_list = p->check_trace_list;
     j->cost = air_cost(j->air);
     p->load += j->cost;
     if (j->big) p->big_open++;
@@ -498,8 +504,8 @@ int pool_wait(Pool* p, uint64_t ticket, uint64_t** proof, size_t* words, starkhi
     }
     const int rc = j->rc;
     if (info) *info = j->info;
-    // (a verdict has no proof to hand over: j->proof is null)
-    if (rc == STARKHIP_OK && proof && words) {
+    // (a verdict has no proof to hand over: j->proof is null; a refused trace hands over its check blob)
+    if ((rc == STARKHIP_OK || (rc == STARKHIP_ERR_TRACE && j->proof)) && proof && words) {
         *proof = j->proof;
         *words = j->words;
     } else {
@@ -568,6 +574,14 @@ int pool_set_option(Pool* p, const char* name, long value) {
         if (value == 1 && p->warm && !p->vs && !p->vs_closed) return p->make_verifier();  // a warmed pool allocates now, not in its first proof
         return STARKHIP_OK;
     }
+    if (strcmp(name, "check_traces") == 0 || strcmp(name, "check_trace_list") == 0) {  // read at submit, like "verify_proofs"
+        const bool list = strcmp(name, "check_trace_list") == 0;
+        if (value < 0 || value > (list ? (long)STARKHIP_CHECK_LIST_MAX : 1)) return STARKHIP_ERR_BAD_SHAPE;
+        std::lock_guard<std::mutex> g(p->mu);
+        if (list) p->check_trace_list = (size_t)value;
+        else p->check_traces = value == 1;
+        return STARKHIP_OK;
+    }
     if (strcmp(name, "verify_arena_mb") == 0) {
         if (value < 1 || value > (1l << 20)) return STARKHIP_ERR_BAD_SHAPE;
         std::lock_guard<std::mutex> g(p->vs_mu);
@@ -631,5 +645,16 @@ int pool_verify_stats(Pool* p, starkhip_pool_verify_stats_t* out) {
     return STARKHIP_OK;
 }
 
-}  // namespace starkhip
+int pool_check_stats(Pool* p, uint64_t out[2]) {
+    out[0] = out[1] = 0;
+    for (const std::vector<Ctx*>* ctxs : {&p->big_ctx, &p->small_ctx})
+        for (Ctx* c : *ctxs) {
+            uint64_t one[2];
+            ctx_check_stats(c, one);
+            out[0] += one[0];
+            out[1] += one[1];
+        }
+    return STARKHIP_OK;
+}
 
+}  // namespace starkhip

@@ -30,6 +30,8 @@ struct Job {
     bool big = false;
     double cost = 0;  // relative proving cost (air_cost): what the job adds to its pool's load until it is done
     bool verify = false;  // "verify_proofs" was on when it was submitted: the pool's verifier checks the proof before wait returns it
+    bool check = false;   // "check_traces" was on when it was submitted: its context checks the trace against the AIR before the LDE ...
+    size_t check_list = 16;  // ... and a refusal's check blob lists this many violations ("check_trace_list" at submit)
     // result
     JobState state = JobState::Queued;
     int rc = STARKHIP_OK;

@@ -21,6 +21,9 @@ class HashService;  // scheduler.h
 void ctx_attach_hash_service(Ctx* c, HashService* hs);  // trace commitments of this context go through the pool's scheduler
 bool ctx_has_hash_service(Ctx* c);
 int ctx_set_urgent(Ctx* c, bool urgent);
+// "check_trace" and "check_trace_list" of the context's next proofs, as a pool sets them per job; {traces checked, traces rejected} so far
+void ctx_set_check_trace(Ctx* c, bool on, size_t list_cap);
+void ctx_check_stats(Ctx* c, uint64_t out[2]);
 // tables, plan, work buffers, upload staging and `proof_blobs` page-locked proof blobs (blob_arena.h) for proofs of `air`,
 // allocated now (a pool's warm-up)
 int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t log_bytes, unsigned proof_blobs = 0, bool device_traces = false);
@@ -39,6 +42,7 @@ int pool_host_info(Pool* p, starkhip_pool_host_info_t* out);
 int pool_set_option(Pool* p, const char* name, long value);
 int pool_submit_verify(Pool* p, int air, const starkhip_config_t* cfg, const uint64_t* proof, size_t words, uint64_t* ticket);
 int pool_verify_stats(Pool* p, starkhip_pool_verify_stats_t* out);
+int pool_check_stats(Pool* p, uint64_t out[2]);
 double air_verify_cost(int air);
 unsigned cpu_budget();  // multipool.cpp: CPUs this process may really use
 void host_cpu_seconds(double out[3]);

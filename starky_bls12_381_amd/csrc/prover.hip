@@ -190,7 +190,8 @@ struct ProveCall {
     std::vector<gl2_t> op_local, op_next, op_q, final_poly;
     gl_t alphas[2] = {0, 0};
     gl2_t zeta = gl2_zero();
-    uint64_t* out = nullptr;  // the proof blob, from queries() on
+    uint64_t* out = nullptr;  // the proof blob, from queries() on -- or the check blob of a trace that upload() refused
+    size_t check_words = 0;   // ... and that blob's length
     int upload(), ifft_lde(), trace_merkle(), quotient(), quotient_commit(), openings(), fri_combine(), fri_commit(), pow(), queries();
     int upload_recording(const TraceLog* log), upload_column_table(const uint64_t* const* cols), leaf_hash_on_host();
     int run_quotient_tiles(unsigned debug_mode, gl_t* qvals_out, bool timed), run_quotient_ops(), compare_quotient_evaluators();
@@ -256,11 +257,16 @@ int ProveCall::upload_column_table(const uint64_t* const* cols) {
 }
 
 int ProveCall::upload() {
+    int rc;
     switch (in.form) {
-        case TraceForm::Recording: return upload_recording(in.log);
-        case TraceForm::ColumnTable: return upload_column_table(in.columns);
-        default: return upload_dense(c, in, d_trace, &d_values);
+        case TraceForm::Recording: rc = upload_recording(in.log); break;
+        case TraceForm::ColumnTable: rc = upload_column_table(in.columns); break;
+        default: rc = upload_dense(c, in, d_trace, &d_values);
     }
+    // "check_trace": every constraint on every row of the trace where the upload has just put it, before anything of the LDE is
+    // enqueued; a violating trace ends the proof here with STARKHIP_ERR_TRACE and its check blob in `out`
+    if (rc == 0 && c->opt_check_trace) rc = check_trace_in_prove(c, air, d_values, s.n, pis_host, &out, &check_words);
+    return rc;
 }
 
 // ---- phase 1: IFFT + LDE (PolynomialBatch::from_values, App. A.3)
@@ -732,7 +738,13 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     for (const auto& ph : PHASES) {
         HIPCHK(hipEventRecord(c->ev[evi++], st));
         ranges.next(ph.range);
-        if (int rc = (p.*ph.run)()) return rc;
+        if (int rc = (p.*ph.run)()) {
+            if (rc == STARKHIP_ERR_TRACE) {  // the check blob instead of a proof
+                *proof_out = p.out;
+                *proof_words = p.check_words;
+            }
+            return rc;
+        }
     }
     uint64_t* const out = p.out;
     if (hipEventRecord(c->ev[evi++], st) != hipSuccess || stream_wait(c) != hipSuccess) {

@@ -16,7 +16,16 @@ them to OUT_DIR/free_cells_final_exp.json and OUT_DIR/free_cells_builtin_airs.js
 the read-back of the three planes, beside the plain check and the free-cell audit timed in the same session; one warm-up call, best
 and median of five.  Then classifies one real trace of each built-in AIR and records the four class totals, the columns holding
 silent cells, the wholly unread columns and the constraints that were never open, each list as runs of indices ("3,7-9").  Prints the two results as
-JSON lines and, with OUT_DIR, writes them to OUT_DIR/free_cell_classes_final_exp.json and OUT_DIR/free_cell_classes_builtin_airs.json."""
+JSON lines and, with OUT_DIR, writes them to OUT_DIR/free_cell_classes_final_exp.json and OUT_DIR/free_cell_classes_builtin_airs.json.
+
+--in-prove [OUT_DIR]: the cost of the context option "check_trace" inside a proof.  One FinalExp proof alone, the trace in column-major
+device memory, the option off and on alternated, five each after a warm-up proof of each: medians, minima and maxima of the call
+time, of the proof's total device time and of its phase [0], which holds the check.  The same with the trace as host rows.  Then the
+refusal of the trace with every cell of row 4000 raised by one.  One JSON line and, with OUT_DIR, OUT_DIR/check_in_prove.json.
+
+--prove-off N: N FinalExp proofs from column-major device memory with every option at its default, after one warm-up proof; prints their
+call times and total device times as one JSON line.  For alternating two builds on one box: --package-root DIR imports
+starky_bls12_381_amd from DIR (another checkout, built) instead of this one."""
 import ctypes as C
 import json
 import os
@@ -24,7 +33,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+PACKAGE_ROOT = sys.argv[sys.argv.index("--package-root") + 1] if "--package-root" in sys.argv[1:-1] else ROOT
+sys.path[:0] = [PACKAGE_ROOT, os.path.join(ROOT, "tests")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402  (before the library: torch's HIP runtime is loaded first, as in bench.py)
@@ -198,7 +208,99 @@ def free_classes_mode(out_dir):
                 f.write("\n")
 
 
+def spread(ts):
+    ts = sorted(ts)
+    return {"median": ts[len(ts) // 2], "min": ts[0], "max": ts[-1]}
+
+
+def final_exp_on_device():
+    t, pis = S.trace_final_exp(fp_arr(*[int(s) for s in native_vectors()["final_exp_input_aa"]]))
+    cols = torch.from_numpy(np.ascontiguousarray(t.T).view(np.int64)).to("cuda:0")
+    torch.cuda.synchronize()
+    return t, pis, cols
+
+
+def in_prove_mode(out_dir):
+    torch.cuda.set_device(0)
+    pv = S.Prover(0)
+    air = S.AIR_FINAL_EXP
+    cfg = S.StarkConfig.for_air(air)
+    t, pis, cols = final_exp_on_device()
+    n = t.shape[0]
+    out = {"times": "ms; call = wall time of the C call, total and phase0 = starkhip_last_timings [10] and [0]", "proofs_each": 5}
+
+    def alternate(prove):
+        runs = {0: {"call": [], "total": [], "phase0": []}, 1: {"call": [], "total": [], "phase0": []}}
+        for on in (0, 1):  # warm-up: buffers, plan, the check program
+            pv.set_option("check_trace", on)
+            prove()
+        for _ in range(5):
+            for on in (0, 1):
+                pv.set_option("check_trace", on)
+                prove()
+                runs[on]["call"].append(pv.last_call_s * 1e3)
+                ms = pv.last_timings()
+                runs[on]["total"].append(ms["total"])
+                runs[on]["phase0"].append(ms["upload"])
+        res = {("on" if on else "off"): {k: spread(v) for k, v in r.items()} for on, r in runs.items()}
+        res["on_minus_off_median_ms"] = {k: res["on"][k]["median"] - res["off"][k]["median"] for k in ("call", "total", "phase0")}
+        return res
+
+    out["device_colmajor"] = alternate(lambda: pv.prove_device(air, cfg, cols.data_ptr(), n, pis, layout=1, keep=False))
+    out["host_rows"] = alternate(lambda: pv.prove(air, cfg, t, pis))
+    stats = pv.check_stats()
+    assert stats == {"checked": 12, "rejected": 0}, stats
+    p_minus_1 = int(np.array([S.P - 1], dtype=np.uint64).view(np.int64)[0])
+    row = cols[:, 4000]
+    cols[:, 4000] = torch.where(row == p_minus_1, torch.zeros_like(row), row + 1)
+    torch.cuda.synchronize()
+    pv.set_option("check_trace", 1)
+    ts, rep = [], None
+    for _ in range(3):
+        t0 = time.perf_counter()
+        try:
+            pv.prove_device(air, cfg, cols.data_ptr(), n, pis, layout=1, keep=False)
+            raise SystemExit("the corrupted trace was proven")
+        except S.TraceViolation as e:
+            rep = e.report
+        ts.append((time.perf_counter() - t0) * 1e3)
+    out["refusal_row_4000_corrupted_call_ms"] = spread(ts)
+    out["refusal_row_4000_corrupted"] = {"violations": rep.violations, "constraints_violated": rep.constraints_violated,
+                                         "rows_violated": rep.rows_violated, "listed": len(rep.list)}
+    pv.close()
+    print(json.dumps(out))
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "check_in_prove.json"), "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+def prove_off_mode(reps):
+    torch.cuda.set_device(0)
+    pv = S.Prover(0)
+    air = S.AIR_FINAL_EXP
+    cfg = S.StarkConfig.for_air(air)
+    t, pis, cols = final_exp_on_device()
+    n = t.shape[0]
+    del t
+    pv.prove_device(air, cfg, cols.data_ptr(), n, pis, layout=1, keep=False)
+    call, total = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        pv.prove_device(air, cfg, cols.data_ptr(), n, pis, layout=1, keep=False)
+        call.append((time.perf_counter() - t0) * 1e3)  # (the wall time of the Python call: the parent's binding keeps no call time here)
+        total.append(pv.last_timings()["total"])
+    pv.close()
+    print(json.dumps({"library": S.LIB_PATH, "call_ms": call, "total_ms": total}))
+
+
 def main():
+    if "--in-prove" in sys.argv[1:]:
+        rest = sys.argv[sys.argv.index("--in-prove") + 1:]
+        return in_prove_mode(rest[0] if rest else None)
+    if "--prove-off" in sys.argv[1:]:
+        return prove_off_mode(int(sys.argv[sys.argv.index("--prove-off") + 1]))
     if "--report" in sys.argv[1:]:
         return report_mode()
     if "--free-classes" in sys.argv[1:]:
