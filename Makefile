@@ -65,6 +65,14 @@ asan-pool-test: tests/tsan_pool_main.cpp $(ASAN_SRCS) $(HDRS)
 	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_pool tests/tsan_pool_main.cpp $(ASAN_SRCS) -lpthread
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_pool
 
+# the grouped lane-form launch of the commitment scheduler (eight big contexts, groups of 2 .. 4, a member that fails) under both
+lane-group-test: tests/lane_group_pool_main.cpp $(ASAN_SRCS) $(HDRS)
+	@mkdir -p build/tsan build/asan
+	g++ -O1 -g -std=c++17 -fsanitize=thread -fno-omit-frame-pointer -Iinclude -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o build/tsan/lane_group_pool tests/lane_group_pool_main.cpp $(ASAN_SRCS) -lpthread
+	TSAN_OPTIONS=halt_on_error=1 build/tsan/lane_group_pool
+	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/lane_group_pool tests/lane_group_pool_main.cpp $(ASAN_SRCS) -lpthread
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/lane_group_pool
+
 # Experiment builds of the device code for A/B runs on one box: `make variant NAME=x DEFS="-D..."` -> build/x/libstarkhip_x.so, selected
 # at run time with STARKHIP_LIBRARY=build/x/libstarkhip_x.so (e.g. NAME=nomfma DEFS=-DSTARKHIP_LANE_NO_MFMA: the lane-form leaf hash with every
 # round as multiply-add chains; NAME=noprio DEFS=-DSTARKHIP_NO_PRIO: no raised issue priority for the kernels beside the lane-form hash)
@@ -80,4 +88,4 @@ build/$(NAME)/libstarkhip_$(NAME).so: $(VAR_OBJS) $(filter %.cpp.o,$(OBJS))
 clean:
 	rm -rf build $(OUT)
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test variant
+.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test variant

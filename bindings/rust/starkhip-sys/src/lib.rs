@@ -295,6 +295,7 @@ extern "C" {
     pub fn starkhip_multipool_wait(mpool: *mut c_void, ticket: u64, proof: *mut *mut u64, proof_words: *mut usize,
                                    info: *mut starkhip_ticket_info_t) -> c_int;
     pub fn starkhip_hw_queues_status() -> c_int;
+    pub fn starkhip_hw_queues_in_effect() -> c_int;
     pub fn starkhip_pool_set_option(pool: *mut c_void, name: *const c_char, value: c_long) -> c_int;
     pub fn starkhip_pool_submit_verify(pool: *mut c_void, air: Air, cfg: *const starkhip_config_t, proof: *const u64, proof_words: usize,
                                        ticket: *mut u64) -> c_int;

@@ -395,7 +395,7 @@ int starkhip_prove_compact(void* ctx, starkhip_air_t air, const starkhip_config_
  * stay the caller's and must stay valid until the ticket has been waited for; submit_witness copies its operands.
  * Hardware queues: starkhip_pool_create sets GPU_MAX_HW_QUEUES=16 unless the variable exists, but the HIP runtime reads it only when
  * the process first uses HIP -- a process that has used HIP before it creates its first pool exports the variable itself, earlier
- * (with HIP's default of 4 queues the same pool is 6 % slower: INTEGRATION.md). */
+ * (what four queues cost; starkhip_hw_queues_in_effect: what the process has). */
 typedef struct {
     int device;
     unsigned big_contexts;      /* 0 = default (3).  Five or more: the trace commitments of these proofs go out in groups of up to four in the
@@ -430,6 +430,7 @@ typedef struct {
 } starkhip_ticket_info_t;
 typedef struct {
     unsigned long big_commit_launches, small_commit_launches, small_commit_requests, max_merged_commitments;
+    unsigned long big_commit_grids; /* kernel launches behind big_commit_launches (which counts commitments): a lane-form group is ONE grid */
 } starkhip_pool_stats_t;
 int starkhip_pool_create(const starkhip_pool_config_t* cfg, void** pool);
 void starkhip_pool_destroy(void* pool); /* runs what is queued to the end first */
@@ -473,6 +474,8 @@ typedef struct {
     unsigned pools_on_device; /* pools of the same multi-device handle on this pool's device: 1, unless the handle was given one ordinal
                                * several times -- the rehearsal of N devices on one card (the tests do it); such a handle's figures are not a
                                * measurement of N devices, and starkhip_multipool_create says so once on stderr */
+    unsigned hw_queues;       /* starkhip_hw_queues_in_effect: hardware queues per stream priority class of this process */
+    unsigned stream_budget;   /* default-class streams this pool can have busy at once (at most 16); above hw_queues its contexts share queues */
 } starkhip_pool_host_info_t;
 int starkhip_pool_host_info(void* pool, starkhip_pool_host_info_t* out);
 unsigned starkhip_cpu_budget(void);
@@ -489,8 +492,16 @@ void starkhip_proof_blob_stats(uint64_t out[5]);
 
 /* 0: GPU_MAX_HW_QUEUES was in the environment before the HIP runtime came up (the library's 16 or the caller's own value); 1: the
  * runtime was already initialised when the first pool / multi-device handle of this process set it, so the pools run on HIP's default
- * of 4 hardware queues (a line on stderr says so once).  Detected without touching HIP (the runtime's open /dev/kfd). */
+ * of 4 hardware queues (a line on stderr says so once).  Detected without touching HIP (the runtime's open /dev/kfd).
+ * 0 says WHEN the variable was set, not that its value is enough: starkhip_hw_queues_in_effect is the number of hardware queues per
+ * stream priority class the process really has -- the variable's value when it was in the environment before the runtime came up (the
+ * caller's own value is respected, never overridden), 4 when it came late; 0 before the first pool of the process.  A pool whose
+ * default-class streams outnumber it (a stream per context and one per merged window: 10 for eight big contexts and a small one) shares
+ * queues among its contexts, and starkhip_pool_create says so once on stderr.  The pool's launches that last hundreds of milliseconds
+ * (lane-form groups, the lone pair-form commitment) run in a priority class of their own and hold none of those queues, so four are
+ * enough for them. */
 int starkhip_hw_queues_status(void);
+int starkhip_hw_queues_in_effect(void);
 
 /* --- verification inside a pool ----------------------------------------------------------------------------------
  * The reference's drivers call verify_stark_proof straight after prove (src/aggregate_proof.rs:67,113,146,177).  A pool does the same on its
@@ -630,6 +641,13 @@ int starkhip_field_ops_batch(void* ctx, int op, const uint64_t* a, const uint64_
  * capacity-only last round, which specifies words 8 .. 11 (pair: 2 .. 5 and 8 .. 11) -- the other words come back unchanged.  Canonical
  * words out.  STARKHIP_ERR_BAD_SHAPE for a form or variant that does not exist, before any device work. */
 int starkhip_poseidon_permute_batch_form(void* ctx, int form, int variant, uint64_t* states, size_t n_states);
+/* the lane-form leaf hash under test, as a proof pool launches it: n_segments (1 .. 4) coset-major matrices of one shape, each [n_cols][N],
+ * N = 2^(log_n + rate_bits) leaves, one after the other in `mats`; grouped != 0: ONE grid over all of them (grid.y = matrix, the pool's
+ * lane-form group), grouped == 0: the per-commitment launch, one per matrix.  digests_out: n_segments x N x 4 words, leaf digests in
+ * tree order.  STARKHIP_ERR_BAD_SHAPE, before any device work, for no or more than four segments, no columns, or more than 2^20 leaves
+ * (a leaf count is a power of two by construction: the tree order is a bit reversal). */
+int starkhip_leaf_hash_lane_group(void* ctx, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped,
+                                  uint64_t* digests_out);
 /* CPU check (no GPU needed) of the constant tables the leaf-hash kernels use for their merged partial rounds -- three at a time in the
  * quad form, four at a time in the lane and pair forms: replays both formulations on n_states inputs against the plain permutation;
  * returns the number of mismatches (0 = good), -1 if a sum of the four-round merge would not fit its 64-bit accumulator */

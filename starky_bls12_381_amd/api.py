@@ -93,6 +93,7 @@ lib.starkhip_lde_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_
 lib.starkhip_merkle_cap.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_uint, _u64p]
 lib.starkhip_poseidon_permute_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t]
 lib.starkhip_poseidon_permute_batch_form.argtypes = [C.c_void_p, C.c_int, C.c_int, _u64p, C.c_size_t]
+lib.starkhip_leaf_hash_lane_group.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _u64p]
 lib.starkhip_field_ops_batch.argtypes = [C.c_void_p, C.c_int, _u64p, _u64p, _u64p, C.c_size_t]
 lib.starkhip_poseidon_permute_host.argtypes = [_u64p]
 lib.starkhip_poseidon_permute_host.restype = None
@@ -1001,6 +1002,17 @@ class Prover:
         _chk(lib.starkhip_field_ops_batch(self._ctx, op, _p64(a), _p64(b), _p64(out), a.size))
         return out
 
+    def leaf_hash_lane_group(self, mats, log_n, rate_bits=0, grouped=True):
+        """Leaf digests (segments x leaves x 4, tree order) of `mats` (segments x columns x leaves, coset-major) in the lane form of the leaf
+        hash: as ONE grid over all segments (grouped, what a proof pool launches for a group) or one launch per segment."""
+        m = np.ascontiguousarray(mats, dtype=np.uint64)
+        assert m.ndim == 3
+        out = np.zeros((m.shape[0], m.shape[2], 4), dtype=np.uint64)
+        if m.shape[2] != 1 << (log_n + rate_bits):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        _chk(lib.starkhip_leaf_hash_lane_group(self._ctx, _p64(m), m.shape[0], m.shape[1], log_n, rate_bits, 1 if grouped else 0, _p64(out)))
+        return out
+
     def poseidon_permute_batch(self, states, form=0, variant=0):
         """The permutation of every row of `states` (n x 12).  form: 0 the generic device loop, 1 .. 4 the quad, row, lane and pair forms of
         the leaf hash, each through the function its leaf kernel calls; variant 1 (quad, lane, pair): the form with the capacity-only last
@@ -1043,7 +1055,7 @@ class TicketInfo(C.Structure):
 
 
 class PoolStats(C.Structure):
-    _fields_ = [(n, C.c_ulong) for n in ("big_commit_launches", "small_commit_launches", "small_commit_requests", "max_merged_commitments")]
+    _fields_ = [(n, C.c_ulong) for n in ("big_commit_launches", "small_commit_launches", "small_commit_requests", "max_merged_commitments", "big_commit_grids")]
 
 
 lib.starkhip_pool_create.argtypes = [C.POINTER(PoolConfig), C.POINTER(C.c_void_p)]
@@ -1102,6 +1114,7 @@ lib.starkhip_plan_verify.argtypes = [C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
 lib.starkhip_air_verify_cost.argtypes = [C.c_int]
 lib.starkhip_air_verify_cost.restype = C.c_double
 lib.starkhip_hw_queues_status.argtypes = []
+lib.starkhip_hw_queues_in_effect.argtypes = []
 
 
 def plan_lpt(airs, n_pools):
@@ -1121,8 +1134,15 @@ def hw_queues_late():
     return bool(lib.starkhip_hw_queues_status())
 
 
+def hw_queues_in_effect():
+    """Hardware queues per stream priority class this process really has (starkhip_hw_queues_in_effect): GPU_MAX_HW_QUEUES as it was in the
+    environment before the HIP runtime came up, 4 when it came late; 0 before the first pool of the process."""
+    return int(lib.starkhip_hw_queues_in_effect())
+
+
 class PoolHostInfo(C.Structure):
-    _fields_ = [(n, C.c_uint) for n in ("cpu_budget", "generator_threads", "trace_threads_big", "trace_threads_small", "prover_threads")] + [("device", C.c_int), ("pools_on_device", C.c_uint)]
+    _fields_ = [(n, C.c_uint) for n in ("cpu_budget", "generator_threads", "trace_threads_big", "trace_threads_small", "prover_threads")] + [("device", C.c_int), ("pools_on_device", C.c_uint)] + \
+               [("hw_queues", C.c_uint), ("stream_budget", C.c_uint)]
 
 
 lib.starkhip_pool_host_info.argtypes = [C.c_void_p, C.POINTER(PoolHostInfo)]

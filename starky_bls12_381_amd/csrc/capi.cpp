@@ -572,7 +572,9 @@ int starkhip_prove_compact(void* ctx, starkhip_air_t air, const starkhip_config_
 // driver's device node, /dev/kfd.  0 = the variable was in the environment before the runtime came up (ours or the caller's own);
 // 1 = the runtime was already up when the first pool set it: the pools run on HIP's default, and the caller should export the variable
 // itself, earlier (bench.py does).
-static std::atomic<int> g_hw_queues_late(-1);
+// The value IN EFFECT (starkhip_hw_queues_in_effect): the variable's when it was there before the runtime came up -- a caller's own value
+// is respected, whatever it is --, HIP's default of 4 when it came late.
+static std::atomic<int> g_hw_queues_late(-1), g_hw_queues_in_effect(0);
 static bool hip_runtime_is_up() {
     DIR* d = opendir("/proc/self/fd");  // every descriptor, whatever its number (a server may hold thousands)
     if (!d) return false;
@@ -599,14 +601,26 @@ static void ask_for_hw_queues() {
         if (!getenv("GPU_MAX_HW_QUEUES")) {
             late = hip_runtime_is_up() ? 1 : 0;
             setenv("GPU_MAX_HW_QUEUES", "16", 0);
-            if (late)
-                fprintf(stderr, "starkhip: the HIP runtime was initialised before the first pool could set GPU_MAX_HW_QUEUES=16; pools run on HIP's "
-                                "default of 4 hardware queues (about 6 %% slower). Export GPU_MAX_HW_QUEUES=16 before the process first uses HIP.\n");
         }
+        const int asked = atoi(getenv("GPU_MAX_HW_QUEUES"));
+        g_hw_queues_in_effect.store(late || asked <= 0 ? 4 : asked);
         g_hw_queues_late.store(late);
     });
 }
+// Once per process, by the first pool whose default-class streams outnumber the queues: its contexts share hardware queues.
+static void hint_hw_queues(unsigned budget) {
+    const int have = g_hw_queues_in_effect.load();
+    static std::atomic<bool> said(false);
+    if (have <= 0 || (unsigned)have >= budget || said.exchange(true)) return;
+    fprintf(stderr, "starkhip: this process has %d hardware queues per stream priority class (%s) and the pool keeps %u streams busy: contexts "
+                    "share queues, and a kernel waits for the kernels enqueued before it on its queue (the pool's long launches hold none of "
+                    "them; eight FinalExp contexts measured about 1 %% slower on 4 queues than on 16). To give every context a queue, export "
+                    "GPU_MAX_HW_QUEUES=16 before the process first uses HIP.\n",
+            have, g_hw_queues_late.load() == 1 ? "the HIP runtime was initialised before the first pool could set GPU_MAX_HW_QUEUES" : "GPU_MAX_HW_QUEUES in the environment",
+            budget);
+}
 int starkhip_hw_queues_status(void) { return std::max(0, g_hw_queues_late.load()); }
+int starkhip_hw_queues_in_effect(void) { return g_hw_queues_in_effect.load(); }
 
 int starkhip_pool_create(const starkhip_pool_config_t* cfg, void** pool) {
     if (!cfg || !pool) return STARKHIP_ERR_BAD_SHAPE;
@@ -616,6 +630,8 @@ int starkhip_pool_create(const starkhip_pool_config_t* cfg, void** pool) {
     try {
         const int rc = pool_create(*cfg, &p);
         *pool = p;
+        starkhip_pool_host_info_t hi;
+        if (rc == STARKHIP_OK && pool_host_info(p, &hi) == STARKHIP_OK) hint_hw_queues(hi.stream_budget);
         return rc;
     } catch (const std::bad_alloc&) {
         return STARKHIP_ERR_OOM;
@@ -708,6 +724,8 @@ int starkhip_multipool_create(const int* devices, size_t n_devices, const starkh
     try {
         const int rc = multipool_create(devices, n_devices, *cfg, &mp);
         *mpool = mp;
+        starkhip_pool_host_info_t hi;
+        if (rc == STARKHIP_OK && multipool_size(mp) && pool_host_info(multipool_pool(mp, 0), &hi) == STARKHIP_OK) hint_hw_queues(hi.stream_budget);
         return rc;
     } catch (const std::bad_alloc&) {
         return STARKHIP_ERR_OOM;
@@ -862,6 +880,11 @@ int starkhip_poseidon_permute_batch(void* ctx, uint64_t* states, size_t n_states
 int starkhip_poseidon_permute_batch_form(void* ctx, int form, int variant, uint64_t* states, size_t n_states) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     return permute_batch_form((Ctx*)ctx, form, variant, states, n_states);
+}
+int starkhip_leaf_hash_lane_group(void* ctx, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped,
+                                  uint64_t* digests_out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    return leaf_hash_lane_group((Ctx*)ctx, mats, n_segments, n_cols, log_n, rate_bits, grouped, digests_out);
 }
 int starkhip_field_ops_batch(void* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;

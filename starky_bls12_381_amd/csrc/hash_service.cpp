@@ -107,11 +107,45 @@ void HashService::drain(std::vector<hipEvent_t>& evs) {
     evs.clear();
 }
 
+// The stream of the long launches (scheduler.h: the stream budget): the lowest priority class, whose hardware queues no stream of the
+// default class shares.  Two of them, so that a group does not wait in stream order for the tail of the one before; an urgent
+// commitment (pools with stream_priority 1 only) takes the high-priority stream, made when the first one comes.
+hipStream_t HashService::pick_long_stream(bool urgent, hipError_t* err) {
+    *err = hipSuccess;
+    int least = 0, greatest = 0;
+    if (urgent) {
+        if (!st_high_ && (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
+                          hipStreamCreateWithPriority(&st_high_, hipStreamNonBlocking, greatest) != hipSuccess))
+            st_high_ = nullptr;
+        if (st_high_) return st_high_;
+    }
+    for (int k = 0; k < N_LONG_STREAMS; k++) {
+        hipStream_t& s = long_st_[(next_long_st_ + k) % N_LONG_STREAMS];
+        bool idle = false;
+        if (!s) {
+            *err = hipDeviceGetStreamPriorityRange(&least, &greatest);
+            if (*err == hipSuccess) *err = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least);
+            if (*err != hipSuccess) return s = nullptr;
+            idle = true;
+        } else {
+            idle = hipStreamQuery(s) == hipSuccess;
+            (void)hipGetLastError();  // hipErrorNotReady from a query is not an error
+        }
+        if (idle) {
+            next_long_st_ = (next_long_st_ + k + 1) % N_LONG_STREAMS;
+            return s;
+        }
+    }
+    hipStream_t s = long_st_[next_long_st_];
+    next_long_st_ = (next_long_st_ + 1) % N_LONG_STREAMS;
+    return s;
+}
+
 void HashService::launch_big(Req* r, bool lane, unsigned group) {
-    hipStream_t s = (r->urgent && st_high_) ? st_high_ : st_;
     const LeafHashForm form = lane ? FORM_LANE : FORM_PAIR;
     hipError_t e = hipSuccess;
-    if (lane) s = pick_small_stream(&e);  // lane-form grids are a quarter of the chip each: they must overlap, not queue in one stream
+    // lane-form grids launched one by one (STARKHIP_POOL_LANE_GROUPED=0) are a quarter of the chip each: they must overlap, not queue in one stream
+    hipStream_t s = lane ? pick_small_stream(&e) : pick_long_stream(r->urgent, &e);
     if (e == hipSuccess) e = wait_ready(r);
     if (r->timing) {
         r->timing->form = leaf_hash_sent(form);
@@ -124,6 +158,49 @@ void HashService::launch_big(Req* r, bool lane, unsigned group) {
     if (e == hipSuccess) e = hipEventRecord(r->done, s);
     r->err = e;
     if (e == hipSuccess) track(running_big_, r->done);
+}
+
+// A lane-form group as ONE grid (grid.y = commitment) on one long-launch stream.  A member whose `ready` failed fails alone and is left
+// out; members of another shape than the first's go out in a grid of their own (FinalExp and ECCAgg commitments join the same groups).
+// Returns the number of grids launched.
+unsigned HashService::launch_big_group(std::vector<Req*>& group) {
+    std::vector<Req*> live;
+    for (Req* r : group) {
+        r->err = wait_ready(r);
+        if (r->err == hipSuccess) live.push_back(r);
+    }
+    for (Req* r : live)
+        if (r->timing) {
+            r->timing->form = SENT_LANE;
+            r->timing->group = (unsigned)live.size();
+        }
+    unsigned grids = 0;
+    while (!live.empty()) {
+        std::vector<Req*> same, rest;
+        for (Req* r : live)
+            ((r->n_cols == live[0]->n_cols && r->log_n == live[0]->log_n && r->rate_bits == live[0]->rate_bits && same.size() < LEAF_HASH_MAX_BATCH) ? same : rest).push_back(r);
+        LeafHashBatch B = {};
+        for (size_t i = 0; i < same.size(); i++) {
+            B.mat[i] = same[i]->mat;
+            B.digests[i] = same[i]->digests;
+        }
+        hipError_t e = hipSuccess;
+        hipStream_t s = pick_long_stream(false, &e);
+        for (Req* r : same)
+            if (e == hipSuccess && r->timing && r->timing->t0) e = hipEventRecord(r->timing->t0, s);
+        if (e == hipSuccess) {
+            e = launch_leaf_hash_lane_group(B, (unsigned)same.size(), same[0]->n_cols, same[0]->log_n, same[0]->rate_bits, s);
+            grids += e == hipSuccess;
+        }
+        for (Req* r : same) {
+            if (e == hipSuccess && r->timing && r->timing->t1) e = hipEventRecord(r->timing->t1, s);
+            if (e == hipSuccess) e = hipEventRecord(r->done, s);
+            r->err = e;
+            if (e == hipSuccess) track(running_big_, r->done);
+        }
+        live.swap(rest);
+    }
+    return grids;
 }
 
 // Done events of launches that may still be executing.  Only policy 1 (exclusive classes) ever waits for them, so only policy 1
@@ -219,11 +296,7 @@ double HashService::big_wait_bound() const { return big_expected_ > 0 ? cfg.big_
 void HashService::run() {
     pthread_setname_np(pthread_self(), "starkhip-hash");  // thread names: bench.py attributes host CPU time by them
     (void)hipSetDevice(device_);
-    int least = 0, greatest = 0;
-    if (hipStreamCreateWithFlags(&st_, hipStreamNonBlocking) != hipSuccess) st_ = nullptr;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
-        hipStreamCreateWithPriority(&st_high_, hipStreamNonBlocking, greatest) != hipSuccess)
-        st_high_ = nullptr;
+    // (every stream of the service is made when the first launch needs it: pick_long_stream, pick_small_stream)
     std::unique_lock<std::mutex> lk(mu_);
     while (true) {
         cv_.wait(lk, [&] { return stop_ || !big_.empty() || !small_.empty(); });
@@ -261,10 +334,20 @@ void HashService::run() {
             wait_for.swap(running_small_);
             lk.unlock();
             if (cfg.policy == 1) drain(wait_for);  // exclusive classes: the small window has left the chip
-            for (Req* r : group) launch_big(r, cfg.big_lane && group.size() >= 2, (unsigned)group.size());
+            const bool lane = cfg.big_lane && group.size() >= 2;
+            unsigned grids = 0;
+            if (lane && cfg.lane_grouped) {
+                grids = launch_big_group(group);
+            } else {
+                for (Req* r : group) {
+                    launch_big(r, lane, (unsigned)group.size());
+                    grids += r->err == hipSuccess;
+                }
+            }
             lk.lock();
             for (Req* r : group) r->state = r->err == hipSuccess ? 1 : 2;
             stats_.big_launches += group.size();
+            stats_.big_grids += grids;
             last_was_big_ = true;
             cv_done_.notify_all();
             continue;
@@ -298,7 +381,7 @@ void HashService::run() {
         cv_.wait_until(lk, std::chrono::system_clock::now() + std::chrono::microseconds((long)(std::max(0.1, left_ms) * 1e3)));
     }
     lk.unlock();
-    for (hipStream_t s : {st_, st_high_})
+    for (hipStream_t s : {long_st_[0], long_st_[1], st_high_})
         if (s) {
             (void)hipStreamSynchronize(s);
             (void)hipStreamDestroy(s);

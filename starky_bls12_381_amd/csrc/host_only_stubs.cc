@@ -38,7 +38,12 @@ struct Ctx {
     float timings[STARKHIP_N_PHASES] = {0}, ktimings[3] = {0}, htimings[2] = {0};
     double verify_timings[4] = {0};
     std::set<int> blob_airs;
+    HashService::Timing hash_timing;  // how the scheduler sent the last "commitment" out (no timing events: form and group only)
+    char done_tag = 0;                // its address is this context's `done` event: the scheduler's records of it are counted
 };
+// a `ready` event whose wait fails (pow_witness 0xBAD3: the work before a commitment failed on the device)
+static char g_failing_ready_tag = 0;
+static hipEvent_t failing_ready() { return (hipEvent_t)&g_failing_ready_tag; }
 int ctx_create(int device, Ctx** out, int) {
     if (!fake_device() || device < 0 || device >= 8) {  // the pretended node has eight devices
         *out = nullptr;
@@ -60,7 +65,7 @@ double* ctx_verify_timings(Ctx* c) { return c->verify_timings; }
 int ctx_device(Ctx* c) { return c->device; }
 const float* ctx_kernel_timings(Ctx* c) { return c->ktimings; }
 const float* ctx_host_timings(Ctx* c) { return c->htimings; }
-void ctx_commit_info(Ctx*, int* form, unsigned* group) { *form = SENT_QUAD; *group = 1; }
+void ctx_commit_info(Ctx* c, int* form, unsigned* group) { *form = c->hash_timing.form; *group = c->hash_timing.group; }
 int ctx_set_option(Ctx*, const char*, long) { return STARKHIP_ERR_NO_DEVICE; }
 void ctx_attach_hash_service(Ctx* c, HashService* hs) { c->hs = hs; }
 bool ctx_has_hash_service(Ctx* c) { return c->hs != nullptr; }
@@ -90,7 +95,9 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     if (c->hs) {
         c->hash_requested = true;
         static gl_t dummy[8];
-        if (c->hs->hash(dummy, air.cols, log_n, cfg.rate_bits, dummy, nullptr, nullptr, nullptr, !HashService::is_big(log_n, cfg.rate_bits), c->urgent) != hipSuccess)
+        c->hash_timing = HashService::Timing();
+        if (c->hs->hash(dummy, air.cols, log_n, cfg.rate_bits, dummy, nullptr, pow_witness == 0xBAD3 ? failing_ready() : nullptr, (hipEvent_t)&c->done_tag,
+                        !HashService::is_big(log_n, cfg.rate_bits), c->urgent, &c->hash_timing) != hipSuccess)
             return STARKHIP_ERR_HIP;
     }
     std::this_thread::sleep_for(std::chrono::milliseconds(2));  // "the rest of the proof"
@@ -109,6 +116,7 @@ int ntt_long(Ctx*, uint64_t*, size_t, unsigned, int) { return STARKHIP_ERR_NO_DE
 int merkle_cap(Ctx*, const uint64_t*, size_t, unsigned, unsigned, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int permute_batch(Ctx*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int permute_batch_form(Ctx*, int, int, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
+int leaf_hash_lane_group(Ctx*, const uint64_t*, size_t, size_t, unsigned, unsigned, int, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int expand_log(Ctx*, const TraceLog*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int check_trace(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int check_trace_report(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_check_report_t*) {
@@ -126,14 +134,24 @@ int field_ops(Ctx*, int, const uint64_t*, const uint64_t*, uint64_t*, size_t) { 
 int host_alloc(Ctx*, size_t, void**) { return STARKHIP_ERR_NO_DEVICE; }
 void host_free(void*) {}
 
-hipError_t event_wait_sleeping(hipEvent_t) { return hipSuccess; }  // ctx.hip's sleeping wait: the fake device is always done
+// ctx.hip's sleeping wait: the fake device is always done -- except with the work that the failing `ready` stands for
+hipError_t event_wait_sleeping(hipEvent_t ev) { return ev == failing_ready() ? hipErrorUnknown : hipSuccess; }
 
 // the two launches the commitment scheduler makes
-static std::atomic<unsigned long> g_fake_launches(0), g_fake_merged(0);
+static std::atomic<unsigned long> g_fake_launches(0), g_fake_merged(0), g_fake_lane_grids(0), g_fake_lane_members(0), g_service_records(0);
 hipError_t launch_leaf_hash_form(LeafHashForm, const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { g_fake_launches++; return hipSuccess; }
 hipError_t launch_leaf_hash_multi(const LeafHashBatch&, unsigned count, size_t, unsigned, unsigned, hipStream_t) {
     g_fake_launches++;
     g_fake_merged += count;
+    return hipSuccess;
+}
+hipError_t launch_leaf_hash_lane_group(const LeafHashBatch& B, unsigned count, size_t, unsigned, unsigned, hipStream_t) {
+    if (count == 0 || count > LEAF_HASH_MAX_BATCH) return hipErrorInvalidValue;
+    for (unsigned i = 0; i < count; i++)
+        if (!B.mat[i] || !B.digests[i]) return hipErrorInvalidValue;
+    g_fake_launches++;
+    g_fake_lane_grids++;
+    g_fake_lane_members += count;
     return hipSuccess;
 }
 // the device verifier's launches (verifier_device.cpp, verify_service.cpp): with the pretended device, their routine on the host --
@@ -172,6 +190,12 @@ hipError_t launch_verify_queries(const gl_t* words, const VQProof* proofs, const
 // (starkhip_stub_allocations: the pool's verifier must not allocate after its setup)
 static std::atomic<unsigned long> g_stub_allocs(0);
 extern "C" unsigned long starkhip_stub_allocations(void) { return g_stub_allocs.load(); }
+// what the commitment scheduler has launched and recorded so far: [0] leaf-hash launches of every kind, [1] lane-form group grids, [2] the
+// commitments in them, [3] events recorded on the scheduler's own streams (the members' `done`; the fake proofs have no timing events)
+extern "C" void starkhip_stub_commit_counters(unsigned long out[4]) {
+    out[0] = starkhip::g_fake_launches.load(); out[1] = starkhip::g_fake_lane_grids.load(); out[2] = starkhip::g_fake_lane_members.load();
+    out[3] = starkhip::g_service_records.load();
+}
 extern "C" {
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
@@ -183,7 +207,7 @@ hipError_t hipStreamDestroy(hipStream_t s) { free((void*)s); return hipSuccess; 
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t, hipStream_t s) { if (s) starkhip::g_service_records++; return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) { g_stub_allocs++; *p = malloc(bytes ? bytes : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }

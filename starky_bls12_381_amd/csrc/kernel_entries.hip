@@ -175,6 +175,31 @@ int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n
     return STARKHIP_OK;
 }
 
+// the lane-form leaf hash on 1 .. 4 matrices of one shape: the pool's grouped launch (one grid) or the per-commitment launches
+int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped, uint64_t* digests_out) {
+    if (!mats || !digests_out || n_segments == 0 || n_segments > 4 || n_cols == 0 || log_n + rate_bits > 20 || n_cols > ((size_t)1 << 20)) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t N = (size_t)1 << (log_n + rate_bits), mat_words = n_cols * N, dig_words = 4 * N;
+    HIPCHK(c->staging.ensure(n_segments * (mat_words + dig_words) * 8));
+    gl_t* d_mats = c->staging.as<gl_t>();
+    gl_t* d_dig = d_mats + n_segments * mat_words;
+    HIPCHK(hipMemcpyAsync(d_mats, mats, n_segments * mat_words * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemsetAsync(d_dig, 0xEE, n_segments * dig_words * 8, c->st));  // a digest that is not written does not come back as a field element
+    LeafHashBatch B = {};
+    for (size_t s = 0; s < n_segments; s++) {
+        B.mat[s] = d_mats + s * mat_words;
+        B.digests[s] = d_dig + s * dig_words;
+    }
+    if (grouped) {
+        HIPCHK(launch_leaf_hash_lane_group(B, (unsigned)n_segments, n_cols, log_n, rate_bits, c->st));
+    } else {
+        for (size_t s = 0; s < n_segments; s++) HIPCHK(launch_leaf_hash_form(FORM_LANE, B.mat[s], n_cols, log_n, rate_bits, B.digests[s], c->st));
+    }
+    HIPCHK(hipMemcpyAsync(digests_out, d_dig, n_segments * dig_words * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
 int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(c->staging.ensure(3 * n * 8));

@@ -88,6 +88,8 @@ struct LeafHashBatch {
     gl_t* digests[LEAF_HASH_MAX_BATCH];
 };
 hipError_t launch_leaf_hash_multi(const LeafHashBatch& B, unsigned count, size_t n_cols, unsigned log_n, unsigned rate_bits, hipStream_t st);
+// the same in the lane form (one lane per leaf): the big commitments of a pool's lane group as ONE grid, grid.y = commitment
+hipError_t launch_leaf_hash_lane_group(const LeafHashBatch& B, unsigned count, size_t n_cols, unsigned log_n, unsigned rate_bits, hipStream_t st);
 // The leaf-hash forms in the numbering of the "leaf_hash_form" option and of the test entries (starkhip_poseidon_permute_batch_form,
 // starkhip_hash_table_image).  FORM_AUTO: the option's "the library picks"; as a permutation entry, the generic loop.
 enum LeafHashForm : int {

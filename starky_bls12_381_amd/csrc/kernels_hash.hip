@@ -232,8 +232,12 @@ __global__ __launch_bounds__(256) void verify_leaf_digest_kernel(const gl_t* __r
 // ---- the lane form (poseidon_dev.h): one lane per leaf, for big commitments when several are in flight (the pool picks).
 // Same digests as leaf_hash_kernel.  64 adjacent points of a column per wave: every load is one 512-byte run.
 __constant__ LaneTables LANE_TABLES;
-__global__ __launch_bounds__(256, 2) void leaf_hash_lane_kernel(const gl_t* __restrict__ mat, size_t n_cols, unsigned log_n, unsigned rate_bits,
-                                                              gl_t* __restrict__ digests) {
+// grid.y = commitment (LeafHashBatch, as leaf_hash_multi_kernel): the lane-form group of a proof pool is ONE grid -- four launches on four
+// streams occupy four hardware queues for 350 ms each, and with HIP's default of four queues every other stream of the process then waits
+// behind one of them (tools/experiments/hw_queue_probe.hip).  The segment's two pointers are looked up once, from the kernel arguments.
+__global__ __launch_bounds__(256, 2) void leaf_hash_lane_kernel(LeafHashBatch B, size_t n_cols, unsigned log_n, unsigned rate_bits) {
+    const gl_t* __restrict__ mat = B.mat[blockIdx.y];
+    gl_t* __restrict__ digests = B.digests[blockIdx.y];
     __shared__ LaneTables T;
     {
         const uint32_t* src = (const uint32_t*)&LANE_TABLES;
@@ -572,7 +576,12 @@ hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_co
             break;
         case FORM_LANE:
             if (hipError_t e = ensure_lane_tables(); e != hipSuccess) return e;
-            hipLaunchKernelGGL(leaf_hash_lane_kernel, dim3(nblocks(N, 256)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+            {
+                LeafHashBatch B = {};
+                B.mat[0] = mat;
+                B.digests[0] = digests;
+                hipLaunchKernelGGL(leaf_hash_lane_kernel, dim3(nblocks(N, 256)), dim3(256), 0, st, B, n_cols, log_n, rate_bits);
+            }
             break;
         case FORM_PAIR:
             if (hipError_t e = ensure_pair_tables(); e != hipSuccess) return e;
@@ -594,6 +603,13 @@ hipError_t launch_leaf_hash_multi(const LeafHashBatch& B, unsigned count, size_t
     if (hipError_t e = ensure_quad_merged_tables(); e != hipSuccess) return e;
     if (count == 1) hipLaunchKernelGGL(leaf_hash_kernel, dim3(nblocks(4 * N, 256)), dim3(256), 0, st, B.mat[0], n_cols, log_n, rate_bits, B.digests[0]);
     else hipLaunchKernelGGL(leaf_hash_multi_kernel, dim3(nblocks(4 * N, 256), count), dim3(256), 0, st, B, n_cols, log_n, rate_bits);
+    return hipGetLastError();
+}
+hipError_t launch_leaf_hash_lane_group(const LeafHashBatch& B, unsigned count, size_t n_cols, unsigned log_n, unsigned rate_bits, hipStream_t st) {
+    if (count == 0 || count > LEAF_HASH_MAX_BATCH) return hipErrorInvalidValue;
+    const size_t N = (size_t)1 << (log_n + rate_bits);
+    if (hipError_t e = ensure_lane_tables(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(leaf_hash_lane_kernel, dim3(nblocks(N, 256), count), dim3(256), 0, st, B, n_cols, log_n, rate_bits);
     return hipGetLastError();
 }
 hipError_t launch_leaf_hash_rows(const gl_t* rows, size_t width, size_t n_leaves, gl_t* digests, hipStream_t st) {

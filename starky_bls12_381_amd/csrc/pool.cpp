@@ -357,6 +357,8 @@ int pool_create(const starkhip_pool_config_t& cfg_in, Pool** out, unsigned cpu_s
         if (rl && *rl) hc.row_leaves = (size_t)atol(rl);
         const char* lg = getenv("STARKHIP_POOL_LANE_GROUP");
         if (lg && *lg && atoi(lg) >= 2 && atoi(lg) <= 8) hc.lane_group = (unsigned)atoi(lg);
+        const char* gr = getenv("STARKHIP_POOL_LANE_GROUPED");
+        if (gr && *gr) hc.lane_grouped = *gr != '0';
         const char* bg = getenv("STARKHIP_POOL_BIG_GATHER_MS");
         if (bg && *bg && atof(bg) > 0) hc.big_gather_ms = atof(bg);
     }
@@ -544,6 +546,8 @@ int pool_host_info(Pool* p, starkhip_pool_host_info_t* out) {
     out->prover_threads = (unsigned)(p->big_ctx.size() + p->small_ctx.size());
     out->device = p->device;
     out->pools_on_device = p->pools_on_device;
+    out->hw_queues = (unsigned)std::max(0, starkhip_hw_queues_in_effect());
+    out->stream_budget = pool_stream_budget((unsigned)p->big_ctx.size(), (unsigned)p->small_ctx.size());
     return STARKHIP_OK;
 }
 
@@ -560,6 +564,7 @@ int pool_stats(Pool* p, starkhip_pool_stats_t* out) {
     out->small_commit_launches = s.small_launches;
     out->small_commit_requests = s.small_requests;
     out->max_merged_commitments = s.max_merged;
+    out->big_commit_grids = s.big_grids;
     return STARKHIP_OK;
 }
 int pool_set_option(Pool* p, const char* name, long value) {

@@ -90,6 +90,7 @@ int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, uns
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);
 int permute_batch(Ctx* c, uint64_t* states, size_t n);
 int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n);
+int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped, uint64_t* digests_out);
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor);
 int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms = nullptr);
 int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);

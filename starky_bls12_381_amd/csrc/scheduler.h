@@ -11,6 +11,18 @@
 //    up to 12 167 sequential permutations, 7/8 of the chip idle.  So: commitments of the small class that arrive together are
 //    launched as ONE merged grid (leaf_hash_multi_kernel, grid.y = proof); optionally (policy 1) the two classes never
 //    overlap -- a big commitment then starts when the small window has drained and vice versa.
+//
+// The stream budget.  The HIP runtime carries the streams of a process on GPU_MAX_HW_QUEUES hardware queues PER PRIORITY CLASS (HIP's
+// default, and what a host that has used HIP before the first pool is left with: 4); streams of one class beyond that share queues, and a
+// kernel waits for everything enqueued earlier on ITS QUEUE, whatever the stream (tools/experiments/hw_queue_probe.hip,
+// profiles/hwq_probe_4_queues.txt: one 100 ms kernel holds 2 of 11 other default-class streams, four hold all of them, one on a stream of
+// another priority class holds none).  A pool of eight big contexts has busy at once, by class:
+//    default   8 context streams + its small contexts' streams + one stream per merged small window + the verifier's      (>= 10)
+//    lowest    the long launches -- a lane-form group as ONE grid, the lone pair-form commitment: N_LONG_STREAMS = 2
+//    highest   nothing, unless the pool was made with stream_priority (then: urgent contexts' streams, one urgent commitment stream)
+// The launches that last hundreds of milliseconds are alone in their class: no short kernel of a context can be enqueued behind one.
+// The context streams still share the default class's queues among themselves (POOL_STREAM_BUDGET against the value in effect:
+// starkhip_hw_queues_status), behind kernels of tens of milliseconds at most.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +46,11 @@ inline double now_s() { return std::chrono::duration<double>(std::chrono::steady
 hipError_t event_wait_sleeping(hipEvent_t ev);  // ctx.hip: a few queries, then sleeps of 20 .. 200 microseconds between them
 extern std::atomic<uint64_t> g_wait_cpu_ns;     // ctx.hip: CPU time inside the context threads' waits for the device
 
+// Default-class streams a pool can have busy at once (the header comment): a stream per context and a merged small window; the pool of
+// eight big contexts and one small one that the benchmark runs: 10.  Capped at the 16 queues the library asks for by itself (24 measured
+// slower than 16).  Below it, contexts share hardware queues: starkhip_pool_create says so once on stderr.
+inline unsigned pool_stream_budget(unsigned big_contexts, unsigned small_contexts) { return std::min(16u, big_contexts + small_contexts + 1u); }
+
 class HashService {
   public:
     static bool is_big(unsigned log_n, unsigned rate_bits) { return log_n + rate_bits >= 15; }  // >= 2048 waves: fills every SIMD twice
@@ -52,6 +69,8 @@ class HashService {
         bool big_lane = false;    // big commitments in groups, a group of two or more in the lane form (one lane per leaf): pools with five or
                                   // more big contexts; STARKHIP_POOL_BIG_LANE=0 / 1 overrides
         unsigned lane_group = 4;  // STARKHIP_POOL_LANE_GROUP: commitments per lane-form group (four fill the chip: two waves of 256 registers per SIMD)
+        bool lane_grouped = true; // a lane-form group is ONE grid on a long-launch stream; STARKHIP_POOL_LANE_GROUPED=0: a launch per commitment, each on a
+                                  // default-class stream of its own (what the pool did before; for A/B runs)
         double big_gather_ms = 1000.0;  // lane form: how long a group of big commitments waits at most for proofs that HAVE STARTED to join (a group of three
                                         // wastes a quarter of a 350 ms launch: full groups measured 6.46 against 6.2 - 6.3 proofs/s with a 150 ms bound)
         double big_queued_wait_ms = STARKHIP_QUEUED_WAIT_MS;  // ... and for jobs that have not started (queued, or being recorded) when nobody who has started is on the
@@ -90,6 +109,7 @@ class HashService {
 
     struct Stats {
         unsigned long big_launches = 0, small_launches = 0, small_requests = 0, max_merged = 0;
+        unsigned long big_grids = 0;  // kernel launches behind big_launches (commitments): a lane-form group is one
     };
     Stats stats();
 
@@ -111,12 +131,17 @@ class HashService {
     double big_wait_bound() const;  // under mu_: how long the oldest queued big commitment waits at most for its group to fill
     hipError_t wait_ready(Req* r);  // the service thread, before it launches r's kernel: sleeps until r's caller has seen `ready`
     void launch_big(Req* r, bool lane, unsigned group);
+    unsigned launch_big_group(std::vector<Req*>& group);
     void launch_small(std::vector<Req*>& reqs);
     void drain(std::vector<hipEvent_t>& evs);
     void track(std::vector<hipEvent_t>& evs, hipEvent_t done);
 
     int device_;
-    hipStream_t st_ = nullptr, st_high_ = nullptr;  // big commitments: ordinary / urgent (high-priority stream)
+    // big commitments: the long-launch streams (lowest priority class) / urgent (highest class; made for the first urgent commitment)
+    static const int N_LONG_STREAMS = 2;
+    hipStream_t long_st_[N_LONG_STREAMS] = {}, st_high_ = nullptr;
+    unsigned next_long_st_ = 0;
+    hipStream_t pick_long_stream(bool urgent, hipError_t* err);
     // merged launches run side by side: each goes to a stream that is idle, so a window never queues behind an earlier one
     static const int N_SMALL_STREAMS = 12;
     hipStream_t small_st_[N_SMALL_STREAMS] = {};
