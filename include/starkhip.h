@@ -223,7 +223,8 @@ int starkhip_check_blob_replay(starkhip_air_t air, const uint64_t* trace, size_t
  * trace, n_rows, n_cols, layout, on_device, public_inputs and the BAD_SHAPE cases are starkhip_check_trace's; delta == 0,
  * delta >= p and a NULL `out` are BAD_SHAPE too.  The result is a pure function of the arguments, the same on every run.  One call at
  * a time per context, not beside a prove on it; starkhip_check_trace, the report and their results are unchanged.  On the context's
- * device (csrc/kernels_free_cells.hip) every constraint is re-evaluated once per cell it reads, several times the plain check's work. */
+ * device it is the run of starkhip_check_trace_free_cell_classes below (csrc/kernels_free_classes.hip), whose caught plane,
+ * complemented on the rows of the trace, is free_mask: several times the plain check's work. */
 typedef struct {
     uint64_t cells;                /* n_rows * n_cols */
     uint64_t free_cells;           /* cells no constraint notices */
@@ -260,8 +261,9 @@ int starkhip_check_trace_free_cells_replay(starkhip_air_t air, const uint64_t* t
  * as silent, an open one as gated, for the at most `degree` roots in delta per occurrence).  Arguments, layouts, the BAD_SHAPE cases
  * (delta == 0, delta >= p, a NULL `out`) and "one call at a time per context, not beside a prove" are starkhip_check_trace_free_cells's;
  * cells are read mod p, the trace need not satisfy the AIR, and the result is a pure function of the arguments, the same bytes on
- * every run.  On the context's device (csrc/kernels_free_classes.hip) it is the audit's walks, the body skipped where every gate
- * product of the wave is zero; the other checkers and their results are unchanged. */
+ * every run.  On the context's device (csrc/kernels_free_classes.hip) every constraint is re-evaluated once per cell it reads, the
+ * body skipped where every gate product of the wave is zero, and the audit is this run's caught plane; the other checkers and their
+ * results are unchanged. */
 typedef struct {
     uint64_t cells, caught, silent, gated, unread;  /* caught + silent + gated + unread == cells */
     uint64_t silent_columns;                        /* columns with at least one silent cell */

@@ -107,28 +107,9 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
 }
 
 gl_t air_constraint_value_at(const AirProgram& P, uint32_t group_word, uint32_t term_word, const gl_t* local, const gl_t* next, const gl_t* pis) {
-    auto cell = [&](uint32_t ref) { return gl_from_u64(((ref & REF_NEXT) ? next : local)[ref & REF_COL_MASK]); };  // any word of the class mod p
-    AirReader rd(P, group_word);
-    GroupWord grp;
-    rd.group(&grp);
-    gl_t G = 1;
-    for (uint32_t j = 0; j < grp.n_gates; j++) {
-        const uint32_t ref = rd.ref();
-        G = gl_mul(G, (ref & REF_COMPL) ? gl_sub(1, cell(ref)) : cell(ref));
-    }
-    rd = AirReader(P, term_word);
-    gl_t body = 0;
-    for (;;) {
-        const TermWord tw = rd.term();
-        gl_t u = 1;
-        for (uint32_t f = 0; f < tw.nf; f++) u = gl_mul(u, cell(rd.ref()));
-        if (tw.ck == CK_PLUS) body = gl_add(body, u);
-        else if (tw.ck == CK_MINUS) body = gl_sub(body, u);
-        else if (tw.ck == CK_CONST) body = gl_add(body, gl_mul(u, P.consts[tw.idx]));
-        else if (tw.ck == CK_PI) body = gl_add(body, gl_mul(u, pis[tw.idx]));
-        else body = gl_sub(body, gl_mul(u, pis[tw.idx]));
-        if (tw.last) return gl_mul(G, body);
-    }
+    gl_t G, body;
+    air_constraint_parts_at(P, group_word, term_word, local, next, pis, &G, &body);
+    return gl_mul(G, body);
 }
 
 void air_constraint_parts_at(const AirProgram& P, uint32_t group_word, uint32_t term_word, const gl_t* local, const gl_t* next, const gl_t* pis,

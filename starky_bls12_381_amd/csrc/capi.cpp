@@ -173,7 +173,6 @@ static int checker_args(const AirInfo* a, const TraceInput& in, const uint64_t* 
     return STARKHIP_OK;
 }
 static bool bad_list(const uint64_t* list, size_t cap) { return cap > STARKHIP_CHECK_LIST_MAX || (cap && !list); }
-static bool bad_delta(uint64_t delta) { return delta == 0 || delta >= GL_P; }
 
 int starkhip_check_trace_report(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
                                 const uint64_t* public_inputs, uint32_t* per_constraint, uint64_t* row_mask, uint64_t* list, size_t cap,
@@ -220,7 +219,7 @@ int starkhip_check_trace_free_cells(void* ctx, starkhip_air_t air, const uint64_
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     const AirInfo* a = air_get(air);
     const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
-    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    if (int rc = checker_args(a, in, public_inputs, out, free_cells_bad_delta(delta))) return rc;
     return guarded([&] { return check_trace_free_cells((Ctx*)ctx, *a, in, public_inputs, delta, per_column, free_mask, out); });
 }
 
@@ -229,7 +228,7 @@ int starkhip_check_trace_free_cells_replay(starkhip_air_t air, const uint64_t* t
                                            starkhip_free_cells_t* out) {
     const AirInfo* a = air_get(air);
     const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
-    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    if (int rc = checker_args(a, in, public_inputs, out, free_cells_bad_delta(delta))) return rc;
     return guarded([&] { return check_trace_free_cells_replay(*a, in, public_inputs, delta, per_column, free_mask, out); });
 }
 
@@ -239,7 +238,7 @@ int starkhip_check_trace_free_cell_classes(void* ctx, starkhip_air_t air, const 
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
     const AirInfo* a = air_get(air);
     const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
-    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    if (int rc = checker_args(a, in, public_inputs, out, free_cells_bad_delta(delta))) return rc;
     return guarded([&] { return check_trace_free_cell_classes((Ctx*)ctx, *a, in, public_inputs, delta, per_column, planes, open_rows, out); });
 }
 
@@ -248,7 +247,7 @@ int starkhip_check_trace_free_cell_classes_replay(starkhip_air_t air, const uint
                                                   uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
     const AirInfo* a = air_get(air);
     const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
-    if (int rc = checker_args(a, in, public_inputs, out, bad_delta(delta))) return rc;
+    if (int rc = checker_args(a, in, public_inputs, out, free_cells_bad_delta(delta))) return rc;
     return guarded([&] { return check_trace_free_cell_classes_replay(*a, in, public_inputs, delta, per_column, planes, open_rows, out); });
 }
 

@@ -1,5 +1,5 @@
 // Host halves of the trace checkers: starkhip_check_trace, starkhip_check_trace_report (under check_report.h; kernels_check.hip) and
-// starkhip_check_trace_free_cells with starkhip_check_trace_free_cell_classes (free_cells.h; kernels_free_cells.hip,
+// starkhip_check_trace_free_cell_classes with starkhip_check_trace_free_cells, one run and a projection of it (free_cells.h;
 // kernels_free_classes.hip), and the check prove() runs on its own copy of the trace ("check_trace": check_trace_in_prove).  What the
 // stand-alone ones share is check_trace_prepare: the shape checks, the cached op stream of the AIR (check_program, Ctx::CheckProgram),
 // the trace and the public inputs on the device -- the CheckView the kernels read.
@@ -213,39 +213,14 @@ static int free_cells_program(Ctx* c, const AirInfo& air) {
     return STARKHIP_OK;
 }
 
-// starkhip_check_trace_free_cells: the audit kernel of kernels_free_cells.hip over the view the checkers share, then the count per
-// column.  One launch each: a FinalExp audit stays far below a second.  The bitmap comes back only when asked for.
-int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
-                           uint64_t* free_mask, starkhip_free_cells_t* out) {
+// What both free-cell entries do on the device: the kernel of kernels_free_classes.hip over the view the checkers share, then the count
+// per column.  One launch each: a FinalExp run stays far below a second.  `counts` comes back as per_column [C][3]
+// followed by open_rows [K]; of the planes, what the caller asks for comes back into `planes_out`: all three, the caught one, or none.
+enum class FreePlanes { NONE, CAUGHT, ALL };
+static int free_cell_classes_run(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, FreePlanes planes,
+                                 uint64_t* planes_out, std::vector<uint32_t>* counts) {
     const AirProgram& P = air.prog;
-    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
-    CheckView V = {};
-    if (int rc = check_trace_prepare(c, air, in, pis, &V)) return rc;
-    const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64;
-    hipStream_t st = c->st;
-    Ctx::FreeCellsProgram& fc = c->free_chk;
-    if (int rc = free_cells_program(c, air)) return rc;
-    HIPCHK(fc.words.ensure(C * W * 8));
-    HIPCHK(fc.per_column.ensure(C * 4));
-    HIPCHK(hipMemsetAsync(fc.words.p, 0, C * W * 8, st));
-    HIPCHK(launch_free_cells(V, fc.cons.as<FreeCon>(), fc.pivots.as<uint32_t>(), P.n_constraints, delta, fc.words.as<unsigned long long>(), st));
-    HIPCHK(launch_free_cells_count(fc.words.as<unsigned long long>(), (uint32_t)C, V.log_n, fc.per_column.as<uint32_t>(), st));
-    std::vector<uint32_t> per(C);
-    HIPCHK(hipMemcpyAsync(per.data(), fc.per_column.p, C * 4, hipMemcpyDeviceToHost, st));
-    if (free_mask) HIPCHK(hipMemcpyAsync(free_mask, fc.words.p, C * W * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(stream_wait(c));
-    if (per_column) std::copy(per.begin(), per.end(), per_column);
-    *out = free_cells_summary(per.data(), n, C);
-    return STARKHIP_OK;
-}
-
-// starkhip_check_trace_free_cell_classes: the kernel of kernels_free_classes.hip over the same view and the same compiled form, then
-// the count per column.  Buffers of its own beside the audit's, so that neither call disturbs the other's.  The planes come back
-// only when asked for.
-int check_trace_free_cell_classes(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
-                                  uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
-    const AirProgram& P = air.prog;
-    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    if (free_cells_bad_delta(delta)) return STARKHIP_ERR_BAD_SHAPE;
     CheckView V = {};
     if (int rc = check_trace_prepare(c, air, in, pis, &V)) return rc;
     const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64, K = P.n_constraints;
@@ -253,21 +228,41 @@ int check_trace_free_cell_classes(Ctx* c, const AirInfo& air, const TraceInput& 
     Ctx::FreeCellsProgram& fc = c->free_chk;
     if (int rc = free_cells_program(c, air)) return rc;
     HIPCHK(fc.planes.ensure(3 * C * W * 8));
-    HIPCHK(fc.class_counts.ensure((3 * C + K) * 4));  // per_column [C][3], open_rows [K]
+    HIPCHK(fc.class_counts.ensure((3 * C + K) * 4));
+    unsigned long long* d_planes = fc.planes.as<unsigned long long>();
     uint32_t* d_per = fc.class_counts.as<uint32_t>();
     uint32_t* d_open = d_per + 3 * C;
-    HIPCHK(hipMemsetAsync(fc.planes.p, 0, 3 * C * W * 8, st));
+    HIPCHK(hipMemsetAsync(d_planes, 0, 3 * C * W * 8, st));
     HIPCHK(hipMemsetAsync(d_open, 0, K * 4, st));
-    HIPCHK(launch_free_cell_classes(V, fc.cons.as<FreeCon>(), fc.pivots.as<uint32_t>(), P.n_constraints, delta, fc.planes.as<unsigned long long>(),
-                                    C * W, d_open, st));
-    HIPCHK(launch_free_cell_classes_count(fc.planes.as<unsigned long long>(), C * W, (uint32_t)C, V.log_n, d_per, st));
-    std::vector<uint32_t> counts(3 * C + K);
-    HIPCHK(hipMemcpyAsync(counts.data(), d_per, counts.size() * 4, hipMemcpyDeviceToHost, st));
-    if (planes) HIPCHK(hipMemcpyAsync(planes, fc.planes.p, 3 * C * W * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(launch_free_cell_classes(V, fc.cons.as<FreeCon>(), fc.pivots.as<uint32_t>(), P.n_constraints, delta, d_planes, C * W, d_open, st));
+    HIPCHK(launch_free_cell_classes_count(d_planes, C * W, (uint32_t)C, V.log_n, d_per, st));
+    counts->resize(3 * C + K);
+    HIPCHK(hipMemcpyAsync(counts->data(), d_per, counts->size() * 4, hipMemcpyDeviceToHost, st));
+    if (planes == FreePlanes::ALL) HIPCHK(hipMemcpyAsync(planes_out, d_planes, 3 * C * W * 8, hipMemcpyDeviceToHost, st));
+    if (planes == FreePlanes::CAUGHT) HIPCHK(hipMemcpyAsync(planes_out, d_planes + 2 * C * W, C * W * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+// starkhip_check_trace_free_cell_classes.  The planes come back only when asked for.
+int check_trace_free_cell_classes(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                  uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
+    const size_t C = air.prog.n_cols, K = air.prog.n_constraints;
+    std::vector<uint32_t> counts;
+    if (int rc = free_cell_classes_run(c, air, in, pis, delta, planes ? FreePlanes::ALL : FreePlanes::NONE, planes, &counts)) return rc;
     if (per_column) std::copy(counts.begin(), counts.begin() + 3 * C, per_column);
     if (open_rows) std::copy(counts.begin() + 3 * C, counts.end(), open_rows);
-    *out = free_cell_classes_summary(counts.data(), counts.data() + 3 * C, n, C, K);
+    *out = free_cell_classes_summary(counts.data(), counts.data() + 3 * C, in.n_rows, C, K);
+    return STARKHIP_OK;
+}
+
+// starkhip_check_trace_free_cells: the same run, and of its result the projection of free_cells.h.  The bitmap is the caught plane,
+// read back only when asked for and complemented in the caller's buffer.
+int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                           uint64_t* free_mask, starkhip_free_cells_t* out) {
+    std::vector<uint32_t> counts;
+    if (int rc = free_cell_classes_run(c, air, in, pis, delta, free_mask ? FreePlanes::CAUGHT : FreePlanes::NONE, free_mask, &counts)) return rc;
+    *out = free_cells_from_classes(counts.data(), in.n_rows, air.prog.n_cols, per_column, free_mask);
     return STARKHIP_OK;
 }
 

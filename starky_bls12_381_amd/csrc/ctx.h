@@ -181,15 +181,14 @@ struct Ctx {
             for (DevBuf* b : d->bufs()) v.push_back(b);
         return v;
     }
-    // free-cell audit (starkhip_check_trace_free_cells): compile_free_cells of the op stream in `chk` -- same AIR, same `want` -- and
-    // the results: the bitmap [C][(n + 63) / 64] and the free rows of each column.  Last, so that the work buffers stay where they were.
+    // the free-cell entries (starkhip_check_trace_free_cell_classes, starkhip_check_trace_free_cells): compile_free_cells of the op
+    // stream in `chk` -- same AIR, same `want` -- and the results of the one kernel behind both: the planes [3][C][(n + 63) / 64], and
+    // per_column [C][3] followed by open_rows [K].  Last, so that the work buffers stay where they were.
     struct FreeCellsProgram {
         int air = -1;
         unsigned want = 0;
-        DevBuf cons, pivots, words, per_column;
-        // starkhip_check_trace_free_cell_classes: the planes [3][C][(n + 63) / 64], and per_column [C][3] followed by open_rows [K]
-        DevBuf planes, class_counts;
-        std::vector<DevBuf*> bufs() { return {&cons, &pivots, &words, &per_column, &planes, &class_counts}; }
+        DevBuf cons, pivots, planes, class_counts;
+        std::vector<DevBuf*> bufs() { return {&cons, &pivots, &planes, &class_counts}; }
     } free_chk;
 };
 

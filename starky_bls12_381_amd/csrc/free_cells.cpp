@@ -1,5 +1,5 @@
-// starkhip_check_trace_free_cells' host half (free_cells.h): the compiled form the kernel walks, the summary, and the replay
-// without a device; and the same for starkhip_check_trace_free_cell_classes, which walks that compiled form too.
+// Host half of starkhip_check_trace_free_cell_classes and starkhip_check_trace_free_cells (free_cells.h): the compiled form the
+// kernel walks, the summaries, the audit as a projection of the classes, and the one replay without a device behind both.
 #include "free_cells.h"
 
 #include <algorithm>
@@ -53,63 +53,6 @@ starkhip_free_cells_t free_cells_summary(const uint32_t* per_column, size_t n_ro
     return s;
 }
 
-int check_trace_free_cells_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
-                                  uint64_t* free_mask, starkhip_free_cells_t* out) {
-    unsigned log_n = 0;
-    if (int rc = check_trace_shape(air, in.n_rows, pis, &log_n)) return rc;
-    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
-    const AirProgram& P = air.prog;
-    const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64;
-    std::vector<uint64_t> rows;  // row-major, and ours to change: a cell is raised in place, evaluated and put back
-    in.to_row_major(rows);
-    std::vector<uint64_t> caught(C * W, 0);
-    AirReader rd(P);
-    GroupWord grp;
-    std::vector<uint32_t> pivots;
-    for (size_t g = 0; rd.group(&grp); g++) {
-        const uint32_t group_word = P.group_off[g];
-        std::vector<uint32_t> gates(grp.n_gates);
-        for (uint32_t& ref : gates) ref = rd.ref();
-        for (uint32_t j = 0; j < grp.m; j++) {
-            const uint32_t term_word = (uint32_t)(rd.w - P.code.data());
-            pivots.clear();
-            for (uint32_t ref : gates) add_pivot(pivots, 0, ref);
-            TermWord tw;
-            do {
-                tw = rd.term();
-                for (uint32_t f = 0; f < tw.nf; f++) add_pivot(pivots, 0, rd.ref());
-            } while (!tw.last);
-            for (uint32_t piv : pivots) {
-                const size_t col = piv & REF_COL_MASK;
-                for (size_t r = 0; r < n; r++) {
-                    const size_t frame = (piv & REF_NEXT) ? (r + n - 1) % n : r;
-                    if (!constraint_applies<size_t>(grp.kind, frame, n)) continue;
-                    uint64_t& cell = rows[r * C + col];
-                    const uint64_t kept = cell;
-                    cell = gl_add(gl_from_u64(kept), delta);  // the cell is any word of its class mod p
-                    const gl_t v = air_constraint_value_at(P, group_word, term_word, &rows[frame * C], &rows[(frame + 1) % n * C], pis);
-                    cell = kept;
-                    if (v != 0) caught[col * W + (r >> 6)] |= 1ull << (r & 63);
-                }
-            }
-        }
-    }
-    std::vector<uint32_t> per(C);
-    for (size_t c = 0; c < C; c++) {
-        size_t set = 0;
-        for (size_t w = 0; w < W; w++) {
-            const uint64_t all = n - w * 64 >= 64 ? ~0ull : (1ull << (n - w * 64)) - 1;
-            const uint64_t free_w = ~caught[c * W + w] & all;
-            if (free_mask) free_mask[c * W + w] = free_w;
-            set += (size_t)__builtin_popcountll(free_w);
-        }
-        per[c] = (uint32_t)set;
-    }
-    if (per_column) std::copy(per.begin(), per.end(), per_column);
-    *out = free_cells_summary(per.data(), n, C);
-    return STARKHIP_OK;
-}
-
 starkhip_free_cell_classes_t free_cell_classes_summary(const uint32_t* per_column, const uint32_t* open_rows, size_t n_rows, size_t n_cols,
                                                        size_t n_constraints) {
     starkhip_free_cell_classes_t s = {(uint64_t)n_rows * n_cols, 0, 0, 0, 0, 0, 0};
@@ -124,18 +67,38 @@ starkhip_free_cell_classes_t free_cell_classes_summary(const uint32_t* per_colum
     return s;
 }
 
-int check_trace_free_cell_classes_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
-                                         uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
+starkhip_free_cells_t free_cells_from_classes(const uint32_t* class_per_column, size_t n_rows, size_t n_cols, uint32_t* per_column, uint64_t* mask) {
+    std::vector<uint32_t> per(n_cols);
+    for (size_t c = 0; c < n_cols; c++) per[c] = class_per_column[3 * c] + class_per_column[3 * c + 1] + class_per_column[3 * c + 2];
+    if (per_column) std::copy(per.begin(), per.end(), per_column);
+    const size_t W = (n_rows + 63) / 64;
+    const uint64_t all = n_rows >= 64 ? ~0ull : (1ull << n_rows) - 1;  // n_rows is a power of two: below 64 it is one word's low bits
+    if (mask)
+        for (size_t i = 0; i < n_cols * W; i++) mask[i] = ~mask[i] & all;
+    return free_cells_summary(per.data(), n_rows, n_cols);
+}
+
+// The one replay: the planes, the per-column counts [C][3] and open_rows [K] of the rule in free_cells.h.
+namespace {
+struct ClassesReplay {
+    std::vector<uint64_t> bits;  // [3][C][W]: read, open, caught
+    std::vector<uint32_t> per, open;
+};
+}  // namespace
+
+static int free_cell_classes_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, ClassesReplay* R) {
     unsigned log_n = 0;
     if (int rc = check_trace_shape(air, in.n_rows, pis, &log_n)) return rc;
-    if (delta == 0 || delta >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    if (free_cells_bad_delta(delta)) return STARKHIP_ERR_BAD_SHAPE;
     const AirProgram& P = air.prog;
     const size_t n = in.n_rows, C = P.n_cols, W = (n + 63) / 64;
     std::vector<uint64_t> rows;  // row-major, and ours to change: a cell is raised in place, evaluated and put back
     in.to_row_major(rows);
-    std::vector<uint64_t> bits(3 * C * W, 0);  // read, open, caught
+    std::vector<uint64_t>& bits = R->bits;
+    bits.assign(3 * C * W, 0);
     uint64_t *rd_p = bits.data(), *op_p = rd_p + C * W, *ca_p = op_p + C * W;
-    std::vector<uint32_t> open(P.n_constraints, 0);
+    std::vector<uint32_t>& open = R->open;
+    open.assign(P.n_constraints, 0);
     AirReader rd(P);
     GroupWord grp;
     std::vector<uint32_t> pivots;
@@ -178,7 +141,8 @@ int check_trace_free_cell_classes_replay(const AirInfo& air, const TraceInput& i
             }
         }
     }
-    std::vector<uint32_t> per(3 * C);
+    std::vector<uint32_t>& per = R->per;
+    per.assign(3 * C, 0);
     for (size_t c = 0; c < C; c++) {
         uint32_t silent = 0, gated = 0, unread = 0;
         for (size_t w = 0; w < W; w++) {
@@ -192,10 +156,26 @@ int check_trace_free_cell_classes_replay(const AirInfo& air, const TraceInput& i
         per[3 * c + 1] = gated;
         per[3 * c + 2] = unread;
     }
-    if (per_column) std::copy(per.begin(), per.end(), per_column);
-    if (planes) std::copy(bits.begin(), bits.end(), planes);
-    if (open_rows) std::copy(open.begin(), open.end(), open_rows);
-    *out = free_cell_classes_summary(per.data(), open.data(), n, C, P.n_constraints);
+    return STARKHIP_OK;
+}
+
+int check_trace_free_cell_classes_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                         uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out) {
+    ClassesReplay R;
+    if (int rc = free_cell_classes_replay(air, in, pis, delta, &R)) return rc;
+    if (per_column) std::copy(R.per.begin(), R.per.end(), per_column);
+    if (planes) std::copy(R.bits.begin(), R.bits.end(), planes);
+    if (open_rows) std::copy(R.open.begin(), R.open.end(), open_rows);
+    *out = free_cell_classes_summary(R.per.data(), R.open.data(), in.n_rows, air.prog.n_cols, air.prog.n_constraints);
+    return STARKHIP_OK;
+}
+
+int check_trace_free_cells_replay(const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
+                                  uint64_t* free_mask, starkhip_free_cells_t* out) {
+    ClassesReplay R;
+    if (int rc = free_cell_classes_replay(air, in, pis, delta, &R)) return rc;
+    if (free_mask) std::copy(R.bits.begin() + 2 * (R.bits.size() / 3), R.bits.end(), free_mask);  // the caught plane
+    *out = free_cells_from_classes(R.per.data(), in.n_rows, air.prog.n_cols, per_column, free_mask);
     return STARKHIP_OK;
 }
 

@@ -180,18 +180,12 @@ hipError_t launch_check_report_count(const CheckView& v, uint32_t* counts, unsig
 hipError_t launch_check_report_list(const CheckView& v, const uint32_t* chunks, unsigned n_launched, uint32_t* cursors, const unsigned long long* row_mask,
                                     const uint32_t* base, unsigned long long* list, uint32_t list_len, hipStream_t st);
 
-// kernels_free_cells.hip: the free-cell audit (starkhip_check_trace_free_cells) over the same view.  caught[c][blockIdx.x] |= the rows
-// of the wave whose cell of column c some constraint notices when delta is added to it (zeroed by the caller); `cons` and `pivots` are
-// compile_free_cells' (free_cells.h).  The count turns the caught words into free words in place and sets per_column[c] to their bits.
+// kernels_free_classes.hip: the free-cell kernel (starkhip_check_trace_free_cell_classes, and starkhip_check_trace_free_cells as its
+// caught plane) over the same view; `cons` and `pivots` are compile_free_cells' (free_cells.h).  planes [3][C][(n + 63) / 64] -- read,
+// open, caught; plane_words = C x (n + 63) / 64 -- and open_rows [K] are zeroed by the caller and only gain bits and counts: a cell's
+// caught bit is set when some constraint notices delta added to it.  The count leaves the planes as they are and sets
+// per_column[c][0 .. 2] to the column's silent, gated and unread rows.
 struct FreeCon;
-hipError_t launch_free_cells(const CheckView& v, const FreeCon* cons, const uint32_t* pivots, uint32_t n_constraints, gl_t delta,
-                             unsigned long long* caught, hipStream_t st);
-hipError_t launch_free_cells_count(unsigned long long* words, uint32_t n_cols, unsigned log_n, uint32_t* per_column, hipStream_t st);
-
-// kernels_free_classes.hip: the audit's free cells by class (starkhip_check_trace_free_cell_classes) over the same view and the same
-// `cons` and `pivots`.  planes [3][C][(n + 63) / 64] -- read, open, caught; plane_words = C x (n + 63) / 64 -- and open_rows [K] are
-// zeroed by the caller and only gain bits and counts.  The count leaves the planes as they are and sets per_column[c][0 .. 2] to the
-// column's silent, gated and unread rows.
 hipError_t launch_free_cell_classes(const CheckView& v, const FreeCon* cons, const uint32_t* pivots, uint32_t n_constraints, gl_t delta,
                                     unsigned long long* planes, size_t plane_words, uint32_t* open_rows, hipStream_t st);
 hipError_t launch_free_cell_classes_count(const unsigned long long* planes, size_t plane_words, uint32_t n_cols, unsigned log_n,

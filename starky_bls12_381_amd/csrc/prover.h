@@ -78,7 +78,8 @@ int check_trace(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t
 // starkhip_check_trace_report: the same check with per-constraint counts, the rows and a list (kernels_check.hip, check_report.h)
 int check_trace_report(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint32_t* per_constraint, uint64_t* row_mask,
                        uint64_t* list, size_t cap, starkhip_check_report_t* out);
-// starkhip_check_trace_free_cells: the cells no constraint notices when delta is added to them (kernels_free_cells.hip, free_cells.h)
+// starkhip_check_trace_free_cells: the cells no constraint notices when delta is added to them -- the caught plane of the classes
+// below, complemented (kernels_free_classes.hip, free_cells.h)
 int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
                            uint64_t* free_mask, starkhip_free_cells_t* out);
 // starkhip_check_trace_free_cell_classes: those cells as unread, gated off or silent, and the rows each constraint's gates were open on

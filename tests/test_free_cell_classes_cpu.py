@@ -1,6 +1,7 @@
 """starkhip_check_trace_free_cell_classes_replay (csrc/free_cells.cpp) against a brute force of the rule written in Python
-(free_cell_classes_util.Expected), against recorded class counts, against starkhip_check_trace_free_cells_replay, and on a
-hand-written AIR whose classes are known by construction.  No GPU."""
+(free_cell_classes_util.Expected), against recorded class counts, against starkhip_check_trace_free_cells_replay (its projection), and
+on a hand-written AIR whose classes are known by construction; and that brute force against the audit's (free_cells_util.Expected).
+No GPU."""
 import ctypes as C
 import functools
 
@@ -11,6 +12,7 @@ import oracle_lib as O
 import starky_bls12_381_amd as S
 from free_cell_classes_util import CASES, Expected, assert_classes, assert_nested, assert_same, assert_same_counts, hand_air, summary
 from free_cells_util import CPU_CASES, DELTA, P, case, corrupt_one, register
+from free_cells_util import Expected as AuditExpected
 
 KEYS = list(CASES)
 
@@ -58,6 +60,28 @@ def test_caught_is_the_audits_rule_and_the_free_classes_partition_its_free_cells
     assert got.n_silent + got.n_gated + got.n_unread == audit.free and got.n_caught == audit.cells - audit.free
     assert np.array_equal(got.per_column.sum(axis=1, dtype=np.uint32), audit.per_column)
     assert_nested(got, key[3])
+
+
+def assert_brute_forces_agree(classes, audit):
+    assert np.array_equal(classes.caught, ~audit.mask)
+    assert np.array_equal(classes.silent | classes.gated | classes.unread, audit.mask)
+    assert np.array_equal(classes.per_column.sum(axis=1, dtype=np.uint32), audit.per_column)
+
+
+# The library's audit is a projection of its classes, so the test above compares one replay loop with itself.  What keeps the two
+# results independent are the two brute forces, written apart and neither touching the library: free_cells_util.Expected evaluates
+# the expanded polynomial G * body, free_cell_classes_util.Expected gates and body apart.  Each pins its own replay; this holds them
+# to each other.
+@pytest.mark.parametrize("key", list(CPU_CASES), ids=str)
+def test_the_two_brute_forces_agree(key):
+    blob, trace, pis = case(key)
+    assert_brute_forces_agree(expected(key), AuditExpected(blob, trace, pis))
+
+
+@pytest.mark.parametrize("n", (2, 64, 128))
+def test_the_two_brute_forces_agree_on_the_hand_written_air(n):
+    h = hand_air(n)
+    assert_brute_forces_agree(Expected(h.blob, h.trace, h.pis), AuditExpected(h.blob, h.trace, h.pis))
 
 
 @pytest.mark.parametrize("n", (2, 64, 128))

@@ -1,6 +1,6 @@
 """starkhip_check_trace_free_cell_classes on the device (kernels_free_classes.hip) against its host replay, bit for bit: a hand-written
 AIR whose classes are known by construction, random AIRs of 128 to 4096 rows, a violating trace, cells at or above p, a trace in
-device memory, and the context shared with the audit, the checkers and a proof."""
+device memory, the audit as the projection of the classes, and the context shared with the audit, the checkers and a proof."""
 import functools
 import os
 import subprocess
@@ -14,6 +14,7 @@ from check_report_util import corrupt
 from free_cell_classes_util import assert_classes, assert_same, assert_same_counts, hand_air
 from free_cells_util import P, case, corrupt_one, register
 from free_cells_util import assert_same as assert_same_audit
+from free_cells_util import summary as summary_audit
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,6 +78,28 @@ def test_cells_at_or_above_p(prover):
     assert_same(prover.free_cell_classes(air, aliased.T.copy(), pis, layout=1), replay(key))
 
 
+# The audit's device entry is the classes' run and a projection of it on the host: the caught plane alone is read back and complemented
+# on the live rows in the caller's buffer, per_column is the sum of the three class counts.  The shapes are the ones the projection
+# itself can go wrong at -- 2 rows: one word per column, whose 62 high bits have to stay zero after the complement; 64: a full word;
+# 128: two words; and the random AIRs, up to 64 words per column and several chunks.
+@pytest.mark.parametrize("shape", [2, 64, 128] + RANDOM, ids=str)
+def test_the_audit_is_the_projection_of_the_classes(prover, shape):
+    if isinstance(shape, int):
+        h = hand_air(shape)
+        blob, trace, pis, n = h.blob, h.trace, h.pis, shape
+    else:
+        (blob, trace, pis), n = case(shape), shape[3]
+    air = register(blob, n)
+    audit = prover.free_cells(air, trace, pis)
+    got = prover.free_cell_classes(air, trace, pis)
+    live = np.uint64((1 << min(n, 64)) - 1)
+    assert got.plane_words[2].shape == audit.mask_words.shape == (trace.shape[1], (n + 63) // 64)
+    assert ((got.plane_words[2] ^ audit.mask_words) == live).all()
+    assert np.array_equal(got.per_column.sum(axis=1, dtype=np.uint32), audit.per_column)
+    bare = prover.free_cells(air, trace, pis, mask=False)  # no plane read back: the same counts and summary
+    assert bare.mask is None and summary_audit(bare) == summary_audit(audit) and np.array_equal(bare.per_column, audit.per_column)
+
+
 DEVICE_CHILD = r"""
 import os, sys, faulthandler
 faulthandler.dump_traceback_later(120, exit=True)
@@ -135,7 +158,7 @@ def test_one_context_serves_both_audits_the_checkers_and_a_proof(prover):
     assert_same_audit(prover.free_cells(air, trace, pis), audit)
     got = prover.free_cell_classes(air, trace, pis)
     assert_same(got, replay(key))
-    assert_same_audit(prover.free_cells(air, trace, pis), audit)  # the audit after the classes: its own buffers, the shared compiled form
+    assert_same_audit(prover.free_cells(air, trace, pis), audit)  # the audit after the classes: the same buffers and compiled form
     assert np.array_equal(got.caught, ~audit.mask)
     assert after(prover) == want
     assert_same(prover.free_cell_classes(air, trace, pis), got)  # and the classes after them

@@ -1,4 +1,4 @@
-"""starkhip_check_trace_free_cells on the device (kernels_free_cells.hip) against its host replay, bit for bit: a hand-written AIR
+"""starkhip_check_trace_free_cells on the device (kernels_free_classes.hip) against its host replay, bit for bit: a hand-written AIR
 whose free cells are known by construction, random AIRs of 128 to 4096 rows, and a real FP12Mul trace."""
 import functools
 import os
