@@ -73,6 +73,12 @@ lane-group-test: tests/lane_group_pool_main.cpp $(ASAN_SRCS) $(HDRS)
 	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/lane_group_pool tests/lane_group_pool_main.cpp $(ASAN_SRCS) -lpthread
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/lane_group_pool
 
+# the Keccak hasher's host code (keccak.h, keccak_host.cpp) under AddressSanitizer + UndefinedBehaviorSanitizer: a stand-alone program
+asan-keccak-test: tests/asan_keccak_main.cpp $(CSRC)/keccak_host.cpp $(CSRC)/keccak.h $(CSRC)/gl.h
+	@mkdir -p build/asan
+	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_keccak tests/asan_keccak_main.cpp $(CSRC)/keccak_host.cpp
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_keccak
+
 # Experiment builds of the device code for A/B runs on one box: `make variant NAME=x DEFS="-D..."` -> build/x/libstarkhip_x.so, selected
 # at run time with STARKHIP_LIBRARY=build/x/libstarkhip_x.so (e.g. NAME=nomfma DEFS=-DSTARKHIP_LANE_NO_MFMA: the lane-form leaf hash with every
 # round as multiply-add chains; NAME=noprio DEFS=-DSTARKHIP_NO_PRIO: no raised issue priority for the kernels beside the lane-form hash)
@@ -88,4 +94,4 @@ build/$(NAME)/libstarkhip_$(NAME).so: $(VAR_OBJS) $(filter %.cpp.o,$(OBJS))
 clean:
 	rm -rf build $(OUT)
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test variant
+.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test asan-keccak-test variant

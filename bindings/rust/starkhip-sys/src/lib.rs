@@ -51,6 +51,9 @@ pub const STARKHIP_ERR_TRACE: c_int = -9;
 /// First word of the check blob a checking prove hands back with `STARKHIP_ERR_TRACE` ("SSCHK001").
 pub const STARKHIP_CHECK_MAGIC: u64 = 0x3130304B48435353;
 pub const STARKHIP_POW_SEARCH: u64 = u64::MAX;
+/// The hasher of a proof (`C: GenericConfig`): the context / pool option "hasher", and header word 12 of a proof blob.
+pub const STARKHIP_HASHER_POSEIDON: c_int = 0;
+pub const STARKHIP_HASHER_KECCAK: c_int = 1;
 /// A registered AIR is proved on any power of two of rows in 2 ..= 2^STARKHIP_MAX_LOG_ROWS; a built-in AIR on at most 8192.
 pub const STARKHIP_MAX_LOG_ROWS: u32 = 20;
 pub const STARKHIP_N_PHASES: usize = 11;
@@ -321,6 +324,14 @@ extern "C" {
     pub fn starkhip_verify_batch_replay(n: usize, airs: *const Air, cfgs: *const starkhip_config_t, proofs: *const *const u64,
                                         proof_words: *const usize, results: *mut c_int) -> c_int;
     pub fn starkhip_proof_layout(proof: *const u64, proof_words: usize, out: *mut starkhip_proof_layout_t) -> c_int;
+    pub fn starkhip_proof_hasher(proof: *const u64, proof_words: usize) -> c_int;
+    pub fn starkhip_keccak256(bytes: *const u8, len: usize, out32: *mut u8);
+    pub fn starkhip_keccak_permute_host(state12: *mut u64);
+    pub fn starkhip_keccak_state_from_words(words: *const u64, n: usize, state12: *mut u64) -> c_int;
+    pub fn starkhip_keccak_permute_batch(ctx: *mut c_void, states: *mut u64, n: usize) -> c_int;
+    pub fn starkhip_merkle_tree_hasher(ctx: *mut c_void, hasher: c_int, lde_colmajor: *const u64, n_cols: usize, log_n: c_uint, cap_height: c_uint,
+                                       digests_out: *mut u64, cap_out: *mut u64) -> c_int;
+    pub fn starkhip_hash_rows_hasher(ctx: *mut c_void, hasher: c_int, rows: *const u64, width: usize, n_leaves: usize, digests_out: *mut u64) -> c_int;
     /// The config rule of every entry point (no GPU): the FRI reduction arities and final polynomial length of a config at
     /// 2^log_n rows, or `STARKHIP_ERR_BAD_SHAPE` for a config the prover and verifiers refuse.
     pub fn starkhip_fri_geometry(cfg: *const starkhip_config_t, log_n: c_uint, arities_out: *mut c_uint, cap: usize, n_layers: *mut usize,
@@ -365,6 +376,12 @@ impl Proof {
         let mut l = std::mem::MaybeUninit::<starkhip_proof_layout_t>::zeroed();
         check(unsafe { starkhip_proof_layout(self.0.as_ptr(), self.0.len(), l.as_mut_ptr()) })?;
         Ok(unsafe { l.assume_init() })
+    }
+    /// `STARKHIP_HASHER_POSEIDON` or `STARKHIP_HASHER_KECCAK`: the hasher the proof's header names (the verify entries verify under it).
+    pub fn hasher(&self) -> Result<c_int, Error> {
+        let h = unsafe { starkhip_proof_hasher(self.0.as_ptr(), self.0.len()) };
+        if h < 0 { check(h)?; }
+        Ok(h)
     }
     pub fn public_inputs(&self) -> Result<&[u64], Error> {
         let l = self.layout()?;

@@ -102,6 +102,18 @@ enum {
 
 #define STARKHIP_POW_SEARCH UINT64_MAX
 
+/* The hasher of a proof -- plonky2's `C: GenericConfig`: PoseidonGoldilocksConfig (what the reference's drivers select, and the default)
+ * or KeccakGoldilocksConfig (KeccakHash<25>; COMPAT.md K1 - K8).  Chosen per context ("hasher", starkhip_set_option) or per pool, and
+ * carried in header word 12 of the proof, which every verify entry reads: a proof is verified under the hasher its header names, and a
+ * batch may mix both.  A Keccak digest is 25 bytes; in the blob it is the four field elements plonky2's challenger observes for it
+ * (the bytes in little-endian chunks of 7, 7, 7 and 4), so a digest is 4 words under either hasher, every proof word stays a canonical
+ * field element and the blob layout below holds for both.  A Keccak proof with a digest word outside those ranges (2^56, the last 2^32)
+ * is rejected. */
+enum {
+    STARKHIP_HASHER_POSEIDON = 0,
+    STARKHIP_HASHER_KECCAK = 1
+};
+
 /* --- configuration ------------------------------------------------------------------- */
 void starkhip_config_standard_fast(starkhip_config_t* cfg);
 /* the per-AIR config the reference builds (rate_bits override for PairingPrecomp / FinalExp) */
@@ -342,6 +354,10 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
  * "check_trace" (0 = default / 1: every prove on the context checks its trace against the AIR before the LDE and returns
  * STARKHIP_ERR_TRACE with a check blob for a violating one -- "the check inside prove()" above), "check_trace_list" (0 ..
  * STARKHIP_CHECK_LIST_MAX, default 16: the violations such a blob lists),
+ * "hasher" (STARKHIP_HASHER_POSEIDON, the default, or STARKHIP_HASHER_KECCAK: the hash of every prove entry of the context -- trace
+ * and quotient commitments, FRI layers, proof of work and the transcript's sponge.  With 0 every byte of every proof is what it is
+ * without the option.  Under STARKHIP_HASHER_KECCAK "leaf_hash_form" and "host_commit_leaves" do not apply: they pick among Poseidon
+ * forms and are ignored),
  * "quotient_waves", "quotient_slots", "lde_closed_forms" (1 = constant and unit-vector trace columns take their closed-form LDE
  * instead of five transforms, 0 = every column is transformed; same bytes either way; traces of 2^14 rows and more have no closed forms and transform every column), "host_commit_leaves" (default 64: trace commitments of at most this many leaves -- FP12Mul's 32 -- are hashed by host threads with the
  * challenger's permutation, 0.8 us against 5.6 us per permutation of a lone GPU wave; 0 = never; only with "leaf_hash_form" 0), "leaf_hash_form" (0 = a context on its own
@@ -426,7 +442,8 @@ typedef struct {
     float host_ms[2];     /* as starkhip_last_host_timings */
     double t_submit, t_generate_start, t_generate_end, t_prove_start, t_done; /* seconds since the pool was created */
     int leaf_hash_form;       /* how the trace commitment went out: 0 quad form, 1 row form, 2 one grid merged with other proofs' commitments
-                                 (quad form), 3 lane form, 4 hashed by host threads (at most "host_commit_leaves" leaves), 5 pair form; kernel_ms[1] is
+                                 (quad form), 3 lane form, 4 hashed by host threads (at most "host_commit_leaves" leaves), 5 pair form,
+                                 6 the Keccak leaf hash ("hasher" 1: always the context's own launch); kernel_ms[1] is
                                  that kernel's own duration on its launch stream (form 4: the host's time) */
     unsigned leaf_hash_group; /* commitments that were launched side by side with it (itself included) */
 } starkhip_ticket_info_t;
@@ -521,7 +538,12 @@ int starkhip_hw_queues_in_effect(void);
  *                     as the context option "check_trace" does, whichever submit it came through (a witness job's recording included).
  *                     A violating trace: starkhip_pool_wait returns STARKHIP_ERR_TRACE and hands over the check blob in *proof
  *                     (starkhip_free); with "verify_proofs" on as well it never reaches the verifier.
- *   "check_trace_list" 0 .. STARKHIP_CHECK_LIST_MAX (default 16): the violations such a blob lists; read at submit too. */
+ *   "check_trace_list" 0 .. STARKHIP_CHECK_LIST_MAX (default 16): the violations such a blob lists; read at submit too.
+ *   "hasher"          STARKHIP_HASHER_POSEIDON (default) or STARKHIP_HASHER_KECCAK: the hasher of every proving ticket submitted from then
+ *                     on, as the context option "hasher".  A Keccak proof's trace commitment is launched by its context on its own stream,
+ *                     not by the pool's commitment scheduler (whose merged and lane-group launches are Poseidon forms): the counters of
+ *                     starkhip_pool_stats do not move for it and its ticket reports leaf_hash_form 6.  The pool's verifier
+ *                     ("verify_proofs", verify jobs) takes each proof's hasher from its header, whatever this option says. */
 int starkhip_pool_set_option(void* pool, const char* name, long value);
 /* out = {traces checked, traces rejected}, summed over the pool's contexts (per slot of a multi-device handle: starkhip_multipool_pool) */
 int starkhip_pool_check_stats(void* pool, uint64_t out[2]);
@@ -687,6 +709,27 @@ int starkhip_quotient_solve_table(unsigned log_rows, unsigned quotient_degree_bi
  * stats: [0] classes, [1] cosets, [2] chunks, [3] work rows, [4] records, [5] piece ends, [6] tile phases, [7] contributions,
  * [8 + c] constraints of class c + 1, [24 + t] chunks of coset t. */
 int starkhip_quotient_class_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[32]);
+/* --- the Keccak hasher under test (COMPAT.md K1 - K8; csrc/keccak.h) ---
+ * keccak256 of `len` bytes on the host: Keccak-f[1600], rate 136, padding 0x01 .. 0x80 (not SHA-3's 0x06), 32 bytes out */
+void starkhip_keccak256(const uint8_t* bytes, size_t len, uint8_t out32[32]);
+/* the challenger's permutation under STARKHIP_HASHER_KECCAK on the host, in place (canonical words in and out): the 12 elements as 96
+ * little-endian bytes, h1 = keccak256 of them, h2 = keccak256 of h1, ...; each h gives four little-endian words, words >= p are
+ * skipped, and the first 12 accepted words are the new state */
+void starkhip_keccak_permute_host(uint64_t state12[12]);
+/* that word filter alone, the function host and device code share: the words below p of words[0 .. n) fill state12 in order; returns
+ * how many words it consumed up to and including the twelfth accepted one, or -1 when the stream holds fewer than 12 such words
+ * (state12 then holds the ones it found, the rest untouched) */
+int starkhip_keccak_state_from_words(const uint64_t* words, size_t n, uint64_t state12[12]);
+/* the same permutation on the device, n states of 12 words in place */
+int starkhip_keccak_permute_batch(void* ctx, uint64_t* states, size_t n);
+/* starkhip_merkle_cap under `hasher`: Merkle tree of the matrix whose leaf j is the row bitrev of j of an LDE given column-major in
+ * natural order [n_cols][2^log_N]; digests_out: the 2^log_N leaf digests x 4 words in tree order, or NULL; cap_out: 2^cap_height x 4.
+ * Hasher 0 hashes the leaves in the form a lone proof of this shape would.  BAD_SHAPE for an unknown hasher, no columns, or
+ * log_N < cap_height or > 28 */
+int starkhip_merkle_tree_hasher(void* ctx, int hasher, const uint64_t* lde_colmajor, size_t n_cols, unsigned log_N, unsigned cap_height,
+                                uint64_t* digests_out, uint64_t* cap_out);
+/* digests (n_leaves x 4 words) of row-major leaves rows[n_leaves][width] under `hasher`, as the FRI layers are hashed */
+int starkhip_hash_rows_hasher(void* ctx, int hasher, const uint64_t* rows, size_t width, size_t n_leaves, uint64_t* digests_out);
 /* host-side permutation (the one the Fiat-Shamir challenger uses) */
 void starkhip_poseidon_permute_host(uint64_t state[12]);
 /* n chained host permutations; which = 0: the challenger's tuned permutation, 1: the portable loop */
@@ -719,7 +762,7 @@ const char* starkhip_error_string(int code);
 
 /* Proof blob, uint64 words (canonical field order of StarkProofWithPublicInputs):
  *   [0..16)  header: magic "SSPRF001", C, Q, degree_bits, rate_bits, cap_height, L (FRI layers),
- *            num_query_rounds, final_poly_len, n_pis, arity_bits, num_challenges, 0,0,0,0
+ *            num_query_rounds, final_poly_len, n_pis, arity_bits, num_challenges, hasher (STARKHIP_HASHER_*: 0 for Poseidon), 0,0,0
  *   trace_cap[2^cap_h][4]; quotient_polys_cap[2^cap_h][4]
  *   openings.local_values[C][2]; openings.next_values[C][2]; openings.quotient_polys[Q][2]
  *   commit_phase_merkle_caps[L][2^cap_h][4]
@@ -744,6 +787,9 @@ typedef struct {
 } starkhip_proof_layout_t;
 /* STARKHIP_ERR_BAD_SHAPE when the blob's header is not a proof header or disagrees with proof_words */
 int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_proof_layout_t* out);
+/* the hasher id in the proof's header (STARKHIP_HASHER_*), or STARKHIP_ERR_BAD_SHAPE for a blob that is not a proof or names an unknown
+ * hasher.  The verify entries accept either hasher; a caller that insists on one asks here. */
+int starkhip_proof_hasher(const uint64_t* proof, size_t proof_words);
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,12 @@ struct Proof {
     size_t n_public_inputs = 0;
     starkhip_ticket_info_t info{};  // pool proofs: phase times and the job's timeline (starkhip_pool_wait)
     const uint64_t* public_inputs() const { return words.data() + words.size() - n_public_inputs; }
+    // STARKHIP_HASHER_POSEIDON or STARKHIP_HASHER_KECCAK: the hasher the proof's header names (every verify entry verifies under it)
+    int hasher() const {
+        const int h = starkhip_proof_hasher(words.data(), words.size());
+        if (h < 0) throw Error("starkhip_proof_hasher", h);
+        return h;
+    }
     Proof() = default;
     Proof(Proof&&) = default;
     Proof& operator=(Proof&&) = default;
@@ -92,6 +98,8 @@ class Prover {
     explicit Prover(int device = 0) { check("starkhip_init", starkhip_init(device, &ctx_)); }
     ~Prover() { starkhip_shutdown(ctx_); }
     void* handle() const { return ctx_; }  // the context (starkhip_init), e.g. for verify_batch_on_device
+    // `C: GenericConfig` of the proofs this context makes from now on: STARKHIP_HASHER_POSEIDON (the default) or STARKHIP_HASHER_KECCAK
+    void set_hasher(int hasher) { check("starkhip_set_option", starkhip_set_option(ctx_, "hasher", hasher)); }
     Prover(const Prover&) = delete;
     Prover& operator=(const Prover&) = delete;
 
@@ -308,7 +316,8 @@ class Pool {
         if (verify.on == VerifyOn::host) check("starkhip_verify", starkhip_verify(air, &p.config, p.words.data(), p.words.size()));
         return p;
     }
-    // starkhip_pool_set_option (every pool of a multi-device handle): "verify_proofs", "verify_arena_mb", "check_traces", "check_trace_list"
+    // starkhip_pool_set_option (every pool of a multi-device handle): "verify_proofs", "verify_arena_mb", "check_traces", "check_trace_list",
+    // "hasher" (STARKHIP_HASHER_*: the hasher of the tickets submitted from then on)
     void set_option(const char* name, long value) {
         if (multi_) check("starkhip_multipool_set_option", starkhip_multipool_set_option(pool_, name, value));
         else check("starkhip_pool_set_option", starkhip_pool_set_option(pool_, name, value));

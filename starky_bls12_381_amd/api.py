@@ -130,6 +130,17 @@ lib.starkhip_native_final_exponentiate.argtypes = [_u32p, _u32p]
 lib.starkhip_native_miller_loop.argtypes = [_u32p, _u32p, _u32p, _u32p, _u32p, _u32p]
 lib.starkhip_native_pairing_precomp.argtypes = [_u32p, _u32p, _u32p, _u32p]
 _u8p = C.POINTER(C.c_uint8)
+HASHER_POSEIDON, HASHER_KECCAK = 0, 1  # STARKHIP_HASHER_*: the "hasher" option of a Prover or a ProofPool, and header word 12 of a proof
+LEAF_HASH_FORM_KECCAK = 6  # TicketInfo.leaf_hash_form of a Keccak proof
+lib.starkhip_keccak256.argtypes = [C.c_char_p, C.c_size_t, _u8p]
+lib.starkhip_keccak256.restype = None
+lib.starkhip_keccak_permute_host.argtypes = [_u64p]
+lib.starkhip_keccak_permute_host.restype = None
+lib.starkhip_keccak_state_from_words.argtypes = [_u64p, C.c_size_t, _u64p]
+lib.starkhip_keccak_permute_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t]
+lib.starkhip_merkle_tree_hasher.argtypes = [C.c_void_p, C.c_int, _u64p, C.c_size_t, C.c_uint, C.c_uint, _u64p, _u64p]
+lib.starkhip_hash_rows_hasher.argtypes = [C.c_void_p, C.c_int, _u64p, C.c_size_t, C.c_size_t, _u64p]
+lib.starkhip_proof_hasher.argtypes = [_u64p, C.c_size_t]
 lib.starkhip_trace_ecc_aggregate.argtypes = [_u32p, _u8p, _u64p, C.c_size_t, _u64p]
 lib.starkhip_native_g1_aggregate.argtypes = [_u32p, _u8p, _u32p]
 
@@ -740,6 +751,39 @@ def poseidon_permute_host(state):
     return s
 
 
+def keccak256(data):
+    """keccak256 (padding 0x01 .. 0x80) of `data` on the host: 32 bytes."""
+    data = bytes(data)
+    out = (C.c_uint8 * 32)()
+    lib.starkhip_keccak256(data, len(data), out)
+    return bytes(out)
+
+
+def keccak_permute_host(state):
+    """The challenger's permutation under the Keccak hasher (COMPAT.md K7) on one state of 12 canonical words."""
+    s = np.ascontiguousarray(state, dtype=np.uint64).copy()
+    assert s.size == 12
+    lib.starkhip_keccak_permute_host(_p64(s))
+    return s
+
+
+def keccak_state_from_words(words):
+    """K7's word filter: (state of 12, words consumed), or (partial state, -1) when `words` holds fewer than 12 words below p."""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    state = np.zeros(12, dtype=np.uint64)
+    used = lib.starkhip_keccak_state_from_words(_p64(w), w.size, _p64(state))
+    return state, used
+
+
+def proof_hasher(proof):
+    """HASHER_POSEIDON or HASHER_KECCAK: the hasher a proof's header names (every verify entry verifies under it)."""
+    p = np.ascontiguousarray(proof, dtype=np.uint64)
+    rc = lib.starkhip_proof_hasher(_p64(p), p.size)
+    if rc < 0:
+        raise StarkhipError(rc)
+    return rc
+
+
 def _column_table(columns):
     """(pointer table, the arrays it points into, n_rows) for starkhip_prove_columns / starkhip_pool_submit_columns."""
     keep = [np.ascontiguousarray(c, dtype=np.uint64) for c in columns]
@@ -993,6 +1037,30 @@ class Prover:
         _chk(lib.starkhip_merkle_cap(self._ctx, _p64(v), ncols, N.bit_length() - 1, cap_height, _p64(cap)))
         return cap
 
+    def merkle_tree(self, lde_colmajor, cap_height, hasher=HASHER_POSEIDON):
+        """(leaf digests [N][4] in tree order, cap [2^cap_height][4]) of an LDE given column-major in natural order, under `hasher`."""
+        v = np.ascontiguousarray(lde_colmajor, dtype=np.uint64)
+        ncols, N = v.shape
+        digests = np.zeros((N, 4), dtype=np.uint64)
+        cap = np.zeros((1 << cap_height, 4), dtype=np.uint64)
+        _chk(lib.starkhip_merkle_tree_hasher(self._ctx, hasher, _p64(v), ncols, N.bit_length() - 1, cap_height, _p64(digests), _p64(cap)))
+        return digests, cap
+
+    def hash_rows(self, rows, hasher=HASHER_POSEIDON):
+        """Digests [n_leaves][4] of row-major leaves [n_leaves][width] under `hasher`, as the FRI layers are hashed."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        assert r.ndim == 2
+        out = np.zeros((r.shape[0], 4), dtype=np.uint64)
+        _chk(lib.starkhip_hash_rows_hasher(self._ctx, hasher, _p64(r), r.shape[1], r.shape[0], _p64(out)))
+        return out
+
+    def keccak_permute_batch(self, states):
+        """The Keccak hasher's challenger permutation of every row of `states` (n x 12) on the device."""
+        s = np.ascontiguousarray(states, dtype=np.uint64).copy()
+        assert s.ndim == 2 and s.shape[1] == 12
+        _chk(lib.starkhip_keccak_permute_batch(self._ctx, _p64(s), s.shape[0]))
+        return s
+
     def field_ops(self, op, a, b):
         """Device field arithmetic under test (kernels_selftest.hip): canonical(op(a[i], b[i]))."""
         a = np.ascontiguousarray(a, dtype=np.uint64)
@@ -1226,7 +1294,8 @@ class ProofPool:
 
     def set_option(self, name, value):
         """starkhip_pool_set_option on every pool of the handle: "verify_proofs" (0 / 1), "verify_arena_mb", "check_traces" (0 / 1: wait
-        raises TraceViolation for a trace that violates its AIR), "check_trace_list"."""
+        raises TraceViolation for a trace that violates its AIR), "check_trace_list", "hasher" (HASHER_POSEIDON / HASHER_KECCAK: the
+        hasher of the proving tickets submitted from then on)."""
         if self._multi:
             _chk(lib.starkhip_multipool_set_option(self._h, name.encode(), int(value)))
         else:
@@ -1400,7 +1469,8 @@ class ProofPool:
                        "kernel_ms": {"lde_columns": float(info.kernel_ms[0]), "leaf_hash": float(info.kernel_ms[1]), "quotient_eval": float(info.kernel_ms[2])},
                        "host_ms": {"fiat_shamir": float(info.host_ms[0]), "other": float(info.host_ms[1])},
                        "timeline_s": [info.t_submit, info.t_generate_start, info.t_generate_end, info.t_prove_start, info.t_done],
-                       "leaf_hash_form": ("quad", "row", "merged", "lane", "host", "pair")[min(info.leaf_hash_form, 5)], "leaf_hash_group": int(info.leaf_hash_group)}
+                       "leaf_hash_form": ("quad", "row", "merged", "lane", "host", "pair", "keccak")[min(info.leaf_hash_form, 6)],
+                       "leaf_hash_form_id": int(info.leaf_hash_form), "leaf_hash_group": int(info.leaf_hash_group)}
 
     def reservation(self):
         """starkhip_pool_reservation: what the pool's contexts hold (bytes; summed over the devices' pools, the per-context figures the largest)."""

@@ -927,6 +927,34 @@ size_t starkhip_lde_launch_ranges(size_t n_cols, unsigned rate_bits, uint64_t* t
     return plan.size();
 }
 void starkhip_poseidon_permute_host(uint64_t state[12]) { poseidon_permute_host(state); }
+
+/* --- the Keccak hasher's test entries (keccak.h) */
+void starkhip_keccak256(const uint8_t* bytes, size_t len, uint8_t out32[32]) { keccak256_host(bytes, len, out32); }
+void starkhip_keccak_permute_host(uint64_t state12[12]) { keccak_permute_host(state12); }
+int starkhip_keccak_state_from_words(const uint64_t* words, size_t n, uint64_t state12[12]) {
+    if (!words || !state12) return -1;
+    int used = 0;
+    const int have = keccak_take_words(words, (int)std::min<size_t>(n, 1u << 20), state12, 0, &used);
+    return have == 12 ? used : -1;
+}
+int starkhip_keccak_permute_batch(void* ctx, uint64_t* states, size_t n) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    return keccak_permute_batch((Ctx*)ctx, states, n);
+}
+int starkhip_merkle_tree_hasher(void* ctx, int hasher, const uint64_t* lde_colmajor, size_t n_cols, unsigned log_N, unsigned cap_height,
+                                uint64_t* digests_out, uint64_t* cap_out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    return merkle_tree_hasher((Ctx*)ctx, hasher, lde_colmajor, n_cols, log_N, cap_height, digests_out, cap_out);
+}
+int starkhip_hash_rows_hasher(void* ctx, int hasher, const uint64_t* rows, size_t width, size_t n_leaves, uint64_t* digests_out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    return hash_rows_hasher((Ctx*)ctx, hasher, rows, width, n_leaves, digests_out);
+}
+int starkhip_proof_hasher(const uint64_t* proof, size_t proof_words) {
+    ProofLayout pl;
+    if (!proof || !pl.read_header(proof, proof_words)) return STARKHIP_ERR_BAD_SHAPE;
+    return (int)pl.hasher;
+}
 /* n chained permutations with the challenger's host permutation (which = 0) or the portable reference loop (which = 1);
  * lets the tests compare the two and the benchmark report the host hashing rate */
 void starkhip_poseidon_permute_host_many(uint64_t state[12], size_t n, int which) {

@@ -125,6 +125,7 @@ struct Ctx {
     Tables* tab = nullptr;    // the current shape's (ensure_tables)
     PlanDev* plan = nullptr;  // the current AIR's (ensure_plan)
     long opt_leaf_hash_form = FORM_AUTO;  // a LeafHashForm (kernels.h).  0: a lone context's commitments: row form for <= 4096 leaves, pair form for >= 32 768, quad form between; 1: quad always; 2: row always; 3: lane always; 4: pair always
+    long opt_hasher = 0;             // STARKHIP_HASHER_POSEIDON / _KECCAK: the hash of this context's commitments, Merkle trees, proof of work and transcript
     long opt_lde_impl = 0;           // 0: 8192-row traces take lde_columns_wave_kernel; 1: lde_columns_v2_kernel for every shape (the cross-check)
     long opt_lde_closed_forms = 1;   // constant / unit-vector columns skip their transforms (kernels_lde.hip); 0: every column is transformed
     long opt_host_commit_leaves = 64; // trace commitments of at most this many leaves (and >= 64 columns) are hashed by host threads (0: never)

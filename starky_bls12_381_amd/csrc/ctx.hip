@@ -372,6 +372,7 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
     else if (k == "quotient_cosets" && (value == 0 || value == 1)) c->opt_quotient_cosets = value;
     else if (k == "quotient_chunks" && value >= 0 && value <= 4096) c->opt_quotient_chunks = value;  // plans are cached by (AIR, chunks)
     else if (k == "verify_chunk_mb" && value >= 1) c->opt_verify_chunk_mb = value;
+    else if (k == "hasher" && value >= STARKHIP_HASHER_POSEIDON && value <= STARKHIP_HASHER_KECCAK) c->opt_hasher = value;
     else if (k == "check_trace" && (value == 0 || value == 1)) c->opt_check_trace = value;
     else if (k == "check_trace_list" && value >= 0 && value <= (long)STARKHIP_CHECK_LIST_MAX) c->opt_check_trace_list = value;
     else return STARKHIP_ERR_BAD_SHAPE;
@@ -381,6 +382,7 @@ void ctx_set_check_trace(Ctx* c, bool on, size_t list_cap) {
     c->opt_check_trace = on;
     c->opt_check_trace_list = (long)std::min<size_t>(list_cap, STARKHIP_CHECK_LIST_MAX);
 }
+void ctx_set_hasher(Ctx* c, int hasher) { c->opt_hasher = hasher; }
 void ctx_check_stats(Ctx* c, uint64_t out[2]) {
     out[0] = c->traces_checked.load();
     out[1] = c->traces_rejected.load();

@@ -73,6 +73,7 @@ void ctx_hash_request_reset(Ctx* c) { c->hash_requested = false; }
 bool ctx_hash_requested(Ctx* c) { return c->hash_requested; }
 int ctx_set_urgent(Ctx* c, bool urgent) { c->urgent = urgent; return STARKHIP_OK; }
 void ctx_set_check_trace(Ctx* c, bool on, size_t) { c->check_trace = on; }  // the pretended check finds every trace satisfying
+void ctx_set_hasher(Ctx*, int) {}
 void ctx_check_stats(Ctx* c, uint64_t out[2]) { out[0] = c->traces_checked.load(); out[1] = 0; }
 int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t&, size_t, unsigned proof_blobs, bool) {
     if (proof_blobs && !c->blob_airs.count(air.id)) {  // the fake proofs are tiny; what is exercised is the arena's bookkeeping
@@ -116,6 +117,9 @@ int ntt_long(Ctx*, uint64_t*, size_t, unsigned, int) { return STARKHIP_ERR_NO_DE
 int merkle_cap(Ctx*, const uint64_t*, size_t, unsigned, unsigned, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int permute_batch(Ctx*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int permute_batch_form(Ctx*, int, int, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
+int keccak_permute_batch(Ctx*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
+int merkle_tree_hasher(Ctx*, int, const uint64_t*, size_t, unsigned, unsigned, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
+int hash_rows_hasher(Ctx*, int, const uint64_t*, size_t, size_t, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int leaf_hash_lane_group(Ctx*, const uint64_t*, size_t, size_t, unsigned, unsigned, int, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int expand_log(Ctx*, const TraceLog*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int check_trace(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
@@ -154,6 +158,18 @@ hipError_t launch_leaf_hash_lane_group(const LeafHashBatch& B, unsigned count, s
     g_fake_lane_members += count;
     return hipSuccess;
 }
+// the Keccak hasher's launches (kernels_keccak.hip): no host code calls them -- a pretended proof hashes nothing -- and the device
+// verifier's Keccak leaves go through launch_verify_leaf_digests below, on the host
+hipError_t launch_leaf_hash_keccak(const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_leaf_hash_rows_keccak(const gl_t*, size_t, size_t, gl_t*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_merkle_levels_keccak(gl_t*, unsigned, unsigned, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_permute_batch_keccak(gl_t*, size_t, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_pow_grind_keccak(const gl_t*, int, unsigned, uint64_t, uint64_t, unsigned long long*, hipStream_t) { return hipErrorNoDevice; }
+hipError_t launch_verify_leaf_digests_keccak(const gl_t* words, const VQLeaf* leaves, size_t n, gl_t* digests, hipStream_t) {
+    if (!fake_device()) return hipErrorNoDevice;
+    verify_host_leaf_digests(words, leaves, n, digests);
+    return hipSuccess;
+}
 // the device verifier's launches (verifier_device.cpp, verify_service.cpp): with the pretended device, their routine on the host --
 // the same code as starkhip_verify_batch_replay's (verify_query.h, the host permutation) on the "device" buffers, which are host memory
 // here, so that a CPU build of the pool gives real verdicts; without it, no device
@@ -162,7 +178,7 @@ hipError_t launch_ext_powers(gl2_t* out, gl2_t alpha, size_t n, hipStream_t) {
     verify_host_ext_powers(out, alpha, n);
     return hipSuccess;
 }
-hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n, gl_t* digests, hipStream_t) {
+hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n, gl_t* digests, unsigned, hipStream_t) {
     if (!fake_device()) return hipErrorNoDevice;
     verify_host_leaf_digests(words, leaves, n, digests);
     return hipSuccess;

@@ -160,6 +160,53 @@ int permute_batch(Ctx* c, uint64_t* states, size_t n) {
     return STARKHIP_OK;
 }
 
+// the Keccak hasher's challenger permutation (keccak.h: K7) on whole states
+int keccak_permute_batch(Ctx* c, uint64_t* states, size_t n) {
+    if (n == 0) return STARKHIP_OK;
+    if (!states) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->staging.ensure(n * 96));
+    HIPCHK(hipMemcpyAsync(c->staging.p, states, n * 96, hipMemcpyHostToDevice, c->st));
+    HIPCHK(launch_permute_batch_keccak(c->staging.as<gl_t>(), n, c->st));
+    HIPCHK(hipMemcpyAsync(states, c->staging.p, n * 96, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+// merkle_cap under either hasher, with the leaf digests: hasher 0 takes the leaf-hash form a lone proof would, hasher 1 the Keccak kernel
+int merkle_tree_hasher(Ctx* c, int hasher, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* digests_out, uint64_t* cap_out) {
+    if (hasher < STARKHIP_HASHER_POSEIDON || hasher > STARKHIP_HASHER_KECCAK || !lde_natural || !cap_out || !n_cols || log_N < cap_h || log_N > 28)
+        return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t N = (size_t)1 << log_N;
+    HIPCHK(c->lde.ensure(n_cols * N * 8));  // rate_bits = 0: coset-major == natural
+    HIPCHK(c->digests.ensure(digest_words(N) * 8));
+    HIPCHK(hipMemcpyAsync(c->lde.p, lde_natural, n_cols * N * 8, hipMemcpyHostToDevice, c->st));
+    int form;
+    if (hasher == STARKHIP_HASHER_KECCAK) HIPCHK(launch_leaf_hash_keccak(c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st));
+    else HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), n_cols, log_N, 0, c->digests.as<gl_t>(), c->st, &form));
+    HIPCHK(launch_merkle_levels_by(hasher, c->digests.as<gl_t>(), log_N, cap_h, c->st));
+    if (digests_out) HIPCHK(hipMemcpyAsync(digests_out, c->digests.p, 4 * N * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(cap_out, c->digests.as<gl_t>() + 4 * level_off(N, log_N - cap_h), ((size_t)4 << cap_h) * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+int hash_rows_hasher(Ctx* c, int hasher, const uint64_t* rows, size_t width, size_t n_leaves, uint64_t* digests_out) {
+    if (hasher < STARKHIP_HASHER_POSEIDON || hasher > STARKHIP_HASHER_KECCAK || !rows || !digests_out || !width || !n_leaves || width > ((size_t)1 << 24) ||
+        n_leaves > ((size_t)1 << 28))
+        return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->staging.ensure((width + 4) * n_leaves * 8));
+    gl_t* d_rows = c->staging.as<gl_t>();
+    gl_t* d_dig = d_rows + width * n_leaves;
+    HIPCHK(hipMemcpyAsync(d_rows, rows, width * n_leaves * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(launch_leaf_hash_rows_by(hasher, d_rows, width, n_leaves, d_dig, c->st));
+    HIPCHK(hipMemcpyAsync(digests_out, d_dig, 4 * n_leaves * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
 // the permutation of one leaf-hash form on whole states (kernels_hash.hip: the test entry points); a bad form or variant launches nothing
 int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n) {
     if (variant < 0 || (unsigned)variant >= permute_form_variants(form)) return STARKHIP_ERR_BAD_SHAPE;

@@ -107,6 +107,7 @@ enum LeafHashSent : int {
     SENT_LANE = 3,
     SENT_HOST = 4,    // hashed by host threads
     SENT_PAIR = 5,
+    SENT_KECCAK = 6,  // the Keccak hasher's leaf hash (kernels_keccak.hip), always the context's own launch
 };
 // what a lone launch of `form` (not FORM_AUTO) is reported as
 inline LeafHashSent leaf_hash_sent(LeafHashForm form) {
@@ -134,6 +135,20 @@ hipError_t launch_permute_quad_form(bool cap_only, const gl_t* in, gl_t* out, si
 hipError_t launch_permute_batch_form(int form, int variant, const gl_t* in, gl_t* out, size_t n, hipStream_t st);
 hipError_t launch_pow_grind(const gl_t* base_state, int pos, unsigned pow_bits, uint64_t start, uint64_t count, unsigned long long* best,
                             hipStream_t st);
+// kernels_keccak.hip: the Keccak hasher's counterparts of the launches above (keccak.h) -- one lane per hash, the same digest slots
+hipError_t launch_leaf_hash_keccak(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st);
+hipError_t launch_leaf_hash_rows_keccak(const gl_t* rows, size_t width, size_t n_leaves, gl_t* digests, hipStream_t st);
+hipError_t launch_merkle_levels_keccak(gl_t* digests, unsigned log_leaves, unsigned cap_h, hipStream_t st);
+hipError_t launch_permute_batch_keccak(gl_t* states, size_t n, hipStream_t st);
+hipError_t launch_pow_grind_keccak(const gl_t* base_state, int pos, unsigned pow_bits, uint64_t start, uint64_t count, unsigned long long* best,
+                                   hipStream_t st);
+// by hasher id (starkhip.h: 0 Poseidon, 1 Keccak), where a proof's phases pick
+inline hipError_t launch_leaf_hash_rows_by(int hasher, const gl_t* rows, size_t width, size_t n_leaves, gl_t* digests, hipStream_t st) {
+    return hasher ? launch_leaf_hash_rows_keccak(rows, width, n_leaves, digests, st) : launch_leaf_hash_rows(rows, width, n_leaves, digests, st);
+}
+inline hipError_t launch_merkle_levels_by(int hasher, gl_t* digests, unsigned log_leaves, unsigned cap_h, hipStream_t st) {
+    return hasher ? launch_merkle_levels_keccak(digests, log_leaves, cap_h, st) : launch_merkle_levels(digests, log_leaves, cap_h, st);
+}
 // kernels_selftest.hip
 hipError_t launch_field_ops(int op, const gl_t* a, const gl_t* b, gl_t* out, size_t n, hipStream_t st);
 
@@ -214,7 +229,9 @@ hipError_t launch_query_path(const gl_t* digests, size_t n_leaves, unsigned dept
 
 // device verifier (verifier_device.cpp): the row-form digests of opened leaves (kernels_hash.hip), then kernels_verify.hip's range check
 // of the query sections (bad[p] |= 1), fri_combine_initial's sums (two per query) and the per-query checks (one status word per query)
-hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, hipStream_t st);
+// (hashers: bit h set when some leaf of the list belongs to a proof of hasher h; each hasher's kernel walks the list and takes its own)
+hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, unsigned hashers, hipStream_t st);
+hipError_t launch_verify_leaf_digests_keccak(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, hipStream_t st);
 hipError_t launch_verify_range(const gl_t* words, const VQProof* proofs, size_t n_proofs, uint32_t* bad, hipStream_t st);
 hipError_t launch_verify_combine(const gl_t* words, const VQProof* proofs, const uint32_t* query_proof, size_t n_queries, const gl2_t* apow,
                                  gl2_t* sums, hipStream_t st);

@@ -203,6 +203,7 @@ __global__ __launch_bounds__(256) void verify_leaf_digest_kernel(const gl_t* __r
     const size_t q = tid >> 4;
     if (q >= n_leaves) return;  // whole rows drop out together
     const VQLeaf lf = leaves[q];
+    if (lf.hasher != STARKHIP_HASHER_POSEIDON) return;  // another hasher's leaf: its own kernel takes it (kernels_keccak.hip)
     const gl_t* in = words + lf.off;
     gl_t* out = digests + 4 * (size_t)lf.slot;
     if (lf.len <= 4) {  // hash_or_noop: short leaves are copied, zero padded
@@ -591,11 +592,15 @@ hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_co
     }
     return hipGetLastError();
 }
-hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, hipStream_t st) {
+hipError_t launch_verify_leaf_digests(const gl_t* words, const VQLeaf* leaves, size_t n_leaves, gl_t* digests, unsigned hashers, hipStream_t st) {
     if (!n_leaves) return hipSuccess;
-    if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(verify_leaf_digest_kernel, dim3(nblocks(16 * n_leaves, 256)), dim3(256), 0, st, words, leaves, n_leaves, digests);
-    return hipGetLastError();
+    if (hashers & (1u << STARKHIP_HASHER_POSEIDON)) {
+        if (hipError_t e = ensure_row_merged_tables(); e != hipSuccess) return e;
+        hipLaunchKernelGGL(verify_leaf_digest_kernel, dim3(nblocks(16 * n_leaves, 256)), dim3(256), 0, st, words, leaves, n_leaves, digests);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    if (hashers & (1u << STARKHIP_HASHER_KECCAK)) return launch_verify_leaf_digests_keccak(words, leaves, n_leaves, digests, st);
+    return hipSuccess;
 }
 hipError_t launch_leaf_hash_multi(const LeafHashBatch& B, unsigned count, size_t n_cols, unsigned log_n, unsigned rate_bits, hipStream_t st) {
     if (count == 0 || count > LEAF_HASH_MAX_BATCH) return hipErrorInvalidValue;

@@ -61,6 +61,7 @@ struct Pool {
     unsigned long verified_proofs = 0, verify_jobs = 0;  // under mu
     bool check_traces = false;    // under mu
     size_t check_trace_list = 16; // under mu
+    int hasher = 0;               // under mu: "hasher", read at submit
     double vload = 0;       // sum of air_verify_cost over the verify jobs that are not done (under mu)
     std::map<int, int> idle_big, idle_small;                 // idle contexts by the AIR they proved last (under mu)
     unsigned stream_priority = 0;
@@ -223,11 +224,12 @@ struct Pool {
     // one proof on context `c` between its hand-overs to the commitment scheduler; leaves the timings in the job and frees its recording
     int prove_job(Ctx* c, Job* j, bool big, bool announce_big) {
         int rc;
-        const bool announce = !big && ctx_has_hash_service(c);
+        const bool announce = !big && ctx_has_hash_service(c) && j->hasher == STARKHIP_HASHER_POSEIDON;
         if (announce) hs->announce_small();
         ctx_hash_request_reset(c);
         const uint64_t cpu0 = thread_cpu_ns();
         ctx_set_check_trace(c, j->check, j->check_list);
+        ctx_set_hasher(c, j->hasher);
         try {
             const AirInfo* a = air_get(j->air);
             rc = prove(c, *a, j->cfg, j->in, j->pis, j->n_pis, j->pow, &j->proof, &j->words);
@@ -298,7 +300,7 @@ struct Pool {
                 urgent = big && stream_priority == 1 && q.size() + big_in_gen < big_ctx.size();
                 // announced BEFORE it stops counting as queued: between the two a waiting lane group would see nobody on the way
                 // and go out short, and this proof's commitment would follow it alone
-                announce_big = big && ctx_has_hash_service(c);
+                announce_big = big && ctx_has_hash_service(c) && j->hasher == STARKHIP_HASHER_POSEIDON;
                 if (announce_big) hs->announce_big();
                 if (big) tell_big_queued();
             }
@@ -441,6 +443,7 @@ static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     j->verify = p->verify_proofs;
     j->check = p->check_traces;
     j->check_list = p->check_trace_list;
+    j->hasher = p->hasher;
     j->cost = air_cost(j->air);
     p->load += j->cost;
     if (j->big) p->big_open++;
@@ -585,6 +588,12 @@ int pool_set_option(Pool* p, const char* name, long value) {
         std::lock_guard<std::mutex> g(p->mu);
         if (list) p->check_trace_list = (size_t)value;
         else p->check_traces = value == 1;
+        return STARKHIP_OK;
+    }
+    if (strcmp(name, "hasher") == 0) {  // read at submit too
+        if (value < STARKHIP_HASHER_POSEIDON || value > STARKHIP_HASHER_KECCAK) return STARKHIP_ERR_BAD_SHAPE;
+        std::lock_guard<std::mutex> g(p->mu);
+        p->hasher = (int)value;
         return STARKHIP_OK;
     }
     if (strcmp(name, "verify_arena_mb") == 0) {

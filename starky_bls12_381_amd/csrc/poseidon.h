@@ -4,6 +4,7 @@
 // `type C = PoseidonGoldilocksConfig` at /root/reference/src/aggregate_proof.rs:236.
 #pragma once
 #include "gl.h"
+#include "keccak.h"
 #include "poseidon_consts.h"
 
 namespace starkhip {
@@ -140,22 +141,27 @@ GL_HD void poseidon_hash_or_noop(const gl_t* in, size_t len, size_t stride, gl_t
 void poseidon_permute_host(gl_t* s);
 
 // ---------------------------------------------------------------- Challenger (host only)
+// Parametrised by the permutation: `hasher` 0 duplexes through Poseidon, 1 through the Keccak hasher's permutation (keccak.h, COMPAT.md
+// K7).  Rate 8, the overwriting of inputs and the pop from the end of the output buffer are the same for both (K8).
 struct Challenger {
+    int hasher = 0;
     gl_t state[12];
     gl_t in[8];
     int n_in;
     gl_t out[8];
     int n_out;
-    Challenger() : n_in(0), n_out(0) {
+    Challenger(int hasher_id = 0) : hasher(hasher_id), n_in(0), n_out(0) {
         for (int i = 0; i < 12; i++) state[i] = 0;
     }
     void duplex() {
         for (int i = 0; i < n_in; i++) state[i] = in[i];
         n_in = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
-        poseidon_permute(state);
+        if (hasher) keccak_permute(state);
+        else poseidon_permute(state);
 #else
-        poseidon_permute_host(state);
+        if (hasher) keccak_permute_host(state);
+        else poseidon_permute_host(state);
 #endif
         for (int i = 0; i < 8; i++) out[i] = state[i];
         n_out = 8;

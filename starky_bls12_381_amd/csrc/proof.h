@@ -55,6 +55,7 @@ inline unsigned quotient_degree_bits(unsigned degree) {
 
 struct ProofLayout {
     size_t C, Q, log_n, rate_bits, cap_h, L, n_queries, final_len, n_pis, arity_bits, n_challenges;
+    size_t hasher = 0;  // header word 12: STARKHIP_HASHER_POSEIDON (0, what the word has always been) or STARKHIP_HASHER_KECCAK
     size_t ncap;     // 2^cap_h
     size_t log_N;
     // offsets (in words)
@@ -63,8 +64,9 @@ struct ProofLayout {
     std::vector<size_t> layer_depth;  // siblings per FRI layer
 
     // the layout of a proof of AIR program `P` with 2^log_n rows under `cfg` (`geo`: FriGeometry::make(cfg, log_n))
-    static ProofLayout make(const AirProgram& P, const starkhip_config_t& cfg, const FriGeometry& geo, unsigned log_n) {
+    static ProofLayout make(const AirProgram& P, const starkhip_config_t& cfg, const FriGeometry& geo, unsigned log_n, unsigned hasher = 0) {
         ProofLayout pl;
+        pl.hasher = hasher;
         pl.C = P.n_cols; pl.Q = (size_t)quotient_factor(P.degree) * 2; pl.log_n = log_n; pl.rate_bits = cfg.rate_bits; pl.cap_h = cfg.cap_height;
         pl.L = geo.arities.size(); pl.n_queries = cfg.num_query_rounds; pl.final_len = geo.final_poly_len; pl.n_pis = P.n_pis;
         pl.arity_bits = cfg.arity_bits; pl.n_challenges = 2;
@@ -101,12 +103,14 @@ struct ProofLayout {
     void write_header(uint64_t* h) const {
         h[0] = STARKHIP_PROOF_MAGIC; h[1] = C; h[2] = Q; h[3] = log_n; h[4] = rate_bits; h[5] = cap_h; h[6] = L;
         h[7] = n_queries; h[8] = final_len; h[9] = n_pis; h[10] = arity_bits; h[11] = n_challenges;
-        h[12] = h[13] = h[14] = h[15] = 0;
+        h[12] = hasher;
+        h[13] = h[14] = h[15] = 0;
     }
     bool read_header(const uint64_t* h, size_t words) {
         if (words < 16 || h[0] != STARKHIP_PROOF_MAGIC) return false;
         C = h[1]; Q = h[2]; log_n = h[3]; rate_bits = h[4]; cap_h = h[5]; L = h[6]; n_queries = h[7]; final_len = h[8];
-        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11];
+        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11]; hasher = h[12];
+        if (hasher > STARKHIP_HASHER_KECCAK) return false;
         if (log_n > 32 || rate_bits > 8 || cap_h > 16 || L > 16 || arity_bits > 8 || log_n + rate_bits < cap_h) return false;
         if (L * arity_bits + cap_h > log_n + rate_bits) return false;
         compute();

@@ -23,6 +23,7 @@ bool ctx_has_hash_service(Ctx* c);
 int ctx_set_urgent(Ctx* c, bool urgent);
 // "check_trace" and "check_trace_list" of the context's next proofs, as a pool sets them per job; {traces checked, traces rejected} so far
 void ctx_set_check_trace(Ctx* c, bool on, size_t list_cap);
+void ctx_set_hasher(Ctx* c, int hasher);  // the "hasher" option of the context's next proofs, as a pool sets it per job
 void ctx_check_stats(Ctx* c, uint64_t out[2]);
 // tables, plan, work buffers, upload staging and `proof_blobs` page-locked proof blobs (blob_arena.h) for proofs of `air`,
 // allocated now (a pool's warm-up)
@@ -90,6 +91,11 @@ int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int invers
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out);
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);
 int permute_batch(Ctx* c, uint64_t* states, size_t n);
+int keccak_permute_batch(Ctx* c, uint64_t* states, size_t n);
+// Merkle tree of an LDE given column-major in natural order under `hasher`: leaf digests in tree order (may be NULL) and the cap
+int merkle_tree_hasher(Ctx* c, int hasher, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* digests_out, uint64_t* cap_out);
+// digests of n_leaves row-major leaves of `width` words under `hasher`
+int hash_rows_hasher(Ctx* c, int hasher, const uint64_t* rows, size_t width, size_t n_leaves, uint64_t* digests_out);
 int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n);
 int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped, uint64_t* digests_out);
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor);

@@ -321,7 +321,14 @@ int ProveCall::leaf_hash_on_host() {
 // ---- phase 2: Merkle tree over bit-reversed LDE rows
 int ProveCall::trace_merkle() {
     HIPCHK(hipEventRecord(c->kev[0], st));
-    if (s.N <= (size_t)c->opt_host_commit_leaves && s.C >= 64 && c->opt_leaf_hash_form == FORM_AUTO) {
+    if (c->opt_hasher == STARKHIP_HASHER_KECCAK) {
+        // The Keccak leaf hash is the context's own launch on its own stream, pooled or not: the pool's merged and lane-group launches are
+        // Poseidon forms (its jobs of this hasher are not announced to the scheduler either: pool.cpp), and "leaf_hash_form" and
+        // "host_commit_leaves" pick among Poseidon forms
+        c->hash_timing.form = SENT_KECCAK;
+        c->hash_timing.group = 1;
+        HIPCHK(launch_leaf_hash_keccak(c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st));
+    } else if (s.N <= (size_t)c->opt_host_commit_leaves && s.C >= 64 && c->opt_leaf_hash_form == FORM_AUTO) {
         if (int rc = leaf_hash_on_host()) return rc;
     } else if (c->hs) {  // pooled: the scheduler decides when this commitment runs and which others share its launch
         c->hash_requested = true;
@@ -332,7 +339,7 @@ int ProveCall::trace_merkle() {
         HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st, &c->hash_timing.form));
     }
     HIPCHK(hipEventRecord(c->kev[1], st));
-    HIPCHK(launch_merkle_levels(c->digests.as<gl_t>(), s.log_N, s.cap_h, st));
+    HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, c->digests.as<gl_t>(), s.log_N, s.cap_h, st));
     trace_cap.resize(4 * s.ncap);
     HIPCHK(read_back(c, trace_cap.data(), c->digests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
     return 0;
@@ -454,8 +461,9 @@ int ProveCall::quotient_commit() {
     for (gl_t v : quot_tail)
         if (v != 0) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
     HIPCHK(run_lde(c, c->qcoef.as<gl_t>(), nullptr, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, 1));
-    HIPCHK(launch_leaf_hash_form(FORM_QUAD, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
-    HIPCHK(launch_merkle_levels(c->qdigests.as<gl_t>(), s.log_N, s.cap_h, st));
+    if (c->opt_hasher == STARKHIP_HASHER_KECCAK) HIPCHK(launch_leaf_hash_keccak(c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
+    else HIPCHK(launch_leaf_hash_form(FORM_QUAD, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
+    HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, c->qdigests.as<gl_t>(), s.log_N, s.cap_h, st));
     quot_cap.resize(4 * s.ncap);
     HIPCHK(read_back(c, quot_cap.data(), c->qdigests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
     return 0;
@@ -561,8 +569,8 @@ int ProveCall::fri_commit() {
         const unsigned ab = s.geo.arities[l];
         const size_t n_leaves = len >> ab, width = 2 << ab;
         HIPCHK(launch_fri_leaves(vals, log_len, ab, c->fri_rows[l].as<gl_t>(), st));
-        HIPCHK(launch_leaf_hash_rows(c->fri_rows[l].as<gl_t>(), width, n_leaves, c->fri_digests[l].as<gl_t>(), st));
-        HIPCHK(launch_merkle_levels(c->fri_digests[l].as<gl_t>(), log_len - ab, s.cap_h, st));
+        HIPCHK(launch_leaf_hash_rows_by((int)c->opt_hasher, c->fri_rows[l].as<gl_t>(), width, n_leaves, c->fri_digests[l].as<gl_t>(), st));
+        HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, c->fri_digests[l].as<gl_t>(), log_len - ab, s.cap_h, st));
         // leaves and digests stay on the device (the query phase gathers from them); only the cap feeds the transcript
         gl_t* cap = fri_caps.data() + l * 4 * ncap;
         HIPCHK(read_back(c, cap, c->fri_digests[l].as<gl_t>() + 4 * level_off(n_leaves, log_len - ab - s.cap_h), 4 * ncap * 8, st));
@@ -609,7 +617,10 @@ int ProveCall::pow() {
             for (uint64_t start = 0; best == ~0ULL; start += batch) {
                 if (start >= GL_P - batch) return STARKHIP_ERR_HIP;
                 HIPCHK(hipMemcpyAsync(c->pow_best.p, &best, 8, hipMemcpyHostToDevice, st));
-                HIPCHK(launch_pow_grind(c->pow_state.as<gl_t>(), ch.n_in, cfg.proof_of_work_bits, start, batch, c->pow_best.as<unsigned long long>(), st));
+                if (c->opt_hasher == STARKHIP_HASHER_KECCAK)
+                    HIPCHK(launch_pow_grind_keccak(c->pow_state.as<gl_t>(), ch.n_in, cfg.proof_of_work_bits, start, batch, c->pow_best.as<unsigned long long>(), st));
+                else
+                    HIPCHK(launch_pow_grind(c->pow_state.as<gl_t>(), ch.n_in, cfg.proof_of_work_bits, start, batch, c->pow_best.as<unsigned long long>(), st));
                 HIPCHK(read_back(c, &best, c->pow_best.p, 8, st));
                 HIPCHK(stream_wait(c));
             }
@@ -699,6 +710,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     } read_back_guard{c};
     ProofShape s;
     if (n_pis != air.prog.n_pis || in.n_cols != air.prog.n_cols || ProofShape::make(air, cfg, in.n_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
+    s.pl.hasher = (size_t)c->opt_hasher;  // header word 12
     for (size_t i = 0; i < n_pis; i++)
         if (pis_host[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
@@ -727,6 +739,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
 
     ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde,
                 trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()};
+    p.ch.hasher = (int)c->opt_hasher;  // the transcript's sponge duplexes through the context's hasher
     // before each phase: the boundary event of starkhip_last_timings on the stream and the phase's rocTX range (rocprofv3 --marker-trace)
     static const struct { const char* range; int (ProveCall::*run)(); } PHASES[STARKHIP_N_PHASES - 1] = {
         {"starkhip:upload", &ProveCall::upload}, {"starkhip:ifft_lde", &ProveCall::ifft_lde}, {"starkhip:trace_merkle", &ProveCall::trace_merkle},
@@ -763,7 +776,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     (void)hipEventElapsedTime(&c->ktimings[0], c->kev[4], c->kev[5]);
     // pooled: the commitment kernel's own duration on the scheduler's launch stream (kev[0] .. kev[1] on this context's stream would
     // include the wait for its group to form)
-    if (c->hs && c->hash_timing.form != SENT_HOST) (void)hipEventElapsedTime(&c->ktimings[1], c->hash_timing.t0, c->hash_timing.t1);
+    if (c->hs && c->hash_timing.form != SENT_HOST && c->hash_timing.form != SENT_KECCAK) (void)hipEventElapsedTime(&c->ktimings[1], c->hash_timing.t0, c->hash_timing.t1);
     else (void)hipEventElapsedTime(&c->ktimings[1], c->kev[0], c->kev[1]);
     *proof_out = out;
     *proof_words = s.pl.total;

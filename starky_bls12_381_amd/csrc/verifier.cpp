@@ -18,13 +18,21 @@
 
 namespace starkhip {
 
-static bool merkle_verify_to_cap(const gl_t* leaf, size_t leaf_len, size_t index, const gl_t* cap, const gl_t* siblings, size_t depth) {
+// under the proof's hasher; a Keccak sibling whose words are outside a digest's ranges (COMPAT.md K6) fails the path
+static bool merkle_verify_to_cap(size_t hasher, const gl_t* leaf, size_t leaf_len, size_t index, const gl_t* cap, const gl_t* siblings, size_t depth) {
+    const bool keccak = hasher == STARKHIP_HASHER_KECCAK;
     gl_t cur[4];
-    poseidon_hash_or_noop(leaf, leaf_len, 1, cur);
+    if (keccak) keccak_hash_or_noop(leaf, leaf_len, 1, cur);
+    else poseidon_hash_or_noop(leaf, leaf_len, 1, cur);
     for (size_t d = 0; d < depth; d++) {
         gl_t nxt[4];
-        if (index & 1) poseidon_two_to_one(siblings + 4 * d, cur, nxt);
-        else poseidon_two_to_one(cur, siblings + 4 * d, nxt);
+        const gl_t* sib = siblings + 4 * d;
+        if (keccak) {
+            if (!keccak_digest_in_range(sib)) return false;
+            if (index & 1) keccak_two_to_one(sib, cur, nxt);
+            else keccak_two_to_one(cur, sib, nxt);
+        } else if (index & 1) poseidon_two_to_one(sib, cur, nxt);
+        else poseidon_two_to_one(cur, sib, nxt);
         memcpy(cur, nxt, sizeof cur);
         index >>= 1;
     }
@@ -84,6 +92,12 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     for (size_t i = skip_hi; i < words; i++)
         if (proof[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     if (geo.arities.size() != pl.L || geo.final_poly_len != pl.final_len) return STARKHIP_ERR_BAD_SHAPE;
+    if (pl.hasher == STARKHIP_HASHER_KECCAK) {  // K6: a cap entry outside a digest's ranges is not the encoding of any 25 bytes
+        for (size_t i = 0; i < 2 * pl.ncap; i++)
+            if (!keccak_digest_in_range(proof + pl.off_trace_cap + 4 * i)) return STARKHIP_ERR_VERIFY;
+        for (size_t i = 0; i < pl.L * pl.ncap; i++)
+            if (!keccak_digest_in_range(proof + pl.off_fri_caps + 4 * i)) return STARKHIP_ERR_VERIFY;
+    }
 
     const size_t C = pl.C, Q = pl.Q, n = (size_t)1 << pl.log_n, N = (size_t)1 << pl.log_N, ncap = pl.ncap;
     const gl2_t* op_local = (const gl2_t*)(proof + pl.off_local);
@@ -93,7 +107,7 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     const gl_t* pis = proof + pl.off_pis;
 
     // ---- challenges, in transcript order (App. A.5)
-    Challenger ch;
+    Challenger ch((int)pl.hasher);  // the hasher the header names: the sponge's permutation, and proof of work through it
     ch.observe_many(proof + pl.off_trace_cap, 4 * ncap);
     std::vector<gl2_t> alphas(cfg.num_challenges);
     for (auto& a : alphas) a = gl2_from_base(ch.get());
@@ -170,8 +184,8 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
         const gl_t* tsib = qp; qp += 4 * d0;
         const gl_t* qleaf = qp; qp += Q;
         const gl_t* qsib = qp; qp += 4 * d0;
-        if (!merkle_verify_to_cap(tleaf, C, x_index, proof + pl.off_trace_cap, tsib, d0)) return false;
-        if (!merkle_verify_to_cap(qleaf, Q, x_index, proof + pl.off_quot_cap, qsib, d0)) return false;
+        if (!merkle_verify_to_cap(pl.hasher, tleaf, C, x_index, proof + pl.off_trace_cap, tsib, d0)) return false;
+        if (!merkle_verify_to_cap(pl.hasher, qleaf, Q, x_index, proof + pl.off_quot_cap, qsib, d0)) return false;
         gl_t subgroup_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity((unsigned)pl.log_N), gl_bitrev((uint32_t)x_index, (unsigned)pl.log_N)));
         // fri_combine_initial
         gl2_t e0 = gl2_zero(), e1 = gl2_zero();
@@ -190,7 +204,7 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
             size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
             if (!gl2_eq(evals[within], old_eval)) return false;
             old_eval = fri_fold_eval(subgroup_x, within, ab, evals, betas[l]);
-            if (!merkle_verify_to_cap((const gl_t*)evals, 2 * arity, coset_index, proof + pl.off_fri_caps + l * 4 * ncap, sib, pl.layer_depth[l]))
+            if (!merkle_verify_to_cap(pl.hasher, (const gl_t*)evals, 2 * arity, coset_index, proof + pl.off_fri_caps + l * 4 * ncap, sib, pl.layer_depth[l]))
                 return false;
             for (unsigned b = 0; b < ab; b++) subgroup_x = gl_sqr(subgroup_x);
             x_index = coset_index;

@@ -88,6 +88,8 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     P.final_len = (uint32_t)pl.final_len;
     P.first_query = (uint32_t)ch.query_proof.size();
     P.first_digest = (uint32_t)ch.digests;
+    P.hasher = (uint32_t)pl.hasher;
+    ch.hashers |= 1u << P.hasher;
     for (size_t l = 0; l < pl.L; l++) {
         P.arity_bits[l] = pre.geo.arities[l];
         P.layer_depth[l] = (uint32_t)pl.layer_depth[l];
@@ -102,13 +104,13 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     for (size_t q = 0; q < pl.n_queries; q++) {
         const uint32_t slot = (uint32_t)(ch.digests + q * per_q);
         size_t o = P.base + P.off_queries + q * pl.query_words;
-        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.C, slot});
+        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.C, slot, P.hasher, 0});
         o += pl.C + 4 * d0;
-        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.Q, slot + 1});
+        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.Q, slot + 1, P.hasher, 0});
         o += pl.Q + 4 * d0;
         for (size_t l = 0; l < pl.L; l++) {
             const size_t arity = (size_t)1 << pre.geo.arities[l];
-            ch.leaves.push_back(VQLeaf{o, (uint32_t)(2 * arity), (uint32_t)(slot + 2 + l)});
+            ch.leaves.push_back(VQLeaf{o, (uint32_t)(2 * arity), (uint32_t)(slot + 2 + l), P.hasher, 0});
             o += 2 * arity + 4 * pl.layer_depth[l];
         }
         ch.query_proof.push_back((uint32_t)ch.proofs.size());
@@ -202,7 +204,7 @@ hipError_t verify_chunk_launch(const VerifyChunk& ch, const VerifyDevBufs& b, hi
         e = launch_ext_powers(b.apow + P.apow, ch.alphas[k], P.C + P.Q, st);
     }
     if (e == hipSuccess) e = launch_verify_range(b.words, b.proofs, ch.proofs.size(), b.bad, st);
-    if (e == hipSuccess) e = launch_verify_leaf_digests(b.words, b.leaves, ch.leaves.size(), b.dig, st);
+    if (e == hipSuccess) e = launch_verify_leaf_digests(b.words, b.leaves, ch.leaves.size(), b.dig, ch.hashers, st);
     if (e == hipSuccess) e = launch_verify_combine(b.words, b.proofs, b.qproof, ch.query_proof.size(), b.apow, b.sums, st);
     if (e == hipSuccess) e = launch_verify_queries(b.words, b.proofs, b.qproof, b.xidx, ch.query_proof.size(), b.dig, b.sums, b.status, st);
     return e;
@@ -234,6 +236,10 @@ void verify_host_leaf_digests(const gl_t* W, const VQLeaf* leaves, size_t n, gl_
         const VQLeaf& lf = leaves[k];
         gl_t* out = dig + 4 * (size_t)lf.slot;
         const gl_t* in = W + lf.off;
+        if (lf.hasher == STARKHIP_HASHER_KECCAK) {
+            keccak_hash_or_noop(in, lf.len, 1, out);
+            continue;
+        }
         if (lf.len <= 4) {
             for (uint32_t i = 0; i < 4; i++) out[i] = i < lf.len ? in[i] : 0;
             continue;

@@ -34,6 +34,7 @@ struct VerifyChunk {
     std::vector<uint64_t> x_index;
     std::vector<gl2_t> alphas;  // per proof: the FRI alpha
     size_t words = 0, apow = 0, digests = 0, bytes = 0;
+    unsigned hashers = 0;  // bit h: the chunk holds a proof of hasher h (which leaf-digest kernels run)
 };
 void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre);
 void verify_chunk_seal(VerifyChunk& ch);  // the leaves longest first

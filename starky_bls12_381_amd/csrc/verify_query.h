@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "gl.h"
+#include "keccak.h"
 #include "poseidon.h"
 #if defined(__HIPCC__)
 #include "poseidon_dev.h"
@@ -37,17 +38,23 @@ struct VQProof {
     uint32_t first_query;   // global index of query 0 (statuses, indices, sums)
     uint32_t first_digest;  // global slot of query 0's trace-leaf digest; query q's are first_digest + q (2 + L) + {0: trace, 1: quotient, 2 + l: layer l}
     uint32_t arity_bits[VQ_MAX_LAYERS], layer_depth[VQ_MAX_LAYERS];
+    uint32_t hasher;        // the proof's hasher id (header word 12): every Merkle path of its queries is checked under it
     gl2_t zeta, gzeta, red0, red1, alpha_pow_C;
     gl2_t betas[VQ_MAX_LAYERS];
 };
 
-// one opened leaf to hash: `len` words at `off` of the word buffer -> digest slot `slot`
+// one opened leaf to hash: `len` words at `off` of the word buffer -> digest slot `slot`, under its proof's hasher
 struct VQLeaf {
     uint64_t off;
     uint32_t len, slot;
+    uint32_t hasher, pad_;
 };
 
-GL_HD void vq_two_to_one(const gl_t* a, const gl_t* b, gl_t* out) {
+GL_HD void vq_two_to_one(uint32_t hasher, const gl_t* a, const gl_t* b, gl_t* out) {
+    if (hasher == STARKHIP_HASHER_KECCAK) {
+        keccak_two_to_one(a, b, out);
+        return;
+    }
 #if defined(__HIP_DEVICE_COMPILE__)
     poseidon_two_to_one_dev(a, b, out);
 #else
@@ -62,18 +69,27 @@ GL_HD void vq_two_to_one(const gl_t* a, const gl_t* b, gl_t* out) {
 #endif
 }
 
-// Merkle path from a leaf digest to the cap entry the remaining index selects
-GL_HD bool vq_path_to_cap(const gl_t* digest, uint64_t index, const gl_t* cap, const gl_t* siblings, uint32_t depth) {
+// Merkle path from a leaf digest to the cap entry the remaining index selects.  Under the Keccak hasher a sibling whose words are outside
+// a digest's ranges (COMPAT.md K6) fails the path: its 25 bytes would not be the words' own.
+GL_HD bool vq_path_to_cap(uint32_t hasher, const gl_t* digest, uint64_t index, const gl_t* cap, const gl_t* siblings, uint32_t depth) {
     gl_t cur[4] = {digest[0], digest[1], digest[2], digest[3]};
+    bool in_range = true;
     for (uint32_t d = 0; d < depth; d++) {
         gl_t nxt[4];
-        if (index & 1) vq_two_to_one(siblings + 4 * d, cur, nxt);
-        else vq_two_to_one(cur, siblings + 4 * d, nxt);
+        if (hasher == STARKHIP_HASHER_KECCAK) in_range = in_range && keccak_digest_in_range(siblings + 4 * d);
+        gl_t l[4], r[4];  // one call site: the left and right child by value
+        const bool odd = (index & 1) != 0;
+        for (int i = 0; i < 4; i++) {
+            const gl_t sb = siblings[4 * d + i];
+            l[i] = odd ? sb : cur[i];
+            r[i] = odd ? cur[i] : sb;
+        }
+        vq_two_to_one(hasher, l, r, nxt);
         for (int i = 0; i < 4; i++) cur[i] = nxt[i];
         index >>= 1;
     }
     const gl_t* c = cap + 4 * index;
-    return cur[0] == c[0] && cur[1] == c[1] && cur[2] == c[2] && cur[3] == c[3];
+    return in_range && cur[0] == c[0] && cur[1] == c[1] && cur[2] == c[2] && cur[3] == c[3];
 }
 
 // plonky2 fri::verifier::compute_evaluation: the arity coset values (stored bit-reversed) interpolated at beta, by Lagrange's
@@ -113,8 +129,8 @@ GL_HD uint32_t vq_check_query(const VQProof& P, const gl_t* region, const gl_t* 
     const gl_t* tsib = qp + P.C;
     const gl_t* qsib = tsib + 4 * d0 + P.Q;
     qp = qsib + 4 * d0;
-    if (!vq_path_to_cap(digests, x_index, region, tsib, d0)) status |= VQ_TRACE_PATH;
-    if (!vq_path_to_cap(digests + 4, x_index, region + P.off_quot_cap, qsib, d0)) status |= VQ_QUOT_PATH;
+    if (!vq_path_to_cap(P.hasher, digests, x_index, region, tsib, d0)) status |= VQ_TRACE_PATH;
+    if (!vq_path_to_cap(P.hasher, digests + 4, x_index, region + P.off_quot_cap, qsib, d0)) status |= VQ_QUOT_PATH;
     gl_t subgroup_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(P.log_N), gl_bitrev((uint32_t)x_index, P.log_N)));
     const gl2_t xe = gl2_from_base(subgroup_x);
     gl2_t sum = gl2_mul(gl2_sub(e0, P.red0), gl2_inv(gl2_sub(xe, P.zeta)));
@@ -129,7 +145,7 @@ GL_HD uint32_t vq_check_query(const VQProof& P, const gl_t* region, const gl_t* 
         const uint64_t coset_index = x_index >> ab, within = x_index & (arity - 1);
         if (!gl2_eq(gl2_make(evals[2 * within], evals[2 * within + 1]), old_eval)) status |= VQ_FRI_COSET;
         old_eval = vq_fold_eval(subgroup_x, within, ab, evals, P.betas[l]);
-        if (!vq_path_to_cap(digests + 4 * (2 + l), coset_index, region + P.off_fri_caps + (uint64_t)l * (4u << P.cap_h), sib, P.layer_depth[l]))
+        if (!vq_path_to_cap(P.hasher, digests + 4 * (2 + l), coset_index, region + P.off_fri_caps + (uint64_t)l * (4u << P.cap_h), sib, P.layer_depth[l]))
             status |= VQ_FRI_PATH;
         for (uint32_t b = 0; b < ab; b++) subgroup_x = gl_sqr(subgroup_x);
         x_index = coset_index;

@@ -56,6 +56,10 @@ def proof_to_value(blob):
     """Proof blob (numpy uint64) -> nested dict / list value in serde's shape."""
     blob = np.asarray(blob, dtype=np.uint64)
     lay = _Layout(blob)
+    if int(blob[12]) != 0:  # header word 12: the hasher id, 0 = Poseidon
+        # KeccakGoldilocksConfig's digests are BytesHash<25>, whose serde form this project cannot pin; the blob's four-word encoding of
+        # them (INTEGRATION.md) is the project's own and would not deserialize as one
+        raise ValueError("the hand-off format covers PoseidonGoldilocksConfig proofs only: this proof's header names hasher %d" % int(blob[12]))
     pos = 16
 
     def take(n):
