@@ -92,6 +92,13 @@ pub struct starkhip_proof_layout_t {
     pub q_step_evals: [usize; 16],
     pub q_step_siblings: [usize; 16],
     pub step_sibling_count: [usize; 16],
+    // permutation arguments (all 0 for a proof with nZ = 0)
+    pub n_permutation_zs: usize,
+    pub off_permutation_zs_cap: usize,
+    pub off_permutation_zs: usize,
+    pub off_permutation_zs_next: usize,
+    pub q_permutation_zs_leaf: usize,
+    pub q_permutation_zs_siblings: usize,
 }
 
 /// `starkhip_pool_config_t` (0 = the library's default).
@@ -204,6 +211,18 @@ extern "C" {
     // AIRs only, so the entry points that take `Air` cannot carry one.
     pub fn starkhip_air_check_program(blob: *const u64, words: usize, why: *mut c_char, why_len: usize) -> c_int;
     pub fn starkhip_air_register(blob: *const u64, words: usize, name: *const c_char, default_rows: u32, id_out: *mut c_int) -> c_int;
+    // permutation arguments (starky's permutation_pairs(); COMPAT.md P1 - P8): the pairs a registered program declares and nZ = 2 x batches
+    pub fn starkhip_air_permutation_pairs(air: c_int) -> c_int;
+    pub fn starkhip_air_permutation_zs(air: c_int) -> c_int;
+    // tests: the Z polynomials of a trace on the device and from plain loops (challenges B x 2 x {beta, gamma}; zs_out [nZ][n_rows],
+    // closing_out [nZ]); the constraint fold over the AIR's own and the permutation constraints on one extension frame
+    pub fn starkhip_permutation_zs(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                   on_device: c_int, challenges: *const u64, zs_out: *mut u64, closing_out: *mut u64) -> c_int;
+    pub fn starkhip_permutation_zs_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                          challenges: *const u64, zs_out: *mut u64, closing_out: *mut u64) -> c_int;
+    pub fn starkhip_air_eval_frame_full(air: c_int, local: *const u64, next: *const u64, public_inputs: *const u64, masks: *const u64,
+                                        alphas: *const u64, n_alpha: c_int, zs: *const u64, zs_next: *const u64, challenges: *const u64,
+                                        acc_out: *mut u64) -> c_int;
     pub fn starkhip_check_trace(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                 on_device: c_int, public_inputs: *const u64, violations: *mut u64, first: *mut u64) -> c_int;
     // The full report: per_constraint [starkhip_air_num_constraints(air)] or null, row_mask [(n_rows + 63) / 64] or null (bit r & 63 of
@@ -706,7 +725,7 @@ pub fn final_exponentiate_main(prover: &mut Prover, x: &[u32; 144]) -> Result<Pr
 
 #[allow(dead_code)]
 fn _abi_sizes() {
-    // the header's structs are plain C: eight u32 / 27 + 48 size_t
+    // the header's structs are plain C: eight u32 / 27 + 48 + 6 size_t
     let _ = [(); 32][std::mem::size_of::<starkhip_config_t>() - 32];
     let _: c_uint = 0;
 }
@@ -753,8 +772,9 @@ pub mod handoff {
         let openings = StarkOpeningSet {
             local_values: exts(&b[l.off_local_values..l.off_local_values + 2 * l.n_columns]),
             next_values: exts(&b[l.off_next_values..l.off_next_values + 2 * l.n_columns]),
-            permutation_zs: None,       // none of the five AIRs uses permutation arguments
-            permutation_zs_next: None,
+            // None for the five built-in AIRs; a registered AIR with permutation pairs has nZ of each
+            permutation_zs: (l.n_permutation_zs > 0).then(|| exts(&b[l.off_permutation_zs..l.off_permutation_zs + 2 * l.n_permutation_zs])),
+            permutation_zs_next: (l.n_permutation_zs > 0).then(|| exts(&b[l.off_permutation_zs_next..l.off_permutation_zs_next + 2 * l.n_permutation_zs])),
             quotient_polys: exts(&b[l.off_quotient_openings..l.off_quotient_openings + 2 * l.n_quotient_polys]),
         };
         let commit_phase_merkle_caps = (0..l.n_fri_layers).map(|i| cap(&b[l.off_fri_caps + i * ncap..l.off_fri_caps + (i + 1) * ncap])).collect();
@@ -762,12 +782,16 @@ pub mod handoff {
             .map(|r| {
                 let q = &b[l.off_query_rounds + r * l.query_round_words..l.off_query_rounds + (r + 1) * l.query_round_words];
                 let d0 = 4 * l.initial_sibling_count;
-                // oracle 0 = trace, oracle 1 = quotient polynomials (the order PolynomialBatch commitments are passed to prove_openings)
-                let evals_proofs = vec![
+                // the oracles in the order PolynomialBatch commitments are passed to prove_openings: trace, [permutation Zs,] quotient polynomials
+                let mut evals_proofs = vec![
                     (q[l.q_trace_leaf..l.q_trace_leaf + l.n_columns].iter().map(|&w| f(w)).collect(), path(&q[l.q_trace_siblings..l.q_trace_siblings + d0])),
-                    (q[l.q_quotient_leaf..l.q_quotient_leaf + l.n_quotient_polys].iter().map(|&w| f(w)).collect(),
-                     path(&q[l.q_quotient_siblings..l.q_quotient_siblings + d0])),
                 ];
+                if l.n_permutation_zs > 0 {
+                    evals_proofs.push((q[l.q_permutation_zs_leaf..l.q_permutation_zs_leaf + l.n_permutation_zs].iter().map(|&w| f(w)).collect(),
+                                       path(&q[l.q_permutation_zs_siblings..l.q_permutation_zs_siblings + d0])));
+                }
+                evals_proofs.push((q[l.q_quotient_leaf..l.q_quotient_leaf + l.n_quotient_polys].iter().map(|&w| f(w)).collect(),
+                                   path(&q[l.q_quotient_siblings..l.q_quotient_siblings + d0])));
                 let steps = (0..l.n_fri_layers)
                     .map(|s| FriQueryStep {
                         evals: exts(&q[l.q_step_evals[s]..l.q_step_evals[s] + (2usize << l.arity_bits)]),
@@ -786,7 +810,7 @@ pub mod handoff {
         Ok(StarkProofWithPublicInputs {
             proof: StarkProof {
                 trace_cap: cap(&b[l.off_trace_cap..l.off_trace_cap + ncap]),
-                permutation_zs_cap: None,
+                permutation_zs_cap: (l.n_permutation_zs > 0).then(|| cap(&b[l.off_permutation_zs_cap..l.off_permutation_zs_cap + ncap])),
                 quotient_polys_cap: cap(&b[l.off_quotient_cap..l.off_quotient_cap + ncap]),
                 openings,
                 opening_proof,

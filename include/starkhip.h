@@ -73,6 +73,8 @@ typedef struct {
 #define STARKHIP_AIR_MAX_PUBLIC_INPUTS 65535u /* a public-input index travels in 16 bits of a device op (quotient_ops.h) */
 #define STARKHIP_AIR_MAX_CODE_WORDS (1u << 26)
 #define STARKHIP_AIR_MAX_DEGREE 8u /* 4 gates + 3 factors + 1 for a first / last-row constraint: the most a program can reach */
+#define STARKHIP_AIR_MAX_PERMUTATION_PAIRS 64u   /* permutation pairs of a program, and entries of one pair */
+#define STARKHIP_AIR_MAX_PERMUTATION_ENTRIES 64u
 
 typedef enum {
     STARKHIP_AIR_FP12_MUL = 0,
@@ -135,6 +137,14 @@ int starkhip_air_program(starkhip_air_t air, const uint64_t** blob, size_t* word
  * are base-field.  Host only. */
 int starkhip_air_eval_frame(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
                             const uint64_t masks[8], const uint64_t* alphas, int n_alpha, uint64_t* acc_out);
+/* Permutation arguments (starky's Stark::permutation_pairs(); COMPAT.md P1 - P8).  A registered program may declare pairs of column
+ * lists: the rows of the lhs columns are a permutation of the rows of the rhs columns.  The pairs are cut into batches of
+ * B = max(1, degree - 1) in declaration order; every batch has one running-product polynomial Z per challenge (2 of them), index
+ * batch * 2 + challenge, committed between the trace and the quotient.  The two queries: the number of pairs, and nZ = 2 x batches
+ * (0 for an AIR without pairs, which is every built-in one); BAD_AIR for an unknown id.  A proof of an AIR with pairs always evaluates
+ * its quotient on every coset ("quotient_cosets" = 1, as degree > 5 does), behind either "quotient_impl". */
+int starkhip_air_permutation_pairs(starkhip_air_t air);
+int starkhip_air_permutation_zs(starkhip_air_t air);
 
 /* --- user-defined AIRs ------------------------------------------------------------------
  * A starky user's own `impl Stark` reaches the library as its constraint program: the blob starkhip_air_program returns (format:
@@ -349,7 +359,7 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
  * give the same proof bytes.  For a trace that violates a constraint they do not: the violated class's sum is not divisible by Z_H, so
  * its values on a few cosets and on all of them interpolate to different polynomials; either proof is rejected by the verifier, an AIR
  * whose quotient has a spare coset (degree 4) fails with STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE either way, and starkhip_check_trace is the
- * tool for such a trace -- or "check_trace" below, which refuses it inside the prove call.  AIRs of degree above 5, the profiling modes and the comparison of the two evaluators always run as 1),
+ * tool for such a trace -- or "check_trace" below, which refuses it inside the prove call.  AIRs of degree above 5, AIRs with permutation pairs, the profiling modes and the comparison of the two evaluators always run as 1),
  * "quotient_chunks" (0 = automatic),
  * "check_trace" (0 = default / 1: every prove on the context checks its trace against the AIR before the LDE and returns
  * STARKHIP_ERR_TRACE with a check blob for a violating one -- "the check inside prove()" above), "check_trace_list" (0 ..
@@ -614,7 +624,8 @@ int starkhip_plan_lpt(size_t n_jobs, const starkhip_air_t* airs, size_t n_pools,
 double starkhip_air_cost(starkhip_air_t air);
 
 /* per-phase device timings of the last prove on this ctx, milliseconds (HIP events; with "check_trace" on, [0] includes the check):
- * [0] upload/transpose [1] ifft+lde [2] trace leaf hash + merkle [3] quotient [4] quotient commit
+ * [0] upload/transpose [1] ifft+lde [2] trace leaf hash + merkle [3] quotient (for an AIR with permutation pairs: the Z polynomials,
+ * their LDE and commitment first) [4] quotient commit
  * [5] openings [6] fri combine [7] fri commit [8] pow [9] queries [10] total */
 #define STARKHIP_N_PHASES 11
 int starkhip_last_timings(void* ctx, float ms[STARKHIP_N_PHASES]);
@@ -636,6 +647,24 @@ int starkhip_host_alloc(void* ctx, size_t bytes, void** out);
 void starkhip_host_free(void* p);
 
 /* --- kernel-level entry points (parity tests / micro-benchmarks) ---------------------- */
+/* The Z polynomials of an AIR with permutation pairs on one trace, as prove() computes them (csrc/kernels_permutation.hip): trace as
+ * in starkhip_check_trace (layout 0 row-major / 1 column-major, host or device memory, any word of a cell's class mod p);
+ * challenges: B x 2 x {beta, gamma} canonical words, set-major (B = max(1, degree - 1)); zs_out [nZ][n_rows]: Z[0] = 1,
+ * Z[r + 1] = Z[r] ratio(r); closing_out [nZ]: Z[n - 1] ratio(n - 1), 1 exactly when the batch's lhs and rhs agree as multisets (up to
+ * the challenges' luck).  The inverse of a zero denominator is 0.  BAD_AIR for an unknown AIR or one without pairs, BAD_SHAPE for a
+ * bad trace argument, rows that are no power of two in 2 .. 2^STARKHIP_MAX_LOG_ROWS or a challenge >= p. */
+int starkhip_permutation_zs(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                            const uint64_t* challenges, uint64_t* zs_out, uint64_t* closing_out);
+/* the same from plain loops on the host (host memory only); no device needed */
+int starkhip_permutation_zs_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const uint64_t* challenges,
+                                   uint64_t* zs_out, uint64_t* closing_out);
+/* starkhip_air_eval_frame plus the permutation constraints (COMPAT.md P4): zs / zs_next hold nZ pairs (the Z openings at zeta and
+ * g zeta), challenges B x 2 x {beta, gamma} base-field words; acc_out is the fold over all K + 2 nZ constraints -- the AIR's own K,
+ * then nZ first-row constraints Z_i - 1, then nZ plain ones Z_i(next) prod red_rhs - Z_i(local) prod red_lhs.  For an AIR without pairs
+ * zs, zs_next and challenges may be NULL and the result is starkhip_air_eval_frame's.  Host only. */
+int starkhip_air_eval_frame_full(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
+                                 const uint64_t masks[8], const uint64_t* alphas, int n_alpha, const uint64_t* zs, const uint64_t* zs_next,
+                                 const uint64_t* challenges, uint64_t* acc_out);
 /* values column-major [C][n] (host) -> coeffs [C][n] and LDE [C][N] in NATURAL point order i <-> 7*w_N^i.  1 <= log_n <=
  * STARKHIP_MAX_LOG_ROWS and rate_bits <= 8, BAD_SHAPE otherwise; from log_n 14 on through csrc/kernels_lde_long.hip */
 int starkhip_lde_batch(void* ctx, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out,
@@ -762,14 +791,18 @@ const char* starkhip_error_string(int code);
 
 /* Proof blob, uint64 words (canonical field order of StarkProofWithPublicInputs):
  *   [0..16)  header: magic "SSPRF001", C, Q, degree_bits, rate_bits, cap_height, L (FRI layers),
- *            num_query_rounds, final_poly_len, n_pis, arity_bits, num_challenges, hasher (STARKHIP_HASHER_*: 0 for Poseidon), 0,0,0
- *   trace_cap[2^cap_h][4]; quotient_polys_cap[2^cap_h][4]
- *   openings.local_values[C][2]; openings.next_values[C][2]; openings.quotient_polys[Q][2]
+ *            num_query_rounds, final_poly_len, n_pis, arity_bits, num_challenges, hasher (STARKHIP_HASHER_*: 0 for Poseidon),
+ *            nZ (permutation Z polynomials: 0 for an AIR without permutation pairs, at most 128), 0,0
+ *   trace_cap[2^cap_h][4]; [nZ > 0: permutation_zs_cap[2^cap_h][4];] quotient_polys_cap[2^cap_h][4]
+ *   openings.local_values[C][2]; openings.next_values[C][2];
+ *   [nZ > 0: openings.permutation_zs[nZ][2]; openings.permutation_zs_next[nZ][2];] openings.quotient_polys[Q][2]
  *   commit_phase_merkle_caps[L][2^cap_h][4]
  *   query_round_proofs[num_query_rounds]:
- *       trace leaf[C], trace siblings[log N - cap_h][4], quotient leaf[Q], quotient siblings[log N - cap_h][4],
+ *       trace leaf[C], trace siblings[log N - cap_h][4], [nZ > 0: Z leaf[nZ], Z siblings[log N - cap_h][4],]
+ *       quotient leaf[Q], quotient siblings[log N - cap_h][4],
  *       steps[L]: evals[2^arity][2], siblings[log(N / arity^(l+1)) - cap_h][4]
  *   final_poly[final_poly_len][2]; pow_witness; public_inputs[n_pis]
+ * A proof with nZ = 0 has exactly the bytes it always had.
  */
 #define STARKHIP_PROOF_MAGIC 0x3130304652505353ULL
 
@@ -784,6 +817,8 @@ typedef struct {
         query_round_words, off_final_poly, off_pow_witness, off_public_inputs, total_words;
     size_t q_trace_leaf, q_trace_siblings, q_quotient_leaf, q_quotient_siblings, initial_sibling_count;
     size_t q_step_evals[16], q_step_siblings[16], step_sibling_count[16];
+    /* permutation arguments (all 0 for a proof with nZ = 0) */
+    size_t n_permutation_zs, off_permutation_zs_cap, off_permutation_zs, off_permutation_zs_next, q_permutation_zs_leaf, q_permutation_zs_siblings;
 } starkhip_proof_layout_t;
 /* STARKHIP_ERR_BAD_SHAPE when the blob's header is not a proof header or disagrees with proof_words */
 int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_proof_layout_t* out);

@@ -19,6 +19,7 @@ import numpy as np
 
 P = 0xFFFFFFFF00000001
 AIR_MAGIC = 0x3152495F52494153  # "SAIR_IR1"
+AIR_PERM_MAGIC = 0x3153524941504D50  # "PMPAIRS1": the section of permutation pairs
 KIND_PLAIN, KIND_TRANSITION, KIND_FIRST, KIND_LAST = 0, 1, 2, 3
 CK_PLUS, CK_MINUS, CK_CONST, CK_PI, CK_NEG_PI = 0, 1, 2, 3, 4
 REF_NEXT, REF_COMPL, REF_COL_MASK = 1 << 30, 1 << 31, 0xFFFFFF
@@ -179,6 +180,7 @@ class AirBuilder:
         self.consts, self._const_idx = [], {}
         self.code, self.group_off, self.group_k0 = [], [], []
         self._open, self._kind, self._gates, self._cur = False, 0, [], []
+        self.perm_pairs = []
 
     def L(self, col):
         self._check_col(col)
@@ -213,6 +215,15 @@ class AirBuilder:
     def last_row(self, e):
         self._emit(KIND_LAST, _expr(e))
 
+    def permutation_pair(self, entries):
+        """One of starky's `permutation_pairs()`: entries = [(lhs column, rhs column), ...]; the rows of the lhs columns are a permutation
+        of the rows of the rhs columns.  Pairs are batched B = max(1, degree - 1) at a time in the order they are declared here."""
+        entries = [(int(l), int(r)) for l, r in entries]
+        for l, r in entries:
+            self._check_col(l)
+            self._check_col(r)
+        self.perm_pairs.append(entries)
+
     def count(self):
         return self.n_constraints
 
@@ -224,6 +235,10 @@ class AirBuilder:
         code = self.code + [0] * (len(self.code) & 1)
         words += [code[i] | (code[i + 1] << 32) for i in range(0, len(code), 2)]
         words += [off | (k0 << 32) for off, k0 in zip(self.group_off, self.group_k0)]
+        if self.perm_pairs:  # the optional section; a program without pairs keeps its bytes
+            words += [AIR_PERM_MAGIC, len(self.perm_pairs)]
+            for entries in self.perm_pairs:
+                words += [len(entries)] + [l | (r << 32) for l, r in entries]
         return np.array(words, dtype=np.uint64)
 
     def _check_col(self, col):

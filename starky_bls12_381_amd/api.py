@@ -195,6 +195,22 @@ def air_default_rows(air):
     return r
 
 
+def air_permutation_pairs(air):
+    """Permutation pairs the AIR declares (starky's permutation_pairs(); 0 for every built-in AIR)."""
+    r = lib.starkhip_air_permutation_pairs(air)
+    if r < 0:
+        raise StarkhipError(r)
+    return r
+
+
+def air_permutation_zs(air):
+    """nZ: the Z polynomials a proof of the AIR commits for its permutation pairs, 2 per batch of max(1, degree - 1) pairs."""
+    r = lib.starkhip_air_permutation_zs(air)
+    if r < 0:
+        raise StarkhipError(r)
+    return r
+
+
 def air_program(air):
     """Serialised constraint program (numpy uint64 copy)."""
     blob = _u64p()
@@ -501,7 +517,9 @@ class ProofLayout(C.Structure):
         "n_public_inputs", "arity_bits", "off_trace_cap", "off_quotient_cap", "off_local_values", "off_next_values",
         "off_quotient_openings", "off_fri_caps", "off_query_rounds", "query_round_words", "off_final_poly", "off_pow_witness",
         "off_public_inputs", "total_words", "q_trace_leaf", "q_trace_siblings", "q_quotient_leaf", "q_quotient_siblings",
-        "initial_sibling_count")] + [(n, C.c_size_t * 16) for n in ("q_step_evals", "q_step_siblings", "step_sibling_count")]
+        "initial_sibling_count")] + [(n, C.c_size_t * 16) for n in ("q_step_evals", "q_step_siblings", "step_sibling_count")] + \
+        [(n, C.c_size_t) for n in ("n_permutation_zs", "off_permutation_zs_cap", "off_permutation_zs", "off_permutation_zs_next",
+                                   "q_permutation_zs_leaf", "q_permutation_zs_siblings")]
 
 
 lib.starkhip_proof_layout.argtypes = [_u64p, C.c_size_t, C.POINTER(ProofLayout)]
@@ -580,6 +598,50 @@ def air_eval_frame(air, local, nxt, pis, masks, alphas):
     out = np.zeros_like(alphas)
     _chk(lib.starkhip_air_eval_frame(air, _p64(local), _p64(nxt), _p64(pis), _p64(masks), _p64(alphas), alphas.shape[0], _p64(out)))
     return out
+
+
+lib.starkhip_air_eval_frame_full.argtypes = [C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p, C.c_int, _u64p, _u64p, _u64p, _u64p]
+
+
+def air_eval_frame_full(air, local, nxt, pis, masks, alphas, zs, zs_next, challenges):
+    """air_eval_frame continued over the permutation constraints (COMPAT.md P4): zs / zs_next [nZ, 2] are the Z openings at zeta and
+    g zeta, challenges the B x 2 x (beta, gamma) base-field words; the fold over all K + 2 nZ constraints, [k, 2]."""
+    local, nxt, masks, alphas, zs, zs_next = (np.ascontiguousarray(x, dtype=np.uint64) for x in (local, nxt, masks, alphas, zs, zs_next))
+    pis = np.ascontiguousarray(pis, dtype=np.uint64)
+    challenges = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+    cols, nz = air_columns(air), air_permutation_zs(air)
+    if local.shape != (cols, 2) or nxt.shape != (cols, 2) or masks.shape != (4, 2) or alphas.ndim != 2 or alphas.shape[1] != 2 \
+            or pis.size != air_public_inputs(air) or zs.shape != (nz, 2) or zs_next.shape != (nz, 2) \
+            or challenges.size != 4 * max(1, air_constraint_degree(air) - 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    out = np.zeros_like(alphas)
+    _chk(lib.starkhip_air_eval_frame_full(air, _p64(local), _p64(nxt), _p64(pis), _p64(masks), _p64(alphas), alphas.shape[0], _p64(zs),
+                                          _p64(zs_next), _p64(challenges), _p64(out)))
+    return out
+
+
+lib.starkhip_permutation_zs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, _u64p, _u64p]
+lib.starkhip_permutation_zs_replay.argtypes = [C.c_int, _u64p, C.c_size_t, C.c_size_t, C.c_int, _u64p, _u64p, _u64p]
+
+
+def _perm_zs_args(air, n_rows, challenges):
+    challenges = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+    if challenges.size != 4 * max(1, air_constraint_degree(air) - 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    nz = air_permutation_zs(air)
+    return challenges, np.zeros((nz, n_rows), dtype=np.uint64), np.zeros(nz, dtype=np.uint64)
+
+
+def permutation_zs_replay(air, trace, challenges, layout=0):
+    """The Z polynomials of `trace` (row-major [n][C], or column-major [C][n] with layout=1) under `challenges` (B x 2 x (beta, gamma)),
+    from plain loops on the host (starkhip_permutation_zs_replay): (zs [nZ, n], closing products [nZ])."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    challenges, zs, closing = _perm_zs_args(air, n_rows, challenges)
+    _chk(lib.starkhip_permutation_zs_replay(air, _p64(trace), n_rows, n_cols, layout, _p64(challenges), _p64(zs), _p64(closing)))
+    return zs, closing
 
 
 # ----------------------------------------------------------------------------- traces (generate_trace)
@@ -865,6 +927,24 @@ class Prover:
         self.last_call_s = time.perf_counter() - t0
         _chk(rc)
         return bad.value, tuple(int(x) for x in first)
+
+    def permutation_zs(self, air, trace, challenges, layout=0):
+        """permutation_zs_replay's result from this context's device, through the kernels prove() uses (starkhip_permutation_zs)."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        if trace.ndim != 2 or layout not in (0, 1):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+        challenges, zs, closing = _perm_zs_args(air, n_rows, challenges)
+        _chk(lib.starkhip_permutation_zs(self._ctx, air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, _p64(challenges), _p64(zs),
+                                         _p64(closing)))
+        return zs, closing
+
+    def permutation_zs_device(self, air, trace_ptr, n_rows, challenges, layout=1):
+        """permutation_zs on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
+        challenges, zs, closing = _perm_zs_args(air, n_rows, challenges)
+        _chk(lib.starkhip_permutation_zs(self._ctx, air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, _p64(challenges), _p64(zs),
+                                         _p64(closing)))
+        return zs, closing
 
     def check_trace_device(self, air, trace_ptr, n_rows, public_inputs, layout=1):
         """check_trace on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""

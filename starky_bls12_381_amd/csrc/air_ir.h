@@ -26,6 +26,11 @@
 //     followed by nf x cellref
 //   END word   : 0
 // cellref: [23:0]=column  [30]=next row  [31]=complement (gates only: value 1 - cell)
+//
+// Permutation pairs (starky's Stark::permutation_pairs(), COMPAT.md P1-P8): an OPTIONAL section of the blob after the group table,
+//   AIR_PERM_MAGIC, n_pairs, then per pair: n_entries, n_entries words  lhs column | rhs column << 32.
+// A program without pairs has no section and keeps its bytes.  The pairs are cut into batches of B = max(1, degree - 1) in
+// declaration order; a batch has one Z polynomial per challenge (2), index batch * 2 + challenge.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -45,6 +50,7 @@ enum : uint32_t { CK_PLUS = 0, CK_MINUS = 1, CK_CONST = 2, CK_PI = 3, CK_NEG_PI 
 enum : uint32_t { REF_NEXT = 1u << 30, REF_COMPL = 1u << 31, REF_COL_MASK = 0xFFFFFFu };
 static const uint32_t AIR_MAX_GROUP = 255;
 static const uint64_t AIR_MAGIC = 0x3152495F52494153ULL;  // "SAIR_IR1"
+static const uint64_t AIR_PERM_MAGIC = 0x3153524941504D50ULL;  // "PMPAIRS1": the section of permutation pairs
 
 // The rows a constraint of `kind` applies to, of a trace of n rows: the one rule of the device checkers' walker
 // (kernels_check.hip) and of the host replay (check_report.cpp).  Written without short-circuit operators: in the walker's loop
@@ -75,10 +81,15 @@ struct AirProgram {
     std::vector<uint32_t> code;
     // per group: word offset of the GROUP word, and number of constraints before it
     std::vector<uint32_t> group_off, group_k0;
+    // permutation pairs: per pair its entries, lhs column | rhs column << 32 (empty for every built-in AIR)
+    std::vector<std::vector<uint64_t>> perm_pairs;
+    uint32_t perm_batch_size() const { return degree > 1 ? degree - 1 : 1; }  // B: quotient_degree_factor, and permutation_batch_size()
+    uint32_t perm_batches() const { return (uint32_t)((perm_pairs.size() + perm_batch_size() - 1) / perm_batch_size()); }
+    uint32_t perm_zs() const { return 2 * perm_batches(); }  // nZ: one Z per (batch, challenge)
 
     // blob layout (u64 words): magic, n_cols, n_pis, degree, n_constraints, n_consts,
     // n_code_words, n_groups, consts[], code[] (two u32 per u64, zero padded),
-    // group_off[] / group_k0[] packed as (off | k0<<32)
+    // group_off[] / group_k0[] packed as (off | k0<<32), then the section of permutation pairs if there are any
     std::vector<uint64_t> serialize() const {
         std::vector<uint64_t> b;
         b.push_back(AIR_MAGIC);
@@ -97,6 +108,14 @@ struct AirProgram {
         }
         for (size_t i = 0; i < group_off.size(); i++)
             b.push_back((uint64_t)group_off[i] | ((uint64_t)group_k0[i] << 32));
+        if (!perm_pairs.empty()) {
+            b.push_back(AIR_PERM_MAGIC);
+            b.push_back(perm_pairs.size());
+            for (const auto& pr : perm_pairs) {
+                b.push_back(pr.size());
+                b.insert(b.end(), pr.begin(), pr.end());
+            }
+        }
         return b;
     }
 };
@@ -294,6 +313,17 @@ class AirBuilder {
     void transition(const Expr& e) { emit(KIND_TRANSITION, e); }
     void first_row(const Expr& e) { emit(KIND_FIRST, e); }
     void last_row(const Expr& e) { emit(KIND_LAST, e); }
+
+    // one PermutationPair: the lhs columns, under any row permutation, hold what the rhs columns hold (checked by air_parse_checked)
+    void permutation_pair(const std::vector<std::pair<uint32_t, uint32_t>>& entries) {
+        std::vector<uint64_t> e;
+        for (const auto& lr : entries) {
+            check_col(lr.first);
+            check_col(lr.second);
+            e.push_back((uint64_t)lr.first | ((uint64_t)lr.second << 32));
+        }
+        prog_.perm_pairs.push_back(std::move(e));
+    }
 
     uint32_t count() const { return prog_.n_constraints; }
 

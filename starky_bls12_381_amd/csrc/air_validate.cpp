@@ -25,8 +25,10 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
     if (n_constraints < 1 || n_constraints > n_code) return refuse(why, "n_constraints " + std::to_string(n_constraints) + " not in 1..code size");
     if (n_groups < 1 || n_groups > n_code) return refuse(why, "n_groups " + std::to_string(n_groups) + " not in 1..code size");
     const uint64_t code_u64 = (n_code + 1) / 2;
-    if ((uint64_t)words != 8 + n_consts + code_u64 + n_groups)  // every count is below 2^27 here: no overflow
-        return refuse(why, "blob length " + std::to_string(words) + " differs from the " + std::to_string(8 + n_consts + code_u64 + n_groups) + " words its header implies");
+    const uint64_t base_words = 8 + n_consts + code_u64 + n_groups;  // every count is below 2^27 here: no overflow
+    // what follows the group table is the section of permutation pairs, or nothing (a word that is not the section's magic is a wrong length)
+    if ((uint64_t)words < base_words || ((uint64_t)words > base_words && blob[base_words] != AIR_PERM_MAGIC))
+        return refuse(why, "blob length " + std::to_string(words) + " differs from the " + std::to_string(base_words) + " words its header implies");
     const uint64_t* consts = blob + 8;
     const uint64_t* code64 = consts + n_consts;
     const uint64_t* groups = code64 + code_u64;
@@ -102,6 +104,36 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
     }
     if (g != n_groups) return refuse(why, "group table has " + std::to_string(n_groups) + " entries, the code " + std::to_string(g) + " groups");
     if (k != n_constraints) return refuse(why, "n_constraints " + std::to_string(n_constraints) + " but the code has " + std::to_string(k));
+
+    // ---- permutation pairs: every column a kernel will read is < n_cols, every count within what the proof header and the kernels carry
+    if ((uint64_t)words > base_words) {
+        const uint64_t* sec = blob + base_words;
+        const uint64_t sec_words = (uint64_t)words - base_words;
+        if (sec_words < 2) return refuse(why, "permutation section shorter than its 2-word header");
+        const uint64_t n_pairs = sec[1];
+        if (n_pairs < 1 || n_pairs > STARKHIP_AIR_MAX_PERMUTATION_PAIRS)
+            return refuse(why, "permutation section with " + std::to_string(n_pairs) + " pairs (1.." + std::to_string(STARKHIP_AIR_MAX_PERMUTATION_PAIRS) + ")");
+        if (degree < 2) return refuse(why, "permutation pairs need degree >= 2 (a Z constraint has degree 1 + the pairs of its batch)");
+        const uint64_t B = degree - 1, n_batches = (n_pairs + B - 1) / B;
+        if (n_batches > B)  // upstream draws B challenge sets and zips the batches with them: the batches beyond B would go unchecked
+            return refuse(why, std::to_string(n_pairs) + " permutation pairs make " + std::to_string(n_batches) + " batches, more than the " + std::to_string(B) + " challenge sets of degree " + std::to_string(degree));
+        uint64_t at = 2;
+        for (uint64_t p = 0; p < n_pairs; p++) {
+            const std::string atp = "permutation pair " + std::to_string(p) + ": ";
+            if (at >= sec_words) return refuse(why, atp + "runs past the blob");
+            const uint64_t ne = sec[at++];
+            if (ne < 1) return refuse(why, atp + "empty pair");
+            if (ne > STARKHIP_AIR_MAX_PERMUTATION_ENTRIES) return refuse(why, atp + std::to_string(ne) + " entries (at most " + std::to_string(STARKHIP_AIR_MAX_PERMUTATION_ENTRIES) + ")");
+            if (sec_words - at < ne) return refuse(why, atp + "entries run past the blob");
+            for (uint64_t e = 0; e < ne; e++) {
+                const uint64_t lhs = sec[at + e] & 0xFFFFFFFFu, rhs = sec[at + e] >> 32;
+                if (lhs >= n_cols || rhs >= n_cols) return refuse(why, atp + "column " + std::to_string(lhs >= n_cols ? lhs : rhs) + " out of range");
+            }
+            P.perm_pairs.emplace_back(sec + at, sec + at + ne);
+            at += ne;
+        }
+        if (at != sec_words) return refuse(why, "trailing words after the permutation section");
+    }
     if (out) *out = std::move(P);
     return true;
 }

@@ -16,6 +16,7 @@
 #include "free_cells.h"
 #include "kernels.h"
 #include "lde_ranges.h"
+#include "permutation.h"
 #include "trace_log.h"
 
 #include <atomic>
@@ -123,6 +124,77 @@ int starkhip_air_eval_frame(starkhip_air_t air, const uint64_t* local, const uin
         return STARKHIP_ERR_OOM;
     }
     return STARKHIP_OK;
+}
+
+int starkhip_air_permutation_pairs(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->prog.perm_pairs.size() : STARKHIP_ERR_BAD_AIR; }
+int starkhip_air_permutation_zs(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->prog.perm_zs() : STARKHIP_ERR_BAD_AIR; }
+
+int starkhip_air_eval_frame_full(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
+                                 const uint64_t masks[8], const uint64_t* alphas, int n_alpha, const uint64_t* zs, const uint64_t* zs_next,
+                                 const uint64_t* challenges, uint64_t* acc_out) {
+    const int rc = starkhip_air_eval_frame(air, local, next, public_inputs, masks, alphas, n_alpha, acc_out);
+    if (rc != STARKHIP_OK) return rc;
+    const AirInfo* a = air_get(air);
+    const size_t nZ = a->prog.perm_zs();
+    if (!nZ) return STARKHIP_OK;
+    if (!zs || !zs_next || !challenges) return STARKHIP_ERR_BAD_SHAPE;
+    for (size_t i = 0; i < (size_t)a->prog.perm_batch_size() * 4; i++)
+        if (challenges[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    try {
+        std::vector<gl2_t> l(a->cols), z(nZ), zn(nZ), al(n_alpha), acc(n_alpha);
+        for (size_t i = 0; i < a->cols; i++) l[i] = gl2_make(local[2 * i], local[2 * i + 1]);
+        for (size_t i = 0; i < nZ; i++) {
+            z[i] = ExtOps::canon(gl2_make(zs[2 * i], zs[2 * i + 1]));
+            zn[i] = ExtOps::canon(gl2_make(zs_next[2 * i], zs_next[2 * i + 1]));
+        }
+        gl2_t mk[4];
+        for (int i = 0; i < 4; i++) mk[i] = gl2_make(masks[2 * i], masks[2 * i + 1]);
+        for (int j = 0; j < n_alpha; j++) {
+            al[j] = gl2_make(alphas[2 * j], alphas[2 * j + 1]);
+            acc[j] = gl2_make(acc_out[2 * j], acc_out[2 * j + 1]);
+        }
+        perm_eval_folded<ExtOps>(a->prog, l.data(), z.data(), zn.data(), challenges, mk, al.data(), n_alpha, acc.data());
+        for (int j = 0; j < n_alpha; j++) {
+            acc_out[2 * j] = acc[j].a0;
+            acc_out[2 * j + 1] = acc[j].a1;
+        }
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+    return STARKHIP_OK;
+}
+
+// what the two Z entries refuse: an AIR that is unknown or has no pairs (BAD_AIR); a trace argument that cannot be one of it, rows that
+// are no power of two in 2 .. 2^STARKHIP_MAX_LOG_ROWS, a missing argument or a challenge that is not canonical (BAD_SHAPE)
+static int permutation_zs_args(const AirInfo* a, const TraceInput& in, const uint64_t* challenges, const uint64_t* zs_out, const uint64_t* closing_out) {
+    if (!a || a->prog.perm_pairs.empty()) return STARKHIP_ERR_BAD_AIR;
+    if (in.check(*a) || !challenges || !zs_out || !closing_out || in.n_rows < 2 || in.n_rows > ((size_t)1 << STARKHIP_MAX_LOG_ROWS) || (in.n_rows & (in.n_rows - 1)))
+        return STARKHIP_ERR_BAD_SHAPE;
+    for (size_t i = 0; i < (size_t)a->prog.perm_batch_size() * 4; i++)
+        if (challenges[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    return STARKHIP_OK;
+}
+
+int starkhip_permutation_zs(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                            const uint64_t* challenges, uint64_t* zs_out, uint64_t* closing_out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = permutation_zs_args(a, in, challenges, zs_out, closing_out)) return rc;
+    return guarded([&] { return permutation_zs((Ctx*)ctx, *a, in, challenges, zs_out, closing_out); });
+}
+
+int starkhip_permutation_zs_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const uint64_t* challenges,
+                                   uint64_t* zs_out, uint64_t* closing_out) {
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = permutation_zs_args(a, in, challenges, zs_out, closing_out)) return rc;
+    return guarded([&] {
+        const bool col_major = in.form == TraceForm::ColMajor;
+        perm_zs_host(a->prog, n_rows, [&](uint32_t col, size_t row) { return col_major ? trace[(size_t)col * n_rows + row] : trace[row * n_cols + col]; }, challenges,
+                     zs_out, closing_out);
+        return (int)STARKHIP_OK;
+    });
 }
 
 int starkhip_air_check_program(const uint64_t* blob, size_t words, char* why, size_t why_len) {
@@ -456,6 +528,7 @@ int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_pr
     size_t o = 0;
     out->q_trace_leaf = o; o += pl.C;
     out->q_trace_siblings = o; o += 4 * d0;
+    o += pl.nZ ? pl.nZ + 4 * d0 : 0;  // the Z leaf and its siblings (below)
     out->q_quotient_leaf = o; o += pl.Q;
     out->q_quotient_siblings = o; o += 4 * d0;
     for (size_t l = 0; l < pl.L && l < 16; l++) {
@@ -464,6 +537,10 @@ int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_pr
         out->step_sibling_count[l] = pl.layer_depth[l];
     }
     out->initial_sibling_count = d0;
+    if (pl.nZ) {
+        out->n_permutation_zs = pl.nZ; out->off_permutation_zs_cap = pl.off_zs_cap; out->off_permutation_zs = pl.off_zs;
+        out->off_permutation_zs_next = pl.off_zs_next; out->q_permutation_zs_leaf = pl.C + 4 * d0; out->q_permutation_zs_siblings = pl.C + 4 * d0 + pl.nZ;
+    }
     return STARKHIP_OK;
 }
 

@@ -176,6 +176,7 @@ struct Ctx {
         for (DevBuf* b : prog.bufs()) v.push_back(b);
         for (DevBuf* b : chk.bufs()) v.push_back(b);
         for (DevBuf* b : free_chk.bufs()) v.push_back(b);
+        for (DevBuf* b : perm.bufs()) v.push_back(b);
         for (auto& t : table_cache)
             for (DevBuf* b : t->bufs()) v.push_back(b);
         for (auto& d : plan_cache)
@@ -191,6 +192,15 @@ struct Ctx {
         DevBuf cons, pivots, planes, class_counts;
         std::vector<DevBuf*> bufs() { return {&cons, &pivots, &planes, &class_counts}; }
     } free_chk;
+    // permutation arguments (an AIR with permutation pairs; COMPAT.md P1 - P8), all empty otherwise -- work buffers of a proof, sized
+    // by work_buffers() like the ones above: the pair columns copied aside at upload (a short trace parked in the LDE buffer is
+    // overwritten by its LDE), the two descriptors (by copy slot, by trace column) and the challenges, the Zs' values, their
+    // coefficients (long traces: the transform's scratch), LDE and Merkle tree, the spans' products of the prefix scan followed by
+    // the closing products, and the Z openings
+    struct PermBufs {
+        DevBuf cols, desc, chal, zvals, zcoef, zlde, zdigests, scan, open_z, open_zn;
+        std::vector<DevBuf*> bufs() { return {&cols, &desc, &chal, &zvals, &zcoef, &zlde, &zdigests, &scan, &open_z, &open_zn}; }
+    } perm;
 };
 
 // ---- ctx.hip

@@ -135,6 +135,7 @@ int check_trace_free_cell_classes(Ctx*, const AirInfo&, const TraceInput&, const
 }
 int lde_bench(Ctx*, size_t, unsigned, unsigned, unsigned, unsigned, const uint64_t*, float*, float*) { return STARKHIP_ERR_NO_DEVICE; }
 int field_ops(Ctx*, int, const uint64_t*, const uint64_t*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
+int permutation_zs(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int host_alloc(Ctx*, size_t, void**) { return STARKHIP_ERR_NO_DEVICE; }
 void host_free(void*) {}
 

@@ -7,8 +7,39 @@
 #include <vector>
 
 #include "ctx.h"
+#include "kernels_permutation.h"
+#include "permutation.h"
 
 namespace starkhip {
+
+// kernel-level test entry: the Z polynomials of `air` on the caller's trace as prove() computes them -- the pair columns gathered into
+// the copy prove() keeps aside, then launch_perm_zs.  The caller has checked the trace argument, the rows and the challenges.
+int permutation_zs(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* challenges, uint64_t* zs_out, uint64_t* closing_out) {
+    const AirProgram& P = air.prog;
+    const size_t n = in.n_rows, C = in.n_cols, nZ = P.perm_zs(), B = P.perm_batch_size();
+    HIPCHK(hipSetDevice(c->device));
+    const std::vector<uint32_t> cols = perm_columns(P), desc = perm_descriptor(P, true);
+    Ctx::PermBufs& pb = c->perm;
+    HIPCHK(c->values.ensure(C * n * 8));
+    HIPCHK(c->lde.ensure(C * n * 8));  // upload_dense stages host rows there
+    HIPCHK(pb.cols.ensure(cols.size() * n * 8));
+    HIPCHK(pb.desc.ensure(desc.size() * 4));
+    HIPCHK(pb.chal.ensure(B * 4 * 8));
+    HIPCHK(pb.zvals.ensure(nZ * n * 8));
+    HIPCHK(pb.scan.ensure((perm_scratch_words(n, (unsigned)nZ) + nZ) * 8));
+    const gl_t* d_values = nullptr;
+    if (int rc = upload_dense(c, in, c->values.as<gl_t>(), &d_values)) return rc;
+    for (size_t k = 0; k < cols.size(); k++)
+        HIPCHK(hipMemcpyAsync(pb.cols.as<gl_t>() + k * n, d_values + (size_t)cols[k] * n, n * 8, hipMemcpyDeviceToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(pb.desc.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(pb.chal.p, challenges, B * 4 * 8, hipMemcpyHostToDevice, c->st));
+    gl_t* const d_closing = pb.scan.as<gl_t>() + perm_scratch_words(n, (unsigned)nZ);
+    HIPCHK(launch_perm_zs(pb.desc.as<uint32_t>(), pb.cols.as<gl_t>(), n, pb.chal.as<gl_t>(), n, (unsigned)nZ, pb.zvals.as<gl_t>(), pb.scan.as<gl_t>(), d_closing, c->st));
+    HIPCHK(hipMemcpyAsync(zs_out, pb.zvals.p, nZ * n * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(closing_out, d_closing, nZ * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
 
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out) {
     if (log_n < 1 || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8) return STARKHIP_ERR_BAD_SHAPE;

@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void verify_range_kernel(const gl_t* __restric
 }
 
 // fri_combine_initial's two sums of one query (verifier.cpp: e0, e1), as dot products with the powers of alpha:
-//   e1 = sum_c alpha^c trace[c],   e0 = e1 + sum_q alpha^(C + q) quotient[q]
+//   e1 = sum_c alpha^c trace[c] + sum_z alpha^(C + z) Z[z],   e0 = e1 + sum_q alpha^(C + nZ + q) quotient[q]
 // One workgroup per query; the partial sums meet in LDS.
 __global__ __launch_bounds__(256) void verify_combine_kernel(const gl_t* __restrict__ words, const VQProof* __restrict__ proofs,
                                                              const uint32_t* __restrict__ query_proof, const gl2_t* __restrict__ apow,
@@ -30,11 +30,13 @@ __global__ __launch_bounds__(256) void verify_combine_kernel(const gl_t* __restr
     const uint32_t g = blockIdx.x;
     const VQProof& P = proofs[query_proof[g]];
     const gl_t* tleaf = words + P.base + P.off_queries + (uint64_t)(g - P.first_query) * P.query_words;
-    const gl_t* qleaf = tleaf + P.C + 4 * (P.log_N - P.cap_h);
+    const gl_t* zleaf = tleaf + P.C + 4 * (P.log_N - P.cap_h);  // read only when the proof has Zs
+    const gl_t* qleaf = tleaf + vq_quot_leaf_off(P);
     const gl2_t* ap = apow + P.apow;
     gl2_t st = gl2_zero(), sq = gl2_zero();
     for (uint32_t c = threadIdx.x; c < P.C; c += blockDim.x) st = gl2_add(st, gl2_mul_base(ap[c], tleaf[c]));
-    for (uint32_t q = threadIdx.x; q < P.Q; q += blockDim.x) sq = gl2_add(sq, gl2_mul_base(ap[P.C + q], qleaf[q]));
+    for (uint32_t z = threadIdx.x; z < P.nZ; z += blockDim.x) st = gl2_add(st, gl2_mul_base(ap[P.C + z], zleaf[z]));
+    for (uint32_t q = threadIdx.x; q < P.Q; q += blockDim.x) sq = gl2_add(sq, gl2_mul_base(ap[P.C + P.nZ + q], qleaf[q]));
     red[0][threadIdx.x] = st;
     red[1][threadIdx.x] = sq;
     __syncthreads();
@@ -61,7 +63,7 @@ __global__ __launch_bounds__(64) void verify_query_kernel(const gl_t* __restrict
     if (i >= n_queries) return;
     const VQProof& P = proofs[query_proof[i]];
     const uint32_t qi = (uint32_t)i - P.first_query;
-    const gl_t* dg = digests + 4 * ((size_t)P.first_digest + (size_t)qi * (2 + P.L));
+    const gl_t* dg = digests + 4 * ((size_t)P.first_digest + (size_t)qi * vq_slots(P));
     status[i] = vq_check_query(P, words + P.base, dg, sums[2 * i], sums[2 * i + 1], x_index[i], qi);
 }
 

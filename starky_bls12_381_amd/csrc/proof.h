@@ -56,11 +56,13 @@ inline unsigned quotient_degree_bits(unsigned degree) {
 struct ProofLayout {
     size_t C, Q, log_n, rate_bits, cap_h, L, n_queries, final_len, n_pis, arity_bits, n_challenges;
     size_t hasher = 0;  // header word 12: STARKHIP_HASHER_POSEIDON (0, what the word has always been) or STARKHIP_HASHER_KECCAK
+    size_t nZ = 0;      // header word 13: permutation Z polynomials (0, what the word has always been, for an AIR without pairs)
     size_t ncap;     // 2^cap_h
     size_t log_N;
     // offsets (in words)
     size_t off_trace_cap, off_quot_cap, off_local, off_next, off_quot_open, off_fri_caps, off_queries, query_words, off_final,
         off_pow, off_pis, total;
+    size_t off_zs_cap = 0, off_zs = 0, off_zs_next = 0;  // nZ > 0 only: the Z cap after the trace cap, the Z openings after next_values
     std::vector<size_t> layer_depth;  // siblings per FRI layer
 
     // the layout of a proof of AIR program `P` with 2^log_n rows under `cfg` (`geo`: FriGeometry::make(cfg, log_n))
@@ -70,6 +72,7 @@ struct ProofLayout {
         pl.C = P.n_cols; pl.Q = (size_t)quotient_factor(P.degree) * 2; pl.log_n = log_n; pl.rate_bits = cfg.rate_bits; pl.cap_h = cfg.cap_height;
         pl.L = geo.arities.size(); pl.n_queries = cfg.num_query_rounds; pl.final_len = geo.final_poly_len; pl.n_pis = P.n_pis;
         pl.arity_bits = cfg.arity_bits; pl.n_challenges = 2;
+        pl.nZ = P.perm_zs();
         pl.compute();
         return pl;
     }
@@ -78,14 +81,17 @@ struct ProofLayout {
         log_N = log_n + rate_bits;
         size_t o = 16;
         off_trace_cap = o; o += 4 * ncap;
+        off_zs_cap = nZ ? o : 0; o += nZ ? 4 * ncap : 0;
         off_quot_cap = o; o += 4 * ncap;
         off_local = o; o += 2 * C;
         off_next = o; o += 2 * C;
+        off_zs = nZ ? o : 0; o += 2 * nZ;
+        off_zs_next = nZ ? o : 0; o += 2 * nZ;
         off_quot_open = o; o += 2 * Q;
         off_fri_caps = o; o += L * 4 * ncap;
         off_queries = o;
         size_t d0 = log_N - cap_h;
-        query_words = C + 4 * d0 + Q + 4 * d0;
+        query_words = C + 4 * d0 + (nZ ? nZ + 4 * d0 : 0) + Q + 4 * d0;  // the Z leaf and its siblings between the trace's and the quotient's
         layer_depth.clear();
         size_t lg = log_N;
         for (size_t l = 0; l < L; l++) {
@@ -104,13 +110,14 @@ struct ProofLayout {
         h[0] = STARKHIP_PROOF_MAGIC; h[1] = C; h[2] = Q; h[3] = log_n; h[4] = rate_bits; h[5] = cap_h; h[6] = L;
         h[7] = n_queries; h[8] = final_len; h[9] = n_pis; h[10] = arity_bits; h[11] = n_challenges;
         h[12] = hasher;
-        h[13] = h[14] = h[15] = 0;
+        h[13] = nZ;
+        h[14] = h[15] = 0;
     }
     bool read_header(const uint64_t* h, size_t words) {
         if (words < 16 || h[0] != STARKHIP_PROOF_MAGIC) return false;
         C = h[1]; Q = h[2]; log_n = h[3]; rate_bits = h[4]; cap_h = h[5]; L = h[6]; n_queries = h[7]; final_len = h[8];
-        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11]; hasher = h[12];
-        if (hasher > STARKHIP_HASHER_KECCAK) return false;
+        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11]; hasher = h[12]; nZ = h[13];
+        if (hasher > STARKHIP_HASHER_KECCAK || nZ > 128) return false;
         if (log_n > 32 || rate_bits > 8 || cap_h > 16 || L > 16 || arity_bits > 8 || log_n + rate_bits < cap_h) return false;
         if (L * arity_bits + cap_h > log_n + rate_bits) return false;
         compute();

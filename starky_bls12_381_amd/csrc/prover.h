@@ -101,6 +101,9 @@ int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor);
 int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms = nullptr);
 int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+// starkhip_permutation_zs: the Z polynomials of an AIR with permutation pairs on one trace, through the kernels prove() uses
+// (kernels_permutation.hip); challenges B x 2 x {beta, gamma}, zs_out [nZ][n_rows], closing_out [nZ]
+int permutation_zs(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* challenges, uint64_t* zs_out, uint64_t* closing_out);
 int host_alloc(Ctx* c, size_t bytes, void** out);
 void host_free(void* p);
 

@@ -2,7 +2,8 @@
 // /root/reference/src/aggregate_proof.rs:59-65 (and :105, :138, :169).  prove() follows the transcript of SURVEY.md App. A.5 as a list
 // of phases (the methods of ProveCall), sized and laid out by one ProofShape and one table of work buffers that ctx_reserve() shares;
 // every heavy step is one of the kernels in kernels_*.hip, the host only runs the Fiat-Shamir challenger, two length-n synthetic
-// divisions and the proof assembly.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
+// divisions and the proof assembly.  An AIR with permutation pairs (COMPAT.md P1 - P8) has its Z polynomials made and committed at the
+// start of the quotient phase (ProveCall::permutation) and carried as a third matrix from there on.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
 // checkers' host halves check_trace.hip, the kernel-level entry points of the tests kernel_entries.hip.
 #include <hip/hip_runtime.h>
 
@@ -19,7 +20,9 @@
 #include "check_report.h"
 #include "ctx.h"
 #include "kernels.h"
+#include "kernels_permutation.h"
 #include "lde_ranges.h"
+#include "permutation.h"
 #include "trace_log.h"
 #include "poseidon.h"
 #include "proof.h"
@@ -92,6 +95,7 @@ struct HostWatch {  // accumulates wall time of the host-side stretches of prove
 struct ProofShape {
     unsigned log_n, r, cap_h, log_N, qdb, factor;  // log2 of rows, blow-up, cap size, LDE points; the quotient's degree bits and factor
     size_t n, N, C, Q, size, ncap, L;              // rows, LDE points, trace and quotient columns, quotient points (n << qdb), cap nodes, FRI layers
+    size_t nZ, perm_cols, perm_desc_words;         // permutation pairs: Z polynomials, the columns the pairs name, words of one descriptor (0 without pairs)
     FriGeometry geo;
     ProofLayout pl;
     // STARKHIP_ERR_BAD_SHAPE for what prove() refuses: rows that are no power of two in 2 .. 2^max_log_rows(air), a config that the one
@@ -105,6 +109,7 @@ struct ProofShape {
         s->qdb = quotient_degree_bits(P.degree); s->factor = quotient_factor(P.degree);
         s->n = n_rows; s->N = s->n << s->r; s->C = P.n_cols; s->Q = (size_t)s->factor * 2; s->size = s->n << s->qdb;
         s->ncap = (size_t)1 << s->cap_h; s->L = s->geo.arities.size();
+        s->nZ = P.perm_zs(); s->perm_cols = s->nZ ? perm_columns(P).size() : 0; s->perm_desc_words = s->nZ ? perm_descriptor(P, false).size() : 0;
         s->pl = ProofLayout::make(P, cfg, s->geo, log_n);
         return STARKHIP_OK;
     }
@@ -131,10 +136,19 @@ static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n
         {&c->qdigests, digest_words(N) * 8},
         {&c->zpow, 2 * n * 16},  // powers of zeta (the quotient polynomials' openings), then the coset-0 weights of zeta
         {&c->gzpow, n * 16},     // the weights of g zeta
-        {&c->open_local, C * 16}, {&c->open_next, C * 16}, {&c->open_q, Q * 16}, {&c->ext_apow, (C + Q) * 16},
-        {&c->comb_partial, comb_chunks(C) * n * 16}, {&c->comb_out, 2 * n * 16}, {&c->fri_coef, 2 * N * 8}, {&c->fri_vals, 2 * N * 8},
+        {&c->open_local, C * 16}, {&c->open_next, C * 16}, {&c->open_q, Q * 16}, {&c->ext_apow, (C + s.nZ + Q) * 16},
+        {&c->comb_partial, (comb_chunks(C) + (s.nZ ? 1 : 0)) * n * 16},  // (the Zs' sum is one more chunk)
+        {&c->comb_out, 2 * n * 16}, {&c->fri_coef, 2 * N * 8}, {&c->fri_vals, 2 * N * 8},
         {&c->scale_tab, N * 8}, {&c->pow_state, 12 * 8}, {&c->pow_best, 8}, {&c->qidx, nq * 4},
         {&c->gather_t, nq * s.pl.query_words * 8}};  // every query round's leaves and Merkle paths, in proof layout
+    if (const size_t nZ = s.nZ) {  // an AIR with permutation pairs (Ctx::PermBufs)
+        Ctx::PermBufs& pb = c->perm;
+        for (const BufWant& b : {BufWant{&pb.cols, s.perm_cols * n * 8}, BufWant{&pb.desc, 2 * s.perm_desc_words * 4}, BufWant{&pb.chal, 4 * (size_t)s.factor * 8},
+                                 BufWant{&pb.zvals, nZ * n * 8}, BufWant{&pb.zcoef, lde_long_supported(s.log_n) ? nZ * n * 8 : 0}, BufWant{&pb.zlde, nZ * N * 8},
+                                 BufWant{&pb.zdigests, digest_words(N) * 8}, BufWant{&pb.scan, (perm_scratch_words(n, (unsigned)nZ) + nZ) * 8},
+                                 BufWant{&pb.open_z, nZ * 16}, BufWant{&pb.open_zn, nZ * 16}})
+            w.push_back(b);
+    }
     size_t len = N;
     for (size_t l = 0; l < s.L; l++) {  // a FRI layer's leaves and digests stay on the device for the query phase
         w.push_back({&c->fri_rows[l], len * 2 * 8});
@@ -188,6 +202,12 @@ struct ProveCall {
     HostWatch fs, host_other;  // Fiat-Shamir hashing / other host arithmetic of this proof
     std::vector<gl_t> trace_cap, quot_cap, quot_tail, fri_caps;
     std::vector<gl2_t> op_local, op_next, op_q, final_poly;
+    // an AIR with permutation pairs: the challenges (B sets of 2 x {beta, gamma}), the two descriptors back to back (by copy slot, by
+    // trace column), the Z cap and the Z openings
+    std::vector<gl_t> perm_chal, zs_cap;
+    std::vector<uint32_t> perm_desc;
+    std::vector<gl2_t> op_z, op_zn;
+    int permutation();
     gl_t alphas[2] = {0, 0};
     gl2_t zeta = gl2_zero();
     uint64_t* out = nullptr;  // the proof blob, from queries() on -- or the check blob of a trace that upload() refused
@@ -266,6 +286,11 @@ int ProveCall::upload() {
     // "check_trace": every constraint on every row of the trace where the upload has just put it, before anything of the LDE is
     // enqueued; a violating trace ends the proof here with STARKHIP_ERR_TRACE and its check blob in `out`
     if (rc == 0 && c->opt_check_trace) rc = check_trace_in_prove(c, air, d_values, s.n, pis_host, &out, &check_words);
+    if (rc == 0 && s.nZ) {  // the columns the permutation pairs name, aside: the LDE overwrites a parked trace and keeps no coefficients of it
+        const std::vector<uint32_t> cols = perm_columns(air.prog);
+        for (size_t k = 0; k < cols.size(); k++)
+            HIPCHK(hipMemcpyAsync(c->perm.cols.as<gl_t>() + k * s.n, d_values + (size_t)cols[k] * s.n, s.n * 8, hipMemcpyDeviceToDevice, st));
+    }
     return rc;
 }
 
@@ -423,12 +448,53 @@ int ProveCall::compare_quotient_evaluators() {
     return 0;
 }
 
+// ---- phase 3, for an AIR with permutation pairs (COMPAT.md P1 - P3; timed with the quotient): the challenges, the Z polynomials from
+// the copy of the pair columns, their closing products -- a Z that does not close ends the proof here with QUOTIENT_NOT_DIVISIBLE,
+// before anything of the Zs is committed (upstream would go on to a quotient that does not divide, or to a proof nobody accepts) --
+// then the Zs through the LDE and the commitment path of the trace under the context's hasher, and their cap into the transcript
+int ProveCall::permutation() {
+    const AirProgram& P = air.prog;
+    const size_t n = s.n, nZ = s.nZ;
+    fs.start();
+    perm_chal.resize((size_t)P.perm_batch_size() * 4);  // P1: B sets (not n_batches), each 2 x (beta, gamma), set-major, beta first
+    for (gl_t& x : perm_chal) x = ch.get();
+    fs.stop();
+    perm_desc = perm_descriptor(P, true);
+    const std::vector<uint32_t> by_col = perm_descriptor(P, false);
+    perm_desc.insert(perm_desc.end(), by_col.begin(), by_col.end());
+    Ctx::PermBufs& pb = c->perm;
+    HIPCHK(hipMemcpyAsync(pb.desc.p, perm_desc.data(), perm_desc.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(pb.chal.p, perm_chal.data(), perm_chal.size() * 8, hipMemcpyHostToDevice, st));
+    gl_t* const d_closing = pb.scan.as<gl_t>() + perm_scratch_words(n, (unsigned)nZ);
+    HIPCHK(launch_perm_zs(pb.desc.as<uint32_t>(), pb.cols.as<gl_t>(), n, pb.chal.as<gl_t>(), n, (unsigned)nZ, pb.zvals.as<gl_t>(), pb.scan.as<gl_t>(), d_closing, st));
+    std::vector<gl_t> closing(nZ);
+    HIPCHK(read_back(c, closing.data(), d_closing, nZ * 8, st));
+    HIPCHK(stream_wait(c));
+    for (gl_t v : closing)
+        if (v != 1) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
+    HIPCHK(run_lde(c, pb.zvals.as<gl_t>(), lde_long_supported(s.log_n) ? pb.zcoef.as<gl_t>() : nullptr, pb.zlde.as<gl_t>(), nZ, s.log_n, s.r, 0));
+    if (c->opt_hasher == STARKHIP_HASHER_KECCAK) HIPCHK(launch_leaf_hash_keccak(pb.zlde.as<gl_t>(), nZ, s.log_n, s.r, pb.zdigests.as<gl_t>(), st));
+    else HIPCHK(launch_leaf_hash_form(FORM_QUAD, pb.zlde.as<gl_t>(), nZ, s.log_n, s.r, pb.zdigests.as<gl_t>(), st));
+    HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, pb.zdigests.as<gl_t>(), s.log_N, s.cap_h, st));
+    zs_cap.resize(4 * s.ncap);
+    HIPCHK(read_back(c, zs_cap.data(), pb.zdigests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
+    HIPCHK(stream_wait(c));
+    fs.start();
+    ch.observe_many(zs_cap.data(), zs_cap.size());
+    fs.stop();
+    return 0;
+}
+
 // ---- phase 3: quotient polynomials (App. A.6)
 int ProveCall::quotient() {
     const size_t n = s.n, size = s.size, factor = s.factor;
     HIPCHK(stream_wait(c));  // the trace cap
     fs.start();
     ch.observe_many(trace_cap.data(), trace_cap.size());  // public inputs are NOT observed (App. A.5)
+    fs.stop();
+    if (s.nZ)
+        if (int rc = permutation()) return rc;
+    fs.start();
     alphas[0] = ch.get();
     alphas[1] = ch.get();
     fs.stop();
@@ -440,6 +506,10 @@ int ProveCall::quotient() {
         if (int rc = tiled ? run_quotient_tiles(debug, c->qvals.as<gl_t>(), true) : run_quotient_ops()) return rc;
         if (c->opt_quotient_debug == 9 && !tiled)
             if (int rc = compare_quotient_evaluators()) return rc;
+        if (s.nZ)  // P4: the permutation constraints join the fold where its values are (kernels_permutation.hip)
+            HIPCHK(launch_perm_quotient(c->perm.desc.as<uint32_t>() + s.perm_desc_words, c->lde.as<gl_t>(), c->perm.zlde.as<gl_t>(), c->perm.chal.as<gl_t>(),
+                                        c->tab->qtab.as<gl_t>(), c->qvals.as<gl_t>(), alphas[0], alphas[1], gl_pow(alphas[0], 2 * s.nZ), gl_pow(alphas[1], 2 * s.nZ),
+                                        s.log_n, s.r, s.qdb, st));
         // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
         if (int rc = run_ntt(c, c->qvals.as<gl_t>(), c->partial.as<gl_t>(), 2, size, s.log_n + s.qdb, true, nullptr, c->tab->qshift_inv.as<gl_t>()))  // (the chunks' partial sums are spent)
             return rc;
@@ -471,7 +541,7 @@ int ProveCall::quotient_commit() {
 
 // ---- phase 5: openings (App. A.7)
 int ProveCall::openings() {
-    const size_t n = s.n, C = s.C, Q = s.Q;
+    const size_t n = s.n, C = s.C, Q = s.Q, nZ = s.nZ;
     HIPCHK(stream_wait(c));  // the quotient cap
     fs.start();
     ch.observe_many(quot_cap.data(), quot_cap.size());
@@ -491,6 +561,14 @@ int ProveCall::openings() {
     HIPCHK(launch_openings(c->lde.as<gl_t>(), s.N, C, n, c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), c->open_local.as<gl2_t>(),
                            c->open_next.as<gl2_t>(), st));
     HIPCHK(launch_openings(c->qcoef.as<gl_t>(), n, Q, n, c->zpow.as<gl2_t>(), nullptr, c->open_q.as<gl2_t>(), nullptr, st));
+    if (nZ) {  // P5: the Zs at zeta and at g zeta, like the trace from coset 0 of their LDE
+        HIPCHK(launch_openings(c->perm.zlde.as<gl_t>(), s.N, nZ, n, c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), c->perm.open_z.as<gl2_t>(),
+                               c->perm.open_zn.as<gl2_t>(), st));
+        op_z.resize(nZ);
+        op_zn.resize(nZ);
+        HIPCHK(read_back(c, op_z.data(), c->perm.open_z.p, nZ * 16, st));
+        HIPCHK(read_back(c, op_zn.data(), c->perm.open_zn.p, nZ * 16, st));
+    }
     op_local.resize(C);
     op_next.resize(C);
     op_q.resize(Q);
@@ -502,24 +580,28 @@ int ProveCall::openings() {
 
 // ---- phase 6: FRI batch combination (prove_openings, App. A.8)
 int ProveCall::fri_combine() {
-    const size_t n = s.n, N = s.N, C = s.C, Q = s.Q;
+    const size_t n = s.n, N = s.N, C = s.C, Q = s.Q, nZ = s.nZ;
     HIPCHK(stream_wait(c));  // the openings
     fs.start();  // 2 (2 C + Q) field elements through the sponge, one permutation per 8: the longest host stretch of a proof
     for (size_t i = 0; i < C; i++) ch.observe_ext(op_local[i]);
+    for (size_t i = 0; i < nZ; i++) ch.observe_ext(op_z[i]);  // batch 0: local || zs || quotient, batch 1: next || zs_next (P5)
     for (size_t i = 0; i < Q; i++) ch.observe_ext(op_q[i]);
     for (size_t i = 0; i < C; i++) ch.observe_ext(op_next[i]);
+    for (size_t i = 0; i < nZ; i++) ch.observe_ext(op_zn[i]);
     const gl2_t fri_alpha = ch.get_ext();
     fs.stop();
     const gl2_t gzeta = gl2_mul_base(zeta, gl_root_of_unity(s.log_n));
-    HIPCHK(launch_ext_powers(c->ext_apow.as<gl2_t>(), fri_alpha, C + Q, st));
+    HIPCHK(launch_ext_powers(c->ext_apow.as<gl2_t>(), fri_alpha, C + nZ + Q, st));
     // sum_j alpha^j trace_j: the sum is taken on coset 0 of the LDE (n values a column) and turned into coefficients by ONE inverse
     // coset transform of its two words -- linear, so these are the coefficients of the reference's sum of coefficient vectors
     gl_t* comb_t = c->comb_out.as<gl_t>();        // [2][n] words
     gl2_t* comb_q = c->comb_out.as<gl2_t>() + n;  // [n] extension elements
     HIPCHK(launch_fri_combine(c->lde.as<gl_t>(), N, C, n, c->ext_apow.as<gl2_t>(), COMB_PPC, comb_chunks(C), c->comb_partial.as<gl2_t>(), st));
-    HIPCHK(launch_ext_reduce(c->comb_partial.as<gl2_t>(), comb_chunks(C), n, comb_t, st));
+    if (nZ)  // + sum_i alpha^(C + i) Z_i, one more chunk of the same sum
+        HIPCHK(launch_fri_combine(c->perm.zlde.as<gl_t>(), N, nZ, n, c->ext_apow.as<gl2_t>() + C, nZ, 1, c->comb_partial.as<gl2_t>() + comb_chunks(C) * n, st));
+    HIPCHK(launch_ext_reduce(c->comb_partial.as<gl2_t>(), comb_chunks(C) + (nZ ? 1 : 0), n, comb_t, st));
     if (int rc = run_ntt(c, comb_t, c->fri_vals.as<gl_t>(), 2, n, s.log_n, true, nullptr, c->tab->qshift_inv.as<gl_t>())) return rc;  // (fri_vals: idle until fri_commit)
-    HIPCHK(launch_fri_combine(c->qcoef.as<gl_t>(), n, Q, n, c->ext_apow.as<gl2_t>() + C, Q, 1, comb_q, st));  // alpha^(C+q) quotient_q
+    HIPCHK(launch_fri_combine(c->qcoef.as<gl_t>(), n, Q, n, c->ext_apow.as<gl2_t>() + C + nZ, Q, 1, comb_q, st));  // alpha^(C+nZ+q) quotient_q
     std::vector<gl_t> F1w(2 * n);
     std::vector<gl2_t> F1(n), tailq(n), F0(n), q0(n), q1(n), fin(n);
     HIPCHK(read_back(c, F1w.data(), comb_t, n * 16, st));
@@ -528,9 +610,9 @@ int ProveCall::fri_combine() {
     host_other.start();
     for (size_t k = 0; k < n; k++) F1[k] = gl2_make(F1w[k], F1w[n + k]);
     for (size_t k = 0; k < n; k++) F0[k] = gl2_add(F1[k], tailq[k]);
-    divide_by_linear(F0.data(), n, zeta, q0.data());  // batch 0: trace ++ quotient at zeta
-    divide_by_linear(F1.data(), n, gzeta, q1.data());   // batch 1: trace at g*zeta
-    const gl2_t shift = gl2_pow(fri_alpha, C);          // alpha^{|batch 1|}
+    divide_by_linear(F0.data(), n, zeta, q0.data());  // batch 0: trace ++ Zs ++ quotient at zeta
+    divide_by_linear(F1.data(), n, gzeta, q1.data());   // batch 1: trace ++ Zs at g*zeta
+    const gl2_t shift = gl2_pow(fri_alpha, C + nZ);     // alpha^{|batch 1|}
     for (size_t k = 0; k < n; k++) fin[k] = gl2_add(gl2_mul(q0[k], shift), q1[k]);
     // upload as SoA, zero padded to N (lde(rate_bits))
     std::vector<gl_t> soa(2 * N, 0);
@@ -661,6 +743,10 @@ int ProveCall::queries() {
     if (!err) {
         HIPCHK_FREE(launch_query_leaf_colmajor(c->lde.as<gl_t>(), C, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += C;
         HIPCHK_FREE(launch_query_path(c->digests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
+        if (s.nZ) {  // P6: trace, zs, quotient
+            HIPCHK_FREE(launch_query_leaf_colmajor(c->perm.zlde.as<gl_t>(), s.nZ, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += s.nZ;
+            HIPCHK_FREE(launch_query_path(c->perm.zdigests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
+        }
         HIPCHK_FREE(launch_query_leaf_colmajor(c->qlde.as<gl_t>(), Q, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += Q;
         HIPCHK_FREE(launch_query_path(c->qdigests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
         size_t len = N;
@@ -682,6 +768,11 @@ int ProveCall::queries() {
     memcpy(out + pl.off_local, op_local.data(), C * 16);
     memcpy(out + pl.off_next, op_next.data(), C * 16);
     memcpy(out + pl.off_quot_open, op_q.data(), Q * 16);
+    if (s.nZ) {
+        memcpy(out + pl.off_zs_cap, zs_cap.data(), 4 * ncap * 8);
+        memcpy(out + pl.off_zs, op_z.data(), s.nZ * 16);
+        memcpy(out + pl.off_zs_next, op_zn.data(), s.nZ * 16);
+    }
     if (L) memcpy(out + pl.off_fri_caps, fri_caps.data(), L * 4 * ncap * 8);
     HIPCHK_FREE(stream_wait(c));  // xs goes out of scope
 #undef HIPCHK_FREE
@@ -718,7 +809,8 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
     const bool tiled = c->opt_quotient_impl == 0;
     // the profiling modes and the evaluators' comparison run every constraint on every coset, like "quotient_cosets" = 1
-    const bool by_class = tiled && c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0;
+    // ... and so does an AIR with permutation pairs: their constraints join the quotient's values, which the classes never form
+    const bool by_class = tiled && c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0 && s.nZ == 0;
     if (int rc = tiled ? ensure_plan(c, air, s.size, by_class) : ensure_program(c, air, s.size)) return rc;
     const unsigned n_chunks = tiled ? c->plan->chunks : c->prog.chunks;
 
@@ -793,7 +885,7 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t
     if (ProofShape::make(air, cfg, air.default_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
     if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
-    if (int rc = ensure_plan(c, air, s.size, c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0)) return rc;
+    if (int rc = ensure_plan(c, air, s.size, c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0 && s.nZ == 0)) return rc;
     // `values`: a trace waits for its LDE inside the LDE buffer (prove(): trace_in_lde) but for the tail of run_lde_trace; rate_bits == 0
     // makes prove() ask for a whole trace.  The LDE buffer also stages the upload: a recording of log_bytes.
     const size_t values_bytes = values_bytes_for(s, s.r >= 1, false);

@@ -41,8 +41,8 @@ bool query_words_in_range(const uint64_t* proof, const ProofLayout& pl) {
     return true;
 }
 
-// A proof's words in the chunk's buffer: [trace cap | quotient cap] then [FRI caps .. final polynomial] of the blob
-size_t head_words(const ProofLayout& pl) { return 8 * pl.ncap; }
+// A proof's words in the chunk's buffer: [trace cap | (Z cap) | quotient cap] then [FRI caps .. final polynomial] of the blob
+size_t head_words(const ProofLayout& pl) { return (pl.nZ ? 12 : 8) * pl.ncap; }  // with the Z cap between them when there is one
 size_t region_words(const ProofLayout& pl) { return head_words(pl) + (pl.off_pow - pl.off_fri_caps); }
 
 }  // namespace
@@ -64,8 +64,8 @@ void verify_prelude_item(int id, const starkhip_config_t& cfg, const uint64_t* p
 }
 
 size_t verify_device_bytes(const ProofLayout& pl) {
-    const size_t per_query = (2 + pl.L) * (4 * 8 + sizeof(VQLeaf)) + 2 * sizeof(gl2_t) + 8 + 4 + 4;
-    return 8 * region_words(pl) + sizeof(gl2_t) * (pl.C + pl.Q) + pl.n_queries * per_query + sizeof(VQProof) + 4;
+    const size_t per_query = (2 + pl.L + (pl.nZ ? 1 : 0)) * (4 * 8 + sizeof(VQLeaf)) + 2 * sizeof(gl2_t) + 8 + 4 + 4;
+    return 8 * region_words(pl) + sizeof(gl2_t) * (pl.C + pl.nZ + pl.Q) + pl.n_queries * per_query + sizeof(VQProof) + 4;
 }
 
 void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
@@ -75,7 +75,9 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     const size_t h = head_words(pl);
     P.base = ch.words;
     P.query_words = pl.query_words;
-    P.off_quot_cap = 4 * pl.ncap;
+    P.off_quot_cap = (pl.nZ ? 8 : 4) * pl.ncap;
+    P.off_zs_cap = 4 * pl.ncap;
+    P.nZ = (uint32_t)pl.nZ;
     P.off_fri_caps = h;
     P.off_queries = h + (pl.off_queries - pl.off_fri_caps);
     P.off_final = h + (pl.off_final - pl.off_fri_caps);
@@ -100,12 +102,16 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     P.red0 = pre.red0;
     P.red1 = pre.red1;
     P.alpha_pow_C = pre.alpha_pow_C;
-    const size_t d0 = pl.log_N - pl.cap_h, per_q = 2 + pl.L;
+    const size_t d0 = pl.log_N - pl.cap_h, per_q = vq_slots(P);
     for (size_t q = 0; q < pl.n_queries; q++) {
         const uint32_t slot = (uint32_t)(ch.digests + q * per_q);
         size_t o = P.base + P.off_queries + q * pl.query_words;
         ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.C, slot, P.hasher, 0});
         o += pl.C + 4 * d0;
+        if (pl.nZ) {
+            ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.nZ, (uint32_t)(slot + 2 + pl.L), P.hasher, 0});
+            o += pl.nZ + 4 * d0;
+        }
         ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.Q, slot + 1, P.hasher, 0});
         o += pl.Q + 4 * d0;
         for (size_t l = 0; l < pl.L; l++) {
@@ -120,7 +126,7 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     ch.ids.push_back(id);
     ch.alphas.push_back(pre.fri_alpha);
     ch.words += region_words(pl);
-    ch.apow += pl.C + pl.Q;
+    ch.apow += pl.C + pl.nZ + pl.Q;
     ch.digests += pl.n_queries * per_q;
     ch.bytes += verify_device_bytes(pl);
 }
@@ -201,7 +207,7 @@ hipError_t verify_chunk_launch(const VerifyChunk& ch, const VerifyDevBufs& b, hi
     hipError_t e = hipSuccess;
     for (size_t k = 0; k < ch.proofs.size() && e == hipSuccess; k++) {
         const VQProof& P = ch.proofs[k];
-        e = launch_ext_powers(b.apow + P.apow, ch.alphas[k], P.C + P.Q, st);
+        e = launch_ext_powers(b.apow + P.apow, ch.alphas[k], P.C + P.nZ + P.Q, st);
     }
     if (e == hipSuccess) e = launch_verify_range(b.words, b.proofs, ch.proofs.size(), b.bad, st);
     if (e == hipSuccess) e = launch_verify_leaf_digests(b.words, b.leaves, ch.leaves.size(), b.dig, ch.hashers, st);
@@ -258,10 +264,12 @@ void verify_host_combine(const gl_t* W, const VQProof* proofs, const uint32_t* q
         const VQProof& P = proofs[query_proof[g]];
         const uint32_t qi = (uint32_t)g - P.first_query;
         const gl_t* tleaf = W + P.base + P.off_queries + (uint64_t)qi * P.query_words;
-        const gl_t* qleaf = tleaf + P.C + 4 * (P.log_N - P.cap_h);
+        const gl_t* zleaf = tleaf + P.C + 4 * (P.log_N - P.cap_h);
+        const gl_t* qleaf = tleaf + vq_quot_leaf_off(P);
         gl2_t st = gl2_zero(), sq = gl2_zero();
         for (uint32_t c = 0; c < P.C; c++) st = gl2_add(st, gl2_mul_base(apow[P.apow + c], tleaf[c]));
-        for (uint32_t q = 0; q < P.Q; q++) sq = gl2_add(sq, gl2_mul_base(apow[P.apow + P.C + q], qleaf[q]));
+        for (uint32_t z = 0; z < P.nZ; z++) st = gl2_add(st, gl2_mul_base(apow[P.apow + P.C + z], zleaf[z]));
+        for (uint32_t q = 0; q < P.Q; q++) sq = gl2_add(sq, gl2_mul_base(apow[P.apow + P.C + P.nZ + q], qleaf[q]));
         sums[2 * g] = gl2_add(st, sq);
         sums[2 * g + 1] = st;
     }
@@ -272,7 +280,7 @@ void verify_host_queries(const gl_t* W, const VQProof* proofs, const uint32_t* q
     for (size_t g = 0; g < n_queries; g++) {
         const VQProof& P = proofs[query_proof[g]];
         const uint32_t qi = (uint32_t)g - P.first_query;
-        status[g] = vq_check_query(P, W + P.base, dig + 4 * ((size_t)P.first_digest + (size_t)qi * (2 + P.L)), sums[2 * g], sums[2 * g + 1],
+        status[g] = vq_check_query(P, W + P.base, dig + 4 * ((size_t)P.first_digest + (size_t)qi * vq_slots(P)), sums[2 * g], sums[2 * g + 1],
                                    x_index[g], qi);
     }
 }
@@ -455,7 +463,7 @@ int verify_batch_replay(size_t n, const starkhip_air_t* airs, const starkhip_con
             VerifyPiece pc[2];
             verify_pieces(ch, k, proofs[id], items[id].pre.pl, pc);
             for (const VerifyPiece& p : pc) memcpy(W.data() + p.dst, p.src, p.words * 8);
-            verify_host_ext_powers(apow.data() + ch.proofs[k].apow, ch.alphas[k], (size_t)ch.proofs[k].C + ch.proofs[k].Q);
+            verify_host_ext_powers(apow.data() + ch.proofs[k].apow, ch.alphas[k], (size_t)ch.proofs[k].C + ch.proofs[k].nZ + ch.proofs[k].Q);
         }
         verify_host_range(W.data(), ch.proofs.data(), ch.proofs.size(), bad.data());
         verify_host_leaf_digests(W.data(), ch.leaves.data(), ch.leaves.size(), dig.data());

@@ -24,11 +24,14 @@ enum : uint32_t {
     VQ_FRI_COSET = 4u,    // a layer's coset value differs from the previous layer's evaluation (the first: the sum at x)
     VQ_FRI_PATH = 8u,     // a layer's leaf -> that layer's cap
     VQ_FINAL_POLY = 16u,  // the final polynomial at x differs from the last evaluation
+    VQ_PERM_PATH = 32u,   // permutation Z leaf -> Z cap (proofs with nZ > 0)
 };
 
 // What the queries of one proof need, in the device word buffer.  A proof's region there is
-//   [trace cap | quotient cap | FRI caps | query rounds | final polynomial]
+//   [trace cap | (Z cap) | quotient cap | FRI caps | query rounds | final polynomial]
 // (the blob's words off_trace_cap .. off_quot_cap + 4 ncap, then off_fri_caps .. off_pow; openings and the rest stay on the host).
+// A proof with permutation Zs (nZ > 0) has its Z cap between the other two, the Z leaf and its siblings between the trace's and the
+// quotient's in every round, and one more digest per query, the last of the query's slots.
 struct VQProof {
     uint64_t base;         // first word of the region
     uint64_t query_words;  // words per query round
@@ -36,9 +39,11 @@ struct VQProof {
     uint64_t apow;         // first element of this proof's powers of the FRI alpha (C + Q of them)
     uint32_t C, Q, L, log_N, cap_h, final_len;
     uint32_t first_query;   // global index of query 0 (statuses, indices, sums)
-    uint32_t first_digest;  // global slot of query 0's trace-leaf digest; query q's are first_digest + q (2 + L) + {0: trace, 1: quotient, 2 + l: layer l}
+    uint32_t first_digest;  // global slot of query 0's trace-leaf digest; query q's are first_digest + q vq_slots(P) + {0: trace, 1: quotient, 2 + l: layer l, 2 + L: Z}
     uint32_t arity_bits[VQ_MAX_LAYERS], layer_depth[VQ_MAX_LAYERS];
     uint32_t hasher;        // the proof's hasher id (header word 12): every Merkle path of its queries is checked under it
+    uint32_t nZ;            // permutation Z polynomials (header word 13); 0: no Z cap, leaf or digest
+    uint64_t off_zs_cap;    // within the region (nZ > 0)
     gl2_t zeta, gzeta, red0, red1, alpha_pow_C;
     gl2_t betas[VQ_MAX_LAYERS];
 };
@@ -49,6 +54,14 @@ struct VQLeaf {
     uint32_t len, slot;
     uint32_t hasher, pad_;
 };
+
+// digest slots per query
+GL_HD uint32_t vq_slots(const VQProof& P) { return 2 + P.L + (P.nZ ? 1u : 0u); }
+// words of a query round in front of the quotient leaf: the trace leaf and its siblings, then the Z leaf and its siblings
+GL_HD uint64_t vq_quot_leaf_off(const VQProof& P) {
+    const uint64_t d0 = P.log_N - P.cap_h;
+    return P.C + 4 * d0 + (P.nZ ? P.nZ + 4 * d0 : 0);
+}
 
 GL_HD void vq_two_to_one(uint32_t hasher, const gl_t* a, const gl_t* b, gl_t* out) {
     if (hasher == STARKHIP_HASHER_KECCAK) {
@@ -120,16 +133,17 @@ GL_HD gl2_t vq_fold_eval(gl_t x, uint64_t within, uint32_t arity_bits, const gl_
 }
 
 // Every check of query `qi` of proof P.  region: the proof's words; digests: this query's 2 + L leaf digests (4 words each);
-// e0, e1: fri_combine_initial's two sums over the opened trace and quotient leaves; x_index: the query's index into the LDE.
+// e0, e1: fri_combine_initial's two sums over the opened trace, Z and quotient leaves; x_index: the query's index into the LDE.
 // 0 = accepted; otherwise the VQ_* bits of the checks that failed.
 GL_HD uint32_t vq_check_query(const VQProof& P, const gl_t* region, const gl_t* digests, gl2_t e0, gl2_t e1, uint64_t x_index, uint32_t qi) {
     uint32_t status = 0;
     const uint32_t d0 = P.log_N - P.cap_h;
     const gl_t* qp = region + P.off_queries + (uint64_t)qi * P.query_words;
     const gl_t* tsib = qp + P.C;
-    const gl_t* qsib = tsib + 4 * d0 + P.Q;
+    const gl_t* qsib = qp + vq_quot_leaf_off(P) + P.Q;
     qp = qsib + 4 * d0;
     if (!vq_path_to_cap(P.hasher, digests, x_index, region, tsib, d0)) status |= VQ_TRACE_PATH;
+    if (P.nZ && !vq_path_to_cap(P.hasher, digests + 4 * (2 + P.L), x_index, region + P.off_zs_cap, tsib + 4 * d0 + P.nZ, d0)) status |= VQ_PERM_PATH;
     if (!vq_path_to_cap(P.hasher, digests + 4, x_index, region + P.off_quot_cap, qsib, d0)) status |= VQ_QUOT_PATH;
     gl_t subgroup_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(P.log_N), gl_bitrev((uint32_t)x_index, P.log_N)));
     const gl2_t xe = gl2_from_base(subgroup_x);

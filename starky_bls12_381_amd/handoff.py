@@ -4,9 +4,9 @@
 
 Shape (field names and nesting of starky 0.1.x / plonky2 0.1.x, restated from memory of the crates, SURVEY App. A.9;
 they are NOT under /root/reference and there is no Rust toolchain here, so this mapping is unpinned):
-  {"proof": {"trace_cap": [HashOut..], "permutation_zs_cap": null, "quotient_polys_cap": [HashOut..],
-             "openings": {"local_values": [Ext..], "next_values": [Ext..], "permutation_zs": null,
-                          "permutation_zs_next": null, "quotient_polys": [Ext..]},
+  {"proof": {"trace_cap": [HashOut..], "permutation_zs_cap": null | [HashOut..], "quotient_polys_cap": [HashOut..],
+             "openings": {"local_values": [Ext..], "next_values": [Ext..], "permutation_zs": null | [Ext..],
+                          "permutation_zs_next": null | [Ext..], "quotient_polys": [Ext..]},
              "opening_proof": {"commit_phase_merkle_caps": [[HashOut..]..],
                                "query_round_proofs": [{"initial_trees_proof": {"evals_proofs": [[[F..], {"siblings": [HashOut..]}], ..]},
                                                        "steps": [{"evals": [Ext..], "merkle_proof": {"siblings": [HashOut..]}}, ..]}, ..],
@@ -30,6 +30,7 @@ class _Layout:
             raise ValueError("not a starkhip proof blob")
         (self.C, self.Q, self.log_n, self.rate_bits, self.cap_h, self.L, self.n_queries, self.final_len, self.n_pis, self.arity_bits,
          self.n_challenges) = h[1:12]
+        self.nZ = h[13]  # permutation Z polynomials: 0 for an AIR without permutation pairs
         self.ncap = 1 << self.cap_h
         self.log_N = self.log_n + self.rate_bits
         self.depth0 = self.log_N - self.cap_h
@@ -41,7 +42,7 @@ class _Layout:
 
     def header(self):
         return [MAGIC, self.C, self.Q, self.log_n, self.rate_bits, self.cap_h, self.L, self.n_queries, self.final_len, self.n_pis, self.arity_bits,
-                self.n_challenges, 0, 0, 0, 0]
+                self.n_challenges, 0, self.nZ, 0, 0]
 
 
 def _hashes(words):
@@ -70,15 +71,18 @@ def proof_to_value(blob):
         pos += n
         return out
     trace_cap = _hashes(take(4 * lay.ncap))
+    zs_cap = _hashes(take(4 * lay.ncap)) if lay.nZ else None  # Option<MerkleCap>: Some for an AIR with permutation pairs
     quot_cap = _hashes(take(4 * lay.ncap))
     local_values = _exts(take(2 * lay.C))
     next_values = _exts(take(2 * lay.C))
+    zs = _exts(take(2 * lay.nZ)) if lay.nZ else None
+    zs_next = _exts(take(2 * lay.nZ)) if lay.nZ else None
     quotient_polys = _exts(take(2 * lay.Q))
     caps = [_hashes(take(4 * lay.ncap)) for _ in range(lay.L)]
     rounds = []
     for _ in range(lay.n_queries):
         evals_proofs = []
-        for width in (lay.C, lay.Q):  # oracle 0 = trace, oracle 1 = quotient polys (no permutation oracle)
+        for width in ((lay.C, lay.nZ, lay.Q) if lay.nZ else (lay.C, lay.Q)):  # the oracles: trace, [permutation Zs,] quotient polys
             leaf = [int(x) for x in take(width)]
             evals_proofs.append([leaf, {"siblings": _hashes(take(4 * lay.depth0))}])
         steps = []
@@ -94,9 +98,9 @@ def proof_to_value(blob):
     return {
         "proof": {
             "trace_cap": trace_cap,
-            "permutation_zs_cap": None,
+            "permutation_zs_cap": zs_cap,
             "quotient_polys_cap": quot_cap,
-            "openings": {"local_values": local_values, "next_values": next_values, "permutation_zs": None, "permutation_zs_next": None,
+            "openings": {"local_values": local_values, "next_values": next_values, "permutation_zs": zs, "permutation_zs_next": zs_next,
                          "quotient_polys": quotient_polys},
             "opening_proof": {"commit_phase_merkle_caps": caps, "query_round_proofs": rounds, "final_poly": final_poly,
                               "pow_witness": pow_witness},
@@ -111,8 +115,9 @@ def value_to_proof(value, degree_bits, rate_bits, arity_bits=4, num_challenges=2
     op, fri = p["openings"], p["opening_proof"]
     C, Q = len(op["local_values"]), len(op["quotient_polys"])
     cap_h = (len(p["trace_cap"]) - 1).bit_length()
+    nZ = len(op["permutation_zs"]) if op.get("permutation_zs") else 0
     words = [MAGIC, C, Q, degree_bits, rate_bits, cap_h, len(fri["commit_phase_merkle_caps"]), len(fri["query_round_proofs"]),
-             len(fri["final_poly"]["coeffs"]), len(value["public_inputs"]), arity_bits, num_challenges, 0, 0, 0, 0]
+             len(fri["final_poly"]["coeffs"]), len(value["public_inputs"]), arity_bits, num_challenges, 0, nZ, 0, 0]
 
     def put_hashes(hs):
         for h in hs:
@@ -122,9 +127,14 @@ def value_to_proof(value, degree_bits, rate_bits, arity_bits=4, num_challenges=2
         for e in es:
             words.extend(e)
     put_hashes(p["trace_cap"])
+    if nZ:
+        put_hashes(p["permutation_zs_cap"])
     put_hashes(p["quotient_polys_cap"])
     put_exts(op["local_values"])
     put_exts(op["next_values"])
+    if nZ:
+        put_exts(op["permutation_zs"])
+        put_exts(op["permutation_zs_next"])
     put_exts(op["quotient_polys"])
     for cap in fri["commit_phase_merkle_caps"]:
         put_hashes(cap)
