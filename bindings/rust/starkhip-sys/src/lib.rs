@@ -199,6 +199,27 @@ pub struct starkhip_free_cell_classes_t {
     pub constraints_never_open: u64,
 }
 
+/// `STARKHIP_PERM_CHECK_ATTEMPTS`: the seeds `starkhip_check_trace_permutations` tries for a pair before it calls it undecided.
+pub const STARKHIP_PERM_CHECK_ATTEMPTS: usize = 4;
+
+/// `starkhip_perm_check_t`: the summary of `starkhip_check_trace_permutations`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct starkhip_perm_check_t {
+    /// the AIR's permutation pairs
+    pub pairs: u64,
+    /// decided pairs with at least one unmatched row
+    pub pairs_violated: u64,
+    /// pairs whose sort keys collided under every attempt seed (per_pair = u32::MAX)
+    pub pairs_undecided: u64,
+    /// flagged rows over all decided pairs, both sides (even)
+    pub unmatched: u64,
+    /// entries written to `list`: min(cap, unmatched)
+    pub listed: u64,
+    /// reruns of a pair because two different tuples shared a key
+    pub reseeds: u64,
+}
+
 extern "C" {
     pub fn starkhip_config_standard_fast(cfg: *mut starkhip_config_t);
     pub fn starkhip_config_for_air(air: Air, cfg: *mut starkhip_config_t) -> c_int;
@@ -260,6 +281,21 @@ extern "C" {
     pub fn starkhip_check_trace_free_cell_classes_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                                          public_inputs: *const u64, delta: u64, per_column: *mut u32, planes: *mut u64,
                                                          open_rows: *mut u32, out: *mut starkhip_free_cell_classes_t) -> c_int;
+    // The permutation pairs of a registered AIR, pair by pair and exactly: which rows of a pair's lhs columns have no partner among the rows
+    // of its rhs columns, and the other way round.  seed: 2 <= seed < p (draw it at random); per_pair [starkhip_air_permutation_pairs(air)]
+    // or null (u32::MAX: undecided), masks [n_pairs][2][(n_rows + 63) / 64] or null (lhs, rhs; bit r & 63 of word r >> 6), list
+    // cap x {pair, side, row} (may be null when cap == 0; cap <= STARKHIP_CHECK_LIST_MAX), by pair, side, row.
+    pub fn starkhip_check_trace_permutations(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                             on_device: c_int, seed: u64, per_pair: *mut u32, masks: *mut u64, list: *mut u64, cap: usize,
+                                             out: *mut starkhip_perm_check_t) -> c_int;
+    // tests: the same host driver over host loops (std::stable_sort); `trace` is host memory
+    pub fn starkhip_check_trace_permutations_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int, seed: u64,
+                                                    per_pair: *mut u32, masks: *mut u64, list: *mut u64, cap: usize,
+                                                    out: *mut starkhip_perm_check_t) -> c_int;
+    // out [STARKHIP_PERM_CHECK_ATTEMPTS]: the seeds the check tries for `seed`, in order
+    pub fn starkhip_perm_check_seeds(seed: u64, out: *mut u64) -> c_int;
+    // ms [4]: upload, sort, classification, read-back of the context's last starkhip_check_trace_permutations
+    pub fn starkhip_perm_check_timings(ctx: *mut c_void, ms: *mut f32) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

@@ -298,8 +298,56 @@ int starkhip_check_trace_free_cell_classes(void* ctx, starkhip_air_t air, const 
 int starkhip_check_trace_free_cell_classes_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
                                                   const uint64_t* public_inputs, uint64_t delta, uint32_t* per_column, uint64_t* planes,
                                                   uint32_t* open_rows, starkhip_free_cell_classes_t* out);
+/* The trace checkers above look at the AIR's own constraints.  This one looks at its PERMUTATION PAIRS (starky's permutation_pairs()),
+ * one pair at a time and exactly: are the rows of the pair's lhs columns a permutation of the rows of its rhs columns, and if not,
+ * which rows have no partner?  The rule, per pair q of the AIR (not per batch): a row r holds on each side a tuple of n_entries cells,
+ * every cell read mod p as every trace reader does.  Let L(v) be the number of lhs rows holding tuple v and R(v) the number of rhs
+ * rows holding it.  The pair holds when L(v) = R(v) for every v.  Otherwise, for every v with L(v) > R(v) the L - R HIGHEST lhs rows
+ * holding v are UNMATCHED, and for every v with R(v) > L(v) the R - L highest rhs rows holding v are: each side of a pair has the
+ * same number of unmatched rows.  The result is a pure function of (AIR, trace mod p), the same bytes on every run whatever `seed`
+ * (except for pairs reported undecided, below); the trace need not satisfy the AIR's own constraints.
+ * One consequence (COMPAT.md 2a): the argument of a proof uses one (beta, gamma) for a whole batch, so a proof shows only that the
+ * UNION of a batch's lhs tuples equals the union of its rhs tuples, with tuples of different widths that agree up to trailing zeros
+ * identified.  A trace can close every Z of starkhip_permutation_zs and still fail this check: a finding about how the pairs are
+ * batched, not a false alarm.
+ * How: the rows are sorted by a 64-bit key, key(row) = sum_t seed^t cell_t mod p (for a one-entry pair the cell itself: exact and
+ * independent of the seed), and every item whose key equals its predecessor's compares its tuple with the predecessor's cell by
+ * cell.  If all agree, equal keys mean equal tuples and the answer is exact.  If two different tuples shared a key the pair is run
+ * again under the next seed, s' = 7 s + 1 mod p (applied again while below 2), STARKHIP_PERM_CHECK_ATTEMPTS seeds in all
+ * (starkhip_perm_check_seeds lists them); a pair that still collides is UNDECIDED: per_pair = UINT32_MAX, zero masks, nothing in
+ * `unmatched` or `list`, and the call still returns STARKHIP_OK.  As with delta above, draw seed at random for a real audit.
+ *   per_pair (starkhip_air_permutation_pairs(air) entries, or NULL): the unmatched rows per side; UINT32_MAX = undecided;
+ *   masks (n_pairs x 2 x (n_rows + 63) / 64 words, or NULL): [pair][side: 0 lhs, 1 rhs], bit (r & 63) of word r >> 6 = row r unmatched;
+ *   list (cap x {pair, side, row}; may be NULL when cap == 0): the first min(cap, unmatched) flagged rows in the order pair, side
+ *     (lhs first), row ascending.
+ * trace, n_rows, n_cols, layout, on_device and their BAD_SHAPE cases are starkhip_check_trace's (both layouts, host or device memory,
+ * column-major device memory read in place, 2 .. 2^STARKHIP_MAX_LOG_ROWS rows).  BAD_AIR for an unknown AIR or one without pairs;
+ * BAD_SHAPE also for seed < 2 or seed >= p, cap > STARKHIP_CHECK_LIST_MAX, a NULL `out`, a NULL `list` with cap > 0.  One call at a
+ * time per context, not beside a prove on it.  On the context's device: a stable radix sort and a classification per pair
+ * (csrc/kernels_multiset.hip); the masks are read back only for a violated pair and only when `masks` or `list` asks for them. */
+#define STARKHIP_PERM_CHECK_ATTEMPTS 4
+typedef struct {
+    uint64_t pairs, pairs_violated, pairs_undecided;
+    uint64_t unmatched;   /* flagged rows over all decided pairs, both sides (even) */
+    uint64_t listed;      /* entries written to `list`: min(cap, unmatched) */
+    uint64_t reseeds;     /* reruns of a pair because two different tuples shared a key */
+} starkhip_perm_check_t;
+int starkhip_check_trace_permutations(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                      int on_device, uint64_t seed, uint32_t* per_pair, uint64_t* masks, uint64_t* list, size_t cap,
+                                      starkhip_perm_check_t* out);
+/* tests: the same host driver -- argument checks, the seed sequence, undecided pairs, the list from the masks, the summary -- with the
+ * device steps replaced by host loops: the keys, std::stable_sort by key, the same classification.  `trace` is host memory.  No device
+ * needed. */
+int starkhip_check_trace_permutations_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, uint64_t seed,
+                                             uint32_t* per_pair, uint64_t* masks, uint64_t* list, size_t cap, starkhip_perm_check_t* out);
+/* out = the seeds the check tries for `seed`, in order.  BAD_SHAPE for seed < 2, seed >= p or a NULL out. */
+int starkhip_perm_check_seeds(uint64_t seed, uint64_t out[STARKHIP_PERM_CHECK_ATTEMPTS]);
+/* ms = {upload and gather of the pair columns, keys and sort passes, classification and counts, read-backs of masks} of the last
+ * starkhip_check_trace_permutations on this context: the first three from events on its stream, summed over pairs and attempts, the
+ * last the host's time in the copies. */
+int starkhip_perm_check_timings(void* ctx, float ms[4]);
 
-/* --- natives + trace generation (host) ----------------------------------------------- */
+/* --- natives + trace generation (host)----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.
  * trace is written row-major [n_rows][columns]; public_inputs has starkhip_air_public_inputs() entries. */
 int starkhip_trace_fp12_mul(const uint32_t x[144], const uint32_t y[144], uint64_t* trace, size_t n_rows, uint64_t* public_inputs);

@@ -644,6 +644,87 @@ def permutation_zs_replay(air, trace, challenges, layout=0):
     return zs, closing
 
 
+PERM_CHECK_ATTEMPTS = 4  # STARKHIP_PERM_CHECK_ATTEMPTS
+PERM_UNDECIDED = 0xFFFFFFFF  # per_pair of a pair whose keys collided under every attempt seed
+
+
+class _PermCheckStruct(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("pairs", "pairs_violated", "pairs_undecided", "unmatched", "listed", "reseeds")]
+
+
+lib.starkhip_check_trace_permutations.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_uint64, _u32p, _u64p,
+                                                  _u64p, C.c_size_t, C.POINTER(_PermCheckStruct)]
+lib.starkhip_check_trace_permutations_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_uint64, _u32p, _u64p, _u64p,
+                                                         C.c_size_t, C.POINTER(_PermCheckStruct)]
+lib.starkhip_perm_check_seeds.argtypes = [C.c_uint64, _u64p]
+lib.starkhip_perm_check_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+# The seed of the sort keys when the caller names none: fixed, so that a run can be reproduced.  The result does not depend on it except
+# for pairs reported undecided; a real audit should pass a random one, 2 <= seed < P.
+DEFAULT_SEED = 0x9E3779B97F4A7C15
+
+
+def perm_check_seeds(seed=DEFAULT_SEED):
+    """The seeds check_trace_permutations tries for `seed`, in order (starkhip_perm_check_seeds): a list of PERM_CHECK_ATTEMPTS ints."""
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    out = np.zeros(PERM_CHECK_ATTEMPTS, dtype=np.uint64)
+    _chk(lib.starkhip_perm_check_seeds(seed, _p64(out)))
+    return [int(x) for x in out]
+
+
+class PermutationCheck:
+    """What starkhip_check_trace_permutations found, pair by pair of the AIR: `pairs`, `pairs_violated`, `pairs_undecided`; `unmatched`:
+    the flagged rows over all decided pairs, both sides; `reseeds`: reruns of a pair because two different tuples shared a sort key;
+    `per_pair` (np.uint32[n_pairs]): the unmatched rows per side, PERM_UNDECIDED for an undecided pair; `masks` (bool[n_pairs, 2, n]):
+    masks[q, side, r] is True when row r of pair q's lhs (side 0) or rhs (side 1) has no partner; `mask_words` (np.uint64[n_pairs, 2,
+    (n + 63) // 64]): the same as the library wrote it; `list` (np.uint64[listed, 3]): the first min(cap, unmatched) flagged rows as
+    (pair, side, row), by pair, side (lhs first), row."""
+
+    def __init__(self, summary, per_pair, words, entries, n_rows):
+        self.pairs, self.pairs_violated, self.pairs_undecided = int(summary.pairs), int(summary.pairs_violated), int(summary.pairs_undecided)
+        self.unmatched, self.reseeds = int(summary.unmatched), int(summary.reseeds)
+        self.per_pair, self.mask_words = per_pair, words
+        self.list = entries[:int(summary.listed)].copy()
+        self._n_rows, self._masks = n_rows, None
+
+    @property
+    def masks(self):  # unpacked on first use: eight times the words
+        if self._masks is None:
+            bits = np.unpackbits(self.mask_words.view(np.uint8).reshape(self.mask_words.shape[0], 2, -1), axis=2, bitorder="little")
+            self._masks = np.ascontiguousarray(bits[:, :, :self._n_rows]).astype(bool)
+        return self._masks
+
+    def __repr__(self):
+        return (f"PermutationCheck(pairs={self.pairs}, pairs_violated={self.pairs_violated}, pairs_undecided={self.pairs_undecided}, "
+                f"unmatched={self.unmatched}, listed={len(self.list)}, reseeds={self.reseeds})")
+
+
+def _check_trace_permutations(call, air, n_rows, seed, cap):
+    """`call(seed, per_pair, masks, list, cap, summary)` -> rc: one of the two entry points with its leading arguments bound."""
+    seed, cap = int(seed), int(cap)
+    if cap < 0 or not 0 <= seed < 1 << 64:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_pairs = air_permutation_pairs(air)
+    per = np.zeros(n_pairs, dtype=np.uint32)
+    words = np.zeros((n_pairs, 2, (n_rows + 63) // 64), dtype=np.uint64)
+    entries = np.zeros((min(cap, CHECK_LIST_MAX), 3), dtype=np.uint64)  # a larger cap is the library's to refuse
+    summary = _PermCheckStruct()
+    _chk(call(seed, per.ctypes.data_as(_u32p), _p64(words) if n_pairs else None, _p64(entries) if cap else None, cap, C.byref(summary)))
+    return PermutationCheck(summary, per, words, entries, n_rows)
+
+
+def check_trace_permutations_replay(air, trace, layout=0, seed=DEFAULT_SEED, cap=1024):
+    """starkhip_check_trace_permutations_replay (tests): Prover.check_trace_permutations' host driver with the device steps replaced by
+    host loops -- the keys, std::stable_sort, the same classification.  No device needed."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    return _check_trace_permutations(lambda *a: lib.starkhip_check_trace_permutations_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols,
+                                                                                            layout, *a), air, n_rows, seed, cap)
+
+
 # ----------------------------------------------------------------------------- traces (generate_trace)
 class CompactTrace:
     """A trace recorded as runs (starkhip_trace_log_*): the generator's limb vectors with the rows they
@@ -945,6 +1026,34 @@ class Prover:
         _chk(lib.starkhip_permutation_zs(self._ctx, air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, _p64(challenges), _p64(zs),
                                          _p64(closing)))
         return zs, closing
+
+    def check_trace_permutations(self, air, trace, layout=0, seed=DEFAULT_SEED, cap=1024):
+        """Which rows of each permutation pair of `air` have no partner on the pair's other side (starkhip_check_trace_permutations): a
+        PermutationCheck.  Exact and per pair -- a sort and a classification on this context's device -- where the closing products
+        of permutation_zs speak of a whole batch under random challenges."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        if trace.ndim != 2 or layout not in (0, 1):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+        return self._check_trace_permutations(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, seed, cap)
+
+    def check_trace_permutations_device(self, air, trace_ptr, n_rows, layout=1, seed=DEFAULT_SEED, cap=1024):
+        """check_trace_permutations on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
+        return self._check_trace_permutations(air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, seed, cap)
+
+    def _check_trace_permutations(self, air, trace_arg, n_rows, n_cols, layout, on_device, seed, cap):
+        t0 = time.perf_counter()
+        try:
+            return _check_trace_permutations(lambda *a: lib.starkhip_check_trace_permutations(self._ctx, air, trace_arg, n_rows, n_cols, layout,
+                                                                                             on_device, *a), air, n_rows, seed, cap)
+        finally:
+            self.last_call_s = time.perf_counter() - t0
+
+    def last_perm_check_timings(self):
+        """Milliseconds of the last check_trace_permutations: {upload, sort, classify, read_back} (starkhip_perm_check_timings)."""
+        ms = (C.c_float * 4)()
+        _chk(lib.starkhip_perm_check_timings(self._ctx, ms))
+        return dict(zip(("upload", "sort", "classify", "read_back"), (float(x) for x in ms)))
 
     def check_trace_device(self, air, trace_ptr, n_rows, public_inputs, layout=1):
         """check_trace on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""

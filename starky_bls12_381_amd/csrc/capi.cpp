@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "lde_ranges.h"
 #include "permutation.h"
+#include "permutation_check.h"
 #include "trace_log.h"
 
 #include <atomic>
@@ -321,6 +322,37 @@ int starkhip_check_trace_free_cell_classes_replay(starkhip_air_t air, const uint
     const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
     if (int rc = checker_args(a, in, public_inputs, out, free_cells_bad_delta(delta))) return rc;
     return guarded([&] { return check_trace_free_cell_classes_replay(*a, in, public_inputs, delta, per_column, planes, open_rows, out); });
+}
+
+int starkhip_check_trace_permutations(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                                      int on_device, uint64_t seed, uint32_t* per_pair, uint64_t* masks, uint64_t* list, size_t cap,
+                                      starkhip_perm_check_t* out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = perm_check_args(a, in, seed, list, cap, out)) return rc;
+    return guarded([&] { return check_trace_permutations((Ctx*)ctx, *a, in, seed, per_pair, masks, list, cap, out); });
+}
+
+int starkhip_check_trace_permutations_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, uint64_t seed,
+                                             uint32_t* per_pair, uint64_t* masks, uint64_t* list, size_t cap, starkhip_perm_check_t* out) {
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = perm_check_args(a, in, seed, list, cap, out)) return rc;
+    return guarded([&] { return check_trace_permutations_replay(*a, in, seed, per_pair, masks, list, cap, out); });
+}
+
+int starkhip_perm_check_seeds(uint64_t seed, uint64_t out[STARKHIP_PERM_CHECK_ATTEMPTS]) {
+    if (perm_check_bad_seed(seed) || !out) return STARKHIP_ERR_BAD_SHAPE;
+    perm_check_seeds(seed, out);
+    return STARKHIP_OK;
+}
+
+int starkhip_perm_check_timings(void* ctx, float ms[4]) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    if (!ms) return STARKHIP_ERR_BAD_SHAPE;
+    perm_check_timings((Ctx*)ctx, ms);
+    return STARKHIP_OK;
 }
 
 int starkhip_quotient_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[8]) {

@@ -177,6 +177,7 @@ struct Ctx {
         for (DevBuf* b : chk.bufs()) v.push_back(b);
         for (DevBuf* b : free_chk.bufs()) v.push_back(b);
         for (DevBuf* b : perm.bufs()) v.push_back(b);
+        for (DevBuf* b : mset.bufs()) v.push_back(b);
         for (auto& t : table_cache)
             for (DevBuf* b : t->bufs()) v.push_back(b);
         for (auto& d : plan_cache)
@@ -201,6 +202,14 @@ struct Ctx {
         DevBuf cols, desc, chal, zvals, zcoef, zlde, zdigests, scan, open_z, open_zn;
         std::vector<DevBuf*> bufs() { return {&cols, &desc, &chal, &zvals, &zcoef, &zlde, &zdigests, &scan, &open_z, &open_zn}; }
     } perm;
+    // starkhip_check_trace_permutations (check_trace.hip over kernels_multiset.hip), sized for ONE pair and grown like the ones above:
+    // the pairs' columns as indices into perm.cols, the two (key, idx) buffers of the sort (48 MB at 2^20 rows), the digit table with
+    // its chunk sums, the two masks followed by the counters.  ms: the last call's timings (starkhip_perm_check_timings).
+    struct MultisetBufs {
+        DevBuf desc, keys, idx, table, masks;
+        float ms[4] = {0, 0, 0, 0};
+        std::vector<DevBuf*> bufs() { return {&desc, &keys, &idx, &table, &masks}; }
+    } mset;
 };
 
 // ---- ctx.hip

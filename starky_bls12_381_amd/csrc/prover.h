@@ -87,6 +87,11 @@ int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, con
 // (kernels_free_classes.hip, free_cells.h)
 int check_trace_free_cell_classes(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
                                   uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out);
+// starkhip_check_trace_permutations: which rows of each permutation pair have no partner on the other side (kernels_multiset.hip,
+// permutation_check.h); perm_check_timings: the last call's {upload, sort, classify, read-back} milliseconds
+int check_trace_permutations(Ctx* c, const AirInfo& air, const TraceInput& in, uint64_t seed, uint32_t* per_pair, uint64_t* masks, uint64_t* list,
+                             size_t cap, starkhip_perm_check_t* out);
+void perm_check_timings(Ctx* c, float ms[4]);
 int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out);
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);
