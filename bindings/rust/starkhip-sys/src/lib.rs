@@ -307,6 +307,9 @@ extern "C" {
 
     pub fn starkhip_init(device_ordinal: c_int, ctx: *mut *mut c_void) -> c_int;
     pub fn starkhip_shutdown(ctx: *mut c_void);
+    // names and values: include/starkhip.h -- among them "hasher", "check_trace", "check_trace_list", "leaf_hash_form" and
+    // "leaf_hash_prefix" (default 1: the lane and pair forms of the leaf hash start a trace whose first `rows` columns are the unit vectors
+    // e_0 .. e_{rows-1} from a saved state past them; 0: every block is hashed; the same proof bytes either way)
     pub fn starkhip_set_option(ctx: *mut c_void, name: *const c_char, value: c_long) -> c_int;
     pub fn starkhip_prove(ctx: *mut c_void, air: Air, cfg: *const starkhip_config_t, trace: *const u64, n_rows: usize, n_cols: usize,
                           trace_layout: c_int, trace_on_device: c_int, public_inputs: *const u64, n_pis: usize, pow_witness: u64,

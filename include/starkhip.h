@@ -423,6 +423,11 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
  * the pair form -- two lanes per leaf, one 256-register wave per SIMD -- and the ones between in the quad form; 1 = quad always; 2 = row always;
  * 3 = lane form, one lane per leaf: what a pool with five or more big contexts uses for groups of big commitments, slower than the pair form for
  * one commitment alone; 4 = pair always; same digests; a pool's commitments always go through its scheduler),
+ * "leaf_hash_prefix" (1, the default = the lane and pair forms start the leaves of a Poseidon-hashed trace of 2^12 or 2^13 rows and at
+ * least rows + 8 columns from a saved state past its first `rows` columns when those are the unit vectors e_0 .. e_{rows-1} -- FinalExp's
+ * one-hot row selectors, 1 024 of its 9 191 permutations per leaf; each proof decides on the device, from what its own LDE found, and a
+ * trace without that prefix is hashed in full; 0 = the kernels are never given the saved state; same bytes either way; 1 MB of device
+ * memory per context and shape),
  * "lde_impl" (1 = 8192-row traces through lde_columns_v2_kernel instead of the wave-resident kernel; same bytes), "zeta_on_coset"
  * (TESTS ONLY: k + 1 substitutes zeta = 7 w_n^k for the transcript's challenge, a point of the coset the trace values are kept on -- the
  * branch a real transcript takes with probability 2^-115; the result is compared with the oracle under the same substitution and is not a
@@ -746,9 +751,19 @@ int starkhip_poseidon_permute_batch_form(void* ctx, int form, int variant, uint6
  * N = 2^(log_n + rate_bits) leaves, one after the other in `mats`; grouped != 0: ONE grid over all of them (grid.y = matrix, the pool's
  * lane-form group), grouped == 0: the per-commitment launch, one per matrix.  digests_out: n_segments x N x 4 words, leaf digests in
  * tree order.  STARKHIP_ERR_BAD_SHAPE, before any device work, for no or more than four segments, no columns, or more than 2^20 leaves
- * (a leaf count is a power of two by construction: the tree order is a bit reversal). */
+ * (a leaf count is a power of two by construction: the tree order is a bit reversal).
+ * form: 3 the lane form, 4 the pair form (per-commitment launches only: BAD_SHAPE with grouped != 0).  prefix_mask, bit s: segment s is
+ * given the context's saved state past an identity prefix ("leaf_hash_prefix") for this shape and the counter as the context's last
+ * starkhip_lde_batch of this shape left it -- that call counts the columns c < n that are e_c, as prove() does -- so the segment skips
+ * its first n / 8 blocks exactly when that LDE's first n columns were the identity and n_cols >= n + 8; the other segments, and every
+ * segment with "leaf_hash_prefix" = 0 or for a shape without the table (log_n other than 12 and 13), get null pointers and hash every
+ * block.  BAD_SHAPE for a mask bit beyond the segments. */
 int starkhip_leaf_hash_lane_group(void* ctx, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped,
-                                  uint64_t* digests_out);
+                                  int form, unsigned prefix_mask, uint64_t* digests_out);
+/* the table behind "leaf_hash_prefix" under test: cap_out [4][N], N = 2^(log_n + rate_bits): word w of the sponge's capacity of leaf
+ * q = s n + k (coset s, point k of the coset-major LDE) after the columns e_0 .. e_{n-1}.  BAD_SHAPE for log_n other than 12 and 13 or
+ * with the option at 0. */
+int starkhip_leaf_prefix_table(void* ctx, unsigned log_n, unsigned rate_bits, uint64_t* cap_out);
 /* CPU check (no GPU needed) of the constant tables the leaf-hash kernels use for their merged partial rounds -- three at a time in the
  * quad form, four at a time in the lane and pair forms: replays both formulations on n_states inputs against the plain permutation;
  * returns the number of mismatches (0 = good), -1 if a sum of the four-round merge would not fit its 64-bit accumulator */

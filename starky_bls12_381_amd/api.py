@@ -93,7 +93,8 @@ lib.starkhip_lde_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_
 lib.starkhip_merkle_cap.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_uint, C.c_uint, _u64p]
 lib.starkhip_poseidon_permute_batch.argtypes = [C.c_void_p, _u64p, C.c_size_t]
 lib.starkhip_poseidon_permute_batch_form.argtypes = [C.c_void_p, C.c_int, C.c_int, _u64p, C.c_size_t]
-lib.starkhip_leaf_hash_lane_group.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint, C.c_int, _u64p]
+lib.starkhip_leaf_hash_lane_group.argtypes = [C.c_void_p, _u64p, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_uint, _u64p]
+lib.starkhip_leaf_prefix_table.argtypes = [C.c_void_p, C.c_uint, C.c_uint, _u64p]
 lib.starkhip_field_ops_batch.argtypes = [C.c_void_p, C.c_int, _u64p, _u64p, _u64p, C.c_size_t]
 lib.starkhip_poseidon_permute_host.argtypes = [_u64p]
 lib.starkhip_poseidon_permute_host.restype = None
@@ -1156,7 +1157,10 @@ class Prover:
 
     def set_option(self, name, value):
         """Tuning knob of this context (starkhip_set_option).  "check_trace" = 1: every prove* checks its trace against the AIR on the
-        device before the LDE and raises TraceViolation for a violating one ("check_trace_list": the violations its report lists)."""
+        device before the LDE and raises TraceViolation for a violating one ("check_trace_list": the violations its report lists).
+        "leaf_hash_prefix" (default 1; 0: off): the lane and pair forms of the leaf hash start a trace whose first `rows` columns are
+        e_0 .. e_{rows-1} (FinalExp's row selectors) from a saved state past them; same proof bytes either way.  The other names
+        ("hasher", "leaf_hash_form", "lde_closed_forms", "lde_impl", "host_commit_leaves", "quotient_*", ...): include/starkhip.h."""
         _chk(lib.starkhip_set_option(self._ctx, name.encode(), int(value)))
 
     def check_stats(self):
@@ -1259,15 +1263,23 @@ class Prover:
         _chk(lib.starkhip_field_ops_batch(self._ctx, op, _p64(a), _p64(b), _p64(out), a.size))
         return out
 
-    def leaf_hash_lane_group(self, mats, log_n, rate_bits=0, grouped=True):
+    def leaf_hash_lane_group(self, mats, log_n, rate_bits=0, grouped=True, form=3, prefix_mask=0):
         """Leaf digests (segments x leaves x 4, tree order) of `mats` (segments x columns x leaves, coset-major) in the lane form of the leaf
-        hash: as ONE grid over all segments (grouped, what a proof pool launches for a group) or one launch per segment."""
+        hash: as ONE grid over all segments (grouped, what a proof pool launches for a group) or one launch per segment -- those also in
+        the pair form (form=4).  prefix_mask bit s: segment s gets the context's saved state past an identity prefix
+        ("leaf_hash_prefix") and the counter the context's last lde_batch of this shape left."""
         m = np.ascontiguousarray(mats, dtype=np.uint64)
         assert m.ndim == 3
         out = np.zeros((m.shape[0], m.shape[2], 4), dtype=np.uint64)
         if m.shape[2] != 1 << (log_n + rate_bits):
             raise StarkhipError(ERR_BAD_SHAPE)
-        _chk(lib.starkhip_leaf_hash_lane_group(self._ctx, _p64(m), m.shape[0], m.shape[1], log_n, rate_bits, 1 if grouped else 0, _p64(out)))
+        _chk(lib.starkhip_leaf_hash_lane_group(self._ctx, _p64(m), m.shape[0], m.shape[1], log_n, rate_bits, 1 if grouped else 0, form, prefix_mask, _p64(out)))
+        return out
+
+    def leaf_prefix_table(self, log_n, rate_bits):
+        """starkhip_leaf_prefix_table: cap[4][N], the sponge capacity of every leaf (coset-major index) after the columns e_0 .. e_{n-1}."""
+        out = np.zeros((4, 1 << (log_n + rate_bits)), dtype=np.uint64)
+        _chk(lib.starkhip_leaf_prefix_table(self._ctx, log_n, rate_bits, _p64(out)))
         return out
 
     def poseidon_permute_batch(self, states, form=0, variant=0):

@@ -990,9 +990,13 @@ int starkhip_poseidon_permute_batch_form(void* ctx, int form, int variant, uint6
     return permute_batch_form((Ctx*)ctx, form, variant, states, n_states);
 }
 int starkhip_leaf_hash_lane_group(void* ctx, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped,
-                                  uint64_t* digests_out) {
+                                  int form, unsigned prefix_mask, uint64_t* digests_out) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
-    return leaf_hash_lane_group((Ctx*)ctx, mats, n_segments, n_cols, log_n, rate_bits, grouped, digests_out);
+    return leaf_hash_lane_group((Ctx*)ctx, mats, n_segments, n_cols, log_n, rate_bits, grouped, form, prefix_mask, digests_out);
+}
+int starkhip_leaf_prefix_table(void* ctx, unsigned log_n, unsigned rate_bits, uint64_t* cap_out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    return leaf_prefix_table((Ctx*)ctx, log_n, rate_bits, cap_out);
 }
 int starkhip_field_ops_batch(void* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;

@@ -93,13 +93,18 @@ struct Ctx {
         DevBuf qsolve;  // quotient_solve_table: the constants of the recombination of the classes' chunks
         DevBuf lde2_fwd, lde2_inv, lde2_cs, lde2_oh;  // kernels_lde.hip tables (log_n >= 8)
         DevBuf lde_wave;                               // ... and of its wave-resident kernel (log_n == 13)
+        // beside lde2_oh, from which it is built: the leaf hash's saved capacity past an identity prefix, cap[4][N], then the word in
+        // which the LDE kernels count a proof's columns e_c (kernels.h: LeafPrefix).  Allocated and built for the first Poseidon-hashed
+        // proof of this shape that can use it (leaf_prefix_wanted, ensure_leaf_prefix); empty otherwise.
+        DevBuf leaf_prefix;
+        bool leaf_prefix_built = false;
         // kernels_lde_long.hip (log_n >= 14, and the proof's other vectors of 2^16 .. 2^20 words): the coset powers (7 w_N^s)^j, the
         // sub-transforms' twiddles, and the inter-pass twiddles of every length this shape has transformed (ensure_long_tw)
         DevBuf long_cs, long_sub;
         struct LongTw { unsigned log_len; DevBuf fwd, inv; };
         std::vector<std::unique_ptr<LongTw>> long_tw;
         std::vector<DevBuf*> bufs() {
-            std::vector<DevBuf*> v = {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &qsolve, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave, &long_cs, &long_sub};
+            std::vector<DevBuf*> v = {&tw_fwd, &tw_inv, &coset_scale, &qtab, &qshift_inv, &qsolve, &lde2_fwd, &lde2_inv, &lde2_cs, &lde2_oh, &lde_wave, &leaf_prefix, &long_cs, &long_sub};
             for (auto& t : long_tw) {
                 v.push_back(&t->fwd);
                 v.push_back(&t->inv);
@@ -128,6 +133,7 @@ struct Ctx {
     long opt_hasher = 0;             // STARKHIP_HASHER_POSEIDON / _KECCAK: the hash of this context's commitments, Merkle trees, proof of work and transcript
     long opt_lde_impl = 0;           // 0: 8192-row traces take lde_columns_wave_kernel; 1: lde_columns_v2_kernel for every shape (the cross-check)
     long opt_lde_closed_forms = 1;   // constant / unit-vector columns skip their transforms (kernels_lde.hip); 0: every column is transformed
+    long opt_leaf_hash_prefix = 1;   // lane and pair forms start a trace whose first n columns are e_0 .. e_{n-1} from the saved state past them (kernels.h: LeafPrefix); 0: every block is hashed
     long opt_host_commit_leaves = 64; // trace commitments of at most this many leaves (and >= 64 columns) are hashed by host threads (0: never)
     long opt_verify_chunk_mb = 1024;  // device memory one chunk of starkhip_verify_batch may take (verifier_device.cpp)
     double verify_timings[4] = {0};   // the last starkhip_verify_batch: host prelude ms, upload ms, device ms, host CPU seconds
@@ -221,14 +227,27 @@ bool long_vector(unsigned log_len);
 int ensure_long_tw(Ctx* c, unsigned log_len, LdeLongTables* out);
 int ensure_plan(Ctx* c, const AirInfo& air, size_t quotient_points, bool by_class = false);
 int ensure_program(Ctx* c, const AirInfo& air, size_t quotient_points);
-hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs);
+// col_base, unit_count: the trace LDE of a proof that may use the leaf hash's saved prefix state (else 0, null: nothing is counted)
+hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs, unsigned col_base = 0,
+                   unsigned* unit_count = nullptr);
+// The saved prefix state (kernels.h: LeafPrefix) with the current tables (ensure_tables).  wanted: this context would use it for a trace
+// of n_cols columns under `hasher`; bytes: what its buffer takes then (work_buffers: prover.hip), else 0; ensure: the buffer holds the
+// table (built once, on the context's stream); the counter word, null where the buffer is not there; reset: the counter cleared in
+// stream order, before the first LDE launch of a proof; leaf_prefix: what the leaf-hash launches get (nulls unless built).
+bool leaf_prefix_wanted(const Ctx* c, size_t n_cols, unsigned log_n, unsigned rate);
+size_t leaf_prefix_bytes(const Ctx* c, size_t n_cols, unsigned log_n, unsigned rate);
+int ensure_leaf_prefix(Ctx* c, unsigned log_n, unsigned rate);
+unsigned* leaf_prefix_counter(const Ctx* c);
+hipError_t leaf_prefix_reset(Ctx* c);
+LeafPrefix leaf_prefix(const Ctx* c);
 int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,
             const gl_t* post_scale);
 int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values);
 // ---- check_trace.hip
 int check_trace_in_prove(Ctx* c, const AirInfo& air, const gl_t* d_trace, size_t n_rows, const uint64_t* pis, uint64_t** blob, size_t* words);
 // ---- ctx.hip
-hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form);
+hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form,
+                                 LeafPrefix prefix = LeafPrefix());
 
 // digest buffer: level 0 (n_leaves nodes) followed by level 1, ... ; offset of level l in nodes
 static inline size_t level_off(size_t n_leaves, unsigned l) { return 2 * n_leaves - (2 * n_leaves >> l); }

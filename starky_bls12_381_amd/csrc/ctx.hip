@@ -152,7 +152,8 @@ int ensure_long_tw(Ctx* c, unsigned log_len, LdeLongTables* out) {
 }
 
 // IFFT + coset LDE of `cols` columns with the tables of ensure_tables(log_n, rate, .)
-hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs) {
+hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t cols, unsigned log_n, unsigned rate, int from_coeffs, unsigned col_base,
+                   unsigned* unit_count) {
     // 2^14 rows and more: a column is split over workgroups; `coeffs` is that transform's scratch as well (required unless from_coeffs).
     // No closed forms for constant / unit-vector columns there ("lde_closed_forms" has nothing to switch).
     if (lde_long_supported(log_n)) {
@@ -166,14 +167,51 @@ hipError_t run_lde(Ctx* c, const gl_t* values, gl_t* coeffs, gl_t* lde, size_t c
         unsigned* next = (unsigned*)(c->tab->lde_wave.as<gl_t>() + lde_wave_table_words(rate));
         if (hipError_t e = hipMemsetAsync(next, 0, sizeof(unsigned), c->st); e != hipSuccess) return e;
         return launch_lde_columns_wave(values, lde, cols, rate, c->tab->lde_wave.as<gl_t>(),
-                                       (c->opt_lde_closed_forms && lde_v2_oh_words(log_n, rate)) ? c->tab->lde2_oh.as<gl_t>() : nullptr, next, c->st);
+                                       (c->opt_lde_closed_forms && lde_v2_oh_words(log_n, rate)) ? c->tab->lde2_oh.as<gl_t>() : nullptr, next, c->st, col_base, unit_count);
     }
     if (lde_v2_supported(log_n))
         return launch_lde_columns_v2(values, coeffs, lde, cols, log_n, rate, c->tab->lde2_fwd.as<gl_t>(), c->tab->lde2_inv.as<gl_t>(),
                                      c->tab->lde2_cs.as<gl_t>(),
-                                     (c->opt_lde_closed_forms && lde_v2_oh_words(log_n, rate)) ? c->tab->lde2_oh.as<gl_t>() : nullptr, from_coeffs, c->st);
+                                     (c->opt_lde_closed_forms && lde_v2_oh_words(log_n, rate)) ? c->tab->lde2_oh.as<gl_t>() : nullptr, from_coeffs, c->st, col_base,
+                                     unit_count);
     return launch_lde_columns(values, coeffs, lde, cols, log_n, rate, c->tab->tw_fwd.as<gl_t>(), c->tab->tw_inv.as<gl_t>(), log_n + rate,
                               c->tab->coset_scale.as<gl_t>(), from_coeffs, c->st);
+}
+
+// ---- the leaf hash's saved state past an identity prefix (kernels.h: LeafPrefix; declarations and what each is for: ctx.h)
+bool leaf_prefix_wanted(const Ctx* c, size_t n_cols, unsigned log_n, unsigned rate) {
+    return c->opt_leaf_hash_prefix && c->opt_hasher == STARKHIP_HASHER_POSEIDON && (log_n == 12 || log_n == 13) && leaf_prefix_words(log_n, rate) != 0 &&
+           n_cols >= ((size_t)1 << log_n) + 8;
+}
+size_t leaf_prefix_bytes(const Ctx* c, size_t n_cols, unsigned log_n, unsigned rate) {
+    return leaf_prefix_wanted(c, n_cols, log_n, rate) ? (leaf_prefix_words(log_n, rate) + 1) * 8 : 0;
+}
+int ensure_leaf_prefix(Ctx* c, unsigned log_n, unsigned rate) {
+    Ctx::Tables* T = c->tab;
+    if (T->leaf_prefix_built) return 0;
+    const size_t words = leaf_prefix_words(log_n, rate);
+    if (!words || T->log_n != (int)log_n || T->rate != (int)rate) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(T->leaf_prefix.ensure((words + 1) * 8));
+    HIPCHK(hipMemsetAsync(T->leaf_prefix.as<gl_t>() + words, 0, 8, c->st));
+    HIPCHK(launch_leaf_prefix_build(T->lde2_oh.as<gl_t>(), log_n, rate, T->leaf_prefix.as<gl_t>(), c->st));
+    T->leaf_prefix_built = true;
+    return 0;
+}
+unsigned* leaf_prefix_counter(const Ctx* c) {
+    const Ctx::Tables* T = c->tab;
+    return T && T->leaf_prefix_built ? (unsigned*)(T->leaf_prefix.as<gl_t>() + leaf_prefix_words((unsigned)T->log_n, (unsigned)T->rate)) : nullptr;
+}
+hipError_t leaf_prefix_reset(Ctx* c) {
+    unsigned* const count = leaf_prefix_counter(c);
+    return count ? hipMemsetAsync(count, 0, sizeof(unsigned), c->st) : hipSuccess;
+}
+LeafPrefix leaf_prefix(const Ctx* c) {
+    LeafPrefix p;
+    if (unsigned* const count = leaf_prefix_counter(c)) {
+        p.count = count;
+        p.cap = c->tab->leaf_prefix.as<gl_t>();
+    }
+    return p;
 }
 
 int ensure_program(Ctx* c, const AirInfo& air, size_t quotient_points) {
@@ -367,6 +405,7 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
     else if (k == "zeta_on_coset" && value >= 0) c->opt_zeta_on_coset = value;  // tests: substitute zeta = 7 w_n^(value - 1); the proof is not a transcript any more
     else if (k == "lde_closed_forms" && (value == 0 || value == 1)) c->opt_lde_closed_forms = value;
     else if (k == "lde_impl" && (value == 0 || value == 1)) c->opt_lde_impl = value;
+    else if (k == "leaf_hash_prefix" && (value == 0 || value == 1)) c->opt_leaf_hash_prefix = value;
     else if (k == "host_commit_leaves" && value >= 0 && value <= 4096) c->opt_host_commit_leaves = value;
     else if (k == "leaf_hash_form" && value >= FORM_AUTO && value <= FORM_PAIR) c->opt_leaf_hash_form = value;
     else if (k == "quotient_cosets" && (value == 0 || value == 1)) c->opt_quotient_cosets = value;
@@ -448,10 +487,11 @@ int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values)
 
 // The leaf hash of a LONE context's commitment in the form use_pair_form / use_row_form / "leaf_hash_form" pick; `*form` says which
 // (HashService::Timing::form)
-hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form) {
+hipError_t launch_leaf_hash_lone(const Ctx* c, const gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate, gl_t* digests, hipStream_t st, int* form,
+                                 LeafPrefix prefix) {
     const LeafHashForm f = c->opt_leaf_hash_form == FORM_LANE ? FORM_LANE : use_pair_form(c, n_cols, log_n + rate) ? FORM_PAIR : use_row_form(c, n_cols, log_n + rate) ? FORM_ROW : FORM_QUAD;
     *form = leaf_hash_sent(f);
-    return launch_leaf_hash_form(f, lde, n_cols, log_n, rate, digests, st);
+    return launch_leaf_hash_form(f, lde, n_cols, log_n, rate, digests, st, prefix);  // (the quad and row forms ignore the prefix)
 }
 
 // In-place transform of n_vecs vectors of 2^log_len words, vec_stride apart, as launch_ntt_global does it (inverse: tw_inv's direction and

@@ -60,10 +60,11 @@ HashService::Stats HashService::stats() {
 }
 
 hipError_t HashService::hash(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st, hipEvent_t ready,
-                             hipEvent_t done, bool announced, bool urgent, Timing* timing) {
+                             hipEvent_t done, bool announced, bool urgent, Timing* timing, LeafPrefix prefix) {
     hipError_t e = hipEventRecord(ready, st);
     Req r;
     r.timing = timing;
+    r.prefix = prefix;
     r.mat = mat; r.digests = digests; r.n_cols = n_cols; r.log_n = log_n; r.rate_bits = rate_bits; r.ready = ready; r.done = done;
     r.big = is_big(log_n, rate_bits);
     r.urgent = urgent;
@@ -153,7 +154,7 @@ void HashService::launch_big(Req* r, bool lane, unsigned group) {
         if (e == hipSuccess && r->timing->t0) e = hipEventRecord(r->timing->t0, s);
     }
     // a big commitment on its own: the pair form (is_big() = 32 768 leaves or more: 1 024 waves of it fill the chip)
-    if (e == hipSuccess) e = launch_leaf_hash_form(form, r->mat, r->n_cols, r->log_n, r->rate_bits, r->digests, s);
+    if (e == hipSuccess) e = launch_leaf_hash_form(form, r->mat, r->n_cols, r->log_n, r->rate_bits, r->digests, s, r->prefix);
     if (e == hipSuccess && r->timing && r->timing->t1) e = hipEventRecord(r->timing->t1, s);
     if (e == hipSuccess) e = hipEventRecord(r->done, s);
     r->err = e;
@@ -183,6 +184,8 @@ unsigned HashService::launch_big_group(std::vector<Req*>& group) {
         for (size_t i = 0; i < same.size(); i++) {
             B.mat[i] = same[i]->mat;
             B.digests[i] = same[i]->digests;
+            B.prefix_count[i] = same[i]->prefix.count;
+            B.prefix_cap[i] = same[i]->prefix.cap;
         }
         hipError_t e = hipSuccess;
         hipStream_t s = pick_long_stream(false, &e);
@@ -253,7 +256,7 @@ void HashService::launch_small(std::vector<Req*>& reqs) {
             const size_t cnt = std::min<size_t>(LEAF_HASH_MAX_BATCH, g.size() - at);
             hipError_t e = hipSuccess;
             hipStream_t s = pick_small_stream(&e);
-            LeafHashBatch B;
+            LeafHashBatch B = {};
             for (size_t i = 0; i < cnt && e == hipSuccess; i++) {
                 B.mat[i] = g[at + i]->mat;
                 B.digests[i] = g[at + i]->digests;

@@ -120,7 +120,8 @@ int permute_batch_form(Ctx*, int, int, uint64_t*, size_t) { return STARKHIP_ERR_
 int keccak_permute_batch(Ctx*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int merkle_tree_hasher(Ctx*, int, const uint64_t*, size_t, unsigned, unsigned, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int hash_rows_hasher(Ctx*, int, const uint64_t*, size_t, size_t, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
-int leaf_hash_lane_group(Ctx*, const uint64_t*, size_t, size_t, unsigned, unsigned, int, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
+int leaf_hash_lane_group(Ctx*, const uint64_t*, size_t, size_t, unsigned, unsigned, int, int, unsigned, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
+int leaf_prefix_table(Ctx*, unsigned, unsigned, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int expand_log(Ctx*, const TraceLog*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int check_trace(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int check_trace_report(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_check_report_t*) {
@@ -148,7 +149,7 @@ hipError_t event_wait_sleeping(hipEvent_t ev) { return ev == failing_ready() ? h
 
 // the two launches the commitment scheduler makes
 static std::atomic<unsigned long> g_fake_launches(0), g_fake_merged(0), g_fake_lane_grids(0), g_fake_lane_members(0), g_service_records(0);
-hipError_t launch_leaf_hash_form(LeafHashForm, const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t) { g_fake_launches++; return hipSuccess; }
+hipError_t launch_leaf_hash_form(LeafHashForm, const gl_t*, size_t, unsigned, unsigned, gl_t*, hipStream_t, LeafPrefix) { g_fake_launches++; return hipSuccess; }
 hipError_t launch_leaf_hash_multi(const LeafHashBatch&, unsigned count, size_t, unsigned, unsigned, hipStream_t) {
     g_fake_launches++;
     g_fake_merged += count;

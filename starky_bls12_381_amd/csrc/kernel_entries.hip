@@ -53,16 +53,26 @@ int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, uns
     // the LDE comes from the kernel prove() uses for this shape: for 8192 rows the wave-resident one, which keeps no coefficients --
     // those, when asked for, come from the other kernel afterwards (in place of the values, which the first run leaves untouched)
     const bool wave = lde_wave_supported(log_n) && c->opt_lde_impl == 0;
+    // as in prove(): the kernels count the columns e_c for the leaf hash's saved prefix state (kernels.h: LeafPrefix), from zero for
+    // each run over the columns -- what starkhip_leaf_hash_lane_group's prefix_mask then reads.  Whatever n_cols: with fewer than n + 8
+    // columns it is the leaf kernels that must not skip.
+    const bool prefix = leaf_prefix_wanted(c, n + 8, log_n, rate_bits);
+    if (prefix && (rc = ensure_leaf_prefix(c, log_n, rate_bits))) return rc;
+    unsigned* const unit_count = prefix ? leaf_prefix_counter(c) : nullptr;
     std::vector<gl_t> tmp;
     if (wave) {
-        HIPCHK(run_lde(c, c->values.as<gl_t>(), nullptr, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0));
+        HIPCHK(leaf_prefix_reset(c));
+        HIPCHK(run_lde(c, c->values.as<gl_t>(), nullptr, c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0, 0, unit_count));
         if (lde_out) {
             tmp.resize(n_cols * N);
             HIPCHK(hipMemcpyAsync(tmp.data(), c->lde.p, n_cols * N * 8, hipMemcpyDeviceToHost, c->st));
             HIPCHK(stream_wait(c));
         }
     }
-    if (!wave || coeffs_out) HIPCHK(run_lde(c, c->values.as<gl_t>(), c->values.as<gl_t>(), c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0));
+    if (!wave || coeffs_out) {
+        HIPCHK(leaf_prefix_reset(c));
+        HIPCHK(run_lde(c, c->values.as<gl_t>(), c->values.as<gl_t>(), c->lde.as<gl_t>(), n_cols, log_n, rate_bits, 0, 0, unit_count));
+    }
     if (coeffs_out) HIPCHK(hipMemcpyAsync(coeffs_out, c->values.p, n_cols * n * 8, hipMemcpyDeviceToHost, c->st));  // in place
     HIPCHK(stream_wait(c));
     if (lde_out) {
@@ -253,10 +263,21 @@ int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n
     return STARKHIP_OK;
 }
 
-// the lane-form leaf hash on 1 .. 4 matrices of one shape: the pool's grouped launch (one grid) or the per-commitment launches
-int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped, uint64_t* digests_out) {
+// the lane-form leaf hash on 1 .. 4 matrices of one shape: the pool's grouped launch (one grid) or the per-commitment launches -- those
+// also in the pair form.  prefix_mask bit s: segment s is given the context's saved prefix state for this shape and the counter as the
+// last starkhip_lde_batch of this shape left it (kernels.h: LeafPrefix); the other segments get null pointers.
+int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped, int form,
+                         unsigned prefix_mask, uint64_t* digests_out) {
     if (!mats || !digests_out || n_segments == 0 || n_segments > 4 || n_cols == 0 || log_n + rate_bits > 20 || n_cols > ((size_t)1 << 20)) return STARKHIP_ERR_BAD_SHAPE;
+    if ((form != FORM_LANE && form != FORM_PAIR) || (grouped && form != FORM_LANE) || (prefix_mask >> n_segments) != 0) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
+    LeafPrefix pf;
+    // (whatever n_cols, as in lde_batch; with "leaf_hash_prefix" = 0, or for a shape without the table, every segment gets null pointers)
+    if (prefix_mask && leaf_prefix_wanted(c, ((size_t)1 << log_n) + 8, log_n, rate_bits)) {
+        if (int rc = ensure_tables(c, log_n, rate_bits, 0)) return rc;
+        if (int rc = ensure_leaf_prefix(c, log_n, rate_bits)) return rc;
+        pf = leaf_prefix(c);
+    }
     const size_t N = (size_t)1 << (log_n + rate_bits), mat_words = n_cols * N, dig_words = 4 * N;
     HIPCHK(c->staging.ensure(n_segments * (mat_words + dig_words) * 8));
     gl_t* d_mats = c->staging.as<gl_t>();
@@ -267,13 +288,27 @@ int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t
     for (size_t s = 0; s < n_segments; s++) {
         B.mat[s] = d_mats + s * mat_words;
         B.digests[s] = d_dig + s * dig_words;
+        if (prefix_mask >> s & 1u) {
+            B.prefix_count[s] = pf.count;
+            B.prefix_cap[s] = pf.cap;
+        }
     }
     if (grouped) {
         HIPCHK(launch_leaf_hash_lane_group(B, (unsigned)n_segments, n_cols, log_n, rate_bits, c->st));
     } else {
-        for (size_t s = 0; s < n_segments; s++) HIPCHK(launch_leaf_hash_form(FORM_LANE, B.mat[s], n_cols, log_n, rate_bits, B.digests[s], c->st));
+        for (size_t s = 0; s < n_segments; s++) HIPCHK(launch_leaf_hash_form((LeafHashForm)form, B.mat[s], n_cols, log_n, rate_bits, B.digests[s], c->st, LeafPrefix{B.prefix_count[s], B.prefix_cap[s]}));
     }
     HIPCHK(hipMemcpyAsync(digests_out, d_dig, n_segments * dig_words * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+int leaf_prefix_table(Ctx* c, unsigned log_n, unsigned rate_bits, uint64_t* cap_out) {
+    if (!cap_out || log_n > STARKHIP_MAX_LOG_ROWS || rate_bits > 8 || !leaf_prefix_wanted(c, ((size_t)1 << log_n) + 8, log_n, rate_bits)) return STARKHIP_ERR_BAD_SHAPE;
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = ensure_tables(c, log_n, rate_bits, 0)) return rc;
+    if (int rc = ensure_leaf_prefix(c, log_n, rate_bits)) return rc;
+    HIPCHK(hipMemcpyAsync(cap_out, c->tab->leaf_prefix.p, leaf_prefix_words(log_n, rate_bits) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(stream_wait(c));
     return STARKHIP_OK;
 }

@@ -50,14 +50,17 @@ bool lde_v2_supported(unsigned log_n);
 size_t lde_v2_tw_words(unsigned log_n);
 size_t lde_v2_oh_words(unsigned log_n, unsigned rate_bits);  // closed-form tables of unit-vector columns (0: shape without them)
 hipError_t lde_v2_upload_tables(unsigned log_n, unsigned rate_bits, gl_t* d_tw_fwd, gl_t* d_tw_inv, gl_t* d_cs, gl_t* d_oh, hipStream_t st);
+// col_base / unit_count (both LDE kernels with closed forms, 2^12 and 2^13 rows; null: nothing is counted): the absolute index of the launch's
+// first column in its trace and a device word that gains 1 for every column c < n found to be the unit vector e_c -- see LeafPrefix below
 hipError_t launch_lde_columns_v2(const gl_t* values, gl_t* coeffs, gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate_bits,
-                                 const gl_t* tw_fwd, const gl_t* tw_inv, const gl_t* cs, const gl_t* oh, int from_coeffs, hipStream_t st);
+                                 const gl_t* tw_fwd, const gl_t* tw_inv, const gl_t* cs, const gl_t* oh, int from_coeffs, hipStream_t st,
+                                 unsigned col_base = 0, unsigned* unit_count = nullptr);
 // 2^13 rows, values -> LDE only (no coefficient output): the wave-resident kernel (kernels_lde.hip; tools/lde_wave_model.py)
 bool lde_wave_supported(unsigned log_n);
 size_t lde_wave_table_words(unsigned rate_bits);
 hipError_t lde_wave_upload_tables(unsigned rate_bits, gl_t* d_tab, hipStream_t st);
 hipError_t launch_lde_columns_wave(const gl_t* values, gl_t* lde, size_t n_cols, unsigned rate_bits, const gl_t* d_tab, const gl_t* oh, unsigned* next,
-                                   hipStream_t st);
+                                   hipStream_t st, unsigned col_base = 0, unsigned* unit_count = nullptr);
 // 2^14 .. 2^26 points, a vector split over workgroups in two passes (kernels_lde_long.hip; tools/lde_long_model.py).  `sub`: the
 // sub-transforms' twiddles (lde_long_sub_words() words, the same for every length; the inverse ones carry the inverse's n^-1);
 // tw_fwd / tw_inv: the inter-pass twiddles w_n^(+-j0 k1) of ONE length (2^log_n words each, lde_long_fill_twiddles).
@@ -83,9 +86,26 @@ hipError_t launch_ntt_global(gl_t* data, size_t n_vecs, size_t vec_stride, unsig
 // kernels_hash.hip
 // up to LEAF_HASH_MAX_BATCH matrices of one shape hashed by one launch (the trace commitments of proofs of the same AIR)
 static const unsigned LEAF_HASH_MAX_BATCH = 64;
+// The saved sponge state past a fixed identity prefix (lane and pair forms; the other forms and the Keccak hasher ignore it).  Where the
+// first n columns of an n-row trace are the unit vectors e_0 .. e_{n-1} -- FinalExp's one-hot row selectors, which its constraints force --
+// their LDE is the closed form of kernels_lde.hip: column c at point (s, k) is e0[s][(k - c) mod n], a table of the shape alone.  n columns
+// are n / 8 whole blocks of the rate-8 sponge and the next block, a full one, overwrites the whole rate: the state of leaf q = s n + k after
+// them is its four capacity words, cap[w][q] (struct of arrays: a wave reads 512-byte runs), the same for every such trace.  `count` is the
+// proof's own evidence that it has such a trace: the LDE kernels add 1 to it for every column c < n they find to be e_c (each column is
+// transformed once per proof), so *count == n exactly when the prefix is the identity.  A kernel given both starts its leaves from `cap`
+// at block n / 8 when *count == n and n_cols >= n + 8, and hashes every block otherwise.  Null pointers: never skip.
+struct LeafPrefix {
+    const unsigned* count = nullptr;
+    const gl_t* cap = nullptr;  // [4][N]
+};
+size_t leaf_prefix_words(unsigned log_n, unsigned rate_bits);  // 4 N, or 0 for a shape whose LDE kernels have no closed forms
+// cap[4][N] from the LDE-of-e_0 half of the closed-form table `oh` (lde_v2_upload_tables): one lane per leaf, n / 8 permutations each
+hipError_t launch_leaf_prefix_build(const gl_t* oh, unsigned log_n, unsigned rate_bits, gl_t* cap, hipStream_t st);
 struct LeafHashBatch {
     const gl_t* mat[LEAF_HASH_MAX_BATCH];
     gl_t* digests[LEAF_HASH_MAX_BATCH];
+    const unsigned* prefix_count[LEAF_HASH_MAX_BATCH];  // LeafPrefix per member (lane form; null: that member never skips)
+    const gl_t* prefix_cap[LEAF_HASH_MAX_BATCH];
 };
 hipError_t launch_leaf_hash_multi(const LeafHashBatch& B, unsigned count, size_t n_cols, unsigned log_n, unsigned rate_bits, hipStream_t st);
 // the same in the lane form (one lane per leaf): the big commitments of a pool's lane group as ONE grid, grid.y = commitment
@@ -114,7 +134,8 @@ inline LeafHashSent leaf_hash_sent(LeafHashForm form) {
     return form == FORM_ROW ? SENT_ROW : form == FORM_LANE ? SENT_LANE : form == FORM_PAIR ? SENT_PAIR : SENT_QUAD;
 }
 // the same digests from every form; hipErrorInvalidValue for FORM_AUTO
-hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st);
+hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st,
+                                 LeafPrefix prefix = LeafPrefix());
 // Copies a host-built table (poseidon_tables.h) to its __constant__ symbol once per device, under a lock.  `done`: the symbol's own
 // flags, one per device, set after a successful copy.  hipErrorInvalidDevice for a device index outside 0 .. 63, hipErrorInvalidValue
 // for an image that could not be built (null).

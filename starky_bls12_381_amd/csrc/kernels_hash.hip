@@ -233,6 +233,13 @@ __global__ __launch_bounds__(256) void verify_leaf_digest_kernel(const gl_t* __r
 // ---- the lane form (poseidon_dev.h): one lane per leaf, for big commitments when several are in flight (the pool picks).
 // Same digests as leaf_hash_kernel.  64 adjacent points of a column per wave: every load is one 512-byte run.
 __constant__ LaneTables LANE_TABLES;
+// The first block a leaf absorbs: n / 8 where this commitment may start from the saved state past its identity prefix, else 0.  Uniform
+// over the launch's segment: the counter is one word read through a uniform pointer.
+__device__ __forceinline__ size_t leaf_prefix_blocks(const unsigned* count, const gl_t* cap, size_t n_cols, unsigned log_n) {
+    const size_t n = (size_t)1 << log_n;
+    if (count == nullptr || cap == nullptr || n_cols < n + 8) return 0;
+    return __builtin_amdgcn_readfirstlane(*count) == (unsigned)n ? n / 8 : 0;
+}
 // grid.y = commitment (LeafHashBatch, as leaf_hash_multi_kernel): the lane-form group of a proof pool is ONE grid -- four launches on four
 // streams occupy four hardware queues for 350 ms each, and with HIP's default of four queues every other stream of the process then waits
 // behind one of them (tools/experiments/hw_queue_probe.hip).  The segment's two pointers are looked up once, from the kernel arguments.
@@ -263,10 +270,13 @@ __global__ __launch_bounds__(256, 2) void leaf_hash_lane_kernel(LeafHashBatch B,
         return;
     }
     const size_t n_full = n_cols / 8, rem = n_cols % 8;
+    // The saved state past an identity prefix (kernels.h: LeafPrefix): one uniform load decides for the whole grid segment.  With it the
+    // leaves start at block n / 8 from the table's capacity; the rate is zero and the first block absorbed overwrites all of it.
+    const size_t b0 = leaf_prefix_blocks(B.prefix_count[blockIdx.y], B.prefix_cap[blockIdx.y], n_cols, log_n);
     gl_t nx[8];
     if (n_full) {
 #pragma unroll
-        for (int e = 0; e < 8; e++) nx[e] = col[(size_t)e * N];
+        for (int e = 0; e < 8; e++) nx[e] = col[(8 * b0 + e) * N];
     }
     LaneZeros Z;
     lane_zeros_init(Z);
@@ -276,7 +286,12 @@ __global__ __launch_bounds__(256, 2) void leaf_hash_lane_kernel(LeafHashBatch B,
     LaneState st;
 #pragma unroll
     for (int w = 0; w < 8; w++) st.t0[w] = st.t1[w] = st.t2[w] = 0;
-    for (size_t b = 0; b < n_full; b++) {
+    if (b0) {
+        const gl_t* cap = B.prefix_cap[blockIdx.y] + q;
+#pragma unroll
+        for (int e = 0; e < 4; e++) lane_set(st.t2, e, cap[(size_t)e * N]);
+    }
+    for (size_t b = b0; b < n_full; b++) {
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             lane_set(st.t0, e, nx[e]);
@@ -309,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void leaf_hash_lane_kernel(LeafHashBatch B,
 // columns 8 b + 6, 8 b + 7 of the same point and carries the capacity: every load is a 256-byte run.
 __constant__ PairTables PAIR_TABLES;
 __global__ __launch_bounds__(256, 2) void leaf_hash_pair_kernel(const gl_t* __restrict__ mat, size_t n_cols, unsigned log_n, unsigned rate_bits,
-                                                              gl_t* __restrict__ digests) {
+                                                              gl_t* __restrict__ digests, const unsigned* prefix_count, const gl_t* __restrict__ prefix_cap) {
     __shared__ PairTables T;
     {
         const uint32_t* src = (const uint32_t*)&PAIR_TABLES;
@@ -335,13 +350,15 @@ __global__ __launch_bounds__(256, 2) void leaf_hash_pair_kernel(const gl_t* __re
     const size_t n_full = n_cols / 8, rem = n_cols % 8;
     const unsigned first = half ? 6u : 0u;            // this lane's columns inside a block of eight: first .. first + cnt - 1
     const gl_t* col = mat + q + (size_t)first * N;
+    const size_t b0 = leaf_prefix_blocks(prefix_count, prefix_cap, n_cols, log_n);  // as in leaf_hash_lane_kernel
     gl_t nx[6];
     if (n_full) {
-        nx[0] = col[0];
-        nx[1] = col[N];
+        const gl_t* nc = col + 8 * b0 * N;
+        nx[0] = nc[0];
+        nx[1] = nc[N];
         if (half == 0) {
 #pragma unroll
-            for (int e = 2; e < 6; e++) nx[e] = col[(size_t)e * N];
+            for (int e = 2; e < 6; e++) nx[e] = nc[(size_t)e * N];
         }
     }
     LaneZeros Z;
@@ -353,7 +370,14 @@ __global__ __launch_bounds__(256, 2) void leaf_hash_pair_kernel(const gl_t* __re
     PairState st;
 #pragma unroll
     for (int w = 0; w < 4; w++) st.t0[w] = st.t1[w] = st.t2[w] = 0;
-    for (size_t b = 0; b < n_full; b++) {
+    if (b0 && half) {  // the capacity: the upper lane's elements 2 .. 5
+        const gl_t* cap = prefix_cap + q;
+        pair_set(st.t1, 0, cap[0]);
+        pair_set(st.t1, 1, cap[N]);
+        pair_set(st.t2, 0, cap[2 * N]);
+        pair_set(st.t2, 1, cap[3 * N]);
+    }
+    for (size_t b = b0; b < n_full; b++) {
         pair_set(st.t0, 0, nx[0]);
         pair_set(st.t0, 1, nx[1]);
         if (half == 0) {   // the upper lane's elements 2 .. 5 are the capacity
@@ -544,7 +568,38 @@ __global__ void pow_grind_kernel(const gl_t* __restrict__ base_state, int pos, u
     if ((s[7] >> (64 - pow_bits)) == 0) atomicMin(best, (unsigned long long)w);
 }
 
+// The table of LeafPrefix (kernels.h): the sponge of leaf q = s n + k over the n columns e_0 .. e_{n-1}, whose LDE at that point is the
+// LDE of e_0 rotated -- column c reads e0[s][(k - c) mod n] -- so no matrix is ever formed.  One lane per leaf, the generic permutation:
+// it runs once per context and shape.
+__global__ __launch_bounds__(64) void leaf_prefix_build_kernel(const gl_t* __restrict__ oh, unsigned log_n, unsigned rate_bits, gl_t* __restrict__ cap) { STARKHIP_PRIO_ENTRY
+    const size_t n = (size_t)1 << log_n, N = n << rate_bits;
+    const size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (q >= N) return;
+    const size_t sidx = q >> log_n;
+    const unsigned k = (unsigned)(q & (n - 1)), mask = (unsigned)(n - 1);
+    const gl_t* e0 = oh + n + sidx * n;
+    gl_t s[12];
+#pragma unroll
+    for (int e = 0; e < 12; e++) s[e] = 0;
+#pragma unroll 1
+    for (unsigned c = 0; c < (unsigned)n; c += 8) {
+#pragma unroll
+        for (unsigned e = 0; e < 8; e++) s[e] = e0[(k - c - e) & mask];
+        poseidon_permute_dev(s);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; e++) cap[(size_t)e * N + q] = gl_canon(s[8 + e]);
+}
+
 static inline unsigned nblocks(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
+
+size_t leaf_prefix_words(unsigned log_n, unsigned rate_bits) { return lde_v2_oh_words(log_n, rate_bits) ? (size_t)4 << (log_n + rate_bits) : 0; }
+hipError_t launch_leaf_prefix_build(const gl_t* oh, unsigned log_n, unsigned rate_bits, gl_t* cap, hipStream_t st) {
+    if (!leaf_prefix_words(log_n, rate_bits) || !oh || !cap) return hipErrorInvalidValue;
+    const size_t N = (size_t)1 << (log_n + rate_bits);
+    hipLaunchKernelGGL(leaf_prefix_build_kernel, dim3(nblocks(N, 64)), dim3(64), 0, st, oh, log_n, rate_bits, cap);
+    return hipGetLastError();
+}
 
 hipError_t upload_table_once(const void* symbol, const void* image, size_t bytes, bool (&done)[64]) {
     static std::mutex mu;
@@ -564,7 +619,8 @@ static hipError_t ensure_row_merged_tables() { return upload_table_once(&ROW_MER
 static hipError_t ensure_lane_tables() { return upload_table_once(&LANE_TABLES, lane_tables_host(), sizeof LANE_TABLES, lane_uploaded); }
 static hipError_t ensure_pair_tables() { return upload_table_once(&PAIR_TABLES, pair_tables_host(), sizeof PAIR_TABLES, pair_uploaded); }
 
-hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st) {
+hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st,
+                                 LeafPrefix prefix) {
     const size_t N = (size_t)1 << (log_n + rate_bits);
     switch (form) {
         case FORM_QUAD:
@@ -581,12 +637,14 @@ hipError_t launch_leaf_hash_form(LeafHashForm form, const gl_t* mat, size_t n_co
                 LeafHashBatch B = {};
                 B.mat[0] = mat;
                 B.digests[0] = digests;
+                B.prefix_count[0] = prefix.count;
+                B.prefix_cap[0] = prefix.cap;
                 hipLaunchKernelGGL(leaf_hash_lane_kernel, dim3(nblocks(N, 256)), dim3(256), 0, st, B, n_cols, log_n, rate_bits);
             }
             break;
         case FORM_PAIR:
             if (hipError_t e = ensure_pair_tables(); e != hipSuccess) return e;
-            hipLaunchKernelGGL(leaf_hash_pair_kernel, dim3(nblocks(N, 128)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests);
+            hipLaunchKernelGGL(leaf_hash_pair_kernel, dim3(nblocks(N, 128)), dim3(256), 0, st, mat, n_cols, log_n, rate_bits, digests, prefix.count, prefix.cap);
             break;
         default: return hipErrorInvalidValue;
     }

@@ -125,7 +125,8 @@ __global__ __launch_bounds__(LdePlan<LOGN>::THREADS, 4) void lde_columns_v2_kern
                                                                                     gl_t* lde, unsigned n_cols, unsigned rate_bits,
                                                                                     const gl_t* __restrict__ tw_fwd,
                                                                                     const gl_t* __restrict__ tw_inv, const gl_t* __restrict__ cs,
-                                                                                    const gl_t* __restrict__ oh, int from_coeffs) { STARKHIP_PRIO_ENTRY
+                                                                                    const gl_t* __restrict__ oh, int from_coeffs, unsigned col_base,
+                                                                                    unsigned* unit_count) { STARKHIP_PRIO_ENTRY
     using PL = LdePlan<LOGN>;
     constexpr int T = PL::T, n = PL::N;
     extern __shared__ gl_t lds_all[];
@@ -204,6 +205,8 @@ __global__ __launch_bounds__(LdePlan<LOGN>::THREADS, 4) void lde_columns_v2_kern
                         }
                     } else {
                         const unsigned r = cls[2];
+                        // the proof's evidence for the leaf hash's saved prefix state (kernels.h: LeafPrefix): column c < n is e_c
+                        if (unit_count != nullptr && threadIdx.x == 0 && col_base + col0 < (unsigned)n && r == col_base + col0) atomicAdd(unit_count, 1u);
                         if (cf_keep) {
 #pragma unroll
                             for (int i = 0; i < 8; i++) {
@@ -344,7 +347,7 @@ __device__ __forceinline__ void lde_swap_halves(gl_t& a, gl_t& b) {
 // launch), so a launch is 2 workgroups per CU however many columns it has: no workgroup turnover (LDS allocation, wave launch, the
 // first loads' HBM latency with nothing to hide behind) between columns, and short columns (closed forms) even out by themselves.
 __global__ __launch_bounds__(512, 4) void lde_columns_wave_kernel(const gl_t* values, gl_t* lde, unsigned n_cols, unsigned rate_bits, LdeWaveTables tb,
-                                                                   const gl_t* __restrict__ oh, unsigned* next) { STARKHIP_PRIO_ENTRY
+                                                                   const gl_t* __restrict__ oh, unsigned* next, unsigned col_base, unsigned* unit_count) { STARKHIP_PRIO_ENTRY
     constexpr int n = 1 << LDE_WAVE_LOGN, T = n / 16;
     extern __shared__ gl_t lds_all[];  // 8192 words, no padding
     __shared__ unsigned cls[3], next_col;
@@ -407,6 +410,8 @@ __global__ __launch_bounds__(512, 4) void lde_columns_wave_kernel(const gl_t* va
                 }
             } else {
                 const unsigned r = cls[2];
+                // the proof's evidence for the leaf hash's saved prefix state (kernels.h: LeafPrefix): column c < n is e_c
+                if (unit_count != nullptr && t == 0 && col_base + col < (unsigned)n && r == col_base + col) atomicAdd(unit_count, 1u);
                 for (unsigned s = 0; s < n_cosets; s++) {
                     const gl_t* e0 = oh + n + (size_t)s * n;
 #pragma unroll
@@ -546,7 +551,7 @@ __global__ __launch_bounds__(512, 4) void lde_columns_wave_kernel(const gl_t* va
 // ---------------------------------------------------------------- host side
 template <int LOGN>
 static hipError_t launch_v2(const gl_t* values, gl_t* coeffs, gl_t* lde, size_t n_cols, unsigned rate_bits, const gl_t* tw_fwd,
-                            const gl_t* tw_inv, const gl_t* cs, const gl_t* oh, int from_coeffs, hipStream_t st) {
+                            const gl_t* tw_inv, const gl_t* cs, const gl_t* oh, int from_coeffs, hipStream_t st, unsigned col_base, unsigned* unit_count) {
     using PL = LdePlan<LOGN>;
     const size_t lds_bytes = (size_t)PL::CPB * PL::LDS_COL * sizeof(gl_t);
     if (lds_bytes > 64 * 1024) {  // per device, so not cached in a static
@@ -559,7 +564,7 @@ static hipError_t launch_v2(const gl_t* values, gl_t* coeffs, gl_t* lde, size_t 
     gl_t* cf = keep ? coeffs : lde + (((size_t)1 << rate_bits) - 1) * PL::N;
     const unsigned cf_stride = keep ? (unsigned)PL::N : (unsigned)PL::N << rate_bits;
     hipLaunchKernelGGL(lde_columns_v2_kernel<LOGN>, dim3(blocks), dim3(PL::THREADS), lds_bytes, st, values, cf, cf_stride, keep ? 1 : 0, lde,
-                       (unsigned)n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs);
+                       (unsigned)n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, col_base, unit_count);
     return hipGetLastError();
 }
 
@@ -635,15 +640,16 @@ hipError_t lde_v2_upload_tables(unsigned log_n, unsigned rate_bits, gl_t* d_tw_f
 }
 
 hipError_t launch_lde_columns_v2(const gl_t* values, gl_t* coeffs, gl_t* lde, size_t n_cols, unsigned log_n, unsigned rate_bits,
-                                 const gl_t* tw_fwd, const gl_t* tw_inv, const gl_t* cs, const gl_t* oh, int from_coeffs, hipStream_t st) {
+                                 const gl_t* tw_fwd, const gl_t* tw_inv, const gl_t* cs, const gl_t* oh, int from_coeffs, hipStream_t st,
+                                 unsigned col_base, unsigned* unit_count) {
     if (n_cols == 0) return hipSuccess;
     switch (log_n) {
-        case 8: return launch_v2<8>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st);
-        case 9: return launch_v2<9>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st);
-        case 10: return launch_v2<10>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st);
-        case 11: return launch_v2<11>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st);
-        case 12: return launch_v2<12>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st);
-        case 13: return launch_v2<13>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st);
+        case 8: return launch_v2<8>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st, col_base, unit_count);
+        case 9: return launch_v2<9>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st, col_base, unit_count);
+        case 10: return launch_v2<10>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st, col_base, unit_count);
+        case 11: return launch_v2<11>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st, col_base, unit_count);
+        case 12: return launch_v2<12>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st, col_base, unit_count);
+        case 13: return launch_v2<13>(values, coeffs, lde, n_cols, rate_bits, tw_fwd, tw_inv, cs, oh, from_coeffs, st, col_base, unit_count);
         default: return hipErrorInvalidValue;
     }
 }
@@ -692,7 +698,7 @@ hipError_t lde_wave_upload_tables(unsigned rate_bits, gl_t* d_tab, hipStream_t s
 
 // values [C][8192] -> lde [C][2^rate][8192]; `next`: a device word holding 0 (the launch's column counter); `oh`: the closed-form tables of lde_v2_upload_tables (or null: every column is transformed)
 hipError_t launch_lde_columns_wave(const gl_t* values, gl_t* lde, size_t n_cols, unsigned rate_bits, const gl_t* d_tab, const gl_t* oh, unsigned* next,
-                                   hipStream_t st) {
+                                   hipStream_t st, unsigned col_base, unsigned* unit_count) {
     if (n_cols == 0) return hipSuccess;
     constexpr size_t T = (1u << LDE_WAVE_LOGN) / 16, lds_bytes = (size_t)8 << LDE_WAVE_LOGN;
     hipError_t e = hipFuncSetAttribute((const void*)lde_columns_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);  // per device: not cached
@@ -707,7 +713,7 @@ hipError_t launch_lde_columns_wave(const gl_t* values, gl_t* lde, size_t n_cols,
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const unsigned grid = (unsigned)std::min<size_t>(n_cols, (size_t)2 * (size_t)std::max(cus, 1));
-    hipLaunchKernelGGL(lde_columns_wave_kernel, dim3(grid), dim3(512), lds_bytes, st, values, lde, (unsigned)n_cols, rate_bits, tb, oh, next);
+    hipLaunchKernelGGL(lde_columns_wave_kernel, dim3(grid), dim3(512), lds_bytes, st, values, lde, (unsigned)n_cols, rate_bits, tb, oh, next, col_base, unit_count);
     return hipGetLastError();
 }
 

@@ -102,7 +102,10 @@ int merkle_tree_hasher(Ctx* c, int hasher, const uint64_t* lde_natural, size_t n
 // digests of n_leaves row-major leaves of `width` words under `hasher`
 int hash_rows_hasher(Ctx* c, int hasher, const uint64_t* rows, size_t width, size_t n_leaves, uint64_t* digests_out);
 int permute_batch_form(Ctx* c, int form, int variant, uint64_t* states, size_t n);
-int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped, uint64_t* digests_out);
+int leaf_hash_lane_group(Ctx* c, const uint64_t* mats, size_t n_segments, size_t n_cols, unsigned log_n, unsigned rate_bits, int grouped, int form,
+                         unsigned prefix_mask, uint64_t* digests_out);
+// the leaf hash's saved capacity past an identity prefix, cap[4][N], as the context builds it for this shape (kernel-level test entry)
+int leaf_prefix_table(Ctx* c, unsigned log_n, unsigned rate_bits, uint64_t* cap_out);
 int expand_log(Ctx* c, const TraceLog* log, uint64_t* out_colmajor);
 int lde_bench(Ctx* c, size_t n_cols, unsigned log_n, unsigned rate_bits, unsigned reps, unsigned const_per_64, const uint64_t* device_values, float* ms_out, float* each_ms = nullptr);
 int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);

@@ -59,8 +59,10 @@ struct PhaseRanges {
 // launch has transformed, and the last lde_tail_columns(C) columns -- 1/64 of them, 75 MB for FinalExp -- from a copy (`tail`).  Carried
 // to the end the series would be log_R(C) launches, the last of them a few columns wide and each as long as one column takes; four
 // launches cost 0.07 ms of 17.5 against one (same box, alternating builds).
-static hipError_t run_lde_trace(Ctx* c, const gl_t* values, gl_t* lde, gl_t* tail, size_t C, unsigned log_n, unsigned rate, bool in_place) {
-    if (!in_place) return run_lde(c, values, nullptr, lde, C, log_n, rate, 0);
+// unit_count (or null): the word in which the launches count the columns e_c, each launch from the absolute index of its first column
+// (kernels.h: LeafPrefix); every column is transformed by exactly one launch.
+static hipError_t run_lde_trace(Ctx* c, const gl_t* values, gl_t* lde, gl_t* tail, size_t C, unsigned log_n, unsigned rate, bool in_place, unsigned* unit_count) {
+    if (!in_place) return run_lde(c, values, nullptr, lde, C, log_n, rate, 0, 0, unit_count);
     const size_t n = (size_t)1 << log_n, R = (size_t)1 << rate;
     for (const LdeLaunch& l : lde_launch_plan(C, rate)) {
         const gl_t* in = values + l.a * n;
@@ -68,7 +70,7 @@ static hipError_t run_lde_trace(Ctx* c, const gl_t* values, gl_t* lde, gl_t* tai
             if (hipError_t e = hipMemcpyAsync(tail, in, (l.b - l.a) * n * 8, hipMemcpyDeviceToDevice, c->st); e != hipSuccess) return e;
             in = tail;
         }
-        if (hipError_t e = run_lde(c, in, nullptr, lde + l.a * R * n, l.b - l.a, log_n, rate, 0); e != hipSuccess) return e;
+        if (hipError_t e = run_lde(c, in, nullptr, lde + l.a * R * n, l.b - l.a, log_n, rate, 0, (unsigned)l.a, unit_count); e != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -140,7 +142,9 @@ static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n
         {&c->comb_partial, (comb_chunks(C) + (s.nZ ? 1 : 0)) * n * 16},  // (the Zs' sum is one more chunk)
         {&c->comb_out, 2 * n * 16}, {&c->fri_coef, 2 * N * 8}, {&c->fri_vals, 2 * N * 8},
         {&c->scale_tab, N * 8}, {&c->pow_state, 12 * 8}, {&c->pow_best, 8}, {&c->qidx, nq * 4},
-        {&c->gather_t, nq * s.pl.query_words * 8}};  // every query round's leaves and Merkle paths, in proof layout
+        {&c->gather_t, nq * s.pl.query_words * 8},  // every query round's leaves and Merkle paths, in proof layout
+        // the leaf hash's saved state past an identity prefix and its counter, kept with the shape's tables (ctx.h); 0 where this proof cannot use it
+        {&c->tab->leaf_prefix, leaf_prefix_bytes(c, C, s.log_n, s.r)}};
     if (const size_t nZ = s.nZ) {  // an AIR with permutation pairs (Ctx::PermBufs)
         Ctx::PermBufs& pb = c->perm;
         for (const BufWant& b : {BufWant{&pb.cols, s.perm_cols * n * 8}, BufWant{&pb.desc, 2 * s.perm_desc_words * 4}, BufWant{&pb.chal, 4 * (size_t)s.factor * 8},
@@ -196,6 +200,7 @@ struct ProveCall {
     bool tiled;          // the quotient's evaluator: the tiled plan, or the op-stream interpreter
     unsigned n_chunks;   // ... and the chunks its constraints are cut into
     bool trace_in_lde;   // the trace waits for the LDE inside the LDE buffer, as its last C n words (run_lde_trace)
+    bool prefix;         // the LDE counts the columns e_c and the trace commitment may start from the saved state past them (kernels.h: LeafPrefix)
     gl_t* d_trace;       // where the upload puts the trace, column-major
     const gl_t* d_values = nullptr;  // where it is: d_trace, or the caller's own device memory
     Challenger ch;
@@ -298,7 +303,10 @@ int ProveCall::upload() {
 int ProveCall::ifft_lde() {
     HIPCHK(hipEventRecord(c->kev[4], st));
     if (lde_long_supported(s.log_n)) HIPCHK(run_lde(c, d_values, c->values.as<gl_t>(), c->lde.as<gl_t>(), s.C, s.log_n, s.r, 0));  // coefficients into `values`
-    else HIPCHK(run_lde_trace(c, d_values, c->lde.as<gl_t>(), c->values.as<gl_t>(), s.C, s.log_n, s.r, trace_in_lde));
+    else {
+        HIPCHK(leaf_prefix_reset(c));  // whatever an earlier proof of this shape counted
+        HIPCHK(run_lde_trace(c, d_values, c->lde.as<gl_t>(), c->values.as<gl_t>(), s.C, s.log_n, s.r, trace_in_lde, prefix ? leaf_prefix_counter(c) : nullptr));
+    }
     HIPCHK(hipEventRecord(c->kev[5], st));
     return 0;
 }
@@ -345,6 +353,7 @@ int ProveCall::leaf_hash_on_host() {
 
 // ---- phase 2: Merkle tree over bit-reversed LDE rows
 int ProveCall::trace_merkle() {
+    const LeafPrefix pf = prefix ? leaf_prefix(c) : LeafPrefix();
     HIPCHK(hipEventRecord(c->kev[0], st));
     if (c->opt_hasher == STARKHIP_HASHER_KECCAK) {
         // The Keccak leaf hash is the context's own launch on its own stream, pooled or not: the pool's merged and lane-group launches are
@@ -358,10 +367,10 @@ int ProveCall::trace_merkle() {
     } else if (c->hs) {  // pooled: the scheduler decides when this commitment runs and which others share its launch
         c->hash_requested = true;
         HIPCHK(c->hs->hash(c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st, c->hash_ready, c->hash_done, !HashService::is_big(s.log_n, s.r), c->urgent,
-                           &c->hash_timing));
+                           &c->hash_timing, pf));
     } else {
         c->hash_timing.group = 1;
-        HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st, &c->hash_timing.form));
+        HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st, &c->hash_timing.form, pf));
     }
     HIPCHK(hipEventRecord(c->kev[1], st));
     HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, c->digests.as<gl_t>(), s.log_N, s.cap_h, st));
@@ -828,8 +837,11 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     const size_t values_bytes = values_bytes_for(s, trace_in_lde, callers_columns);
     for (const BufWant& w : work_buffers(c, s, n_chunks, tiled ? c->plan : nullptr, values_bytes, park_words * 8)) HIPCHK(w.b->ensure(w.bytes));
     if (int rc = ensure_long_tables(c, s)) return rc;
+    const bool prefix = leaf_prefix_wanted(c, C, s.log_n, s.r);
+    if (prefix)
+        if (int rc = ensure_leaf_prefix(c, s.log_n, s.r)) return rc;
 
-    ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde,
+    ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde, prefix,
                 trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()};
     p.ch.hasher = (int)c->opt_hasher;  // the transcript's sponge duplexes through the context's hasher
     // before each phase: the boundary event of starkhip_last_timings on the stream and the phase's rocTX range (rocprofv3 --marker-trace)
@@ -891,6 +903,8 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t
     const size_t values_bytes = values_bytes_for(s, s.r >= 1, false);
     for (const BufWant& w : work_buffers(c, s, c->plan->chunks, c->plan, values_bytes, log_bytes + 64)) HIPCHK(w.b->ensure(w.bytes));
     if (int rc = ensure_long_tables(c, s)) return rc;
+    if (leaf_prefix_wanted(c, s.C, s.log_n, s.r))
+        if (int rc = ensure_leaf_prefix(c, s.log_n, s.r)) return rc;
     if (log_bytes && !device_traces) HIPCHK(ensure_host_staging(c, log_bytes, log_bytes));
     if (proof_blobs && !c->blob_airs.count(air.id)) {  // page-locked blobs for this AIR's proofs, once per context
         if (blob_arena_add(c, s.pl.total * 8, proof_blobs) != 0) return STARKHIP_ERR_OOM;

@@ -102,8 +102,10 @@ class HashService {
         int form = SENT_QUAD;
         unsigned group = 1;
     };
+    // `prefix`: the caller's saved state past an identity prefix (kernels.h: LeafPrefix) for the lane and pair forms; a group may mix
+    // members with and without one.
     hipError_t hash(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, gl_t* digests, hipStream_t st, hipEvent_t ready,
-                    hipEvent_t done, bool announced, bool urgent = false, Timing* timing = nullptr);
+                    hipEvent_t done, bool announced, bool urgent = false, Timing* timing = nullptr, LeafPrefix prefix = LeafPrefix());
 
     const Config cfg;
 
@@ -126,6 +128,7 @@ class HashService {
         hipError_t err = hipSuccess;
         double t_arrive = 0;
         Timing* timing = nullptr;
+        LeafPrefix prefix;
     };
     void run();
     double big_wait_bound() const;  // under mu_: how long the oldest queued big commitment waits at most for its group to fill
