@@ -85,6 +85,12 @@ asan-perm-check-test: tests/asan_perm_check_main.cpp $(ASAN_SRCS) $(HDRS)
 	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_perm_check tests/asan_perm_check_main.cpp $(ASAN_SRCS) -lpthread
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_perm_check
 
+# the host driver and the replay of starkhip_lookup_columns (lookup_columns.cpp) and AirBuilder::lookup under the same two: a stand-alone program
+asan-lookup-test: tests/asan_lookup_main.cpp $(ASAN_SRCS) $(HDRS)
+	@mkdir -p build/asan
+	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_lookup tests/asan_lookup_main.cpp $(ASAN_SRCS) -lpthread
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_lookup
+
 # Experiment builds of the device code for A/B runs on one box: `make variant NAME=x DEFS="-D..."` -> build/x/libstarkhip_x.so, selected
 # at run time with STARKHIP_LIBRARY=build/x/libstarkhip_x.so (e.g. NAME=nomfma DEFS=-DSTARKHIP_LANE_NO_MFMA: the lane-form leaf hash with every
 # round as multiply-add chains; NAME=noprio DEFS=-DSTARKHIP_NO_PRIO: no raised issue priority for the kernels beside the lane-form hash)
@@ -100,4 +106,4 @@ build/$(NAME)/libstarkhip_$(NAME).so: $(VAR_OBJS) $(filter %.cpp.o,$(OBJS))
 clean:
 	rm -rf build $(OUT)
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test asan-keccak-test asan-perm-check-test variant
+.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test asan-keccak-test asan-perm-check-test asan-lookup-test variant

@@ -220,6 +220,37 @@ pub struct starkhip_perm_check_t {
     pub reseeds: u64,
 }
 
+/// `STARKHIP_LOOKUPS_MAX`: the lookups one `starkhip_lookup_columns` call takes.
+pub const STARKHIP_LOOKUPS_MAX: usize = 64;
+
+/// `starkhip_lookup_t`: one lookup as four columns of the trace.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct starkhip_lookup_t {
+    /// the column that is looked up
+    pub input: u32,
+    /// the column it is looked up in
+    pub table: u32,
+    /// the witness column that receives the input sorted
+    pub permuted_input: u32,
+    /// the witness column that receives the table rearranged beside it
+    pub permuted_table: u32,
+}
+
+/// `starkhip_lookup_report_t`: the summary of `starkhip_lookup_columns`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct starkhip_lookup_report_t {
+    /// the lookups of the call
+    pub lookups: u64,
+    /// lookups whose table lacks a value of their input: their output columns were left as they were
+    pub lookups_failed: u64,
+    /// input rows holding such a value, over all lookups
+    pub missing_rows: u64,
+    /// entries written to `list`: min(cap, missing_rows)
+    pub listed: u64,
+}
+
 extern "C" {
     pub fn starkhip_config_standard_fast(cfg: *mut starkhip_config_t);
     pub fn starkhip_config_for_air(air: Air, cfg: *mut starkhip_config_t) -> c_int;
@@ -296,6 +327,18 @@ extern "C" {
     pub fn starkhip_perm_check_seeds(seed: u64, out: *mut u64) -> c_int;
     // ms [4]: upload, sort, classification, read-back of the context's last starkhip_check_trace_permutations
     pub fn starkhip_perm_check_timings(ctx: *mut c_void, ms: *mut f32) -> c_int;
+    // Fill the permuted columns of each lookup in the caller's trace, in place (host or device memory, both layouts).  per_lookup
+    // [n_lookups] or null, missing_masks [n_lookups][(n_rows + 63) / 64] or null (bit r & 63 of word r >> 6), list cap x {lookup, row}
+    // (may be null when cap == 0; cap <= STARKHIP_CHECK_LIST_MAX), by lookup, row.  A lookup that fails keeps its columns.
+    pub fn starkhip_lookup_columns(ctx: *mut c_void, trace: *mut u64, n_rows: usize, n_cols: usize, layout: c_int, on_device: c_int,
+                                   lookups: *const starkhip_lookup_t, n_lookups: usize, per_lookup: *mut u32, missing_masks: *mut u64,
+                                   list: *mut u64, cap: usize, out: *mut starkhip_lookup_report_t) -> c_int;
+    // tests: the same host driver over host loops (std::stable_sort); `trace` is host memory
+    pub fn starkhip_lookup_columns_replay(trace: *mut u64, n_rows: usize, n_cols: usize, layout: c_int, lookups: *const starkhip_lookup_t,
+                                          n_lookups: usize, per_lookup: *mut u32, missing_masks: *mut u64, list: *mut u64, cap: usize,
+                                          out: *mut starkhip_lookup_report_t) -> c_int;
+    // ms [4]: upload or gather, sort, placement, read-back of the context's last starkhip_lookup_columns
+    pub fn starkhip_lookup_timings(ctx: *mut c_void, ms: *mut f32) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

@@ -347,6 +347,60 @@ int starkhip_perm_check_seeds(uint64_t seed, uint64_t out[STARKHIP_PERM_CHECK_AT
  * last the host's time in the copies. */
 int starkhip_perm_check_timings(void* ctx, float ms[4]);
 
+/* LOOKUPS.  Nobody declares a permutation pair for its own sake: a pair range-checks a column or looks it up in a table, in the
+ * Halo2-style argument plonky2's evm/src/lookup.rs builds on starky's pairs (COMPAT.md 2b).  For a lookup of column a in table
+ * column t the trace carries two witness columns: a' a permutation of a, t' a permutation of t, with a'[i] = t'[i] or a'[i] =
+ * a'[i - 1] on every row.  This entry FILLS those two columns of a trace, per lookup {input, table, permuted_input, permuted_table}
+ * (four column numbers; the call takes no AIR), by one rule -- a pure function of the two multisets, cells read mod p as every trace
+ * reader does, outputs canonical:
+ *   A = a sorted ascending, T = t sorted ascending; permuted_input = A.  Position i of A is a HEAD when i = 0 or A[i] != A[i - 1];
+ *   position j of T is USED when it is the first position of T holding its value and that value occurs in a.  The lookup HOLDS
+ *   when every value of a occurs in t; then heads and used positions are equally many, permuted_table[i] = A[i] on every head, and
+ *   the k-th non-head position of A takes the k-th unused entry of T (both ascending).  It FAILS when some value of a is absent
+ *   from t: those rows of the input column are its MISSING rows, and its two output columns are left exactly as they were; the
+ *   other lookups of the call are still written.
+ * This is a valid witness, not the one evm's permuted_cols computes (which hands unused table values out last-in first-out).
+ * The output columns are written into the caller's trace where it lies: device memory in place (element r of a column at stride 1
+ * for layout 1, n_cols for layout 0); of a host trace only the two columns of each lookup go up and the two output columns come
+ * back.  Nothing else in the trace is touched.
+ *   per_lookup (n_lookups entries, or NULL): the missing rows of each lookup;
+ *   missing_masks (n_lookups x (n_rows + 63) / 64 words, or NULL): bit (r & 63) of word r >> 6 = row r of the lookup's input is missing;
+ *   list (cap x {lookup, row}; may be NULL when cap == 0): the first min(cap, missing_rows) missing rows by lookup, then row.
+ * The same bytes on every run.  STARKHIP_OK whether or not lookups failed: the report says.  trace, n_rows, n_cols, layout and
+ * on_device are starkhip_check_trace_permutations' (2 .. 2^STARKHIP_MAX_LOG_ROWS rows, a power of two).  BAD_SHAPE for a NULL
+ * trace, lookups or out, an unknown layout, rows outside the limits, n_lookups = 0 or > STARKHIP_LOOKUPS_MAX, a column >= n_cols,
+ * an output column that is also any lookup's input or table column or another output column of the call, cap >
+ * STARKHIP_CHECK_LIST_MAX, a NULL list with cap > 0.  A table column shared by several lookups is fine.  One call at a time per
+ * context, not beside a prove on it.  On the context's device: the stable sort of csrc/kernels_multiset.hip, then a mark pass, a scan
+ * and two placements per lookup (csrc/kernels_lookup.hip); the placements run only once the lookup's missing count is known zero. */
+#define STARKHIP_LOOKUPS_MAX 64
+typedef struct {
+    uint32_t input, table, permuted_input, permuted_table;
+} starkhip_lookup_t;
+typedef struct {
+    uint64_t lookups, lookups_failed;
+    uint64_t missing_rows;   /* over all lookups */
+    uint64_t listed;         /* entries written to `list`: min(cap, missing_rows) */
+} starkhip_lookup_report_t;
+int starkhip_lookup_columns(void* ctx, uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                            const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* missing_masks,
+                            uint64_t* list, size_t cap, starkhip_lookup_report_t* out);
+/* tests: the same host driver -- argument checks, the loop over the lookups, the list from the masks, the report -- with the device
+ * steps replaced by host loops that implement the rule literally (std::stable_sort).  `trace` is host memory.  No device needed. */
+int starkhip_lookup_columns_replay(uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const starkhip_lookup_t* lookups,
+                                   size_t n_lookups, uint32_t* per_lookup, uint64_t* missing_masks, uint64_t* list, size_t cap,
+                                   starkhip_lookup_report_t* out);
+/* ms = {upload or gather of the lookups' columns, keys and sort passes, mark + scan + placements, read-backs of masks and of a host
+ * trace's output columns} of the last starkhip_lookup_columns on this context: the first three from events on its stream, summed over
+ * the lookups, the last the host's time in the copies. */
+int starkhip_lookup_timings(void* ctx, float ms[4]);
+/* tests: the program the C++ AirBuilder (csrc/air_ir.h) makes of n_cols columns, no public inputs and `degree` with one
+ * AirBuilder::lookup per entry of `lookups` -- per lookup the constraint (N(pi) - L(pi)) (N(pi) - N(pt)), the last-row constraint
+ * N(pi) - N(pt), and the pairs [(input, pi)], [(table, pt)] -- for comparison with the Python builder's.  *words = its length; the blob
+ * is written when it fits cap_words (BAD_SHAPE otherwise, and for arguments the builder refuses). */
+int starkhip_lookup_air_blob(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, uint64_t* blob,
+                             size_t cap_words, size_t* words);
+
 /* --- natives + trace generation (host)----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.
  * trace is written row-major [n_rows][columns]; public_inputs has starkhip_air_public_inputs() entries. */

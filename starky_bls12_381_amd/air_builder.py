@@ -181,6 +181,7 @@ class AirBuilder:
         self.code, self.group_off, self.group_k0 = [], [], []
         self._open, self._kind, self._gates, self._cur = False, 0, [], []
         self.perm_pairs = []
+        self.lookups = []  # (input, table, permuted_input, permuted_table) of every lookup()
 
     def L(self, col):
         self._check_col(col)
@@ -223,6 +224,21 @@ class AirBuilder:
             self._check_col(l)
             self._check_col(r)
         self.perm_pairs.append(entries)
+
+    def lookup(self, input, table, permuted_input, permuted_table):
+        """One lookup of column `input` in table column `table` through the witness columns `permuted_input` (pi) and `permuted_table`
+        (pt), in the form of evm's `eval_lookups`: the constraint (N(pi) - L(pi)) * (N(pi) - N(pt)) on every row and the last-row
+        constraint N(pi) - N(pt), whose next row is row 0; then the pairs [(input, pi)] and [(table, pt)], in that order.  The four
+        columns are recorded in `self.lookups`, the list `Prover.lookup_columns` takes to fill pi and pt.  The validator's limits
+        decide what fits: two pairs need degree >= 3, and an AIR holds at most B batches of B = degree - 1 pairs.  One batch shares
+        one challenge: COMPAT.md §2a says what that does and does not show."""
+        cols = tuple(int(c) for c in (input, table, permuted_input, permuted_table))
+        pi, pt = cols[2], cols[3]
+        self.constraint((self.N(pi) - self.L(pi)) * (self.N(pi) - self.N(pt)))
+        self.last_row(self.N(pi) - self.N(pt))
+        self.permutation_pair([(cols[0], pi)])
+        self.permutation_pair([(cols[1], pt)])
+        self.lookups.append(cols)
 
     def count(self):
         return self.n_constraints

@@ -726,6 +726,98 @@ def check_trace_permutations_replay(air, trace, layout=0, seed=DEFAULT_SEED, cap
                                                                                             layout, *a), air, n_rows, seed, cap)
 
 
+LOOKUPS_MAX = 64  # STARKHIP_LOOKUPS_MAX
+
+
+class _LookupStruct(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("input", "table", "permuted_input", "permuted_table")]
+
+
+class _LookupReportStruct(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("lookups", "lookups_failed", "missing_rows", "listed")]
+
+
+lib.starkhip_lookup_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.POINTER(_LookupStruct), C.c_size_t, _u32p,
+                                        _u64p, _u64p, C.c_size_t, C.POINTER(_LookupReportStruct)]
+lib.starkhip_lookup_columns_replay.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(_LookupStruct), C.c_size_t, _u32p, _u64p, _u64p,
+                                               C.c_size_t, C.POINTER(_LookupReportStruct)]
+lib.starkhip_lookup_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+lib.starkhip_lookup_air_blob.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(_LookupStruct), C.c_size_t, _u64p, C.c_size_t, C.POINTER(C.c_size_t)]
+
+
+class LookupReport:
+    """What starkhip_lookup_columns did, lookup by lookup: `lookups`, `failed`: the lookups some of whose input values their table does
+    not hold -- their two output columns were left as they were; `missing_rows`: those input rows over all lookups; `per_lookup`
+    (np.uint32[n_lookups]): per lookup; `masks` (bool[n_lookups, n]): masks[q, r] is True when row r of lookup q's input is missing;
+    `mask_words` (np.uint64[n_lookups, (n + 63) // 64]): the same as the library wrote it; `list` (np.uint64[listed, 2]): the first
+    min(cap, missing_rows) missing rows as (lookup, row), by lookup, then row; `timings`: the call's milliseconds by phase on the
+    device (None for the replay)."""
+
+    def __init__(self, summary, per_lookup, words, entries, n_rows, timings=None):
+        self.lookups, self.failed, self.missing_rows = int(summary.lookups), int(summary.lookups_failed), int(summary.missing_rows)
+        self.per_lookup, self.mask_words = per_lookup, words
+        self.list = entries[:int(summary.listed)].copy()
+        self.timings = timings
+        self._n_rows, self._masks = n_rows, None
+
+    @property
+    def masks(self):  # unpacked on first use: eight times the words
+        if self._masks is None:
+            bits = np.unpackbits(self.mask_words.view(np.uint8).reshape(self.mask_words.shape[0], -1), axis=1, bitorder="little")
+            self._masks = np.ascontiguousarray(bits[:, :self._n_rows]).astype(bool)
+        return self._masks
+
+    def __repr__(self):
+        return f"LookupReport(lookups={self.lookups}, failed={self.failed}, missing_rows={self.missing_rows}, listed={len(self.list)})"
+
+
+def _lookup_array(lookups):
+    """lookups: [(input, table, permuted_input, permuted_table), ...] (AirBuilder.lookups) -> the C array"""
+    lookups = [tuple(int(c) for c in lk) for lk in lookups]
+    if any(len(lk) != 4 or not all(0 <= c < 1 << 32 for c in lk) for lk in lookups):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    return (_LookupStruct * max(1, len(lookups)))(*[_LookupStruct(*lk) for lk in lookups]), len(lookups)
+
+
+def _lookup_columns(call, lookups, n_rows, cap):
+    """`call(lookups, n_lookups, per_lookup, masks, list, cap, summary)` -> rc: one of the two entry points with its leading arguments bound."""
+    cap = int(cap)
+    if cap < 0:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    arr, nl = _lookup_array(lookups)
+    per = np.zeros(max(1, nl), dtype=np.uint32)
+    words = np.zeros((min(nl, LOOKUPS_MAX), (n_rows + 63) // 64), dtype=np.uint64)  # more lookups are the library's to refuse
+    entries = np.zeros((min(cap, CHECK_LIST_MAX), 2), dtype=np.uint64)  # a larger cap is the library's to refuse
+    summary = _LookupReportStruct()
+    _chk(call(arr, nl, per.ctypes.data_as(_u32p) if nl <= LOOKUPS_MAX else None, _p64(words) if words.size else None, _p64(entries) if cap else None,
+              cap, C.byref(summary)))
+    return LookupReport(summary, per[:nl], words, entries, n_rows)
+
+
+def _writable_trace(trace, layout):
+    if not isinstance(trace, np.ndarray) or trace.dtype != np.uint64 or trace.ndim != 2 or not trace.flags.c_contiguous or not trace.flags.writeable \
+            or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    return trace.shape if layout == 0 else trace.shape[::-1]
+
+
+def lookup_columns_replay(trace, lookups, layout=0, cap=1024):
+    """starkhip_lookup_columns_replay (tests): Prover.lookup_columns' host driver with the device steps replaced by host loops that
+    implement the rule literally.  Writes into `trace` (a C-contiguous writable np.uint64 array).  No device needed."""
+    n_rows, n_cols = _writable_trace(trace, layout)
+    return _lookup_columns(lambda *a: lib.starkhip_lookup_columns_replay(trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, *a), lookups,
+                           n_rows, cap)
+
+
+def lookup_air_blob(n_cols, degree, lookups):
+    """tests: the program the C++ AirBuilder makes of `n_cols` columns and `degree` with one lookup() per entry (starkhip_lookup_air_blob)."""
+    arr, nl = _lookup_array(lookups)
+    words = C.c_size_t()
+    blob = np.zeros(4096, dtype=np.uint64)
+    _chk(lib.starkhip_lookup_air_blob(n_cols, degree, arr, nl, _p64(blob), blob.size, C.byref(words)))
+    return blob[:words.value].copy()
+
+
 # ----------------------------------------------------------------------------- traces (generate_trace)
 class CompactTrace:
     """A trace recorded as runs (starkhip_trace_log_*): the generator's limb vectors with the rows they
@@ -1055,6 +1147,35 @@ class Prover:
         ms = (C.c_float * 4)()
         _chk(lib.starkhip_perm_check_timings(self._ctx, ms))
         return dict(zip(("upload", "sort", "classify", "read_back"), (float(x) for x in ms)))
+
+    def lookup_columns(self, trace, lookups, layout=0, cap=1024):
+        """Fill the permuted columns of each lookup of `lookups` -- [(input, table, permuted_input, permuted_table), ...], e.g.
+        AirBuilder.lookups -- in `trace` (starkhip_lookup_columns): a sort and a placement per lookup on this context's device, written
+        into the array given (C-contiguous, writable, np.uint64; row-major [n][C], or column-major [C][n] with layout=1).  A lookup
+        whose table lacks a value of its input keeps its columns as they were and reports the rows.  Returns a LookupReport."""
+        n_rows, n_cols = _writable_trace(trace, layout)
+        return self._lookup_columns(trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, lookups, cap)
+
+    def lookup_columns_device(self, trace_ptr, n_rows, n_cols, lookups, layout=1, cap=1024):
+        """lookup_columns on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr()),
+        written in place."""
+        return self._lookup_columns(C.c_void_p(trace_ptr), n_rows, n_cols, layout, 1, lookups, cap)
+
+    def _lookup_columns(self, trace_arg, n_rows, n_cols, layout, on_device, lookups, cap):
+        t0 = time.perf_counter()
+        try:
+            rep = _lookup_columns(lambda *a: lib.starkhip_lookup_columns(self._ctx, trace_arg, n_rows, n_cols, layout, on_device, *a), lookups,
+                                  n_rows, cap)
+        finally:
+            self.last_call_s = time.perf_counter() - t0
+        rep.timings = self.last_lookup_timings()
+        return rep
+
+    def last_lookup_timings(self):
+        """Milliseconds of the last lookup_columns: {upload, sort, place, read_back} (starkhip_lookup_timings)."""
+        ms = (C.c_float * 4)()
+        _chk(lib.starkhip_lookup_timings(self._ctx, ms))
+        return dict(zip(("upload", "sort", "place", "read_back"), (float(x) for x in ms)))
 
     def check_trace_device(self, air, trace_ptr, n_rows, public_inputs, layout=1):
         """check_trace on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""

@@ -325,6 +325,21 @@ class AirBuilder {
         prog_.perm_pairs.push_back(std::move(e));
     }
 
+    // One lookup of column `input` in table column `table` through the witness columns permuted_input (pi) and permuted_table (pt), in
+    // the form of evm's eval_lookups: the constraint (N(pi) - L(pi)) (N(pi) - N(pt)) on every row and the last-row constraint
+    // N(pi) - N(pt), whose next row is row 0; then the pairs [(input, pi)] and [(table, pt)], in that order.  starkhip_lookup_columns
+    // fills pi and pt; lookups() is the list it takes.  The validator's limits decide what fits: two pairs need degree >= 3, and an
+    // AIR holds at most B batches of B = degree - 1 pairs.  One batch shares one challenge: COMPAT.md 2a says what that shows.
+    void lookup(uint32_t input, uint32_t table, uint32_t permuted_input, uint32_t permuted_table) {
+        constraint((N(permuted_input) - L(permuted_input)) * (N(permuted_input) - N(permuted_table)));
+        last_row(N(permuted_input) - N(permuted_table));
+        permutation_pair({{input, permuted_input}});
+        permutation_pair({{table, permuted_table}});
+        lookups_.push_back({input, table, permuted_input, permuted_table});
+    }
+    struct Lookup { uint32_t input, table, permuted_input, permuted_table; };  // as starkhip_lookup_t
+    const std::vector<Lookup>& lookups() const { return lookups_; }
+
     uint32_t count() const { return prog_.n_constraints; }
 
     AirProgram finish() {
@@ -343,6 +358,7 @@ class AirBuilder {
     uint32_t cur_kind_ = 0;
     std::vector<uint32_t> cur_gates_;
     std::vector<Pending> cur_;
+    std::vector<Lookup> lookups_;
 
     void check_col(uint32_t col) const {
         if (col >= prog_.n_cols) throw std::runtime_error("air_ir: column " + std::to_string(col) + " out of range");

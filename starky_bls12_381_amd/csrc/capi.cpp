@@ -16,6 +16,7 @@
 #include "free_cells.h"
 #include "kernels.h"
 #include "lde_ranges.h"
+#include "lookup_columns.h"
 #include "permutation.h"
 #include "permutation_check.h"
 #include "trace_log.h"
@@ -353,6 +354,44 @@ int starkhip_perm_check_timings(void* ctx, float ms[4]) {
     if (!ms) return STARKHIP_ERR_BAD_SHAPE;
     perm_check_timings((Ctx*)ctx, ms);
     return STARKHIP_OK;
+}
+
+int starkhip_lookup_columns(void* ctx, uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                            const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* missing_masks,
+                            uint64_t* list, size_t cap, starkhip_lookup_report_t* out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const LookupTrace tr = {trace, n_rows, n_cols, layout, on_device != 0};
+    if (int rc = lookup_args(tr, lookups, n_lookups, list, cap, out)) return rc;
+    return guarded([&] { return lookup_columns((Ctx*)ctx, tr, lookups, n_lookups, per_lookup, missing_masks, list, cap, out); });
+}
+
+int starkhip_lookup_columns_replay(uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const starkhip_lookup_t* lookups,
+                                   size_t n_lookups, uint32_t* per_lookup, uint64_t* missing_masks, uint64_t* list, size_t cap,
+                                   starkhip_lookup_report_t* out) {
+    const LookupTrace tr = {trace, n_rows, n_cols, layout, 0};
+    if (int rc = lookup_args(tr, lookups, n_lookups, list, cap, out)) return rc;
+    return guarded([&] { return lookup_columns_replay(tr, lookups, n_lookups, per_lookup, missing_masks, list, cap, out); });
+}
+
+int starkhip_lookup_timings(void* ctx, float ms[4]) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    if (!ms) return STARKHIP_ERR_BAD_SHAPE;
+    lookup_timings((Ctx*)ctx, ms);
+    return STARKHIP_OK;
+}
+
+int starkhip_lookup_air_blob(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, uint64_t* blob,
+                             size_t cap_words, size_t* words) {
+    if (!lookups || !words || (cap_words && !blob)) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] {
+        AirBuilder b(n_cols, 0, degree);
+        for (size_t q = 0; q < n_lookups; q++) b.lookup(lookups[q].input, lookups[q].table, lookups[q].permuted_input, lookups[q].permuted_table);
+        const std::vector<uint64_t> w = b.finish().serialize();
+        *words = w.size();
+        if (w.size() > cap_words) return (int)STARKHIP_ERR_BAD_SHAPE;
+        std::copy(w.begin(), w.end(), blob);
+        return (int)STARKHIP_OK;
+    });
 }
 
 int starkhip_quotient_plan_check(starkhip_air_t air, unsigned want_chunks, uint64_t seed, uint64_t stats[8]) {

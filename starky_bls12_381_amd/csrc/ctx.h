@@ -1,7 +1,7 @@
 // The prover context and what the host files around it share: Ctx and its device buffers (DevBuf), the error macro of every HIP call
 // (HIPCHK), and the declarations of ctx.hip -- the sleeping wait and the read-back arena, the per-shape table cache, the per-AIR plan and
 // op-stream program caches, the transform dispatch and the uploads that proof, trace checkers and test entries have in common.
-// Internal to the .hip files that define prover.h's functions (ctx.hip, prover.hip, check_trace.hip, kernel_entries.hip): prover.h stays
+// Internal to the .hip files that define prover.h's functions (ctx.hip, prover.hip, check_trace.hip, lookup_columns.hip, kernel_entries.hip): prover.h stays
 // the opaque interface for capi.cpp, the pools and the verifier.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -184,6 +184,7 @@ struct Ctx {
         for (DevBuf* b : free_chk.bufs()) v.push_back(b);
         for (DevBuf* b : perm.bufs()) v.push_back(b);
         for (DevBuf* b : mset.bufs()) v.push_back(b);
+        for (DevBuf* b : lookup.bufs()) v.push_back(b);
         for (auto& t : table_cache)
             for (DevBuf* b : t->bufs()) v.push_back(b);
         for (auto& d : plan_cache)
@@ -216,6 +217,16 @@ struct Ctx {
         float ms[4] = {0, 0, 0, 0};
         std::vector<DevBuf*> bufs() { return {&desc, &keys, &idx, &table, &masks}; }
     } mset;
+    // starkhip_lookup_columns (lookup_columns.hip over kernels_multiset.hip and kernels_lookup.hip), sized for ONE lookup and grown like
+    // the ones above; keys, idx and the digit table are mset's.  desc: per lookup {1, input, table}, then {1, 0, 1} for staged columns;
+    // cols: the staging of a trace that is not column-major device memory, [4][n] -- input, table, then the two output columns of a
+    // host trace; flags: what each sorted position is; sums: the tile counts [3][tiles]; slot: the non-heads' ranks; mask: the missing
+    // rows of the lookup followed by their count.  ms: the last call's timings (starkhip_lookup_timings).
+    struct LookupBufs {
+        DevBuf desc, cols, flags, sums, slot, mask;
+        float ms[4] = {0, 0, 0, 0};
+        std::vector<DevBuf*> bufs() { return {&desc, &cols, &flags, &sums, &slot, &mask}; }
+    } lookup;
 };
 
 // ---- ctx.hip

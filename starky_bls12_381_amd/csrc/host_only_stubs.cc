@@ -138,6 +138,10 @@ int check_trace_permutations(Ctx*, const AirInfo&, const TraceInput&, uint64_t, 
     return STARKHIP_ERR_NO_DEVICE;
 }
 void perm_check_timings(Ctx*, float ms[4]) { ms[0] = ms[1] = ms[2] = ms[3] = 0; }
+int lookup_columns(Ctx*, const LookupTrace&, const starkhip_lookup_t*, size_t, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_lookup_report_t*) {
+    return STARKHIP_ERR_NO_DEVICE;
+}
+void lookup_timings(Ctx*, float ms[4]) { ms[0] = ms[1] = ms[2] = ms[3] = 0; }
 int lde_bench(Ctx*, size_t, unsigned, unsigned, unsigned, unsigned, const uint64_t*, float*, float*) { return STARKHIP_ERR_NO_DEVICE; }
 int field_ops(Ctx*, int, const uint64_t*, const uint64_t*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int permutation_zs(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
