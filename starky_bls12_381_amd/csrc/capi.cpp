@@ -360,17 +360,17 @@ int starkhip_lookup_columns(void* ctx, uint64_t* trace, size_t n_rows, size_t n_
                             const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* missing_masks,
                             uint64_t* list, size_t cap, starkhip_lookup_report_t* out) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
-    const LookupTrace tr = {trace, n_rows, n_cols, layout, on_device != 0};
-    if (int rc = lookup_args(tr, lookups, n_lookups, list, cap, out)) return rc;
-    return guarded([&] { return lookup_columns((Ctx*)ctx, tr, lookups, n_lookups, per_lookup, missing_masks, list, cap, out); });
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = lookup_args(in, lookups, n_lookups, list, cap, out)) return rc;
+    return guarded([&] { return lookup_columns((Ctx*)ctx, in, trace, lookups, n_lookups, per_lookup, missing_masks, list, cap, out); });
 }
 
 int starkhip_lookup_columns_replay(uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const starkhip_lookup_t* lookups,
                                    size_t n_lookups, uint32_t* per_lookup, uint64_t* missing_masks, uint64_t* list, size_t cap,
                                    starkhip_lookup_report_t* out) {
-    const LookupTrace tr = {trace, n_rows, n_cols, layout, 0};
-    if (int rc = lookup_args(tr, lookups, n_lookups, list, cap, out)) return rc;
-    return guarded([&] { return lookup_columns_replay(tr, lookups, n_lookups, per_lookup, missing_masks, list, cap, out); });
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = lookup_args(in, lookups, n_lookups, list, cap, out)) return rc;
+    return guarded([&] { return lookup_columns_replay(in, trace, lookups, n_lookups, per_lookup, missing_masks, list, cap, out); });
 }
 
 int starkhip_lookup_timings(void* ctx, float ms[4]) {

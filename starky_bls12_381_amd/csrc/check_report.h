@@ -26,6 +26,22 @@ inline bool log2_rows(size_t n_rows, unsigned* log_n) {
 // input that is not canonical.  *log_n = log2(n_rows).
 int check_trace_shape(const AirInfo& air, size_t n_rows, const uint64_t* pis, unsigned* log_n);
 
+// The rows of a mask of W words as list entries, in ascending row order: an entry is the n_lead words of `lead`, then the row, and goes
+// to list[(n_lead + 1) * *listed] while *listed < cap.  Returns the popcount of the whole mask, listed or not.
+inline uint64_t mask_to_list(const uint64_t* mask, size_t W, const uint64_t* lead, size_t n_lead, uint64_t* list, size_t cap, uint64_t* listed) {
+    uint64_t bits = 0;
+    for (size_t w = 0; w < W; w++) {
+        uint64_t word = mask[w];
+        bits += (uint64_t)__builtin_popcountll(word);
+        for (; word && *listed < cap; word &= word - 1) {
+            uint64_t* e = list + (n_lead + 1) * (*listed)++;
+            for (size_t i = 0; i < n_lead; i++) e[i] = lead[i];
+            e[n_lead] = w * 64 + (size_t)__builtin_ctzll(word);
+        }
+    }
+    return bits;
+}
+
 struct CheckPasses {
     virtual ~CheckPasses() {}
     // counts[k] (zeroed, n_constraints entries) = rows on which constraint k is violated; mask (zeroed, (n + 63) / 64 words) = those rows

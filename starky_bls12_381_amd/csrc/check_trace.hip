@@ -1,22 +1,18 @@
-// Host halves of the trace checkers: starkhip_check_trace, starkhip_check_trace_report (under check_report.h; kernels_check.hip) and
+// Host halves of the trace checkers: starkhip_check_trace, starkhip_check_trace_report (under check_report.h; kernels_check.hip),
 // starkhip_check_trace_free_cell_classes with starkhip_check_trace_free_cells, one run and a projection of it (free_cells.h;
-// kernels_free_classes.hip), the check prove() runs on its own copy of the trace ("check_trace": check_trace_in_prove), and the check
-// of the permutation pairs, starkhip_check_trace_permutations (under permutation_check.h; kernels_multiset.hip).  What the
-// stand-alone ones share is check_trace_prepare: the shape checks, the cached op stream of the AIR (check_program, Ctx::CheckProgram),
-// the trace and the public inputs on the device -- the CheckView the kernels read.
+// kernels_free_classes.hip), and the check prove() runs on its own copy of the trace ("check_trace": check_trace_in_prove).  The check
+// of the permutation pairs is not here: permutation_check.hip.  What the stand-alone ones share is check_trace_prepare: the shape
+// checks, the cached op stream of the AIR (check_program, Ctx::CheckProgram), the trace and the public inputs on the device -- the
+// CheckView the kernels read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
 #include "air_validate.h"
 #include "check_report.h"
 #include "ctx.h"
 #include "free_cells.h"
-#include "kernels_multiset.h"
-#include "permutation.h"
-#include "permutation_check.h"
 #include "quotient_ops.h"
 
 namespace starkhip {
@@ -270,92 +266,5 @@ int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, con
     *out = free_cells_from_classes(counts.data(), in.n_rows, air.prog.n_cols, per_column, free_mask);
     return STARKHIP_OK;
 }
-
-// starkhip_check_trace_permutations: one pair under one seed as the device steps of kernels_multiset.hip -- keys, sort, classification
-// and the masks' popcounts -- under the host half of permutation_check.h.  The pair columns are gathered where permutation_zs() and
-// prove() keep them (perm.cols, by perm_columns()); c->mset holds one pair's buffers.
-namespace {
-struct DevicePermSteps : PermCheckSteps {
-    Ctx* c;
-    size_t n, W;
-    std::vector<uint32_t> pair_at;  // where each pair starts in mset.desc
-    DevicePermSteps(Ctx* c_, size_t n_) : c(c_), n(n_), W((n_ + 63) / 64) {}
-    unsigned long long* d_masks() const { return c->mset.masks.as<unsigned long long>(); }  // [2][W], then the three counters
-    int run(size_t q, gl_t seed, uint64_t counts[3]) override {
-        hipStream_t st = c->st;
-        Ctx::MultisetBufs& mb = c->mset;
-        const size_t items = 2 * n;
-        gl_t* keys = mb.keys.as<gl_t>();
-        uint32_t* idx = mb.idx.as<uint32_t>();
-        uint32_t* table = mb.table.as<uint32_t>();
-        const uint32_t* pair = mb.desc.as<uint32_t>() + pair_at[q];
-        const gl_t* cols = c->perm.cols.as<gl_t>();
-        HIPCHK(hipMemsetAsync(d_masks(), 0, (2 * W + 3) * 8, st));
-        HIPCHK(hipEventRecord(c->kev[2], st));
-        HIPCHK(launch_multiset_keys(pair, cols, n, n, seed, keys, idx, st));
-        HIPCHK(launch_multiset_sort(keys, idx, keys + items, idx + items, items, table, table + multiset_table_words(items), st));
-        HIPCHK(hipEventRecord(c->kev[3], st));
-        HIPCHK(launch_multiset_classify(pair, cols, n, n, keys, idx, d_masks(), d_masks() + 2 * W, st));
-        HIPCHK(launch_multiset_count(d_masks(), n, d_masks() + 2 * W, st));
-        HIPCHK(hipEventRecord(c->kev[4], st));
-        unsigned long long res[3] = {0, 0, 0};
-        HIPCHK(read_back(c, res, d_masks() + 2 * W, sizeof res, st));
-        HIPCHK(stream_wait(c));
-        float sort_ms = 0, classify_ms = 0;
-        HIPCHK(hipEventElapsedTime(&sort_ms, c->kev[2], c->kev[3]));
-        HIPCHK(hipEventElapsedTime(&classify_ms, c->kev[3], c->kev[4]));
-        mb.ms[1] += sort_ms;
-        mb.ms[2] += classify_ms;
-        for (int i = 0; i < 3; i++) counts[i] = res[i];
-        return STARKHIP_OK;
-    }
-    int masks(uint64_t* out) override {
-        const auto t0 = std::chrono::steady_clock::now();
-        HIPCHK(hipMemcpyAsync(out, d_masks(), 2 * W * 8, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(stream_wait(c));
-        c->mset.ms[3] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return STARKHIP_OK;
-    }
-};
-}  // namespace
-
-int check_trace_permutations(Ctx* c, const AirInfo& air, const TraceInput& in, uint64_t seed, uint32_t* per_pair, uint64_t* masks, uint64_t* list,
-                             size_t cap, starkhip_perm_check_t* out) {
-    const AirProgram& P = air.prog;
-    const size_t n = in.n_rows, C = P.n_cols, items = 2 * n;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->st;
-    const std::vector<uint32_t> cols = perm_columns(P);
-    DevicePermSteps steps(c, n);
-    std::vector<uint32_t> desc;  // per pair: n_entries, then n_entries x (lhs, rhs) as indices into `cols`
-    for (const auto& pr : P.perm_pairs) {
-        steps.pair_at.push_back((uint32_t)desc.size());
-        desc.push_back((uint32_t)pr.size());
-        for (uint64_t e : pr)
-            for (uint32_t col : {(uint32_t)e, (uint32_t)(e >> 32)}) desc.push_back((uint32_t)(std::lower_bound(cols.begin(), cols.end(), col) - cols.begin()));
-    }
-    Ctx::MultisetBufs& mb = c->mset;
-    if (!in.callers_columns()) HIPCHK(c->values.ensure(C * n * 8));
-    if (in.park_words(C)) HIPCHK(c->lde.ensure(in.park_words(C) * 8));  // the staging of row-major host rows
-    HIPCHK(c->perm.cols.ensure(cols.size() * n * 8));
-    HIPCHK(mb.desc.ensure(desc.size() * 4));
-    HIPCHK(mb.keys.ensure(2 * items * 8));
-    HIPCHK(mb.idx.ensure(2 * items * 4));
-    HIPCHK(mb.table.ensure((multiset_table_words(items) + multiset_scan_chunks(items)) * 4));
-    HIPCHK(mb.masks.ensure((2 * steps.W + 3) * 8));
-    std::fill(mb.ms, mb.ms + 4, 0.f);
-    HIPCHK(hipEventRecord(c->kev[0], st));
-    const gl_t* d_values = nullptr;
-    if (int rc = upload_dense(c, in, c->values.as<gl_t>(), &d_values)) return rc;
-    for (size_t k = 0; k < cols.size(); k++)
-        HIPCHK(hipMemcpyAsync(c->perm.cols.as<gl_t>() + k * n, d_values + (size_t)cols[k] * n, n * 8, hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(mb.desc.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(c->kev[1], st));
-    HIPCHK(stream_wait(c));  // (`desc` may go out of scope on any return below)
-    HIPCHK(hipEventElapsedTime(&mb.ms[0], c->kev[0], c->kev[1]));
-    return perm_check_run(P, n, steps, seed, per_pair, masks, list, cap, out);
-}
-
-void perm_check_timings(Ctx* c, float ms[4]) { std::copy(c->mset.ms, c->mset.ms + 4, ms); }
 
 }  // namespace starkhip

@@ -1,7 +1,7 @@
 // The prover context and what the host files around it share: Ctx and its device buffers (DevBuf), the error macro of every HIP call
 // (HIPCHK), and the declarations of ctx.hip -- the sleeping wait and the read-back arena, the per-shape table cache, the per-AIR plan and
 // op-stream program caches, the transform dispatch and the uploads that proof, trace checkers and test entries have in common.
-// Internal to the .hip files that define prover.h's functions (ctx.hip, prover.hip, check_trace.hip, lookup_columns.hip, kernel_entries.hip): prover.h stays
+// Internal to the .hip files that define prover.h's functions (ctx.hip, prover.hip, check_trace.hip, permutation_check.hip, lookup_columns.hip, kernel_entries.hip): prover.h stays
 // the opaque interface for capi.cpp, the pools and the verifier.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -209,19 +209,21 @@ struct Ctx {
         DevBuf cols, desc, chal, zvals, zcoef, zlde, zdigests, scan, open_z, open_zn;
         std::vector<DevBuf*> bufs() { return {&cols, &desc, &chal, &zvals, &zcoef, &zlde, &zdigests, &scan, &open_z, &open_zn}; }
     } perm;
-    // starkhip_check_trace_permutations (check_trace.hip over kernels_multiset.hip), sized for ONE pair and grown like the ones above:
-    // the pairs' columns as indices into perm.cols, the two (key, idx) buffers of the sort (48 MB at 2^20 rows), the digit table with
-    // its chunk sums, the two masks followed by the counters.  ms: the last call's timings (starkhip_perm_check_timings).
+    // The sorted items of ONE set and what starkhip_check_trace_permutations keeps beside them (permutation_check.hip), grown like the ones
+    // above.  keys, idx, table: the two (key, idx) buffers of the sort (48 MB at 2^20 rows) and the digit table with its chunk sums --
+    // sized, split and filled by sorted_items_reserve / sorted_items_run (ctx.hip) alone, for the permutation check and the lookups
+    // alike.  desc: the pairs' columns as indices into perm.cols; masks: the two masks followed by the counters.  ms: the last call's
+    // timings (starkhip_perm_check_timings).
     struct MultisetBufs {
         DevBuf desc, keys, idx, table, masks;
         float ms[4] = {0, 0, 0, 0};
         std::vector<DevBuf*> bufs() { return {&desc, &keys, &idx, &table, &masks}; }
     } mset;
-    // starkhip_lookup_columns (lookup_columns.hip over kernels_multiset.hip and kernels_lookup.hip), sized for ONE lookup and grown like
-    // the ones above; keys, idx and the digit table are mset's.  desc: per lookup {1, input, table}, then {1, 0, 1} for staged columns;
-    // cols: the staging of a trace that is not column-major device memory, [4][n] -- input, table, then the two output columns of a
-    // host trace; flags: what each sorted position is; sums: the tile counts [3][tiles]; slot: the non-heads' ranks; mask: the missing
-    // rows of the lookup followed by their count.  ms: the last call's timings (starkhip_lookup_timings).
+    // starkhip_lookup_columns (lookup_columns.hip over kernels_lookup.hip), sized for ONE lookup and grown like the ones above: what the
+    // placement needs beside the sorted items, which are mset's (sorted_items_run).  desc: per lookup {1, input, table}, then {1, 0, 1}
+    // for staged columns; cols: the staging of a trace that is not column-major device memory, [4][n] -- input, table, then the two
+    // output columns of a host trace; flags: what each sorted position is; sums: the tile counts [3][tiles]; slot: the non-heads'
+    // ranks; mask: the missing rows of the lookup followed by their count.  ms: the last call's timings (starkhip_lookup_timings).
     struct LookupBufs {
         DevBuf desc, cols, flags, sums, slot, mask;
         float ms[4] = {0, 0, 0, 0};
@@ -254,6 +256,9 @@ LeafPrefix leaf_prefix(const Ctx* c);
 int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, unsigned log_len, bool inverse, const gl_t* pre_scale,
             const gl_t* post_scale);
 int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values);
+// the sorted (key, idx) items of one set of 2 n items in c->mset: room for them, then keys and the stable sort on the context's stream
+int sorted_items_reserve(Ctx* c, size_t items);
+int sorted_items_run(Ctx* c, const uint32_t* desc, const gl_t* cols, size_t stride, size_t n, gl_t seed, const gl_t** keys, const uint32_t** idx);
 // ---- check_trace.hip
 int check_trace_in_prove(Ctx* c, const AirInfo& air, const gl_t* d_trace, size_t n_rows, const uint64_t* pis, uint64_t** blob, size_t* words);
 // ---- ctx.hip

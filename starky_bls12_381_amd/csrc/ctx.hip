@@ -14,6 +14,7 @@
 
 #include "blob_arena.h"
 #include "ctx.h"
+#include "kernels_multiset.h"
 #include "quotient_ops.h"
 #include "quotient_plan.h"
 #include "verifier.h"
@@ -482,6 +483,26 @@ int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values)
         HIPCHK(hipMemcpyAsync(c->lde.p, in.words, C * n * 8, hipMemcpyHostToDevice, c->st));
         HIPCHK(launch_transpose(c->lde.as<gl_t>(), dst, n, C, c->st));
     }
+    return 0;
+}
+
+// The sorted (key, idx) items of ONE set on the context (c->mset.keys / idx / table; kernels_multiset.h has the kernels).  reserve: room
+// for a set of `items`: each of keys and idx is the sort's two buffers, the digit table is followed by its chunk sums.  run: the keys of
+// the 2 n items of `desc` over `cols` under `seed` (launch_multiset_keys) and their stable sort, enqueued on the context's stream; *keys
+// and *idx are where the sorted items lie.
+int sorted_items_reserve(Ctx* c, size_t items) {
+    HIPCHK(c->mset.keys.ensure(2 * items * 8));
+    HIPCHK(c->mset.idx.ensure(2 * items * 4));
+    HIPCHK(c->mset.table.ensure((multiset_table_words(items) + multiset_scan_chunks(items)) * 4));
+    return 0;
+}
+int sorted_items_run(Ctx* c, const uint32_t* desc, const gl_t* cols, size_t stride, size_t n, gl_t seed, const gl_t** keys, const uint32_t** idx) {
+    const size_t items = 2 * n;
+    gl_t* k = c->mset.keys.as<gl_t>();
+    uint32_t *i = c->mset.idx.as<uint32_t>(), *table = c->mset.table.as<uint32_t>();
+    HIPCHK(launch_multiset_keys(desc, cols, stride, n, seed, k, i, c->st));
+    HIPCHK(launch_multiset_sort(k, i, k + items, i + items, items, table, table + multiset_table_words(items), c->st));
+    *keys = k, *idx = i;
     return 0;
 }
 

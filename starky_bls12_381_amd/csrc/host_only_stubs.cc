@@ -138,7 +138,7 @@ int check_trace_permutations(Ctx*, const AirInfo&, const TraceInput&, uint64_t, 
     return STARKHIP_ERR_NO_DEVICE;
 }
 void perm_check_timings(Ctx*, float ms[4]) { ms[0] = ms[1] = ms[2] = ms[3] = 0; }
-int lookup_columns(Ctx*, const LookupTrace&, const starkhip_lookup_t*, size_t, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_lookup_report_t*) {
+int lookup_columns(Ctx*, const TraceInput&, uint64_t*, const starkhip_lookup_t*, size_t, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_lookup_report_t*) {
     return STARKHIP_ERR_NO_DEVICE;
 }
 void lookup_timings(Ctx*, float ms[4]) { ms[0] = ms[1] = ms[2] = ms[3] = 0; }

@@ -32,6 +32,9 @@ struct VQLeaf;
 
 namespace starkhip {
 
+// workgroups of `bs` lanes that cover n items, one lane each: what the launchers size a grid with
+inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
+
 // kernels_ntt.hip
 hipError_t launch_fill_powers(gl_t* out, gl_t base, gl_t mult, size_t count, hipStream_t st);  // out[i] = base * mult^i
 hipError_t launch_fill_coset_scale(gl_t* out, unsigned log_n, unsigned rate_bits, hipStream_t st);

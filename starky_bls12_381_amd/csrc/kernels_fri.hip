@@ -182,8 +182,6 @@ __global__ void fri_fold_kernel(const gl_t* __restrict__ in, size_t len, unsigne
     out[olen + k] = acc.a1;
 }
 
-static inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-
 hipError_t launch_ext_powers(gl2_t* out, gl2_t base, size_t count, hipStream_t st) {
     hipLaunchKernelGGL(ext_powers_kernel, dim3(nb(count, 256)), dim3(256), 0, st, out, base, count);
     return hipGetLastError();

@@ -5,13 +5,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_scan.h"
 #include "gl.h"
 
 namespace starkhip {
 
-// sorted positions one workgroup marks, counts and places: LOOKUP_TILE / 64 wave-sized slots, four per wave
-static const unsigned LOOKUP_TILE = 1024;
-inline size_t lookup_tiles(size_t items) { return (items + LOOKUP_TILE - 1) / LOOKUP_TILE; }
+// sorted positions one workgroup marks, counts and places: the tile of block_scan.h
+static const unsigned LOOKUP_TILE = TILE_ITEMS;
+inline size_t lookup_tiles(size_t items) { return tile_count(items); }
 inline size_t lookup_sum_words(size_t items) { return 3 * lookup_tiles(items); }  // uint32 [3][tiles]: inputs, non-head inputs, unused table items
 
 // out [2][n] = columns col_input and col_table of the row-major trace [n][n_cols]

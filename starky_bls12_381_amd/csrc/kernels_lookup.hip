@@ -5,12 +5,12 @@
 //
 //  * lookup_mark_kernel: one lane per position.  An INPUT item (idx < n) is a HEAD when it starts its run; a table item is USED when
 //    its predecessor is an input item of its run -- the first table item of a run that has inputs; an input item is MISSING when the
-//    last item of its run, found by binary search for the run's end, is an input item too: the run holds no table item.  The flags
-//    kept per position are the three things the placement counts -- input, non-head input, unused table item -- and each workgroup
-//    leaves the totals of its tile of LOOKUP_TILE positions in sums[count][tile].  Missing rows go into the mask through 64-bit
-//    atomicOr and into one counter: both independent of the order of arrival.
+//    last item of its run, found by binary search for the run's end (sorted_run_end), is an input item too: the run holds no table
+//    item.  The flags kept per position are the three things the placement counts -- input, non-head input, unused table item -- and
+//    each workgroup leaves the totals of its tile of LOOKUP_TILE positions (the sort's tile: block_scan.h) in sums[count][tile].
+//    Missing rows go into the mask through 64-bit atomicOr and into one counter: both independent of the order of arrival.
 //  * lookup_scan_kernel: the exclusive prefix sums of the three rows of tile totals, one workgroup per row walking its row in pieces
-//    of LK_BLOCK with a carry: any number of tiles.
+//    of TILE_BLOCK with a carry: any number of tiles.
 //  * lookup_place_inputs_kernel, lookup_place_table_kernel: a position's rank among the inputs, the non-head inputs or the unused
 //    table items = the scanned total of the tiles before its own + the counts of the earlier slots of its tile (LDS) + the lower
 //    lanes of its slot (a __ballot and a popcount).  The inputs in sorted order ARE permuted_input, so an input item writes its key
@@ -21,25 +21,25 @@
 // is given.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "kernels.h"
 #include "kernels_lookup.h"
 
 namespace starkhip {
 
-static const unsigned LK_BLOCK = 256, LK_WAVES = LK_BLOCK / 64, LK_SLOTS = LOOKUP_TILE / 64, LK_ROUNDS = LK_SLOTS / LK_WAVES;
 enum : uint32_t { LK_INPUT = 1, LK_NONHEAD = 2, LK_UNUSED = 4 };  // the flags of a position: bit c = it counts towards sums[c]
 
 struct LkCounts { uint32_t c[3]; };
 
-// The flags f[r] of this lane's LK_ROUNDS positions -- position base + slot * 64 + lane with slot = r * LK_WAVES + wave, 0 for a
+// The flags f[r] of this lane's TILE_ROUNDS positions -- position base + slot * 64 + lane with slot = tile_slot(r, wave), 0 for a
 // position past the items -- give before[r] = how many positions of the tile BEFORE that one carry each flag, and the tile's totals.
-// cnt: [3][LK_SLOTS] words of LDS.  Every lane of the workgroup calls it.
-__device__ __forceinline__ void lk_tile_ranks(const uint32_t f[LK_ROUNDS], uint32_t (*cnt)[LK_SLOTS], LkCounts before[LK_ROUNDS], LkCounts* total) {
+// cnt: [3][TILE_SLOTS] words of LDS.  Every lane of the workgroup calls it.
+__device__ __forceinline__ void lk_tile_ranks(const uint32_t f[TILE_ROUNDS], uint32_t (*cnt)[TILE_SLOTS], LkCounts before[TILE_ROUNDS], LkCounts* total) {
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const unsigned long long lower = (1ull << lane) - 1;
 #pragma unroll
-    for (unsigned r = 0; r < LK_ROUNDS; r++) {
-        const unsigned slot = r * LK_WAVES + w;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const unsigned slot = tile_slot(r, w);
 #pragma unroll
         for (unsigned c = 0; c < 3; c++) {
             const unsigned long long m = __ballot((f[r] >> c) & 1u);
@@ -52,59 +52,36 @@ __device__ __forceinline__ void lk_tile_ranks(const uint32_t f[LK_ROUNDS], uint3
     for (unsigned c = 0; c < 3; c++) {
         uint32_t run = 0;
 #pragma unroll
-        for (unsigned s = 0; s < LK_SLOTS; s++) {
+        for (unsigned s = 0; s < TILE_SLOTS; s++) {
             const uint32_t v = cnt[c][s];
 #pragma unroll
-            for (unsigned r = 0; r < LK_ROUNDS; r++)
-                if (s < r * LK_WAVES + w) before[r].c[c] += v;
+            for (unsigned r = 0; r < TILE_ROUNDS; r++)
+                if (s < tile_slot(r, w)) before[r].c[c] += v;
             run += v;
         }
         total->c[c] = run;
     }
 }
 
-// exclusive prefix sum of v over the workgroup's LK_BLOCK lanes, and the sum of all of them.  lds: LK_WAVES words
-__device__ __forceinline__ uint32_t lk_block_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (unsigned d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (unsigned k = 0; k < LK_WAVES; k++) {
-        const uint32_t t = lds[k];
-        if (k < w) before += t;
-        all += t;
-    }
-    __syncthreads();  // lds is free for the next call
-    *total = all;
-    return before + incl - v;
-}
-
-__global__ __launch_bounds__(LK_BLOCK) void lookup_gather_kernel(const gl_t* __restrict__ trace, size_t n_cols, uint32_t n, uint32_t col_input, uint32_t col_table,
-                                                                 gl_t* __restrict__ out) { STARKHIP_PRIO_ENTRY
-    const uint32_t i = blockIdx.x * LK_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(TILE_BLOCK) void lookup_gather_kernel(const gl_t* __restrict__ trace, size_t n_cols, uint32_t n, uint32_t col_input, uint32_t col_table,
+                                                                   gl_t* __restrict__ out) { STARKHIP_PRIO_ENTRY
+    const uint32_t i = blockIdx.x * TILE_BLOCK + threadIdx.x;
     if (i >= 2 * n) return;
     const uint32_t side = i >= n, row = i - side * n;
     out[i] = trace[(size_t)row * n_cols + (side ? col_table : col_input)];
 }
 
 // grid: tiles
-__global__ __launch_bounds__(LK_BLOCK) void lookup_mark_kernel(const gl_t* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t n, uint8_t* __restrict__ flags,
-                                                               uint32_t* __restrict__ sums, uint32_t tiles, unsigned long long* __restrict__ mask,
-                                                               unsigned long long* __restrict__ missing) { STARKHIP_PRIO_ENTRY
-    __shared__ uint32_t cnt[3][LK_SLOTS];
+__global__ __launch_bounds__(TILE_BLOCK) void lookup_mark_kernel(const gl_t* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t n, uint8_t* __restrict__ flags,
+                                                                 uint32_t* __restrict__ sums, uint32_t tiles, unsigned long long* __restrict__ mask,
+                                                                 unsigned long long* __restrict__ missing) { STARKHIP_PRIO_ENTRY
+    __shared__ uint32_t cnt[3][TILE_SLOTS];
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t items = 2 * n, base = blockIdx.x * LOOKUP_TILE;
-    uint32_t f[LK_ROUNDS];
+    uint32_t f[TILE_ROUNDS];
 #pragma unroll
-    for (unsigned r = 0; r < LK_ROUNDS; r++) {
-        const uint32_t j = base + (r * LK_WAVES + w) * 64 + lane;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const uint32_t j = base + tile_slot(r, w) * 64 + lane;
         f[r] = 0;
         bool miss = false;
         uint32_t row = 0;
@@ -114,13 +91,7 @@ __global__ __launch_bounds__(LK_BLOCK) void lookup_mark_kernel(const gl_t* __res
             const bool input = id < n, same = j > 0 && keys[j - 1] == k;  // continues the run of its predecessor
             if (input) {
                 f[r] = same ? LK_INPUT | LK_NONHEAD : LK_INPUT;
-                uint32_t lo = j + 1, hi = items;  // the run's end: the first position whose key is > k
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (keys[mid] <= k) lo = mid + 1;
-                    else hi = mid;
-                }
-                miss = idx[lo - 1] < n;  // the run's last item is an input item: inputs come first, so it holds no table item
+                miss = idx[sorted_run_end(keys, k, j, items) - 1] < n;  // the run's last item is an input item: inputs come first, so it holds no table item
                 row = id;
             } else if (!(same && idx[j - 1] < n)) f[r] = LK_UNUSED;
             flags[j] = (uint8_t)f[r];
@@ -129,45 +100,45 @@ __global__ __launch_bounds__(LK_BLOCK) void lookup_mark_kernel(const gl_t* __res
         const unsigned long long hit = __ballot(miss);
         if (lane == 0 && hit) atomicAdd(missing, (unsigned long long)__popcll(hit));  // a count: the order of the adds does not matter
     }
-    LkCounts before[LK_ROUNDS], total;
+    LkCounts before[TILE_ROUNDS], total;
     lk_tile_ranks(f, cnt, before, &total);
     if (threadIdx.x < 3) sums[(size_t)threadIdx.x * tiles + blockIdx.x] = threadIdx.x == 0 ? total.c[0] : threadIdx.x == 1 ? total.c[1] : total.c[2];
 }
 
 // grid: 3, one workgroup per row of sums
-__global__ __launch_bounds__(LK_BLOCK) void lookup_scan_kernel(uint32_t* __restrict__ sums, uint32_t tiles) { STARKHIP_PRIO_ENTRY
-    __shared__ uint32_t lds[LK_WAVES];
+__global__ __launch_bounds__(TILE_BLOCK) void lookup_scan_kernel(uint32_t* __restrict__ sums, uint32_t tiles) { STARKHIP_PRIO_ENTRY
+    __shared__ uint32_t lds[TILE_WAVES];
     uint32_t* row = sums + (size_t)blockIdx.x * tiles;
     uint32_t carry = 0;
-    for (uint32_t at = 0; at < tiles; at += LK_BLOCK) {  // the same trip count on every lane
+    for (uint32_t at = 0; at < tiles; at += TILE_BLOCK) {  // the same trip count on every lane
         const uint32_t j = at + threadIdx.x;
         const uint32_t v = j < tiles ? row[j] : 0u;
         uint32_t total;
-        const uint32_t excl = lk_block_scan(v, lds, &total);
+        const uint32_t excl = block_scan(v, ScanAdd(), 0u, lds, &total);
         if (j < tiles) row[j] = carry + excl;
         carry += total;
     }
 }
 
 // sums: scanned.  grid: tiles
-__global__ __launch_bounds__(LK_BLOCK) void lookup_place_inputs_kernel(const gl_t* __restrict__ keys, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sums,
-                                                                       uint32_t tiles, uint32_t n, gl_t* permuted_input, gl_t* permuted_table, size_t stride,
-                                                                       uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
-    __shared__ uint32_t cnt[3][LK_SLOTS];
+__global__ __launch_bounds__(TILE_BLOCK) void lookup_place_inputs_kernel(const gl_t* __restrict__ keys, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sums,
+                                                                         uint32_t tiles, uint32_t n, gl_t* permuted_input, gl_t* permuted_table, size_t stride,
+                                                                         uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
+    __shared__ uint32_t cnt[3][TILE_SLOTS];
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t items = 2 * n, base = blockIdx.x * LOOKUP_TILE;
-    uint32_t f[LK_ROUNDS];
+    uint32_t f[TILE_ROUNDS];
 #pragma unroll
-    for (unsigned r = 0; r < LK_ROUNDS; r++) {
-        const uint32_t j = base + (r * LK_WAVES + w) * 64 + lane;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const uint32_t j = base + tile_slot(r, w) * 64 + lane;
         f[r] = j < items ? flags[j] : 0u;
     }
-    LkCounts before[LK_ROUNDS], total;
+    LkCounts before[TILE_ROUNDS], total;
     lk_tile_ranks(f, cnt, before, &total);
     const uint32_t inputs0 = sums[blockIdx.x], nonheads0 = sums[(size_t)tiles + blockIdx.x];
 #pragma unroll
-    for (unsigned r = 0; r < LK_ROUNDS; r++) {
-        const uint32_t j = base + (r * LK_WAVES + w) * 64 + lane;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const uint32_t j = base + tile_slot(r, w) * 64 + lane;
         if (!(f[r] & LK_INPUT)) continue;  // (a position past the items has no flag)
         const uint32_t rank = inputs0 + before[r].c[0];
         if (rank >= n) continue;
@@ -182,24 +153,24 @@ __global__ __launch_bounds__(LK_BLOCK) void lookup_place_inputs_kernel(const gl_
 }
 
 // sums: scanned; slot: as lookup_place_inputs_kernel left it.  grid: tiles
-__global__ __launch_bounds__(LK_BLOCK) void lookup_place_table_kernel(const gl_t* __restrict__ keys, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sums,
-                                                                      uint32_t tiles, uint32_t n, gl_t* permuted_table, size_t stride,
-                                                                      const uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
-    __shared__ uint32_t cnt[3][LK_SLOTS];
+__global__ __launch_bounds__(TILE_BLOCK) void lookup_place_table_kernel(const gl_t* __restrict__ keys, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sums,
+                                                                        uint32_t tiles, uint32_t n, gl_t* permuted_table, size_t stride,
+                                                                        const uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
+    __shared__ uint32_t cnt[3][TILE_SLOTS];
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t items = 2 * n, base = blockIdx.x * LOOKUP_TILE;
-    uint32_t f[LK_ROUNDS];
+    uint32_t f[TILE_ROUNDS];
 #pragma unroll
-    for (unsigned r = 0; r < LK_ROUNDS; r++) {
-        const uint32_t j = base + (r * LK_WAVES + w) * 64 + lane;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const uint32_t j = base + tile_slot(r, w) * 64 + lane;
         f[r] = j < items ? flags[j] : 0u;
     }
-    LkCounts before[LK_ROUNDS], total;
+    LkCounts before[TILE_ROUNDS], total;
     lk_tile_ranks(f, cnt, before, &total);
     const uint32_t unused0 = sums[2 * (size_t)tiles + blockIdx.x];
 #pragma unroll
-    for (unsigned r = 0; r < LK_ROUNDS; r++) {
-        const uint32_t j = base + (r * LK_WAVES + w) * 64 + lane;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const uint32_t j = base + tile_slot(r, w) * 64 + lane;
         if (!(f[r] & LK_UNUSED)) continue;
         const uint32_t un = unused0 + before[r].c[2];
         if (un >= n) continue;
@@ -208,29 +179,27 @@ __global__ __launch_bounds__(LK_BLOCK) void lookup_place_table_kernel(const gl_t
     }
 }
 
-static inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-
 hipError_t launch_lookup_gather(const gl_t* trace, size_t n_cols, size_t n, uint32_t col_input, uint32_t col_table, gl_t* out, hipStream_t st) {
-    hipLaunchKernelGGL(lookup_gather_kernel, dim3(nb(2 * n, LK_BLOCK)), dim3(LK_BLOCK), 0, st, trace, n_cols, (uint32_t)n, col_input, col_table, out);
+    hipLaunchKernelGGL(lookup_gather_kernel, dim3(nb(2 * n, TILE_BLOCK)), dim3(TILE_BLOCK), 0, st, trace, n_cols, (uint32_t)n, col_input, col_table, out);
     return hipGetLastError();
 }
 
 hipError_t launch_lookup_mark(const gl_t* keys, const uint32_t* idx, size_t n, uint8_t* flags, uint32_t* sums, unsigned long long* mask,
                               unsigned long long* missing, hipStream_t st) {
     const uint32_t tiles = (uint32_t)lookup_tiles(2 * n);
-    hipLaunchKernelGGL(lookup_mark_kernel, dim3(tiles), dim3(LK_BLOCK), 0, st, keys, idx, (uint32_t)n, flags, sums, tiles, mask, missing);
+    hipLaunchKernelGGL(lookup_mark_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, idx, (uint32_t)n, flags, sums, tiles, mask, missing);
     return hipGetLastError();
 }
 
 hipError_t launch_lookup_scan(uint32_t* sums, size_t n, hipStream_t st) {
-    hipLaunchKernelGGL(lookup_scan_kernel, dim3(3), dim3(LK_BLOCK), 0, st, sums, (uint32_t)lookup_tiles(2 * n));
+    hipLaunchKernelGGL(lookup_scan_kernel, dim3(3), dim3(TILE_BLOCK), 0, st, sums, (uint32_t)lookup_tiles(2 * n));
     return hipGetLastError();
 }
 
 hipError_t launch_lookup_place_inputs(const gl_t* keys, const uint8_t* flags, const uint32_t* sums, size_t n, gl_t* permuted_input, gl_t* permuted_table,
                                       size_t stride, uint32_t* slot, hipStream_t st) {
     const uint32_t tiles = (uint32_t)lookup_tiles(2 * n);
-    hipLaunchKernelGGL(lookup_place_inputs_kernel, dim3(tiles), dim3(LK_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, permuted_input, permuted_table, stride,
+    hipLaunchKernelGGL(lookup_place_inputs_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, permuted_input, permuted_table, stride,
                        slot);
     return hipGetLastError();
 }
@@ -238,7 +207,7 @@ hipError_t launch_lookup_place_inputs(const gl_t* keys, const uint8_t* flags, co
 hipError_t launch_lookup_place_table(const gl_t* keys, const uint8_t* flags, const uint32_t* sums, size_t n, gl_t* permuted_table, size_t stride,
                                      const uint32_t* slot, hipStream_t st) {
     const uint32_t tiles = (uint32_t)lookup_tiles(2 * n);
-    hipLaunchKernelGGL(lookup_place_table_kernel, dim3(tiles), dim3(LK_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, permuted_table, stride, slot);
+    hipLaunchKernelGGL(lookup_place_table_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, permuted_table, stride, slot);
     return hipGetLastError();
 }
 

@@ -1,18 +1,19 @@
 // Launchers of kernels_multiset.hip: the multiset comparison behind starkhip_check_trace_permutations (permutation_check.h has the
-// rule).  All launches are asynchronous on `st`.
+// rule).  Host code reaches keys and sort through sorted_items_run (ctx.hip), which owns their buffers.  All launches are asynchronous on `st`.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_scan.h"
 #include "gl.h"
 
 namespace starkhip {
 
-// items one workgroup of the sort handles in a pass: MULTISET_TILE / 64 wave-sized slots, four per wave
-static const unsigned MULTISET_TILE = 1024;
+// items one workgroup of the sort handles in a pass: the tile of block_scan.h
+static const unsigned MULTISET_TILE = TILE_ITEMS;
 // words of the digit table one workgroup of its scan handles
 static const unsigned MULTISET_SCAN_CHUNK = 4096;
-inline size_t multiset_tiles(size_t items) { return (items + MULTISET_TILE - 1) / MULTISET_TILE; }
+inline size_t multiset_tiles(size_t items) { return tile_count(items); }
 inline size_t multiset_table_words(size_t items) { return 256 * multiset_tiles(items); }                                       // uint32 [256][tiles]
 inline size_t multiset_scan_chunks(size_t items) { return (multiset_table_words(items) + MULTISET_SCAN_CHUNK - 1) / MULTISET_SCAN_CHUNK; }
 

@@ -6,7 +6,7 @@
 //    starts from is therefore: all lhs rows ascending, then all rhs rows ascending.
 //  * a STABLE least-significant-digit radix sort of (key, idx) by key: 8-bit digits, eight passes between two buffers, each pass four
 //    launches on the caller's stream.  A workgroup owns a tile of MULTISET_TILE consecutive items as 16 slots of 64, slot s of wave
-//    s & 3 in its round s >> 2.
+//    s & 3 in its round s >> 2: the tile of block_scan.h, which also has the workgroup scan the table scan is made of.
 //      - multiset_histogram_kernel: the tile's digit counts through LDS counters into table[digit][tile];
 //      - multiset_scan_sums_kernel + multiset_scan_apply_kernel: the exclusive scan of the table in digit-major order -- the sum of
 //        each chunk of MULTISET_SCAN_CHUNK words, then every chunk scanned in place from the sum of the chunks before it (a table
@@ -17,7 +17,7 @@
 //        item in the input among those of its digit, so equal digits keep their order: the pass is stable, and so is the sort.
 //    No workgroup waits for another inside a launch, and no global atomic decides where an item lands: the destination is a function
 //    of the input order alone.
-//  * multiset_classify_kernel: one lane per sorted position.  Binary searches by key for the start and the end of the item's run, and
+//  * multiset_classify_kernel: one lane per sorted position.  Binary searches by key for the start and the end (sorted_run_end) of the item's run, and
 //    by the side bit of idx -- monotone inside a run because the sort is stable -- for the run's first rhs item; from these L, R and
 //    the item's rank on its side: it is unmatched when that rank is >= the other side's count, i.e. the |L - R| highest rows of the
 //    larger side are.  An item whose key equals its predecessor's compares its tuple with the predecessor's cell by cell mod p; a
@@ -29,14 +29,14 @@
 
 #include <utility>
 
+#include "block_scan.h"
 #include "kernels.h"
 #include "kernels_multiset.h"
 
 namespace starkhip {
 
-static const unsigned MS_BLOCK = 256, MS_WAVES = MS_BLOCK / 64, MS_SLOTS = MULTISET_TILE / 64, MS_ROUNDS = MS_SLOTS / MS_WAVES;
-static const unsigned MS_SCAN_ITEMS = MULTISET_SCAN_CHUNK / MS_BLOCK;
-static_assert(MS_BLOCK == 256, "one lane per digit in the scatter's slot scan");
+static const unsigned MS_SCAN_ITEMS = MULTISET_SCAN_CHUNK / TILE_BLOCK;
+static_assert(TILE_BLOCK == 256, "one lane per digit in the scatter's slot scan");
 
 // the lanes of the wave that are `valid` and hold the same 8-bit digit as this one
 __device__ __forceinline__ unsigned long long ms_match(unsigned d, bool valid) {
@@ -50,33 +50,10 @@ __device__ __forceinline__ unsigned long long ms_match(unsigned d, bool valid) {
     return m;
 }
 
-// exclusive prefix sum of v over the workgroup's MS_BLOCK lanes, and the sum of all of them.  lds: MS_WAVES words
-__device__ __forceinline__ uint32_t ms_block_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (unsigned d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (unsigned k = 0; k < MS_WAVES; k++) {
-        const uint32_t t = lds[k];
-        if (k < w) before += t;
-        all += t;
-    }
-    __syncthreads();  // lds is free for the next call
-    *total = all;
-    return before + incl - v;
-}
-
 // pair: n_entries, then n_entries x (lhs, rhs) columns of `cols`
-__global__ __launch_bounds__(MS_BLOCK) void multiset_keys_kernel(const uint32_t* __restrict__ pair, const gl_t* __restrict__ cols, size_t stride, uint32_t n,
-                                                                 gl_t seed, gl_t* __restrict__ keys, uint32_t* __restrict__ idx) { STARKHIP_PRIO_ENTRY
-    const uint32_t i = blockIdx.x * MS_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_keys_kernel(const uint32_t* __restrict__ pair, const gl_t* __restrict__ cols, size_t stride, uint32_t n,
+                                                                   gl_t seed, gl_t* __restrict__ keys, uint32_t* __restrict__ idx) { STARKHIP_PRIO_ENTRY
+    const uint32_t i = blockIdx.x * TILE_BLOCK + threadIdx.x;
     if (i >= 2 * n) return;
     const uint32_t side = i >= n, row = i - side * n, ne = pair[0];
     gl_t key = 0, pw = 1;
@@ -90,16 +67,16 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_keys_kernel(const uint32_t*
 }
 
 // table[digit][tile] = the tile's items of that digit.  grid: tiles
-__global__ __launch_bounds__(MS_BLOCK) void multiset_histogram_kernel(const gl_t* __restrict__ keys, uint32_t items, unsigned shift, uint32_t* __restrict__ table,
-                                                                      uint32_t tiles) { STARKHIP_PRIO_ENTRY
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_histogram_kernel(const gl_t* __restrict__ keys, uint32_t items, unsigned shift, uint32_t* __restrict__ table,
+                                                                        uint32_t tiles) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t hist[256];
     const unsigned lane = threadIdx.x & 63u;
     hist[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * MULTISET_TILE;
 #pragma unroll
-    for (unsigned r = 0; r < MS_ROUNDS; r++) {
-        const uint32_t pos = base + r * MS_BLOCK + threadIdx.x;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const uint32_t pos = base + r * TILE_BLOCK + threadIdx.x;
         const bool valid = pos < items;
         const unsigned d = valid ? (unsigned)(keys[pos] >> shift) & 255u : 0u;
         const unsigned long long m = ms_match(d, valid);
@@ -110,26 +87,26 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_histogram_kernel(const gl_t
 }
 
 // sums[chunk] = the sum of the chunk's words.  grid: chunks
-__global__ __launch_bounds__(MS_BLOCK) void multiset_scan_sums_kernel(const uint32_t* __restrict__ table, uint32_t words, uint32_t* __restrict__ sums) { STARKHIP_PRIO_ENTRY
-    __shared__ uint32_t lds[MS_WAVES];
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_scan_sums_kernel(const uint32_t* __restrict__ table, uint32_t words, uint32_t* __restrict__ sums) { STARKHIP_PRIO_ENTRY
+    __shared__ uint32_t lds[TILE_WAVES];
     const uint32_t base = blockIdx.x * MULTISET_SCAN_CHUNK;
     uint32_t s = 0;
 #pragma unroll
     for (unsigned k = 0; k < MS_SCAN_ITEMS; k++) {
-        const uint32_t j = base + k * MS_BLOCK + threadIdx.x;
+        const uint32_t j = base + k * TILE_BLOCK + threadIdx.x;
         if (j < words) s += table[j];
     }
     uint32_t total;
-    (void)ms_block_scan(s, lds, &total);
+    (void)block_scan(s, ScanAdd(), 0u, lds, &total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
 // table[j] <- the sum of table[0 .. j), chunk by chunk: each lane a run of MS_SCAN_ITEMS consecutive words.  grid: chunks
-__global__ __launch_bounds__(MS_BLOCK) void multiset_scan_apply_kernel(uint32_t* __restrict__ table, uint32_t words, const uint32_t* __restrict__ sums) { STARKHIP_PRIO_ENTRY
-    __shared__ uint32_t lds[MS_WAVES];
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_scan_apply_kernel(uint32_t* __restrict__ table, uint32_t words, const uint32_t* __restrict__ sums) { STARKHIP_PRIO_ENTRY
+    __shared__ uint32_t lds[TILE_WAVES];
     uint32_t s = 0, carry;
-    for (uint32_t j = threadIdx.x; j < blockIdx.x; j += MS_BLOCK) s += sums[j];
-    (void)ms_block_scan(s, lds, &carry);
+    for (uint32_t j = threadIdx.x; j < blockIdx.x; j += TILE_BLOCK) s += sums[j];
+    (void)block_scan(s, ScanAdd(), 0u, lds, &carry);
     const uint32_t j0 = blockIdx.x * MULTISET_SCAN_CHUNK + threadIdx.x * MS_SCAN_ITEMS;
     uint32_t v[MS_SCAN_ITEMS];
     s = 0;
@@ -139,7 +116,7 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_scan_apply_kernel(uint32_t*
         s += v[k];
     }
     uint32_t total;
-    uint32_t run = carry + ms_block_scan(s, lds, &total);
+    uint32_t run = carry + block_scan(s, ScanAdd(), 0u, lds, &total);
 #pragma unroll
     for (unsigned k = 0; k < MS_SCAN_ITEMS; k++) {
         if (j0 + k < words) table[j0 + k] = run;
@@ -148,20 +125,20 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_scan_apply_kernel(uint32_t*
 }
 
 // table: scanned.  grid: tiles
-__global__ __launch_bounds__(MS_BLOCK) void multiset_scatter_kernel(const gl_t* __restrict__ keys_in, const uint32_t* __restrict__ idx_in, gl_t* __restrict__ keys_out,
-                                                                    uint32_t* __restrict__ idx_out, uint32_t items, unsigned shift,
-                                                                    const uint32_t* __restrict__ table, uint32_t tiles) { STARKHIP_PRIO_ENTRY
-    __shared__ uint32_t cnt[MS_SLOTS][256];  // the slot's items of each digit, then where the slot's first item of the digit lands
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_scatter_kernel(const gl_t* __restrict__ keys_in, const uint32_t* __restrict__ idx_in, gl_t* __restrict__ keys_out,
+                                                                      uint32_t* __restrict__ idx_out, uint32_t items, unsigned shift,
+                                                                      const uint32_t* __restrict__ table, uint32_t tiles) { STARKHIP_PRIO_ENTRY
+    __shared__ uint32_t cnt[TILE_SLOTS][256];  // the slot's items of each digit, then where the slot's first item of the digit lands
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
 #pragma unroll
-    for (unsigned s = 0; s < MS_SLOTS; s++) cnt[s][threadIdx.x] = 0;
+    for (unsigned s = 0; s < TILE_SLOTS; s++) cnt[s][threadIdx.x] = 0;
     __syncthreads();
     const uint32_t base = blockIdx.x * MULTISET_TILE;
-    gl_t key[MS_ROUNDS];
-    uint32_t id[MS_ROUNDS], dr[MS_ROUNDS];  // digit | rank inside the slot << 8
+    gl_t key[TILE_ROUNDS];
+    uint32_t id[TILE_ROUNDS], dr[TILE_ROUNDS];  // digit | rank inside the slot << 8
 #pragma unroll
-    for (unsigned r = 0; r < MS_ROUNDS; r++) {
-        const unsigned slot = r * MS_WAVES + w;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const unsigned slot = tile_slot(r, w);
         const uint32_t pos = base + slot * 64 + lane;
         const bool valid = pos < items;
         key[r] = valid ? keys_in[pos] : 0;
@@ -176,7 +153,7 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_scatter_kernel(const gl_t* 
     {
         uint32_t run = table[(size_t)threadIdx.x * tiles + blockIdx.x];
 #pragma unroll
-        for (unsigned s = 0; s < MS_SLOTS; s++) {
+        for (unsigned s = 0; s < TILE_SLOTS; s++) {
             const uint32_t c = cnt[s][threadIdx.x];
             cnt[s][threadIdx.x] = run;
             run += c;
@@ -184,8 +161,8 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_scatter_kernel(const gl_t* 
     }
     __syncthreads();
 #pragma unroll
-    for (unsigned r = 0; r < MS_ROUNDS; r++) {
-        const unsigned slot = r * MS_WAVES + w;
+    for (unsigned r = 0; r < TILE_ROUNDS; r++) {
+        const unsigned slot = tile_slot(r, w);
         const uint32_t pos = base + slot * 64 + lane;
         const uint32_t dst = cnt[slot][dr[r] & 255u] + (dr[r] >> 8);
         if (pos < items && dst < items) {
@@ -195,10 +172,10 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_scatter_kernel(const gl_t* 
     }
 }
 
-__global__ __launch_bounds__(MS_BLOCK) void multiset_classify_kernel(const uint32_t* __restrict__ pair, const gl_t* __restrict__ cols, size_t stride, uint32_t n,
-                                                                     const gl_t* __restrict__ keys, const uint32_t* __restrict__ idx,
-                                                                     unsigned long long* __restrict__ masks, unsigned long long* __restrict__ counters) { STARKHIP_PRIO_ENTRY
-    const uint32_t items = 2 * n, j = blockIdx.x * MS_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_classify_kernel(const uint32_t* __restrict__ pair, const gl_t* __restrict__ cols, size_t stride, uint32_t n,
+                                                                       const gl_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                                       unsigned long long* __restrict__ masks, unsigned long long* __restrict__ counters) { STARKHIP_PRIO_ENTRY
+    const uint32_t items = 2 * n, j = blockIdx.x * TILE_BLOCK + threadIdx.x;
     const bool valid = j < items;
     bool collision = false;
     if (valid) {
@@ -210,13 +187,7 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_classify_kernel(const uint3
             else hi = mid;
         }
         const uint32_t a = lo;
-        lo = j + 1, hi = items;  // its end: the first position whose key is > k
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (keys[mid] <= k) lo = mid + 1;
-            else hi = mid;
-        }
-        const uint32_t b = lo;
+        const uint32_t b = sorted_run_end(keys, k, j, items);
         lo = a, hi = b;  // the run's first rhs item
         while (lo < hi) {
             const uint32_t mid = (lo + hi) >> 1;
@@ -238,9 +209,9 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_classify_kernel(const uint3
     if (collision && (hit & ((1ull << (threadIdx.x & 63u)) - 1)) == 0) atomicAdd(&counters[0], (unsigned long long)__popcll(hit));
 }
 
-__global__ __launch_bounds__(MS_BLOCK) void multiset_count_kernel(const unsigned long long* __restrict__ masks, uint32_t words_per_side,
-                                                                  unsigned long long* __restrict__ counters) { STARKHIP_PRIO_ENTRY
-    const uint32_t j = blockIdx.x * MS_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_count_kernel(const unsigned long long* __restrict__ masks, uint32_t words_per_side,
+                                                                    unsigned long long* __restrict__ counters) { STARKHIP_PRIO_ENTRY
+    const uint32_t j = blockIdx.x * TILE_BLOCK + threadIdx.x;
     const uint32_t c = j < 2 * words_per_side ? (uint32_t)__popcll(masks[j]) : 0u;
     uint32_t c0 = j < words_per_side ? c : 0u, c1 = c - c0;
 #pragma unroll
@@ -254,10 +225,8 @@ __global__ __launch_bounds__(MS_BLOCK) void multiset_count_kernel(const unsigned
     }
 }
 
-static inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-
 hipError_t launch_multiset_keys(const uint32_t* pair, const gl_t* cols, size_t stride, size_t n, gl_t seed, gl_t* keys, uint32_t* idx, hipStream_t st) {
-    hipLaunchKernelGGL(multiset_keys_kernel, dim3(nb(2 * n, MS_BLOCK)), dim3(MS_BLOCK), 0, st, pair, cols, stride, (uint32_t)n, seed, keys, idx);
+    hipLaunchKernelGGL(multiset_keys_kernel, dim3(nb(2 * n, TILE_BLOCK)), dim3(TILE_BLOCK), 0, st, pair, cols, stride, (uint32_t)n, seed, keys, idx);
     return hipGetLastError();
 }
 
@@ -265,10 +234,10 @@ hipError_t launch_multiset_sort(gl_t* keys, uint32_t* idx, gl_t* keys_alt, uint3
     const uint32_t tiles = (uint32_t)multiset_tiles(items), words = (uint32_t)multiset_table_words(items), chunks = (uint32_t)multiset_scan_chunks(items);
     for (unsigned pass = 0; pass < 8; pass++) {
         const unsigned shift = 8 * pass;
-        hipLaunchKernelGGL(multiset_histogram_kernel, dim3(tiles), dim3(MS_BLOCK), 0, st, keys, (uint32_t)items, shift, table, tiles);
-        if (chunks > 1) hipLaunchKernelGGL(multiset_scan_sums_kernel, dim3(chunks), dim3(MS_BLOCK), 0, st, table, words, sums);  // (chunk 0 reads no sum)
-        hipLaunchKernelGGL(multiset_scan_apply_kernel, dim3(chunks), dim3(MS_BLOCK), 0, st, table, words, sums);
-        hipLaunchKernelGGL(multiset_scatter_kernel, dim3(tiles), dim3(MS_BLOCK), 0, st, keys, idx, keys_alt, idx_alt, (uint32_t)items, shift, table, tiles);
+        hipLaunchKernelGGL(multiset_histogram_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, (uint32_t)items, shift, table, tiles);
+        if (chunks > 1) hipLaunchKernelGGL(multiset_scan_sums_kernel, dim3(chunks), dim3(TILE_BLOCK), 0, st, table, words, sums);  // (chunk 0 reads no sum)
+        hipLaunchKernelGGL(multiset_scan_apply_kernel, dim3(chunks), dim3(TILE_BLOCK), 0, st, table, words, sums);
+        hipLaunchKernelGGL(multiset_scatter_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, idx, keys_alt, idx_alt, (uint32_t)items, shift, table, tiles);
         std::swap(keys, keys_alt);
         std::swap(idx, idx_alt);
     }
@@ -277,13 +246,13 @@ hipError_t launch_multiset_sort(gl_t* keys, uint32_t* idx, gl_t* keys_alt, uint3
 
 hipError_t launch_multiset_classify(const uint32_t* pair, const gl_t* cols, size_t stride, size_t n, const gl_t* keys, const uint32_t* idx,
                                     unsigned long long* masks, unsigned long long* counters, hipStream_t st) {
-    hipLaunchKernelGGL(multiset_classify_kernel, dim3(nb(2 * n, MS_BLOCK)), dim3(MS_BLOCK), 0, st, pair, cols, stride, (uint32_t)n, keys, idx, masks, counters);
+    hipLaunchKernelGGL(multiset_classify_kernel, dim3(nb(2 * n, TILE_BLOCK)), dim3(TILE_BLOCK), 0, st, pair, cols, stride, (uint32_t)n, keys, idx, masks, counters);
     return hipGetLastError();
 }
 
 hipError_t launch_multiset_count(const unsigned long long* masks, size_t n, unsigned long long* counters, hipStream_t st) {
     const uint32_t W = (uint32_t)((n + 63) / 64);
-    hipLaunchKernelGGL(multiset_count_kernel, dim3(nb(2 * (size_t)W, MS_BLOCK)), dim3(MS_BLOCK), 0, st, masks, W, counters);
+    hipLaunchKernelGGL(multiset_count_kernel, dim3(nb(2 * (size_t)W, TILE_BLOCK)), dim3(TILE_BLOCK), 0, st, masks, W, counters);
     return hipGetLastError();
 }
 

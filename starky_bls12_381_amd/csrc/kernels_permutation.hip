@@ -6,7 +6,7 @@
 //  * the exclusive prefix product over rows, per Z, n = 2 .. 2^20, as THREE launches on the proof's stream: the product of each
 //    workgroup's span of PERM_SPAN rows (perm_block_products_kernel), an exclusive scan of those products in one workgroup per Z,
 //    which also leaves the closing product Z[n - 1] ratio(n - 1) (perm_scan_blocks_kernel), and the scan of each span started from its
-//    prefix (perm_apply_kernel).  Inside a workgroup: wave scans through __shfl_up, the waves' totals through LDS.  No workgroup waits
+//    prefix (perm_apply_kernel).  Inside a workgroup: block_scan (block_scan.h) under gl_mul.  No workgroup waits
 //    for another inside a launch.  Field multiplication is exact and associative and every product is canonical, so the words do not
 //    depend on how the rows are split.
 //  * perm_quotient_kernel: one lane per point of the quotient's domain.  The AIR's own fold, already divided by Z_H, is in qvals;
@@ -17,39 +17,13 @@
 // Every index is bounded by the row or point count the launch is given; the columns come from a validated program (air_validate.cpp).
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "kernels.h"
 #include "kernels_permutation.h"
 
 namespace starkhip {
 
-static const unsigned PERM_BLOCK = 256, PERM_ITEMS = PERM_SPAN_ROWS / PERM_BLOCK;
-
-__device__ __forceinline__ gl_t perm_shfl_up(gl_t v, unsigned d) { return (gl_t)__shfl_up((unsigned long long)v, d, 64); }
-
-// exclusive prefix product of v over the workgroup's PERM_BLOCK lanes, and the product of all of them.  lds: PERM_BLOCK / 64 words
-__device__ __forceinline__ gl_t perm_block_scan(gl_t v, gl_t* lds, gl_t* total) {
-    const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    gl_t incl = v;
-#pragma unroll
-    for (unsigned d = 1; d < 64; d <<= 1) {
-        const gl_t t = perm_shfl_up(incl, d);
-        if (lane >= d) incl = gl_mul(t, incl);
-    }
-    gl_t excl = perm_shfl_up(incl, 1);
-    if (lane == 0) excl = 1;
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    gl_t before = 1, all = 1;
-#pragma unroll
-    for (unsigned k = 0; k < PERM_BLOCK / 64; k++) {
-        const gl_t t = lds[k];
-        if (k < w) before = gl_mul(before, t);
-        all = gl_mul(all, t);
-    }
-    __syncthreads();  // lds is free for the next call
-    *total = all;
-    return gl_mul(before, excl);
-}
+static const unsigned PERM_BLOCK = TILE_BLOCK, PERM_ITEMS = PERM_SPAN_ROWS / PERM_BLOCK;  // block_scan's workgroup
 
 // ratio[z][r] for every Z of the program.  cols: the pair columns, column c at cols + c * stride
 __global__ __launch_bounds__(PERM_BLOCK) void perm_ratio_kernel(const uint32_t* __restrict__ desc, const gl_t* __restrict__ cols, size_t stride,
@@ -86,7 +60,7 @@ __global__ __launch_bounds__(PERM_BLOCK) void perm_ratio_kernel(const uint32_t* 
 
 // bp[z][blk] = the product of the span's ratios.  grid (n_blocks, nZ)
 __global__ __launch_bounds__(PERM_BLOCK) void perm_block_products_kernel(const gl_t* __restrict__ ratio, size_t n, size_t n_blocks, gl_t* __restrict__ bp) { STARKHIP_PRIO_ENTRY
-    __shared__ gl_t lds[PERM_BLOCK / 64];
+    __shared__ gl_t lds[TILE_WAVES];
     const gl_t* v = ratio + (size_t)blockIdx.y * n;
     const size_t r0 = (size_t)blockIdx.x * PERM_SPAN_ROWS;
     gl_t p = 1;
@@ -96,20 +70,20 @@ __global__ __launch_bounds__(PERM_BLOCK) void perm_block_products_kernel(const g
         if (r < n) p = gl_mul(p, v[r]);
     }
     gl_t total;
-    (void)perm_block_scan(p, lds, &total);
+    (void)block_scan(p, ScanMul(), (gl_t)1, lds, &total);
     if (threadIdx.x == 0) bp[(size_t)blockIdx.y * n_blocks + blockIdx.x] = total;
 }
 
 // pre[z][blk] = the product of bp[z][0 .. blk), closing[z] = the product of all of them.  One workgroup per Z, each lane a run of blocks
 __global__ __launch_bounds__(PERM_BLOCK) void perm_scan_blocks_kernel(const gl_t* __restrict__ bp, size_t n_blocks, gl_t* __restrict__ pre, gl_t* __restrict__ closing) { STARKHIP_PRIO_ENTRY
-    __shared__ gl_t lds[PERM_BLOCK / 64];
+    __shared__ gl_t lds[TILE_WAVES];
     const gl_t* in = bp + (size_t)blockIdx.x * n_blocks;
     gl_t* out = pre + (size_t)blockIdx.x * n_blocks;
     const size_t per = (n_blocks + PERM_BLOCK - 1) / PERM_BLOCK, j0 = threadIdx.x * per, j1 = j0 + per < n_blocks ? j0 + per : n_blocks;
     gl_t p = 1;
     for (size_t j = j0; j < j1; j++) p = gl_mul(p, in[j]);
     gl_t total;
-    gl_t run = perm_block_scan(p, lds, &total);
+    gl_t run = block_scan(p, ScanMul(), (gl_t)1, lds, &total);
     for (size_t j = j0; j < j1; j++) {
         const gl_t v = in[j];
         out[j] = run;
@@ -120,7 +94,7 @@ __global__ __launch_bounds__(PERM_BLOCK) void perm_scan_blocks_kernel(const gl_t
 
 // zs[z][r] <- pre[z][blk] times the product of the span's ratios before r; in place over the ratios.  grid (n_blocks, nZ)
 __global__ __launch_bounds__(PERM_BLOCK) void perm_apply_kernel(gl_t* __restrict__ zs, size_t n, size_t n_blocks, const gl_t* __restrict__ pre) { STARKHIP_PRIO_ENTRY
-    __shared__ gl_t lds[PERM_BLOCK / 64];
+    __shared__ gl_t lds[TILE_WAVES];
     gl_t* v = zs + (size_t)blockIdx.y * n;
     const size_t r0 = (size_t)blockIdx.x * PERM_SPAN_ROWS;
     gl_t carry = pre[(size_t)blockIdx.y * n_blocks + blockIdx.x];
@@ -129,7 +103,7 @@ __global__ __launch_bounds__(PERM_BLOCK) void perm_apply_kernel(gl_t* __restrict
         const size_t r = r0 + it * PERM_BLOCK + threadIdx.x;
         const gl_t x = r < n ? v[r] : 1;
         gl_t total;
-        const gl_t excl = perm_block_scan(x, lds, &total);
+        const gl_t excl = block_scan(x, ScanMul(), (gl_t)1, lds, &total);
         if (r < n) v[r] = gl_mul(carry, excl);
         carry = gl_mul(carry, total);
     }
@@ -185,8 +159,6 @@ __global__ __launch_bounds__(PERM_BLOCK) void perm_quotient_kernel(const uint32_
     qvals[i] = gl_add(gl_mul(qvals[i], scale0), gl_mul(acc0, zh_inv));
     qvals[size + i] = gl_add(gl_mul(qvals[size + i], scale1), gl_mul(acc1, zh_inv));
 }
-
-static inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
 
 hipError_t launch_perm_zs(const uint32_t* desc, const gl_t* cols, size_t stride, const gl_t* chal, size_t n, unsigned n_zs, gl_t* zs, gl_t* scratch,
                           gl_t* closing, hipStream_t st) {

@@ -43,8 +43,6 @@ __global__ void query_path_kernel(const gl_t* __restrict__ digests, size_t n_lea
     out[q * stride + off + t] = digests[4 * (level_off_dev(n_leaves, l) + idx) + e];
 }
 
-static inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-
 hipError_t launch_query_leaf_colmajor(const gl_t* mat, size_t n_cols, unsigned log_n, unsigned rate_bits, const uint32_t* xs, size_t n_queries,
                                       gl_t* out, size_t stride, size_t off, hipStream_t st) {
     if (n_queries == 0 || n_cols == 0) return hipSuccess;  // num_query_rounds = 0: a grid of zero blocks is a launch error

@@ -67,8 +67,6 @@ __global__ __launch_bounds__(64) void verify_query_kernel(const gl_t* __restrict
     status[i] = vq_check_query(P, words + P.base, dg, sums[2 * i], sums[2 * i + 1], x_index[i], qi);
 }
 
-static inline unsigned nb(size_t n, unsigned bs) { return (unsigned)((n + bs - 1) / bs); }
-
 hipError_t launch_verify_range(const gl_t* words, const VQProof* proofs, size_t n_proofs, uint32_t* bad, hipStream_t st) {
     if (!n_proofs) return hipSuccess;
     hipLaunchKernelGGL(verify_range_kernel, dim3(64, (unsigned)n_proofs), dim3(256), 0, st, words, proofs, bad);

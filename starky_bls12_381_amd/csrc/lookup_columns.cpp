@@ -9,15 +9,15 @@
 
 namespace starkhip {
 
-int lookup_args(const LookupTrace& tr, const starkhip_lookup_t* lookups, size_t n_lookups, const uint64_t* list, size_t cap, const void* out) {
+int lookup_args(const TraceInput& in, const starkhip_lookup_t* lookups, size_t n_lookups, const uint64_t* list, size_t cap, const void* out) {
     unsigned log_n = 0;
-    if (!tr.words || (tr.layout != 0 && tr.layout != 1) || !tr.n_cols || tr.n_cols > UINT32_MAX) return STARKHIP_ERR_BAD_SHAPE;
-    if (!log2_rows(tr.n_rows, &log_n) || log_n > STARKHIP_MAX_LOG_ROWS) return STARKHIP_ERR_BAD_SHAPE;
+    if (!in.words || in.unknown_layout || !in.n_cols || in.n_cols > UINT32_MAX) return STARKHIP_ERR_BAD_SHAPE;
+    if (!log2_rows(in.n_rows, &log_n) || log_n > STARKHIP_MAX_LOG_ROWS) return STARKHIP_ERR_BAD_SHAPE;
     if (!lookups || !n_lookups || n_lookups > STARKHIP_LOOKUPS_MAX) return STARKHIP_ERR_BAD_SHAPE;
     if (cap > STARKHIP_CHECK_LIST_MAX || (cap && !list) || !out) return STARKHIP_ERR_BAD_SHAPE;
     for (size_t q = 0; q < n_lookups; q++) {
         const starkhip_lookup_t& a = lookups[q];
-        if (a.input >= tr.n_cols || a.table >= tr.n_cols || a.permuted_input >= tr.n_cols || a.permuted_table >= tr.n_cols) return STARKHIP_ERR_BAD_SHAPE;
+        if (a.input >= in.n_cols || a.table >= in.n_cols || a.permuted_input >= in.n_cols || a.permuted_table >= in.n_cols) return STARKHIP_ERR_BAD_SHAPE;
         if (a.permuted_input == a.permuted_table) return STARKHIP_ERR_BAD_SHAPE;
         for (size_t r = 0; r < n_lookups; r++) {  // an output column is nobody's input or table, and nobody else's output
             const starkhip_lookup_t& b = lookups[r];
@@ -46,16 +46,8 @@ int lookup_run(size_t n_rows, const starkhip_lookup_t* lookups, size_t n_lookups
         rep.lookups_failed++;
         if (!masks && rep.listed >= cap) continue;
         if (int rc = steps.mask(pm.data())) return rc;
-        uint64_t bits = 0;
-        for (size_t w = 0; w < W; w++) {
-            uint64_t word = pm[w];
-            bits += (uint64_t)__builtin_popcountll(word);
-            for (; word && rep.listed < cap; word &= word - 1) {
-                uint64_t* e = list + 2 * rep.listed++;
-                e[0] = q;
-                e[1] = w * 64 + (size_t)__builtin_ctzll(word);
-            }
-        }
+        const uint64_t lead = q;
+        const uint64_t bits = mask_to_list(pm.data(), W, &lead, 1, list, cap, &rep.listed);
         if (bits != missing) return STARKHIP_ERR_HIP;  // the mask is the one that was counted
         if (masks) std::copy(pm.begin(), pm.end(), masks + q * W);
     }
@@ -66,15 +58,16 @@ int lookup_run(size_t n_rows, const starkhip_lookup_t* lookups, size_t n_lookups
 namespace {
 // one lookup as host loops over the caller's trace: the rule of lookup_columns.h, literally
 struct ReplaySteps : LookupSteps {
-    const LookupTrace& tr;
+    const TraceInput& in;
+    uint64_t* words;
     size_t n, W;
     std::vector<uint64_t> last;
-    explicit ReplaySteps(const LookupTrace& tr_) : tr(tr_), n(tr_.n_rows), W((tr_.n_rows + 63) / 64), last(W) {}
+    ReplaySteps(const TraceInput& in_, uint64_t* words_) : in(in_), words(words_), n(in_.n_rows), W((in_.n_rows + 63) / 64), last(W) {}
     int run(size_t, const starkhip_lookup_t& lk, uint64_t* missing) override {
         std::vector<gl_t> a(n), A, T(n);
         for (size_t r = 0; r < n; r++) {
-            a[r] = gl_from_u64(tr.words[tr.at(r, lk.input)]);
-            T[r] = gl_from_u64(tr.words[tr.at(r, lk.table)]);
+            a[r] = gl_from_u64(in.words[in.at(r, lk.input)]);
+            T[r] = gl_from_u64(in.words[in.at(r, lk.table)]);
         }
         A = a;
         std::stable_sort(A.begin(), A.end());
@@ -96,8 +89,8 @@ struct ReplaySteps : LookupSteps {
         for (size_t i = 0; i < n; i++) {
             const bool head = i == 0 || A[i] != A[i - 1];
             if (!head && k >= unused.size()) return STARKHIP_ERR_HIP;  // heads and used positions are equally many
-            tr.words[tr.at(i, lk.permuted_input)] = A[i];
-            tr.words[tr.at(i, lk.permuted_table)] = head ? A[i] : unused[k++];
+            words[in.at(i, lk.permuted_input)] = A[i];
+            words[in.at(i, lk.permuted_table)] = head ? A[i] : unused[k++];
         }
         return k == unused.size() ? STARKHIP_OK : STARKHIP_ERR_HIP;
     }
@@ -108,10 +101,10 @@ struct ReplaySteps : LookupSteps {
 };
 }  // namespace
 
-int lookup_columns_replay(const LookupTrace& tr, const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* masks,
+int lookup_columns_replay(const TraceInput& in, uint64_t* words, const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* masks,
                           uint64_t* list, size_t cap, starkhip_lookup_report_t* out) {
-    ReplaySteps steps(tr);
-    return lookup_run(tr.n_rows, lookups, n_lookups, steps, per_lookup, masks, list, cap, out);
+    ReplaySteps steps(in, words);
+    return lookup_run(in.n_rows, lookups, n_lookups, steps, per_lookup, masks, list, cap, out);
 }
 
 }  // namespace starkhip

@@ -13,19 +13,14 @@
 #include <stdint.h>
 
 #include "../../include/starkhip.h"
+#include "trace_input.h"
 
 namespace starkhip {
 
-// the caller's trace: dense, written in place (host memory, or device memory when on_device)
-struct LookupTrace {
-    uint64_t* words;
-    size_t n_rows, n_cols;
-    int layout, on_device;
-    size_t at(size_t row, size_t col) const { return layout == 1 ? col * n_rows + row : row * n_cols + col; }
-};
-
+// The caller's trace is dense and written in place: `in` is the view of it every trace entry gets, `words` the same memory, writable
+// (host memory, or device memory when in.on_device).
 // BAD_SHAPE for what the entries refuse of their arguments
-int lookup_args(const LookupTrace& tr, const starkhip_lookup_t* lookups, size_t n_lookups, const uint64_t* list, size_t cap, const void* out);
+int lookup_args(const TraceInput& in, const starkhip_lookup_t* lookups, size_t n_lookups, const uint64_t* list, size_t cap, const void* out);
 
 struct LookupSteps {
     virtual ~LookupSteps() {}
@@ -38,7 +33,7 @@ struct LookupSteps {
 int lookup_run(size_t n_rows, const starkhip_lookup_t* lookups, size_t n_lookups, LookupSteps& steps, uint32_t* per_lookup, uint64_t* masks,
                uint64_t* list, size_t cap, starkhip_lookup_report_t* out);
 
-int lookup_columns_replay(const LookupTrace& tr, const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* masks,
+int lookup_columns_replay(const TraceInput& in, uint64_t* words, const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* masks,
                           uint64_t* list, size_t cap, starkhip_lookup_report_t* out);
 
 }  // namespace starkhip

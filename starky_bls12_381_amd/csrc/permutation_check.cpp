@@ -44,17 +44,8 @@ int perm_check_run(const AirProgram& P, size_t n_rows, PermCheckSteps& steps, ui
         if (!masks && rep.listed >= cap) continue;
         if (int rc = steps.masks(pm.data())) return rc;
         for (size_t side = 0; side < 2; side++) {
-            uint64_t bits = 0;
-            for (size_t w = 0; w < W; w++) {
-                uint64_t word = pm[side * W + w];
-                bits += (uint64_t)__builtin_popcountll(word);
-                for (; word && rep.listed < cap; word &= word - 1) {
-                    uint64_t* e = list + 3 * rep.listed++;
-                    e[0] = q;
-                    e[1] = side;
-                    e[2] = w * 64 + (size_t)__builtin_ctzll(word);
-                }
-            }
+            const uint64_t lead[2] = {q, side};
+            const uint64_t bits = mask_to_list(pm.data() + side * W, W, lead, 2, list, cap, &rep.listed);
             if (bits != counts[1 + side]) return STARKHIP_ERR_HIP;  // the masks are the ones that were counted
         }
         if (masks) std::copy(pm.begin(), pm.end(), masks + q * 2 * W);

@@ -1,5 +1,5 @@
-// Host half of starkhip_check_trace_permutations (starkhip.h has the rule), the same for the device path (check_trace.hip:
-// check_trace_permutations over kernels_multiset.hip) and for the replay without a device (permutation_check.cpp): the argument checks,
+// Host half of starkhip_check_trace_permutations (starkhip.h has the rule), the same for the device path (permutation_check.hip
+// over kernels_multiset.hip) and for the replay without a device (permutation_check.cpp): the argument checks,
 // the seed sequence, the rerun of a pair whose keys collided, undecided pairs, the counts, the list from the masks in its fixed order
 // and the summary.  What differs is who runs one pair under one seed: three device steps, or host loops.
 #pragma once

@@ -1,11 +1,11 @@
 // Internal interface between the C ABI (capi.cpp) and the GPU prover driver: the context (ctx.hip), the proof (prover.hip), the trace checkers
-// (check_trace.hip), the fill of a lookup's permuted columns (lookup_columns.hip) and the kernel-level entries of the tests (kernel_entries.hip).
+// (check_trace.hip), the check of the permutation pairs (permutation_check.hip), the fill of a lookup's permuted columns (lookup_columns.hip)
+// and the kernel-level entries of the tests (kernel_entries.hip).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "airs.h"
-#include "lookup_columns.h"
 #include "trace_input.h"
 
 namespace starkhip {
@@ -88,14 +88,14 @@ int check_trace_free_cells(Ctx* c, const AirInfo& air, const TraceInput& in, con
 // (kernels_free_classes.hip, free_cells.h)
 int check_trace_free_cell_classes(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t delta, uint32_t* per_column,
                                   uint64_t* planes, uint32_t* open_rows, starkhip_free_cell_classes_t* out);
-// starkhip_check_trace_permutations: which rows of each permutation pair have no partner on the other side (kernels_multiset.hip,
-// permutation_check.h); perm_check_timings: the last call's {upload, sort, classify, read-back} milliseconds
+// starkhip_check_trace_permutations: which rows of each permutation pair have no partner on the other side (permutation_check.hip over
+// kernels_multiset.hip, permutation_check.h); perm_check_timings: the last call's {upload, sort, classify, read-back} milliseconds
 int check_trace_permutations(Ctx* c, const AirInfo& air, const TraceInput& in, uint64_t seed, uint32_t* per_pair, uint64_t* masks, uint64_t* list,
                              size_t cap, starkhip_perm_check_t* out);
 void perm_check_timings(Ctx* c, float ms[4]);
-// starkhip_lookup_columns: the permuted columns of each lookup written into the caller's trace (kernels_multiset.hip, kernels_lookup.hip,
-// lookup_columns.h); lookup_timings: the last call's {upload or gather, sort, place, read-back} milliseconds
-int lookup_columns(Ctx* c, const LookupTrace& tr, const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* masks,
+// starkhip_lookup_columns: the permuted columns of each lookup written into the caller's trace -- `words`, the memory `in` views (lookup_columns.hip
+// over kernels_multiset.hip and kernels_lookup.hip, lookup_columns.h); lookup_timings: the last call's {upload or gather, sort, place, read-back} milliseconds
+int lookup_columns(Ctx* c, const TraceInput& in, uint64_t* words, const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* masks,
                    uint64_t* list, size_t cap, starkhip_lookup_report_t* out);
 void lookup_timings(Ctx* c, float ms[4]);
 int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);

@@ -4,7 +4,7 @@
 // every heavy step is one of the kernels in kernels_*.hip, the host only runs the Fiat-Shamir challenger, two length-n synthetic
 // divisions and the proof assembly.  An AIR with permutation pairs (COMPAT.md P1 - P8) has its Z polynomials made and committed at the
 // start of the quotient phase (ProveCall::permutation) and carried as a third matrix from there on.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
-// checkers' host halves check_trace.hip, the kernel-level entry points of the tests kernel_entries.hip.
+// checkers' host halves check_trace.hip and permutation_check.hip, the kernel-level entry points of the tests kernel_entries.hip.
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>

@@ -42,7 +42,7 @@ size_t TraceInput::park_words(size_t C) const {
 void TraceInput::to_row_major(std::vector<uint64_t>& rows) const {
     rows.resize(n_rows * n_cols);
     for (size_t r = 0; r < n_rows; r++)
-        for (size_t c = 0; c < n_cols; c++) rows[r * n_cols + c] = form == TraceForm::ColMajor ? words[c * n_rows + r] : words[r * n_cols + c];
+        for (size_t c = 0; c < n_cols; c++) rows[r * n_cols + c] = words[at(r, c)];
 }
 
 }  // namespace starkhip

@@ -35,6 +35,7 @@ struct TraceInput {  // a view; owns nothing
     // that is not the AIR's, a null column, a recording without rows, device memory in a form that has none.  Rows and public inputs
     // are the proof's to judge (ProofShape::make, check_trace_shape).
     int check(const AirInfo& air) const;
+    size_t at(size_t row, size_t col) const { return form == TraceForm::ColMajor ? col * n_rows + row : row * n_cols + col; }  // dense forms: a cell's index in `words`
     bool callers_columns() const { return form == TraceForm::ColMajor && on_device; }  // read where it is: nothing is uploaded
     // 64-bit words the upload stages at the start of the LDE buffer for a trace of C columns: a recording's words, offsets and late
     // zeros, or host rows on their way through the transpose

@@ -1,5 +1,5 @@
-"""starkhip_lookup_columns on the GPU (csrc/kernels_multiset.hip: keys and the stable sort; csrc/kernels_lookup.hip: mark, scan, the
-two placements): the filled trace and the report equal the Python reference of lookup_ref.py and the C++ replay byte for byte.  The
+"""starkhip_lookup_columns on the GPU (csrc/lookup_columns.hip over csrc/kernels_multiset.hip: keys and the stable sort, and
+csrc/kernels_lookup.hip: mark, scan, the two placements; their tile and workgroup scan are csrc/block_scan.h's): the filled trace and the report equal the Python reference of lookup_ref.py and the C++ replay byte for byte.  The
 shapes are where the kernels change shape: 2 rows (four items, less than a wave), 64 (2 n is two waves of one tile), 1024 (2 n fills
 exactly two tiles of 1024 items), 4096, 2^14 (32 tiles: the sort's table scan takes its chunk sums and the placement more than one tile
 total) and one run at 2^20 (2^21 items, 2048 tiles: the scan of the tile totals walks its row in eight pieces)."""

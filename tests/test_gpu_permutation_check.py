@@ -1,5 +1,5 @@
-"""starkhip_check_trace_permutations on the GPU (csrc/kernels_multiset.hip: keys, the stable radix sort, the classification): the
-device result equals the replay and the Python reference of permutation_check_util.py byte for byte -- counts, per_pair, masks and
+"""starkhip_check_trace_permutations on the GPU (csrc/permutation_check.hip over csrc/kernels_multiset.hip: keys, the stable radix sort,
+the classification; the tile, the workgroup scan and the run-end search are csrc/block_scan.h's): the device result equals the replay and the Python reference of permutation_check_util.py byte for byte -- counts, per_pair, masks and
 list.  The shapes are the smallest at which the sort can go wrong: 2 rows (four items, less than a wave), 32 (2 n is one wave), 512
 and 1024 (2 n is one and two workgroups' tiles: MULTISET_TILE = 1024 items), 2^13 and 2^14 (16 and 32 tiles: a digit table of one scan
 chunk, scanned without chunk sums, and the first of two), and one run at 2^20 rows (a table of 128 chunks) against the C++ replay alone."""
@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = R.P
 SEED = S.DEFAULT_SEED
-SMALL = [2, 32, 512, 1024]  # csrc/kernels_multiset.h: MULTISET_TILE = 1024 items per workgroup
+SMALL = [2, 32, 512, 1024]  # csrc/kernels_multiset.h: MULTISET_TILE = TILE_ITEMS (csrc/block_scan.h) = 1024 items per workgroup
 
 
 def _check(prover, air, pairs, trace, reference=True, **kw):
