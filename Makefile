@@ -91,6 +91,13 @@ asan-lookup-test: tests/asan_lookup_main.cpp $(ASAN_SRCS) $(HDRS)
 	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_lookup tests/asan_lookup_main.cpp $(ASAN_SRCS) -lpthread
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_lookup
 
+# what "fill_lookups" adds to the host code -- the check of a lookup list and the registry keyed by (blob, list), the host driver in uneven
+# batches over the replay steps, the lookup blob's builder and parser -- under the same two: a stand-alone program
+asan-lookup-fill-test: tests/asan_lookup_fill_main.cpp $(ASAN_SRCS) $(HDRS)
+	@mkdir -p build/asan
+	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_lookup_fill tests/asan_lookup_fill_main.cpp $(ASAN_SRCS) -lpthread
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_lookup_fill
+
 # Experiment builds of the device code for A/B runs on one box: `make variant NAME=x DEFS="-D..."` -> build/x/libstarkhip_x.so, selected
 # at run time with STARKHIP_LIBRARY=build/x/libstarkhip_x.so (e.g. NAME=nomfma DEFS=-DSTARKHIP_LANE_NO_MFMA: the lane-form leaf hash with every
 # round as multiply-add chains; NAME=noprio DEFS=-DSTARKHIP_NO_PRIO: no raised issue priority for the kernels beside the lane-form hash)
@@ -106,4 +113,4 @@ build/$(NAME)/libstarkhip_$(NAME).so: $(VAR_OBJS) $(filter %.cpp.o,$(OBJS))
 clean:
 	rm -rf build $(OUT)
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test asan-keccak-test asan-perm-check-test asan-lookup-test variant
+.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test asan-keccak-test asan-perm-check-test asan-lookup-test asan-lookup-fill-test variant

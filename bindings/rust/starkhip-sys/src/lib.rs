@@ -50,6 +50,8 @@ pub const STARKHIP_ERR_BAD_AIR: c_int = -8;
 pub const STARKHIP_ERR_TRACE: c_int = -9;
 /// First word of the check blob a checking prove hands back with `STARKHIP_ERR_TRACE` ("SSCHK001").
 pub const STARKHIP_CHECK_MAGIC: u64 = 0x3130304B48435353;
+/// Word 0 of the lookup blob a prove with "fill_lookups" hands back with `STARKHIP_ERR_TRACE` ("SSLKP001").
+pub const STARKHIP_LOOKUP_MAGIC: u64 = 0x3130_3050_4B4C_5353;
 pub const STARKHIP_POW_SEARCH: u64 = u64::MAX;
 /// The hasher of a proof (`C: GenericConfig`): the context / pool option "hasher", and header word 12 of a proof blob.
 pub const STARKHIP_HASHER_POSEIDON: c_int = 0;
@@ -339,6 +341,23 @@ extern "C" {
                                           out: *mut starkhip_lookup_report_t) -> c_int;
     // ms [4]: upload or gather, sort, placement, read-back of the context's last starkhip_lookup_columns
     pub fn starkhip_lookup_timings(ctx: *mut c_void, ms: *mut f32) -> c_int;
+    // An AIR registered with its lookups: the key is (blob, lookups) -- the same two again return their first id, the same blob through
+    // starkhip_air_register keeps an id of its own without a list.  With the context option "fill_lookups" = 1 (a pool's option of the
+    // same name) every prove of such an AIR fills the permuted columns in its own copy of the trace first; a lookup that fails:
+    // STARKHIP_ERR_TRACE and a lookup blob in *proof (starkhip_free).
+    pub fn starkhip_air_register_lookups(blob: *const u64, words: usize, name: *const c_char, default_rows: u32, lookups: *const starkhip_lookup_t,
+                                         n_lookups: usize, id_out: *mut starkhip_air_t) -> c_int;
+    // the length of the AIR's list; its first min(cap, length) entries go to `out` (may be null).  0 without a list.
+    pub fn starkhip_air_lookups(air: starkhip_air_t, out: *mut starkhip_lookup_t, cap: usize) -> usize;
+    // STARKHIP_OK, or STARKHIP_ERR_BAD_AIR with the reason in `why` (may be null)
+    pub fn starkhip_air_check_lookups(blob: *const u64, words: usize, lookups: *const starkhip_lookup_t, n_lookups: usize, why: *mut c_char,
+                                      why_len: usize) -> c_int;
+    // a lookup blob: 8 header words {STARKHIP_LOOKUP_MAGIC, AIR id, n_rows, lookups, lookups_failed, missing_rows, listed, 0}, then
+    // listed x {lookup, row}; *list (may be null) points into the blob
+    pub fn starkhip_lookup_blob_layout(blob: *const u64, words: usize, out: *mut starkhip_lookup_report_t, list: *mut *const u64) -> c_int;
+    // tests: the blob a filling prove must hand back for a host trace, without a device (STARKHIP_OK and a null blob when every lookup holds)
+    pub fn starkhip_lookup_blob_replay(air: starkhip_air_t, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int, cap: usize,
+                                       blob: *mut *mut u64, words: *mut usize) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

@@ -361,8 +361,8 @@ int starkhip_perm_check_timings(void* ctx, float ms[4]);
  *   other lookups of the call are still written.
  * This is a valid witness, not the one evm's permuted_cols computes (which hands unused table values out last-in first-out).
  * The output columns are written into the caller's trace where it lies: device memory in place (element r of a column at stride 1
- * for layout 1, n_cols for layout 0); of a host trace only the two columns of each lookup go up and the two output columns come
- * back.  Nothing else in the trace is touched.
+ * for layout 1, n_cols for layout 0); of a host trace the four columns of each lookup of a batch go up in one copy and, for a
+ * lookup that holds, the two output columns come back.  Nothing else in the trace is touched.
  *   per_lookup (n_lookups entries, or NULL): the missing rows of each lookup;
  *   missing_masks (n_lookups x (n_rows + 63) / 64 words, or NULL): bit (r & 63) of word r >> 6 = row r of the lookup's input is missing;
  *   list (cap x {lookup, row}; may be NULL when cap == 0): the first min(cap, missing_rows) missing rows by lookup, then row.
@@ -372,7 +372,8 @@ int starkhip_perm_check_timings(void* ctx, float ms[4]);
  * an output column that is also any lookup's input or table column or another output column of the call, cap >
  * STARKHIP_CHECK_LIST_MAX, a NULL list with cap > 0.  A table column shared by several lookups is fine.  One call at a time per
  * context, not beside a prove on it.  On the context's device: the stable sort of csrc/kernels_multiset.hip, then a mark pass, a scan
- * and two placements per lookup (csrc/kernels_lookup.hip); the placements run only once the lookup's missing count is known zero. */
+ * and two placements per lookup (csrc/kernels_lookup.hip), the lookups of a call in batches that share each launch (grid.y = lookup;
+ * DESIGN.md 13c) with one host wait per batch; the placements of a lookup write only when its missing count on the device is zero. */
 #define STARKHIP_LOOKUPS_MAX 64
 typedef struct {
     uint32_t input, table, permuted_input, permuted_table;
@@ -400,6 +401,53 @@ int starkhip_lookup_timings(void* ctx, float ms[4]);
  * is written when it fits cap_words (BAD_SHAPE otherwise, and for arguments the builder refuses). */
 int starkhip_lookup_air_blob(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, uint64_t* blob,
                              size_t cap_words, size_t* words);
+/* --- an AIR that knows its lookups, and the fill inside prove() ------------------------------------------------------
+ * starkhip_air_register_lookups registers a program together with the list of its lookups.  The list is witness information: no
+ * verifier reads it and it is no part of the blob.  The registry's key is (blob, list): the same two again return their first id,
+ * another list -- or the same blob through starkhip_air_register, which has none -- is another AIR with an id of its own, and a proof
+ * made under one id verifies under the other (the program is the same).  starkhip_air_lookups returns the length of an AIR's list and
+ * writes its first min(cap, length) entries to `out` (may be NULL); 0 for built-in AIRs, plain registrations and unknown ids.
+ * starkhip_air_check_lookups is the validation, callable without registering: STARKHIP_OK, or STARKHIP_ERR_BAD_AIR with the reason in
+ * `why` (may be NULL) for a blob starkhip_air_check_program refuses, n_lookups outside 1 .. STARKHIP_LOOKUPS_MAX, a column >= n_cols, a
+ * lookup whose two output columns are one, an output column that is any lookup's input or table or another lookup's output, and a
+ * lookup whose pairs [(input, permuted_input)] and [(table, permuted_table)] the program does not both declare -- such a list would
+ * have the fill write columns that the proof does not bind.
+ *
+ * With the context option "fill_lookups" = 1 (a pool's option of the same name) every starkhip_prove, _prove_columns and
+ * _prove_compact of an AIR that has a list runs starkhip_lookup_columns' rule on the copy of the trace it has just put in device
+ * memory: after the upload has left the trace column-major there, BEFORE "check_trace" (which therefore sees the filled columns)
+ * and before the pair columns are copied aside for the Zs.  The caller submits a trace whose permuted columns hold anything and gets
+ * the proof that starkhip_prove without the option gives for the trace starkhip_lookup_columns would have filled: the same bytes.
+ * The caller's buffer is only read: column-major device memory, which prove otherwise reads where it lies, is first copied into the
+ * context's own trace buffer (one device-to-device copy of 8 n_rows n_cols bytes) and the proof works on that copy.  The lookups run
+ * in batches, one host wait per batch; on its own copy the prover places every lookup without waiting for its count.
+ * Some lookup fails: the call returns STARKHIP_ERR_TRACE, no later phase has been enqueued, the context stays usable, starkhip_check_stats
+ * counts the trace as checked and rejected, and *proof / *proof_words hand back a LOOKUP BLOB -- library-owned, released with
+ * starkhip_free:
+ *   word 0  STARKHIP_LOOKUP_MAGIC ("SSLKP001")       word 4  lookups_failed
+ *   word 1  AIR id                                   word 5  missing_rows
+ *   word 2  n_rows                                   word 6  listed
+ *   word 3  lookups                                  word 7  0
+ *   then listed x {lookup, row}: starkhip_lookup_columns' list for the same trace and the AIR's list with cap = "check_trace_list".
+ * An AIR without a list (every built-in AIR, every plain registration): nothing is enqueued and every byte of every proof is what it is
+ * without the option.  starkhip_last_timings[0] includes the fill; starkhip_lookup_timings reports the last fill of the context,
+ * whichever entry ran it.  "lookup_batch" (0 = automatic, the default; 1 .. STARKHIP_LOOKUPS_MAX = at most that many lookups share one
+ * set of launches) is for tests: results do not depend on it.
+ * starkhip_lookup_blob_layout validates magic and length like starkhip_check_blob_layout (a proof, a check blob, a truncated blob and
+ * a `listed` that disagrees with the length: BAD_SHAPE).  starkhip_lookup_blob_replay (tests): what a filling prove must hand back for
+ * `trace` (host memory, only read) with "check_trace_list" = cap, without a device: STARKHIP_OK and *blob = NULL when every lookup
+ * holds or the AIR has no list, STARKHIP_ERR_TRACE and the blob (starkhip_free) otherwise. */
+#define STARKHIP_LOOKUP_MAGIC 0x313030504B4C5353ULL
+int starkhip_air_check_lookups(const uint64_t* blob, size_t words, const starkhip_lookup_t* lookups, size_t n_lookups, char* why, size_t why_len);
+int starkhip_air_register_lookups(const uint64_t* blob, size_t words, const char* name, uint32_t default_rows, const starkhip_lookup_t* lookups,
+                                  size_t n_lookups, starkhip_air_t* id_out);
+size_t starkhip_air_lookups(starkhip_air_t air, starkhip_lookup_t* out, size_t cap);
+int starkhip_lookup_blob_layout(const uint64_t* blob, size_t words, starkhip_lookup_report_t* out, const uint64_t** list);
+int starkhip_lookup_blob_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, size_t cap, uint64_t** blob,
+                                size_t* words);
+/* tests: starkhip_lookup_air_blob's program registered with AirBuilder::lookups() as its list */
+int starkhip_lookup_air_register(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, const char* name, uint32_t default_rows,
+                                 starkhip_air_t* id_out);
 
 /* --- natives + trace generation (host)----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.
@@ -438,7 +486,8 @@ void starkhip_shutdown(void* ctx);
  * representatives of 0 .. 2^32 - 2 (plonky2's GoldilocksField keeps such words in memory).  This holds for every entry that reads a
  * trace -- this one, starkhip_prove_columns, the pools' submits, starkhip_check_trace, its report and the free-cell audit, on host
  * or device memory, in either layout -- and every result (proof bytes, counts, `first`, lists and their values, masks) is what the same
- * call returns for the trace reduced mod p.  The caller's buffer is only read.  (A refusal would cost a pass over 4.8 GB of a
+ * call returns for the trace reduced mod p.  The caller's buffer is only read -- with "fill_lookups" too, which fills the permuted
+ * columns in the context's own copy (column-major device memory is copied for it; see "the fill inside prove()").  (A refusal would cost a pass over 4.8 GB of a
  * device-resident FinalExp trace, after the point where bad shapes are refused; tests/test_gpu_noncanonical_cells.py.) */
 int starkhip_prove(void* ctx, starkhip_air_t air, const starkhip_config_t* cfg, const uint64_t* trace, size_t n_rows, size_t n_cols,
                    int trace_layout, int trace_on_device, const uint64_t* public_inputs, size_t n_pis, uint64_t pow_witness,
@@ -466,6 +515,9 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
  * "check_trace" (0 = default / 1: every prove on the context checks its trace against the AIR before the LDE and returns
  * STARKHIP_ERR_TRACE with a check blob for a violating one -- "the check inside prove()" above), "check_trace_list" (0 ..
  * STARKHIP_CHECK_LIST_MAX, default 16: the violations such a blob lists),
+ * "fill_lookups" (0 = default / 1: every prove of an AIR registered with its lookups fills their permuted columns in its own copy of
+ * the trace first -- "the fill inside prove()" above; STARKHIP_ERR_TRACE with a lookup blob when a lookup fails), "lookup_batch" (0 =
+ * automatic / 1 .. STARKHIP_LOOKUPS_MAX: the lookups that share one set of launches, there and in starkhip_lookup_columns),
  * "hasher" (STARKHIP_HASHER_POSEIDON, the default, or STARKHIP_HASHER_KECCAK: the hash of every prove entry of the context -- trace
  * and quotient commitments, FRI layers, proof of work and the transcript's sponge.  With 0 every byte of every proof is what it is
  * without the option.  Under STARKHIP_HASHER_KECCAK "leaf_hash_form" and "host_commit_leaves" do not apply: they pick among Poseidon
@@ -656,6 +708,10 @@ int starkhip_hw_queues_in_effect(void);
  *                     A violating trace: starkhip_pool_wait returns STARKHIP_ERR_TRACE and hands over the check blob in *proof
  *                     (starkhip_free); with "verify_proofs" on as well it never reaches the verifier.
  *   "check_trace_list" 0 .. STARKHIP_CHECK_LIST_MAX (default 16): the violations such a blob lists; read at submit too.
+ *   "fill_lookups"    0 (default) or 1: every proving ticket submitted from then on has the permuted columns of its AIR's lookups filled
+ *                     by its context, as the context option "fill_lookups" does, before "check_traces" looks at the trace.  A failing
+ *                     lookup: starkhip_pool_wait returns STARKHIP_ERR_TRACE and hands over the lookup blob in *proof (starkhip_free);
+ *                     it never reaches the verifier, and starkhip_pool_check_stats counts it as rejected.
  *   "hasher"          STARKHIP_HASHER_POSEIDON (default) or STARKHIP_HASHER_KECCAK: the hasher of every proving ticket submitted from then
  *                     on, as the context option "hasher".  A Keccak proof's trace commitment is launched by its context on its own stream,
  *                     not by the pool's commitment scheduler (whose merged and lane-group launches are Poseidon forms): the counters of

@@ -308,7 +308,7 @@ class Pool {
         uint64_t* blob = nullptr;
         size_t words = 0;
         const int rc = multi_ ? starkhip_multipool_wait(pool_, ticket, &blob, &words, &p.info) : starkhip_pool_wait(pool_, ticket, &blob, &words, &p.info);
-        if (rc != STARKHIP_OK) starkhip_free(blob);  // "check_traces": a refused trace (STARKHIP_ERR_TRACE) comes with a check blob; this driver does not keep it
+        if (rc != STARKHIP_OK) starkhip_free(blob);  // "check_traces" / "fill_lookups": a refused trace (STARKHIP_ERR_TRACE) comes with a check blob or a lookup blob; this driver keeps neither
         check(multi_ ? "starkhip_multipool_wait" : "starkhip_pool_wait", rc);
         if (info) *info = p.info;
         p.words = Words(blob, words);

@@ -304,14 +304,22 @@ def parse_check_blob(blob):
     return CheckBlobReport(b[1], b[2], summary, entries)
 
 
+LOOKUP_MAGIC = 0x313030504B4C5353
+
+
 class TraceViolation(StarkhipError):
     """ERR_TRACE from a prove with "check_trace" on, or from a pool with "check_traces": the trace violates the AIR.  `.blob` is the
-    check blob (np.uint64) and `.report` its CheckBlobReport."""
+    check blob (np.uint64) and `.report` its CheckBlobReport.  From a prove or a pool with "fill_lookups" for a trace some lookup of
+    which fails: `.blob` is the lookup blob, `.lookup_report` its LookupBlobReport and `.report` is None (else `.lookup_report` is)."""
 
     def __init__(self, blob):
         super().__init__(ERR_TRACE)
         self.blob = blob
-        self.report = parse_check_blob(blob)
+        self.report = self.lookup_report = None
+        if len(blob) and int(blob[0]) == LOOKUP_MAGIC:
+            self.lookup_report = parse_lookup_blob(blob)
+        else:
+            self.report = parse_check_blob(blob)
 
 
 def _take_blob(rc, out, words, keep=True):
@@ -497,14 +505,43 @@ def air_check_program(blob):
     return why.value.decode()
 
 
-def register_air(blob, name=None, default_rows=0):
+def register_air(blob, name=None, default_rows=0, lookups=None):
     """Register a constraint program (csrc/air_ir.h format; air_builder.AirBuilder makes one) and return its AIR id, usable wherever a
     built-in id is.  The same blob again returns the same id.  A program the validator refuses raises StarkhipError(ERR_BAD_AIR).
-    default_rows: 0, or a power of two in 2 .. 2^MAX_LOG_ROWS (anything else: ERR_BAD_SHAPE)."""
+    default_rows: 0, or a power of two in 2 .. 2^MAX_LOG_ROWS (anything else: ERR_BAD_SHAPE).
+    lookups: [(input, table, permuted_input, permuted_table), ...] (AirBuilder.lookups) registers the program together with its lookups
+    (starkhip_air_register_lookups): a prover or pool with "fill_lookups" then fills their permuted columns itself.  The id is that of
+    (blob, lookups); the same blob without a list keeps an id of its own.  A list air_check_lookups refuses: ERR_BAD_AIR."""
     blob = np.ascontiguousarray(blob, dtype=np.uint64)
     out = C.c_int()
-    _chk(lib.starkhip_air_register(_p64(blob), blob.size, name.encode() if name is not None else None, default_rows, C.byref(out)))
+    cname = name.encode() if name is not None else None
+    if lookups is None:
+        _chk(lib.starkhip_air_register(_p64(blob), blob.size, cname, default_rows, C.byref(out)))
+    else:
+        arr, nl = _lookup_array(lookups)
+        _chk(lib.starkhip_air_register_lookups(_p64(blob), blob.size, cname, default_rows, arr, nl, C.byref(out)))
     return out.value
+
+
+def air_check_lookups(blob, lookups):
+    """The validator of register_air(lookups=...) (starkhip_air_check_lookups): None for a list it accepts for this program, else the reason."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint64)
+    arr, nl = _lookup_array(lookups)
+    why = C.create_string_buffer(512)
+    rc = lib.starkhip_air_check_lookups(_p64(blob), blob.size, arr, nl, why, len(why))
+    if rc == 0:
+        return None
+    if rc != ERR_BAD_AIR:
+        raise StarkhipError(rc)
+    return why.value.decode()
+
+
+def air_lookups(air):
+    """The lookups `air` was registered with, [(input, table, permuted_input, permuted_table), ...]; [] for a built-in AIR or a plain registration."""
+    n = lib.starkhip_air_lookups(air, None, 0)
+    arr = (_LookupStruct * max(1, n))()
+    lib.starkhip_air_lookups(air, arr, n)
+    return [(a.input, a.table, a.permuted_input, a.permuted_table) for a in arr[:n]]
 
 
 lib.starkhip_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -769,6 +806,65 @@ class LookupReport:
 
     def __repr__(self):
         return f"LookupReport(lookups={self.lookups}, failed={self.failed}, missing_rows={self.missing_rows}, listed={len(self.list)})"
+
+
+lib.starkhip_air_check_lookups.argtypes = [_u64p, C.c_size_t, C.POINTER(_LookupStruct), C.c_size_t, C.c_char_p, C.c_size_t]
+lib.starkhip_air_register_lookups.argtypes = [_u64p, C.c_size_t, C.c_char_p, C.c_uint32, C.POINTER(_LookupStruct), C.c_size_t, C.POINTER(C.c_int)]
+lib.starkhip_air_lookups.argtypes = [C.c_int, C.POINTER(_LookupStruct), C.c_size_t]
+lib.starkhip_air_lookups.restype = C.c_size_t
+lib.starkhip_lookup_blob_layout.argtypes = [_u64p, C.c_size_t, C.POINTER(_LookupReportStruct), C.POINTER(_u64p)]
+lib.starkhip_lookup_blob_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(_u64p), C.POINTER(C.c_size_t)]
+lib.starkhip_lookup_air_register.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(_LookupStruct), C.c_size_t, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]
+
+
+class LookupBlobReport:
+    """A lookup blob read (parse_lookup_blob): `air`, `n_rows`, `lookups`, `failed`, `missing_rows` and `list` (np.uint64[listed, 2]):
+    the first missing rows as (lookup, row), by lookup, then row, cut at the prover's "check_trace_list"."""
+
+    def __init__(self, air, n_rows, summary, entries):
+        self.air, self.n_rows = int(air), int(n_rows)
+        self.lookups, self.failed, self.missing_rows = int(summary.lookups), int(summary.lookups_failed), int(summary.missing_rows)
+        self.list = entries
+
+    def __repr__(self):
+        return f"LookupBlobReport(air={self.air}, n_rows={self.n_rows}, failed={self.failed}, missing_rows={self.missing_rows}, listed={len(self.list)})"
+
+
+def parse_lookup_blob(blob):
+    """starkhip_lookup_blob_layout on a lookup blob (np.uint64): its LookupBlobReport; StarkhipError(ERR_BAD_SHAPE) for anything else."""
+    b = np.ascontiguousarray(blob, dtype=np.uint64).reshape(-1)
+    summary = _LookupReportStruct()
+    lst = _u64p()
+    _chk(lib.starkhip_lookup_blob_layout(_p64(b), b.size, C.byref(summary), C.byref(lst)))
+    listed = int(summary.listed)
+    return LookupBlobReport(b[1], b[2], summary, b[8:8 + 2 * listed].reshape(listed, 2).copy())
+
+
+def lookup_blob_replay(air, trace, layout=0, cap=16):
+    """starkhip_lookup_blob_replay (tests, small shapes): the lookup blob a prove with "fill_lookups" must hand back for `trace` (only
+    read) with "check_trace_list" = cap, or None when every lookup of the AIR holds; no device needed."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1) or int(cap) < 0:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    out = _u64p()
+    words = C.c_size_t()
+    rc = lib.starkhip_lookup_blob_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, int(cap), C.byref(out), C.byref(words))
+    if rc == 0:
+        return None
+    if rc != ERR_TRACE:
+        raise StarkhipError(rc)
+    blob = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
+    lib.starkhip_free(out)
+    return blob
+
+
+def lookup_air_register(n_cols, degree, lookups, name=None, default_rows=0):
+    """tests: lookup_air_blob's program registered from the C++ AirBuilder with AirBuilder::lookups() as its list (starkhip_lookup_air_register)."""
+    arr, nl = _lookup_array(lookups)
+    out = C.c_int()
+    _chk(lib.starkhip_lookup_air_register(n_cols, degree, arr, nl, name.encode() if name is not None else None, default_rows, C.byref(out)))
+    return out.value
 
 
 def _lookup_array(lookups):
@@ -1279,6 +1375,8 @@ class Prover:
     def set_option(self, name, value):
         """Tuning knob of this context (starkhip_set_option).  "check_trace" = 1: every prove* checks its trace against the AIR on the
         device before the LDE and raises TraceViolation for a violating one ("check_trace_list": the violations its report lists).
+        "fill_lookups" = 1: every prove* of an AIR registered with its lookups (register_air(lookups=...)) fills their permuted columns
+        in the prover's own copy of the trace first, and raises TraceViolation with a lookup blob when a lookup fails.
         "leaf_hash_prefix" (default 1; 0: off): the lane and pair forms of the leaf hash start a trace whose first `rows` columns are
         e_0 .. e_{rows-1} (FinalExp's row selectors) from a saved state past them; same proof bytes either way.  The other names
         ("hasher", "leaf_hash_form", "lde_closed_forms", "lde_impl", "host_commit_leaves", "quotient_*", ...): include/starkhip.h."""
@@ -1616,7 +1714,8 @@ class ProofPool:
 
     def set_option(self, name, value):
         """starkhip_pool_set_option on every pool of the handle: "verify_proofs" (0 / 1), "verify_arena_mb", "check_traces" (0 / 1: wait
-        raises TraceViolation for a trace that violates its AIR), "check_trace_list", "hasher" (HASHER_POSEIDON / HASHER_KECCAK: the
+        raises TraceViolation for a trace that violates its AIR), "check_trace_list", "fill_lookups" (0 / 1: the permuted columns of an AIR
+        registered with its lookups are filled by the proving context; wait raises TraceViolation with the lookup blob when one fails), "hasher" (HASHER_POSEIDON / HASHER_KECCAK: the
         hasher of the proving tickets submitted from then on)."""
         if self._multi:
             _chk(lib.starkhip_multipool_set_option(self._h, name.encode(), int(value)))

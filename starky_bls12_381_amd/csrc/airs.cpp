@@ -41,12 +41,19 @@ int g_custom_count = 0;                            // under g_custom_mu
 struct BlobLess {
     bool operator()(const std::vector<uint64_t>* a, const std::vector<uint64_t>* b) const { return *a < *b; }
 };
-std::map<const std::vector<uint64_t>*, int, BlobLess> g_custom_ids;  // registered blob (the entry's own copy) -> id, under g_custom_mu
+std::map<const std::vector<uint64_t>*, int, BlobLess> g_custom_ids;  // registered key (the entry's own copy: AirInfo::key) -> id, under g_custom_mu
 }  // namespace
 
-int air_register(AirProgram&& prog, const std::vector<uint64_t>& blob, const char* name, uint32_t default_rows, int* id) {
+int air_register(AirProgram&& prog, const std::vector<uint64_t>& blob, const char* name, uint32_t default_rows, int* id,
+                 const std::vector<starkhip_lookup_t>& lookups) {
+    std::vector<uint64_t> key = {blob.size()};  // the length first: a blob followed by a list is no other blob
+    key.insert(key.end(), blob.begin(), blob.end());
+    for (const starkhip_lookup_t& lk : lookups) {
+        key.push_back((uint64_t)lk.input | ((uint64_t)lk.table << 32));
+        key.push_back((uint64_t)lk.permuted_input | ((uint64_t)lk.permuted_table << 32));
+    }
     std::lock_guard<std::mutex> g(g_custom_mu);
-    auto it = g_custom_ids.find(&blob);
+    auto it = g_custom_ids.find(&key);
     if (it != g_custom_ids.end()) {
         *id = it->second;
         return STARKHIP_OK;
@@ -63,7 +70,9 @@ int air_register(AirProgram&& prog, const std::vector<uint64_t>& blob, const cha
     c->info.degree = c->info.prog.degree;
     c->info.default_rows = default_rows;
     c->info.blob = blob;
-    g_custom_ids.emplace(&c->info.blob, new_id);
+    c->info.lookups = lookups;
+    c->info.key = std::move(key);
+    g_custom_ids.emplace(&c->info.key, new_id);
     g_custom[g_custom_count++].store(c.release(), std::memory_order_release);  // lives as long as the process
     *id = new_id;
     return STARKHIP_OK;

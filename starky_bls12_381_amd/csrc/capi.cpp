@@ -229,6 +229,64 @@ int starkhip_air_register(const uint64_t* blob, size_t words, const char* name, 
     }
 }
 
+static void copy_reason(const std::string& msg, char* why, size_t why_len) {
+    if (!why || !why_len) return;
+    const size_t n = std::min(msg.size(), why_len - 1);
+    memcpy(why, msg.data(), n);
+    why[n] = 0;
+}
+
+int starkhip_air_check_lookups(const uint64_t* blob, size_t words, const starkhip_lookup_t* lookups, size_t n_lookups, char* why, size_t why_len) {
+    std::string msg;
+    bool ok;
+    try {
+        AirProgram prog;
+        ok = air_parse_checked(blob, words, &prog, &msg) && air_lookups_ok(prog, lookups, n_lookups, &msg);
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+    copy_reason(msg, why, why_len);
+    return ok ? STARKHIP_OK : STARKHIP_ERR_BAD_AIR;
+}
+
+int starkhip_air_register_lookups(const uint64_t* blob, size_t words, const char* name, uint32_t default_rows, const starkhip_lookup_t* lookups,
+                                  size_t n_lookups, starkhip_air_t* id_out) {
+    if (!id_out || (default_rows && (default_rows < 2 || default_rows > (1u << STARKHIP_MAX_LOG_ROWS) || (default_rows & (default_rows - 1))))) return STARKHIP_ERR_BAD_SHAPE;
+    try {
+        AirProgram prog;
+        if (!air_parse_checked(blob, words, &prog, nullptr) || !air_lookups_ok(prog, lookups, n_lookups, nullptr)) return STARKHIP_ERR_BAD_AIR;
+        int id = 0;
+        const int rc = air_register(std::move(prog), std::vector<uint64_t>(blob, blob + words), name, default_rows, &id,
+                                    std::vector<starkhip_lookup_t>(lookups, lookups + n_lookups));
+        if (rc == STARKHIP_OK) *id_out = (starkhip_air_t)id;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+}
+
+size_t starkhip_air_lookups(starkhip_air_t air, starkhip_lookup_t* out, size_t cap) {
+    const AirInfo* a = air_get(air);
+    if (!a) return 0;
+    if (out) std::copy(a->lookups.begin(), a->lookups.begin() + std::min(cap, a->lookups.size()), out);
+    return a->lookups.size();
+}
+
+int starkhip_lookup_blob_layout(const uint64_t* blob, size_t words, starkhip_lookup_report_t* out, const uint64_t** list) {
+    if (!out || !lookup_blob_read(blob, words, out, list)) return STARKHIP_ERR_BAD_SHAPE;
+    return STARKHIP_OK;
+}
+
+int starkhip_lookup_blob_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, size_t cap, uint64_t** blob,
+                                size_t* words) {
+    const AirInfo* a = air_get(air);
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    unsigned log_n = 0;
+    if (in.check(*a) || !blob || !words || cap > STARKHIP_CHECK_LIST_MAX || !log2_rows(n_rows, &log_n) || log_n > max_log_rows(*a)) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] { return lookup_blob_replay(*a, in, cap, blob, words); });
+}
+
 int starkhip_check_trace(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
                          const uint64_t* public_inputs, uint64_t* violations, uint64_t first[3]) {
     if (!ctx) return STARKHIP_ERR_NO_DEVICE;
@@ -378,6 +436,19 @@ int starkhip_lookup_timings(void* ctx, float ms[4]) {
     if (!ms) return STARKHIP_ERR_BAD_SHAPE;
     lookup_timings((Ctx*)ctx, ms);
     return STARKHIP_OK;
+}
+
+int starkhip_lookup_air_register(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, const char* name, uint32_t default_rows,
+                                 starkhip_air_t* id_out) {
+    if (!lookups || !id_out) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] {
+        AirBuilder b(n_cols, 0, degree);
+        for (size_t q = 0; q < n_lookups; q++) b.lookup(lookups[q].input, lookups[q].table, lookups[q].permuted_input, lookups[q].permuted_table);
+        const std::vector<uint64_t> w = b.finish().serialize();
+        std::vector<starkhip_lookup_t> list;  // AirBuilder::lookups(), as the entry takes them
+        for (const AirBuilder::Lookup& lk : b.lookups()) list.push_back({lk.input, lk.table, lk.permuted_input, lk.permuted_table});
+        return starkhip_air_register_lookups(w.data(), w.size(), name, default_rows, list.data(), list.size(), id_out);
+    });
 }
 
 int starkhip_lookup_air_blob(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, uint64_t* blob,
@@ -1165,7 +1236,7 @@ const char* starkhip_error_string(int code) {
         case STARKHIP_ERR_NO_DEVICE: return "no such HIP device / context";
         case STARKHIP_ERR_VERIFY: return "proof rejected";
         case STARKHIP_ERR_BAD_AIR: return "unknown or unbuildable AIR id";
-        case STARKHIP_ERR_TRACE: return "the trace violates the AIR (\"check_trace\"): a check blob is returned instead of a proof";
+        case STARKHIP_ERR_TRACE: return "the trace violates the AIR (\"check_trace\": a check blob is returned instead of a proof) or a lookup of it fails (\"fill_lookups\": a lookup blob)";
         default: return "unknown error";
     }
 }

@@ -141,6 +141,10 @@ struct Ctx {
     // "check_trace_list" violations in the blob of a refusal; a pool sets both per job (ctx_set_check_trace).  The counters are read by
     // other threads (starkhip_pool_check_stats).
     long opt_check_trace = 0, opt_check_trace_list = 16;
+    // "fill_lookups": prove() fills the permuted columns of an AIR registered with its lookups (lookup_fill_in_prove) in its own copy of
+    // the trace, before the check and before the pair columns are copied aside; a pool sets it per job (ctx_set_fill_lookups).
+    // "lookup_batch": at most this many lookups share one set of launches (0: as many as lookup_batch_size allows)
+    long opt_fill_lookups = 0, opt_lookup_batch = 0;
     std::atomic<uint64_t> traces_checked{0}, traces_rejected{0};
     std::vector<gl_t> host_lde;      // their LDE on the host
     // op-stream program (quotient_impl = 1; kept as the cross-check)
@@ -209,7 +213,7 @@ struct Ctx {
         DevBuf cols, desc, chal, zvals, zcoef, zlde, zdigests, scan, open_z, open_zn;
         std::vector<DevBuf*> bufs() { return {&cols, &desc, &chal, &zvals, &zcoef, &zlde, &zdigests, &scan, &open_z, &open_zn}; }
     } perm;
-    // The sorted items of ONE set and what starkhip_check_trace_permutations keeps beside them (permutation_check.hip), grown like the ones
+    // The sorted items of ONE set (or of a batch of lookups, strided by set) and what starkhip_check_trace_permutations keeps beside them (permutation_check.hip), grown like the ones
     // above.  keys, idx, table: the two (key, idx) buffers of the sort (48 MB at 2^20 rows) and the digit table with its chunk sums --
     // sized, split and filled by sorted_items_reserve / sorted_items_run (ctx.hip) alone, for the permutation check and the lookups
     // alike.  desc: the pairs' columns as indices into perm.cols; masks: the two masks followed by the counters.  ms: the last call's
@@ -219,13 +223,16 @@ struct Ctx {
         float ms[4] = {0, 0, 0, 0};
         std::vector<DevBuf*> bufs() { return {&desc, &keys, &idx, &table, &masks}; }
     } mset;
-    // starkhip_lookup_columns (lookup_columns.hip over kernels_lookup.hip), sized for ONE lookup and grown like the ones above: what the
-    // placement needs beside the sorted items, which are mset's (sorted_items_run).  desc: per lookup {1, input, table}, then {1, 0, 1}
-    // for staged columns; cols: the staging of a trace that is not column-major device memory, [4][n] -- input, table, then the two
-    // output columns of a host trace; flags: what each sorted position is; sums: the tile counts [3][tiles]; slot: the non-heads'
-    // ranks; mask: the missing rows of the lookup followed by their count.  ms: the last call's timings (starkhip_lookup_timings).
+    // starkhip_lookup_columns and "fill_lookups" (lookup_columns.hip over kernels_lookup.hip), sized for one BATCH of G lookups
+    // (lookup_batch_size) with every per-lookup buffer strided by lookup, and grown like the ones above: what the placement needs beside
+    // the sorted items, which are mset's (sorted_items_run).  desc: the descriptors of lookup_columns.hip's LookupDesc; cols: the staging
+    // of a trace that is not column-major device memory, [G][4][n] -- input, table, then the two output columns of a host trace; flags:
+    // what each sorted position is; sums: the tile counts [G][3][tiles]; slot: the non-heads' ranks [G][n]; mask: for a batch of g <= G
+    // lookups the missing rows [g][W], then their g counts.  desc_air: the registered AIR whose list `desc` holds (-1: none).  ms: the last fill's timings (starkhip_lookup_timings).
     struct LookupBufs {
         DevBuf desc, cols, flags, sums, slot, mask;
+        int desc_air = -1;
+        size_t desc_G = 0;  // ... cut for batches of this many
         float ms[4] = {0, 0, 0, 0};
         std::vector<DevBuf*> bufs() { return {&desc, &cols, &flags, &sums, &slot, &mask}; }
     } lookup;
@@ -257,8 +264,18 @@ int run_ntt(Ctx* c, gl_t* data, gl_t* mid, size_t n_vecs, size_t vec_stride, uns
             const gl_t* post_scale);
 int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values);
 // the sorted (key, idx) items of one set of 2 n items in c->mset: room for them, then keys and the stable sort on the context's stream
-int sorted_items_reserve(Ctx* c, size_t items);
-int sorted_items_run(Ctx* c, const uint32_t* desc, const gl_t* cols, size_t stride, size_t n, gl_t seed, const gl_t** keys, const uint32_t** idx);
+// (`sets` sets of that size side by side, set y's descriptor at desc + y * desc_stride: the lookups of a batch)
+int sorted_items_reserve(Ctx* c, size_t items, size_t sets = 1);
+int sorted_items_run(Ctx* c, const uint32_t* desc, const gl_t* cols, size_t stride, size_t n, gl_t seed, const gl_t** keys, const uint32_t** idx, size_t sets = 1,
+                     uint32_t desc_stride = 0);
+// ---- lookup_columns.hip
+// "fill_lookups": the permuted columns of every lookup of `air` written into the prover's own column-major copy of the trace, before
+// anything reads it.  STARKHIP_OK when every lookup holds; STARKHIP_ERR_TRACE and the lookup blob (lookup_columns.h) otherwise.
+int lookup_fill_in_prove(Ctx* c, const AirInfo& air, gl_t* d_trace, size_t n_rows, uint64_t** blob, size_t* words);
+// THE sizes of the buffers a fill of `n_lookups` lookups over n_rows takes (`staged`: of a trace that is not column-major device
+// memory): work_buffers()' share for a proof that fills, and what starkhip_lookup_columns allocates from
+struct LookupWant { DevBuf* b; size_t bytes; };
+std::vector<LookupWant> lookup_work_buffers(Ctx* c, size_t n_rows, size_t n_lookups, bool staged);
 // ---- check_trace.hip
 int check_trace_in_prove(Ctx* c, const AirInfo& air, const gl_t* d_trace, size_t n_rows, const uint64_t* pis, uint64_t** blob, size_t* words);
 // ---- ctx.hip

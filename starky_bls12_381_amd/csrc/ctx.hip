@@ -415,6 +415,8 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
     else if (k == "hasher" && value >= STARKHIP_HASHER_POSEIDON && value <= STARKHIP_HASHER_KECCAK) c->opt_hasher = value;
     else if (k == "check_trace" && (value == 0 || value == 1)) c->opt_check_trace = value;
     else if (k == "check_trace_list" && value >= 0 && value <= (long)STARKHIP_CHECK_LIST_MAX) c->opt_check_trace_list = value;
+    else if (k == "fill_lookups" && (value == 0 || value == 1)) c->opt_fill_lookups = value;
+    else if (k == "lookup_batch" && value >= 0 && value <= (long)STARKHIP_LOOKUPS_MAX) c->opt_lookup_batch = value;
     else return STARKHIP_ERR_BAD_SHAPE;
     return STARKHIP_OK;
 }
@@ -422,6 +424,7 @@ void ctx_set_check_trace(Ctx* c, bool on, size_t list_cap) {
     c->opt_check_trace = on;
     c->opt_check_trace_list = (long)std::min<size_t>(list_cap, STARKHIP_CHECK_LIST_MAX);
 }
+void ctx_set_fill_lookups(Ctx* c, bool on) { c->opt_fill_lookups = on; }
 void ctx_set_hasher(Ctx* c, int hasher) { c->opt_hasher = hasher; }
 void ctx_check_stats(Ctx* c, uint64_t out[2]) {
     out[0] = c->traces_checked.load();
@@ -486,22 +489,24 @@ int upload_dense(Ctx* c, const TraceInput& in, gl_t* dst, const gl_t** d_values)
     return 0;
 }
 
-// The sorted (key, idx) items of ONE set on the context (c->mset.keys / idx / table; kernels_multiset.h has the kernels).  reserve: room
-// for a set of `items`: each of keys and idx is the sort's two buffers, the digit table is followed by its chunk sums.  run: the keys of
-// the 2 n items of `desc` over `cols` under `seed` (launch_multiset_keys) and their stable sort, enqueued on the context's stream; *keys
-// and *idx are where the sorted items lie.
-int sorted_items_reserve(Ctx* c, size_t items) {
-    HIPCHK(c->mset.keys.ensure(2 * items * 8));
-    HIPCHK(c->mset.idx.ensure(2 * items * 4));
-    HIPCHK(c->mset.table.ensure((multiset_table_words(items) + multiset_scan_chunks(items)) * 4));
+// The sorted (key, idx) items of `sets` sets of equal size on the context (c->mset.keys / idx / table; kernels_multiset.h has the kernels
+// and how the sets lie strided in them).  reserve: room for sets of `items` each: each of keys and idx is the sort's two buffers, the
+// digit tables are followed by their chunk sums.  run: the keys of the 2 n items of each set -- set y's descriptor at desc + y *
+// desc_stride -- over `cols` under `seed` (launch_multiset_keys_batch) and their stable sort, enqueued on the context's stream; *keys
+// and *idx are where the sorted items of set 0 lie, set y's 2 n items further each.  One set is what the permutation check takes.
+int sorted_items_reserve(Ctx* c, size_t items, size_t sets) {
+    HIPCHK(c->mset.keys.ensure(2 * sets * items * 8));
+    HIPCHK(c->mset.idx.ensure(2 * sets * items * 4));
+    HIPCHK(c->mset.table.ensure(sets * (multiset_table_words(items) + multiset_scan_chunks(items)) * 4));
     return 0;
 }
-int sorted_items_run(Ctx* c, const uint32_t* desc, const gl_t* cols, size_t stride, size_t n, gl_t seed, const gl_t** keys, const uint32_t** idx) {
+int sorted_items_run(Ctx* c, const uint32_t* desc, const gl_t* cols, size_t stride, size_t n, gl_t seed, const gl_t** keys, const uint32_t** idx, size_t sets,
+                     uint32_t desc_stride) {
     const size_t items = 2 * n;
     gl_t* k = c->mset.keys.as<gl_t>();
     uint32_t *i = c->mset.idx.as<uint32_t>(), *table = c->mset.table.as<uint32_t>();
-    HIPCHK(launch_multiset_keys(desc, cols, stride, n, seed, k, i, c->st));
-    HIPCHK(launch_multiset_sort(k, i, k + items, i + items, items, table, table + multiset_table_words(items), c->st));
+    HIPCHK(launch_multiset_keys_batch(desc, desc_stride, sets, cols, stride, n, seed, k, i, c->st));
+    HIPCHK(launch_multiset_sort_batch(k, i, k + sets * items, i + sets * items, items, sets, table, table + sets * multiset_table_words(items), c->st));
     *keys = k, *idx = i;
     return 0;
 }

@@ -73,6 +73,7 @@ void ctx_hash_request_reset(Ctx* c) { c->hash_requested = false; }
 bool ctx_hash_requested(Ctx* c) { return c->hash_requested; }
 int ctx_set_urgent(Ctx* c, bool urgent) { c->urgent = urgent; return STARKHIP_OK; }
 void ctx_set_check_trace(Ctx* c, bool on, size_t) { c->check_trace = on; }  // the pretended check finds every trace satisfying
+void ctx_set_fill_lookups(Ctx*, bool) {}  // the pretended proof fills nothing
 void ctx_set_hasher(Ctx*, int) {}
 void ctx_check_stats(Ctx* c, uint64_t out[2]) { out[0] = c->traces_checked.load(); out[1] = 0; }
 int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t&, size_t, unsigned proof_blobs, bool) {

@@ -19,6 +19,12 @@
 // No workgroup waits for another inside a launch and no global atomic decides where anything lands: every destination is a function
 // of the sorted order alone, so the columns are the same bytes on every run.  Every index is bounded by the item count the launch
 // is given.
+//
+// Every launch has a batch dimension: grid.y = a lookup of the batch, whose buffers lie strided by lookup -- its sorted items at keys /
+// idx + y * 2 n (the sort's own stride), flags + y * 2 n, sums + y * 3 tiles, slot + y * n, its mask at mask + y * (n + 63) / 64 and
+// its missing count at missing[y].  Nothing of one lookup reads or writes anything of another, so what holds for one launch holds
+// for the batch; a batch of one is the launch it was.  The placements find their two output columns in out_cols[y] and, given a
+// gate, leave a lookup alone whose gate[y] is not zero: its missing count, so a failed lookup keeps its columns.
 #include <hip/hip_runtime.h>
 
 #include "block_scan.h"
@@ -63,21 +69,28 @@ __device__ __forceinline__ void lk_tile_ranks(const uint32_t f[TILE_ROUNDS], uin
     }
 }
 
-__global__ __launch_bounds__(TILE_BLOCK) void lookup_gather_kernel(const gl_t* __restrict__ trace, size_t n_cols, uint32_t n, uint32_t col_input, uint32_t col_table,
+// desc: per lookup of the batch {1, input, table}; out: [batch][4][n], of which this fills the first two columns
+__global__ __launch_bounds__(TILE_BLOCK) void lookup_gather_kernel(const gl_t* __restrict__ trace, size_t n_cols, uint32_t n, const uint32_t* __restrict__ desc,
                                                                    gl_t* __restrict__ out) { STARKHIP_PRIO_ENTRY
     const uint32_t i = blockIdx.x * TILE_BLOCK + threadIdx.x;
     if (i >= 2 * n) return;
     const uint32_t side = i >= n, row = i - side * n;
-    out[i] = trace[(size_t)row * n_cols + (side ? col_table : col_input)];
+    out[(size_t)blockIdx.y * 4 * n + i] = trace[(size_t)row * n_cols + desc[3 * blockIdx.y + 1 + side]];
 }
 
-// grid: tiles
+// grid: tiles x lookups
 __global__ __launch_bounds__(TILE_BLOCK) void lookup_mark_kernel(const gl_t* __restrict__ keys, const uint32_t* __restrict__ idx, uint32_t n, uint8_t* __restrict__ flags,
                                                                  uint32_t* __restrict__ sums, uint32_t tiles, unsigned long long* __restrict__ mask,
                                                                  unsigned long long* __restrict__ missing) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t cnt[3][TILE_SLOTS];
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t items = 2 * n, base = blockIdx.x * LOOKUP_TILE;
+    keys += (size_t)blockIdx.y * items;
+    idx += (size_t)blockIdx.y * items;
+    flags += (size_t)blockIdx.y * items;
+    sums += (size_t)blockIdx.y * 3 * tiles;
+    mask += (size_t)blockIdx.y * ((n + 63) / 64);
+    missing += blockIdx.y;
     uint32_t f[TILE_ROUNDS];
 #pragma unroll
     for (unsigned r = 0; r < TILE_ROUNDS; r++) {
@@ -105,10 +118,10 @@ __global__ __launch_bounds__(TILE_BLOCK) void lookup_mark_kernel(const gl_t* __r
     if (threadIdx.x < 3) sums[(size_t)threadIdx.x * tiles + blockIdx.x] = threadIdx.x == 0 ? total.c[0] : threadIdx.x == 1 ? total.c[1] : total.c[2];
 }
 
-// grid: 3, one workgroup per row of sums
+// grid: 3 x lookups, one workgroup per row of sums
 __global__ __launch_bounds__(TILE_BLOCK) void lookup_scan_kernel(uint32_t* __restrict__ sums, uint32_t tiles) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t lds[TILE_WAVES];
-    uint32_t* row = sums + (size_t)blockIdx.x * tiles;
+    uint32_t* row = sums + ((size_t)blockIdx.y * 3 + blockIdx.x) * tiles;
     uint32_t carry = 0;
     for (uint32_t at = 0; at < tiles; at += TILE_BLOCK) {  // the same trip count on every lane
         const uint32_t j = at + threadIdx.x;
@@ -120,13 +133,24 @@ __global__ __launch_bounds__(TILE_BLOCK) void lookup_scan_kernel(uint32_t* __res
     }
 }
 
-// sums: scanned.  grid: tiles
+// Where the placements write: element r of column c is base[c * col_stride + r * row_stride]
+struct LkOut { gl_t* base; size_t col_stride, row_stride; };
+
+// sums: scanned.  out_cols: per lookup {permuted_input, permuted_table}.  grid: tiles x lookups
 __global__ __launch_bounds__(TILE_BLOCK) void lookup_place_inputs_kernel(const gl_t* __restrict__ keys, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sums,
-                                                                         uint32_t tiles, uint32_t n, gl_t* permuted_input, gl_t* permuted_table, size_t stride,
-                                                                         uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
+                                                                         uint32_t tiles, uint32_t n, LkOut out, const uint32_t* __restrict__ out_cols,
+                                                                         const unsigned long long* __restrict__ gate, uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t cnt[3][TILE_SLOTS];
+    if (gate && gate[blockIdx.y]) return;  // the same for every lane of the workgroup
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t items = 2 * n, base = blockIdx.x * LOOKUP_TILE;
+    keys += (size_t)blockIdx.y * items;
+    flags += (size_t)blockIdx.y * items;
+    sums += (size_t)blockIdx.y * 3 * tiles;
+    slot += (size_t)blockIdx.y * n;
+    const size_t stride = out.row_stride;
+    gl_t* permuted_input = out.base + out_cols[2 * blockIdx.y] * out.col_stride;
+    gl_t* permuted_table = out.base + out_cols[2 * blockIdx.y + 1] * out.col_stride;
     uint32_t f[TILE_ROUNDS];
 #pragma unroll
     for (unsigned r = 0; r < TILE_ROUNDS; r++) {
@@ -152,13 +176,20 @@ __global__ __launch_bounds__(TILE_BLOCK) void lookup_place_inputs_kernel(const g
     }
 }
 
-// sums: scanned; slot: as lookup_place_inputs_kernel left it.  grid: tiles
+// sums: scanned; slot: as lookup_place_inputs_kernel left it.  grid: tiles x lookups
 __global__ __launch_bounds__(TILE_BLOCK) void lookup_place_table_kernel(const gl_t* __restrict__ keys, const uint8_t* __restrict__ flags, const uint32_t* __restrict__ sums,
-                                                                        uint32_t tiles, uint32_t n, gl_t* permuted_table, size_t stride,
-                                                                        const uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
+                                                                        uint32_t tiles, uint32_t n, LkOut out, const uint32_t* __restrict__ out_cols,
+                                                                        const unsigned long long* __restrict__ gate, const uint32_t* __restrict__ slot) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t cnt[3][TILE_SLOTS];
+    if (gate && gate[blockIdx.y]) return;  // the same for every lane of the workgroup
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const uint32_t items = 2 * n, base = blockIdx.x * LOOKUP_TILE;
+    keys += (size_t)blockIdx.y * items;
+    flags += (size_t)blockIdx.y * items;
+    sums += (size_t)blockIdx.y * 3 * tiles;
+    slot += (size_t)blockIdx.y * n;
+    const size_t stride = out.row_stride;
+    gl_t* permuted_table = out.base + out_cols[2 * blockIdx.y + 1] * out.col_stride;
     uint32_t f[TILE_ROUNDS];
 #pragma unroll
     for (unsigned r = 0; r < TILE_ROUNDS; r++) {
@@ -179,35 +210,30 @@ __global__ __launch_bounds__(TILE_BLOCK) void lookup_place_table_kernel(const gl
     }
 }
 
-hipError_t launch_lookup_gather(const gl_t* trace, size_t n_cols, size_t n, uint32_t col_input, uint32_t col_table, gl_t* out, hipStream_t st) {
-    hipLaunchKernelGGL(lookup_gather_kernel, dim3(nb(2 * n, TILE_BLOCK)), dim3(TILE_BLOCK), 0, st, trace, n_cols, (uint32_t)n, col_input, col_table, out);
+hipError_t launch_lookup_gather(const gl_t* trace, size_t n_cols, size_t n, const uint32_t* desc, size_t batch, gl_t* out, hipStream_t st) {
+    hipLaunchKernelGGL(lookup_gather_kernel, dim3(nb(2 * n, TILE_BLOCK), (unsigned)batch), dim3(TILE_BLOCK), 0, st, trace, n_cols, (uint32_t)n, desc, out);
     return hipGetLastError();
 }
 
-hipError_t launch_lookup_mark(const gl_t* keys, const uint32_t* idx, size_t n, uint8_t* flags, uint32_t* sums, unsigned long long* mask,
+hipError_t launch_lookup_mark(const gl_t* keys, const uint32_t* idx, size_t n, size_t batch, uint8_t* flags, uint32_t* sums, unsigned long long* mask,
                               unsigned long long* missing, hipStream_t st) {
     const uint32_t tiles = (uint32_t)lookup_tiles(2 * n);
-    hipLaunchKernelGGL(lookup_mark_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, idx, (uint32_t)n, flags, sums, tiles, mask, missing);
+    hipLaunchKernelGGL(lookup_mark_kernel, dim3(tiles, (unsigned)batch), dim3(TILE_BLOCK), 0, st, keys, idx, (uint32_t)n, flags, sums, tiles, mask, missing);
     return hipGetLastError();
 }
 
-hipError_t launch_lookup_scan(uint32_t* sums, size_t n, hipStream_t st) {
-    hipLaunchKernelGGL(lookup_scan_kernel, dim3(3), dim3(TILE_BLOCK), 0, st, sums, (uint32_t)lookup_tiles(2 * n));
+hipError_t launch_lookup_scan(uint32_t* sums, size_t n, size_t batch, hipStream_t st) {
+    hipLaunchKernelGGL(lookup_scan_kernel, dim3(3, (unsigned)batch), dim3(TILE_BLOCK), 0, st, sums, (uint32_t)lookup_tiles(2 * n));
     return hipGetLastError();
 }
 
-hipError_t launch_lookup_place_inputs(const gl_t* keys, const uint8_t* flags, const uint32_t* sums, size_t n, gl_t* permuted_input, gl_t* permuted_table,
-                                      size_t stride, uint32_t* slot, hipStream_t st) {
+hipError_t launch_lookup_place(const gl_t* keys, const uint8_t* flags, const uint32_t* sums, size_t n, size_t batch, const LookupOut& out, const uint32_t* out_cols,
+                               const unsigned long long* gate, uint32_t* slot, hipStream_t st) {
     const uint32_t tiles = (uint32_t)lookup_tiles(2 * n);
-    hipLaunchKernelGGL(lookup_place_inputs_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, permuted_input, permuted_table, stride,
-                       slot);
-    return hipGetLastError();
-}
-
-hipError_t launch_lookup_place_table(const gl_t* keys, const uint8_t* flags, const uint32_t* sums, size_t n, gl_t* permuted_table, size_t stride,
-                                     const uint32_t* slot, hipStream_t st) {
-    const uint32_t tiles = (uint32_t)lookup_tiles(2 * n);
-    hipLaunchKernelGGL(lookup_place_table_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, permuted_table, stride, slot);
+    const LkOut o = {out.base, out.col_stride, out.row_stride};
+    hipLaunchKernelGGL(lookup_place_inputs_kernel, dim3(tiles, (unsigned)batch), dim3(TILE_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, o, out_cols, gate, slot);
+    hipLaunchKernelGGL(lookup_place_table_kernel, dim3(tiles, (unsigned)batch), dim3(TILE_BLOCK), 0, st, keys, flags, sums, tiles, (uint32_t)n, o, out_cols, gate,
+                       (const uint32_t*)slot);
     return hipGetLastError();
 }
 

@@ -24,6 +24,13 @@ hipError_t launch_multiset_keys(const uint32_t* pair, const gl_t* cols, size_t s
 // Stable ascending sort of (key, idx) by key: eight passes of 8-bit digits between (keys, idx) and (keys_alt, idx_alt); the result is
 // back in (keys, idx).  table: multiset_table_words(items) uint32, sums: multiset_scan_chunks(items) uint32.
 hipError_t launch_multiset_sort(gl_t* keys, uint32_t* idx, gl_t* keys_alt, uint32_t* idx_alt, size_t items, uint32_t* table, uint32_t* sums, hipStream_t st);
+// The same for `sets` sets of 2 n items each in one set of launches (grid.y = set): set y has its descriptor at pair + y * pair_stride,
+// its items at keys / idx / keys_alt / idx_alt + y * items, its table at table + y * multiset_table_words(items) and its chunk sums at
+// sums + y * multiset_scan_chunks(items).  One set is the launch above.
+hipError_t launch_multiset_keys_batch(const uint32_t* pair, uint32_t pair_stride, size_t sets, const gl_t* cols, size_t stride, size_t n, gl_t seed, gl_t* keys,
+                                      uint32_t* idx, hipStream_t st);
+hipError_t launch_multiset_sort_batch(gl_t* keys, uint32_t* idx, gl_t* keys_alt, uint32_t* idx_alt, size_t items, size_t sets, uint32_t* table, uint32_t* sums,
+                                      hipStream_t st);
 // Over the sorted items: masks [2][(n + 63) / 64] |= the unmatched rows of each side (zeroed by the caller), counters[0] += the items
 // whose key equals their predecessor's while their tuple does not (zeroed by the caller).
 hipError_t launch_multiset_classify(const uint32_t* pair, const gl_t* cols, size_t stride, size_t n, const gl_t* keys, const uint32_t* idx,

@@ -50,11 +50,15 @@ __device__ __forceinline__ unsigned long long ms_match(unsigned d, bool valid) {
     return m;
 }
 
-// pair: n_entries, then n_entries x (lhs, rhs) columns of `cols`
-__global__ __launch_bounds__(TILE_BLOCK) void multiset_keys_kernel(const uint32_t* __restrict__ pair, const gl_t* __restrict__ cols, size_t stride, uint32_t n,
-                                                                   gl_t seed, gl_t* __restrict__ keys, uint32_t* __restrict__ idx) { STARKHIP_PRIO_ENTRY
+// pair: n_entries, then n_entries x (lhs, rhs) columns of `cols`.  grid.y: the sets of a batch -- set y has its descriptor at
+// pair + y * pair_stride and its items at keys / idx + y * 2 n (every kernel of the sort strides by the set's item count alike)
+__global__ __launch_bounds__(TILE_BLOCK) void multiset_keys_kernel(const uint32_t* __restrict__ pair, uint32_t pair_stride, const gl_t* __restrict__ cols, size_t stride,
+                                                                   uint32_t n, gl_t seed, gl_t* __restrict__ keys, uint32_t* __restrict__ idx) { STARKHIP_PRIO_ENTRY
     const uint32_t i = blockIdx.x * TILE_BLOCK + threadIdx.x;
     if (i >= 2 * n) return;
+    pair += (size_t)blockIdx.y * pair_stride;
+    keys += (size_t)blockIdx.y * 2 * n;
+    idx += (size_t)blockIdx.y * 2 * n;
     const uint32_t side = i >= n, row = i - side * n, ne = pair[0];
     gl_t key = 0, pw = 1;
     for (uint32_t e = 0; e < ne; e++) {
@@ -66,10 +70,12 @@ __global__ __launch_bounds__(TILE_BLOCK) void multiset_keys_kernel(const uint32_
     idx[i] = i;
 }
 
-// table[digit][tile] = the tile's items of that digit.  grid: tiles
+// table[digit][tile] = the tile's items of that digit.  grid: tiles x sets, set y with its own table of 256 tiles words
 __global__ __launch_bounds__(TILE_BLOCK) void multiset_histogram_kernel(const gl_t* __restrict__ keys, uint32_t items, unsigned shift, uint32_t* __restrict__ table,
                                                                         uint32_t tiles) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t hist[256];
+    keys += (size_t)blockIdx.y * items;
+    table += (size_t)blockIdx.y * 256 * tiles;
     const unsigned lane = threadIdx.x & 63u;
     hist[threadIdx.x] = 0;
     __syncthreads();
@@ -86,9 +92,11 @@ __global__ __launch_bounds__(TILE_BLOCK) void multiset_histogram_kernel(const gl
     table[(size_t)threadIdx.x * tiles + blockIdx.x] = hist[threadIdx.x];
 }
 
-// sums[chunk] = the sum of the chunk's words.  grid: chunks
+// sums[chunk] = the sum of the chunk's words.  grid: chunks x sets, set y with its own `words` of table and gridDim.x of sums
 __global__ __launch_bounds__(TILE_BLOCK) void multiset_scan_sums_kernel(const uint32_t* __restrict__ table, uint32_t words, uint32_t* __restrict__ sums) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t lds[TILE_WAVES];
+    table += (size_t)blockIdx.y * words;
+    sums += (size_t)blockIdx.y * gridDim.x;
     const uint32_t base = blockIdx.x * MULTISET_SCAN_CHUNK;
     uint32_t s = 0;
 #pragma unroll
@@ -101,9 +109,11 @@ __global__ __launch_bounds__(TILE_BLOCK) void multiset_scan_sums_kernel(const ui
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
-// table[j] <- the sum of table[0 .. j), chunk by chunk: each lane a run of MS_SCAN_ITEMS consecutive words.  grid: chunks
+// table[j] <- the sum of table[0 .. j), chunk by chunk: each lane a run of MS_SCAN_ITEMS consecutive words.  grid: chunks x sets
 __global__ __launch_bounds__(TILE_BLOCK) void multiset_scan_apply_kernel(uint32_t* __restrict__ table, uint32_t words, const uint32_t* __restrict__ sums) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t lds[TILE_WAVES];
+    table += (size_t)blockIdx.y * words;
+    sums += (size_t)blockIdx.y * gridDim.x;
     uint32_t s = 0, carry;
     for (uint32_t j = threadIdx.x; j < blockIdx.x; j += TILE_BLOCK) s += sums[j];
     (void)block_scan(s, ScanAdd(), 0u, lds, &carry);
@@ -124,12 +134,17 @@ __global__ __launch_bounds__(TILE_BLOCK) void multiset_scan_apply_kernel(uint32_
     }
 }
 
-// table: scanned.  grid: tiles
+// table: scanned.  grid: tiles x sets
 __global__ __launch_bounds__(TILE_BLOCK) void multiset_scatter_kernel(const gl_t* __restrict__ keys_in, const uint32_t* __restrict__ idx_in, gl_t* __restrict__ keys_out,
                                                                       uint32_t* __restrict__ idx_out, uint32_t items, unsigned shift,
                                                                       const uint32_t* __restrict__ table, uint32_t tiles) { STARKHIP_PRIO_ENTRY
     __shared__ uint32_t cnt[TILE_SLOTS][256];  // the slot's items of each digit, then where the slot's first item of the digit lands
     const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    {
+        const size_t at = (size_t)blockIdx.y * items;
+        keys_in += at, idx_in += at, keys_out += at, idx_out += at;
+        table += (size_t)blockIdx.y * 256 * tiles;
+    }
 #pragma unroll
     for (unsigned s = 0; s < TILE_SLOTS; s++) cnt[s][threadIdx.x] = 0;
     __syncthreads();
@@ -225,23 +240,35 @@ __global__ __launch_bounds__(TILE_BLOCK) void multiset_count_kernel(const unsign
     }
 }
 
-hipError_t launch_multiset_keys(const uint32_t* pair, const gl_t* cols, size_t stride, size_t n, gl_t seed, gl_t* keys, uint32_t* idx, hipStream_t st) {
-    hipLaunchKernelGGL(multiset_keys_kernel, dim3(nb(2 * n, TILE_BLOCK)), dim3(TILE_BLOCK), 0, st, pair, cols, stride, (uint32_t)n, seed, keys, idx);
+hipError_t launch_multiset_keys_batch(const uint32_t* pair, uint32_t pair_stride, size_t sets, const gl_t* cols, size_t stride, size_t n, gl_t seed, gl_t* keys,
+                                      uint32_t* idx, hipStream_t st) {
+    hipLaunchKernelGGL(multiset_keys_kernel, dim3(nb(2 * n, TILE_BLOCK), (unsigned)sets), dim3(TILE_BLOCK), 0, st, pair, pair_stride, cols, stride, (uint32_t)n, seed,
+                       keys, idx);
     return hipGetLastError();
 }
 
-hipError_t launch_multiset_sort(gl_t* keys, uint32_t* idx, gl_t* keys_alt, uint32_t* idx_alt, size_t items, uint32_t* table, uint32_t* sums, hipStream_t st) {
+hipError_t launch_multiset_keys(const uint32_t* pair, const gl_t* cols, size_t stride, size_t n, gl_t seed, gl_t* keys, uint32_t* idx, hipStream_t st) {
+    return launch_multiset_keys_batch(pair, 0, 1, cols, stride, n, seed, keys, idx, st);
+}
+
+hipError_t launch_multiset_sort_batch(gl_t* keys, uint32_t* idx, gl_t* keys_alt, uint32_t* idx_alt, size_t items, size_t sets, uint32_t* table, uint32_t* sums,
+                                      hipStream_t st) {
     const uint32_t tiles = (uint32_t)multiset_tiles(items), words = (uint32_t)multiset_table_words(items), chunks = (uint32_t)multiset_scan_chunks(items);
+    const unsigned G = (unsigned)sets;
     for (unsigned pass = 0; pass < 8; pass++) {
         const unsigned shift = 8 * pass;
-        hipLaunchKernelGGL(multiset_histogram_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, (uint32_t)items, shift, table, tiles);
-        if (chunks > 1) hipLaunchKernelGGL(multiset_scan_sums_kernel, dim3(chunks), dim3(TILE_BLOCK), 0, st, table, words, sums);  // (chunk 0 reads no sum)
-        hipLaunchKernelGGL(multiset_scan_apply_kernel, dim3(chunks), dim3(TILE_BLOCK), 0, st, table, words, sums);
-        hipLaunchKernelGGL(multiset_scatter_kernel, dim3(tiles), dim3(TILE_BLOCK), 0, st, keys, idx, keys_alt, idx_alt, (uint32_t)items, shift, table, tiles);
+        hipLaunchKernelGGL(multiset_histogram_kernel, dim3(tiles, G), dim3(TILE_BLOCK), 0, st, keys, (uint32_t)items, shift, table, tiles);
+        if (chunks > 1) hipLaunchKernelGGL(multiset_scan_sums_kernel, dim3(chunks, G), dim3(TILE_BLOCK), 0, st, table, words, sums);  // (chunk 0 reads no sum)
+        hipLaunchKernelGGL(multiset_scan_apply_kernel, dim3(chunks, G), dim3(TILE_BLOCK), 0, st, table, words, sums);
+        hipLaunchKernelGGL(multiset_scatter_kernel, dim3(tiles, G), dim3(TILE_BLOCK), 0, st, keys, idx, keys_alt, idx_alt, (uint32_t)items, shift, table, tiles);
         std::swap(keys, keys_alt);
         std::swap(idx, idx_alt);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_multiset_sort(gl_t* keys, uint32_t* idx, gl_t* keys_alt, uint32_t* idx_alt, size_t items, uint32_t* table, uint32_t* sums, hipStream_t st) {
+    return launch_multiset_sort_batch(keys, idx, keys_alt, idx_alt, items, 1, table, sums, st);
 }
 
 hipError_t launch_multiset_classify(const uint32_t* pair, const gl_t* cols, size_t stride, size_t n, const gl_t* keys, const uint32_t* idx,

@@ -24,6 +24,8 @@ bool ctx_has_hash_service(Ctx* c);
 int ctx_set_urgent(Ctx* c, bool urgent);
 // "check_trace" and "check_trace_list" of the context's next proofs, as a pool sets them per job; {traces checked, traces rejected} so far
 void ctx_set_check_trace(Ctx* c, bool on, size_t list_cap);
+// "fill_lookups" of the context's next proofs, as a pool sets it per job
+void ctx_set_fill_lookups(Ctx* c, bool on);
 void ctx_set_hasher(Ctx* c, int hasher);  // the "hasher" option of the context's next proofs, as a pool sets it per job
 void ctx_check_stats(Ctx* c, uint64_t out[2]);
 // tables, plan, work buffers, upload staging and `proof_blobs` page-locked proof blobs (blob_arena.h) for proofs of `air`,
