@@ -662,27 +662,22 @@ int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_pr
     out->n_columns = pl.C; out->n_quotient_polys = pl.Q; out->degree_bits = pl.log_n; out->rate_bits = pl.rate_bits;
     out->cap_height = pl.cap_h; out->n_fri_layers = pl.L; out->n_query_rounds = pl.n_queries; out->final_poly_len = pl.final_len;
     out->n_public_inputs = pl.n_pis; out->arity_bits = pl.arity_bits;
-    out->off_trace_cap = pl.off_trace_cap; out->off_quotient_cap = pl.off_quot_cap; out->off_local_values = pl.off_local;
-    out->off_next_values = pl.off_next; out->off_quotient_openings = pl.off_quot_open; out->off_fri_caps = pl.off_fri_caps;
+    const MatrixLayout &t = pl.mat[0], z = pl.n_mats == 3 ? pl.mat[1] : MatrixLayout(), &q = pl.quotient();  // (z: all 0 for a proof without Zs)
+    out->off_trace_cap = t.off_cap; out->off_quotient_cap = q.off_cap; out->off_local_values = t.off_open[0];
+    out->off_next_values = t.off_open[1]; out->off_quotient_openings = q.off_open[0]; out->off_fri_caps = pl.off_fri_caps;
     out->off_query_rounds = pl.off_queries; out->query_round_words = pl.query_words; out->off_final_poly = pl.off_final;
     out->off_pow_witness = pl.off_pow; out->off_public_inputs = pl.off_pis; out->total_words = pl.total;
     const size_t d0 = pl.log_N - pl.cap_h;
-    size_t o = 0;
-    out->q_trace_leaf = o; o += pl.C;
-    out->q_trace_siblings = o; o += 4 * d0;
-    o += pl.nZ ? pl.nZ + 4 * d0 : 0;  // the Z leaf and its siblings (below)
-    out->q_quotient_leaf = o; o += pl.Q;
-    out->q_quotient_siblings = o; o += 4 * d0;
+    out->q_trace_leaf = t.q_leaf; out->q_trace_siblings = t.q_sib; out->q_quotient_leaf = q.q_leaf; out->q_quotient_siblings = q.q_sib;
+    out->n_permutation_zs = z.cols; out->off_permutation_zs_cap = z.off_cap; out->off_permutation_zs = z.off_open[0];
+    out->off_permutation_zs_next = z.off_open[1]; out->q_permutation_zs_leaf = z.q_leaf; out->q_permutation_zs_siblings = z.q_sib;
+    size_t o = q.q_sib + 4 * d0;
     for (size_t l = 0; l < pl.L && l < 16; l++) {
         out->q_step_evals[l] = o; o += 2 * ((size_t)1 << pl.arity_bits);
         out->q_step_siblings[l] = o; o += 4 * pl.layer_depth[l];
         out->step_sibling_count[l] = pl.layer_depth[l];
     }
     out->initial_sibling_count = d0;
-    if (pl.nZ) {
-        out->n_permutation_zs = pl.nZ; out->off_permutation_zs_cap = pl.off_zs_cap; out->off_permutation_zs = pl.off_zs;
-        out->off_permutation_zs_next = pl.off_zs_next; out->q_permutation_zs_leaf = pl.C + 4 * d0; out->q_permutation_zs_siblings = pl.C + 4 * d0 + pl.nZ;
-    }
     return STARKHIP_OK;
 }
 

@@ -53,16 +53,25 @@ inline unsigned quotient_degree_bits(unsigned degree) {
     return qdb;
 }
 
+// One matrix of polynomials a proof commits -- in proof order the trace, the permutation Zs of an AIR with pairs, the quotient -- and where its words are.  A proof
+// treats them alike (a cap in the transcript, openings, a run of powers of the FRI alpha, a leaf and a path per query round), so the prover and both verifiers walk ProofLayout::mat.
+struct MatrixLayout {
+    size_t cols, off_cap;           // polynomials (a leaf's words), and its cap [2^cap_h][4]
+    size_t n_open[2], off_open[2];  // how many are opened at zeta (all) and at g zeta (all, or none: the quotient), 2 words each, and where
+    size_t q_leaf, q_sib;           // inside a query round: its leaf, its log N - cap_h siblings of 4 words
+};
+
 struct ProofLayout {
     size_t C, Q, log_n, rate_bits, cap_h, L, n_queries, final_len, n_pis, arity_bits, n_challenges;
     size_t hasher = 0;  // header word 12: STARKHIP_HASHER_POSEIDON (0, what the word has always been) or STARKHIP_HASHER_KECCAK
     size_t nZ = 0;      // header word 13: permutation Z polynomials (0, what the word has always been, for an AIR without pairs)
     size_t ncap;     // 2^cap_h
     size_t log_N;
-    // offsets (in words)
-    size_t off_trace_cap, off_quot_cap, off_local, off_next, off_quot_open, off_fri_caps, off_queries, query_words, off_final,
-        off_pow, off_pis, total;
-    size_t off_zs_cap = 0, off_zs = 0, off_zs_next = 0;  // nZ > 0 only: the Z cap after the trace cap, the Z openings after next_values
+    MatrixLayout mat[3];  // the committed matrices, n_mats of them: trace, Zs if nZ > 0, quotient (the last)
+    size_t n_mats = 0;
+    size_t batch_cols[2];  // polynomials opened at zeta (all) and at g zeta: the lengths of the two FRI batches
+    // offsets (in words) of what follows the matrices' caps and openings
+    size_t off_fri_caps, off_queries, query_words, off_final, off_pow, off_pis, total;
     std::vector<size_t> layer_depth;  // siblings per FRI layer
 
     // the layout of a proof of AIR program `P` with 2^log_n rows under `cfg` (`geo`: FriGeometry::make(cfg, log_n))
@@ -76,30 +85,37 @@ struct ProofLayout {
         pl.compute();
         return pl;
     }
+    const MatrixLayout& quotient() const { return mat[n_mats - 1]; }
     void compute() {
         ncap = (size_t)1 << cap_h;
         log_N = log_n + rate_bits;
-        size_t o = 16;
-        off_trace_cap = o; o += 4 * ncap;
-        off_zs_cap = nZ ? o : 0; o += nZ ? 4 * ncap : 0;
-        off_quot_cap = o; o += 4 * ncap;
-        off_local = o; o += 2 * C;
-        off_next = o; o += 2 * C;
-        off_zs = nZ ? o : 0; o += 2 * nZ;
-        off_zs_next = nZ ? o : 0; o += 2 * nZ;
-        off_quot_open = o; o += 2 * Q;
+        const size_t d0 = log_N - cap_h;
+        n_mats = nZ ? 3 : 2;
+        mat[0].cols = C; mat[1].cols = nZ; mat[n_mats - 1].cols = Q;
+        size_t o = 16 + n_mats * 4 * ncap, q = 0;  // the caps back to back, then the openings matrix by matrix
+        batch_cols[0] = batch_cols[1] = 0;
+        for (size_t k = 0; k < n_mats; k++) {
+            MatrixLayout& m = mat[k];
+            m.off_cap = 16 + k * 4 * ncap;
+            for (size_t b = 0; b < 2; b++) {
+                m.n_open[b] = b == 0 || k + 1 < n_mats ? m.cols : 0;  // at g zeta: all but the quotient
+                m.off_open[b] = o; o += 2 * m.n_open[b];
+                batch_cols[b] += m.n_open[b];
+            }
+            m.q_leaf = q; q += m.cols;
+            m.q_sib = q; q += 4 * d0;
+        }
         off_fri_caps = o; o += L * 4 * ncap;
         off_queries = o;
-        size_t d0 = log_N - cap_h;
-        query_words = C + 4 * d0 + (nZ ? nZ + 4 * d0 : 0) + Q + 4 * d0;  // the Z leaf and its siblings between the trace's and the quotient's
         layer_depth.clear();
         size_t lg = log_N;
         for (size_t l = 0; l < L; l++) {
             lg -= arity_bits;
             size_t d = lg - cap_h;
             layer_depth.push_back(d);
-            query_words += 2 * ((size_t)1 << arity_bits) + 4 * d;
+            q += 2 * ((size_t)1 << arity_bits) + 4 * d;
         }
+        query_words = q;
         o += n_queries * query_words;
         off_final = o; o += 2 * final_len;
         off_pow = o; o += 1;

@@ -2,8 +2,8 @@
 // /root/reference/src/aggregate_proof.rs:59-65 (and :105, :138, :169).  prove() follows the transcript of SURVEY.md App. A.5 as a list
 // of phases (the methods of ProveCall), sized and laid out by one ProofShape and one table of work buffers that ctx_reserve() shares;
 // every heavy step is one of the kernels in kernels_*.hip, the host only runs the Fiat-Shamir challenger, two length-n synthetic
-// divisions and the proof assembly.  An AIR with permutation pairs (COMPAT.md P1 - P8) has its Z polynomials made and committed at the
-// start of the quotient phase (ProveCall::permutation) and carried as a third matrix from there on.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
+// divisions and the proof assembly.  What a proof commits is a list of matrices in proof order (ProveCall::mats beside ProofLayout::mat): the trace, the Zs of an
+// AIR with permutation pairs (COMPAT.md P1 - P8; made and committed at the start of the quotient phase, ProveCall::permutation), the quotient.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
 // checkers' host halves check_trace.hip and permutation_check.hip, the kernel-level entry points of the tests kernel_entries.hip.
 #include <hip/hip_runtime.h>
 
@@ -117,7 +117,7 @@ struct ProofShape {
     }
 };
 
-// fri_combine_kernel sums the trace columns in chunks of this many, one partial sum per chunk (comb_partial)
+// fri_combine_kernel sums the columns of a matrix in chunks of this many, one partial sum per chunk (comb_partial)
 static const size_t COMB_PPC = 256;
 static size_t comb_chunks(size_t C) { return (C + COMB_PPC - 1) / COMB_PPC; }
 
@@ -140,8 +140,8 @@ static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n
         {&c->qdigests, digest_words(N) * 8},
         {&c->zpow, 2 * n * 16},  // powers of zeta (the quotient polynomials' openings), then the coset-0 weights of zeta
         {&c->gzpow, n * 16},     // the weights of g zeta
-        {&c->open_local, C * 16}, {&c->open_next, C * 16}, {&c->open_q, Q * 16}, {&c->ext_apow, (C + s.nZ + Q) * 16},
-        {&c->comb_partial, (comb_chunks(C) + (s.nZ ? 1 : 0)) * n * 16},  // (the Zs' sum is one more chunk)
+        {&c->open_local, C * 16}, {&c->open_next, C * 16}, {&c->open_q, Q * 16}, {&c->ext_apow, s.pl.batch_cols[0] * 16},
+        {&c->comb_partial, (comb_chunks(C) + s.pl.n_mats - 2) * n * 16},  // (the Zs' sum is one more chunk)
         {&c->comb_out, 2 * n * 16}, {&c->fri_coef, 2 * N * 8}, {&c->fri_vals, 2 * N * 8},
         {&c->scale_tab, N * 8}, {&c->pow_state, 12 * 8}, {&c->pow_best, 8}, {&c->qidx, nq * 4},
         {&c->gather_t, nq * s.pl.query_words * 8},  // every query round's leaves and Merkle paths, in proof layout
@@ -210,13 +210,22 @@ struct ProveCall {
     const gl_t* d_values = nullptr;  // where it is: d_trace, or the caller's own device memory
     Challenger ch;
     HostWatch fs, host_other;  // Fiat-Shamir hashing / other host arithmetic of this proof
-    std::vector<gl_t> trace_cap, quot_cap, quot_tail, fri_caps;
-    std::vector<gl2_t> op_local, op_next, op_q, final_poly;
-    // an AIR with permutation pairs: the challenges (B sets of 2 x {beta, gamma}), the two descriptors back to back (by copy slot, by
-    // trace column), the Z cap and the Z openings
-    std::vector<gl_t> perm_chal, zs_cap;
+    // The committed matrix that s.pl.mat[k] lays out (trace, Zs of an AIR with pairs, quotient): the context's own buffers (ctx.h),
+    // only pointed at, and the host vectors its cap's and its openings' read-backs land in.  (Without Zs the third record is unused.)
+    struct Committed {
+        DevBuf *lde, *digests;  // its LDE, column-major, and the Merkle tree over its bit-reversed rows
+        DevBuf* d_open[2];      // where the openings at zeta / at g zeta are computed
+        DevBuf* coef;           // null: opened from coset 0 of the LDE (trace, Zs); else from these coefficients (quotient)
+        std::vector<gl_t> cap;
+        std::vector<gl2_t> open[2];
+    } mats[3] = {{&c->lde, &c->digests, {&c->open_local, &c->open_next}},
+                 s.nZ ? Committed{&c->perm.zlde, &c->perm.zdigests, {&c->perm.open_z, &c->perm.open_zn}} : Committed{&c->qlde, &c->qdigests, {&c->open_q}, &c->qcoef},
+                 {&c->qlde, &c->qdigests, {&c->open_q}, &c->qcoef}};
+    std::vector<gl_t> quot_tail, fri_caps;
+    std::vector<gl2_t> final_poly;
+    // an AIR with permutation pairs: the challenges (B sets of 2 x {beta, gamma}), the two descriptors back to back (by copy slot, by trace column)
+    std::vector<gl_t> perm_chal;
     std::vector<uint32_t> perm_desc;
-    std::vector<gl2_t> op_z, op_zn;
     int permutation();
     gl_t alphas[2] = {0, 0};
     gl2_t zeta = gl2_zero();
@@ -225,8 +234,23 @@ struct ProveCall {
     int upload(), ifft_lde(), trace_merkle(), quotient(), quotient_commit(), openings(), fri_combine(), fri_commit(), pow(), queries();
     int upload_recording(const TraceLog* log), upload_column_table(const uint64_t* const* cols), leaf_hash_on_host();
     int run_quotient_tiles(unsigned debug_mode, gl_t* qvals_out, bool timed), run_quotient_ops(), compare_quotient_evaluators();
-    int run_quotient_classes();
+    int run_quotient_classes(), commit_cap(Committed& m), commit_narrow(Committed& m, size_t cols);
 };
+
+// The end of a commitment, above leaf digests the caller has enqueued: the Merkle levels under the context's hasher, and the cap's
+// read-back requested -- the caller's (or the next phase's) stream_wait completes it
+int ProveCall::commit_cap(Committed& m) {
+    HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, m.digests->as<gl_t>(), s.log_N, s.cap_h, st));
+    m.cap.resize(4 * s.ncap);
+    HIPCHK(read_back(c, m.cap.data(), m.digests->as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
+    return 0;
+}
+// A matrix of a few columns (the Zs, the quotient) from its LDE: the leaves under Keccak or in the quad form, then the above
+int ProveCall::commit_narrow(Committed& m, size_t cols) {
+    if (c->opt_hasher == STARKHIP_HASHER_KECCAK) HIPCHK(launch_leaf_hash_keccak(m.lde->as<gl_t>(), cols, s.log_n, s.r, m.digests->as<gl_t>(), st));
+    else HIPCHK(launch_leaf_hash_form(FORM_QUAD, m.lde->as<gl_t>(), cols, s.log_n, s.r, m.digests->as<gl_t>(), st));
+    return commit_cap(m);
+}
 
 // ---- phase 0: trace into column-major device memory (trace_rows_to_poly_values), by layout
 // compact trace: upload the generator's write log and expand it here
@@ -389,10 +413,7 @@ int ProveCall::trace_merkle() {
         HIPCHK(launch_leaf_hash_lone(c, c->lde.as<gl_t>(), s.C, s.log_n, s.r, c->digests.as<gl_t>(), st, &c->hash_timing.form, pf));
     }
     HIPCHK(hipEventRecord(c->kev[1], st));
-    HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, c->digests.as<gl_t>(), s.log_N, s.cap_h, st));
-    trace_cap.resize(4 * s.ncap);
-    HIPCHK(read_back(c, trace_cap.data(), c->digests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
-    return 0;
+    return commit_cap(mats[0]);
 }
 
 // The tiled evaluator (quotient_plan.h) with the context's current plan: per-proof weights of the plan's records, one pass over the
@@ -498,14 +519,10 @@ int ProveCall::permutation() {
     for (gl_t v : closing)
         if (v != 1) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
     HIPCHK(run_lde(c, pb.zvals.as<gl_t>(), lde_long_supported(s.log_n) ? pb.zcoef.as<gl_t>() : nullptr, pb.zlde.as<gl_t>(), nZ, s.log_n, s.r, 0));
-    if (c->opt_hasher == STARKHIP_HASHER_KECCAK) HIPCHK(launch_leaf_hash_keccak(pb.zlde.as<gl_t>(), nZ, s.log_n, s.r, pb.zdigests.as<gl_t>(), st));
-    else HIPCHK(launch_leaf_hash_form(FORM_QUAD, pb.zlde.as<gl_t>(), nZ, s.log_n, s.r, pb.zdigests.as<gl_t>(), st));
-    HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, pb.zdigests.as<gl_t>(), s.log_N, s.cap_h, st));
-    zs_cap.resize(4 * s.ncap);
-    HIPCHK(read_back(c, zs_cap.data(), pb.zdigests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
+    if (int rc = commit_narrow(mats[1], nZ)) return rc;
     HIPCHK(stream_wait(c));
     fs.start();
-    ch.observe_many(zs_cap.data(), zs_cap.size());
+    ch.observe_many(mats[1].cap.data(), mats[1].cap.size());
     fs.stop();
     return 0;
 }
@@ -515,7 +532,7 @@ int ProveCall::quotient() {
     const size_t n = s.n, size = s.size, factor = s.factor;
     HIPCHK(stream_wait(c));  // the trace cap
     fs.start();
-    ch.observe_many(trace_cap.data(), trace_cap.size());  // public inputs are NOT observed (App. A.5)
+    ch.observe_many(mats[0].cap.data(), mats[0].cap.size());  // public inputs are NOT observed (App. A.5)
     fs.stop();
     if (s.nZ)
         if (int rc = permutation()) return rc;
@@ -556,20 +573,15 @@ int ProveCall::quotient_commit() {
     for (gl_t v : quot_tail)
         if (v != 0) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
     HIPCHK(run_lde(c, c->qcoef.as<gl_t>(), nullptr, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, 1));
-    if (c->opt_hasher == STARKHIP_HASHER_KECCAK) HIPCHK(launch_leaf_hash_keccak(c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
-    else HIPCHK(launch_leaf_hash_form(FORM_QUAD, c->qlde.as<gl_t>(), s.Q, s.log_n, s.r, c->qdigests.as<gl_t>(), st));
-    HIPCHK(launch_merkle_levels_by((int)c->opt_hasher, c->qdigests.as<gl_t>(), s.log_N, s.cap_h, st));
-    quot_cap.resize(4 * s.ncap);
-    HIPCHK(read_back(c, quot_cap.data(), c->qdigests.as<gl_t>() + 4 * level_off(s.N, s.log_N - s.cap_h), 4 * s.ncap * 8, st));
-    return 0;
+    return commit_narrow(mats[s.pl.n_mats - 1], s.Q);
 }
 
 // ---- phase 5: openings (App. A.7)
 int ProveCall::openings() {
-    const size_t n = s.n, C = s.C, Q = s.Q, nZ = s.nZ;
+    const size_t n = s.n;
     HIPCHK(stream_wait(c));  // the quotient cap
     fs.start();
-    ch.observe_many(quot_cap.data(), quot_cap.size());
+    ch.observe_many(mats[s.pl.n_mats - 1].cap.data(), 4 * s.ncap);
     zeta = ch.get_ext();
     fs.stop();
     if (c->opt_zeta_on_coset > 0)  // test hook ("zeta_on_coset" = k + 1): zeta = 7 w_n^k, a point of coset 0 itself (probability 2^-115 in a real transcript)
@@ -583,50 +595,46 @@ int ProveCall::openings() {
     const gl2_t w_scale = gl2_mul_base(zh, gl_inv(gl_mul((gl_t)n, shift_n)));
     HIPCHK(launch_ext_powers(c->zpow.as<gl2_t>(), zeta, n, st));
     HIPCHK(launch_coset_weights(c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), zeta, w_scale, s.log_n, st));
-    HIPCHK(launch_openings(c->lde.as<gl_t>(), s.N, C, n, c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), c->open_local.as<gl2_t>(),
-                           c->open_next.as<gl2_t>(), st));
-    HIPCHK(launch_openings(c->qcoef.as<gl_t>(), n, Q, n, c->zpow.as<gl2_t>(), nullptr, c->open_q.as<gl2_t>(), nullptr, st));
-    if (nZ) {  // P5: the Zs at zeta and at g zeta, like the trace from coset 0 of their LDE
-        HIPCHK(launch_openings(c->perm.zlde.as<gl_t>(), s.N, nZ, n, c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), c->perm.open_z.as<gl2_t>(),
-                               c->perm.open_zn.as<gl2_t>(), st));
-        op_z.resize(nZ);
-        op_zn.resize(nZ);
-        HIPCHK(read_back(c, op_z.data(), c->perm.open_z.p, nZ * 16, st));
-        HIPCHK(read_back(c, op_zn.data(), c->perm.open_zn.p, nZ * 16, st));
+    for (size_t k = 0; k < s.pl.n_mats; k++) {  // (P5: the Zs like the trace)
+        const Committed& m = mats[k];
+        if (m.coef) HIPCHK(launch_openings(m.coef->as<gl_t>(), n, s.pl.mat[k].cols, n, c->zpow.as<gl2_t>(), nullptr, m.d_open[0]->as<gl2_t>(), nullptr, st));
+        else HIPCHK(launch_openings(m.lde->as<gl_t>(), s.N, s.pl.mat[k].cols, n, c->zpow.as<gl2_t>() + n, c->gzpow.as<gl2_t>(), m.d_open[0]->as<gl2_t>(), m.d_open[1]->as<gl2_t>(), st));
     }
-    op_local.resize(C);
-    op_next.resize(C);
-    op_q.resize(Q);
-    HIPCHK(read_back(c, op_local.data(), c->open_local.p, C * 16, st));
-    HIPCHK(read_back(c, op_next.data(), c->open_next.p, C * 16, st));
-    HIPCHK(read_back(c, op_q.data(), c->open_q.p, Q * 16, st));
+    for (size_t k = 0; k < s.pl.n_mats; k++)
+        for (size_t b = 0, cnt; b < 2 && (cnt = s.pl.mat[k].n_open[b]); b++) {
+            mats[k].open[b].resize(cnt);
+            HIPCHK(read_back(c, mats[k].open[b].data(), mats[k].d_open[b]->p, cnt * 16, st));
+        }
     return 0;
 }
 
 // ---- phase 6: FRI batch combination (prove_openings, App. A.8)
 int ProveCall::fri_combine() {
-    const size_t n = s.n, N = s.N, C = s.C, Q = s.Q, nZ = s.nZ;
+    const size_t n = s.n, N = s.N;
     HIPCHK(stream_wait(c));  // the openings
     fs.start();  // 2 (2 C + Q) field elements through the sponge, one permutation per 8: the longest host stretch of a proof
-    for (size_t i = 0; i < C; i++) ch.observe_ext(op_local[i]);
-    for (size_t i = 0; i < nZ; i++) ch.observe_ext(op_z[i]);  // batch 0: local || zs || quotient, batch 1: next || zs_next (P5)
-    for (size_t i = 0; i < Q; i++) ch.observe_ext(op_q[i]);
-    for (size_t i = 0; i < C; i++) ch.observe_ext(op_next[i]);
-    for (size_t i = 0; i < nZ; i++) ch.observe_ext(op_zn[i]);
+    for (int b = 0; b < 2; b++)  // batch 0: every matrix at zeta -- local || zs || quotient, batch 1: at g zeta -- next || zs_next (P5)
+        for (size_t k = 0; k < s.pl.n_mats; k++)
+            for (const gl2_t& v : mats[k].open[b]) ch.observe_ext(v);
     const gl2_t fri_alpha = ch.get_ext();
     fs.stop();
     const gl2_t gzeta = gl2_mul_base(zeta, gl_root_of_unity(s.log_n));
-    HIPCHK(launch_ext_powers(c->ext_apow.as<gl2_t>(), fri_alpha, C + nZ + Q, st));
+    HIPCHK(launch_ext_powers(c->ext_apow.as<gl2_t>(), fri_alpha, s.pl.batch_cols[0], st));
     // sum_j alpha^j trace_j: the sum is taken on coset 0 of the LDE (n values a column) and turned into coefficients by ONE inverse
     // coset transform of its two words -- linear, so these are the coefficients of the reference's sum of coefficient vectors
     gl_t* comb_t = c->comb_out.as<gl_t>();        // [2][n] words
     gl2_t* comb_q = c->comb_out.as<gl2_t>() + n;  // [n] extension elements
-    HIPCHK(launch_fri_combine(c->lde.as<gl_t>(), N, C, n, c->ext_apow.as<gl2_t>(), COMB_PPC, comb_chunks(C), c->comb_partial.as<gl2_t>(), st));
-    if (nZ)  // + sum_i alpha^(C + i) Z_i, one more chunk of the same sum
-        HIPCHK(launch_fri_combine(c->perm.zlde.as<gl_t>(), N, nZ, n, c->ext_apow.as<gl2_t>() + C, nZ, 1, c->comb_partial.as<gl2_t>() + comb_chunks(C) * n, st));
-    HIPCHK(launch_ext_reduce(c->comb_partial.as<gl2_t>(), comb_chunks(C) + (nZ ? 1 : 0), n, comb_t, st));
+    // every matrix kept as an LDE, up to the quotient: its run of powers of alpha, its chunks of the sum (the Zs, at most 128 < COMB_PPC: one more)
+    size_t k = 0, col = 0, chunk = 0;
+    for (; !mats[k].coef; k++) {
+        const size_t cols = s.pl.mat[k].cols;
+        HIPCHK(launch_fri_combine(mats[k].lde->as<gl_t>(), N, cols, n, c->ext_apow.as<gl2_t>() + col, COMB_PPC, comb_chunks(cols), c->comb_partial.as<gl2_t>() + chunk * n, st));
+        col += cols;
+        chunk += comb_chunks(cols);
+    }
+    HIPCHK(launch_ext_reduce(c->comb_partial.as<gl2_t>(), chunk, n, comb_t, st));
     if (int rc = run_ntt(c, comb_t, c->fri_vals.as<gl_t>(), 2, n, s.log_n, true, nullptr, c->tab->qshift_inv.as<gl_t>())) return rc;  // (fri_vals: idle until fri_commit)
-    HIPCHK(launch_fri_combine(c->qcoef.as<gl_t>(), n, Q, n, c->ext_apow.as<gl2_t>() + C + nZ, Q, 1, comb_q, st));  // alpha^(C+nZ+q) quotient_q
+    HIPCHK(launch_fri_combine(mats[k].coef->as<gl_t>(), n, s.Q, n, c->ext_apow.as<gl2_t>() + col, s.Q, 1, comb_q, st));  // alpha^(C+nZ+q) quotient_q
     std::vector<gl_t> F1w(2 * n);
     std::vector<gl2_t> F1(n), tailq(n), F0(n), q0(n), q1(n), fin(n);
     HIPCHK(read_back(c, F1w.data(), comb_t, n * 16, st));
@@ -637,7 +645,7 @@ int ProveCall::fri_combine() {
     for (size_t k = 0; k < n; k++) F0[k] = gl2_add(F1[k], tailq[k]);
     divide_by_linear(F0.data(), n, zeta, q0.data());  // batch 0: trace ++ Zs ++ quotient at zeta
     divide_by_linear(F1.data(), n, gzeta, q1.data());   // batch 1: trace ++ Zs at g*zeta
-    const gl2_t shift = gl2_pow(fri_alpha, C + nZ);     // alpha^{|batch 1|}
+    const gl2_t shift = gl2_pow(fri_alpha, s.pl.batch_cols[1]);  // alpha^{|batch 1|}
     for (size_t k = 0; k < n; k++) fin[k] = gl2_add(gl2_mul(q0[k], shift), q1[k]);
     // upload as SoA, zero padded to N (lde(rate_bits))
     std::vector<gl_t> soa(2 * N, 0);
@@ -743,7 +751,7 @@ int ProveCall::pow() {
 // returned from (HIPCHK_FREE): the copy into the blob may be in flight, so the stream is waited for before the blob is freed.
 int ProveCall::queries() {
     const ProofLayout& pl = s.pl;
-    const size_t N = s.N, C = s.C, Q = s.Q, L = s.L, ncap = s.ncap;
+    const size_t N = s.N, L = s.L, ncap = s.ncap;
     if (!c->hs && !c->blob_airs.count(air.id)) {
         // a context on its own (not a pool's: those reserve at warm-up) gets its two page-locked blobs with its first proof of an AIR,
         // the proof that also grows the work buffers -- hipHostMalloc waits for the device like the hipMallocs before it
@@ -764,16 +772,13 @@ int ProveCall::queries() {
     gl_t* dq = c->gather_t.as<gl_t>();
     if (nq) HIPCHK_FREE(hipMemcpyAsync(c->qidx.p, xs.data(), nq * 4, hipMemcpyHostToDevice, st));
     const uint32_t* dxs = c->qidx.as<uint32_t>();
-    size_t off = 0;
+    size_t off = pl.quotient().q_sib + 4 * d0;  // the FRI steps follow the matrices' leaves and paths
     if (!err) {
-        HIPCHK_FREE(launch_query_leaf_colmajor(c->lde.as<gl_t>(), C, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += C;
-        HIPCHK_FREE(launch_query_path(c->digests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
-        if (s.nZ) {  // P6: trace, zs, quotient
-            HIPCHK_FREE(launch_query_leaf_colmajor(c->perm.zlde.as<gl_t>(), s.nZ, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += s.nZ;
-            HIPCHK_FREE(launch_query_path(c->perm.zdigests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
+        for (size_t k = 0; k < pl.n_mats; k++) {  // P6: trace, zs, quotient
+            const MatrixLayout& e = pl.mat[k];
+            HIPCHK_FREE(launch_query_leaf_colmajor(mats[k].lde->as<gl_t>(), e.cols, s.log_n, s.r, dxs, nq, dq, stride, e.q_leaf, st));
+            HIPCHK_FREE(launch_query_path(mats[k].digests->as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, e.q_sib, st));
         }
-        HIPCHK_FREE(launch_query_leaf_colmajor(c->qlde.as<gl_t>(), Q, s.log_n, s.r, dxs, nq, dq, stride, off, st)); off += Q;
-        HIPCHK_FREE(launch_query_path(c->qdigests.as<gl_t>(), N, d0, dxs, 0, nq, dq, stride, off, st)); off += 4 * d0;
         size_t len = N;
         unsigned shift_bits = 0;
         for (size_t l = 0; l < L; l++) {
@@ -788,15 +793,10 @@ int ProveCall::queries() {
         if (nq) HIPCHK_FREE(hipMemcpyAsync(out + pl.off_queries, dq, nq * stride * 8, hipMemcpyDeviceToHost, st));
     }
     pl.write_header(out);
-    memcpy(out + pl.off_trace_cap, trace_cap.data(), 4 * ncap * 8);
-    memcpy(out + pl.off_quot_cap, quot_cap.data(), 4 * ncap * 8);
-    memcpy(out + pl.off_local, op_local.data(), C * 16);
-    memcpy(out + pl.off_next, op_next.data(), C * 16);
-    memcpy(out + pl.off_quot_open, op_q.data(), Q * 16);
-    if (s.nZ) {
-        memcpy(out + pl.off_zs_cap, zs_cap.data(), 4 * ncap * 8);
-        memcpy(out + pl.off_zs, op_z.data(), s.nZ * 16);
-        memcpy(out + pl.off_zs_next, op_zn.data(), s.nZ * 16);
+    for (size_t k = 0; k < pl.n_mats; k++) {
+        const MatrixLayout& e = pl.mat[k];
+        memcpy(out + e.off_cap, mats[k].cap.data(), 4 * ncap * 8);
+        for (size_t b = 0; b < 2 && e.n_open[b]; b++) memcpy(out + e.off_open[b], mats[k].open[b].data(), e.n_open[b] * 16);
     }
     if (L) memcpy(out + pl.off_fri_caps, fri_caps.data(), L * 4 * ncap * 8);
     HIPCHK_FREE(stream_wait(c));  // xs goes out of scope

@@ -94,38 +94,34 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
         if (proof[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     if (geo.arities.size() != pl.L || geo.final_poly_len != pl.final_len) return STARKHIP_ERR_BAD_SHAPE;
     if (pl.hasher == STARKHIP_HASHER_KECCAK) {  // K6: a cap entry outside a digest's ranges is not the encoding of any 25 bytes
-        for (size_t i = 0; i < (pl.nZ ? 3 : 2) * pl.ncap; i++)  // the trace cap, the Z cap if there is one, the quotient cap: back to back
-            if (!keccak_digest_in_range(proof + pl.off_trace_cap + 4 * i)) return STARKHIP_ERR_VERIFY;
+        for (size_t k = 0; k < pl.n_mats; k++)
+            for (size_t i = 0; i < pl.ncap; i++)
+                if (!keccak_digest_in_range(proof + pl.mat[k].off_cap + 4 * i)) return STARKHIP_ERR_VERIFY;
         for (size_t i = 0; i < pl.L * pl.ncap; i++)
             if (!keccak_digest_in_range(proof + pl.off_fri_caps + 4 * i)) return STARKHIP_ERR_VERIFY;
     }
 
-    const size_t C = pl.C, Q = pl.Q, n = (size_t)1 << pl.log_n, N = (size_t)1 << pl.log_N, ncap = pl.ncap;
-    const gl2_t* op_local = (const gl2_t*)(proof + pl.off_local);
-    const gl2_t* op_next = (const gl2_t*)(proof + pl.off_next);
-    const gl2_t* op_q = (const gl2_t*)(proof + pl.off_quot_open);
-    const gl2_t* op_z = (const gl2_t*)(proof + pl.off_zs);  // nZ > 0 only
-    const gl2_t* op_zn = (const gl2_t*)(proof + pl.off_zs_next);
-    const size_t nZ = pl.nZ;
+    const size_t n = (size_t)1 << pl.log_n, N = (size_t)1 << pl.log_N, ncap = pl.ncap, nZ = pl.nZ, last = pl.n_mats - 1;
+    // the openings of matrix k at zeta (batch 0) or at g zeta (batch 1), pl.mat[k].n_open[batch] of them
+    auto opened = [&](size_t k, int batch) { return (const gl2_t*)(proof + pl.mat[k].off_open[batch]); };
+    const gl2_t *op_local = opened(0, 0), *op_next = opened(0, 1), *op_q = opened(last, 0);
     const gl2_t* final_poly = (const gl2_t*)(proof + pl.off_final);
     const gl_t* pis = proof + pl.off_pis;
 
     // ---- challenges, in transcript order (App. A.5)
     Challenger ch((int)pl.hasher);  // the hasher the header names: the sponge's permutation, and proof of work through it
-    ch.observe_many(proof + pl.off_trace_cap, 4 * ncap);
+    ch.observe_many(proof + pl.mat[0].off_cap, 4 * ncap);
     // permutation challenges (COMPAT.md P1): B sets of 2 x (beta, gamma) after the trace cap, then the Z cap (P3), then the alphas
     std::vector<gl_t> perm_chal(nZ ? (size_t)P.perm_batch_size() * 4 : 0);
     for (gl_t& x : perm_chal) x = ch.get();
-    if (nZ) ch.observe_many(proof + pl.off_zs_cap, 4 * ncap);
+    for (size_t k = 1; k < last; k++) ch.observe_many(proof + pl.mat[k].off_cap, 4 * ncap);
     std::vector<gl2_t> alphas(cfg.num_challenges);
     for (auto& a : alphas) a = gl2_from_base(ch.get());
-    ch.observe_many(proof + pl.off_quot_cap, 4 * ncap);
+    ch.observe_many(proof + pl.mat[last].off_cap, 4 * ncap);
     gl2_t zeta = ch.get_ext();
-    for (size_t c = 0; c < C; c++) ch.observe_ext(op_local[c]);
-    for (size_t z = 0; z < nZ; z++) ch.observe_ext(op_z[z]);  // P5: local || zs || quotient, then next || zs_next
-    for (size_t q = 0; q < Q; q++) ch.observe_ext(op_q[q]);
-    for (size_t c = 0; c < C; c++) ch.observe_ext(op_next[c]);
-    for (size_t z = 0; z < nZ; z++) ch.observe_ext(op_zn[z]);
+    for (int batch = 0; batch < 2; batch++)  // P5: local || zs || quotient, then next || zs_next
+        for (size_t k = 0; k < pl.n_mats; k++)
+            for (size_t i = 0; i < pl.mat[k].n_open[batch]; i++) ch.observe_ext(opened(k, batch)[i]);
     gl2_t fri_alpha = ch.get_ext();
     std::vector<gl2_t>& betas = out->betas;
     betas.resize(pl.L);
@@ -152,7 +148,7 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     masks[KIND_LAST] = gl2_mul(z_h, gl2_inv(gl2_mul_base(gl2_sub(gl2_mul_base(zeta, g), gl2_one()), (gl_t)n)));
     std::vector<gl2_t> acc(cfg.num_challenges);
     air_eval_folded<ExtOps>(P, op_local, op_next, pis, masks, alphas.data(), (int)cfg.num_challenges, acc.data());
-    if (nZ) perm_eval_folded<ExtOps>(P, op_local, op_z, op_zn, perm_chal.data(), masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // P4
+    if (nZ) perm_eval_folded<ExtOps>(P, op_local, opened(1, 0), opened(1, 1), perm_chal.data(), masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // P4
     for (unsigned i = 0; i < cfg.num_challenges; i++) {
         gl2_t s = gl2_zero();
         for (unsigned k = factor; k-- > 0;) s = gl2_add(gl2_mul(s, zeta_n), op_q[i * factor + k]);
@@ -164,15 +160,11 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     out->gzeta = gl2_mul_base(zeta, g);
     out->fri_alpha = fri_alpha;
     // precomputed reduced openings per batch: sum_j alpha^j open_j
-    gl2_t red0 = gl2_zero(), red1 = gl2_zero();
-    for (size_t q = Q; q-- > 0;) red0 = gl2_add(gl2_mul(red0, fri_alpha), op_q[q]);
-    for (size_t z = nZ; z-- > 0;) red0 = gl2_add(gl2_mul(red0, fri_alpha), op_z[z]);
-    for (size_t c = C; c-- > 0;) red0 = gl2_add(gl2_mul(red0, fri_alpha), op_local[c]);
-    for (size_t z = nZ; z-- > 0;) red1 = gl2_add(gl2_mul(red1, fri_alpha), op_zn[z]);
-    for (size_t c = C; c-- > 0;) red1 = gl2_add(gl2_mul(red1, fri_alpha), op_next[c]);
-    out->red0 = red0;
-    out->red1 = red1;
-    out->alpha_pow_C = gl2_pow(fri_alpha, C + nZ);  // alpha^{|batch 1|}
+    out->red[0] = out->red[1] = gl2_zero();
+    for (int batch = 0; batch < 2; batch++)
+        for (size_t k = pl.n_mats; k-- > 0;)
+            for (size_t i = pl.mat[k].n_open[batch]; i-- > 0;) out->red[batch] = gl2_add(gl2_mul(out->red[batch], fri_alpha), opened(k, batch)[i]);
+    out->alpha_pow_C = gl2_pow(fri_alpha, pl.batch_cols[1]);  // alpha^{|batch 1|}
     return STARKHIP_OK;
 }
 
@@ -181,8 +173,8 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
     if (int rc = verify_prelude(air, cfg, proof, words, true, &pre); rc != STARKHIP_OK) return rc;
     const ProofLayout& pl = pre.pl;
     const FriGeometry& geo = pre.geo;
-    const size_t C = pl.C, Q = pl.Q, ncap = pl.ncap;
-    const gl2_t fri_alpha = pre.fri_alpha, zeta = pre.zeta, gzeta = pre.gzeta, red0 = pre.red0, red1 = pre.red1, alpha_pow_C = pre.alpha_pow_C;
+    const size_t ncap = pl.ncap;
+    const gl2_t fri_alpha = pre.fri_alpha, zeta = pre.zeta, gzeta = pre.gzeta, red0 = pre.red[0], red1 = pre.red[1], alpha_pow_C = pre.alpha_pow_C;
     const std::vector<gl2_t>& betas = pre.betas;
     const std::vector<size_t>& indices = pre.indices;
     const gl2_t* final_poly = (const gl2_t*)(proof + pl.off_final);
@@ -193,23 +185,16 @@ int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_
     auto check_query = [&](size_t qi) -> bool {
         const uint64_t* qp = proof + pl.off_queries + qi * pl.query_words;
         size_t x_index = indices[qi];
-        const gl_t* tleaf = qp; qp += C;
-        const gl_t* tsib = qp; qp += 4 * d0;
-        const gl_t* zleaf = qp; qp += pl.nZ;  // nZ > 0: the Z leaf and its path between the trace's and the quotient's (P6)
-        const gl_t* zsib = qp; qp += pl.nZ ? 4 * d0 : 0;
-        const gl_t* qleaf = qp; qp += Q;
-        const gl_t* qsib = qp; qp += 4 * d0;
-        if (!merkle_verify_to_cap(pl.hasher, tleaf, C, x_index, proof + pl.off_trace_cap, tsib, d0)) return false;
-        if (pl.nZ && !merkle_verify_to_cap(pl.hasher, zleaf, pl.nZ, x_index, proof + pl.off_zs_cap, zsib, d0)) return false;
-        if (!merkle_verify_to_cap(pl.hasher, qleaf, Q, x_index, proof + pl.off_quot_cap, qsib, d0)) return false;
         gl_t subgroup_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity((unsigned)pl.log_N), gl_bitrev((uint32_t)x_index, (unsigned)pl.log_N)));
-        // fri_combine_initial
+        // every matrix's leaf (P6: trace, zs, quotient) against its cap, and into fri_combine_initial's sums: batch 0, and batch 1 if it is opened at g zeta
         gl2_t e0 = gl2_zero(), e1 = gl2_zero();
-        for (size_t q = Q; q-- > 0;) e0 = gl2_add(gl2_mul(e0, fri_alpha), gl2_from_base(qleaf[q]));
-        for (size_t z = pl.nZ; z-- > 0;) e0 = gl2_add(gl2_mul(e0, fri_alpha), gl2_from_base(zleaf[z]));
-        for (size_t c = C; c-- > 0;) e0 = gl2_add(gl2_mul(e0, fri_alpha), gl2_from_base(tleaf[c]));
-        for (size_t z = pl.nZ; z-- > 0;) e1 = gl2_add(gl2_mul(e1, fri_alpha), gl2_from_base(zleaf[z]));
-        for (size_t c = C; c-- > 0;) e1 = gl2_add(gl2_mul(e1, fri_alpha), gl2_from_base(tleaf[c]));
+        for (size_t k = pl.n_mats; k-- > 0;) {
+            const MatrixLayout& m = pl.mat[k];
+            if (!merkle_verify_to_cap(pl.hasher, qp + m.q_leaf, m.cols, x_index, proof + m.off_cap, qp + m.q_sib, d0)) return false;
+            for (size_t i = m.n_open[0]; i-- > 0;) e0 = gl2_add(gl2_mul(e0, fri_alpha), gl2_from_base(qp[m.q_leaf + i]));
+            for (size_t i = m.n_open[1]; i-- > 0;) e1 = gl2_add(gl2_mul(e1, fri_alpha), gl2_from_base(qp[m.q_leaf + i]));
+        }
+        qp += pl.quotient().q_sib + 4 * d0;
         gl2_t xe = gl2_from_base(subgroup_x);
         gl2_t sum = gl2_mul(gl2_sub(e0, red0), gl2_inv(gl2_sub(xe, zeta)));
         sum = gl2_add(gl2_mul(sum, alpha_pow_C), gl2_mul(gl2_sub(e1, red1), gl2_inv(gl2_sub(xe, gzeta))));

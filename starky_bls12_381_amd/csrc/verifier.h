@@ -19,7 +19,7 @@ struct VerifyPrelude {
     ProofLayout pl;
     FriGeometry geo;
     gl2_t zeta, gzeta, fri_alpha;
-    gl2_t red0, red1;     // the reduced openings: sum_j alpha^j open_j at zeta (trace, [Zs,] then quotient) and at g zeta (trace [, Zs])
+    gl2_t red[2];         // the reduced openings: sum_j alpha^j open_j at zeta (trace, [Zs,] then quotient) and at g zeta (trace [, Zs])
     gl2_t alpha_pow_C;    // alpha^(C + nZ): the length of the g zeta batch
     std::vector<gl2_t> betas;
     std::vector<size_t> indices;

@@ -42,7 +42,7 @@ bool query_words_in_range(const uint64_t* proof, const ProofLayout& pl) {
 }
 
 // A proof's words in the chunk's buffer: [trace cap | (Z cap) | quotient cap] then [FRI caps .. final polynomial] of the blob
-size_t head_words(const ProofLayout& pl) { return (pl.nZ ? 12 : 8) * pl.ncap; }  // with the Z cap between them when there is one
+size_t head_words(const ProofLayout& pl) { return pl.quotient().off_cap + 4 * pl.ncap - pl.mat[0].off_cap; }  // from the first matrix's cap through the last's
 size_t region_words(const ProofLayout& pl) { return head_words(pl) + (pl.off_pow - pl.off_fri_caps); }
 
 }  // namespace
@@ -64,8 +64,8 @@ void verify_prelude_item(int id, const starkhip_config_t& cfg, const uint64_t* p
 }
 
 size_t verify_device_bytes(const ProofLayout& pl) {
-    const size_t per_query = (2 + pl.L + (pl.nZ ? 1 : 0)) * (4 * 8 + sizeof(VQLeaf)) + 2 * sizeof(gl2_t) + 8 + 4 + 4;
-    return 8 * region_words(pl) + sizeof(gl2_t) * (pl.C + pl.nZ + pl.Q) + pl.n_queries * per_query + sizeof(VQProof) + 4;
+    const size_t per_query = (pl.n_mats + pl.L) * (4 * 8 + sizeof(VQLeaf)) + 2 * sizeof(gl2_t) + 8 + 4 + 4;
+    return 8 * region_words(pl) + sizeof(gl2_t) * pl.batch_cols[0] + pl.n_queries * per_query + sizeof(VQProof) + 4;
 }
 
 void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
@@ -75,7 +75,7 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     const size_t h = head_words(pl);
     P.base = ch.words;
     P.query_words = pl.query_words;
-    P.off_quot_cap = (pl.nZ ? 8 : 4) * pl.ncap;
+    P.off_quot_cap = pl.quotient().off_cap - pl.mat[0].off_cap;
     P.off_zs_cap = 4 * pl.ncap;
     P.nZ = (uint32_t)pl.nZ;
     P.off_fri_caps = h;
@@ -99,21 +99,18 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     }
     P.zeta = pre.zeta;
     P.gzeta = pre.gzeta;
-    P.red0 = pre.red0;
-    P.red1 = pre.red1;
+    P.red0 = pre.red[0];
+    P.red1 = pre.red[1];
     P.alpha_pow_C = pre.alpha_pow_C;
     const size_t d0 = pl.log_N - pl.cap_h, per_q = vq_slots(P);
     for (size_t q = 0; q < pl.n_queries; q++) {
         const uint32_t slot = (uint32_t)(ch.digests + q * per_q);
         size_t o = P.base + P.off_queries + q * pl.query_words;
-        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.C, slot, P.hasher, 0});
-        o += pl.C + 4 * d0;
-        if (pl.nZ) {
-            ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.nZ, (uint32_t)(slot + 2 + pl.L), P.hasher, 0});
-            o += pl.nZ + 4 * d0;
+        for (size_t k = 0; k < pl.n_mats; k++) {  // digest slots (verify_query.h): 0 trace, 1 quotient, 2 + l the layers, 2 + L the Zs
+            const uint32_t at = k == 0 ? 0 : k + 1 == pl.n_mats ? 1 : (uint32_t)(2 + pl.L);
+            ch.leaves.push_back(VQLeaf{o + pl.mat[k].q_leaf, (uint32_t)pl.mat[k].cols, slot + at, P.hasher, 0});
         }
-        ch.leaves.push_back(VQLeaf{o, (uint32_t)pl.Q, slot + 1, P.hasher, 0});
-        o += pl.Q + 4 * d0;
+        o += pl.quotient().q_sib + 4 * d0;
         for (size_t l = 0; l < pl.L; l++) {
             const size_t arity = (size_t)1 << pre.geo.arities[l];
             ch.leaves.push_back(VQLeaf{o, (uint32_t)(2 * arity), (uint32_t)(slot + 2 + l), P.hasher, 0});
@@ -126,7 +123,7 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     ch.ids.push_back(id);
     ch.alphas.push_back(pre.fri_alpha);
     ch.words += region_words(pl);
-    ch.apow += pl.C + pl.nZ + pl.Q;
+    ch.apow += pl.batch_cols[0];
     ch.digests += pl.n_queries * per_q;
     ch.bytes += verify_device_bytes(pl);
 }
@@ -161,7 +158,7 @@ bool verify_bufs_carve(const VerifyChunk& ch, void* base, size_t cap, VerifyDevB
 
 void verify_pieces(const VerifyChunk& ch, size_t k, const uint64_t* proof, const ProofLayout& pl, VerifyPiece out[2]) {
     const size_t base = ch.proofs[k].base;
-    out[0] = VerifyPiece{proof + pl.off_trace_cap, head_words(pl), base};
+    out[0] = VerifyPiece{proof + pl.mat[0].off_cap, head_words(pl), base};
     out[1] = VerifyPiece{proof + pl.off_fri_caps, pl.off_pow - pl.off_fri_caps, base + head_words(pl)};
 }
 

@@ -312,6 +312,69 @@ def test_header_word_13_is_part_of_the_shape(golden):
     assert cpu_code(plain_air, cfg, proofs[0]) == S.ERR_BAD_SHAPE
 
 
+def _header(C, Q, nZ, L, cap_h, n_queries, log_n=4, rate_bits=2, arity_bits=1, n_pis=3):
+    return [0x3130304652505353, C, Q, log_n, rate_bits, cap_h, L, n_queries, 1 << (log_n - L * arity_bits), n_pis, arity_bits, 2, 0, nZ, 0, 0]
+
+
+@pytest.mark.parametrize("n_queries", [0, 3])
+@pytest.mark.parametrize("cap_h", [0, 2])
+@pytest.mark.parametrize("L", [0, 2])
+@pytest.mark.parametrize("C,Q,nZ", [(2, 2, 0), (6, 4, 2), (6, 8, 4), (0, 2, 0), (2, 0, 0), (0, 0, 2)])  # (the header check lets 0 columns pass)
+def test_layout_of_a_bare_header_is_the_documented_walk(C, Q, nZ, L, cap_h, n_queries):
+    """starkhip_proof_layout reads the header and the length alone: every offset and every q_* field against the field list of the
+    layout comment in include/starkhip.h, walked here in its order -- (name, words) of the blob, then of one query round."""
+    h = _header(C, Q, nZ, L, cap_h, n_queries)
+    log_N, ab, final_len, n_pis = h[3] + h[4], h[10], h[8], h[9]
+    ncap, d0 = 1 << cap_h, log_N - cap_h
+    depth = [log_N - (l + 1) * ab - cap_h for l in range(L)]
+    zs = nZ > 0
+    round_fields = [("q_trace_leaf", C), ("q_trace_siblings", 4 * d0)]
+    round_fields += [("q_permutation_zs_leaf", nZ), ("q_permutation_zs_siblings", 4 * d0)] if zs else []
+    round_fields += [("q_quotient_leaf", Q), ("q_quotient_siblings", 4 * d0)]
+    for l in range(L):
+        round_fields += [(("q_step_evals", l), 2 * (1 << ab)), (("q_step_siblings", l), 4 * depth[l])]
+    round_words = sum(w for _, w in round_fields)
+    blob_fields = [("off_trace_cap", 4 * ncap)] + ([("off_permutation_zs_cap", 4 * ncap)] if zs else []) + [("off_quotient_cap", 4 * ncap)]
+    blob_fields += [("off_local_values", 2 * C), ("off_next_values", 2 * C)]
+    blob_fields += [("off_permutation_zs", 2 * nZ), ("off_permutation_zs_next", 2 * nZ)] if zs else []
+    blob_fields += [("off_quotient_openings", 2 * Q), ("off_fri_caps", L * 4 * ncap), ("off_query_rounds", n_queries * round_words),
+                    ("off_final_poly", 2 * final_len), ("off_pow_witness", 1), ("off_public_inputs", n_pis)]
+    want, o = {}, 16
+    for name, w in blob_fields:
+        want[name], o = o, o + w
+    total, o = o, 0
+    for name, w in round_fields:
+        want[name], o = o, o + w
+    want.update(total_words=total, query_round_words=round_words, initial_sibling_count=d0, n_permutation_zs=nZ, n_columns=C, n_quotient_polys=Q,
+                degree_bits=h[3], rate_bits=h[4], cap_height=cap_h, n_fri_layers=L, n_query_rounds=n_queries, final_poly_len=final_len,
+                n_public_inputs=n_pis, arity_bits=ab)
+    for l in range(L):
+        want[("step_sibling_count", l)] = depth[l]
+    blob = np.zeros(total, dtype=np.uint64)
+    blob[:16] = h
+    got_struct = S.proof_layout(blob)
+    got = {}
+    for name, _ in S.ProofLayout._fields_:
+        v = getattr(got_struct, name)
+        if isinstance(v, int):
+            got[name] = v
+        else:
+            got.update({(name, l): int(x) for l, x in enumerate(v)})
+    # what the comment's walk does not name is 0: the Z fields of a proof without Zs, the step entries past L
+    assert got == {k: want.get(k, 0) for k in got}
+    assert set(want) <= set(got)
+    for words in (total - 1, total + 1):  # a length one word off
+        with pytest.raises(S.StarkhipError):
+            S.proof_layout(np.concatenate([blob, np.zeros(1, dtype=np.uint64)])[:words])
+    over = blob.copy()
+    over[13] = 129  # nZ > 128 is no header, whatever the length
+    for words in (total, total + (129 - nZ) * (4 + n_queries) + (0 if zs else 4 * ncap + 4 * d0 * n_queries)):  # ... the one 129 Zs would give too
+        t = np.zeros(words, dtype=np.uint64)
+        t[:16] = over[:16]
+        with pytest.raises(S.StarkhipError):
+            S.proof_layout(t)
+
+
 def test_rust_mirror_has_the_new_names():
     rs = open(os.path.join(ROOT, "bindings", "rust", "starkhip-sys", "src", "lib.rs")).read()
     hdr = open(os.path.join(ROOT, "include", "starkhip.h")).read()
