@@ -101,6 +101,9 @@ pub struct starkhip_proof_layout_t {
     pub off_permutation_zs_next: usize,
     pub q_permutation_zs_leaf: usize,
     pub q_permutation_zs_siblings: usize,
+    // LogUp lookups: nA (header word 14; 0 for a proof without them).  With nA > 0 the five positions above are those of the
+    // auxiliary polynomials, which take the Zs' place in the blob, and n_permutation_zs is 0
+    pub n_logup_polys: usize,
 }
 
 /// `starkhip_pool_config_t` (0 = the library's default).
@@ -277,6 +280,20 @@ extern "C" {
     pub fn starkhip_air_eval_frame_full(air: c_int, local: *const u64, next: *const u64, public_inputs: *const u64, masks: *const u64,
                                         alphas: *const u64, n_alpha: c_int, zs: *const u64, zs_next: *const u64, challenges: *const u64,
                                         acc_out: *mut u64) -> c_int;
+    // LogUp lookups (starky >= 0.2's Lookup; COMPAT.md L1 - L7): the lookups a registered program declares and nA = 2 sum (H + 1)
+    pub fn starkhip_air_logups(air: c_int) -> c_int;
+    pub fn starkhip_air_logup_polys(air: c_int) -> c_int;
+    // tests: the auxiliary polynomials of a trace on the device and from plain loops (challenges chi_0, chi_1; polys_out [nA][n_rows],
+    // closing_out [2][n_lookups], the count of zero denominators); the constraint fold over the AIR's own and the LogUp constraints
+    pub fn starkhip_logup_polys(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                on_device: c_int, challenges: *const u64, polys_out: *mut u64, closing_out: *mut u64,
+                                zero_denominators_out: *mut u64) -> c_int;
+    pub fn starkhip_logup_polys_replay(air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                       challenges: *const u64, polys_out: *mut u64, closing_out: *mut u64,
+                                       zero_denominators_out: *mut u64) -> c_int;
+    pub fn starkhip_air_eval_frame_logup(air: c_int, local: *const u64, next: *const u64, public_inputs: *const u64, masks: *const u64,
+                                         alphas: *const u64, n_alpha: c_int, aux: *const u64, aux_next: *const u64, challenges: *const u64,
+                                         acc_out: *mut u64) -> c_int;
     pub fn starkhip_check_trace(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                 on_device: c_int, public_inputs: *const u64, violations: *mut u64, first: *mut u64) -> c_int;
     // The full report: per_constraint [starkhip_air_num_constraints(air)] or null, row_mask [(n_rows + 63) / 64] or null (bit r & 63 of
@@ -868,6 +885,9 @@ pub mod handoff {
 
     pub fn stark_proof_with_public_inputs(proof: &Proof) -> Result<StarkProofWithPublicInputs<F, C, D>, Error> {
         let l = proof.layout()?;
+        // starky 0.1.2's StarkProof has no place for LogUp auxiliary polynomials (they are starky >= 0.2's auxiliary_polys_cap): such a
+        // proof is handed off through the Python value (handoff.py), not through this type
+        if l.n_logup_polys > 0 { return Err(Error(STARKHIP_ERR_BAD_SHAPE)); }
         let b = &proof.0[..];
         let ncap = 4usize << l.cap_height; // words per cap
         let openings = StarkOpeningSet {

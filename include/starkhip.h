@@ -75,6 +75,9 @@ typedef struct {
 #define STARKHIP_AIR_MAX_DEGREE 8u /* 4 gates + 3 factors + 1 for a first / last-row constraint: the most a program can reach */
 #define STARKHIP_AIR_MAX_PERMUTATION_PAIRS 64u   /* permutation pairs of a program, and entries of one pair */
 #define STARKHIP_AIR_MAX_PERMUTATION_ENTRIES 64u
+#define STARKHIP_AIR_MAX_LOGUP_LOOKUPS 64u /* LogUp lookups of a program, and looked-up columns of one lookup */
+#define STARKHIP_AIR_MAX_LOGUP_COLUMNS 64u
+#define STARKHIP_AIR_MAX_LOGUP_POLYS 1024u /* nA: the auxiliary polynomials a proof of the program commits (header word 14) */
 
 typedef enum {
     STARKHIP_AIR_FP12_MUL = 0,
@@ -145,6 +148,19 @@ int starkhip_air_eval_frame(starkhip_air_t air, const uint64_t* local, const uin
  * its quotient on every coset ("quotient_cosets" = 1, as degree > 5 does), behind either "quotient_impl". */
 int starkhip_air_permutation_pairs(starkhip_air_t air);
 int starkhip_air_permutation_zs(starkhip_air_t air);
+/* LogUp lookups (starky >= 0.2's Lookup { columns, table_column, frequencies_column }; COMPAT.md L1 - L7).  A registered program may
+ * declare lookups instead of permutation pairs (a program with both is refused): every cell of a lookup's m columns occurs in its table
+ * column, and its frequencies column holds, row by row, how often that row's table value is looked up.  With d the program's degree
+ * (>= 2) the m columns are cut in declaration order into H = ceil(m / (d - 1)) helper batches.  Per challenge (2), then per lookup, a
+ * proof commits the H helper polynomials and one running sum Z, between the trace and the quotient: nA = 2 sum (H + 1) polynomials
+ * (at most STARKHIP_AIR_MAX_LOGUP_POLYS), and nL = 2 sum (H + 2) constraints follow the AIR's own in the alpha fold.  The two queries:
+ * the number of lookups, and nA (0 for an AIR without them, which is every built-in one); BAD_AIR for an unknown id.  starkhip_prove
+ * refuses a trace whose running sums do not close (wrong frequencies, a value missing from the table) or in which a denominator
+ * chi + cell is zero with STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE, before the auxiliary polynomials are committed; the context stays
+ * usable.  Such a proof evaluates its quotient on every coset, behind either "quotient_impl".  Filling the frequencies column is the
+ * caller's. */
+int starkhip_air_logups(starkhip_air_t air);
+int starkhip_air_logup_polys(starkhip_air_t air);
 
 /* --- user-defined AIRs ------------------------------------------------------------------
  * A starky user's own `impl Stark` reaches the library as its constraint program: the blob starkhip_air_program returns (format:
@@ -828,6 +844,26 @@ int starkhip_permutation_zs_replay(starkhip_air_t air, const uint64_t* trace, si
 int starkhip_air_eval_frame_full(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
                                  const uint64_t masks[8], const uint64_t* alphas, int n_alpha, const uint64_t* zs, const uint64_t* zs_next,
                                  const uint64_t* challenges, uint64_t* acc_out);
+/* The auxiliary polynomials of an AIR with LogUp lookups on one trace, as prove() computes them (csrc/kernels_logup.hip): trace as in
+ * starkhip_permutation_zs; challenges: chi_0, chi_1, canonical words; polys_out [nA][n_rows], challenge-major, per lookup its helpers
+ * h_j(r) = sum over batch j of 1 / (chi + c(r)) and then Z with Z[0] = 0, Z[r + 1] = Z[r] + sum_j h_j(r) - f(r) / (chi + t(r));
+ * closing_out [2][n_lookups], challenge-major: Z[n - 1] plus the last row's increment, 0 exactly when the frequencies hold the
+ * multiplicities (up to the challenges' luck); *zero_denominators_out: how many chi + cell were zero -- their inverse is taken as 0.
+ * BAD_AIR for an unknown AIR or one without LogUp lookups, BAD_SHAPE for a bad trace argument, rows that are no power of two in
+ * 2 .. 2^STARKHIP_MAX_LOG_ROWS or a challenge >= p. */
+int starkhip_logup_polys(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                         const uint64_t* challenges, uint64_t* polys_out, uint64_t* closing_out, uint64_t* zero_denominators_out);
+/* the same from plain loops on the host (host memory only); no device needed */
+int starkhip_logup_polys_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const uint64_t* challenges,
+                                uint64_t* polys_out, uint64_t* closing_out, uint64_t* zero_denominators_out);
+/* starkhip_air_eval_frame plus the LogUp constraints (COMPAT.md L4): aux / aux_next hold nA pairs (the auxiliary openings at zeta and
+ * g zeta), challenges chi_0, chi_1 base-field words; acc_out is the fold over all K + nL constraints -- the AIR's own K, then per
+ * (challenge, lookup) the helper constraints h_j prod (chi + c) - sum_c prod_{c' != c} (chi + c'), Z on the first row, and
+ * (Z(next) - Z) (chi + t) - (sum_j h_j) (chi + t) + f.  For an AIR without LogUp lookups aux, aux_next and challenges may be NULL and
+ * the result is starkhip_air_eval_frame's.  Host only. */
+int starkhip_air_eval_frame_logup(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
+                                  const uint64_t masks[8], const uint64_t* alphas, int n_alpha, const uint64_t* aux, const uint64_t* aux_next,
+                                  const uint64_t* challenges, uint64_t* acc_out);
 /* values column-major [C][n] (host) -> coeffs [C][n] and LDE [C][N] in NATURAL point order i <-> 7*w_N^i.  1 <= log_n <=
  * STARKHIP_MAX_LOG_ROWS and rate_bits <= 8, BAD_SHAPE otherwise; from log_n 14 on through csrc/kernels_lde_long.hip */
 int starkhip_lde_batch(void* ctx, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out,
@@ -965,7 +1001,8 @@ const char* starkhip_error_string(int code);
 /* Proof blob, uint64 words (canonical field order of StarkProofWithPublicInputs):
  *   [0..16)  header: magic "SSPRF001", C, Q, degree_bits, rate_bits, cap_height, L (FRI layers),
  *            num_query_rounds, final_poly_len, n_pis, arity_bits, num_challenges, hasher (STARKHIP_HASHER_*: 0 for Poseidon),
- *            nZ (permutation Z polynomials: 0 for an AIR without permutation pairs, at most 128), 0,0
+ *            nZ (permutation Z polynomials: 0 for an AIR without permutation pairs, at most 128),
+ *            nA (LogUp auxiliary polynomials: 0 for an AIR without LogUp lookups, at most 1024; never beside nZ), 0
  *   trace_cap[2^cap_h][4]; [nZ > 0: permutation_zs_cap[2^cap_h][4];] quotient_polys_cap[2^cap_h][4]
  *   openings.local_values[C][2]; openings.next_values[C][2];
  *   [nZ > 0: openings.permutation_zs[nZ][2]; openings.permutation_zs_next[nZ][2];] openings.quotient_polys[Q][2]
@@ -975,7 +1012,8 @@ const char* starkhip_error_string(int code);
  *       quotient leaf[Q], quotient siblings[log N - cap_h][4],
  *       steps[L]: evals[2^arity][2], siblings[log(N / arity^(l+1)) - cap_h][4]
  *   final_poly[final_poly_len][2]; pow_witness; public_inputs[n_pis]
- * A proof with nZ = 0 has exactly the bytes it always had.
+ * A proof with nA > 0 has the same shape with its auxiliary polynomials in the Zs' place: auxiliary_polys_cap, openings.auxiliary_polys[nA][2]
+ * and openings.auxiliary_polys_next[nA][2], the auxiliary leaf[nA] and its siblings.  A proof with nZ = nA = 0 has exactly the bytes it always had.
  */
 #define STARKHIP_PROOF_MAGIC 0x3130304652505353ULL
 
@@ -992,6 +1030,9 @@ typedef struct {
     size_t q_step_evals[16], q_step_siblings[16], step_sibling_count[16];
     /* permutation arguments (all 0 for a proof with nZ = 0) */
     size_t n_permutation_zs, off_permutation_zs_cap, off_permutation_zs, off_permutation_zs_next, q_permutation_zs_leaf, q_permutation_zs_siblings;
+    /* LogUp lookups: nA (0 for a proof without them).  With nA > 0 the five positions above are those of the auxiliary polynomials,
+     * which take the Zs' place in the blob, and n_permutation_zs is 0 */
+    size_t n_logup_polys;
 } starkhip_proof_layout_t;
 /* STARKHIP_ERR_BAD_SHAPE when the blob's header is not a proof header or disagrees with proof_words */
 int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_proof_layout_t* out);

@@ -20,6 +20,7 @@ import numpy as np
 P = 0xFFFFFFFF00000001
 AIR_MAGIC = 0x3152495F52494153  # "SAIR_IR1"
 AIR_PERM_MAGIC = 0x3153524941504D50  # "PMPAIRS1": the section of permutation pairs
+AIR_LOGUP_MAGIC = 0x3130535055474F4C  # "LOGUPS01": the section of LogUp lookups
 KIND_PLAIN, KIND_TRANSITION, KIND_FIRST, KIND_LAST = 0, 1, 2, 3
 CK_PLUS, CK_MINUS, CK_CONST, CK_PI, CK_NEG_PI = 0, 1, 2, 3, 4
 REF_NEXT, REF_COMPL, REF_COL_MASK = 1 << 30, 1 << 31, 0xFFFFFF
@@ -182,6 +183,7 @@ class AirBuilder:
         self._open, self._kind, self._gates, self._cur = False, 0, [], []
         self.perm_pairs = []
         self.lookups = []  # (input, table, permuted_input, permuted_table) of every lookup()
+        self.logups = []  # (columns, table, frequencies) of every logup()
 
     def L(self, col):
         self._check_col(col)
@@ -240,6 +242,15 @@ class AirBuilder:
         self.permutation_pair([(cols[1], pt)])
         self.lookups.append(cols)
 
+    def logup(self, columns, table, frequencies):
+        """One LogUp lookup (starky >= 0.2's `Lookup`; COMPAT.md L1 - L7): every cell of `columns` occurs in column `table`, and column
+        `frequencies` holds, row by row, how often that row's table value is looked up.  No constraint is emitted here: prover and
+        verifiers add the helper and Z constraints after the AIR's own.  The validator refuses it beside permutation pairs and at degree 1."""
+        columns = [int(c) for c in columns]
+        for c in columns + [int(table), int(frequencies)]:
+            self._check_col(c)
+        self.logups.append((columns, int(table), int(frequencies)))
+
     def count(self):
         return self.n_constraints
 
@@ -255,6 +266,10 @@ class AirBuilder:
             words += [AIR_PERM_MAGIC, len(self.perm_pairs)]
             for entries in self.perm_pairs:
                 words += [len(entries)] + [l | (r << 32) for l, r in entries]
+        if self.logups:  # the other optional section, in the same place
+            words += [AIR_LOGUP_MAGIC, len(self.logups)]
+            for columns, table, freq in self.logups:
+                words += [len(columns), table | (freq << 32)] + columns
         return np.array(words, dtype=np.uint64)
 
     def _check_col(self, col):

@@ -212,6 +212,23 @@ def air_permutation_zs(air):
     return r
 
 
+def air_logups(air):
+    """LogUp lookups the AIR declares (AirBuilder.logup; 0 for every built-in AIR)."""
+    r = lib.starkhip_air_logups(air)
+    if r < 0:
+        raise StarkhipError(r)
+    return r
+
+
+def air_logup_polys(air):
+    """nA: the auxiliary polynomials a proof of the AIR commits for its LogUp lookups: per challenge (2) and lookup its
+    ceil(m / (degree - 1)) helpers and one running sum."""
+    r = lib.starkhip_air_logup_polys(air)
+    if r < 0:
+        raise StarkhipError(r)
+    return r
+
+
 def air_program(air):
     """Serialised constraint program (numpy uint64 copy)."""
     blob = _u64p()
@@ -557,7 +574,7 @@ class ProofLayout(C.Structure):
         "off_public_inputs", "total_words", "q_trace_leaf", "q_trace_siblings", "q_quotient_leaf", "q_quotient_siblings",
         "initial_sibling_count")] + [(n, C.c_size_t * 16) for n in ("q_step_evals", "q_step_siblings", "step_sibling_count")] + \
         [(n, C.c_size_t) for n in ("n_permutation_zs", "off_permutation_zs_cap", "off_permutation_zs", "off_permutation_zs_next",
-                                   "q_permutation_zs_leaf", "q_permutation_zs_siblings")]
+                                   "q_permutation_zs_leaf", "q_permutation_zs_siblings", "n_logup_polys")]
 
 
 lib.starkhip_proof_layout.argtypes = [_u64p, C.c_size_t, C.POINTER(ProofLayout)]
@@ -656,6 +673,49 @@ def air_eval_frame_full(air, local, nxt, pis, masks, alphas, zs, zs_next, challe
     _chk(lib.starkhip_air_eval_frame_full(air, _p64(local), _p64(nxt), _p64(pis), _p64(masks), _p64(alphas), alphas.shape[0], _p64(zs),
                                           _p64(zs_next), _p64(challenges), _p64(out)))
     return out
+
+
+lib.starkhip_air_eval_frame_logup.argtypes = [C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p, C.c_int, _u64p, _u64p, _u64p, _u64p]
+
+
+def air_eval_frame_logup(air, local, nxt, pis, masks, alphas, aux, aux_next, challenges):
+    """air_eval_frame continued over the LogUp constraints (COMPAT.md L4): aux / aux_next [nA, 2] are the auxiliary openings at zeta
+    and g zeta, challenges the two base-field words chi_0, chi_1; the fold over all K + nL constraints, [k, 2]."""
+    local, nxt, masks, alphas, aux, aux_next = (np.ascontiguousarray(x, dtype=np.uint64) for x in (local, nxt, masks, alphas, aux, aux_next))
+    pis = np.ascontiguousarray(pis, dtype=np.uint64)
+    challenges = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+    cols, na = air_columns(air), air_logup_polys(air)
+    if local.shape != (cols, 2) or nxt.shape != (cols, 2) or masks.shape != (4, 2) or alphas.ndim != 2 or alphas.shape[1] != 2 \
+            or pis.size != air_public_inputs(air) or aux.shape != (na, 2) or aux_next.shape != (na, 2) or challenges.size != 2:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    out = np.zeros_like(alphas)
+    _chk(lib.starkhip_air_eval_frame_logup(air, _p64(local), _p64(nxt), _p64(pis), _p64(masks), _p64(alphas), alphas.shape[0], _p64(aux),
+                                           _p64(aux_next), _p64(challenges), _p64(out)))
+    return out
+
+
+lib.starkhip_logup_polys.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, _u64p, _u64p, _u64p]
+lib.starkhip_logup_polys_replay.argtypes = [C.c_int, _u64p, C.c_size_t, C.c_size_t, C.c_int, _u64p, _u64p, _u64p, _u64p]
+
+
+def _logup_args(air, n_rows, challenges):
+    challenges = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+    if challenges.size != 2:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    return (challenges, np.zeros((air_logup_polys(air), n_rows), dtype=np.uint64), np.zeros((2, air_logups(air)), dtype=np.uint64),
+            np.zeros(1, dtype=np.uint64))
+
+
+def logup_polys_replay(air, trace, challenges, layout=0):
+    """The auxiliary polynomials of `trace` (row-major [n][C], or column-major [C][n] with layout=1) under the challenges (chi_0, chi_1),
+    from plain loops on the host (starkhip_logup_polys_replay): (polys [nA, n], closing values [2, n_lookups], zero denominators)."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    challenges, polys, closing, zeros = _logup_args(air, n_rows, challenges)
+    _chk(lib.starkhip_logup_polys_replay(air, _p64(trace), n_rows, n_cols, layout, _p64(challenges), _p64(polys), _p64(closing), _p64(zeros)))
+    return polys, closing, int(zeros[0])
 
 
 lib.starkhip_permutation_zs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, _u64p, _u64p]
@@ -1208,6 +1268,24 @@ class Prover:
         _chk(lib.starkhip_permutation_zs(self._ctx, air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, _p64(challenges), _p64(zs),
                                          _p64(closing)))
         return zs, closing
+
+    def logup_polys(self, air, trace, challenges, layout=0):
+        """logup_polys_replay's result from this context's device, through the kernels prove() uses (starkhip_logup_polys)."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        if trace.ndim != 2 or layout not in (0, 1):
+            raise StarkhipError(ERR_BAD_SHAPE)
+        n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+        challenges, polys, closing, zeros = _logup_args(air, n_rows, challenges)
+        _chk(lib.starkhip_logup_polys(self._ctx, air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, _p64(challenges), _p64(polys),
+                                      _p64(closing), _p64(zeros)))
+        return polys, closing, int(zeros[0])
+
+    def logup_polys_device(self, air, trace_ptr, n_rows, challenges, layout=1):
+        """logup_polys on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
+        challenges, polys, closing, zeros = _logup_args(air, n_rows, challenges)
+        _chk(lib.starkhip_logup_polys(self._ctx, air, C.c_void_p(trace_ptr), n_rows, air_columns(air), layout, 1, _p64(challenges), _p64(polys),
+                                      _p64(closing), _p64(zeros)))
+        return polys, closing, int(zeros[0])
 
     def permutation_zs_device(self, air, trace_ptr, n_rows, challenges, layout=1):
         """permutation_zs on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""

@@ -31,6 +31,11 @@
 //   AIR_PERM_MAGIC, n_pairs, then per pair: n_entries, n_entries words  lhs column | rhs column << 32.
 // A program without pairs has no section and keeps its bytes.  The pairs are cut into batches of B = max(1, degree - 1) in
 // declaration order; a batch has one Z polynomial per challenge (2), index batch * 2 + challenge.
+//
+// LogUp lookups (starky >= 0.2's Lookup { columns, table_column, frequencies_column }, COMPAT.md L1-L7): the OTHER optional section, in
+// the same place -- a program has pairs or LogUp lookups, not both --
+//   AIR_LOGUP_MAGIC, n_lookups, then per lookup: n_columns, table column | frequencies column << 32, n_columns column words.
+// A lookup's columns are cut in declaration order into helper batches of degree - 1 (logup.h has the polynomials' order).
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -51,6 +56,7 @@ enum : uint32_t { REF_NEXT = 1u << 30, REF_COMPL = 1u << 31, REF_COL_MASK = 0xFF
 static const uint32_t AIR_MAX_GROUP = 255;
 static const uint64_t AIR_MAGIC = 0x3152495F52494153ULL;  // "SAIR_IR1"
 static const uint64_t AIR_PERM_MAGIC = 0x3153524941504D50ULL;  // "PMPAIRS1": the section of permutation pairs
+static const uint64_t AIR_LOGUP_MAGIC = 0x3130535055474F4CULL;  // "LOGUPS01": the section of LogUp lookups
 
 // The rows a constraint of `kind` applies to, of a trace of n rows: the one rule of the device checkers' walker
 // (kernels_check.hip) and of the host replay (check_report.cpp).  Written without short-circuit operators: in the walker's loop
@@ -86,10 +92,24 @@ struct AirProgram {
     uint32_t perm_batch_size() const { return degree > 1 ? degree - 1 : 1; }  // B: quotient_degree_factor, and permutation_batch_size()
     uint32_t perm_batches() const { return (uint32_t)((perm_pairs.size() + perm_batch_size() - 1) / perm_batch_size()); }
     uint32_t perm_zs() const { return 2 * perm_batches(); }  // nZ: one Z per (batch, challenge)
+    // LogUp lookups: `cols` looked up in column `table` with the multiplicities in column `freq` (empty for every built-in AIR)
+    struct Logup {
+        std::vector<uint32_t> cols;
+        uint32_t table, freq;
+    };
+    std::vector<Logup> logups;
+    uint32_t logup_batch_size() const { return degree > 1 ? degree - 1 : 1; }
+    uint32_t logup_helpers(size_t l) const { return (uint32_t)((logups[l].cols.size() + logup_batch_size() - 1) / logup_batch_size()); }  // H_l
+    uint32_t logup_polys() const {  // nA = 2 sum (H_l + 1): per challenge and lookup the helpers, then Z
+        uint32_t a = 0;
+        for (size_t l = 0; l < logups.size(); l++) a += logup_helpers(l) + 1;
+        return 2 * a;
+    }
+    uint32_t logup_constraints() const { return logup_polys() + 2 * (uint32_t)logups.size(); }  // nL = 2 sum (H_l + 2)
 
     // blob layout (u64 words): magic, n_cols, n_pis, degree, n_constraints, n_consts,
     // n_code_words, n_groups, consts[], code[] (two u32 per u64, zero padded),
-    // group_off[] / group_k0[] packed as (off | k0<<32), then the section of permutation pairs if there are any
+    // group_off[] / group_k0[] packed as (off | k0<<32), then the section of permutation pairs or of LogUp lookups if there are any
     std::vector<uint64_t> serialize() const {
         std::vector<uint64_t> b;
         b.push_back(AIR_MAGIC);
@@ -114,6 +134,15 @@ struct AirProgram {
             for (const auto& pr : perm_pairs) {
                 b.push_back(pr.size());
                 b.insert(b.end(), pr.begin(), pr.end());
+            }
+        }
+        if (!logups.empty()) {
+            b.push_back(AIR_LOGUP_MAGIC);
+            b.push_back(logups.size());
+            for (const Logup& l : logups) {
+                b.push_back(l.cols.size());
+                b.push_back((uint64_t)l.table | ((uint64_t)l.freq << 32));
+                b.insert(b.end(), l.cols.begin(), l.cols.end());
             }
         }
         return b;
@@ -338,6 +367,16 @@ class AirBuilder {
         lookups_.push_back({input, table, permuted_input, permuted_table});
     }
     struct Lookup { uint32_t input, table, permuted_input, permuted_table; };  // as starkhip_lookup_t
+
+    // One LogUp lookup (COMPAT.md L1-L7): every cell of `columns` occurs in column `table`, and column `frequencies` holds, row by row,
+    // how often the row's table value is looked up.  No constraint is emitted here: the prover and the verifiers add the helper and Z
+    // constraints after the AIR's own.  The validator refuses it beside permutation pairs and at degree 1.
+    void logup(const std::vector<uint32_t>& columns, uint32_t table, uint32_t frequencies) {
+        for (uint32_t c : columns) check_col(c);
+        check_col(table);
+        check_col(frequencies);
+        prog_.logups.push_back({columns, table, frequencies});
+    }
     const std::vector<Lookup>& lookups() const { return lookups_; }
 
     uint32_t count() const { return prog_.n_constraints; }

@@ -26,8 +26,8 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
     if (n_groups < 1 || n_groups > n_code) return refuse(why, "n_groups " + std::to_string(n_groups) + " not in 1..code size");
     const uint64_t code_u64 = (n_code + 1) / 2;
     const uint64_t base_words = 8 + n_consts + code_u64 + n_groups;  // every count is below 2^27 here: no overflow
-    // what follows the group table is the section of permutation pairs, or nothing (a word that is not the section's magic is a wrong length)
-    if ((uint64_t)words < base_words || ((uint64_t)words > base_words && blob[base_words] != AIR_PERM_MAGIC))
+    // what follows the group table is the section of permutation pairs or of LogUp lookups, or nothing (a word that is neither section's magic is a wrong length)
+    if ((uint64_t)words < base_words || ((uint64_t)words > base_words && blob[base_words] != AIR_PERM_MAGIC && blob[base_words] != AIR_LOGUP_MAGIC))
         return refuse(why, "blob length " + std::to_string(words) + " differs from the " + std::to_string(base_words) + " words its header implies");
     const uint64_t* consts = blob + 8;
     const uint64_t* code64 = consts + n_consts;
@@ -106,7 +106,7 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
     if (k != n_constraints) return refuse(why, "n_constraints " + std::to_string(n_constraints) + " but the code has " + std::to_string(k));
 
     // ---- permutation pairs: every column a kernel will read is < n_cols, every count within what the proof header and the kernels carry
-    if ((uint64_t)words > base_words) {
+    if ((uint64_t)words > base_words && blob[base_words] == AIR_PERM_MAGIC) {
         const uint64_t* sec = blob + base_words;
         const uint64_t sec_words = (uint64_t)words - base_words;
         if (sec_words < 2) return refuse(why, "permutation section shorter than its 2-word header");
@@ -132,7 +132,44 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
             P.perm_pairs.emplace_back(sec + at, sec + at + ne);
             at += ne;
         }
+        if (at < sec_words && sec[at] == AIR_LOGUP_MAGIC)
+            return refuse(why, "permutation pairs and LogUp lookups together (the two share the middle matrix of a proof)");
         if (at != sec_words) return refuse(why, "trailing words after the permutation section");
+    }
+    // ---- LogUp lookups: the same for the other section
+    if ((uint64_t)words > base_words && blob[base_words] == AIR_LOGUP_MAGIC) {
+        const uint64_t* sec = blob + base_words;
+        const uint64_t sec_words = (uint64_t)words - base_words;
+        if (sec_words < 2) return refuse(why, "LogUp section shorter than its 2-word header");
+        const uint64_t n_lookups = sec[1];
+        if (n_lookups < 1 || n_lookups > STARKHIP_AIR_MAX_LOGUP_LOOKUPS)
+            return refuse(why, "LogUp section with " + std::to_string(n_lookups) + " lookups (1.." + std::to_string(STARKHIP_AIR_MAX_LOGUP_LOOKUPS) + ")");
+        if (degree < 2) return refuse(why, "LogUp lookups need degree >= 2 (a helper constraint has degree 1 + the columns of its batch)");
+        uint64_t at = 2;
+        for (uint64_t l = 0; l < n_lookups; l++) {
+            const std::string atl = "LogUp lookup " + std::to_string(l) + ": ";
+            if (sec_words - at < 2) return refuse(why, atl + "runs past the blob");
+            const uint64_t m = sec[at], table = sec[at + 1] & 0xFFFFFFFFu, freq = sec[at + 1] >> 32;
+            at += 2;
+            if (m < 1) return refuse(why, atl + "empty lookup");
+            if (m > STARKHIP_AIR_MAX_LOGUP_COLUMNS) return refuse(why, atl + std::to_string(m) + " columns (at most " + std::to_string(STARKHIP_AIR_MAX_LOGUP_COLUMNS) + ")");
+            if (table >= n_cols || freq >= n_cols) return refuse(why, atl + "column " + std::to_string(table >= n_cols ? table : freq) + " out of range");
+            if (sec_words - at < m) return refuse(why, atl + "columns run past the blob");
+            AirProgram::Logup lk;
+            lk.table = (uint32_t)table;
+            lk.freq = (uint32_t)freq;
+            for (uint64_t e = 0; e < m; e++) {
+                if (sec[at + e] >= n_cols) return refuse(why, atl + "column " + std::to_string(sec[at + e]) + " out of range");
+                lk.cols.push_back((uint32_t)sec[at + e]);
+            }
+            P.logups.push_back(std::move(lk));
+            at += m;
+        }
+        if (at < sec_words && sec[at] == AIR_PERM_MAGIC)
+            return refuse(why, "permutation pairs and LogUp lookups together (the two share the middle matrix of a proof)");
+        if (at != sec_words) return refuse(why, "trailing words after the LogUp section");
+        if (P.logup_polys() > STARKHIP_AIR_MAX_LOGUP_POLYS)
+            return refuse(why, "LogUp lookups make " + std::to_string(P.logup_polys()) + " auxiliary polynomials (at most " + std::to_string(STARKHIP_AIR_MAX_LOGUP_POLYS) + ")");
     }
     if (out) *out = std::move(P);
     return true;

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "lde_ranges.h"
 #include "lookup_columns.h"
+#include "logup.h"
 #include "permutation.h"
 #include "permutation_check.h"
 #include "trace_log.h"
@@ -164,6 +165,74 @@ int starkhip_air_eval_frame_full(starkhip_air_t air, const uint64_t* local, cons
         return STARKHIP_ERR_OOM;
     }
     return STARKHIP_OK;
+}
+
+int starkhip_air_logups(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->prog.logups.size() : STARKHIP_ERR_BAD_AIR; }
+int starkhip_air_logup_polys(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->prog.logup_polys() : STARKHIP_ERR_BAD_AIR; }
+
+int starkhip_air_eval_frame_logup(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
+                                  const uint64_t masks[8], const uint64_t* alphas, int n_alpha, const uint64_t* aux, const uint64_t* aux_next,
+                                  const uint64_t* challenges, uint64_t* acc_out) {
+    const int rc = starkhip_air_eval_frame(air, local, next, public_inputs, masks, alphas, n_alpha, acc_out);
+    if (rc != STARKHIP_OK) return rc;
+    const AirInfo* a = air_get(air);
+    const size_t nA = a->prog.logup_polys();
+    if (!nA) return STARKHIP_OK;
+    if (!aux || !aux_next || !challenges || challenges[0] >= GL_P || challenges[1] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
+    try {
+        std::vector<gl2_t> l(a->cols), x(nA), xn(nA), al(n_alpha), acc(n_alpha);
+        for (size_t i = 0; i < a->cols; i++) l[i] = gl2_make(local[2 * i], local[2 * i + 1]);
+        for (size_t i = 0; i < nA; i++) {
+            x[i] = ExtOps::canon(gl2_make(aux[2 * i], aux[2 * i + 1]));
+            xn[i] = ExtOps::canon(gl2_make(aux_next[2 * i], aux_next[2 * i + 1]));
+        }
+        gl2_t mk[4];
+        for (int i = 0; i < 4; i++) mk[i] = gl2_make(masks[2 * i], masks[2 * i + 1]);
+        for (int j = 0; j < n_alpha; j++) {
+            al[j] = gl2_make(alphas[2 * j], alphas[2 * j + 1]);
+            acc[j] = gl2_make(acc_out[2 * j], acc_out[2 * j + 1]);
+        }
+        logup_eval_folded<ExtOps>(a->prog, l.data(), x.data(), xn.data(), challenges, mk, al.data(), n_alpha, acc.data());
+        for (int j = 0; j < n_alpha; j++) {
+            acc_out[2 * j] = acc[j].a0;
+            acc_out[2 * j + 1] = acc[j].a1;
+        }
+    } catch (const std::bad_alloc&) {
+        return STARKHIP_ERR_OOM;
+    }
+    return STARKHIP_OK;
+}
+
+// what the two LogUp entries refuse: as the two Z entries below, for an AIR without LogUp lookups and the two challenges
+static int logup_polys_args(const AirInfo* a, const TraceInput& in, const uint64_t* challenges, const uint64_t* polys_out, const uint64_t* closing_out,
+                            const uint64_t* zero_denominators_out) {
+    if (!a || a->prog.logups.empty()) return STARKHIP_ERR_BAD_AIR;
+    if (in.check(*a) || !challenges || !polys_out || !closing_out || !zero_denominators_out || in.n_rows < 2 ||
+        in.n_rows > ((size_t)1 << STARKHIP_MAX_LOG_ROWS) || (in.n_rows & (in.n_rows - 1)) || challenges[0] >= GL_P || challenges[1] >= GL_P)
+        return STARKHIP_ERR_BAD_SHAPE;
+    return STARKHIP_OK;
+}
+
+int starkhip_logup_polys(void* ctx, starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                         const uint64_t* challenges, uint64_t* polys_out, uint64_t* closing_out, uint64_t* zero_denominators_out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = logup_polys_args(a, in, challenges, polys_out, closing_out, zero_denominators_out)) return rc;
+    return guarded([&] { return logup_polys((Ctx*)ctx, *a, in, challenges, polys_out, closing_out, zero_denominators_out); });
+}
+
+int starkhip_logup_polys_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, const uint64_t* challenges,
+                                uint64_t* polys_out, uint64_t* closing_out, uint64_t* zero_denominators_out) {
+    const AirInfo* a = air_get(air);
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = logup_polys_args(a, in, challenges, polys_out, closing_out, zero_denominators_out)) return rc;
+    return guarded([&] {
+        const bool col_major = in.form == TraceForm::ColMajor;
+        logup_polys_host(a->prog, n_rows, [&](uint32_t col, size_t row) { return col_major ? trace[(size_t)col * n_rows + row] : trace[row * n_cols + col]; }, challenges,
+                         polys_out, closing_out, zero_denominators_out);
+        return (int)STARKHIP_OK;
+    });
 }
 
 // what the two Z entries refuse: an AIR that is unknown or has no pairs (BAD_AIR); a trace argument that cannot be one of it, rows that
@@ -669,7 +738,7 @@ int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_pr
     out->off_pow_witness = pl.off_pow; out->off_public_inputs = pl.off_pis; out->total_words = pl.total;
     const size_t d0 = pl.log_N - pl.cap_h;
     out->q_trace_leaf = t.q_leaf; out->q_trace_siblings = t.q_sib; out->q_quotient_leaf = q.q_leaf; out->q_quotient_siblings = q.q_sib;
-    out->n_permutation_zs = z.cols; out->off_permutation_zs_cap = z.off_cap; out->off_permutation_zs = z.off_open[0];
+    out->n_permutation_zs = pl.nZ; out->n_logup_polys = pl.nA; out->off_permutation_zs_cap = z.off_cap; out->off_permutation_zs = z.off_open[0];
     out->off_permutation_zs_next = z.off_open[1]; out->q_permutation_zs_leaf = z.q_leaf; out->q_permutation_zs_siblings = z.q_sib;
     size_t o = q.q_sib + 4 * d0;
     for (size_t l = 0; l < pl.L && l < 16; l++) {

@@ -204,6 +204,10 @@ struct Ctx {
         DevBuf cons, pivots, planes, class_counts;
         std::vector<DevBuf*> bufs() { return {&cons, &pivots, &planes, &class_counts}; }
     } free_chk;
+    // The middle matrix of a proof.  An AIR with LogUp lookups (COMPAT.md L1 - L7) uses the same slots, its auxiliary polynomials in the
+    // Zs' place: cols the named columns, desc the two descriptors and then the Zs' polynomial indices, zvals / zcoef / zlde / zdigests
+    // and the openings the auxiliary matrix, scan the spans' sums followed by the closing values and the count of zero denominators
+    // (chal is not used: the two challenges travel as kernel arguments).
     // permutation arguments (an AIR with permutation pairs; COMPAT.md P1 - P8), all empty otherwise -- work buffers of a proof, sized
     // by work_buffers() like the ones above: the pair columns copied aside at upload (a short trace parked in the LDE buffer is
     // overwritten by its LDE), the two descriptors (by copy slot, by trace column) and the challenges, the Zs' values, their

@@ -7,7 +7,9 @@
 #include <vector>
 
 #include "ctx.h"
+#include "kernels_logup.h"
 #include "kernels_permutation.h"
+#include "logup.h"
 #include "permutation.h"
 
 namespace starkhip {
@@ -38,6 +40,43 @@ int permutation_zs(Ctx* c, const AirInfo& air, const TraceInput& in, const uint6
     HIPCHK(hipMemcpyAsync(zs_out, pb.zvals.p, nZ * n * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipMemcpyAsync(closing_out, d_closing, nZ * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(stream_wait(c));
+    return STARKHIP_OK;
+}
+
+// kernel-level test entry: the auxiliary polynomials of `air` on the caller's trace as prove() computes them -- the named columns gathered
+// into the copy prove() keeps aside (the slots of the pairs' buffers: Ctx::PermBufs), then launch_logup_polys.  The caller has checked
+// the trace argument, the rows and the challenges.
+int logup_polys(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* challenges, uint64_t* polys_out, uint64_t* closing_out, uint64_t* zero_denominators_out) {
+    const AirProgram& P = air.prog;
+    const size_t n = in.n_rows, C = in.n_cols, nA = P.logup_polys();
+    const unsigned nzs = 2 * (unsigned)P.logups.size();
+    HIPCHK(hipSetDevice(c->device));
+    const std::vector<uint32_t> cols = logup_columns(P);
+    std::vector<uint32_t> desc = logup_descriptor(P, true);
+    const size_t desc_words = desc.size();
+    const std::vector<uint32_t> zp = logup_z_polys(P);
+    desc.insert(desc.end(), zp.begin(), zp.end());
+    Ctx::PermBufs& pb = c->perm;
+    HIPCHK(c->values.ensure(C * n * 8));
+    HIPCHK(c->lde.ensure(C * n * 8));  // upload_dense stages host rows there
+    HIPCHK(pb.cols.ensure(cols.size() * n * 8));
+    HIPCHK(pb.desc.ensure(desc.size() * 4));
+    HIPCHK(pb.zvals.ensure(nA * n * 8));
+    HIPCHK(pb.scan.ensure((logup_scratch_words(n, nzs) + logup_result_words(nzs)) * 8));
+    const gl_t* d_values = nullptr;
+    if (int rc = upload_dense(c, in, c->values.as<gl_t>(), &d_values)) return rc;
+    for (size_t k = 0; k < cols.size(); k++)
+        HIPCHK(hipMemcpyAsync(pb.cols.as<gl_t>() + k * n, d_values + (size_t)cols[k] * n, n * 8, hipMemcpyDeviceToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(pb.desc.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, c->st));
+    gl_t* const d_results = pb.scan.as<gl_t>() + logup_scratch_words(n, nzs);
+    HIPCHK(launch_logup_polys(pb.desc.as<uint32_t>(), pb.desc.as<uint32_t>() + desc_words, pb.cols.as<gl_t>(), n, challenges[0], challenges[1], n, nzs,
+                              pb.zvals.as<gl_t>(), pb.scan.as<gl_t>(), d_results, c->st));
+    std::vector<gl_t> results(logup_result_words(nzs));
+    HIPCHK(hipMemcpyAsync(polys_out, pb.zvals.p, nA * n * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(results.data(), d_results, results.size() * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    std::copy(results.begin(), results.begin() + nzs, closing_out);
+    *zero_denominators_out = results[nzs];
     return STARKHIP_OK;
 }
 

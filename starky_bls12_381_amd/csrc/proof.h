@@ -53,7 +53,7 @@ inline unsigned quotient_degree_bits(unsigned degree) {
     return qdb;
 }
 
-// One matrix of polynomials a proof commits -- in proof order the trace, the permutation Zs of an AIR with pairs, the quotient -- and where its words are.  A proof
+// One matrix of polynomials a proof commits -- in proof order the trace, the middle matrix (the permutation Zs of an AIR with pairs, or the auxiliary polynomials of one with LogUp lookups), the quotient -- and where its words are.  A proof
 // treats them alike (a cap in the transcript, openings, a run of powers of the FRI alpha, a leaf and a path per query round), so the prover and both verifiers walk ProofLayout::mat.
 struct MatrixLayout {
     size_t cols, off_cap;           // polynomials (a leaf's words), and its cap [2^cap_h][4]
@@ -65,9 +65,11 @@ struct ProofLayout {
     size_t C, Q, log_n, rate_bits, cap_h, L, n_queries, final_len, n_pis, arity_bits, n_challenges;
     size_t hasher = 0;  // header word 12: STARKHIP_HASHER_POSEIDON (0, what the word has always been) or STARKHIP_HASHER_KECCAK
     size_t nZ = 0;      // header word 13: permutation Z polynomials (0, what the word has always been, for an AIR without pairs)
+    size_t nA = 0;      // header word 14: LogUp auxiliary polynomials (0, what the word has always been, for an AIR without LogUp lookups); never beside nZ
     size_t ncap;     // 2^cap_h
     size_t log_N;
-    MatrixLayout mat[3];  // the committed matrices, n_mats of them: trace, Zs if nZ > 0, quotient (the last)
+    MatrixLayout mat[3];  // the committed matrices, n_mats of them: trace, the middle matrix if nZ + nA > 0, quotient (the last)
+    size_t middle() const { return nZ + nA; }  // the middle matrix's polynomials (one of the two is 0)
     size_t n_mats = 0;
     size_t batch_cols[2];  // polynomials opened at zeta (all) and at g zeta: the lengths of the two FRI batches
     // offsets (in words) of what follows the matrices' caps and openings
@@ -82,6 +84,7 @@ struct ProofLayout {
         pl.L = geo.arities.size(); pl.n_queries = cfg.num_query_rounds; pl.final_len = geo.final_poly_len; pl.n_pis = P.n_pis;
         pl.arity_bits = cfg.arity_bits; pl.n_challenges = 2;
         pl.nZ = P.perm_zs();
+        pl.nA = P.logup_polys();
         pl.compute();
         return pl;
     }
@@ -90,8 +93,8 @@ struct ProofLayout {
         ncap = (size_t)1 << cap_h;
         log_N = log_n + rate_bits;
         const size_t d0 = log_N - cap_h;
-        n_mats = nZ ? 3 : 2;
-        mat[0].cols = C; mat[1].cols = nZ; mat[n_mats - 1].cols = Q;
+        n_mats = middle() ? 3 : 2;
+        mat[0].cols = C; mat[1].cols = middle(); mat[n_mats - 1].cols = Q;
         size_t o = 16 + n_mats * 4 * ncap, q = 0;  // the caps back to back, then the openings matrix by matrix
         batch_cols[0] = batch_cols[1] = 0;
         for (size_t k = 0; k < n_mats; k++) {
@@ -127,13 +130,14 @@ struct ProofLayout {
         h[7] = n_queries; h[8] = final_len; h[9] = n_pis; h[10] = arity_bits; h[11] = n_challenges;
         h[12] = hasher;
         h[13] = nZ;
-        h[14] = h[15] = 0;
+        h[14] = nA;
+        h[15] = 0;
     }
     bool read_header(const uint64_t* h, size_t words) {
         if (words < 16 || h[0] != STARKHIP_PROOF_MAGIC) return false;
         C = h[1]; Q = h[2]; log_n = h[3]; rate_bits = h[4]; cap_h = h[5]; L = h[6]; n_queries = h[7]; final_len = h[8];
-        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11]; hasher = h[12]; nZ = h[13];
-        if (hasher > STARKHIP_HASHER_KECCAK || nZ > 128) return false;
+        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11]; hasher = h[12]; nZ = h[13]; nA = h[14];
+        if (hasher > STARKHIP_HASHER_KECCAK || nZ > 128 || nA > STARKHIP_AIR_MAX_LOGUP_POLYS || (nZ && nA)) return false;
         if (log_n > 32 || rate_bits > 8 || cap_h > 16 || L > 16 || arity_bits > 8 || log_n + rate_bits < cap_h) return false;
         if (L * arity_bits + cap_h > log_n + rate_bits) return false;
         compute();

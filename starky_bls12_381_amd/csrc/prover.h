@@ -120,6 +120,9 @@ int field_ops(Ctx* c, int op, const uint64_t* a, const uint64_t* b, uint64_t* ou
 // starkhip_permutation_zs: the Z polynomials of an AIR with permutation pairs on one trace, through the kernels prove() uses
 // (kernels_permutation.hip); challenges B x 2 x {beta, gamma}, zs_out [nZ][n_rows], closing_out [nZ]
 int permutation_zs(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* challenges, uint64_t* zs_out, uint64_t* closing_out);
+// starkhip_logup_polys: the auxiliary polynomials of an AIR with LogUp lookups on one trace, through the kernels prove() uses
+// (kernels_logup.hip); challenges {chi_0, chi_1}, polys_out [nA][n_rows], closing_out [2][n_lookups], the count of zero denominators
+int logup_polys(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* challenges, uint64_t* polys_out, uint64_t* closing_out, uint64_t* zero_denominators_out);
 int host_alloc(Ctx* c, size_t bytes, void** out);
 void host_free(void* p);
 

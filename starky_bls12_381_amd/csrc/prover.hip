@@ -3,7 +3,7 @@
 // of phases (the methods of ProveCall), sized and laid out by one ProofShape and one table of work buffers that ctx_reserve() shares;
 // every heavy step is one of the kernels in kernels_*.hip, the host only runs the Fiat-Shamir challenger, two length-n synthetic
 // divisions and the proof assembly.  What a proof commits is a list of matrices in proof order (ProveCall::mats beside ProofLayout::mat): the trace, the Zs of an
-// AIR with permutation pairs (COMPAT.md P1 - P8; made and committed at the start of the quotient phase, ProveCall::permutation), the quotient.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
+// AIR with permutation pairs (COMPAT.md P1 - P8; made and committed at the start of the quotient phase, ProveCall::permutation) or the auxiliary polynomials of one with LogUp lookups (L1 - L7; ProveCall::logup, in the same place and the same buffers), the quotient.  Below prove(): the pool's reservation.  The context and its caches are ctx.h / ctx.hip, the trace
 // checkers' host halves check_trace.hip and permutation_check.hip, the kernel-level entry points of the tests kernel_entries.hip.
 #include <hip/hip_runtime.h>
 
@@ -20,8 +20,10 @@
 #include "check_report.h"
 #include "ctx.h"
 #include "kernels.h"
+#include "kernels_logup.h"
 #include "kernels_permutation.h"
 #include "lde_ranges.h"
+#include "logup.h"
 #include "permutation.h"
 #include "trace_log.h"
 #include "poseidon.h"
@@ -98,6 +100,8 @@ struct ProofShape {
     unsigned log_n, r, cap_h, log_N, qdb, factor;  // log2 of rows, blow-up, cap size, LDE points; the quotient's degree bits and factor
     size_t n, N, C, Q, size, ncap, L;              // rows, LDE points, trace and quotient columns, quotient points (n << qdb), cap nodes, FRI layers
     size_t nZ, perm_cols, perm_desc_words;         // permutation pairs: Z polynomials, the columns the pairs name, words of one descriptor (0 without pairs)
+    size_t nA, nLZ;                                // LogUp lookups: auxiliary polynomials and, of them, the Zs (2 per lookup); perm_cols and perm_desc_words are then theirs
+    size_t mid;                                    // the middle matrix's polynomials: nZ or nA (never both), 0 without either
     FriGeometry geo;
     ProofLayout pl;
     // STARKHIP_ERR_BAD_SHAPE for what prove() refuses: rows that are no power of two in 2 .. 2^max_log_rows(air), a config that the one
@@ -112,6 +116,8 @@ struct ProofShape {
         s->n = n_rows; s->N = s->n << s->r; s->C = P.n_cols; s->Q = (size_t)s->factor * 2; s->size = s->n << s->qdb;
         s->ncap = (size_t)1 << s->cap_h; s->L = s->geo.arities.size();
         s->nZ = P.perm_zs(); s->perm_cols = s->nZ ? perm_columns(P).size() : 0; s->perm_desc_words = s->nZ ? perm_descriptor(P, false).size() : 0;
+        s->nA = P.logup_polys(); s->nLZ = 2 * P.logups.size(); s->mid = s->nZ + s->nA;
+        if (s->nA) { s->perm_cols = logup_columns(P).size(); s->perm_desc_words = logup_descriptor(P, false).size(); }
         s->pl = ProofLayout::make(P, cfg, s->geo, log_n);
         return STARKHIP_OK;
     }
@@ -141,17 +147,18 @@ static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n
         {&c->zpow, 2 * n * 16},  // powers of zeta (the quotient polynomials' openings), then the coset-0 weights of zeta
         {&c->gzpow, n * 16},     // the weights of g zeta
         {&c->open_local, C * 16}, {&c->open_next, C * 16}, {&c->open_q, Q * 16}, {&c->ext_apow, s.pl.batch_cols[0] * 16},
-        {&c->comb_partial, (comb_chunks(C) + s.pl.n_mats - 2) * n * 16},  // (the Zs' sum is one more chunk)
+        {&c->comb_partial, (comb_chunks(C) + comb_chunks(s.mid)) * n * 16},  // (the middle matrix's sum: one more chunk for the Zs, up to four for LogUp)
         {&c->comb_out, 2 * n * 16}, {&c->fri_coef, 2 * N * 8}, {&c->fri_vals, 2 * N * 8},
         {&c->scale_tab, N * 8}, {&c->pow_state, 12 * 8}, {&c->pow_best, 8}, {&c->qidx, nq * 4},
         {&c->gather_t, nq * s.pl.query_words * 8},  // every query round's leaves and Merkle paths, in proof layout
         // the leaf hash's saved state past an identity prefix and its counter, kept with the shape's tables (ctx.h); 0 where this proof cannot use it
         {&c->tab->leaf_prefix, leaf_prefix_bytes(c, C, s.log_n, s.r)}};
-    if (const size_t nZ = s.nZ) {  // an AIR with permutation pairs (Ctx::PermBufs)
+    if (const size_t nZ = s.mid) {  // an AIR with permutation pairs or with LogUp lookups: the middle matrix (Ctx::PermBufs)
         Ctx::PermBufs& pb = c->perm;
-        for (const BufWant& b : {BufWant{&pb.cols, s.perm_cols * n * 8}, BufWant{&pb.desc, 2 * s.perm_desc_words * 4}, BufWant{&pb.chal, 4 * (size_t)s.factor * 8},
+        const size_t scan_words = s.nA ? logup_scratch_words(n, (unsigned)s.nLZ) + logup_result_words((unsigned)s.nLZ) : perm_scratch_words(n, (unsigned)nZ) + nZ;
+        for (const BufWant& b : {BufWant{&pb.cols, s.perm_cols * n * 8}, BufWant{&pb.desc, (2 * s.perm_desc_words + s.nLZ) * 4}, BufWant{&pb.chal, 4 * (size_t)s.factor * 8},
                                  BufWant{&pb.zvals, nZ * n * 8}, BufWant{&pb.zcoef, lde_long_supported(s.log_n) ? nZ * n * 8 : 0}, BufWant{&pb.zlde, nZ * N * 8},
-                                 BufWant{&pb.zdigests, digest_words(N) * 8}, BufWant{&pb.scan, (perm_scratch_words(n, (unsigned)nZ) + nZ) * 8},
+                                 BufWant{&pb.zdigests, digest_words(N) * 8}, BufWant{&pb.scan, scan_words * 8},
                                  BufWant{&pb.open_z, nZ * 16}, BufWant{&pb.open_zn, nZ * 16}})
             w.push_back(b);
     }
@@ -210,7 +217,7 @@ struct ProveCall {
     const gl_t* d_values = nullptr;  // where it is: d_trace, or the caller's own device memory
     Challenger ch;
     HostWatch fs, host_other;  // Fiat-Shamir hashing / other host arithmetic of this proof
-    // The committed matrix that s.pl.mat[k] lays out (trace, Zs of an AIR with pairs, quotient): the context's own buffers (ctx.h),
+    // The committed matrix that s.pl.mat[k] lays out (trace, Zs of an AIR with pairs or auxiliary polynomials of one with LogUp lookups, quotient): the context's own buffers (ctx.h),
     // only pointed at, and the host vectors its cap's and its openings' read-backs land in.  (Without Zs the third record is unused.)
     struct Committed {
         DevBuf *lde, *digests;  // its LDE, column-major, and the Merkle tree over its bit-reversed rows
@@ -219,14 +226,17 @@ struct ProveCall {
         std::vector<gl_t> cap;
         std::vector<gl2_t> open[2];
     } mats[3] = {{&c->lde, &c->digests, {&c->open_local, &c->open_next}},
-                 s.nZ ? Committed{&c->perm.zlde, &c->perm.zdigests, {&c->perm.open_z, &c->perm.open_zn}} : Committed{&c->qlde, &c->qdigests, {&c->open_q}, &c->qcoef},
+                 s.mid ? Committed{&c->perm.zlde, &c->perm.zdigests, {&c->perm.open_z, &c->perm.open_zn}} : Committed{&c->qlde, &c->qdigests, {&c->open_q}, &c->qcoef},
                  {&c->qlde, &c->qdigests, {&c->open_q}, &c->qcoef}};
     std::vector<gl_t> quot_tail, fri_caps;
     std::vector<gl2_t> final_poly;
-    // an AIR with permutation pairs: the challenges (B sets of 2 x {beta, gamma}), the two descriptors back to back (by copy slot, by trace column)
+    // an AIR with permutation pairs: the challenges (B sets of 2 x {beta, gamma}), the two descriptors back to back (by copy slot, by trace column;
+    // for LogUp lookups theirs, followed by the Zs' polynomial indices)
     std::vector<gl_t> perm_chal;
     std::vector<uint32_t> perm_desc;
     int permutation();
+    gl_t logup_chal[2] = {0, 0};  // an AIR with LogUp lookups: chi_0, chi_1
+    int logup();
     gl_t alphas[2] = {0, 0};
     gl2_t zeta = gl2_zero();
     uint64_t* out = nullptr;  // the proof blob, from queries() on -- or the check blob of a trace that upload() refused
@@ -331,8 +341,8 @@ int ProveCall::upload() {
     // "check_trace": every constraint on every row of the trace where the upload has just put it, before anything of the LDE is
     // enqueued; a violating trace ends the proof here with STARKHIP_ERR_TRACE and its check blob in `out`
     if (rc == 0 && c->opt_check_trace) rc = check_trace_in_prove(c, air, d_values, s.n, pis_host, &out, &check_words);
-    if (rc == 0 && s.nZ) {  // the columns the permutation pairs name, aside: the LDE overwrites a parked trace and keeps no coefficients of it
-        const std::vector<uint32_t> cols = perm_columns(air.prog);
+    if (rc == 0 && s.mid) {  // the columns the permutation pairs (or the LogUp lookups) name, aside: the LDE overwrites a parked trace and keeps no coefficients of it
+        const std::vector<uint32_t> cols = s.nA ? logup_columns(air.prog) : perm_columns(air.prog);
         for (size_t k = 0; k < cols.size(); k++)
             HIPCHK(hipMemcpyAsync(c->perm.cols.as<gl_t>() + k * s.n, d_values + (size_t)cols[k] * s.n, s.n * 8, hipMemcpyDeviceToDevice, st));
     }
@@ -527,6 +537,38 @@ int ProveCall::permutation() {
     return 0;
 }
 
+// ---- phase 3, for an AIR with LogUp lookups (COMPAT.md L1 - L3; timed with the quotient), the twin of permutation(): the two challenges,
+// the auxiliary polynomials from the copy of the named columns, their closing values and the count of zero denominators in one wait --
+// a sum that does not close, or any zero denominator, ends the proof here with QUOTIENT_NOT_DIVISIBLE before anything is committed --
+// then the LDE, the commitment under the context's hasher and the cap into the transcript
+int ProveCall::logup() {
+    const AirProgram& P = air.prog;
+    const size_t n = s.n, nA = s.nA;
+    const unsigned nzs = (unsigned)s.nLZ;
+    fs.start();
+    for (gl_t& x : logup_chal) x = ch.get();  // L1
+    fs.stop();
+    perm_desc = logup_descriptor(P, true);  // by copy slot, by trace column, the Zs' polynomial indices
+    for (const std::vector<uint32_t>& more : {logup_descriptor(P, false), logup_z_polys(P)}) perm_desc.insert(perm_desc.end(), more.begin(), more.end());
+    Ctx::PermBufs& pb = c->perm;
+    HIPCHK(hipMemcpyAsync(pb.desc.p, perm_desc.data(), perm_desc.size() * 4, hipMemcpyHostToDevice, st));
+    gl_t* const d_results = pb.scan.as<gl_t>() + logup_scratch_words(n, nzs);
+    HIPCHK(launch_logup_polys(pb.desc.as<uint32_t>(), pb.desc.as<uint32_t>() + 2 * s.perm_desc_words, pb.cols.as<gl_t>(), n, logup_chal[0], logup_chal[1], n, nzs,
+                              pb.zvals.as<gl_t>(), pb.scan.as<gl_t>(), d_results, st));
+    std::vector<gl_t> results(logup_result_words(nzs));
+    HIPCHK(read_back(c, results.data(), d_results, results.size() * 8, st));
+    HIPCHK(stream_wait(c));
+    for (gl_t v : results)  // the closing values, then the zero denominators
+        if (v != 0) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
+    HIPCHK(run_lde(c, pb.zvals.as<gl_t>(), lde_long_supported(s.log_n) ? pb.zcoef.as<gl_t>() : nullptr, pb.zlde.as<gl_t>(), nA, s.log_n, s.r, 0));
+    if (int rc = commit_narrow(mats[1], nA)) return rc;
+    HIPCHK(stream_wait(c));
+    fs.start();
+    ch.observe_many(mats[1].cap.data(), mats[1].cap.size());
+    fs.stop();
+    return 0;
+}
+
 // ---- phase 3: quotient polynomials (App. A.6)
 int ProveCall::quotient() {
     const size_t n = s.n, size = s.size, factor = s.factor;
@@ -536,6 +578,8 @@ int ProveCall::quotient() {
     fs.stop();
     if (s.nZ)
         if (int rc = permutation()) return rc;
+    if (s.nA)
+        if (int rc = logup()) return rc;
     fs.start();
     alphas[0] = ch.get();
     alphas[1] = ch.get();
@@ -552,6 +596,12 @@ int ProveCall::quotient() {
             HIPCHK(launch_perm_quotient(c->perm.desc.as<uint32_t>() + s.perm_desc_words, c->lde.as<gl_t>(), c->perm.zlde.as<gl_t>(), c->perm.chal.as<gl_t>(),
                                         c->tab->qtab.as<gl_t>(), c->qvals.as<gl_t>(), alphas[0], alphas[1], gl_pow(alphas[0], 2 * s.nZ), gl_pow(alphas[1], 2 * s.nZ),
                                         s.log_n, s.r, s.qdb, st));
+        if (s.nA) {  // L4: the LogUp constraints likewise (kernels_logup.hip)
+            const uint64_t nL = air.prog.logup_constraints();
+            HIPCHK(launch_logup_quotient(c->perm.desc.as<uint32_t>() + s.perm_desc_words, c->lde.as<gl_t>(), c->perm.zlde.as<gl_t>(), logup_chal[0], logup_chal[1],
+                                         c->tab->qtab.as<gl_t>(), c->qvals.as<gl_t>(), alphas[0], alphas[1], gl_pow(alphas[0], nL), gl_pow(alphas[1], nL), s.log_n, s.r,
+                                         s.qdb, st));
+        }
         // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
         if (int rc = run_ntt(c, c->qvals.as<gl_t>(), c->partial.as<gl_t>(), 2, size, s.log_n + s.qdb, true, nullptr, c->tab->qshift_inv.as<gl_t>()))  // (the chunks' partial sums are spent)
             return rc;
@@ -835,7 +885,7 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     const bool tiled = c->opt_quotient_impl == 0;
     // the profiling modes and the evaluators' comparison run every constraint on every coset, like "quotient_cosets" = 1
     // ... and so does an AIR with permutation pairs: their constraints join the quotient's values, which the classes never form
-    const bool by_class = tiled && c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0 && s.nZ == 0;
+    const bool by_class = tiled && c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0 && s.mid == 0;
     if (int rc = tiled ? ensure_plan(c, air, s.size, by_class) : ensure_program(c, air, s.size)) return rc;
     const unsigned n_chunks = tiled ? c->plan->chunks : c->prog.chunks;
 
@@ -914,7 +964,7 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t
     if (ProofShape::make(air, cfg, air.default_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     HIPCHK(hipSetDevice(c->device));
     if (int rc = ensure_tables(c, s.log_n, s.r, s.qdb)) return rc;
-    if (int rc = ensure_plan(c, air, s.size, c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0 && s.nZ == 0)) return rc;
+    if (int rc = ensure_plan(c, air, s.size, c->opt_quotient_cosets == 0 && c->opt_quotient_debug == 0 && s.mid == 0)) return rc;
     // `values`: a trace waits for its LDE inside the LDE buffer (prove(): trace_in_lde) but for the tail of run_lde_trace; rate_bits == 0
     // makes prove() ask for a whole trace.  The LDE buffer also stages the upload: a recording of log_bytes.
     const size_t values_bytes = values_bytes_for(s, s.r >= 1, false);

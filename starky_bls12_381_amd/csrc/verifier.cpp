@@ -12,6 +12,7 @@
 
 #include "air_eval.h"
 #include "airs.h"
+#include "logup.h"
 #include "permutation.h"
 #include "poseidon.h"
 #include "proof.h"
@@ -85,7 +86,7 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     const unsigned factor = quotient_factor(P.degree);
     if (pl.C != P.n_cols || pl.n_pis != P.n_pis || pl.rate_bits != cfg.rate_bits || pl.cap_h != cfg.cap_height ||
         pl.n_queries != cfg.num_query_rounds || pl.n_challenges != cfg.num_challenges || pl.Q != (size_t)factor * cfg.num_challenges ||
-        pl.arity_bits != cfg.arity_bits || pl.nZ != P.perm_zs())
+        pl.arity_bits != cfg.arity_bits || pl.nZ != P.perm_zs() || pl.nA != P.logup_polys())
         return STARKHIP_ERR_BAD_SHAPE;
     const size_t skip_lo = check_query_words ? words : pl.off_queries, skip_hi = check_query_words ? words : pl.off_final;
     for (size_t i = 16; i < skip_lo; i++)
@@ -114,6 +115,10 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     // permutation challenges (COMPAT.md P1): B sets of 2 x (beta, gamma) after the trace cap, then the Z cap (P3), then the alphas
     std::vector<gl_t> perm_chal(nZ ? (size_t)P.perm_batch_size() * 4 : 0);
     for (gl_t& x : perm_chal) x = ch.get();
+    // LogUp challenges (COMPAT.md L1): chi_0, chi_1 in the same place, then the auxiliary cap (L3)
+    gl_t logup_chal[2] = {0, 0};
+    if (pl.nA)
+        for (gl_t& x : logup_chal) x = ch.get();
     for (size_t k = 1; k < last; k++) ch.observe_many(proof + pl.mat[k].off_cap, 4 * ncap);
     std::vector<gl2_t> alphas(cfg.num_challenges);
     for (auto& a : alphas) a = gl2_from_base(ch.get());
@@ -149,6 +154,7 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     std::vector<gl2_t> acc(cfg.num_challenges);
     air_eval_folded<ExtOps>(P, op_local, op_next, pis, masks, alphas.data(), (int)cfg.num_challenges, acc.data());
     if (nZ) perm_eval_folded<ExtOps>(P, op_local, opened(1, 0), opened(1, 1), perm_chal.data(), masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // P4
+    if (pl.nA) logup_eval_folded<ExtOps>(P, op_local, opened(1, 0), opened(1, 1), logup_chal, masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // L4
     for (unsigned i = 0; i < cfg.num_challenges; i++) {
         gl2_t s = gl2_zero();
         for (unsigned k = factor; k-- > 0;) s = gl2_add(gl2_mul(s, zeta_n), op_q[i * factor + k]);

@@ -77,7 +77,7 @@ void verify_chunk_add(VerifyChunk& ch, size_t id, const VerifyPrelude& pre) {
     P.query_words = pl.query_words;
     P.off_quot_cap = pl.quotient().off_cap - pl.mat[0].off_cap;
     P.off_zs_cap = 4 * pl.ncap;
-    P.nZ = (uint32_t)pl.nZ;
+    P.nZ = (uint32_t)pl.middle();  // the middle matrix, whichever kind
     P.off_fri_caps = h;
     P.off_queries = h + (pl.off_queries - pl.off_fri_caps);
     P.off_final = h + (pl.off_final - pl.off_fri_caps);

@@ -42,7 +42,7 @@ struct VQProof {
     uint32_t first_digest;  // global slot of query 0's trace-leaf digest; query q's are first_digest + q vq_slots(P) + {0: trace, 1: quotient, 2 + l: layer l, 2 + L: Z}
     uint32_t arity_bits[VQ_MAX_LAYERS], layer_depth[VQ_MAX_LAYERS];
     uint32_t hasher;        // the proof's hasher id (header word 12): every Merkle path of its queries is checked under it
-    uint32_t nZ;            // permutation Z polynomials (header word 13); 0: no Z cap, leaf or digest
+    uint32_t nZ;            // polynomials of the middle matrix: permutation Zs (header word 13) or LogUp auxiliary polynomials (word 14); 0: no such cap, leaf or digest
     uint64_t off_zs_cap;    // within the region (nZ > 0)
     gl2_t zeta, gzeta, red0, red1, alpha_pow_C;
     gl2_t betas[VQ_MAX_LAYERS];

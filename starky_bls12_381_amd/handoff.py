@@ -15,6 +15,10 @@ they are NOT under /root/reference and there is no Rust toolchain here, so this 
 with F = canonical u64 (GoldilocksField is a transparent newtype), Ext = [a0, a1] (QuadraticExtension is a newtype over
 [F; 2]), HashOut = {"elements": [F; 4]}, MerkleCap a newtype over Vec<HashOut>.  Python ints keep all 64 bits;
 `dumps` writes them as JSON numbers, as serde_json does for u64.
+
+A proof of an AIR with LogUp lookups (header word 14, nA > 0) has starky >= 0.2's names instead: "auxiliary_polys_cap" in the place of
+"permutation_zs_cap", and "auxiliary_polys" / "auxiliary_polys_next" among the openings (equally from memory, COMPAT.md 6.2); the
+three permutation keys are absent from such a value.  A proof without LogUp lookups has the value it always had.
 """
 import json
 
@@ -31,6 +35,10 @@ class _Layout:
         (self.C, self.Q, self.log_n, self.rate_bits, self.cap_h, self.L, self.n_queries, self.final_len, self.n_pis, self.arity_bits,
          self.n_challenges) = h[1:12]
         self.nZ = h[13]  # permutation Z polynomials: 0 for an AIR without permutation pairs
+        self.nA = h[14]  # LogUp auxiliary polynomials: 0 for an AIR without LogUp lookups; they take the Zs' place in the blob
+        if self.nZ and self.nA:
+            raise ValueError("a proof has permutation Zs or LogUp auxiliary polynomials, not both")
+        self.mid = self.nZ or self.nA
         self.ncap = 1 << self.cap_h
         self.log_N = self.log_n + self.rate_bits
         self.depth0 = self.log_N - self.cap_h
@@ -42,7 +50,7 @@ class _Layout:
 
     def header(self):
         return [MAGIC, self.C, self.Q, self.log_n, self.rate_bits, self.cap_h, self.L, self.n_queries, self.final_len, self.n_pis, self.arity_bits,
-                self.n_challenges, 0, self.nZ, 0, 0]
+                self.n_challenges, 0, self.nZ, self.nA, 0]
 
 
 def _hashes(words):
@@ -71,18 +79,18 @@ def proof_to_value(blob):
         pos += n
         return out
     trace_cap = _hashes(take(4 * lay.ncap))
-    zs_cap = _hashes(take(4 * lay.ncap)) if lay.nZ else None  # Option<MerkleCap>: Some for an AIR with permutation pairs
+    zs_cap = _hashes(take(4 * lay.ncap)) if lay.mid else None  # Option<MerkleCap>: Some for an AIR with permutation pairs (or LogUp lookups)
     quot_cap = _hashes(take(4 * lay.ncap))
     local_values = _exts(take(2 * lay.C))
     next_values = _exts(take(2 * lay.C))
-    zs = _exts(take(2 * lay.nZ)) if lay.nZ else None
-    zs_next = _exts(take(2 * lay.nZ)) if lay.nZ else None
+    zs = _exts(take(2 * lay.mid)) if lay.mid else None
+    zs_next = _exts(take(2 * lay.mid)) if lay.mid else None
     quotient_polys = _exts(take(2 * lay.Q))
     caps = [_hashes(take(4 * lay.ncap)) for _ in range(lay.L)]
     rounds = []
     for _ in range(lay.n_queries):
         evals_proofs = []
-        for width in ((lay.C, lay.nZ, lay.Q) if lay.nZ else (lay.C, lay.Q)):  # the oracles: trace, [permutation Zs,] quotient polys
+        for width in ((lay.C, lay.mid, lay.Q) if lay.mid else (lay.C, lay.Q)):  # the oracles: trace, [permutation Zs or auxiliary polys,] quotient polys
             leaf = [int(x) for x in take(width)]
             evals_proofs.append([leaf, {"siblings": _hashes(take(4 * lay.depth0))}])
         steps = []
@@ -95,6 +103,19 @@ def proof_to_value(blob):
     public_inputs = [int(x) for x in take(lay.n_pis)]
     if pos != len(blob):
         raise ValueError("trailing words in proof blob")
+    if lay.nA:  # starky >= 0.2's names for the middle matrix
+        return {
+            "proof": {
+                "trace_cap": trace_cap,
+                "auxiliary_polys_cap": zs_cap,
+                "quotient_polys_cap": quot_cap,
+                "openings": {"local_values": local_values, "next_values": next_values, "auxiliary_polys": zs, "auxiliary_polys_next": zs_next,
+                             "quotient_polys": quotient_polys},
+                "opening_proof": {"commit_phase_merkle_caps": caps, "query_round_proofs": rounds, "final_poly": final_poly,
+                                  "pow_witness": pow_witness},
+            },
+            "public_inputs": public_inputs,
+        }
     return {
         "proof": {
             "trace_cap": trace_cap,
@@ -116,8 +137,13 @@ def value_to_proof(value, degree_bits, rate_bits, arity_bits=4, num_challenges=2
     C, Q = len(op["local_values"]), len(op["quotient_polys"])
     cap_h = (len(p["trace_cap"]) - 1).bit_length()
     nZ = len(op["permutation_zs"]) if op.get("permutation_zs") else 0
+    nA = len(op["auxiliary_polys"]) if op.get("auxiliary_polys") else 0
+    if nZ and nA:
+        raise ValueError("a proof has permutation Zs or LogUp auxiliary polynomials, not both")
+    mid_cap, mid, mid_next = (p.get("auxiliary_polys_cap"), op.get("auxiliary_polys"), op.get("auxiliary_polys_next")) if nA else \
+        (p.get("permutation_zs_cap"), op.get("permutation_zs"), op.get("permutation_zs_next"))
     words = [MAGIC, C, Q, degree_bits, rate_bits, cap_h, len(fri["commit_phase_merkle_caps"]), len(fri["query_round_proofs"]),
-             len(fri["final_poly"]["coeffs"]), len(value["public_inputs"]), arity_bits, num_challenges, 0, nZ, 0, 0]
+             len(fri["final_poly"]["coeffs"]), len(value["public_inputs"]), arity_bits, num_challenges, 0, nZ, nA, 0]
 
     def put_hashes(hs):
         for h in hs:
@@ -127,14 +153,14 @@ def value_to_proof(value, degree_bits, rate_bits, arity_bits=4, num_challenges=2
         for e in es:
             words.extend(e)
     put_hashes(p["trace_cap"])
-    if nZ:
-        put_hashes(p["permutation_zs_cap"])
+    if nZ or nA:
+        put_hashes(mid_cap)
     put_hashes(p["quotient_polys_cap"])
     put_exts(op["local_values"])
     put_exts(op["next_values"])
-    if nZ:
-        put_exts(op["permutation_zs"])
-        put_exts(op["permutation_zs_next"])
+    if nZ or nA:
+        put_exts(mid)
+        put_exts(mid_next)
     put_exts(op["quotient_polys"])
     for cap in fri["commit_phase_merkle_caps"]:
         put_hashes(cap)
