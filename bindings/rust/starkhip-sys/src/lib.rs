@@ -52,6 +52,8 @@ pub const STARKHIP_ERR_TRACE: c_int = -9;
 pub const STARKHIP_CHECK_MAGIC: u64 = 0x3130304B48435353;
 /// Word 0 of the lookup blob a prove with "fill_lookups" hands back with `STARKHIP_ERR_TRACE` ("SSLKP001").
 pub const STARKHIP_LOOKUP_MAGIC: u64 = 0x3130_3050_4B4C_5353;
+/// `STARKHIP_LOGUP_MAGIC` ("SSLGU001"): word 0 of the LogUp blob a prove with "fill_frequencies" hands back.
+pub const STARKHIP_LOGUP_MAGIC: u64 = 0x3130_3055_474C_5353;
 pub const STARKHIP_POW_SEARCH: u64 = u64::MAX;
 /// The hasher of a proof (`C: GenericConfig`): the context / pool option "hasher", and header word 12 of a proof blob.
 pub const STARKHIP_HASHER_POSEIDON: c_int = 0;
@@ -256,6 +258,22 @@ pub struct starkhip_lookup_report_t {
     pub listed: u64,
 }
 
+/// `starkhip_logup_report_t`: the summary of `starkhip_logup_frequencies`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct starkhip_logup_report_t {
+    /// the LogUp lookups of the AIR
+    pub lookups: u64,
+    /// lookups some cell of which their table lacks: their frequencies column was left as it was
+    pub lookups_failed: u64,
+    /// such cells, over all lookups
+    pub missing_cells: u64,
+    /// rows with at least one such cell, over all lookups
+    pub missing_rows: u64,
+    /// entries written to `list`: min(cap, missing_rows)
+    pub listed: u64,
+}
+
 extern "C" {
     pub fn starkhip_config_standard_fast(cfg: *mut starkhip_config_t);
     pub fn starkhip_config_for_air(air: Air, cfg: *mut starkhip_config_t) -> c_int;
@@ -283,6 +301,8 @@ extern "C" {
     // LogUp lookups (starky >= 0.2's Lookup; COMPAT.md L1 - L7): the lookups a registered program declares and nA = 2 sum (H + 1)
     pub fn starkhip_air_logups(air: c_int) -> c_int;
     pub fn starkhip_air_logup_polys(air: c_int) -> c_int;
+    // the looked-up columns of all LogUp lookups together: the length of starkhip_logup_frequencies' per_column
+    pub fn starkhip_air_logup_columns(air: c_int) -> c_int;
     // tests: the auxiliary polynomials of a trace on the device and from plain loops (challenges chi_0, chi_1; polys_out [nA][n_rows],
     // closing_out [2][n_lookups], the count of zero denominators); the constraint fold over the AIR's own and the LogUp constraints
     pub fn starkhip_logup_polys(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
@@ -375,6 +395,29 @@ extern "C" {
     // tests: the blob a filling prove must hand back for a host trace, without a device (STARKHIP_OK and a null blob when every lookup holds)
     pub fn starkhip_lookup_blob_replay(air: starkhip_air_t, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int, cap: usize,
                                        blob: *mut *mut u64, words: *mut usize) -> c_int;
+    // 1 when no frequencies column of the AIR's LogUp lookups is a looked-up, table or other frequencies column, 0 otherwise; BAD_AIR
+    // for an unknown AIR or one without LogUp lookups
+    pub fn starkhip_air_logup_fillable(air: starkhip_air_t) -> c_int;
+    // Fill the frequencies column of each LogUp lookup of the AIR in the caller's trace, in place (host or device memory, both
+    // layouts).  per_lookup [n_lookups] or null, per_column [sum m] or null: missing cells; missing_masks and list as
+    // starkhip_lookup_columns'.  A lookup that fails keeps its column.  With the context option "fill_frequencies" = 1 (a pool's
+    // option of the same name) every prove of such an AIR does this in its own copy of the trace first; a lookup that fails:
+    // STARKHIP_ERR_TRACE and a LogUp blob in *proof (starkhip_free).
+    pub fn starkhip_logup_frequencies(ctx: *mut c_void, air: starkhip_air_t, trace: *mut u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                      on_device: c_int, per_lookup: *mut u32, per_column: *mut u32, missing_masks: *mut u64, list: *mut u64,
+                                      cap: usize, out: *mut starkhip_logup_report_t) -> c_int;
+    // tests: the same host driver over host loops; `trace` is host memory
+    pub fn starkhip_logup_frequencies_replay(air: starkhip_air_t, trace: *mut u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                             per_lookup: *mut u32, per_column: *mut u32, missing_masks: *mut u64, list: *mut u64, cap: usize,
+                                             out: *mut starkhip_logup_report_t) -> c_int;
+    // ms [5]: upload, table sort, count, write, read-back of the context's last fill of LogUp frequencies
+    pub fn starkhip_logup_frequency_timings(ctx: *mut c_void, ms: *mut f32) -> c_int;
+    // a LogUp blob: 8 header words {STARKHIP_LOGUP_MAGIC, AIR id, n_rows, lookups, lookups_failed, missing_rows, listed, missing_cells},
+    // then listed x {lookup, row}; *list (may be null) points into the blob
+    pub fn starkhip_logup_blob_layout(blob: *const u64, words: usize, out: *mut starkhip_logup_report_t, list: *mut *const u64) -> c_int;
+    // tests: the blob a filling prove must hand back for a host trace, without a device (STARKHIP_OK and a null blob when every lookup holds)
+    pub fn starkhip_logup_blob_replay(air: starkhip_air_t, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int, cap: usize,
+                                      blob: *mut *mut u64, words: *mut usize) -> c_int;
 
     pub fn starkhip_trace_fp12_mul(x: *const u32, y: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;
     pub fn starkhip_trace_final_exp(x: *const u32, trace: *mut u64, n_rows: usize, public_inputs: *mut u64) -> c_int;

@@ -157,10 +157,14 @@ int starkhip_air_permutation_zs(starkhip_air_t air);
  * the number of lookups, and nA (0 for an AIR without them, which is every built-in one); BAD_AIR for an unknown id.  starkhip_prove
  * refuses a trace whose running sums do not close (wrong frequencies, a value missing from the table) or in which a denominator
  * chi + cell is zero with STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE, before the auxiliary polynomials are committed; the context stays
- * usable.  Such a proof evaluates its quotient on every coset, behind either "quotient_impl".  Filling the frequencies column is the
- * caller's. */
+ * usable.  Such a proof evaluates its quotient on every coset, behind either "quotient_impl".  The frequencies column is filled by
+ * starkhip_logup_frequencies, or inside prove() under "fill_frequencies" ("LogUp FREQUENCIES" below), which also says which cells
+ * miss the table. */
 int starkhip_air_logups(starkhip_air_t air);
 int starkhip_air_logup_polys(starkhip_air_t air);
+/* the looked-up columns of all LogUp lookups of the AIR together (sum m: the length of starkhip_logup_frequencies' per_column; 0 for
+ * an AIR without them); BAD_AIR for an unknown id */
+int starkhip_air_logup_columns(starkhip_air_t air);
 
 /* --- user-defined AIRs ------------------------------------------------------------------
  * A starky user's own `impl Stark` reaches the library as its constraint program: the blob starkhip_air_program returns (format:
@@ -465,6 +469,73 @@ int starkhip_lookup_blob_replay(starkhip_air_t air, const uint64_t* trace, size_
 int starkhip_lookup_air_register(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, const char* name, uint32_t default_rows,
                                  starkhip_air_t* id_out);
 
+/* --- LogUp FREQUENCIES -------------------------------------------------------------------------------------------------
+ * The witness of a LogUp lookup (starkhip_air_logups above) is its frequencies column.  This entry FILLS the frequencies columns of
+ * a trace, for the lookups the AIR's program declares.  The rule, per lookup with m looked-up columns, table column t and
+ * frequencies column f over n rows, cells read mod p, outputs canonical:
+ *   row r of the table is a FIRST when no row r' < r has t[r'] = t[r]; a looked-up cell is MISSING when its value occurs nowhere in
+ *   t; the lookup HOLDS when it has no missing cell.  When it holds, f[r] = the number of cells among the m n looked-up cells that
+ *   equal t[r] if r is a first, and 0 otherwise: sum f = m n, and a value the table holds several times gives all its count to the
+ *   lowest such row (any split over duplicate table rows closes the argument -- COMPAT.md 2c; this one is the prover's choice).
+ *   When the lookup fails, its frequencies column is left exactly as it was; the other lookups of the call are still written.
+ *   Nothing but the frequencies columns is written.
+ * A pure function of the trace: the device, starkhip_logup_frequencies_replay and a numpy reference agree byte for byte, and two runs
+ * give identical bytes.  trace, n_rows, n_cols, layout and on_device as in starkhip_lookup_columns: a device trace is read and written
+ * in place in either layout; of a host trace only the distinct columns the lookups read go up and, for a lookup that holds, its
+ * frequencies column comes back.
+ *   per_lookup (n_lookups entries, or NULL): the missing cells of each lookup;
+ *   per_column (sum m entries, or NULL): the missing cells of each looked-up column, the lookups' columns back to back in
+ *     declaration order -- it names the offending column;
+ *   missing_masks (n_lookups x (n_rows + 63) / 64 words, or NULL): bit (r & 63) of word r >> 6 = row r has at least one missing cell;
+ *   list (cap x {lookup, row}; may be NULL when cap == 0): the first min(cap, missing_rows) missing rows by lookup, then row.
+ * STARKHIP_OK whether or not lookups failed: the report says.  BAD_AIR for an unknown AIR or one without LogUp lookups; BAD_SHAPE for
+ * a NULL trace or out, an unknown layout, a column count that is not the AIR's, rows that are no power of two in
+ * 2 .. 2^STARKHIP_MAX_LOG_ROWS, cap > STARKHIP_CHECK_LIST_MAX, a NULL list with cap > 0, and an AIR that is not FILLABLE: one in which
+ * a frequencies column is also a looked-up or table column of any lookup or another lookup's frequencies column
+ * (starkhip_air_logup_fillable: 1, 0, or BAD_AIR for an unknown AIR or one without LogUp lookups) -- so the order of the lookups does
+ * not matter.  One call at a time per context.  Implementation: the table column of each lookup sorted once per distinct table
+ * (csrc/kernels_multiset.hip, n items), one lane per looked-up cell counting at the lower bound of its value, one lane per sorted
+ * position writing (csrc/kernels_logup_freq.hip); the lookups of a call share each launch, one host wait per batch. */
+typedef struct {
+    uint64_t lookups, lookups_failed;
+    uint64_t missing_cells;  /* over all lookups */
+    uint64_t missing_rows;   /* over all lookups: rows with at least one missing cell */
+    uint64_t listed;
+} starkhip_logup_report_t;
+int starkhip_air_logup_fillable(starkhip_air_t air);
+int starkhip_logup_frequencies(void* ctx, starkhip_air_t air, uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                               uint32_t* per_lookup, uint32_t* per_column, uint64_t* missing_masks, uint64_t* list, size_t cap,
+                               starkhip_logup_report_t* out);
+/* tests: the same host driver with the device steps replaced by host loops that follow the rule literally; no device needed */
+int starkhip_logup_frequencies_replay(starkhip_air_t air, uint64_t* trace, size_t n_rows, size_t n_cols, int layout, uint32_t* per_lookup,
+                                      uint32_t* per_column, uint64_t* missing_masks, uint64_t* list, size_t cap,
+                                      starkhip_logup_report_t* out);
+/* ms = {upload of a host trace's columns, keys and sort of the tables, count, write, read-backs of masks and of a host trace's
+ * frequencies columns} of the last fill on this context, whichever entry ran it: the first four from events on its stream, summed
+ * over the batches, the last the host's time in the copies. */
+int starkhip_logup_frequency_timings(void* ctx, float ms[5]);
+/* The fill inside prove().  With the context option "fill_frequencies" = 1 (a pool's option of the same name) every starkhip_prove,
+ * _prove_columns and _prove_compact of a fillable AIR with LogUp lookups runs the rule on the copy of the trace it has just put in
+ * device memory, at the place and under the terms of "fill_lookups" above: before "check_trace" and before the named columns are
+ * copied aside, the caller's buffer only read (column-major device memory is copied first), the write not gated.  The proof is, byte
+ * for byte, the proof of the pre-filled trace without the option.  An AIR with LogUp lookups that is not fillable: STARKHIP_ERR_BAD_AIR.
+ * An AIR without LogUp lookups: nothing changes.  Some lookup fails: STARKHIP_ERR_TRACE, nothing later is enqueued, the context stays
+ * usable, starkhip_check_stats counts the trace as checked and rejected, and *proof / *proof_words hand back a LOGUP BLOB
+ * (starkhip_free), the lookup blob's word layout under its own magic:
+ *   word 0  STARKHIP_LOGUP_MAGIC ("SSLGU001")        word 4  lookups_failed
+ *   word 1  AIR id                                   word 5  missing_rows
+ *   word 2  n_rows                                   word 6  listed
+ *   word 3  lookups                                  word 7  missing_cells
+ *   then listed x {lookup, row}: starkhip_logup_frequencies' list for the same trace with cap = "check_trace_list".
+ * starkhip_logup_blob_layout validates magic and length (anything else, a lookup blob included: BAD_SHAPE; starkhip_lookup_blob_layout
+ * refuses a LogUp blob likewise).  starkhip_logup_blob_replay (tests): what a filling prove must hand back for `trace` (host memory,
+ * only read) with "check_trace_list" = cap, without a device: STARKHIP_OK and *blob = NULL when every lookup holds, STARKHIP_ERR_TRACE
+ * and the blob otherwise; BAD_AIR for an AIR without LogUp lookups or one that is not fillable. */
+#define STARKHIP_LOGUP_MAGIC 0x31303055474C5353ULL
+int starkhip_logup_blob_layout(const uint64_t* blob, size_t words, starkhip_logup_report_t* out, const uint64_t** list);
+int starkhip_logup_blob_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, size_t cap, uint64_t** blob,
+                               size_t* words);
+
 /* --- natives + trace generation (host)----------------------------------------------- */
 /* inputs are u32 limb arrays: Fp = 12, Fp2 = 24, Fp12 = 144 limbs.
  * trace is written row-major [n_rows][columns]; public_inputs has starkhip_air_public_inputs() entries. */
@@ -534,6 +605,9 @@ int starkhip_prove_columns(void* ctx, starkhip_air_t air, const starkhip_config_
  * "fill_lookups" (0 = default / 1: every prove of an AIR registered with its lookups fills their permuted columns in its own copy of
  * the trace first -- "the fill inside prove()" above; STARKHIP_ERR_TRACE with a lookup blob when a lookup fails), "lookup_batch" (0 =
  * automatic / 1 .. STARKHIP_LOOKUPS_MAX: the lookups that share one set of launches, there and in starkhip_lookup_columns),
+ * "fill_frequencies" (0 = default / 1: every prove of a fillable AIR with LogUp lookups fills their frequencies columns in its own
+ * copy of the trace first -- "LogUp FREQUENCIES" above; STARKHIP_ERR_TRACE with a LogUp blob when a lookup fails),
+ * "logup_count_combine" (1 = default / 0: the count kernel of that fill adds every cell alone; the same bytes, for measurements),
  * "hasher" (STARKHIP_HASHER_POSEIDON, the default, or STARKHIP_HASHER_KECCAK: the hash of every prove entry of the context -- trace
  * and quotient commitments, FRI layers, proof of work and the transcript's sponge.  With 0 every byte of every proof is what it is
  * without the option.  Under STARKHIP_HASHER_KECCAK "leaf_hash_form" and "host_commit_leaves" do not apply: they pick among Poseidon
@@ -728,6 +802,8 @@ int starkhip_hw_queues_in_effect(void);
  *                     by its context, as the context option "fill_lookups" does, before "check_traces" looks at the trace.  A failing
  *                     lookup: starkhip_pool_wait returns STARKHIP_ERR_TRACE and hands over the lookup blob in *proof (starkhip_free);
  *                     it never reaches the verifier, and starkhip_pool_check_stats counts it as rejected.
+ *   "fill_frequencies" 0 (default) or 1: the same for the frequencies columns of the LogUp lookups of a ticket's AIR, as the context
+ *                     option "fill_frequencies" does; a failing lookup hands over the LogUp blob.  Read at submit too.
  *   "hasher"          STARKHIP_HASHER_POSEIDON (default) or STARKHIP_HASHER_KECCAK: the hasher of every proving ticket submitted from then
  *                     on, as the context option "hasher".  A Keccak proof's trace commitment is launched by its context on its own stream,
  *                     not by the pool's commitment scheduler (whose merged and lane-group launches are Poseidon forms): the counters of

@@ -220,6 +220,14 @@ def air_logups(air):
     return r
 
 
+def air_logup_columns(air):
+    """The looked-up columns of all LogUp lookups of the AIR together (starkhip_air_logup_columns): the length of a LogupReport's per_column."""
+    r = lib.starkhip_air_logup_columns(air)
+    if r < 0:
+        raise StarkhipError(r)
+    return r
+
+
 def air_logup_polys(air):
     """nA: the auxiliary polynomials a proof of the AIR commits for its LogUp lookups: per challenge (2) and lookup its
     ceil(m / (degree - 1)) helpers and one running sum."""
@@ -322,19 +330,24 @@ def parse_check_blob(blob):
 
 
 LOOKUP_MAGIC = 0x313030504B4C5353
+LOGUP_MAGIC = 0x31303055474C5353  # STARKHIP_LOGUP_MAGIC
 
 
 class TraceViolation(StarkhipError):
     """ERR_TRACE from a prove with "check_trace" on, or from a pool with "check_traces": the trace violates the AIR.  `.blob` is the
     check blob (np.uint64) and `.report` its CheckBlobReport.  From a prove or a pool with "fill_lookups" for a trace some lookup of
-    which fails: `.blob` is the lookup blob, `.lookup_report` its LookupBlobReport and `.report` is None (else `.lookup_report` is)."""
+    which fails: `.blob` is the lookup blob, `.lookup_report` its LookupBlobReport and `.report` is None (else `.lookup_report` is).
+    With "fill_frequencies" for a trace some LogUp lookup of which fails: `.blob` is the LogUp blob and `.logup_report` its
+    LogupBlobReport (None otherwise)."""
 
     def __init__(self, blob):
         super().__init__(ERR_TRACE)
         self.blob = blob
-        self.report = self.lookup_report = None
+        self.report = self.lookup_report = self.logup_report = None
         if len(blob) and int(blob[0]) == LOOKUP_MAGIC:
             self.lookup_report = parse_lookup_blob(blob)
+        elif len(blob) and int(blob[0]) == LOGUP_MAGIC:
+            self.logup_report = parse_logup_blob(blob)
         else:
             self.report = parse_check_blob(blob)
 
@@ -974,6 +987,122 @@ def lookup_air_blob(n_cols, degree, lookups):
     return blob[:words.value].copy()
 
 
+# ---- LogUp frequencies (starkhip.h: "LogUp FREQUENCIES")
+class _LogupReportStruct(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("lookups", "lookups_failed", "missing_cells", "missing_rows", "listed")]
+
+
+lib.starkhip_air_logup_fillable.argtypes = [C.c_int]
+lib.starkhip_logup_frequencies.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u32p, _u32p, _u64p, _u64p, C.c_size_t,
+                                           C.POINTER(_LogupReportStruct)]
+lib.starkhip_logup_frequencies_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, _u32p, _u32p, _u64p, _u64p, C.c_size_t,
+                                                  C.POINTER(_LogupReportStruct)]
+lib.starkhip_logup_frequency_timings.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+lib.starkhip_logup_blob_layout.argtypes = [_u64p, C.c_size_t, C.POINTER(_LogupReportStruct), C.POINTER(_u64p)]
+lib.starkhip_logup_blob_replay.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(_u64p), C.POINTER(C.c_size_t)]
+
+
+def air_logup_fillable(air):
+    """starkhip_air_logup_fillable: no frequencies column of the AIR's LogUp lookups is a looked-up or table column of any of them, or
+    another lookup's frequencies column -- what logup_frequencies and "fill_frequencies" need."""
+    r = lib.starkhip_air_logup_fillable(air)
+    if r < 0:
+        raise StarkhipError(r)
+    return bool(r)
+
+
+class LogupReport(LookupReport):
+    """What starkhip_logup_frequencies did, lookup by lookup: `lookups`, `failed`: the lookups some cell of which their table does not
+    hold -- their frequencies column was left as it was; `missing_cells`, `missing_rows`: those cells, and the rows that have one, over
+    all lookups; `per_lookup` (np.uint32[n_lookups]): the missing cells of each lookup; `per_column` (np.uint32[sum m]): of each
+    looked-up column, the lookups' columns back to back in declaration order; `masks`, `mask_words`, `list`, `timings` as LookupReport's."""
+
+    def __init__(self, summary, per_lookup, per_column, words, entries, n_rows, timings=None):
+        super().__init__(summary, per_lookup, words, entries, n_rows, timings)
+        self.missing_cells, self.per_column = int(summary.missing_cells), per_column
+
+    def __repr__(self):
+        return (f"LogupReport(lookups={self.lookups}, failed={self.failed}, missing_cells={self.missing_cells}, missing_rows={self.missing_rows}, "
+                f"listed={len(self.list)})")
+
+
+def _logup_frequencies(call, n_lookups, n_columns, n_rows, cap):
+    """`call(per_lookup, per_column, masks, list, cap, summary)` -> rc: one of the two entry points with its leading arguments bound."""
+    cap = int(cap)
+    if cap < 0:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    per = np.zeros(max(1, n_lookups), dtype=np.uint32)
+    per_col = np.zeros(max(1, n_columns), dtype=np.uint32)
+    words = np.zeros((n_lookups, (n_rows + 63) // 64), dtype=np.uint64)
+    entries = np.zeros((min(cap, CHECK_LIST_MAX), 2), dtype=np.uint64)  # a larger cap is the library's to refuse
+    summary = _LogupReportStruct()
+    _chk(call(per.ctypes.data_as(_u32p), per_col.ctypes.data_as(_u32p), _p64(words) if words.size else None, _p64(entries) if cap else None, cap,
+              C.byref(summary)))
+    return LogupReport(summary, per[:n_lookups], per_col[:n_columns], words, entries, n_rows)
+
+
+def _logup_shape(air):
+    """(lookups, looked-up columns over all of them) of an AIR's program; (0, 0) for an unknown AIR, which the library refuses"""
+    nl, nc = lib.starkhip_air_logups(air), lib.starkhip_air_logup_columns(air)
+    return (nl, nc) if nl >= 0 and nc >= 0 else (0, 0)
+
+
+def logup_frequencies_replay(air, trace, layout=0, cap=1024):
+    """starkhip_logup_frequencies_replay (tests): Prover.logup_frequencies' host driver with the device steps replaced by host loops
+    that implement the rule literally.  Writes into `trace` (a C-contiguous writable np.uint64 array).  No device needed."""
+    n_rows, n_cols = _writable_trace(trace, layout)
+    nl, nc = _logup_shape(air)
+    return _logup_frequencies(lambda *a: lib.starkhip_logup_frequencies_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, *a), nl, nc,
+                              n_rows, cap)
+
+
+class LogupBlobReport:
+    """A LogUp blob read (parse_logup_blob): `air`, `n_rows`, `lookups`, `failed`, `missing_cells`, `missing_rows` and `list`
+    (np.uint64[listed, 2]): the first missing rows as (lookup, row), by lookup, then row, cut at the prover's "check_trace_list"."""
+
+    def __init__(self, air, n_rows, summary, entries):
+        self.air, self.n_rows = int(air), int(n_rows)
+        self.lookups, self.failed = int(summary.lookups), int(summary.lookups_failed)
+        self.missing_cells, self.missing_rows = int(summary.missing_cells), int(summary.missing_rows)
+        self.list = entries
+
+    def __repr__(self):
+        return (f"LogupBlobReport(air={self.air}, n_rows={self.n_rows}, failed={self.failed}, missing_cells={self.missing_cells}, "
+                f"missing_rows={self.missing_rows}, listed={len(self.list)})")
+
+
+def logup_blob_layout(blob):
+    """starkhip_logup_blob_layout on a LogUp blob (np.uint64): its LogupBlobReport; StarkhipError(ERR_BAD_SHAPE) for anything else."""
+    b = np.ascontiguousarray(blob, dtype=np.uint64).reshape(-1)
+    summary = _LogupReportStruct()
+    lst = _u64p()
+    _chk(lib.starkhip_logup_blob_layout(_p64(b), b.size, C.byref(summary), C.byref(lst)))
+    listed = int(summary.listed)
+    return LogupBlobReport(b[1], b[2], summary, b[8:8 + 2 * listed].reshape(listed, 2).copy())
+
+
+parse_logup_blob = logup_blob_layout
+
+
+def logup_blob_replay(air, trace, layout=0, cap=16):
+    """starkhip_logup_blob_replay (tests, small shapes): the LogUp blob a prove with "fill_frequencies" must hand back for `trace`
+    (only read) with "check_trace_list" = cap, or None when every lookup of the AIR holds; no device needed."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1) or int(cap) < 0:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    out = _u64p()
+    words = C.c_size_t()
+    rc = lib.starkhip_logup_blob_replay(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, int(cap), C.byref(out), C.byref(words))
+    if rc == 0:
+        return None
+    if rc != ERR_TRACE:
+        raise StarkhipError(rc)
+    blob = np.ctypeslib.as_array(out, shape=(words.value,)).copy()
+    lib.starkhip_free(out)
+    return blob
+
+
 # ----------------------------------------------------------------------------- traces (generate_trace)
 class CompactTrace:
     """A trace recorded as runs (starkhip_trace_log_*): the generator's limb vectors with the rows they
@@ -1351,6 +1480,37 @@ class Prover:
         _chk(lib.starkhip_lookup_timings(self._ctx, ms))
         return dict(zip(("upload", "sort", "place", "read_back"), (float(x) for x in ms)))
 
+    def logup_frequencies(self, air, trace, layout=0, cap=1024):
+        """Fill the frequencies column of each LogUp lookup of `air` in `trace` (starkhip_logup_frequencies): the tables sorted once
+        each and one lane per looked-up cell on this context's device, written into the array given (C-contiguous, writable,
+        np.uint64; row-major [n][C], or column-major [C][n] with layout=1).  A lookup some cell of which its table lacks keeps its
+        column as it was and reports the rows and the columns.  Returns a LogupReport."""
+        n_rows, n_cols = _writable_trace(trace, layout)
+        return self._logup_frequencies(air, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, cap)
+
+    def logup_frequencies_device(self, air, trace_ptr, n_rows, n_cols, layout=1, cap=1024):
+        """logup_frequencies on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr()),
+        read and written in place."""
+        return self._logup_frequencies(air, C.c_void_p(trace_ptr), n_rows, n_cols, layout, 1, cap)
+
+    def _logup_frequencies(self, air, trace_arg, n_rows, n_cols, layout, on_device, cap):
+        nl, nc = _logup_shape(air)
+        t0 = time.perf_counter()
+        try:
+            rep = _logup_frequencies(lambda *a: lib.starkhip_logup_frequencies(self._ctx, air, trace_arg, n_rows, n_cols, layout, on_device, *a), nl, nc,
+                                     n_rows, cap)
+        finally:
+            self.last_call_s = time.perf_counter() - t0
+        rep.timings = self.last_logup_frequency_timings()
+        return rep
+
+    def last_logup_frequency_timings(self):
+        """Milliseconds of the last fill of LogUp frequencies on this context: {upload, sort, count, write, read_back}
+        (starkhip_logup_frequency_timings)."""
+        ms = (C.c_float * 5)()
+        _chk(lib.starkhip_logup_frequency_timings(self._ctx, ms))
+        return dict(zip(("upload", "sort", "count", "write", "read_back"), (float(x) for x in ms)))
+
     def check_trace_device(self, air, trace_ptr, n_rows, public_inputs, layout=1):
         """check_trace on a trace already in this device's memory (trace_ptr: a device address, e.g. torch tensor.data_ptr())."""
         pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
@@ -1455,6 +1615,8 @@ class Prover:
         device before the LDE and raises TraceViolation for a violating one ("check_trace_list": the violations its report lists).
         "fill_lookups" = 1: every prove* of an AIR registered with its lookups (register_air(lookups=...)) fills their permuted columns
         in the prover's own copy of the trace first, and raises TraceViolation with a lookup blob when a lookup fails.
+        "fill_frequencies" = 1: every prove* of a fillable AIR with LogUp lookups fills their frequencies columns likewise, and raises
+        TraceViolation with a LogUp blob (`.logup_report`) when a cell misses its table.
         "leaf_hash_prefix" (default 1; 0: off): the lane and pair forms of the leaf hash start a trace whose first `rows` columns are
         e_0 .. e_{rows-1} (FinalExp's row selectors) from a saved state past them; same proof bytes either way.  The other names
         ("hasher", "leaf_hash_form", "lde_closed_forms", "lde_impl", "host_commit_leaves", "quotient_*", ...): include/starkhip.h."""
@@ -1793,7 +1955,8 @@ class ProofPool:
     def set_option(self, name, value):
         """starkhip_pool_set_option on every pool of the handle: "verify_proofs" (0 / 1), "verify_arena_mb", "check_traces" (0 / 1: wait
         raises TraceViolation for a trace that violates its AIR), "check_trace_list", "fill_lookups" (0 / 1: the permuted columns of an AIR
-        registered with its lookups are filled by the proving context; wait raises TraceViolation with the lookup blob when one fails), "hasher" (HASHER_POSEIDON / HASHER_KECCAK: the
+        registered with its lookups are filled by the proving context; wait raises TraceViolation with the lookup blob when one fails),
+        "fill_frequencies" (0 / 1: the same for the frequencies columns of a fillable AIR's LogUp lookups; the LogUp blob), "hasher" (HASHER_POSEIDON / HASHER_KECCAK: the
         hasher of the proving tickets submitted from then on)."""
         if self._multi:
             _chk(lib.starkhip_multipool_set_option(self._h, name.encode(), int(value)))

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "lde_ranges.h"
 #include "lookup_columns.h"
+#include "logup_frequencies.h"
 #include "logup.h"
 #include "permutation.h"
 #include "permutation_check.h"
@@ -168,6 +169,13 @@ int starkhip_air_eval_frame_full(starkhip_air_t air, const uint64_t* local, cons
 }
 
 int starkhip_air_logups(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->prog.logups.size() : STARKHIP_ERR_BAD_AIR; }
+int starkhip_air_logup_columns(starkhip_air_t air) {
+    const AirInfo* a = air_get(air);
+    if (!a) return STARKHIP_ERR_BAD_AIR;
+    size_t m = 0;
+    for (const AirProgram::Logup& l : a->prog.logups) m += l.cols.size();
+    return (int)m;
+}
 int starkhip_air_logup_polys(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->prog.logup_polys() : STARKHIP_ERR_BAD_AIR; }
 
 int starkhip_air_eval_frame_logup(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
@@ -505,6 +513,55 @@ int starkhip_lookup_timings(void* ctx, float ms[4]) {
     if (!ms) return STARKHIP_ERR_BAD_SHAPE;
     lookup_timings((Ctx*)ctx, ms);
     return STARKHIP_OK;
+}
+
+int starkhip_air_logup_fillable(starkhip_air_t air) {
+    const AirInfo* a = air_get(air);
+    if (!a || a->prog.logups.empty()) return STARKHIP_ERR_BAD_AIR;
+    return guarded([&] { return logup_fillable(a->prog, nullptr) ? 1 : 0; });
+}
+
+int starkhip_logup_frequencies(void* ctx, starkhip_air_t air, uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                               uint32_t* per_lookup, uint32_t* per_column, uint64_t* missing_masks, uint64_t* list, size_t cap,
+                               starkhip_logup_report_t* out) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    const AirInfo* a = air_get(air);
+    if (!a || a->prog.logups.empty()) return STARKHIP_ERR_BAD_AIR;
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, on_device);
+    if (int rc = logup_freq_args(*a, in, list, cap, out)) return rc;
+    return guarded([&] { return logup_frequencies((Ctx*)ctx, *a, in, trace, per_lookup, per_column, missing_masks, list, cap, out); });
+}
+
+int starkhip_logup_frequencies_replay(starkhip_air_t air, uint64_t* trace, size_t n_rows, size_t n_cols, int layout, uint32_t* per_lookup,
+                                      uint32_t* per_column, uint64_t* missing_masks, uint64_t* list, size_t cap,
+                                      starkhip_logup_report_t* out) {
+    const AirInfo* a = air_get(air);
+    if (!a || a->prog.logups.empty()) return STARKHIP_ERR_BAD_AIR;
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    if (int rc = logup_freq_args(*a, in, list, cap, out)) return rc;
+    return guarded([&] { return logup_frequencies_replay(*a, in, trace, per_lookup, per_column, missing_masks, list, cap, out); });
+}
+
+int starkhip_logup_frequency_timings(void* ctx, float ms[5]) {
+    if (!ctx) return STARKHIP_ERR_NO_DEVICE;
+    if (!ms) return STARKHIP_ERR_BAD_SHAPE;
+    logup_frequency_timings((Ctx*)ctx, ms);
+    return STARKHIP_OK;
+}
+
+int starkhip_logup_blob_layout(const uint64_t* blob, size_t words, starkhip_logup_report_t* out, const uint64_t** list) {
+    if (!out || !logup_blob_read(blob, words, out, list)) return STARKHIP_ERR_BAD_SHAPE;
+    return STARKHIP_OK;
+}
+
+int starkhip_logup_blob_replay(starkhip_air_t air, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, size_t cap, uint64_t** blob,
+                               size_t* words) {
+    const AirInfo* a = air_get(air);
+    if (!a || a->prog.logups.empty()) return STARKHIP_ERR_BAD_AIR;
+    const TraceInput in = TraceInput::dense(trace, n_rows, n_cols, layout, 0);
+    unsigned log_n = 0;
+    if (in.check(*a) || !blob || !words || cap > STARKHIP_CHECK_LIST_MAX || !log2_rows(n_rows, &log_n) || log_n > max_log_rows(*a)) return STARKHIP_ERR_BAD_SHAPE;
+    return guarded([&] { return logup_fillable(a->prog, nullptr) ? logup_blob_replay(*a, in, cap, blob, words) : (int)STARKHIP_ERR_BAD_AIR; });
 }
 
 int starkhip_lookup_air_register(uint32_t n_cols, uint32_t degree, const starkhip_lookup_t* lookups, size_t n_lookups, const char* name, uint32_t default_rows,
@@ -1300,7 +1357,7 @@ const char* starkhip_error_string(int code) {
         case STARKHIP_ERR_NO_DEVICE: return "no such HIP device / context";
         case STARKHIP_ERR_VERIFY: return "proof rejected";
         case STARKHIP_ERR_BAD_AIR: return "unknown or unbuildable AIR id";
-        case STARKHIP_ERR_TRACE: return "the trace violates the AIR (\"check_trace\": a check blob is returned instead of a proof) or a lookup of it fails (\"fill_lookups\": a lookup blob)";
+        case STARKHIP_ERR_TRACE: return "the trace violates the AIR (\"check_trace\": a check blob is returned instead of a proof) or a lookup of it fails (\"fill_lookups\": a lookup blob; \"fill_frequencies\": a LogUp blob)";
         default: return "unknown error";
     }
 }

@@ -145,6 +145,10 @@ struct Ctx {
     // the trace, before the check and before the pair columns are copied aside; a pool sets it per job (ctx_set_fill_lookups).
     // "lookup_batch": at most this many lookups share one set of launches (0: as many as lookup_batch_size allows)
     long opt_fill_lookups = 0, opt_lookup_batch = 0;
+    // "fill_frequencies": prove() fills the frequencies columns of a fillable AIR's LogUp lookups (logup_fill_in_prove) in its own copy
+    // of the trace, at the same place; a pool sets it per job (ctx_set_fill_frequencies).  "logup_count_combine": the count kernel adds
+    // equal positions of a wave as one (1, the default) or every cell alone (0: the measurement's other form; the same bytes)
+    long opt_fill_frequencies = 0, opt_logup_count_combine = 1;
     std::atomic<uint64_t> traces_checked{0}, traces_rejected{0};
     std::vector<gl_t> host_lde;      // their LDE on the host
     // op-stream program (quotient_impl = 1; kept as the cross-check)
@@ -189,6 +193,7 @@ struct Ctx {
         for (DevBuf* b : perm.bufs()) v.push_back(b);
         for (DevBuf* b : mset.bufs()) v.push_back(b);
         for (DevBuf* b : lookup.bufs()) v.push_back(b);
+        for (DevBuf* b : logup_freq.bufs()) v.push_back(b);
         for (auto& t : table_cache)
             for (DevBuf* b : t->bufs()) v.push_back(b);
         for (auto& d : plan_cache)
@@ -240,6 +245,18 @@ struct Ctx {
         float ms[4] = {0, 0, 0, 0};
         std::vector<DevBuf*> bufs() { return {&desc, &cols, &flags, &sums, &slot, &mask}; }
     } lookup;
+    // starkhip_logup_frequencies and "fill_frequencies" (logup_frequencies.hip over kernels_logup_freq.hip), sized for one BATCH of G
+    // lookups (logup_freq_batch_size) and grown like the ones above: what the count needs beside the sorted tables, which are mset's
+    // (n items per distinct table of a batch).  desc: a batch's descriptors -- its table columns, {table slot, frequencies column} per
+    // lookup, {column, lookup, table slot} per looked-up column; cols: the staging of a host trace, the distinct columns the fill reads
+    // and then one frequencies column per lookup, [K + L][n]; count: [G][n] uint32 by sorted table position; mask: for a batch of g
+    // lookups the missing rows [g][W], then the missing cells of its g lookups and of its looked-up columns, uint32.  ms: the last
+    // fill's timings (starkhip_logup_frequency_timings).
+    struct LogupFreqBufs {
+        DevBuf desc, cols, count, mask;
+        float ms[5] = {0, 0, 0, 0, 0};
+        std::vector<DevBuf*> bufs() { return {&desc, &cols, &count, &mask}; }
+    } logup_freq;
 };
 
 // ---- ctx.hip
@@ -280,6 +297,12 @@ int lookup_fill_in_prove(Ctx* c, const AirInfo& air, gl_t* d_trace, size_t n_row
 // memory): work_buffers()' share for a proof that fills, and what starkhip_lookup_columns allocates from
 struct LookupWant { DevBuf* b; size_t bytes; };
 std::vector<LookupWant> lookup_work_buffers(Ctx* c, size_t n_rows, size_t n_lookups, bool staged);
+// ---- logup_frequencies.hip
+// "fill_frequencies": the frequencies column of every LogUp lookup of `air` (fillable) written into the prover's own column-major copy
+// of the trace, before anything reads it.  STARKHIP_OK when every lookup holds; STARKHIP_ERR_TRACE and the LogUp blob otherwise.
+int logup_fill_in_prove(Ctx* c, const AirInfo& air, gl_t* d_trace, size_t n_rows, uint64_t** blob, size_t* words);
+// THE sizes of the buffers a fill of the LogUp lookups of `P` over n_rows takes (`staged`: of a host trace)
+std::vector<LookupWant> logup_freq_work_buffers(Ctx* c, const AirProgram& P, size_t n_rows, bool staged);
 // ---- check_trace.hip
 int check_trace_in_prove(Ctx* c, const AirInfo& air, const gl_t* d_trace, size_t n_rows, const uint64_t* pis, uint64_t** blob, size_t* words);
 // ---- ctx.hip

@@ -417,6 +417,8 @@ int ctx_set_option(Ctx* c, const char* name, long value) {
     else if (k == "check_trace_list" && value >= 0 && value <= (long)STARKHIP_CHECK_LIST_MAX) c->opt_check_trace_list = value;
     else if (k == "fill_lookups" && (value == 0 || value == 1)) c->opt_fill_lookups = value;
     else if (k == "lookup_batch" && value >= 0 && value <= (long)STARKHIP_LOOKUPS_MAX) c->opt_lookup_batch = value;
+    else if (k == "fill_frequencies" && (value == 0 || value == 1)) c->opt_fill_frequencies = value;
+    else if (k == "logup_count_combine" && (value == 0 || value == 1)) c->opt_logup_count_combine = value;
     else return STARKHIP_ERR_BAD_SHAPE;
     return STARKHIP_OK;
 }
@@ -425,6 +427,7 @@ void ctx_set_check_trace(Ctx* c, bool on, size_t list_cap) {
     c->opt_check_trace_list = (long)std::min<size_t>(list_cap, STARKHIP_CHECK_LIST_MAX);
 }
 void ctx_set_fill_lookups(Ctx* c, bool on) { c->opt_fill_lookups = on; }
+void ctx_set_fill_frequencies(Ctx* c, bool on) { c->opt_fill_frequencies = on; }
 void ctx_set_hasher(Ctx* c, int hasher) { c->opt_hasher = hasher; }
 void ctx_check_stats(Ctx* c, uint64_t out[2]) {
     out[0] = c->traces_checked.load();

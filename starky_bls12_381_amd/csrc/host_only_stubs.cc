@@ -74,6 +74,7 @@ bool ctx_hash_requested(Ctx* c) { return c->hash_requested; }
 int ctx_set_urgent(Ctx* c, bool urgent) { c->urgent = urgent; return STARKHIP_OK; }
 void ctx_set_check_trace(Ctx* c, bool on, size_t) { c->check_trace = on; }  // the pretended check finds every trace satisfying
 void ctx_set_fill_lookups(Ctx*, bool) {}  // the pretended proof fills nothing
+void ctx_set_fill_frequencies(Ctx*, bool) {}
 void ctx_set_hasher(Ctx*, int) {}
 void ctx_check_stats(Ctx* c, uint64_t out[2]) { out[0] = c->traces_checked.load(); out[1] = 0; }
 int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t&, size_t, unsigned proof_blobs, bool) {
@@ -143,6 +144,10 @@ int lookup_columns(Ctx*, const TraceInput&, uint64_t*, const starkhip_lookup_t*,
     return STARKHIP_ERR_NO_DEVICE;
 }
 void lookup_timings(Ctx*, float ms[4]) { ms[0] = ms[1] = ms[2] = ms[3] = 0; }
+int logup_frequencies(Ctx*, const AirInfo&, const TraceInput&, uint64_t*, uint32_t*, uint32_t*, uint64_t*, uint64_t*, size_t, starkhip_logup_report_t*) {
+    return STARKHIP_ERR_NO_DEVICE;
+}
+void logup_frequency_timings(Ctx*, float ms[5]) { ms[0] = ms[1] = ms[2] = ms[3] = ms[4] = 0; }
 int lde_bench(Ctx*, size_t, unsigned, unsigned, unsigned, unsigned, const uint64_t*, float*, float*) { return STARKHIP_ERR_NO_DEVICE; }
 int field_ops(Ctx*, int, const uint64_t*, const uint64_t*, uint64_t*, size_t) { return STARKHIP_ERR_NO_DEVICE; }
 int permutation_zs(Ctx*, const AirInfo&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }

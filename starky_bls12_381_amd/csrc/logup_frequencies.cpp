@@ -1,0 +1,182 @@
+// starkhip_logup_frequencies' host half (logup_frequencies.h) and its replay without a device.
+#include "logup_frequencies.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "check_report.h"
+#include "gl.h"
+
+namespace starkhip {
+
+bool logup_fillable(const AirProgram& P, std::string* why) {
+    auto refuse = [&](const std::string& m) {
+        if (why) *why = m;
+        return false;
+    };
+    for (size_t q = 0; q < P.logups.size(); q++) {
+        const uint32_t f = P.logups[q].freq;
+        const std::string who = "LogUp lookup " + std::to_string(q) + ": frequencies column " + std::to_string(f);
+        for (size_t r = 0; r < P.logups.size(); r++) {
+            const AirProgram::Logup& b = P.logups[r];
+            if (f == b.table) return refuse(who + " is the table column of lookup " + std::to_string(r));
+            if (std::find(b.cols.begin(), b.cols.end(), f) != b.cols.end()) return refuse(who + " is a looked-up column of lookup " + std::to_string(r));
+            if (r != q && f == b.freq) return refuse(who + " is also the frequencies column of lookup " + std::to_string(r));
+        }
+    }
+    return true;
+}
+
+LogupFreqPlan::LogupFreqPlan(const AirProgram& P) : L(P.logups.size()) {
+    col_off.push_back(0);
+    for (const AirProgram::Logup& l : P.logups) {
+        cols.insert(cols.end(), l.cols.begin(), l.cols.end());
+        col_off.push_back((uint32_t)cols.size());
+        table.push_back(l.table);
+        freq.push_back(l.freq);
+    }
+    named = cols;
+    named.insert(named.end(), table.begin(), table.end());
+    std::sort(named.begin(), named.end());
+    named.erase(std::unique(named.begin(), named.end()), named.end());
+}
+
+int logup_freq_args(const AirInfo& air, const TraceInput& in, const uint64_t* list, size_t cap, const void* out) {
+    unsigned log_n = 0;
+    if (in.check(air) || !log2_rows(in.n_rows, &log_n) || log_n > STARKHIP_MAX_LOG_ROWS) return STARKHIP_ERR_BAD_SHAPE;
+    if (cap > STARKHIP_CHECK_LIST_MAX || (cap && !list) || !out) return STARKHIP_ERR_BAD_SHAPE;
+    return logup_fillable(air.prog, nullptr) ? STARKHIP_OK : STARKHIP_ERR_BAD_SHAPE;
+}
+
+int logup_freq_run(size_t n_rows, const LogupFreqPlan& plan, size_t batch, LogupFreqSteps& steps, uint32_t* per_lookup, uint32_t* per_column, uint64_t* masks,
+                   uint64_t* list, size_t cap, starkhip_logup_report_t* out) {
+    const size_t W = (n_rows + 63) / 64, L = plan.L;
+    starkhip_logup_report_t rep = {L, 0, 0, 0, 0};
+    if (!batch) return STARKHIP_ERR_BAD_SHAPE;
+    std::vector<uint64_t> pm(W);
+    std::vector<uint32_t> col_missing;
+    if (masks) std::fill(masks, masks + L * W, 0);
+    for (size_t q0 = 0; q0 < L; q0 += batch) {
+        const size_t g = std::min(batch, L - q0), c0 = plan.col_off[q0];
+        col_missing.assign(plan.col_off[q0 + g] - c0, 0);
+        if (int rc = steps.run(q0, g, col_missing.data())) return rc;
+        if (per_column) std::copy(col_missing.begin(), col_missing.end(), per_column + c0);
+        for (size_t i = 0; i < g; i++) {
+            const size_t q = q0 + i;
+            uint64_t cells = 0;
+            for (size_t k = plan.col_off[q]; k < plan.col_off[q + 1]; k++) {
+                if (col_missing[k - c0] > n_rows) return STARKHIP_ERR_HIP;
+                cells += col_missing[k - c0];
+            }
+            if (per_lookup) per_lookup[q] = (uint32_t)cells;
+            if (!cells) continue;
+            rep.lookups_failed++;
+            rep.missing_cells += cells;
+            if (int rc = steps.mask(i, pm.data())) return rc;
+            const uint64_t lead = q;
+            const uint64_t rows = mask_to_list(pm.data(), W, &lead, 1, list, cap, &rep.listed);
+            if (!rows || rows > cells || rows > n_rows) return STARKHIP_ERR_HIP;  // the mask is the one that was counted
+            rep.missing_rows += rows;
+            if (masks) std::copy(pm.begin(), pm.end(), masks + q * W);
+        }
+    }
+    *out = rep;
+    return STARKHIP_OK;
+}
+
+namespace {
+// one lookup as host loops over the caller's trace: the rule of logup_frequencies.h, literally
+struct ReplayFreqSteps : LogupFreqSteps {
+    const LogupFreqPlan& plan;
+    const TraceInput& in;
+    uint64_t* words;
+    size_t n, W;
+    std::vector<uint64_t> batch_masks;  // [g][W] of the last batch
+    ReplayFreqSteps(const LogupFreqPlan& plan_, const TraceInput& in_, uint64_t* words_)
+        : plan(plan_), in(in_), words(words_), n(in_.n_rows), W((in_.n_rows + 63) / 64) {}
+    int run(size_t q0, size_t g, uint32_t* col_missing) override {
+        batch_masks.assign(g * W, 0);
+        for (size_t i = 0; i < g; i++) run_one(q0 + i, batch_masks.data() + i * W, col_missing + (plan.col_off[q0 + i] - plan.col_off[q0]));
+        return STARKHIP_OK;
+    }
+    void run_one(size_t q, uint64_t* mask, uint32_t* col_missing) {
+        std::vector<gl_t> t(n);
+        for (size_t r = 0; r < n; r++) t[r] = gl_from_u64(in.words[in.at(r, plan.table[q])]);
+        std::vector<uint32_t> order(n);  // the rows by (value, row): the first of a run of equal values is a FIRST
+        std::iota(order.begin(), order.end(), 0u);
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return t[a] < t[b]; });
+        std::vector<gl_t> sorted(n);
+        for (size_t j = 0; j < n; j++) sorted[j] = t[order[j]];
+        std::vector<uint32_t> count(n, 0);
+        bool any = false;
+        for (size_t k = 0; k < plan.m(q); k++) {
+            const uint32_t col = plan.cols[plan.col_off[q] + k];
+            for (size_t r = 0; r < n; r++) {
+                const gl_t v = gl_from_u64(in.words[in.at(r, col)]);
+                const size_t pos = (size_t)(std::lower_bound(sorted.begin(), sorted.end(), v) - sorted.begin());
+                if (pos < n && sorted[pos] == v) count[pos]++;
+                else {
+                    mask[r >> 6] |= 1ull << (r & 63);
+                    col_missing[k]++;
+                    any = true;
+                }
+            }
+        }
+        if (any) return;
+        for (size_t j = 0; j < n; j++) words[in.at(order[j], plan.freq[q])] = count[j];
+    }
+    int mask(size_t i, uint64_t* out) override {
+        if ((i + 1) * W > batch_masks.size()) return STARKHIP_ERR_BAD_SHAPE;
+        std::copy(batch_masks.begin() + i * W, batch_masks.begin() + (i + 1) * W, out);
+        return STARKHIP_OK;
+    }
+};
+}  // namespace
+
+int logup_frequencies_replay(const AirInfo& air, const TraceInput& in, uint64_t* words, uint32_t* per_lookup, uint32_t* per_column, uint64_t* masks, uint64_t* list,
+                             size_t cap, starkhip_logup_report_t* out) {
+    const LogupFreqPlan plan(air.prog);
+    ReplayFreqSteps steps(plan, in, words);
+    return logup_freq_run(in.n_rows, plan, logup_freq_batch_size(in.n_rows, plan.L), steps, per_lookup, per_column, masks, list, cap, out);
+}
+
+uint64_t* logup_blob_make(int air, size_t n_rows, const starkhip_logup_report_t& rep, const uint64_t* list, size_t* words) {
+    const size_t total = LOGUP_BLOB_HEADER + 2 * (size_t)rep.listed;
+    uint64_t* b = (uint64_t*)malloc(total * 8);
+    if (!b) return nullptr;
+    const uint64_t head[LOGUP_BLOB_HEADER] = {STARKHIP_LOGUP_MAGIC, (uint64_t)air, n_rows, rep.lookups, rep.lookups_failed, rep.missing_rows, rep.listed, rep.missing_cells};
+    memcpy(b, head, sizeof head);
+    if (rep.listed) memcpy(b + LOGUP_BLOB_HEADER, list, 2 * (size_t)rep.listed * 8);
+    *words = total;
+    return b;
+}
+
+bool logup_blob_read(const uint64_t* blob, size_t words, starkhip_logup_report_t* out, const uint64_t** list) {
+    if (!blob || words < LOGUP_BLOB_HEADER || blob[0] != STARKHIP_LOGUP_MAGIC) return false;
+    const uint64_t listed = blob[6];
+    if (listed > STARKHIP_CHECK_LIST_MAX || listed > blob[5] || blob[5] > blob[7] || words != LOGUP_BLOB_HEADER + 2 * (size_t)listed) return false;
+    *out = starkhip_logup_report_t{blob[3], blob[4], blob[7], blob[5], listed};
+    if (list) *list = listed ? blob + LOGUP_BLOB_HEADER : nullptr;
+    return true;
+}
+
+int logup_blob_replay(const AirInfo& air, const TraceInput& in, size_t cap, uint64_t** blob, size_t* words) {
+    *blob = nullptr;
+    *words = 0;
+    std::vector<uint64_t> copy(in.words, in.words + in.n_rows * in.n_cols);  // the caller's trace is only read
+    TraceInput mine = in;
+    mine.words = copy.data();
+    std::vector<uint64_t> list(2 * std::max<size_t>(1, cap));
+    starkhip_logup_report_t rep = {0, 0, 0, 0, 0};
+    if (int rc = logup_frequencies_replay(air, mine, copy.data(), nullptr, nullptr, nullptr, list.data(), cap, &rep)) return rc;
+    if (!rep.lookups_failed) return STARKHIP_OK;
+    *blob = logup_blob_make(air.id, in.n_rows, rep, list.data(), words);
+    return *blob ? STARKHIP_ERR_TRACE : STARKHIP_ERR_OOM;
+}
+
+}  // namespace starkhip

@@ -62,6 +62,7 @@ struct Pool {
     bool check_traces = false;    // under mu
     size_t check_trace_list = 16; // under mu
     bool fill_lookups = false;    // under mu
+    bool fill_frequencies = false;  // under mu
     int hasher = 0;               // under mu: "hasher", read at submit
     double vload = 0;       // sum of air_verify_cost over the verify jobs that are not done (under mu)
     std::map<int, int> idle_big, idle_small;                 // idle contexts by the AIR they proved last (under mu)
@@ -231,6 +232,7 @@ struct Pool {
         const uint64_t cpu0 = thread_cpu_ns();
         ctx_set_check_trace(c, j->check, j->check_list);
         ctx_set_fill_lookups(c, j->fill);
+        ctx_set_fill_frequencies(c, j->fill_freq);
         ctx_set_hasher(c, j->hasher);
         try {
             const AirInfo* a = air_get(j->air);
@@ -446,6 +448,7 @@ static int pool_enqueue(Pool* p, Job* j, uint64_t* ticket) {
     j->check = p->check_traces;
     j->check_list = p->check_trace_list;
     j->fill = p->fill_lookups;
+    j->fill_freq = p->fill_frequencies;
     j->hasher = p->hasher;
     j->cost = air_cost(j->air);
     p->load += j->cost;
@@ -597,6 +600,12 @@ int pool_set_option(Pool* p, const char* name, long value) {
         if (value != 0 && value != 1) return STARKHIP_ERR_BAD_SHAPE;
         std::lock_guard<std::mutex> g(p->mu);
         p->fill_lookups = value == 1;
+        return STARKHIP_OK;
+    }
+    if (strcmp(name, "fill_frequencies") == 0) {  // read at submit too
+        if (value != 0 && value != 1) return STARKHIP_ERR_BAD_SHAPE;
+        std::lock_guard<std::mutex> g(p->mu);
+        p->fill_frequencies = value == 1;
         return STARKHIP_OK;
     }
     if (strcmp(name, "hasher") == 0) {  // read at submit too

@@ -32,6 +32,7 @@ struct Job {
     bool verify = false;  // "verify_proofs" was on when it was submitted: the pool's verifier checks the proof before wait returns it
     bool check = false;   // "check_traces" was on when it was submitted: its context checks the trace against the AIR before the LDE ...
     bool fill = false;    // "fill_lookups" was on when it was submitted: its context fills the permuted columns of the AIR's lookups first
+    bool fill_freq = false;  // "fill_frequencies" was on when it was submitted: its context fills the frequencies columns of the AIR's LogUp lookups first
     size_t check_list = 16;  // ... and a refusal's check blob lists this many violations ("check_trace_list" at submit)
     int hasher = 0;       // "hasher" at submit.  A Keccak job's trace commitment is its context's own launch: it is not announced to the
                           // commitment scheduler and does not move the scheduler's counters

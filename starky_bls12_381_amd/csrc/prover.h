@@ -26,6 +26,8 @@ int ctx_set_urgent(Ctx* c, bool urgent);
 void ctx_set_check_trace(Ctx* c, bool on, size_t list_cap);
 // "fill_lookups" of the context's next proofs, as a pool sets it per job
 void ctx_set_fill_lookups(Ctx* c, bool on);
+// "fill_frequencies" likewise
+void ctx_set_fill_frequencies(Ctx* c, bool on);
 void ctx_set_hasher(Ctx* c, int hasher);  // the "hasher" option of the context's next proofs, as a pool sets it per job
 void ctx_check_stats(Ctx* c, uint64_t out[2]);
 // tables, plan, work buffers, upload staging and `proof_blobs` page-locked proof blobs (blob_arena.h) for proofs of `air`,
@@ -100,6 +102,12 @@ void perm_check_timings(Ctx* c, float ms[4]);
 int lookup_columns(Ctx* c, const TraceInput& in, uint64_t* words, const starkhip_lookup_t* lookups, size_t n_lookups, uint32_t* per_lookup, uint64_t* masks,
                    uint64_t* list, size_t cap, starkhip_lookup_report_t* out);
 void lookup_timings(Ctx* c, float ms[4]);
+// starkhip_logup_frequencies: the frequencies column of each LogUp lookup of `air` written into the caller's trace -- `words`, the memory
+// `in` views (logup_frequencies.hip over kernels_multiset.hip and kernels_logup_freq.hip, logup_frequencies.h);
+// logup_frequency_timings: the last call's {upload, table sort, count, write, read-back} milliseconds
+int logup_frequencies(Ctx* c, const AirInfo& air, const TraceInput& in, uint64_t* words, uint32_t* per_lookup, uint32_t* per_column, uint64_t* masks, uint64_t* list,
+                      size_t cap, starkhip_logup_report_t* out);
+void logup_frequency_timings(Ctx* c, float ms[5]);
 int ntt_long(Ctx* c, uint64_t* data, size_t n_vecs, unsigned log_len, int inverse);
 int lde_batch(Ctx* c, const uint64_t* values, size_t n_cols, unsigned log_n, unsigned rate_bits, uint64_t* coeffs_out, uint64_t* lde_out);
 int merkle_cap(Ctx* c, const uint64_t* lde_natural, size_t n_cols, unsigned log_N, unsigned cap_h, uint64_t* cap_out);

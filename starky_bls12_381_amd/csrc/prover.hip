@@ -24,6 +24,7 @@
 #include "kernels_permutation.h"
 #include "lde_ranges.h"
 #include "logup.h"
+#include "logup_frequencies.h"
 #include "permutation.h"
 #include "trace_log.h"
 #include "poseidon.h"
@@ -134,8 +135,9 @@ static size_t comb_chunks(size_t C) { return (C + COMB_PPC - 1) / COMB_PPC; }
 // the upload stages at the start of the LDE buffer.
 struct BufWant { DevBuf* b; size_t bytes; };
 // fill_lookups: the proof fills `n_lookups` lookups first (lookup_fill_in_prove), in batches whose buffers are listed here too.
+// fill_freq: the program whose LogUp frequencies the proof fills first (logup_fill_in_prove), or null: likewise.
 static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n_chunks, const Ctx::PlanDev* plan, size_t values_bytes, size_t park_bytes,
-                                         size_t fill_lookups) {
+                                         size_t fill_lookups, const AirProgram* fill_freq) {
     const size_t n = s.n, N = s.N, C = s.C, Q = s.Q, size = s.size, nq = s.pl.n_queries;
     const bool by_class = plan && plan->by_class;
     const size_t partial_words = by_class ? std::max<size_t>((size_t)plan->n_work * plan->n_classes * 2 * n, 2 * size) : (size_t)n_chunks * 2 * size;
@@ -164,6 +166,8 @@ static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n
     }
     if (fill_lookups)  // "fill_lookups" on an AIR registered with its lookups (Ctx::LookupBufs and the sorted items of a batch)
         for (const LookupWant& b : lookup_work_buffers(c, n, fill_lookups, false)) w.push_back({b.b, b.bytes});
+    if (fill_freq)  // "fill_frequencies" on a fillable AIR with LogUp lookups (Ctx::LogupFreqBufs and the sorted tables of a batch)
+        for (const LookupWant& b : logup_freq_work_buffers(c, *fill_freq, n, false)) w.push_back({b.b, b.bytes});
     size_t len = N;
     for (size_t l = 0; l < s.L; l++) {  // a FRI layer's leaves and digests stay on the device for the query phase
         w.push_back({&c->fri_rows[l], len * 2 * 8});
@@ -212,6 +216,7 @@ struct ProveCall {
     unsigned n_chunks;   // ... and the chunks its constraints are cut into
     bool trace_in_lde;   // the trace waits for the LDE inside the LDE buffer, as its last C n words (run_lde_trace)
     bool fill;           // "fill_lookups" and an AIR registered with its lookups: upload() fills their permuted columns in the prover's own copy
+    bool fill_freq;      // "fill_frequencies" and a fillable AIR with LogUp lookups: upload() fills their frequencies columns likewise
     bool prefix;         // the LDE counts the columns e_c and the trace commitment may start from the saved state past them (kernels.h: LeafPrefix)
     gl_t* d_trace;       // where the upload puts the trace, column-major
     const gl_t* d_values = nullptr;  // where it is: d_trace, or the caller's own device memory
@@ -331,12 +336,15 @@ int ProveCall::upload() {
     // check below and the copy of the pair columns, from which the Zs are built.  Column-major device memory of the caller's, which
     // is otherwise read where it lies, is copied first: the caller's buffer is only read.  A lookup that fails ends the proof here
     // with STARKHIP_ERR_TRACE and the lookup blob in `out`.
-    if (rc == 0 && fill) {
+    if (rc == 0 && (fill || fill_freq)) {
         if (in.callers_columns()) {
             HIPCHK(hipMemcpyAsync(d_trace, in.words, s.C * s.n * 8, hipMemcpyDeviceToDevice, st));
             d_values = d_trace;
         }
-        rc = lookup_fill_in_prove(c, air, d_trace, s.n, &out, &check_words);
+        if (fill) rc = lookup_fill_in_prove(c, air, d_trace, s.n, &out, &check_words);
+        // "fill_frequencies": the frequencies columns of the AIR's LogUp lookups, at the same place and under the same terms; a
+        // lookup that fails hands back the LogUp blob
+        if (rc == 0 && fill_freq) rc = logup_fill_in_prove(c, air, d_trace, s.n, &out, &check_words);
     }
     // "check_trace": every constraint on every row of the trace where the upload has just put it, before anything of the LDE is
     // enqueued; a violating trace ends the proof here with STARKHIP_ERR_TRACE and its check blob in `out`
@@ -894,7 +902,9 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     // a separate buffer only when there is no room beside it (rate_bits == 0, or a recording longer than the rest of the buffer).
     const size_t n = s.n, N = s.N, C = s.C;
     const bool fill = c->opt_fill_lookups && !air.lookups.empty();
-    const bool callers_columns = in.callers_columns() && !fill;  // (a fill works on the prover's own copy of the columns)
+    const bool fill_freq = c->opt_fill_frequencies && !air.prog.logups.empty();
+    if (fill_freq && !logup_fillable(air.prog, nullptr)) return STARKHIP_ERR_BAD_AIR;
+    const bool callers_columns = in.callers_columns() && !fill && !fill_freq;  // (a fill works on the prover's own copy of the columns)
     const size_t park_words = in.park_words(C);  // what the upload parks at the start of the LDE buffer, in 64-bit words
     // A long trace (2^14 rows and more) is not parked there: its transform goes through the LDE buffer between its two passes and keeps
     // the coefficients in `values`, a whole trace of words, whoever owns the input (run_lde).
@@ -902,13 +912,13 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     const bool trace_in_lde = s.r >= 1 && park_words <= (((size_t)1 << s.r) - 1) * C * n && !callers_columns && !long_trace;
     // `values`: the columns the last LDE launch reads (run_lde_trace), a whole trace, or nothing this proof needs
     const size_t values_bytes = values_bytes_for(s, trace_in_lde, callers_columns);
-    for (const BufWant& w : work_buffers(c, s, n_chunks, tiled ? c->plan : nullptr, values_bytes, park_words * 8, fill ? air.lookups.size() : 0)) HIPCHK(w.b->ensure(w.bytes));
+    for (const BufWant& w : work_buffers(c, s, n_chunks, tiled ? c->plan : nullptr, values_bytes, park_words * 8, fill ? air.lookups.size() : 0, fill_freq ? &air.prog : nullptr)) HIPCHK(w.b->ensure(w.bytes));
     if (int rc = ensure_long_tables(c, s)) return rc;
     const bool prefix = leaf_prefix_wanted(c, C, s.log_n, s.r);
     if (prefix)
         if (int rc = ensure_leaf_prefix(c, s.log_n, s.r)) return rc;
 
-    ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde, fill, prefix,
+    ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde, fill, fill_freq, prefix,
                 trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()};
     p.ch.hasher = (int)c->opt_hasher;  // the transcript's sponge duplexes through the context's hasher
     // before each phase: the boundary event of starkhip_last_timings on the stream and the phase's rocTX range (rocprofv3 --marker-trace)
@@ -968,7 +978,9 @@ int ctx_reserve(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, size_t
     // `values`: a trace waits for its LDE inside the LDE buffer (prove(): trace_in_lde) but for the tail of run_lde_trace; rate_bits == 0
     // makes prove() ask for a whole trace.  The LDE buffer also stages the upload: a recording of log_bytes.
     const size_t values_bytes = values_bytes_for(s, s.r >= 1, false);
-    for (const BufWant& w : work_buffers(c, s, c->plan->chunks, c->plan, values_bytes, log_bytes + 64, air.lookups.size())) HIPCHK(w.b->ensure(w.bytes));
+    // the buffers of "fill_frequencies" only for a context that has the option on: others hold nothing more than before
+    const bool fill_freq = c->opt_fill_frequencies && !air.prog.logups.empty() && logup_fillable(air.prog, nullptr);
+    for (const BufWant& w : work_buffers(c, s, c->plan->chunks, c->plan, values_bytes, log_bytes + 64, air.lookups.size(), fill_freq ? &air.prog : nullptr)) HIPCHK(w.b->ensure(w.bytes));
     if (int rc = ensure_long_tables(c, s)) return rc;
     if (leaf_prefix_wanted(c, s.C, s.log_n, s.r))
         if (int rc = ensure_leaf_prefix(c, s.log_n, s.r)) return rc;
