@@ -112,6 +112,13 @@ asan-logup-freq-test: tests/asan_logup_freq_main.cpp $(ASAN_SRCS) $(HDRS)
 	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_logup_freq tests/asan_logup_freq_main.cpp $(ASAN_SRCS) -lpthread
 	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_logup_freq
 
+# the host code of LogUp lookups over Columns and Filters -- the validator over truncated and oversized general sections, the
+# descriptors' walkers, the replays of the auxiliary polynomials and of the fill, the blob replay -- under the same two: a stand-alone program
+asan-logup-columns-test: tests/asan_logup_columns_main.cpp $(ASAN_SRCS) $(HDRS)
+	@mkdir -p build/asan
+	g++ $(filter-out -shared -fPIC,$(ASAN_FLAGS)) -o build/asan/asan_logup_columns tests/asan_logup_columns_main.cpp $(ASAN_SRCS) -lpthread
+	ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 build/asan/asan_logup_columns
+
 # Experiment builds of the device code for A/B runs on one box: `make variant NAME=x DEFS="-D..."` -> build/x/libstarkhip_x.so, selected
 # at run time with STARKHIP_LIBRARY=build/x/libstarkhip_x.so (e.g. NAME=nomfma DEFS=-DSTARKHIP_LANE_NO_MFMA: the lane-form leaf hash with every
 # round as multiply-add chains; NAME=noprio DEFS=-DSTARKHIP_NO_PRIO: no raised issue priority for the kernels beside the lane-form hash)
@@ -127,4 +134,4 @@ build/$(NAME)/libstarkhip_$(NAME).so: $(VAR_OBJS) $(filter %.cpp.o,$(OBJS))
 clean:
 	rm -rf build $(OUT)
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test asan-keccak-test asan-perm-check-test asan-lookup-test asan-lookup-fill-test asan-logup-test asan-logup-freq-test variant
+.PHONY: all oracle clean demo asan asan-test tsan-test asan-pool-test lane-group-test asan-keccak-test asan-perm-check-test asan-lookup-test asan-lookup-fill-test asan-logup-test asan-logup-freq-test asan-logup-columns-test variant

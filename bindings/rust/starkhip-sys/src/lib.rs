@@ -303,6 +303,7 @@ extern "C" {
     pub fn starkhip_air_logup_polys(air: c_int) -> c_int;
     // the looked-up columns of all LogUp lookups together: the length of starkhip_logup_frequencies' per_column
     pub fn starkhip_air_logup_columns(air: c_int) -> c_int;
+    pub fn starkhip_air_logup_general(air: c_int) -> c_int;
     // tests: the auxiliary polynomials of a trace on the device and from plain loops (challenges chi_0, chi_1; polys_out [nA][n_rows],
     // closing_out [2][n_lookups], the count of zero denominators); the constraint fold over the AIR's own and the LogUp constraints
     pub fn starkhip_logup_polys(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,

@@ -165,6 +165,23 @@ int starkhip_air_logup_polys(starkhip_air_t air);
 /* the looked-up columns of all LogUp lookups of the AIR together (sum m: the length of starkhip_logup_frequencies' per_column; 0 for
  * an AIR without them); BAD_AIR for an unknown id */
 int starkhip_air_logup_columns(starkhip_air_t air);
+/* General lookups (upstream's Column and Filter, COMPAT.md 2c): a program may declare its lookups in the section "LOGUPS02" instead of
+ * "LOGUPS01" (never both; u64 words, in the same place):
+ *     "LOGUPS02", n_lookups, then per lookup: n_columns, COLUMN table, COLUMN frequencies, n_columns x { COLUMN value, FILTER }
+ *     COLUMN := n_local | n_next << 32, constant, then (n_local + n_next) x { trace column, coefficient }   (local terms first)
+ *     FILTER := n_products | n_sums << 32, then 2 n_products + n_sums COLUMNs (each product's A then B, then the sums)
+ * A COLUMN is constant + sum coefficient * cell over the local and the next row (the last row's next is row 0; at most 16 terms,
+ * coefficients canonical and nonzero); a FILTER is sum A B + sum C (at most 4 products and 4 sums) and 1 when empty.  With phi_c the
+ * filter of the looked-up value v_c the helpers are h_j = sum over batch j of phi_c / (chi + v_c), the running sum steps by
+ * sum_j h_j - f / (chi + t); polynomials, constraints and their order are those above, and so is the proof layout: a proof of a
+ * "LOGUPS02" program whose lookups are all plain (every COLUMN one local cell with coefficient 1 and constant 0, every FILTER empty)
+ * is byte for byte the proof of the "LOGUPS01" program.  A zero chi + v_c counts as a zero denominator whatever its filter says.
+ * starkhip_air_logup_general: 1 when some lookup of the AIR is not plain, 0 otherwise (0 for an AIR without lookups); BAD_AIR for an
+ * unknown id.  The fill ("LogUp FREQUENCIES" below), extended: the keys of a table are its COLUMN's values; a looked-up cell is
+ * skipped when its filter is 0 on the row, looked up and counted when it is 1, and counts as MISSING on its row when it is anything
+ * else; an AIR is fillable when every frequencies COLUMN is one plain column that no COLUMN or FILTER of any lookup reads and no two
+ * lookups share. */
+int starkhip_air_logup_general(starkhip_air_t air);
 
 /* --- user-defined AIRs ------------------------------------------------------------------
  * A starky user's own `impl Stark` reaches the library as its constraint program: the blob starkhip_air_program returns (format:

@@ -21,6 +21,7 @@ P = 0xFFFFFFFF00000001
 AIR_MAGIC = 0x3152495F52494153  # "SAIR_IR1"
 AIR_PERM_MAGIC = 0x3153524941504D50  # "PMPAIRS1": the section of permutation pairs
 AIR_LOGUP_MAGIC = 0x3130535055474F4C  # "LOGUPS01": the section of LogUp lookups
+AIR_LOGUP2_MAGIC = 0x3230535055474F4C  # "LOGUPS02": the same over Columns and Filters
 KIND_PLAIN, KIND_TRANSITION, KIND_FIRST, KIND_LAST = 0, 1, 2, 3
 CK_PLUS, CK_MINUS, CK_CONST, CK_PI, CK_NEG_PI = 0, 1, 2, 3, 4
 REF_NEXT, REF_COMPL, REF_COL_MASK = 1 << 30, 1 << 31, 0xFFFFFF
@@ -171,6 +172,59 @@ def _expr(x):
     raise TypeError(f"air_builder: cannot use {type(x).__name__} in a constraint")
 
 
+class Column:
+    """constant + sum coefficient * local[column] + sum coefficient * next[column] (starky's `Column`, COMPAT.md §2c): what a general
+    LogUp lookup looks up, its table and its frequencies.  `local` and `next` are lists of (trace column, coefficient); a coefficient
+    is reduced mod p (so -1 is p - 1) and must not be 0.  The next row of the last row is row 0."""
+
+    def __init__(self, local=(), next=(), constant=0):
+        self.local = [(int(c), int(k) % P) for c, k in local]
+        self.next = [(int(c), int(k) % P) for c, k in next]
+        self.constant = int(constant) % P
+
+    @staticmethod
+    def single(col):
+        """the plain column `col`: one local cell, coefficient 1, constant 0"""
+        return Column([(col, 1)])
+
+    @staticmethod
+    def const(c):
+        return Column(constant=c)
+
+    def is_plain(self):
+        return len(self.local) == 1 and not self.next and self.local[0][1] == 1 and self.constant == 0
+
+    def words(self):
+        w = [len(self.local) | (len(self.next) << 32), self.constant]
+        for c, k in self.local + self.next:
+            w += [c, k]
+        return w
+
+
+class Filter:
+    """sum A * B + sum C over `Column`s (starky's `Filter`): `products` a list of (A, B), `sums` a list of C.  The empty filter is 1."""
+
+    def __init__(self, products=(), sums=()):
+        self.products = [(_column(a), _column(b)) for a, b in products]
+        self.sums = [_column(c) for c in sums]
+
+    def is_empty(self):
+        return not self.products and not self.sums
+
+    def words(self):
+        w = [len(self.products) | (len(self.sums) << 32)]
+        for a, b in self.products:
+            w += a.words() + b.words()
+        for c in self.sums:
+            w += c.words()
+        return w
+
+
+def _column(x):
+    """a Column, or a trace column's number for the plain one"""
+    return x if isinstance(x, Column) else Column.single(int(x))
+
+
 class AirBuilder:
     """csrc/air_ir.h `AirBuilder`: constraints in the order of the reference's eval_packed_generic (the order fixes each one's power
     of alpha); finish() returns the serialised program as a numpy uint64 array."""
@@ -184,6 +238,8 @@ class AirBuilder:
         self.perm_pairs = []
         self.lookups = []  # (input, table, permuted_input, permuted_table) of every lookup()
         self.logups = []  # (columns, table, frequencies) of every logup()
+        self.general_logups = []  # every lookup, in declaration order, as (pairs, table, frequencies) of Columns and Filters
+        self._logup_general = False  # a logup_columns() was declared: all of them go into the general section
 
     def L(self, col):
         self._check_col(col)
@@ -250,6 +306,22 @@ class AirBuilder:
         for c in columns + [int(table), int(frequencies)]:
             self._check_col(c)
         self.logups.append((columns, int(table), int(frequencies)))
+        self.general_logups.append(([(Column.single(c), Filter()) for c in columns], Column.single(table), Column.single(frequencies)))
+
+    def logup_columns(self, pairs, table, frequencies):
+        """One general LogUp lookup (COMPAT.md §2c): `pairs` is a list of (Column, Filter or None) -- each looked-up value with the filter
+        that says on which rows it is looked up (1) or not (0) --, `table` and `frequencies` are Columns; a trace column's number stands
+        for the plain Column.  Once one is declared the program's lookups, those of logup() included, go into the "LOGUPS02" section in
+        declaration order; a program with logup() alone keeps its "LOGUPS01" bytes."""
+        pairs = [(_column(v), f if f is not None else Filter()) for v, f in pairs]
+        table, frequencies = _column(table), _column(frequencies)
+        for v, f in pairs:
+            for col in [v] + [x for ab in f.products for x in ab] + f.sums:
+                self._check_column(col)
+        self._check_column(table)
+        self._check_column(frequencies)
+        self.general_logups.append((pairs, table, frequencies))
+        self._logup_general = True
 
     def count(self):
         return self.n_constraints
@@ -266,7 +338,13 @@ class AirBuilder:
             words += [AIR_PERM_MAGIC, len(self.perm_pairs)]
             for entries in self.perm_pairs:
                 words += [len(entries)] + [l | (r << 32) for l, r in entries]
-        if self.logups:  # the other optional section, in the same place
+        if self._logup_general:  # the general section holds every lookup
+            words += [AIR_LOGUP2_MAGIC, len(self.general_logups)]
+            for pairs, table, freq in self.general_logups:
+                words += [len(pairs)] + table.words() + freq.words()
+                for v, f in pairs:
+                    words += v.words() + f.words()
+        elif self.logups:  # the other optional section, in the same place
             words += [AIR_LOGUP_MAGIC, len(self.logups)]
             for columns, table, freq in self.logups:
                 words += [len(columns), table | (freq << 32)] + columns
@@ -275,6 +353,12 @@ class AirBuilder:
     def _check_col(self, col):
         if not 0 <= col < self.n_cols:
             raise ValueError(f"air_builder: column {col} out of range")
+
+    def _check_column(self, column):
+        for c, k in column.local + column.next:
+            self._check_col(c)
+            if k == 0:
+                raise ValueError("air_builder: zero coefficient in a Column")
 
     def _const_index(self, c):
         if c not in self._const_idx:

@@ -237,6 +237,15 @@ def air_logup_polys(air):
     return r
 
 
+def air_logup_general(air):
+    """starkhip_air_logup_general: 1 when some LogUp lookup of the AIR is over Column combinations or has a filter (the general kernels
+    run), 0 when all are plain."""
+    r = lib.starkhip_air_logup_general(air)
+    if r < 0:
+        raise StarkhipError(r)
+    return r
+
+
 def air_program(air):
     """Serialised constraint program (numpy uint64 copy)."""
     blob = _u64p()

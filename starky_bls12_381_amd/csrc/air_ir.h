@@ -36,6 +36,11 @@
 // the same place -- a program has pairs or LogUp lookups, not both --
 //   AIR_LOGUP_MAGIC, n_lookups, then per lookup: n_columns, table column | frequencies column << 32, n_columns column words.
 // A lookup's columns are cut in declaration order into helper batches of degree - 1 (logup.h has the polynomials' order).
+// The general form of the same section (upstream's Column and Filter, COMPAT.md 2c), never beside the first:
+//   AIR_LOGUP2_MAGIC, n_lookups, then per lookup: n_columns, COLUMN table, COLUMN frequencies, n_columns x { COLUMN value, FILTER }
+//   COLUMN := n_local | n_next << 32, constant, then (n_local + n_next) x { trace column, coefficient }   (local terms first)
+//   FILTER := n_products | n_sums << 32, then 2 n_products + n_sums COLUMNs (each product's A then B, then the sums)
+// A COLUMN is constant + sum coefficient * cell over the local and the next row; a FILTER is sum A B + sum C, and 1 when it is empty.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -57,6 +62,8 @@ static const uint32_t AIR_MAX_GROUP = 255;
 static const uint64_t AIR_MAGIC = 0x3152495F52494153ULL;  // "SAIR_IR1"
 static const uint64_t AIR_PERM_MAGIC = 0x3153524941504D50ULL;  // "PMPAIRS1": the section of permutation pairs
 static const uint64_t AIR_LOGUP_MAGIC = 0x3130535055474F4CULL;  // "LOGUPS01": the section of LogUp lookups
+static const uint64_t AIR_LOGUP2_MAGIC = 0x3230535055474F4CULL;  // "LOGUPS02": the same over Columns and Filters
+static const uint32_t AIR_LOGUP_MAX_TERMS = 16, AIR_LOGUP_MAX_FILTER_PRODUCTS = 4, AIR_LOGUP_MAX_FILTER_SUMS = 4;
 
 // The rows a constraint of `kind` applies to, of a trace of n rows: the one rule of the device checkers' walker
 // (kernels_check.hip) and of the host replay (check_report.cpp).  Written without short-circuit operators: in the walker's loop
@@ -92,11 +99,62 @@ struct AirProgram {
     uint32_t perm_batch_size() const { return degree > 1 ? degree - 1 : 1; }  // B: quotient_degree_factor, and permutation_batch_size()
     uint32_t perm_batches() const { return (uint32_t)((perm_pairs.size() + perm_batch_size() - 1) / perm_batch_size()); }
     uint32_t perm_zs() const { return 2 * perm_batches(); }  // nZ: one Z per (batch, challenge)
-    // LogUp lookups: `cols` looked up in column `table` with the multiplicities in column `freq` (empty for every built-in AIR)
-    struct Logup {
-        std::vector<uint32_t> cols;
-        uint32_t table, freq;
+    // LogUp lookups (empty for every built-in AIR).  A Column is constant + sum coef * cell, the first n_local terms on the local row and
+    // the others on the next; a Filter is sum A B + sum C over Columns (`cols`: each product's A then B, then the sums), 1 when empty.
+    struct Column {
+        struct Term { uint32_t col; gl_t coef; };
+        uint32_t n_local = 0;
+        gl_t constant = 0;
+        std::vector<Term> terms;
+        Column() {}
+        Column(uint32_t col) : n_local(1), terms{{col, 1}} {}  // a plain column: one local cell, coefficient 1, constant 0
+        bool plain() const { return n_local == 1 && terms.size() == 1 && terms[0].coef == 1 && constant == 0; }
+        uint32_t col() const { return terms.empty() ? ~0u : terms[0].col; }  // of a plain one
+        operator uint32_t() const { return col(); }                             // (code that knows plain lookups alone reads a column number)
+        bool operator==(const Column& o) const {
+            if (n_local != o.n_local || constant != o.constant || terms.size() != o.terms.size()) return false;
+            for (size_t k = 0; k < terms.size(); k++)
+                if (terms[k].col != o.terms[k].col || terms[k].coef != o.terms[k].coef) return false;
+            return true;
+        }
+        void push(std::vector<uint64_t>& b) const {
+            b.push_back((uint64_t)n_local | ((uint64_t)(terms.size() - n_local) << 32));
+            b.push_back(constant);
+            for (const Term& t : terms) { b.push_back(t.col); b.push_back(t.coef); }
+        }
+        template <class F> void each_column(const F& f) const { for (const Term& t : terms) f(t.col); }
     };
+    struct Filter {
+        uint32_t n_products = 0;
+        std::vector<Column> cols;
+        bool empty() const { return cols.empty(); }
+        void push(std::vector<uint64_t>& b) const {
+            b.push_back((uint64_t)n_products | ((uint64_t)(cols.size() - 2 * n_products) << 32));
+            for (const Column& c : cols) c.push(b);
+        }
+    };
+    // `cols` under `filters` (one each) looked up in `table` with the multiplicities in `freq`
+    struct Logup {
+        std::vector<Column> cols;
+        std::vector<Filter> filters;
+        Column table, freq;
+        bool plain() const {
+            for (const Column& v : cols) if (!v.plain()) return false;
+            for (const Filter& f : filters) if (!f.empty()) return false;
+            return table.plain() && freq.plain();
+        }
+        template <class F> void each_column(const F& f) const {  // every trace column the lookup reads
+            table.each_column(f);
+            freq.each_column(f);
+            for (const Column& v : cols) v.each_column(f);
+            for (const Filter& fl : filters) for (const Column& c : fl.cols) c.each_column(f);
+        }
+    };
+    bool logup_section2 = false;  // the lookups came from (and go back into) the general section
+    bool logup_general() const {  // some lookup is not plain: the general kernels run
+        for (const Logup& l : logups) if (!l.plain()) return true;
+        return false;
+    }
     std::vector<Logup> logups;
     uint32_t logup_batch_size() const { return degree > 1 ? degree - 1 : 1; }
     uint32_t logup_helpers(size_t l) const { return (uint32_t)((logups[l].cols.size() + logup_batch_size() - 1) / logup_batch_size()); }  // H_l
@@ -136,13 +194,26 @@ struct AirProgram {
                 b.insert(b.end(), pr.begin(), pr.end());
             }
         }
-        if (!logups.empty()) {
+        if (!logups.empty() && !logup_section2) {  // (a program of the first section has plain lookups only)
             b.push_back(AIR_LOGUP_MAGIC);
             b.push_back(logups.size());
             for (const Logup& l : logups) {
                 b.push_back(l.cols.size());
-                b.push_back((uint64_t)l.table | ((uint64_t)l.freq << 32));
-                b.insert(b.end(), l.cols.begin(), l.cols.end());
+                b.push_back((uint64_t)l.table.col() | ((uint64_t)l.freq.col() << 32));
+                for (const Column& v : l.cols) b.push_back(v.col());
+            }
+        }
+        if (!logups.empty() && logup_section2) {
+            b.push_back(AIR_LOGUP2_MAGIC);
+            b.push_back(logups.size());
+            for (const Logup& l : logups) {
+                b.push_back(l.cols.size());
+                l.table.push(b);
+                l.freq.push(b);
+                for (size_t k = 0; k < l.cols.size(); k++) {
+                    l.cols[k].push(b);
+                    l.filters[k].push(b);
+                }
             }
         }
         return b;
@@ -372,10 +443,40 @@ class AirBuilder {
     // how often the row's table value is looked up.  No constraint is emitted here: the prover and the verifiers add the helper and Z
     // constraints after the AIR's own.  The validator refuses it beside permutation pairs and at degree 1.
     void logup(const std::vector<uint32_t>& columns, uint32_t table, uint32_t frequencies) {
-        for (uint32_t c : columns) check_col(c);
-        check_col(table);
-        check_col(frequencies);
-        prog_.logups.push_back({columns, table, frequencies});
+        AirProgram::Logup lk;
+        for (uint32_t c : columns) lk.cols.push_back(AirProgram::Column(c));
+        lk.filters.resize(columns.size());
+        lk.table = AirProgram::Column(table);
+        lk.freq = AirProgram::Column(frequencies);
+        check_logup(lk);
+        prog_.logups.push_back(std::move(lk));
+    }
+    // The general LogUp lookup: pairs of a looked-up Column and its Filter (an empty one for none), a table Column and a frequencies
+    // Column.  Column { constant, local terms, next terms } and Filter { products, sums } are AirProgram's; column_of() makes one.  Once a
+    // general lookup is declared every lookup of the program, plain ones included, goes into the general section.
+    static AirProgram::Column column_of(gl_t constant, const std::vector<std::pair<uint32_t, gl_t>>& local, const std::vector<std::pair<uint32_t, gl_t>>& next = {}) {
+        AirProgram::Column c;
+        c.constant = constant;
+        c.n_local = (uint32_t)local.size();
+        for (const auto& t : local) c.terms.push_back({t.first, t.second});
+        for (const auto& t : next) c.terms.push_back({t.first, t.second});
+        return c;
+    }
+    static AirProgram::Filter filter_of(const std::vector<std::pair<AirProgram::Column, AirProgram::Column>>& products, const std::vector<AirProgram::Column>& sums = {}) {
+        AirProgram::Filter f;
+        f.n_products = (uint32_t)products.size();
+        for (const auto& ab : products) { f.cols.push_back(ab.first); f.cols.push_back(ab.second); }
+        f.cols.insert(f.cols.end(), sums.begin(), sums.end());
+        return f;
+    }
+    void logup_columns(const std::vector<std::pair<AirProgram::Column, AirProgram::Filter>>& pairs, const AirProgram::Column& table, const AirProgram::Column& frequencies) {
+        AirProgram::Logup lk;
+        for (const auto& vf : pairs) { lk.cols.push_back(vf.first); lk.filters.push_back(vf.second); }
+        lk.table = table;
+        lk.freq = frequencies;
+        check_logup(lk);
+        prog_.logups.push_back(std::move(lk));
+        prog_.logup_section2 = true;
     }
     const std::vector<Lookup>& lookups() const { return lookups_; }
 
@@ -401,6 +502,10 @@ class AirBuilder {
 
     void check_col(uint32_t col) const {
         if (col >= prog_.n_cols) throw std::runtime_error("air_ir: column " + std::to_string(col) + " out of range");
+    }
+
+    void check_logup(const AirProgram::Logup& lk) const {
+        lk.each_column([&](uint32_t col) { check_col(col); });
     }
 
     uint32_t const_index(gl_t c) {

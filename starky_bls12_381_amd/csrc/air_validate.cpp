@@ -27,7 +27,7 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
     const uint64_t code_u64 = (n_code + 1) / 2;
     const uint64_t base_words = 8 + n_consts + code_u64 + n_groups;  // every count is below 2^27 here: no overflow
     // what follows the group table is the section of permutation pairs or of LogUp lookups, or nothing (a word that is neither section's magic is a wrong length)
-    if ((uint64_t)words < base_words || ((uint64_t)words > base_words && blob[base_words] != AIR_PERM_MAGIC && blob[base_words] != AIR_LOGUP_MAGIC))
+    if ((uint64_t)words < base_words || ((uint64_t)words > base_words && blob[base_words] != AIR_PERM_MAGIC && blob[base_words] != AIR_LOGUP_MAGIC && blob[base_words] != AIR_LOGUP2_MAGIC))
         return refuse(why, "blob length " + std::to_string(words) + " differs from the " + std::to_string(base_words) + " words its header implies");
     const uint64_t* consts = blob + 8;
     const uint64_t* code64 = consts + n_consts;
@@ -132,7 +132,7 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
             P.perm_pairs.emplace_back(sec + at, sec + at + ne);
             at += ne;
         }
-        if (at < sec_words && sec[at] == AIR_LOGUP_MAGIC)
+        if (at < sec_words && (sec[at] == AIR_LOGUP_MAGIC || sec[at] == AIR_LOGUP2_MAGIC))
             return refuse(why, "permutation pairs and LogUp lookups together (the two share the middle matrix of a proof)");
         if (at != sec_words) return refuse(why, "trailing words after the permutation section");
     }
@@ -156,17 +156,85 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
             if (table >= n_cols || freq >= n_cols) return refuse(why, atl + "column " + std::to_string(table >= n_cols ? table : freq) + " out of range");
             if (sec_words - at < m) return refuse(why, atl + "columns run past the blob");
             AirProgram::Logup lk;
-            lk.table = (uint32_t)table;
-            lk.freq = (uint32_t)freq;
+            lk.table = AirProgram::Column((uint32_t)table);
+            lk.freq = AirProgram::Column((uint32_t)freq);
             for (uint64_t e = 0; e < m; e++) {
                 if (sec[at + e] >= n_cols) return refuse(why, atl + "column " + std::to_string(sec[at + e]) + " out of range");
-                lk.cols.push_back((uint32_t)sec[at + e]);
+                lk.cols.push_back(AirProgram::Column((uint32_t)sec[at + e]));
             }
+            lk.filters.resize(m);
             P.logups.push_back(std::move(lk));
             at += m;
         }
         if (at < sec_words && sec[at] == AIR_PERM_MAGIC)
             return refuse(why, "permutation pairs and LogUp lookups together (the two share the middle matrix of a proof)");
+        if (at < sec_words && sec[at] == AIR_LOGUP2_MAGIC) return refuse(why, "LogUp sections of both versions together (declare every lookup in the general one)");
+        if (at != sec_words) return refuse(why, "trailing words after the LogUp section");
+        if (P.logup_polys() > STARKHIP_AIR_MAX_LOGUP_POLYS)
+            return refuse(why, "LogUp lookups make " + std::to_string(P.logup_polys()) + " auxiliary polynomials (at most " + std::to_string(STARKHIP_AIR_MAX_LOGUP_POLYS) + ")");
+    }
+    // ---- LogUp lookups over Columns and Filters: the general section, by the same rules
+    if ((uint64_t)words > base_words && blob[base_words] == AIR_LOGUP2_MAGIC) {
+        const uint64_t* sec = blob + base_words;
+        const uint64_t sec_words = (uint64_t)words - base_words;
+        if (sec_words < 2) return refuse(why, "LogUp section shorter than its 2-word header");
+        const uint64_t n_lookups = sec[1];
+        if (n_lookups < 1 || n_lookups > STARKHIP_AIR_MAX_LOGUP_LOOKUPS)
+            return refuse(why, "LogUp section with " + std::to_string(n_lookups) + " lookups (1.." + std::to_string(STARKHIP_AIR_MAX_LOGUP_LOOKUPS) + ")");
+        if (degree < 2) return refuse(why, "LogUp lookups need degree >= 2 (a helper constraint has degree 1 + the columns of its batch)");
+        uint64_t at = 2;
+        std::string msg2;
+        auto column = [&](AirProgram::Column* c) {  // one COLUMN at sec[at]
+            if (sec_words - at < 2) return msg2 = "runs past the blob", false;
+            const uint64_t nl = sec[at] & 0xFFFFFFFFu, nn = sec[at] >> 32, constant = sec[at + 1];
+            at += 2;
+            if (nl + nn > AIR_LOGUP_MAX_TERMS) return msg2 = "Column of " + std::to_string(nl + nn) + " terms (at most " + std::to_string(AIR_LOGUP_MAX_TERMS) + ")", false;
+            if (constant >= GL_P) return msg2 = "Column constant is not canonical", false;
+            if ((sec_words - at) / 2 < nl + nn) return msg2 = "Column terms run past the blob", false;
+            c->n_local = (uint32_t)nl;
+            c->constant = constant;
+            for (uint64_t k = 0; k < nl + nn; k++, at += 2) {
+                if (sec[at] >= n_cols) return msg2 = "column " + std::to_string(sec[at]) + " out of range", false;
+                if (sec[at + 1] == 0) return msg2 = "Column coefficient is zero", false;
+                if (sec[at + 1] >= GL_P) return msg2 = "Column coefficient is not canonical", false;
+                c->terms.push_back({(uint32_t)sec[at], sec[at + 1]});
+            }
+            return true;
+        };
+        for (uint64_t l = 0; l < n_lookups; l++) {
+            const std::string atl = "LogUp lookup " + std::to_string(l) + ": ";
+            if (at >= sec_words) return refuse(why, atl + "runs past the blob");
+            const uint64_t m = sec[at++];
+            if (m < 1) return refuse(why, atl + "empty lookup");
+            if (m > STARKHIP_AIR_MAX_LOGUP_COLUMNS) return refuse(why, atl + std::to_string(m) + " columns (at most " + std::to_string(STARKHIP_AIR_MAX_LOGUP_COLUMNS) + ")");
+            AirProgram::Logup lk;
+            if (!column(&lk.table)) return refuse(why, atl + "table: " + msg2);
+            if (!column(&lk.freq)) return refuse(why, atl + "frequencies: " + msg2);
+            for (uint64_t e = 0; e < m; e++) {
+                const std::string ate = atl + "column " + std::to_string(e) + ": ";
+                AirProgram::Column v;
+                if (!column(&v)) return refuse(why, ate + msg2);
+                if (at >= sec_words) return refuse(why, ate + "filter runs past the blob");
+                const uint64_t np = sec[at] & 0xFFFFFFFFu, ns = sec[at] >> 32;
+                at++;
+                if (np > AIR_LOGUP_MAX_FILTER_PRODUCTS) return refuse(why, ate + "filter of " + std::to_string(np) + " products (at most " + std::to_string(AIR_LOGUP_MAX_FILTER_PRODUCTS) + ")");
+                if (ns > AIR_LOGUP_MAX_FILTER_SUMS) return refuse(why, ate + "filter of " + std::to_string(ns) + " sums (at most " + std::to_string(AIR_LOGUP_MAX_FILTER_SUMS) + ")");
+                AirProgram::Filter f;
+                f.n_products = (uint32_t)np;
+                for (uint64_t k = 0; k < 2 * np + ns; k++) {
+                    AirProgram::Column fc;
+                    if (!column(&fc)) return refuse(why, ate + "filter: " + msg2);
+                    f.cols.push_back(std::move(fc));
+                }
+                lk.cols.push_back(std::move(v));
+                lk.filters.push_back(std::move(f));
+            }
+            P.logups.push_back(std::move(lk));
+        }
+        P.logup_section2 = true;
+        if (at < sec_words && sec[at] == AIR_PERM_MAGIC)
+            return refuse(why, "permutation pairs and LogUp lookups together (the two share the middle matrix of a proof)");
+        if (at < sec_words && sec[at] == AIR_LOGUP_MAGIC) return refuse(why, "LogUp sections of both versions together (declare every lookup in the general one)");
         if (at != sec_words) return refuse(why, "trailing words after the LogUp section");
         if (P.logup_polys() > STARKHIP_AIR_MAX_LOGUP_POLYS)
             return refuse(why, "LogUp lookups make " + std::to_string(P.logup_polys()) + " auxiliary polynomials (at most " + std::to_string(STARKHIP_AIR_MAX_LOGUP_POLYS) + ")");

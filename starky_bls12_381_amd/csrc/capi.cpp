@@ -176,6 +176,7 @@ int starkhip_air_logup_columns(starkhip_air_t air) {
     for (const AirProgram::Logup& l : a->prog.logups) m += l.cols.size();
     return (int)m;
 }
+int starkhip_air_logup_general(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (a->prog.logup_general() ? 1 : 0) : STARKHIP_ERR_BAD_AIR; }
 int starkhip_air_logup_polys(starkhip_air_t air) { const AirInfo* a = air_get(air); return a ? (int)a->prog.logup_polys() : STARKHIP_ERR_BAD_AIR; }
 
 int starkhip_air_eval_frame_logup(starkhip_air_t air, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
@@ -188,8 +189,11 @@ int starkhip_air_eval_frame_logup(starkhip_air_t air, const uint64_t* local, con
     if (!nA) return STARKHIP_OK;
     if (!aux || !aux_next || !challenges || challenges[0] >= GL_P || challenges[1] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
     try {
-        std::vector<gl2_t> l(a->cols), x(nA), xn(nA), al(n_alpha), acc(n_alpha);
-        for (size_t i = 0; i < a->cols; i++) l[i] = gl2_make(local[2 * i], local[2 * i + 1]);
+        std::vector<gl2_t> l(a->cols), nx(a->cols), x(nA), xn(nA), al(n_alpha), acc(n_alpha);
+        for (size_t i = 0; i < a->cols; i++) {
+            l[i] = gl2_make(local[2 * i], local[2 * i + 1]);
+            nx[i] = gl2_make(next[2 * i], next[2 * i + 1]);
+        }
         for (size_t i = 0; i < nA; i++) {
             x[i] = ExtOps::canon(gl2_make(aux[2 * i], aux[2 * i + 1]));
             xn[i] = ExtOps::canon(gl2_make(aux_next[2 * i], aux_next[2 * i + 1]));
@@ -200,7 +204,7 @@ int starkhip_air_eval_frame_logup(starkhip_air_t air, const uint64_t* local, con
             al[j] = gl2_make(alphas[2 * j], alphas[2 * j + 1]);
             acc[j] = gl2_make(acc_out[2 * j], acc_out[2 * j + 1]);
         }
-        logup_eval_folded<ExtOps>(a->prog, l.data(), x.data(), xn.data(), challenges, mk, al.data(), n_alpha, acc.data());
+        logup_eval_folded<ExtOps>(a->prog, l.data(), nx.data(), x.data(), xn.data(), challenges, mk, al.data(), n_alpha, acc.data());
         for (int j = 0; j < n_alpha; j++) {
             acc_out[2 * j] = acc[j].a0;
             acc_out[2 * j + 1] = acc[j].a1;

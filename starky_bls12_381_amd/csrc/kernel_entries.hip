@@ -52,7 +52,8 @@ int logup_polys(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t
     const unsigned nzs = 2 * (unsigned)P.logups.size();
     HIPCHK(hipSetDevice(c->device));
     const std::vector<uint32_t> cols = logup_columns(P);
-    std::vector<uint32_t> desc = logup_descriptor(P, true);
+    const bool general = logup_use_general(P);
+    std::vector<uint32_t> desc = logup_descriptor(P, true, general);
     const size_t desc_words = desc.size();
     const std::vector<uint32_t> zp = logup_z_polys(P);
     desc.insert(desc.end(), zp.begin(), zp.end());
@@ -69,7 +70,7 @@ int logup_polys(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t
         HIPCHK(hipMemcpyAsync(pb.cols.as<gl_t>() + k * n, d_values + (size_t)cols[k] * n, n * 8, hipMemcpyDeviceToDevice, c->st));
     HIPCHK(hipMemcpyAsync(pb.desc.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, c->st));
     gl_t* const d_results = pb.scan.as<gl_t>() + logup_scratch_words(n, nzs);
-    HIPCHK(launch_logup_polys(pb.desc.as<uint32_t>(), pb.desc.as<uint32_t>() + desc_words, pb.cols.as<gl_t>(), n, challenges[0], challenges[1], n, nzs,
+    HIPCHK(launch_logup_polys(pb.desc.as<uint32_t>(), general, pb.desc.as<uint32_t>() + desc_words, pb.cols.as<gl_t>(), n, challenges[0], challenges[1], n, nzs,
                               pb.zvals.as<gl_t>(), pb.scan.as<gl_t>(), d_results, c->st));
     std::vector<gl_t> results(logup_result_words(nzs));
     HIPCHK(hipMemcpyAsync(polys_out, pb.zvals.p, nA * n * 8, hipMemcpyDeviceToHost, c->st));

@@ -22,6 +22,14 @@ hipError_t launch_logup_freq_keys(const LogupFreqTrace& t, size_t n, const uint3
 // combine: equal positions inside a wave are added as one (the result is the same either way).
 hipError_t launch_logup_freq_count(const LogupFreqTrace& t, size_t n, const uint32_t* cols, size_t n_cols, size_t lookups, const gl_t* keys, uint32_t* count,
                                    unsigned long long* mask, uint32_t* missing, bool combine, hipStream_t st);
+// The same two for lookups over Columns and Filters: desc holds COLUMNs and FILTERs in logup.h's descriptor words, over the trace's
+// columns as `t` numbers them; offs [slots]: where slot y's table COLUMN starts; cols: n_cols x {where the value's COLUMN, followed by
+// its FILTER, starts, lookup of the batch, table slot of the batch}.  A cell whose filter is 0 is skipped; one whose filter is neither
+// 0 nor 1 counts as missing.  n is a power of two (the next row of the last is row 0).
+hipError_t launch_logup_freq_keys_general(const LogupFreqTrace& t, size_t n, const uint32_t* desc, const uint32_t* offs, size_t slots, gl_t* keys, uint32_t* idx,
+                                          hipStream_t st);
+hipError_t launch_logup_freq_count_general(const LogupFreqTrace& t, size_t n, const uint32_t* desc, const uint32_t* cols, size_t n_cols, size_t lookups, const gl_t* keys,
+                                           uint32_t* count, unsigned long long* mask, uint32_t* missing, bool combine, hipStream_t st);
 // One lane per sorted table position of each lookup; lks: lookups x {table slot, frequencies column}: f[idx[pos]] = count[pos].
 // gate (device, or null): lookup y is written only when gate[y] == 0 -- its missing count, so that a lookup that fails leaves its
 // column as it was.  Null writes every lookup (the prover's own copy of a trace).

@@ -11,6 +11,7 @@
 
 #include "check_report.h"
 #include "gl.h"
+#include "logup.h"
 
 namespace starkhip {
 
@@ -20,28 +21,55 @@ bool logup_fillable(const AirProgram& P, std::string* why) {
         return false;
     };
     for (size_t q = 0; q < P.logups.size(); q++) {
-        const uint32_t f = P.logups[q].freq;
-        const std::string who = "LogUp lookup " + std::to_string(q) + ": frequencies column " + std::to_string(f);
+        const std::string who = "LogUp lookup " + std::to_string(q) + ": ";
+        if (!P.logups[q].freq.plain()) return refuse(who + "its frequencies are a combination, not one plain column");
+        const uint32_t f = P.logups[q].freq.col();
         for (size_t r = 0; r < P.logups.size(); r++) {
             const AirProgram::Logup& b = P.logups[r];
-            if (f == b.table) return refuse(who + " is the table column of lookup " + std::to_string(r));
-            if (std::find(b.cols.begin(), b.cols.end(), f) != b.cols.end()) return refuse(who + " is a looked-up column of lookup " + std::to_string(r));
-            if (r != q && f == b.freq) return refuse(who + " is also the frequencies column of lookup " + std::to_string(r));
+            if (r != q && b.freq.plain() && f == b.freq.col()) return refuse(who + "frequencies column " + std::to_string(f) + " is also the frequencies column of lookup " + std::to_string(r));
+            bool read = false;
+            auto see = [&](uint32_t col) { read |= col == f; };
+            b.table.each_column(see);
+            if (read) return refuse(who + "frequencies column " + std::to_string(f) + " is read by the table column of lookup " + std::to_string(r));
+            for (const AirProgram::Column& v : b.cols) v.each_column(see);
+            for (const AirProgram::Filter& fl : b.filters)
+                for (const AirProgram::Column& c : fl.cols) c.each_column(see);
+            if (read) return refuse(who + "frequencies column " + std::to_string(f) + " is read by a looked-up column or a filter of lookup " + std::to_string(r));
         }
     }
     return true;
 }
 
-LogupFreqPlan::LogupFreqPlan(const AirProgram& P) : L(P.logups.size()) {
+LogupFreqPlan::LogupFreqPlan(const AirProgram& P) : L(P.logups.size()), prog(&P) {
     col_off.push_back(0);
-    for (const AirProgram::Logup& l : P.logups) {
-        cols.insert(cols.end(), l.cols.begin(), l.cols.end());
-        col_off.push_back((uint32_t)cols.size());
-        table.push_back(l.table);
-        freq.push_back(l.freq);
+    general = false;
+    for (const AirProgram::Logup& l : P.logups) general |= !l.plain();
+    size_t words = 0;
+    auto column_words = [](const AirProgram::Column& c) { return 3 + 3 * c.terms.size(); };
+    for (size_t q = 0; q < L; q++) {
+        const AirProgram::Logup& l = P.logups[q];
+        col_off.push_back(col_off.back() + (uint32_t)l.cols.size());
+        freq.push_back(l.freq.col());  // (a fillable program: plain)
+        size_t first = q;
+        for (size_t r = 0; r < q && first == q; r++)
+            if (P.logups[r].table == l.table) first = r;
+        table_of.push_back((uint32_t)first);
+        if (!general) {
+            for (const AirProgram::Column& v : l.cols) cols.push_back(v.col());
+            table.push_back(l.table.col());
+        }
+        l.table.each_column([&](uint32_t c) { named.push_back(c); });
+        words += column_words(l.table);
+        for (size_t k = 0; k < l.cols.size(); k++) {
+            l.cols[k].each_column([&](uint32_t c) { named.push_back(c); });
+            words += column_words(l.cols[k]) + 1;
+            for (const AirProgram::Column& c : l.filters[k].cols) {
+                c.each_column([&](uint32_t x) { named.push_back(x); });
+                words += column_words(c);
+            }
+        }
     }
-    named = cols;
-    named.insert(named.end(), table.begin(), table.end());
+    desc_words = 3 * (L + n_values()) + (general ? words : 0);
     std::sort(named.begin(), named.end());
     named.erase(std::unique(named.begin(), named.end()), named.end());
 }
@@ -105,8 +133,10 @@ struct ReplayFreqSteps : LogupFreqSteps {
         return STARKHIP_OK;
     }
     void run_one(size_t q, uint64_t* mask, uint32_t* col_missing) {
+        const AirProgram::Logup& lk = plan.prog->logups[q];
+        auto cell = [&](uint32_t col, size_t r) { return in.words[in.at(r, col)]; };
         std::vector<gl_t> t(n);
-        for (size_t r = 0; r < n; r++) t[r] = gl_from_u64(in.words[in.at(r, plan.table[q])]);
+        for (size_t r = 0; r < n; r++) t[r] = logup_column_at(lk.table, cell, r, n);
         std::vector<uint32_t> order(n);  // the rows by (value, row): the first of a run of equal values is a FIRST
         std::iota(order.begin(), order.end(), 0u);
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return t[a] < t[b]; });
@@ -115,12 +145,13 @@ struct ReplayFreqSteps : LogupFreqSteps {
         std::vector<uint32_t> count(n, 0);
         bool any = false;
         for (size_t k = 0; k < plan.m(q); k++) {
-            const uint32_t col = plan.cols[plan.col_off[q] + k];
             for (size_t r = 0; r < n; r++) {
-                const gl_t v = gl_from_u64(in.words[in.at(r, col)]);
+                const gl_t phi = logup_filter_at(lk.filters[k], cell, r, n);
+                if (phi == 0) continue;  // skipped
+                const gl_t v = logup_column_at(lk.cols[k], cell, r, n);
                 const size_t pos = (size_t)(std::lower_bound(sorted.begin(), sorted.end(), v) - sorted.begin());
-                if (pos < n && sorted[pos] == v) count[pos]++;
-                else {
+                if (phi == 1 && pos < n && sorted[pos] == v) count[pos]++;
+                else {  // missing, or flagged
                     mask[r >> 6] |= 1ull << (r & 63);
                     col_missing[k]++;
                     any = true;

@@ -8,6 +8,11 @@
 //   no cell is missing, f[r] = the number of the m n looked-up cells equal to t[r] on a first and 0 elsewhere.  Otherwise f stays as it
 //   was, and the rows with a missing cell are the lookup's missing rows.
 //
+// A lookup over Columns and Filters (logup.h) follows the same rule with values for cells: the keys of a table are its Column's values,
+// and a looked-up cell (c, r) is SKIPPED when its filter phi_c(r) is 0, looked up and counted when phi_c(r) is 1, and FLAGGED when
+// phi_c(r) is anything else -- the fill needs a multiplicity, and the argument would need phi as one.  Flagged cells count as missing,
+// in the same masks, counters, list and LogUp blob, whose layouts do not change.
+//
 // The lookups of a call run in BATCHES of G consecutive lookups (logup_freq_batch_size): one set of launches and one wait for the
 // missing counts on the device.  The same file has the LogUp blob a prove() with "fill_frequencies" hands back for a trace some lookup
 // of which fails.
@@ -24,16 +29,23 @@
 
 namespace starkhip {
 
-// An AIR is FILLABLE when no frequencies column is a looked-up or table column of any lookup or another lookup's frequencies column:
-// then the order of the lookups does not matter.  `why` (may be null) gets the reason of a refusal.
+// An AIR is FILLABLE when every frequencies Column is one plain local column (coefficient 1, constant 0) that no Column or Filter of
+// any lookup reads and that is no other lookup's frequencies column: then the order of the lookups does not matter.  `why` (may be null) gets the reason of a refusal.
 bool logup_fillable(const AirProgram& P, std::string* why);
 
-// The lookups of a program as the steps want them.  cols: the looked-up columns of all lookups back to back in declaration order
-// (sum m entries), those of lookup q from col_off[q] to col_off[q + 1]; named: the distinct columns a fill READS, ascending.
+// The lookups of a fillable program as the steps want them.  The looked-up values of all lookups are numbered back to back in
+// declaration order (sum m), those of lookup q from col_off[q] to col_off[q + 1]; freq: the frequencies columns; table_of[q]: the
+// first lookup with the same table Column (compared structurally: the distinct tables of a batch); named: the distinct columns a fill
+// READS, ascending.  A program of plain lookups (general == false) also has cols and table, the looked-up and the table columns, and
+// runs the kernels over columns; any other runs the ones that evaluate Columns and Filters.  `prog` must outlive the plan.
 struct LogupFreqPlan {
     size_t L = 0;
-    std::vector<uint32_t> cols, col_off, table, freq, named;
+    const AirProgram* prog = nullptr;
+    bool general = false;
+    size_t desc_words = 0;  // what one batch's descriptor takes at most
+    std::vector<uint32_t> cols, col_off, table, table_of, freq, named;
     explicit LogupFreqPlan(const AirProgram& P);
+    size_t n_values() const { return col_off.back(); }
     size_t m(size_t q) const { return col_off[q + 1] - col_off[q]; }
 };
 

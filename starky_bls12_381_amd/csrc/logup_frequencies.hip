@@ -1,7 +1,8 @@
 // starkhip_logup_frequencies and the fill of prove() ("fill_frequencies") on the context's device: the LogUp lookups of an AIR in
 // batches of G consecutive lookups (logup_freq_batch_size).  Per batch: the keys of its distinct table columns and their stable sort
 // (kernels_multiset.hip, in the sorted-items buffers of the context, n items per table), then count and write of
-// kernels_logup_freq.hip with grid.y = looked-up column and grid.y = lookup, under the host half of logup_frequencies.h.  A device
+// kernels_logup_freq.hip with grid.y = looked-up column and grid.y = lookup, under the host half of logup_frequencies.h.  A program with
+// a lookup over Columns or Filters runs the general keys and count kernels over a descriptor of them; a plain one the kernels it always ran.  A device
 // trace is read and written where it lies, in either layout (element r of column c at stride 1 or n_cols); of a host trace the
 // distinct columns the fill reads go up in one copy and, for a lookup that holds, its frequencies column comes back.
 // The write follows the count on the stream without a wait in between.  In the caller's trace it is gated on the device by the
@@ -16,6 +17,7 @@
 #include "ctx.h"
 #include "kernels_logup_freq.h"
 #include "kernels_multiset.h"
+#include "logup.h"
 #include "logup_frequencies.h"
 
 namespace starkhip {
@@ -57,24 +59,47 @@ struct DeviceFreqSteps : LogupFreqSteps {
         if (!g || q0 + g > plan.L || g > logup_freq_batch_size(n, plan.L)) return STARKHIP_ERR_BAD_SHAPE;
         hipStream_t st = c->st;
         Ctx::LogupFreqBufs& lf = c->logup_freq;
-        const size_t c0 = plan.col_off[q0], nc = plan.col_off[q0 + g] - c0;
+        const size_t nc = plan.col_off[q0 + g] - plan.col_off[q0];
         last_g = g;
         if (!ev0) HIPCHK(hipEventRecord(c->kev[0], st));
         ev0 = false;
         // the batch's descriptors: its distinct tables in order of first use, its lookups, its looked-up columns
-        std::vector<uint32_t> tabs, slot_of(g);
+        std::vector<uint32_t> tabs, slot_of(g);  // (a table is named by the first lookup that has it)
         for (size_t i = 0; i < g; i++) {
-            const uint32_t t = plan.table[q0 + i];
+            const uint32_t t = plan.table_of[q0 + i];
             const size_t s = (size_t)(std::find(tabs.begin(), tabs.end(), t) - tabs.begin());
             if (s == tabs.size()) tabs.push_back(t);
             slot_of[i] = (uint32_t)s;
         }
         const size_t S = tabs.size();
         desc.clear();
-        for (uint32_t t : tabs) desc.push_back(tr(t));
-        for (size_t i = 0; i < g; i++) desc.insert(desc.end(), {slot_of[i], in.on_device ? plan.freq[q0 + i] : (uint32_t)(K + q0 + i)});
-        for (size_t i = 0; i < g; i++)
-            for (size_t k = plan.col_off[q0 + i]; k < plan.col_off[q0 + i + 1]; k++) desc.insert(desc.end(), {tr(plan.cols[k]), (uint32_t)i, slot_of[i]});
+        if (!plan.general) {
+            for (uint32_t t : tabs) desc.push_back(tr(plan.table[t]));
+            for (size_t i = 0; i < g; i++) desc.insert(desc.end(), {slot_of[i], in.on_device ? plan.freq[q0 + i] : (uint32_t)(K + q0 + i)});
+            for (size_t i = 0; i < g; i++)
+                for (size_t k = plan.col_off[q0 + i]; k < plan.col_off[q0 + i + 1]; k++) desc.insert(desc.end(), {tr(plan.cols[k]), (uint32_t)i, slot_of[i]});
+        } else {  // the same three tables with places in the descriptor for columns, then the Columns and Filters themselves
+            desc.resize(S + 2 * g + 3 * nc);
+            auto ref = [&](uint32_t col) { return tr(col); };
+            for (size_t s = 0; s < S; s++) {
+                desc[s] = (uint32_t)desc.size();
+                logup_desc_push_column(desc, plan.prog->logups[tabs[s]].table, ref);
+            }
+            size_t e = S + 2 * g;
+            for (size_t i = 0; i < g; i++) {
+                const AirProgram::Logup& lk = plan.prog->logups[q0 + i];
+                desc[S + 2 * i] = slot_of[i];
+                desc[S + 2 * i + 1] = in.on_device ? plan.freq[q0 + i] : (uint32_t)(K + q0 + i);
+                for (size_t k = 0; k < lk.cols.size(); k++, e += 3) {
+                    desc[e] = (uint32_t)desc.size();
+                    desc[e + 1] = (uint32_t)i;
+                    desc[e + 2] = slot_of[i];
+                    logup_desc_push_column(desc, lk.cols[k], ref);
+                    logup_desc_push_filter(desc, lk.filters[k], ref);
+                }
+            }
+            if (desc.size() > plan.desc_words) return STARKHIP_ERR_BAD_SHAPE;
+        }
         const uint32_t* d_tabs = lf.desc.as<uint32_t>();
         const uint32_t *d_lks = d_tabs + S, *d_cols = d_lks + 2 * g;
         HIPCHK(hipMemcpyAsync(lf.desc.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, st));
@@ -86,10 +111,12 @@ struct DeviceFreqSteps : LogupFreqSteps {
         const LogupFreqTrace t = view();
         gl_t* keys = c->mset.keys.as<gl_t>();
         uint32_t *idx = c->mset.idx.as<uint32_t>(), *table = c->mset.table.as<uint32_t>();
-        HIPCHK(launch_logup_freq_keys(t, n, d_tabs, S, keys, idx, st));
+        if (plan.general) HIPCHK(launch_logup_freq_keys_general(t, n, d_tabs, d_tabs, S, keys, idx, st));
+        else HIPCHK(launch_logup_freq_keys(t, n, d_tabs, S, keys, idx, st));
         HIPCHK(launch_multiset_sort_batch(keys, idx, keys + S * n, idx + S * n, n, S, table, table + S * multiset_table_words(n), st));
         HIPCHK(hipEventRecord(c->kev[2], st));
-        HIPCHK(launch_logup_freq_count(t, n, d_cols, nc, g, keys, count, d_mask(), missing, c->opt_logup_count_combine != 0, st));
+        if (plan.general) HIPCHK(launch_logup_freq_count_general(t, n, d_tabs, d_cols, nc, g, keys, count, d_mask(), missing, c->opt_logup_count_combine != 0, st));
+        else HIPCHK(launch_logup_freq_count(t, n, d_cols, nc, g, keys, count, d_mask(), missing, c->opt_logup_count_combine != 0, st));
         HIPCHK(hipEventRecord(c->kev[3], st));
         HIPCHK(launch_logup_freq_write(t, n, d_lks, g, idx, count, own ? nullptr : missing, st));
         HIPCHK(hipEventRecord(c->kev[4], st));
@@ -134,10 +161,10 @@ std::vector<LookupWant> freq_work_buffers(Ctx* c, const LogupFreqPlan& plan, siz
     return {{&c->mset.keys, 2 * G * n * 8},
             {&c->mset.idx, 2 * G * n * 4},
             {&c->mset.table, G * (multiset_table_words(n) + multiset_scan_chunks(n)) * 4},
-            {&lf.desc, 3 * (plan.L + plan.cols.size()) * 4},
+            {&lf.desc, plan.desc_words * 4},
             {&lf.cols, staged ? (plan.named.size() + plan.L) * n * 8 : 0},
             {&lf.count, G * n * 4},
-            {&lf.mask, G * W * 8 + (plan.L + plan.cols.size()) * 4}};
+            {&lf.mask, G * W * 8 + (plan.L + plan.n_values()) * 4}};
 }
 
 int freq_run(Ctx* c, const LogupFreqPlan& plan, const TraceInput& in, uint64_t* words, bool own, uint32_t* per_lookup, uint32_t* per_column, uint64_t* masks,

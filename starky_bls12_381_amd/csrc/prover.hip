@@ -103,6 +103,7 @@ struct ProofShape {
     size_t nZ, perm_cols, perm_desc_words;         // permutation pairs: Z polynomials, the columns the pairs name, words of one descriptor (0 without pairs)
     size_t nA, nLZ;                                // LogUp lookups: auxiliary polynomials and, of them, the Zs (2 per lookup); perm_cols and perm_desc_words are then theirs
     size_t mid;                                    // the middle matrix's polynomials: nZ or nA (never both), 0 without either
+    bool logup_general;                            // LogUp lookups over Columns and Filters (or the general kernels forced): the form of the descriptors
     FriGeometry geo;
     ProofLayout pl;
     // STARKHIP_ERR_BAD_SHAPE for what prove() refuses: rows that are no power of two in 2 .. 2^max_log_rows(air), a config that the one
@@ -117,8 +118,8 @@ struct ProofShape {
         s->n = n_rows; s->N = s->n << s->r; s->C = P.n_cols; s->Q = (size_t)s->factor * 2; s->size = s->n << s->qdb;
         s->ncap = (size_t)1 << s->cap_h; s->L = s->geo.arities.size();
         s->nZ = P.perm_zs(); s->perm_cols = s->nZ ? perm_columns(P).size() : 0; s->perm_desc_words = s->nZ ? perm_descriptor(P, false).size() : 0;
-        s->nA = P.logup_polys(); s->nLZ = 2 * P.logups.size(); s->mid = s->nZ + s->nA;
-        if (s->nA) { s->perm_cols = logup_columns(P).size(); s->perm_desc_words = logup_descriptor(P, false).size(); }
+        s->nA = P.logup_polys(); s->nLZ = 2 * P.logups.size(); s->mid = s->nZ + s->nA; s->logup_general = false;
+        if (s->nA) { s->perm_cols = logup_columns(P).size(); s->logup_general = logup_use_general(P); s->perm_desc_words = logup_descriptor(P, false, s->logup_general).size(); }
         s->pl = ProofLayout::make(P, cfg, s->geo, log_n);
         return STARKHIP_OK;
     }
@@ -556,12 +557,12 @@ int ProveCall::logup() {
     fs.start();
     for (gl_t& x : logup_chal) x = ch.get();  // L1
     fs.stop();
-    perm_desc = logup_descriptor(P, true);  // by copy slot, by trace column, the Zs' polynomial indices
-    for (const std::vector<uint32_t>& more : {logup_descriptor(P, false), logup_z_polys(P)}) perm_desc.insert(perm_desc.end(), more.begin(), more.end());
+    perm_desc = logup_descriptor(P, true, s.logup_general);  // by copy slot, by trace column, the Zs' polynomial indices
+    for (const std::vector<uint32_t>& more : {logup_descriptor(P, false, s.logup_general), logup_z_polys(P)}) perm_desc.insert(perm_desc.end(), more.begin(), more.end());
     Ctx::PermBufs& pb = c->perm;
     HIPCHK(hipMemcpyAsync(pb.desc.p, perm_desc.data(), perm_desc.size() * 4, hipMemcpyHostToDevice, st));
     gl_t* const d_results = pb.scan.as<gl_t>() + logup_scratch_words(n, nzs);
-    HIPCHK(launch_logup_polys(pb.desc.as<uint32_t>(), pb.desc.as<uint32_t>() + 2 * s.perm_desc_words, pb.cols.as<gl_t>(), n, logup_chal[0], logup_chal[1], n, nzs,
+    HIPCHK(launch_logup_polys(pb.desc.as<uint32_t>(), s.logup_general, pb.desc.as<uint32_t>() + 2 * s.perm_desc_words, pb.cols.as<gl_t>(), n, logup_chal[0], logup_chal[1], n, nzs,
                               pb.zvals.as<gl_t>(), pb.scan.as<gl_t>(), d_results, st));
     std::vector<gl_t> results(logup_result_words(nzs));
     HIPCHK(read_back(c, results.data(), d_results, results.size() * 8, st));
@@ -606,7 +607,7 @@ int ProveCall::quotient() {
                                         s.log_n, s.r, s.qdb, st));
         if (s.nA) {  // L4: the LogUp constraints likewise (kernels_logup.hip)
             const uint64_t nL = air.prog.logup_constraints();
-            HIPCHK(launch_logup_quotient(c->perm.desc.as<uint32_t>() + s.perm_desc_words, c->lde.as<gl_t>(), c->perm.zlde.as<gl_t>(), logup_chal[0], logup_chal[1],
+            HIPCHK(launch_logup_quotient(c->perm.desc.as<uint32_t>() + s.perm_desc_words, s.logup_general, c->lde.as<gl_t>(), c->perm.zlde.as<gl_t>(), logup_chal[0], logup_chal[1],
                                          c->tab->qtab.as<gl_t>(), c->qvals.as<gl_t>(), alphas[0], alphas[1], gl_pow(alphas[0], nL), gl_pow(alphas[1], nL), s.log_n, s.r,
                                          s.qdb, st));
         }

@@ -154,7 +154,7 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     std::vector<gl2_t> acc(cfg.num_challenges);
     air_eval_folded<ExtOps>(P, op_local, op_next, pis, masks, alphas.data(), (int)cfg.num_challenges, acc.data());
     if (nZ) perm_eval_folded<ExtOps>(P, op_local, opened(1, 0), opened(1, 1), perm_chal.data(), masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // P4
-    if (pl.nA) logup_eval_folded<ExtOps>(P, op_local, opened(1, 0), opened(1, 1), logup_chal, masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // L4
+    if (pl.nA) logup_eval_folded<ExtOps>(P, op_local, op_next, opened(1, 0), opened(1, 1), logup_chal, masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // L4
     for (unsigned i = 0; i < cfg.num_challenges; i++) {
         gl2_t s = gl2_zero();
         for (unsigned k = factor; k-- > 0;) s = gl2_add(gl2_mul(s, zeta_n), op_q[i * factor + k]);
