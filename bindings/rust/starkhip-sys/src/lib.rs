@@ -106,6 +106,9 @@ pub struct starkhip_proof_layout_t {
     // LogUp lookups: nA (header word 14; 0 for a proof without them).  With nA > 0 the five positions above are those of the
     // auxiliary polynomials, which take the Zs' place in the blob, and n_permutation_zs is 0
     pub n_logup_polys: usize,
+    // cross-table lookups: nC (header word 15; 0 unless the blob is a table proof of a system) and where its nC / 2 sums are
+    pub n_ctl_polys: usize,
+    pub off_ctl_sums: usize,
 }
 
 /// `starkhip_pool_config_t` (0 = the library's default).
@@ -315,6 +318,32 @@ extern "C" {
     pub fn starkhip_air_eval_frame_logup(air: c_int, local: *const u64, next: *const u64, public_inputs: *const u64, masks: *const u64,
                                          alphas: *const u64, n_alpha: c_int, aux: *const u64, aux_next: *const u64, challenges: *const u64,
                                          acc_out: *mut u64) -> c_int;
+    // Cross-table lookups: several registered AIRs proved and verified as one system (include/starkhip.h has the blobs; as text: no
+    // toolchain has compiled these).  A system id is a plain c_int; cfgs points to one StarkConfig per table.
+    pub fn starkhip_system_check(blob: *const u64, words: usize, why: *mut c_char, why_len: usize) -> c_int;
+    pub fn starkhip_system_register(blob: *const u64, words: usize, id_out: *mut c_int) -> c_int;
+    pub fn starkhip_system_tables(sys: c_int) -> c_int;
+    pub fn starkhip_system_ctls(sys: c_int) -> c_int;
+    pub fn starkhip_system_table_air(sys: c_int, table: usize) -> c_int;
+    pub fn starkhip_system_table_endpoints(sys: c_int, table: usize) -> c_int;
+    pub fn starkhip_system_create(device: c_int, sys: c_int, handle: *mut *mut c_void) -> c_int;
+    pub fn starkhip_system_destroy(handle: *mut c_void);
+    pub fn starkhip_system_set_option(handle: *mut c_void, name: *const c_char, value: c_long) -> c_int;
+    pub fn starkhip_system_last_timings(handle: *mut c_void, table: usize, out_ms: *mut f32) -> c_int;
+    pub fn starkhip_system_prove(handle: *mut c_void, cfgs: *const StarkConfig, traces: *const *const u64, n_rows: *const usize,
+                                 layouts: *const c_int, on_device: *const c_int, public_inputs: *const *const u64, n_pis: *const usize,
+                                 pow_witness: u64, proof: *mut *mut u64, proof_words: *mut usize, failing_ctl: *mut c_int) -> c_int;
+    pub fn starkhip_system_verify(sys: c_int, cfgs: *const StarkConfig, proof: *const u64, proof_words: usize) -> c_int;
+    pub fn starkhip_system_proof_layout(proof: *const u64, proof_words: usize, n_tables: *mut usize, offsets: *mut usize, cap: usize) -> c_int;
+    pub fn starkhip_ctl_span_rows() -> c_uint;
+    pub fn starkhip_ctl_polys(ctx: *mut c_void, sys: c_int, table: usize, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                              on_device: c_int, challenges: *const u64, polys_out: *mut u64, sums_out: *mut u64,
+                              zero_denominators_out: *mut u64) -> c_int;
+    pub fn starkhip_ctl_polys_replay(sys: c_int, table: usize, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
+                                     challenges: *const u64, polys_out: *mut u64, sums_out: *mut u64, zero_denominators_out: *mut u64) -> c_int;
+    pub fn starkhip_system_eval_frame_ctl(sys: c_int, table: usize, local: *const u64, next: *const u64, public_inputs: *const u64,
+                                          masks: *const u64, alphas: *const u64, n_alpha: c_int, aux: *const u64, aux_next: *const u64,
+                                          logup_challenges: *const u64, ctl_challenges: *const u64, sums: *const u64, acc_out: *mut u64) -> c_int;
     pub fn starkhip_check_trace(ctx: *mut c_void, air: c_int, trace: *const u64, n_rows: usize, n_cols: usize, layout: c_int,
                                 on_device: c_int, public_inputs: *const u64, violations: *mut u64, first: *mut u64) -> c_int;
     // The full report: per_constraint [starkhip_air_num_constraints(air)] or null, row_mask [(n_rows + 63) / 64] or null (bit r & 63 of

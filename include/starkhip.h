@@ -1095,7 +1095,8 @@ const char* starkhip_error_string(int code);
  *   [0..16)  header: magic "SSPRF001", C, Q, degree_bits, rate_bits, cap_height, L (FRI layers),
  *            num_query_rounds, final_poly_len, n_pis, arity_bits, num_challenges, hasher (STARKHIP_HASHER_*: 0 for Poseidon),
  *            nZ (permutation Z polynomials: 0 for an AIR without permutation pairs, at most 128),
- *            nA (LogUp auxiliary polynomials: 0 for an AIR without LogUp lookups, at most 1024; never beside nZ), 0
+ *            nA (LogUp auxiliary polynomials: 0 for an AIR without LogUp lookups, at most 1024; never beside nZ),
+ *            nC (cross-table-lookup polynomials of a table proof of a system: 4 per endpoint, behind the nA in the same matrix; 0 otherwise)
  *   trace_cap[2^cap_h][4]; [nZ > 0: permutation_zs_cap[2^cap_h][4];] quotient_polys_cap[2^cap_h][4]
  *   openings.local_values[C][2]; openings.next_values[C][2];
  *   [nZ > 0: openings.permutation_zs[nZ][2]; openings.permutation_zs_next[nZ][2];] openings.quotient_polys[Q][2]
@@ -1107,6 +1108,8 @@ const char* starkhip_error_string(int code);
  *   final_poly[final_poly_len][2]; pow_witness; public_inputs[n_pis]
  * A proof with nA > 0 has the same shape with its auxiliary polynomials in the Zs' place: auxiliary_polys_cap, openings.auxiliary_polys[nA][2]
  * and openings.auxiliary_polys_next[nA][2], the auxiliary leaf[nA] and its siblings.  A proof with nZ = nA = 0 has exactly the bytes it always had.
+ * A table proof of a system (nC > 0) has nA + nC polynomials in that matrix, LogUp || CTL, and after public_inputs one more section:
+ *   ctl_sums[nC / 2], challenge-major and then in the table's endpoint order.
  */
 #define STARKHIP_PROOF_MAGIC 0x3130304652505353ULL
 
@@ -1126,12 +1129,84 @@ typedef struct {
     /* LogUp lookups: nA (0 for a proof without them).  With nA > 0 the five positions above are those of the auxiliary polynomials,
      * which take the Zs' place in the blob, and n_permutation_zs is 0 */
     size_t n_logup_polys;
+    /* cross-table lookups: nC (0 unless the blob is a table proof of a system) and where its nC / 2 sums are.  With nC > 0 the middle
+     * matrix holds n_logup_polys + n_ctl_polys polynomials */
+    size_t n_ctl_polys, off_ctl_sums;
 } starkhip_proof_layout_t;
 /* STARKHIP_ERR_BAD_SHAPE when the blob's header is not a proof header or disagrees with proof_words */
 int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_proof_layout_t* out);
 /* the hasher id in the proof's header (STARKHIP_HASHER_*), or STARKHIP_ERR_BAD_SHAPE for a blob that is not a proof or names an unknown
  * hasher.  The verify entries accept either hasher; a caller that insists on one asks here. */
 int starkhip_proof_hasher(const uint64_t* proof, size_t proof_words);
+
+/* ---- Cross-table lookups: several registered AIRs proved and verified as one system (COMPAT.md 2d, C1 - C8).
+ * A system is an ordered list of T >= 2 tables (registered AIRs without permutation pairs, degree >= 2) and a list of CTLs.  CTL k has
+ * a width w, one looked endpoint and L >= 1 looking endpoints; an endpoint is (table, w Columns, one Filter) in the word encoding of
+ * the general LogUp section.  For both challenge pairs (beta, gamma) the proof shows  sum over looking of S = S of looked,  where
+ * S = sum over rows of filter / (gamma + sum_j beta^j column_j).  The filter's value is the multiplicity.
+ * System blob (uint64 words): STARKHIP_SYSTEM_MAGIC, T, T table ids, K, then per CTL: w, L, and its 1 + L endpoints, the looked one
+ * first, each: table, w (again), w COLUMNs, FILTER.
+ * System proof blob: STARKHIP_SYSTEM_PROOF_MAGIC, T, T + 1 word offsets (table t's proof is [off[t], off[t + 1]); off[T] is the length),
+ * then the T table proofs in table order. */
+#define STARKHIP_SYSTEM_MAGIC 0x31304C5443535953ULL       /* "SYSCTL01" */
+#define STARKHIP_SYSTEM_PROOF_MAGIC 0x31304650535953ULL   /* "SYSPF01" */
+#define STARKHIP_SYSTEM_CAPACITY 1024
+typedef int starkhip_system_t;
+/* STARKHIP_OK, or STARKHIP_ERR_BAD_AIR with the reason in why (may be NULL): a table id that is no registered AIR, a table with
+ * permutation pairs or of degree 1, an endpoint's table out of range, a width mismatch between a CTL's endpoints, a column outside
+ * its table's n_cols, a Column or Filter beyond the LogUp term limits (16 terms, 4 products, 4 sums), nA + nC above
+ * STARKHIP_AIR_MAX_LOGUP_POLYS for some table, a blob that ends early or late, and a count beyond the limits below */
+#define STARKHIP_SYSTEM_MAX_TABLES 64u   /* T: tables of a system (at least 2) */
+#define STARKHIP_SYSTEM_MAX_CTLS 256u    /* K: CTLs of a system */
+#define STARKHIP_SYSTEM_MAX_LOOKING 64u  /* L: looking endpoints of one CTL (at least 1) */
+#define STARKHIP_CTL_MAX_WIDTH 64u       /* w: columns of an endpoint (at least 1) */
+int starkhip_system_check(const uint64_t* blob, size_t words, char* why, size_t why_len);
+/* registers a system that passes the check; the same blob again returns its first id */
+int starkhip_system_register(const uint64_t* blob, size_t words, starkhip_system_t* id_out);
+/* getters: T, K, table t's AIR, table t's endpoints E_t (its proof carries nC = 4 E_t polynomials and 2 E_t sums); a negative code otherwise */
+int starkhip_system_tables(starkhip_system_t sys);
+int starkhip_system_ctls(starkhip_system_t sys);
+int starkhip_system_table_air(starkhip_system_t sys, size_t table);
+int starkhip_system_table_endpoints(starkhip_system_t sys, size_t table);
+/* A system prover: one context per table on one device.  starkhip_system_set_option sets a context option ("hasher", ...) on all of them. */
+int starkhip_system_create(int device, starkhip_system_t sys, void** handle);
+void starkhip_system_destroy(void* handle);
+int starkhip_system_set_option(void* handle, const char* name, long value);
+/* starkhip_last_timings of table `table`'s context: the phases of that table's last proof (its two halves).  The quotient phase starts
+ * where the table's CTL polynomials are enqueued, so they and the auxiliary commitment are timed with it; what the table's stream idles
+ * after its trace commitment, while the other tables' first halves run, is counted in trace_merkle, and the host's work between the
+ * CTL polynomials and the second half (the other tables' polynomials, the balances) in quotient. */
+int starkhip_system_last_timings(void* handle, size_t table, float out_ms[STARKHIP_N_PHASES]);
+/* One proof of the whole system.  Per table t: cfgs[t] (the configs may differ in rate_bits only), traces[t] with n_rows[t] rows in
+ * layouts[t] (0 row-major, 1 column-major) in host or (on_device[t]) device memory, public_inputs[t] with n_pis[t] words.  Every
+ * table's trace is committed once; the system transcript draws the CTL challenges from all the trace caps.  If some CTL's sums do not
+ * balance, or a denominator was zero, nothing auxiliary is committed: STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE with the first such CTL in
+ * *failing_ctl (may be NULL; -1 otherwise; zero denominators are counted per endpoint, so the CTL named is the first that does not
+ * balance or has one), and the handle stays usable.  *proof is freed with starkhip_free. */
+int starkhip_system_prove(void* handle, const starkhip_config_t* cfgs, const uint64_t* const* traces, const size_t* n_rows, const int* layouts,
+                          const int* on_device, const uint64_t* const* public_inputs, const size_t* n_pis, uint64_t pow_witness, uint64_t** proof,
+                          size_t* proof_words, int* failing_ctl);
+/* the CPU verifier of a system proof: the system transcript replayed from the table proofs' trace caps, every table proof from the
+ * copied state (the four CTL constraints at zeta with the sums taken from the proof), every CTL's sum equation under both challenges.
+ * starkhip_verify and starkhip_verify_batch, given a table proof with endpoints alone, answer STARKHIP_ERR_BAD_SHAPE. */
+int starkhip_system_verify(starkhip_system_t sys, const starkhip_config_t* cfgs, const uint64_t* proof, size_t proof_words);
+/* the T + 1 offsets of a system proof blob into offsets[cap] (cap >= T + 1) and T into *n_tables; STARKHIP_ERR_BAD_SHAPE otherwise */
+int starkhip_system_proof_layout(const uint64_t* proof, size_t proof_words, size_t* n_tables, size_t* offsets, size_t cap);
+/* the rows one workgroup of the running sums' scan takes (tests put their row counts on either side of its multiples) */
+unsigned starkhip_ctl_span_rows(void);
+/* tests: the CTL polynomials [4 E][n_rows] (per (challenge, endpoint) h then Z), the sums [2 E] and the count of zero denominators of
+ * table `table` on one trace under challenges {beta_0, gamma_0, beta_1, gamma_1}: through the kernels the system prover uses, and from
+ * plain loops on the host */
+int starkhip_ctl_polys(void* ctx, starkhip_system_t sys, size_t table, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout, int on_device,
+                       const uint64_t* challenges, uint64_t* polys_out, uint64_t* sums_out, uint64_t* zero_denominators_out);
+int starkhip_ctl_polys_replay(starkhip_system_t sys, size_t table, const uint64_t* trace, size_t n_rows, size_t n_cols, int layout,
+                              const uint64_t* challenges, uint64_t* polys_out, uint64_t* sums_out, uint64_t* zero_denominators_out);
+/* tests: starkhip_air_eval_frame_logup of the table's AIR continued over the table's 8 E CTL constraints.  aux / aux_next: the
+ * nA + nC middle-matrix polynomials at the point and the next row's (2 words each), logup_challenges {chi_0, chi_1} (read only with
+ * nA > 0), ctl_challenges[4], sums [2 E] */
+int starkhip_system_eval_frame_ctl(starkhip_system_t sys, size_t table, const uint64_t* local, const uint64_t* next, const uint64_t* public_inputs,
+                                   const uint64_t masks[8], const uint64_t* alphas, int n_alpha, const uint64_t* aux, const uint64_t* aux_next,
+                                   const uint64_t* logup_challenges, const uint64_t* ctl_challenges, const uint64_t* sums, uint64_t* acc_out);
 
 #ifdef __cplusplus
 }

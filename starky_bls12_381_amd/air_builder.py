@@ -410,3 +410,39 @@ class AirBuilder:
         for w in self._cur:
             self.code += w
         self._cur, self._open = [], False
+
+
+SYSTEM_MAGIC = int.from_bytes(b"SYSCTL01", "little")
+
+
+class SystemBuilder:
+    """A system of tables tied by cross-table lookups (starky's `CrossTableLookup`, COMPAT.md §2d): `tables` are the ids of registered
+    AIRs (what register_air returned for AirBuilder results), each proved on a trace of its own; ctl() declares that the rows the looking
+    endpoints send are the rows the looked endpoint receives.  finish() returns the blob register_system takes.
+
+        sb = SystemBuilder([cpu_air, range_air])
+        sb.ctl(looked=(1, [0], Filter(sums=[Column.single(1)])), looking=[(0, [3], Filter(sums=[Column.single(4)]))])
+        system = register_system(sb.finish())
+    """
+
+    def __init__(self, tables):
+        self.tables = [int(t) for t in tables]
+        self.ctls = []
+
+    def ctl(self, looked, looking):
+        """looked, and each of looking: (table index, columns, filter) -- `columns` a list of Columns (a trace column's number stands for
+        the plain one), all of one width; `filter` a Filter, or None for the filter that is 1.  The filter's value is the multiplicity:
+        0 / 1 selectors on both sides give a multiset equality, a multiplicity column as the looked side's filter a lookup."""
+        eps = [(int(t), [_column(c) for c in cols], f if f is not None else Filter()) for t, cols, f in [looked] + list(looking)]
+        self.ctls.append(eps)
+
+    def finish(self):
+        words = [SYSTEM_MAGIC, len(self.tables)] + self.tables + [len(self.ctls)]
+        for eps in self.ctls:
+            words += [len(eps[0][1]), len(eps) - 1]
+            for t, cols, f in eps:
+                words += [t, len(cols)]
+                for c in cols:
+                    words += c.words()
+                words += f.words()
+        return np.array(words, dtype=np.uint64)

@@ -596,7 +596,7 @@ class ProofLayout(C.Structure):
         "off_public_inputs", "total_words", "q_trace_leaf", "q_trace_siblings", "q_quotient_leaf", "q_quotient_siblings",
         "initial_sibling_count")] + [(n, C.c_size_t * 16) for n in ("q_step_evals", "q_step_siblings", "step_sibling_count")] + \
         [(n, C.c_size_t) for n in ("n_permutation_zs", "off_permutation_zs_cap", "off_permutation_zs", "off_permutation_zs_next",
-                                   "q_permutation_zs_leaf", "q_permutation_zs_siblings", "n_logup_polys")]
+                                   "q_permutation_zs_leaf", "q_permutation_zs_siblings", "n_logup_polys", "n_ctl_polys", "off_ctl_sums")]
 
 
 lib.starkhip_proof_layout.argtypes = [_u64p, C.c_size_t, C.POINTER(ProofLayout)]
@@ -2244,3 +2244,216 @@ def free_cell_classes_replay(air, trace, public_inputs, layout=0, delta=DEFAULT_
 def trace_rows_to_poly_values(trace_rows):
     """starky::util::trace_rows_to_poly_values: row-major [n][C] -> column-major [C][n]."""
     return np.ascontiguousarray(np.asarray(trace_rows, dtype=np.uint64).T)
+
+
+# ---- cross-table lookups: several registered AIRs proved and verified as one system (COMPAT.md §2d; air_builder.SystemBuilder makes the blob)
+SYSTEM_PROOF_MAGIC = 0x31304650535953  # "SYSPF01"
+SYSTEM_MAX_TABLES = 64  # STARKHIP_SYSTEM_MAX_TABLES
+lib.starkhip_ctl_span_rows.restype = C.c_uint
+lib.starkhip_ctl_span_rows.argtypes = []
+CTL_SPAN_ROWS = int(lib.starkhip_ctl_span_rows())  # the rows one workgroup of the running sums' scan takes: the scan's own constant
+_szp = C.POINTER(C.c_size_t)
+_intp = C.POINTER(C.c_int)
+lib.starkhip_system_check.argtypes = [_u64p, C.c_size_t, C.c_char_p, C.c_size_t]
+lib.starkhip_system_register.argtypes = [_u64p, C.c_size_t, _intp]
+lib.starkhip_system_tables.argtypes = [C.c_int]
+lib.starkhip_system_ctls.argtypes = [C.c_int]
+lib.starkhip_system_table_air.argtypes = [C.c_int, C.c_size_t]
+lib.starkhip_system_table_endpoints.argtypes = [C.c_int, C.c_size_t]
+lib.starkhip_system_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+lib.starkhip_system_destroy.argtypes = [C.c_void_p]
+lib.starkhip_system_destroy.restype = None
+lib.starkhip_system_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
+lib.starkhip_system_last_timings.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_float)]
+lib.starkhip_system_prove.argtypes = [C.c_void_p, C.POINTER(StarkConfig), C.POINTER(C.c_void_p), _szp, _intp, _intp, C.POINTER(_u64p), _szp, C.c_uint64,
+                                      C.POINTER(_u64p), _szp, _intp]
+lib.starkhip_system_verify.argtypes = [C.c_int, C.POINTER(StarkConfig), _u64p, C.c_size_t]
+lib.starkhip_system_proof_layout.argtypes = [_u64p, C.c_size_t, _szp, _szp, C.c_size_t]
+lib.starkhip_ctl_polys.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, _u64p, _u64p, _u64p, _u64p]
+lib.starkhip_ctl_polys_replay.argtypes = [C.c_int, C.c_size_t, _u64p, C.c_size_t, C.c_size_t, C.c_int, _u64p, _u64p, _u64p, _u64p]
+lib.starkhip_system_eval_frame_ctl.argtypes = [C.c_int, C.c_size_t, _u64p, _u64p, _u64p, _u64p, _u64p, C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]
+
+
+class SystemRefused(StarkhipError):
+    """SystemProver.prove: some CTL's sums do not balance, or a denominator was zero (ERR_QUOTIENT_NOT_DIVISIBLE); `.ctl` is the CTL."""
+
+    def __init__(self, ctl):
+        super().__init__(ERR_QUOTIENT_NOT_DIVISIBLE)
+        self.ctl = ctl
+
+
+def system_check(blob):
+    """The validator starkhip_system_register runs: None for a system it accepts, else the reason it refuses it."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint64)
+    why = C.create_string_buffer(512)
+    rc = lib.starkhip_system_check(_p64(blob), blob.size, why, len(why))
+    if rc == 0:
+        return None
+    if rc != ERR_BAD_AIR:
+        raise StarkhipError(rc)
+    return why.value.decode()
+
+
+def register_system(blob):
+    """Register a system blob (air_builder.SystemBuilder.finish()) and return its id; the same blob again returns the same id.  A system
+    the validator refuses raises StarkhipError(ERR_BAD_AIR)."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint64)
+    out = C.c_int()
+    _chk(lib.starkhip_system_register(_p64(blob), blob.size, C.byref(out)))
+    return out.value
+
+
+def _nonneg(r):
+    if r < 0:
+        raise StarkhipError(r)
+    return r
+
+
+def system_tables(system):
+    """the AIR ids of the system's tables, in table order"""
+    return [_nonneg(lib.starkhip_system_table_air(system, t)) for t in range(_nonneg(lib.starkhip_system_tables(system)))]
+
+
+def system_ctls(system):
+    return _nonneg(lib.starkhip_system_ctls(system))
+
+
+def system_table_endpoints(system, table):
+    """E_t: the CTL endpoints table `table` carries; its proof has nC = 4 E_t polynomials and 2 E_t sums"""
+    return _nonneg(lib.starkhip_system_table_endpoints(system, table))
+
+
+def system_proof_tables(proof):
+    """The table proofs of a system proof blob, in table order (views of `proof`); StarkhipError(ERR_BAD_SHAPE) for anything else."""
+    p = np.ascontiguousarray(proof, dtype=np.uint64)
+    n = C.c_size_t()
+    off = (C.c_size_t * (SYSTEM_MAX_TABLES + 1))()
+    _chk(lib.starkhip_system_proof_layout(_p64(p), p.size, C.byref(n), off, SYSTEM_MAX_TABLES + 1))
+    return [p[off[t]:off[t + 1]] for t in range(n.value)]
+
+
+def system_proof_join(table_proofs):
+    """a system proof blob from table proofs (tests: tampered copies)"""
+    T = len(table_proofs)
+    offs, at = [], 3 + T
+    for p in table_proofs:
+        offs.append(at)
+        at += len(p)
+    return np.concatenate([np.array([SYSTEM_PROOF_MAGIC, T] + offs + [at], dtype=np.uint64)] + [np.asarray(p, dtype=np.uint64) for p in table_proofs])
+
+
+def verify_system_proof(system, configs, proof):
+    """starkhip_system_verify: the system transcript replayed from the table proofs' trace caps, every table proof from the copied state,
+    every CTL's sum equation; raises StarkhipError on rejection.  configs: one StarkConfig per table (they may differ in rate_bits only)."""
+    p = np.ascontiguousarray(proof, dtype=np.uint64)
+    cfgs = (StarkConfig * len(configs))(*configs)
+    _chk(lib.starkhip_system_verify(system, cfgs, _p64(p), p.size))
+
+
+def _ctl_args(system, table, n_rows, challenges):
+    challenges = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+    if challenges.size != 4:
+        raise StarkhipError(ERR_BAD_SHAPE)
+    E = system_table_endpoints(system, table)
+    return challenges, np.zeros((4 * E, n_rows), dtype=np.uint64), np.zeros(2 * E, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+
+
+def ctl_polys_replay(system, table, trace, challenges, layout=0):
+    """The CTL polynomials of table `table` on one trace under challenges [beta_0, gamma_0, beta_1, gamma_1], from plain loops on the
+    host (starkhip_ctl_polys_replay): (polys [4 E, n] -- per (challenge, endpoint) h then Z --, sums [2 E], zero denominators)."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    challenges, polys, sums, zeros = _ctl_args(system, table, n_rows, challenges)
+    _chk(lib.starkhip_ctl_polys_replay(system, table, _p64(trace), n_rows, n_cols, layout, _p64(challenges), _p64(polys), _p64(sums), _p64(zeros)))
+    return polys, sums, int(zeros[0])
+
+
+def ctl_polys(prover, system, table, trace, challenges, layout=0):
+    """ctl_polys_replay's result from the Prover's device, through the kernels the system prover uses (starkhip_ctl_polys)."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    if trace.ndim != 2 or layout not in (0, 1):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    n_rows, n_cols = trace.shape if layout == 0 else trace.shape[::-1]
+    challenges, polys, sums, zeros = _ctl_args(system, table, n_rows, challenges)
+    _chk(lib.starkhip_ctl_polys(prover._ctx, system, table, trace.ctypes.data_as(C.c_void_p), n_rows, n_cols, layout, 0, _p64(challenges), _p64(polys),
+                                _p64(sums), _p64(zeros)))
+    return polys, sums, int(zeros[0])
+
+
+def system_eval_frame_ctl(system, table, local, nxt, pis, masks, alphas, aux, aux_next, logup_challenges, ctl_challenges, sums):
+    """starkhip_system_eval_frame_ctl: the alpha fold of the table's AIR constraints, its LogUp constraints and its 8 E CTL constraints
+    on one extension frame.  local / nxt [C, 2], masks [4, 2], alphas [n, 2], aux / aux_next [nA + nC, 2]; returns [n, 2]."""
+    arr = lambda a: np.ascontiguousarray(a, dtype=np.uint64)  # noqa: E731
+    local, nxt, pis, masks, alphas, aux, aux_next = (arr(a) for a in (local, nxt, pis, masks, alphas, aux, aux_next))
+    lch, cch, sums = arr(logup_challenges), arr(ctl_challenges), arr(sums)
+    air = _nonneg(lib.starkhip_system_table_air(system, table))
+    want = air_logup_polys(air) + 4 * system_table_endpoints(system, table)
+    if local.shape != (air_columns(air), 2) or nxt.shape != local.shape or masks.shape != (4, 2) or alphas.ndim != 2 or alphas.shape[1] != 2 or \
+            aux.shape != (want, 2) or aux_next.shape != aux.shape or lch.size != 2 or cch.size != 4 or sums.size * 2 != 4 * system_table_endpoints(system, table):
+        raise StarkhipError(ERR_BAD_SHAPE)
+    acc = np.zeros_like(alphas)
+    _chk(lib.starkhip_system_eval_frame_ctl(system, table, _p64(local), _p64(nxt), _p64(pis), _p64(masks), _p64(alphas), alphas.shape[0], _p64(aux),
+                                            _p64(aux_next), _p64(lch), _p64(cch), _p64(sums), _p64(acc)))
+    return acc
+
+
+class SystemProver:
+    """A system prover (starkhip_system_create): one context per table on one device.  prove() commits every table's trace once, draws
+    the CTL challenges from all the trace caps, checks every CTL's balance before anything auxiliary is committed and returns one blob."""
+
+    def __init__(self, system, device=0):
+        self.system = system
+        self._h = C.c_void_p()
+        _chk(lib.starkhip_system_create(device, system, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib.starkhip_system_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_option(self, name, value):
+        """a context option ("hasher", ...) on every table's context"""
+        _chk(lib.starkhip_system_set_option(self._h, name.encode(), int(value)))
+
+    def last_timings(self, table):
+        """{phase: ms} of table `table`'s last proof (starkhip_system_last_timings)"""
+        ms = (C.c_float * N_PHASES)()
+        _chk(lib.starkhip_system_last_timings(self._h, table, ms))
+        return dict(zip(PHASE_NAMES, [float(x) for x in ms]))
+
+    def prove(self, configs, traces, public_inputs, pow_witness=POW_SEARCH, layouts=None, device_ptrs=None):
+        """configs, traces, public_inputs: one per table.  traces[t]: numpy uint64, row-major [n, C] (layouts[t] = 0, the default) or
+        column-major [C, n] (1); with device_ptrs[t] = (address, n_rows) the table's trace is read from this device's memory instead.
+        Raises SystemRefused (naming the CTL) when a CTL does not balance."""
+        T = len(configs)
+        layouts = list(layouts) if layouts is not None else [0] * T
+        keep, ptrs, rows, on_dev = [], [], [], []
+        for t in range(T):
+            if device_ptrs is not None and device_ptrs[t] is not None:
+                ptrs.append(C.c_void_p(device_ptrs[t][0]))
+                rows.append(int(device_ptrs[t][1]))
+                on_dev.append(1)
+                continue
+            tr = np.ascontiguousarray(traces[t], dtype=np.uint64)
+            if tr.ndim != 2 or layouts[t] not in (0, 1):
+                raise StarkhipError(ERR_BAD_SHAPE)
+            keep.append(tr)
+            ptrs.append(tr.ctypes.data_as(C.c_void_p))
+            rows.append(tr.shape[0] if layouts[t] == 0 else tr.shape[1])
+            on_dev.append(0)
+        pis = [np.ascontiguousarray(p, dtype=np.uint64) for p in public_inputs]
+        out, words, bad = _u64p(), C.c_size_t(), C.c_int(-1)
+        rc = lib.starkhip_system_prove(self._h, (StarkConfig * T)(*configs), (C.c_void_p * T)(*ptrs), (C.c_size_t * T)(*rows), (C.c_int * T)(*layouts),
+                                       (C.c_int * T)(*on_dev), (_u64p * T)(*[_p64(p) for p in pis]), (C.c_size_t * T)(*[p.size for p in pis]), pow_witness,
+                                       C.byref(out), C.byref(words), C.byref(bad))
+        if rc == ERR_QUOTIENT_NOT_DIVISIBLE and bad.value >= 0:
+            raise SystemRefused(bad.value)
+        return _take_blob(rc, out, words)

@@ -10,7 +10,103 @@ bool refuse(std::string* why, const std::string& msg) {
     if (why) *why = msg;
     return false;
 }
+// one COLUMN of the general LogUp section (air_ir.h) at sec[*at], of a program of n_cols columns; *at moves past it
+bool read_column(const uint64_t* sec, uint64_t sec_words, uint64_t* at_io, uint64_t n_cols, AirProgram::Column* c, std::string* msg) {
+    uint64_t at = *at_io;
+    if (sec_words < at || sec_words - at < 2) return *msg = "runs past the blob", false;
+    const uint64_t nl = sec[at] & 0xFFFFFFFFu, nn = sec[at] >> 32, constant = sec[at + 1];
+    at += 2;
+    if (nl + nn > AIR_LOGUP_MAX_TERMS) return *msg = "Column of " + std::to_string(nl + nn) + " terms (at most " + std::to_string(AIR_LOGUP_MAX_TERMS) + ")", false;
+    if (constant >= GL_P) return *msg = "Column constant is not canonical", false;
+    if ((sec_words - at) / 2 < nl + nn) return *msg = "Column terms run past the blob", false;
+    c->n_local = (uint32_t)nl;
+    c->constant = constant;
+    for (uint64_t k = 0; k < nl + nn; k++, at += 2) {
+        if (sec[at] >= n_cols) return *msg = "column " + std::to_string(sec[at]) + " out of range", false;
+        if (sec[at + 1] == 0) return *msg = "Column coefficient is zero", false;
+        if (sec[at + 1] >= GL_P) return *msg = "Column coefficient is not canonical", false;
+        c->terms.push_back({(uint32_t)sec[at], sec[at + 1]});
+    }
+    *at_io = at;
+    return true;
+}
 }  // namespace
+
+// A system blob (ctl.h): SYSTEM_MAGIC, T, the T table ids, K, then per CTL: width, L, and its 1 + L endpoints, the looked one first:
+//   table, width (again), width COLUMNs, FILTER      (COLUMN and FILTER as in the general LogUp section, air_ir.h)
+bool system_parse_checked(const uint64_t* blob, size_t words, const std::function<const AirProgram*(int)>& air_of, SystemProgram* out, std::string* why) {
+    if (!blob || words < 3) return refuse(why, "system blob shorter than its header");
+    if (blob[0] != SYSTEM_MAGIC) return refuse(why, "bad magic (not a SYSCTL01 system)");
+    const uint64_t T = blob[1], W = words;
+    if (T < 2 || T > SYSTEM_MAX_TABLES) return refuse(why, "a system of " + std::to_string(T) + " tables (2.." + std::to_string(SYSTEM_MAX_TABLES) + ")");
+    if (W < 3 + T) return refuse(why, "table ids run past the blob");
+    SystemProgram S;
+    std::vector<const AirProgram*> progs;
+    for (uint64_t t = 0; t < T; t++) {
+        const std::string att = "table " + std::to_string(t) + ": ";
+        const AirProgram* P = blob[2 + t] <= 0x7FFFFFFFu ? air_of((int)blob[2 + t]) : nullptr;
+        if (!P) return refuse(why, att + "table id " + std::to_string(blob[2 + t]) + " is not a registered AIR");
+        if (!P->perm_pairs.empty()) return refuse(why, att + "an AIR with permutation pairs cannot be a table of a system (its Zs take the middle matrix)");
+        if (P->degree < 2) return refuse(why, att + "cross-table lookups need degree >= 2 (h c - filter has degree 2)");
+        S.airs.push_back((int)blob[2 + t]);
+        progs.push_back(P);
+    }
+    uint64_t at = 2 + T;
+    const uint64_t K = blob[at++];
+    if (K > SYSTEM_MAX_CTLS) return refuse(why, "a system of " + std::to_string(K) + " CTLs (at most " + std::to_string(SYSTEM_MAX_CTLS) + ")");
+    std::vector<uint64_t> eps_of(T, 0);
+    std::string msg;
+    for (uint64_t k = 0; k < K; k++) {
+        const std::string atk = "CTL " + std::to_string(k) + ": ";
+        if (W < at || W - at < 2) return refuse(why, atk + "runs past the blob");
+        const uint64_t width = blob[at], L = blob[at + 1];
+        at += 2;
+        if (width < 1 || width > CTL_MAX_WIDTH) return refuse(why, atk + "width " + std::to_string(width) + " outside 1.." + std::to_string(CTL_MAX_WIDTH));
+        if (L < 1 || L > SYSTEM_MAX_LOOKING) return refuse(why, atk + std::to_string(L) + " looking endpoints (1.." + std::to_string(SYSTEM_MAX_LOOKING) + ")");
+        Ctl ctl;
+        ctl.width = (uint32_t)width;
+        for (uint64_t e = 0; e <= L; e++) {
+            const std::string ate = atk + (e == 0 ? std::string("looked endpoint: ") : "looking endpoint " + std::to_string(e - 1) + ": ");
+            if (W < at || W - at < 2) return refuse(why, ate + "runs past the blob");
+            const uint64_t table = blob[at], w_e = blob[at + 1];
+            at += 2;
+            if (table >= T) return refuse(why, ate + "table " + std::to_string(table) + " out of range (the system has " + std::to_string(T) + ")");
+            if (w_e != width) return refuse(why, ate + "width mismatch: " + std::to_string(w_e) + " columns, the CTL has " + std::to_string(width));
+            CtlEndpoint ep;
+            ep.table = (uint32_t)table;
+            ep.ctl = (uint32_t)k;
+            ep.looked = e == 0;
+            const uint64_t n_cols = progs[table]->n_cols;
+            for (uint64_t j = 0; j < width; j++) {
+                AirProgram::Column c;
+                if (!read_column(blob, W, &at, n_cols, &c, &msg)) return refuse(why, ate + "column " + std::to_string(j) + ": " + msg);
+                ep.cols.push_back(std::move(c));
+            }
+            if (at >= W) return refuse(why, ate + "filter runs past the blob");
+            const uint64_t np = blob[at] & 0xFFFFFFFFu, ns = blob[at] >> 32;
+            at++;
+            if (np > AIR_LOGUP_MAX_FILTER_PRODUCTS) return refuse(why, ate + "filter of " + std::to_string(np) + " products (at most " + std::to_string(AIR_LOGUP_MAX_FILTER_PRODUCTS) + ")");
+            if (ns > AIR_LOGUP_MAX_FILTER_SUMS) return refuse(why, ate + "filter of " + std::to_string(ns) + " sums (at most " + std::to_string(AIR_LOGUP_MAX_FILTER_SUMS) + ")");
+            ep.filter.n_products = (uint32_t)np;
+            for (uint64_t j = 0; j < 2 * np + ns; j++) {
+                AirProgram::Column fc;
+                if (!read_column(blob, W, &at, n_cols, &fc, &msg)) return refuse(why, ate + "filter: " + msg);
+                ep.filter.cols.push_back(std::move(fc));
+            }
+            eps_of[table]++;
+            if (e == 0) ctl.looked = std::move(ep);
+            else ctl.looking.push_back(std::move(ep));
+        }
+        S.ctls.push_back(std::move(ctl));
+    }
+    if (at != W) return refuse(why, "trailing words after the last CTL");
+    for (uint64_t t = 0; t < T; t++)
+        if (progs[t]->logup_polys() + 4 * eps_of[t] > STARKHIP_AIR_MAX_LOGUP_POLYS)
+            return refuse(why, "table " + std::to_string(t) + ": " + std::to_string(progs[t]->logup_polys()) + " LogUp and " + std::to_string(4 * eps_of[t]) +
+                                   " CTL polynomials, nA + nC above " + std::to_string(STARKHIP_AIR_MAX_LOGUP_POLYS));
+    if (out) *out = std::move(S);
+    return true;
+}
 
 bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std::string* why) {
     if (!blob || words < 8) return refuse(why, "blob shorter than its 8-word header");
@@ -184,23 +280,7 @@ bool air_parse_checked(const uint64_t* blob, size_t words, AirProgram* out, std:
         if (degree < 2) return refuse(why, "LogUp lookups need degree >= 2 (a helper constraint has degree 1 + the columns of its batch)");
         uint64_t at = 2;
         std::string msg2;
-        auto column = [&](AirProgram::Column* c) {  // one COLUMN at sec[at]
-            if (sec_words - at < 2) return msg2 = "runs past the blob", false;
-            const uint64_t nl = sec[at] & 0xFFFFFFFFu, nn = sec[at] >> 32, constant = sec[at + 1];
-            at += 2;
-            if (nl + nn > AIR_LOGUP_MAX_TERMS) return msg2 = "Column of " + std::to_string(nl + nn) + " terms (at most " + std::to_string(AIR_LOGUP_MAX_TERMS) + ")", false;
-            if (constant >= GL_P) return msg2 = "Column constant is not canonical", false;
-            if ((sec_words - at) / 2 < nl + nn) return msg2 = "Column terms run past the blob", false;
-            c->n_local = (uint32_t)nl;
-            c->constant = constant;
-            for (uint64_t k = 0; k < nl + nn; k++, at += 2) {
-                if (sec[at] >= n_cols) return msg2 = "column " + std::to_string(sec[at]) + " out of range", false;
-                if (sec[at + 1] == 0) return msg2 = "Column coefficient is zero", false;
-                if (sec[at + 1] >= GL_P) return msg2 = "Column coefficient is not canonical", false;
-                c->terms.push_back({(uint32_t)sec[at], sec[at + 1]});
-            }
-            return true;
-        };
+        auto column = [&](AirProgram::Column* c) { return read_column(sec, sec_words, &at, n_cols, c, &msg2); };  // one COLUMN at sec[at]
         for (uint64_t l = 0; l < n_lookups; l++) {
             const std::string atl = "LogUp lookup " + std::to_string(l) + ": ";
             if (at >= sec_words) return refuse(why, atl + "runs past the blob");

@@ -801,6 +801,7 @@ int starkhip_proof_layout(const uint64_t* proof, size_t proof_words, starkhip_pr
     out->q_trace_leaf = t.q_leaf; out->q_trace_siblings = t.q_sib; out->q_quotient_leaf = q.q_leaf; out->q_quotient_siblings = q.q_sib;
     out->n_permutation_zs = pl.nZ; out->n_logup_polys = pl.nA; out->off_permutation_zs_cap = z.off_cap; out->off_permutation_zs = z.off_open[0];
     out->off_permutation_zs_next = z.off_open[1]; out->q_permutation_zs_leaf = z.q_leaf; out->q_permutation_zs_siblings = z.q_sib;
+    out->n_ctl_polys = pl.nC; out->off_ctl_sums = pl.nC ? pl.off_sums : 0;  // (all 0 for a proof that is no table proof with endpoints)
     size_t o = q.q_sib + 4 * d0;
     for (size_t l = 0; l < pl.L && l < 16; l++) {
         out->q_step_evals[l] = o; o += 2 * ((size_t)1 << pl.arity_bits);

@@ -114,6 +114,17 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     c->timings[STARKHIP_N_PHASES - 1] = 3.0f;
     return STARKHIP_OK;
 }
+// the halves of prove() a system runs (system.cpp): no pretended system proofs
+int prove_first_half(Ctx*, const AirInfo&, const starkhip_config_t&, const TraceInput&, const uint64_t*, size_t, uint64_t, const CtlTable*, ProveJob** job, uint64_t**, size_t*) {
+    *job = nullptr;
+    return STARKHIP_ERR_NO_DEVICE;
+}
+int prove_trace_cap(ProveJob*, const uint64_t**, size_t*) { return STARKHIP_ERR_NO_DEVICE; }
+int prove_job_hasher(ProveJob*) { return 0; }
+int prove_ctl_polys(ProveJob*, const uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
+int prove_second_half(ProveJob*, const Challenger*, uint64_t**, size_t*) { return STARKHIP_ERR_NO_DEVICE; }
+void prove_job_free(ProveJob*) {}
+int ctl_polys(Ctx*, const CtlTable&, const TraceInput&, const uint64_t*, uint64_t*, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int lde_batch(Ctx*, const uint64_t*, size_t, unsigned, unsigned, uint64_t*, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }
 int ntt_long(Ctx*, uint64_t*, size_t, unsigned, int) { return STARKHIP_ERR_NO_DEVICE; }
 int merkle_cap(Ctx*, const uint64_t*, size_t, unsigned, unsigned, uint64_t*) { return STARKHIP_ERR_NO_DEVICE; }

@@ -6,7 +6,9 @@
 #include <algorithm>
 #include <vector>
 
+#include "ctl.h"
 #include "ctx.h"
+#include "kernels_ctl.h"
 #include "kernels_logup.h"
 #include "kernels_permutation.h"
 #include "logup.h"
@@ -78,6 +80,43 @@ int logup_polys(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t
     HIPCHK(stream_wait(c));
     std::copy(results.begin(), results.begin() + nzs, closing_out);
     *zero_denominators_out = results[nzs];
+    return STARKHIP_OK;
+}
+
+// kernel-level test entry: the CTL polynomials of one table of a system on the caller's trace as the system prover computes them -- the
+// named columns gathered into the copy kept aside, then launch_ctl_polys (no LogUp polynomials in front).  The caller has checked the
+// trace argument, the rows and the challenges.
+int ctl_polys(Ctx* c, const CtlTable& T, const TraceInput& in, const uint64_t* challenges, uint64_t* polys_out, uint64_t* sums_out, uint64_t* zero_denominators_out) {
+    const size_t n = in.n_rows, C = in.n_cols;
+    const unsigned E = (unsigned)T.eps.size();
+    HIPCHK(hipSetDevice(c->device));
+    const std::vector<uint32_t> cols = ctl_columns(T);
+    std::vector<uint32_t> desc = ctl_descriptor(T, true);
+    const size_t desc_words = desc.size();
+    const std::vector<uint32_t> zp = ctl_z_polys(T, 0);
+    desc.insert(desc.end(), zp.begin(), zp.end());
+    Ctx::PermBufs& pb = c->perm;
+    HIPCHK(c->values.ensure(C * n * 8));
+    HIPCHK(c->lde.ensure(C * n * 8));  // upload_dense stages host rows there
+    HIPCHK(pb.cols.ensure(cols.size() * n * 8));
+    HIPCHK(pb.desc.ensure(desc.size() * 4));
+    HIPCHK(pb.zvals.ensure(T.polys() * n * 8));
+    HIPCHK(pb.scan.ensure((ctl_scratch_words(n, E) + ctl_result_words(E)) * 8));
+    const gl_t* d_values = nullptr;
+    if (int rc = upload_dense(c, in, c->values.as<gl_t>(), &d_values)) return rc;
+    for (size_t k = 0; k < cols.size(); k++)
+        HIPCHK(hipMemcpyAsync(pb.cols.as<gl_t>() + k * n, d_values + (size_t)cols[k] * n, n * 8, hipMemcpyDeviceToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(pb.desc.p, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, c->st));
+    gl_t* const d_results = pb.scan.as<gl_t>() + ctl_scratch_words(n, E);
+    HIPCHK(launch_ctl_polys(pb.desc.as<uint32_t>(), pb.desc.as<uint32_t>() + desc_words, pb.cols.as<gl_t>(), n, CtlChallenges{challenges[0], challenges[1], challenges[2], challenges[3]},
+                            n, E, pb.zvals.as<gl_t>(), 0, pb.scan.as<gl_t>(), d_results, c->st));
+    std::vector<gl_t> results(ctl_result_words(E));
+    HIPCHK(hipMemcpyAsync(polys_out, pb.zvals.p, T.polys() * n * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(results.data(), d_results, results.size() * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(stream_wait(c));
+    std::copy(results.begin(), results.begin() + 2 * E, sums_out);
+    *zero_denominators_out = 0;
+    for (unsigned e = 0; e < E; e++) *zero_denominators_out += results[2 * E + e];  // (counted per endpoint)
     return STARKHIP_OK;
 }
 

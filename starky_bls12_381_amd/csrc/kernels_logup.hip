@@ -319,6 +319,18 @@ hipError_t launch_logup_polys(const uint32_t* desc, bool general, const uint32_t
     return hipGetLastError();
 }
 
+// the three scan launches alone, over increments somebody else has written (the cross-table lookups' running sums: kernels_ctl.hip)
+hipError_t launch_logup_scan(const uint32_t* zpoly, size_t n, unsigned n_zs, gl_t* polys, gl_t* scratch, gl_t* totals, hipStream_t st) {
+    if (!n_zs) return hipSuccess;
+    const size_t blocks = perm_span_count(n);
+    gl_t* bs = scratch;
+    gl_t* pre = scratch + (size_t)n_zs * blocks;
+    hipLaunchKernelGGL(logup_block_sums_kernel, dim3((unsigned)blocks, n_zs), dim3(LOGUP_BLOCK), 0, st, polys, zpoly, n, blocks, bs);
+    hipLaunchKernelGGL(logup_scan_blocks_kernel, dim3(n_zs), dim3(LOGUP_BLOCK), 0, st, bs, blocks, pre, totals);
+    hipLaunchKernelGGL(logup_apply_kernel, dim3((unsigned)blocks, n_zs), dim3(LOGUP_BLOCK), 0, st, polys, zpoly, n, blocks, pre);
+    return hipGetLastError();
+}
+
 hipError_t launch_logup_quotient(const uint32_t* desc, bool general, const gl_t* lde, const gl_t* alde, gl_t chi0, gl_t chi1, const gl_t* tab, gl_t* qvals, gl_t alpha0,
                                  gl_t alpha1, gl_t scale0, gl_t scale1, unsigned log_n, unsigned rate_bits, unsigned qdb, hipStream_t st) {
     const size_t size = (size_t)1 << (log_n + qdb);

@@ -66,18 +66,20 @@ struct ProofLayout {
     size_t hasher = 0;  // header word 12: STARKHIP_HASHER_POSEIDON (0, what the word has always been) or STARKHIP_HASHER_KECCAK
     size_t nZ = 0;      // header word 13: permutation Z polynomials (0, what the word has always been, for an AIR without pairs)
     size_t nA = 0;      // header word 14: LogUp auxiliary polynomials (0, what the word has always been, for an AIR without LogUp lookups); never beside nZ
+    size_t nC = 0;      // header word 15: cross-table-lookup polynomials, 4 per endpoint of the table, behind the nA LogUp ones in the middle matrix (0, what the
+                        // word has always been, for a proof that is no table of a system with endpoints); never beside nZ
     size_t ncap;     // 2^cap_h
     size_t log_N;
     MatrixLayout mat[3];  // the committed matrices, n_mats of them: trace, the middle matrix if nZ + nA > 0, quotient (the last)
-    size_t middle() const { return nZ + nA; }  // the middle matrix's polynomials (one of the two is 0)
+    size_t middle() const { return nZ + nA + nC; }  // the middle matrix's polynomials: the Zs, or LogUp || CTL
     size_t n_mats = 0;
     size_t batch_cols[2];  // polynomials opened at zeta (all) and at g zeta: the lengths of the two FRI batches
     // offsets (in words) of what follows the matrices' caps and openings
-    size_t off_fri_caps, off_queries, query_words, off_final, off_pow, off_pis, total;
+    size_t off_fri_caps, off_queries, query_words, off_final, off_pow, off_pis, off_sums, total;  // (off_sums: the nC / 2 CTL sums, the last section)
     std::vector<size_t> layer_depth;  // siblings per FRI layer
 
     // the layout of a proof of AIR program `P` with 2^log_n rows under `cfg` (`geo`: FriGeometry::make(cfg, log_n))
-    static ProofLayout make(const AirProgram& P, const starkhip_config_t& cfg, const FriGeometry& geo, unsigned log_n, unsigned hasher = 0) {
+    static ProofLayout make(const AirProgram& P, const starkhip_config_t& cfg, const FriGeometry& geo, unsigned log_n, unsigned hasher = 0, size_t n_ctl_polys = 0) {
         ProofLayout pl;
         pl.hasher = hasher;
         pl.C = P.n_cols; pl.Q = (size_t)quotient_factor(P.degree) * 2; pl.log_n = log_n; pl.rate_bits = cfg.rate_bits; pl.cap_h = cfg.cap_height;
@@ -85,6 +87,7 @@ struct ProofLayout {
         pl.arity_bits = cfg.arity_bits; pl.n_challenges = 2;
         pl.nZ = P.perm_zs();
         pl.nA = P.logup_polys();
+        pl.nC = n_ctl_polys;
         pl.compute();
         return pl;
     }
@@ -123,6 +126,7 @@ struct ProofLayout {
         off_final = o; o += 2 * final_len;
         off_pow = o; o += 1;
         off_pis = o; o += n_pis;
+        off_sums = o; o += nC / 2;
         total = o;
     }
     void write_header(uint64_t* h) const {
@@ -131,13 +135,14 @@ struct ProofLayout {
         h[12] = hasher;
         h[13] = nZ;
         h[14] = nA;
-        h[15] = 0;
+        h[15] = nC;
     }
     bool read_header(const uint64_t* h, size_t words) {
         if (words < 16 || h[0] != STARKHIP_PROOF_MAGIC) return false;
         C = h[1]; Q = h[2]; log_n = h[3]; rate_bits = h[4]; cap_h = h[5]; L = h[6]; n_queries = h[7]; final_len = h[8];
-        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11]; hasher = h[12]; nZ = h[13]; nA = h[14];
+        n_pis = h[9]; arity_bits = h[10]; n_challenges = h[11]; hasher = h[12]; nZ = h[13]; nA = h[14]; nC = h[15];
         if (hasher > STARKHIP_HASHER_KECCAK || nZ > 128 || nA > STARKHIP_AIR_MAX_LOGUP_POLYS || (nZ && nA)) return false;
+        if ((nC & 3) || nC > STARKHIP_AIR_MAX_LOGUP_POLYS || nA + nC > STARKHIP_AIR_MAX_LOGUP_POLYS || (nZ && nC)) return false;
         if (log_n > 32 || rate_bits > 8 || cap_h > 16 || L > 16 || arity_bits > 8 || log_n + rate_bits < cap_h) return false;
         if (L * arity_bits + cap_h > log_n + rate_bits) return false;
         compute();

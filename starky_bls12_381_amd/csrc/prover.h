@@ -79,6 +79,24 @@ size_t ctx_pinned_bytes(Ctx* c);  // page-locked host memory it holds (upload st
 
 int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow_witness,
           uint64_t** proof_out, size_t* proof_words);
+// prove() in two halves over one job (prover.hip): upload .. trace_merkle, then quotient .. queries.  prove() is the two back to back with
+// no endpoints and no initial challenger.  A system of tables (system.cpp; COMPAT.md 2d) runs every table's first half, reads the trace
+// caps, replays the system transcript, has every table compute its CTL polynomials and sums under the system's challenges, checks the
+// balances and runs every second half from a copy of the system's challenger.  A job that is not taken through its second half is
+// freed with prove_job_free; the first half hands out no job when it fails (a refused trace: its check blob in *proof_out).
+struct CtlTable;    // ctl.h
+struct Challenger;  // poseidon.h
+struct ProveJob;
+int prove_first_half(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in, const uint64_t* pis, size_t n_pis, uint64_t pow_witness,
+                     const CtlTable* ctl, ProveJob** job_out, uint64_t** proof_out, size_t* proof_words);
+int prove_trace_cap(ProveJob* job, const uint64_t** cap, size_t* words);
+int prove_job_hasher(ProveJob* job);  // the hasher its transcript and commitments run under (STARKHIP_HASHER_*)
+int prove_ctl_polys(ProveJob* job, const uint64_t challenges[4], uint64_t* sums, uint64_t* zero_denominators);  // sums [2 E], zero denominators per endpoint [E]
+int prove_second_half(ProveJob* job, const Challenger* initial, uint64_t** proof_out, size_t* proof_words);
+void prove_job_free(ProveJob* job);
+// starkhip_ctl_polys: the CTL polynomials of one table of a system on one trace, through the kernels the system prover uses (kernels_ctl.hip);
+// challenges {beta_0, gamma_0, beta_1, gamma_1}, polys_out [4 E][n_rows], sums_out [2 E], the count of zero denominators
+int ctl_polys(Ctx* c, const CtlTable& table, const TraceInput& in, const uint64_t* challenges, uint64_t* polys_out, uint64_t* sums_out, uint64_t* zero_denominators_out);
 // starkhip_check_trace: every constraint of `air` on every row of the trace, on the device (kernels_check.hip)
 int check_trace(Ctx* c, const AirInfo& air, const TraceInput& in, const uint64_t* pis, uint64_t* violations, uint64_t first[3]);
 // starkhip_check_trace_report: the same check with per-constraint counts, the rows and a list (kernels_check.hip, check_report.h)

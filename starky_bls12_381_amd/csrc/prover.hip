@@ -13,13 +13,16 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <vector>
 
 #include "airs.h"
 #include "blob_arena.h"
 #include "check_report.h"
+#include "ctl.h"
 #include "ctx.h"
 #include "kernels.h"
+#include "kernels_ctl.h"
 #include "kernels_logup.h"
 #include "kernels_permutation.h"
 #include "lde_ranges.h"
@@ -102,13 +105,14 @@ struct ProofShape {
     size_t n, N, C, Q, size, ncap, L;              // rows, LDE points, trace and quotient columns, quotient points (n << qdb), cap nodes, FRI layers
     size_t nZ, perm_cols, perm_desc_words;         // permutation pairs: Z polynomials, the columns the pairs name, words of one descriptor (0 without pairs)
     size_t nA, nLZ;                                // LogUp lookups: auxiliary polynomials and, of them, the Zs (2 per lookup); perm_cols and perm_desc_words are then theirs
-    size_t mid;                                    // the middle matrix's polynomials: nZ or nA (never both), 0 without either
+    size_t nC, nE, ctl_cols, ctl_desc_words;       // a table of a system: its CTL polynomials (4 per endpoint), its endpoints, the columns they name, words of one CTL descriptor
+    size_t mid;                                    // the middle matrix's polynomials: nZ, or nA + nC (LogUp || CTL), 0 without any
     bool logup_general;                            // LogUp lookups over Columns and Filters (or the general kernels forced): the form of the descriptors
     FriGeometry geo;
     ProofLayout pl;
     // STARKHIP_ERR_BAD_SHAPE for what prove() refuses: rows that are no power of two in 2 .. 2^max_log_rows(air), a config that the one
     // config rule (FriGeometry::make) refuses or whose blow-up is below the AIR's quotient degree
-    static int make(const AirInfo& air, const starkhip_config_t& cfg, size_t n_rows, ProofShape* s) {
+    static int make(const AirInfo& air, const starkhip_config_t& cfg, size_t n_rows, ProofShape* s, const CtlTable* ctl = nullptr) {
         const AirProgram& P = air.prog;
         unsigned log_n = 0;
         if (!log2_rows(n_rows, &log_n) || cfg.num_challenges != 2 || log_n > max_log_rows(air)) return STARKHIP_ERR_BAD_SHAPE;
@@ -118,9 +122,12 @@ struct ProofShape {
         s->n = n_rows; s->N = s->n << s->r; s->C = P.n_cols; s->Q = (size_t)s->factor * 2; s->size = s->n << s->qdb;
         s->ncap = (size_t)1 << s->cap_h; s->L = s->geo.arities.size();
         s->nZ = P.perm_zs(); s->perm_cols = s->nZ ? perm_columns(P).size() : 0; s->perm_desc_words = s->nZ ? perm_descriptor(P, false).size() : 0;
-        s->nA = P.logup_polys(); s->nLZ = 2 * P.logups.size(); s->mid = s->nZ + s->nA; s->logup_general = false;
+        s->nA = P.logup_polys(); s->nLZ = 2 * P.logups.size(); s->logup_general = false;
         if (s->nA) { s->perm_cols = logup_columns(P).size(); s->logup_general = logup_use_general(P); s->perm_desc_words = logup_descriptor(P, false, s->logup_general).size(); }
-        s->pl = ProofLayout::make(P, cfg, s->geo, log_n);
+        s->nE = ctl ? ctl->eps.size() : 0; s->nC = 4 * s->nE; s->ctl_cols = s->nE ? ctl_columns(*ctl).size() : 0; s->ctl_desc_words = s->nE ? ctl_descriptor(*ctl, false).size() : 0;
+        if (s->nC && (s->nZ || s->nA + s->nC > STARKHIP_AIR_MAX_LOGUP_POLYS || P.degree < 2)) return STARKHIP_ERR_BAD_SHAPE;  // (a registered system never has such a table)
+        s->mid = s->nZ + s->nA + s->nC;
+        s->pl = ProofLayout::make(P, cfg, s->geo, log_n, 0, s->nC);
         return STARKHIP_OK;
     }
 };
@@ -158,8 +165,12 @@ static std::vector<BufWant> work_buffers(Ctx* c, const ProofShape& s, unsigned n
         {&c->tab->leaf_prefix, leaf_prefix_bytes(c, C, s.log_n, s.r)}};
     if (const size_t nZ = s.mid) {  // an AIR with permutation pairs or with LogUp lookups: the middle matrix (Ctx::PermBufs)
         Ctx::PermBufs& pb = c->perm;
-        const size_t scan_words = s.nA ? logup_scratch_words(n, (unsigned)s.nLZ) + logup_result_words((unsigned)s.nLZ) : perm_scratch_words(n, (unsigned)nZ) + nZ;
-        for (const BufWant& b : {BufWant{&pb.cols, s.perm_cols * n * 8}, BufWant{&pb.desc, (2 * s.perm_desc_words + s.nLZ) * 4}, BufWant{&pb.chal, 4 * (size_t)s.factor * 8},
+        // (a table of a system: the CTL columns behind the LogUp ones, the two CTL descriptors and the Zs' indices behind LogUp's, the scan's
+        // scratch shared -- the CTL polynomials are done before logup() starts --, and in `chal` the CTL sums and the count of zero denominators)
+        const size_t scan_words = s.nA + s.nC ? std::max(logup_scratch_words(n, (unsigned)s.nLZ) + logup_result_words((unsigned)s.nLZ), ctl_scratch_words(n, (unsigned)s.nE))
+                                              : perm_scratch_words(n, (unsigned)nZ) + nZ;
+        for (const BufWant& b : {BufWant{&pb.cols, (s.perm_cols + s.ctl_cols) * n * 8}, BufWant{&pb.desc, (2 * s.perm_desc_words + s.nLZ + 2 * s.ctl_desc_words + 2 * s.nE) * 4},
+                                 BufWant{&pb.chal, std::max(4 * (size_t)s.factor, ctl_result_words((unsigned)s.nE)) * 8},
                                  BufWant{&pb.zvals, nZ * n * 8}, BufWant{&pb.zcoef, lde_long_supported(s.log_n) ? nZ * n * 8 : 0}, BufWant{&pb.zlde, nZ * N * 8},
                                  BufWant{&pb.zdigests, digest_words(N) * 8}, BufWant{&pb.scan, scan_words * 8},
                                  BufWant{&pb.open_z, nZ * 16}, BufWant{&pb.open_zn, nZ * 16}})
@@ -243,6 +254,17 @@ struct ProveCall {
     int permutation();
     gl_t logup_chal[2] = {0, 0};  // an AIR with LogUp lookups: chi_0, chi_1
     int logup();
+    // A table of a system (COMPAT.md 2d): its endpoints (null: a proof on its own), the challenger after the system transcript, which the
+    // table's transcript starts from instead of observing its own trace cap (C2), the CTL challenges, the table's sums (challenge-major)
+    // and how many denominators were zero.  ctl_polys() runs between the two halves of the proof; aux_commit() commits LogUp || CTL.
+    const CtlTable* ctl = nullptr;
+    const Challenger* ch_initial = nullptr;
+    CtlChallenges ctl_chal = {0, 0, 0, 0};
+    std::vector<gl_t> ctl_sums;
+    std::vector<uint64_t> ctl_zero_denominators;  // per endpoint, both challenges together
+    size_t ctl_desc_at() const { return 2 * s.perm_desc_words + s.nLZ; }  // where the CTL descriptors start in perm.desc: by slot, the Zs' indices, by trace column
+    int ctl_polys(const gl_t chal[4]);
+    int aux_commit();
     gl_t alphas[2] = {0, 0};
     gl2_t zeta = gl2_zero();
     uint64_t* out = nullptr;  // the proof blob, from queries() on -- or the check blob of a trace that upload() refused
@@ -351,9 +373,14 @@ int ProveCall::upload() {
     // enqueued; a violating trace ends the proof here with STARKHIP_ERR_TRACE and its check blob in `out`
     if (rc == 0 && c->opt_check_trace) rc = check_trace_in_prove(c, air, d_values, s.n, pis_host, &out, &check_words);
     if (rc == 0 && s.mid) {  // the columns the permutation pairs (or the LogUp lookups) name, aside: the LDE overwrites a parked trace and keeps no coefficients of it
-        const std::vector<uint32_t> cols = s.nA ? logup_columns(air.prog) : perm_columns(air.prog);
+        const std::vector<uint32_t> cols = s.nA ? logup_columns(air.prog) : s.nZ ? perm_columns(air.prog) : std::vector<uint32_t>();
         for (size_t k = 0; k < cols.size(); k++)
             HIPCHK(hipMemcpyAsync(c->perm.cols.as<gl_t>() + k * s.n, d_values + (size_t)cols[k] * s.n, s.n * 8, hipMemcpyDeviceToDevice, st));
+        if (s.nC) {  // ... and the columns the table's CTL endpoints name, behind them
+            const std::vector<uint32_t> more = ctl_columns(*ctl);
+            for (size_t k = 0; k < more.size(); k++)
+                HIPCHK(hipMemcpyAsync(c->perm.cols.as<gl_t>() + (cols.size() + k) * s.n, d_values + (size_t)more[k] * s.n, s.n * 8, hipMemcpyDeviceToDevice, st));
+        }
     }
     return rc;
 }
@@ -552,7 +579,7 @@ int ProveCall::permutation() {
 // then the LDE, the commitment under the context's hasher and the cap into the transcript
 int ProveCall::logup() {
     const AirProgram& P = air.prog;
-    const size_t n = s.n, nA = s.nA;
+    const size_t n = s.n;
     const unsigned nzs = (unsigned)s.nLZ;
     fs.start();
     for (gl_t& x : logup_chal) x = ch.get();  // L1
@@ -569,12 +596,46 @@ int ProveCall::logup() {
     HIPCHK(stream_wait(c));
     for (gl_t v : results)  // the closing values, then the zero denominators
         if (v != 0) return STARKHIP_ERR_QUOTIENT_NOT_DIVISIBLE;
-    HIPCHK(run_lde(c, pb.zvals.as<gl_t>(), lde_long_supported(s.log_n) ? pb.zcoef.as<gl_t>() : nullptr, pb.zlde.as<gl_t>(), nA, s.log_n, s.r, 0));
-    if (int rc = commit_narrow(mats[1], nA)) return rc;
+    return 0;
+}
+
+// ... and the end of it, for LogUp lookups, CTL endpoints or both: the middle matrix LogUp || CTL through the LDE, one commitment under the
+// context's hasher, its cap into the transcript (L3, C3), then the table's sums (C2)
+int ProveCall::aux_commit() {
+    Ctx::PermBufs& pb = c->perm;
+    const size_t nM = s.nA + s.nC;
+    HIPCHK(run_lde(c, pb.zvals.as<gl_t>(), lde_long_supported(s.log_n) ? pb.zcoef.as<gl_t>() : nullptr, pb.zlde.as<gl_t>(), nM, s.log_n, s.r, 0));
+    if (int rc = commit_narrow(mats[1], nM)) return rc;
     HIPCHK(stream_wait(c));
     fs.start();
     ch.observe_many(mats[1].cap.data(), mats[1].cap.size());
+    if (s.nC) ch.observe_many(ctl_sums.data(), ctl_sums.size());
     fs.stop();
+    return 0;
+}
+
+// Between the halves of a table's proof (C3): the CTL polynomials h and Z of every endpoint under both challenge pairs, from the copy of
+// the named columns, behind where logup() will put its own; the sums and the count of zero denominators come back to the host, and the
+// sums stay on the device for the quotient.  The caller (the system) checks the balances before anything auxiliary is committed.
+int ProveCall::ctl_polys(const gl_t chal[4]) {
+    const size_t n = s.n;
+    const unsigned E = (unsigned)s.nE;
+    ctl_chal = {chal[0], chal[1], chal[2], chal[3]};
+    ctl_sums.assign(2 * E, 0);
+    ctl_zero_denominators.assign(E, 0);
+    if (!E) return 0;
+    Ctx::PermBufs& pb = c->perm;
+    std::vector<uint32_t> desc = ctl_descriptor(*ctl, true, (uint32_t)s.perm_cols);
+    for (const std::vector<uint32_t>& more : {ctl_z_polys(*ctl, (uint32_t)s.nA), ctl_descriptor(*ctl, false)}) desc.insert(desc.end(), more.begin(), more.end());
+    uint32_t* const d_desc = pb.desc.as<uint32_t>() + ctl_desc_at();
+    HIPCHK(hipMemcpyAsync(d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_ctl_polys(d_desc, d_desc + s.ctl_desc_words, pb.cols.as<gl_t>(), n, ctl_chal, n, E, pb.zvals.as<gl_t>(), (unsigned)s.nA, pb.scan.as<gl_t>(),
+                            pb.chal.as<gl_t>(), st));
+    std::vector<gl_t> results(ctl_result_words(E));
+    HIPCHK(read_back(c, results.data(), pb.chal.p, results.size() * 8, st));
+    HIPCHK(stream_wait(c));  // desc goes out of scope
+    std::copy(results.begin(), results.begin() + 2 * E, ctl_sums.begin());
+    ctl_zero_denominators.assign(results.begin() + 2 * E, results.end());
     return 0;
 }
 
@@ -583,12 +644,20 @@ int ProveCall::quotient() {
     const size_t n = s.n, size = s.size, factor = s.factor;
     HIPCHK(stream_wait(c));  // the trace cap
     fs.start();
-    ch.observe_many(mats[0].cap.data(), mats[0].cap.size());  // public inputs are NOT observed (App. A.5)
+    if (ch_initial) {  // a table of a system starts from the system transcript, which has observed every table's trace cap (C2)
+        const int hasher = ch.hasher;
+        ch = *ch_initial;
+        ch.hasher = hasher;
+    } else {
+        ch.observe_many(mats[0].cap.data(), mats[0].cap.size());  // public inputs are NOT observed (App. A.5)
+    }
     fs.stop();
     if (s.nZ)
         if (int rc = permutation()) return rc;
     if (s.nA)
         if (int rc = logup()) return rc;
+    if (s.nA + s.nC)
+        if (int rc = aux_commit()) return rc;
     fs.start();
     alphas[0] = ch.get();
     alphas[1] = ch.get();
@@ -610,6 +679,12 @@ int ProveCall::quotient() {
             HIPCHK(launch_logup_quotient(c->perm.desc.as<uint32_t>() + s.perm_desc_words, s.logup_general, c->lde.as<gl_t>(), c->perm.zlde.as<gl_t>(), logup_chal[0], logup_chal[1],
                                          c->tab->qtab.as<gl_t>(), c->qvals.as<gl_t>(), alphas[0], alphas[1], gl_pow(alphas[0], nL), gl_pow(alphas[1], nL), s.log_n, s.r,
                                          s.qdb, st));
+        }
+        if (s.nC) {  // C4: the CTL constraints after them (kernels_ctl.hip)
+            const uint64_t nK = ctl->constraints() / 2;  // one challenge's share: the kernel scales what is there by its square
+            HIPCHK(launch_ctl_quotient(c->perm.desc.as<uint32_t>() + ctl_desc_at() + s.ctl_desc_words + 2 * s.nE, c->lde.as<gl_t>(), c->perm.zlde.as<gl_t>() + s.nA * s.N, ctl_chal,
+                                       c->perm.chal.as<gl_t>(), c->tab->qtab.as<gl_t>(), c->qvals.as<gl_t>(), alphas[0], alphas[1], gl_pow(alphas[0], nK), gl_pow(alphas[1], nK),
+                                       s.log_n, s.r, s.qdb, st));
         }
         // coset_ifft(7): inverse transform, scale by size^-1 and by 7^-i
         if (int rc = run_ntt(c, c->qvals.as<gl_t>(), c->partial.as<gl_t>(), 2, size, s.log_n + s.qdb, true, nullptr, c->tab->qshift_inv.as<gl_t>()))  // (the chunks' partial sums are spent)
@@ -867,24 +942,77 @@ int ProveCall::queries() {
     memcpy(out + pl.off_final, final_poly.data(), s.geo.final_poly_len * 16);
     out[pl.off_pow] = pow_witness;
     if (pl.n_pis) memcpy(out + pl.off_pis, pis_host, pl.n_pis * 8);
+    if (pl.nC) memcpy(out + pl.off_sums, ctl_sums.data(), ctl_sums.size() * 8);  // C6: the table's sums, the last section
     return 0;
 }
 
 }  // namespace
 
-// The transcript of SURVEY.md App. A.5: argument checks, tables and plan, buffers, then the phases.  The order of what they enqueue on the
-// context's stream and the places where the host waits for it make the phase timings mean what starkhip.h says; a pool's overlap depends on it.
-int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in, const uint64_t* pis_host, size_t n_pis, uint64_t pow_witness,
-          uint64_t** proof_out, size_t* proof_words) {
-    struct ReadBackGuard {  // an early return between a read_back() and its stream_wait() must not leave destinations of this call behind
-        Ctx* c;
-        ~ReadBackGuard() {
-            c->rb_pending.clear();
-            c->rb_used = 0;
-        }
-    } read_back_guard{c};
+// One proof between its two halves: the shape, the copies of the arguments its phases keep pointing at, the phases' state and where the
+// list of phases stands.  The guard of the read-backs lives as long as the proof does.
+struct ProveJob {
+    Ctx* c;
+    const AirInfo& air;
+    starkhip_config_t cfg;
+    TraceInput in;
+    std::vector<uint64_t> pis;
+    CtlTable ctl;
     ProofShape s;
-    if (n_pis != air.prog.n_pis || in.n_cols != air.prog.n_cols || ProofShape::make(air, cfg, in.n_rows, &s) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
+    std::unique_ptr<ProveCall> p;
+    int evi = 0;
+    bool quotient_started = false;  // prove_ctl_polys has recorded the quotient phase's boundary
+    PhaseRanges ranges;
+    ProveJob(Ctx* c_, const AirInfo& air_, const starkhip_config_t& cfg_, const TraceInput& in_, const uint64_t* pis_, size_t n_pis, const CtlTable* ctl_)
+        : c(c_), air(air_), cfg(cfg_), in(in_), pis(pis_, pis_ + n_pis) {
+        if (ctl_) ctl = *ctl_;
+    }
+    ~ProveJob() {  // an early return between a read_back() and its stream_wait() must not leave destinations of this proof behind
+        c->rb_pending.clear();
+        c->rb_used = 0;
+    }
+};
+
+namespace {
+// before each phase: the boundary event of starkhip_last_timings on the stream and the phase's rocTX range (rocprofv3 --marker-trace)
+const struct { const char* range; int (ProveCall::*run)(); } PHASES[STARKHIP_N_PHASES - 1] = {
+    {"starkhip:upload", &ProveCall::upload}, {"starkhip:ifft_lde", &ProveCall::ifft_lde}, {"starkhip:trace_merkle", &ProveCall::trace_merkle},
+    {"starkhip:quotient", &ProveCall::quotient}, {"starkhip:quotient_commit", &ProveCall::quotient_commit}, {"starkhip:openings", &ProveCall::openings},
+    {"starkhip:fri_combine", &ProveCall::fri_combine}, {"starkhip:fri_commit", &ProveCall::fri_commit}, {"starkhip:pow", &ProveCall::pow},
+    {"starkhip:queries", &ProveCall::queries}};
+const int FIRST_HALF_PHASES = 3;  // upload, ifft_lde, trace_merkle
+
+// phases [from, to) of the job; a refused trace hands its check blob out
+int run_phases(ProveJob* j, int from, int to, uint64_t** proof_out, size_t* proof_words) {
+    ProveCall& p = *j->p;
+    for (int k = from; k < to; k++) {
+        if (!(k == FIRST_HALF_PHASES && j->quotient_started)) {
+            HIPCHK(hipEventRecord(j->c->ev[j->evi++], p.st));
+            j->ranges.next(PHASES[k].range);
+        }
+        if (int rc = (p.*PHASES[k].run)()) {
+            if (rc == STARKHIP_ERR_TRACE) {  // the check blob instead of a proof
+                *proof_out = p.out;
+                *proof_words = p.check_words;
+            }
+            return rc;
+        }
+    }
+    return 0;
+}
+}  // namespace
+
+// The transcript of SURVEY.md App. A.5 in two halves over one ProveCall.  The first: argument checks, tables and plan, buffers, then the
+// phases upload .. trace_merkle.  The order of what the phases enqueue on the context's stream and the places where the host waits for it
+// make the phase timings mean what starkhip.h says; a pool's overlap depends on it.  `ctl`: the endpoints of a table of a system, or null.
+int prove_first_half(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in_arg, const uint64_t* pis_arg, size_t n_pis, uint64_t pow_witness,
+                     const CtlTable* ctl, ProveJob** job_out, uint64_t** proof_out, size_t* proof_words) {
+    *job_out = nullptr;
+    if (n_pis != air.prog.n_pis || in_arg.n_cols != air.prog.n_cols) return STARKHIP_ERR_BAD_SHAPE;
+    std::unique_ptr<ProveJob> job(new ProveJob(c, air, cfg, in_arg, pis_arg, n_pis, ctl));
+    ProofShape& s = job->s;
+    const TraceInput& in = job->in;
+    const uint64_t* pis_host = job->pis.data();
+    if (ProofShape::make(air, cfg, in.n_rows, &s, ctl ? &job->ctl : nullptr) != STARKHIP_OK) return STARKHIP_ERR_BAD_SHAPE;
     s.pl.hasher = (size_t)c->opt_hasher;  // header word 12
     for (size_t i = 0; i < n_pis; i++)
         if (pis_host[i] >= GL_P) return STARKHIP_ERR_BAD_SHAPE;
@@ -919,30 +1047,52 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     if (prefix)
         if (int rc = ensure_leaf_prefix(c, s.log_n, s.r)) return rc;
 
-    ProveCall p{c, air, cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde, fill, fill_freq, prefix,
-                trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()};
-    p.ch.hasher = (int)c->opt_hasher;  // the transcript's sponge duplexes through the context's hasher
-    // before each phase: the boundary event of starkhip_last_timings on the stream and the phase's rocTX range (rocprofv3 --marker-trace)
-    static const struct { const char* range; int (ProveCall::*run)(); } PHASES[STARKHIP_N_PHASES - 1] = {
-        {"starkhip:upload", &ProveCall::upload}, {"starkhip:ifft_lde", &ProveCall::ifft_lde}, {"starkhip:trace_merkle", &ProveCall::trace_merkle},
-        {"starkhip:quotient", &ProveCall::quotient}, {"starkhip:quotient_commit", &ProveCall::quotient_commit}, {"starkhip:openings", &ProveCall::openings},
-        {"starkhip:fri_combine", &ProveCall::fri_combine}, {"starkhip:fri_commit", &ProveCall::fri_commit}, {"starkhip:pow", &ProveCall::pow},
-        {"starkhip:queries", &ProveCall::queries}};
-    int evi = 0;
-    PhaseRanges ranges;
-    for (const auto& ph : PHASES) {
-        HIPCHK(hipEventRecord(c->ev[evi++], st));
-        ranges.next(ph.range);
-        if (int rc = (p.*ph.run)()) {
-            if (rc == STARKHIP_ERR_TRACE) {  // the check blob instead of a proof
-                *proof_out = p.out;
-                *proof_words = p.check_words;
-            }
-            return rc;
-        }
+    job->p.reset(new ProveCall{c, air, job->cfg, s, st, in, pis_host, pow_witness, tiled, n_chunks, trace_in_lde, fill, fill_freq, prefix,
+                               trace_in_lde ? c->lde.as<gl_t>() + (N - n) * C : c->values.as<gl_t>()});
+    job->p->ch.hasher = (int)c->opt_hasher;  // the transcript's sponge duplexes through the context's hasher
+    if (ctl) job->p->ctl = &job->ctl;
+    if (int rc = run_phases(job.get(), 0, FIRST_HALF_PHASES, proof_out, proof_words)) return rc;
+    *job_out = job.release();
+    return STARKHIP_OK;
+}
+
+// what a system needs of a table between the halves: its trace cap (the wait for it is the one quotient() would have made) ...
+int prove_trace_cap(ProveJob* j, const uint64_t** cap, size_t* words) {
+    HIPCHK(stream_wait(j->c));
+    *cap = j->p->mats[0].cap.data();
+    *words = j->p->mats[0].cap.size();
+    return STARKHIP_OK;
+}
+int prove_job_hasher(ProveJob* j) { return j->p->ch.hasher; }
+// ... and its CTL polynomials under the system's challenges: sums [2 E] challenge-major and, per endpoint, the count of zero denominators [E]
+int prove_ctl_polys(ProveJob* j, const uint64_t chal[4], uint64_t* sums, uint64_t* zero_denominators) {
+    HIPCHK(hipSetDevice(j->c->device));
+    // the quotient phase starts here: the CTL polynomials are timed with it, as the LogUp ones are (the second half does not record the
+    // boundary again).  What the stream idled since its trace commitment -- the other tables' first halves -- ends up in trace_merkle.
+    if (!j->quotient_started) {
+        HIPCHK(hipEventRecord(j->c->ev[j->evi++], j->p->st));
+        j->ranges.next(PHASES[FIRST_HALF_PHASES].range);
+        j->quotient_started = true;
     }
+    if (int rc = j->p->ctl_polys(chal)) return rc;
+    std::copy(j->p->ctl_sums.begin(), j->p->ctl_sums.end(), sums);
+    std::copy(j->p->ctl_zero_denominators.begin(), j->p->ctl_zero_denominators.end(), zero_denominators);
+    return STARKHIP_OK;
+}
+
+// The second half: quotient .. queries.  `initial`: the challenger the table's transcript starts from (a table of a system), or null: the
+// proof observes its own trace cap, as a proof on its own does.  The job is spent either way.
+int prove_second_half(ProveJob* job_in, const Challenger* initial, uint64_t** proof_out, size_t* proof_words) {
+    std::unique_ptr<ProveJob> job(job_in);
+    Ctx* c = job->c;
+    ProveCall& p = *job->p;
+    const ProofShape& s = job->s;
+    HIPCHK(hipSetDevice(c->device));
+    p.ch_initial = initial;
+    if (int rc = run_phases(job.get(), FIRST_HALF_PHASES, STARKHIP_N_PHASES - 1, proof_out, proof_words)) return rc;
+    hipStream_t st = p.st;
     uint64_t* const out = p.out;
-    if (hipEventRecord(c->ev[evi++], st) != hipSuccess || stream_wait(c) != hipSuccess) {
+    if (hipEventRecord(c->ev[job->evi++], st) != hipSuccess || stream_wait(c) != hipSuccess) {
         blob_free(out);
         return STARKHIP_ERR_HIP;
     }
@@ -963,6 +1113,15 @@ int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceI
     *proof_out = out;
     *proof_words = s.pl.total;
     return STARKHIP_OK;
+}
+void prove_job_free(ProveJob* job) { delete job; }
+
+// A proof on its own: the two halves back to back, no endpoints, no initial challenger
+int prove(Ctx* c, const AirInfo& air, const starkhip_config_t& cfg, const TraceInput& in, const uint64_t* pis_host, size_t n_pis, uint64_t pow_witness,
+          uint64_t** proof_out, size_t* proof_words) {
+    ProveJob* job = nullptr;
+    if (int rc = prove_first_half(c, air, cfg, in, pis_host, n_pis, pow_witness, nullptr, &job, proof_out, proof_words)) return rc;
+    return prove_second_half(job, nullptr, proof_out, proof_words);
 }
 
 // Everything a proof of `air` (default rows, config `cfg`) will ask of this context, allocated NOW: shape tables, the constraint

@@ -12,6 +12,7 @@
 
 #include "air_eval.h"
 #include "airs.h"
+#include "ctl.h"
 #include "logup.h"
 #include "permutation.h"
 #include "poseidon.h"
@@ -77,7 +78,7 @@ static gl2_t fri_fold_eval(gl_t x, size_t x_index_within_coset, unsigned arity_b
 }
 
 int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words, bool check_query_words,
-                   VerifyPrelude* out) {
+                   VerifyPrelude* out, const CtlVerify* ctl) {
     ProofLayout& pl = out->pl;
     if (!pl.read_header(proof, words)) return STARKHIP_ERR_BAD_SHAPE;
     const AirProgram& P = air.prog;
@@ -86,7 +87,8 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     const unsigned factor = quotient_factor(P.degree);
     if (pl.C != P.n_cols || pl.n_pis != P.n_pis || pl.rate_bits != cfg.rate_bits || pl.cap_h != cfg.cap_height ||
         pl.n_queries != cfg.num_query_rounds || pl.n_challenges != cfg.num_challenges || pl.Q != (size_t)factor * cfg.num_challenges ||
-        pl.arity_bits != cfg.arity_bits || pl.nZ != P.perm_zs() || pl.nA != P.logup_polys())
+        pl.arity_bits != cfg.arity_bits || pl.nZ != P.perm_zs() || pl.nA != P.logup_polys() ||
+        pl.nC != (ctl ? ctl->table->polys() : 0))  // (a table proof of a system on its own: its header names CTL polynomials, nobody here knows its endpoints)
         return STARKHIP_ERR_BAD_SHAPE;
     const size_t skip_lo = check_query_words ? words : pl.off_queries, skip_hi = check_query_words ? words : pl.off_final;
     for (size_t i = 16; i < skip_lo; i++)
@@ -111,7 +113,12 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
 
     // ---- challenges, in transcript order (App. A.5)
     Challenger ch((int)pl.hasher);  // the hasher the header names: the sponge's permutation, and proof of work through it
-    ch.observe_many(proof + pl.mat[0].off_cap, 4 * ncap);
+    if (ctl) {  // C2: the table's transcript is a copy of the system's, which has observed every table's trace cap
+        if (ctl->initial->hasher != (int)pl.hasher) return STARKHIP_ERR_VERIFY;
+        ch = *ctl->initial;
+    } else {
+        ch.observe_many(proof + pl.mat[0].off_cap, 4 * ncap);
+    }
     // permutation challenges (COMPAT.md P1): B sets of 2 x (beta, gamma) after the trace cap, then the Z cap (P3), then the alphas
     std::vector<gl_t> perm_chal(nZ ? (size_t)P.perm_batch_size() * 4 : 0);
     for (gl_t& x : perm_chal) x = ch.get();
@@ -120,6 +127,7 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     if (pl.nA)
         for (gl_t& x : logup_chal) x = ch.get();
     for (size_t k = 1; k < last; k++) ch.observe_many(proof + pl.mat[k].off_cap, 4 * ncap);
+    ch.observe_many(proof + pl.off_sums, pl.nC / 2);  // C2: the table's sums, behind the cap of LogUp || CTL
     std::vector<gl2_t> alphas(cfg.num_challenges);
     for (auto& a : alphas) a = gl2_from_base(ch.get());
     ch.observe_many(proof + pl.mat[last].off_cap, 4 * ncap);
@@ -155,6 +163,9 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     air_eval_folded<ExtOps>(P, op_local, op_next, pis, masks, alphas.data(), (int)cfg.num_challenges, acc.data());
     if (nZ) perm_eval_folded<ExtOps>(P, op_local, opened(1, 0), opened(1, 1), perm_chal.data(), masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // P4
     if (pl.nA) logup_eval_folded<ExtOps>(P, op_local, op_next, opened(1, 0), opened(1, 1), logup_chal, masks, alphas.data(), (int)cfg.num_challenges, acc.data());  // L4
+    if (pl.nC)  // C4, with the sums taken from the proof
+        ctl_eval_folded<ExtOps>(*ctl->table, op_local, op_next, opened(1, 0) + pl.nA, opened(1, 1) + pl.nA, ctl->challenges, proof + pl.off_sums, masks, alphas.data(),
+                                (int)cfg.num_challenges, acc.data());
     for (unsigned i = 0; i < cfg.num_challenges; i++) {
         gl2_t s = gl2_zero();
         for (unsigned k = factor; k-- > 0;) s = gl2_add(gl2_mul(s, zeta_n), op_q[i * factor + k]);
@@ -174,9 +185,11 @@ int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint6
     return STARKHIP_OK;
 }
 
-int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words) {
+int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words) { return verify_proof(air, cfg, proof, words, nullptr); }
+
+int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words, const CtlVerify* ctl) {
     VerifyPrelude pre;
-    if (int rc = verify_prelude(air, cfg, proof, words, true, &pre); rc != STARKHIP_OK) return rc;
+    if (int rc = verify_prelude(air, cfg, proof, words, true, &pre, ctl); rc != STARKHIP_OK) return rc;
     const ProofLayout& pl = pre.pl;
     const FriGeometry& geo = pre.geo;
     const size_t ncap = pl.ncap;

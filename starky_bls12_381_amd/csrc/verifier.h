@@ -28,8 +28,24 @@ struct VerifyPrelude {
 // STARKHIP_OK: the queries decide; STARKHIP_ERR_BAD_SHAPE / STARKHIP_ERR_VERIFY: the proof's result, except that with
 // check_query_words = false the words of the query section are not range-checked here, and a word >= p there must still turn a
 // VERIFY into BAD_SHAPE (the CPU verifier checks every word before it looks at any).  `out->pl` is valid unless BAD_SHAPE.
+// `ctl`: the proof is a table's of a system (verifier_system.cpp; COMPAT.md C7) -- its endpoints, the challenger after the system
+// transcript, from which the table's transcript starts without observing its trace cap again, and the CTL challenges.  Null: a proof on
+// its own, and one whose header names CTL polynomials is BAD_SHAPE.
+struct CtlTable;
+struct Challenger;
+struct CtlVerify {
+    const CtlTable* table;
+    const Challenger* initial;
+    gl_t challenges[4];
+};
 int verify_prelude(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words, bool check_query_words,
-                   VerifyPrelude* out);
+                   VerifyPrelude* out, const CtlVerify* ctl = nullptr);
+// the CPU verifier of one proof (verifier.cpp): the prelude, then the query rounds on host threads
+int verify_proof(const AirInfo& air, const starkhip_config_t& cfg, const uint64_t* proof, size_t words, const CtlVerify* ctl);
+// the system verifier (verifier_system.cpp): the system transcript replayed from the table proofs' trace caps, every table proof from the
+// copied state, every CTL's sum equation under both challenges; one verdict
+struct SystemProgram;
+int verify_system_proof(const SystemProgram& sys, const starkhip_config_t* cfgs, const uint64_t* blob, size_t words);
 
 // starkhip_verify_batch: results[i] = starkhip_verify's code for proof i; the return value describes the call
 int verify_batch_device(Ctx* c, size_t n, const starkhip_air_t* airs, const starkhip_config_t* cfgs, const uint64_t* const* proofs,
